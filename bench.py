@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- V-cycles/s and achieved HBM GB/s of the geometric-multigrid hot path.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c4|c3|c2|c1] [--mu 50]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c4|c3|c2|c1] [--mu 50] [--dump-outputs DIR]
 
 A "step" is one V(mu, mu) cycle (V_cycle_scheme, multigrid.py:231-268) of the synthetic P1
 Poisson hierarchy named by --config, device-resident from start to end (the hierarchy and the
@@ -91,7 +91,13 @@ def parse():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-odd-rows", action="store_true", help="skip the extra hierarchy with 1 %% odd rows (value_with_odd_rows)")
     ap.add_argument("--cpu-sample-level", type=int, default=4, help="finest level of the CPU sample (N = 8*2^l)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the finest level's iterate after the timed cycles to DIR/v.npy (float64, lexicographic order; "
+                         "a fixed seeded sample with its indices in DIR/v_index.npy when the whole vector exceeds 64 MB)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 class _StdoutToStderr:
@@ -279,6 +285,34 @@ def timed_cycles(h, rv, level, warmup, steps):
     return rv.max(time.perf_counter() - t0)
 
 
+DUMP_BYTES = 64 << 20          # --dump-outputs writes at most this much in all
+
+
+def output_sample(n, budget=DUMP_BYTES):
+    """Entries of an output of n float64 values that --dump-outputs writes: None (all of them) when they fit in the
+    budget, else a fixed seeded sample -- sorted, without repeats -- that fits together with its float64 index array."""
+    if 8 * n <= budget:
+        return None
+    rng = np.random.default_rng(1025)
+    return np.unique(rng.integers(0, n, size=budget // 32, dtype=np.int64))
+
+
+def dump_outputs(path, h, rv, level):
+    """--dump-outputs: what the timed cycles left in `v` on the finest level -- the solution a caller of the V-cycle
+    receives -- in the caller's lexicographic order (gathered from every slab first when the grid is split)."""
+    v = h.get_vector(level, "v", gather=rv.world > 1).ravel()
+    if rv.rank == 0:
+        os.makedirs(path, exist_ok=True)
+        idx = output_sample(v.size)
+        if idx is None:
+            np.save(os.path.join(path, "v.npy"), v)
+        else:
+            np.save(os.path.join(path, "v.npy"), v[idx])
+            np.save(os.path.join(path, "v_index.npy"), idx.astype(np.float64))
+    del v
+    rv.barrier()
+
+
 def cpu_baseline(args):
     """The oracle (a port of the reference's NumPy/SciPy V-cycle) on a bounded sample of the same
     workload: same dimension, smoother and level count rule, smaller fine grid; 1 thread, like the
@@ -378,6 +412,8 @@ def main():
     t_setup = time.perf_counter() - t_setup
 
     elapsed = timed_cycles(h, rv, hi, args.warmup, args.steps)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, h, rv, hi)
     res_after = h.vcycle(hi, 1, residuals=True)[0]          # untimed: convergence evidence
     f_norm = h.norm2(hi, "f")
 

@@ -96,3 +96,44 @@ def test_bench_with_two_ranks_starts_itself():
     assert d["n_gpus"] == 2 and d["scaling"] == "strong" and d["value"] > 0
     assert d["config"]["parallelism"].startswith("slab2")
     assert d["residual_l2_after"] < d["rhs_l2"]
+
+
+def test_dump_sample_is_fixed_and_within_the_budget():
+    """--dump-outputs writes small outputs whole and a fixed seeded sample of large ones: sorted distinct indices, the
+    same from run to run, values and float64 indices together within 64 MB."""
+    import numpy as np
+    import bench
+
+    assert bench.output_sample(4225) is None
+    assert bench.output_sample(bench.DUMP_BYTES // 8) is None
+    n = 1025 ** 3
+    idx = bench.output_sample(n)
+    assert np.array_equal(idx, bench.output_sample(n))
+    assert idx.dtype == np.int64 and idx[0] >= 0 and idx[-1] < n and np.all(np.diff(idx) > 0)
+    assert 16 * idx.size <= bench.DUMP_BYTES and idx.size > bench.DUMP_BYTES // 40
+    assert np.array_equal(idx.astype(np.float64).astype(np.int64), idx)
+
+
+@pytest.mark.gpu
+def test_bench_dumps_what_the_timed_cycles_computed(tmp_path):
+    """--dump-outputs DIR: the finest level's iterate after the warm-up and the timed V-cycles, float64, equal to the
+    same cycles run through the library directly; the JSON line is unchanged."""
+    import numpy as np
+    from multigrid_dolfinx_amd.hierarchy import DeviceHierarchy
+
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "c1", "--steps", "2", "--warmup", "1",
+                          "--kernel-reps", "2", "--no-cpu-baseline", "--dump-outputs", str(tmp_path / "dump")],
+                         capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-3000:]
+    lines = [l for l in out.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1 and json.loads(lines[0])["steps"] == 2
+    assert sorted(os.listdir(tmp_path / "dump")) == ["v.npy"]
+    got = np.load(tmp_path / "dump" / "v.npy")
+    assert got.dtype == np.float64 and got.shape == (65 * 65,) and np.all(np.isfinite(got))
+    with DeviceHierarchy.synthetic(2, 1, 3, c=8, mu1=50, mu2=50, omega=2.0 / 3.0, prune_zeros=True) as h:
+        h.zero_vector(3, "v")
+        h.vcycle(3, 1)
+        h.vcycle(3, 2)
+        want = h.get_vector(3, "v").ravel()
+    assert np.linalg.norm(want) > 0
+    assert np.linalg.norm(got - want) <= 1e-12 * np.linalg.norm(want)

@@ -68,9 +68,21 @@ def test_paired_sweeps_on_slabs_match_single_handle(world, mu, segments):
 @pytest.mark.gpu
 def test_rccl_entry_points_on_one_rank():
     """Every RCCL call the slab transport makes (unique id by value, init, all-reduce, grouped
-    broadcast, grouped send/recv, destroy), on a one-rank communicator -- all a 1-GPU box can run."""
-    from multigrid_dolfinx_amd import _capi
-    _capi.check(_capi.load().mg_comm_selftest(0))
+    broadcast, grouped send/recv, destroy), on a one-rank communicator -- all a 1-GPU box can run.
+
+    In a process of its own: torch ships its own HIP runtime and RCCL under the same sonames, so in a process that
+    loaded libmg_hip.so before importing torch (as the test session does), `librccl.so.1` is torch's copy, bound to
+    the other HIP runtime."""
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    code = ("import sys; sys.path.insert(0, %r); from multigrid_dolfinx_amd import _capi; "
+            "_capi.check(_capi.load().mg_comm_selftest(0)); print('OK')" % root)
+    env = {k: v for k, v in os.environ.items() if k != "MG_RCCL_LIBRARY"}
+    out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
+    assert "OK" in out.stdout
 
 
 @pytest.mark.gpu
