@@ -414,6 +414,33 @@ int mg_fmg_ex(mg_handle h, int top_level, int mu0, double tol, int max_cycles, i
  * V-cycles replayed from a captured hipGraph, graphs currently cached.  No reference counterpart. */
 int mg_counters(mg_handle h, int64_t* uploads, int64_t* downloads, int64_t* graph_replays, int* graphs_cached);
 
+/* Which kernels the Jacobi smoother (mg_smooth, the smoother calls of a V-cycle) ran, per level and per path.  A smoother
+ * call tries the paths in a fixed order -- MG_PATH_SMALL, MG_PATH_BLOCK, MG_PATH_K2D, MG_PATH_KSWEEP_SLAB, MG_PATH_KSWEEP /
+ * MG_PATH_KSWEEP_ESCAPE, the pair passes, one sweep at a time -- and the first one that applies takes the sweeps it can
+ * (DESIGN.md section 5 lists the size thresholds).  No reference counterpart; for tests.
+ *   launches       kernel launches of that path (a pass split into several launches counts each of them)
+ *   sweeps         Jacobi sweeps of the whole level those passes completed, each pass counted once: for mg_smooth calls
+ *                  alone the sweeps summed over all paths equal the sum of their nw
+ *   tail_launches  K-sweep launches whose planner split off a last, nearly empty round of tiles ("fuse_k_tail")
+ * Counts are taken on the host when a launch is enqueued or captured into a V-cycle graph: replays of a captured
+ * cycle add nothing (mg_counters counts those), and neither do the launches of mg_time_kernel.  Gauss-Seidel
+ * smoothers are not counted.  mg_reset_smoother_launches sets every count of every level to zero. */
+enum mg_smoother_path {
+    MG_PATH_SLICE = 0,          /* one sweep per launch, persistent slice kernels (also the boundary sweeps of slabs)       */
+    MG_PATH_SWEEP1C = 1,        /* one sweep per launch as a plane march with row classes (sdia_sweep1c, "march_min_rows")  */
+    MG_PATH_PAIR_CLASS = 2,     /* two sweeps per pass through row classes (sdia_jacobi2c, "fuse_min_rows")                */
+    MG_PATH_PAIR_PLAIN = 3,     /* two sweeps per pass on the stored rows (sdia_jacobi2p / sdia_jacobi2)                   */
+    MG_PATH_KSWEEP = 4,         /* 3..5 sweeps per pass, the K-sweep march on whole levels (sdia_jacobikc, "fuse_k")       */
+    MG_PATH_KSWEEP_ESCAPE = 5,  /* ... its variant for levels with escape rows (sdia_jacobikc_escape)                      */
+    MG_PATH_KSWEEP_SLAB = 6,    /* ... on slabs with K halo planes ("halo_depth"): edge and rest launches of one pass      */
+    MG_PATH_BLOCK = 7,          /* 2..4 sweeps per launch on blocks resident on the CU (sdia_jacobi_block, "fuse_block")   */
+    MG_PATH_K2D = 8,            /* 2..5 sweeps per launch on 2-D levels (sdia_jacobik2d, "fuse_2d")                        */
+    MG_PATH_SMALL = 9,          /* all sweeps of a call in one launch of one workgroup (sdia_jacobi_small, "fuse_small")  */
+    MG_PATH_COUNT = 10
+};
+int mg_smoother_launches(mg_handle h, int level, int path, int64_t* launches, int64_t* sweeps, int64_t* tail_launches);
+int mg_reset_smoother_launches(mg_handle h);
+
 /* ---- measurement -----------------------------------------------------------------------------
  * mg_time_kernel: average duration in milliseconds of `reps` back-to-back launches of
  * one kernel of the path on `level`, measured with HIP events on the handle's own
@@ -424,7 +451,8 @@ int mg_counters(mg_handle h, int64_t* uploads, int64_t* downloads, int64_t* grap
  * "jacobik3" = one launch of the K-sweep plane march on a 3-D level ("jacobik3!": wherever it applies), "jacobiblk" = one launch
  * of the block pass ("fuse_block"; "jacobiblk!": whatever the level's size), errors on levels that do not use them;
  * "gs" = one full Gauss-Seidel sweep, all colours, with the configured Gauss-Seidel smoother).
- * Used by bench.py for the roofline figure.  mg_sync waits for the handle's stream. */
+ * Used by bench.py for the roofline figure; its launches leave mg_smoother_launches as they were.  mg_sync waits for
+ * the handle's stream. */
 int mg_time_kernel(mg_handle h, const char* kernel, int level, int reps, double* avg_ms);
 int mg_sync(mg_handle h);
 /* bytes of device memory held by the handle */

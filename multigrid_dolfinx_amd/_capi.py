@@ -18,6 +18,9 @@ MG_VEC_V, MG_VEC_F, MG_VEC_R, MG_VEC_ERR = 0, 1, 2, 3
 MG_RESTRICT_INJECTION, MG_RESTRICT_FULL_WEIGHTING, MG_RESTRICT_TABLE = 0, 1, 2
 MG_SMOOTH_JACOBI, MG_SMOOTH_RBGS, MG_SMOOTH_MCGS = 0, 1, 2
 MG_NORM_L2, MG_NORM_MASS = 0, 1
+# enum mg_smoother_path, in its order (mg_smoother_launches)
+SMOOTHER_PATHS = ("slice", "sweep1c", "pair_class", "pair_plain", "ksweep", "ksweep_escape", "ksweep_slab", "block", "k2d",
+                  "small")
 
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double),
                           C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int64)
@@ -76,6 +79,8 @@ SIGNATURES = {
     "mg_set_exact": [_H, C.c_int, C.c_void_p],
     "mg_fmg_ex": [_H, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_void_p, _ip],
     "mg_counters": [_H, _i64p, _i64p, _i64p, _ip],
+    "mg_smoother_launches": [_H, C.c_int, C.c_int, _i64p, _i64p, _i64p],
+    "mg_reset_smoother_launches": [_H],
     "mg_time_kernel": [_H, C.c_char_p, C.c_int, C.c_int, _dp],
     "mg_sync": [_H],
     "mg_memory_bytes": [_H, _i64p],

@@ -332,6 +332,10 @@ struct mg_context {
     DVector mass_out, diff, uexact;
     int uexact_level = -1;
     int64_t uploads = 0, downloads = 0, graph_replays = 0;   // whole-vector host <-> device copies; hipGraphLaunch calls
+    // Jacobi smoother passes per level and path (mg_smoother_launches), counted when enqueued or captured
+    struct SmootherCount { int64_t launches = 0, sweeps = 0, tail = 0; };
+    std::vector<std::array<SmootherCount, MG_PATH_COUNT>> smoother_counts;
+    int jk3_tail = 0;               // the last launch of the K-sweep march split off a last round of tiles (a.ta < ntile)
     double* stage = nullptr;        // device staging for host vectors (caller numbering)
     int64_t stage_elems = 0;
     int64_t bytes = 0;
@@ -1415,6 +1419,7 @@ int launch_jacobikc_t(mg_context* c, JK3Args a, bool finest, const JK3Range& zr,
     MG_TRY(allow_large_lds(c, reinterpret_cast<const void*>(kern), lds));
     hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * WAVE), lds, c->stream, a);
     HIP_TRY(hipGetLastError());
+    c->jk3_tail = a.ta < ntile ? 1 : 0;
     return 0;
 }
 
@@ -1476,6 +1481,7 @@ int launch_jacobikc(mg_context* c, const Level& L, int K, const double* x_rows, 
     a.escape = L.cls_escape ? 1 : 0; a.dvals = L.dvals; a.mlead = L.mlead; a.sshift = L.R == 1 ? 6 : (L.R == 2 ? 7 : 8);
     const JK3Range whole{0, L.g.nk, 0, 0};
     const bool finest = c->nlev > 1 && &L == &c->L[c->nlev - 1];
+    c->jk3_tail = 0;
     switch (K) {
         case 2: return launch_jacobikc_k<2>(c, a, finest, zr ? *zr : whole, seglen);
         case 3: return launch_jacobikc_k<3>(c, a, finest, zr ? *zr : whole, seglen);
@@ -1733,6 +1739,15 @@ bool slab_ksweep_level(const mg_context* c, const Level& L) {
            min_slab_rows(L) >= std::max<int64_t>(8 * L.g.plane, c->fuse_k_slab_min_rows);
 }
 
+// mg_smoother_launches: one pass of `sweeps` Jacobi sweeps of the whole level, made of `launches` launches of `path`
+// (host-side bookkeeping when the pass is enqueued or captured)
+void count_pass(mg_context* c, int level, int path, int launches, int sweeps, int tail_launches = 0) {
+    auto& n = c->smoother_counts[(size_t)level][(size_t)path];
+    n.launches += launches;
+    n.sweeps += sweeps;
+    n.tail += tail_launches;
+}
+
 // nw Jacobi sweeps; v halos must be valid on entry and are valid on exit.
 int smooth(mg_context* c, int level, int nw) {
     Level& L = c->L[level];
@@ -1775,6 +1790,7 @@ int smooth(mg_context* c, int level, int nw) {
     const bool dist = !L.replicated && c->comm.active();
     if (!dist && nw >= 2 && small_level_ok(c, L)) {
         MG_TRY(launch_jacobi_small(c, L, nw, L.v.rows, L.f.rows, L.v2.rows));
+        count_pass(c, level, MG_PATH_SMALL, 1, nw);
         std::swap(L.v, L.v2);
         return 0;
     }
@@ -1786,6 +1802,7 @@ int smooth(mg_context* c, int level, int nw) {
             int k = std::min(plan.K, left);
             if (left - k == 1 && k > 2) --k;                // 4 = 2 + 2 rather than 3 + 1
             MG_TRY(launch_jacobi_block(c, L, k, plan.EZ, L.v.rows, L.f.rows, L.v2.rows));
+            count_pass(c, level, MG_PATH_BLOCK, 1, k);
             std::swap(L.v, L.v2);
             left -= k;
         }
@@ -1798,6 +1815,7 @@ int smooth(mg_context* c, int level, int nw) {
             int k = std::min(c->fuse_2d_k, left);
             if (left - k == 1 && k > 2) --k;                // 6 = 3 + 3 rather than 5 + 1
             MG_TRY(launch_jacobik(c, L, k, L.v.rows, L.f.rows, L.v2.rows));
+            count_pass(c, level, MG_PATH_K2D, 1, k);
             std::swap(L.v, L.v2);
             left -= k;
         }
@@ -1849,14 +1867,17 @@ int smooth(mg_context* c, int level, int nw) {
                     const int lob = lo ? e : 0, hib = hi ? e : 0;
                     const JK3Range edge{0, lob, nk - hib, nk}, rest{lob, nk - hib, 0, 0};
                     MG_TRY(launch_jacobikc(c, L, k, L.v.rows, L.f.rows, L.v2.rows, &edge, e));
+                    const int edge_tail = c->jk3_tail;
                     HIP_TRY(hipEventRecord(c->ev_boundary, c->stream));
                     HIP_TRY(hipStreamWaitEvent(c->comm_stream, c->ev_boundary, 0));
                     MG_TRY(exchange_halo(c, L, L.v2, c->comm_stream, e));
                     HIP_TRY(hipEventRecord(c->ev_halo, c->comm_stream));
                     MG_TRY(launch_jacobikc(c, L, k, L.v.rows, L.f.rows, L.v2.rows, &rest));
+                    count_pass(c, level, MG_PATH_KSWEEP_SLAB, 2, k, edge_tail + c->jk3_tail);
                     HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_halo, 0));
                 } else {
                     MG_TRY(launch_jacobikc(c, L, k, L.v.rows, L.f.rows, L.v2.rows));
+                    count_pass(c, level, MG_PATH_KSWEEP_SLAB, 1, k, c->jk3_tail);
                     MG_TRY(exchange_halo(c, L, L.v2, nullptr, e));
                 }
                 std::swap(L.v, L.v2);
@@ -1874,15 +1895,19 @@ int smooth(mg_context* c, int level, int nw) {
             int k = left >= kmax + 2 || left == kmax ? kmax : left == kmax + 1 ? kmax - 1 : left;
             if (k < 3) break;
             MG_TRY(launch_jacobikc(c, L, k, L.v.rows, L.f.rows, L.v2.rows));
+            count_pass(c, level, L.cls_escape ? MG_PATH_KSWEEP_ESCAPE : MG_PATH_KSWEEP, 1, k, c->jk3_tail);
             std::swap(L.v, L.v2);
             left -= k;
         }
         nw = left;
     }
+    const int pair_path = cls_full(L) && c->fuse_classes ? MG_PATH_PAIR_CLASS : MG_PATH_PAIR_PLAIN;
+    const int single_path = sweep1c_ok(c, L) ? MG_PATH_SWEEP1C : MG_PATH_SLICE;     // (launch_ell's choice for a whole level)
     for (int s = 0; s < nw; ++s) {
         if (fused && s + 1 < nw) {
             if (!dist) {
                 MG_TRY(launch_jacobi2(c, L, plan, 0, 1, plan.nseg, L.v.rows, L.f.rows, L.v2.rows));
+                count_pass(c, level, pair_path, 1, 2);
                 std::swap(L.v, L.v2);
                 ++s;
                 continue;
@@ -1923,6 +1948,7 @@ int smooth(mg_context* c, int level, int nw) {
                 const int rc = boundary_chain(c->stream);
                 std::swap(c->stream, c->comm_stream);
                 MG_TRY(rc);
+                count_pass(c, level, pair_path, 3, 2);                 // two launches of the pass, the boundary chain's
                 HIP_TRY(hipEventRecord(c->ev_halo, c->comm_stream));
                 HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_halo, 0));
             } else if (overlap && c->slab_pair_form != 1 && hi2 > lo2) {
@@ -1951,11 +1977,13 @@ int smooth(mg_context* c, int level, int nw) {
                 }();
                 std::swap(c->stream, c->comm_stream);
                 MG_TRY(rc);
+                count_pass(c, level, pair_path, 3, 2);                 // the pass, the first sweep of the boundary planes, the chain's
                 HIP_TRY(hipEventRecord(c->ev_halo, c->comm_stream));
                 HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_halo, 0));
             } else {
                 MG_TRY(launch_jacobi2(c, L, plan, 0, 1, plan.nseg, L.v.rows, L.f.rows, L.v2.rows, st_lo, st_hi, L.sw.rows));
                 MG_TRY(boundary_chain(c->stream));
+                count_pass(c, level, pair_path, 2, 2);                 // the pass, the boundary chain's one-sweep launch
             }
             std::swap(L.v, L.v2);
             ++s;
@@ -1963,6 +1991,7 @@ int smooth(mg_context* c, int level, int nw) {
         }
         if (!overlap) {
             MG_TRY(launch_ell(c, L, MODE_JACOBI, false, L.v.base, L.f.rows, L.v2.rows, nullptr, nullptr));
+            count_pass(c, level, single_path, 1, 1);
             std::swap(L.v, L.v2);
             MG_TRY(exchange_halo(c, L, L.v));
             continue;
@@ -1976,6 +2005,7 @@ int smooth(mg_context* c, int level, int nw) {
         HIP_TRY(hipEventRecord(c->ev_halo, c->comm_stream));
         MG_TRY(launch_ell(c, L, MODE_JACOBI, false, L.v.base, L.f.rows, L.v2.rows, nullptr, nullptr, nullptr, lo_end,
                           hi_begin - lo_end));
+        count_pass(c, level, MG_PATH_SLICE, 2, 1);                   // boundary slices, interior slices
         HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_halo, 0));
         std::swap(L.v, L.v2);
     }
@@ -2892,6 +2922,7 @@ int mg_create(int n_levels, int dim, int device, mg_handle* out) {
     c->nlev = n_levels;
     c->device = device;
     c->L.resize(n_levels);
+    c->smoother_counts.resize(n_levels);
     HIP_TRY(hipGetDeviceProperties(&c->prop, device));
     HIP_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
     {
@@ -3971,6 +4002,22 @@ int mg_counters(mg_handle c, int64_t* uploads, int64_t* downloads, int64_t* grap
     return 0;
 }
 
+int mg_smoother_launches(mg_handle c, int level, int path, int64_t* launches, int64_t* sweeps, int64_t* tail_launches) {
+    MG_TRY(check_level(c, level, false));
+    if (path < 0 || path >= MG_PATH_COUNT) return fail("smoother path " + std::to_string(path) + " out of range");
+    const auto& n = c->smoother_counts[(size_t)level][(size_t)path];
+    if (launches) *launches = n.launches;
+    if (sweeps) *sweeps = n.sweeps;
+    if (tail_launches) *tail_launches = n.tail;
+    return 0;
+}
+
+int mg_reset_smoother_launches(mg_handle c) {
+    if (!c) return fail("null handle");
+    for (auto& level : c->smoother_counts) level.fill({});
+    return 0;
+}
+
 int mg_prepare_cycle(mg_handle c, int level) {
     MG_TRY(check_level(c, level));
     for (int l = 0; l <= level; ++l) {
@@ -4111,10 +4158,18 @@ int mg_time_kernel(mg_handle c, const char* kernel, int level, int reps, double*
         if (k == "norm2") return dot_device(c, L, L.v.rows, L.v.rows, 1);
         return fail("unknown kernel " + k);
     };
-    MG_TRY(once());   // warm-up
-    HIP_TRY(hipEventRecord(e0, c->stream));
-    for (int r = 0; r < reps; ++r) MG_TRY(once());
-    HIP_TRY(hipEventRecord(e1, c->stream));
+    // (its launches are not the smoother's: mg_smoother_launches stays as it was, "gs" included)
+    const auto counts = c->smoother_counts;
+    auto timed = [&]() -> int {
+        MG_TRY(once());   // warm-up
+        HIP_TRY(hipEventRecord(e0, c->stream));
+        for (int r = 0; r < reps; ++r) MG_TRY(once());
+        HIP_TRY(hipEventRecord(e1, c->stream));
+        return 0;
+    };
+    const int rc = timed();
+    c->smoother_counts = counts;
+    MG_TRY(rc);
     HIP_TRY(hipEventSynchronize(e1));
     float ms = 0.f;
     HIP_TRY(hipEventElapsedTime(&ms, e0, e1));

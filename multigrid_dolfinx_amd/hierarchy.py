@@ -474,6 +474,20 @@ class DeviceHierarchy:
         return {"uploads": int(up.value), "downloads": int(down.value), "graph_replays": int(rep.value),
                 "graphs_cached": int(cached.value)}
 
+    def smoother_launches(self, level: int) -> dict:
+        """What the Jacobi smoother ran on `level` since the handle was made or last reset (`mg_smoother_launches`):
+        {path: (launches, sweeps, tail_launches)} for the paths that ran, path names as in `_capi.SMOOTHER_PATHS`."""
+        out = {}
+        for i, name in enumerate(_capi.SMOOTHER_PATHS):
+            n, s, t = C.c_int64(), C.c_int64(), C.c_int64()
+            check(self._lib.mg_smoother_launches(self._h, self._idx(level), i, C.byref(n), C.byref(s), C.byref(t)))
+            if n.value or s.value or t.value:
+                out[name] = (int(n.value), int(s.value), int(t.value))
+        return out
+
+    def reset_smoother_launches(self):
+        check(self._lib.mg_reset_smoother_launches(self._h))
+
     def set_level_grid(self, level: int, grid_index=None):
         """Geometry + numbering only (transfer operators without a matrix)."""
         n = self.n_dofs(level)

@@ -102,14 +102,15 @@ def gpu_slab_worker(rank, world, port, dim, lo, hi, c, mu, replicate_below, mode
                 h.set_params(mu, mu, bag.omega)
                 h.set_vector(hi, "f", f)
         info = par.level_info(hi)
-        if "fuse_min_rows" in tuning:           # the smoother really pairs sweeps on this slab
-            assert par.time_kernel("jacobi2", hi, 1) > 0.0
         assert not info["replicated"] and par.level_info(lo)["replicated"]
         assert info["n_local"] < info["n_global"]
         for h in (par, ser):
             h.zero_vector(hi, "v")
         rp = par.vcycle(hi, 2, residuals=True)
         rs = ser.vcycle(hi, 2, residuals=True)
+        if "fuse_min_rows" in tuning:           # the smoother really pairs sweeps on this slab (K per pass with "halo_depth")
+            ran = par.smoother_launches(hi)
+            assert ran.get("ksweep_slab" if tuning.get("halo_depth", 0) >= 2 else "pair_class", (0, 0, 0))[1] > 0, ran
         got = par.get_vector(hi, "v", gather=True)
         want = ser.get_vector(hi, "v")
         assert np.array_equal(got, want), float(np.abs(got - want).max())

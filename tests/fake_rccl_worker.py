@@ -47,7 +47,9 @@ def main(world, dim, lo, hi, c, mu, replicate_below, overlap):
                 # the K-sweep march really runs on this slab (its class halos get built at the first smoother call)
                 h.zero_vector(hi, "v")
                 h.smooth(hi, mu)
-                assert h.time_kernel("jacobik3", hi, 1) > 0
+                # (fuse_k_slab_min_sweeps 2: every pass of the call, the last pair included)
+                ran = h.smoother_launches(hi)
+                assert set(ran) == {"ksweep_slab"} and ran["ksweep_slab"][1] == mu, ran
             h.prepare_cycle(hi)
             phase(h)
             h.zero_vector(hi, "v")

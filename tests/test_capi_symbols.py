@@ -59,3 +59,21 @@ def test_every_tuning_key_is_documented_in_the_header():
     block = header[header.index("Tuning and format knobs"):header.index("int mg_set_tuning")]
     documented = set(re.findall(r'^\s*\*\s+"([a-z_0-9]+)"', block, flags=re.M))
     assert accepted and accepted == documented, (sorted(accepted - documented), sorted(documented - accepted))
+
+
+def test_smoother_path_names_match_the_header():
+    """`mg_smoother_launches` takes a path as an index of `enum mg_smoother_path`: the Python names must be that enum's
+    entries, in its order, with the values the header gives them, and MG_PATH_COUNT one past the last."""
+    header = open(os.path.join(ROOT, "include", "mg_hip.h")).read()
+    block = header[header.index("enum mg_smoother_path"):]
+    block = re.sub(r"/\*.*?\*/", "", block[:block.index("};")], flags=re.S)
+    entries = re.findall(r"\bMG_PATH_([A-Z0-9_]+)\s*=\s*(\d+)", block)
+    names = [n.lower() for n, _ in entries if n != "COUNT"]
+    assert names == list(_capi.SMOOTHER_PATHS)
+    assert [int(v) for _, v in entries] == list(range(len(entries)))
+    assert entries[-1][0] == "COUNT"
+    # every path is one the smoother counts
+    src = open(os.path.join(ROOT, "multigrid_dolfinx_amd", "csrc", "mg_capi.hip")).read()
+    body = src[src.index("int smooth(mg_context* c, int level, int nw)"):src.index("\nint residual(mg_context* c, int level)")]
+    counted = set(re.findall(r"MG_PATH_([A-Z0-9_]+)", body))
+    assert counted == {n.upper() for n in _capi.SMOOTHER_PATHS}, counted

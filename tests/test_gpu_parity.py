@@ -473,6 +473,51 @@ def test_headline_size_checksums_agree_between_formats():
         assert np.all(np.abs(norms[0] - other) <= 1e-12 * other)
 
 
+def _fingerprint(v, chunk=1 << 24):
+    """An exact fingerprint of a vector too large to keep two of on the host: per chunk of 2^24 entries the XOR and the
+    (wrapping) sum of their bit patterns -- a difference in any one bit changes its chunk's XOR --, and a seeded sample."""
+    u = np.ascontiguousarray(v).reshape(-1).view(np.uint64)
+    xors = np.array([np.bitwise_xor.reduce(u[i:i + chunk]) for i in range(0, u.size, chunk)], dtype=np.uint64)
+    sums = np.array([u[i:i + chunk].sum(dtype=np.uint64) for i in range(0, u.size, chunk)], dtype=np.uint64)
+    sample = u[np.random.default_rng(7).integers(0, u.size, 4096)].copy()
+    return xors, sums, sample
+
+
+def test_headline_size_march_is_bit_identical_to_single_sweeps():
+    """BASELINE config C4's hierarchy (1025^3 unknowns, 6 levels, one GPU) with V(7,7): the default passes -- the five-sweep
+    K-sweep march with its tail of short segments (817 tiles of 64 x 32 on 1025^2 planes: 768 in full-length segments, 49
+    cut shorter; 220 tiles, 170 + 50, on 513^2) and a pair after it, 7 = 4 + 3 on 257^3, the block pass on 129^3 and 65^3
+    -- against one sweep per launch on every level.  The same arithmetic in the same order: the residual norms are equal
+    and the finest iterate is bit-identical (compared through an exact fingerprint: one 8.6 GB vector on the host at a
+    time).  This is the one test of the march at the size with 64-bit byte offsets.  The launch counts are those of the
+    fresh handle's first cycle, counted when it is captured."""
+    from multigrid_dolfinx_amd.hierarchy import DeviceHierarchy
+    norms, prints, counts = [], [], []
+    for kw in (dict(), dict(fuse_k=0, fuse_sweeps=0, fuse_block=0, fuse_small=0)):
+        with DeviceHierarchy.synthetic(3, 2, 7, c=8, mu1=7, mu2=7, **kw) as dev:
+            f_norm = dev.norm2(7, "f")
+            dev.zero_vector(7, "v")
+            res = dev.vcycle(7, 1, residuals=True)
+            counts.append({level: dev.smoother_launches(level) for level in range(3, 8)})
+            v = dev.get_vector(7, "v")
+        norms.append((f_norm, float(res[0])))
+        prints.append(_fingerprint(v))
+        del v
+    fused, single = counts
+    for level in (7, 6):                                 # two smoother calls of 5 + a pair
+        assert set(fused[level]) == {"ksweep", "pair_class"}, fused[level]
+        assert fused[level]["ksweep"][:2] == (2, 10) and fused[level]["ksweep"][2] > 0, fused[level]
+        assert fused[level]["pair_class"] == (2, 4, 0), fused[level]
+    assert fused[5] == {"ksweep": (4, 14, 0)}, fused[5]  # 4 + 3, twice
+    for level in (4, 3):
+        assert set(fused[level]) == {"block"} and fused[level]["block"][1] == 14, fused[level]
+    for level in range(3, 8):
+        assert set(single[level]) <= {"slice", "sweep1c"} and sum(s for _, s, _ in single[level].values()) == 14, single[level]
+    assert norms[0] == norms[1], norms
+    for a, b in zip(prints[0], prints[1]):
+        assert np.array_equal(a, b)
+
+
 @pytest.mark.parametrize("dim,lo,hi,c,seed", [(2, 1, 3, 8, 4), (3, 1, 3, 2, None), (3, 1, 3, 4, 6)])
 def test_red_black_gauss_seidel_matches_oracle(dim, lo, hi, c, seed):
     """BASELINE config 5's smoother (no reference implementation: parity unpinned, oracle only)."""
@@ -656,25 +701,40 @@ def _n128_oracle():
 
 
 _SMALL = dict(fuse_min_rows=0, march_min_rows=0, fuse_k_min_rows=0, fuse_k4_min_rows=0, fuse_k5_min_rows=0)
+# (the block pass takes every level of 2^15 .. 2^23 rows by default, 129^3 and 65^3 included: off wherever another kernel is meant)
+_MARCH = dict(_SMALL, fuse_block=0)
 
 
-@pytest.mark.parametrize("tuning", [dict(), dict(_SMALL), dict(_SMALL, fuse_k=0), dict(_SMALL, fuse_k=3, fuse_k_shape=0),
-                                    dict(_SMALL, fuse_k=5, fuse_k_shape=4), dict(_SMALL, fuse_classes=0, class_sweeps=0)])
-def test_3d_n128_reference_parameters_match_oracle(tuning):
+# tuning, what the smoother runs on the 129^3 level in one V(50,50) cycle: {path: (launches, sweeps)}
+@pytest.mark.parametrize("tuning,ran", [
+    (dict(), {"block": (34, 100)}),                                             # 50 = 16 x 3 + 2 per call
+    (dict(_MARCH), {"ksweep": (20, 100)}),                                      # five sweeps per pass (< fuse_k_small_rows)
+    (dict(_MARCH, fuse_k=0), {"pair_class": (50, 100)}),
+    (dict(_MARCH, fuse_k=3, fuse_k_shape=0), {"ksweep": (32, 96), "pair_class": (2, 4)}),       # 50 = 16 x 3 + a pair
+    (dict(_MARCH, fuse_k=5, fuse_k_shape=4), {"ksweep": (20, 100)}),
+    (dict(_MARCH, fuse_classes=0, class_sweeps=0), {"pair_plain": (50, 100)}),
+    (dict(_MARCH, fuse_k=4), {"ksweep": (24, 96), "pair_class": (2, 4)}),       # 50 = 12 x 4 + a pair
+    (dict(_MARCH, fuse_k=3), {"ksweep": (32, 96), "pair_class": (2, 4)}),
+    (dict(_MARCH, fuse_k_tail=4), {"ksweep": (20, 100)}),                       # planned for 4 resident workgroups: a tail
+    (dict(_MARCH, fuse_sweeps=0), {"sweep1c": (100, 100)})], ids=[f"tuning{i}" for i in range(10)])
+def test_3d_n128_reference_parameters_match_oracle(tuning, ran):
     """The largest 3-D oracle comparison that fits a test budget: 129^3 unknowns, 3 levels (coarsest 33^3 =
     BASELINE's coarsest grid), the reference's V(50,50), omega = 2/3.  3-D is parity-unpinned (no reference);
-    this pins the HIP path to the CPU restatement at the north-star tolerance.  With the size thresholds at zero the
-    kernels that the headline sizes run -- the K-sweep march `sdia_jacobikc`, the two-sweep passes `sdia_jacobi2c` /
-    `sdia_jacobi2p`, the one-sweep march `sdia_sweep1c` -- face the oracle themselves, not only the slice kernels they
-    are bit-identical to (default thresholds: 129^3 rows stay below them)."""
+    this pins the HIP path to the CPU restatement at the north-star tolerance.  With the size thresholds at zero and the
+    block pass off, the kernels that the headline sizes run -- the K-sweep march `sdia_jacobikc` with three, four and five
+    sweeps per pass and with a tail of short segments, the two-sweep passes `sdia_jacobi2c` / `sdia_jacobi2p`, the
+    one-sweep march `sdia_sweep1c` -- face the oracle themselves; the defaults run the block pass `sdia_jacobi_block`.
+    The smoother's launch counts say that each variant ran the kernel it is meant to, and nothing else, on 129^3."""
     from multigrid_dolfinx_amd.hierarchy import DeviceHierarchy
     want, res_want = _n128_oracle()
     with DeviceHierarchy.synthetic(3, 2, 4, c=8, mu1=50, mu2=50, **tuning) as dev:
-        if tuning:
-            assert dev.time_kernel("jacobi2", 4, 1) > 0             # the smoother does run the march kernels on this level
         dev.zero_vector(4, "v")
         res = dev.vcycle(4, 1, residuals=True)
         got = dev.get_vector(4, "v")
+        counts = dev.smoother_launches(4)
+    assert {p: (n, s) for p, (n, s, _) in counts.items()} == ran, counts
+    tails = {p: t for p, (_, _, t) in counts.items() if t}
+    assert tails == ({"ksweep": 20} if tuning.get("fuse_k_tail") else {}), counts
     assert rel_l2(got, want) <= TOL_ITER
     assert abs(res[0] - res_want) <= TOL_ITER * res_want
 
@@ -1210,17 +1270,43 @@ def test_adhoc_contexts_are_bounded(mg):
     assert len(mg._adhoc) == 0 and len(mg._grid_cache) == 0
 
 
+def _fits_one_cu(dim, n_side):
+    """small_level_ok's size test: at most 16384 rows, and x, the result and the class table in 150 KiB of LDS"""
+    rows, pad = n_side ** dim, n_side ** (dim - 1)
+    return rows <= 16384 and 256 * 8 * 8 + 2 * (rows + 2 * pad) * 8 <= 150 * 1024
+
+
+def _paths_3d(kw, n_side, nw):
+    """The smoother paths a variant of the bit-identity tests may take on a whole 3-D Poisson level with n_side^3 rows
+    (the size thresholds all at zero), and the one among them that must run (None: any of them)."""
+    small = kw.get("fuse_small", 1) and _fits_one_cu(3, n_side)
+    single = {"slice", "sweep1c"}
+    if nw >= 2 and small and kw.get("fuse_classes", 1) and kw.get("row_classes", 1):
+        return {"small"}, "small"
+    if kw.get("fuse_block", 0) >= 2 and nw >= 2:
+        return {"block"} | single, "block"
+    if n_side < 32 or not kw.get("fuse_sweeps", 1) or nw < 2:                 # (the pair and K-sweep passes: 32 x 32 planes)
+        return single, None
+    pair = "pair_class" if kw.get("fuse_classes", 1) and kw.get("row_classes", 1) else "pair_plain"
+    if pair == "pair_class" and kw.get("fuse_k", 5) >= 3 and nw >= 3 and not (kw.get("fuse_k", 5) == 3 and nw == 4):
+        return {"ksweep", pair}, "ksweep"                                       # (three sweeps per pass at most: 4 = 2 + 2)
+    return {pair} | single, pair
+
+
 @pytest.mark.parametrize("c,lo,hi", [(8, 2, 4), (5, 1, 3), (7, 1, 4)])
 def test_two_sweep_kernel_is_bit_identical_to_single_sweeps(c, lo, hi):
     """mg_jacobi2.hip.h: two Jacobi sweeps per pass over the matrix (tile + plane march, intermediate iterate in
     LDS / registers) must reproduce two launches of the one-sweep kernel bit for bit -- for every tile shape,
-    plane segmentation, odd sweep count and grid size that is not a multiple of the tile."""
+    plane segmentation, odd sweep count and grid size that is not a multiple of the tile.  The reference runs one sweep
+    per launch; every other variant runs with the block pass off (but the ones that are about it), and the smoother's
+    launch counts say that each level took the pass the variant is about."""
     from multigrid_dolfinx_amd.hierarchy import DeviceHierarchy
     rng = np.random.default_rng(c)
     want = {}
     # (fuse_k=0: pairs of sweeps only, the two-sweep pass; fuse_k=3..5: the K-sweep march of mg_jacobik3d.hip.h in its
     #  three tile shapes, with and without the DPP neighbour exchange, with one / several plane segments)
-    variants = [dict(fuse_sweeps=0, fuse_small=0), dict(), dict(fuse_sweeps=0), dict(fuse_k=0), dict(fuse_k=0, fuse_segments=1),
+    reference = dict(fuse_sweeps=0, fuse_small=0, fuse_block=0, fuse_k=0)
+    variants = [reference, dict(), dict(fuse_sweeps=0), dict(fuse_k=0), dict(fuse_k=0, fuse_segments=1),
                 dict(fuse_k=0, fuse_segments=3), dict(fuse_classes=0), dict(fuse_classes=0, fuse_plain_shape=1),
                 dict(fuse_classes=0, fuse_plain_shape=2, fuse_segments=3),
                 dict(fuse_classes=0, fuse_plain=1), dict(fuse_k=0, fuse_shape=0), dict(fuse_k=0, fuse_shape=3),
@@ -1243,6 +1329,8 @@ def test_two_sweep_kernel_is_bit_identical_to_single_sweeps(c, lo, hi):
                 dict(fuse_block=2, fuse_block_k=4, fuse_block_ez=11), dict(fuse_block=2, fuse_block_k=2, fuse_block_ez=19),
                 dict(fuse_block=2, fuse_block_k=3, fuse_block_ez=19), dict(fuse_block=2, fuse_block_k=4, fuse_block_ez=19)]
     for kw in variants:
+        if "fuse_block" not in kw:
+            kw = dict(kw, fuse_block=0)
         tune = {k: v for k, v in kw.items() if k.startswith("fuse_")}
         make = {k: v for k, v in kw.items() if not k.startswith("fuse_")}
         classes = make.get("row_classes", 1)
@@ -1263,9 +1351,14 @@ def test_two_sweep_kernel_is_bit_identical_to_single_sweeps(c, lo, hi):
                 for nw in (2, 3, 4, 5, 6, 9):
                     dev.set_vector(level, "v", want[level, "v"])
                     dev.set_vector(level, "f", want[level, "f"])
+                    dev.reset_smoother_launches()
                     dev.smooth(level, nw)
                     got = dev.get_vector(level, "v")
-                    if kw == variants[0]:
+                    ran = dev.smoother_launches(level)
+                    allowed, must = ({"slice", "sweep1c"}, None) if kw is variants[0] else _paths_3d(kw, dev.elements(level) + 1, nw)
+                    assert sum(s for _, s, _ in ran.values()) == nw, (kw, level, nw, ran)
+                    assert set(ran) <= allowed and (must is None or must in ran), (kw, level, nw, ran)
+                    if kw is variants[0]:
                         want[level, nw] = got
                     else:
                         assert np.array_equal(got, want[level, nw]), (kw, level, nw)
@@ -1273,7 +1366,7 @@ def test_two_sweep_kernel_is_bit_identical_to_single_sweeps(c, lo, hi):
             dev.set_params(3, 5, 2.0 / 3.0)
             dev.zero_vector(hi, "v")
             res = dev.vcycle(hi, 3, residuals=True)
-            if kw == variants[0]:
+            if kw is variants[0]:
                 want["res"] = res
             else:
                 assert np.all(np.abs(res - want["res"]) <= 1e-13 * want["res"]), kw
@@ -1374,14 +1467,22 @@ def test_escape_rows_keep_the_class_path(case):
                     # (the odd rows -- but for any that were picked for the dictionary's spare classes -- and the few regular rows
                     #  that the dictionary's sample met only once: rows next to a corner of the grid)
                     assert int(odd.sum()) - 254 <= st["escape_rows"] <= int(odd.sum()) + 64
-                assert dev.time_kernel("jacobik3", 3, 1) > 0.0                  # the march runs on this level
             else:
                 assert info["row_classes"] == 0 and st["escape_rows"] == 0, (info, st)
             for nw in (3, 4, 5, 7, 12):
                 dev.set_vector(3, "v", v_in)
                 dev.set_vector(3, "f", f_in)
+                dev.reset_smoother_launches()
                 dev.smooth(3, nw)
                 outs[escape, nw] = dev.get_vector(3, "v")
+                # the escape variant of the march runs on this level (and at most two single sweeps beside it: 12 = 5 + 5 + 2);
+                # the comparison: single sweeps on the stored rows
+                ran = dev.smoother_launches(3)
+                assert sum(s for _, s, _ in ran.values()) == nw, ran
+                if escape and case != "patch16":
+                    assert "ksweep_escape" in ran and set(ran) <= {"ksweep_escape", "slice"}, ran
+                else:
+                    assert set(ran) == {"slice"}, ran
             dev.set_vector(3, "f", bag.b_dict[3])
             dev.zero_vector(3, "v")
             outs[escape, "res"] = dev.vcycle(3, 3, residuals=True)
@@ -1400,8 +1501,9 @@ def test_k_sweep_kernel_on_2d_levels_is_bit_identical_to_single_sweeps(c, lo, hi
     from multigrid_dolfinx_amd.hierarchy import DeviceHierarchy
     rng = np.random.default_rng(c)
     want = {}
+    reference = dict(fuse_2d=0, fuse_small=0)                                   # one sweep per launch
     # (fuse_2d_lines: regions of 64 / 32 / 16 lines -- eight, four, two cells per thread; 0, the default: chosen per level)
-    for kw in (dict(fuse_2d=0, fuse_small=0), dict(), dict(fuse_small=0), dict(fuse_small=0, fuse_2d_k=2), dict(fuse_2d_k=3),
+    for kw in (reference, dict(), dict(fuse_small=0), dict(fuse_small=0, fuse_2d_k=2), dict(fuse_2d_k=3),
                dict(fuse_small=0, fuse_2d_k=4), dict(rows_per_lane=1), dict(fuse_small=0, fuse_2d_lines=64),
                dict(fuse_small=0, fuse_2d_lines=32, fuse_2d_k=4), dict(fuse_small=0, fuse_2d_lines=16),
                dict(fuse_small=0, fuse_2d_lines=16, fuse_2d_k=3),
@@ -1419,21 +1521,28 @@ def test_k_sweep_kernel_on_2d_levels_is_bit_identical_to_single_sweeps(c, lo, hi
                 if (level, "v") not in want:
                     want[level, "v"] = rng.standard_normal(n)
                     want[level, "f"] = rng.standard_normal(n)
+                # (the one-launch smoother where it fits one CU and the level is not one of the 2-D kernel's -- more than
+                #  "fuse_small_2d_rows" rows --, the 2-D kernel elsewhere; the reference: single sweeps only)
+                small = kw.get("fuse_small", 1) and _fits_one_cu(2, dev.elements(level) + 1) and (
+                    n <= kw.get("fuse_small_2d_rows", 2048) or not kw.get("fuse_2d", 1))
+                must = "small" if small else "k2d" if kw.get("fuse_2d", 1) else "slice"
                 for nw in (2, 3, 5, 6, 7, 11):
                     dev.set_vector(level, "v", want[level, "v"])
                     dev.set_vector(level, "f", want[level, "f"])
+                    dev.reset_smoother_launches()
                     dev.smooth(level, nw)
                     got = dev.get_vector(level, "v")
-                    if not kw:
-                        assert dev.time_kernel("jacobik", level, 1) > 0.0
-                    if kw == dict(fuse_2d=0, fuse_small=0):
+                    ran = dev.smoother_launches(level)
+                    assert sum(s for _, s, _ in ran.values()) == nw, (kw, level, nw, ran)
+                    assert must in ran and set(ran) <= {must, "slice"}, (kw, level, nw, ran)
+                    if kw == reference:
                         want[level, nw] = got
                     else:
                         assert np.array_equal(got, want[level, nw]), (kw, level, nw)
             dev.set_params(50, 49, 2.0 / 3.0)
             dev.zero_vector(hi, "v")
             res = dev.vcycle(hi, 3, residuals=True)
-            if kw == dict(fuse_2d=0, fuse_small=0):
+            if kw == reference:
                 want["res"] = res
             else:
                 assert np.all(np.abs(res - want["res"]) <= 1e-13 * want["res"]), kw
@@ -1460,6 +1569,7 @@ def test_storage_ulps_brings_round_off_noisy_assemblies_to_the_compact_formats()
         kw = dict(storage_auto=0) if ulps == 0 else dict(storage_ulps=ulps) if ulps == 8 else {}
         with DeviceHierarchy(3, 1, 3, c=5, **kw) as dev:
             dev.set_tuning("fuse_min_rows", 0)
+            dev.set_tuning("fuse_block", 0)                                         # (41^3 rows: the block pass's otherwise)
             for l in (1, 2):
                 dev.set_level(l, bag.A_sp_dict[l][0], bag.levels[l].grid_index)
             dev.set_level(3, A, bag.levels[3].grid_index)
@@ -1472,7 +1582,6 @@ def test_storage_ulps_brings_round_off_noisy_assemblies_to_the_compact_formats()
                 assert st["symmetric"] == 0 and st["first_asymmetric_row"] >= 0 and 1 <= st["max_pair_ulps"] <= 4 and st["ulps_used"] == 0, st
             else:
                 assert info["symmetric_diagonals"] == 4 and 2 <= info["row_classes"] <= 255, info
-                assert dev.time_kernel("jacobi2", 3, 1) > 0.0
                 assert st["symmetric"] == 2 and st["ulps_used"] == (8 if ulps == 8 else 4) and 2 <= st["distinct_rows"] <= 255, st
             # (an exactly symmetric, repetitive level: nothing identified -- unless "storage_ulps" asks for the tolerance everywhere)
             assert dev.level_storage(2) == dict(symmetric=1, first_asymmetric_row=-1, max_pair_ulps=0, ulps_used=8 if ulps == 8 else 0,
@@ -1481,6 +1590,8 @@ def test_storage_ulps_brings_round_off_noisy_assemblies_to_the_compact_formats()
             dev.set_vector(3, "f", bag.b_dict[3])
             dev.smooth(3, 6)
             sm = dev.get_vector(3, "v")
+            # the compact formats take the paired pass, the offset-coded level single sweeps
+            assert dev.smoother_launches(3) == ({"slice": (6, 6, 0)} if ulps == 0 else {"pair_class": (3, 6, 0)})
             dev.zero_vector(3, "v")
             res = dev.vcycle(3, 3, residuals=True)
             outs[ulps] = (sm, res, dev.get_vector(3, "v"))
@@ -1488,6 +1599,140 @@ def test_storage_ulps_brings_round_off_noisy_assemblies_to_the_compact_formats()
         assert rel_l2(outs[k][0], outs[0][0]) <= 1e-13
         assert np.all(np.abs(outs[k][1] - outs[0][1]) <= 1e-11 * outs[0][1])
         assert rel_l2(outs[k][2], outs[0][2]) <= 1e-12
+
+
+# mg_set_tuning defaults of the smoother's path selection (mg_hip.h)
+_PATH_DEFAULTS = dict(fuse_small=1, fuse_block=1, fuse_block_min_rows=1 << 15, fuse_block_max_rows=1 << 23, fuse_block_k=0,
+                      fuse_2d=1, fuse_2d_k=5, fuse_small_2d_rows=2048, fuse_k=5, fuse_k_min_rows=1 << 24, fuse_k4_min_rows=0,
+                      fuse_k_small_rows=1 << 22, fuse_k5_min_rows=1 << 26, fuse_sweeps=1, fuse_min_rows=1 << 24,
+                      march_min_rows=1 << 22, fuse_classes=1)
+
+
+def _smoother_plan(dim, m, nw, kw, cus):
+    """What one mg_smooth(level, nw) launches on a whole Poisson level of m^dim rows with row classes, by the documented
+    rules (mg_hip.h): {path: (launches, sweeps)}.  The paths in the order they are tried, each taking
+    what it can: all sweeps in one launch on a level that fits one CU; the block pass on 3-D levels of
+    fuse_block_min_rows <= rows < fuse_block_max_rows (K = fuse_block_k, or four where the blocks then all run at once,
+    else three; 4 = 2 + 2, not 3 + 1); the 2-D kernel (6 = 3 + 3, not 5 + 1); the K-sweep march on levels of at least
+    fuse_k_min_rows with K = 3 below fuse_k4_min_rows, 5 below fuse_k_small_rows, 4 below fuse_k5_min_rows, else 5
+    (7 = 4 + 3 and 6 = 4 + a pair: no single sweep over); pairs on levels of at least fuse_min_rows; single sweeps,
+    as the one-sweep march on levels of at least march_min_rows.  The plane marches need 32 x 32 planes."""
+    t = dict(_PATH_DEFAULTS, **kw)
+    rows, cls = m ** dim, t["fuse_classes"]
+    out = {}
+
+    def run(path, k):
+        n, s = out.get(path, (0, 0))
+        out[path] = (n + 1, s + k)
+
+    def up_to(kmax, left, path):
+        while left >= 2:
+            k = min(kmax, left)
+            if left - k == 1 and k > 2:
+                k -= 1
+            run(path, k)
+            left -= k
+        return left
+
+    if nw >= 2 and t["fuse_small"] and cls and _fits_one_cu(dim, m) and (
+            dim == 3 or rows <= t["fuse_small_2d_rows"] or not t["fuse_2d"]):
+        run("small", nw)
+        return out
+    if dim == 3 and nw >= 2 and cls and t["fuse_block"] and (
+            t["fuse_block"] >= 2 or t["fuse_block_min_rows"] <= rows < t["fuse_block_max_rows"]):
+        blocks4 = (-(-m // 24)) ** 2 * -(-m // 3)                   # blocks of 32 x 32 x 11 cells keeping 24 x 24 x 3
+        nw = up_to(t["fuse_block_k"] or (4 if blocks4 <= cus else 3), nw, "block")
+    if dim == 2 and cls and t["fuse_2d"]:
+        nw = up_to(t["fuse_2d_k"], nw, "k2d")
+    planes = dim == 3 and m >= 32
+    if planes and nw >= 3 and cls and t["fuse_sweeps"] and t["fuse_k"] >= 3 and rows >= t["fuse_k_min_rows"]:
+        kmax = min(t["fuse_k"], 5, 3 if rows < t["fuse_k4_min_rows"] else 5 if rows < t["fuse_k_small_rows"]
+                   else 4 if rows < t["fuse_k5_min_rows"] else 5)
+        while nw >= 3:
+            k = kmax if nw >= kmax + 2 or nw == kmax else kmax - 1 if nw == kmax + 1 else nw
+            if k < 3:
+                break
+            run("ksweep", k)
+            nw -= k
+    pairs = planes and t["fuse_sweeps"] and rows >= t["fuse_min_rows"]
+    while nw:
+        if pairs and nw >= 2:
+            run("pair_class" if cls else "pair_plain", 2)
+            nw -= 2
+        else:
+            run("sweep1c" if planes and rows >= t["march_min_rows"] else "slice", 1)
+            nw -= 1
+    return out
+
+
+_R33 = 33 ** 3              # the middle level of both tables: thresholds at its row count and at one more
+_PATH_TABLE = {
+    3: [dict(),                                                                             # small 17^3, block 33^3 / 65^3
+        dict(fuse_small=0, fuse_block_min_rows=17 ** 3), dict(fuse_small=0, fuse_block_min_rows=17 ** 3 + 1),
+        dict(fuse_block_min_rows=_R33), dict(fuse_block_min_rows=_R33 + 1),
+        dict(fuse_small=0, fuse_block_min_rows=0, fuse_block_max_rows=_R33), dict(fuse_block_max_rows=_R33 + 1),
+        dict(fuse_block=2, fuse_small=0, fuse_block_k=3), dict(fuse_block=2, fuse_block_k=2),
+        dict(fuse_block=0, fuse_k_min_rows=_R33), dict(fuse_block=0, fuse_k_min_rows=_R33 + 1),
+        dict(fuse_block=0, fuse_k_min_rows=0, fuse_k4_min_rows=_R33 + 1),                   # three sweeps per pass
+        dict(fuse_block=0, fuse_k_min_rows=0, fuse_k4_min_rows=_R33, fuse_k_small_rows=_R33 + 1),
+        dict(fuse_block=0, fuse_k_min_rows=0, fuse_k_small_rows=_R33, fuse_k5_min_rows=_R33 + 1),
+        dict(fuse_block=0, fuse_k_min_rows=0, fuse_k_small_rows=_R33, fuse_k5_min_rows=_R33),
+        dict(fuse_block=0, fuse_min_rows=_R33), dict(fuse_block=0, fuse_min_rows=_R33 + 1),
+        dict(fuse_block=0, fuse_k_min_rows=0, fuse_min_rows=0, fuse_k=4),                   # 7 = 4 + 3, 6 = 4 + a pair
+        dict(fuse_block=0, fuse_k_min_rows=0, fuse_min_rows=0, fuse_k=3),
+        dict(fuse_block=0, march_min_rows=_R33), dict(fuse_block=0, march_min_rows=_R33 + 1),
+        dict(fuse_block_min_rows=0, fuse_k_min_rows=0, fuse_min_rows=0, march_min_rows=0),  # everything on: what comes first
+        dict(fuse_small=0, fuse_block=0, fuse_k_min_rows=0, fuse_min_rows=0, march_min_rows=0),
+        dict(fuse_block=0, fuse_classes=0, fuse_k_min_rows=0, fuse_min_rows=0)],            # no classes: plain pairs
+    2: [dict(),                                                                             # small 33^2, the 2-D kernel above
+        dict(fuse_small_2d_rows=65 ** 2), dict(fuse_small_2d_rows=65 ** 2 - 1), dict(fuse_small_2d_rows=_R33),
+        dict(fuse_small=0), dict(fuse_small=0, fuse_2d_k=2), dict(fuse_2d_k=3), dict(fuse_small=0, fuse_2d_k=4),
+        dict(fuse_2d=0),                                                                    # 65^2 fits one CU: small again
+        dict(fuse_2d=0, fuse_classes=0)],
+}
+
+
+@pytest.mark.parametrize("dim", [3, 2])
+def test_smoother_path_selection_follows_the_size_thresholds(dim):
+    """smooth() tries its paths in a fixed order and the first that applies takes the sweeps; nine size thresholds decide
+    which applies (_smoother_plan states the rules).  On 17^3 / 33^3 / 65^3 and 33^2 / 65^2 / 129^2 levels, with every
+    threshold at the middle level's row count and at one more, each level lands on each path in turn: for nw = 1 .. 12 the
+    launch counts per path (hence K per pass and how a count splits) are the documented ones, the sweeps add up to nw, and
+    the result is bit-identical to one sweep per launch."""
+    import re
+    from multigrid_dolfinx_amd.hierarchy import DeviceHierarchy
+    c, lo, hi = (4, 1, 4) if dim == 3 else (8, 1, 4)      # (the coarsest level has no row classes: the direct solve's)
+    reference = dict(fuse_small=0, fuse_block=0, fuse_k=0, fuse_sweeps=0) if dim == 3 else dict(fuse_small=0, fuse_2d=0)
+    rng = np.random.default_rng(dim)
+    want = {}
+    seen = set()
+    for kw in [reference] + _PATH_TABLE[dim]:
+        with DeviceHierarchy.synthetic(dim, lo, hi, c=c, mu1=2, mu2=2, **kw) as dev:
+            cus = int(re.search(r"(\d+) CUs", dev.device_info()).group(1))
+            for level in range(lo + 1, hi + 1):
+                m = dev.elements(level) + 1
+                assert dev.level_info(level)["row_classes"] > 0
+                if (level, "v") not in want:
+                    want[level, "v"] = rng.standard_normal(m ** dim)
+                    want[level, "f"] = rng.standard_normal(m ** dim)
+                for nw in range(1, 13):
+                    dev.set_vector(level, "v", want[level, "v"])
+                    dev.set_vector(level, "f", want[level, "f"])
+                    dev.reset_smoother_launches()
+                    dev.smooth(level, nw)
+                    got = dev.get_vector(level, "v")
+                    ran = dev.smoother_launches(level)
+                    plan = _smoother_plan(dim, m, nw, kw, cus)
+                    assert {p: (n, s) for p, (n, s, _) in ran.items()} == plan, (kw, m, nw, ran)
+                    assert sum(s for _, s, _ in ran.values()) == nw
+                    seen |= set(ran)
+                    if kw is reference:
+                        assert set(ran) == {"slice"}, ran
+                        want[level, nw] = got
+                    else:
+                        assert np.array_equal(got, want[level, nw]), (kw, m, nw)
+    assert seen == ({"slice", "sweep1c", "pair_class", "pair_plain", "ksweep", "block", "small"} if dim == 3
+                    else {"slice", "k2d", "small"}), seen
 
 
 def test_time_kernel_reports_where_the_two_sweep_pass_is_not_used():
@@ -1518,12 +1763,13 @@ def test_3d_cycles_converge_to_the_direct_solution():
     gi = {l: L.grid_index for l, L in bag.levels.items()}
     A, f = bag.A_sp_dict[4][0].tocsc(), bag.b_dict[4]
     u = spla.spsolve(A, f.ravel())
-    with DeviceHierarchy.from_bag(bag, dim=3, grid_index=gi, fuse_min_rows=0) as dev:
-        assert dev.time_kernel("jacobi2", 4, 1) > 0.0                               # the 33^3 level pairs its sweeps
+    with DeviceHierarchy.from_bag(bag, dim=3, grid_index=gi, fuse_min_rows=0, fuse_block=0) as dev:
         dev.zero_vector(4, "v")
         dev.set_vector(4, "f", f)
         res = dev.vcycle(4, 150, residuals=True)
         v = dev.get_vector(4, "v").ravel()
+        ran = dev.smoother_launches(4)                                              # the 33^3 level pairs its sweeps
+    assert set(ran) == {"pair_class"} and ran["pair_class"][1] == 2 * ran["pair_class"][0] > 0, ran
     assert np.all(res[1:] < res[:-1]) or res[-1] <= 1e-13 * np.linalg.norm(f)
     assert res[-1] <= 1e-10 * np.linalg.norm(f), res[-1] / np.linalg.norm(f)
     assert np.linalg.norm(v - u) <= 1e-9 * np.linalg.norm(u)
