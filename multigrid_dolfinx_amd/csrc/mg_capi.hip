@@ -283,9 +283,11 @@ struct mg_context {
     int fuse_plain = 2;             // the pass on the stored rows (no classes): 2 = round-2 structure (sdia_jacobi2p), 1 = round 1's
     int class_sweeps = 1;           // so do the one-sweep kernels (residual, single Jacobi / Gauss-Seidel sweeps, SpMV)
     int fuse_k = 5;                 // sweeps per pass of the class-coded K-sweep march (mg_jacobik3d.hip.h): 3..5; < 3: pairs only
-    int fuse_k_shape = 7;           // ... its tile: 0 = 128 x 24 cells (12 waves x 2 lines), 1 = 64 x 48 (12 waves x 4 lines),
+    int fuse_k_shape = -1;          // ... its tile: 0 = 128 x 24 cells (12 waves x 2 lines), 1 = 64 x 48 (12 waves x 4 lines),
                                     // 2 = 128 x 24 (8 waves x 3 lines, 256 registers), 3 .. 5 = 64 x 24 by 6 / 8 / 4 waves, two workgroups
-                                    // per CU, 6 = 64 x 48 by 16 waves, 7 = 64 x 32 by 16 waves (no spills up to five sweeps: measured best)
+                                    // per CU, 6 = 64 x 48 by 16 waves, 7 = 64 x 32 by 16 waves (no spills up to five sweeps), 8 = shape 7
+                                    // with one barrier per step (level 0 in registers, images double-buffered); -1: 8 for five sweeps
+                                    // per pass, 7 for three and four (jk3_shape)
     int fuse_k_segments = 0;        // ... plane segments per tile (0: chosen from the item count)
     int timing_force_form = -1;     // mg_time_kernel("jacobik3:formN"): every step of the K-sweep pass in one form (wrong results; how fast
                                     // each form is by itself)
@@ -1363,13 +1365,18 @@ int escape_kmax(mg_context* c, const Level& L, const unsigned char* cls, int64_t
 // plane ranges of one launch of the march: [za0, za1) and then [zb0, zb1)
 struct JK3Range { int za0, za1, zb0, zb1; };
 
-template <int K, int NW, int LPW, int M, bool DPP, int PF = 1, int WPE = (NW == 12 ? 3 : 2), int TR = 256, bool ESC = false>
+// the tile shape of a K-sweep pass ("fuse_k_shape"; -1: chosen by K)
+int jk3_shape(const mg_context* c, int K) {
+    return c->fuse_k_shape >= 0 ? c->fuse_k_shape : (K >= 5 ? 8 : 7);
+}
+
+template <int K, int NW, int LPW, int M, bool DPP, int PF = 1, int WPE = (NW == 12 ? 3 : 2), int TR = 256, bool ESC = false, bool B1 = false>
 int launch_jacobikc_t(mg_context* c, JK3Args a, bool finest, const JK3Range& zr, int seglen) {
     constexpr int EX = 64 * M, EY = NW * LPW, WI = EX - 2 * K, HY = EY - 2 * K + 2;
     a.ntx = (a.nx + WI - 1) / WI;
     a.nty = (a.ny + HY - 1) / HY;
     const int64_t ntile = (int64_t)a.ntx * a.nty;
-    constexpr size_t lds = jk3_lds_bytes<K, NW, LPW, M, TR, ESC>();
+    constexpr size_t lds = B1 ? jk3b_lds_bytes<K, NW, LPW, M, TR>() : jk3_lds_bytes<K, NW, LPW, M, TR, ESC>();
     static_assert(lds <= 160 * 1024, "one CU's LDS");
     a.za0 = zr.za0; a.za1 = zr.za1; a.zb0 = zr.zb0; a.zb1 = zr.zb1;
     const int planes = std::max(0, zr.za1 - zr.za0) + std::max(0, zr.zb1 - zr.zb0);
@@ -1414,8 +1421,10 @@ int launch_jacobikc_t(mg_context* c, JK3Args a, bool finest, const JK3Range& zr,
     const int64_t group = 8 * (int64_t)a.xcd_chunk;
     const unsigned grid = (unsigned)(((items + group - 1) / group) * group);
     if (a.ncls > TR) return fail("more row classes than this tile shape keeps in LDS");
-    void (*kern)(JK3Args) = finest ? sdia_jacobikc_finest<K, NW, LPW, M, DPP, PF, WPE, TR> : sdia_jacobikc<K, NW, LPW, M, DPP, PF, WPE, TR>;
+    void (*kern)(JK3Args) = nullptr;
     if constexpr (ESC) kern = sdia_jacobikc_escape<K, NW, LPW, M, DPP, PF, WPE, TR>;
+    else if constexpr (B1) kern = finest ? sdia_jacobikc_finest_b1<K, NW, LPW, M, WPE, TR> : sdia_jacobikc_b1<K, NW, LPW, M, WPE, TR>;
+    else kern = finest ? sdia_jacobikc_finest<K, NW, LPW, M, DPP, PF, WPE, TR> : sdia_jacobikc<K, NW, LPW, M, DPP, PF, WPE, TR>;
     MG_TRY(allow_large_lds(c, reinterpret_cast<const void*>(kern), lds));
     hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * WAVE), lds, c->stream, a);
     HIP_TRY(hipGetLastError());
@@ -1427,7 +1436,7 @@ template <int K, int PF>
 int launch_jacobikc_kp(mg_context* c, const JK3Args& a, bool finest, const JK3Range& zr, int seglen) {
     if (!c->fuse_k_dpp) return launch_jacobikc_t<K, 12, 2, 2, false, PF>(c, a, finest, zr, seglen);     // (experiment: -1 / +1 neighbours through LDS)
     // shapes 3..5: 64 x 24 tiles, two workgroups per CU (class table of 64 rows); levels with more classes take shape 1
-    int shape = c->fuse_k_shape >= 3 && a.ncls > 64 ? 1 : c->fuse_k_shape;
+    int shape = jk3_shape(c, K) >= 3 && a.ncls > 64 ? 1 : jk3_shape(c, K);
     // planes with fewer 64 x 48 tiles than the GPU has CUs (the 513^2 and 257^2 planes of a slab's coarser levels): half
     // as tall tiles, two workgroups per CU
     if (shape == 1 && a.ncls <= 64 && K <= 4 && c->fuse_k_small_tiles) {
@@ -1442,6 +1451,8 @@ int launch_jacobikc_kp(mg_context* c, const JK3Args& a, bool finest, const JK3Ra
         case 5: if constexpr (K <= 4) return launch_jacobikc_t<K, 4, 6, 1, true, PF, 2, 64>(c, a, finest, zr, seglen);
         case 6: if constexpr (K <= 4 && PF == 1) return launch_jacobikc_t<K, 16, 3, 1, true, 1, 4>(c, a, finest, zr, seglen);      // 64 x 48 by 16 waves
         case 7: return launch_jacobikc_t<K, 16, 2, 1, true, PF, 4>(c, a, finest, zr, seglen);                                      // 64 x 32 by 16 waves
+        case 8: if constexpr (PF == 1) return launch_jacobikc_t<K, 16, 2, 1, true, 1, 4, 256, false, true>(c, a, finest, zr, seglen);  // ... one barrier per step
+                else return fail("tile shape 8 stages one plane of x (fuse_k_pf 1)");
         default: return launch_jacobikc_t<K, 12, 2, 2, true, PF>(c, a, finest, zr, seglen);
     }
 }
@@ -1455,7 +1466,7 @@ int launch_jacobikc_k(mg_context* c, const JK3Args& a, bool finest, const JK3Ran
     }
     // a second plane of x staged in registers ("fuse_k_pf" 2) fits the register budget with three sweeps only
     if constexpr (K == 3 || K == 4) {
-        if (c->fuse_k_pf == 2 && (K == 3 || c->fuse_k_shape == 7)) return launch_jacobikc_kp<K, 2>(c, a, finest, zr, seglen);
+        if (c->fuse_k_pf == 2 && (K == 3 || jk3_shape(c, K) == 7)) return launch_jacobikc_kp<K, 2>(c, a, finest, zr, seglen);
     }
     // (two sweeps per pass: slabs only, where a pass also saves an exchange; one tile shape)
     if constexpr (K == 2) return launch_jacobikc_t<K, 12, 4, 1, true, 1>(c, a, finest, zr, seglen);
@@ -3290,7 +3301,7 @@ int mg_set_tuning(mg_handle c, const char* key, int64_t value) {
         if (value < 0 || value > 5) return fail("fuse_k must be in 0..5 (below 3: pairs of sweeps only)");
         c->fuse_k = (int)value;
     } else if (k == "fuse_k_shape") {
-        if (value < 0 || value > 7) return fail("fuse_k_shape must be 0..7");
+        if (value < -1 || value > 8) return fail("fuse_k_shape must be 0..8, or -1 (by sweeps per pass)");
         c->fuse_k_shape = (int)value;
     } else if (k == "fuse_k_slab_min_rows") {
         c->fuse_k_slab_min_rows = value;

@@ -84,6 +84,21 @@ constexpr int jk3_pool(int K) { return K >= 5 ? 512 : 1024; }
 template <int K, int NW, int LPW, int M, int TR> constexpr size_t jk3_lds_doubles() {
     return TR * CLS_W + (size_t)K * (NW * LPW + 2) * (64 * M) + 2 * (64 * M + 2);
 }
+// One barrier per step (tile shape 8, `B1`): level 0 is not kept in LDS at all -- a wave has x of its own lines in registers
+// and loads the line above and the line below them too (lines its neighbour waves load in the same step: they come from
+// the caches) --, and the images of levels 1 .. K-1 are double-buffered by the parity of the step.  Phase A of step k
+// writes parity k & 1 and reads its own slots of parity (k - 1) & 1; phase B reads parity k & 1, so the barrier behind
+// phase B goes: the next write of a parity that phase B(k) reads is phase A(k + 2), and the barrier in front of phase
+// B(k + 1) lies between them.  Images of EY lines, stride EY + 1: the zero lines between them (and before the first) are
+// the line below and above the tile of every level >= 1 (those rows were always outside the level's valid region).
+//   [zero] [level 1, parity 0] [zero] [level 2, parity 0] [zero] ... [level K-1, parity 1] [zero]
+template <int K, int NW, int LPW, int M, int TR> constexpr size_t jk3b_lds_doubles() {
+    return TR * CLS_W + (size_t)(2 * (K - 1) * (NW * LPW + 1) + 1) * (64 * M);
+}
+template <int K, int NW, int LPW, int M, int TR> constexpr size_t jk3b_lds_bytes() {
+    return sizeof(double) * jk3b_lds_doubles<K, NW, LPW, M, TR>();
+}
+
 template <int K, int NW, int LPW, int M, int TR, bool ESC = false> constexpr size_t jk3_lds_bytes() {
     constexpr size_t base = jk3_lds_doubles<K, NW, LPW, M, TR>();
     return sizeof(double) * (ESC ? (base + CLS_W - 1) / CLS_W * CLS_W + (size_t)(jk3_pool(K) + 1) * CLS_W : base);
@@ -91,9 +106,12 @@ template <int K, int NW, int LPW, int M, int TR, bool ESC = false> constexpr siz
 
 // (jk3_from_west / jk3_from_east -- the value of the lane next door through DPP -- live in mg_jacobi2.hip.h)
 
-template <int K, int NW, int LPW, int M, bool DPP, int PF, int TR, bool ESC = false>
+template <int K, int NW, int LPW, int M, bool DPP, int PF, int TR, bool ESC = false, bool B1 = false>
 __device__ __forceinline__ void jk3_body(const JK3Args& a) {
     constexpr int EX = 64 * M, EY = NW * LPW, NC = M * LPW, IMG = (EY + 2) * EX;
+    // (B1) image stride and parity stride, in doubles
+    constexpr int IS = (EY + 1) * EX, PS = (K - 1) * IS;
+    static_assert(!B1 || (DPP && PF == 1 && !ESC), "one barrier per step: DPP neighbours, one plane of x in flight, no escape rows");
     // classes in the ring: a byte per cell, four cells to a register -- sixteen bits where pool rows are classes too
     constexpr int CBITS = ESC ? 16 : 8, CPR = 32 / CBITS, CW = (NC + CPR - 1) / CPR;
     constexpr unsigned CMASK = (1u << CBITS) - 1u;
@@ -106,6 +124,7 @@ __device__ __forceinline__ void jk3_body(const JK3Args& a) {
     extern __shared__ double j2_smem[];
     double* const sT = j2_smem;                               // 256 x 8   entries of the row classes, [7] = omega / diagonal
     double* const sI = sT + TR * CLS_W + (EX + 2);           // K x (EY+2) x EX   one plane of level t, origin (0,-1)
+                                                              // (B1: see jk3b_lds_doubles; addressed from j2_smem)
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
 
@@ -146,7 +165,8 @@ __device__ __forceinline__ void jk3_body(const JK3Args& a) {
             }
             sT[i] = v;
         }
-        for (int i = threadIdx.x; i < K * IMG + 2 * (EX + 2); i += NW * WAVE) sT[TR * CLS_W + i] = 0.0;
+        constexpr int NZ = B1 ? (2 * (K - 1) * (EY + 1) + 1) * EX : K * IMG + 2 * (EX + 2);
+        for (int i = threadIdx.x; i < NZ; i += NW * WAVE) sT[TR * CLS_W + i] = 0.0;
     }
     unsigned* const esc_count = reinterpret_cast<unsigned*>(sT + (size_t)CLS_W * (DYN0 + jk3_pool(K)));   // (ESC) pool rows handed out so far
     if constexpr (ESC) {
@@ -170,6 +190,12 @@ __device__ __forceinline__ void jk3_body(const JK3Args& a) {
         asm volatile("" : "+v"(ibase[q]));
     }
     auto image = [&](int t) -> double* { return sI + ibase[t >> 1] + (t & 1) * IMG; };  // level t's plane, at cell 0
+    // (B1) level t >= 1 of the step's parity (bcur) or of the step before (bprev), at cell 0: one address register each,
+    // set per step, at the wave's line -1 of level 1 -- every access of a step is `register + 16-bit immediate`
+    int bcur = 0, bprev = 0;
+    auto limg = [&](int base, int t) -> double* { return j2_smem + base + (t - 1) * IS + EX; };
+    double XP[B1 ? NC : 1];     // (B1) x of the plane before the newest, own cells: the value level 1 relaxes
+    double hS[M], hN[M];        // (B1) x of the line below / above this wave's lines, of the newest plane
     unsigned inT = 0;           // bit c: this lane's cell c gets all K sweeps and lies on the grid
     const int64_t rb0 = (int64_t)(ty0 + ey0) * a.nx + (tx0 + lane);
     auto rowof = [&](int c) -> int64_t { return rb0 + (int64_t)(c / M) * a.nx + 64 * (c % M); };
@@ -204,6 +230,14 @@ __device__ __forceinline__ void jk3_body(const JK3Args& a) {
 #pragma unroll
     for (int r = 0; r < M; ++r)
         eor[r] = 8u * (unsigned)((wlo ? max(ty0 - 1, -2) : min(ty0 + EY, a.ny + 1)) * a.nx + tx0 + min(lane + 64 * r, xcl) + bias);
+    unsigned eos[B1 ? M : 1], eon[B1 ? M : 1];      // (B1) the lines below / above the wave's, clamped like `eo`
+    if constexpr (B1) {
+#pragma unroll
+        for (int r = 0; r < M; ++r) {
+            eos[r] = 8u * (unsigned)(min(max(ty0 + ey0 - 1, -2), a.ny + 1) * a.nx + tx0 + min(lane + 64 * r, xcl) + bias);
+            eon[r] = 8u * (unsigned)(min(max(ty0 + ey0 + LPW, -2), a.ny + 1) * a.nx + tx0 + min(lane + 64 * r, xcl) + bias);
+        }
+    }
     const unsigned char* const clsb = a.cls + a.clead - bias;
     const double* const xb0 = a.x - bias;
     const double* const fb0 = a.f - bias;
@@ -250,8 +284,10 @@ __device__ __forceinline__ void jk3_body(const JK3Args& a) {
 #pragma unroll
         for (int q = 0; q < CW; ++q) cw[j][q] = 0u;
 #pragma unroll
-    for (int r = 0; r < M; ++r) hyA[r] = 0.0;
+    for (int r = 0; r < M; ++r) hyA[r] = hS[r] = hN[r] = 0.0;
     XB[0] = 0.0; hyB[0] = 0.0; CB[0] = 0; FN[0] = 0.0;
+#pragma unroll
+    for (int c = 0; c < (B1 ? NC : 1); ++c) XP[c] = 0.0;   // (level 0 below the first plane: the zeros of the image it replaces)
 
     // Loads are issued in slices, slice i of n between the pieces of phase B: issued in one burst (14 per wave, all twelve
     // waves at the same point of the step) they keep every wave at the vector-memory issue port in front of the barrier
@@ -272,7 +308,12 @@ __device__ __forceinline__ void jk3_body(const JK3Args& a) {
             if constexpr (PF == 2) FN[c] = ldd(fb, eo[c]);
             else fr[K - 1][c] = ldd(fb, eo[c]);
         }
-        if (i == n - 1 && (wlo || whi)) {
+        if constexpr (B1) {
+            if (i == n - 1) {
+#pragma unroll
+                for (int r = 0; r < M; ++r) { hS[r] = ldd(xb, eos[r]); hN[r] = ldd(xb, eon[r]); }
+            }
+        } else if (i == n - 1 && (wlo || whi)) {
 #pragma unroll
             for (int r = 0; r < M; ++r) hy[r] = ldd(xb, eor[r]);
         }
@@ -325,6 +366,15 @@ __device__ __forceinline__ void jk3_body(const JK3Args& a) {
                 double nw = X[c];
 #pragma unroll
                 for (int t = 1; t <= K; ++t) {
+                    if constexpr (B1) {
+                        const double wd = t == 1 ? XP[c] : limg(bprev, t - 1)[iw];
+                        const double s = fma(k6, nw, acc[t - 1][c]);      // +P
+                        const double o = wd + kcf * (fr[K - t][c] - s);
+                        acc[t - 1][c] = fma(k0, wd, 0.0);                 // -P of the plane above
+                        if (t > 1) limg(bcur, t - 1)[iw] = nw;
+                        nw = o;
+                        continue;
+                    }
                     double* const img = image(t - 1);
                     const double wd = img[iw];
                     const double s = fma(k6, nw, acc[t - 1][c]);      // +P
@@ -339,12 +389,19 @@ __device__ __forceinline__ void jk3_body(const JK3Args& a) {
     };
     // (phase B comes in K pieces, one per level, so that the loads can go out in COMMON code between them: a load issued
     //  inside the branches of the three forms makes the compiler spill hundreds of registers)
-    auto phase_b_fast = [&](auto col_tag, const int t) __attribute__((always_inline)) {
+    auto phase_b_fast = [&](auto col_tag, const int t, const double (&X)[NC]) __attribute__((always_inline)) {
         constexpr bool COL = decltype(col_tag)::value;
-        const double* const img = image(t - 1);
+        const double* const img = B1 ? limg(bcur, t > 1 ? t - 1 : 1) : image(t - 1);
         double v[LPW][M], ys[M], yn[M];
 #pragma unroll
         for (int r = 0; r < M; ++r) {
+            if (B1 && t == 1) {         // (level 0: registers)
+                ys[r] = hS[r];
+#pragma unroll
+                for (int l = 0; l < LPW; ++l) v[l][r] = X[l * M + r];
+                yn[r] = hN[r];
+                continue;
+            }
             ys[r] = img[-EX + 64 * r];
 #pragma unroll
             for (int l = 0; l < LPW; ++l) v[l][r] = img[l * EX + 64 * r];
@@ -399,15 +456,15 @@ __device__ __forceinline__ void jk3_body(const JK3Args& a) {
 #pragma unroll
             for (int t = 1; t <= K; ++t) {
                 const int j = K - t;                                  // ring index of the plane being finished
-                double* const img = image(t - 1);
-                const double wd = img[iw];
+                double* const img = B1 ? limg(bcur, t > 1 ? t - 1 : 1) : image(t - 1);
+                const double wd = B1 ? (t == 1 ? XP[B1 ? c : 0] : limg(bprev, t - 1)[iw]) : img[iw];
                 const dvec2_t t67 = reinterpret_cast<const dvec2_t*>(sT + CLS_W * cls_now(j, c))[3];
                 const dvec2_t t01 = reinterpret_cast<const dvec2_t*>(sT + CLS_W * cls_now(j + 1, c))[0];
                 const double s = fma(t67.x, nw, acc[t - 1][c]);
                 double o = wd + t67.y * (fr[j][c] - s);
                 o = (unsigned)(pc + j - lo_t[t]) < (unsigned)n_t[t] ? o : 0.0;
                 acc[t - 1][c] = fma(t01.x, wd, 0.0);
-                img[iw] = nw;
+                if (!B1 || t > 1) img[iw] = nw;
                 nw = o;
                 __builtin_amdgcn_sched_barrier(0);      // (rare path: one cell and level at a time keeps it out of the
                                                         //  register budget of the straight-line forms)
@@ -415,12 +472,35 @@ __device__ __forceinline__ void jk3_body(const JK3Args& a) {
             if (k_store && (inT >> c & 1u)) store(c, nw);
         }
     };
-    auto phase_b_general = [&](const int t) __attribute__((always_inline)) {
+    auto phase_b_general = [&](const int t, const double (&X)[NC]) __attribute__((always_inline)) {
+        // (B1, level 0: the -1 / +1 neighbours through DPP as in the straight-line form, all cells' before the first use)
+        double x0w[B1 ? NC : 1], x0e[B1 ? NC : 1];
+        if constexpr (B1) {
+            if (t == 1) {
+                double fw[NC], fe[NC];
+#pragma unroll
+                for (int c = 0; c < NC; ++c) { fw[c] = jk3_from_west(X[c]); fe[c] = jk3_from_east(X[c]); }
+#pragma unroll
+                for (int c = 0; c < NC; ++c) {
+                    const int r = c % M;
+                    x0w[c] = (r > 0 && lane == 0) ? fw[r > 0 ? c - 1 : c] : fw[c];
+                    x0e[c] = (r + 1 < M && lane == 63) ? fe[r + 1 < M ? c + 1 : c] : fe[c];
+                }
+            }
+        }
 #pragma unroll
         for (int c = 0; c < NC; ++c) {
             const int iw = lwof(c);
-            const double* const img = image(t - 1);
-            const double ys = img[iw - EX], yw = img[iw - 1], yd = img[iw], ye = img[iw + 1], yn = img[iw + EX];
+            double ys, yw, yd, ye, yn;
+            if (B1 && t == 1) {
+                const int l = c / M, r = c % M;
+                ys = l > 0 ? X[l > 0 ? c - M : c] : hS[r];
+                yw = x0w[B1 ? c : 0]; yd = X[c]; ye = x0e[B1 ? c : 0];
+                yn = l + 1 < LPW ? X[l + 1 < LPW ? c + M : c] : hN[r];
+            } else {
+                const double* const img = B1 ? limg(bcur, t > 1 ? t - 1 : 1) : image(t - 1);
+                ys = img[iw - EX]; yw = img[iw - 1]; yd = img[iw]; ye = img[iw + 1]; yn = img[iw + EX];
+            }
             const dvec2_t* const tr = reinterpret_cast<const dvec2_t*>(sT + CLS_W * cls_now(K - t, c));
             const dvec2_t t01 = tr[0], t23 = tr[1], t45 = tr[2];
             double s = acc[t - 1][c];
@@ -442,6 +522,12 @@ __device__ __forceinline__ void jk3_body(const JK3Args& a) {
     auto step = [&](const int k, double (&X)[NC], int (&C)[NC], double (&hy)[M], double (&XN)[PF == 2 ? NC : 1],
                     int (&CN)[PF == 2 ? NC : 1], double (&hyN)[PF == 2 ? M : 1]) __attribute__((always_inline)) {
         k_plane = k; k_store = k >= z0;
+        if constexpr (B1) {
+            bcur = TR * CLS_W + ey0 * EX + lane + (k & 1) * PS;
+            bprev = TR * CLS_W + ey0 * EX + lane + ((k + 1) & 1) * PS;
+            asm volatile("" : "+v"(bcur));
+            asm volatile("" : "+v"(bprev));
+        }
         {
             const unsigned long long u = (unsigned long long)(a.out - bias + (int64_t)k * a.P);
             const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)u);
@@ -535,7 +621,10 @@ __device__ __forceinline__ void jk3_body(const JK3Args& a) {
         if (form == 0) phase_a_fast(std::false_type{}, X);
         else if (form == 1) phase_a_fast(std::true_type{}, X);
         else phase_a_general(X);
-        if (wlo || whi) {
+        if constexpr (B1) {
+#pragma unroll
+            for (int c = 0; c < NC; ++c) XP[c] = X[c];
+        } else if (wlo || whi) {
             double* const ring = image(0) + (wlo ? -EX : LPW * EX);
 #pragma unroll
             for (int r = 0; r < M; ++r) ring[64 * r] = hy[r];
@@ -576,12 +665,12 @@ __device__ __forceinline__ void jk3_body(const JK3Args& a) {
         };
 #pragma unroll
         for (int t = 1; t <= K; ++t) {
-            if (form == 0) phase_b_fast(std::false_type{}, t);
-            else if (form == 1) phase_b_fast(std::true_type{}, t);
-            else phase_b_general(t);
+            if (form == 0) phase_b_fast(std::false_type{}, t, X);
+            else if (form == 1) phase_b_fast(std::true_type{}, t, X);
+            else phase_b_general(t, X);
             issue(t - 1, K);
         }
-        __syncthreads();
+        if constexpr (!B1) __syncthreads();
     };
 
     load_slice(0, 1, z0 - K, z0 - K - 1, XA, CA, hyA);
@@ -608,6 +697,18 @@ template <int K, int NW, int LPW, int M, bool DPP, int PF, int WPE, int TR>
 __global__ __attribute__((amdgpu_flat_work_group_size(NW * WAVE, NW * WAVE), amdgpu_waves_per_eu(WPE, WPE)))
 void sdia_jacobikc_finest(JK3Args a) {
     jk3_body<K, NW, LPW, M, DPP, PF, TR>(a);
+}
+
+// tile shape 8: one barrier per step (see jk3b_lds_doubles)
+template <int K, int NW, int LPW, int M, int WPE, int TR>
+__global__ __attribute__((amdgpu_flat_work_group_size(NW * WAVE, NW * WAVE), amdgpu_waves_per_eu(WPE, WPE)))
+void sdia_jacobikc_b1(JK3Args a) {
+    jk3_body<K, NW, LPW, M, true, 1, TR, false, true>(a);
+}
+template <int K, int NW, int LPW, int M, int WPE, int TR>
+__global__ __attribute__((amdgpu_flat_work_group_size(NW * WAVE, NW * WAVE), amdgpu_waves_per_eu(WPE, WPE)))
+void sdia_jacobikc_finest_b1(JK3Args a) {
+    jk3_body<K, NW, LPW, M, true, 1, TR, false, true>(a);
 }
 
 // (levels with rows of class CLS_ESCAPE)
