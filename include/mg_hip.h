@@ -372,7 +372,9 @@ int mg_copy_vector(mg_handle h, int level, int dst_which, int src_which);
  *              0..top_level: MG_VEC_F[top_level] is the right-hand side there, the coarser
  *              levels use the true right-hand sides given with mg_set_rhs_true (b_dict,
  *              multigrid.py:279).  elements_per_dim == 0 in mg_set_level_csr declares a
- *              "flat" level (any square matrix, smoother/residual only, single GPU). */
+ *              "flat" level (any square matrix, smoother/residual only, single GPU).
+ * mg_pcg       solve to a tolerance: flexible CG preconditioned by one V-cycle per iteration
+ *              (no reference counterpart; declared after mg_fmg_ex) */
 int mg_smooth(mg_handle h, int level, int nw);
 /* jacobiRelaxation on the reference's own split operands (multigrid.py:223-228), for callers that hand
  * over (D^-1 R, D^-1) rather than A: the level's matrix is D^-1 (A - D) (set with
@@ -410,6 +412,19 @@ int mg_set_mass_csr(mg_handle h, int level, int64_t n_rows, int64_t nnz, const v
 int mg_set_exact(mg_handle h, int level, const double* host);
 int mg_fmg_ex(mg_handle h, int top_level, int mu0, double tol, int max_cycles, int norm, double* resid_hist,
               double* err_hist, int* cycles_done);
+/* Flexible CG on `level` preconditioned by one V(mu1,mu2) cycle per iteration.  Starts from MG_VEC_V, solves
+ * A x = MG_VEC_F, stops when ||r_k||_2 <= rtol * ||F||_2 or after max_iter iterations (rtol <= 0: exactly
+ * max_iter), or earlier if the recursive residual is exactly zero.  On return: MG_VEC_V = x, MG_VEC_F unchanged bit
+ * for bit, MG_VEC_R = F - A x (recomputed, not the recursive residual).  resid_hist[k] (optional, max_iter entries)
+ * = ||r_k||_2 of the recursion after iteration k + 1; *iterations = iterations done (0 if the start already meets the
+ * tolerance).  The preconditioner is one V-cycle of the handle's hierarchy from a zero guess -- whatever restriction,
+ * smoother, prolongation table and coarsest solve the handle has -- and is neither symmetric nor exactly linear, hence
+ * the flexible (Polak-Ribiere) form beta = -alpha (z.q) / (r.z)_old.  Level >= 1, grid levels only; reaching max_iter
+ * is not an error.  The first call on a level allocates four work vectors of its size (x, p, q = A p, the saved
+ * right-hand side), freed with the handle; only one scalar per iteration crosses to the host (mg_counters' uploads and
+ * downloads do not change).  Slabs: every dot product is all-reduced.  No reference counterpart (the reference solves
+ * with V-cycles / FMG only). */
+int mg_pcg(mg_handle h, int level, double rtol, int max_iter, double* resid_hist, int* iterations);
 /* Bookkeeping for tests: whole-vector host -> device / device -> host copies made through this handle so far,
  * V-cycles replayed from a captured hipGraph, graphs currently cached.  No reference counterpart. */
 int mg_counters(mg_handle h, int64_t* uploads, int64_t* downloads, int64_t* graph_replays, int* graphs_cached);

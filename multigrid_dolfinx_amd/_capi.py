@@ -78,6 +78,7 @@ SIGNATURES = {
     "mg_set_mass_csr": [_H, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p],
     "mg_set_exact": [_H, C.c_int, C.c_void_p],
     "mg_fmg_ex": [_H, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_void_p, _ip],
+    "mg_pcg": [_H, C.c_int, C.c_double, C.c_int, C.c_void_p, _ip],
     "mg_counters": [_H, _i64p, _i64p, _i64p, _ip],
     "mg_smoother_launches": [_H, C.c_int, C.c_int, _i64p, _i64p, _i64p],
     "mg_reset_smoother_launches": [_H],

@@ -177,6 +177,7 @@ struct Level {
     double* dinv = nullptr;
     DVector v, v2, f, err, ftrue;
     DVector sw;                             // once-relaxed boundary planes of a slab (paired sweeps, world > 1)
+    DVector fcg_x, fcg_p, fcg_q, fcg_b;     // mg_pcg on this level: iterate, direction, A p, the saved right-hand side
     int* perm = nullptr;
     unsigned long long nnz_stored = 0, nnz_nonzero = 0;
     // per-rank plane ownership (for gathers): k-plane boundaries s[0..world]
@@ -243,6 +244,11 @@ struct mg_context {
     DVector pcg_p;
     int pcg_parts = 0, pcg_parts_a = 0;
     int pcg_predict = 0;
+    // mg_pcg: scalars, folded / slab-reduced sums and the step kernels' partial sums (fcg_work, fcg_work_n doubles); the
+    // SpMV's partial sums of p.q (fcg_spmv, fcg_spmv_n doubles: one per block of the level's SpMV)
+    double* fcg_work = nullptr;
+    double* fcg_spmv = nullptr;
+    int64_t fcg_work_n = 0, fcg_spmv_n = 0;
     int use_graph = 1;              // replay whole V-cycles as hipGraphs (single GPU, direct coarsest solve)
     int comm_priority = 1;          // communication stream created with the highest priority (MG_COMM_PRIORITY=0: lowest)
     int lattice_march = 1;          // wide lattice stencils (P2 levels) as a plane march with x in LDS (mg_lattice.hip.h)
@@ -543,6 +549,10 @@ void free_level(mg_context* c, Level& L) {
     vec_free(c, L, &L.err);
     vec_free(c, L, &L.ftrue);
     vec_free(c, L, &L.sw);
+    vec_free(c, L, &L.fcg_x);
+    vec_free(c, L, &L.fcg_p);
+    vec_free(c, L, &L.fcg_q);
+    vec_free(c, L, &L.fcg_b);
     L.set = false;
     L.has_matrix = false;
 }
@@ -2456,6 +2466,155 @@ int vcycle_graphed(mg_context* c, int level) {
     return 0;
 }
 
+// ---- flexible CG preconditioned by one V-cycle (mg_pcg) ---------------------------------------------------------------
+// Vector roles during the iteration: r is the level's MG_VEC_F (the cycle's right-hand side), z the cycle's iterate
+// MG_VEC_V; x, p, q and the saved right-hand side b are the level's fcg_* vectors.  The step kernels (mg_kernels.hip.h,
+// fcg_*) run eagerly around the captured V-cycle; per iteration one 8-byte scalar (||r||^2) crosses to the host.
+constexpr int kFcgFold = 256;       // SpMV partial sums beyond this many are folded to this many before fcg_update
+
+// 4 blocks of 256 threads per CU, fewer where a thread would stream less than four pairs of rows
+unsigned fcg_grid(const mg_context* c, const Level& L) {
+    const int64_t want = (L.nloc / 2 + 4 * BLOCK - 1) / (4 * BLOCK);
+    return (unsigned)std::max<int64_t>(1, std::min<int64_t>(want, 4 * std::max(1, c->prop.multiProcessorCount)));
+}
+
+// Layout of c->fcg_work: [0, 8) scalars (fcg kernels' sc, then the slab totals pq, rr, rz, zq), [8, 8 + kFcgFold) folded
+// p.q, then the step kernels' partial sums: r.r (gmax), r.z / z.q interleaved (2 gmax).
+struct FcgWork {
+    double *sc, *tot_pq, *tot_rr, *tot_dots, *fold_pq, *part_rr, *part_dots;
+};
+FcgWork fcg_work(const mg_context* c) {
+    const int64_t gmax = 4 * std::max(1, c->prop.multiProcessorCount);
+    double* w = c->fcg_work;
+    return FcgWork{w, w + 2, w + 3, w + 4, w + 8, w + 8 + kFcgFold, w + 8 + kFcgFold + gmax};
+}
+
+// Sums the kernels reduce in every block: `np` groups of `stride` partial sums at `parts`.  On slabs they are summed to one
+// group here and all-reduced (1-2 doubles); on one GPU more than `fold_above` groups are folded to kFcgFold first.  Every
+// order is fixed by the level and the device.
+int fcg_sums(mg_context* c, const Level& L, const double*& parts, int64_t& np, int stride, int64_t fold_above, double* fold,
+             double* total) {
+    const bool slab = !L.replicated && c->comm.active();
+    if (!slab && np > fold_above) {
+        hipLaunchKernelGGL(fcg_fold, dim3(kFcgFold), dim3(BLOCK), 0, c->stream, parts, np, stride, fold);
+        parts = fold;
+        np = kFcgFold;
+    }
+    if (slab) {
+        hipLaunchKernelGGL(fcg_fold, dim3(1), dim3(BLOCK), 0, c->stream, parts, np, stride, total);
+        HIP_TRY(hipGetLastError());
+        MG_TRY(allreduce_sum(c, total, stride));
+        parts = total;
+        np = 1;
+    }
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// z = one V(mu1, mu2) cycle from a zero guess on r (= F); the cycle may swap the level's V buffers, so z is read after it.
+// v_zeroed: fcg_update has zeroed V (whole levels: V is the owned rows and nothing else)
+int fcg_precondition(mg_context* c, int level, FcgArgs& a, bool v_zeroed) {
+    Level& L = c->L[level];
+    if (!v_zeroed) MG_TRY(zero_vec(c, L, L.v));
+    MG_TRY(vcycle_graphed(c, level));
+    a.z = L.v.rows;
+    if (reinterpret_cast<uintptr_t>(a.z) % 16) return fail("mg_pcg: misaligned iterate");
+    return 0;
+}
+
+int fcg_solve(mg_context* c, int level, double rtol, int max_iter, double* hist, int* iters_out) {
+    Level& L = c->L[level];
+    MG_TRY(prepare_cycle(c, level));
+    MG_TRY(vec_alloc(c, L, &L.fcg_x));
+    MG_TRY(vec_alloc(c, L, &L.fcg_p));
+    MG_TRY(vec_alloc(c, L, &L.fcg_q));
+    MG_TRY(vec_alloc(c, L, &L.fcg_b));
+    const int64_t gmax = 4 * std::max(1, c->prop.multiProcessorCount);
+    if (!c->fcg_work) {
+        c->fcg_work_n = 8 + kFcgFold + 3 * gmax;
+        MG_TRY(dev_alloc(c, &c->fcg_work, (size_t)c->fcg_work_n));
+    }
+    const int64_t nspmv = blocks_for(L.nslices, WAVES_PER_BLOCK);       // partial sums of the SpMV (launch_ell with dot)
+    if (c->fcg_spmv_n < nspmv) {
+        dev_free(c, c->fcg_spmv, (size_t)c->fcg_spmv_n);
+        c->fcg_spmv_n = 0;
+        MG_TRY(dev_alloc(c, &c->fcg_spmv, (size_t)nspmv));
+        c->fcg_spmv_n = nspmv;
+    }
+    const FcgWork w = fcg_work(c);
+    const size_t bytes = (size_t)L.xlen * sizeof(double);
+
+    // x = V, b = F, r = F - A x (in F)
+    HIP_TRY(hipMemcpyAsync(L.fcg_b.base, L.f.base, bytes, hipMemcpyDeviceToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(L.fcg_x.base, L.v.base, bytes, hipMemcpyDeviceToDevice, c->stream));
+    MG_TRY(exchange_halo(c, L, L.fcg_x));
+    MG_TRY(launch_ell(c, L, MODE_RESIDUAL, false, L.fcg_x.base, L.fcg_b.rows, L.f.rows, nullptr, nullptr));
+    double bnorm = 0.0, rnorm = 0.0;
+    MG_TRY(norm2(c, L, L.fcg_b.rows, &bnorm));
+    MG_TRY(norm2(c, L, L.f.rows, &rnorm));
+    const double tol = rtol > 0.0 ? rtol * bnorm : -1.0;
+
+    FcgArgs a{};
+    a.x = L.fcg_x.rows; a.r = L.f.rows; a.p = L.fcg_p.rows; a.q = L.fcg_q.rows; a.sc = w.sc; a.n = L.nloc;
+    for (const double* v : {(const double*)a.x, (const double*)a.r, (const double*)a.p, a.q})
+        if (reinterpret_cast<uintptr_t>(v) % 16) return fail("mg_pcg: misaligned work vector");
+    const dim3 grid(fcg_grid(c, L)), blk(BLOCK);
+    int it = 0;
+    if (max_iter > 0 && rnorm > tol && rnorm > 0.0) {
+        // z = M r, p = z
+        MG_TRY(fcg_precondition(c, level, a, false));
+        a.out = w.part_dots;
+        hipLaunchKernelGGL(fcg_dots<false>, grid, blk, 0, c->stream, a);
+        hipLaunchKernelGGL(fcg_direction<true>, grid, blk, 0, c->stream, a);
+        const double* dots = w.part_dots;
+        int64_t nd = grid.x;
+        MG_TRY(fcg_sums(c, L, dots, nd, 2, INT64_MAX, nullptr, w.tot_dots));
+        a.dots = dots; a.nd = (int)nd;
+        for (;;) {
+            // q = A p with the partial sums of p.q
+            MG_TRY(exchange_halo(c, L, L.fcg_p));
+            unsigned nsp = 0;
+            MG_TRY(launch_ell(c, L, MODE_SPMV, true, L.fcg_p.base, nullptr, L.fcg_q.rows, c->fcg_spmv, nullptr, &nsp));
+            if ((int64_t)nsp > c->fcg_spmv_n) return fail("mg_pcg: SpMV partial sums overflow");
+            const double* pq = c->fcg_spmv;
+            int64_t npq = nsp;
+            MG_TRY(fcg_sums(c, L, pq, npq, 1, kFcgFold, w.fold_pq, w.tot_pq));
+            a.pq = pq; a.npq = (int)npq;
+            // alpha, x += alpha p, r -= alpha q, ||r||^2 to the host
+            a.out = w.part_rr;
+            a.vz = L.g.lead == 0 && L.xlen == L.nloc ? L.v.rows : nullptr;
+            hipLaunchKernelGGL(fcg_update, grid, blk, 0, c->stream, a);
+            hipLaunchKernelGGL(fcg_fold, dim3(1), blk, 0, c->stream, w.part_rr, (int64_t)grid.x, 1, w.tot_rr);
+            HIP_TRY(hipGetLastError());
+            if (!L.replicated) MG_TRY(allreduce_sum(c, w.tot_rr, 1));
+            HIP_TRY(hipMemcpyAsync(c->h_scalars, w.tot_rr, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(hipStreamSynchronize(c->stream));
+            const double rn = std::sqrt(c->h_scalars[0]);
+            if (hist) hist[it] = rn;
+            ++it;
+            if (rn <= tol || rn == 0.0 || it >= max_iter) break;
+            // z = M r; r.z and z.q; p = z + beta p
+            MG_TRY(fcg_precondition(c, level, a, a.vz != nullptr));
+            a.out = w.part_dots;
+            hipLaunchKernelGGL(fcg_dots<true>, grid, blk, 0, c->stream, a);
+            dots = w.part_dots;
+            nd = grid.x;
+            MG_TRY(fcg_sums(c, L, dots, nd, 2, INT64_MAX, nullptr, w.tot_dots));
+            a.dots = dots; a.nd = (int)nd;
+            hipLaunchKernelGGL(fcg_direction<false>, grid, blk, 0, c->stream, a);
+            HIP_TRY(hipGetLastError());
+        }
+    }
+    // V = x, F = b bit for bit, R = F - A x
+    HIP_TRY(hipMemcpyAsync(L.v.base, L.fcg_x.base, bytes, hipMemcpyDeviceToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(L.f.base, L.fcg_b.base, bytes, hipMemcpyDeviceToDevice, c->stream));
+    MG_TRY(exchange_halo(c, L, L.v));
+    MG_TRY(residual(c, level));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (iters_out) *iters_out = it;
+    return 0;
+}
+
 int ensure_stage(mg_context* c, int64_t elems) {
     if (c->stage_elems >= elems) return 0;
     dev_free(c, c->stage, (size_t)c->stage_elems);
@@ -2974,6 +3133,8 @@ int mg_destroy(mg_handle c) {
     (void)hipFree(c->pcg_p.raw);
     (void)hipFree(c->pcg_part_a);
     (void)hipFree(c->pcg_part_b);
+    (void)hipFree(c->fcg_work);
+    (void)hipFree(c->fcg_spmv);
     (void)hipFree(c->stage);
     if (c->h_scalars) (void)hipHostFree(c->h_scalars);
     if (c->comm.h_stage) (void)hipHostFree(c->comm.h_stage);
@@ -4109,6 +4270,20 @@ int mg_fmg_ex(mg_handle c, int top, int mu0, double tol, int max_cycles, int nor
 
 int mg_fmg(mg_handle c, int top, int mu0, double tol, int max_cycles, double* resid_l2, int* cycles_done) {
     return mg_fmg_ex(c, top, mu0, tol, max_cycles, MG_NORM_L2, resid_l2, nullptr, cycles_done);
+}
+
+int mg_pcg(mg_handle c, int level, double rtol, int max_iter, double* resid_hist, int* iterations) {
+    MG_TRY(check_level(c, level));
+    if (c->L[level].flat)
+        return fail("mg_pcg: level " + std::to_string(level) + " is flat (no grid): there is no V-cycle to precondition with");
+    if (level < 1) return fail("mg_pcg: level 0 is the coarsest level: the V-cycle preconditioner needs level >= 1");
+    if (max_iter < 0) return fail("mg_pcg: max_iter must not be negative");
+    for (int l = 0; l <= level; ++l) {
+        MG_TRY(need_matrix(c, l));
+        MG_TRY(need_grid(c, l));
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    return fcg_solve(c, level, rtol, max_iter, resid_hist, iterations);
 }
 
 int mg_time_kernel(mg_handle c, const char* kernel, int level, int reps, double* avg_ms) {

@@ -1716,4 +1716,133 @@ __global__ __launch_bounds__(BLOCK) void pcg_direction(PcgArgs a, int it) {
     }
 }
 
+// ---- flexible CG preconditioned by one V-cycle (mg_pcg) -------------------------------------------------------------
+// The V-cycle runs between fcg_update and fcg_dots and reads r as its right-hand side (r is the level's MG_VEC_F); z is
+// the cycle's iterate MG_VEC_V.  Every vector is a row pointer of one level (16-byte aligned: vec_front), so the body
+// moves double2 and a scalar tail takes an odd last row.  All sums are deterministic: each block writes its own partial
+// sum, and a kernel that needs the total reduces the same partials in the same order in every block (fcg_sum).
+// Scalars sc[0] = alpha, sc[1] = r.z of the iteration (written by block 0 of fcg_update, read by fcg_direction).
+struct FcgArgs {
+    double* x; double* r; double* p; const double* q; const double* z;
+    const double* pq; int npq;          // partial sums of p.q (SpMV, possibly folded)
+    const double* dots; int nd;         // partial sums of r.z / z.q, interleaved (fcg_dots, possibly folded)
+    double* out;                        // this kernel's partial sums
+    double* vz;                         // fcg_update: also zero these rows (the next cycle's start, MG_VEC_V), or null
+    double* sc; int64_t n;
+};
+
+// sum of part[t * stride], t < np, in a fixed order; the result in every thread of the block
+__device__ __forceinline__ double fcg_sum(const double* part, int np, int stride) {
+    __shared__ double s_tot;
+    double s = 0.0;
+    for (int t = threadIdx.x; t < np; t += blockDim.x) s += part[(int64_t)t * stride];
+    const double r = block_sum(s);
+    if (threadIdx.x == 0) s_tot = r;
+    __syncthreads();
+    const double out = s_tot;
+    __syncthreads();
+    return out;
+}
+
+// np groups of `stride` interleaved partial sums -> gridDim.x groups: block b sums the groups [np b / G, np (b+1) / G)
+__global__ __launch_bounds__(BLOCK) void fcg_fold(const double* __restrict__ in, int64_t np, int stride,
+                                                  double* __restrict__ out) {
+    const int64_t lo = np * blockIdx.x / gridDim.x, hi = np * (blockIdx.x + 1) / gridDim.x;
+    for (int s = 0; s < stride; ++s) {
+        double acc = 0.0;
+        for (int64_t t = lo + threadIdx.x; t < hi; t += blockDim.x) acc += in[t * stride + s];
+        const double r = block_sum(acc);
+        if (threadIdx.x == 0) out[(int64_t)blockIdx.x * stride + s] = r;
+    }
+}
+
+// alpha = (r.z) / (p.q); x += alpha p; r -= alpha q; partial sums of r.r -> out[block]; vz = 0 (8 B/row in this pass
+// instead of a separate fill: z is dead once fcg_direction has run, and the next V-cycle starts from zero)
+__global__ __launch_bounds__(BLOCK) void fcg_update(FcgArgs a) {
+    const double pq = fcg_sum(a.pq, a.npq, 1);
+    const double rz = fcg_sum(a.dots, a.nd, 2);
+    const double alpha = rz / pq;
+    if (blockIdx.x == 0 && threadIdx.x == 0) { a.sc[0] = alpha; a.sc[1] = rz; }
+    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (int64_t)gridDim.x * blockDim.x;
+    double2* X = reinterpret_cast<double2*>(a.x);
+    double2* R = reinterpret_cast<double2*>(a.r);
+    const double2* P = reinterpret_cast<const double2*>(a.p);
+    const double2* Q = reinterpret_cast<const double2*>(a.q);
+    double rr = 0.0;
+    for (int64_t i = tid; i < (a.n >> 1); i += stride) {
+        double2 x = X[i], r = R[i];
+        const double2 p = P[i], q = Q[i];
+        x.x = fma(alpha, p.x, x.x); x.y = fma(alpha, p.y, x.y);
+        r.x = fma(-alpha, q.x, r.x); r.y = fma(-alpha, q.y, r.y);
+        X[i] = x; R[i] = r;
+        if (a.vz) reinterpret_cast<double2*>(a.vz)[i] = make_double2(0.0, 0.0);
+        rr = fma(r.x, r.x, rr); rr = fma(r.y, r.y, rr);
+    }
+    if (tid == 0 && (a.n & 1)) {
+        const int64_t t = a.n - 1;
+        a.x[t] = fma(alpha, a.p[t], a.x[t]);
+        const double r = fma(-alpha, a.q[t], a.r[t]);
+        a.r[t] = r;
+        if (a.vz) a.vz[t] = 0.0;
+        rr = fma(r, r, rr);
+    }
+    const double s = block_sum(rr);
+    if (threadIdx.x == 0) a.out[blockIdx.x] = s;
+}
+
+// partial sums of r.z and z.q -> out[2 block], out[2 block + 1] (HAS_Q = false: the first iteration, no q yet, z.q = 0)
+template <bool HAS_Q>
+__global__ __launch_bounds__(BLOCK) void fcg_dots(FcgArgs a) {
+    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (int64_t)gridDim.x * blockDim.x;
+    const double2* R = reinterpret_cast<const double2*>(a.r);
+    const double2* Z = reinterpret_cast<const double2*>(a.z);
+    const double2* Q = reinterpret_cast<const double2*>(a.q);
+    double rz = 0.0, zq = 0.0;
+    for (int64_t i = tid; i < (a.n >> 1); i += stride) {
+        const double2 r = R[i], z = Z[i];
+        rz = fma(r.x, z.x, rz); rz = fma(r.y, z.y, rz);
+        if (HAS_Q) {
+            const double2 q = Q[i];
+            zq = fma(z.x, q.x, zq); zq = fma(z.y, q.y, zq);
+        }
+    }
+    if (tid == 0 && (a.n & 1)) {
+        const int64_t t = a.n - 1;
+        rz = fma(a.r[t], a.z[t], rz);
+        if (HAS_Q) zq = fma(a.z[t], a.q[t], zq);
+    }
+    const double s1 = block_sum(rz);
+    const double s2 = block_sum(zq);
+    if (threadIdx.x == 0) { a.out[2 * blockIdx.x] = s1; a.out[2 * blockIdx.x + 1] = s2; }
+}
+
+// beta = -alpha (z.q) / (r.z)_old (flexible, Polak-Ribiere: z.(r_new - r_old) / (r.z)_old); p = z + beta p.
+// FIRST: p = z.
+template <bool FIRST>
+__global__ __launch_bounds__(BLOCK) void fcg_direction(FcgArgs a) {
+    double beta = 0.0;
+    if (!FIRST) {
+        const double zq = fcg_sum(a.dots + 1, a.nd, 2);
+        beta = -a.sc[0] * zq / a.sc[1];
+    }
+    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (int64_t)gridDim.x * blockDim.x;
+    double2* P = reinterpret_cast<double2*>(a.p);
+    const double2* Z = reinterpret_cast<const double2*>(a.z);
+    for (int64_t i = tid; i < (a.n >> 1); i += stride) {
+        const double2 z = Z[i];
+        double2 p;
+        if (FIRST) {
+            p = z;
+        } else {
+            p = P[i];
+            p.x = fma(beta, p.x, z.x); p.y = fma(beta, p.y, z.y);
+        }
+        P[i] = p;
+    }
+    if (tid == 0 && (a.n & 1)) {
+        const int64_t t = a.n - 1;
+        a.p[t] = FIRST ? a.z[t] : fma(beta, a.p[t], a.z[t]);
+    }
+}
+
 }  // namespace mgk

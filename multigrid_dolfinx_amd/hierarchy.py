@@ -455,6 +455,17 @@ class DeviceHierarchy:
             return hist[:done.value].copy(), ehist[:done.value].copy()
         return hist[:done.value].copy()
 
+    def pcg(self, rtol: float = 1e-11, max_iter: int = 200, level: Optional[int] = None) -> np.ndarray:
+        """Flexible CG preconditioned by one V(mu1, mu2) cycle per iteration (`mg_pcg`), from "v" on A x = "f" of `level`
+        (default: the finest) until ||r||_2 <= rtol ||f||_2 or `max_iter` iterations (rtol <= 0: exactly that many).
+        Returns ||r_k||_2 of the recursion after every iteration; the iterate is in "v", "f" is unchanged and "r" holds
+        f - A x.  After `fmg(mu0, tol=0)` it starts from the FMG iterate."""
+        level = self.finest_level if level is None else level
+        hist = np.zeros(max(1, int(max_iter)))
+        done = C.c_int()
+        check(self._lib.mg_pcg(self._h, self._idx(level), float(rtol), int(max_iter), ptr(hist), C.byref(done)))
+        return hist[:done.value].copy()
+
     def set_mass(self, level: int, M):
         """The P1 mass matrix of `level` (SciPy CSR, the level's DoF numbering) for the L2(Omega) norms of fmg."""
         indptr, is64, indices, data = _csr_arrays(M)

@@ -409,6 +409,23 @@ def FullMultiGrid_test(A_h, f_h, test=False):
     return out
 
 
+def MultigridPCG(A_h, f_h, v_h=None, rtol=1e-11, max_iter=200):
+    """Solve to a tolerance: flexible conjugate gradients preconditioned by one V(mu1, mu2) cycle of the initialised
+    hierarchy per iteration (`mg_pcg`; no reference counterpart).  Same calling convention as `V_cycle_scheme`: `A_h`
+    selects the level (`A_h[2]`), `f_h` is the right-hand side, `v_h` the start (zero if None).  Stops when the l2 norm of
+    the residual is <= rtol * ||f_h||_2 or after `max_iter` iterations; appends ||r||_2 after every iteration to
+    `residual_per_V_cycle_finest` when that list is not None, as `FullMultiGrid` does.  Returns the `(n, 1)` iterate."""
+    h = _hierarchy()
+    level = A_h[2]
+    f = _column(f_h)
+    h.set_vector(level, "v", np.zeros_like(f) if v_h is None else _column(v_h))
+    h.set_vector(level, "f", f)
+    hist = h.pcg(rtol=rtol, max_iter=max_iter, level=level)
+    if residual_per_V_cycle_finest is not None:
+        residual_per_V_cycle_finest.extend(float(x) for x in hist)
+    return h.get_vector(level, "v")
+
+
 # ---- CSV helpers (multigrid.py:345-356) ---------------------------------------------------------------------------------------
 def writing_residual_for_mesh_to_csv(residual):
     name = (f'residual_for_{coarsest_level_elements_per_dim * 2 ** finest_level}_'
