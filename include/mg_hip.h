@@ -47,7 +47,8 @@ enum mg_vec {
 enum mg_restriction {
     MG_RESTRICT_INJECTION = 0,      /* Restriction2D_direct, multigrid.py:123-132 (the live path, :251-252) */
     MG_RESTRICT_FULL_WEIGHTING = 1, /* Restriction2D,        multigrid.py:135-198                            */
-    MG_RESTRICT_TABLE = 2           /* transpose of the table prolongation (mg_set_restriction_table); no reference */
+    MG_RESTRICT_TABLE = 2,          /* transpose of the table prolongation (mg_set_restriction_table); no reference */
+    MG_RESTRICT_P1_TRANSPOSE = 3    /* R = P^T of the P1 natural embedding (mg_set_prolongation_p1); no reference */
 };
 
 enum mg_smoother {
@@ -180,6 +181,34 @@ int mg_set_prolongation_table(mg_handle h, const int* count /*[64]*/, const int*
  * SURVEY.md App. A Q1).  Whole levels only.  No reference counterpart. */
 int mg_set_restriction_table(mg_handle h, int max_entries, const int* count /*[8]*/, const int* offsets /*[8][max][3]*/,
                              const double* weights /*[8][max]*/);
+/* P1 natural-embedding transfers on the structured simplicial mesh of poisson.py (squares cut along (1, 1), cubes into six
+ * Kuhn simplices; edges along the non-negative p in {0,1}^dim \ {0}).  No reference counterpart: the reference injects
+ * (multigrid.py:123-132) and interpolates bilinearly (Interpolation2D, multigrid.py:59-120), which is not the embedding of the
+ * coarse P1 space.  Results then differ from the reference's on purpose.
+ *   prolongation (enable = 1): fine node 2I + p takes v_c(I) for p = 0 and 0.5 * (v_c(I) + v_c(I + p)) otherwise, with the
+ *     ERR / add semantics of mg_prolong.  It and a prolongation table exclude each other: setting one clears the other
+ *     (enable = 0: back to the reference's interpolation, or to whatever table is set afterwards).
+ *   restriction MG_RESTRICT_P1_TRANSPOSE (mg_set_params / mg_restrict): R = P^T -- an interior coarse node I sums
+ *     w * r_f(2I + d) over d in {0} U +-dirs (w = 1 for d = 0, 0.5 otherwise), multiplied first, then added in ascending fine
+ *     lexicographic order (the convention of MG_RESTRICT_TABLE, which gives the same bits fed poisson.p1_restriction_table);
+ *     boundary coarse nodes take the coincident fine value.
+ * Both check at first use that the stencils of the levels involved lie in that Kuhn pattern: a level that couples other
+ * nodes (a mesh cut the other way with its zero couplings kept, P2 rows) is refused with an error, on slabs by every rank
+ * together.  A matrix with its zeros pruned cannot show how the mesh was cut: the 2-D Poisson matrices of both diagonal
+ * directions have the same five-point stencil, pass the check, and the transfers are then those of poisson.py's mesh.
+ * Slabs: the same halos as the Q1 interpolation / full weighting (halo_planes = 1). */
+int mg_set_prolongation_p1(mg_handle h, int enable);
+/* Galerkin coarse level: sets level - 1's matrix to P^T A_level P with the P1 embedding above, P restricted to interior fine
+ * and interior coarse nodes, plus identity rows on the boundary, as the handed-over levels have.  Computed on the device by
+ * one thread per coarse row from the fine level's storage, whichever format it has; entries summed in a fixed order (fine
+ * rows of P's column, then their entries, in ascending lexicographic order), so repeated calls are bit-identical.  Nothing
+ * is flushed to zero, but exact zeros are dropped as prune_zeros does.  The coarse level then gets the storage analysis of
+ * mg_set_level_csr (symmetric diagonals, offset codes, row classes, "storage_auto").  Needs a whole (not slab) grid level
+ * with an even elements_per_dim and a stencil in the Kuhn pattern.  Level - 1 is rebuilt from scratch: its vectors cross in
+ * lexicographic numbering and start at zero, and mg_fmg on it needs mg_set_rhs_true again.  No reference counterpart.
+ * mg_galerkin_hierarchy applies it from top_level down to level 1. */
+int mg_galerkin_level(mg_handle h, int level);
+int mg_galerkin_hierarchy(mg_handle h, int top_level);
 /* Tuning and format knobs (defaults in parentheses; DESIGN.md sections 4-6 explain each):
  *   before any level is set:
  *     "rows_per_lane"      1 | 2 | 4 rows of a slice per lane (2)

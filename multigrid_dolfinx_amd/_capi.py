@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmg_hip.so")
 
 MG_VEC_V, MG_VEC_F, MG_VEC_R, MG_VEC_ERR = 0, 1, 2, 3
-MG_RESTRICT_INJECTION, MG_RESTRICT_FULL_WEIGHTING, MG_RESTRICT_TABLE = 0, 1, 2
+MG_RESTRICT_INJECTION, MG_RESTRICT_FULL_WEIGHTING, MG_RESTRICT_TABLE, MG_RESTRICT_P1_TRANSPOSE = 0, 1, 2, 3
 MG_SMOOTH_JACOBI, MG_SMOOTH_RBGS, MG_SMOOTH_MCGS = 0, 1, 2
 MG_NORM_L2, MG_NORM_MASS = 0, 1
 # enum mg_smoother_path, in its order (mg_smoother_launches)
@@ -56,6 +56,9 @@ SIGNATURES = {
     "mg_set_tuning": [_H, C.c_char_p, C.c_int64],
     "mg_set_prolongation_table": [_H, C.c_void_p, C.c_void_p, C.c_void_p],
     "mg_set_restriction_table": [_H, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
+    "mg_set_prolongation_p1": [_H, C.c_int],
+    "mg_galerkin_level": [_H, C.c_int],
+    "mg_galerkin_hierarchy": [_H, C.c_int],
     "mg_level_info": [_H, C.c_int, _i64p, _i64p, _i64p, _i64p, _i64p, _ip, _ip, _ip],
     "mg_level_row_classes": [_H, C.c_int, _ip],
     "mg_level_storage": [_H, C.c_int, _ip, _i64p, _i64p, _ip, _ip, _i64p],

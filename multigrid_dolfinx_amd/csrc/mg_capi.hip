@@ -179,6 +179,8 @@ struct Level {
     DVector sw;                             // once-relaxed boundary planes of a slab (paired sweeps, world > 1)
     DVector fcg_x, fcg_p, fcg_q, fcg_b;     // mg_pcg on this level: iterate, direction, A p, the saved right-hand side
     int* perm = nullptr;
+    int p1_ok = -1;                         // stencil offsets within the Kuhn pattern of the P1 transfers (-1: not checked yet)
+    std::vector<int> h_offsets;             // the offset table (linear offsets) of an offset-coded level, host copy
     unsigned long long nnz_stored = 0, nnz_nonzero = 0;
     // per-rank plane ownership (for gathers): k-plane boundaries s[0..world]
     std::vector<int> splits;
@@ -329,6 +331,7 @@ struct mg_context {
     // matrix M of one level (mg_set_mass_csr), optionally the exact solution's nodal values (mg_set_exact)
     // table prolongation (mg_set_prolongation_table; null: the reference's bilinear / trilinear interpolation)
     int* ptab_count = nullptr;
+    int p1_prolong = 0;                     // mg_set_prolongation_p1: the P1 natural embedding (excludes the table)
     int* rtab_count = nullptr;              // table restriction (mg_set_restriction_table), MG_RESTRICT_TABLE
     int* rtab_off = nullptr;
     double* rtab_w = nullptr;
@@ -405,6 +408,19 @@ void vec_free(mg_context* c, const Level& L, DVector* v) {
         v->base = v->rows = nullptr;
     }
 }
+
+// Temporary device buffer that frees itself (set-up paths have many early exits).
+struct DevTemp {
+    void* p = nullptr;
+    DevTemp() = default;
+    DevTemp(const DevTemp&) = delete;
+    DevTemp& operator=(const DevTemp&) = delete;
+    ~DevTemp() { if (p) (void)hipFree(p); }
+    int alloc(size_t bytes) {
+        HIP_TRY(hipMalloc(&p, std::max<size_t>(1, bytes)));
+        return 0;
+    }
+};
 
 inline unsigned blocks_for(int64_t n, int per_block) { return (unsigned)((n + per_block - 1) / per_block); }
 
@@ -540,6 +556,8 @@ void free_level(mg_context* c, Level& L) {
     L.coded = false;
     L.rb_ok = false;
     L.mc_ok = -1;
+    L.p1_ok = -1;
+    L.h_offsets.clear();
     L.sdia = false;
     dev_free(c, L.dinv, (size_t)L.nslices * WAVE * L.R);
     dev_free(c, L.perm, (size_t)L.n_global);
@@ -2050,6 +2068,68 @@ Grid coarse_target_grid(const mg_context* c, const Level& C, const Level& F) {
     return g;
 }
 
+// The Kuhn pattern of the P1 transfers as linear offsets on level L (kuhn_off order; dj = 0 in 2-D).
+int kuhn_lin(const mg_context* c, const Level& L, int64_t* lin) {
+    const int K = c->dim == 3 ? 15 : 7;
+    for (int t = 0; t < K; ++t) {
+        const int di = c->dim == 3 ? kuhn_off<3>(t, 0) : kuhn_off<2>(t, 0), dj = c->dim == 3 ? kuhn_off<3>(t, 1) : 0;
+        const int dk = c->dim == 3 ? kuhn_off<3>(t, 2) : kuhn_off<2>(t, 2);
+        lin[t] = di + (int64_t)dj * L.g.nx + (int64_t)dk * L.g.plane;
+    }
+    return K;
+}
+
+// The P1 transfers and the Galerkin product assume the mesh of poisson.py: a level whose matrix couples a node to anything
+// but its Kuhn neighbours (a mesh cut the other way whose zero couplings were kept, P2 rows) is refused.  A pruned matrix
+// cannot show how the mesh was cut: the Poisson matrices of both 2-D orientations have the same five-point stencil and pass.
+// Levels without a matrix pass.  On slabs the ranks' verdicts are all-reduced (every rank checks the same levels in the same
+// order), so all of them refuse together.  Synchronises for int32-column levels and slabs (prepare_cycle runs it before a
+// V-cycle is captured).
+int check_p1_stencil(mg_context* c, Level& L) {
+    if (L.p1_ok < 0) {
+        int64_t lin[15];
+        const int K = kuhn_lin(c, L, lin);
+        auto in = [&](int64_t o) { return std::find(lin, lin + K, o) != lin + K; };
+        bool ok = true;
+        if (!L.has_matrix) {
+        } else if (L.flat) {
+            ok = false;
+        } else if (L.sdia) {
+            for (int t = 1; t < 8; ++t) ok = ok && (L.up[t] == 0 || in(L.up[t]));
+        } else if (L.coded) {
+            for (int o : L.h_offsets) ok = ok && in(o);
+        } else {
+            DevTemp d_lin;
+            MG_TRY(d_lin.alloc(sizeof(lin)));
+            int* flag = reinterpret_cast<int*>(c->partials);
+            HIP_TRY(hipMemcpyAsync(d_lin.p, lin, sizeof(lin), hipMemcpyHostToDevice, c->stream));
+            HIP_TRY(hipMemsetAsync(flag, 0, sizeof(int), c->stream));
+            hipLaunchKernelGGL(p1_pattern_check, dim3(blocks_for(L.nloc, 256)), dim3(256), 0, c->stream, L.cols, L.nloc, L.W, L.R,
+                               L.g.lead, static_cast<const int64_t*>(d_lin.p), K, flag);
+            HIP_TRY(hipGetLastError());
+            int h = 1;
+            HIP_TRY(hipMemcpyAsync(&h, flag, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(hipStreamSynchronize(c->stream));
+            ok = h == 0;
+        }
+        if (!L.replicated && c->comm.active()) {
+            // one verdict for every rank: a rank that refused alone would leave the others waiting in the next exchange
+            double bad = ok ? 0.0 : 1.0;
+            double* d_bad = reinterpret_cast<double*>(c->partials);
+            HIP_TRY(hipMemcpyAsync(d_bad, &bad, sizeof(double), hipMemcpyHostToDevice, c->stream));
+            MG_TRY(allreduce_sum(c, d_bad, 1));
+            HIP_TRY(hipMemcpyAsync(&bad, d_bad, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(hipStreamSynchronize(c->stream));
+            ok = bad == 0.0;
+        }
+        L.p1_ok = ok ? 1 : 0;
+    }
+    if (!L.p1_ok)
+        return fail("the P1 transfers need levels whose stencil lies in the Kuhn pattern of the structured simplicial mesh "
+                    "(poisson._offsets: squares cut along (1, 1), cubes into six Kuhn simplices); this level couples other nodes");
+    return 0;
+}
+
 int restrict_to(mg_context* c, int level, int kind) {
     Level& F = c->L[level];
     Level& C = c->L[level - 1];
@@ -2063,6 +2143,14 @@ int restrict_to(mg_context* c, int level, int kind) {
         }
         const RestrictTable t{c->rtab_count, c->rtab_off, c->rtab_w, c->rtab_m};
         hipLaunchKernelGGL(restrict_table, grid3(gc, gc.nk), dim3(kPlaneBlock), 0, c->stream, gc, F.g, t, F.v2.base, C.f.base);
+    } else if (kind == MG_RESTRICT_P1_TRANSPOSE) {
+        MG_TRY(check_p1_stencil(c, F));
+        MG_TRY(check_p1_stencil(c, C));
+        MG_TRY(exchange_halo(c, F, F.v2));          // (the same fine planes as full weighting)
+        if (c->dim == 3)
+            hipLaunchKernelGGL(restrict_p1t<3>, grid3(gc, gc.nk), dim3(kPlaneBlock), 0, c->stream, gc, F.g, F.v2.base, C.f.base);
+        else
+            hipLaunchKernelGGL(restrict_p1t<2>, grid3(gc, gc.nk), dim3(kPlaneBlock), 0, c->stream, gc, F.g, F.v2.base, C.f.base);
     } else if (kind == MG_RESTRICT_FULL_WEIGHTING) {
         MG_TRY(exchange_halo(c, F, F.v2));
         hipLaunchKernelGGL(restrict_full_weighting, grid3(gc, gc.nk), dim3(kPlaneBlock), 0, c->stream, gc, F.g, F.v2.base,
@@ -2105,6 +2193,21 @@ int prolong(mg_context* c, int level, int add) {
     Level& C = c->L[level - 1];
     const bool keep = !add || c->keep_err;
     if (keep) MG_TRY(vec_alloc(c, F, &F.err));
+    if (c->p1_prolong) {
+        // the coarse planes K and K + 1, as the Q1 interpolation reads them
+        MG_TRY(check_p1_stencil(c, F));
+        MG_TRY(check_p1_stencil(c, C));
+        const dim3 grid = grid3(F.g, F.g.nk), blk(kPlaneBlock);
+        if (add && keep)
+            hipLaunchKernelGGL((prolong_p1<true, true>), grid, blk, 0, c->stream, C.g, F.g, C.v.base, F.v.base, F.err.base);
+        else if (add)
+            hipLaunchKernelGGL((prolong_p1<true, false>), grid, blk, 0, c->stream, C.g, F.g, C.v.base, F.v.base, (double*)nullptr);
+        else
+            hipLaunchKernelGGL((prolong_p1<false, true>), grid, blk, 0, c->stream, C.g, F.g, C.v.base, F.v.base, F.err.base);
+        HIP_TRY(hipGetLastError());
+        if (add) MG_TRY(exchange_halo(c, F, F.v));
+        return 0;
+    }
     if (c->ptab_count) {
         if (!F.replicated && c->comm.active() && c->halo_planes < 2)
             return fail("the table prolongation reaches two coarse planes: halo_planes must be 2 on slabs");
@@ -2426,6 +2529,8 @@ int prepare_cycle(mg_context* c, int level) {
             }
     if (c->keep_err)
         for (int l = 1; l <= level; ++l) MG_TRY(vec_alloc(c, c->L[l], &c->L[l].err));
+    if (c->p1_prolong || c->restriction == MG_RESTRICT_P1_TRANSPOSE)       // (may synchronise: not inside a capture)
+        for (int l = 0; l <= level; ++l) MG_TRY(check_p1_stencil(c, c->L[l]));
     return 0;
 }
 
@@ -2676,6 +2781,7 @@ int encode_level(mg_context* c, Level& L) {
     if (zero == offs.end()) return fail("offset table lacks the diagonal");
     L.ntable = (int)offs.size();
     L.dcode = (int)(zero - offs.begin());
+    L.h_offsets = offs;
     L.rb_ok = !L.flat && (L.g.nx & 1) && (L.g.ny & 1);
     for (int o : offs)
         if (o != 0 && (o & 1) == 0) L.rb_ok = false;       // a coupling inside one colour
@@ -3237,7 +3343,8 @@ int mg_set_params(mg_handle c, int mu1, int mu2, double omega, int restriction, 
                   int coarse_maxit, int keep_err) {
     if (!c) return fail("null handle");
     if (mu1 < 0 || mu2 < 0) return fail("mu1/mu2 must be >= 0");
-    if (restriction != MG_RESTRICT_INJECTION && restriction != MG_RESTRICT_FULL_WEIGHTING && restriction != MG_RESTRICT_TABLE)
+    if (restriction != MG_RESTRICT_INJECTION && restriction != MG_RESTRICT_FULL_WEIGHTING && restriction != MG_RESTRICT_TABLE &&
+        restriction != MG_RESTRICT_P1_TRANSPOSE)
         return fail("unknown restriction");
     if (smoother != MG_SMOOTH_JACOBI && smoother != MG_SMOOTH_RBGS && smoother != MG_SMOOTH_MCGS) return fail("unknown smoother");
     const double rtol = coarse_rtol > 0 ? coarse_rtol : c->coarse_rtol;
@@ -3261,6 +3368,7 @@ int mg_set_prolongation_table(mg_handle c, const int* count, const int* offsets,
     (void)hipStreamSynchronize(c->stream);
     (void)hipFree(c->ptab_count); (void)hipFree(c->ptab_off); (void)hipFree(c->ptab_w);
     c->ptab_count = nullptr; c->ptab_off = nullptr; c->ptab_w = nullptr;
+    c->p1_prolong = 0;                                            // (a table and the P1 embedding exclude each other)
     if (!count && !offsets && !weights) return 0;                 // back to the reference's interpolation
     if (!count || !offsets || !weights) return fail("null table");
     for (int r = 0; r < 64; ++r) {
@@ -3275,6 +3383,20 @@ int mg_set_prolongation_table(mg_handle c, const int* count, const int* offsets,
     HIP_TRY(hipMemcpy(c->ptab_count, count, 64 * sizeof(int), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(c->ptab_off, offsets, 64 * 10 * 3 * sizeof(int), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(c->ptab_w, weights, 64 * 10 * sizeof(double), hipMemcpyHostToDevice));
+    return 0;
+}
+
+int mg_set_prolongation_p1(mg_handle c, int enable) {
+    if (!c) return fail("null handle");
+    if (enable != 0 && enable != 1) return fail("enable must be 0 or 1");
+    HIP_TRY(hipSetDevice(c->device));
+    ++c->epoch;
+    if (enable && c->ptab_count) {                                // a table and the P1 embedding exclude each other
+        (void)hipStreamSynchronize(c->stream);
+        (void)hipFree(c->ptab_count); (void)hipFree(c->ptab_off); (void)hipFree(c->ptab_w);
+        c->ptab_count = nullptr; c->ptab_off = nullptr; c->ptab_w = nullptr;
+    }
+    c->p1_prolong = enable;
     return 0;
 }
 
@@ -3513,19 +3635,6 @@ int mg_set_tuning(mg_handle c, const char* key, int64_t value) {
 
 namespace {
 
-// Temporary device buffer that frees itself (set-up paths have many early exits).
-struct DevTemp {
-    void* p = nullptr;
-    DevTemp() = default;
-    DevTemp(const DevTemp&) = delete;
-    DevTemp& operator=(const DevTemp&) = delete;
-    ~DevTemp() { if (p) (void)hipFree(p); }
-    int alloc(size_t bytes) {
-        HIP_TRY(hipMalloc(&p, std::max<size_t>(1, bytes)));
-        return 0;
-    }
-};
-
 // grid_index[dof] (int64, caller) -> L.perm (int32, device), validated as a permutation of the nodes.
 int upload_permutation(mg_context* c, Level& L, const int64_t* grid_index, int64_t n_rows) {
     if (!grid_index) return 0;
@@ -3547,16 +3656,22 @@ int upload_permutation(mg_context* c, Level& L, const int64_t* grid_index, int64
 // otherwise rows and columns are global DoF numbers and `grid_index` (or the identity) maps them to nodes.
 int build_level_from_csr(mg_context* c, int level, Level& L, int64_t n_rows, int64_t nnz, const void* indptr,
                          int indptr_is_64, const int32_t* indices, const double* data, const int64_t* grid_index,
-                         int prune_zeros, bool vectors = true, const int64_t* local_cols = nullptr, int64_t n_cols = 0) {
-    // upload the hand-off
+                         int prune_zeros, bool vectors = true, const int64_t* local_cols = nullptr, int64_t n_cols = 0,
+                         bool device_csr = false) {
+    // upload the hand-off (device_csr: the three arrays are device memory already -- mg_galerkin_level)
     DevTemp d_ptr, d_idx, d_val;
     const size_t ptr_bytes = (size_t)(n_rows + 1) * (indptr_is_64 ? 8 : 4);
-    MG_TRY(d_ptr.alloc(ptr_bytes));
-    MG_TRY(d_idx.alloc((size_t)nnz * 4));
-    MG_TRY(d_val.alloc((size_t)nnz * 8));
-    HIP_TRY(hipMemcpyAsync(d_ptr.p, indptr, ptr_bytes, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(d_idx.p, indices, (size_t)nnz * 4, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(d_val.p, data, (size_t)nnz * 8, hipMemcpyHostToDevice, c->stream));
+    if (!device_csr) {
+        MG_TRY(d_ptr.alloc(ptr_bytes));
+        MG_TRY(d_idx.alloc((size_t)nnz * 4));
+        MG_TRY(d_val.alloc((size_t)nnz * 8));
+        HIP_TRY(hipMemcpyAsync(d_ptr.p, indptr, ptr_bytes, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(d_idx.p, indices, (size_t)nnz * 4, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(d_val.p, data, (size_t)nnz * 8, hipMemcpyHostToDevice, c->stream));
+    }
+    const void* const dp_ptr = device_csr ? indptr : d_ptr.p;
+    const void* const dp_idx = device_csr ? static_cast<const void*>(indices) : d_idx.p;
+    const void* const dp_val = device_csr ? static_cast<const void*>(data) : d_val.p;
     DevTemp d_map;
     if (local_cols) {
         // vectors keep crossing in the caller's GLOBAL numbering (grid_index, n_global entries); the matrix kernels see the
@@ -3583,7 +3698,7 @@ int build_level_from_csr(mg_context* c, int level, Level& L, int64_t n_rows, int
         MG_TRY(upload_permutation(c, L, grid_index, n_rows));
     }
     CsrArgs a{};
-    a.indptr = d_ptr.p; a.indptr64 = indptr_is_64; a.indices = static_cast<const int*>(d_idx.p); a.data = static_cast<const double*>(d_val.p);
+    a.indptr = dp_ptr; a.indptr64 = indptr_is_64; a.indices = static_cast<const int*>(dp_idx); a.data = static_cast<const double*>(dp_val);
     a.perm = local_cols ? static_cast<const int*>(d_map.p) : L.perm;
     a.n = n_rows; a.row0 = L.row0; a.nloc = L.nloc; a.lead = L.g.lead; a.xlen = L.xlen;
     a.prune = prune_zeros;
@@ -3610,7 +3725,7 @@ int build_level_from_csr(mg_context* c, int level, Level& L, int64_t n_rows, int
     HIP_TRY(hipGetLastError());
     // true non-zeros among the kept entries (== kept when pruned); counted on the caller's copy (set-up only)
     L.nnz_nonzero = L.nnz_stored;
-    if (!prune_zeros && (!c->comm.active() || L.replicated) && !local_cols) {
+    if (!prune_zeros && (!c->comm.active() || L.replicated) && !local_cols && !device_csr) {
         unsigned long long nz = 0;
         for (int64_t q = 0; q < nnz; ++q) nz += data[q] != 0.0;
         L.nnz_nonzero = nz;
@@ -3622,6 +3737,91 @@ int build_level_from_csr(mg_context* c, int level, Level& L, int64_t n_rows, int
     L.has_matrix = true;
     if (!vectors) { L.set = true; return 0; }
     return finish_level(c, L);
+}
+
+// Galerkin coarse level: level - 1's matrix = P^T A_level P on the interior nodes (identity rows on the boundary), computed on
+// the device from the fine level's storage and handed to the CSR builder as device arrays (K entries per row, exact zeros
+// dropped): the coarse level then gets the same storage analysis as any handed-over level.
+extern "C++" {
+template <int DIM>
+int launch_galerkin(mg_context* c, int fmt, const GalerkinArgs& a, dim3 grid) {
+    switch (fmt) {
+        case 0: hipLaunchKernelGGL((galerkin_p1<DIM, 0>), grid, dim3(kPlaneBlock), 0, c->stream, a); break;
+        case 1: hipLaunchKernelGGL((galerkin_p1<DIM, 1>), grid, dim3(kPlaneBlock), 0, c->stream, a); break;
+        case 2: hipLaunchKernelGGL((galerkin_p1<DIM, 2>), grid, dim3(kPlaneBlock), 0, c->stream, a); break;
+        default: hipLaunchKernelGGL((galerkin_p1<DIM, 3>), grid, dim3(kPlaneBlock), 0, c->stream, a); break;
+    }
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+}  // extern "C++"
+
+int galerkin_level(mg_context* c, int level) {
+    if (level < 1) return fail("mg_galerkin_level: level must be >= 1 (it sets level - 1)");
+    MG_TRY(need_matrix(c, level));
+    MG_TRY(need_grid(c, level));
+    Level& F = c->L[level];
+    if (!F.replicated) return fail("Galerkin coarse levels need a whole fine level, not a slab");
+    if (F.N < 2 || (F.N & 1)) return fail("Galerkin coarse levels need an even elements_per_dim");
+    MG_TRY(check_p1_stencil(c, F));
+    GalerkinArgs a{};
+    a.gf = F.g;
+    a.R = F.R; a.W = F.W; a.lead = F.g.lead;
+    const int K = kuhn_lin(c, F, a.flin);
+    for (int q = 0; q < 15; ++q) a.code[q] = a.diag[q] = a.tpos[q] = -1;
+    int fmt = 0;
+    if (cls_full(F)) {
+        fmt = 3;
+        a.cls = F.cls + F.cls_lead; a.ctab = F.ctab;
+    } else if (F.sdia) {
+        fmt = 2;
+        a.dvals = F.dvals; a.wu = F.wu; a.mlead = F.mlead;
+    } else if (F.coded) {
+        fmt = 1;
+        a.vals = F.vals; a.codes = F.codes;
+        for (int q = 0; q < K; ++q) {
+            const auto it = std::find(F.h_offsets.begin(), F.h_offsets.end(), (int)a.flin[q]);
+            if (it != F.h_offsets.end()) a.code[q] = (int)(it - F.h_offsets.begin());
+        }
+    } else {
+        a.vals = F.vals; a.cols = F.cols;
+    }
+    if (fmt >= 2)
+        for (int q = 0; q < K; ++q) {
+            const int64_t o = std::llabs(a.flin[q]);
+            for (int t = 0; t < 8 && a.diag[q] < 0; ++t)
+                if ((t == 0 && o == 0) || (t > 0 && o != 0 && F.up[t] == o)) a.diag[q] = t;
+            if (a.diag[q] >= 0) a.tpos[q] = 3 + (a.flin[q] < 0 ? -a.diag[q] : a.diag[q]);
+        }
+    Level& C = c->L[level - 1];
+    free_level(c, C);
+    int rc = [&]() -> int {
+        MG_TRY(setup_geometry(c, C, level - 1, F.N / 2));
+        if (!C.replicated) return fail("Galerkin coarse levels need a whole coarse level");
+        const int64_t n = C.n_global, nnz = n * K;
+        DevTemp d_ptr, d_idx, d_val;
+        MG_TRY(d_ptr.alloc((size_t)(n + 1) * 8));
+        MG_TRY(d_idx.alloc((size_t)nnz * 4));
+        MG_TRY(d_val.alloc((size_t)nnz * 8));
+        a.gc = C.g;
+        a.indptr = static_cast<int64_t*>(d_ptr.p); a.indices = static_cast<int*>(d_idx.p); a.data = static_cast<double*>(d_val.p);
+        a.flag = reinterpret_cast<int*>(c->partials);
+        HIP_TRY(hipMemsetAsync(a.flag, 0, sizeof(int), c->stream));
+        const dim3 grid = grid3(C.g, C.g.nk);
+        MG_TRY(c->dim == 3 ? launch_galerkin<3>(c, fmt, a, grid) : launch_galerkin<2>(c, fmt, a, grid));
+        int flag = 0;
+        HIP_TRY(hipMemcpyAsync(&flag, a.flag, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        if (flag) return fail("a Galerkin entry falls outside the coarse Kuhn pattern");
+        return build_level_from_csr(c, level - 1, C, n, nnz, d_ptr.p, 1, static_cast<const int32_t*>(d_idx.p),
+                                    static_cast<const double*>(d_val.p), nullptr, 1, true, nullptr, 0, true);
+    }();
+    if (rc) {
+        const std::string why = g_err;
+        free_level(c, C);
+        g_err = why;
+    }
+    return rc;
 }
 
 }  // namespace
@@ -3700,6 +3900,19 @@ int mg_set_level_grid(mg_handle c, int level, int N, int64_t n_rows, const int64
         g_err = why;
     }
     return rc;
+}
+
+int mg_galerkin_level(mg_handle c, int level) {
+    MG_TRY(check_level(c, level));
+    HIP_TRY(hipSetDevice(c->device));
+    return galerkin_level(c, level);
+}
+
+int mg_galerkin_hierarchy(mg_handle c, int top_level) {
+    MG_TRY(check_level(c, top_level));
+    HIP_TRY(hipSetDevice(c->device));
+    for (int l = top_level; l >= 1; --l) MG_TRY(galerkin_level(c, l));
+    return 0;
 }
 
 int mg_gen_poisson_level(mg_handle c, int level, int N, int prune_zeros) {
@@ -3996,7 +4209,9 @@ int mg_restrict(mg_handle c, int level, int kind) {
     if (level == 0) return fail("level 0 has no coarser level");
     MG_TRY(need_grid(c, level));
     MG_TRY(need_grid(c, level - 1));
-    if (kind != MG_RESTRICT_INJECTION && kind != MG_RESTRICT_FULL_WEIGHTING && kind != MG_RESTRICT_TABLE) return fail("unknown restriction");
+    if (kind != MG_RESTRICT_INJECTION && kind != MG_RESTRICT_FULL_WEIGHTING && kind != MG_RESTRICT_TABLE &&
+        kind != MG_RESTRICT_P1_TRANSPOSE)
+        return fail("unknown restriction");
     HIP_TRY(hipSetDevice(c->device));
     return restrict_to(c, level, kind);
 }

@@ -1570,6 +1570,214 @@ __global__ void restrict_table(Grid gc, Grid gf, RestrictTable t, const double* 
     fc[gc.lead + (int64_t)kl * gc.plane + (int64_t)j * gc.nx + i] = s;
 }
 
+// ---- P1 natural embedding and its transpose (mg_set_prolongation_p1, MG_RESTRICT_P1_TRANSPOSE; no reference counterpart) --
+// The structured simplicial mesh of poisson.py: every cube cut into six Kuhn simplices, every square along (1, 1) (device
+// axes (i, k) in 2-D).  Its edges run along the non-negative p in {0,1}^dim \ {0}, so every fine node 2I + p is a coarse node
+// (p = 0) or the midpoint of the coarse edge (I, I + p).  kuhn_off<DIM>(t): the pattern {0} U +-dirs as (di, dj, dk) in
+// ascending lexicographic order (dk, then dj, then di): 15 offsets in 3-D, 7 in 2-D -- the P1 matrix stencil, poisson._offsets.
+template <int DIM> struct Kuhn { static constexpr int K = DIM == 3 ? 15 : 7; static constexpr int C = K / 2; };
+
+template <int DIM>
+__host__ __device__ constexpr int kuhn_off(int t, int d) {
+    constexpr int o3[15][3] = {{-1, -1, -1}, {0, -1, -1}, {-1, 0, -1}, {0, 0, -1}, {-1, -1, 0}, {0, -1, 0}, {-1, 0, 0}, {0, 0, 0},
+                               {1, 0, 0},    {0, 1, 0},   {1, 1, 0},   {0, 0, 1},  {1, 0, 1},   {0, 1, 1},  {1, 1, 1}};
+    constexpr int o2[7][3] = {{-1, 0, -1}, {0, 0, -1}, {-1, 0, 0}, {0, 0, 0}, {1, 0, 0}, {0, 0, 1}, {1, 0, 1}};
+    return DIM == 3 ? o3[t][d] : o2[t][d];
+}
+
+// index of (di, dj, dk) in kuhn_off, -1 if it is not in the pattern
+template <int DIM>
+__host__ __device__ constexpr int kuhn_slot(int di, int dj, int dk) {
+    for (int t = 0; t < Kuhn<DIM>::K; ++t)
+        if (kuhn_off<DIM>(t, 0) == di && kuhn_off<DIM>(t, 1) == dj && kuhn_off<DIM>(t, 2) == dk) return t;
+    return -1;
+}
+
+// Prolongation: v_f(2I + p) = v_c(I) for p = 0, 0.5 * (v_c(I) + v_c(I + p)) otherwise.  One thread per fine node; reads the
+// coarse planes K and K + 1 (as prolong_correct).  ERR written when KEEP, V += ERR when ADD.
+template <bool ADD, bool KEEP>
+__global__ void prolong_p1(Grid gc, Grid gf, const double* __restrict__ vc, double* __restrict__ vf, double* __restrict__ err) {
+    int i, j;
+    if (!plane_node(gf, &i, &j)) return;
+    const int kl = blockIdx.y;
+    const int k = gf.k0 + kl;
+    const int pi = i & 1, pj = gf.refine_y ? (j & 1) : 0, pk = k & 1;
+    const int jc = gf.refine_y ? (j >> 1) : j;
+    const double* q = vc + gc.lead + (int64_t)((k >> 1) - gc.k0) * gc.plane + (int64_t)jc * gc.nx + (i >> 1);
+    const double a = q[0];
+    const double b = q[(int64_t)pk * gc.plane + (int64_t)pj * gc.nx + pi];     // (= a on coarse nodes)
+    const double s = (pi | pj | pk) ? 0.5 * (a + b) : a;
+    const int64_t o = gf.lead + (int64_t)kl * gf.plane + (int64_t)j * gf.nx + i;
+    if (KEEP) err[o] = s;
+    if (ADD) vf[o] = vf[o] + s;
+}
+
+// Restriction R = P^T, gathered per coarse node: an interior coarse node I sums w * r_f(2I + d) over the Kuhn pattern d in
+// ascending fine lexicographic order, w = 1 for d = 0 and 0.5 otherwise, multiply then add (the order of MG_RESTRICT_TABLE
+// fed poisson.p1_restriction_table).  Every such 2I + d is an interior fine node.  Boundary coarse nodes take the coincident
+// fine value.  Reads the fine planes 2K - 1 .. 2K + 1 (as full weighting).
+template <int DIM>
+__global__ void restrict_p1t(Grid gc, Grid gf, const double* __restrict__ rf, double* __restrict__ fc) {
+    int i, j;
+    if (!plane_node(gc, &i, &j)) return;
+    const int kl = blockIdx.y;
+    const int K = gc.k0 + kl;
+    const int fj = DIM == 3 ? 2 * j : j;
+    const double* q = rf + gf.lead + (int64_t)(2 * K - gf.k0) * gf.plane + (int64_t)fj * gf.nx + 2 * i;
+    const bool bnd = i == 0 || i == gc.nx - 1 || K == 0 || K == gc.nz - 1 || (DIM == 3 && (j == 0 || j == gc.ny - 1));
+    double s = q[0];
+    if (!bnd) {
+        double v[Kuhn<DIM>::K];
+#pragma unroll
+        for (int t = 0; t < Kuhn<DIM>::K; ++t)
+            v[t] = q[(int64_t)kuhn_off<DIM>(t, 2) * gf.plane + (int64_t)kuhn_off<DIM>(t, 1) * gf.nx + kuhn_off<DIM>(t, 0)];
+#pragma unroll
+        for (int t = 0; t < Kuhn<DIM>::K; ++t) {
+            const double term = (t == Kuhn<DIM>::C ? 1.0 : 0.5) * v[t];
+            s = t == 0 ? term : s + term;
+        }
+    }
+    fc[gc.lead + (int64_t)kl * gc.plane + (int64_t)j * gc.nx + i] = s;
+}
+
+// Stencil check of levels kept with int32 columns: flag = 1 if an entry's column is not the row plus a Kuhn offset
+// (lin[t]: the pattern as linear offsets on this level).
+__global__ void p1_pattern_check(const int* __restrict__ cols, int64_t nloc, int W, int R, int64_t lead, const int64_t* lin, int K,
+                                 int* flag) {
+    const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= nloc) return;
+    const int64_t S = (int64_t)WAVE * R;
+    const size_t base = (size_t)(r / S) * W * S + (size_t)(r % S);
+    for (int k = 0; k < W; ++k) {
+        const int64_t d = (int64_t)cols[base + (size_t)k * S] - lead - r;
+        bool ok = false;
+        for (int t = 0; t < K; ++t) ok = ok || d == lin[t];
+        if (!ok) atomicOr(flag, 1);
+    }
+}
+
+// ---- Galerkin coarse level P^T A P (mg_galerkin_level) ---------------------------------------------------------------
+// One coarse row per thread.  Interior coarse row I: for every fine row a = 2I + da of P's column I (da in kuhn_off order,
+// weight w_a = 1 for da = 0 and 0.5 otherwise), every entry A(a, b) of that row in kuhn_off order with b an interior fine node,
+// and every coarse node J whose basis function is non-zero at b (J = b / 2 with weight 1, or the ends of the coarse edge
+// through b with 0.5 each, lower one first) that is an interior coarse node: acc[J - I] += (w_a * A(a, b)) * w_J.  That
+// order is fixed: repeated calls are bit-identical.  Nothing is flushed to zero.  Boundary coarse rows: identity.  Output:
+// K (col, value) slots per row in ascending column order as a CSR with K entries per row; slots without an interior J hold
+// (own column, 0.0), which the CSR builder drops with the other exact zeros (prune_zeros).
+// The fine matrix is read from whatever storage the level has: FMT 0 int32 columns, 1 offset codes, 2 symmetric diagonals,
+// 3 row classes.
+struct GalerkinArgs {
+    Grid gc, gf;                        // whole levels
+    const double* vals; const int* cols; const unsigned long long* codes;   // FMT 0 / 1: sliced ELL (W entries, R rows per lane)
+    int W, R;
+    int64_t lead;
+    int code[15];                       // FMT 1: code of each Kuhn offset (-1: not in the table)
+    const double* dvals; int wu; int64_t mlead;                             // FMT 2
+    int diag[15];                       // FMT 2: stored diagonal of each Kuhn offset (-1: none)
+    const unsigned char* cls; const double* ctab;                           // FMT 3: class byte of row r at cls[r]
+    int tpos[15];                       // FMT 3: position of each Kuhn offset in a table row (-1: none)
+    int64_t flin[15];                   // Kuhn offsets as linear offsets on the fine level
+    int64_t* indptr; int* indices; double* data;
+    int* flag;                          // 1: a non-zero contribution outside the coarse Kuhn pattern
+};
+
+template <int DIM, int FMT>
+__device__ __forceinline__ void galerkin_fine_row(const GalerkinArgs& a, int64_t r, double (&row)[Kuhn<DIM>::K]) {
+    constexpr int K = Kuhn<DIM>::K;
+    const int64_t S = (int64_t)WAVE * a.R;
+    if (FMT == 3) {
+        const double* t = a.ctab + 8 * (int)a.cls[r];
+#pragma unroll
+        for (int q = 0; q < K; ++q) row[q] = a.tpos[q] < 0 ? 0.0 : t[a.tpos[q]];
+    } else if (FMT == 2) {
+#pragma unroll
+        for (int q = 0; q < K; ++q) {
+            const int64_t m = r + a.mlead + (a.flin[q] < 0 ? a.flin[q] : 0);       // lower entries are stored in the upper row
+            row[q] = a.diag[q] < 0 ? 0.0 : a.dvals[((size_t)(m / S) * a.wu + a.diag[q]) * S + (size_t)(m % S)];
+        }
+    } else {
+#pragma unroll
+        for (int q = 0; q < K; ++q) row[q] = 0.0;
+        const size_t base = (size_t)(r / S) * a.W * S + (size_t)(r % S);
+        for (int k = 0; k < a.W; ++k) {
+            const double v = a.vals[base + (size_t)k * S];
+            if (FMT == 1) {
+                const int code = (int)((a.codes[(size_t)(r / S) * ((a.W + 7) / 8) * S + (size_t)(r % S) + (size_t)(k / 8) * S] >> (8 * (k % 8))) & 0xffull);
+#pragma unroll
+                for (int q = 0; q < K; ++q) row[q] = row[q] + (code == a.code[q] ? v : 0.0);
+            } else {
+                const int64_t d = (int64_t)a.cols[base + (size_t)k * S] - a.lead - r;
+#pragma unroll
+                for (int q = 0; q < K; ++q) row[q] = row[q] + (d == a.flin[q] ? v : 0.0);
+            }
+        }
+    }
+}
+
+template <int DIM, int FMT>
+__global__ void galerkin_p1(GalerkinArgs a) {
+    constexpr int K = Kuhn<DIM>::K, CTR = Kuhn<DIM>::C;
+    int i, j;
+    if (!plane_node(a.gc, &i, &j)) return;
+    const int k = blockIdx.y;
+    const int nc = a.gc.nx - 1, nf = a.gf.nx - 1;
+    const int64_t row = (int64_t)k * a.gc.plane + (int64_t)j * a.gc.nx + i;
+    const bool bnd = i == 0 || i == nc || k == 0 || k == nc || (DIM == 3 && (j == 0 || j == nc));
+    auto c_in = [&](int ei, int ej, int ek) {             // coarse node I + e interior
+        return i + ei >= 1 && i + ei <= nc - 1 && k + ek >= 1 && k + ek <= nc - 1 && (DIM == 2 || (j + ej >= 1 && j + ej <= nc - 1));
+    };
+    double acc[K];
+#pragma unroll
+    for (int q = 0; q < K; ++q) acc[q] = 0.0;
+    if (bnd) {
+        acc[CTR] = 1.0;
+    } else {
+        const int fi = 2 * i, fj = DIM == 3 ? 2 * j : 0, fk = 2 * k;
+#pragma unroll
+        for (int ta = 0; ta < K; ++ta) {
+            const int ai = kuhn_off<DIM>(ta, 0), aj = kuhn_off<DIM>(ta, 1), ak = kuhn_off<DIM>(ta, 2);
+            const double wa = ta == CTR ? 1.0 : 0.5;
+            const int64_t fa = (int64_t)(fk + ak) * a.gf.plane + (int64_t)(fj + aj) * a.gf.nx + (fi + ai);
+            double rv[K];
+            galerkin_fine_row<DIM, FMT>(a, fa, rv);
+#pragma unroll
+            for (int tb = 0; tb < K; ++tb) {
+                const int di = ai + kuhn_off<DIM>(tb, 0), dj = aj + kuhn_off<DIM>(tb, 1), dk = ak + kuhn_off<DIM>(tb, 2);
+                const bool b_in = fi + di >= 1 && fi + di <= nf - 1 && fk + dk >= 1 && fk + dk <= nf - 1 &&
+                                  (DIM == 2 || (fj + dj >= 1 && fj + dj <= nf - 1));
+                if (!b_in) continue;
+                const double av = wa * rv[tb];
+                // b = 2 (I + B) + p, p in {0,1}^3
+                const int bi = di >> 1, bj = dj >> 1, bk = dk >> 1;
+                const int pi = di & 1, pj = dj & 1, pk = dk & 1;
+                const int np = (pi | pj | pk) ? 2 : 1;
+#pragma unroll
+                for (int u = 0; u < 2; ++u) {
+                    if (u >= np) continue;
+                    const int ei = bi + u * pi, ej = bj + u * pj, ek = bk + u * pk;
+                    const double term = np == 1 ? av : av * 0.5;
+                    const int s = kuhn_slot<DIM>(ei, ej, ek);
+                    if (s < 0) {
+                        if (term != 0.0 && c_in(ei, ej, ek)) atomicOr(a.flag, 1);
+                        continue;
+                    }
+                    if (c_in(ei, ej, ek)) acc[s] = acc[s] + term;
+                }
+            }
+        }
+    }
+    const size_t o = (size_t)row * K;
+#pragma unroll
+    for (int q = 0; q < K; ++q) {
+        const int ei = kuhn_off<DIM>(q, 0), ej = kuhn_off<DIM>(q, 1), ek = kuhn_off<DIM>(q, 2);
+        const bool keep = bnd ? q == CTR : c_in(ei, ej, ek);
+        a.indices[o + q] = (int)(keep ? row + (int64_t)ek * a.gc.plane + (int64_t)ej * a.gc.nx + ei : row);
+        a.data[o + q] = keep ? acc[q] : 0.0;
+    }
+    a.indptr[row] = (int64_t)o;
+    if (row == (int64_t)a.gc.plane * a.gc.nz - 1) a.indptr[row + 1] = (int64_t)o + K;
+}
+
 // ---- vector utilities ---------------------------------------------------------------------------
 __global__ void fill_zero(double* x, int64_t n) {
     for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (int64_t)gridDim.x * blockDim.x)

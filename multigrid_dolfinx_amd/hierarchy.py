@@ -23,7 +23,8 @@ __all__ = ["DeviceHierarchy", "jacobi_split"]
 
 _VEC = {"v": MG_VEC_V, "f": MG_VEC_F, "r": MG_VEC_R, "err": MG_VEC_ERR}
 _RESTRICT = {"direct": MG_RESTRICT_INJECTION, "injection": MG_RESTRICT_INJECTION,
-             "full_weighting": MG_RESTRICT_FULL_WEIGHTING, "table": _capi.MG_RESTRICT_TABLE}
+             "full_weighting": MG_RESTRICT_FULL_WEIGHTING, "table": _capi.MG_RESTRICT_TABLE,
+             "p1_transpose": _capi.MG_RESTRICT_P1_TRANSPOSE}
 
 
 def _csr_arrays(A):
@@ -212,12 +213,17 @@ class DeviceHierarchy:
 
     def set_prolongation(self, kind: str = "q1"):
         """"q1": the reference's bilinear / trilinear interpolation (`Interpolation2D`); "p2": the natural embedding of
-        the coarse P2 space (`poisson.p2_prolongation_table`), for hierarchies of P2 lattice levels."""
+        the coarse P2 space (`poisson.p2_prolongation_table`), for hierarchies of P2 lattice levels; "p1": the natural
+        embedding of the coarse P1 space on the simplicial mesh of `poisson` (`mg_set_prolongation_p1`; its transpose is
+        `set_params(restriction="p1_transpose")`)."""
         if kind == "q1":
             check(self._lib.mg_set_prolongation_table(self._h, None, None, None))
             return
+        if kind == "p1":
+            check(self._lib.mg_set_prolongation_p1(self._h, 1))
+            return
         if kind != "p2":
-            raise ValueError("prolongation must be 'q1' or 'p2'")
+            raise ValueError("prolongation must be 'q1', 'p1' or 'p2'")
         from .poisson import p2_prolongation_table
         cnt, off, w = p2_prolongation_table(self.dim)
         cnt = np.ascontiguousarray(cnt, dtype=np.int32)
@@ -231,6 +237,33 @@ class DeviceHierarchy:
         ro = np.ascontiguousarray(ro, dtype=np.int32)
         rw = np.ascontiguousarray(rw, dtype=np.float64)
         check(self._lib.mg_set_restriction_table(self._h, int(ro.shape[1]), ptr(rc), ptr(ro), ptr(rw)))
+
+    def galerkin(self, top_level: Optional[int] = None):
+        """Galerkin coarse levels (`mg_galerkin_hierarchy`): every level below `top_level` (default: the finest) becomes
+        P^T A P of the level above it, with P the P1 natural embedding, computed on the device.  The coarse levels' vectors
+        are lexicographic and start at zero; `fmg` on them needs `set_rhs_true` again."""
+        top = self.finest_level if top_level is None else top_level
+        check(self._lib.mg_galerkin_hierarchy(self._h, self._idx(top)))
+
+    def galerkin_level(self, level: int):
+        """Level - 1 := P^T A_level P (`mg_galerkin_level`)."""
+        check(self._lib.mg_galerkin_level(self._h, self._idx(level)))
+
+    @classmethod
+    def galerkin_from_matrix(cls, dim: int, coarsest_level: int, finest_level: int, A=None, grid_index=None, c: int = 8,
+                             mu1: int = 2, mu2: int = 2, omega: float = 2.0 / 3.0, smoother: str = "jacobi",
+                             prune_zeros: bool = True, device: int = 0, **tuning):
+        """A hierarchy from ONE finest matrix: `A` (SciPy CSR in the DoF numbering `grid_index`), or None for the device
+        generator (`gen_poisson_level`), then Galerkin coarse levels with the P1 transfers selected."""
+        h = cls(dim, coarsest_level, finest_level, c=c, device=device, **tuning)
+        if A is None:
+            h.gen_poisson_level(finest_level, prune_zeros=prune_zeros)
+        else:
+            h.set_level(finest_level, A, grid_index, prune_zeros=prune_zeros)
+        h.galerkin(finest_level)
+        h.set_params(mu1, mu2, omega, restriction="p1_transpose", smoother=smoother)
+        h.set_prolongation("p1")
+        return h
 
     def level_slab(self, level: int):
         """`(row0, n_local, halo_lo, halo_hi)`: the lexicographic nodes this rank owns on `level` and how many nodes

@@ -52,7 +52,7 @@ u_exact_fine = None
 V_fine_dolfx = None
 
 # ---- state of this implementation --------------------------------------------------------------------
-_options = {"dim": 2, "prune_zeros": True, "device": 0, "restriction": "direct", "smoother": "jacobi",
+_options = {"dim": 2, "prune_zeros": True, "device": 0, "restriction": "direct", "prolongation": "q1", "smoother": "jacobi",
             "grid_index": None, "norm": "auto",
             "coarse_rtol": 1e-14, "stop_tol": 1e-11, "max_cycles": 10000, "tuning": {}}
 _hier = None            # DeviceHierarchy of the initialised problem
@@ -95,7 +95,10 @@ _adhoc = _LRU(close=lambda hit: _release(hit[0]))       # stand-alone device con
 
 def configure(**kw):
     """Options with no reference counterpart: `dim` (2 or 3), `prune_zeros`, `device`,
-    `restriction` ('direct' = the live path, or 'full_weighting'), `smoother` ('jacobi' = the
+    `restriction` ('direct' = the live path, 'full_weighting', or 'p1_transpose' = the transpose of the P1 embedding),
+    `prolongation` ('q1' = the reference's interpolation, or 'p1' = the natural embedding of the coarse P1 space: with
+    'p1_transpose' the cycle contracts several times faster, and its results differ from the reference's on purpose),
+    `smoother` ('jacobi' = the
     reference's, or 'rbgs' = red-black Gauss-Seidel with `omega` as SOR factor), `grid_index`
     ({level: lexicographic node index per DoF}, instead of coordinate dictionaries),
     `norm` ('auto': the reference's L2(Omega) norm through the mass matrix `V_fine_dolfx`, the l2 norm when that is
@@ -173,6 +176,8 @@ def _hierarchy():
             elif mesh_dof_list_dict:
                 gi = _grid_index_of(mesh_dof_list_dict[level], h.elements(level), dim)
             h.set_level(level, A_sp_dict[level][0], gi, prune_zeros=_options["prune_zeros"])
+        if _options["prolongation"] != "q1":
+            h.set_prolongation(_options["prolongation"])
         _hier, _hier_params = h, None
     # the parameters go to the device only when they change (the captured V-cycle graphs depend on them)
     params = (mu1, mu2, omega, _options["restriction"], _options["coarse_rtol"], _options["smoother"])

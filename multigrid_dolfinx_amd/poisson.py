@@ -490,3 +490,61 @@ def p2_restriction_table(dim: int):
             roff[typ, e] = d
             rw[typ, e] = w
     return rcount, roff, rw
+
+
+# ---- P1 natural embedding in the table format (no reference implementation exists) ---------------------------------
+def kuhn_offsets(dim: int):
+    """The P1 stencil of the structured simplicial mesh as device offsets (di, dj, dk) in ascending lexicographic order
+    (dk, then dj, then di): `_offsets(dim)` with 2-D's (x, y) stored as (i, k).  The non-negative half are the mesh's edge
+    directions: (1, 0), (0, 1), (1, 1) in 2-D; the seven non-zero p in {0,1}^3 in 3-D (six Kuhn simplices per cube)."""
+    offs = []
+    for o in _offsets(dim):
+        offs.append((o[0], 0, o[1]) if dim == 2 else tuple(o))
+    return offs
+
+
+def p1_prolongation_table(dim: int):
+    """The natural prolongation between nested P1 spaces on the structured simplicial meshes, in the table format of
+    `p2_prolongation_table` (residue `ri + 4 rj + 16 rk` of `(i, j, k) mod 4` -> coarse points `2 * floor((i, j, k) / 4) +
+    offsets`): fine node `2I + p` takes `v(I)` for p = 0 and `0.5 v(I) + 0.5 v(I + p)` otherwise -- every fine node is a
+    coarse node or the midpoint of a coarse edge, which runs along p in {0,1}^dim.  The same operator as the device's
+    `mg_set_prolongation_p1`; this table is its independent cross-check through `mg_set_prolongation_table`.  NO REFERENCE
+    COUNTERPART (`Interpolation2D` is bilinear, multigrid.py:59-120, which on this mesh is not the embedding)."""
+    axes = (0, 2) if dim == 2 else (0, 1, 2)
+    count = np.zeros(64, dtype=np.int32)
+    offsets = np.zeros((64, 10, 3), dtype=np.int32)
+    weights = np.zeros((64, 10))
+    for res in range(64):
+        r = (res & 3, (res >> 2) & 3, (res >> 4) & 3)
+        if dim == 2 and r[1]:
+            continue
+        base = [0, 0, 0]
+        p = [0, 0, 0]
+        for a in axes:
+            base[a] = r[a] >> 1                      # floor(i / 2) - 2 floor(i / 4)
+            p[a] = r[a] & 1
+        if not any(p):
+            entries = [(tuple(base), 1.0)]
+        else:
+            entries = [(tuple(base), 0.5), (tuple(b + q for b, q in zip(base, p)), 0.5)]
+        count[res] = len(entries)
+        for t, (o, w) in enumerate(entries):
+            offsets[res, t] = o
+            weights[res, t] = w
+    return count, offsets, weights
+
+
+def p1_restriction_table(dim: int):
+    """Transpose of `p1_prolongation_table` in the format of `p2_restriction_table`: every interior coarse point, whatever
+    its type, sums `w * r[2 A + d]` over the Kuhn pattern d (`kuhn_offsets`) in ascending fine lexicographic order, w = 1 for
+    d = 0 and 0.5 otherwise.  The same operator as the device's MG_RESTRICT_P1_TRANSPOSE.  NO REFERENCE COUNTERPART."""
+    offs = kuhn_offsets(dim)
+    M = len(offs)
+    count = np.full(8, M, dtype=np.int32)
+    offsets = np.zeros((8, M, 3), dtype=np.int32)
+    weights = np.zeros((8, M))
+    for typ in range(8):
+        for e, d in enumerate(offs):
+            offsets[typ, e] = d
+            weights[typ, e] = 1.0 if d == (0, 0, 0) else 0.5
+    return count, offsets, weights
