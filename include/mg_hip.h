@@ -57,10 +57,13 @@ enum mg_smoother {
                                        BASELINE.json config 5): per sweep one in-place half sweep per
                                        colour, colour = parity of the lexicographic node index.  Needs
                                        pruned grid matrices (P1 stencils are then bipartite). */
-    MG_SMOOTH_MCGS = 2              /* nine-colour Gauss-Seidel / SOR for P2 rows (BASELINE.json config 5; no
+    MG_SMOOTH_MCGS = 2,             /* nine-colour Gauss-Seidel / SOR for P2 rows (BASELINE.json config 5; no
                                        reference): the seven parity classes of the lattice's mid-points plus the
                                        vertices split red / black; one in-place launch per colour in ascending
                                        order.  Valid for pruned P2 and P1 grid matrices (checked per level). */
+    MG_SMOOTH_CHEBYSHEV = 3         /* Chebyshev polynomial in D^-1 A (no reference; mg_set_chebyshev below): mu1 / mu2
+                                       (nw of mg_smooth) are the polynomial's degree, each call a fresh polynomial from
+                                       MG_VEC_V, one matrix application per degree.  omega is ignored. */
 };
 
 /* ---- life cycle ----------------------------------------------------------------
@@ -165,6 +168,35 @@ int mg_jacobi_split(int device, int64_t n_rows, int64_t nnz, const void* indptr,
  * in for spsolve on the coarsest level (multigrid.py:239). */
 int mg_set_params(mg_handle h, int mu1, int mu2, double omega, int restriction, int smoother,
                   double coarse_rtol, int coarse_maxit, int keep_err);
+/* Chebyshev smoother (MG_SMOOTH_CHEBYSHEV; no reference counterpart).  A call of degree m on level l runs the three-term
+ * recurrence (Saad, Iterative Methods, Alg. 12.1) on the interval [a, b] of that level, with theta = (b + a) / 2,
+ * delta = (b - a) / 2, sigma = theta / delta, rho_0 = 1 / sigma:
+ *     x_1     = x_0 + (1 / theta) D^-1 (f - A x_0)
+ *     x_{k+1} = x_k + rho_k rho_{k-1} (x_k - x_{k-1}) + (2 rho_k / delta) D^-1 (f - A x_k),  rho_k = 1 / (2 sigma - rho_{k-1}),
+ * i.e. step k computes (x + (alpha_k * (1 / d)) * (f - A x)) + beta_k * (x - x_{k-1}) row by row in every kernel, alpha_k and
+ * beta_k evaluated on the host in double in this order; the first step does not read x_{k-1}.  x_{k-1} lives in the level's
+ * second iterate buffer (MG_VEC_R, which the Jacobi ping-pong overwrites as well): no vector is added to the hierarchy.
+ * mg_set_chebyshev: b = upper_factor * lambda_max(D^-1 A) as estimated, a = b / lower_ratio, per level (defaults: eig_steps 10,
+ *   lower_ratio 6, upper_factor 1.1).  The estimate is eig_steps steps of Jacobi-preconditioned CG (Lanczos) from a start
+ *   vector that hashes each node's global lexicographic index, then the largest eigenvalue of the small tridiagonal matrix on the
+ *   host; dot products are fixed-order device sums (all-reduced over slabs: every rank gets the same bits).  It runs once per
+ *   level from mg_prepare_cycle, the first cycle or a stand-alone mg_smooth (never inside a captured cycle), and again only after
+ *   the level's matrix or these settings change.  Its four work vectors of the level's size are freed afterwards
+ *   (mg_memory_bytes does not change; mg_chebyshev_estimate_bytes reports what the last estimate held).  Refused with an error:
+ *   a level whose storage analysis found it non-symmetric (mg_level_storage), and one on which CG breaks down before two steps,
+ *   unless the caller has set that level's interval.
+ * mg_set_chebyshev_bounds: the caller's interval [lmin, lmax] for one level (lmin <= 0: lmax / lower_ratio); lmax <= 0 goes back
+ *   to the estimate.
+ * mg_chebyshev_bounds: the interval in use on a level and the estimate (0 if none has run); runs the estimate if it has not run.
+ * Kernels: the one-sweep Jacobi kernels of every storage format with a Chebyshev epilogue, one step per launch, counted by
+ *   mg_smoother_launches under MG_PATH_SLICE / MG_PATH_SWEEP1C; on levels that fit one CU ("fuse_small") up to 32 steps per
+ *   launch of one workgroup (MG_PATH_SMALL); on 2-D five-point levels ("fuse_2d") a whole call of 2 .. "fuse_2d_k" steps in one
+ *   launch (MG_PATH_K2D; longer calls one step per launch).  Every fused path is bit-identical to one step per launch
+ *   ("Chebyshev smoother").  On slabs every entry point here is collective: each rank calls it alike. */
+int mg_set_chebyshev(mg_handle h, int eig_steps, double lower_ratio, double upper_factor);
+int mg_set_chebyshev_bounds(mg_handle h, int level, double lmin, double lmax);
+int mg_chebyshev_bounds(mg_handle h, int level, double* lmin, double* lmax, double* lmax_estimate);
+int mg_chebyshev_estimate_bytes(mg_handle h, int64_t* bytes);
 /* Prolongation from a table instead of the reference's bilinear / trilinear Interpolation2D (multigrid.py:59-120): a fine
  * lattice point (i, j, k) combines the count[r] coarse lattice points 2 * floor((i, j, k) / 4) + offsets[r][t] (each
  * offset component 0..2, at most 10 entries) with weights[r][t], r = (i mod 4) + 4 (j mod 4) + 16 (k mod 4); 2-D levels
@@ -490,6 +522,8 @@ int mg_reset_smoother_launches(mg_handle h);
  * one kernel of the path on `level`, measured with HIP events on the handle's own
  * stream ("jacobi", "residual", "restrict", "prolong", "norm2"; "jacobi2" = the two-sweep pass, an
  * error on levels where mg_smooth does not use it; "jacobi2!" = the same wherever the kernel applies;
+ * "chebyshev" = one Chebyshev step that reads x_{k-1}, with whichever one-step kernel mg_smooth would launch on the level;
+ * "lattice" = one Jacobi launch of the lattice plane march ("lattice_march"), an error on levels that do not use it;
  * "jacobi_small" = the mu1 sweeps of a small level in one launch, an error where mg_smooth does not do that;
  * "jacobik" = one launch of the K-sweep 2-D kernel with K = "fuse_2d_k", an error on levels that do not use it;
  * "jacobik3" = one launch of the K-sweep plane march on a 3-D level ("jacobik3!": wherever it applies), "jacobiblk" = one launch

@@ -16,7 +16,7 @@ LIB_PATH = os.path.join(_HERE, "libmg_hip.so")
 
 MG_VEC_V, MG_VEC_F, MG_VEC_R, MG_VEC_ERR = 0, 1, 2, 3
 MG_RESTRICT_INJECTION, MG_RESTRICT_FULL_WEIGHTING, MG_RESTRICT_TABLE, MG_RESTRICT_P1_TRANSPOSE = 0, 1, 2, 3
-MG_SMOOTH_JACOBI, MG_SMOOTH_RBGS, MG_SMOOTH_MCGS = 0, 1, 2
+MG_SMOOTH_JACOBI, MG_SMOOTH_RBGS, MG_SMOOTH_MCGS, MG_SMOOTH_CHEBYSHEV = 0, 1, 2, 3
 MG_NORM_L2, MG_NORM_MASS = 0, 1
 # enum mg_smoother_path, in its order (mg_smoother_launches)
 SMOOTHER_PATHS = ("slice", "sweep1c", "pair_class", "pair_plain", "ksweep", "ksweep_escape", "ksweep_slab", "block", "k2d",
@@ -54,6 +54,10 @@ SIGNATURES = {
                         C.c_void_p, C.c_void_p],
     "mg_set_params": [_H, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int],
     "mg_set_tuning": [_H, C.c_char_p, C.c_int64],
+    "mg_set_chebyshev": [_H, C.c_int, C.c_double, C.c_double],
+    "mg_set_chebyshev_bounds": [_H, C.c_int, C.c_double, C.c_double],
+    "mg_chebyshev_bounds": [_H, C.c_int, _dp, _dp, _dp],
+    "mg_chebyshev_estimate_bytes": [_H, _i64p],
     "mg_set_prolongation_table": [_H, C.c_void_p, C.c_void_p, C.c_void_p],
     "mg_set_restriction_table": [_H, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
     "mg_set_prolongation_p1": [_H, C.c_int],

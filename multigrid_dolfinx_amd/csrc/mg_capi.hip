@@ -23,6 +23,10 @@
 
 using namespace mgk;
 
+// lower_ratio of the Chebyshev interval unless mg_set_chebyshev says otherwise (the cycle study of tools/time_chebyshev.py,
+// DESIGN.md section 5, "Chebyshev smoother")
+constexpr double CHEB_DEFAULT_LOWER_RATIO = 6.0;
+
 namespace {
 
 thread_local std::string g_err;
@@ -178,6 +182,10 @@ struct Level {
     DVector v, v2, f, err, ftrue;
     DVector sw;                             // once-relaxed boundary planes of a slab (paired sweeps, world > 1)
     DVector fcg_x, fcg_p, fcg_q, fcg_b;     // mg_pcg on this level: iterate, direction, A p, the saved right-hand side
+    // Chebyshev smoother (mg_set_chebyshev): the Lanczos estimate of lambda_max(D^-1 A) (cheb_est_ok: it is valid for the level's
+    // matrix and the handle's settings) and the caller's interval for this level (cheb_user_lmax > 0: used instead)
+    bool cheb_est_ok = false;
+    double cheb_lmax_est = 0.0, cheb_user_lmin = 0.0, cheb_user_lmax = 0.0;
     int* perm = nullptr;
     int p1_ok = -1;                         // stencil offsets within the Kuhn pattern of the P1 transfers (-1: not checked yet)
     std::vector<int> h_offsets;             // the offset table (linear offsets) of an offset-coded level, host copy
@@ -224,6 +232,11 @@ struct mg_context {
     double coarse_rtol = 1e-14;
     int coarse_maxit = 20000;
     int keep_err = 0;
+    // Chebyshev smoother (MG_SMOOTH_CHEBYSHEV, mg_set_chebyshev): Lanczos steps of the estimate, interval [b / lower_ratio, b]
+    // with b = upper_factor * the estimate; device bytes the last estimate held while it ran (freed afterwards)
+    int cheb_eig_steps = 10;
+    double cheb_lower_ratio = CHEB_DEFAULT_LOWER_RATIO, cheb_upper_factor = 1.1;
+    int64_t cheb_peak_bytes = 0;
     // tuning
     int use_codes = 1;          // offset-coded columns where a level allows it
     int use_sdia = 1;           // symmetric diagonal storage where a level is bit-for-bit symmetric
@@ -557,6 +570,7 @@ void free_level(mg_context* c, Level& L) {
     L.rb_ok = false;
     L.mc_ok = -1;
     L.p1_ok = -1;
+    L.cheb_est_ok = false; L.cheb_lmax_est = 0.0;
     L.h_offsets.clear();
     L.sdia = false;
     dev_free(c, L.dinv, (size_t)L.nslices * WAVE * L.R);
@@ -582,6 +596,8 @@ void launch_ell_wr(int mode, bool dot, const EllArgs& a, unsigned grid, hipStrea
         hipLaunchKernelGGL((ell_apply<WT, R, MODE_RESIDUAL, false>), dim3(grid), dim3(BLOCK), 0, s, a);
     else if (mode == MODE_JACOBI)
         hipLaunchKernelGGL((ell_apply<WT, R, MODE_JACOBI, false>), dim3(grid), dim3(BLOCK), 0, s, a);
+    else if (mode == MODE_CHEB)
+        hipLaunchKernelGGL((ell_apply<WT, R, MODE_CHEB, false>), dim3(grid), dim3(BLOCK), 0, s, a);
     else if (mode == MODE_GS)
         hipLaunchKernelGGL((ell_apply<WT, R, MODE_GS, false>), dim3(grid), dim3(BLOCK), 0, s, a);
     else if (dot)
@@ -596,6 +612,8 @@ void launch_ell_coded_wrn(int mode, bool dot, const EllArgs& a, unsigned grid, h
         hipLaunchKernelGGL((ell_apply_coded<WT, R, MODE_RESIDUAL, false, NT>), dim3(grid), dim3(BLOCK), 0, s, a);
     else if (mode == MODE_JACOBI)
         hipLaunchKernelGGL((ell_apply_coded<WT, R, MODE_JACOBI, false, NT>), dim3(grid), dim3(BLOCK), 0, s, a);
+    else if (mode == MODE_CHEB)
+        hipLaunchKernelGGL((ell_apply_coded<WT, R, MODE_CHEB, false, NT>), dim3(grid), dim3(BLOCK), 0, s, a);
     else if (mode == MODE_GS)
         hipLaunchKernelGGL((ell_apply_coded<WT, R, MODE_GS, false, NT>), dim3(grid), dim3(BLOCK), 0, s, a);
     else if (dot)
@@ -619,6 +637,8 @@ void launch_sdia_wrn(int mode, bool dot, bool finest, const EllArgs& a, unsigned
         hipLaunchKernelGGL((sdia_apply<WU, R, MODE_RESIDUAL, false, NT>), dim3(grid), dim3(BLOCK), lds, s, a);
     else if (mode == MODE_JACOBI)
         hipLaunchKernelGGL((sdia_apply<WU, R, MODE_JACOBI, false, NT>), dim3(grid), dim3(BLOCK), lds, s, a);
+    else if (mode == MODE_CHEB)
+        hipLaunchKernelGGL((sdia_apply<WU, R, MODE_CHEB, false, NT>), dim3(grid), dim3(BLOCK), lds, s, a);
     else if (mode == MODE_GS)
         hipLaunchKernelGGL((sdia_apply<WU, R, MODE_GS, false, NT>), dim3(grid), dim3(BLOCK), lds, s, a);
     else if (dot)
@@ -635,6 +655,8 @@ void launch_sdia_cls_wrn(int mode, bool dot, bool finest, const EllArgs& a, unsi
         hipLaunchKernelGGL((sdia_cls_apply<WU, R, MODE_RESIDUAL, false, NT>), dim3(grid), dim3(BLOCK), 0, s, a);
     else if (mode == MODE_JACOBI)
         hipLaunchKernelGGL((sdia_cls_apply<WU, R, MODE_JACOBI, false, NT>), dim3(grid), dim3(BLOCK), 0, s, a);
+    else if (mode == MODE_CHEB)
+        hipLaunchKernelGGL((sdia_cls_apply<WU, R, MODE_CHEB, false, NT>), dim3(grid), dim3(BLOCK), 0, s, a);
     else if (mode == MODE_GS)
         hipLaunchKernelGGL((sdia_cls_apply<WU, R, MODE_GS, false, NT>), dim3(grid), dim3(BLOCK), 0, s, a);
     else if (dot)
@@ -669,6 +691,8 @@ void launch_ell_cls_rn(int mode, bool dot, const EllArgs& a, unsigned grid, hipS
         hipLaunchKernelGGL((ell_cls_apply<R, MODE_RESIDUAL, false, NT>), dim3(grid), dim3(BLOCK), 0, s, a, L.scls, L.s_off, L.s_val, L.s_cnt);
     else if (mode == MODE_JACOBI)
         hipLaunchKernelGGL((ell_cls_apply<R, MODE_JACOBI, false, NT>), dim3(grid), dim3(BLOCK), 0, s, a, L.scls, L.s_off, L.s_val, L.s_cnt);
+    else if (mode == MODE_CHEB)
+        hipLaunchKernelGGL((ell_cls_apply<R, MODE_CHEB, false, NT>), dim3(grid), dim3(BLOCK), 0, s, a, L.scls, L.s_off, L.s_val, L.s_cnt);
     else if (mode == MODE_GS)
         hipLaunchKernelGGL((ell_cls_apply<R, MODE_GS, false, NT>), dim3(grid), dim3(BLOCK), 0, s, a, L.scls, L.s_off, L.s_val, L.s_cnt);
     else if (dot)
@@ -707,7 +731,7 @@ void launch_ell_r(int W, int mode, bool dot, const EllArgs& a, unsigned grid, hi
 }
 
 int launch_sweep1c(mg_context* c, const Level& L, int mode, const double* x_rows, const double* f_rows, double* out_rows,
-                   int color);
+                   int color, double alpha = 0.0, double beta = 0.0);
 bool sweep1c_ok(const mg_context* c, const Level& L);
 
 int allow_large_lds(mg_context* c, const void* kernel, size_t bytes);
@@ -750,7 +774,8 @@ int launch_lat_march_t(mg_context* c, const Level& L, LatArgs a, int mode) {
     const int64_t group = 8 * (int64_t)a.xcd_chunk;
     const unsigned grid = (unsigned)(((items + group - 1) / group) * group);
     void (*kern)(LatArgs) = mode == MODE_RESIDUAL ? lat_march<MODE_RESIDUAL, TI, TJ, NT>
-                          : mode == MODE_GS ? lat_march<MODE_GS, TI, TJ, NT> : lat_march<MODE_JACOBI, TI, TJ, NT>;
+                          : mode == MODE_GS ? lat_march<MODE_GS, TI, TJ, NT>
+                          : mode == MODE_CHEB ? lat_march<MODE_CHEB, TI, TJ, NT> : lat_march<MODE_JACOBI, TI, TJ, NT>;
     if (lds > (size_t)150 * 1024) return fail("lattice march: class tables too wide");
     MG_TRY(allow_large_lds(c, reinterpret_cast<const void*>(kern), (size_t)150 * 1024));
     hipLaunchKernelGGL(kern, dim3(grid), dim3(NT), lds, c->stream, a);
@@ -759,16 +784,17 @@ int launch_lat_march_t(mg_context* c, const Level& L, LatArgs a, int mode) {
 }
 
 int launch_lat_march(mg_context* c, const Level& L, int mode, const double* x_rows, const double* f_rows, double* out_rows,
-                     int color) {
+                     int color, double alpha, double beta) {
     LatArgs a{};
     a.x = x_rows; a.f = f_rows; a.out = out_rows;
+    a.xp = out_rows; a.beta = beta;
     a.cls = L.scls; a.s_pack = L.s_pack; a.s_val = L.s_val; a.s_cnt = L.s_cnt;
     a.W = L.W; a.WP = (L.W + 3) / 4 * 4 + 4; a.ntop = L.lm_ntop;
     for (int t = 0; t < LM_K; ++t) a.top[t] = L.lm_top[t];
     a.nloc = L.nloc; a.P = L.g.plane;
     a.xlo = -(L.halo_lo ? (int64_t)c->halo_planes * L.g.plane : 0); a.xhi = L.nloc + (L.halo_hi ? (int64_t)c->halo_planes * L.g.plane : 0);
     a.nx = L.g.nx; a.ny = L.g.ny; a.nz = L.g.nk; a.kg0 = (int)(L.row0 / L.g.plane);
-    a.color = color; a.omega = c->omega;
+    a.color = color; a.omega = mode == MODE_CHEB ? alpha : c->omega;
     // ("lattice_tile" 2: the wide tile moves 23 % fewer bytes but its one 512-thread workgroup per CU is slower than two of
     //  256 -- 8.0 against 6.9 ms per Gauss-Seidel sweep of the 513^3 lattice: kept for experiments)
     if (c->lattice_tile == 2 && L.g.nx >= 128) return launch_lat_march_t<128, 16, 512>(c, L, a, mode);
@@ -778,17 +804,20 @@ int launch_lat_march(mg_context* c, const Level& L, int mode, const double* x_ro
 // out = op(A, x) over all owned slices of the level
 int launch_ell(mg_context* c, const Level& L, int mode, bool dot, const double* x_base, const double* f_rows,
                double* out_rows, double* partials, const int* done, unsigned* grid_out = nullptr,
-               int64_t slice0 = 0, int64_t slice_count = -1, int color = 0, int64_t split = 0, int64_t gap = 0) {
+               int64_t slice0 = 0, int64_t slice_count = -1, int color = 0, int64_t split = 0, int64_t gap = 0,
+               double alpha = 0.0, double beta = 0.0) {
     // (gap > 0: the slice_count slices are [slice0, slice0 + split) and [slice0 + split + gap, ...) -- two ranges, one launch)
+    // (MODE_CHEB: one Chebyshev step with the step scalars alpha, beta; x_{k-1} is read from out_rows)
     if (slice_count < 0) slice_count = L.nslices - slice0;
     if (slice_count == 0) return 0;
     // whole large 3-D levels with row classes: one sweep as a plane march (mg_jacobi2.hip.h, sdia_sweep1c)
     if (!dot && !done && mode != MODE_SPMV && slice0 == 0 && slice_count == L.nslices && sweep1c_ok(c, L))
-        return launch_sweep1c(c, L, mode, x_base + L.g.lead, f_rows, out_rows, color);
+        return launch_sweep1c(c, L, mode, x_base + L.g.lead, f_rows, out_rows, color, alpha, beta);
     EllArgs a{};
     a.vals = L.vals; a.cols = L.cols; a.x = x_base; a.f = f_rows; a.dinv = L.dinv; a.out = out_rows;
     a.partials = partials; a.done_flag = done; a.nloc = L.nloc; a.lead = L.g.lead;
     a.slice0 = slice0; a.nslices = slice_count; a.split = split; a.gap = gap; a.omega = c->omega; a.W = L.W; a.chunk = c->chunk;
+    if (mode == MODE_CHEB) { a.omega = alpha; a.xp = out_rows; a.beta = beta; }
     a.codes = L.codes; a.offsets = L.offsets; a.ntable = L.ntable; a.dcode = L.dcode;
     a.color = color; a.color_kind = c->smoother == MG_SMOOTH_MCGS ? COLOR_LATTICE9 : COLOR_PARITY;
     a.grow0 = L.row0; a.gnx = L.g.nx; a.gny = L.g.ny;
@@ -850,7 +879,7 @@ int launch_ell(mg_context* c, const Level& L, int mode, bool dot, const double* 
     if (L.coded && L.scls && c->class_sweeps) {
         // whole 3-D lattice levels: plane march with x in LDS (mg_lattice.hip.h)
         if (!dot && !done && mode != MODE_SPMV && slice0 == 0 && slice_count == L.nslices && gap == 0 && lat_march_ok(c, L))
-            return launch_lat_march(c, L, mode, x_base + L.g.lead, f_rows, out_rows, color);
+            return launch_lat_march(c, L, mode, x_base + L.g.lead, f_rows, out_rows, color, alpha, beta);
         // wide rows through their stencil classes: 25 bytes per row instead of the stored row (ell_cls_apply)
         if (grid_out) *grid_out = grid;
         const bool nt = c->nontemporal != 0;
@@ -1575,9 +1604,9 @@ bool sweeps2d_ok(const mg_context* c, const Level& L) {
 // (profiles/r03_2d_lines.txt).  A launch on a small level takes as long as ONE workgroup does, about 2 us plus 1.3 us per cell
 // a thread owns: 16 lines (two cells) while all tiles still run at once.
 template <int K, int H>
-int launch_jacobik_th(mg_context* c, const JKArgs& a) {
+int launch_jacobik_th(mg_context* c, const JKArgs& a, bool cheb) {
     constexpr size_t lds = jk_lds_bytes<H>();
-    void (*const kern)(JKArgs) = sdia_jacobik2d<K, H>;
+    void (*const kern)(JKArgs) = cheb ? sdia_jacobik2d<K, H, true> : sdia_jacobik2d<K, H>;
     MG_TRY(allow_large_lds(c, reinterpret_cast<const void*>(kern), lds));
     JKArgs b = a;
     b.ntx = (a.nx + JK_W - 2 * K - 1) / (JK_W - 2 * K);
@@ -1588,30 +1617,37 @@ int launch_jacobik_th(mg_context* c, const JKArgs& a) {
 }
 
 template <int K>
-int launch_jacobik_t(mg_context* c, const JKArgs& a) {
+int launch_jacobik_t(mg_context* c, const JKArgs& a, bool cheb) {
     const int64_t cus = std::max(1, c->prop.multiProcessorCount);
     const int64_t ntx = (a.nx + JK_W - 2 * K - 1) / (JK_W - 2 * K);
     int best = c->fuse_2d_lines;
     if (!best) best = K <= 5 && ntx * ((a.nlines + 16 - 2 * K - 1) / (16 - 2 * K)) <= 2 * cus ? 16 : 32;
     switch (best) {
-        case 16: return launch_jacobik_th<K, 16>(c, a);
-        case 32: return launch_jacobik_th<K, 32>(c, a);
-        default: return launch_jacobik_th<K, 64>(c, a);
+        case 16: return launch_jacobik_th<K, 16>(c, a, cheb);
+        case 32: return launch_jacobik_th<K, 32>(c, a, cheb);
+        default: return launch_jacobik_th<K, 64>(c, a, cheb);
     }
 }
 
-// out = K Jacobi sweeps applied to x (2 <= K <= 5)
-int launch_jacobik(mg_context* c, const Level& L, int K, const double* x_rows, const double* f_rows, double* out_rows) {
+// out = K Jacobi sweeps applied to x (2 <= K <= 5); with al / be: the K steps of a whole Chebyshev call (be[0] == 0)
+int launch_jacobik(mg_context* c, const Level& L, int K, const double* x_rows, const double* f_rows, double* out_rows,
+                   const double* al = nullptr, const double* be = nullptr) {
     JKArgs a{};
     a.x = x_rows; a.f = f_rows; a.out = out_rows;
     a.cls = L.cls + L.cls_lead; a.ctab = L.ctab; a.ncls = L.ncls; a.cmain = L.cmain;
     for (int t = 0; t < 8; ++t) a.cm[t] = L.cm[t];
     a.n = L.nloc; a.nx = L.g.nx; a.nlines = L.g.nz; a.omega = c->omega;
+    const bool cheb = al != nullptr;
+    if (cheb) {
+        if (K > 5 || be[0] != 0.0) return fail("Chebyshev: one launch of the 2-D kernel takes a whole call of at most 5 steps");
+        a.omega = 1.0;                                  // (the class table then holds 1 / d, bit for bit)
+        for (int t = 0; t < K; ++t) { a.al[t] = al[t]; a.be[t] = be[t]; }
+    }
     switch (K) {
-        case 2: return launch_jacobik_t<2>(c, a);
-        case 3: return launch_jacobik_t<3>(c, a);
-        case 4: return launch_jacobik_t<4>(c, a);
-        case 5: return launch_jacobik_t<5>(c, a);
+        case 2: return launch_jacobik_t<2>(c, a, cheb);
+        case 3: return launch_jacobik_t<3>(c, a, cheb);
+        case 4: return launch_jacobik_t<4>(c, a, cheb);
+        case 5: return launch_jacobik_t<5>(c, a, cheb);
         default: return fail("sweeps per launch must be in 2..5");
     }
 }
@@ -1650,7 +1686,8 @@ int launch_sweep1c_t(mg_context* c, J2Args& a, int mode) {
     const unsigned grid = (unsigned)(((items + group - 1) / group) * group);
     constexpr size_t lds = j1c_lds_bytes<NW, LPW>();
     void (*kern)(J2Args) = mode == MODE_RESIDUAL ? sdia_sweep1c<NW, LPW, MODE_RESIDUAL>
-                         : mode == MODE_GS ? sdia_sweep1c<NW, LPW, MODE_GS> : sdia_sweep1c<NW, LPW, MODE_JACOBI>;
+                         : mode == MODE_GS ? sdia_sweep1c<NW, LPW, MODE_GS>
+                         : mode == MODE_CHEB ? sdia_sweep1c<NW, LPW, MODE_CHEB> : sdia_sweep1c<NW, LPW, MODE_JACOBI>;
     MG_TRY(allow_large_lds(c, reinterpret_cast<const void*>(kern), lds));
     hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * WAVE), lds, c->stream, a);
     HIP_TRY(hipGetLastError());
@@ -1658,10 +1695,11 @@ int launch_sweep1c_t(mg_context* c, J2Args& a, int mode) {
 }
 
 int launch_sweep1c(mg_context* c, const Level& L, int mode, const double* x_rows, const double* f_rows, double* out_rows,
-                   int color) {
+                   int color, double alpha, double beta) {
     J2Args a{};
     a.x = x_rows; a.f = f_rows; a.out = out_rows;
-    a.nloc = L.nloc; a.P = L.g.plane; a.nx = L.g.nx; a.ny = L.g.ny; a.nz = L.g.nk; a.omega = c->omega;
+    a.xp = out_rows; a.beta = beta;
+    a.nloc = L.nloc; a.P = L.g.plane; a.nx = L.g.nx; a.ny = L.g.ny; a.nz = L.g.nk; a.omega = mode == MODE_CHEB ? alpha : c->omega;
     a.cls = L.cls; a.ctab = L.ctab; a.clead = L.cls_lead; a.ncls = L.ncls; a.cmain = L.cmain;
     for (int t = 0; t < 8; ++t) a.cm[t] = L.cm[t];
     a.color = color; a.color_kind = c->smoother == MG_SMOOTH_MCGS ? COLOR_LATTICE9 : COLOR_PARITY; a.grow0 = L.row0;
@@ -1741,27 +1779,41 @@ bool small_level_ok(const mg_context* c, const Level& L) {
     return L.nloc <= 16384 && js_lds_bytes((int)L.nloc, pad) <= (size_t)150 * 1024;
 }
 
-int launch_jacobi_small(mg_context* c, const Level& L, int nw, const double* x_rows, const double* f_rows, double* out_rows) {
+// nw Jacobi sweeps; with al / be: nw <= JS_CHEB_STEPS Chebyshev steps, continuing from x_{k-1} in out_rows when be[0] != 0
+// and leaving x_{nw-1} in x_rows (the state of the one-step sequence once v and v2 swap)
+int launch_jacobi_small(mg_context* c, const Level& L, int nw, const double* x_rows, const double* f_rows, double* out_rows,
+                        const double* al = nullptr, const double* be = nullptr) {
     JSArgs a{};
     a.x = x_rows; a.f = f_rows; a.out = out_rows;
     a.cls = L.cls + L.cls_lead; a.ctab = L.ctab; a.ncls = L.ncls; a.cmain = L.cmain;
     for (int t = 0; t < 8; ++t) a.cm[t] = L.cm[t];
     a.n = (int)L.nloc; a.nw = nw; a.up1 = L.up[1]; a.up2 = L.up[2]; a.up3 = L.wu == 4 ? L.up[3] : 0; a.omega = c->omega;
+    const bool cheb = al != nullptr;
+    if (cheb) {
+        if (nw > JS_CHEB_STEPS) return fail("Chebyshev: too many steps for one launch of the small-level kernel");
+        a.omega = 1.0;                                  // (the class table then holds 1 / d, bit for bit)
+        a.xp = out_rows; a.xm = const_cast<double*>(x_rows);
+        for (int t = 0; t < nw; ++t) { a.al[t] = al[t]; a.be[t] = be[t]; }
+    }
     const size_t lds = js_lds_bytes(a.n, L.wu == 4 ? a.up3 : a.up2);
     // rows per thread: the smallest instance that covers the level
     const int need = (a.n + 1023) / 1024;
     void (*kern)(JSArgs) = nullptr;
     auto pick = [&](auto wu_tag) {
         constexpr int WU = decltype(wu_tag)::value;
-        if (need <= 1) kern = sdia_jacobi_small<WU, 1>;
-        else if (need <= 2) kern = sdia_jacobi_small<WU, 2>;
-        else if (need <= 3) kern = sdia_jacobi_small<WU, 3>;
-        else if (need <= 4) kern = sdia_jacobi_small<WU, 4>;
-        else if (need <= 5) kern = sdia_jacobi_small<WU, 5>;
-        else if (need <= 6) kern = sdia_jacobi_small<WU, 6>;
-        else if (need <= 8) kern = sdia_jacobi_small<WU, 8>;
-        else if (need <= 12) kern = sdia_jacobi_small<WU, 12>;
-        else kern = sdia_jacobi_small<WU, 16>;
+        auto k = [&](auto rpt_tag) {
+            constexpr int RPT = decltype(rpt_tag)::value;
+            kern = cheb ? sdia_jacobi_small<WU, RPT, true, true> : sdia_jacobi_small<WU, RPT>;
+        };
+        if (need <= 1) k(std::integral_constant<int, 1>{});
+        else if (need <= 2) k(std::integral_constant<int, 2>{});
+        else if (need <= 3) k(std::integral_constant<int, 3>{});
+        else if (need <= 4) k(std::integral_constant<int, 4>{});
+        else if (need <= 5) k(std::integral_constant<int, 5>{});
+        else if (need <= 6) k(std::integral_constant<int, 6>{});
+        else if (need <= 8) k(std::integral_constant<int, 8>{});
+        else if (need <= 12) k(std::integral_constant<int, 12>{});
+        else k(std::integral_constant<int, 16>{});
     };
     if (L.wu == 4) pick(std::integral_constant<int, 4>{});
     else pick(std::integral_constant<int, 3>{});
@@ -1787,9 +1839,65 @@ void count_pass(mg_context* c, int level, int path, int launches, int sweeps, in
     n.tail += tail_launches;
 }
 
-// nw Jacobi sweeps; v halos must be valid on entry and are valid on exit.
+int cheb_interval(mg_context* c, int level, double* lo, double* hi);
+
+// The step scalars of a Chebyshev polynomial of degree m on [lo, hi] (Saad, Iterative Methods, Alg. 12.1): step k is
+// x_{k+1} = x_k + alpha[k] D^-1 (f - A x_k) + beta[k] (x_k - x_{k-1}), beta[0] = 0.  Host doubles in this fixed order, so that
+// tests/cheb_reference.py gets the same bits; they reach the kernels as arguments (a captured cycle replays them).
+void cheb_steps(double lo, double hi, int m, double* alpha, double* beta) {
+    const double theta = 0.5 * (hi + lo), delta = 0.5 * (hi - lo), sigma = theta / delta;
+    double rho = 1.0 / sigma;
+    if (m > 0) { alpha[0] = 1.0 / theta; beta[0] = 0.0; }
+    for (int k = 1; k < m; ++k) {
+        const double rn = 1.0 / (2.0 * sigma - rho);
+        alpha[k] = 2.0 * rn / delta;
+        beta[k] = rn * rho;
+        rho = rn;
+    }
+}
+
+// nw Jacobi sweeps (Chebyshev: a polynomial of degree nw); v halos must be valid on entry and are valid on exit.
 int smooth(mg_context* c, int level, int nw) {
     Level& L = c->L[level];
+    if (c->smoother == MG_SMOOTH_CHEBYSHEV) {
+        // one step per launch of whatever kernel launch_ell picks for a Jacobi sweep of the level (counted under its path):
+        // x_{k-1} lives in v2, which each step overwrites row by row with x_{k+1} before v and v2 swap; slabs exchange the
+        // halo of v after each step (x_{k-1} needs none)
+        if (nw == 0) return 0;
+        double lo = 0.0, hi = 0.0;
+        MG_TRY(cheb_interval(c, level, &lo, &hi));
+        std::vector<double> al((size_t)nw), be((size_t)nw);
+        cheb_steps(lo, hi, nw, al.data(), be.data());
+        const bool dist = !L.replicated && c->comm.active();
+        if (!dist && nw >= 2 && small_level_ok(c, L)) {
+            // levels that fit one CU: up to JS_CHEB_STEPS steps per launch of one workgroup, x_{k-1} in registers; a launch
+            // continues from and leaves the one-step sequence's state (v = x_k, v2 = x_{k-1}), so longer calls chain launches
+            for (int s0 = 0; s0 < nw; s0 += JS_CHEB_STEPS) {
+                const int k = std::min(JS_CHEB_STEPS, nw - s0);
+                MG_TRY(launch_jacobi_small(c, L, k, L.v.rows, L.f.rows, L.v2.rows, al.data() + s0, be.data() + s0));
+                count_pass(c, level, MG_PATH_SMALL, 1, k);
+                std::swap(L.v, L.v2);
+            }
+            return 0;
+        }
+        if (!dist && nw >= 2 && nw <= std::min(5, c->fuse_2d_k) && sweeps2d_ok(c, L)) {
+            // 2-D levels: a whole call of at most "fuse_2d_k" steps in one launch.  (Tiles read their halo of x_{k-1}: a launch
+            // that continued a call would read cells that other tiles overwrite, so longer calls run one step per launch.)
+            MG_TRY(launch_jacobik(c, L, nw, L.v.rows, L.f.rows, L.v2.rows, al.data(), be.data()));
+            count_pass(c, level, MG_PATH_K2D, 1, nw);
+            std::swap(L.v, L.v2);
+            return 0;
+        }
+        const int one_path = sweep1c_ok(c, L) ? MG_PATH_SWEEP1C : MG_PATH_SLICE;     // (launch_ell's choice for a whole level)
+        for (int s = 0; s < nw; ++s) {
+            MG_TRY(launch_ell(c, L, MODE_CHEB, false, L.v.base, L.f.rows, L.v2.rows, nullptr, nullptr, nullptr, 0, -1, 0, 0, 0,
+                              al[(size_t)s], be[(size_t)s]));
+            count_pass(c, level, one_path, 1, 1);
+            std::swap(L.v, L.v2);
+            MG_TRY(exchange_halo(c, L, L.v));
+        }
+        return 0;
+    }
     if (c->smoother == MG_SMOOTH_RBGS) {
         // red-black Gauss-Seidel: two in-place half sweeps per sweep, halos refreshed after each colour
         if (!L.rb_ok)
@@ -2260,6 +2368,138 @@ int norm2(mg_context* c, const Level& L, const double* x_rows, double* out) {
     return 0;
 }
 
+// ---- Chebyshev smoother: interval per level -------------------------------------------------------------------------------
+// Largest eigenvalue of the symmetric tridiagonal matrix (diagonal d, off-diagonal e) by bisection on Sturm counts
+double tridiag_max_eig(const std::vector<double>& d, const std::vector<double>& e) {
+    const int n = (int)d.size();
+    double lo = 1e300, hi = -1e300;
+    for (int i = 0; i < n; ++i) {
+        const double r = (i > 0 ? std::fabs(e[(size_t)i - 1]) : 0.0) + (i + 1 < n ? std::fabs(e[(size_t)i]) : 0.0);
+        lo = std::min(lo, d[(size_t)i] - r);
+        hi = std::max(hi, d[(size_t)i] + r);
+    }
+    auto below = [&](double x) {            // eigenvalues < x
+        int k = 0;
+        double q = d[0] - x;
+        if (q < 0.0) ++k;
+        for (int i = 1; i < n; ++i) {
+            q = d[(size_t)i] - x - e[(size_t)i - 1] * e[(size_t)i - 1] / (q != 0.0 ? q : 1e-300);
+            if (q < 0.0) ++k;
+        }
+        return k;
+    };
+    for (int it = 0; it < 2000; ++it) {
+        const double mid = 0.5 * (lo + hi);
+        if (!(mid > lo && mid < hi)) break;
+        if (below(mid) < n) lo = mid; else hi = mid;
+    }
+    return hi;
+}
+
+// lambda_max(D^-1 A) of one level: cheb_eig_steps steps of Jacobi-preconditioned CG (Lanczos) from a start vector that hashes
+// each node's global lexicographic index, then the largest eigenvalue of the CG tridiagonal matrix on the host.  Four temporary
+// vectors of the level's layout (freed on return: mg_memory_bytes does not change); dot products are the fixed-order partial
+// sums of dot_device, all-reduced over slabs, so that every rank gets the same bits.  Synchronises: never inside a capture.
+int cheb_estimate(mg_context* c, int level) {
+    Level& L = c->L[level];
+    // (slabs: each rank tested its own rows, so the refusal is voted before the first collective -- every rank refuses
+    //  together, none waits in an all-reduce for a rank that has left)
+    bool asym = L.rep_sym == 0;
+    if (!L.replicated && c->comm.active()) {
+        c->h_scalars[0] = asym ? 1.0 : 0.0;
+        HIP_TRY(hipMemcpyAsync(c->scalars, c->h_scalars, sizeof(double), hipMemcpyHostToDevice, c->stream));
+        MG_TRY(allreduce_sum(c, c->scalars, 1));
+        HIP_TRY(hipMemcpyAsync(c->h_scalars, c->scalars, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        asym = c->h_scalars[0] != 0.0;
+    }
+    if (asym)
+        return fail("Chebyshev smoother: level " + std::to_string(level) +
+                    " is not symmetric (mg_level_storage), so CG cannot estimate its spectrum: set its interval with "
+                    "mg_set_chebyshev_bounds");
+    const int64_t vt = (vec_total(L) + 31) / 32 * 32;         // (each vector 256-byte aligned, like hipMalloc's)
+    DevTemp tmp;
+    MG_TRY(tmp.alloc((size_t)(4 * vt) * sizeof(double)));
+    HIP_TRY(hipMemsetAsync(tmp.p, 0, (size_t)(4 * vt) * sizeof(double), c->stream));
+    c->cheb_peak_bytes = 4 * vt * (int64_t)sizeof(double);
+    double* const raw = static_cast<double*>(tmp.p);
+    DVector p;
+    p.raw = raw; p.base = p.raw + vec_front(L); p.rows = p.base + L.g.lead;
+    double* const r = raw + vt + vec_front(L) + L.g.lead;
+    double* const z = raw + 2 * vt + vec_front(L) + L.g.lead;
+    double* const q = raw + 3 * vt + vec_front(L) + L.g.lead;
+    const int64_t n = L.nloc;
+    const dim3 grid((unsigned)std::min<int64_t>(4096, std::max<int64_t>(1, (n + 255) / 256))), blk(256);
+    auto scalar = [&](const double* x, const double* y, double* out) -> int {
+        MG_TRY(dot_device(c, L, x, y, 0));
+        HIP_TRY(hipMemcpyAsync(c->h_scalars, c->scalars, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        *out = c->h_scalars[0];
+        return 0;
+    };
+    hipLaunchKernelGGL(cheb_start, grid, blk, 0, c->stream, r, z, p.rows, L.dinv, n, L.row0);
+    HIP_TRY(hipGetLastError());
+    double rz = 0.0;
+    MG_TRY(scalar(r, z, &rz));
+    std::vector<double> al, be;
+    if (rz > 0.0 && std::isfinite(rz)) {
+        for (int j = 0; j < c->cheb_eig_steps; ++j) {
+            MG_TRY(exchange_halo(c, L, p));
+            MG_TRY(launch_ell(c, L, MODE_SPMV, false, p.base, nullptr, q, nullptr, nullptr));
+            double pq = 0.0;
+            MG_TRY(scalar(p.rows, q, &pq));
+            if (!(pq > 0.0) || !std::isfinite(pq)) break;          // breakdown: A not positive definite on the Krylov space
+            const double alpha = rz / pq;
+            al.push_back(alpha);
+            hipLaunchKernelGGL(cheb_cg_update, grid, blk, 0, c->stream, r, z, q, L.dinv, n, alpha);
+            HIP_TRY(hipGetLastError());
+            double rz_new = 0.0;
+            MG_TRY(scalar(r, z, &rz_new));
+            if (!(rz_new > 0.0) || !std::isfinite(rz_new) || j + 1 == c->cheb_eig_steps) break;
+            const double beta = rz_new / rz;
+            be.push_back(beta);
+            rz = rz_new;
+            hipLaunchKernelGGL(cheb_cg_direction, grid, blk, 0, c->stream, p.rows, z, n, beta);
+            HIP_TRY(hipGetLastError());
+        }
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    const int m = (int)al.size();
+    if (m < 2)
+        return fail("Chebyshev smoother: CG on level " + std::to_string(level) + " broke down after " + std::to_string(m) +
+                    " step(s), so its spectrum cannot be estimated: set its interval with mg_set_chebyshev_bounds");
+    // Lanczos matrix of the CG coefficients: T_jj = 1/alpha_j + beta_{j-1}/alpha_{j-1}, T_{j,j+1} = sqrt(beta_j)/alpha_j
+    std::vector<double> d((size_t)m), e((size_t)m - 1);
+    for (int j = 0; j < m; ++j) {
+        d[(size_t)j] = 1.0 / al[(size_t)j] + (j > 0 ? be[(size_t)j - 1] / al[(size_t)j - 1] : 0.0);
+        if (j + 1 < m) e[(size_t)j] = std::sqrt(be[(size_t)j]) / al[(size_t)j];
+    }
+    L.cheb_lmax_est = tridiag_max_eig(d, e);
+    L.cheb_est_ok = true;
+    return 0;
+}
+
+// The interval [lo, hi] the Chebyshev smoother damps on `level`: the caller's (mg_set_chebyshev_bounds), else
+// hi = upper_factor * the estimate and lo = hi / lower_ratio.  Runs the estimate when it is missing -- not inside a capture.
+int cheb_interval(mg_context* c, int level, double* lo, double* hi) {
+    Level& L = c->L[level];
+    if (L.cheb_user_lmax > 0.0) {
+        *hi = L.cheb_user_lmax;
+        *lo = L.cheb_user_lmin > 0.0 ? L.cheb_user_lmin : L.cheb_user_lmax / c->cheb_lower_ratio;
+        return 0;
+    }
+    if (!L.cheb_est_ok) {
+        hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+        HIP_TRY(hipStreamIsCapturing(c->stream, &st));
+        if (st != hipStreamCaptureStatusNone)
+            return fail("Chebyshev smoother: the estimate of level " + std::to_string(level) + " is missing inside a capture");
+        MG_TRY(cheb_estimate(c, level));
+    }
+    *hi = c->cheb_upper_factor * L.cheb_lmax_est;
+    *lo = *hi / c->cheb_lower_ratio;
+    return 0;
+}
+
 void free_direct(mg_context* c) {
     DirectSolver& d = c->direct;
     const size_t pw = (size_t)d.g.nb * d.g.p * (d.g.W > 0 ? d.g.W : 1), np = (size_t)d.g.nb * d.g.p;
@@ -2529,6 +2769,11 @@ int prepare_cycle(mg_context* c, int level) {
             }
     if (c->keep_err)
         for (int l = 1; l <= level; ++l) MG_TRY(vec_alloc(c, c->L[l], &c->L[l].err));
+    if (c->smoother == MG_SMOOTH_CHEBYSHEV)                // (the estimate synchronises: not inside a capture)
+        for (int l = 1; l <= level; ++l) {
+            double lo = 0.0, hi = 0.0;
+            MG_TRY(cheb_interval(c, l, &lo, &hi));
+        }
     if (c->p1_prolong || c->restriction == MG_RESTRICT_P1_TRANSPOSE)       // (may synchronise: not inside a capture)
         for (int l = 0; l <= level; ++l) MG_TRY(check_p1_stencil(c, c->L[l]));
     return 0;
@@ -3346,7 +3591,8 @@ int mg_set_params(mg_handle c, int mu1, int mu2, double omega, int restriction, 
     if (restriction != MG_RESTRICT_INJECTION && restriction != MG_RESTRICT_FULL_WEIGHTING && restriction != MG_RESTRICT_TABLE &&
         restriction != MG_RESTRICT_P1_TRANSPOSE)
         return fail("unknown restriction");
-    if (smoother != MG_SMOOTH_JACOBI && smoother != MG_SMOOTH_RBGS && smoother != MG_SMOOTH_MCGS) return fail("unknown smoother");
+    if (smoother != MG_SMOOTH_JACOBI && smoother != MG_SMOOTH_RBGS && smoother != MG_SMOOTH_MCGS && smoother != MG_SMOOTH_CHEBYSHEV)
+        return fail("unknown smoother");
     const double rtol = coarse_rtol > 0 ? coarse_rtol : c->coarse_rtol;
     const int maxit = coarse_maxit > 0 ? coarse_maxit : c->coarse_maxit;
     // captured V-cycles (vcycle_graphed) are keyed on the epoch: callers such as the Python shim set the same
@@ -3358,6 +3604,49 @@ int mg_set_params(mg_handle c, int mu1, int mu2, double omega, int restriction, 
     c->mu1 = mu1; c->mu2 = mu2; c->omega = omega; c->restriction = restriction; c->smoother = smoother;
     c->coarse_rtol = rtol; c->coarse_maxit = maxit;
     c->keep_err = keep_err;
+    return 0;
+}
+
+int mg_set_chebyshev(mg_handle c, int eig_steps, double lower_ratio, double upper_factor) {
+    if (!c) return fail("null handle");
+    if (eig_steps < 2 || eig_steps > 1000) return fail("eig_steps must be in 2..1000");
+    if (!(lower_ratio > 1.0) || !std::isfinite(lower_ratio)) return fail("lower_ratio must be a finite number > 1");
+    if (!(upper_factor > 0.0) || !std::isfinite(upper_factor)) return fail("upper_factor must be a finite number > 0");
+    if (eig_steps == c->cheb_eig_steps && lower_ratio == c->cheb_lower_ratio && upper_factor == c->cheb_upper_factor) return 0;
+    ++c->epoch;
+    c->cheb_eig_steps = eig_steps; c->cheb_lower_ratio = lower_ratio; c->cheb_upper_factor = upper_factor;
+    for (auto& L : c->L) L.cheb_est_ok = false;
+    return 0;
+}
+
+int mg_set_chebyshev_bounds(mg_handle c, int level, double lmin, double lmax) {
+    MG_TRY(check_level(c, level, false));
+    if (lmax > 0.0 && (!std::isfinite(lmax) || !std::isfinite(lmin) || !(lmin < lmax)))
+        return fail("Chebyshev bounds must be finite with lmin < lmax");
+    ++c->epoch;
+    Level& L = c->L[level];
+    L.cheb_user_lmax = lmax > 0.0 ? lmax : 0.0;
+    L.cheb_user_lmin = lmax > 0.0 && lmin > 0.0 ? lmin : 0.0;
+    return 0;
+}
+
+int mg_chebyshev_bounds(mg_handle c, int level, double* lmin, double* lmax, double* lmax_estimate) {
+    MG_TRY(need_matrix(c, level));
+    HIP_TRY(hipSetDevice(c->device));
+    Level& L = c->L[level];
+    // (the estimate runs if it has not, except on a non-symmetric level with the caller's interval: it would be refused)
+    if (!L.cheb_est_ok && (L.cheb_user_lmax <= 0.0 || L.rep_sym != 0)) MG_TRY(cheb_estimate(c, level));
+    double lo = 0.0, hi = 0.0;
+    MG_TRY(cheb_interval(c, level, &lo, &hi));
+    if (lmin) *lmin = lo;
+    if (lmax) *lmax = hi;
+    if (lmax_estimate) *lmax_estimate = L.cheb_est_ok ? L.cheb_lmax_est : 0.0;
+    return 0;
+}
+
+int mg_chebyshev_estimate_bytes(mg_handle c, int64_t* bytes) {
+    if (!c || !bytes) return fail("bad arguments");
+    *bytes = c->cheb_peak_bytes;
     return 0;
 }
 
@@ -4516,6 +4805,13 @@ int mg_time_kernel(mg_handle c, const char* kernel, int level, int reps, double*
     const hipEvent_t e0 = ev.e0, e1 = ev.e1;
     auto once = [&]() -> int {
         if (k == "jacobi") return launch_ell(c, L, MODE_JACOBI, false, L.v.base, L.f.rows, L.v2.rows, nullptr, nullptr);
+        if (k == "chebyshev") {     // one step with x_{k-1} (the scalars of step 1 of a degree-2 polynomial on the level's interval)
+            double lo = 0.0, hi = 0.0, al[2], be[2];
+            MG_TRY(cheb_interval(c, level, &lo, &hi));
+            cheb_steps(lo, hi, 2, al, be);
+            return launch_ell(c, L, MODE_CHEB, false, L.v.base, L.f.rows, L.v2.rows, nullptr, nullptr, nullptr, 0, -1, 0, 0, 0,
+                              al[1], be[1]);
+        }
         // "jacobi2": only where mg_smooth itself pairs sweeps on this level; "jacobi2!": wherever the kernel applies
         if (k == "jacobi2" || k == "jacobi2!") {
             if (!fused_sweeps_ok(c, L, k == "jacobi2!")) return fail("level does not use the two-sweep kernel");
@@ -4544,6 +4840,10 @@ int mg_time_kernel(mg_handle c, const char* kernel, int level, int reps, double*
         if (k == "jacobi_small") {           // all mu1 sweeps of a small level in one launch
             if (!small_level_ok(c, L) || c->mu1 < 2) return fail("level does not use the one-launch smoother");
             return launch_jacobi_small(c, L, c->mu1, L.v.rows, L.f.rows, L.v2.rows);
+        }
+        if (k == "lattice") {              // one Jacobi launch of the lattice plane march, an error where the level does not use it
+            if (!(L.coded && L.scls && c->class_sweeps && lat_march_ok(c, L))) return fail("level does not use the lattice march");
+            return launch_lat_march(c, L, MODE_JACOBI, L.v.rows, L.f.rows, L.v2.rows, 0, 0.0, 0.0);
         }
         if (k == "jacobik") {
             if (!sweeps2d_ok(c, L)) return fail("level does not use the K-sweep 2-D kernel");

@@ -54,6 +54,8 @@ struct J2Args {
     int ntx, nty, nseg, zb, seglen, seg0, seg_stride;
     unsigned nitems;
     double omega;
+    const double* xp;       // one-step march, MODE_CHEB: x_{k-1} (row-based, the same buffer as out) and the step's beta
+    double beta;
 };
 
 constexpr int J2_EX = 128;
@@ -1161,13 +1163,20 @@ __device__ __forceinline__ void j1c_body(const J2Args& a) {
     // k+1 (in flight, with the y ring of x in plane k+1)
     int c1[NC], c2[NC];
     double f1[NC], f2[NC], va[NC], vb[NC], vc[NC], vd[NC];
+    // MODE_CHEB: x_{k-1} of planes k and k+1 (in flight with f), loaded a step ahead like f
+    constexpr int NP = MODE == MODE_CHEB ? NC : 1;
+    double p1[NP], p2[NP];
+    const bool want_xp = MODE == MODE_CHEB && a.beta != 0.0;
+    const double* const pb0 = (MODE == MODE_CHEB ? a.xp : a.f) - bias;
     double hy[2];
     unsigned fast = 0;
 #pragma unroll
     for (int c = 0; c < NC; ++c) { f1[c] = f2[c] = va[c] = vb[c] = vc[c] = vd[c] = 0.0; c1[c] = c2[c] = 0; }
+#pragma unroll
+    for (int c = 0; c < NP; ++c) p1[c] = p2[c] = 0.0;
     hy[0] = hy[1] = 0.0;
 
-    auto load_cf = [&](const int plane, int (&cc)[NC], double (&fr)[NC]) {
+    auto load_cf = [&](const int plane, int (&cc)[NC], double (&fr)[NC], double (&pr)[NP]) {
         const int64_t o = (int64_t)min(max(plane, -1), a.nz) * a.P;
         const gcptr_t cb = sbase(clsb + o);
         const gcptr_t fb = sbase(fb0 + o);
@@ -1175,6 +1184,12 @@ __device__ __forceinline__ void j1c_body(const J2Args& a) {
         for (int c = 0; c < NC; ++c) {
             cc[c] = ldc(cb, eo[c]);
             fr[c] = ldd(fb, eo[c]);
+        }
+        if (MODE == MODE_CHEB && want_xp) {
+            // (cells of the ring and outside the level read whatever lies there, as x and f do; only result cells use it)
+            const gcptr_t pb = sbase(pb0 + o);
+#pragma unroll
+            for (int c = 0; c < NP; ++c) pr[c] = ldd(pb, eo[c]);
         }
         if (wlo || whi) {
             const gcptr_t xb = sbase(xb0 + o);
@@ -1211,10 +1226,10 @@ __device__ __forceinline__ void j1c_body(const J2Args& a) {
     load_x(z0 - 1, va);
     load_x(z0, vb);
     load_x(z0 + 1, vc);
-    load_cf(z0, c1, f1);                    // (with the y ring of plane z0)
+    load_cf(z0, c1, f1, p1);                // (with the y ring of plane z0)
     park(z0, vb);
     fast = all_main(c1);
-    load_cf(z0 + 1, c2, f2);
+    load_cf(z0 + 1, c2, f2, p2);
     load_x(z0 + 2, vd);
     __syncthreads();
 
@@ -1250,7 +1265,11 @@ __device__ __forceinline__ void j1c_body(const J2Args& a) {
             const int64_t r = rowof(c) + o1;
             bool store = (inT >> c & 1u) != 0 && r >= 0 && r < a.nloc;
             if (MODE == MODE_GS) store = store && lattice_color(a.color_kind, r + a.grow0, a.nx, a.ny) == a.color;
-            if (store) a.out[r] = MODE == MODE_RESIDUAL ? f1[c] - acc : vb[c] + cf * (f1[c] - acc);
+            if (store) {
+                double o = MODE == MODE_RESIDUAL ? f1[c] - acc : vb[c] + cf * (f1[c] - acc);
+                if (MODE == MODE_CHEB && want_xp) o = cheb_term(o, vb[c], a.beta, p1[MODE == MODE_CHEB ? c : 0]);
+                a.out[r] = o;
+            }
         }
         // ---- park plane k+1, rotate, issue the loads of the step after the next ----
         park(k + 1, vc);
@@ -1263,7 +1282,9 @@ __device__ __forceinline__ void j1c_body(const J2Args& a) {
             asm volatile("" : "+v"(f1[c]));
             asm volatile("" : "+v"(vc[c]));
         }
-        load_cf(k + 2, c2, f2);
+#pragma unroll
+        for (int c = 0; c < NP; ++c) p1[c] = p2[c];
+        load_cf(k + 2, c2, f2, p2);
         load_x(k + 3, vd);
         __syncthreads();
     }
@@ -1333,6 +1354,10 @@ struct JKArgs {
     int nx, nlines;         // grid: nx columns, nlines lines (row = line * nx + column)
     int ntx, nty;
     double omega;
+    // Chebyshev (CHEB): the K steps of a whole smoother call (the first does not read x_{k-1}), scalars al / be, 1 / d from
+    // the table (omega = 1); x_{k-1} of the thread's cells in a second register array.  (A call that continued from an earlier
+    // launch would need x_{k-1} of the tile's halo while other tiles overwrite it: such calls run one step per launch.)
+    double al[5], be[5];
 };
 
 constexpr int JK_W = 128;
@@ -1344,7 +1369,7 @@ template <int H> constexpr size_t jk_lds_bytes() { return (size_t)2 * H * JK_W *
 //  consecutive cells of a line, its first and last lane read the LDS copy) and a cell costs three LDS accesses per sweep
 //  instead of eight.  H = 32 or 16: two workgroups per CU, one computing while the other waits at its barrier -- faster than one
 //  workgroup on 64 lines although a sweep keeps fewer of the lines, see launch_jacobik_t.)
-template <int K, int H>
+template <int K, int H, bool CHEB = false>
 __global__ __launch_bounds__(1024) void sdia_jacobik2d(JKArgs a) {
     constexpr int W = JK_W, NT = 1024, CELLS = W * H, PER = CELLS / NT;
     static_assert(CELLS % NT == 0, "whole rounds of the workgroup");
@@ -1358,9 +1383,11 @@ __global__ __launch_bounds__(1024) void sdia_jacobik2d(JKArgs a) {
     const int ex = tid % W, ey0 = tid / W;                   // the thread's cells: (ex, ey0 + (NT / W) i)
 
     // ---- region -> registers and the first LDS copy (rows outside the level: zeros, class 0) ----
-    double xr[PER], fr[PER];
+    double xr[PER], fr[PER], xq[CHEB ? PER : 1];
     int cr[PER];
     unsigned okmask = 0u;
+#pragma unroll
+    for (int i = 0; i < (CHEB ? PER : 1); ++i) xq[i] = 0.0;
 #pragma unroll
     for (int i = 0; i < PER; ++i) {
         const int idx = tid + i * NT;
@@ -1413,7 +1440,7 @@ __global__ __launch_bounds__(1024) void sdia_jacobik2d(JKArgs a) {
                 acc = fma(m3, xc, acc);
                 acc = fma(m4, xe, acc);
                 acc = fma(m5, xn, acc);
-                o = xc + mcf * (fr[i] - acc);
+                o = CHEB ? xc + (a.al[s - 1] * mcf) * (fr[i] - acc) : xc + mcf * (fr[i] - acc);
             } else {
                 const dvec2_t* const tr = reinterpret_cast<const dvec2_t*>(sT + CLS_W * cr[i]);
                 const dvec2_t t01 = tr[0], t23 = tr[1], t45 = tr[2], t67 = tr[3];
@@ -1423,11 +1450,15 @@ __global__ __launch_bounds__(1024) void sdia_jacobik2d(JKArgs a) {
                 acc = fma(t23.y, xc, acc);
                 acc = fma(t45.x, xe, acc);
                 acc = fma(t45.y, xn, acc);
-                o = xc + t67.y * (fr[i] - acc);
+                o = CHEB ? xc + (a.al[s - 1] * t67.y) * (fr[i] - acc) : xc + t67.y * (fr[i] - acc);
+            }
+            if constexpr (CHEB) {
+                if (a.be[s - 1] != 0.0) o = cheb_term(o, xc, a.be[s - 1], xq[i]);
             }
             if (ex >= s && ex < W - s) {
                 o = (okmask >> i & 1u) ? o : 0.0;
                 dst[idx] = o;
+                if constexpr (CHEB) xq[i] = xc;
                 xr[i] = o;
             }
         }
@@ -1461,6 +1492,8 @@ namespace mgk {
 // neighbours ahead of the arithmetic, CH > 1 below, made it slower: 1.61).  What is left is instruction issue on ONE CU.
 // Arithmetic of sdia_cls_body<WU, ...> in the same order: bit-identical to single sweeps.  Five- and seven-point levels
 // with row classes.
+constexpr int JS_CHEB_STEPS = 32;      // Chebyshev steps per launch of sdia_jacobi_small (more: several launches)
+
 struct JSArgs {
     const double* x;        // row-based
     const double* f;
@@ -1472,11 +1505,18 @@ struct JSArgs {
     int n, nw;
     int up1, up2, up3;      // the positive offsets (+1, +nx, +plane; up3 = 0 for five-point rows)
     double omega;
+    // Chebyshev (CHEB): step s computes cheb_term(x + (al[s] * (1 / d)) * (f - A x), x, be[s], x_{k-1}) -- the one-step
+    // kernels' expression -- with 1 / d from the table (omega = 1); x_{k-1} of the thread's rows in a second register array,
+    // read from xp (the same buffer as out) only when be[0] != 0 (a call continued from the previous launch); at the end
+    // x_{nw-1} goes to xm (the same buffer as x, which only the owning thread read): the one-step ping-pong's state
+    const double* xp;
+    double* xm;
+    double al[JS_CHEB_STEPS], be[JS_CHEB_STEPS];
 };
 
 inline size_t js_lds_bytes(int n, int pad) { return (size_t)256 * CLS_W * 8 + (size_t)2 * (n + 2 * pad) * 8; }
 
-template <int WU, int RPT, bool DPP = true>
+template <int WU, int RPT, bool DPP = true, bool CHEB = false>
 __global__ __launch_bounds__(1024) void sdia_jacobi_small(JSArgs a) {
     extern __shared__ double j2_smem[];
     const int n = a.n, pad = WU == 4 ? a.up3 : a.up2, stride = n + 2 * pad;
@@ -1493,7 +1533,7 @@ __global__ __launch_bounds__(1024) void sdia_jacobi_small(JSArgs a) {
         sT[i] = v;
     }
     __syncthreads();
-    double xr[RPT], fr[RPT];
+    double xr[RPT], fr[RPT], xq[CHEB ? RPT : 1];
     int cr[RPT];
 #pragma unroll
     for (int i = 0; i < RPT; ++i) {
@@ -1503,6 +1543,7 @@ __global__ __launch_bounds__(1024) void sdia_jacobi_small(JSArgs a) {
         fr[i] = in ? a.f[r] : 0.0;
         cr[i] = in ? (int)a.cls[r] : 0;
         if (in) sX[pad + r] = xr[i];
+        if constexpr (CHEB) xq[i] = in && a.be[0] != 0.0 ? a.xp[r] : 0.0;
     }
     const double m0 = a.cm[0], m1 = a.cm[1], m2 = a.cm[2], m3 = a.cm[3], m4 = a.cm[4], m5 = a.cm[5], m6 = a.cm[6];
     const double mcf = a.omega * (1.0 / (m3 != 0.0 ? m3 : 1.0));
@@ -1575,7 +1616,14 @@ __global__ __launch_bounds__(1024) void sdia_jacobi_small(JSArgs a) {
                     cf = t67.y;
                 }
                 if (in) {
-                    const double o = xc + cf * (fr[i] - acc);
+                    double o;
+                    if constexpr (CHEB) {
+                        o = xc + (a.al[s] * cf) * (fr[i] - acc);
+                        if (a.be[s] != 0.0) o = cheb_term(o, xc, a.be[s], xq[i]);
+                        xq[i] = xc;
+                    } else {
+                        o = xc + cf * (fr[i] - acc);
+                    }
                     dst[r] = o;
                     xr[i] = o;
                 }
@@ -1587,6 +1635,7 @@ __global__ __launch_bounds__(1024) void sdia_jacobi_small(JSArgs a) {
     for (int i = 0; i < RPT; ++i) {
         const int r = tid + 1024 * i;
         if (r < n) a.out[r] = xr[i];
+        if constexpr (CHEB) if (r < n) a.xm[r] = xq[i];
     }
 }
 

@@ -48,7 +48,14 @@ template <int R> struct alignas(8) DVecU { double d[R]; };
 // MODE_GS: in-place relaxation of the rows of one colour (red-black Gauss-Seidel half sweep);
 // the colour of a row is the parity of its global lexicographic index, a valid two-colouring of
 // the pruned P1 stencils on grids with an odd number of nodes per axis.
-enum { MODE_RESIDUAL = 0, MODE_JACOBI = 1, MODE_SPMV = 2, MODE_GS = 3 };
+// MODE_CHEB: one step of the Chebyshev smoother (mg_set_chebyshev; DESIGN.md section 5, "Chebyshev smoother"), the Jacobi output plus a term in
+// the previous iterate xp = x_{k-1} of the same row, in ONE expression for every kernel (cheb_term):
+//     out = (x + (alpha * (1 / d)) * (f - A x)) + beta * (x - xp)
+// with alpha passed as `omega`.  xp is read only when beta != 0 (the first step of a polynomial: the buffer is stale and
+// 0 * NaN is NaN).  out and xp are the same buffer: each row's xp is read by the thread that then writes that row.
+enum { MODE_RESIDUAL = 0, MODE_JACOBI = 1, MODE_SPMV = 2, MODE_GS = 3, MODE_CHEB = 4 };
+
+__device__ __forceinline__ double cheb_term(double jac, double x, double beta, double xp) { return jac + beta * (x - xp); }
 enum { COLOR_PARITY = 0, COLOR_LATTICE9 = 1 };
 
 // Colour of a lexicographic lattice index.  COLOR_LATTICE9 (P2 rows, two lattice planes of reach): the seven parity
@@ -167,6 +174,9 @@ struct EllArgs {
     int ncls, cmain;
     double cm[8];
     unsigned nvirt;         // groups of four slices to process (persistent blocks stride over them)
+    // MODE_CHEB: x_{k-1} (row-based, the same buffer as out) and the step's beta; alpha is `omega`
+    const double* xp;
+    double beta;
 };
 
 // ---- XCD strip traversal ----------------------------------------------------------------------
@@ -237,12 +247,18 @@ __device__ __forceinline__ void tile_epilogue(const EllArgs& a, int64_t row, con
                 }
             } else {
                 const DVec<R> fr = load_d<R, NT>(a.f + row);
+                DVec<R> pr;                                     // (x_{k-1} issued with f)
+                if (MODE == MODE_CHEB && a.beta != 0.0) pr = load_d<R, false>(a.xp + row);
                 if (MODE == MODE_RESIDUAL) {
 #pragma unroll
                     for (int r = 0; r < R; ++r) o.d[r] = fr.d[r] - acc[r];
                 } else {
 #pragma unroll
                     for (int r = 0; r < R; ++r) o.d[r] = xr[r] + (a.omega * (1.0 / diag[r])) * (fr.d[r] - acc[r]);
+                    if (MODE == MODE_CHEB && a.beta != 0.0) {
+#pragma unroll
+                        for (int r = 0; r < R; ++r) o.d[r] = cheb_term(o.d[r], xr[r], a.beta, pr.d[r]);
+                    }
                 }
             }
             // the Jacobi / SpMV output is the next sweep's gathered source: keep it cacheable
@@ -261,6 +277,7 @@ __device__ __forceinline__ void tile_epilogue(const EllArgs& a, int64_t row, con
                         val = a.f[rr] - acc[r];
                     } else {
                         val = xr[r] + (a.omega * (1.0 / diag[r])) * (a.f[rr] - acc[r]);
+                        if (MODE == MODE_CHEB && a.beta != 0.0) val = cheb_term(val, xr[r], a.beta, a.xp[rr]);
                     }
                     a.out[rr] = val;
                 }
@@ -976,6 +993,11 @@ __global__ __launch_bounds__(BLOCK) void ell_apply(EllArgs a) {
                     const DVec<R> di = *reinterpret_cast<const DVec<R>*>(a.dinv + row);
 #pragma unroll
                     for (int r = 0; r < R; ++r) o.d[r] = xr.d[r] + (a.omega * di.d[r]) * (fr.d[r] - acc[r]);
+                    if (MODE == MODE_CHEB && a.beta != 0.0) {
+                        const DVec<R> pr = *reinterpret_cast<const DVec<R>*>(a.xp + row);
+#pragma unroll
+                        for (int r = 0; r < R; ++r) o.d[r] = cheb_term(o.d[r], xr.d[r], a.beta, pr.d[r]);
+                    }
                 }
             }
             *reinterpret_cast<DVec<R>*>(a.out + row) = o;
@@ -993,6 +1015,7 @@ __global__ __launch_bounds__(BLOCK) void ell_apply(EllArgs a) {
                         val = a.f[rr] - acc[r];
                     } else {
                         val = a.x[a.lead + rr] + (a.omega * a.dinv[rr]) * (a.f[rr] - acc[r]);
+                        if (MODE == MODE_CHEB && a.beta != 0.0) val = cheb_term(val, a.x[a.lead + rr], a.beta, a.xp[rr]);
                     }
                     a.out[rr] = val;
                 }
@@ -2051,6 +2074,43 @@ __global__ __launch_bounds__(BLOCK) void fcg_direction(FcgArgs a) {
         const int64_t t = a.n - 1;
         a.p[t] = FIRST ? a.z[t] : fma(beta, a.p[t], a.z[t]);
     }
+}
+
+// ---- Chebyshev smoother: the Lanczos estimate of lambda_max(D^-1 A) (set-up, mg_capi.hip: cheb_estimate) ----------------
+// Jacobi-preconditioned CG from a start vector that depends on the global lexicographic node index only (slabs and a single
+// handle start alike): splitmix64 of the index, its top 53 bits as a number in [-1, 1).  tests/cheb_reference.py has the same.
+__device__ __forceinline__ double cheb_hash(uint64_t g) {
+    uint64_t z = g + 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    z = z ^ (z >> 31);
+    return (double)(z >> 11) * (1.0 / 4503599627370496.0) - 1.0;        // (z >> 11) / 2^52 - 1
+}
+
+// r = hash(row0 + t), z = D^-1 r, p = z over the n owned rows
+__global__ void cheb_start(double* __restrict__ r, double* __restrict__ z, double* __restrict__ p,
+                           const double* __restrict__ dinv, int64_t n, int64_t row0) {
+    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (int64_t)gridDim.x * blockDim.x) {
+        const double rv = cheb_hash((uint64_t)(row0 + t));
+        const double zv = dinv[t] * rv;
+        r[t] = rv; z[t] = zv; p[t] = zv;
+    }
+}
+
+// r = r - alpha q, z = D^-1 r
+__global__ void cheb_cg_update(double* __restrict__ r, double* __restrict__ z, const double* __restrict__ q,
+                               const double* __restrict__ dinv, int64_t n, double alpha) {
+    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (int64_t)gridDim.x * blockDim.x) {
+        const double rv = r[t] - alpha * q[t];
+        r[t] = rv;
+        z[t] = dinv[t] * rv;
+    }
+}
+
+// p = z + beta p
+__global__ void cheb_cg_direction(double* __restrict__ p, const double* __restrict__ z, int64_t n, double beta) {
+    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (int64_t)gridDim.x * blockDim.x)
+        p[t] = z[t] + beta * p[t];
 }
 
 }  // namespace mgk

@@ -48,6 +48,8 @@ struct LatArgs {
     int kg0;                    // global index of local plane 0 (colours)
     int color;
     double omega;
+    const double* xp;           // MODE_CHEB: x_{k-1} (row-based, the same buffer as out) and the step's beta
+    double beta;
     int ntx, nty, seglen;
     unsigned nitems, xcd_chunk;
 };
@@ -265,7 +267,9 @@ __global__ __launch_bounds__(LM_THREADS) void lat_march(LatArgs a) {
                         s_ = fma(v, xv, s_);
                     }
                 }
-                a.out[row] = MODE == MODE_RESIDUAL ? fr[c] - s_ : xr + (a.omega * (1.0 / diag)) * (fr[c] - s_);
+                double o = MODE == MODE_RESIDUAL ? fr[c] - s_ : xr + (a.omega * (1.0 / diag)) * (fr[c] - s_);
+                if (MODE == MODE_CHEB && a.beta != 0.0) o = cheb_term(o, xr, a.beta, a.xp[row]);
+                a.out[row] = o;
             }
         }
         store_plane(k + 3, rs);                                     // slot (k-3) mod 6: last read a step ago

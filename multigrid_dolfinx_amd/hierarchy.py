@@ -21,6 +21,9 @@ from .poisson import grid_index_from_coords
 
 __all__ = ["DeviceHierarchy", "jacobi_split"]
 
+# lower_ratio of the Chebyshev interval by default (include/mg_hip.h, mg_set_chebyshev)
+CHEB_LOWER_RATIO = 6.0
+
 _VEC = {"v": MG_VEC_V, "f": MG_VEC_F, "r": MG_VEC_R, "err": MG_VEC_ERR}
 _RESTRICT = {"direct": MG_RESTRICT_INJECTION, "injection": MG_RESTRICT_INJECTION,
              "full_weighting": MG_RESTRICT_FULL_WEIGHTING, "table": _capi.MG_RESTRICT_TABLE,
@@ -329,9 +332,33 @@ class DeviceHierarchy:
     def set_params(self, mu1: int, mu2: int, omega: float, restriction: str = "direct",
                    coarse_rtol: float = 1e-14, coarse_maxit: int = 20000, keep_err: bool = False,
                    smoother: str = "jacobi"):
-        sm = {"jacobi": _capi.MG_SMOOTH_JACOBI, "rbgs": _capi.MG_SMOOTH_RBGS, "mcgs": _capi.MG_SMOOTH_MCGS}[smoother]
+        sm = {"jacobi": _capi.MG_SMOOTH_JACOBI, "rbgs": _capi.MG_SMOOTH_RBGS, "mcgs": _capi.MG_SMOOTH_MCGS,
+              "chebyshev": _capi.MG_SMOOTH_CHEBYSHEV}[smoother]
         check(self._lib.mg_set_params(self._h, int(mu1), int(mu2), float(omega), _RESTRICT[restriction],
                                       sm, float(coarse_rtol), int(coarse_maxit), 1 if keep_err else 0))
+
+    def set_chebyshev(self, eig_steps: int = 10, lower_ratio: float = CHEB_LOWER_RATIO, upper_factor: float = 1.1):
+        """Settings of the Chebyshev smoother (`smoother="chebyshev"`, `mg_set_chebyshev`): Lanczos steps of the estimate of
+        lambda_max(D^-1 A) per level, and the interval [b / lower_ratio, b] with b = upper_factor * that estimate."""
+        check(self._lib.mg_set_chebyshev(self._h, int(eig_steps), float(lower_ratio), float(upper_factor)))
+
+    def set_chebyshev_bounds(self, level: int, lmin: float, lmax: float):
+        """The Chebyshev interval [lmin, lmax] of one level instead of the estimate's (lmin <= 0: lmax / lower_ratio;
+        lmax <= 0: back to the estimate)."""
+        check(self._lib.mg_set_chebyshev_bounds(self._h, self._idx(level), float(lmin), float(lmax)))
+
+    def chebyshev_bounds(self, level: int) -> dict:
+        """{"lmin", "lmax"}: the interval the Chebyshev smoother uses on `level`; "lmax_estimate": the Lanczos estimate of
+        lambda_max(D^-1 A) (0.0 if none has run).  Runs the estimate if it has not run yet."""
+        lo, hi, est = C.c_double(), C.c_double(), C.c_double()
+        check(self._lib.mg_chebyshev_bounds(self._h, self._idx(level), C.byref(lo), C.byref(hi), C.byref(est)))
+        return {"lmin": lo.value, "lmax": hi.value, "lmax_estimate": est.value}
+
+    def chebyshev_estimate_bytes(self) -> int:
+        """Device bytes the last Chebyshev estimate held while it ran (freed afterwards)."""
+        b = C.c_int64()
+        check(self._lib.mg_chebyshev_estimate_bytes(self._h, C.byref(b)))
+        return int(b.value)
 
     @classmethod
     def from_bag(cls, bag, dim: int = 2, grid_index: Optional[Dict[int, np.ndarray]] = None,

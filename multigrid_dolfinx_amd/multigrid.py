@@ -99,7 +99,8 @@ def configure(**kw):
     `prolongation` ('q1' = the reference's interpolation, or 'p1' = the natural embedding of the coarse P1 space: with
     'p1_transpose' the cycle contracts several times faster, and its results differ from the reference's on purpose),
     `smoother` ('jacobi' = the
-    reference's, or 'rbgs' = red-black Gauss-Seidel with `omega` as SOR factor), `grid_index`
+    reference's, 'rbgs' = red-black Gauss-Seidel with `omega` as SOR factor, or 'chebyshev' = a Chebyshev polynomial in
+    D^-1 A of degree mu1 / mu2 on an interval estimated per level; `omega` is then ignored), `grid_index`
     ({level: lexicographic node index per DoF}, instead of coordinate dictionaries),
     `norm` ('auto': the reference's L2(Omega) norm through the mass matrix `V_fine_dolfx`, the l2 norm when that is
     None; 'l2': always the l2 norm), `coarse_rtol`, `stop_tol`, `max_cycles`, `tuning` (kernel knobs)."""
