@@ -154,6 +154,31 @@ int mg_gen_poisson_level(mg_handle h, int level, int elements_per_dim, int prune
  * Multigrid_prototype.py:77-108).  `lattice_steps` = lattice points per dimension - 1 (even).  Single GPU. */
 int mg_gen_lattice_level(mg_handle h, int level, int lattice_steps, int width, const int* count, const int* offsets,
                          const double* values, const double* load);
+/* Variable-coefficient diffusion level (no reference counterpart): the P1 matrix of -div(kappa grad u) on the Kuhn mesh of
+ * mg_gen_poisson_level, with kappa one positive double per cell -- 3-D cube (ci, cj, ck) at (ck * N + cj) * N + ci, 2-D square
+ * (ci, cy) at cy * N + ci, x fastest -- shared by all simplices of the cell.  Every simplex of that mesh has a right dihedral
+ * angle at each non-axis edge, so the rows keep the five- / seven-point shape of the Poisson level: the axis edge between
+ * node i and neighbour j gets a_ij = -(sum_c n_c kappa_c) h / 6 (3-D) or -(sum_c kappa_c) / 2 (2-D), c the cells holding the
+ * edge in ascending index, n_c = 2 where the cell's corner at the edge has both other local coordinates equal, else 1; the
+ * diagonal is the sum of the row's edge sums (ascending offset order), scaled the same way.  Boundary rows, zeroed columns
+ * and the lifted right-hand side as mg_gen_poisson_level; kappa == 1 gives its level bit for bit.  a_ij and a_ji have the
+ * same bits, so the level is bit-symmetric.  The level then gets the storage analysis, row classes and escape rows of any
+ * level; "gen_odd_rows" does not apply.  `kappa` holds all N^dim cells of the level on the host; on slabs every rank passes
+ * the whole array (as for mg_set_vector) and only the cell planes its owned rows read are uploaded.  A kappa that is not
+ * positive and finite is refused, naming the first bad cell (found on the device), and the level is left as it was.  The
+ * device copy of kappa is freed on return.  poisson.diffusion_level is the host restatement. */
+int mg_gen_diffusion_level(mg_handle h, int level, int elements_per_dim, const double* kappa, int prune_zeros);
+/* Levels top_level .. 0 from one kappa of the top level (elements_per_dim cells per dimension): each coarser level's kappa
+ * is coarsened on the device from the level above -- the 2^dim children in ascending lexicographic order, summed one by
+ * one, x 2^-dim (MG_KAPPA_ARITHMETIC) or 2^dim / sum of 1 / kappa (MG_KAPPA_HARMONIC); poisson.coarsen_kappa restates it --
+ * and every level is generated as mg_gen_diffusion_level(..., prune_zeros = 1) would.  At most two kappa fields are on the
+ * device at a time, none after return.  Needs a whole (not slab) handle and an even elements_per_dim on every level above
+ * level 0; on slabs, call mg_gen_diffusion_level per level. */
+enum mg_kappa_averaging {
+    MG_KAPPA_ARITHMETIC = 0,
+    MG_KAPPA_HARMONIC = 1
+};
+int mg_gen_diffusion_hierarchy(mg_handle h, int top_level, int elements_per_dim, const double* kappa_top, int averaging);
 /* getJacobiMatrices (multigrid.py:48-56) as a stand-alone set-up kernel, for callers that
  * want the reference's split operands back: for every stored entry a_ij of the CSR matrix
  * writes scaled[q] = a_ij / a_ii computed as (1/a_ii) * a_ij, keep[q] = 1 unless the entry

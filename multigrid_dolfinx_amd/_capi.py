@@ -18,6 +18,7 @@ MG_VEC_V, MG_VEC_F, MG_VEC_R, MG_VEC_ERR = 0, 1, 2, 3
 MG_RESTRICT_INJECTION, MG_RESTRICT_FULL_WEIGHTING, MG_RESTRICT_TABLE, MG_RESTRICT_P1_TRANSPOSE = 0, 1, 2, 3
 MG_SMOOTH_JACOBI, MG_SMOOTH_RBGS, MG_SMOOTH_MCGS, MG_SMOOTH_CHEBYSHEV = 0, 1, 2, 3
 MG_NORM_L2, MG_NORM_MASS = 0, 1
+MG_KAPPA_ARITHMETIC, MG_KAPPA_HARMONIC = 0, 1
 # enum mg_smoother_path, in its order (mg_smoother_launches)
 SMOOTHER_PATHS = ("slice", "sweep1c", "pair_class", "pair_plain", "ksweep", "ksweep_escape", "ksweep_slab", "block", "k2d",
                   "small")
@@ -50,6 +51,8 @@ SIGNATURES = {
                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_int],
     "mg_gen_poisson_level": [_H, C.c_int, C.c_int, C.c_int],
     "mg_gen_lattice_level": [_H, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    "mg_gen_diffusion_level": [_H, C.c_int, C.c_int, C.c_void_p, C.c_int],
+    "mg_gen_diffusion_hierarchy": [_H, C.c_int, C.c_int, C.c_void_p, C.c_int],
     "mg_jacobi_split": [C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                         C.c_void_p, C.c_void_p],
     "mg_set_params": [_H, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int],

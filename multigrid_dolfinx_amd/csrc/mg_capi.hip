@@ -4305,6 +4305,150 @@ int mg_gen_lattice_level(mg_handle c, int level, int N, int width, const int* co
     return 0;
 }
 
+namespace {
+
+// cell planes [kc0, kc1) along the slab axis that the interior rows of a level's owned planes read (kappa of the cells
+// on both sides of every owned node plane)
+void diffusion_planes(const Level& L, int* kc0, int* kc1) {
+    *kc0 = std::max(L.g.k0 - 1, 0);
+    *kc1 = std::min(L.g.k0 + L.g.nk, L.N);
+}
+
+int64_t cell_plane(const mg_context* c, int N) { return c->dim == 3 ? (int64_t)N * N : (int64_t)N; }
+
+// the first entry of the device kappa (global cell index base + q) that is not a positive finite double, as an error
+int check_kappa(mg_context* c, const double* d_kappa, int64_t n, int64_t base, int N) {
+    DevTemp d_first;
+    MG_TRY(d_first.alloc(sizeof(unsigned long long)));
+    HIP_TRY(hipMemsetAsync(d_first.p, 0xff, sizeof(unsigned long long), c->stream));
+    const unsigned nb = (unsigned)std::max<int64_t>(1, std::min<int64_t>(8192, (n + 255) / 256));
+    hipLaunchKernelGGL(kappa_check, dim3(nb), dim3(256), 0, c->stream, d_kappa, n, base,
+                       static_cast<unsigned long long*>(d_first.p));
+    HIP_TRY(hipGetLastError());
+    unsigned long long first = 0;
+    HIP_TRY(hipMemcpyAsync(&first, d_first.p, sizeof(first), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (first == ~0ull) return 0;
+    double x = 0.0;
+    HIP_TRY(hipMemcpy(&x, d_kappa + (first - base), sizeof(double), hipMemcpyDeviceToHost));
+    const int64_t q = (int64_t)first;
+    std::string cell = "(" + std::to_string(q % N) + ", ";
+    cell += c->dim == 3 ? std::to_string((q / N) % N) + ", " + std::to_string(q / ((int64_t)N * N)) : std::to_string(q / N);
+    char val[40];
+    snprintf(val, sizeof(val), "%.17g", x);
+    return fail("kappa must be positive and finite: cell " + cell + ") = index " + std::to_string(q) + " holds " + val);
+}
+
+// the level from a device kappa holding cell planes [kc0, ...): mg_gen_poisson_level's pipeline with gen_diffusion
+int gen_diffusion_level(mg_context* c, int level, int N, const double* d_kappa, int kc0, int prune_zeros) {
+    Level& L = c->L[level];
+    free_level(c, L);
+    const int rc = [&]() -> int {
+        MG_TRY(setup_geometry(c, L, level, N));
+        DiffusionArgs d{};
+        GenArgs& a = d.ga;
+        a.g = L.g; a.N = N; a.dim = c->dim; a.prune = prune_zeros;
+        a.h = 1.0 / (double)N;
+        a.fh = (c->dim == 2 ? -6.0 : -12.0) * std::pow(a.h, (double)c->dim);
+        sorted_offsets(c->dim, a.off, &a.noff);
+        L.W = prune_zeros ? (c->dim == 2 ? 5 : 7) : a.noff;
+        a.W = L.W;
+        d.kappa = d_kappa;
+        d.kc0 = kc0;
+        MG_TRY(alloc_ell(c, L));
+        MG_TRY(alloc_level_vectors(c, L));
+        unsigned long long* d_counts = reinterpret_cast<unsigned long long*>(c->partials);
+        HIP_TRY(hipMemsetAsync(d_counts, 0, 2 * sizeof(unsigned long long), c->stream));
+        const dim3 grid = grid3(L.g, L.g.nk), blk(kPlaneBlock);
+        switch (L.R) {
+            case 1: hipLaunchKernelGGL(gen_diffusion<1>, grid, blk, 0, c->stream, d, L.vals, L.cols, L.dinv, L.f.rows, d_counts); break;
+            case 2: hipLaunchKernelGGL(gen_diffusion<2>, grid, blk, 0, c->stream, d, L.vals, L.cols, L.dinv, L.f.rows, d_counts); break;
+            default: hipLaunchKernelGGL(gen_diffusion<4>, grid, blk, 0, c->stream, d, L.vals, L.cols, L.dinv, L.f.rows, d_counts); break;
+        }
+        HIP_TRY(hipGetLastError());
+        unsigned long long counts[2] = {0, 0};
+        HIP_TRY(hipMemcpyAsync(counts, d_counts, sizeof(counts), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        L.nnz_stored = counts[0];
+        L.nnz_nonzero = counts[1];
+        MG_TRY(encode_level(c, L));
+        MG_TRY(repack_sdia(c, L, level));
+        MG_TRY(build_stencil_classes(c, L));
+        if (level + 1 < c->nlev) {
+            MG_TRY(vec_alloc(c, L, &L.ftrue));
+            HIP_TRY(hipMemcpyAsync(L.ftrue.base, L.f.base, (size_t)L.xlen * 8, hipMemcpyDeviceToDevice, c->stream));
+        }
+        L.set = true;
+        L.has_matrix = true;
+        return 0;
+    }();
+    if (rc) {
+        const std::string why = g_err;
+        free_level(c, L);
+        g_err = why;
+    }
+    return rc;
+}
+
+}  // namespace
+
+int mg_gen_diffusion_level(mg_handle c, int level, int N, const double* kappa, int prune_zeros) {
+    MG_TRY(check_level(c, level, false));
+    if (N <= 0) return fail("elements_per_dim must be positive");
+    if (!kappa) return fail("null kappa");
+    HIP_TRY(hipSetDevice(c->device));
+    Level geo;                                   // checked before the level is touched: a refusal leaves it as it was
+    MG_TRY(setup_geometry(c, geo, level, N));
+    int kc0 = 0, kc1 = 0;
+    diffusion_planes(geo, &kc0, &kc1);
+    const int64_t cp = cell_plane(c, N), n = (int64_t)(kc1 - kc0) * cp;
+    DevTemp d_kappa;
+    MG_TRY(d_kappa.alloc((size_t)n * 8));
+    HIP_TRY(hipMemcpy(d_kappa.p, kappa + (size_t)kc0 * cp, (size_t)n * 8, hipMemcpyHostToDevice));
+    MG_TRY(check_kappa(c, static_cast<const double*>(d_kappa.p), n, (int64_t)kc0 * cp, N));
+    return gen_diffusion_level(c, level, N, static_cast<const double*>(d_kappa.p), kc0, prune_zeros);
+}
+
+int mg_gen_diffusion_hierarchy(mg_handle c, int top_level, int N, const double* kappa_top, int averaging) {
+    MG_TRY(check_level(c, top_level, false));
+    if (N <= 0) return fail("elements_per_dim must be positive");
+    if (!kappa_top) return fail("null kappa");
+    if (averaging != MG_KAPPA_ARITHMETIC && averaging != MG_KAPPA_HARMONIC) return fail("unknown kappa averaging");
+    if (c->comm.active())
+        return fail("mg_gen_diffusion_hierarchy needs a whole (not slab) handle: on slabs, call mg_gen_diffusion_level per "
+                    "level");
+    if (N % (1 << top_level))
+        return fail("mg_gen_diffusion_hierarchy needs an even elements_per_dim on every level above level 0 (" +
+                    std::to_string(N) + " is not N0 * 2^" + std::to_string(top_level) + ")");
+    HIP_TRY(hipSetDevice(c->device));
+    Level geo;
+    MG_TRY(setup_geometry(c, geo, top_level, N));
+    int64_t n = cell_plane(c, N) * N;
+    DevTemp fine, coarse;                        // at most two kappa fields alive at a time
+    MG_TRY(fine.alloc((size_t)n * 8));
+    HIP_TRY(hipMemcpy(fine.p, kappa_top, (size_t)n * 8, hipMemcpyHostToDevice));
+    MG_TRY(check_kappa(c, static_cast<const double*>(fine.p), n, 0, N));
+    MG_TRY(gen_diffusion_level(c, top_level, N, static_cast<const double*>(fine.p), 0, 1));
+    for (int l = top_level - 1, Nl = N / 2; l >= 0; --l, Nl /= 2) {
+        n = cell_plane(c, Nl) * Nl;
+        MG_TRY(coarse.alloc((size_t)n * 8));
+        const unsigned nb = (unsigned)std::max<int64_t>(1, std::min<int64_t>(8192, (n + 255) / 256));
+        if (c->dim == 3)
+            hipLaunchKernelGGL(kappa_coarsen<3>, dim3(nb), dim3(256), 0, c->stream, static_cast<const double*>(fine.p),
+                               static_cast<double*>(coarse.p), Nl, averaging == MG_KAPPA_HARMONIC ? 1 : 0);
+        else
+            hipLaunchKernelGGL(kappa_coarsen<2>, dim3(nb), dim3(256), 0, c->stream, static_cast<const double*>(fine.p),
+                               static_cast<double*>(coarse.p), Nl, averaging == MG_KAPPA_HARMONIC ? 1 : 0);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        HIP_TRY(hipFree(fine.p));
+        fine.p = coarse.p;
+        coarse.p = nullptr;
+        MG_TRY(gen_diffusion_level(c, l, Nl, static_cast<const double*>(fine.p), 0, 1));
+    }
+    return 0;
+}
+
 int mg_jacobi_split(int device, int64_t n_rows, int64_t nnz, const void* indptr, int indptr_is_64,
                     const int32_t* indices, const double* data, double* dinv, double* scaled, unsigned char* keep) {
     if (!indptr || !indices || !data || !dinv || !scaled || !keep) return fail("null argument");

@@ -1294,6 +1294,143 @@ __global__ void gen_lattice(LatticeArgs a, double* vals, int* cols, double* dinv
     }
 }
 
+// ---- variable-coefficient P1 diffusion level, -div(kappa grad u), one kappa per cell --------------------------------
+// On the Kuhn mesh every simplex has a right dihedral angle at each non-axis edge, so the P1 stiffness couples only axis
+// neighbours whatever kappa does from cell to cell: the level has the five- / seven-point shape of the Poisson level.
+// The axis edge between a node and its neighbour gets -(sum_c n_c kappa_c) h / 6 (3-D) or -(sum_c kappa_c) / 2 (2-D) over
+// the cells c holding the edge, in ascending cell index; n_c = 2 where the cell's corner at the edge has both other local
+// coordinates equal, 1 otherwise.  The diagonal is the sum of the row's edge sums in ascending offset order, scaled the
+// same way (sum first, scale last: kappa == 1 gives gen_poisson's entries bit for bit).  Boundary treatment, right-hand
+// side and tile layout as gen_poisson.  poisson.diffusion_level is the host restatement of this arithmetic.
+struct DiffusionArgs {
+    GenArgs ga;             // grid, N, dim, prune, W, h, fh and the sorted offsets, as gen_poisson has them
+    const double* kappa;    // cell planes [kc0, ...) along the slab axis (z in 3-D, y = k in 2-D), x fastest
+    int kc0;
+};
+
+__device__ __forceinline__ double diff_kappa(const DiffusionArgs& a, int ci, int cj, int ck) {
+    const int64_t N = a.ga.N;
+    return a.kappa[((int64_t)(ck - a.kc0) * (a.ga.dim == 3 ? N : 1) + cj) * N + ci];
+}
+
+template <int R>
+__global__ void gen_diffusion(DiffusionArgs d, double* vals, int* cols, double* dinv, double* f, unsigned long long* counts) {
+    const GenArgs& a = d.ga;
+    int i = 0, j = 0;
+    const bool active = plane_node(a.g, &i, &j);
+    const int kl = blockIdx.y;
+    unsigned nz = 0, kept = 0;
+    if (active) {
+        const int k = a.g.k0 + kl;
+        const int64_t lr = (int64_t)kl * a.g.plane + (int64_t)j * a.g.nx + i;
+        const size_t base = (size_t)(lr / (WAVE * R)) * a.W * (WAVE * R) + (size_t)(lr % (WAVE * R));
+        const bool bnd = gen_on_boundary(a, i, j, k);
+        // se[axis][side]: edge sums towards the lower (side 0) / upper (side 1) neighbour along axis 0 (i), 1 (j), 2 (k)
+        double se[3][2] = {{0.0, 0.0}, {0.0, 0.0}, {0.0, 0.0}};
+        double diag = 1.0;
+        if (!bnd) {
+            if (a.dim == 3) {
+                double K[2][2][2];      // K[dz][dy][dx]: cell (i - 1 + dx, j - 1 + dy, k - 1 + dz)
+                for (int dz = 0; dz < 2; ++dz)
+                    for (int dy = 0; dy < 2; ++dy)
+                        for (int dx = 0; dx < 2; ++dx) K[dz][dy][dx] = diff_kappa(d, i - 1 + dx, j - 1 + dy, k - 1 + dz);
+                // the four cells of an edge, ascending index: other-axis offsets (0,0), (1,0), (0,1), (1,1), n = 2, 1, 1, 2
+                for (int s = 0; s < 2; ++s) {
+                    double t = 2.0 * K[0][0][s];
+                    t = t + K[0][1][s]; t = t + K[1][0][s]; t = t + 2.0 * K[1][1][s];
+                    se[0][s] = t;
+                    t = 2.0 * K[0][s][0];
+                    t = t + K[0][s][1]; t = t + K[1][s][0]; t = t + 2.0 * K[1][s][1];
+                    se[1][s] = t;
+                    t = 2.0 * K[s][0][0];
+                    t = t + K[s][0][1]; t = t + K[s][1][0]; t = t + 2.0 * K[s][1][1];
+                    se[2][s] = t;
+                }
+                double t = se[2][0];
+                t = t + se[1][0]; t = t + se[0][0]; t = t + se[0][1]; t = t + se[1][1]; t = t + se[2][1];
+                diag = (t / 6.0) * a.h;
+            } else {
+                double K[2][2];         // K[dy][dx]: cell (i - 1 + dx, k - 1 + dy)
+                for (int dy = 0; dy < 2; ++dy)
+                    for (int dx = 0; dx < 2; ++dx) K[dy][dx] = diff_kappa(d, i - 1 + dx, 0, k - 1 + dy);
+                for (int s = 0; s < 2; ++s) {
+                    se[0][s] = K[0][s] + K[1][s];
+                    se[2][s] = K[s][0] + K[s][1];
+                }
+                double t = se[2][0];
+                t = t + se[0][0]; t = t + se[0][1]; t = t + se[2][1];
+                diag = t / 2.0;
+            }
+        }
+        double b = bnd ? gen_g(a, i, j, k) : a.fh;
+        for (int t = 0; t < a.noff; ++t) {
+            const int di = a.off[t][0], dj = a.off[t][1], dk = a.off[t][2];
+            const int ii = i + di, jj = j + dj, kk = k + dk;
+            if (ii < 0 || ii >= a.g.nx || jj < 0 || jj >= a.g.ny || kk < 0 || kk >= a.g.nz) continue;
+            const int naxis = (di != 0) + (dj != 0) + (dk != 0);
+            double v = 0.0;
+            if (naxis == 0) {
+                v = diag;
+            } else if (naxis == 1 && !bnd) {
+                const int ax = di != 0 ? 0 : (dj != 0 ? 1 : 2);
+                const double s = se[ax][(di + dj + dk) > 0 ? 1 : 0];
+                const double w = a.dim == 3 ? (s / 6.0) * a.h : s / 2.0;
+                if (gen_on_boundary(a, ii, jj, kk)) b = b - (-w) * gen_g(a, ii, jj, kk);
+                else v = -w;
+            }
+            if (v != 0.0) ++nz;
+            if (a.prune && v == 0.0) continue;
+            const int64_t lc = a.g.lead + lr + (int64_t)dk * a.g.plane + (int64_t)dj * a.g.nx + di;
+            if ((int)kept < a.W) {
+                vals[base + (size_t)kept * (WAVE * R)] = v;
+                cols[base + (size_t)kept * (WAVE * R)] = (int)lc;
+            }
+            ++kept;
+        }
+        dinv[lr] = 1.0 / diag;
+        f[lr] = b;
+    }
+    const unsigned ksum = (unsigned)wave_sum((double)kept);
+    const unsigned zsum = (unsigned)wave_sum((double)nz);
+    if ((threadIdx.x & 63) == 0) {
+        atomicAdd(&counts[0], (unsigned long long)ksum);
+        atomicAdd(&counts[1], (unsigned long long)zsum);
+    }
+}
+
+// Set-up check of a kappa field: the lowest index (plus `base`) of an entry that is not a positive finite double, by an
+// atomic minimum into *first (the caller sets it to ~0 first).
+__global__ void kappa_check(const double* __restrict__ kappa, int64_t n, int64_t base, unsigned long long* first) {
+    for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < n; q += (int64_t)gridDim.x * blockDim.x) {
+        const double x = kappa[q];
+        if (!(x > 0.0 && x <= 1.7976931348623157e308)) atomicMin(first, (unsigned long long)(base + q));
+    }
+}
+
+// kappa of the coarse cells (N_c = N_f / 2 per dimension): the 2^DIM children in ascending lexicographic order summed one
+// by one, then x 2^-DIM (harmonic == 0) or 2^DIM / sum of 1 / kappa (harmonic == 1); poisson.coarsen_kappa restates it.
+template <int DIM>
+__global__ void kappa_coarsen(const double* __restrict__ fine, double* __restrict__ coarse, int Nc, int harmonic) {
+    const int64_t nc = DIM == 3 ? (int64_t)Nc * Nc * Nc : (int64_t)Nc * Nc;
+    const int64_t Nf = 2 * (int64_t)Nc;
+    for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < nc; q += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t ci = q % Nc;
+        const int64_t cj = DIM == 3 ? (q / Nc) % Nc : 0;
+        const int64_t ck = DIM == 3 ? q / ((int64_t)Nc * Nc) : q / Nc;
+        double s = 0.0;
+        for (int c = 0; c < (DIM == 3 ? 2 : 1); ++c)
+            for (int b = 0; b < 2; ++b)
+                for (int a = 0; a < 2; ++a) {
+                    // 3-D: (z, y, x) = (2ck + c, 2cj + b, 2ci + a); 2-D: (y, x) = (2ck + b, 2ci + a)
+                    const int64_t f = DIM == 3 ? ((2 * ck + c) * Nf + 2 * cj + b) * Nf + 2 * ci + a
+                                               : (2 * ck + b) * Nf + 2 * ci + a;
+                    const double x = fine[f];
+                    s = s + (harmonic ? 1.0 / x : x);
+                }
+        coarse[q] = harmonic ? (DIM == 3 ? 8.0 : 4.0) / s : s * (DIM == 3 ? 0.125 : 0.25);
+    }
+}
+
 // ---- grid transfers (lexicographic index arithmetic; no coordinate hashing) ---------------------
 // Injection (Restriction2D_direct, multigrid.py:123-132): coarse (I,J,K) <- fine (2I,2J,2K).
 __global__ void restrict_inject(Grid gc, Grid gf, const double* __restrict__ rf, double* __restrict__ fc) {

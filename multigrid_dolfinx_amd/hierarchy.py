@@ -296,6 +296,58 @@ class DeviceHierarchy:
         check(self._lib.mg_gen_poisson_level(self._h, self._idx(level), self.elements(level),
                                              1 if prune_zeros else 0))
 
+    def _kappa(self, level: int, kappa) -> np.ndarray:
+        k = np.ascontiguousarray(np.asarray(kappa, dtype=np.float64).reshape(-1))
+        if k.size != self.elements(level) ** self.dim:
+            raise ValueError(f"level {level}: kappa has {k.size} entries, the level has {self.elements(level) ** self.dim} cells")
+        return k
+
+    def gen_diffusion_level(self, level: int, kappa, prune_zeros: bool = True):
+        """Device-side level of -div(kappa grad u), one kappa per cell (`mg_gen_diffusion_level`; the host restatement is
+        `poisson.diffusion_level`).  On slabs every rank passes the whole kappa of the level."""
+        k = self._kappa(level, kappa)
+        check(self._lib.mg_gen_diffusion_level(self._h, self._idx(level), self.elements(level), ptr(k),
+                                               1 if prune_zeros else 0))
+
+    def gen_diffusion_hierarchy(self, kappa, averaging: str = "arithmetic", top_level: Optional[int] = None):
+        """Levels top_level (default: the finest) .. coarsest from one kappa, coarsened on the device
+        (`mg_gen_diffusion_hierarchy`, as `poisson.coarsen_kappa` does it); pruned; whole handles only."""
+        top = self.finest_level if top_level is None else top_level
+        k = self._kappa(top, kappa)
+        avg = {"arithmetic": _capi.MG_KAPPA_ARITHMETIC, "harmonic": _capi.MG_KAPPA_HARMONIC}[averaging]
+        check(self._lib.mg_gen_diffusion_hierarchy(self._h, self._idx(top), self.elements(top), ptr(k), avg))
+
+    @classmethod
+    def synthetic_diffusion(cls, dim: int, coarsest_level: int, finest_level: int, kappa, c: int = 8,
+                            coarse: str = "arithmetic", mu1: int = 2, mu2: int = 2, omega: float = 2.0 / 3.0,
+                            smoother: str = "jacobi", prune_zeros: bool = True, device: int = 0, comm=None, **tuning):
+        """Hierarchy of -div(kappa grad u) levels from the finest level's kappa, with the P1 transfers (P and R = P^T).
+        Coarse levels: `coarse="arithmetic"` / `"harmonic"` regenerate them from a coarsened kappa -- on one handle with
+        `mg_gen_diffusion_hierarchy`, on slabs (`comm`) level by level with `poisson.coarsen_kappa` on the host --
+        and `"galerkin"` takes P^T A P (whole handles only)."""
+        from .poisson import coarsen_kappa
+        if coarse not in ("arithmetic", "harmonic", "galerkin"):
+            raise ValueError("coarse must be 'arithmetic', 'harmonic' or 'galerkin'")
+        if coarse == "galerkin" and comm is not None:
+            raise ValueError("Galerkin coarse levels need a whole handle, not slabs")
+        h = cls(dim, coarsest_level, finest_level, c=c, device=device, **tuning)
+        if comm is not None:
+            comm(h)
+        if coarse == "galerkin":
+            h.gen_diffusion_level(finest_level, kappa, prune_zeros=prune_zeros)
+            h.galerkin(finest_level)
+        elif comm is not None or not prune_zeros:
+            k = np.asarray(kappa, dtype=np.float64).reshape(-1)
+            for level in range(finest_level, coarsest_level - 1, -1):
+                h.gen_diffusion_level(level, k, prune_zeros=prune_zeros)
+                if level > coarsest_level:
+                    k = coarsen_kappa(k, dim, coarse)
+        else:
+            h.gen_diffusion_hierarchy(kappa, coarse)
+        h.set_params(mu1, mu2, omega, restriction="p1_transpose", smoother=smoother)
+        h.set_prolongation("p1")
+        return h
+
     def gen_p2_level(self, level: int):
         """Device-side synthetic P2 level on the lattice with `elements(level)` steps per dimension (= twice the
         cells; BASELINE config 5), from the per-class interior stencils of `poisson.p2_stencils`."""

@@ -548,3 +548,130 @@ def p1_restriction_table(dim: int):
             offsets[typ, e] = d
             weights[typ, e] = 1.0 if d == (0, 0, 0) else 0.5
     return count, offsets, weights
+
+
+# ---- variable-coefficient diffusion, -div(kappa grad u) with one kappa per cell (no reference counterpart) ----------
+def _kappa_cells(kappa, N: int, dim: int) -> np.ndarray:
+    k = np.asarray(kappa, dtype=np.float64)
+    if k.size != N ** dim:
+        raise ValueError(f"kappa has {k.size} entries, the level has {N ** dim} cells")
+    return k.reshape((N,) * dim)
+
+
+def diffusion_level(N: int, dim: int, kappa, keep_zeros: bool = True) -> Level:
+    """The level `mg_gen_diffusion_level` generates, assembled on the host in the kernel's operation order (same bits), in
+    the hand-off conventions of `lexicographic_level`.  `kappa` holds one positive value per cell: cube (ci, cj, ck) at
+    `(ck * N + cj) * N + ci`, square (ci, cy) at `cy * N + ci`.  On the Kuhn mesh the P1 stiffness of -div(kappa grad u)
+    couples axis neighbours only: the edge towards a neighbour gets -(sum_c n_c kappa_c) h / 6 (3-D) or -(sum_c kappa_c) / 2
+    (2-D) over the cells holding the edge in ascending index (n_c = 2 where the cell's other two local coordinates at the
+    edge are equal, else 1), the diagonal the sum of the row's edge sums in ascending offset order, scaled the same way.
+    Identity rows, zeroed columns and the lifted right-hand side as `lexicographic_level`, which kappa == 1 reproduces bit
+    for bit."""
+    kap = _kappa_cells(kappa, N, dim)
+    if np.any(~(kap > 0.0)) or not np.all(np.isfinite(kap)):
+        raise ValueError("kappa must be positive and finite")
+    kp = np.pad(kap, 1, constant_values=1.0)            # node (i, ..) -> cells i - 1 + d: padded index i + d
+    n1 = N + 1
+    h = 1.0 / N
+    if dim == 3:
+        K = [[[kp[dz:dz + n1, dy:dy + n1, dx:dx + n1].reshape(-1) for dx in (0, 1)] for dy in (0, 1)] for dz in (0, 1)]
+        # se[axis][side]; the four cells of an edge in ascending index, n = 2, 1, 1, 2
+        se = [[None, None] for _ in range(3)]
+        for s in (0, 1):
+            se[0][s] = ((2.0 * K[0][0][s] + K[0][1][s]) + K[1][0][s]) + 2.0 * K[1][1][s]
+            se[1][s] = ((2.0 * K[0][s][0] + K[0][s][1]) + K[1][s][0]) + 2.0 * K[1][s][1]
+            se[2][s] = ((2.0 * K[s][0][0] + K[s][0][1]) + K[s][1][0]) + 2.0 * K[s][1][1]
+        t = ((((se[2][0] + se[1][0]) + se[0][0]) + se[0][1]) + se[1][1]) + se[2][1]
+        diag = (t / 6.0) * h
+        weight = lambda s: (s / 6.0) * h
+    else:
+        K = [[kp[dy:dy + n1, dx:dx + n1].reshape(-1) for dx in (0, 1)] for dy in (0, 1)]
+        se = [[K[0][s] + K[1][s] for s in (0, 1)], [K[s][0] + K[s][1] for s in (0, 1)]]
+        t = ((se[1][0] + se[0][0]) + se[0][1]) + se[1][1]
+        diag = t / 2.0
+        weight = lambda s: s / 2.0
+
+    n = n1 ** dim
+    idx = np.arange(n, dtype=np.int64)
+    ijk = [idx % n1, (idx // n1) % n1]
+    if dim == 3:
+        ijk.append(idx // (n1 * n1))
+    on_bnd = np.zeros(n, dtype=bool)
+    for c in ijk:
+        on_bnd |= (c == 0) | (c == N)
+    coords = np.zeros((n, 3))
+    for d in range(dim):
+        coords[:, d] = ijk[d] / N
+    g = boundary_data(coords, dim)
+    strides = [1, n1, n1 * n1][:dim]
+    b = np.where(on_bnd, g, source_term(dim) * h ** dim)
+    valid, colv, valv = [], [], []
+    for o in _offsets(dim):
+        ok = np.ones(n, dtype=bool)
+        delta = 0
+        for d in range(dim):
+            if o[d] > 0:
+                ok &= ijk[d] + o[d] <= N
+            elif o[d] < 0:
+                ok &= ijk[d] + o[d] >= 0
+            delta += o[d] * strides[d]
+        col = idx + delta
+        axes = [d for d in range(dim) if o[d] != 0]
+        if not axes:
+            val = np.where(on_bnd, 1.0, diag)
+        elif len(axes) == 1:
+            ax = axes[0]
+            a = -weight(se[ax][1 if o[ax] > 0 else 0])
+            colc = np.clip(col, 0, n - 1)
+            both_int = ok & ~on_bnd & ~on_bnd[colc]
+            val = np.where(both_int, a, 0.0)
+            lift = ok & ~on_bnd & on_bnd[colc]
+            b = np.where(lift, b - a * g[colc], b)
+        else:
+            val = np.zeros(n)
+        if not keep_zeros:
+            ok = ok & (val != 0.0)
+        valid.append(ok)
+        colv.append(col)
+        valv.append(val)
+    counts = np.zeros(n, dtype=np.int64)
+    for ok in valid:
+        counts += ok
+    indptr = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(counts, out=indptr[1:])
+    nnz = int(indptr[-1])
+    indices = np.empty(nnz, dtype=np.int32)
+    data = np.empty(nnz, dtype=np.float64)
+    pos = indptr[:-1].copy()
+    for ok, col, val in zip(valid, colv, valv):
+        p = pos[ok]
+        indices[p] = col[ok]
+        data[p] = val[ok]
+        pos += ok
+    A = sp.csr_matrix((data, indices, indptr.astype(np.int32)), shape=(n, n))
+    A.has_sorted_indices = True
+    return Level(N=N, dim=dim, A=A, b=b.reshape(n, 1), coords=coords, grid_index=idx.copy(), h=h)
+
+
+def coarsen_kappa(kappa, dim: int, averaging: str = "arithmetic") -> np.ndarray:
+    """kappa of the coarse cells (N / 2 per dimension) as `mg_gen_diffusion_hierarchy` computes it: the 2^dim children in
+    ascending lexicographic order summed one by one (explicit adds, so the order is pinned), then x 2^-dim ("arithmetic")
+    or 2^dim / sum of 1 / kappa ("harmonic").  Flat array in the cell order of `diffusion_level`."""
+    k = np.asarray(kappa, dtype=np.float64)
+    N = int(round(k.size ** (1.0 / dim)))
+    kap = _kappa_cells(k, N, dim)
+    if N % 2:
+        raise ValueError("coarsening needs an even number of cells per dimension")
+    if averaging not in ("arithmetic", "harmonic"):
+        raise ValueError("averaging must be 'arithmetic' or 'harmonic'")
+    if dim == 3:
+        children = [kap[c::2, b::2, a::2] for c in (0, 1) for b in (0, 1) for a in (0, 1)]
+    else:
+        children = [kap[b::2, a::2] for b in (0, 1) for a in (0, 1)]
+    s = None
+    for x in children:
+        term = 1.0 / x if averaging == "harmonic" else x
+        s = term.copy() if s is None else s + term
+    m = float(2 ** dim)
+    out = m / s if averaging == "harmonic" else s * (1.0 / m)
+    return np.ascontiguousarray(out.reshape(-1))
