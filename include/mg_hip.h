@@ -179,6 +179,25 @@ enum mg_kappa_averaging {
     MG_KAPPA_HARMONIC = 1
 };
 int mg_gen_diffusion_hierarchy(mg_handle h, int top_level, int elements_per_dim, const double* kappa_top, int averaging);
+/* Matrix-free storage of the same level (opt-in; 3-D, whole handles, prune_zeros = 1): the level keeps the device kappa
+ * (8 B per row) and its right-hand side and stores no matrix at all -- no ELL tiles, diagonals, row classes or 1 / diagonal.
+ * Jacobi sweeps, residuals, the SpMV of mg_pcg and of the Chebyshev estimate and Chebyshev steps rebuild each row from the
+ * eight cells around its node while they march through the planes (mg_diffusion_mf.hip.h, one step per launch, counted under
+ * MG_PATH_MATRIX_FREE): 32 B per row and sweep instead of 56, 24 instead of 48 for the SpMV, 40 instead of 64 for a
+ * Chebyshev step.  The row is defined by the level mg_gen_diffusion_level(..., 1) stores and every result has the bits that
+ * level's one-step kernel gives (finite iterates; the p.q partial sums of the SpMV are per workgroup, so mg_pcg agrees to
+ * rounding, not to bits).  Transfers run unfused (residual, then the transfer kernel).  Refused with an error: 2-D handles,
+ * slab handles, level 0 (the coarsest level is factorised by the direct solve and read row by row by the coarse CG: it is
+ * always stored), mg_galerkin_level of such a level (it reads stored rows), Gauss-Seidel smoothers with such a level in
+ * the cycle (mg_smooth, mg_vcycle, mg_prepare_cycle, mg_fmg and mg_pcg refuse before anything is launched).  A bad kappa is
+ * refused as mg_gen_diffusion_level refuses it. */
+int mg_gen_diffusion_level_mf(mg_handle h, int level, int elements_per_dim, const double* kappa);
+/* mg_gen_diffusion_hierarchy with matrix-free levels: levels above level 0 with at least min_rows rows keep their kappa
+ * and no matrix; smaller levels and always level 0 (which the direct solve factorises) are stored as today. */
+int mg_gen_diffusion_hierarchy_mf(mg_handle h, int top_level, int elements_per_dim, const double* kappa_top, int averaging,
+                                  int64_t min_rows);
+/* *on = 1 if the level is matrix-free, *kappa_bytes = the device bytes of its kappa (0 otherwise) */
+int mg_level_matrix_free(mg_handle h, int level, int* on, int64_t* kappa_bytes);
 /* getJacobiMatrices (multigrid.py:48-56) as a stand-alone set-up kernel, for callers that
  * want the reference's split operands back: for every stored entry a_ij of the CSR matrix
  * writes scaled[q] = a_ij / a_ii computed as (1/a_ii) * a_ij, keep[q] = 1 unless the entry
@@ -537,7 +556,8 @@ enum mg_smoother_path {
     MG_PATH_BLOCK = 7,          /* 2..4 sweeps per launch on blocks resident on the CU (sdia_jacobi_block, "fuse_block")   */
     MG_PATH_K2D = 8,            /* 2..5 sweeps per launch on 2-D levels (sdia_jacobik2d, "fuse_2d")                        */
     MG_PATH_SMALL = 9,          /* all sweeps of a call in one launch of one workgroup (sdia_jacobi_small, "fuse_small")  */
-    MG_PATH_COUNT = 10
+    MG_PATH_MATRIX_FREE = 10,   /* one sweep per launch on a matrix-free diffusion level (diffusion_mf)                    */
+    MG_PATH_COUNT = 11
 };
 int mg_smoother_launches(mg_handle h, int level, int path, int64_t* launches, int64_t* sweeps, int64_t* tail_launches);
 int mg_reset_smoother_launches(mg_handle h);
@@ -553,7 +573,9 @@ int mg_reset_smoother_launches(mg_handle h);
  * "jacobik" = one launch of the K-sweep 2-D kernel with K = "fuse_2d_k", an error on levels that do not use it;
  * "jacobik3" = one launch of the K-sweep plane march on a 3-D level ("jacobik3!": wherever it applies), "jacobiblk" = one launch
  * of the block pass ("fuse_block"; "jacobiblk!": whatever the level's size), errors on levels that do not use them;
- * "gs" = one full Gauss-Seidel sweep, all colours, with the configured Gauss-Seidel smoother).
+ * "gs" = one full Gauss-Seidel sweep, all colours, with the configured Gauss-Seidel smoother;
+ * "spmv" = one SpMV without the dot product, with the level's one-step kernel; "diffusion_mf", "diffusion_mf:jacobi",
+ * ":residual", ":spmv", ":chebyshev" = the matrix-free diffusion march in that mode, an error on stored levels).
  * Used by bench.py for the roofline figure; its launches leave mg_smoother_launches as they were.  mg_sync waits for
  * the handle's stream. */
 int mg_time_kernel(mg_handle h, const char* kernel, int level, int reps, double* avg_ms);

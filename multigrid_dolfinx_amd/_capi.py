@@ -21,7 +21,7 @@ MG_NORM_L2, MG_NORM_MASS = 0, 1
 MG_KAPPA_ARITHMETIC, MG_KAPPA_HARMONIC = 0, 1
 # enum mg_smoother_path, in its order (mg_smoother_launches)
 SMOOTHER_PATHS = ("slice", "sweep1c", "pair_class", "pair_plain", "ksweep", "ksweep_escape", "ksweep_slab", "block", "k2d",
-                  "small")
+                  "small", "matrix_free")
 
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double),
                           C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int64)
@@ -53,6 +53,9 @@ SIGNATURES = {
     "mg_gen_lattice_level": [_H, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
     "mg_gen_diffusion_level": [_H, C.c_int, C.c_int, C.c_void_p, C.c_int],
     "mg_gen_diffusion_hierarchy": [_H, C.c_int, C.c_int, C.c_void_p, C.c_int],
+    "mg_gen_diffusion_level_mf": [_H, C.c_int, C.c_int, C.c_void_p],
+    "mg_gen_diffusion_hierarchy_mf": [_H, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int64],
+    "mg_level_matrix_free": [_H, C.c_int, _ip, _i64p],
     "mg_jacobi_split": [C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                         C.c_void_p, C.c_void_p],
     "mg_set_params": [_H, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int],

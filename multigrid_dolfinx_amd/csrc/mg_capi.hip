@@ -8,6 +8,7 @@
 #include "mg_jacobik3d.hip.h"
 #include "mg_jacobiblk.hip.h"
 #include "mg_lattice.hip.h"
+#include "mg_diffusion_mf.hip.h"
 
 #include <dlfcn.h>
 #include <rccl/rccl.h>
@@ -179,6 +180,10 @@ struct Level {
     double cm[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     int64_t cls_lead = 0, cls_rows = 0;     // cls[row + cls_lead], zero padding of cls_lead entries on both sides
     double* dinv = nullptr;
+    // matrix-free diffusion level (mg_diffusion_mf.hip.h): kappa of the N^3 cells is all the matrix there is
+    bool mf = false;
+    double* kappa = nullptr;
+    int64_t kappa_n = 0;
     DVector v, v2, f, err, ftrue;
     DVector sw;                             // once-relaxed boundary planes of a slab (paired sweeps, world > 1)
     DVector fcg_x, fcg_p, fcg_q, fcg_b;     // mg_pcg on this level: iterate, direction, A p, the saved right-hand side
@@ -457,6 +462,15 @@ int need_matrix(mg_context* c, int level) {
     return 0;
 }
 
+// Code that reads a level's stored rows (values, columns, codes, diagonals, 1 / diagonal) asks here first: a matrix-free
+// diffusion level has a matrix (has_matrix) but keeps kappa and none of those arrays.
+int need_stored_rows(const mg_context* c, const Level& L, const std::string& who) {
+    if (L.mf)
+        return fail(who + ": level " + std::to_string((int)(&L - c->L.data())) + " is a matrix-free diffusion level (kappa only); " +
+                    "this reads stored rows");
+    return 0;
+}
+
 int need_grid(mg_context* c, int level) {
     MG_TRY(check_level(c, level));
     if (c->L[level].flat) return fail("level " + std::to_string(level) + " is flat (no grid): transfers are undefined");
@@ -574,6 +588,9 @@ void free_level(mg_context* c, Level& L) {
     L.h_offsets.clear();
     L.sdia = false;
     dev_free(c, L.dinv, (size_t)L.nslices * WAVE * L.R);
+    dev_free(c, L.kappa, (size_t)L.kappa_n);
+    L.kappa_n = 0;
+    L.mf = false;
     dev_free(c, L.perm, (size_t)L.n_global);
     vec_free(c, L, &L.v);
     vec_free(c, L, &L.v2);
@@ -801,6 +818,68 @@ int launch_lat_march(mg_context* c, const Level& L, int mode, const double* x_ro
     return launch_lat_march_t<64, 16, 256>(c, L, a, mode);
 }
 
+// Tiles, plane segments and grid of the matrix-free diffusion march on a level.  Four workgroups fit a CU (35 KB of LDS
+// each), so the launch runs in rounds of 4 x CUs items; a segment re-reads three planes to warm up.  The number of segments
+// (of at least sixteen planes) is the one with the best product of the last round's filling and the planes a segment keeps.
+struct MfPlan { int ntx, nty, nseg, seglen; unsigned nitems, ch, grid; };
+MfPlan mf_plan(const mg_context* c, const Level& L) {
+    MfPlan p{};
+    p.ntx = (L.g.nx + MF_TX - 1) / MF_TX;
+    p.nty = (L.g.ny + MF_TY - 1) / MF_TY;
+    const int64_t ntile = (int64_t)p.ntx * p.nty;
+    const int64_t slots = 4 * (int64_t)std::max(1, c->prop.multiProcessorCount);
+    int nseg = 1;
+    double best = 0.0;
+    for (int n = 1; n <= std::max(1, L.g.nz / 16); ++n) {
+        const int len = (L.g.nz + n - 1) / n;
+        const int64_t items = ntile * ((L.g.nz + len - 1) / len);
+        const double score = (double)items / (double)((items + slots - 1) / slots * slots) * (double)len / (double)(len + 3);
+        if (score > best) { best = score; nseg = n; }
+    }
+    p.seglen = (L.g.nz + nseg - 1) / nseg;
+    p.nseg = (L.g.nz + p.seglen - 1) / p.seglen;
+    p.nitems = (unsigned)(ntile * p.nseg);
+    p.ch = p.nitems >= 8u * 16u * 4u ? 16u : 1u;
+    p.grid = (p.nitems + 8u * p.ch - 1) / (8u * p.ch) * (8u * p.ch);
+    return p;
+}
+
+int launch_diffusion_mf(mg_context* c, const Level& L, int mode, bool dot, const double* x_rows, const double* f_rows,
+                        double* out_rows, double* partials, unsigned* grid_out, double alpha, double beta) {
+    const MfPlan p = mf_plan(c, L);
+    MfArgs a{};
+    a.x = x_rows; a.f = f_rows; a.xp = out_rows; a.out = out_rows; a.kappa = L.kappa; a.partials = partials;
+    a.nx = L.g.nx; a.ny = L.g.ny; a.nz = L.g.nz; a.N = L.N; a.P = L.g.plane;
+    a.ntx = p.ntx; a.nty = p.nty; a.nseg = p.nseg; a.seglen = p.seglen; a.nitems = p.nitems; a.ch = p.ch;
+    a.h = 1.0 / (double)L.N;
+    a.omega = mode == MODE_CHEB ? alpha : c->omega;
+    a.beta = beta;
+    if (grid_out) *grid_out = p.grid;
+    const dim3 grid(p.grid), blk(MF_NT);
+    if (mode == MODE_JACOBI) hipLaunchKernelGGL((diffusion_mf<MODE_JACOBI, false>), grid, blk, 0, c->stream, a);
+    else if (mode == MODE_RESIDUAL) hipLaunchKernelGGL((diffusion_mf<MODE_RESIDUAL, false>), grid, blk, 0, c->stream, a);
+    else if (mode == MODE_CHEB) hipLaunchKernelGGL((diffusion_mf<MODE_CHEB, false>), grid, blk, 0, c->stream, a);
+    else if (mode == MODE_SPMV && dot) hipLaunchKernelGGL((diffusion_mf<MODE_SPMV, true>), grid, blk, 0, c->stream, a);
+    else if (mode == MODE_SPMV) hipLaunchKernelGGL((diffusion_mf<MODE_SPMV, false>), grid, blk, 0, c->stream, a);
+    else return fail("matrix-free diffusion levels have no kernel for this mode");
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// f (and / or 1 / diagonal) of the level gen_diffusion would store from a whole device kappa, without the matrix
+int launch_diffusion_rhs(mg_context* c, const Level& L, const double* d_kappa, double* f_rows, double* dinv_rows) {
+    DiffusionArgs d{};
+    GenArgs& a = d.ga;
+    a.g = L.g; a.N = L.N; a.dim = 3; a.prune = 1;
+    a.h = 1.0 / (double)L.N;
+    a.fh = -12.0 * std::pow(a.h, 3.0);
+    d.kappa = d_kappa;
+    d.kc0 = 0;
+    hipLaunchKernelGGL(gen_diffusion_rhs, grid3(L.g, L.g.nk), dim3(kPlaneBlock), 0, c->stream, d, f_rows, dinv_rows);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 // out = op(A, x) over all owned slices of the level
 int launch_ell(mg_context* c, const Level& L, int mode, bool dot, const double* x_base, const double* f_rows,
                double* out_rows, double* partials, const int* done, unsigned* grid_out = nullptr,
@@ -810,6 +889,12 @@ int launch_ell(mg_context* c, const Level& L, int mode, bool dot, const double* 
     // (MODE_CHEB: one Chebyshev step with the step scalars alpha, beta; x_{k-1} is read from out_rows)
     if (slice_count < 0) slice_count = L.nslices - slice0;
     if (slice_count == 0) return 0;
+    if (L.mf) {
+        // matrix-free diffusion level: the rows rebuilt from kappa (mg_diffusion_mf.hip.h); whole levels only
+        if (done || slice0 != 0 || slice_count != L.nslices || gap != 0 || mode == MODE_GS)
+            return fail("matrix-free diffusion levels run whole-level Jacobi, residual, SpMV and Chebyshev launches only");
+        return launch_diffusion_mf(c, L, mode, dot, x_base + L.g.lead, f_rows, out_rows, partials, grid_out, alpha, beta);
+    }
     // whole large 3-D levels with row classes: one sweep as a plane march (mg_jacobi2.hip.h, sdia_sweep1c)
     if (!dot && !done && mode != MODE_SPMV && slice0 == 0 && slice_count == L.nslices && sweep1c_ok(c, L))
         return launch_sweep1c(c, L, mode, x_base + L.g.lead, f_rows, out_rows, color, alpha, beta);
@@ -1562,6 +1647,7 @@ int launch_jacobikc(mg_context* c, const Level& L, int K, const double* x_rows, 
 // Is lattice_color(COLOR_LATTICE9) a valid Gauss-Seidel colouring of the level's matrix?  (structure of the stored
 // non-zeros, in whatever format the level has)
 int check_coloring(mg_context* c, Level& L) {
+    MG_TRY(need_stored_rows(c, L, "the colouring check of the Gauss-Seidel smoothers"));
     EllArgs a{};
     a.vals = L.vals; a.cols = L.cols; a.codes = L.codes; a.offsets = L.offsets; a.W = L.W;
     a.nloc = L.nloc; a.lead = L.g.lead; a.dinv = L.dinv; a.color_kind = COLOR_LATTICE9; a.grow0 = L.row0; a.gnx = L.g.nx; a.gny = L.g.ny;
@@ -1859,6 +1945,18 @@ void cheb_steps(double lo, double hi, int m, double* alpha, double* beta) {
 // nw Jacobi sweeps (Chebyshev: a polynomial of degree nw); v halos must be valid on entry and are valid on exit.
 int smooth(mg_context* c, int level, int nw) {
     Level& L = c->L[level];
+    if (L.mf && c->smoother != MG_SMOOTH_JACOBI && c->smoother != MG_SMOOTH_CHEBYSHEV)
+        return fail("level " + std::to_string(level) + " is a matrix-free diffusion level: Gauss-Seidel smoothers (RBGS, MCGS) "
+                    "need stored rows; use Jacobi or Chebyshev");
+    if (L.mf && c->smoother == MG_SMOOTH_JACOBI) {
+        // one sweep per launch, the rows rebuilt from kappa (the fused passes all read stored rows or row classes)
+        for (int s = 0; s < nw; ++s) {
+            MG_TRY(launch_ell(c, L, MODE_JACOBI, false, L.v.base, L.f.rows, L.v2.rows, nullptr, nullptr));
+            count_pass(c, level, MG_PATH_MATRIX_FREE, 1, 1);
+            std::swap(L.v, L.v2);
+        }
+        return 0;
+    }
     if (c->smoother == MG_SMOOTH_CHEBYSHEV) {
         // one step per launch of whatever kernel launch_ell picks for a Jacobi sweep of the level (counted under its path):
         // x_{k-1} lives in v2, which each step overwrites row by row with x_{k+1} before v and v2 swap; slabs exchange the
@@ -1888,7 +1986,8 @@ int smooth(mg_context* c, int level, int nw) {
             std::swap(L.v, L.v2);
             return 0;
         }
-        const int one_path = sweep1c_ok(c, L) ? MG_PATH_SWEEP1C : MG_PATH_SLICE;     // (launch_ell's choice for a whole level)
+        // (launch_ell's choice for a whole level)
+        const int one_path = L.mf ? MG_PATH_MATRIX_FREE : sweep1c_ok(c, L) ? MG_PATH_SWEEP1C : MG_PATH_SLICE;
         for (int s = 0; s < nw; ++s) {
             MG_TRY(launch_ell(c, L, MODE_CHEB, false, L.v.base, L.f.rows, L.v2.rows, nullptr, nullptr, nullptr, 0, -1, 0, 0, 0,
                               al[(size_t)s], be[(size_t)s]));
@@ -2199,7 +2298,7 @@ int check_p1_stencil(mg_context* c, Level& L) {
         const int K = kuhn_lin(c, L, lin);
         auto in = [&](int64_t o) { return std::find(lin, lin + K, o) != lin + K; };
         bool ok = true;
-        if (!L.has_matrix) {
+        if (!L.has_matrix || L.mf) {           // (matrix-free diffusion levels: the seven axis offsets, by construction)
         } else if (L.flat) {
             ok = false;
         } else if (L.sdia) {
@@ -2429,6 +2528,15 @@ int cheb_estimate(mg_context* c, int level) {
     double* const z = raw + 2 * vt + vec_front(L) + L.g.lead;
     double* const q = raw + 3 * vt + vec_front(L) + L.g.lead;
     const int64_t n = L.nloc;
+    // (a matrix-free level keeps no 1 / diagonal: the estimate rebuilds it from kappa for as long as it runs)
+    DevTemp mf_dinv;
+    const double* dinv = L.dinv;
+    if (L.mf) {
+        MG_TRY(mf_dinv.alloc((size_t)n * sizeof(double)));
+        c->cheb_peak_bytes += n * (int64_t)sizeof(double);
+        MG_TRY(launch_diffusion_rhs(c, L, L.kappa, nullptr, static_cast<double*>(mf_dinv.p)));
+        dinv = static_cast<const double*>(mf_dinv.p);
+    }
     const dim3 grid((unsigned)std::min<int64_t>(4096, std::max<int64_t>(1, (n + 255) / 256))), blk(256);
     auto scalar = [&](const double* x, const double* y, double* out) -> int {
         MG_TRY(dot_device(c, L, x, y, 0));
@@ -2437,7 +2545,7 @@ int cheb_estimate(mg_context* c, int level) {
         *out = c->h_scalars[0];
         return 0;
     };
-    hipLaunchKernelGGL(cheb_start, grid, blk, 0, c->stream, r, z, p.rows, L.dinv, n, L.row0);
+    hipLaunchKernelGGL(cheb_start, grid, blk, 0, c->stream, r, z, p.rows, dinv, n, L.row0);
     HIP_TRY(hipGetLastError());
     double rz = 0.0;
     MG_TRY(scalar(r, z, &rz));
@@ -2451,7 +2559,7 @@ int cheb_estimate(mg_context* c, int level) {
             if (!(pq > 0.0) || !std::isfinite(pq)) break;          // breakdown: A not positive definite on the Krylov space
             const double alpha = rz / pq;
             al.push_back(alpha);
-            hipLaunchKernelGGL(cheb_cg_update, grid, blk, 0, c->stream, r, z, q, L.dinv, n, alpha);
+            hipLaunchKernelGGL(cheb_cg_update, grid, blk, 0, c->stream, r, z, q, dinv, n, alpha);
             HIP_TRY(hipGetLastError());
             double rz_new = 0.0;
             MG_TRY(scalar(r, z, &rz_new));
@@ -2521,6 +2629,7 @@ int build_direct(mg_context* c) {
     DirectSolver& d = c->direct;
     d.tried = true;
     Level& L = c->L[0];
+    MG_TRY(need_stored_rows(c, L, "the coarsest solve"));
     if (!c->use_direct || L.flat || L.g.lead != 0) return 0;
     const int64_t plane = L.g.plane;
     const int nz = L.g.nz;
@@ -2726,7 +2835,7 @@ int vcycle(mg_context* c, int level) {
     if (level == 0) return coarse_solve(c, nullptr, nullptr);
     Level& C = c->L[level - 1];
     MG_TRY(smooth(c, level, c->mu1));
-    if (c->restriction == MG_RESTRICT_INJECTION && c->fuse_restrict) {
+    if (c->restriction == MG_RESTRICT_INJECTION && c->fuse_restrict && !c->L[level].mf) {
         MG_TRY(residual_restrict_fused(c, level));
     } else {
         MG_TRY(residual(c, level));
@@ -2755,6 +2864,12 @@ void drop_graphs(mg_context* c) {
 // Everything a V-cycle from `level` builds or allocates on first use (the direct coarsest solve and its validation, the
 // colouring checks, the parked-sweep and error vectors): afterwards a cycle -- and its capture -- only enqueues work.
 int prepare_cycle(mg_context* c, int level) {
+    // (refused here, before the colouring check and before anything is captured; smooth() refuses a single call)
+    if (c->smoother == MG_SMOOTH_RBGS || c->smoother == MG_SMOOTH_MCGS)
+        for (int l = 1; l <= level; ++l)
+            if (c->L[l].mf)
+                return fail("level " + std::to_string(l) + " is a matrix-free diffusion level: Gauss-Seidel smoothers (RBGS, MCGS) "
+                            "need stored rows; use Jacobi or Chebyshev");
     if (!c->direct.tried) { MG_TRY(build_direct(c)); MG_TRY(validate_direct(c)); }
     if (c->smoother == MG_SMOOTH_MCGS)                   // (the check synchronises: not inside a capture)
         for (int l = 1; l <= level; ++l)
@@ -2884,7 +2999,8 @@ int fcg_solve(mg_context* c, int level, double rtol, int max_iter, double* hist,
         c->fcg_work_n = 8 + kFcgFold + 3 * gmax;
         MG_TRY(dev_alloc(c, &c->fcg_work, (size_t)c->fcg_work_n));
     }
-    const int64_t nspmv = blocks_for(L.nslices, WAVES_PER_BLOCK);       // partial sums of the SpMV (launch_ell with dot)
+    // partial sums of the SpMV (launch_ell with dot): one per block of the level's kernel
+    const int64_t nspmv = L.mf ? (int64_t)mf_plan(c, L).grid : (int64_t)blocks_for(L.nslices, WAVES_PER_BLOCK);
     if (c->fcg_spmv_n < nspmv) {
         dev_free(c, c->fcg_spmv, (size_t)c->fcg_spmv_n);
         c->fcg_spmv_n = 0;
@@ -4050,6 +4166,7 @@ int galerkin_level(mg_context* c, int level) {
     MG_TRY(need_matrix(c, level));
     MG_TRY(need_grid(c, level));
     Level& F = c->L[level];
+    MG_TRY(need_stored_rows(c, F, "mg_galerkin_level (the Galerkin product; generate the level with mg_gen_diffusion_level instead)"));
     if (!F.replicated) return fail("Galerkin coarse levels need a whole fine level, not a slab");
     if (F.N < 2 || (F.N & 1)) return fail("Galerkin coarse levels need an even elements_per_dim");
     MG_TRY(check_p1_stencil(c, F));
@@ -4409,43 +4526,142 @@ int mg_gen_diffusion_level(mg_handle c, int level, int N, const double* kappa, i
     return gen_diffusion_level(c, level, N, static_cast<const double*>(d_kappa.p), kc0, prune_zeros);
 }
 
-int mg_gen_diffusion_hierarchy(mg_handle c, int top_level, int N, const double* kappa_top, int averaging) {
-    MG_TRY(check_level(c, top_level, false));
+namespace {
+
+// the matrix-free level from a whole device kappa (N^3 cells), which the level takes over on success
+int gen_diffusion_level_mf(mg_context* c, int level, int N, double* d_kappa, int64_t n) {
+    Level& L = c->L[level];
+    free_level(c, L);
+    const int rc = [&]() -> int {
+        MG_TRY(setup_geometry(c, L, level, N));
+        L.W = 7;
+        L.R = c->rows_per_lane;         // (the slice count is what callers of launch_ell take a whole level's range from)
+        L.nslices = (L.nloc + (int64_t)WAVE * L.R - 1) / ((int64_t)WAVE * L.R);
+        MG_TRY(alloc_level_vectors(c, L));
+        MG_TRY(launch_diffusion_rhs(c, L, d_kappa, L.f.rows, nullptr));
+        if (level + 1 < c->nlev) {
+            MG_TRY(vec_alloc(c, L, &L.ftrue));
+            HIP_TRY(hipMemcpyAsync(L.ftrue.base, L.f.base, (size_t)L.xlen * 8, hipMemcpyDeviceToDevice, c->stream));
+        }
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        // what the stored level would report: seven entries per interior row less the columns on the boundary, one per boundary row
+        const int64_t m = N - 1;
+        L.nnz_stored = L.nnz_nonzero = (unsigned long long)(m * m * m + 6 * m * m * (m - 1) + (L.n_global - m * m * m));
+        L.rep_sym = 1;
+        L.rb_ok = false;
+        L.mf = true;
+        L.kappa = d_kappa;
+        L.kappa_n = n;
+        c->bytes += n * (int64_t)sizeof(double);
+        L.set = true;
+        L.has_matrix = true;
+        return 0;
+    }();
+    if (rc) {
+        const std::string why = g_err;
+        free_level(c, L);
+        g_err = why;
+    }
+    return rc;
+}
+
+int mf_refusals(mg_context* c, const char* who) {
+    if (c->dim != 3) return fail(std::string(who) + ": matrix-free diffusion levels are 3-D only (this handle is 2-D)");
+    if (c->comm.active()) return fail(std::string(who) + ": matrix-free diffusion levels need a whole (not slab) handle");
+    return 0;
+}
+
+}  // namespace
+
+int mg_gen_diffusion_level_mf(mg_handle c, int level, int N, const double* kappa) {
+    MG_TRY(check_level(c, level, false));
+    MG_TRY(mf_refusals(c, "mg_gen_diffusion_level_mf"));
+    if (level == 0)
+        return fail("mg_gen_diffusion_level_mf: level 0 is the coarsest level, which the direct solve factorises and the coarse "
+                    "CG reads row by row: it needs stored rows (mg_gen_diffusion_level)");
+    if (N <= 0) return fail("elements_per_dim must be positive");
+    if (!kappa) return fail("null kappa");
+    HIP_TRY(hipSetDevice(c->device));
+    Level geo;                                   // checked before the level is touched: a refusal leaves it as it was
+    MG_TRY(setup_geometry(c, geo, level, N));
+    const int64_t n = cell_plane(c, N) * N;
+    DevTemp d_kappa;
+    MG_TRY(d_kappa.alloc((size_t)n * 8));
+    HIP_TRY(hipMemcpy(d_kappa.p, kappa, (size_t)n * 8, hipMemcpyHostToDevice));
+    MG_TRY(check_kappa(c, static_cast<const double*>(d_kappa.p), n, 0, N));
+    MG_TRY(gen_diffusion_level_mf(c, level, N, static_cast<double*>(d_kappa.p), n));
+    d_kappa.p = nullptr;                         // the level owns it now
+    return 0;
+}
+
+namespace {
+
+// Levels top_level .. 0 from the top level's kappa, coarsened on the device; levels above level 0 with at least min_rows rows
+// become matrix-free and take their kappa over, the others are stored (generated before their kappa is coarsened and freed).
+// At most two kappa fields are alive at a time besides those the matrix-free levels keep.
+int gen_diffusion_hierarchy(mg_context* c, const std::string& who, int top_level, int N, const double* kappa_top, int averaging,
+                            int64_t min_rows) {
     if (N <= 0) return fail("elements_per_dim must be positive");
     if (!kappa_top) return fail("null kappa");
     if (averaging != MG_KAPPA_ARITHMETIC && averaging != MG_KAPPA_HARMONIC) return fail("unknown kappa averaging");
     if (c->comm.active())
-        return fail("mg_gen_diffusion_hierarchy needs a whole (not slab) handle: on slabs, call mg_gen_diffusion_level per "
-                    "level");
+        return fail(who + " needs a whole (not slab) handle: on slabs, call mg_gen_diffusion_level per level");
     if (N % (1 << top_level))
-        return fail("mg_gen_diffusion_hierarchy needs an even elements_per_dim on every level above level 0 (" +
-                    std::to_string(N) + " is not N0 * 2^" + std::to_string(top_level) + ")");
+        return fail(who + " needs an even elements_per_dim on every level above level 0 (" + std::to_string(N) +
+                    " is not N0 * 2^" + std::to_string(top_level) + ")");
     HIP_TRY(hipSetDevice(c->device));
     Level geo;
     MG_TRY(setup_geometry(c, geo, top_level, N));
     int64_t n = cell_plane(c, N) * N;
-    DevTemp fine, coarse;                        // at most two kappa fields alive at a time
+    DevTemp fine, coarse;
     MG_TRY(fine.alloc((size_t)n * 8));
     HIP_TRY(hipMemcpy(fine.p, kappa_top, (size_t)n * 8, hipMemcpyHostToDevice));
     MG_TRY(check_kappa(c, static_cast<const double*>(fine.p), n, 0, N));
-    MG_TRY(gen_diffusion_level(c, top_level, N, static_cast<const double*>(fine.p), 0, 1));
-    for (int l = top_level - 1, Nl = N / 2; l >= 0; --l, Nl /= 2) {
+    for (int l = top_level, Nl = N; l >= 0; --l, Nl /= 2) {
         n = cell_plane(c, Nl) * Nl;
-        MG_TRY(coarse.alloc((size_t)n * 8));
-        const unsigned nb = (unsigned)std::max<int64_t>(1, std::min<int64_t>(8192, (n + 255) / 256));
-        if (c->dim == 3)
-            hipLaunchKernelGGL(kappa_coarsen<3>, dim3(nb), dim3(256), 0, c->stream, static_cast<const double*>(fine.p),
-                               static_cast<double*>(coarse.p), Nl, averaging == MG_KAPPA_HARMONIC ? 1 : 0);
-        else
-            hipLaunchKernelGGL(kappa_coarsen<2>, dim3(nb), dim3(256), 0, c->stream, static_cast<const double*>(fine.p),
-                               static_cast<double*>(coarse.p), Nl, averaging == MG_KAPPA_HARMONIC ? 1 : 0);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        HIP_TRY(hipFree(fine.p));
+        const int64_t rows = c->dim == 3 ? ((int64_t)Nl + 1) * (Nl + 1) * (Nl + 1) : ((int64_t)Nl + 1) * (Nl + 1);
+        const bool mf = l > 0 && rows >= min_rows;
+        if (!mf) MG_TRY(gen_diffusion_level(c, l, Nl, static_cast<const double*>(fine.p), 0, 1));
+        if (l > 0) {
+            const int Nc = Nl / 2;
+            const int64_t nc = cell_plane(c, Nc) * Nc;
+            MG_TRY(coarse.alloc((size_t)nc * 8));
+            const unsigned nb = (unsigned)std::max<int64_t>(1, std::min<int64_t>(8192, (nc + 255) / 256));
+            if (c->dim == 3)
+                hipLaunchKernelGGL(kappa_coarsen<3>, dim3(nb), dim3(256), 0, c->stream, static_cast<const double*>(fine.p),
+                                   static_cast<double*>(coarse.p), Nc, averaging == MG_KAPPA_HARMONIC ? 1 : 0);
+            else
+                hipLaunchKernelGGL(kappa_coarsen<2>, dim3(nb), dim3(256), 0, c->stream, static_cast<const double*>(fine.p),
+                                   static_cast<double*>(coarse.p), Nc, averaging == MG_KAPPA_HARMONIC ? 1 : 0);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipStreamSynchronize(c->stream));
+        }
+        if (mf) MG_TRY(gen_diffusion_level_mf(c, l, Nl, static_cast<double*>(fine.p), n));     // (the level owns its kappa now)
+        else HIP_TRY(hipFree(fine.p));
         fine.p = coarse.p;
         coarse.p = nullptr;
-        MG_TRY(gen_diffusion_level(c, l, Nl, static_cast<const double*>(fine.p), 0, 1));
     }
+    return 0;
+}
+
+}  // namespace
+
+int mg_gen_diffusion_hierarchy(mg_handle c, int top_level, int N, const double* kappa_top, int averaging) {
+    MG_TRY(check_level(c, top_level, false));
+    return gen_diffusion_hierarchy(c, "mg_gen_diffusion_hierarchy", top_level, N, kappa_top, averaging, INT64_MAX);
+}
+
+int mg_gen_diffusion_hierarchy_mf(mg_handle c, int top_level, int N, const double* kappa_top, int averaging, int64_t min_rows) {
+    MG_TRY(check_level(c, top_level, false));
+    MG_TRY(mf_refusals(c, "mg_gen_diffusion_hierarchy_mf"));
+    return gen_diffusion_hierarchy(c, "mg_gen_diffusion_hierarchy_mf", top_level, N, kappa_top, averaging, min_rows);
+}
+
+int mg_level_matrix_free(mg_handle c, int level, int* on, int64_t* kappa_bytes) {
+    MG_TRY(check_level(c, level));
+    const Level& L = c->L[level];
+    if (on) *on = L.mf ? 1 : 0;
+    if (kappa_bytes) *kappa_bytes = L.mf ? L.kappa_n * (int64_t)sizeof(double) : 0;
     return 0;
 }
 
@@ -4683,7 +4899,7 @@ int mg_quadratic_form(mg_handle c, int level, int which, double* out) {
     DVector* v = pick(L, which);
     if (!v || !v->raw || v == &L.v2) return fail("vector is not available for a quadratic form");
     MG_TRY(exchange_halo(c, L, *v));
-    const unsigned grid = blocks_for(L.nslices, WAVES_PER_BLOCK);
+    const unsigned grid = L.mf ? mf_plan(c, L).grid : blocks_for(L.nslices, WAVES_PER_BLOCK);
     double* parts = nullptr;
     MG_TRY(dev_alloc(c, &parts, grid));
     int rc = launch_ell(c, L, MODE_SPMV, true, v->base, nullptr, L.v2.rows, parts, nullptr);
@@ -4996,6 +5212,22 @@ int mg_time_kernel(mg_handle c, const char* kernel, int level, int reps, double*
         if (k == "gs") {            // one full Gauss-Seidel sweep (all colours) with the configured colouring
             if (c->smoother == MG_SMOOTH_JACOBI) return fail("the configured smoother is Jacobi");
             return smooth(c, level, 1);
+        }
+        if (k == "spmv") return launch_ell(c, L, MODE_SPMV, false, L.v.base, nullptr, L.v2.rows, nullptr, nullptr);
+        if (k.rfind("diffusion_mf", 0) == 0) {      // the matrix-free march in one mode: "diffusion_mf[:jacobi|:residual|:spmv|:chebyshev]"
+            if (!L.mf) return fail("level is not a matrix-free diffusion level");
+            const std::string m = k.size() > 12 ? k.substr(12) : ":jacobi";
+            if (m == ":jacobi") return launch_ell(c, L, MODE_JACOBI, false, L.v.base, L.f.rows, L.v2.rows, nullptr, nullptr);
+            if (m == ":residual") return residual(c, level);
+            if (m == ":spmv") return launch_ell(c, L, MODE_SPMV, false, L.v.base, nullptr, L.v2.rows, nullptr, nullptr);
+            if (m == ":chebyshev") {
+                double lo = 0.0, hi = 0.0, al[2], be[2];
+                MG_TRY(cheb_interval(c, level, &lo, &hi));
+                cheb_steps(lo, hi, 2, al, be);
+                return launch_ell(c, L, MODE_CHEB, false, L.v.base, L.f.rows, L.v2.rows, nullptr, nullptr, nullptr, 0, -1, 0, 0, 0,
+                                  al[1], be[1]);
+            }
+            return fail("unknown mode of diffusion_mf: " + m);
         }
         if (k == "residual") return residual(c, level);
         if (k == "restrict") return level > 0 ? restrict_to(c, level, c->restriction) : fail("level 0");

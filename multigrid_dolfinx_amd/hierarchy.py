@@ -302,34 +302,63 @@ class DeviceHierarchy:
             raise ValueError(f"level {level}: kappa has {k.size} entries, the level has {self.elements(level) ** self.dim} cells")
         return k
 
-    def gen_diffusion_level(self, level: int, kappa, prune_zeros: bool = True):
+    def gen_diffusion_level(self, level: int, kappa, prune_zeros: bool = True, matrix_free: bool = False):
         """Device-side level of -div(kappa grad u), one kappa per cell (`mg_gen_diffusion_level`; the host restatement is
-        `poisson.diffusion_level`).  On slabs every rank passes the whole kappa of the level."""
+        `poisson.diffusion_level`).  On slabs every rank passes the whole kappa of the level.  `matrix_free=True`
+        (`mg_gen_diffusion_level_mf`; 3-D, whole handles, pruned) keeps kappa instead of a matrix: same results bit for bit."""
         k = self._kappa(level, kappa)
+        if matrix_free:
+            if not prune_zeros:
+                raise ValueError("matrix-free diffusion levels are pruned levels (prune_zeros=True)")
+            check(self._lib.mg_gen_diffusion_level_mf(self._h, self._idx(level), self.elements(level), ptr(k)))
+            return
         check(self._lib.mg_gen_diffusion_level(self._h, self._idx(level), self.elements(level), ptr(k),
                                                1 if prune_zeros else 0))
 
-    def gen_diffusion_hierarchy(self, kappa, averaging: str = "arithmetic", top_level: Optional[int] = None):
+    def gen_diffusion_hierarchy(self, kappa, averaging: str = "arithmetic", top_level: Optional[int] = None,
+                                matrix_free_min_rows: Optional[int] = None):
         """Levels top_level (default: the finest) .. coarsest from one kappa, coarsened on the device
-        (`mg_gen_diffusion_hierarchy`, as `poisson.coarsen_kappa` does it); pruned; whole handles only."""
+        (`mg_gen_diffusion_hierarchy`, as `poisson.coarsen_kappa` does it); pruned; whole handles only.  With
+        `matrix_free_min_rows` the levels above the coarsest with at least that many rows are matrix-free
+        (`mg_gen_diffusion_hierarchy_mf`)."""
         top = self.finest_level if top_level is None else top_level
         k = self._kappa(top, kappa)
         avg = {"arithmetic": _capi.MG_KAPPA_ARITHMETIC, "harmonic": _capi.MG_KAPPA_HARMONIC}[averaging]
+        if matrix_free_min_rows is not None:
+            check(self._lib.mg_gen_diffusion_hierarchy_mf(self._h, self._idx(top), self.elements(top), ptr(k), avg,
+                                                          int(matrix_free_min_rows)))
+            return
         check(self._lib.mg_gen_diffusion_hierarchy(self._h, self._idx(top), self.elements(top), ptr(k), avg))
+
+    def level_matrix_free(self, level: int) -> bool:
+        """True if the level keeps kappa instead of a matrix (`mg_level_matrix_free`)."""
+        on = C.c_int(0)
+        check(self._lib.mg_level_matrix_free(self._h, self._idx(level), C.byref(on), None))
+        return bool(on.value)
+
+    def level_kappa_bytes(self, level: int) -> int:
+        """Device bytes of the kappa a matrix-free level keeps (8 per cell); 0 for a stored level."""
+        nbytes = C.c_int64(0)
+        check(self._lib.mg_level_matrix_free(self._h, self._idx(level), None, C.byref(nbytes)))
+        return int(nbytes.value)
 
     @classmethod
     def synthetic_diffusion(cls, dim: int, coarsest_level: int, finest_level: int, kappa, c: int = 8,
                             coarse: str = "arithmetic", mu1: int = 2, mu2: int = 2, omega: float = 2.0 / 3.0,
-                            smoother: str = "jacobi", prune_zeros: bool = True, device: int = 0, comm=None, **tuning):
+                            smoother: str = "jacobi", prune_zeros: bool = True, device: int = 0, comm=None,
+                            matrix_free_min_rows: Optional[int] = None, **tuning):
         """Hierarchy of -div(kappa grad u) levels from the finest level's kappa, with the P1 transfers (P and R = P^T).
         Coarse levels: `coarse="arithmetic"` / `"harmonic"` regenerate them from a coarsened kappa -- on one handle with
         `mg_gen_diffusion_hierarchy`, on slabs (`comm`) level by level with `poisson.coarsen_kappa` on the host --
-        and `"galerkin"` takes P^T A P (whole handles only)."""
+        and `"galerkin"` takes P^T A P (whole handles only).  `matrix_free_min_rows`: regenerated levels with at least
+        that many rows keep kappa instead of a matrix (whole handles, 3-D, pruned; `gen_diffusion_hierarchy`)."""
         from .poisson import coarsen_kappa
         if coarse not in ("arithmetic", "harmonic", "galerkin"):
             raise ValueError("coarse must be 'arithmetic', 'harmonic' or 'galerkin'")
         if coarse == "galerkin" and comm is not None:
             raise ValueError("Galerkin coarse levels need a whole handle, not slabs")
+        if matrix_free_min_rows is not None and (coarse == "galerkin" or comm is not None or not prune_zeros):
+            raise ValueError("matrix-free levels need regenerated, pruned coarse levels on a whole handle")
         h = cls(dim, coarsest_level, finest_level, c=c, device=device, **tuning)
         if comm is not None:
             comm(h)
@@ -343,7 +372,7 @@ class DeviceHierarchy:
                 if level > coarsest_level:
                     k = coarsen_kappa(k, dim, coarse)
         else:
-            h.gen_diffusion_hierarchy(kappa, coarse)
+            h.gen_diffusion_hierarchy(kappa, coarse, matrix_free_min_rows=matrix_free_min_rows)
         h.set_params(mu1, mu2, omega, restriction="p1_transpose", smoother=smoother)
         h.set_prolongation("p1")
         return h
