@@ -198,6 +198,20 @@ int mg_gen_diffusion_hierarchy_mf(mg_handle h, int top_level, int elements_per_d
                                   int64_t min_rows);
 /* *on = 1 if the level is matrix-free, *kappa_bytes = the device bytes of its kappa (0 otherwise) */
 int mg_level_matrix_free(mg_handle h, int level, int* on, int64_t* kappa_bytes);
+/* Sensitivity of the diffusion operator to kappa (no reference counterpart): out_dev[c] = d(a^T A(kappa) b) / d kappa_c for the
+ * N^3 cells c of a 3-D level, cell order as in mg_gen_diffusion_level.  A is linear in kappa, so neither kappa nor a matrix is read,
+ * only the level's grid dimensions: any whole 3-D grid level will do, stored, matrix-free or grid-only.  With a~, b~ = a, b with
+ * the boundary nodes taken as 0 (boundary rows are identity rows, interior rows have no boundary column),
+ *     out[c] = (h / 6) * sum over the 12 axis edges e = (i, j) of cell c of n_{c,e} (a~_i - a~_j) (b~_i - b~_j),   h = 1 / N,
+ * n_{c,e} = 2 where the cell's two other local coordinates at the edge are equal, else 1 (the weights of
+ * mg_gen_diffusion_level).  Summation order: mg_diffusion_adj.hip.h; poisson.diffusion_dkappa restates it bit for bit.
+ * a_dev, b_dev: device arrays of the level's n_global doubles in lexicographic node order (the numbering of generated
+ * levels), possibly the same pointer; out_dev: N^3 doubles on the device.  Runs on the handle's stream, which is synchronised
+ * before return (the caller must have finished producing a and b); nothing crosses to the host.  With u = A^-1 f and the
+ * adjoint solve A lambda = dJ/du (A is symmetric: the same hierarchy, one more mg_pcg), dJ/dkappa = -out(lambda, u).
+ * Refused with an error: 2-D handles, slab handles, flat levels, null pointers and pointers that are not device memory of the
+ * handle's device. */
+int mg_diffusion_dkappa(mg_handle h, int level, const double* a_dev, const double* b_dev, double* out_dev);
 /* getJacobiMatrices (multigrid.py:48-56) as a stand-alone set-up kernel, for callers that
  * want the reference's split operands back: for every stored entry a_ij of the CSR matrix
  * writes scaled[q] = a_ij / a_ii computed as (1/a_ii) * a_ij, keep[q] = 1 unless the entry
@@ -414,6 +428,8 @@ int mg_galerkin_hierarchy(mg_handle h, int top_level);
  *     "lattice_march"      wide lattice stencils (3-D P2 levels with stencil classes) as a plane march with five planes of x in
  *                          LDS instead of gathers from global memory (1); bit-identical either way
  *     "lattice_march_min_rows"  ... only on levels with at least this many owned rows (4194304)
+ *     "dkappa_gather"      1 = mg_diffusion_dkappa runs one thread per cell with sixteen loads through the caches instead of the
+ *                          plane march (0: the march measured 2.2 x faster at 1025^3); bit-identical either way
  *     "lattice_gs2"        1 = the nine-colour Gauss-Seidel sweep on whole 3-D lattice levels runs two colours per launch, out of
  *                          place (five passes over the vector instead of nine; the level's two iterate buffers swap);
  *                          bit-identical, but measured slower (its nine plane slots only fit 32-wide tiles) (0)
@@ -458,6 +474,14 @@ int mg_level_storage(mg_handle h, int level, int* symmetric, int64_t* first_asym
  * rows only unless gather != 0, in which case slabs are all-gathered first. */
 int mg_set_vector(mg_handle h, int level, int which, const double* host);
 int mg_get_vector(mg_handle h, int level, int which, double* host, int gather);
+/* The same two copies from / to DEVICE memory of the handle's device (no reference counterpart): `dev` holds n_global doubles in
+ * the caller's DoF numbering, the permute kernels read / write it directly -- no staging copy, nothing crosses to the host,
+ * mg_counters' uploads and downloads do not move.  The caller must have finished producing `dev` before the call (the handle's
+ * stream does not wait for other streams); both calls wait for the handle's stream before they return.  Refused with an error:
+ * slab handles, and a pointer hipPointerGetAttributes does not report as device memory of the handle's device (before anything
+ * is launched). */
+int mg_set_vector_device(mg_handle h, int level, int which, const double* dev);
+int mg_get_vector_device(mg_handle h, int level, int which, double* dev);
 int mg_zero_vector(mg_handle h, int level, int which);
 int mg_copy_vector(mg_handle h, int level, int dst_which, int src_which);
 
@@ -575,7 +599,8 @@ int mg_reset_smoother_launches(mg_handle h);
  * of the block pass ("fuse_block"; "jacobiblk!": whatever the level's size), errors on levels that do not use them;
  * "gs" = one full Gauss-Seidel sweep, all colours, with the configured Gauss-Seidel smoother;
  * "spmv" = one SpMV without the dot product, with the level's one-step kernel; "diffusion_mf", "diffusion_mf:jacobi",
- * ":residual", ":spmv", ":chebyshev" = the matrix-free diffusion march in that mode, an error on stored levels).
+ * ":residual", ":spmv", ":chebyshev" = the matrix-free diffusion march in that mode, an error on stored levels;
+ * "dkappa" / "dkappa_gather" = mg_diffusion_dkappa of (MG_VEC_V, MG_VEC_F) into MG_VEC_R as the plane march / one thread per cell).
  * Used by bench.py for the roofline figure; its launches leave mg_smoother_launches as they were.  mg_sync waits for
  * the handle's stream. */
 int mg_time_kernel(mg_handle h, const char* kernel, int level, int reps, double* avg_ms);

@@ -74,6 +74,9 @@ SIGNATURES = {
     "mg_level_storage": [_H, C.c_int, _ip, _i64p, _i64p, _ip, _ip, _i64p],
     "mg_set_vector": [_H, C.c_int, C.c_int, C.c_void_p],
     "mg_get_vector": [_H, C.c_int, C.c_int, C.c_void_p, C.c_int],
+    "mg_set_vector_device": [_H, C.c_int, C.c_int, C.c_void_p],
+    "mg_get_vector_device": [_H, C.c_int, C.c_int, C.c_void_p],
+    "mg_diffusion_dkappa": [_H, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
     "mg_zero_vector": [_H, C.c_int, C.c_int],
     "mg_copy_vector": [_H, C.c_int, C.c_int, C.c_int],
     "mg_smooth": [_H, C.c_int, C.c_int],

@@ -9,6 +9,7 @@
 #include "mg_jacobiblk.hip.h"
 #include "mg_lattice.hip.h"
 #include "mg_diffusion_mf.hip.h"
+#include "mg_diffusion_adj.hip.h"
 
 #include <dlfcn.h>
 #include <rccl/rccl.h>
@@ -275,6 +276,8 @@ struct mg_context {
     int64_t lattice_march_min_rows = 1 << 22;       // (measured on C5: the 129^3 and 65^3 lattices are faster with the gathering kernel)
     int lattice_gs2 = 0;            // nine-colour Gauss-Seidel on whole lattice levels: two colours per launch, out of place (lat_gs2;
                                     // measured slower than nine colour launches: 9.1 against 6.8 ms per sweep of the 513^3 lattice)
+    int dkappa_gather = 0;          // mg_diffusion_dkappa: 1 = one thread per cell reading through the caches instead of the plane march
+                                    // (1025^3: 12.5 ms against 5.75 for the march)
     int lattice_tile = 0;           // tile of that march: 0 / 1 = 64 x 16 cells (256 threads), 2 = 128 x 16 (512 threads)
     int lattice_segments = 0;       // plane segments per tile of that march, 0 = chosen from the tile count
     int slab_pair_form = 0;         // overlapped pair sweeps on slabs: 0 = chain beside one launch of the pass, 1 = boundary segments first
@@ -822,27 +825,28 @@ int launch_lat_march(mg_context* c, const Level& L, int mode, const double* x_ro
 // each), so the launch runs in rounds of 4 x CUs items; a segment re-reads three planes to warm up.  The number of segments
 // (of at least sixteen planes) is the one with the best product of the last round's filling and the planes a segment keeps.
 struct MfPlan { int ntx, nty, nseg, seglen; unsigned nitems, ch, grid; };
-MfPlan mf_plan(const mg_context* c, const Level& L) {
+MfPlan mf_plan_dims(const mg_context* c, int nx, int ny, int nz) {
     MfPlan p{};
-    p.ntx = (L.g.nx + MF_TX - 1) / MF_TX;
-    p.nty = (L.g.ny + MF_TY - 1) / MF_TY;
+    p.ntx = (nx + MF_TX - 1) / MF_TX;
+    p.nty = (ny + MF_TY - 1) / MF_TY;
     const int64_t ntile = (int64_t)p.ntx * p.nty;
     const int64_t slots = 4 * (int64_t)std::max(1, c->prop.multiProcessorCount);
     int nseg = 1;
     double best = 0.0;
-    for (int n = 1; n <= std::max(1, L.g.nz / 16); ++n) {
-        const int len = (L.g.nz + n - 1) / n;
-        const int64_t items = ntile * ((L.g.nz + len - 1) / len);
+    for (int n = 1; n <= std::max(1, nz / 16); ++n) {
+        const int len = (nz + n - 1) / n;
+        const int64_t items = ntile * ((nz + len - 1) / len);
         const double score = (double)items / (double)((items + slots - 1) / slots * slots) * (double)len / (double)(len + 3);
         if (score > best) { best = score; nseg = n; }
     }
-    p.seglen = (L.g.nz + nseg - 1) / nseg;
-    p.nseg = (L.g.nz + p.seglen - 1) / p.seglen;
+    p.seglen = (nz + nseg - 1) / nseg;
+    p.nseg = (nz + p.seglen - 1) / p.seglen;
     p.nitems = (unsigned)(ntile * p.nseg);
     p.ch = p.nitems >= 8u * 16u * 4u ? 16u : 1u;
     p.grid = (p.nitems + 8u * p.ch - 1) / (8u * p.ch) * (8u * p.ch);
     return p;
 }
+MfPlan mf_plan(const mg_context* c, const Level& L) { return mf_plan_dims(c, L.g.nx, L.g.ny, L.g.nz); }
 
 int launch_diffusion_mf(mg_context* c, const Level& L, int mode, bool dot, const double* x_rows, const double* f_rows,
                         double* out_rows, double* partials, unsigned* grid_out, double alpha, double beta) {
@@ -877,6 +881,49 @@ int launch_diffusion_rhs(mg_context* c, const Level& L, const double* d_kappa, d
     d.kc0 = 0;
     hipLaunchKernelGGL(gen_diffusion_rhs, grid3(L.g, L.g.nk), dim3(kPlaneBlock), 0, c->stream, d, f_rows, dinv_rows);
     HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// out[cell] = d(a^T A(kappa) b) / d kappa_cell on a whole 3-D grid level (mg_diffusion_adj.hip.h); a, b: lexicographic nodes
+int launch_dkappa(mg_context* c, const Level& L, const double* a, const double* b, double* out, bool gather) {
+    DkMarchArgs m{};
+    DkArgs& d = m.d;
+    d.a = a; d.b = b; d.out = out;
+    d.nx = L.g.nx; d.ny = L.g.ny; d.nz = L.g.nz; d.N = L.N; d.P = L.g.plane;
+    d.scale = (1.0 / (double)L.N) / 6.0;
+    if (gather) {
+        const dim3 grid(blocks_for((int64_t)L.N * L.N, DK_BLOCK), (unsigned)L.N, 1u);
+        hipLaunchKernelGGL(diffusion_dkappa_gather, grid, dim3(DK_BLOCK), 0, c->stream, d);
+    } else {
+        const MfPlan p = mf_plan_dims(c, L.N, L.N, L.N);    // tiles of cells, segments of cell planes
+        m.ntx = p.ntx; m.nty = p.nty; m.nseg = p.nseg; m.seglen = p.seglen; m.nitems = p.nitems; m.ch = p.ch;
+        hipLaunchKernelGGL(diffusion_dkappa_march, dim3(p.grid), dim3(MF_NT), 0, c->stream, m);
+    }
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// mg_diffusion_dkappa and the device-pointer vector calls: whole 3-D grid levels / whole handles, refused by name otherwise
+int need_dkappa_level(mg_context* c, int level, const char* who) {
+    if (!c) return fail("null handle");
+    if (c->dim != 3) return fail(std::string(who) + ": the kappa sensitivity is 3-D only (this handle is 2-D)");
+    if (c->comm.active()) return fail(std::string(who) + " needs a whole (not slab) handle");
+    MG_TRY(check_level(c, level));
+    if (c->L[level].flat) return fail(std::string(who) + ": level " + std::to_string(level) + " is flat (no grid): it has no cells");
+    return 0;
+}
+
+// `p` must be device memory of the handle's device (hipPointerGetAttributes); nothing is launched otherwise
+int need_device_pointer(mg_context* c, const void* p, const char* who, const char* what) {
+    if (!p) return fail(std::string(who) + ": null pointer (" + what + ")");
+    hipPointerAttribute_t at{};
+    const hipError_t e = hipPointerGetAttributes(&at, p);
+    if (e != hipSuccess) (void)hipGetLastError();       // (an unregistered host pointer is an error of the query in some runtimes)
+    if (e != hipSuccess || at.type != hipMemoryTypeDevice)
+        return fail(std::string(who) + ": " + what + " is not device memory (a host pointer?)");
+    if (at.device != c->device)
+        return fail(std::string(who) + ": " + what + " lives on device " + std::to_string(at.device) + ", the handle on device " +
+                    std::to_string(c->device));
     return 0;
 }
 
@@ -3959,6 +4006,8 @@ int mg_set_tuning(mg_handle c, const char* key, int64_t value) {
         c->lattice_march = value != 0;
     } else if (k == "lattice_march_min_rows") {
         c->lattice_march_min_rows = value;
+    } else if (k == "dkappa_gather") {
+        c->dkappa_gather = value != 0;
     } else if (k == "lattice_gs2") {
         c->lattice_gs2 = value != 0;
     } else if (k == "lattice_tile") {
@@ -4799,6 +4848,50 @@ int mg_get_vector(mg_handle c, int level, int which, double* host, int gather) {
     return 0;
 }
 
+int mg_set_vector_device(mg_handle c, int level, int which, const double* dev) {
+    if (!c) return fail("null handle");
+    if (c->comm.active()) return fail("mg_set_vector_device needs a whole (not slab) handle");
+    MG_TRY(check_level(c, level));
+    HIP_TRY(hipSetDevice(c->device));
+    MG_TRY(need_device_pointer(c, dev, "mg_set_vector_device", "the vector"));
+    Level& L = c->L[level];
+    DVector* v = pick(L, which);
+    if (!v) return fail("unknown vector selector");
+    MG_TRY(vec_alloc(c, L, v));
+    const unsigned nb = (unsigned)std::min<int64_t>(4096, (L.n_global + 255) / 256);
+    hipLaunchKernelGGL(scatter_in, dim3(nb), dim3(256), 0, c->stream, dev, L.perm, L.n_global, L.row0, L.g.lead, L.xlen, v->base);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int mg_get_vector_device(mg_handle c, int level, int which, double* dev) {
+    if (!c) return fail("null handle");
+    if (c->comm.active()) return fail("mg_get_vector_device needs a whole (not slab) handle");
+    MG_TRY(check_level(c, level));
+    HIP_TRY(hipSetDevice(c->device));
+    MG_TRY(need_device_pointer(c, dev, "mg_get_vector_device", "the vector"));
+    Level& L = c->L[level];
+    DVector* v = pick(L, which);
+    if (!v || !v->raw) return fail("vector is not available on this level");
+    const unsigned nb = (unsigned)std::min<int64_t>(4096, (L.n_global + 255) / 256);
+    hipLaunchKernelGGL(gather_out, dim3(nb), dim3(256), 0, c->stream, v->base, L.perm, L.n_global, L.row0, L.nloc, L.g.lead, dev);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int mg_diffusion_dkappa(mg_handle c, int level, const double* a_dev, const double* b_dev, double* out_dev) {
+    MG_TRY(need_dkappa_level(c, level, "mg_diffusion_dkappa"));
+    HIP_TRY(hipSetDevice(c->device));
+    MG_TRY(need_device_pointer(c, a_dev, "mg_diffusion_dkappa", "a"));
+    MG_TRY(need_device_pointer(c, b_dev, "mg_diffusion_dkappa", "b"));
+    MG_TRY(need_device_pointer(c, out_dev, "mg_diffusion_dkappa", "out"));
+    MG_TRY(launch_dkappa(c, c->L[level], a_dev, b_dev, out_dev, c->dkappa_gather != 0));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
 int mg_zero_vector(mg_handle c, int level, int which) {
     MG_TRY(check_level(c, level));
     Level& L = c->L[level];
@@ -5228,6 +5321,11 @@ int mg_time_kernel(mg_handle c, const char* kernel, int level, int reps, double*
                                   al[1], be[1]);
             }
             return fail("unknown mode of diffusion_mf: " + m);
+        }
+        if (k == "dkappa" || k == "dkappa_gather") {    // d(v^T A f) / d kappa: the plane march / one thread per cell, into MG_VEC_R
+            MG_TRY(need_dkappa_level(c, level, "mg_time_kernel"));
+            MG_TRY(vec_alloc(c, L, &L.v)); MG_TRY(vec_alloc(c, L, &L.f)); MG_TRY(vec_alloc(c, L, &L.v2));
+            return launch_dkappa(c, L, L.v.rows, L.f.rows, L.v2.rows, k == "dkappa_gather");
         }
         if (k == "residual") return residual(c, level);
         if (k == "restrict") return level > 0 ? restrict_to(c, level, c->restriction) : fail("level 0");

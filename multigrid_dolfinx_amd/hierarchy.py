@@ -76,6 +76,37 @@ def jacobi_split(A, device=0):
     return R, sp.diags(dinv, 0)
 
 
+class _DeviceArray:
+    """A device buffer of float64 for `diffusion_dkappa` fed NumPy arrays (tests): the HIP runtime is reached through
+    libmg_hip.so, which links it, so nothing else has to be found or imported."""
+
+    def __init__(self, lib, device: int, n: int, host: Optional[np.ndarray] = None):
+        self._lib, self.n, self.ptr = lib, int(n), C.c_void_p()
+        for name, args in (("hipSetDevice", [C.c_int]), ("hipMalloc", [C.POINTER(C.c_void_p), C.c_size_t]), ("hipFree", [C.c_void_p]),
+                           ("hipMemcpy", [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int])):
+            fn = getattr(lib, name)
+            fn.argtypes, fn.restype = args, C.c_int
+        self._hip(lib.hipSetDevice(int(device)), "hipSetDevice")
+        self._hip(lib.hipMalloc(C.byref(self.ptr), max(8, 8 * self.n)), "hipMalloc")
+        if host is not None:
+            self._hip(lib.hipMemcpy(self.ptr, ptr(host), 8 * self.n, 1), "hipMemcpy")     # hipMemcpyHostToDevice
+
+    @staticmethod
+    def _hip(status, what):
+        if status != 0:
+            raise _capi.MgError(f"{what} failed with HIP error {status}")
+
+    def download(self) -> np.ndarray:
+        out = np.empty(self.n)
+        self._hip(self._lib.hipMemcpy(ptr(out), self.ptr, 8 * self.n, 2), "hipMemcpy")    # hipMemcpyDeviceToHost
+        return out
+
+    def free(self):
+        if self.ptr:
+            self._lib.hipFree(self.ptr)
+            self.ptr = C.c_void_p()
+
+
 class DeviceHierarchy:
     """One multigrid hierarchy resident on one MI355X (or one slab of it per rank)."""
 
@@ -525,6 +556,49 @@ class DeviceHierarchy:
         out = np.zeros(self.n_dofs(level))
         check(self._lib.mg_get_vector(self._h, self._idx(level), _VEC[which], ptr(out), 1 if gather else 0))
         return out.reshape(-1, 1)
+
+    def set_vector_device(self, level: int, which: str, dev_ptr: int):
+        """`set_vector` from device memory (`mg_set_vector_device`): `dev_ptr` is the integer address of `n_dofs(level)`
+        float64 on this handle's device, in the caller's DoF numbering, and must be complete before the call (synchronise the
+        stream that produced it).  Nothing crosses to the host."""
+        check(self._lib.mg_set_vector_device(self._h, self._idx(level), _VEC[which], C.c_void_p(int(dev_ptr))))
+
+    def get_vector_device(self, level: int, which: str, dev_ptr: int):
+        """`get_vector` into device memory (`mg_get_vector_device`): writes `n_dofs(level)` float64 at the integer device
+        address `dev_ptr`; the handle's stream has finished when this returns."""
+        check(self._lib.mg_get_vector_device(self._h, self._idx(level), _VEC[which], C.c_void_p(int(dev_ptr))))
+
+    def diffusion_dkappa(self, level: int, a, b, out=None):
+        """d(a^T A(kappa) b) / d kappa for every cell of a 3-D grid level (`mg_diffusion_dkappa`; host restatement:
+        `poisson.diffusion_dkappa`).  `a`, `b` (lexicographic nodal values, boundary entries count as 0) and `out`
+        (`elements(level) ** 3` cells) are integer device addresses -- `out` is then required and nothing is returned --
+        or, for tests, NumPy arrays, which are uploaded, and the result comes back as a NumPy array (into `out` if
+        given).  `a is b` passes the same pointer twice."""
+        cells = self.elements(level) ** 3
+        integers = [isinstance(x, (int, np.integer)) for x in (a, b)]
+        if all(integers):
+            if not isinstance(out, (int, np.integer)):
+                raise TypeError("with device addresses for a and b, out must be a device address too")
+            check(self._lib.mg_diffusion_dkappa(self._h, self._idx(level), C.c_void_p(int(a)), C.c_void_p(int(b)),
+                                                C.c_void_p(int(out))))
+            return None
+        if any(integers) or isinstance(out, (int, np.integer)):
+            raise TypeError("a, b and out must be all device addresses or all NumPy arrays")
+        n = self.n_dofs(level)
+        held = []
+        try:
+            held.append(_DeviceArray(self._lib, self.device, n, _capi.as_f64(a, n)))
+            held.append(held[0] if b is a else _DeviceArray(self._lib, self.device, n, _capi.as_f64(b, n)))
+            held.append(_DeviceArray(self._lib, self.device, cells))
+            check(self._lib.mg_diffusion_dkappa(self._h, self._idx(level), held[0].ptr, held[1].ptr, held[2].ptr))
+            got = held[2].download()
+        finally:
+            for d in held:
+                d.free()
+        if out is None:
+            return got
+        out.reshape(-1)[:] = got
+        return out
 
     def zero_vector(self, level: int, which: str = "v"):
         check(self._lib.mg_zero_vector(self._h, self._idx(level), _VEC[which]))

@@ -675,3 +675,42 @@ def coarsen_kappa(kappa, dim: int, averaging: str = "arithmetic") -> np.ndarray:
     m = float(2 ** dim)
     out = m / s if averaging == "harmonic" else s * (1.0 / m)
     return np.ascontiguousarray(out.reshape(-1))
+
+
+def diffusion_dkappa(N: int, a, b) -> np.ndarray:
+    """d(a^T A(kappa) b) / d kappa_c for the N^3 cells of the 3-D `diffusion_level`, as `mg_diffusion_dkappa` computes it (same
+    bits: explicit adds in the order of `dk_cell`, mg_diffusion_adj.hip.h).  `a`, `b`: nodal values in lexicographic order;
+    their boundary entries count as 0 (boundary rows are identity rows and interior rows have no boundary column: that block
+    does not depend on kappa).  A is linear in kappa, so the result needs no kappa: with A~, B~ the masked values at a cell's
+    corners (dz, dy, dx), an axis edge contributes (A~_upper - A~_lower) * (B~_upper - B~_lower), times 2 where the cell's two
+    other local coordinates at the edge are equal; the x edges at (dz, dy) = (0,0), (0,1), (1,0), (1,1), then the y edges at
+    (dz, dx), then the z edges at (dy, dx) are added one by one and the sum is scaled by (1 / N) / 6.  Flat array in the cell
+    order of `diffusion_level`."""
+    n1 = N + 1
+
+    def corners(x):
+        v = np.array(x, dtype=np.float64).reshape(-1)
+        if v.size != n1 ** 3:
+            raise ValueError(f"vector has {v.size} entries, the level has {n1 ** 3} nodes")
+        v = v.reshape(n1, n1, n1)
+        m = np.zeros_like(v)
+        m[1:-1, 1:-1, 1:-1] = v[1:-1, 1:-1, 1:-1]
+        return [[[m[dz:dz + N, dy:dy + N, dx:dx + N] for dx in (0, 1)] for dy in (0, 1)] for dz in (0, 1)]
+
+    A, B = corners(a), corners(b)
+    edge = lambda hi, lo: (A[hi[0]][hi[1]][hi[2]] - A[lo[0]][lo[1]][lo[2]]) * (B[hi[0]][hi[1]][hi[2]] - B[lo[0]][lo[1]][lo[2]])
+    s = None
+    for axis in (0, 1, 2):                      # x, y, z edges; (p, q): the two other coordinates, slower one first
+        for p in (0, 1):
+            for q in (0, 1):
+                if axis == 0:
+                    hi, lo = (p, q, 1), (p, q, 0)
+                elif axis == 1:
+                    hi, lo = (p, 1, q), (p, 0, q)
+                else:
+                    hi, lo = (1, p, q), (0, p, q)
+                t = edge(hi, lo)
+                if p == q:
+                    t = 2.0 * t
+                s = t if s is None else s + t
+    return np.ascontiguousarray((s * ((1.0 / N) / 6.0)).reshape(-1))
