@@ -107,9 +107,25 @@ int mg_set_comm_callbacks(mg_handle h, int rank, int world, mg_exchange_fn ex, m
 /* ---- hierarchy set-up --------------------------------------------------------------
  * mg_set_level_csr: hand over one level's stiffness matrix exactly as
  * scipy.sparse.csr_matrix((av, aj, ai)) holds it after PETSc getValuesCSR()
- * (Multigrid_prototype.py:95-99): fp64 values, int32 column indices (possibly
- * unsorted, possibly with explicit zeros), row pointers int32 or int64
- * (indptr_is_64).  `grid_index[dof]` is the lexicographic node index
+ * (Multigrid_prototype.py:95-99): fp64 values, int32 column indices, row pointers
+ * int32 or int64 (indptr_is_64).  The contract for the three arrays: columns may
+ * come in any order within a row, explicit zeros (0.0 and -0.0) may be stored
+ * anywhere within reach of the row.  A row's kept entries are stored in ascending
+ * grid column whatever order they came in, so all of these describe the same level,
+ * with the same storage format, row classes and order of summation as the sorted,
+ * zero-free form -- except that under prune_zeros = 0 a stored zero is an entry of
+ * the pattern like any other: a zero on an offset no other row uses is a new
+ * diagonal of the pattern and can change the format the level gets, and a row
+ * with a kept zero is a row of its own in the stencil classes of a level without
+ * symmetric diagonals (more classes, or none past 255).  Duplicate (row, column)
+ * entries are REFUSED, not summed: sum them first (A.sum_duplicates()) -- a1 x + a2 x
+ * and (a1 + a2) x round differently, and the compact formats keep one slot per
+ * diagonal.  Structural errors -- indptr[0] != 0, a decreasing indptr,
+ * indptr[n_rows] != nnz, a column index outside [0, n_rows) -- are refused too.
+ * Both are found by mg_csr_check on the host before anything is freed, allocated,
+ * uploaded or launched: a refused hand-off leaves the level as it was.  The same
+ * holds for mg_set_level_csr_local (columns in [0, n_cols)), mg_set_mass_csr and
+ * flat levels.  `grid_index[dof]` is the lexicographic node index
  * i + (N+1)(j + (N+1)k) of each DoF -- the integer form of the reference's
  * coordinate dictionaries (Multigrid_prototype.py:68-74); NULL means the DoFs are
  * already lexicographic.  The library renumbers once (P A P^T), optionally drops
@@ -121,6 +137,16 @@ int mg_set_comm_callbacks(mg_handle h, int rank, int world, mg_exchange_fn ex, m
 int mg_set_level_csr(mg_handle h, int level, int elements_per_dim, int64_t n_rows, int64_t nnz,
                      const void* indptr, int indptr_is_64, const int32_t* indices,
                      const double* data, const int64_t* grid_index, int prune_zeros);
+/* The structural check every host CSR hand-off starts with; pure host code, usable without a device.  0 if
+ * (indptr, indices) describe an n_rows x n_cols CSR pattern of nnz entries; otherwise 1 and mg_last_error names the cause
+ * and, where there is one, the row and column in the caller's numbering: indptr[0] != 0, indptr[i + 1] < indptr[i],
+ * indptr[n_rows] != nnz, a column index < 0 or >= n_cols and, unless allow_duplicates, a (row, column) pair stored twice
+ * ("row r holds column c twice; sum duplicates before the hand-off (A.sum_duplicates())").  Two linear passes, no sorting:
+ * the row pointers first, then the entries against an n_cols array of "last row that touched this column".
+ * mg_jacobi_split calls it with allow_duplicates = 1 (duplicates sum there, as in SciPy), the level and mass hand-offs
+ * with 0.  Device-built matrices (mg_galerkin_level) do not pass through it. */
+int mg_csr_check(int64_t n_rows, int64_t n_cols, int64_t nnz, const void* indptr, int indptr_is_64,
+                 const int32_t* indices, int allow_duplicates);
 /* Per-rank hand-off for slabs: the rank passes ONLY the rows it owns (mg_level_slab says which: the lexicographic
  * nodes [row0, row0 + n_local) of the level, plus how many halo nodes it may couple to on either side), in a local
  * numbering like a distributed assembly has it (PETSc's owned + ghost layout behind getValuesCSR(),

@@ -45,6 +45,7 @@ SIGNATURES = {
     "mg_set_comm_callbacks": [_H, C.c_int, C.c_int, EXCHANGE_FN, ALLREDUCE_FN, ALLGATHERV_FN, C.c_void_p, C.c_int64],
     "mg_set_level_csr": [_H, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                          C.c_void_p, C.c_int],
+    "mg_csr_check": [C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_int],
     "mg_set_level_grid": [_H, C.c_int, C.c_int, C.c_int64, C.c_void_p],
     "mg_level_slab": [_H, C.c_int, C.c_int, _i64p, _i64p, _i64p, _i64p],
     "mg_set_level_csr_local": [_H, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int, C.c_void_p,

@@ -2,6 +2,7 @@
 // kept on the device, RCCL slab exchange.  Host code only orchestrates launches on the
 // handle's stream; all arithmetic of the path runs in the kernels of mg_kernels.hip.h.
 #include "../../include/mg_hip.h"
+#include "mg_csr_check.h"
 #include "mg_kernels.hip.h"
 #include "mg_direct.hip.h"
 #include "mg_jacobi2.hip.h"
@@ -51,6 +52,13 @@ int fail(const std::string& msg) {
         int r_ = (expr);        \
         if (r_ != 0) return r_; \
     } while (0)
+
+// Every host CSR hand-off starts here, before anything is freed, allocated, uploaded or launched (mg_csr_check.h).
+int check_csr(int64_t n_rows, int64_t n_cols, int64_t nnz, const void* indptr, int indptr_is_64, const int32_t* indices,
+              bool allow_duplicates) {
+    const std::string why = csr_check(n_rows, n_cols, nnz, indptr, indptr_is_64, indices, allow_duplicates);
+    return why.empty() ? 0 : fail(why);
+}
 
 // A device vector in local lexicographic storage: [pad | lower halo | owned rows | upper halo],
 // padded so that the first owned row is 32-byte aligned (the tile kernels load R rows per lane).
@@ -4156,6 +4164,7 @@ int build_level_from_csr(mg_context* c, int level, Level& L, int64_t n_rows, int
     a.perm = local_cols ? static_cast<const int*>(d_map.p) : L.perm;
     a.n = n_rows; a.row0 = L.row0; a.nloc = L.nloc; a.lead = L.g.lead; a.xlen = L.xlen;
     a.prune = prune_zeros;
+    a.sort = device_csr ? 0 : 1;
     // pass 1: widest kept row, kept entries, sanity flags
     unsigned long long* d_stats = reinterpret_cast<unsigned long long*>(c->partials);
     HIP_TRY(hipMemsetAsync(d_stats, 0, 4 * sizeof(unsigned long long), c->stream));
@@ -4286,6 +4295,7 @@ int mg_set_level_csr(mg_handle c, int level, int N, int64_t n_rows, int64_t nnz,
     MG_TRY(check_level(c, level, false));
     if (!indptr || !indices || !data) return fail("null CSR arrays");
     if (n_rows <= 0 || nnz < 0) return fail("bad matrix dimensions");
+    MG_TRY(check_csr(n_rows, n_rows, nnz, indptr, indptr_is_64, indices, false));      // (grid and flat levels alike)
     HIP_TRY(hipSetDevice(c->device));
     Level& L = c->L[level];
     free_level(c, L);
@@ -4300,6 +4310,11 @@ int mg_set_level_csr(mg_handle c, int level, int N, int64_t n_rows, int64_t nnz,
         g_err = why;
     }
     return rc;
+}
+
+int mg_csr_check(int64_t n_rows, int64_t n_cols, int64_t nnz, const void* indptr, int indptr_is_64, const int32_t* indices,
+                 int allow_duplicates) {
+    return check_csr(n_rows, n_cols, nnz, indptr, indptr_is_64, indices, allow_duplicates != 0);
 }
 
 int mg_level_slab(mg_handle c, int level, int N, int64_t* row0, int64_t* n_local, int64_t* halo_lo, int64_t* halo_hi) {
@@ -4321,6 +4336,7 @@ int mg_set_level_csr_local(mg_handle c, int level, int N, int64_t n_rows, int64_
     MG_TRY(check_level(c, level, false));
     if (!indptr || !indices || !data || !col_nodes) return fail("null CSR arrays");
     if (N <= 0 || n_rows <= 0 || n_cols < n_rows || nnz < 0) return fail("bad matrix dimensions");
+    MG_TRY(check_csr(n_rows, n_cols, nnz, indptr, indptr_is_64, indices, false));
     HIP_TRY(hipSetDevice(c->device));
     Level& L = c->L[level];
     free_level(c, L);
@@ -4717,6 +4733,8 @@ int mg_level_matrix_free(mg_handle c, int level, int* on, int64_t* kappa_bytes) 
 int mg_jacobi_split(int device, int64_t n_rows, int64_t nnz, const void* indptr, int indptr_is_64,
                     const int32_t* indices, const double* data, double* dinv, double* scaled, unsigned char* keep) {
     if (!indptr || !indices || !data || !dinv || !scaled || !keep) return fail("null argument");
+    // duplicates allowed: they sum, as in SciPy's A.diagonal() and A - D (the reference's getJacobiMatrices)
+    MG_TRY(check_csr(n_rows, n_rows, nnz, indptr, indptr_is_64, indices, true));
     int ndev = 0;
     HIP_TRY(hipGetDeviceCount(&ndev));
     if (ndev <= 0) return fail("no HIP device visible: this library has no CPU path");
@@ -5080,6 +5098,8 @@ int mg_set_mass_csr(mg_handle c, int level, int64_t n_rows, int64_t nnz, const v
     MG_TRY(check_level(c, level));
     MG_TRY(need_grid(c, level));
     if (!indptr || !indices || !data) return fail("null CSR arrays");
+    if (n_rows <= 0 || nnz < 0) return fail("bad matrix dimensions");
+    MG_TRY(check_csr(n_rows, n_rows, nnz, indptr, indptr_is_64, indices, false));
     HIP_TRY(hipSetDevice(c->device));
     Level& L = c->L[level];
     if (n_rows != L.n_global) return fail("mass matrix has " + std::to_string(n_rows) + " rows, level has " + std::to_string(L.n_global));

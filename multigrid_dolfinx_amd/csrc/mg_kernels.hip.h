@@ -776,6 +776,8 @@ __global__ void sdia_fill(SdiaArgs a) {
         const int off = a.offsets[(int)((w >> (8 * (k % 8))) & 0xffull)];
         if (off >= 0) {
             const int c = sdia_slot(a, off);
+            // (one slot per diagonal, the last entry wins: a host hand-off cannot hold two, mg_csr_check refuses
+            //  duplicates; the device-built matrices of mg_galerkin_level hold one per diagonal by construction)
             a.dvals[((size_t)(m / S) * a.WU + c) * S + (size_t)(m % S)] = v;
         } else if (row + off < 0) {
             const int c = sdia_slot(a, -off);
@@ -1039,6 +1041,7 @@ struct CsrArgs {
     int64_t row0, nloc;      // owned global rows [row0, row0+nloc)
     int64_t lead, xlen;      // local vector = [lead | nloc | upper halo], xlen total
     int prune;
+    int sort;                // host hand-offs: a row's kept entries are stored in ascending grid column, whatever order they came in
 };
 
 __device__ __forceinline__ int64_t csr_ptr(const CsrArgs& a, int64_t i) {
@@ -1089,7 +1092,10 @@ __global__ void ell_fill_padding(double* vals, int* cols, int64_t nslices, int W
     cols[t] = (int)(lead + row);
 }
 
-// Pass 2: scatter kept entries in stored order; D^-1.
+// Pass 2: scatter kept entries; D^-1.  With a.sort (host hand-offs) a row's kept entries are inserted in ascending grid
+// column, so that every order a caller may store a row in gives the same tiles -- the same order of summation, and the same
+// stencil classes, which are a dictionary of rows in stored order; a sorted lexicographic hand-off moves nothing.  Without
+// (matrices built on the device, mg_galerkin_level) they keep the order they were built in.
 template <int R>
 __global__ void csr_to_ell(CsrArgs a, double* vals, int* cols, double* dinv, int W) {
     const int64_t d = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1106,11 +1112,20 @@ __global__ void csr_to_ell(CsrArgs a, double* vals, int* cols, double* dinv, int
     for (int64_t q = b; q < e; ++q) {
         const double v = a.data[q];
         const int64_t cp = a.perm ? a.perm[a.indices[q]] : a.indices[q];
+        // (the last diagonal entry wins: a host hand-off cannot hold two, mg_csr_check refuses duplicates, and the
+        //  device-built matrices hold one per row by construction)
         if (cp == p && v != 0.0) diag = v;
         if (a.prune && v == 0.0) continue;
         if (k < W) {
-            vals[base + (size_t)k * (WAVE * R)] = v;
-            cols[base + (size_t)k * (WAVE * R)] = (int)(cp - a.row0 + a.lead);
+            const int lc = (int)(cp - a.row0 + a.lead);
+            int j = k;
+            if (a.sort)
+                for (; j > 0 && cols[base + (size_t)(j - 1) * (WAVE * R)] > lc; --j) {
+                    vals[base + (size_t)j * (WAVE * R)] = vals[base + (size_t)(j - 1) * (WAVE * R)];
+                    cols[base + (size_t)j * (WAVE * R)] = cols[base + (size_t)(j - 1) * (WAVE * R)];
+                }
+            vals[base + (size_t)j * (WAVE * R)] = v;
+            cols[base + (size_t)j * (WAVE * R)] = lc;
         }
         ++k;
     }

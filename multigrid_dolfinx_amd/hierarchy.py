@@ -19,7 +19,7 @@ from ._capi import (MG_RESTRICT_FULL_WEIGHTING, MG_RESTRICT_INJECTION, MG_VEC_ER
                     MG_VEC_V, check, load, ptr)
 from .poisson import grid_index_from_coords
 
-__all__ = ["DeviceHierarchy", "jacobi_split"]
+__all__ = ["DeviceHierarchy", "jacobi_split", "csr_check"]
 
 # lower_ratio of the Chebyshev interval by default (include/mg_hip.h, mg_set_chebyshev)
 CHEB_LOWER_RATIO = 6.0
@@ -36,12 +36,27 @@ def _csr_arrays(A):
     if np.iscomplexobj(A.data):
         raise TypeError("complex scalars are not supported (real fp64 only)")
     data = np.ascontiguousarray(A.data, dtype=np.float64)
-    indices = np.ascontiguousarray(A.indices, dtype=np.int32)
+    indices = np.asarray(A.indices)
+    if indices.dtype != np.int32 and indices.size:
+        # (a 64-bit-index PETSc build delivers int64: narrowing must not wrap)
+        lo, hi = int(indices.min()), int(indices.max())
+        if lo < np.iinfo(np.int32).min or hi > np.iinfo(np.int32).max:
+            raise ValueError(f"column indices {lo}..{hi} do not fit the library's int32 column indices")
+    indices = np.ascontiguousarray(indices, dtype=np.int32)
     if A.indptr.dtype == np.int64:
         indptr, is64 = np.ascontiguousarray(A.indptr), 1
     else:
         indptr, is64 = np.ascontiguousarray(A.indptr, dtype=np.int32), 0
     return indptr, is64, indices, data
+
+
+def csr_check(A, allow_duplicates=False):
+    """The structural check every CSR hand-off starts with (`mg_csr_check`; host only, no device needed): raises
+    `MgError` naming the cause -- row pointers that do not start at 0, decrease or do not end at nnz, a column index
+    outside the matrix and, unless `allow_duplicates`, a (row, column) pair stored twice."""
+    indptr, is64, indices, data = _csr_arrays(A)
+    check(load().mg_csr_check(A.shape[0], A.shape[1], data.size, ptr(indptr), is64, ptr(indices),
+                              1 if allow_duplicates else 0))
 
 
 def jacobi_split(A, device=0):
