@@ -222,6 +222,40 @@ int mg_gen_diffusion_level_mf(mg_handle h, int level, int elements_per_dim, cons
  * and no matrix; smaller levels and always level 0 (which the direct solve factorises) are stored as today. */
 int mg_gen_diffusion_hierarchy_mf(mg_handle h, int top_level, int elements_per_dim, const double* kappa_top, int averaging,
                                   int64_t min_rows);
+/* The same hierarchy from a kappa that is on the device already (opt-in): mg_gen_diffusion_hierarchy (mf_min_rows < 0) or
+ * mg_gen_diffusion_hierarchy_mf (mf_min_rows >= 0, its min_rows), every result bit for bit the same.  kappa_dev: the
+ * elements_per_dim^dim doubles of the top level in device memory of the handle's device, cell order as in
+ * mg_gen_diffusion_level.  The caller's buffer is only read, never written and never taken over: a matrix-free top level
+ * keeps its own copy, written by the pass that coarsens it (kappa_ingest, mg_diffusion_kappa.hip.h: the fine field read
+ * once, the copy and the coarse field written, 17 B per fine cell in 3-D against 8 + 8 for a copy and 8 + 1 for
+ * kappa_coarsen); the levels below take over the coarsened fields as in the host call.  Nothing of kappa crosses to the
+ * host but the flag of the check and, in a refusal, the one bad value.  Runs on the handle's stream, which is synchronised
+ * before return; the caller must have finished producing kappa (the contract of mg_set_vector_device).  Refused with an
+ * error before any level is touched: a null pointer, a pointer that is not device memory of the handle's device, slab
+ * handles, 2-D handles with mf_min_rows >= 0, an elements_per_dim that is not N0 * 2^top_level, an unknown averaging, and
+ * a kappa that is not positive and finite, named by its first bad cell as mg_gen_diffusion_level names it.  As in the host
+ * call only the top level's kappa is checked: the coarsened fields are not (averages of positive finite values can still
+ * overflow). */
+int mg_gen_diffusion_hierarchy_device(mg_handle h, int top_level, int elements_per_dim, const double* kappa_dev, int averaging,
+                                      int64_t mf_min_rows);
+/* Another kappa for levels top_level .. 0 of a hierarchy that one of the three diffusion hierarchy calls generated (the
+ * handle remembers that per level, with the level's size; setting a level in any other way forgets it), without tearing it
+ * down: afterwards the handle is in the state mg_gen_diffusion_hierarchy_device with this kappa and the same split into
+ * stored and matrix-free levels leaves -- right-hand sides, MG_VEC_V and MG_VEC_R zeroed, every result of every later call
+ * and mg_memory_bytes bit for bit.  Matrix-free levels keep their kappa buffer, their vectors and their mg_pcg work
+ * vectors: nothing is freed or allocated for them, kappa is overwritten in place (the top level's by kappa_ingest, from the
+ * caller's buffer; a matrix-free level below is the coarse field the pass above wrote) and MG_VEC_F and the true right-hand
+ * side are recomputed.  Stored levels -- with min_rows set, the small ones -- are rebuilt from the device kappa by the
+ * pipeline of mg_gen_diffusion_level.  What the old matrices fed does not survive: level 0's direct factorisation, every
+ * captured V-cycle, and the Chebyshev estimate of every level (matrix-free ones included); all are rebuilt at next use, so
+ * mg_memory_bytes is lower by the factorisation until then.  Intervals set by mg_set_chebyshev_bounds stay, as they do
+ * across a generation.  kappa_dev, averaging, stream and synchronisation as in mg_gen_diffusion_hierarchy_device.
+ * Refused by name, the handle left as it was (the old hierarchy stays fully usable): slab handles, a null pointer or one
+ * that is not device memory of the handle's device, an unknown averaging, a level in top_level .. 0 that is not set or was
+ * set from CSR, by mg_gen_poisson_level, by mg_galerkin_level or generated singly, and a kappa that is not positive and
+ * finite -- found by a read-only pass over the caller's buffer before anything is written.  The coarsened fields are not
+ * validated, as in the hierarchy calls. */
+int mg_refresh_diffusion_hierarchy(mg_handle h, int top_level, const double* kappa_dev, int averaging);
 /* *on = 1 if the level is matrix-free, *kappa_bytes = the device bytes of its kappa (0 otherwise) */
 int mg_level_matrix_free(mg_handle h, int level, int* on, int64_t* kappa_bytes);
 /* Sensitivity of the diffusion operator to kappa (no reference counterpart): out_dev[c] = d(a^T A(kappa) b) / d kappa_c for the
@@ -626,7 +660,10 @@ int mg_reset_smoother_launches(mg_handle h);
  * "gs" = one full Gauss-Seidel sweep, all colours, with the configured Gauss-Seidel smoother;
  * "spmv" = one SpMV without the dot product, with the level's one-step kernel; "diffusion_mf", "diffusion_mf:jacobi",
  * ":residual", ":spmv", ":chebyshev" = the matrix-free diffusion march in that mode, an error on stored levels;
- * "dkappa" / "dkappa_gather" = mg_diffusion_dkappa of (MG_VEC_V, MG_VEC_F) into MG_VEC_R as the plane march / one thread per cell).
+ * "dkappa" / "dkappa_gather" = mg_diffusion_dkappa of (MG_VEC_V, MG_VEC_F) into MG_VEC_R as the plane march / one thread per cell;
+ * "kappa_ingest" = one launch of the fused copy and coarsening of mg_gen_diffusion_hierarchy_device on a matrix-free level, from a
+ * scratch copy of its kappa back into the level's own (the same bytes: the level is unchanged) and into a scratch coarse field,
+ * arithmetic averaging; an error on stored levels).
  * Used by bench.py for the roofline figure; its launches leave mg_smoother_launches as they were.  mg_sync waits for
  * the handle's stream. */
 int mg_time_kernel(mg_handle h, const char* kernel, int level, int reps, double* avg_ms);

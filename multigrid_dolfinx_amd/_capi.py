@@ -56,6 +56,8 @@ SIGNATURES = {
     "mg_gen_diffusion_hierarchy": [_H, C.c_int, C.c_int, C.c_void_p, C.c_int],
     "mg_gen_diffusion_level_mf": [_H, C.c_int, C.c_int, C.c_void_p],
     "mg_gen_diffusion_hierarchy_mf": [_H, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int64],
+    "mg_gen_diffusion_hierarchy_device": [_H, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int64],
+    "mg_refresh_diffusion_hierarchy": [_H, C.c_int, C.c_void_p, C.c_int],
     "mg_level_matrix_free": [_H, C.c_int, _ip, _i64p],
     "mg_jacobi_split": [C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                         C.c_void_p, C.c_void_p],

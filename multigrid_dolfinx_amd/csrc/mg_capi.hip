@@ -11,6 +11,7 @@
 #include "mg_lattice.hip.h"
 #include "mg_diffusion_mf.hip.h"
 #include "mg_diffusion_adj.hip.h"
+#include "mg_diffusion_kappa.hip.h"
 
 #include <dlfcn.h>
 #include <rccl/rccl.h>
@@ -193,6 +194,7 @@ struct Level {
     bool mf = false;
     double* kappa = nullptr;
     int64_t kappa_n = 0;
+    bool diffusion_hierarchy = false;       // generated by one of the diffusion hierarchy entries: mg_refresh_diffusion_hierarchy may renew it
     DVector v, v2, f, err, ftrue;
     DVector sw;                             // once-relaxed boundary planes of a slab (paired sweeps, world > 1)
     DVector fcg_x, fcg_p, fcg_q, fcg_b;     // mg_pcg on this level: iterate, direction, A p, the saved right-hand side
@@ -602,6 +604,7 @@ void free_level(mg_context* c, Level& L) {
     dev_free(c, L.kappa, (size_t)L.kappa_n);
     L.kappa_n = 0;
     L.mf = false;
+    L.diffusion_hierarchy = false;
     dev_free(c, L.perm, (size_t)L.n_global);
     vec_free(c, L, &L.v);
     vec_free(c, L, &L.v2);
@@ -4705,6 +4708,7 @@ int gen_diffusion_hierarchy(mg_context* c, const std::string& who, int top_level
         else HIP_TRY(hipFree(fine.p));
         fine.p = coarse.p;
         coarse.p = nullptr;
+        c->L[l].diffusion_hierarchy = true;
     }
     return 0;
 }
@@ -4720,6 +4724,138 @@ int mg_gen_diffusion_hierarchy_mf(mg_handle c, int top_level, int N, const doubl
     MG_TRY(check_level(c, top_level, false));
     MG_TRY(mf_refusals(c, "mg_gen_diffusion_hierarchy_mf"));
     return gen_diffusion_hierarchy(c, "mg_gen_diffusion_hierarchy_mf", top_level, N, kappa_top, averaging, min_rows);
+}
+
+namespace {
+
+// one pass over a level's device kappa (mg_diffusion_kappa.hip.h): the level's own copy (fine_out, may be null) and the
+// kappa of the Nc^dim cells of the level below
+int launch_kappa_ingest(mg_context* c, const double* fine, double* fine_out, double* coarse, int Nc, int averaging) {
+    const int64_t nc = cell_plane(c, Nc) * Nc;
+    const unsigned nb = (unsigned)std::max<int64_t>(1, std::min<int64_t>(2048, (nc + KI_BLOCK - 1) / KI_BLOCK));
+    const int vec = ((reinterpret_cast<uintptr_t>(fine) | reinterpret_cast<uintptr_t>(fine_out)) & 15) == 0 ? 1 : 0;
+    const int harmonic = averaging == MG_KAPPA_HARMONIC ? 1 : 0;
+    if (c->dim == 3)
+        hipLaunchKernelGGL(kappa_ingest<3>, dim3(nb), dim3(KI_BLOCK), 0, c->stream, fine, fine_out, coarse, Nc, harmonic, vec);
+    else
+        hipLaunchKernelGGL(kappa_ingest<2>, dim3(nb), dim3(KI_BLOCK), 0, c->stream, fine, fine_out, coarse, Nc, harmonic, vec);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// gen_diffusion_hierarchy from a kappa that is on the device already: the caller's buffer is only read; a matrix-free
+// top level gets its own copy from the pass that coarsens it, the levels below take over the coarsened fields as there
+int gen_diffusion_hierarchy_device(mg_context* c, int top_level, int N, const double* kappa_dev, int averaging, int64_t min_rows) {
+    int64_t n = cell_plane(c, N) * N;
+    MG_TRY(check_kappa(c, kappa_dev, n, 0, N));
+    const double* src = kappa_dev;
+    DevTemp held;                               // src where it is ours: the coarsened field of the level above
+    for (int l = top_level, Nl = N; l >= 0; --l, Nl /= 2) {
+        n = cell_plane(c, Nl) * Nl;
+        const int64_t rows = c->dim == 3 ? ((int64_t)Nl + 1) * (Nl + 1) * (Nl + 1) : ((int64_t)Nl + 1) * (Nl + 1);
+        const bool mf = l > 0 && rows >= min_rows;
+        if (!mf) MG_TRY(gen_diffusion_level(c, l, Nl, src, 0, 1));
+        DevTemp own, coarse;
+        if (mf && !held.p) MG_TRY(own.alloc((size_t)n * 8));       // (matrix-free levels are above level 0: the pass below copies)
+        if (l > 0) {
+            const int Nc = Nl / 2;
+            MG_TRY(coarse.alloc((size_t)(cell_plane(c, Nc) * Nc) * 8));
+            MG_TRY(launch_kappa_ingest(c, src, static_cast<double*>(own.p), static_cast<double*>(coarse.p), Nc, averaging));
+            HIP_TRY(hipStreamSynchronize(c->stream));
+        }
+        if (mf) {
+            DevTemp& mine = own.p ? own : held;
+            MG_TRY(gen_diffusion_level_mf(c, l, Nl, static_cast<double*>(mine.p), n));
+            mine.p = nullptr;                   // the level owns it now
+        }
+        if (held.p) { HIP_TRY(hipFree(held.p)); held.p = nullptr; }
+        held.p = coarse.p;
+        coarse.p = nullptr;
+        src = static_cast<const double*>(held.p);
+        c->L[l].diffusion_hierarchy = true;
+    }
+    return 0;
+}
+
+}  // namespace
+
+int mg_gen_diffusion_hierarchy_device(mg_handle c, int top_level, int N, const double* kappa_dev, int averaging,
+                                      int64_t mf_min_rows) {
+    const std::string who = "mg_gen_diffusion_hierarchy_device";
+    MG_TRY(check_level(c, top_level, false));
+    HIP_TRY(hipSetDevice(c->device));
+    MG_TRY(need_device_pointer(c, kappa_dev, who.c_str(), "kappa"));
+    if (c->comm.active())
+        return fail(who + " needs a whole (not slab) handle: on slabs, call mg_gen_diffusion_level per level");
+    if (mf_min_rows >= 0) MG_TRY(mf_refusals(c, who.c_str()));
+    if (N <= 0) return fail("elements_per_dim must be positive");
+    if (N % (1 << top_level))
+        return fail(who + " needs an even elements_per_dim on every level above level 0 (" + std::to_string(N) +
+                    " is not N0 * 2^" + std::to_string(top_level) + ")");
+    if (averaging != MG_KAPPA_ARITHMETIC && averaging != MG_KAPPA_HARMONIC) return fail("unknown kappa averaging");
+    Level geo;
+    MG_TRY(setup_geometry(c, geo, top_level, N));
+    return gen_diffusion_hierarchy_device(c, top_level, N, kappa_dev, averaging, mf_min_rows >= 0 ? mf_min_rows : INT64_MAX);
+}
+
+int mg_refresh_diffusion_hierarchy(mg_handle c, int top_level, const double* kappa_dev, int averaging) {
+    const std::string who = "mg_refresh_diffusion_hierarchy";
+    MG_TRY(check_level(c, top_level, false));
+    HIP_TRY(hipSetDevice(c->device));
+    if (c->comm.active()) return fail(who + " needs a whole (not slab) handle");
+    MG_TRY(need_device_pointer(c, kappa_dev, who.c_str(), "kappa"));
+    if (averaging != MG_KAPPA_ARITHMETIC && averaging != MG_KAPPA_HARMONIC) return fail("unknown kappa averaging");
+    for (int l = top_level; l >= 0; --l) {
+        const Level& L = c->L[l];
+        if (!L.set || !L.diffusion_hierarchy)
+            return fail(who + ": level " + std::to_string(l) + (L.set ? " was not generated by a diffusion hierarchy call (levels set "
+                        "from CSR, by mg_gen_poisson_level, by mg_galerkin_level or generated one by one cannot be refreshed)"
+                        : " has not been set") + ": generate the hierarchy with mg_gen_diffusion_hierarchy[_mf | _device] first");
+        if (l < top_level && 2 * L.N != c->L[l + 1].N)
+            return fail(who + ": levels " + std::to_string(l + 1) + " and " + std::to_string(l) + " come from hierarchies of different "
+                        "sizes (" + std::to_string(c->L[l + 1].N) + " and " + std::to_string(L.N) + " cells per dimension)");
+        if (L.mf && L.kappa_n != cell_plane(c, L.N) * L.N) return fail(who + ": level " + std::to_string(l) + " keeps a kappa of another size");
+    }
+    const int N = c->L[top_level].N;
+    MG_TRY(check_kappa(c, kappa_dev, cell_plane(c, N) * N, 0, N));      // read-only: a refusal leaves the old hierarchy usable
+    // whatever the old matrices fed goes: captured cycles, level 0's factorisation, every level's Chebyshev estimate
+    ++c->epoch;
+    drop_graphs(c);
+    free_direct(c);
+    for (int l = top_level; l >= 0; --l) { c->L[l].cheb_est_ok = false; c->L[l].cheb_lmax_est = 0.0; }
+    const double* src = kappa_dev;
+    DevTemp held;                               // src where it is a temporary: the coarsened field above a stored level
+    for (int l = top_level, Nl = N; l >= 0; --l, Nl /= 2) {
+        Level& L = c->L[l];
+        const bool mf = L.mf;
+        if (!mf) {                              // stored: the level is rebuilt by the pipeline that made it
+            MG_TRY(gen_diffusion_level(c, l, Nl, src, 0, 1));
+            L.diffusion_hierarchy = true;
+        }
+        DevTemp coarse;
+        double* coarse_p = nullptr;
+        if (l > 0) {                            // straight into the kappa of a matrix-free level below, else into a temporary
+            const int Nc = Nl / 2;
+            if (c->L[l - 1].mf) coarse_p = c->L[l - 1].kappa;
+            else {
+                MG_TRY(coarse.alloc((size_t)(cell_plane(c, Nc) * Nc) * 8));
+                coarse_p = static_cast<double*>(coarse.p);
+            }
+            MG_TRY(launch_kappa_ingest(c, src, mf && src != L.kappa ? L.kappa : nullptr, coarse_p, Nc, averaging));
+        }
+        if (mf) {                               // kappa overwritten in place; the vectors are those of a fresh level
+            MG_TRY(launch_diffusion_rhs(c, L, L.kappa, L.f.rows, nullptr));
+            if (L.ftrue.raw) HIP_TRY(hipMemcpyAsync(L.ftrue.base, L.f.base, (size_t)L.xlen * 8, hipMemcpyDeviceToDevice, c->stream));
+            HIP_TRY(hipMemsetAsync(L.v.raw, 0, (size_t)vec_total(L) * sizeof(double), c->stream));
+            HIP_TRY(hipMemsetAsync(L.v2.raw, 0, (size_t)vec_total(L) * sizeof(double), c->stream));
+        }
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        if (held.p) { HIP_TRY(hipFree(held.p)); held.p = nullptr; }
+        held.p = coarse.p;
+        coarse.p = nullptr;
+        src = coarse_p;
+    }
+    return 0;
 }
 
 int mg_level_matrix_free(mg_handle c, int level, int* on, int64_t* kappa_bytes) {
@@ -5276,6 +5412,7 @@ int mg_time_kernel(mg_handle c, const char* kernel, int level, int reps, double*
     HIP_TRY(hipEventCreate(&ev.e0));
     HIP_TRY(hipEventCreate(&ev.e1));
     const hipEvent_t e0 = ev.e0, e1 = ev.e1;
+    DevTemp ki_src, ki_coarse;      // "kappa_ingest": a copy of the level's kappa to read, a coarse field to write
     auto once = [&]() -> int {
         if (k == "jacobi") return launch_ell(c, L, MODE_JACOBI, false, L.v.base, L.f.rows, L.v2.rows, nullptr, nullptr);
         if (k == "chebyshev") {     // one step with x_{k-1} (the scalars of step 1 of a degree-2 polynomial on the level's interval)
@@ -5346,6 +5483,16 @@ int mg_time_kernel(mg_handle c, const char* kernel, int level, int reps, double*
             MG_TRY(need_dkappa_level(c, level, "mg_time_kernel"));
             MG_TRY(vec_alloc(c, L, &L.v)); MG_TRY(vec_alloc(c, L, &L.f)); MG_TRY(vec_alloc(c, L, &L.v2));
             return launch_dkappa(c, L, L.v.rows, L.f.rows, L.v2.rows, k == "dkappa_gather");
+        }
+        if (k == "kappa_ingest") {  // the copy and the coarsening in one pass, from a scratch copy of kappa back into the level's own
+            if (!L.mf) return fail("level is not a matrix-free diffusion level");
+            if (!ki_src.p) {
+                MG_TRY(ki_src.alloc((size_t)L.kappa_n * 8));
+                MG_TRY(ki_coarse.alloc((size_t)(L.kappa_n / 8) * 8));
+                HIP_TRY(hipMemcpyAsync(ki_src.p, L.kappa, (size_t)L.kappa_n * 8, hipMemcpyDeviceToDevice, c->stream));
+            }
+            return launch_kappa_ingest(c, static_cast<const double*>(ki_src.p), L.kappa, static_cast<double*>(ki_coarse.p), L.N / 2,
+                                       MG_KAPPA_ARITHMETIC);
         }
         if (k == "residual") return residual(c, level);
         if (k == "restrict") return level > 0 ? restrict_to(c, level, c->restriction) : fail("level 0");

@@ -92,7 +92,7 @@ def jacobi_split(A, device=0):
 
 
 class _DeviceArray:
-    """A device buffer of float64 for `diffusion_dkappa` fed NumPy arrays (tests): the HIP runtime is reached through
+    """A device buffer of float64 for `diffusion_dkappa` and `refresh_diffusion_hierarchy` fed NumPy arrays (tests): the HIP runtime is reached through
     libmg_hip.so, which links it, so nothing else has to be found or imported."""
 
     def __init__(self, lib, device: int, n: int, host: Optional[np.ndarray] = None):
@@ -366,15 +366,38 @@ class DeviceHierarchy:
         """Levels top_level (default: the finest) .. coarsest from one kappa, coarsened on the device
         (`mg_gen_diffusion_hierarchy`, as `poisson.coarsen_kappa` does it); pruned; whole handles only.  With
         `matrix_free_min_rows` the levels above the coarsest with at least that many rows are matrix-free
-        (`mg_gen_diffusion_hierarchy_mf`)."""
+        (`mg_gen_diffusion_hierarchy_mf`).  An integer `kappa` is the device address of the top level's cells (the
+        convention of `diffusion_dkappa`): nothing is uploaded, the buffer is only read and the results are the same bit
+        for bit (`mg_gen_diffusion_hierarchy_device`)."""
         top = self.finest_level if top_level is None else top_level
-        k = self._kappa(top, kappa)
         avg = {"arithmetic": _capi.MG_KAPPA_ARITHMETIC, "harmonic": _capi.MG_KAPPA_HARMONIC}[averaging]
+        if isinstance(kappa, (int, np.integer)):
+            check(self._lib.mg_gen_diffusion_hierarchy_device(self._h, self._idx(top), self.elements(top), C.c_void_p(int(kappa)),
+                                                              avg, -1 if matrix_free_min_rows is None else int(matrix_free_min_rows)))
+            return
+        k = self._kappa(top, kappa)
         if matrix_free_min_rows is not None:
             check(self._lib.mg_gen_diffusion_hierarchy_mf(self._h, self._idx(top), self.elements(top), ptr(k), avg,
                                                           int(matrix_free_min_rows)))
             return
         check(self._lib.mg_gen_diffusion_hierarchy(self._h, self._idx(top), self.elements(top), ptr(k), avg))
+
+    def refresh_diffusion_hierarchy(self, kappa, averaging: str = "arithmetic", top_level: Optional[int] = None):
+        """Another kappa for a hierarchy `gen_diffusion_hierarchy` generated, in place (`mg_refresh_diffusion_hierarchy`):
+        the state a fresh generation with the same stored / matrix-free split leaves, bit for bit, without freeing or
+        allocating anything for the matrix-free levels.  `kappa` is a device address or, for tests, a NumPy array, which
+        is uploaded to a temporary device buffer first."""
+        top = self.finest_level if top_level is None else top_level
+        avg = {"arithmetic": _capi.MG_KAPPA_ARITHMETIC, "harmonic": _capi.MG_KAPPA_HARMONIC}[averaging]
+        if isinstance(kappa, (int, np.integer)):
+            check(self._lib.mg_refresh_diffusion_hierarchy(self._h, self._idx(top), C.c_void_p(int(kappa)), avg))
+            return
+        k = self._kappa(top, kappa)
+        dev = _DeviceArray(self._lib, self.device, k.size, k)
+        try:
+            check(self._lib.mg_refresh_diffusion_hierarchy(self._h, self._idx(top), dev.ptr, avg))
+        finally:
+            dev.free()
 
     def level_matrix_free(self, level: int) -> bool:
         """True if the level keeps kappa instead of a matrix (`mg_level_matrix_free`)."""

@@ -2,8 +2,10 @@
 with respect to kappa and f by the adjoint method.
 
 The only module of the package that imports torch.  Tensors enter and leave `libmg_hip.so` by device pointer
-(`mg_set_vector_device`, `mg_get_vector_device`, `mg_diffusion_dkappa`); kappa itself is uploaded from the host, as
-`mg_gen_diffusion_hierarchy` takes it.
+(`mg_set_vector_device`, `mg_get_vector_device`, `mg_diffusion_dkappa`).  So does a kappa that lives on the solver's
+device: the first solve generates the hierarchy from its address (`mg_gen_diffusion_hierarchy_device`), later solves put
+the new kappa into the hierarchy that is there (`mg_refresh_diffusion_hierarchy`), and nothing of kappa crosses to the
+host.  A kappa on the CPU is uploaded as `mg_gen_diffusion_hierarchy` takes it.
 
 Import order matters: torch (or this module) must be imported before anything loads `libmg_hip.so`, so that the library
 binds to the HIP runtime torch ships and both see the same device memory; `DiffusionSolver` raises otherwise.
@@ -47,16 +49,21 @@ class DiffusionSolver:
     -a_ib g_b terms that `mg_gen_diffusion_level` folds into its own right-hand side) depends on kappa itself; that
     dependence is the caller's: build the lifted f from kappa with differentiable torch operations if it matters.
 
-    `kappa`: N^3 positive float64, cell (ci, cj, ck) at (ck * N + cj) * N + ci, any shape, on the CPU or on the device (it
-    crosses to the host either way).  `f`, `u`: (N + 1)^3 float64 on the handle's device.  `averaging` and
-    `matrix_free_min_rows` as in `DeviceHierarchy.gen_diffusion_hierarchy`; `set_params` are those of
+    `kappa`: N^3 positive float64, cell (ci, cj, ck) at (ck * N + cj) * N + ci, any shape, on the CPU (uploaded, every
+    level regenerated) or on the solver's device (it stays there: the first solve generates, later ones refresh in
+    place; `last_generate` says which of "host", "device", "refresh" the last one was).  `f`, `u`: (N + 1)^3 float64 on
+    the handle's device.  `averaging` and `matrix_free_min_rows` as in `DeviceHierarchy.gen_diffusion_hierarchy`; `set_params` are those of
     `DeviceHierarchy.set_params` (defaults: V(2,2), omega 2/3, Jacobi; the restriction is always the P1 transpose).
 
     backward: one more `mg_pcg` on the same hierarchy (A is symmetric), A lambda = grad_u; then grad_f = lambda and
-    grad_kappa = -mg_diffusion_dkappa(lambda, u).  A solve that reaches `max_iter` raises `NotConverged`."""
+    grad_kappa = -mg_diffusion_dkappa(lambda, u).  A solve that reaches `max_iter` raises `NotConverged`.
+
+    `warm_start=True` keeps the last forward and the last adjoint solution and starts the next solve of each kind from
+    them instead of from zero (kappa that moves a little between solves).  The stopping test is relative to the
+    right-hand side either way, so the gradients are those of the converged solve."""
 
     def __init__(self, N: int, n_levels: int, averaging: str = "arithmetic", matrix_free_min_rows: Optional[int] = None,
-                 rtol: float = 1e-10, max_iter: int = 200, device: int = 0, **set_params):
+                 rtol: float = 1e-10, max_iter: int = 200, device: int = 0, warm_start: bool = False, **set_params):
         if n_levels < 2 or N % (1 << (n_levels - 1)):
             raise ValueError("N must be a multiple of 2^(n_levels - 1), with at least two levels")
         self.N, self.top = int(N), n_levels - 1
@@ -71,7 +78,12 @@ class DiffusionSolver:
         self.hierarchy.set_params(**params)
         self.hierarchy.set_prolongation("p1")
         self._generation = 0
+        self._generated = False         # a hierarchy call has generated the levels: a device kappa can refresh them
+        self.last_generate = None       # "host" / "device" / "refresh": how the last kappa reached the hierarchy
+        self.warm_start = bool(warm_start)
+        self._warm = {}                 # "forward" / "adjoint": the last solution of that kind (warm_start)
         self.last_iterations = {}       # "forward" / "adjoint": iterations of the last solve of that kind
+        self.last_residual = {}         # ... and ||r|| / ||rhs|| of mg_pcg's recursion where it stopped (None: no iteration was needed)
 
     def close(self):
         self.hierarchy.close()
@@ -86,8 +98,21 @@ class DiffusionSolver:
         return _Solve.apply(kappa, f, self)
 
     # ---- what the autograd function calls --------------------------------------------------------------------
-    def _generate(self, kappa_host: np.ndarray) -> int:
-        self.hierarchy.gen_diffusion_hierarchy(kappa_host, self.averaging, matrix_free_min_rows=self.matrix_free_min_rows)
+    def _generate(self, kappa) -> int:
+        """`kappa`: a host array (today's path) or a contiguous float64 tensor on the solver's device."""
+        if isinstance(kappa, np.ndarray):
+            self.hierarchy.gen_diffusion_hierarchy(kappa, self.averaging, matrix_free_min_rows=self.matrix_free_min_rows)
+            self.last_generate = "host"
+        else:
+            torch.cuda.current_stream(self.device).synchronize()    # kappa is complete before the handle's stream reads it
+            if self._generated:
+                self.hierarchy.refresh_diffusion_hierarchy(kappa.data_ptr(), self.averaging)
+                self.last_generate = "refresh"
+            else:
+                self.hierarchy.gen_diffusion_hierarchy(kappa.data_ptr(), self.averaging,
+                                                       matrix_free_min_rows=self.matrix_free_min_rows)
+                self.last_generate = "device"
+        self._generated = True
         self._generation += 1
         return self._generation
 
@@ -98,18 +123,25 @@ class DiffusionSolver:
         return x.detach().contiguous()
 
     def _pcg(self, rhs: torch.Tensor, which: str) -> torch.Tensor:
-        """A x = rhs from zero; rhs and x by pointer."""
+        """A x = rhs from zero, or from the last solution of this kind (warm_start); rhs and x by pointer."""
         h = self.hierarchy
         torch.cuda.current_stream(self.device).synchronize()        # rhs is complete before the handle's stream reads it
         h.set_vector_device(self.top, "f", rhs.data_ptr())
-        h.zero_vector(self.top, "v")
+        x0 = self._warm.get(which) if self.warm_start else None
+        if x0 is not None:
+            h.set_vector_device(self.top, "v", x0.data_ptr())
+        else:
+            h.zero_vector(self.top, "v")
         hist = h.pcg(rtol=self.rtol, max_iter=self.max_iter, level=self.top)
         self.last_iterations[which] = len(hist)
+        self.last_residual[which] = float(hist[-1]) / h.norm2(self.top, "f") if len(hist) else None
         if len(hist) >= self.max_iter and not hist[-1] <= self.rtol * h.norm2(self.top, "f"):
             raise NotConverged(f"the {which} solve reached max_iter = {self.max_iter} at ||r|| = {hist[-1]:.3e} "
                                f"(rtol {self.rtol:g}): no gradient is returned")
         x = torch.empty_like(rhs)
         h.get_vector_device(self.top, "v", x.data_ptr())
+        if self.warm_start:
+            self._warm[which] = x.clone()
         return x
 
 
@@ -118,11 +150,14 @@ class _Solve(torch.autograd.Function):
     def forward(ctx, kappa, f, solver):
         if kappa.dtype != torch.float64 or kappa.numel() != solver.N ** 3:
             raise ValueError(f"kappa must hold {solver.N ** 3} float64")
-        kappa_host = np.ascontiguousarray(kappa.detach().cpu().numpy().reshape(-1))
+        if kappa.device == solver.device:       # no .cpu(): a device copy that the caller's later updates do not reach feeds the library
+            kappa_kept = kappa.detach().reshape(-1).clone()
+        else:
+            kappa_kept = np.ascontiguousarray(kappa.detach().cpu().numpy().reshape(-1))
         rhs = solver._device_vector(f, "f")
-        ctx.generation = solver._generate(kappa_host)
+        ctx.generation = solver._generate(kappa_kept)
         u = solver._pcg(rhs, "forward")
-        ctx.solver, ctx.kappa_host = solver, kappa_host
+        ctx.solver, ctx.kappa_kept = solver, kappa_kept
         ctx.kappa_like = (kappa.shape, kappa.device)
         ctx.save_for_backward(u)
         return u.view(f.shape)
@@ -132,7 +167,7 @@ class _Solve(torch.autograd.Function):
         solver = ctx.solver
         (u,) = ctx.saved_tensors
         if ctx.generation != solver._generation:        # another kappa has been solved since: this one's operator again
-            ctx.generation = solver._generate(ctx.kappa_host)
+            ctx.generation = solver._generate(ctx.kappa_kept)
         lam = solver._pcg(solver._device_vector(grad_u, "grad_u"), "adjoint")
         grad_kappa = None
         if ctx.needs_input_grad[0]:

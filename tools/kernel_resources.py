@@ -2,6 +2,8 @@
 code object's notes.
 
     python tools/kernel_resources.py [text=jacobikc]
+
+Names behind tables of DESIGN.md: jacobikc, diffusion_mf, diffusion_dkappa, kappa_ingest.
 """
 import os
 import re
