@@ -227,8 +227,8 @@ int mg_gen_diffusion_hierarchy_mf(mg_handle h, int top_level, int elements_per_d
  * elements_per_dim^dim doubles of the top level in device memory of the handle's device, cell order as in
  * mg_gen_diffusion_level.  The caller's buffer is only read, never written and never taken over: a matrix-free top level
  * keeps its own copy, written by the pass that coarsens it (kappa_ingest, mg_diffusion_kappa.hip.h: the fine field read
- * once, the copy and the coarse field written, 17 B per fine cell in 3-D against 8 + 8 for a copy and 8 + 1 for
- * kappa_coarsen); the levels below take over the coarsened fields as in the host call.  Nothing of kappa crosses to the
+ * once, the copy and the coarse field written, 17 B per fine cell in 3-D against 8 + 8 for a copy and 8 + 1 for a
+ * coarsening pass of its own); the levels below take over the coarsened fields as in the host call.  Nothing of kappa crosses to the
  * host but the flag of the check and, in a refusal, the one bad value.  Runs on the handle's stream, which is synchronised
  * before return; the caller must have finished producing kappa (the contract of mg_set_vector_device).  Refused with an
  * error before any level is touched: a null pointer, a pointer that is not device memory of the handle's device, slab

@@ -620,6 +620,27 @@ void free_level(mg_context* c, Level& L) {
     L.has_matrix = false;
 }
 
+// A level that is being set: what it held goes first, and unless the build ends with `return done()` what it got so far
+// goes too, the error text kept (set-up paths have many early exits; they never leave a half-built level behind).
+struct LevelBuild {
+    mg_context* c;
+    Level& L;
+    bool built = false;
+    LevelBuild(mg_context* c_, Level& L_) : c(c_), L(L_) { free_level(c, L); }
+    LevelBuild(const LevelBuild&) = delete;
+    LevelBuild& operator=(const LevelBuild&) = delete;
+    ~LevelBuild() {
+        if (built) return;
+        const std::string why = g_err;
+        free_level(c, L);
+        g_err = why;
+    }
+    int done() {
+        built = true;
+        return 0;
+    }
+};
+
 // ---- tile kernel dispatch --------------------------------------------------------------------
 template <int WT, int R>
 void launch_ell_wr(int mode, bool dot, const EllArgs& a, unsigned grid, hipStream_t s) {
@@ -3549,6 +3570,15 @@ int finish_level(mg_context* c, Level& L) {
     return 0;
 }
 
+// the storage analysis of a level whose tiles (vals, cols, dinv) are written: every generated or handed-over matrix
+int finish_stored_rows(mg_context* c, Level& L, int level) {
+    MG_TRY(encode_level(c, L));
+    MG_TRY(repack_sdia(c, L, level));
+    MG_TRY(build_stencil_classes(c, L));
+    L.has_matrix = true;
+    return 0;
+}
+
 int alloc_ell(mg_context* c, Level& L) {
     L.R = c->rows_per_lane;
     L.nslices = (L.nloc + (int64_t)WAVE * L.R - 1) / ((int64_t)WAVE * L.R);
@@ -3592,6 +3622,48 @@ void sorted_offsets(int dim, int out[15][3], int* n) {
     *n = (int)offs.size();
     for (int t = 0; t < *n; ++t)
         for (int d = 0; d < 3; ++d) out[t][d] = offs[t][d];
+}
+
+// The stored-level pipeline of every generator: geometry, tiles of width W, vectors, the generating kernel, the storage
+// analysis, and F once more as the level's true right-hand side.  `launch(L, grid, counts)` enqueues the kernel for L.R rows
+// per lane: it writes the tiles, 1 / diagonal and F and counts the kept and the non-zero entries into counts[0], counts[1].
+template <class Launch>
+int gen_stored_level(mg_context* c, int level, int N, int W, Launch launch) {
+    Level& L = c->L[level];
+    LevelBuild build(c, L);
+    MG_TRY(setup_geometry(c, L, level, N));
+    L.W = W;
+    MG_TRY(alloc_ell(c, L));
+    MG_TRY(alloc_level_vectors(c, L));
+    unsigned long long* d_counts = reinterpret_cast<unsigned long long*>(c->partials);
+    HIP_TRY(hipMemsetAsync(d_counts, 0, 2 * sizeof(unsigned long long), c->stream));
+    launch(L, grid3(L.g, L.g.nk), d_counts);
+    HIP_TRY(hipGetLastError());
+    unsigned long long counts[2] = {0, 0};
+    HIP_TRY(hipMemcpyAsync(counts, d_counts, sizeof(counts), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    L.nnz_stored = counts[0];
+    L.nnz_nonzero = counts[1];
+    MG_TRY(finish_stored_rows(c, L, level));
+    // the generated right-hand side is also this level's true right-hand side for mg_fmg
+    if (level + 1 < c->nlev) {
+        MG_TRY(vec_alloc(c, L, &L.ftrue));
+        HIP_TRY(hipMemcpyAsync(L.ftrue.base, L.f.base, (size_t)L.xlen * 8, hipMemcpyDeviceToDevice, c->stream));
+    }
+    L.set = true;
+    return build.done();
+}
+
+// what gen_poisson and gen_diffusion take alike: the mesh width, the load's scale, the stencil's offsets and the level
+// width W (the grid follows at the launch, once the level has its geometry)
+GenArgs gen_args(const mg_context* c, int N, int prune_zeros) {
+    GenArgs a{};
+    a.N = N; a.dim = c->dim; a.prune = prune_zeros;
+    a.h = 1.0 / (double)N;
+    a.fh = (c->dim == 2 ? -6.0 : -12.0) * std::pow(a.h, (double)c->dim);
+    sorted_offsets(c->dim, a.off, &a.noff);
+    a.W = prune_zeros ? (c->dim == 2 ? 5 : 7) : a.noff;
+    return a;
 }
 
 }  // namespace
@@ -4197,10 +4269,7 @@ int build_level_from_csr(mg_context* c, int level, Level& L, int64_t n_rows, int
         L.nnz_nonzero = nz;
     }
     HIP_TRY(hipStreamSynchronize(c->stream));
-    MG_TRY(encode_level(c, L));
-    MG_TRY(repack_sdia(c, L, level));
-    MG_TRY(build_stencil_classes(c, L));
-    L.has_matrix = true;
+    MG_TRY(finish_stored_rows(c, L, level));
     if (!vectors) { L.set = true; return 0; }
     return finish_level(c, L);
 }
@@ -4261,34 +4330,27 @@ int galerkin_level(mg_context* c, int level) {
             if (a.diag[q] >= 0) a.tpos[q] = 3 + (a.flin[q] < 0 ? -a.diag[q] : a.diag[q]);
         }
     Level& C = c->L[level - 1];
-    free_level(c, C);
-    int rc = [&]() -> int {
-        MG_TRY(setup_geometry(c, C, level - 1, F.N / 2));
-        if (!C.replicated) return fail("Galerkin coarse levels need a whole coarse level");
-        const int64_t n = C.n_global, nnz = n * K;
-        DevTemp d_ptr, d_idx, d_val;
-        MG_TRY(d_ptr.alloc((size_t)(n + 1) * 8));
-        MG_TRY(d_idx.alloc((size_t)nnz * 4));
-        MG_TRY(d_val.alloc((size_t)nnz * 8));
-        a.gc = C.g;
-        a.indptr = static_cast<int64_t*>(d_ptr.p); a.indices = static_cast<int*>(d_idx.p); a.data = static_cast<double*>(d_val.p);
-        a.flag = reinterpret_cast<int*>(c->partials);
-        HIP_TRY(hipMemsetAsync(a.flag, 0, sizeof(int), c->stream));
-        const dim3 grid = grid3(C.g, C.g.nk);
-        MG_TRY(c->dim == 3 ? launch_galerkin<3>(c, fmt, a, grid) : launch_galerkin<2>(c, fmt, a, grid));
-        int flag = 0;
-        HIP_TRY(hipMemcpyAsync(&flag, a.flag, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        if (flag) return fail("a Galerkin entry falls outside the coarse Kuhn pattern");
-        return build_level_from_csr(c, level - 1, C, n, nnz, d_ptr.p, 1, static_cast<const int32_t*>(d_idx.p),
-                                    static_cast<const double*>(d_val.p), nullptr, 1, true, nullptr, 0, true);
-    }();
-    if (rc) {
-        const std::string why = g_err;
-        free_level(c, C);
-        g_err = why;
-    }
-    return rc;
+    LevelBuild build(c, C);
+    MG_TRY(setup_geometry(c, C, level - 1, F.N / 2));
+    if (!C.replicated) return fail("Galerkin coarse levels need a whole coarse level");
+    const int64_t n = C.n_global, nnz = n * K;
+    DevTemp d_ptr, d_idx, d_val;
+    MG_TRY(d_ptr.alloc((size_t)(n + 1) * 8));
+    MG_TRY(d_idx.alloc((size_t)nnz * 4));
+    MG_TRY(d_val.alloc((size_t)nnz * 8));
+    a.gc = C.g;
+    a.indptr = static_cast<int64_t*>(d_ptr.p); a.indices = static_cast<int*>(d_idx.p); a.data = static_cast<double*>(d_val.p);
+    a.flag = reinterpret_cast<int*>(c->partials);
+    HIP_TRY(hipMemsetAsync(a.flag, 0, sizeof(int), c->stream));
+    const dim3 grid = grid3(C.g, C.g.nk);
+    MG_TRY(c->dim == 3 ? launch_galerkin<3>(c, fmt, a, grid) : launch_galerkin<2>(c, fmt, a, grid));
+    int flag = 0;
+    HIP_TRY(hipMemcpyAsync(&flag, a.flag, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (flag) return fail("a Galerkin entry falls outside the coarse Kuhn pattern");
+    MG_TRY(build_level_from_csr(c, level - 1, C, n, nnz, d_ptr.p, 1, static_cast<const int32_t*>(d_idx.p),
+                                static_cast<const double*>(d_val.p), nullptr, 1, true, nullptr, 0, true));
+    return build.done();
 }
 
 }  // namespace
@@ -4301,18 +4363,12 @@ int mg_set_level_csr(mg_handle c, int level, int N, int64_t n_rows, int64_t nnz,
     MG_TRY(check_csr(n_rows, n_rows, nnz, indptr, indptr_is_64, indices, false));      // (grid and flat levels alike)
     HIP_TRY(hipSetDevice(c->device));
     Level& L = c->L[level];
-    free_level(c, L);
+    LevelBuild build(c, L);
     MG_TRY(setup_geometry(c, L, level, N, n_rows));
     if (n_rows != L.n_global)
         return fail("matrix has " + std::to_string(n_rows) + " rows, grid has " + std::to_string(L.n_global));
-    const int rc = build_level_from_csr(c, level, L, n_rows, nnz, indptr, indptr_is_64, indices, data, grid_index,
-                                        prune_zeros);
-    if (rc) {
-        const std::string why = g_err;
-        free_level(c, L);           // never leave a half-built level behind
-        g_err = why;
-    }
-    return rc;
+    MG_TRY(build_level_from_csr(c, level, L, n_rows, nnz, indptr, indptr_is_64, indices, data, grid_index, prune_zeros));
+    return build.done();
 }
 
 int mg_csr_check(int64_t n_rows, int64_t n_cols, int64_t nnz, const void* indptr, int indptr_is_64, const int32_t* indices,
@@ -4342,19 +4398,14 @@ int mg_set_level_csr_local(mg_handle c, int level, int N, int64_t n_rows, int64_
     MG_TRY(check_csr(n_rows, n_cols, nnz, indptr, indptr_is_64, indices, false));
     HIP_TRY(hipSetDevice(c->device));
     Level& L = c->L[level];
-    free_level(c, L);
+    LevelBuild build(c, L);
     MG_TRY(setup_geometry(c, L, level, N));
     if (n_rows != L.nloc)
         return fail("the rank owns " + std::to_string(L.nloc) + " rows of this level (mg_level_slab), " + std::to_string(n_rows) +
                     " were handed over");
-    const int rc = build_level_from_csr(c, level, L, n_rows, nnz, indptr, indptr_is_64, indices, data, grid_index, prune_zeros,
-                                        true, col_nodes, n_cols);
-    if (rc) {
-        const std::string why = g_err;
-        free_level(c, L);
-        g_err = why;
-    }
-    return rc;
+    MG_TRY(build_level_from_csr(c, level, L, n_rows, nnz, indptr, indptr_is_64, indices, data, grid_index, prune_zeros, true,
+                                col_nodes, n_cols));
+    return build.done();
 }
 
 int mg_set_level_grid(mg_handle c, int level, int N, int64_t n_rows, const int64_t* grid_index) {
@@ -4362,18 +4413,13 @@ int mg_set_level_grid(mg_handle c, int level, int N, int64_t n_rows, const int64
     if (N < 0) return fail("elements_per_dim must be >= 0");
     HIP_TRY(hipSetDevice(c->device));
     Level& L = c->L[level];
-    free_level(c, L);
+    LevelBuild build(c, L);
     MG_TRY(setup_geometry(c, L, level, N, n_rows));
     if (n_rows != L.n_global)
         return fail("vector has " + std::to_string(n_rows) + " entries, grid has " + std::to_string(L.n_global));
-    int rc = upload_permutation(c, L, grid_index, n_rows);
-    if (!rc) rc = finish_level(c, L);
-    if (rc) {
-        const std::string why = g_err;
-        free_level(c, L);
-        g_err = why;
-    }
-    return rc;
+    MG_TRY(upload_permutation(c, L, grid_index, n_rows));
+    MG_TRY(finish_level(c, L));
+    return build.done();
 }
 
 int mg_galerkin_level(mg_handle c, int level) {
@@ -4393,45 +4439,19 @@ int mg_gen_poisson_level(mg_handle c, int level, int N, int prune_zeros) {
     MG_TRY(check_level(c, level, false));
     if (N <= 0) return fail("elements_per_dim must be positive");
     HIP_TRY(hipSetDevice(c->device));
-    Level& L = c->L[level];
-    free_level(c, L);
-    MG_TRY(setup_geometry(c, L, level, N));
-    GenArgs a{};
-    a.g = L.g; a.N = N; a.dim = c->dim; a.prune = prune_zeros; a.odd = c->gen_odd_rows;
-    a.h = 1.0 / (double)N;
+    GenArgs a = gen_args(c, N, prune_zeros);
+    a.odd = c->gen_odd_rows;
     a.w = c->dim == 2 ? 1.0 : a.h;
     a.diag = c->dim == 2 ? 4.0 : 6.0 * a.h;
-    a.fh = (c->dim == 2 ? -6.0 : -12.0) * std::pow(a.h, (double)c->dim);
-    sorted_offsets(c->dim, a.off, &a.noff);
-    L.W = prune_zeros ? (c->dim == 2 ? 5 : 7) : a.noff;
-    a.W = L.W;
-    MG_TRY(alloc_ell(c, L));
-    MG_TRY(alloc_level_vectors(c, L));
-    unsigned long long* d_counts = reinterpret_cast<unsigned long long*>(c->partials);
-    HIP_TRY(hipMemsetAsync(d_counts, 0, 2 * sizeof(unsigned long long), c->stream));
-    const dim3 grid = grid3(L.g, L.g.nk), blk(kPlaneBlock);
-    switch (L.R) {
-        case 1: hipLaunchKernelGGL(gen_poisson<1>, grid, blk, 0, c->stream, a, L.vals, L.cols, L.dinv, L.f.rows, d_counts); break;
-        case 2: hipLaunchKernelGGL(gen_poisson<2>, grid, blk, 0, c->stream, a, L.vals, L.cols, L.dinv, L.f.rows, d_counts); break;
-        default: hipLaunchKernelGGL(gen_poisson<4>, grid, blk, 0, c->stream, a, L.vals, L.cols, L.dinv, L.f.rows, d_counts); break;
-    }
-    HIP_TRY(hipGetLastError());
-    unsigned long long counts[2] = {0, 0};
-    HIP_TRY(hipMemcpyAsync(counts, d_counts, sizeof(counts), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    L.nnz_stored = counts[0];
-    L.nnz_nonzero = counts[1];
-    MG_TRY(encode_level(c, L));
-    MG_TRY(repack_sdia(c, L, level));
-    MG_TRY(build_stencil_classes(c, L));
-    // the generated right-hand side is also this level's true right-hand side for mg_fmg
-    if (level + 1 < c->nlev) {
-        MG_TRY(vec_alloc(c, L, &L.ftrue));
-        HIP_TRY(hipMemcpyAsync(L.ftrue.base, L.f.base, (size_t)L.xlen * 8, hipMemcpyDeviceToDevice, c->stream));
-    }
-    L.set = true;
-    L.has_matrix = true;
-    return 0;
+    return gen_stored_level(c, level, N, a.W, [&](const Level& L, dim3 grid, unsigned long long* counts) {
+        const dim3 blk(kPlaneBlock);
+        a.g = L.g;
+        switch (L.R) {
+            case 1: hipLaunchKernelGGL(gen_poisson<1>, grid, blk, 0, c->stream, a, L.vals, L.cols, L.dinv, L.f.rows, counts); break;
+            case 2: hipLaunchKernelGGL(gen_poisson<2>, grid, blk, 0, c->stream, a, L.vals, L.cols, L.dinv, L.f.rows, counts); break;
+            default: hipLaunchKernelGGL(gen_poisson<4>, grid, blk, 0, c->stream, a, L.vals, L.cols, L.dinv, L.f.rows, counts); break;
+        }
+    });
 }
 
 int mg_gen_lattice_level(mg_handle c, int level, int N, int width, const int* count, const int* offsets, const double* values,
@@ -4445,9 +4465,6 @@ int mg_gen_lattice_level(mg_handle c, int level, int N, int width, const int* co
     for (int p = 0; p < 8; ++p)
         if (count[p] < 0 || count[p] > width) return fail("a class has more entries than the stated width");
     HIP_TRY(hipSetDevice(c->device));
-    Level& L = c->L[level];
-    free_level(c, L);
-    MG_TRY(setup_geometry(c, L, level, N));
     DevTemp d_count, d_off, d_val, d_load;
     MG_TRY(d_count.alloc(8 * sizeof(int)));
     MG_TRY(d_off.alloc((size_t)8 * LAT_MAX * 3 * sizeof(int)));
@@ -4458,36 +4475,18 @@ int mg_gen_lattice_level(mg_handle c, int level, int N, int width, const int* co
     HIP_TRY(hipMemcpy(d_val.p, values, (size_t)8 * LAT_MAX * sizeof(double), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(d_load.p, load, 8 * sizeof(double), hipMemcpyHostToDevice));
     LatticeArgs a{};
-    a.g = L.g; a.N = N; a.dim = c->dim; a.W = width;
+    a.N = N; a.dim = c->dim; a.W = width;
     a.count = static_cast<const int*>(d_count.p); a.off = static_cast<const int*>(d_off.p);
     a.val = static_cast<const double*>(d_val.p); a.load = static_cast<const double*>(d_load.p);
-    L.W = width;
-    MG_TRY(alloc_ell(c, L));
-    MG_TRY(alloc_level_vectors(c, L));
-    unsigned long long* d_counts = reinterpret_cast<unsigned long long*>(c->partials);
-    HIP_TRY(hipMemsetAsync(d_counts, 0, 2 * sizeof(unsigned long long), c->stream));
-    const dim3 grid = grid3(L.g, L.g.nk), blk(kPlaneBlock);
-    switch (L.R) {
-        case 1: hipLaunchKernelGGL(gen_lattice<1>, grid, blk, 0, c->stream, a, L.vals, L.cols, L.dinv, L.f.rows, d_counts); break;
-        case 2: hipLaunchKernelGGL(gen_lattice<2>, grid, blk, 0, c->stream, a, L.vals, L.cols, L.dinv, L.f.rows, d_counts); break;
-        default: hipLaunchKernelGGL(gen_lattice<4>, grid, blk, 0, c->stream, a, L.vals, L.cols, L.dinv, L.f.rows, d_counts); break;
-    }
-    HIP_TRY(hipGetLastError());
-    unsigned long long counts[2] = {0, 0};
-    HIP_TRY(hipMemcpyAsync(counts, d_counts, sizeof(counts), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    L.nnz_stored = counts[0];
-    L.nnz_nonzero = counts[1];
-    MG_TRY(encode_level(c, L));
-    MG_TRY(repack_sdia(c, L, level));
-    MG_TRY(build_stencil_classes(c, L));
-    if (level + 1 < c->nlev) {
-        MG_TRY(vec_alloc(c, L, &L.ftrue));
-        HIP_TRY(hipMemcpyAsync(L.ftrue.base, L.f.base, (size_t)L.xlen * 8, hipMemcpyDeviceToDevice, c->stream));
-    }
-    L.set = true;
-    L.has_matrix = true;
-    return 0;
+    return gen_stored_level(c, level, N, width, [&](const Level& L, dim3 grid, unsigned long long* counts) {
+        const dim3 blk(kPlaneBlock);
+        a.g = L.g;
+        switch (L.R) {
+            case 1: hipLaunchKernelGGL(gen_lattice<1>, grid, blk, 0, c->stream, a, L.vals, L.cols, L.dinv, L.f.rows, counts); break;
+            case 2: hipLaunchKernelGGL(gen_lattice<2>, grid, blk, 0, c->stream, a, L.vals, L.cols, L.dinv, L.f.rows, counts); break;
+            default: hipLaunchKernelGGL(gen_lattice<4>, grid, blk, 0, c->stream, a, L.vals, L.cols, L.dinv, L.f.rows, counts); break;
+        }
+    });
 }
 
 namespace {
@@ -4524,55 +4523,21 @@ int check_kappa(mg_context* c, const double* d_kappa, int64_t n, int64_t base, i
     return fail("kappa must be positive and finite: cell " + cell + ") = index " + std::to_string(q) + " holds " + val);
 }
 
-// the level from a device kappa holding cell planes [kc0, ...): mg_gen_poisson_level's pipeline with gen_diffusion
+// the stored level from a device kappa holding cell planes [kc0, ...)
 int gen_diffusion_level(mg_context* c, int level, int N, const double* d_kappa, int kc0, int prune_zeros) {
-    Level& L = c->L[level];
-    free_level(c, L);
-    const int rc = [&]() -> int {
-        MG_TRY(setup_geometry(c, L, level, N));
-        DiffusionArgs d{};
-        GenArgs& a = d.ga;
-        a.g = L.g; a.N = N; a.dim = c->dim; a.prune = prune_zeros;
-        a.h = 1.0 / (double)N;
-        a.fh = (c->dim == 2 ? -6.0 : -12.0) * std::pow(a.h, (double)c->dim);
-        sorted_offsets(c->dim, a.off, &a.noff);
-        L.W = prune_zeros ? (c->dim == 2 ? 5 : 7) : a.noff;
-        a.W = L.W;
-        d.kappa = d_kappa;
-        d.kc0 = kc0;
-        MG_TRY(alloc_ell(c, L));
-        MG_TRY(alloc_level_vectors(c, L));
-        unsigned long long* d_counts = reinterpret_cast<unsigned long long*>(c->partials);
-        HIP_TRY(hipMemsetAsync(d_counts, 0, 2 * sizeof(unsigned long long), c->stream));
-        const dim3 grid = grid3(L.g, L.g.nk), blk(kPlaneBlock);
+    DiffusionArgs d{};
+    d.ga = gen_args(c, N, prune_zeros);
+    d.kappa = d_kappa;
+    d.kc0 = kc0;
+    return gen_stored_level(c, level, N, d.ga.W, [&](const Level& L, dim3 grid, unsigned long long* counts) {
+        const dim3 blk(kPlaneBlock);
+        d.ga.g = L.g;
         switch (L.R) {
-            case 1: hipLaunchKernelGGL(gen_diffusion<1>, grid, blk, 0, c->stream, d, L.vals, L.cols, L.dinv, L.f.rows, d_counts); break;
-            case 2: hipLaunchKernelGGL(gen_diffusion<2>, grid, blk, 0, c->stream, d, L.vals, L.cols, L.dinv, L.f.rows, d_counts); break;
-            default: hipLaunchKernelGGL(gen_diffusion<4>, grid, blk, 0, c->stream, d, L.vals, L.cols, L.dinv, L.f.rows, d_counts); break;
+            case 1: hipLaunchKernelGGL(gen_diffusion<1>, grid, blk, 0, c->stream, d, L.vals, L.cols, L.dinv, L.f.rows, counts); break;
+            case 2: hipLaunchKernelGGL(gen_diffusion<2>, grid, blk, 0, c->stream, d, L.vals, L.cols, L.dinv, L.f.rows, counts); break;
+            default: hipLaunchKernelGGL(gen_diffusion<4>, grid, blk, 0, c->stream, d, L.vals, L.cols, L.dinv, L.f.rows, counts); break;
         }
-        HIP_TRY(hipGetLastError());
-        unsigned long long counts[2] = {0, 0};
-        HIP_TRY(hipMemcpyAsync(counts, d_counts, sizeof(counts), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        L.nnz_stored = counts[0];
-        L.nnz_nonzero = counts[1];
-        MG_TRY(encode_level(c, L));
-        MG_TRY(repack_sdia(c, L, level));
-        MG_TRY(build_stencil_classes(c, L));
-        if (level + 1 < c->nlev) {
-            MG_TRY(vec_alloc(c, L, &L.ftrue));
-            HIP_TRY(hipMemcpyAsync(L.ftrue.base, L.f.base, (size_t)L.xlen * 8, hipMemcpyDeviceToDevice, c->stream));
-        }
-        L.set = true;
-        L.has_matrix = true;
-        return 0;
-    }();
-    if (rc) {
-        const std::string why = g_err;
-        free_level(c, L);
-        g_err = why;
-    }
-    return rc;
+    });
 }
 
 }  // namespace
@@ -4596,46 +4561,43 @@ int mg_gen_diffusion_level(mg_handle c, int level, int N, const double* kappa, i
 
 namespace {
 
+// F of a matrix-free level from its kappa, and once more as the level's true right-hand side where it keeps one; allocates
+// nothing (mg_refresh_diffusion_hierarchy relies on that)
+int fill_rhs_mf(mg_context* c, Level& L, const double* d_kappa) {
+    MG_TRY(launch_diffusion_rhs(c, L, d_kappa, L.f.rows, nullptr));
+    if (L.ftrue.raw) HIP_TRY(hipMemcpyAsync(L.ftrue.base, L.f.base, (size_t)L.xlen * 8, hipMemcpyDeviceToDevice, c->stream));
+    return 0;
+}
+
 // the matrix-free level from a whole device kappa (N^3 cells), which the level takes over on success
 int gen_diffusion_level_mf(mg_context* c, int level, int N, double* d_kappa, int64_t n) {
     Level& L = c->L[level];
-    free_level(c, L);
-    const int rc = [&]() -> int {
-        MG_TRY(setup_geometry(c, L, level, N));
-        L.W = 7;
-        L.R = c->rows_per_lane;         // (the slice count is what callers of launch_ell take a whole level's range from)
-        L.nslices = (L.nloc + (int64_t)WAVE * L.R - 1) / ((int64_t)WAVE * L.R);
-        MG_TRY(alloc_level_vectors(c, L));
-        MG_TRY(launch_diffusion_rhs(c, L, d_kappa, L.f.rows, nullptr));
-        if (level + 1 < c->nlev) {
-            MG_TRY(vec_alloc(c, L, &L.ftrue));
-            HIP_TRY(hipMemcpyAsync(L.ftrue.base, L.f.base, (size_t)L.xlen * 8, hipMemcpyDeviceToDevice, c->stream));
-        }
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        // what the stored level would report: seven entries per interior row less the columns on the boundary, one per boundary row
-        const int64_t m = N - 1;
-        L.nnz_stored = L.nnz_nonzero = (unsigned long long)(m * m * m + 6 * m * m * (m - 1) + (L.n_global - m * m * m));
-        L.rep_sym = 1;
-        L.rb_ok = false;
-        L.mf = true;
-        L.kappa = d_kappa;
-        L.kappa_n = n;
-        c->bytes += n * (int64_t)sizeof(double);
-        L.set = true;
-        L.has_matrix = true;
-        return 0;
-    }();
-    if (rc) {
-        const std::string why = g_err;
-        free_level(c, L);
-        g_err = why;
-    }
-    return rc;
+    LevelBuild build(c, L);
+    MG_TRY(setup_geometry(c, L, level, N));
+    L.W = 7;
+    L.R = c->rows_per_lane;         // (the slice count is what callers of launch_ell take a whole level's range from)
+    L.nslices = (L.nloc + (int64_t)WAVE * L.R - 1) / ((int64_t)WAVE * L.R);
+    MG_TRY(alloc_level_vectors(c, L));
+    if (level + 1 < c->nlev) MG_TRY(vec_alloc(c, L, &L.ftrue));     // (the true right-hand side for mg_fmg, as on stored levels)
+    MG_TRY(fill_rhs_mf(c, L, d_kappa));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    // what the stored level would report: seven entries per interior row less the columns on the boundary, one per boundary row
+    const int64_t m = N - 1;
+    L.nnz_stored = L.nnz_nonzero = (unsigned long long)(m * m * m + 6 * m * m * (m - 1) + (L.n_global - m * m * m));
+    L.rep_sym = 1;
+    L.rb_ok = false;
+    L.mf = true;
+    L.kappa = d_kappa;
+    L.kappa_n = n;
+    c->bytes += n * (int64_t)sizeof(double);
+    L.set = true;
+    L.has_matrix = true;
+    return build.done();
 }
 
-int mf_refusals(mg_context* c, const char* who) {
-    if (c->dim != 3) return fail(std::string(who) + ": matrix-free diffusion levels are 3-D only (this handle is 2-D)");
-    if (c->comm.active()) return fail(std::string(who) + ": matrix-free diffusion levels need a whole (not slab) handle");
+int mf_refusals(mg_context* c, const std::string& who) {
+    if (c->dim != 3) return fail(who + ": matrix-free diffusion levels are 3-D only (this handle is 2-D)");
+    if (c->comm.active()) return fail(who + ": matrix-free diffusion levels need a whole (not slab) handle");
     return 0;
 }
 
@@ -4664,72 +4626,8 @@ int mg_gen_diffusion_level_mf(mg_handle c, int level, int N, const double* kappa
 
 namespace {
 
-// Levels top_level .. 0 from the top level's kappa, coarsened on the device; levels above level 0 with at least min_rows rows
-// become matrix-free and take their kappa over, the others are stored (generated before their kappa is coarsened and freed).
-// At most two kappa fields are alive at a time besides those the matrix-free levels keep.
-int gen_diffusion_hierarchy(mg_context* c, const std::string& who, int top_level, int N, const double* kappa_top, int averaging,
-                            int64_t min_rows) {
-    if (N <= 0) return fail("elements_per_dim must be positive");
-    if (!kappa_top) return fail("null kappa");
-    if (averaging != MG_KAPPA_ARITHMETIC && averaging != MG_KAPPA_HARMONIC) return fail("unknown kappa averaging");
-    if (c->comm.active())
-        return fail(who + " needs a whole (not slab) handle: on slabs, call mg_gen_diffusion_level per level");
-    if (N % (1 << top_level))
-        return fail(who + " needs an even elements_per_dim on every level above level 0 (" + std::to_string(N) +
-                    " is not N0 * 2^" + std::to_string(top_level) + ")");
-    HIP_TRY(hipSetDevice(c->device));
-    Level geo;
-    MG_TRY(setup_geometry(c, geo, top_level, N));
-    int64_t n = cell_plane(c, N) * N;
-    DevTemp fine, coarse;
-    MG_TRY(fine.alloc((size_t)n * 8));
-    HIP_TRY(hipMemcpy(fine.p, kappa_top, (size_t)n * 8, hipMemcpyHostToDevice));
-    MG_TRY(check_kappa(c, static_cast<const double*>(fine.p), n, 0, N));
-    for (int l = top_level, Nl = N; l >= 0; --l, Nl /= 2) {
-        n = cell_plane(c, Nl) * Nl;
-        const int64_t rows = c->dim == 3 ? ((int64_t)Nl + 1) * (Nl + 1) * (Nl + 1) : ((int64_t)Nl + 1) * (Nl + 1);
-        const bool mf = l > 0 && rows >= min_rows;
-        if (!mf) MG_TRY(gen_diffusion_level(c, l, Nl, static_cast<const double*>(fine.p), 0, 1));
-        if (l > 0) {
-            const int Nc = Nl / 2;
-            const int64_t nc = cell_plane(c, Nc) * Nc;
-            MG_TRY(coarse.alloc((size_t)nc * 8));
-            const unsigned nb = (unsigned)std::max<int64_t>(1, std::min<int64_t>(8192, (nc + 255) / 256));
-            if (c->dim == 3)
-                hipLaunchKernelGGL(kappa_coarsen<3>, dim3(nb), dim3(256), 0, c->stream, static_cast<const double*>(fine.p),
-                                   static_cast<double*>(coarse.p), Nc, averaging == MG_KAPPA_HARMONIC ? 1 : 0);
-            else
-                hipLaunchKernelGGL(kappa_coarsen<2>, dim3(nb), dim3(256), 0, c->stream, static_cast<const double*>(fine.p),
-                                   static_cast<double*>(coarse.p), Nc, averaging == MG_KAPPA_HARMONIC ? 1 : 0);
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipStreamSynchronize(c->stream));
-        }
-        if (mf) MG_TRY(gen_diffusion_level_mf(c, l, Nl, static_cast<double*>(fine.p), n));     // (the level owns its kappa now)
-        else HIP_TRY(hipFree(fine.p));
-        fine.p = coarse.p;
-        coarse.p = nullptr;
-        c->L[l].diffusion_hierarchy = true;
-    }
-    return 0;
-}
-
-}  // namespace
-
-int mg_gen_diffusion_hierarchy(mg_handle c, int top_level, int N, const double* kappa_top, int averaging) {
-    MG_TRY(check_level(c, top_level, false));
-    return gen_diffusion_hierarchy(c, "mg_gen_diffusion_hierarchy", top_level, N, kappa_top, averaging, INT64_MAX);
-}
-
-int mg_gen_diffusion_hierarchy_mf(mg_handle c, int top_level, int N, const double* kappa_top, int averaging, int64_t min_rows) {
-    MG_TRY(check_level(c, top_level, false));
-    MG_TRY(mf_refusals(c, "mg_gen_diffusion_hierarchy_mf"));
-    return gen_diffusion_hierarchy(c, "mg_gen_diffusion_hierarchy_mf", top_level, N, kappa_top, averaging, min_rows);
-}
-
-namespace {
-
-// one pass over a level's device kappa (mg_diffusion_kappa.hip.h): the level's own copy (fine_out, may be null) and the
-// kappa of the Nc^dim cells of the level below
+// one pass over a level's device kappa (mg_diffusion_kappa.hip.h): the kappa of the Nc^dim cells of the level below and,
+// where fine_out is not null, the level's own copy
 int launch_kappa_ingest(mg_context* c, const double* fine, double* fine_out, double* coarse, int Nc, int averaging) {
     const int64_t nc = cell_plane(c, Nc) * Nc;
     const unsigned nb = (unsigned)std::max<int64_t>(1, std::min<int64_t>(2048, (nc + KI_BLOCK - 1) / KI_BLOCK));
@@ -4743,15 +4641,32 @@ int launch_kappa_ingest(mg_context* c, const double* fine, double* fine_out, dou
     return 0;
 }
 
-// gen_diffusion_hierarchy from a kappa that is on the device already: the caller's buffer is only read; a matrix-free
-// top level gets its own copy from the pass that coarsens it, the levels below take over the coarsened fields as there
-int gen_diffusion_hierarchy_device(mg_context* c, int top_level, int N, const double* kappa_dev, int averaging, int64_t min_rows) {
-    int64_t n = cell_plane(c, N) * N;
-    MG_TRY(check_kappa(c, kappa_dev, n, 0, N));
-    const double* src = kappa_dev;
-    DevTemp held;                               // src where it is ours: the coarsened field of the level above
+// What the three generating hierarchy entries refuse alike (`matrix_free`: the call may make matrix-free levels), a top
+// level whose geometry setup_geometry refuses last.  Only checks: nothing of the handle or the device is touched.
+int hierarchy_refusals(mg_context* c, const std::string& who, int top_level, int N, int averaging, bool matrix_free) {
+    if (matrix_free) MG_TRY(mf_refusals(c, who));
+    if (N <= 0) return fail("elements_per_dim must be positive");
+    if (averaging != MG_KAPPA_ARITHMETIC && averaging != MG_KAPPA_HARMONIC) return fail("unknown kappa averaging");
+    if (c->comm.active())
+        return fail(who + " needs a whole (not slab) handle: on slabs, call mg_gen_diffusion_level per level");
+    if (N % (1 << top_level))
+        return fail(who + " needs an even elements_per_dim on every level above level 0 (" + std::to_string(N) +
+                    " is not N0 * 2^" + std::to_string(top_level) + ")");
+    Level geo;
+    return setup_geometry(c, geo, top_level, N);
+}
+
+// Levels top_level .. 0 from the top level's kappa on the device, coarsened level by level; levels above level 0 with at
+// least min_rows rows become matrix-free, the others are stored (generated before their kappa is coarsened and freed).
+// `held` is `src` where the field is the walker's to give away or free -- a host entry's upload, and below the top level
+// the coarsened field of the level above -- and empty where `src` is the caller's buffer, which is only read.  A
+// matrix-free level takes a held field over as it is and gets its own copy of a borrowed one from the pass that coarsens
+// it.  At most two kappa fields are alive at a time besides those the matrix-free levels keep.
+int gen_diffusion_hierarchy(mg_context* c, int top_level, int N, const double* src, DevTemp& held, int averaging,
+                            int64_t min_rows) {
+    MG_TRY(check_kappa(c, src, cell_plane(c, N) * N, 0, N));
     for (int l = top_level, Nl = N; l >= 0; --l, Nl /= 2) {
-        n = cell_plane(c, Nl) * Nl;
+        const int64_t n = cell_plane(c, Nl) * Nl;
         const int64_t rows = c->dim == 3 ? ((int64_t)Nl + 1) * (Nl + 1) * (Nl + 1) : ((int64_t)Nl + 1) * (Nl + 1);
         const bool mf = l > 0 && rows >= min_rows;
         if (!mf) MG_TRY(gen_diffusion_level(c, l, Nl, src, 0, 1));
@@ -4777,7 +4692,29 @@ int gen_diffusion_hierarchy_device(mg_context* c, int top_level, int N, const do
     return 0;
 }
 
+// the host entries: the top level's kappa is uploaded and the upload handed to the walker as its own
+int gen_diffusion_hierarchy_host(mg_context* c, const std::string& who, int top_level, int N, const double* kappa_top,
+                                 int averaging, bool matrix_free, int64_t min_rows) {
+    MG_TRY(check_level(c, top_level, false));
+    if (!kappa_top) return fail("null kappa");
+    MG_TRY(hierarchy_refusals(c, who, top_level, N, averaging, matrix_free));
+    HIP_TRY(hipSetDevice(c->device));
+    const int64_t n = cell_plane(c, N) * N;
+    DevTemp held;
+    MG_TRY(held.alloc((size_t)n * 8));
+    HIP_TRY(hipMemcpy(held.p, kappa_top, (size_t)n * 8, hipMemcpyHostToDevice));
+    return gen_diffusion_hierarchy(c, top_level, N, static_cast<const double*>(held.p), held, averaging, min_rows);
+}
+
 }  // namespace
+
+int mg_gen_diffusion_hierarchy(mg_handle c, int top_level, int N, const double* kappa_top, int averaging) {
+    return gen_diffusion_hierarchy_host(c, "mg_gen_diffusion_hierarchy", top_level, N, kappa_top, averaging, false, INT64_MAX);
+}
+
+int mg_gen_diffusion_hierarchy_mf(mg_handle c, int top_level, int N, const double* kappa_top, int averaging, int64_t min_rows) {
+    return gen_diffusion_hierarchy_host(c, "mg_gen_diffusion_hierarchy_mf", top_level, N, kappa_top, averaging, true, min_rows);
+}
 
 int mg_gen_diffusion_hierarchy_device(mg_handle c, int top_level, int N, const double* kappa_dev, int averaging,
                                       int64_t mf_min_rows) {
@@ -4785,17 +4722,9 @@ int mg_gen_diffusion_hierarchy_device(mg_handle c, int top_level, int N, const d
     MG_TRY(check_level(c, top_level, false));
     HIP_TRY(hipSetDevice(c->device));
     MG_TRY(need_device_pointer(c, kappa_dev, who.c_str(), "kappa"));
-    if (c->comm.active())
-        return fail(who + " needs a whole (not slab) handle: on slabs, call mg_gen_diffusion_level per level");
-    if (mf_min_rows >= 0) MG_TRY(mf_refusals(c, who.c_str()));
-    if (N <= 0) return fail("elements_per_dim must be positive");
-    if (N % (1 << top_level))
-        return fail(who + " needs an even elements_per_dim on every level above level 0 (" + std::to_string(N) +
-                    " is not N0 * 2^" + std::to_string(top_level) + ")");
-    if (averaging != MG_KAPPA_ARITHMETIC && averaging != MG_KAPPA_HARMONIC) return fail("unknown kappa averaging");
-    Level geo;
-    MG_TRY(setup_geometry(c, geo, top_level, N));
-    return gen_diffusion_hierarchy_device(c, top_level, N, kappa_dev, averaging, mf_min_rows >= 0 ? mf_min_rows : INT64_MAX);
+    MG_TRY(hierarchy_refusals(c, who, top_level, N, averaging, mf_min_rows >= 0));
+    DevTemp none;                               // the caller's buffer is borrowed: the walker holds nothing yet
+    return gen_diffusion_hierarchy(c, top_level, N, kappa_dev, none, averaging, mf_min_rows >= 0 ? mf_min_rows : INT64_MAX);
 }
 
 int mg_refresh_diffusion_hierarchy(mg_handle c, int top_level, const double* kappa_dev, int averaging) {
@@ -4823,6 +4752,8 @@ int mg_refresh_diffusion_hierarchy(mg_handle c, int top_level, const double* kap
     drop_graphs(c);
     free_direct(c);
     for (int l = top_level; l >= 0; --l) { c->L[l].cheb_est_ok = false; c->L[l].cheb_lmax_est = 0.0; }
+    // the walk of gen_diffusion_hierarchy with the split the levels have: a matrix-free level keeps its buffers, so the pass
+    // above it coarsens straight into its kappa and nothing is allocated or freed for it
     const double* src = kappa_dev;
     DevTemp held;                               // src where it is a temporary: the coarsened field above a stored level
     for (int l = top_level, Nl = N; l >= 0; --l, Nl /= 2) {
@@ -4834,7 +4765,7 @@ int mg_refresh_diffusion_hierarchy(mg_handle c, int top_level, const double* kap
         }
         DevTemp coarse;
         double* coarse_p = nullptr;
-        if (l > 0) {                            // straight into the kappa of a matrix-free level below, else into a temporary
+        if (l > 0) {
             const int Nc = Nl / 2;
             if (c->L[l - 1].mf) coarse_p = c->L[l - 1].kappa;
             else {
@@ -4844,8 +4775,7 @@ int mg_refresh_diffusion_hierarchy(mg_handle c, int top_level, const double* kap
             MG_TRY(launch_kappa_ingest(c, src, mf && src != L.kappa ? L.kappa : nullptr, coarse_p, Nc, averaging));
         }
         if (mf) {                               // kappa overwritten in place; the vectors are those of a fresh level
-            MG_TRY(launch_diffusion_rhs(c, L, L.kappa, L.f.rows, nullptr));
-            if (L.ftrue.raw) HIP_TRY(hipMemcpyAsync(L.ftrue.base, L.f.base, (size_t)L.xlen * 8, hipMemcpyDeviceToDevice, c->stream));
+            MG_TRY(fill_rhs_mf(c, L, L.kappa));
             HIP_TRY(hipMemsetAsync(L.v.raw, 0, (size_t)vec_total(L) * sizeof(double), c->stream));
             HIP_TRY(hipMemsetAsync(L.v2.raw, 0, (size_t)vec_total(L) * sizeof(double), c->stream));
         }
@@ -5242,26 +5172,19 @@ int mg_set_mass_csr(mg_handle c, int level, int64_t n_rows, int64_t nnz, const v
     Level& M = c->mass;
     // the work vector of mass_form is sized for the level the previous mass matrix belonged to
     if (c->mass_out.raw && c->mass_level >= 0) vec_free(c, c->L[c->mass_level], &c->mass_out);
-    free_level(c, M);
+    LevelBuild build(c, M);
     c->mass_level = -1;
     M = Level();
     MG_TRY(setup_geometry(c, M, level, L.N));
-    int rc = 0;
     if (L.perm) {                       // the level's DoF numbering
-        rc = dev_alloc(c, &M.perm, (size_t)L.n_global);
-        if (!rc && hipMemcpy(M.perm, L.perm, (size_t)L.n_global * sizeof(int), hipMemcpyDeviceToDevice) != hipSuccess)
-            rc = fail("copy of the level's permutation failed");
+        MG_TRY(dev_alloc(c, &M.perm, (size_t)L.n_global));
+        if (hipMemcpy(M.perm, L.perm, (size_t)L.n_global * sizeof(int), hipMemcpyDeviceToDevice) != hipSuccess)
+            return fail("copy of the level's permutation failed");
     }
     // (level index 1: any level but the coarsest may use symmetric diagonal storage)
-    if (!rc) rc = build_level_from_csr(c, 1, M, n_rows, nnz, indptr, indptr_is_64, indices, data, nullptr, 1, false);
-    if (rc) {
-        const std::string why = g_err;
-        free_level(c, M);
-        g_err = why;
-        return rc;
-    }
+    MG_TRY(build_level_from_csr(c, 1, M, n_rows, nnz, indptr, indptr_is_64, indices, data, nullptr, 1, false));
     c->mass_level = level;
-    return 0;
+    return build.done();
 }
 
 int mg_set_exact(mg_handle c, int level, const double* host) {

@@ -1,12 +1,13 @@
-// kappa handed over from device memory for gfx950: the copy a matrix-free level keeps and the coarsening for the level
-// below in one pass over the fine field (mg_gen_diffusion_hierarchy_device, mg_refresh_diffusion_hierarchy).
+// kappa coarsened on the device for gfx950, and in the same pass over the fine field the copy a matrix-free level keeps
+// of a kappa it does not own (mg_gen_diffusion_hierarchy[_mf | _device], mg_refresh_diffusion_hierarchy).
 //
-// kappa_ingest<DIM> reads the fine kappa once -- the caller's buffer on the top level, the result of the level above
-// below it -- and writes
-//   * the fine level's own copy (fine_out != nullptr: the level is matrix-free and does not own the source), and
-//   * the coarse kappa, with the bits of kappa_coarsen (mg_kernels.hip.h): the 2^DIM children in ascending lexicographic
-//     order, summed one by one into an accumulator that starts at 0.0, then x 2^-DIM (harmonic == 0) or
-//     2^DIM / sum of 1 / kappa (harmonic == 1).  poisson.coarsen_kappa restates it.
+// kappa_ingest<DIM> reads the fine kappa once -- the top level's upload or the caller's device buffer, the result of the
+// level above below it -- and writes
+//   * the coarse kappa (N_c = N_f / 2 cells per dimension): the 2^DIM children in ascending lexicographic order, i.e.
+//     3-D (z, y, x) = (2ck + c, 2cj + b, 2ci + a) and 2-D (y, x) = (2ck + b, 2ci + a) with a fastest, summed one by one
+//     into one accumulator that starts at 0.0, then x 2^-DIM (harmonic == 0) or 2^DIM / sum of 1 / kappa
+//     (harmonic == 1).  poisson.coarsen_kappa restates it, and the tests hold the kernel to it bit for bit;
+//   * the fine level's own copy (fine_out != nullptr: the level is matrix-free and does not own the source).
 // Built with -ffp-contract=off like everything else.
 //
 // One thread owns one coarse cell and loads its children as x-adjacent pairs: the pair (2 ci, 2 ci + 1) of a fine line
@@ -36,7 +37,7 @@ __global__ __launch_bounds__(KI_BLOCK) void kappa_ingest(const double* __restric
         for (int c = 0; c < (DIM == 3 ? 2 : 1); ++c)
 #pragma unroll
             for (int b = 0; b < 2; ++b) {
-                // 3-D: (z, y, x) = (2ck + c, 2cj + b, 2ci); 2-D: (y, x) = (2ck + b, 2ci): the pair a = 0, 1 of kappa_coarsen
+                // 3-D: (z, y, x) = (2ck + c, 2cj + b, 2ci); 2-D: (y, x) = (2ck + b, 2ci): the pair a = 0, 1
                 const int64_t f = DIM == 3 ? ((2 * ck + c) * Nf + 2 * cj + b) * Nf + 2 * ci : (2 * ck + b) * Nf + 2 * ci;
                 double2 x;
                 if (vec) {

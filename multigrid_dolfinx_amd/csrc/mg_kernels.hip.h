@@ -1422,30 +1422,6 @@ __global__ void kappa_check(const double* __restrict__ kappa, int64_t n, int64_t
     }
 }
 
-// kappa of the coarse cells (N_c = N_f / 2 per dimension): the 2^DIM children in ascending lexicographic order summed one
-// by one, then x 2^-DIM (harmonic == 0) or 2^DIM / sum of 1 / kappa (harmonic == 1); poisson.coarsen_kappa restates it.
-template <int DIM>
-__global__ void kappa_coarsen(const double* __restrict__ fine, double* __restrict__ coarse, int Nc, int harmonic) {
-    const int64_t nc = DIM == 3 ? (int64_t)Nc * Nc * Nc : (int64_t)Nc * Nc;
-    const int64_t Nf = 2 * (int64_t)Nc;
-    for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < nc; q += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t ci = q % Nc;
-        const int64_t cj = DIM == 3 ? (q / Nc) % Nc : 0;
-        const int64_t ck = DIM == 3 ? q / ((int64_t)Nc * Nc) : q / Nc;
-        double s = 0.0;
-        for (int c = 0; c < (DIM == 3 ? 2 : 1); ++c)
-            for (int b = 0; b < 2; ++b)
-                for (int a = 0; a < 2; ++a) {
-                    // 3-D: (z, y, x) = (2ck + c, 2cj + b, 2ci + a); 2-D: (y, x) = (2ck + b, 2ci + a)
-                    const int64_t f = DIM == 3 ? ((2 * ck + c) * Nf + 2 * cj + b) * Nf + 2 * ci + a
-                                               : (2 * ck + b) * Nf + 2 * ci + a;
-                    const double x = fine[f];
-                    s = s + (harmonic ? 1.0 / x : x);
-                }
-        coarse[q] = harmonic ? (DIM == 3 ? 8.0 : 4.0) / s : s * (DIM == 3 ? 0.125 : 0.25);
-    }
-}
-
 // ---- grid transfers (lexicographic index arithmetic; no coordinate hashing) ---------------------
 // Injection (Restriction2D_direct, multigrid.py:123-132): coarse (I,J,K) <- fine (2I,2J,2K).
 __global__ void restrict_inject(Grid gc, Grid gf, const double* __restrict__ rf, double* __restrict__ fc) {

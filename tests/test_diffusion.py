@@ -208,6 +208,78 @@ def test_device_hierarchy_entry_equals_per_level_calls(dim, c, nlev, averaging):
             assert r[0].tobytes() == r[1].tobytes(), l
 
 
+def _level_snapshots(h, nlev):
+    """What the hierarchy entries and the per-level calls must agree on, per level: level_info, the stored / matrix-free
+    split, level_storage of a stored level (a matrix-free level has no stored rows to report on), F and the residual of a
+    seeded random vector as bytes."""
+    out = []
+    for l in range(nlev):
+        mf = h.level_matrix_free(l)
+        h.set_vector(l, "v", np.random.default_rng(20 + l).standard_normal(h.n_dofs(l)))
+        f = h.get_vector(l, "f").tobytes()
+        h.residual(l)
+        out.append({"info": h.level_info(l), "matrix_free": mf, "kappa_bytes": h.level_kappa_bytes(l),
+                    "storage": None if mf else _storage(h, l), "f": f, "residual": h.get_vector(l, "r").tobytes()})
+    return out
+
+
+@pytest.fixture(scope="module")
+def per_level_reference():
+    """Per-level mg_gen_diffusion_level[_mf] calls fed by NumPy's poisson.coarsen_kappa, as `_level_snapshots`: computed once
+    per (dim, N, nlev, matrix_free, averaging) and shared by the three sources."""
+    made = {}
+
+    def reference(dim, N, nlev, matrix_free, averaging):
+        key = (dim, N, nlev, matrix_free, averaging)
+        if key not in made:
+            from multigrid_dolfinx_amd.hierarchy import DeviceHierarchy
+            ks = kappa_levels(lognormal_kappa(N, dim, seed=3), dim, nlev, averaging)
+            with DeviceHierarchy(dim, 0, nlev - 1, c=N >> (nlev - 1)) as p:
+                for l in range(nlev):
+                    p.gen_diffusion_level(l, ks[l], matrix_free=matrix_free and l > 0)
+                made[key] = _level_snapshots(p, nlev)
+        return made[key]
+    return reference
+
+
+# 3-D 4 / 2 levels: a coarse field of 2^3 cells, less than a wave; 36 / 3: 36 -> 18 -> 9, an odd coarse N and partial waves;
+# 2-D 24 / 3: the 2-D path.  3-D with all levels stored and with every level above level 0 matrix-free, 2-D stored.
+@pytest.mark.gpu
+@pytest.mark.parametrize("source", ["host", "device", "device_unaligned"])
+@pytest.mark.parametrize("averaging", ["arithmetic", "harmonic"])
+@pytest.mark.parametrize("dim,N,nlev,matrix_free", [(3, 4, 2, False), (3, 4, 2, True), (3, 36, 3, False), (3, 36, 3, True),
+                                                    (2, 24, 3, False)])
+def test_device_hierarchy_entry_equals_per_level_calls_from_every_source(per_level_reference, dim, N, nlev, matrix_free,
+                                                                        averaging, source):
+    """The device's coarsening (kappa_ingest) against NumPy's, whoever owns the top level's kappa: a host array (uploaded;
+    a matrix-free top level takes the upload over), a device address (borrowed; a matrix-free top level gets its copy from
+    the coarsening pass) and a device address 8 bytes into a buffer one double longer, which is not 16-byte aligned and
+    takes the kernel's path of 8-byte accesses.  Every level agrees with the per-level calls (`_level_snapshots`), and a
+    borrowed buffer comes back unchanged."""
+    from multigrid_dolfinx_amd.hierarchy import DeviceHierarchy, _DeviceArray
+    kappa = lognormal_kappa(N, dim, seed=3)
+    min_rows = 0 if matrix_free else None
+    with DeviceHierarchy(dim, 0, nlev - 1, c=N >> (nlev - 1)) as e:
+        if source == "host":
+            e.gen_diffusion_hierarchy(kappa, averaging, matrix_free_min_rows=min_rows)
+        else:
+            shift = 1 if source == "device_unaligned" else 0
+            padded = np.concatenate([np.full(shift, -1.0), kappa])
+            buf = _DeviceArray(e._lib, e.device, padded.size, padded)
+            try:
+                address = buf.ptr.value + 8 * shift
+                assert address % 16 == 8 * shift
+                e.gen_diffusion_hierarchy(address, averaging, matrix_free_min_rows=min_rows)
+                assert buf.download().tobytes() == padded.tobytes()
+            finally:
+                buf.free()
+        got, want = _level_snapshots(e, nlev), per_level_reference(dim, N, nlev, matrix_free, averaging)
+        assert [s["matrix_free"] for s in got] == [False] + [matrix_free] * (nlev - 1)
+        for l in range(nlev):
+            for key in want[l]:
+                assert got[l][key] == want[l][key], (l, key)
+
+
 @pytest.mark.gpu
 def test_device_chebyshev_estimates_on_the_3d_jump_hierarchy():
     from multigrid_dolfinx_amd.hierarchy import DeviceHierarchy

@@ -55,9 +55,11 @@ _SHAPES = [(3, 4, 2, None), (3, 4, 2, 0), (3, 36, 3, None), (3, 36, 3, 0), (3, 1
 def test_device_handoff_equals_host_handoff_to_the_bit(dim, N, nlev, min_rows, averaging):
     """A handle generated from a host kappa and one generated from the same kappa in device memory: level_info and
     level_matrix_free of every level, mg_memory_bytes, F of every level, the residual of one random V and the iterate after
-    one V(2,2) cycle with P1 transfers, all as bytes.  Every coarse level's F and matrix come from the coarsened kappa, so
-    this pins kappa_ingest against kappa_coarsen (and poisson.coarsen_kappa, which the existing tests pin that one to).  The
-    caller's buffer comes back unchanged and no whole-vector copy is counted across the call."""
+    one V(2,2) cycle with P1 transfers, all as bytes.  Both handles coarsen with kappa_ingest, so this pins the two ways
+    the walk over the levels owns its source (an upload it may give away, a borrowed buffer it copies) against each other;
+    the coarsening itself is pinned against poisson.coarsen_kappa by
+    tests/test_diffusion.py::test_device_hierarchy_entry_equals_per_level_calls_from_every_source.  The caller's buffer
+    comes back unchanged and no whole-vector copy is counted across the call."""
     top = nlev - 1
     kappa = lognormal_kappa(N, dim, seed=11)
     V = np.random.default_rng(N).standard_normal((N + 1) ** dim)

@@ -1,7 +1,7 @@
 """kappa from device memory (mg_gen_diffusion_hierarchy_device, mg_refresh_diffusion_hierarchy, kappa_ingest of
 mg_diffusion_kappa.hip.h) against the host hand-off, N_l = 8 * 2^l, levels 2 .. top, log-normal kappa (sigma 1):
-  hierarchy  wall seconds of gen_diffusion_hierarchy from a host array (the entry and code path that existed before the device
-             entries: upload, check, every level freed, reallocated and rebuilt), of the same call from a device address, and of
+  hierarchy  wall seconds of gen_diffusion_hierarchy from a host array (the entry that existed before the device entries:
+             upload, check, every level freed, reallocated and rebuilt), of the same call from a device address, and of
              refresh_diffusion_hierarchy, each on a handle that holds a hierarchy already (what a loop over kappa pays), two
              repetitions after a first call that is reported by itself; every call returns with the stream synchronised
   kernel     "kappa_ingest" through mg_time_kernel on the matrix-free top level, two repetitions of --reps launches: ms per
@@ -112,7 +112,7 @@ def main():
     with DeviceHierarchy(3, 0, 1) as h:
         machine = h.device_info()
     report = {"note": "tools/time_kappa_refresh.py: wall seconds per call, every call returning with the handle's stream synchronised; "
-                      "'host' is gen_diffusion_hierarchy from a host array, whose code path the device entries leave as it was; "
+                      "'host' is gen_diffusion_hierarchy from a host array (uploaded, then the walk over the levels the device entry runs); "
                       "levels with at least 2^22 rows matrix-free; log-normal kappa (sigma 1); two repetitions per figure",
               "machine": machine, "torch": torch.__version__, "commit": commit or "working tree (no git at run time)",
               "hierarchy": {}}
