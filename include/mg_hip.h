@@ -272,6 +272,21 @@ int mg_level_matrix_free(mg_handle h, int level, int* on, int64_t* kappa_bytes);
  * Refused with an error: 2-D handles, slab handles, flat levels, null pointers and pointers that are not device memory of the
  * handle's device. */
 int mg_diffusion_dkappa(mg_handle h, int level, const double* a_dev, const double* b_dev, double* out_dev);
+/* The tangent of the diffusion operator in a direction of kappa (no reference counterpart), the forward-mode half of what
+ * mg_diffusion_dkappa is the reverse-mode half of: out_dev = (dA/dkappa . dkappa) x, the derivative of the product A(kappa) x of
+ * mg_gen_diffusion_level's matrix along dkappa.  A is linear in kappa, so an interior row is the row the matrix-free march
+ * rebuilds with kappa := dkappa (mg_diffusion_mf.hip.h: the same edge sums, (s / 6.0) * h, zero entries towards boundary
+ * neighbours, the same fma order -- the bits of that SpMV where dkappa is a kappa), and a boundary row is +0.0: the identity
+ * block does not depend on kappa.  a . out(w, x) = w . mg_diffusion_dkappa(a, x) for a with zero boundary entries.  Neither
+ * the level's kappa nor a matrix is read: any whole 3-D grid level will do, stored, matrix-free or grid-only.
+ * dkappa_dev: N^3 doubles in the cell order of mg_gen_diffusion_level, of any sign, zeros included (finiteness is the caller's
+ * business, as for any vector); x_dev, out_dev: the level's n_global doubles in lexicographic node order.  All three are device
+ * memory; runs on the handle's stream, which is synchronised before return (the caller must have finished producing dkappa
+ * and x); nothing crosses to the host.  The tangent solve: du = A^-1 (df - out(dkappa, u)); poisson.diffusion_apply_dkappa
+ * restates it in NumPy (no fma there: to a bound, not to the bit).
+ * Refused with an error before anything is launched: 2-D handles, slab handles, flat levels, null pointers, pointers that
+ * are not device memory of the handle's device, and an out_dev that overlaps x_dev or dkappa_dev (the march reads neighbours). */
+int mg_diffusion_apply_dkappa(mg_handle h, int level, const double* dkappa_dev, const double* x_dev, double* out_dev);
 /* getJacobiMatrices (multigrid.py:48-56) as a stand-alone set-up kernel, for callers that
  * want the reference's split operands back: for every stored entry a_ij of the CSR matrix
  * writes scaled[q] = a_ij / a_ii computed as (1/a_ii) * a_ij, keep[q] = 1 unless the entry
@@ -661,6 +676,7 @@ int mg_reset_smoother_launches(mg_handle h);
  * "spmv" = one SpMV without the dot product, with the level's one-step kernel; "diffusion_mf", "diffusion_mf:jacobi",
  * ":residual", ":spmv", ":chebyshev" = the matrix-free diffusion march in that mode, an error on stored levels;
  * "dkappa" / "dkappa_gather" = mg_diffusion_dkappa of (MG_VEC_V, MG_VEC_F) into MG_VEC_R as the plane march / one thread per cell;
+ * "apply_dkappa" = mg_diffusion_apply_dkappa with dkappa = the first N^3 entries of MG_VEC_F and x = MG_VEC_V, into MG_VEC_R;
  * "kappa_ingest" = one launch of the fused copy and coarsening of mg_gen_diffusion_hierarchy_device on a matrix-free level, from a
  * scratch copy of its kappa back into the level's own (the same bytes: the level is unchanged) and into a scratch coarse field,
  * arithmetic averaging; an error on stored levels).

@@ -80,6 +80,7 @@ SIGNATURES = {
     "mg_set_vector_device": [_H, C.c_int, C.c_int, C.c_void_p],
     "mg_get_vector_device": [_H, C.c_int, C.c_int, C.c_void_p],
     "mg_diffusion_dkappa": [_H, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
+    "mg_diffusion_apply_dkappa": [_H, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
     "mg_zero_vector": [_H, C.c_int, C.c_int],
     "mg_copy_vector": [_H, C.c_int, C.c_int, C.c_int],
     "mg_smooth": [_H, C.c_int, C.c_int],

@@ -880,14 +880,20 @@ MfPlan mf_plan_dims(const mg_context* c, int nx, int ny, int nz) {
 }
 MfPlan mf_plan(const mg_context* c, const Level& L) { return mf_plan_dims(c, L.g.nx, L.g.ny, L.g.nz); }
 
-int launch_diffusion_mf(mg_context* c, const Level& L, int mode, bool dot, const double* x_rows, const double* f_rows,
-                        double* out_rows, double* partials, unsigned* grid_out, double alpha, double beta) {
-    const MfPlan p = mf_plan(c, L);
+MfArgs mf_args(const MfPlan& p, const Level& L, const double* kappa, const double* x_rows, double* out_rows) {
     MfArgs a{};
-    a.x = x_rows; a.f = f_rows; a.xp = out_rows; a.out = out_rows; a.kappa = L.kappa; a.partials = partials;
+    a.x = x_rows; a.xp = out_rows; a.out = out_rows; a.kappa = kappa;
     a.nx = L.g.nx; a.ny = L.g.ny; a.nz = L.g.nz; a.N = L.N; a.P = L.g.plane;
     a.ntx = p.ntx; a.nty = p.nty; a.nseg = p.nseg; a.seglen = p.seglen; a.nitems = p.nitems; a.ch = p.ch;
     a.h = 1.0 / (double)L.N;
+    return a;
+}
+
+int launch_diffusion_mf(mg_context* c, const Level& L, int mode, bool dot, const double* x_rows, const double* f_rows,
+                        double* out_rows, double* partials, unsigned* grid_out, double alpha, double beta) {
+    const MfPlan p = mf_plan(c, L);
+    MfArgs a = mf_args(p, L, L.kappa, x_rows, out_rows);
+    a.f = f_rows; a.partials = partials;
     a.omega = mode == MODE_CHEB ? alpha : c->omega;
     a.beta = beta;
     if (grid_out) *grid_out = p.grid;
@@ -898,6 +904,16 @@ int launch_diffusion_mf(mg_context* c, const Level& L, int mode, bool dot, const
     else if (mode == MODE_SPMV && dot) hipLaunchKernelGGL((diffusion_mf<MODE_SPMV, true>), grid, blk, 0, c->stream, a);
     else if (mode == MODE_SPMV) hipLaunchKernelGGL((diffusion_mf<MODE_SPMV, false>), grid, blk, 0, c->stream, a);
     else return fail("matrix-free diffusion levels have no kernel for this mode");
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// out = (dA/dkappa . dkappa) x on a whole 3-D grid level: the SpMV march with kappa := dkappa and +0.0 on boundary rows
+// (diffusion_mf<MODE_SPMV, false, true>).  Reads the grid only; dkappa, x, out: the caller's, lexicographic, out != x.
+int launch_apply_dkappa(mg_context* c, const Level& L, const double* dkappa, const double* x, double* out) {
+    const MfPlan p = mf_plan(c, L);
+    const MfArgs a = mf_args(p, L, dkappa, x, out);
+    hipLaunchKernelGGL((diffusion_mf<MODE_SPMV, false, true>), dim3(p.grid), dim3(MF_NT), 0, c->stream, a);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -4976,6 +4992,27 @@ int mg_diffusion_dkappa(mg_handle c, int level, const double* a_dev, const doubl
     return 0;
 }
 
+int mg_diffusion_apply_dkappa(mg_handle c, int level, const double* dkappa_dev, const double* x_dev, double* out_dev) {
+    const char* who = "mg_diffusion_apply_dkappa";
+    MG_TRY(need_dkappa_level(c, level, who));
+    HIP_TRY(hipSetDevice(c->device));
+    MG_TRY(need_device_pointer(c, dkappa_dev, who, "dkappa"));
+    MG_TRY(need_device_pointer(c, x_dev, who, "x"));
+    MG_TRY(need_device_pointer(c, out_dev, who, "out"));
+    const Level& L = c->L[level];
+    // the march reads the neighbours of a row (and of a cell) while other workgroups write theirs
+    const size_t nodes = (size_t)L.g.plane * (size_t)L.g.nz * 8, cells = (size_t)L.N * L.N * L.N * 8;
+    const auto overlaps = [](const void* p, size_t np, const void* q, size_t nq) {
+        const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
+        return a < b + nq && b < a + np;
+    };
+    if (overlaps(out_dev, nodes, x_dev, nodes)) return fail(std::string(who) + ": out overlaps x (the march reads a row's neighbours)");
+    if (overlaps(out_dev, nodes, dkappa_dev, cells)) return fail(std::string(who) + ": out overlaps dkappa (the march reads a row's cells)");
+    MG_TRY(launch_apply_dkappa(c, L, dkappa_dev, x_dev, out_dev));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
 int mg_zero_vector(mg_handle c, int level, int which) {
     MG_TRY(check_level(c, level));
     Level& L = c->L[level];
@@ -5406,6 +5443,11 @@ int mg_time_kernel(mg_handle c, const char* kernel, int level, int reps, double*
             MG_TRY(need_dkappa_level(c, level, "mg_time_kernel"));
             MG_TRY(vec_alloc(c, L, &L.v)); MG_TRY(vec_alloc(c, L, &L.f)); MG_TRY(vec_alloc(c, L, &L.v2));
             return launch_dkappa(c, L, L.v.rows, L.f.rows, L.v2.rows, k == "dkappa_gather");
+        }
+        if (k == "apply_dkappa") {  // (dA/dkappa . f[:N^3]) v: the SpMV march with kappa := the direction, into MG_VEC_R
+            MG_TRY(need_dkappa_level(c, level, "mg_time_kernel"));
+            MG_TRY(vec_alloc(c, L, &L.v)); MG_TRY(vec_alloc(c, L, &L.f)); MG_TRY(vec_alloc(c, L, &L.v2));
+            return launch_apply_dkappa(c, L, L.f.rows, L.v.rows, L.v2.rows);
         }
         if (k == "kappa_ingest") {  // the copy and the coarsening in one pass, from a scratch copy of kappa back into the level's own
             if (!L.mf) return fail("level is not a matrix-free diffusion level");

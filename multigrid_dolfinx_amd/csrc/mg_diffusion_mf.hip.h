@@ -26,6 +26,12 @@
 // q is faithful, r is exact, and t / 6 is never within 1/6 ulp of a rounding boundary without being on it, so the
 // correction lands on RN(t / 6) (Markstein; Brisebarre, Muller, Raina 2004).  Outside [2^-900, 2^900] (r could underflow,
 // q * 6 could overflow) it falls back to the division.  tests/test_diffusion_mf.py checks it against / 6.0 on the host.
+// Round-to-nearest is symmetric in the sign, so the range test is on |t| and a negative t takes the same three operations
+// (tests/test_diffusion_tangent.py: negated arguments, +-0 and subnormals); kappa > 0 never gets there, a direction does.
+//
+// TANGENT (MODE_SPMV only) is the derivative of that product in a direction of kappa, out = (dA/dkappa . dkappa) x
+// (mg_diffusion_apply_dkappa): A is linear in kappa, so an interior row is the same row with kappa := dkappa, of any sign,
+// and a boundary row -- the identity block does not depend on kappa -- is +0.0.  Everything else is the SpMV.
 #pragma once
 #include "mg_kernels.hip.h"
 
@@ -40,7 +46,7 @@ struct MfArgs {
     const double* f;        // row-based
     const double* xp;       // MODE_CHEB: x_{k-1}, the same buffer as out
     double* out;            // row-based, != x
-    const double* kappa;    // [N][N][N] cells, x fastest
+    const double* kappa;    // [N][N][N] cells, x fastest (TANGENT: the direction dkappa)
     double* partials;       // DOT: one partial sum of x . (A x) per block
     int nx, ny, nz, N;      // nodes per axis (N + 1 each), cells per axis
     int64_t P;              // nx * ny
@@ -50,15 +56,17 @@ struct MfArgs {
 };
 
 __device__ __forceinline__ double mf_div6(double t) {
-    if (!(t >= 0x1p-900 && t <= 0x1p900)) return t / 6.0;
+    const double m = fabs(t);
+    if (!(m >= 0x1p-900 && m <= 0x1p900)) return t / 6.0;
     const double c = 0x1.5555555555555p-3;      // RN(1 / 6)
     const double q = t * c;
     const double r = fma(-q, 6.0, t);
     return fma(r, c, q);
 }
 
-template <int MODE, bool DOT>
+template <int MODE, bool DOT, bool TANGENT = false>
 __global__ __launch_bounds__(MF_NT) void diffusion_mf(MfArgs a) {
+    static_assert(!TANGENT || (MODE == MODE_SPMV && !DOT), "the tangent is a plain SpMV with kappa := dkappa");
     __shared__ double sX[4][MF_XS];
     __shared__ double sK[3][MF_KS];
     __shared__ double s_part[MF_NT / WAVE];
@@ -198,10 +206,10 @@ __global__ __launch_bounds__(MF_NT) void diffusion_mf(MfArgs a) {
                 acc = fma(axu, xb[cx + 1], acc);
                 acc = fma(ayu, xb[cx + MF_XW], acc);
                 acc = fma(azu, xc[cx], acc);
-            } else {
+            } else if (!TANGENT) {
                 // identity row: the stored zeros times finite neighbours leave +0, then 1 * x
                 acc = fma(1.0, x0, acc);
-            }
+            }                                               // (TANGENT: that block does not depend on kappa, +0.0)
             if (on_grid) {
                 double o;
                 if (MODE == MODE_SPMV) {

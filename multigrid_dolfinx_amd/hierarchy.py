@@ -638,6 +638,38 @@ class DeviceHierarchy:
         out.reshape(-1)[:] = got
         return out
 
+    def diffusion_apply_dkappa(self, level: int, dkappa, x, out=None):
+        """(dA/dkappa . dkappa) x on a 3-D grid level, the derivative of A(kappa) x in the direction `dkappa`
+        (`mg_diffusion_apply_dkappa`; host restatement: `poisson.diffusion_apply_dkappa`).  `dkappa`
+        (`elements(level) ** 3` cells, any sign), `x` and `out` (lexicographic nodal values; boundary rows of `out` are 0)
+        are integer device addresses -- `out` is then required, must not overlap the inputs, and nothing is returned -- or,
+        for tests, NumPy arrays, which are uploaded, and the result comes back as a NumPy array (into `out` if given)."""
+        cells = self.elements(level) ** 3
+        integers = [isinstance(v, (int, np.integer)) for v in (dkappa, x)]
+        if all(integers):
+            if not isinstance(out, (int, np.integer)):
+                raise TypeError("with device addresses for dkappa and x, out must be a device address too")
+            check(self._lib.mg_diffusion_apply_dkappa(self._h, self._idx(level), C.c_void_p(int(dkappa)), C.c_void_p(int(x)),
+                                                      C.c_void_p(int(out))))
+            return None
+        if any(integers) or isinstance(out, (int, np.integer)):
+            raise TypeError("dkappa, x and out must be all device addresses or all NumPy arrays")
+        n = self.n_dofs(level)
+        held = []
+        try:
+            held.append(_DeviceArray(self._lib, self.device, cells, _capi.as_f64(dkappa, cells)))
+            held.append(_DeviceArray(self._lib, self.device, n, _capi.as_f64(x, n)))
+            held.append(_DeviceArray(self._lib, self.device, n))
+            check(self._lib.mg_diffusion_apply_dkappa(self._h, self._idx(level), held[0].ptr, held[1].ptr, held[2].ptr))
+            got = held[2].download()
+        finally:
+            for d in held:
+                d.free()
+        if out is None:
+            return got
+        out.reshape(-1)[:] = got
+        return out
+
     def zero_vector(self, level: int, which: str = "v"):
         check(self._lib.mg_zero_vector(self._h, self._idx(level), _VEC[which]))
 

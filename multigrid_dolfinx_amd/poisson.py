@@ -558,6 +558,20 @@ def _kappa_cells(kappa, N: int, dim: int) -> np.ndarray:
     return k.reshape((N,) * dim)
 
 
+def _edge_sums_3d(kp, n1):
+    """Per node of the n1^3 grid, from the cell field padded by one cell: se[axis][side], the sum over the four cells of the
+    edge towards the lower / upper neighbour on that axis in ascending index (n = 2, 1, 1, 2), and the sum of the six in
+    ascending offset order -- `gen_diffusion`'s adds, one by one."""
+    K = [[[kp[dz:dz + n1, dy:dy + n1, dx:dx + n1].reshape(-1) for dx in (0, 1)] for dy in (0, 1)] for dz in (0, 1)]
+    se = [[None, None] for _ in range(3)]
+    for s in (0, 1):
+        se[0][s] = ((2.0 * K[0][0][s] + K[0][1][s]) + K[1][0][s]) + 2.0 * K[1][1][s]
+        se[1][s] = ((2.0 * K[0][s][0] + K[0][s][1]) + K[1][s][0]) + 2.0 * K[1][s][1]
+        se[2][s] = ((2.0 * K[s][0][0] + K[s][0][1]) + K[s][1][0]) + 2.0 * K[s][1][1]
+    t = ((((se[2][0] + se[1][0]) + se[0][0]) + se[0][1]) + se[1][1]) + se[2][1]
+    return se, t
+
+
 def diffusion_level(N: int, dim: int, kappa, keep_zeros: bool = True) -> Level:
     """The level `mg_gen_diffusion_level` generates, assembled on the host in the kernel's operation order (same bits), in
     the hand-off conventions of `lexicographic_level`.  `kappa` holds one positive value per cell: cube (ci, cj, ck) at
@@ -574,14 +588,7 @@ def diffusion_level(N: int, dim: int, kappa, keep_zeros: bool = True) -> Level:
     n1 = N + 1
     h = 1.0 / N
     if dim == 3:
-        K = [[[kp[dz:dz + n1, dy:dy + n1, dx:dx + n1].reshape(-1) for dx in (0, 1)] for dy in (0, 1)] for dz in (0, 1)]
-        # se[axis][side]; the four cells of an edge in ascending index, n = 2, 1, 1, 2
-        se = [[None, None] for _ in range(3)]
-        for s in (0, 1):
-            se[0][s] = ((2.0 * K[0][0][s] + K[0][1][s]) + K[1][0][s]) + 2.0 * K[1][1][s]
-            se[1][s] = ((2.0 * K[0][s][0] + K[0][s][1]) + K[1][s][0]) + 2.0 * K[1][s][1]
-            se[2][s] = ((2.0 * K[s][0][0] + K[s][0][1]) + K[s][1][0]) + 2.0 * K[s][1][1]
-        t = ((((se[2][0] + se[1][0]) + se[0][0]) + se[0][1]) + se[1][1]) + se[2][1]
+        se, t = _edge_sums_3d(kp, n1)
         diag = (t / 6.0) * h
         weight = lambda s: (s / 6.0) * h
     else:
@@ -714,3 +721,39 @@ def diffusion_dkappa(N: int, a, b) -> np.ndarray:
                     t = 2.0 * t
                 s = t if s is None else s + t
     return np.ascontiguousarray((s * ((1.0 / N) / 6.0)).reshape(-1))
+
+
+def diffusion_apply_dkappa(N: int, dkappa, x) -> np.ndarray:
+    """(dA/dkappa . dkappa) x for the 3-D `diffusion_level`: the derivative of A(kappa) x in the direction `dkappa` (N^3 values in
+    the cell order of `diffusion_level`, of any sign), as `mg_diffusion_apply_dkappa` computes it.  A is linear in kappa, so an
+    interior row is the row of `diffusion_level` with kappa := dkappa -- the edge sums and the diagonal sum in its order,
+    weights (s / 6.0) * h, entries towards boundary neighbours zero -- applied as the device sums it: acc = 0, then
+    a * x + acc over z-, y-, x-, the diagonal, x+, y+, z+.  Boundary rows are 0: the identity block does not depend on kappa.
+    The same operations in the same order, but NumPy has no fma: every product here is rounded before its add, on the
+    device it is not, so this restates the kernel to a rounding bound (a few ulps of the sum of the absolute values of a
+    row's terms), not to the bit.  `x`: nodal values in lexicographic order, boundary entries included (an interior row has
+    no boundary column, so they do not count)."""
+    n1 = N + 1
+    dk = _kappa_cells(dkappa, N, 3)
+    v = np.array(x, dtype=np.float64).reshape(-1)
+    if v.size != n1 ** 3:
+        raise ValueError(f"vector has {v.size} entries, the level has {n1 ** 3} nodes")
+    h = 1.0 / N
+    se, t = _edge_sums_3d(np.pad(dk, 1, constant_values=1.0), n1)
+    idx = np.arange(n1 ** 3, dtype=np.int64)
+    ijk = [idx % n1, (idx // n1) % n1, idx // (n1 * n1)]
+    inner = np.ones(n1 ** 3, dtype=bool)
+    for c in ijk:
+        inner &= (c >= 1) & (c <= N - 1)
+    strides = (1, n1, n1 * n1)
+    xp = np.concatenate([np.zeros(strides[2]), v, np.zeros(strides[2])])       # a neighbour outside the grid reads 0
+    nb = lambda delta: xp[strides[2] + delta:strides[2] + delta + v.size]
+    acc = np.zeros(n1 ** 3)
+    for axis in (2, 1, 0):                      # z-, y-, x-
+        a = np.where(ijk[axis] - 1 == 0, 0.0, -((se[axis][0] / 6.0) * h))
+        acc = a * nb(-strides[axis]) + acc
+    acc = ((t / 6.0) * h) * v + acc
+    for axis in (0, 1, 2):                      # x+, y+, z+
+        a = np.where(ijk[axis] + 1 == N, 0.0, -((se[axis][1] / 6.0) * h))
+        acc = a * nb(strides[axis]) + acc
+    return np.where(inner, acc, 0.0)

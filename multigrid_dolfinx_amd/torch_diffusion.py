@@ -58,6 +58,17 @@ class DiffusionSolver:
     backward: one more `mg_pcg` on the same hierarchy (A is symmetric), A lambda = grad_u; then grad_f = lambda and
     grad_kappa = -mg_diffusion_dkappa(lambda, u).  A solve that reaches `max_iter` raises `NotConverged`.
 
+    Higher derivatives: the backward pass is itself written with S(kappa, f) = A^-1 f, D(a, b) = mg_diffusion_dkappa and
+    T(w, x) = mg_diffusion_apply_dkappa = (dA/dkappa . w) x, whose derivatives close on each other (S: lambda = S(kappa, g),
+    f_bar = lambda, kappa_bar = -D(lambda, u); D with cotangent w: a_bar = T(w, b), b_bar = T(w, a); T with cotangent y:
+    w_bar = D(y, x), x_bar = T(w, y)), so `torch.autograd.grad(..., create_graph=True)` through `solve` can be differentiated
+    again: a Hessian-vector product of J(u(kappa)) is four solves on one generation (`n_solves` counts them).  Solves started
+    from a backward pass count as "adjoint" in `last_iterations`, `last_residual` and `NotConverged`; while a backward pass
+    records gradients they start from zero and leave the kept warm-start solutions alone.  Without `create_graph` the
+    backward pass is the one solve and one sensitivity kernel described above.  `tangent` is the forward-mode derivative.
+    Known limit: on deep hierarchies (six levels at 257^3) a third `mg_pcg` in a row on one generation
+    does not converge with captured V-cycles and raises `NotConverged`; `solver.hierarchy.set_tuning("graph", 0)` avoids it.
+
     `warm_start=True` keeps the last forward and the last adjoint solution and starts the next solve of each kind from
     them instead of from zero (kappa that moves a little between solves).  The stopping test is relative to the
     right-hand side either way, so the gradients are those of the converged solve."""
@@ -82,7 +93,9 @@ class DiffusionSolver:
         self.last_generate = None       # "host" / "device" / "refresh": how the last kappa reached the hierarchy
         self.warm_start = bool(warm_start)
         self._warm = {}                 # "forward" / "adjoint": the last solution of that kind (warm_start)
-        self.last_iterations = {}       # "forward" / "adjoint": iterations of the last solve of that kind
+        self._last_operator = None      # the _Operator of the last `solve`: what `tangent` solves again on
+        self.n_solves = 0               # mg_pcg calls so far: what a product costs (a Hessian-vector product: four)
+        self.last_iterations = {}       # "forward" / "adjoint" / "tangent": iterations of the last solve of that kind
         self.last_residual = {}         # ... and ||r|| / ||rhs|| of mg_pcg's recursion where it stopped (None: no iteration was needed)
 
     def close(self):
@@ -95,7 +108,19 @@ class DiffusionSolver:
         self.close()
 
     def solve(self, kappa: torch.Tensor, f: torch.Tensor) -> torch.Tensor:
-        return _Solve.apply(kappa, f, self)
+        return _Solve.apply(kappa, f, self, None, "forward", True)
+
+    def tangent(self, kappa: torch.Tensor, f: torch.Tensor, dkappa: torch.Tensor, df: Optional[torch.Tensor] = None):
+        """(u, du): u = A(kappa)^-1 f and its derivative in the direction (dkappa, df),
+        du = A^-1 (df - (dA/dkappa . dkappa) u), on the same operator: two solves, one generation.  The cheap derivative
+        when kappa depends on a few parameters.  `kappa` as in `solve`; `f`, `dkappa` (N^3 float64, any sign) and `df`
+        (None: zero) on the solver's device.  The second solve counts as "tangent" in `last_iterations`."""
+        u = self.solve(kappa, f)
+        rhs = _Tangent.apply(dkappa.reshape(-1), u.reshape(-1), self).neg()
+        if df is not None:
+            rhs = self._same_size(df, "df").reshape(-1) + rhs
+        du = _Solve.apply(kappa, rhs, self, self._last_operator, "tangent", True)
+        return u, du.view(u.shape)
 
     # ---- what the autograd function calls --------------------------------------------------------------------
     def _generate(self, kappa) -> int:
@@ -116,22 +141,27 @@ class DiffusionSolver:
         self._generation += 1
         return self._generation
 
-    def _device_vector(self, x: torch.Tensor, what: str) -> torch.Tensor:
+    def _same_size(self, x: torch.Tensor, what: str) -> torch.Tensor:
         n = self.hierarchy.n_dofs(self.top)
         if x.dtype != torch.float64 or x.device != self.device or x.numel() != n:
             raise ValueError(f"{what} must hold {n} float64 on {self.device} (got {x.numel()} {x.dtype} on {x.device})")
-        return x.detach().contiguous()
+        return x
 
-    def _pcg(self, rhs: torch.Tensor, which: str) -> torch.Tensor:
-        """A x = rhs from zero, or from the last solution of this kind (warm_start); rhs and x by pointer."""
+    def _device_vector(self, x: torch.Tensor, what: str) -> torch.Tensor:
+        return self._same_size(x, what).detach().contiguous()
+
+    def _pcg(self, rhs: torch.Tensor, which: str, warm: bool = True) -> torch.Tensor:
+        """A x = rhs from zero, or from the last solution of this kind (warm_start and `warm`); rhs and x by pointer."""
         h = self.hierarchy
+        warm = warm and self.warm_start
         torch.cuda.current_stream(self.device).synchronize()        # rhs is complete before the handle's stream reads it
         h.set_vector_device(self.top, "f", rhs.data_ptr())
-        x0 = self._warm.get(which) if self.warm_start else None
+        x0 = self._warm.get(which) if warm else None
         if x0 is not None:
             h.set_vector_device(self.top, "v", x0.data_ptr())
         else:
             h.zero_vector(self.top, "v")
+        self.n_solves += 1
         hist = h.pcg(rtol=self.rtol, max_iter=self.max_iter, level=self.top)
         self.last_iterations[which] = len(hist)
         self.last_residual[which] = float(hist[-1]) / h.norm2(self.top, "f") if len(hist) else None
@@ -140,41 +170,104 @@ class DiffusionSolver:
                                f"(rtol {self.rtol:g}): no gradient is returned")
         x = torch.empty_like(rhs)
         h.get_vector_device(self.top, "v", x.data_ptr())
-        if self.warm_start:
+        if warm:
             self._warm[which] = x.clone()
         return x
 
 
+class _Operator:
+    """The kappa of one `solve` as the library takes it (a host array or a device copy) and the generation of the
+    hierarchy that holds it: what the solves nested in that solve's backward passes share, so that they neither upload
+    nor regenerate an operator that is still in place."""
+
+    def __init__(self, kappa_kept, generation):
+        self.kappa_kept, self.generation = kappa_kept, generation
+
+
 class _Solve(torch.autograd.Function):
+    """S(kappa, f) = A(kappa)^-1 f.  `op` None: the caller's solve, which puts kappa into the hierarchy.  `op` given: a solve
+    on the operator of an earlier one (from a backward pass, or `tangent`); `kappa` is then only what the gradient is
+    taken with respect to (None: nobody asked), and the hierarchy is touched only if another kappa has been solved since."""
+
     @staticmethod
-    def forward(ctx, kappa, f, solver):
-        if kappa.dtype != torch.float64 or kappa.numel() != solver.N ** 3:
-            raise ValueError(f"kappa must hold {solver.N ** 3} float64")
-        if kappa.device == solver.device:       # no .cpu(): a device copy that the caller's later updates do not reach feeds the library
-            kappa_kept = kappa.detach().reshape(-1).clone()
-        else:
-            kappa_kept = np.ascontiguousarray(kappa.detach().cpu().numpy().reshape(-1))
-        rhs = solver._device_vector(f, "f")
-        ctx.generation = solver._generate(kappa_kept)
-        u = solver._pcg(rhs, "forward")
-        ctx.solver, ctx.kappa_kept = solver, kappa_kept
-        ctx.kappa_like = (kappa.shape, kappa.device)
+    def forward(ctx, kappa, f, solver, op, which, warm):
+        rhs = solver._device_vector(f, "f" if op is None else "the right-hand side")
+        if op is None:
+            if kappa.dtype != torch.float64 or kappa.numel() != solver.N ** 3:
+                raise ValueError(f"kappa must hold {solver.N ** 3} float64")
+            if kappa.device == solver.device:   # no .cpu(): a device copy that the caller's later updates do not reach feeds the library
+                kappa_kept = kappa.detach().reshape(-1).clone()
+            else:
+                kappa_kept = np.ascontiguousarray(kappa.detach().cpu().numpy().reshape(-1))
+            op = _Operator(kappa_kept, solver._generate(kappa_kept))
+            solver._last_operator = op
+        elif op.generation != solver._generation:       # another kappa has been solved since: this one's operator again
+            op.generation = solver._generate(op.kappa_kept)
+        u = solver._pcg(rhs, which, warm).view(f.shape)
+        ctx.solver, ctx.op = solver, op
+        ctx.kappa_like = None if kappa is None else (kappa.shape, kappa.device)
+        # kappa is kept as what the gradient is taken with respect to, never for its values (those are op.kappa_kept): not
+        # through save_for_backward, whose version check would refuse a caller who has overwritten the tensor since
+        ctx.kappa = kappa if ctx.needs_input_grad[0] else None
         ctx.save_for_backward(u)
-        return u.view(f.shape)
+        return u
 
     @staticmethod
     def backward(ctx, grad_u):
+        # lambda = S(kappa, grad_u), grad_f = lambda, grad_kappa = -D(lambda, u): A is symmetric.  Written with the functions
+        # themselves, so that under create_graph autograd can differentiate it again; without, it runs under no_grad and is
+        # one mg_pcg and one sensitivity kernel.
         solver = ctx.solver
-        (u,) = ctx.saved_tensors
-        if ctx.generation != solver._generation:        # another kappa has been solved since: this one's operator again
-            ctx.generation = solver._generate(ctx.kappa_kept)
-        lam = solver._pcg(solver._device_vector(grad_u, "grad_u"), "adjoint")
+        kappa, (u,) = ctx.kappa, ctx.saved_tensors
+        lam = _Solve.apply(kappa, grad_u, solver, ctx.op, "adjoint", not torch.is_grad_enabled())
         grad_kappa = None
         if ctx.needs_input_grad[0]:
             shape, device = ctx.kappa_like
-            out = torch.empty(solver.N ** 3, dtype=torch.float64, device=solver.device)
-            torch.cuda.current_stream(solver.device).synchronize()
-            solver.hierarchy.diffusion_dkappa(solver.top, lam.data_ptr(), u.data_ptr(), out.data_ptr())
-            grad_kappa = out.neg_().view(shape).to(device)
-        grad_f = lam.view(grad_u.shape) if ctx.needs_input_grad[1] else None
-        return grad_kappa, grad_f, None
+            grad_kappa = _DKappa.apply(lam, u, solver).neg().view(shape).to(device)
+        grad_f = lam if ctx.needs_input_grad[1] else None
+        return grad_kappa, grad_f, None, None, None, None
+
+
+class _DKappa(torch.autograd.Function):
+    """D(a, b) = mg_diffusion_dkappa(a, b), N^3 cells.  With cotangent w: a_bar = T(w, b), b_bar = T(w, a)."""
+
+    @staticmethod
+    def forward(ctx, a, b, solver):
+        av, bv = solver._device_vector(a, "a"), solver._device_vector(b, "b")
+        out = torch.empty(solver.N ** 3, dtype=torch.float64, device=solver.device)
+        torch.cuda.current_stream(solver.device).synchronize()
+        solver.hierarchy.diffusion_dkappa(solver.top, av.data_ptr(), bv.data_ptr(), out.data_ptr())
+        ctx.solver = solver
+        ctx.save_for_backward(a, b)
+        return out
+
+    @staticmethod
+    def backward(ctx, w):
+        a, b = ctx.saved_tensors
+        grad_a = _Tangent.apply(w, b, ctx.solver).view(a.shape) if ctx.needs_input_grad[0] else None
+        grad_b = _Tangent.apply(w, a, ctx.solver).view(b.shape) if ctx.needs_input_grad[1] else None
+        return grad_a, grad_b, None
+
+
+class _Tangent(torch.autograd.Function):
+    """T(w, x) = (dA/dkappa . w) x = mg_diffusion_apply_dkappa(w, x), (N + 1)^3 nodes.  With cotangent y: w_bar = D(y, x),
+    x_bar = T(w, y)."""
+
+    @staticmethod
+    def forward(ctx, w, x, solver):
+        if w.dtype != torch.float64 or w.device != solver.device or w.numel() != solver.N ** 3:
+            raise ValueError(f"the kappa direction must hold {solver.N ** 3} float64 on {solver.device}")
+        wv, xv = w.detach().contiguous(), solver._device_vector(x, "x")
+        out = torch.empty(xv.numel(), dtype=torch.float64, device=solver.device)
+        torch.cuda.current_stream(solver.device).synchronize()
+        solver.hierarchy.diffusion_apply_dkappa(solver.top, wv.data_ptr(), xv.data_ptr(), out.data_ptr())
+        ctx.solver = solver
+        ctx.save_for_backward(w, x)
+        return out
+
+    @staticmethod
+    def backward(ctx, y):
+        w, x = ctx.saved_tensors
+        grad_w = _DKappa.apply(y, x, ctx.solver).view(w.shape) if ctx.needs_input_grad[0] else None
+        grad_x = _Tangent.apply(w, y, ctx.solver).view(x.shape) if ctx.needs_input_grad[1] else None
+        return grad_w, grad_x, None
