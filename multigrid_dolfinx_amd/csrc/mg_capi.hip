@@ -23,6 +23,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 using namespace mgk;
@@ -642,146 +643,132 @@ struct LevelBuild {
 };
 
 // ---- tile kernel dispatch --------------------------------------------------------------------
-template <int WT, int R>
-void launch_ell_wr(int mode, bool dot, const EllArgs& a, unsigned grid, hipStream_t s) {
-    if (mode == MODE_RESIDUAL)
-        hipLaunchKernelGGL((ell_apply<WT, R, MODE_RESIDUAL, false>), dim3(grid), dim3(BLOCK), 0, s, a);
-    else if (mode == MODE_JACOBI)
-        hipLaunchKernelGGL((ell_apply<WT, R, MODE_JACOBI, false>), dim3(grid), dim3(BLOCK), 0, s, a);
-    else if (mode == MODE_CHEB)
-        hipLaunchKernelGGL((ell_apply<WT, R, MODE_CHEB, false>), dim3(grid), dim3(BLOCK), 0, s, a);
-    else if (mode == MODE_GS)
-        hipLaunchKernelGGL((ell_apply<WT, R, MODE_GS, false>), dim3(grid), dim3(BLOCK), 0, s, a);
-    else if (dot)
-        hipLaunchKernelGGL((ell_apply<WT, R, MODE_SPMV, true>), dim3(grid), dim3(BLOCK), 0, s, a);
-    else
-        hipLaunchKernelGGL((ell_apply<WT, R, MODE_SPMV, false>), dim3(grid), dim3(BLOCK), 0, s, a);
+// A run-time value as a template argument: f(std::integral_constant<int, V>{}) for the V among Vs that equals v.
+// false: v is none of them and f was not called (the caller keeps its own fallback: an error, or with_int_else).
+template <int... Vs, class F>
+bool with_int(int v, F&& f) {
+    return ((v == Vs ? (f(std::integral_constant<int, Vs>{}), true) : false) || ...);
 }
 
-template <int WT, int R, bool NT>
-void launch_ell_coded_wrn(int mode, bool dot, const EllArgs& a, unsigned grid, hipStream_t s) {
-    if (mode == MODE_RESIDUAL)
-        hipLaunchKernelGGL((ell_apply_coded<WT, R, MODE_RESIDUAL, false, NT>), dim3(grid), dim3(BLOCK), 0, s, a);
-    else if (mode == MODE_JACOBI)
-        hipLaunchKernelGGL((ell_apply_coded<WT, R, MODE_JACOBI, false, NT>), dim3(grid), dim3(BLOCK), 0, s, a);
-    else if (mode == MODE_CHEB)
-        hipLaunchKernelGGL((ell_apply_coded<WT, R, MODE_CHEB, false, NT>), dim3(grid), dim3(BLOCK), 0, s, a);
-    else if (mode == MODE_GS)
-        hipLaunchKernelGGL((ell_apply_coded<WT, R, MODE_GS, false, NT>), dim3(grid), dim3(BLOCK), 0, s, a);
-    else if (dot)
-        hipLaunchKernelGGL((ell_apply_coded<WT, R, MODE_SPMV, true, NT>), dim3(grid), dim3(BLOCK), 0, s, a);
-    else
-        hipLaunchKernelGGL((ell_apply_coded<WT, R, MODE_SPMV, false, NT>), dim3(grid), dim3(BLOCK), 0, s, a);
+// ... every other v takes the instance of Else (rows per lane in the set-up kernels: 1, 2, else 4)
+template <int Else, int... Vs, class F>
+void with_int_else(int v, F&& f) {
+    if (!with_int<Vs...>(v, f)) f(std::integral_constant<int, Else>{});
 }
 
-template <int WT, int R>
-void launch_ell_coded_wr(int mode, bool dot, bool nt, const EllArgs& a, unsigned grid, hipStream_t s) {
-    if (nt) launch_ell_coded_wrn<WT, R, true>(mode, dot, a, grid, s);
-    else launch_ell_coded_wrn<WT, R, false>(mode, dot, a, grid, s);
+template <class F>
+void with_bool(bool b, F&& f) {
+    if (b) f(std::true_type{});
+    else f(std::false_type{});
 }
 
-template <int WU, int R, bool NT>
-void launch_sdia_wrn(int mode, bool dot, bool finest, const EllArgs& a, unsigned grid, hipStream_t s, int lds_pad) {
-    const unsigned lds = a.nslices >= 100000 ? (unsigned)lds_pad : 0u;
-    if (mode == MODE_JACOBI && finest)
-        hipLaunchKernelGGL((sdia_jacobi_finest<WU, R, NT>), dim3(grid), dim3(BLOCK), lds, s, a);
-    else if (mode == MODE_RESIDUAL)
-        hipLaunchKernelGGL((sdia_apply<WU, R, MODE_RESIDUAL, false, NT>), dim3(grid), dim3(BLOCK), lds, s, a);
-    else if (mode == MODE_JACOBI)
-        hipLaunchKernelGGL((sdia_apply<WU, R, MODE_JACOBI, false, NT>), dim3(grid), dim3(BLOCK), lds, s, a);
-    else if (mode == MODE_CHEB)
-        hipLaunchKernelGGL((sdia_apply<WU, R, MODE_CHEB, false, NT>), dim3(grid), dim3(BLOCK), lds, s, a);
-    else if (mode == MODE_GS)
-        hipLaunchKernelGGL((sdia_apply<WU, R, MODE_GS, false, NT>), dim3(grid), dim3(BLOCK), lds, s, a);
-    else if (dot)
-        hipLaunchKernelGGL((sdia_apply<WU, R, MODE_SPMV, true, NT>), dim3(grid), dim3(BLOCK), lds, s, a);
-    else
-        hipLaunchKernelGGL((sdia_apply<WU, R, MODE_SPMV, false, NT>), dim3(grid), dim3(BLOCK), lds, s, a);
+// f(mode, dot) of a tile kernel: the four modes that have no dot product, and SpMV (any other mode) with or without one
+template <class F>
+void with_mode(int mode, bool dot, F&& f) {
+    if (mode == MODE_RESIDUAL) f(std::integral_constant<int, MODE_RESIDUAL>{}, std::false_type{});
+    else if (mode == MODE_JACOBI) f(std::integral_constant<int, MODE_JACOBI>{}, std::false_type{});
+    else if (mode == MODE_CHEB) f(std::integral_constant<int, MODE_CHEB>{}, std::false_type{});
+    else if (mode == MODE_GS) f(std::integral_constant<int, MODE_GS>{}, std::false_type{});
+    else if (dot) f(std::integral_constant<int, MODE_SPMV>{}, std::true_type{});
+    else f(std::integral_constant<int, MODE_SPMV>{}, std::false_type{});
 }
 
-template <int WU, int R, bool NT>
-void launch_sdia_cls_wrn(int mode, bool dot, bool finest, const EllArgs& a, unsigned grid, hipStream_t s) {
-    if (mode == MODE_JACOBI && finest)
-        hipLaunchKernelGGL((sdia_cls_jacobi_finest<WU, R, NT>), dim3(grid), dim3(BLOCK), 0, s, a);
-    else if (mode == MODE_RESIDUAL)
-        hipLaunchKernelGGL((sdia_cls_apply<WU, R, MODE_RESIDUAL, false, NT>), dim3(grid), dim3(BLOCK), 0, s, a);
-    else if (mode == MODE_JACOBI)
-        hipLaunchKernelGGL((sdia_cls_apply<WU, R, MODE_JACOBI, false, NT>), dim3(grid), dim3(BLOCK), 0, s, a);
-    else if (mode == MODE_CHEB)
-        hipLaunchKernelGGL((sdia_cls_apply<WU, R, MODE_CHEB, false, NT>), dim3(grid), dim3(BLOCK), 0, s, a);
-    else if (mode == MODE_GS)
-        hipLaunchKernelGGL((sdia_cls_apply<WU, R, MODE_GS, false, NT>), dim3(grid), dim3(BLOCK), 0, s, a);
-    else if (dot)
-        hipLaunchKernelGGL((sdia_cls_apply<WU, R, MODE_SPMV, true, NT>), dim3(grid), dim3(BLOCK), 0, s, a);
-    else
-        hipLaunchKernelGGL((sdia_cls_apply<WU, R, MODE_SPMV, false, NT>), dim3(grid), dim3(BLOCK), 0, s, a);
+// f(mode) of a plane march (lat_march, sdia_sweep1c): residual, Gauss-Seidel and Chebyshev; any other mode is a Jacobi sweep
+template <class F>
+void with_march_mode(int mode, F&& f) {
+    with_mode(mode, false, [&](auto m, auto) {
+        f(std::integral_constant<int, decltype(m)::value == MODE_SPMV ? MODE_JACOBI : decltype(m)::value>{});
+    });
 }
 
-template <int R>
-void launch_sdia_cls_r(int WU, int mode, bool dot, bool nt, bool finest, const EllArgs& a, unsigned grid, hipStream_t s) {
-    if (WU == 3) {
-        if (nt) launch_sdia_cls_wrn<3, R, true>(mode, dot, finest, a, grid, s);
-        else launch_sdia_cls_wrn<3, R, false>(mode, dot, finest, a, grid, s);
-    } else {
-        if (nt) launch_sdia_cls_wrn<4, R, true>(mode, dot, finest, a, grid, s);
-        else launch_sdia_cls_wrn<4, R, false>(mode, dot, finest, a, grid, s);
-    }
-}
-
-template <int R>
-void launch_sdia_r(int WU, int mode, bool dot, bool nt, bool finest, const EllArgs& a, unsigned grid, hipStream_t s, int pad) {
-    switch (WU) {
-        case 3: nt ? launch_sdia_wrn<3, R, true>(mode, dot, finest, a, grid, s, pad) : launch_sdia_wrn<3, R, false>(mode, dot, finest, a, grid, s, pad); break;
-        case 4: nt ? launch_sdia_wrn<4, R, true>(mode, dot, finest, a, grid, s, pad) : launch_sdia_wrn<4, R, false>(mode, dot, finest, a, grid, s, pad); break;
-        default: nt ? launch_sdia_wrn<8, R, true>(mode, dot, finest, a, grid, s, pad) : launch_sdia_wrn<8, R, false>(mode, dot, finest, a, grid, s, pad); break;
-    }
-}
-
-template <int R, bool NT>
-void launch_ell_cls_rn(int mode, bool dot, const EllArgs& a, unsigned grid, hipStream_t s, const Level& L) {
-    if (mode == MODE_RESIDUAL)
-        hipLaunchKernelGGL((ell_cls_apply<R, MODE_RESIDUAL, false, NT>), dim3(grid), dim3(BLOCK), 0, s, a, L.scls, L.s_off, L.s_val, L.s_cnt);
-    else if (mode == MODE_JACOBI)
-        hipLaunchKernelGGL((ell_cls_apply<R, MODE_JACOBI, false, NT>), dim3(grid), dim3(BLOCK), 0, s, a, L.scls, L.s_off, L.s_val, L.s_cnt);
-    else if (mode == MODE_CHEB)
-        hipLaunchKernelGGL((ell_cls_apply<R, MODE_CHEB, false, NT>), dim3(grid), dim3(BLOCK), 0, s, a, L.scls, L.s_off, L.s_val, L.s_cnt);
-    else if (mode == MODE_GS)
-        hipLaunchKernelGGL((ell_cls_apply<R, MODE_GS, false, NT>), dim3(grid), dim3(BLOCK), 0, s, a, L.scls, L.s_off, L.s_val, L.s_cnt);
-    else if (dot)
-        hipLaunchKernelGGL((ell_cls_apply<R, MODE_SPMV, true, NT>), dim3(grid), dim3(BLOCK), 0, s, a, L.scls, L.s_off, L.s_val, L.s_cnt);
-    else
-        hipLaunchKernelGGL((ell_cls_apply<R, MODE_SPMV, false, NT>), dim3(grid), dim3(BLOCK), 0, s, a, L.scls, L.s_off, L.s_val, L.s_cnt);
-}
-
-template <int R>
-void launch_ell_cls_r(int mode, bool dot, bool nt, const EllArgs& a, unsigned grid, hipStream_t s, const Level& L) {
-    if (nt) launch_ell_cls_rn<R, true>(mode, dot, a, grid, s, L);
-    else launch_ell_cls_rn<R, false>(mode, dot, a, grid, s, L);
+// prolongation kernels: (add, keep) = (true, true), (true, false), (false, true) -- a prolongation that does not add keeps
+template <class F>
+void with_add_keep(bool add, bool keep, F&& f) {
+    if (add && keep) f(std::true_type{}, std::true_type{});
+    else if (add) f(std::true_type{}, std::false_type{});
+    else f(std::false_type{}, std::true_type{});
 }
 
 // offset codes are used for every width up to 64 entries per row (5, 7 and 15 have unrolled kernels)
 inline bool coded_width(int W) { return W >= 1 && W <= 64; }
 
-template <int R>
-void launch_ell_coded_r(int W, int mode, bool dot, bool nt, const EllArgs& a, unsigned grid, hipStream_t s) {
-    switch (W) {
-        case 5: launch_ell_coded_wr<5, R>(mode, dot, nt, a, grid, s); break;
-        case 7: launch_ell_coded_wr<7, R>(mode, dot, nt, a, grid, s); break;
-        case 15: launch_ell_coded_wr<15, R>(mode, dot, nt, a, grid, s); break;
-        default: launch_ell_coded_wr<0, R>(mode, dot, nt, a, grid, s); break;
+// The slices of one launch_ell: `count` slices from slice0 on (count < 0: up to the level's last).  gap > 0: they are
+// [slice0, slice0 + split) and [slice0 + split + gap, ...) -- two ranges, one launch.
+struct SliceRange {
+    int64_t slice0 = 0, count = -1, split = 0, gap = 0;
+    static SliceRange of(int64_t slice0, int64_t count) { return {slice0, count, 0, 0}; }
+    // the first lo_count slices and those from hi_begin on, in one launch
+    static SliceRange ends(const Level& L, int64_t lo_count, int64_t hi_begin) {
+        return {0, lo_count + L.nslices - hi_begin, lo_count, hi_begin - lo_count};
     }
+    // ... of a slab: the ends next to a neighbour (lo: below, hi: above); both in one launch where the slab has both
+    static SliceRange ends_of_slab(const Level& L, bool lo, bool hi, int64_t lo_count, int64_t hi_begin) {
+        if (lo && hi) return ends(L, lo_count, hi_begin);
+        if (lo) return of(0, lo_count);
+        return hi ? of(hi_begin, L.nslices - hi_begin) : of(0, 0);
+    }
+};
+
+// What launch_ell is asked for: out = op(A, x) in `mode` over `slices` of the level (default: all of them).
+struct EllRequest {
+    int mode = MODE_JACOBI;
+    bool dot = false;                   // MODE_SPMV: the partial sums of x . out go to `partials` as well
+    const double* x_base = nullptr;     // x with its lower halo (DVector::base)
+    const double* f_rows = nullptr;
+    double* out_rows = nullptr;
+    double* partials = nullptr;
+    const int* done = nullptr;
+    unsigned* grid_out = nullptr;       // the number of blocks launched (= partial sums written), if asked for
+    SliceRange slices{};
+    int color = 0;                      // MODE_GS: the colour that is relaxed
+    double alpha = 0.0, beta = 0.0;     // MODE_CHEB: the step scalars; x_{k-1} is read from out_rows
+};
+
+// the usual operands on a level: x = v, f, out = v2
+EllRequest level_op(const Level& L, int mode) {
+    EllRequest q;
+    q.mode = mode; q.x_base = L.v.base; q.f_rows = mode == MODE_SPMV ? nullptr : L.f.rows; q.out_rows = L.v2.rows;
+    return q;
 }
 
-template <int R>
-void launch_ell_r(int W, int mode, bool dot, const EllArgs& a, unsigned grid, hipStream_t s) {
-    switch (W) {
-        case 5: launch_ell_wr<5, R>(mode, dot, a, grid, s); break;
-        case 7: launch_ell_wr<7, R>(mode, dot, a, grid, s); break;
-        case 15: launch_ell_wr<15, R>(mode, dot, a, grid, s); break;
-        default: launch_ell_wr<0, R>(mode, dot, a, grid, s); break;
-    }
+// the finest of several levels (its Jacobi kernels skip what only coarser levels need) / a slab that exchanges halos
+inline bool is_finest(const mg_context* c, const Level& L) { return c->nlev > 1 && &L == &c->L[c->nlev - 1]; }
+inline bool is_slab(const mg_context* c, const Level& L) { return !L.replicated && c->comm.active(); }
+
+// The class fields of a kernel-argument struct from the level's row classes.  Two conventions: the tile and K-sweep
+// kernels of mg_kernels / mg_jacobi2 (JKArgs, JSArgs, JBArgs, EllArgs) take the class of row 0 ...
+template <class Args>
+void fill_classes(Args& a, const Level& L) {
+    a.cls = L.cls + L.cls_lead; a.ctab = L.ctab; a.ncls = L.ncls; a.cmain = L.cmain;
+    for (int t = 0; t < 8; ++t) a.cm[t] = L.cm[t];
+}
+// ... the plane marches (J2Args, JK3Args) the start of the padded array and its lead
+template <class Args>
+void fill_classes_lead(Args& a, const Level& L) {
+    a.cls = L.cls; a.clead = L.cls_lead; a.ctab = L.ctab; a.ncls = L.ncls; a.cmain = L.cmain;
+    for (int t = 0; t < 8; ++t) a.cm[t] = L.cm[t];
 }
 
+// Plane segments per tile of a plane march: `ntile` tiles cut into n segments run in rounds of `resident` workgroups, a
+// segment costs its planes plus `warmup` plane-times; the n in 1..most with the cheapest rounds x (planes + warm-up), the
+// smallest such n.
+int best_segments(int64_t ntile, int64_t resident, int planes, int most, double warmup) {
+    int best = 1;
+    double best_cost = 1e300;
+    for (int n = 1; n <= std::max(1, most); ++n) {
+        const double cost = (double)((ntile * n + resident - 1) / resident) * ((planes + n - 1) / n + warmup);
+        if (cost < best_cost) { best_cost = cost; best = n; }
+    }
+    return best;
+}
+
+// `items` work items of a launch whose blocks walk them in chunks of xcd_chunk per XCD: the grid, whole groups of 8 chunks
+int tile_grid(int64_t items, unsigned xcd_chunk, unsigned* grid) {
+    if (items >= ((int64_t)1 << 31) - 4096) return fail("too many tiles");
+    const int64_t group = 8 * (int64_t)xcd_chunk;
+    *grid = (unsigned)(((items + group - 1) / group) * group);
+    return 0;
+}
 int launch_sweep1c(mg_context* c, const Level& L, int mode, const double* x_rows, const double* f_rows, double* out_rows,
                    int color, double alpha = 0.0, double beta = 0.0);
 bool sweep1c_ok(const mg_context* c, const Level& L);
@@ -809,25 +796,17 @@ int launch_lat_march_t(mg_context* c, const Level& L, LatArgs a, int mode) {
     const int64_t resident = per_cu * cus;
     int nseg = c->lattice_segments;
     if (nseg <= 0 && 2 * ntile >= resident) nseg = (int)std::max<int64_t>(1, (13 * resident / 2 + ntile - 1) / ntile);
-    if (nseg <= 0) {
-        double best = 1e300;
-        for (int n = 1; n <= std::max(1, L.g.nk / 16); ++n) {
-            const double cost = (double)((ntile * n + resident - 1) / resident) * ((L.g.nk + n - 1) / n + 5.0);
-            if (cost < best) { best = cost; nseg = n; }
-        }
-    }
+    if (nseg <= 0) nseg = best_segments(ntile, resident, L.g.nk, L.g.nk / 16, 5.0);
     nseg = std::max(1, std::min(nseg, std::max(1, L.g.nk / 16)));
     a.seglen = (L.g.nk + nseg - 1) / nseg;
     nseg = (L.g.nk + a.seglen - 1) / a.seglen;
     const int64_t items = ntile * nseg;
-    if (items >= ((int64_t)1 << 31) - 4096) return fail("too many tiles");
-    a.nitems = (unsigned)items;
     a.xcd_chunk = 16;
-    const int64_t group = 8 * (int64_t)a.xcd_chunk;
-    const unsigned grid = (unsigned)(((items + group - 1) / group) * group);
-    void (*kern)(LatArgs) = mode == MODE_RESIDUAL ? lat_march<MODE_RESIDUAL, TI, TJ, NT>
-                          : mode == MODE_GS ? lat_march<MODE_GS, TI, TJ, NT>
-                          : mode == MODE_CHEB ? lat_march<MODE_CHEB, TI, TJ, NT> : lat_march<MODE_JACOBI, TI, TJ, NT>;
+    unsigned grid = 0;
+    MG_TRY(tile_grid(items, a.xcd_chunk, &grid));
+    a.nitems = (unsigned)items;
+    void (*kern)(LatArgs) = nullptr;
+    with_march_mode(mode, [&](auto m) { kern = lat_march<decltype(m)::value, TI, TJ, NT>; });
     if (lds > (size_t)150 * 1024) return fail("lattice march: class tables too wide");
     MG_TRY(allow_large_lds(c, reinterpret_cast<const void*>(kern), (size_t)150 * 1024));
     hipLaunchKernelGGL(kern, dim3(grid), dim3(NT), lds, c->stream, a);
@@ -898,12 +877,13 @@ int launch_diffusion_mf(mg_context* c, const Level& L, int mode, bool dot, const
     a.beta = beta;
     if (grid_out) *grid_out = p.grid;
     const dim3 grid(p.grid), blk(MF_NT);
-    if (mode == MODE_JACOBI) hipLaunchKernelGGL((diffusion_mf<MODE_JACOBI, false>), grid, blk, 0, c->stream, a);
-    else if (mode == MODE_RESIDUAL) hipLaunchKernelGGL((diffusion_mf<MODE_RESIDUAL, false>), grid, blk, 0, c->stream, a);
-    else if (mode == MODE_CHEB) hipLaunchKernelGGL((diffusion_mf<MODE_CHEB, false>), grid, blk, 0, c->stream, a);
-    else if (mode == MODE_SPMV && dot) hipLaunchKernelGGL((diffusion_mf<MODE_SPMV, true>), grid, blk, 0, c->stream, a);
-    else if (mode == MODE_SPMV) hipLaunchKernelGGL((diffusion_mf<MODE_SPMV, false>), grid, blk, 0, c->stream, a);
-    else return fail("matrix-free diffusion levels have no kernel for this mode");
+    bool known = true;
+    with_mode(mode, dot, [&](auto m, auto d) {
+        constexpr int MODE = decltype(m)::value;
+        if constexpr (MODE == MODE_GS) known = false;
+        else hipLaunchKernelGGL((diffusion_mf<MODE, decltype(d)::value>), grid, blk, 0, c->stream, a);
+    });
+    if (!known) return fail("matrix-free diffusion levels have no kernel for this mode");
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -975,31 +955,30 @@ int need_device_pointer(mg_context* c, const void* p, const char* who, const cha
     return 0;
 }
 
-// out = op(A, x) over all owned slices of the level
-int launch_ell(mg_context* c, const Level& L, int mode, bool dot, const double* x_base, const double* f_rows,
-               double* out_rows, double* partials, const int* done, unsigned* grid_out = nullptr,
-               int64_t slice0 = 0, int64_t slice_count = -1, int color = 0, int64_t split = 0, int64_t gap = 0,
-               double alpha = 0.0, double beta = 0.0) {
-    // (gap > 0: the slice_count slices are [slice0, slice0 + split) and [slice0 + split + gap, ...) -- two ranges, one launch)
-    // (MODE_CHEB: one Chebyshev step with the step scalars alpha, beta; x_{k-1} is read from out_rows)
-    if (slice_count < 0) slice_count = L.nslices - slice0;
+// out = op(A, x) over the requested slices of the level (EllRequest)
+int launch_ell(mg_context* c, const Level& L, const EllRequest& q) {
+    const int mode = q.mode;
+    const bool dot = q.dot;
+    const int64_t slice0 = q.slices.slice0, gap = q.slices.gap;
+    const int64_t slice_count = q.slices.count < 0 ? L.nslices - slice0 : q.slices.count;
     if (slice_count == 0) return 0;
+    const bool whole = slice0 == 0 && slice_count == L.nslices;
     if (L.mf) {
         // matrix-free diffusion level: the rows rebuilt from kappa (mg_diffusion_mf.hip.h); whole levels only
-        if (done || slice0 != 0 || slice_count != L.nslices || gap != 0 || mode == MODE_GS)
+        if (q.done || !whole || gap != 0 || mode == MODE_GS)
             return fail("matrix-free diffusion levels run whole-level Jacobi, residual, SpMV and Chebyshev launches only");
-        return launch_diffusion_mf(c, L, mode, dot, x_base + L.g.lead, f_rows, out_rows, partials, grid_out, alpha, beta);
+        return launch_diffusion_mf(c, L, mode, dot, q.x_base + L.g.lead, q.f_rows, q.out_rows, q.partials, q.grid_out, q.alpha, q.beta);
     }
     // whole large 3-D levels with row classes: one sweep as a plane march (mg_jacobi2.hip.h, sdia_sweep1c)
-    if (!dot && !done && mode != MODE_SPMV && slice0 == 0 && slice_count == L.nslices && sweep1c_ok(c, L))
-        return launch_sweep1c(c, L, mode, x_base + L.g.lead, f_rows, out_rows, color, alpha, beta);
+    if (!dot && !q.done && mode != MODE_SPMV && whole && sweep1c_ok(c, L))
+        return launch_sweep1c(c, L, mode, q.x_base + L.g.lead, q.f_rows, q.out_rows, q.color, q.alpha, q.beta);
     EllArgs a{};
-    a.vals = L.vals; a.cols = L.cols; a.x = x_base; a.f = f_rows; a.dinv = L.dinv; a.out = out_rows;
-    a.partials = partials; a.done_flag = done; a.nloc = L.nloc; a.lead = L.g.lead;
-    a.slice0 = slice0; a.nslices = slice_count; a.split = split; a.gap = gap; a.omega = c->omega; a.W = L.W; a.chunk = c->chunk;
-    if (mode == MODE_CHEB) { a.omega = alpha; a.xp = out_rows; a.beta = beta; }
+    a.vals = L.vals; a.cols = L.cols; a.x = q.x_base; a.f = q.f_rows; a.dinv = L.dinv; a.out = q.out_rows;
+    a.partials = q.partials; a.done_flag = q.done; a.nloc = L.nloc; a.lead = L.g.lead;
+    a.slice0 = slice0; a.nslices = slice_count; a.split = q.slices.split; a.gap = gap; a.omega = c->omega; a.W = L.W; a.chunk = c->chunk;
+    if (mode == MODE_CHEB) { a.omega = q.alpha; a.xp = q.out_rows; a.beta = q.beta; }
     a.codes = L.codes; a.offsets = L.offsets; a.ntable = L.ntable; a.dcode = L.dcode;
-    a.color = color; a.color_kind = c->smoother == MG_SMOOTH_MCGS ? COLOR_LATTICE9 : COLOR_PARITY;
+    a.color = q.color; a.color_kind = c->smoother == MG_SMOOTH_MCGS ? COLOR_LATTICE9 : COLOR_PARITY;
     a.grow0 = L.row0; a.gnx = L.g.nx; a.gny = L.g.ny;
     unsigned grid = blocks_for(slice_count, WAVES_PER_BLOCK);
     // XCD strip traversal (optional): pays when a plane is much larger than a strip
@@ -1020,82 +999,80 @@ int launch_ell(mg_context* c, const Level& L, int mode, bool dot, const double* 
             grid = (unsigned)g;
         }
     };
+    // Every tile kernel has the rows per lane, the mode and the dot product as template arguments, most of them the
+    // streaming loads as well: launch(R, MODE, DOT, NT) is called with the level's and the request's.
+    auto tiles = [&](auto&& launch) -> int {
+        if (q.grid_out) *q.grid_out = grid;
+        const bool known = with_int<1, 2, 4>(L.R, [&](auto r) {
+            with_mode(mode, dot, [&](auto m, auto d) { with_bool(c->nontemporal != 0, [&](auto nt) { launch(r, m, d, nt); }); });
+        });
+        if (!known) return fail("unsupported rows_per_lane");
+        HIP_TRY(hipGetLastError());
+        return 0;
+    };
+    const dim3 blk(BLOCK);
     if (L.sdia) {
         a.vals = L.dvals; a.mlead = L.mlead;
         for (int t = 0; t < 8; ++t) a.up[t] = L.up[t];
         plan_strips();
-        if (grid_out) *grid_out = grid;
-        const bool nt = c->nontemporal != 0;
-        const bool finest = c->nlev > 1 && &L == &c->L[c->nlev - 1];
+        const bool finest = is_finest(c, L);
         if (cls_full(L) && c->class_sweeps) {
             // the rows through their classes: 25 instead of 56 bytes per row (mg_kernels.hip.h, sdia_cls_body);
             // persistent blocks (8 per CU, a multiple of 8 so that a block's groups stay on one XCD's share)
-            a.cls = L.cls + L.cls_lead; a.ctab = L.ctab; a.ncls = L.ncls; a.cmain = L.cmain;
-            for (int t = 0; t < 8; ++t) a.cm[t] = L.cm[t];
+            fill_classes(a, L);
             a.nvirt = grid;
             // (with the dot product one group per block, as the other formats have it: the partial sums and with them
             //  the rounding of the result do not depend on the format)
             const unsigned resident = (unsigned)c->cls_blocks_per_cu * (unsigned)std::max(1, c->prop.multiProcessorCount);
             if (!dot) grid = std::min(grid, resident);
-            if (grid_out) *grid_out = grid;
-            switch (L.R) {
-                case 1: launch_sdia_cls_r<1>(L.wu, mode, dot, nt, finest, a, grid, c->stream); break;
-                case 2: launch_sdia_cls_r<2>(L.wu, mode, dot, nt, finest, a, grid, c->stream); break;
-                case 4: launch_sdia_cls_r<4>(L.wu, mode, dot, nt, finest, a, grid, c->stream); break;
-                default: return fail("unsupported rows_per_lane");
-            }
-            HIP_TRY(hipGetLastError());
-            return 0;
+            return tiles([&](auto r, auto m, auto d, auto nt) {
+                constexpr int R = decltype(r)::value, MODE = decltype(m)::value;
+                constexpr bool DOT = decltype(d)::value, NT = decltype(nt)::value;
+                with_int_else<4, 3>(L.wu, [&](auto wu) {
+                    constexpr int WU = decltype(wu)::value;
+                    if (MODE == MODE_JACOBI && finest) hipLaunchKernelGGL((sdia_cls_jacobi_finest<WU, R, NT>), dim3(grid), blk, 0, c->stream, a);
+                    else hipLaunchKernelGGL((sdia_cls_apply<WU, R, MODE, DOT, NT>), dim3(grid), blk, 0, c->stream, a);
+                });
+            });
         }
-        switch (L.R) {
-            case 1: launch_sdia_r<1>(L.wu, mode, dot, nt, finest, a, grid, c->stream, c->lds_pad); break;
-            case 2: launch_sdia_r<2>(L.wu, mode, dot, nt, finest, a, grid, c->stream, c->lds_pad); break;
-            case 4: launch_sdia_r<4>(L.wu, mode, dot, nt, finest, a, grid, c->stream, c->lds_pad); break;
-            default: return fail("unsupported rows_per_lane");
-        }
-        HIP_TRY(hipGetLastError());
-        return 0;
+        const unsigned lds = a.nslices >= 100000 ? (unsigned)c->lds_pad : 0u;      // ("lds_pad", see mg_context)
+        return tiles([&](auto r, auto m, auto d, auto nt) {
+            constexpr int R = decltype(r)::value, MODE = decltype(m)::value;
+            constexpr bool DOT = decltype(d)::value, NT = decltype(nt)::value;
+            with_int_else<8, 3, 4>(L.wu, [&](auto wu) {
+                constexpr int WU = decltype(wu)::value;
+                if (MODE == MODE_JACOBI && finest) hipLaunchKernelGGL((sdia_jacobi_finest<WU, R, NT>), dim3(grid), blk, lds, c->stream, a);
+                else hipLaunchKernelGGL((sdia_apply<WU, R, MODE, DOT, NT>), dim3(grid), blk, lds, c->stream, a);
+            });
+        });
     }
     if (L.coded && L.scls && c->class_sweeps) {
         // whole 3-D lattice levels: plane march with x in LDS (mg_lattice.hip.h)
-        if (!dot && !done && mode != MODE_SPMV && slice0 == 0 && slice_count == L.nslices && gap == 0 && lat_march_ok(c, L))
-            return launch_lat_march(c, L, mode, x_base + L.g.lead, f_rows, out_rows, color, alpha, beta);
+        if (!dot && !q.done && mode != MODE_SPMV && whole && gap == 0 && lat_march_ok(c, L))
+            return launch_lat_march(c, L, mode, q.x_base + L.g.lead, q.f_rows, q.out_rows, q.color, q.alpha, q.beta);
         // wide rows through their stencil classes: 25 bytes per row instead of the stored row (ell_cls_apply)
-        if (grid_out) *grid_out = grid;
-        const bool nt = c->nontemporal != 0;
-        switch (L.R) {
-            case 1: launch_ell_cls_r<1>(mode, dot, nt, a, grid, c->stream, L); break;
-            case 2: launch_ell_cls_r<2>(mode, dot, nt, a, grid, c->stream, L); break;
-            case 4: launch_ell_cls_r<4>(mode, dot, nt, a, grid, c->stream, L); break;
-            default: return fail("unsupported rows_per_lane");
-        }
-        HIP_TRY(hipGetLastError());
-        return 0;
+        return tiles([&](auto r, auto m, auto d, auto nt) {
+            hipLaunchKernelGGL((ell_cls_apply<decltype(r)::value, decltype(m)::value, decltype(d)::value, decltype(nt)::value>), dim3(grid), blk, 0,
+                               c->stream, a, L.scls, L.s_off, L.s_val, L.s_cnt);
+        });
     }
+    // (W not in {5, 7, 15}: the kernels that loop over the width)
     if (L.coded) {
         plan_strips();
-        if (grid_out) *grid_out = grid;
-        const bool nt = c->nontemporal != 0;
-        switch (L.R) {
-            case 1: launch_ell_coded_r<1>(L.W, mode, dot, nt, a, grid, c->stream); break;
-            case 2: launch_ell_coded_r<2>(L.W, mode, dot, nt, a, grid, c->stream); break;
-            case 4: launch_ell_coded_r<4>(L.W, mode, dot, nt, a, grid, c->stream); break;
-            default: return fail("unsupported rows_per_lane");
-        }
-        HIP_TRY(hipGetLastError());
-        return 0;
+        return tiles([&](auto r, auto m, auto d, auto nt) {
+            with_int_else<0, 5, 7, 15>(L.W, [&](auto w) {
+                hipLaunchKernelGGL((ell_apply_coded<decltype(w)::value, decltype(r)::value, decltype(m)::value, decltype(d)::value, decltype(nt)::value>),
+                                   dim3(grid), blk, 0, c->stream, a);
+            });
+        });
     }
-    if (grid_out) *grid_out = grid;
-    switch (L.R) {
-        case 1: launch_ell_r<1>(L.W, mode, dot, a, grid, c->stream); break;
-        case 2: launch_ell_r<2>(L.W, mode, dot, a, grid, c->stream); break;
-        case 4: launch_ell_r<4>(L.W, mode, dot, a, grid, c->stream); break;
-        default: return fail("unsupported rows_per_lane");
-    }
-    HIP_TRY(hipGetLastError());
-    return 0;
+    return tiles([&](auto r, auto m, auto d, auto) {
+        with_int_else<0, 5, 7, 15>(L.W, [&](auto w) {
+            hipLaunchKernelGGL((ell_apply<decltype(w)::value, decltype(r)::value, decltype(m)::value, decltype(d)::value>), dim3(grid), blk, 0,
+                               c->stream, a);
+        });
+    });
 }
-
 // ---- communication -----------------------------------------------------------------------------
 int ensure_host_stage(mg_context* c, size_t elems) {
     Comm& cm = c->comm;
@@ -1248,22 +1225,15 @@ int launch_lat_gs2(mg_context* c, const Level& L, int c1, int c2, const double* 
     // (as launch_lat_march_t; a segment pays 5 + 4 planes of warm-up and 3 of trailing second colour)
     int nseg = c->lattice_segments;
     if (nseg <= 0 && 2 * ntile >= resident) nseg = (int)std::max<int64_t>(1, (13 * resident / 2 + ntile - 1) / ntile);
-    if (nseg <= 0) {
-        double best = 1e300;
-        for (int n = 1; n <= std::max(1, L.g.nk / 16); ++n) {
-            const double cost = (double)((ntile * n + resident - 1) / resident) * ((L.g.nk + n - 1) / n + 12.0);
-            if (cost < best) { best = cost; nseg = n; }
-        }
-    }
+    if (nseg <= 0) nseg = best_segments(ntile, resident, L.g.nk, L.g.nk / 16, 12.0);
     nseg = std::max(1, std::min(nseg, std::max(1, L.g.nk / 16)));
     a.seglen = (L.g.nk + nseg - 1) / nseg;
     nseg = (L.g.nk + a.seglen - 1) / a.seglen;
     const int64_t items = ntile * nseg;
-    if (items >= ((int64_t)1 << 31) - 4096) return fail("too many tiles");
-    a.nitems = (unsigned)items;
     a.xcd_chunk = 16;
-    const int64_t group = 8 * (int64_t)a.xcd_chunk;
-    const unsigned grid = (unsigned)(((items + group - 1) / group) * group);
+    unsigned grid = 0;
+    MG_TRY(tile_grid(items, a.xcd_chunk, &grid));
+    a.nitems = (unsigned)items;
     const size_t lds = g2_lds_bytes(L.W);
     if (lds > (size_t)80 * 1024) return fail("lattice march: class tables too wide");
     MG_TRY(allow_large_lds(c, reinterpret_cast<const void*>(lat_gs2), (size_t)80 * 1024));
@@ -1314,15 +1284,7 @@ J2Plan jacobi2_plan(const mg_context* c, const Level& L, bool slab, int64_t boun
     const int64_t ntile = (int64_t)p.ntx * p.nty;
     const int nk = L.g.nk;
     const int64_t cus = std::max(1, c->prop.multiProcessorCount);      // one resident workgroup per CU
-    auto pieces = [&](int planes, int most) {
-        int best = 1;
-        double best_cost = 1e300;
-        for (int n = 1; n <= std::max(1, most); ++n) {
-            const double cost = (double)((ntile * n + cus - 1) / cus) * ((planes + n - 1) / n + 2.5);
-            if (cost < best_cost) { best_cost = cost; best = n; }
-        }
-        return best;
-    };
+    auto pieces = [&](int planes, int most) { return best_segments(ntile, cus, planes, most, 2.5); };
     if (slab) {
         // one plane more than the rows the neighbours wait for (3 planes + 1 on a 1025^2 plane)
         const int zb = (int)std::max<int64_t>(4, (boundary_rows + L.g.plane - 1) / L.g.plane + 1);
@@ -1352,12 +1314,11 @@ J2Plan jacobi2_plan(const mg_context* c, const Level& L, bool slab, int64_t boun
 template <int NW, int LPW>
 int launch_jacobi2c_t(mg_context* c, const J2Args& a, int nseg, bool finest) {
     const int64_t items = (int64_t)a.ntx * a.nty * nseg;
-    if (items >= ((int64_t)1 << 31) - 4096) return fail("too many tiles");
     J2Args b = a;
-    b.nitems = (unsigned)items;
     b.xcd_chunk = (unsigned)c->fuse_xcd_chunk;
-    const int64_t group = 8 * (int64_t)b.xcd_chunk;
-    const unsigned grid = (unsigned)(((items + group - 1) / group) * group);
+    unsigned grid = 0;
+    MG_TRY(tile_grid(items, b.xcd_chunk, &grid));
+    b.nitems = (unsigned)items;
     constexpr size_t lds = j2c_lds_bytes<NW, LPW>();
     void (*const kern[2])(J2Args) = {sdia_jacobi2c<NW, LPW>, sdia_jacobi2c_finest<NW, LPW>};
     MG_TRY(allow_large_lds(c, reinterpret_cast<const void*>(kern[finest ? 1 : 0]), lds));
@@ -1369,12 +1330,11 @@ int launch_jacobi2c_t(mg_context* c, const J2Args& a, int nseg, bool finest) {
 template <int R, int NW, int LPW>
 int launch_jacobi2p_t(mg_context* c, const J2Args& a, int nseg, bool finest) {
     const int64_t items = (int64_t)a.ntx * a.nty * nseg;
-    if (items >= ((int64_t)1 << 31) - 4096) return fail("too many tiles");
     J2Args b = a;
-    b.nitems = (unsigned)items;
     b.xcd_chunk = (unsigned)c->fuse_xcd_chunk;
-    const int64_t group = 8 * (int64_t)b.xcd_chunk;
-    const unsigned grid = (unsigned)(((items + group - 1) / group) * group);
+    unsigned grid = 0;
+    MG_TRY(tile_grid(items, b.xcd_chunk, &grid));
+    b.nitems = (unsigned)items;
     constexpr size_t lds = j2p_lds_bytes<NW, LPW>();
     void (*const kern[2])(J2Args) = {sdia_jacobi2p<R, NW, LPW>, sdia_jacobi2p_finest<R, NW, LPW>};
     MG_TRY(allow_large_lds(c, reinterpret_cast<const void*>(kern[finest ? 1 : 0]), lds));
@@ -1420,11 +1380,10 @@ int launch_jacobi2(mg_context* c, const Level& L, const J2Plan& plan, int seg0, 
     a.seg0 = seg0; a.seg_stride = stride;
     const int n = count;
     // 8 waves x 2 grid lines each (16 waves x 1 line measured slower and does not fit 128 registers)
-    const bool finest = c->nlev > 1 && &L == &c->L[c->nlev - 1];
+    const bool finest = is_finest(c, L);
     if (cls_full(L) && c->fuse_classes) {
-        a.cls = L.cls; a.ctab = L.ctab; a.clead = L.cls_lead;
-        a.ncls = L.ncls; a.cmain = L.cmain; a.wi = plan.wi;
-        for (int t = 0; t < 8; ++t) a.cm[t] = L.cm[t];
+        fill_classes_lead(a, L);
+        a.wi = plan.wi;
         switch (c->fuse_shape) {
             case 0: return launch_jacobi2c_t<8, 2>(c, a, n, finest);       // 16 lines, 512 threads
             case 2: return launch_jacobi2c_t<16, 1>(c, a, n, finest);      // 16 lines, 1024 threads
@@ -1432,25 +1391,16 @@ int launch_jacobi2(mg_context* c, const Level& L, const J2Plan& plan, int seg0, 
             default: return launch_jacobi2c_t<12, 2>(c, a, n, finest);     // 24 lines, 768 threads (measured best)
         }
     }
-    if (c->fuse_plain == 2) {            // round-2 structure of the pass on the stored rows (sdia_jacobi2p)
-        a.wi = plan.wi;
-        if (c->fuse_plain_shape == 0) {  // 12 waves x 1 grid line (155 VGPRs, no spills: measured best)
-            if (L.R == 2) return launch_jacobi2p_t<2, 12, 1>(c, a, n, finest);
-            if (L.R == 1) return launch_jacobi2p_t<1, 12, 1>(c, a, n, finest);
-            return launch_jacobi2p_t<4, 12, 1>(c, a, n, finest);
-        }
-        if (c->fuse_plain_shape == 2) {  // 16 waves x 1 grid line
-            if (L.R == 2) return launch_jacobi2p_t<2, 16, 1>(c, a, n, finest);
-            if (L.R == 1) return launch_jacobi2p_t<1, 16, 1>(c, a, n, finest);
-            return launch_jacobi2p_t<4, 16, 1>(c, a, n, finest);
-        }
-        if (L.R == 2) return launch_jacobi2p_t<2, 8, 2>(c, a, n, finest);
-        if (L.R == 1) return launch_jacobi2p_t<1, 8, 2>(c, a, n, finest);
-        return launch_jacobi2p_t<4, 8, 2>(c, a, n, finest);
-    }
-    if (L.R == 2) return launch_jacobi2_t<2, 8, 2>(c, a, n, finest);
-    if (L.R == 1) return launch_jacobi2_t<1, 8, 2>(c, a, n, finest);
-    return launch_jacobi2_t<4, 8, 2>(c, a, n, finest);
+    int rc = 0;
+    with_int_else<4, 1, 2>(L.R, [&](auto r) {
+        constexpr int R = decltype(r)::value;
+        if (c->fuse_plain != 2) { rc = launch_jacobi2_t<R, 8, 2>(c, a, n, finest); return; }
+        a.wi = plan.wi;                  // round-2 structure of the pass on the stored rows (sdia_jacobi2p)
+        if (c->fuse_plain_shape == 0) rc = launch_jacobi2p_t<R, 12, 1>(c, a, n, finest);        // 12 waves x 1 grid line (155 VGPRs, no spills: measured best)
+        else if (c->fuse_plain_shape == 2) rc = launch_jacobi2p_t<R, 16, 1>(c, a, n, finest);   // 16 waves x 1 grid line
+        else rc = launch_jacobi2p_t<R, 8, 2>(c, a, n, finest);
+    });
+    return rc;
 }
 
 // ---- row classes of the neighbours' planes (slabs, K-sweep march) --------------------------------------------------
@@ -1554,7 +1504,7 @@ bool sweepsk_ok(const mg_context* c, const Level& L, bool ignore_size = false) {
         if (L.esc_kmax < 3) return false;
         ignore_size = true;
     }
-    const bool slab = !L.replicated && c->comm.active();
+    const bool slab = is_slab(c, L);
     if (slab && (L.hd < 2 || L.cls_halo < 0 || c->halo_planes != 1)) return false;
     if (!ignore_size && (slab ? min_slab_rows(L) < c->fuse_k_slab_min_rows : L.nloc < c->fuse_k_min_rows)) return false;
     // (the size test of the K-sweep pass is the one above: "fuse_min_rows" is the pair pass's)
@@ -1652,11 +1602,10 @@ int launch_jacobikc_t(mg_context* c, JK3Args a, bool finest, const JK3Range& zr,
         items = (int64_t)a.ta * nseg;
         if (a.ta < ntile) items += (ntile - a.ta) * (int64_t)((planes + a.seglen_b - 1) / a.seglen_b);
     }
-    if (items >= ((int64_t)1 << 31) - 4096) return fail("too many tiles");
-    a.nitems = (unsigned)items;
     a.xcd_chunk = (unsigned)c->fuse_xcd_chunk;
-    const int64_t group = 8 * (int64_t)a.xcd_chunk;
-    const unsigned grid = (unsigned)(((items + group - 1) / group) * group);
+    unsigned grid = 0;
+    MG_TRY(tile_grid(items, a.xcd_chunk, &grid));
+    a.nitems = (unsigned)items;
     if (a.ncls > TR) return fail("more row classes than this tile shape keeps in LDS");
     void (*kern)(JK3Args) = nullptr;
     if constexpr (ESC) kern = sdia_jacobikc_escape<K, NW, LPW, M, DPP, PF, WPE, TR>;
@@ -1716,10 +1665,9 @@ int launch_jacobikc(mg_context* c, const Level& L, int K, const double* x_rows, 
                     const JK3Range* zr = nullptr, int seglen = 0) {
     JK3Args a{};
     a.x = x_rows; a.f = f_rows; a.out = out_rows;
-    a.cls = L.cls; a.ctab = L.ctab; a.clead = L.cls_lead; a.ncls = L.ncls; a.cmain = L.cmain;
-    for (int t = 0; t < 8; ++t) a.cm[t] = L.cm[t];
+    fill_classes_lead(a, L);
     a.P = L.g.plane; a.nx = L.g.nx; a.ny = L.g.ny; a.nz = L.g.nk; a.omega = c->omega;
-    const bool dist = !L.replicated && c->comm.active();
+    const bool dist = is_slab(c, L);
     a.plo = dist && c->comm.rank > 0 ? K : 0;
     a.phi = dist && c->comm.rank + 1 < c->comm.world ? K : 0;
     if (dist && (L.hd < K || L.cls_halo != 1)) return fail("the level's halos are not prepared for that many sweeps per pass");
@@ -1728,15 +1676,11 @@ int launch_jacobikc(mg_context* c, const Level& L, int K, const double* x_rows, 
     a.nt_store = c->fuse_k_nt_store;
     a.escape = L.cls_escape ? 1 : 0; a.dvals = L.dvals; a.mlead = L.mlead; a.sshift = L.R == 1 ? 6 : (L.R == 2 ? 7 : 8);
     const JK3Range whole{0, L.g.nk, 0, 0};
-    const bool finest = c->nlev > 1 && &L == &c->L[c->nlev - 1];
     c->jk3_tail = 0;
-    switch (K) {
-        case 2: return launch_jacobikc_k<2>(c, a, finest, zr ? *zr : whole, seglen);
-        case 3: return launch_jacobikc_k<3>(c, a, finest, zr ? *zr : whole, seglen);
-        case 4: return launch_jacobikc_k<4>(c, a, finest, zr ? *zr : whole, seglen);
-        case 5: return launch_jacobikc_k<5>(c, a, finest, zr ? *zr : whole, seglen);
-        default: return fail("sweeps per pass must be in 2..5");
-    }
+    int rc = 0;
+    if (!with_int<2, 3, 4, 5>(K, [&](auto k) { rc = launch_jacobikc_k<decltype(k)::value>(c, a, is_finest(c, L), zr ? *zr : whole, seglen); }))
+        return fail("sweeps per pass must be in 2..5");
+    return rc;
 }
 
 // Is lattice_color(COLOR_LATTICE9) a valid Gauss-Seidel colouring of the level's matrix?  (structure of the stored
@@ -1752,17 +1696,9 @@ int check_coloring(mg_context* c, Level& L) {
     if (L.sdia) {
         a.vals = L.dvals; a.mlead = L.mlead;
         for (int t = 0; t < 8; ++t) a.up[t] = L.up[t];
-        switch (L.R) {
-            case 1: hipLaunchKernelGGL(sdia_check_coloring<1>, grid, blk, 0, c->stream, a, L.wu, d_flag); break;
-            case 2: hipLaunchKernelGGL(sdia_check_coloring<2>, grid, blk, 0, c->stream, a, L.wu, d_flag); break;
-            default: hipLaunchKernelGGL(sdia_check_coloring<4>, grid, blk, 0, c->stream, a, L.wu, d_flag); break;
-        }
+        with_int_else<4, 1, 2>(L.R, [&](auto r) { hipLaunchKernelGGL(sdia_check_coloring<decltype(r)::value>, grid, blk, 0, c->stream, a, L.wu, d_flag); });
     } else {
-        switch (L.R) {
-            case 1: hipLaunchKernelGGL(ell_check_coloring<1>, grid, blk, 0, c->stream, a, L.nslices, d_flag); break;
-            case 2: hipLaunchKernelGGL(ell_check_coloring<2>, grid, blk, 0, c->stream, a, L.nslices, d_flag); break;
-            default: hipLaunchKernelGGL(ell_check_coloring<4>, grid, blk, 0, c->stream, a, L.nslices, d_flag); break;
-        }
+        with_int_else<4, 1, 2>(L.R, [&](auto r) { hipLaunchKernelGGL(ell_check_coloring<decltype(r)::value>, grid, blk, 0, c->stream, a, L.nslices, d_flag); });
     }
     HIP_TRY(hipGetLastError());
     int flag = 1;
@@ -1803,11 +1739,9 @@ int launch_jacobik_t(mg_context* c, const JKArgs& a, bool cheb) {
     const int64_t ntx = (a.nx + JK_W - 2 * K - 1) / (JK_W - 2 * K);
     int best = c->fuse_2d_lines;
     if (!best) best = K <= 5 && ntx * ((a.nlines + 16 - 2 * K - 1) / (16 - 2 * K)) <= 2 * cus ? 16 : 32;
-    switch (best) {
-        case 16: return launch_jacobik_th<K, 16>(c, a, cheb);
-        case 32: return launch_jacobik_th<K, 32>(c, a, cheb);
-        default: return launch_jacobik_th<K, 64>(c, a, cheb);
-    }
+    int rc = 0;
+    with_int_else<64, 16, 32>(best, [&](auto h) { rc = launch_jacobik_th<K, decltype(h)::value>(c, a, cheb); });
+    return rc;
 }
 
 // out = K Jacobi sweeps applied to x (2 <= K <= 5); with al / be: the K steps of a whole Chebyshev call (be[0] == 0)
@@ -1815,8 +1749,7 @@ int launch_jacobik(mg_context* c, const Level& L, int K, const double* x_rows, c
                    const double* al = nullptr, const double* be = nullptr) {
     JKArgs a{};
     a.x = x_rows; a.f = f_rows; a.out = out_rows;
-    a.cls = L.cls + L.cls_lead; a.ctab = L.ctab; a.ncls = L.ncls; a.cmain = L.cmain;
-    for (int t = 0; t < 8; ++t) a.cm[t] = L.cm[t];
+    fill_classes(a, L);
     a.n = L.nloc; a.nx = L.g.nx; a.nlines = L.g.nz; a.omega = c->omega;
     const bool cheb = al != nullptr;
     if (cheb) {
@@ -1824,13 +1757,10 @@ int launch_jacobik(mg_context* c, const Level& L, int K, const double* x_rows, c
         a.omega = 1.0;                                  // (the class table then holds 1 / d, bit for bit)
         for (int t = 0; t < K; ++t) { a.al[t] = al[t]; a.be[t] = be[t]; }
     }
-    switch (K) {
-        case 2: return launch_jacobik_t<2>(c, a, cheb);
-        case 3: return launch_jacobik_t<3>(c, a, cheb);
-        case 4: return launch_jacobik_t<4>(c, a, cheb);
-        case 5: return launch_jacobik_t<5>(c, a, cheb);
-        default: return fail("sweeps per launch must be in 2..5");
-    }
+    int rc = 0;
+    if (!with_int<2, 3, 4, 5>(K, [&](auto k) { rc = launch_jacobik_t<decltype(k)::value>(c, a, cheb); }))
+        return fail("sweeps per launch must be in 2..5");
+    return rc;
 }
 
 // One sweep as a plane march (sdia_sweep1c): whole, undistributed 3-D seven-point levels with row classes, large enough
@@ -1850,25 +1780,18 @@ int launch_sweep1c_t(mg_context* c, J2Args& a, int mode) {
     const int64_t ntile = (int64_t)a.ntx * a.nty;
     // plane segments: enough work items for a few rounds of the CUs, each paying ~2.5 plane-times of warm-up
     const int64_t cus = std::max(1, c->prop.multiProcessorCount);
-    int best = 1;
-    double best_cost = 1e300;
-    for (int n = 1; n <= std::max(1, a.nz / 16); ++n) {
-        const double cost = (double)((ntile * n + cus - 1) / cus) * ((a.nz + n - 1) / n + 2.5);
-        if (cost < best_cost) { best_cost = cost; best = n; }
-    }
+    int best = best_segments(ntile, cus, a.nz, a.nz / 16, 2.5);
     if (c->fuse_segments > 0) best = std::min(c->fuse_segments, a.nz);
     a.seglen = (a.nz + best - 1) / best;
     const int nseg = (a.nz + a.seglen - 1) / a.seglen;
     const int64_t items = ntile * nseg;
-    if (items >= ((int64_t)1 << 31) - 4096) return fail("too many tiles");
-    a.nitems = (unsigned)items;
     a.xcd_chunk = (unsigned)c->fuse_xcd_chunk;
-    const int64_t group = 8 * (int64_t)a.xcd_chunk;
-    const unsigned grid = (unsigned)(((items + group - 1) / group) * group);
+    unsigned grid = 0;
+    MG_TRY(tile_grid(items, a.xcd_chunk, &grid));
+    a.nitems = (unsigned)items;
     constexpr size_t lds = j1c_lds_bytes<NW, LPW>();
-    void (*kern)(J2Args) = mode == MODE_RESIDUAL ? sdia_sweep1c<NW, LPW, MODE_RESIDUAL>
-                         : mode == MODE_GS ? sdia_sweep1c<NW, LPW, MODE_GS>
-                         : mode == MODE_CHEB ? sdia_sweep1c<NW, LPW, MODE_CHEB> : sdia_sweep1c<NW, LPW, MODE_JACOBI>;
+    void (*kern)(J2Args) = nullptr;
+    with_march_mode(mode, [&](auto m) { kern = sdia_sweep1c<NW, LPW, decltype(m)::value>; });
     MG_TRY(allow_large_lds(c, reinterpret_cast<const void*>(kern), lds));
     hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * WAVE), lds, c->stream, a);
     HIP_TRY(hipGetLastError());
@@ -1881,8 +1804,7 @@ int launch_sweep1c(mg_context* c, const Level& L, int mode, const double* x_rows
     a.x = x_rows; a.f = f_rows; a.out = out_rows;
     a.xp = out_rows; a.beta = beta;
     a.nloc = L.nloc; a.P = L.g.plane; a.nx = L.g.nx; a.ny = L.g.ny; a.nz = L.g.nk; a.omega = mode == MODE_CHEB ? alpha : c->omega;
-    a.cls = L.cls; a.ctab = L.ctab; a.clead = L.cls_lead; a.ncls = L.ncls; a.cmain = L.cmain;
-    for (int t = 0; t < 8; ++t) a.cm[t] = L.cm[t];
+    fill_classes_lead(a, L);
     a.color = color; a.color_kind = c->smoother == MG_SMOOTH_MCGS ? COLOR_LATTICE9 : COLOR_PARITY; a.grow0 = L.row0;
     if (c->march_shape == 1) return launch_sweep1c_t<16, 2>(c, a, mode);
     return launch_sweep1c_t<12, 2>(c, a, mode);
@@ -1935,18 +1857,14 @@ int launch_jacobi_block_t(mg_context* c, const Level& L, JBArgs a) {
 int launch_jacobi_block(mg_context* c, const Level& L, int K, int EZ, const double* x_rows, const double* f_rows, double* out_rows) {
     JBArgs a{};
     a.x = x_rows; a.f = f_rows; a.out = out_rows;
-    a.cls = L.cls + L.cls_lead; a.ctab = L.ctab; a.ncls = L.ncls; a.cmain = L.cmain;
-    for (int t = 0; t < 8; ++t) a.cm[t] = L.cm[t];
+    fill_classes(a, L);
     a.omega = c->omega; a.nx = L.g.nx; a.ny = L.g.ny; a.nz = L.g.nk; a.P = L.g.plane;
-    switch (K * 100 + EZ) {
-        case 211: return launch_jacobi_block_t<2, 11>(c, L, a);
-        case 219: return launch_jacobi_block_t<2, 19>(c, L, a);
-        case 311: return launch_jacobi_block_t<3, 11>(c, L, a);
-        case 319: return launch_jacobi_block_t<3, 19>(c, L, a);
-        case 411: return launch_jacobi_block_t<4, 11>(c, L, a);
-        case 419: return launch_jacobi_block_t<4, 19>(c, L, a);
-        default: return fail("block pass: 2..4 sweeps per launch on blocks of 11 or 19 planes");
-    }
+    int rc = 0;
+    const bool known = with_int<2, 3, 4>(K, [&](auto k) {
+        if (!with_int<11, 19>(EZ, [&](auto ez) { rc = launch_jacobi_block_t<decltype(k)::value, decltype(ez)::value>(c, L, a); })) rc = -1;
+    });
+    if (!known || rc == -1) return fail("block pass: 2..4 sweeps per launch on blocks of 11 or 19 planes");
+    return rc;
 }
 
 bool small_level_ok(const mg_context* c, const Level& L) {
@@ -1966,8 +1884,7 @@ int launch_jacobi_small(mg_context* c, const Level& L, int nw, const double* x_r
                         const double* al = nullptr, const double* be = nullptr) {
     JSArgs a{};
     a.x = x_rows; a.f = f_rows; a.out = out_rows;
-    a.cls = L.cls + L.cls_lead; a.ctab = L.ctab; a.ncls = L.ncls; a.cmain = L.cmain;
-    for (int t = 0; t < 8; ++t) a.cm[t] = L.cm[t];
+    fill_classes(a, L);
     a.n = (int)L.nloc; a.nw = nw; a.up1 = L.up[1]; a.up2 = L.up[2]; a.up3 = L.wu == 4 ? L.up[3] : 0; a.omega = c->omega;
     const bool cheb = al != nullptr;
     if (cheb) {
@@ -1996,8 +1913,7 @@ int launch_jacobi_small(mg_context* c, const Level& L, int nw, const double* x_r
         else if (need <= 12) k(std::integral_constant<int, 12>{});
         else k(std::integral_constant<int, 16>{});
     };
-    if (L.wu == 4) pick(std::integral_constant<int, 4>{});
-    else pick(std::integral_constant<int, 3>{});
+    with_int_else<3, 4>(L.wu, pick);
     MG_TRY(allow_large_lds(c, reinterpret_cast<const void*>(kern), (size_t)150 * 1024));
     hipLaunchKernelGGL(kern, dim3(1), dim3(1024), lds, c->stream, a);
     HIP_TRY(hipGetLastError());
@@ -2006,7 +1922,7 @@ int launch_jacobi_small(mg_context* c, const Level& L, int nw, const double* x_r
 
 // a slab level on which calls of enough sweeps take the K-sweep march with K-plane exchanges (the same answer on every rank)
 bool slab_ksweep_level(const mg_context* c, const Level& L) {
-    return !L.replicated && c->comm.active() && c->fuse_k >= 3 && c->fuse_sweeps && c->fuse_classes && c->use_classes && c->use_sdia &&
+    return is_slab(c, L) && c->fuse_k >= 3 && c->fuse_sweeps && c->fuse_classes && c->use_classes && c->use_sdia &&
            L.hd >= 2 && c->halo_planes == 1 && !L.flat && L.g.nx >= 32 && L.g.ny >= 32 &&
            min_slab_rows(L) >= std::max<int64_t>(8 * L.g.plane, c->fuse_k_slab_min_rows);
 }
@@ -2037,325 +1953,417 @@ void cheb_steps(double lo, double hi, int m, double* alpha, double* beta) {
     }
 }
 
+int smooth_matrix_free(mg_context* c, int level, int nw);
+int smooth_chebyshev(mg_context* c, int level, int nw);
+int smooth_rbgs(mg_context* c, int level, int nw);
+int smooth_mcgs(mg_context* c, int level, int nw);
+int smooth_jacobi(mg_context* c, int level, int nw);
+
 // nw Jacobi sweeps (Chebyshev: a polynomial of degree nw); v halos must be valid on entry and are valid on exit.
 int smooth(mg_context* c, int level, int nw) {
-    Level& L = c->L[level];
+    const Level& L = c->L[level];
     if (L.mf && c->smoother != MG_SMOOTH_JACOBI && c->smoother != MG_SMOOTH_CHEBYSHEV)
         return fail("level " + std::to_string(level) + " is a matrix-free diffusion level: Gauss-Seidel smoothers (RBGS, MCGS) "
                     "need stored rows; use Jacobi or Chebyshev");
-    if (L.mf && c->smoother == MG_SMOOTH_JACOBI) {
-        // one sweep per launch, the rows rebuilt from kappa (the fused passes all read stored rows or row classes)
-        for (int s = 0; s < nw; ++s) {
-            MG_TRY(launch_ell(c, L, MODE_JACOBI, false, L.v.base, L.f.rows, L.v2.rows, nullptr, nullptr));
-            count_pass(c, level, MG_PATH_MATRIX_FREE, 1, 1);
-            std::swap(L.v, L.v2);
-        }
-        return 0;
+    switch (c->smoother) {
+        case MG_SMOOTH_CHEBYSHEV: return smooth_chebyshev(c, level, nw);
+        case MG_SMOOTH_RBGS: return smooth_rbgs(c, level, nw);
+        case MG_SMOOTH_MCGS: return smooth_mcgs(c, level, nw);
+        default: return L.mf ? smooth_matrix_free(c, level, nw) : smooth_jacobi(c, level, nw);
     }
-    if (c->smoother == MG_SMOOTH_CHEBYSHEV) {
-        // one step per launch of whatever kernel launch_ell picks for a Jacobi sweep of the level (counted under its path):
-        // x_{k-1} lives in v2, which each step overwrites row by row with x_{k+1} before v and v2 swap; slabs exchange the
-        // halo of v after each step (x_{k-1} needs none)
-        if (nw == 0) return 0;
-        double lo = 0.0, hi = 0.0;
-        MG_TRY(cheb_interval(c, level, &lo, &hi));
-        std::vector<double> al((size_t)nw), be((size_t)nw);
-        cheb_steps(lo, hi, nw, al.data(), be.data());
-        const bool dist = !L.replicated && c->comm.active();
-        if (!dist && nw >= 2 && small_level_ok(c, L)) {
-            // levels that fit one CU: up to JS_CHEB_STEPS steps per launch of one workgroup, x_{k-1} in registers; a launch
-            // continues from and leaves the one-step sequence's state (v = x_k, v2 = x_{k-1}), so longer calls chain launches
-            for (int s0 = 0; s0 < nw; s0 += JS_CHEB_STEPS) {
-                const int k = std::min(JS_CHEB_STEPS, nw - s0);
-                MG_TRY(launch_jacobi_small(c, L, k, L.v.rows, L.f.rows, L.v2.rows, al.data() + s0, be.data() + s0));
-                count_pass(c, level, MG_PATH_SMALL, 1, k);
-                std::swap(L.v, L.v2);
-            }
-            return 0;
-        }
-        if (!dist && nw >= 2 && nw <= std::min(5, c->fuse_2d_k) && sweeps2d_ok(c, L)) {
-            // 2-D levels: a whole call of at most "fuse_2d_k" steps in one launch.  (Tiles read their halo of x_{k-1}: a launch
-            // that continued a call would read cells that other tiles overwrite, so longer calls run one step per launch.)
-            MG_TRY(launch_jacobik(c, L, nw, L.v.rows, L.f.rows, L.v2.rows, al.data(), be.data()));
-            count_pass(c, level, MG_PATH_K2D, 1, nw);
-            std::swap(L.v, L.v2);
-            return 0;
-        }
-        // (launch_ell's choice for a whole level)
-        const int one_path = L.mf ? MG_PATH_MATRIX_FREE : sweep1c_ok(c, L) ? MG_PATH_SWEEP1C : MG_PATH_SLICE;
-        for (int s = 0; s < nw; ++s) {
-            MG_TRY(launch_ell(c, L, MODE_CHEB, false, L.v.base, L.f.rows, L.v2.rows, nullptr, nullptr, nullptr, 0, -1, 0, 0, 0,
-                              al[(size_t)s], be[(size_t)s]));
-            count_pass(c, level, one_path, 1, 1);
-            std::swap(L.v, L.v2);
-            MG_TRY(exchange_halo(c, L, L.v));
-        }
-        return 0;
-    }
-    if (c->smoother == MG_SMOOTH_RBGS) {
-        // red-black Gauss-Seidel: two in-place half sweeps per sweep, halos refreshed after each colour
-        if (!L.rb_ok)
-            return fail("red-black ordering is not a valid two-colouring of level " + std::to_string(level) +
-                        " (needs a pruned grid matrix with an odd number of nodes per axis)");
-        for (int s = 0; s < nw; ++s)
-            for (int color = 0; color < 2; ++color) {
-                MG_TRY(launch_ell(c, L, MODE_GS, false, L.v.base, L.f.rows, L.v.rows, nullptr, nullptr, nullptr, 0, -1, color));
-                MG_TRY(exchange_halo(c, L, L.v));
-            }
-        return 0;
-    }
-    if (c->smoother == MG_SMOOTH_MCGS) {
-        // nine-colour Gauss-Seidel for P2 rows (lattice_color): one in-place launch per colour, in ascending order
-        if (L.flat) return fail("multi-colour Gauss-Seidel needs a grid level");
-        if (L.mc_ok < 0) MG_TRY(check_coloring(c, L));
-        if (!L.mc_ok)
-            return fail("the nine lattice colours are not a valid colouring of level " + std::to_string(level) +
-                        " (needs a pruned P1 / P2 grid matrix)");
-        // whole 3-D lattice levels: two colours per launch, out of place (v -> v2, then the two swap)
-        const bool pairs = c->lattice_gs2 && c->class_sweeps && lat_march_ok(c, L) && (L.replicated || !c->comm.active());
-        for (int s = 0; s < nw; ++s) {
-            if (pairs) {
-                for (int color = 0; color < 9; color += 2)
-                    MG_TRY(launch_lat_gs2(c, L, color, color + 1 < 9 ? color + 1 : -1, L.v.rows, L.v2.rows));
-                std::swap(L.v, L.v2);
-                continue;
-            }
-            for (int color = 0; color < 9; ++color) {
-                if (c->dim == 2 && (color & 2)) continue;            // (nx, 1, nz) storage: j is always 0
-                MG_TRY(launch_ell(c, L, MODE_GS, false, L.v.base, L.f.rows, L.v.rows, nullptr, nullptr, nullptr, 0, -1, color));
-                MG_TRY(exchange_halo(c, L, L.v));
-            }
-        }
-        return 0;
-    }
-    const bool dist = !L.replicated && c->comm.active();
-    if (!dist && nw >= 2 && small_level_ok(c, L)) {
-        MG_TRY(launch_jacobi_small(c, L, nw, L.v.rows, L.f.rows, L.v2.rows));
-        count_pass(c, level, MG_PATH_SMALL, 1, nw);
-        std::swap(L.v, L.v2);
-        return 0;
-    }
-    if (!dist && nw >= 2 && block_sweeps_ok(c, L)) {
-        // middle 3-D levels: K sweeps per launch on blocks resident on the CU, the rest (at most one) as a single sweep
-        const JBPlan plan = block_plan(c, L);
-        int left = nw;
-        while (left >= 2) {
-            int k = std::min(plan.K, left);
-            if (left - k == 1 && k > 2) --k;                // 4 = 2 + 2 rather than 3 + 1
-            MG_TRY(launch_jacobi_block(c, L, k, plan.EZ, L.v.rows, L.f.rows, L.v2.rows));
-            count_pass(c, level, MG_PATH_BLOCK, 1, k);
-            std::swap(L.v, L.v2);
-            left -= k;
-        }
-        nw = left;
-    }
-    if (!dist && sweeps2d_ok(c, L)) {
-        // 2-D levels: up to fuse_2d_k sweeps per launch, the rest (at most one) as a single sweep
-        int left = nw;
-        while (left >= 2) {
-            int k = std::min(c->fuse_2d_k, left);
-            if (left - k == 1 && k > 2) --k;                // 6 = 3 + 3 rather than 5 + 1
-            MG_TRY(launch_jacobik(c, L, k, L.v.rows, L.f.rows, L.v2.rows));
-            count_pass(c, level, MG_PATH_K2D, 1, k);
-            std::swap(L.v, L.v2);
-            left -= k;
-        }
-        nw = left;
-    }
-    // slices that hold rows of the first / last owned plane: their results are what the neighbours need
-    const int64_t S = (int64_t)WAVE * L.R;
-    const int64_t hplanes = (int64_t)c->halo_planes * L.g.plane;
-    const int64_t lo_end = std::min(L.nslices, (hplanes + S - 1) / S);
-    const int64_t hi_begin = std::max<int64_t>(lo_end, (L.nloc - hplanes) / S);
-    // below a few million rows a sweep is shorter than the extra launches and event hops of the overlapped
-    // form: exchange in-stream there
-    // (taken alike on every rank: every slab of a distributed level has at least 2^level >= 2 planes)
-    const bool two_planes = min_slab_rows(L) >= 2 * hplanes;
-    const bool overlap = dist && c->overlap && two_planes && hi_begin > lo_end && c->comm_stream &&
-                         min_slab_rows(L) >= c->overlap_min_rows;
-    // (the paired pass on slabs is written for one halo plane)
-    const bool fused = fused_sweeps_ok(c, L) && (!dist || (c->halo_planes == 1 && two_planes && hi_begin > lo_end));
-    J2Plan plan{};
-    if (fused && nw > 1) {
-        if (dist) MG_TRY(vec_alloc(c, L, &L.sw));
-        plan = jacobi2_plan(c, L, dist, lo_end * S + L.g.plane + L.g.nx + 2);
-    }
-    // Slabs with room for K halo planes ("halo_depth"): K sweeps per pass AND per exchange -- K planes of the iterate travel
-    // once per pass (the same volume as one plane per sweep) and the march relaxes the neighbours' K - 1 planes next to the
-    // slab itself, so there is no boundary chain: two launches and one grouped send / receive per K sweeps.  With the
-    // overlap on, the planes the neighbours wait for are relaxed first (one launch), and travel on the communication
-    // stream while a second launch relaxes the rest.  (Everything that decides is the same on every rank.)
-    if (dist && nw >= c->fuse_k_slab_min_sweeps && slab_ksweep_level(c, L)) {
-        if (L.cls_halo == 0) MG_TRY(ensure_class_halos(c, L));
-        if (L.cls_halo == 1) {
-            const int kmax = std::min(std::min(c->fuse_k, 5), L.hd);
-            auto next_k = [&](int left) -> int {
-                if (left < 2) return 0;
-                const int k = left >= kmax + 2 || left == kmax ? kmax : left == kmax + 1 ? kmax - 1 : left;
-                return std::max(2, std::min(k, kmax));
-            };
-            const bool lo = c->comm.rank > 0, hi = c->comm.rank + 1 < c->comm.world;
-            const int nk = L.g.nk;
-            int left = nw, k = next_k(left);
-            MG_TRY(exchange_halo(c, L, L.f, nullptr, std::max(1, kmax - 1)));
-            MG_TRY(exchange_halo(c, L, L.v, nullptr, k));
-            while (k) {
-                const int kn = next_k(left - k);                    // the pass after this one
-                const int e = kn ? kn : c->halo_planes;             // planes of the new iterate the neighbours need next
-                const bool split = c->overlap && c->comm_stream && min_slab_rows(L) >= c->overlap_min_rows &&
-                                   min_slab_rows(L) >= (int64_t)(4 * e + 8) * L.g.plane;
-                if (split) {
-                    const int lob = lo ? e : 0, hib = hi ? e : 0;
-                    const JK3Range edge{0, lob, nk - hib, nk}, rest{lob, nk - hib, 0, 0};
-                    MG_TRY(launch_jacobikc(c, L, k, L.v.rows, L.f.rows, L.v2.rows, &edge, e));
-                    const int edge_tail = c->jk3_tail;
-                    HIP_TRY(hipEventRecord(c->ev_boundary, c->stream));
-                    HIP_TRY(hipStreamWaitEvent(c->comm_stream, c->ev_boundary, 0));
-                    MG_TRY(exchange_halo(c, L, L.v2, c->comm_stream, e));
-                    HIP_TRY(hipEventRecord(c->ev_halo, c->comm_stream));
-                    MG_TRY(launch_jacobikc(c, L, k, L.v.rows, L.f.rows, L.v2.rows, &rest));
-                    count_pass(c, level, MG_PATH_KSWEEP_SLAB, 2, k, edge_tail + c->jk3_tail);
-                    HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_halo, 0));
-                } else {
-                    MG_TRY(launch_jacobikc(c, L, k, L.v.rows, L.f.rows, L.v2.rows));
-                    count_pass(c, level, MG_PATH_KSWEEP_SLAB, 1, k, c->jk3_tail);
-                    MG_TRY(exchange_halo(c, L, L.v2, nullptr, e));
-                }
-                std::swap(L.v, L.v2);
-                left -= k;
-                k = kn;
-            }
-            nw = left;
-        }
-    }
-    if (!dist && nw >= 3 && sweepsk_ok(c, L)) {
-        // whole levels: K sweeps per pass while that leaves no single sweep over (50 = 12 x 4 + 2, 7 = 4 + 3, 5 = 3 + 2)
-        const int kmax = sweepsk_max(c, L);
-        int left = nw;
-        while (left >= 3) {
-            int k = left >= kmax + 2 || left == kmax ? kmax : left == kmax + 1 ? kmax - 1 : left;
-            if (k < 3) break;
-            MG_TRY(launch_jacobikc(c, L, k, L.v.rows, L.f.rows, L.v2.rows));
-            count_pass(c, level, L.cls_escape ? MG_PATH_KSWEEP_ESCAPE : MG_PATH_KSWEEP, 1, k, c->jk3_tail);
-            std::swap(L.v, L.v2);
-            left -= k;
-        }
-        nw = left;
-    }
-    const int pair_path = cls_full(L) && c->fuse_classes ? MG_PATH_PAIR_CLASS : MG_PATH_PAIR_PLAIN;
-    const int single_path = sweep1c_ok(c, L) ? MG_PATH_SWEEP1C : MG_PATH_SLICE;     // (launch_ell's choice for a whole level)
+}
+
+// Jacobi on a matrix-free diffusion level: one sweep per launch, the rows rebuilt from kappa (the fused passes all read
+// stored rows or row classes)
+int smooth_matrix_free(mg_context* c, int level, int nw) {
+    Level& L = c->L[level];
     for (int s = 0; s < nw; ++s) {
-        if (fused && s + 1 < nw) {
-            if (!dist) {
-                MG_TRY(launch_jacobi2(c, L, plan, 0, 1, plan.nseg, L.v.rows, L.f.rows, L.v2.rows));
-                count_pass(c, level, pair_path, 1, 2);
-                std::swap(L.v, L.v2);
-                ++s;
-                continue;
-            }
-            // Slabs.  The rows of the slices that hold the first / last owned plane need the neighbours' once-relaxed
-            // planes for their second sweep: the pass leaves them out and parks v1 around them in `sw`, whose halos
-            // are then exchanged like any iterate's, and the one-sweep kernel finishes those slices.
-            const bool lo = c->comm.rank > 0, hi = c->comm.rank + 1 < c->comm.world;
-            const int64_t st_lo = lo ? lo_end * S : 0, st_hi = hi ? hi_begin * S : INT64_MAX;
-            auto boundary_chain = [&](hipStream_t stream) -> int {
-                MG_TRY(exchange_halo(c, L, L.sw, stream));
-                // (the first and the last slices in one launch where the slab has both neighbours)
-                if (lo && hi)
-                    MG_TRY(launch_ell(c, L, MODE_JACOBI, false, L.sw.base, L.f.rows, L.v2.rows, nullptr, nullptr, nullptr, 0,
-                                      lo_end + L.nslices - hi_begin, 0, lo_end, hi_begin - lo_end));
-                else if (lo)
-                    MG_TRY(launch_ell(c, L, MODE_JACOBI, false, L.sw.base, L.f.rows, L.v2.rows, nullptr, nullptr, nullptr, 0, lo_end));
-                else if (hi)
-                    MG_TRY(launch_ell(c, L, MODE_JACOBI, false, L.sw.base, L.f.rows, L.v2.rows, nullptr, nullptr, nullptr, hi_begin,
-                                      L.nslices - hi_begin));
-                MG_TRY(exchange_halo(c, L, L.v2, stream));
-                return 0;
-            };
-            // slices whose once-relaxed values the finishing sweep of the first / last slices reads
-            const int64_t reach = L.g.plane + L.g.nx + 2;
-            const int64_t lo2 = std::min(L.nslices, (lo_end * S + reach + S - 1) / S);
-            const int64_t hi2 = std::max<int64_t>(0, (hi_begin * S - reach) / S);
-            if (overlap && c->slab_pair_form == 1 && plan.nseg >= 3) {
-                // ("slab_pair_form" 1.)  The two boundary segments of the pass first, alone on the GPU -- launched beside
-                // the interior they are dispatched AFTER it, the event hop delays them, and finish late --, then the
-                // interior segments on the main stream while the chain runs on the communication stream; the once-
-                // relaxed boundary planes come from the pass (`sw`).
-                MG_TRY(launch_jacobi2(c, L, plan, 0, plan.nseg - 1, 2, L.v.rows, L.f.rows, L.v2.rows, st_lo, st_hi, L.sw.rows));
-                HIP_TRY(hipEventRecord(c->ev_boundary, c->stream));
-                HIP_TRY(hipStreamWaitEvent(c->comm_stream, c->ev_boundary, 0));
-                MG_TRY(launch_jacobi2(c, L, plan, 1, 1, plan.nseg - 2, L.v.rows, L.f.rows, L.v2.rows, st_lo, st_hi, L.sw.rows));
-                std::swap(c->stream, c->comm_stream);
-                const int rc = boundary_chain(c->stream);
-                std::swap(c->stream, c->comm_stream);
-                MG_TRY(rc);
-                count_pass(c, level, pair_path, 3, 2);                 // two launches of the pass, the boundary chain's
-                HIP_TRY(hipEventRecord(c->ev_halo, c->comm_stream));
-                HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_halo, 0));
-            } else if (overlap && c->slab_pair_form != 1 && hi2 > lo2) {
-                // Everything that waits for the neighbours -- the first sweep of the planes next to them, the exchange of
-                // its boundary planes, the second sweep of the first / last slices, the exchange of the result -- runs
-                // on the (high-priority) communication stream from the start of the pair and needs nothing from the
-                // pass itself: four small operations beside ONE launch of the pass over the whole slab, which stores the
-                // second sweep of all other rows.  (Measured on one slab of eight, tools/slab_rank_probe.py: a separate
-                // boundary launch of the pass in front costs 0.1 ms of the pair's 0.8; beside the interior launch it
-                // is dispatched after it and finishes late.)  The first sweep of those few planes is computed twice.
-                HIP_TRY(hipEventRecord(c->ev_boundary, c->stream));
-                HIP_TRY(hipStreamWaitEvent(c->comm_stream, c->ev_boundary, 0));
-                const J2Plan whole = jacobi2_plan(c, L, false, 0);
-                MG_TRY(launch_jacobi2(c, L, whole, 0, 1, whole.nseg, L.v.rows, L.f.rows, L.v2.rows, st_lo, st_hi, nullptr));
-                std::swap(c->stream, c->comm_stream);
-                const int rc = [&]() -> int {
-                    if (lo && hi)
-                        MG_TRY(launch_ell(c, L, MODE_JACOBI, false, L.v.base, L.f.rows, L.sw.rows, nullptr, nullptr, nullptr, 0,
-                                          lo2 + L.nslices - hi2, 0, lo2, hi2 - lo2));
-                    else if (lo)
-                        MG_TRY(launch_ell(c, L, MODE_JACOBI, false, L.v.base, L.f.rows, L.sw.rows, nullptr, nullptr, nullptr, 0, lo2));
-                    else if (hi)
-                        MG_TRY(launch_ell(c, L, MODE_JACOBI, false, L.v.base, L.f.rows, L.sw.rows, nullptr, nullptr, nullptr, hi2,
-                                          L.nslices - hi2));
-                    return boundary_chain(c->stream);
-                }();
-                std::swap(c->stream, c->comm_stream);
-                MG_TRY(rc);
-                count_pass(c, level, pair_path, 3, 2);                 // the pass, the first sweep of the boundary planes, the chain's
-                HIP_TRY(hipEventRecord(c->ev_halo, c->comm_stream));
-                HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_halo, 0));
-            } else {
-                MG_TRY(launch_jacobi2(c, L, plan, 0, 1, plan.nseg, L.v.rows, L.f.rows, L.v2.rows, st_lo, st_hi, L.sw.rows));
-                MG_TRY(boundary_chain(c->stream));
-                count_pass(c, level, pair_path, 2, 2);                 // the pass, the boundary chain's one-sweep launch
-            }
-            std::swap(L.v, L.v2);
-            ++s;
-            continue;
-        }
-        if (!overlap) {
-            MG_TRY(launch_ell(c, L, MODE_JACOBI, false, L.v.base, L.f.rows, L.v2.rows, nullptr, nullptr));
-            count_pass(c, level, single_path, 1, 1);
-            std::swap(L.v, L.v2);
-            MG_TRY(exchange_halo(c, L, L.v));
-            continue;
-        }
-        // boundary planes first, then their exchange on the communication stream while the interior runs
-        MG_TRY(launch_ell(c, L, MODE_JACOBI, false, L.v.base, L.f.rows, L.v2.rows, nullptr, nullptr, nullptr, 0,
-                          lo_end + L.nslices - hi_begin, 0, lo_end, hi_begin - lo_end));
-        HIP_TRY(hipEventRecord(c->ev_boundary, c->stream));
-        HIP_TRY(hipStreamWaitEvent(c->comm_stream, c->ev_boundary, 0));
-        MG_TRY(exchange_halo(c, L, L.v2, c->comm_stream));
-        HIP_TRY(hipEventRecord(c->ev_halo, c->comm_stream));
-        MG_TRY(launch_ell(c, L, MODE_JACOBI, false, L.v.base, L.f.rows, L.v2.rows, nullptr, nullptr, nullptr, lo_end,
-                          hi_begin - lo_end));
-        count_pass(c, level, MG_PATH_SLICE, 2, 1);                   // boundary slices, interior slices
-        HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_halo, 0));
+        MG_TRY(launch_ell(c, L, level_op(L, MODE_JACOBI)));
+        count_pass(c, level, MG_PATH_MATRIX_FREE, 1, 1);
         std::swap(L.v, L.v2);
     }
     return 0;
 }
 
+int smooth_chebyshev(mg_context* c, int level, int nw) {
+    Level& L = c->L[level];
+    // one step per launch of whatever kernel launch_ell picks for a Jacobi sweep of the level (counted under its path):
+    // x_{k-1} lives in v2, which each step overwrites row by row with x_{k+1} before v and v2 swap; slabs exchange the
+    // halo of v after each step (x_{k-1} needs none)
+    if (nw == 0) return 0;
+    double lo = 0.0, hi = 0.0;
+    MG_TRY(cheb_interval(c, level, &lo, &hi));
+    std::vector<double> al((size_t)nw), be((size_t)nw);
+    cheb_steps(lo, hi, nw, al.data(), be.data());
+    const bool dist = is_slab(c, L);
+    if (!dist && nw >= 2 && small_level_ok(c, L)) {
+        // levels that fit one CU: up to JS_CHEB_STEPS steps per launch of one workgroup, x_{k-1} in registers; a launch
+        // continues from and leaves the one-step sequence's state (v = x_k, v2 = x_{k-1}), so longer calls chain launches
+        for (int s0 = 0; s0 < nw; s0 += JS_CHEB_STEPS) {
+            const int k = std::min(JS_CHEB_STEPS, nw - s0);
+            MG_TRY(launch_jacobi_small(c, L, k, L.v.rows, L.f.rows, L.v2.rows, al.data() + s0, be.data() + s0));
+            count_pass(c, level, MG_PATH_SMALL, 1, k);
+            std::swap(L.v, L.v2);
+        }
+        return 0;
+    }
+    if (!dist && nw >= 2 && nw <= std::min(5, c->fuse_2d_k) && sweeps2d_ok(c, L)) {
+        // 2-D levels: a whole call of at most "fuse_2d_k" steps in one launch.  (Tiles read their halo of x_{k-1}: a launch
+        // that continued a call would read cells that other tiles overwrite, so longer calls run one step per launch.)
+        MG_TRY(launch_jacobik(c, L, nw, L.v.rows, L.f.rows, L.v2.rows, al.data(), be.data()));
+        count_pass(c, level, MG_PATH_K2D, 1, nw);
+        std::swap(L.v, L.v2);
+        return 0;
+    }
+    // (launch_ell's choice for a whole level)
+    const int one_path = L.mf ? MG_PATH_MATRIX_FREE : sweep1c_ok(c, L) ? MG_PATH_SWEEP1C : MG_PATH_SLICE;
+    for (int s = 0; s < nw; ++s) {
+        EllRequest step = level_op(L, MODE_CHEB);
+        step.alpha = al[(size_t)s]; step.beta = be[(size_t)s];
+        MG_TRY(launch_ell(c, L, step));
+        count_pass(c, level, one_path, 1, 1);
+        std::swap(L.v, L.v2);
+        MG_TRY(exchange_halo(c, L, L.v));
+    }
+    return 0;
+}
+
+// one Gauss-Seidel colour of the level, in place
+int launch_gs_color(mg_context* c, const Level& L, int color) {
+    EllRequest q = level_op(L, MODE_GS);
+    q.out_rows = L.v.rows; q.color = color;
+    return launch_ell(c, L, q);
+}
+
+// red-black Gauss-Seidel: two in-place half sweeps per sweep, halos refreshed after each colour
+int smooth_rbgs(mg_context* c, int level, int nw) {
+    Level& L = c->L[level];
+    if (!L.rb_ok)
+        return fail("red-black ordering is not a valid two-colouring of level " + std::to_string(level) +
+                    " (needs a pruned grid matrix with an odd number of nodes per axis)");
+    for (int s = 0; s < nw; ++s)
+        for (int color = 0; color < 2; ++color) {
+            MG_TRY(launch_gs_color(c, L, color));
+            MG_TRY(exchange_halo(c, L, L.v));
+        }
+    return 0;
+}
+
+// nine-colour Gauss-Seidel for P2 rows (lattice_color): one in-place launch per colour, in ascending order
+int smooth_mcgs(mg_context* c, int level, int nw) {
+    Level& L = c->L[level];
+    if (L.flat) return fail("multi-colour Gauss-Seidel needs a grid level");
+    if (L.mc_ok < 0) MG_TRY(check_coloring(c, L));
+    if (!L.mc_ok)
+        return fail("the nine lattice colours are not a valid colouring of level " + std::to_string(level) +
+                    " (needs a pruned P1 / P2 grid matrix)");
+    // whole 3-D lattice levels: two colours per launch, out of place (v -> v2, then the two swap)
+    const bool pairs = c->lattice_gs2 && c->class_sweeps && lat_march_ok(c, L) && (L.replicated || !c->comm.active());
+    for (int s = 0; s < nw; ++s) {
+        if (pairs) {
+            for (int color = 0; color < 9; color += 2)
+                MG_TRY(launch_lat_gs2(c, L, color, color + 1 < 9 ? color + 1 : -1, L.v.rows, L.v2.rows));
+            std::swap(L.v, L.v2);
+            continue;
+        }
+        for (int color = 0; color < 9; ++color) {
+            if (c->dim == 2 && (color & 2)) continue;            // (nx, 1, nz) storage: j is always 0
+            MG_TRY(launch_gs_color(c, L, color));
+            MG_TRY(exchange_halo(c, L, L.v));
+        }
+    }
+    return 0;
+}
+
+// ---- Jacobi: the paths, in the order smooth_jacobi tries them.  Each takes the sweeps it can of *nw and leaves the rest. ----
+
+// sweeps of the next launch of a kernel that takes up to kmax and at least two: kmax, but 6 = 3 + 3 rather than 5 + 1
+// (the rest, at most one, is a single sweep)
+int up_to(int kmax, int left) {
+    const int k = std::min(kmax, left);
+    return left - k == 1 && k > 2 ? k - 1 : k;
+}
+
+// sweeps of the next pass of the K-sweep march: kmax while that leaves no single sweep over (50 = 12 x 4 + 2, 7 = 4 + 3,
+// 5 = 3 + 2)
+int next_pass(int left, int kmax) { return left >= kmax + 2 || left == kmax ? kmax : left == kmax + 1 ? kmax - 1 : left; }
+
+// What follows on the communication stream waits for everything enqueued on the main stream so far ...
+int fork_to_comm(mg_context* c) {
+    HIP_TRY(hipEventRecord(c->ev_boundary, c->stream));
+    HIP_TRY(hipStreamWaitEvent(c->comm_stream, c->ev_boundary, 0));
+    return 0;
+}
+// ... and what follows on the main stream for everything enqueued on the communication stream so far.
+int join_comm(mg_context* c) {
+    HIP_TRY(hipEventRecord(c->ev_halo, c->comm_stream));
+    HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_halo, 0));
+    return 0;
+}
+// f() with the communication stream in the main stream's place (the launchers and exchanges enqueue on c->stream)
+template <class F>
+int on_comm_stream(mg_context* c, F&& f) {
+    std::swap(c->stream, c->comm_stream);
+    const int rc = f();
+    std::swap(c->stream, c->comm_stream);
+    return rc;
+}
+
+// all sweeps of a level that fits one CU's LDS in one launch
+int jacobi_small(mg_context* c, int level, int* nw) {
+    Level& L = c->L[level];
+    if (is_slab(c, L) || *nw < 2 || !small_level_ok(c, L)) return 0;
+    MG_TRY(launch_jacobi_small(c, L, *nw, L.v.rows, L.f.rows, L.v2.rows));
+    count_pass(c, level, MG_PATH_SMALL, 1, *nw);
+    std::swap(L.v, L.v2);
+    *nw = 0;
+    return 0;
+}
+
+// middle 3-D levels: K sweeps per launch on blocks resident on the CU, the rest (at most one) as a single sweep
+int jacobi_blocks(mg_context* c, int level, int* nw) {
+    Level& L = c->L[level];
+    if (is_slab(c, L) || *nw < 2 || !block_sweeps_ok(c, L)) return 0;
+    const JBPlan plan = block_plan(c, L);
+    while (*nw >= 2) {
+        const int k = up_to(plan.K, *nw);                   // 4 = 2 + 2 rather than 3 + 1
+        MG_TRY(launch_jacobi_block(c, L, k, plan.EZ, L.v.rows, L.f.rows, L.v2.rows));
+        count_pass(c, level, MG_PATH_BLOCK, 1, k);
+        std::swap(L.v, L.v2);
+        *nw -= k;
+    }
+    return 0;
+}
+
+// 2-D levels: up to fuse_2d_k sweeps per launch, the rest (at most one) as a single sweep
+int jacobi_2d(mg_context* c, int level, int* nw) {
+    Level& L = c->L[level];
+    if (is_slab(c, L) || !sweeps2d_ok(c, L)) return 0;
+    while (*nw >= 2) {
+        const int k = up_to(c->fuse_2d_k, *nw);
+        MG_TRY(launch_jacobik(c, L, k, L.v.rows, L.f.rows, L.v2.rows));
+        count_pass(c, level, MG_PATH_K2D, 1, k);
+        std::swap(L.v, L.v2);
+        *nw -= k;
+    }
+    return 0;
+}
+
+// Slabs with room for K halo planes ("halo_depth"): K sweeps per pass AND per exchange -- K planes of the iterate travel
+// once per pass (the same volume as one plane per sweep) and the march relaxes the neighbours' K - 1 planes next to the
+// slab itself, so there is no boundary chain: two launches and one grouped send / receive per K sweeps.  With the
+// overlap on, the planes the neighbours wait for are relaxed first (one launch), and travel on the communication
+// stream while a second launch relaxes the rest.  (Everything that decides is the same on every rank.)
+int jacobi_ksweep_slab(mg_context* c, int level, int* nw) {
+    Level& L = c->L[level];
+    if (!is_slab(c, L) || *nw < c->fuse_k_slab_min_sweeps || !slab_ksweep_level(c, L)) return 0;
+    if (L.cls_halo == 0) MG_TRY(ensure_class_halos(c, L));
+    if (L.cls_halo != 1) return 0;
+    const int kmax = std::min(std::min(c->fuse_k, 5), L.hd);
+    // (a pass on a slab also saves an exchange: two sweeps are worth one)
+    auto next_k = [&](int left) { return left < 2 ? 0 : std::max(2, std::min(next_pass(left, kmax), kmax)); };
+    const bool lo = c->comm.rank > 0, hi = c->comm.rank + 1 < c->comm.world;
+    const int nk = L.g.nk;
+    int k = next_k(*nw);
+    MG_TRY(exchange_halo(c, L, L.f, nullptr, std::max(1, kmax - 1)));
+    MG_TRY(exchange_halo(c, L, L.v, nullptr, k));
+    while (k) {
+        const int kn = next_k(*nw - k);                     // the pass after this one
+        const int e = kn ? kn : c->halo_planes;             // planes of the new iterate the neighbours need next
+        const bool split = c->overlap && c->comm_stream && min_slab_rows(L) >= c->overlap_min_rows &&
+                           min_slab_rows(L) >= (int64_t)(4 * e + 8) * L.g.plane;
+        if (split) {
+            const int lob = lo ? e : 0, hib = hi ? e : 0;
+            const JK3Range edge{0, lob, nk - hib, nk}, rest{lob, nk - hib, 0, 0};
+            MG_TRY(launch_jacobikc(c, L, k, L.v.rows, L.f.rows, L.v2.rows, &edge, e));
+            const int edge_tail = c->jk3_tail;
+            MG_TRY(fork_to_comm(c));
+            MG_TRY(exchange_halo(c, L, L.v2, c->comm_stream, e));
+            MG_TRY(launch_jacobikc(c, L, k, L.v.rows, L.f.rows, L.v2.rows, &rest));
+            count_pass(c, level, MG_PATH_KSWEEP_SLAB, 2, k, edge_tail + c->jk3_tail);
+            MG_TRY(join_comm(c));
+        } else {
+            MG_TRY(launch_jacobikc(c, L, k, L.v.rows, L.f.rows, L.v2.rows));
+            count_pass(c, level, MG_PATH_KSWEEP_SLAB, 1, k, c->jk3_tail);
+            MG_TRY(exchange_halo(c, L, L.v2, nullptr, e));
+        }
+        std::swap(L.v, L.v2);
+        *nw -= k;
+        k = kn;
+    }
+    return 0;
+}
+
+// whole levels: K sweeps per pass (at least three)
+int jacobi_ksweep(mg_context* c, int level, int* nw) {
+    Level& L = c->L[level];
+    if (is_slab(c, L) || *nw < 3 || !sweepsk_ok(c, L)) return 0;
+    const int kmax = sweepsk_max(c, L);
+    while (*nw >= 3) {
+        const int k = next_pass(*nw, kmax);
+        if (k < 3) break;
+        MG_TRY(launch_jacobikc(c, L, k, L.v.rows, L.f.rows, L.v2.rows));
+        count_pass(c, level, L.cls_escape ? MG_PATH_KSWEEP_ESCAPE : MG_PATH_KSWEEP, 1, k, c->jk3_tail);
+        std::swap(L.v, L.v2);
+        *nw -= k;
+    }
+    return 0;
+}
+
+// What the pair and single-sweep paths of a level share.
+struct PairPlan {
+    int64_t S = 0;                      // rows per slice
+    int64_t lo_end = 0, hi_begin = 0;   // slices [0, lo_end) and [hi_begin, nslices) hold rows of the first / last owned planes:
+                                        // their results are what the neighbours need
+    bool overlap = false;               // slabs: the exchanges run on the communication stream beside the interior's sweep
+    bool fused = false;                 // two sweeps per pass (mg_jacobi2.hip.h)
+    J2Plan plan{};
+};
+
+int plan_pairs(mg_context* c, Level& L, int nw, PairPlan* pp) {
+    const bool dist = is_slab(c, L);
+    pp->S = (int64_t)WAVE * L.R;
+    const int64_t hplanes = (int64_t)c->halo_planes * L.g.plane;
+    pp->lo_end = std::min(L.nslices, (hplanes + pp->S - 1) / pp->S);
+    pp->hi_begin = std::max<int64_t>(pp->lo_end, (L.nloc - hplanes) / pp->S);
+    // below a few million rows a sweep is shorter than the extra launches and event hops of the overlapped
+    // form: exchange in-stream there
+    // (taken alike on every rank: every slab of a distributed level has at least 2^level >= 2 planes)
+    const bool two_planes = min_slab_rows(L) >= 2 * hplanes;
+    pp->overlap = dist && c->overlap && two_planes && pp->hi_begin > pp->lo_end && c->comm_stream &&
+                  min_slab_rows(L) >= c->overlap_min_rows;
+    // (the paired pass on slabs is written for one halo plane)
+    pp->fused = fused_sweeps_ok(c, L) && (!dist || (c->halo_planes == 1 && two_planes && pp->hi_begin > pp->lo_end));
+    if (pp->fused && nw > 1) {
+        if (dist) MG_TRY(vec_alloc(c, L, &L.sw));
+        pp->plan = jacobi2_plan(c, L, dist, pp->lo_end * pp->S + L.g.plane + L.g.nx + 2);
+    }
+    return 0;
+}
+
+// Two sweeps of a slab in one pass.  The rows of the slices that hold the first / last owned plane need the neighbours'
+// once-relaxed planes for their second sweep: the pass leaves them out and parks v1 around them in `sw`, whose halos
+// are then exchanged like any iterate's, and the one-sweep kernel finishes those slices.
+int jacobi_pair_slab(mg_context* c, int level, const PairPlan& pp, int pair_path) {
+    Level& L = c->L[level];
+    const J2Plan& plan = pp.plan;
+    const int64_t S = pp.S, lo_end = pp.lo_end, hi_begin = pp.hi_begin;
+    const bool lo = c->comm.rank > 0, hi = c->comm.rank + 1 < c->comm.world;
+    const int64_t st_lo = lo ? lo_end * S : 0, st_hi = hi ? hi_begin * S : INT64_MAX;
+    // one sweep from `from` into `to_rows` on the slab's end slices next to a neighbour: the first lo_count, those from hi_from on
+    auto sweep_ends = [&](const DVector& from, double* to_rows, int64_t lo_count, int64_t hi_from) {
+        EllRequest q = level_op(L, MODE_JACOBI);
+        q.x_base = from.base; q.out_rows = to_rows; q.slices = SliceRange::ends_of_slab(L, lo, hi, lo_count, hi_from);
+        return launch_ell(c, L, q);
+    };
+    auto boundary_chain = [&]() -> int {
+        MG_TRY(exchange_halo(c, L, L.sw, c->stream));
+        MG_TRY(sweep_ends(L.sw, L.v2.rows, lo_end, hi_begin));
+        MG_TRY(exchange_halo(c, L, L.v2, c->stream));
+        return 0;
+    };
+    // slices whose once-relaxed values the finishing sweep of the first / last slices reads
+    const int64_t reach = L.g.plane + L.g.nx + 2;
+    const int64_t lo2 = std::min(L.nslices, (lo_end * S + reach + S - 1) / S);
+    const int64_t hi2 = std::max<int64_t>(0, (hi_begin * S - reach) / S);
+    if (pp.overlap && c->slab_pair_form == 1 && plan.nseg >= 3) {
+        // ("slab_pair_form" 1.)  The two boundary segments of the pass first, alone on the GPU -- launched beside
+        // the interior they are dispatched AFTER it, the event hop delays them, and finish late --, then the
+        // interior segments on the main stream while the chain runs on the communication stream; the once-
+        // relaxed boundary planes come from the pass (`sw`).
+        MG_TRY(launch_jacobi2(c, L, plan, 0, plan.nseg - 1, 2, L.v.rows, L.f.rows, L.v2.rows, st_lo, st_hi, L.sw.rows));
+        MG_TRY(fork_to_comm(c));
+        MG_TRY(launch_jacobi2(c, L, plan, 1, 1, plan.nseg - 2, L.v.rows, L.f.rows, L.v2.rows, st_lo, st_hi, L.sw.rows));
+        MG_TRY(on_comm_stream(c, boundary_chain));
+        count_pass(c, level, pair_path, 3, 2);                 // two launches of the pass, the boundary chain's
+        MG_TRY(join_comm(c));
+    } else if (pp.overlap && c->slab_pair_form != 1 && hi2 > lo2) {
+        // Everything that waits for the neighbours -- the first sweep of the planes next to them, the exchange of
+        // its boundary planes, the second sweep of the first / last slices, the exchange of the result -- runs
+        // on the (high-priority) communication stream from the start of the pair and needs nothing from the
+        // pass itself: four small operations beside ONE launch of the pass over the whole slab, which stores the
+        // second sweep of all other rows.  (Measured on one slab of eight, tools/slab_rank_probe.py: a separate
+        // boundary launch of the pass in front costs 0.1 ms of the pair's 0.8; beside the interior launch it
+        // is dispatched after it and finishes late.)  The first sweep of those few planes is computed twice.
+        MG_TRY(fork_to_comm(c));
+        const J2Plan whole = jacobi2_plan(c, L, false, 0);
+        MG_TRY(launch_jacobi2(c, L, whole, 0, 1, whole.nseg, L.v.rows, L.f.rows, L.v2.rows, st_lo, st_hi, nullptr));
+        MG_TRY(on_comm_stream(c, [&]() -> int {
+            MG_TRY(sweep_ends(L.v, L.sw.rows, lo2, hi2));
+            return boundary_chain();
+        }));
+        count_pass(c, level, pair_path, 3, 2);                 // the pass, the first sweep of the boundary planes, the chain's
+        MG_TRY(join_comm(c));
+    } else {
+        MG_TRY(launch_jacobi2(c, L, plan, 0, 1, plan.nseg, L.v.rows, L.f.rows, L.v2.rows, st_lo, st_hi, L.sw.rows));
+        MG_TRY(boundary_chain());
+        count_pass(c, level, pair_path, 2, 2);                 // the pass, the boundary chain's one-sweep launch
+    }
+    std::swap(L.v, L.v2);
+    return 0;
+}
+
+// one sweep of a slab whose exchange overlaps: boundary planes first, then their exchange on the communication stream
+// while the interior runs
+int jacobi_single_overlapped(mg_context* c, int level, const PairPlan& pp) {
+    Level& L = c->L[level];
+    EllRequest q = level_op(L, MODE_JACOBI);
+    q.slices = SliceRange::ends(L, pp.lo_end, pp.hi_begin);
+    MG_TRY(launch_ell(c, L, q));
+    MG_TRY(fork_to_comm(c));
+    MG_TRY(exchange_halo(c, L, L.v2, c->comm_stream));
+    q.slices = SliceRange::of(pp.lo_end, pp.hi_begin - pp.lo_end);
+    MG_TRY(launch_ell(c, L, q));
+    count_pass(c, level, MG_PATH_SLICE, 2, 1);                   // boundary slices, interior slices
+    MG_TRY(join_comm(c));
+    std::swap(L.v, L.v2);
+    return 0;
+}
+
+// what is left: pairs of sweeps where the level takes the two-sweep pass, single sweeps otherwise and for an odd one
+int jacobi_pairs_singles(mg_context* c, int level, int nw, const PairPlan& pp) {
+    Level& L = c->L[level];
+    const bool dist = is_slab(c, L);
+    const int pair_path = cls_full(L) && c->fuse_classes ? MG_PATH_PAIR_CLASS : MG_PATH_PAIR_PLAIN;
+    const int single_path = sweep1c_ok(c, L) ? MG_PATH_SWEEP1C : MG_PATH_SLICE;     // (launch_ell's choice for a whole level)
+    for (int s = 0; s < nw; ++s) {
+        if (pp.fused && s + 1 < nw) {
+            if (dist) {
+                MG_TRY(jacobi_pair_slab(c, level, pp, pair_path));
+            } else {
+                MG_TRY(launch_jacobi2(c, L, pp.plan, 0, 1, pp.plan.nseg, L.v.rows, L.f.rows, L.v2.rows));
+                count_pass(c, level, pair_path, 1, 2);
+                std::swap(L.v, L.v2);
+            }
+            ++s;
+        } else if (pp.overlap) {
+            MG_TRY(jacobi_single_overlapped(c, level, pp));
+        } else {
+            MG_TRY(launch_ell(c, L, level_op(L, MODE_JACOBI)));
+            count_pass(c, level, single_path, 1, 1);
+            std::swap(L.v, L.v2);
+            MG_TRY(exchange_halo(c, L, L.v));
+        }
+    }
+    return 0;
+}
+
+// small -> block -> 2-D -> slab K-sweep -> whole-level K-sweep -> pairs / singles
+int smooth_jacobi(mg_context* c, int level, int nw) {
+    Level& L = c->L[level];
+    MG_TRY(jacobi_small(c, level, &nw));
+    MG_TRY(jacobi_blocks(c, level, &nw));
+    MG_TRY(jacobi_2d(c, level, &nw));
+    // (planned here, with the sweeps the K-sweep paths may still take: a slab's `sw` is allocated by the first call of two sweeps or more)
+    PairPlan pp;
+    MG_TRY(plan_pairs(c, L, nw, &pp));
+    MG_TRY(jacobi_ksweep_slab(c, level, &nw));
+    MG_TRY(jacobi_ksweep(c, level, &nw));
+    return jacobi_pairs_singles(c, level, nw, pp);
+}
 int residual(mg_context* c, int level) {
     Level& L = c->L[level];
-    return launch_ell(c, L, MODE_RESIDUAL, false, L.v.base, L.f.rows, L.v2.rows, nullptr, nullptr);
+    return launch_ell(c, L, level_op(L, MODE_RESIDUAL));
 }
 
 // Grid of the coarse planes this rank produces when restricting from `fine`: its own slab if the
@@ -2414,7 +2422,7 @@ int check_p1_stencil(mg_context* c, Level& L) {
             HIP_TRY(hipStreamSynchronize(c->stream));
             ok = h == 0;
         }
-        if (!L.replicated && c->comm.active()) {
+        if (is_slab(c, L)) {
             // one verdict for every rank: a rank that refused alone would leave the others waiting in the next exchange
             double bad = ok ? 0.0 : 1.0;
             double* d_bad = reinterpret_cast<double*>(c->partials);
@@ -2439,7 +2447,7 @@ int restrict_to(mg_context* c, int level, int kind) {
     if (kind == MG_RESTRICT_TABLE) {
         if (!c->rtab_count) return fail("no restriction table (mg_set_restriction_table)");
         // (the transpose of the P2 prolongation reaches three fine planes: on slabs the residual's halo must have room for them)
-        if (!F.replicated && c->comm.active()) {
+        if (is_slab(c, F)) {
             if (F.hd < 3) return fail("the table restriction reaches three fine planes: \"halo_depth\" must be at least 3 on slabs");
             MG_TRY(exchange_halo(c, F, F.v2, nullptr, 3));
         }
@@ -2449,10 +2457,9 @@ int restrict_to(mg_context* c, int level, int kind) {
         MG_TRY(check_p1_stencil(c, F));
         MG_TRY(check_p1_stencil(c, C));
         MG_TRY(exchange_halo(c, F, F.v2));          // (the same fine planes as full weighting)
-        if (c->dim == 3)
-            hipLaunchKernelGGL(restrict_p1t<3>, grid3(gc, gc.nk), dim3(kPlaneBlock), 0, c->stream, gc, F.g, F.v2.base, C.f.base);
-        else
-            hipLaunchKernelGGL(restrict_p1t<2>, grid3(gc, gc.nk), dim3(kPlaneBlock), 0, c->stream, gc, F.g, F.v2.base, C.f.base);
+        with_int_else<2, 3>(c->dim, [&](auto dim) {
+            hipLaunchKernelGGL(restrict_p1t<decltype(dim)::value>, grid3(gc, gc.nk), dim3(kPlaneBlock), 0, c->stream, gc, F.g, F.v2.base, C.f.base);
+        });
     } else if (kind == MG_RESTRICT_FULL_WEIGHTING) {
         MG_TRY(exchange_halo(c, F, F.v2));
         hipLaunchKernelGGL(restrict_full_weighting, grid3(gc, gc.nk), dim3(kPlaneBlock), 0, c->stream, gc, F.g, F.v2.base,
@@ -2495,32 +2502,27 @@ int prolong(mg_context* c, int level, int add) {
     Level& C = c->L[level - 1];
     const bool keep = !add || c->keep_err;
     if (keep) MG_TRY(vec_alloc(c, F, &F.err));
+    double* const err = keep ? F.err.base : nullptr;        // (kept: the prolonged coarse iterate goes there as well)
     if (c->p1_prolong) {
         // the coarse planes K and K + 1, as the Q1 interpolation reads them
         MG_TRY(check_p1_stencil(c, F));
         MG_TRY(check_p1_stencil(c, C));
         const dim3 grid = grid3(F.g, F.g.nk), blk(kPlaneBlock);
-        if (add && keep)
-            hipLaunchKernelGGL((prolong_p1<true, true>), grid, blk, 0, c->stream, C.g, F.g, C.v.base, F.v.base, F.err.base);
-        else if (add)
-            hipLaunchKernelGGL((prolong_p1<true, false>), grid, blk, 0, c->stream, C.g, F.g, C.v.base, F.v.base, (double*)nullptr);
-        else
-            hipLaunchKernelGGL((prolong_p1<false, true>), grid, blk, 0, c->stream, C.g, F.g, C.v.base, F.v.base, F.err.base);
+        with_add_keep(add, keep, [&](auto ad, auto kp) {
+            hipLaunchKernelGGL((prolong_p1<decltype(ad)::value, decltype(kp)::value>), grid, blk, 0, c->stream, C.g, F.g, C.v.base, F.v.base, err);
+        });
         HIP_TRY(hipGetLastError());
         if (add) MG_TRY(exchange_halo(c, F, F.v));
         return 0;
     }
     if (c->ptab_count) {
-        if (!F.replicated && c->comm.active() && c->halo_planes < 2)
+        if (is_slab(c, F) && c->halo_planes < 2)
             return fail("the table prolongation reaches two coarse planes: halo_planes must be 2 on slabs");
         const ProlongTable t{c->ptab_count, c->ptab_off, c->ptab_w};
         const dim3 grid = grid3(F.g, F.g.nk), blk(kPlaneBlock);
-        if (add && keep)
-            hipLaunchKernelGGL((prolong_table<true, true>), grid, blk, 0, c->stream, C.g, F.g, t, C.v.base, F.v.base, F.err.base);
-        else if (add)
-            hipLaunchKernelGGL((prolong_table<true, false>), grid, blk, 0, c->stream, C.g, F.g, t, C.v.base, F.v.base, (double*)nullptr);
-        else
-            hipLaunchKernelGGL((prolong_table<false, true>), grid, blk, 0, c->stream, C.g, F.g, t, C.v.base, F.v.base, F.err.base);
+        with_add_keep(add, keep, [&](auto ad, auto kp) {
+            hipLaunchKernelGGL((prolong_table<decltype(ad)::value, decltype(kp)::value>), grid, blk, 0, c->stream, C.g, F.g, t, C.v.base, F.v.base, err);
+        });
         HIP_TRY(hipGetLastError());
         if (add) MG_TRY(exchange_halo(c, F, F.v));
         return 0;
@@ -2528,12 +2530,9 @@ int prolong(mg_context* c, int level, int add) {
     // one thread per pair of fine nodes along x
     const int64_t pairs = (int64_t)((F.g.nx + 1) / 2) * F.g.ny;
     const dim3 grid((unsigned)((pairs + kPlaneBlock - 1) / kPlaneBlock), (unsigned)F.g.nk, 1u);
-    if (add && keep)
-        hipLaunchKernelGGL((prolong_correct<true, true>), grid, dim3(kPlaneBlock), 0, c->stream, C.g, F.g, C.v.base, F.v.base, F.err.base);
-    else if (add)
-        hipLaunchKernelGGL((prolong_correct<true, false>), grid, dim3(kPlaneBlock), 0, c->stream, C.g, F.g, C.v.base, F.v.base, (double*)nullptr);
-    else
-        hipLaunchKernelGGL((prolong_correct<false, true>), grid, dim3(kPlaneBlock), 0, c->stream, C.g, F.g, C.v.base, F.v.base, F.err.base);
+    with_add_keep(add, keep, [&](auto ad, auto kp) {
+        hipLaunchKernelGGL((prolong_correct<decltype(ad)::value, decltype(kp)::value>), grid, dim3(kPlaneBlock), 0, c->stream, C.g, F.g, C.v.base, F.v.base, err);
+    });
     HIP_TRY(hipGetLastError());
     if (add) MG_TRY(exchange_halo(c, F, F.v));
     return 0;
@@ -2599,7 +2598,7 @@ int cheb_estimate(mg_context* c, int level) {
     // (slabs: each rank tested its own rows, so the refusal is voted before the first collective -- every rank refuses
     //  together, none waits in an all-reduce for a rank that has left)
     bool asym = L.rep_sym == 0;
-    if (!L.replicated && c->comm.active()) {
+    if (is_slab(c, L)) {
         c->h_scalars[0] = asym ? 1.0 : 0.0;
         HIP_TRY(hipMemcpyAsync(c->scalars, c->h_scalars, sizeof(double), hipMemcpyHostToDevice, c->stream));
         MG_TRY(allreduce_sum(c, c->scalars, 1));
@@ -2648,7 +2647,7 @@ int cheb_estimate(mg_context* c, int level) {
     if (rz > 0.0 && std::isfinite(rz)) {
         for (int j = 0; j < c->cheb_eig_steps; ++j) {
             MG_TRY(exchange_halo(c, L, p));
-            MG_TRY(launch_ell(c, L, MODE_SPMV, false, p.base, nullptr, q, nullptr, nullptr));
+            MG_TRY(launch_ell(c, L, {.mode = MODE_SPMV, .x_base = p.base, .out_rows = q}));
             double pq = 0.0;
             MG_TRY(scalar(p.rows, q, &pq));
             if (!(pq > 0.0) || !std::isfinite(pq)) break;          // breakdown: A not positive definite on the Krylov space
@@ -2810,7 +2809,7 @@ int validate_direct(mg_context* c) {
         HIP_TRY(hipMemcpyAsync(L.f.rows, ones.data(), (size_t)L.nloc * 8, hipMemcpyHostToDevice, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
         MG_TRY(direct_solve(c));
-        MG_TRY(launch_ell(c, L, MODE_RESIDUAL, false, L.v.base, L.f.rows, L.v2.rows, nullptr, nullptr));
+        MG_TRY(residual(c, 0));
         double rn = 0.0;
         MG_TRY(norm2(c, L, L.v2.rows, &rn));
         const double rel = rn / std::sqrt((double)L.nloc);
@@ -2900,7 +2899,8 @@ int pcg_solve(mg_context* c, int* iters_out, double* rel_out) {
         batch = std::min(batch, c->coarse_maxit - it);
         for (int b = 0; b < batch; ++b) {
             unsigned np_spmv = 0;
-            MG_TRY(launch_ell(c, L, MODE_SPMV, true, c->pcg_p.base, nullptr, c->pcg_q, c->pcg_part_a, c->done, &np_spmv));
+            MG_TRY(launch_ell(c, L, {.mode = MODE_SPMV, .dot = true, .x_base = c->pcg_p.base, .out_rows = c->pcg_q, .partials = c->pcg_part_a,
+                                     .done = c->done, .grid_out = &np_spmv}));
             hipLaunchKernelGGL(pcg_update, grid, blk, 0, c->stream, a, (int)np_spmv, it + b);
             hipLaunchKernelGGL(pcg_direction, grid, blk, 0, c->stream, a, it + b);
         }
@@ -3054,7 +3054,7 @@ FcgWork fcg_work(const mg_context* c) {
 // order is fixed by the level and the device.
 int fcg_sums(mg_context* c, const Level& L, const double*& parts, int64_t& np, int stride, int64_t fold_above, double* fold,
              double* total) {
-    const bool slab = !L.replicated && c->comm.active();
+    const bool slab = is_slab(c, L);
     if (!slab && np > fold_above) {
         hipLaunchKernelGGL(fcg_fold, dim3(kFcgFold), dim3(BLOCK), 0, c->stream, parts, np, stride, fold);
         parts = fold;
@@ -3109,7 +3109,7 @@ int fcg_solve(mg_context* c, int level, double rtol, int max_iter, double* hist,
     HIP_TRY(hipMemcpyAsync(L.fcg_b.base, L.f.base, bytes, hipMemcpyDeviceToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(L.fcg_x.base, L.v.base, bytes, hipMemcpyDeviceToDevice, c->stream));
     MG_TRY(exchange_halo(c, L, L.fcg_x));
-    MG_TRY(launch_ell(c, L, MODE_RESIDUAL, false, L.fcg_x.base, L.fcg_b.rows, L.f.rows, nullptr, nullptr));
+    MG_TRY(launch_ell(c, L, {.mode = MODE_RESIDUAL, .x_base = L.fcg_x.base, .f_rows = L.fcg_b.rows, .out_rows = L.f.rows}));
     double bnorm = 0.0, rnorm = 0.0;
     MG_TRY(norm2(c, L, L.fcg_b.rows, &bnorm));
     MG_TRY(norm2(c, L, L.f.rows, &rnorm));
@@ -3135,7 +3135,8 @@ int fcg_solve(mg_context* c, int level, double rtol, int max_iter, double* hist,
             // q = A p with the partial sums of p.q
             MG_TRY(exchange_halo(c, L, L.fcg_p));
             unsigned nsp = 0;
-            MG_TRY(launch_ell(c, L, MODE_SPMV, true, L.fcg_p.base, nullptr, L.fcg_q.rows, c->fcg_spmv, nullptr, &nsp));
+            MG_TRY(launch_ell(c, L, {.mode = MODE_SPMV, .dot = true, .x_base = L.fcg_p.base, .out_rows = L.fcg_q.rows, .partials = c->fcg_spmv,
+                                     .grid_out = &nsp}));
             if ((int64_t)nsp > c->fcg_spmv_n) return fail("mg_pcg: SpMV partial sums overflow");
             const double* pq = c->fcg_spmv;
             int64_t npq = nsp;
@@ -3212,11 +3213,7 @@ int encode_level(mg_context* c, Level& L) {
         HIP_TRY(hipMemsetAsync(d_count, 0, 2 * sizeof(int), c->stream));
         const int64_t total = L.nslices * L.W * (WAVE * L.R);
         const dim3 grid(blocks_for(total, 256)), blk(256);
-        switch (L.R) {
-            case 1: hipLaunchKernelGGL(ell_collect_deltas<1>, grid, blk, 0, c->stream, L.cols, L.nslices, L.W, L.nloc, L.g.lead, d_table, d_count); break;
-            case 2: hipLaunchKernelGGL(ell_collect_deltas<2>, grid, blk, 0, c->stream, L.cols, L.nslices, L.W, L.nloc, L.g.lead, d_table, d_count); break;
-            default: hipLaunchKernelGGL(ell_collect_deltas<4>, grid, blk, 0, c->stream, L.cols, L.nslices, L.W, L.nloc, L.g.lead, d_table, d_count); break;
-        }
+        with_int_else<4, 1, 2>(L.R, [&](auto r) { hipLaunchKernelGGL(ell_collect_deltas<decltype(r)::value>, grid, blk, 0, c->stream, L.cols, L.nslices, L.W, L.nloc, L.g.lead, d_table, d_count); });
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(h_counts, d_count, 2 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipMemcpyAsync(h_table.data(), d_table, kDeltaSlots * sizeof(int), hipMemcpyDeviceToHost, c->stream));
@@ -3247,11 +3244,7 @@ int encode_level(mg_context* c, Level& L) {
     const int CW = (L.W + 7) / 8;
     MG_TRY(dev_alloc(c, &L.codes, (size_t)L.nslices * CW * (WAVE * L.R)));
     const dim3 grid(blocks_for(L.nslices * (WAVE * L.R), 256)), blk(256);
-    switch (L.R) {
-        case 1: hipLaunchKernelGGL(ell_encode<1>, grid, blk, 0, c->stream, L.cols, L.codes, L.nslices, L.W, L.nloc, L.g.lead, L.offsets, L.ntable, L.dcode); break;
-        case 2: hipLaunchKernelGGL(ell_encode<2>, grid, blk, 0, c->stream, L.cols, L.codes, L.nslices, L.W, L.nloc, L.g.lead, L.offsets, L.ntable, L.dcode); break;
-        default: hipLaunchKernelGGL(ell_encode<4>, grid, blk, 0, c->stream, L.cols, L.codes, L.nslices, L.W, L.nloc, L.g.lead, L.offsets, L.ntable, L.dcode); break;
-    }
+    with_int_else<4, 1, 2>(L.R, [&](auto r) { hipLaunchKernelGGL(ell_encode<decltype(r)::value>, grid, blk, 0, c->stream, L.cols, L.codes, L.nslices, L.W, L.nloc, L.g.lead, L.offsets, L.ntable, L.dcode); });
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(c->stream));
     dev_free(c, L.cols, (size_t)L.nslices * L.W * (WAVE * L.R));      // 4*W bytes per row back
@@ -3303,17 +3296,9 @@ int build_row_classes_q(mg_context* c, Level& L, int qbits) {
     std::vector<unsigned> hist(256, 0u);
     std::vector<double> tab(256 * CLS_W, 0.0);
     int rc = [&]() -> int {
-        switch (L.R) {
-            case 1: hipLaunchKernelGGL(cls_insert<64>, grid, blk, 0, c->stream, a); break;
-            case 2: hipLaunchKernelGGL(cls_insert<128>, grid, blk, 0, c->stream, a); break;
-            default: hipLaunchKernelGGL(cls_insert<256>, grid, blk, 0, c->stream, a); break;
-        }
+        with_int_else<4, 1, 2>(L.R, [&](auto r) { hipLaunchKernelGGL(cls_insert<64 * decltype(r)::value>, grid, blk, 0, c->stream, a); });
         hipLaunchKernelGGL(cls_assign, dim3(1), dim3(64), 0, c->stream, a);
-        switch (L.R) {
-            case 1: hipLaunchKernelGGL(cls_encode<64>, egrid, blk, 0, c->stream, a); break;
-            case 2: hipLaunchKernelGGL(cls_encode<128>, egrid, blk, 0, c->stream, a); break;
-            default: hipLaunchKernelGGL(cls_encode<256>, egrid, blk, 0, c->stream, a); break;
-        }
+        with_int_else<4, 1, 2>(L.R, [&](auto r) { hipLaunchKernelGGL(cls_encode<64 * decltype(r)::value>, egrid, blk, 0, c->stream, a); });
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(h, ints, 2 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipMemcpyAsync(hist.data(), a.hist, 256 * sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
@@ -3337,11 +3322,7 @@ int build_row_classes_q(mg_context* c, Level& L, int qbits) {
             HIP_TRY(hipMemsetAsync(scratch.p, 0, tag_bytes + val_bytes + int_bytes, c->stream));
             const int64_t nsample = std::min<int64_t>(L.nloc, (int64_t)1 << 20);
             const dim3 sgrid(blocks_for(nsample, 256));
-            switch (L.R) {
-                case 1: hipLaunchKernelGGL(cls_sample_insert<64>, sgrid, blk, 0, c->stream, a, nsample, slot_count, slot_count + CLS_SLOTS); break;
-                case 2: hipLaunchKernelGGL(cls_sample_insert<128>, sgrid, blk, 0, c->stream, a, nsample, slot_count, slot_count + CLS_SLOTS); break;
-                default: hipLaunchKernelGGL(cls_sample_insert<256>, sgrid, blk, 0, c->stream, a, nsample, slot_count, slot_count + CLS_SLOTS); break;
-            }
+            with_int_else<4, 1, 2>(L.R, [&](auto r) { hipLaunchKernelGGL(cls_sample_insert<64 * decltype(r)::value>, sgrid, blk, 0, c->stream, a, nsample, slot_count, slot_count + CLS_SLOTS); });
             HIP_TRY(hipGetLastError());
             std::vector<unsigned> cnt(CLS_SLOTS);
             std::vector<double> sv((size_t)CLS_SLOTS * CLS_W);
@@ -3360,11 +3341,7 @@ int build_row_classes_q(mg_context* c, Level& L, int qbits) {
             HIP_TRY(hipMemcpyAsync(a.slot_class, slot_class.data(), CLS_SLOTS * sizeof(int), hipMemcpyHostToDevice, c->stream));
             HIP_TRY(hipMemcpyAsync(ctab, tab.data(), 256 * CLS_W * sizeof(double), hipMemcpyHostToDevice, c->stream));
             HIP_TRY(hipMemsetAsync(a.hist, 0, 256 * sizeof(unsigned), c->stream));
-            switch (L.R) {
-                case 1: hipLaunchKernelGGL(cls_encode_escape<64>, egrid, blk, 0, c->stream, a); break;
-                case 2: hipLaunchKernelGGL(cls_encode_escape<128>, egrid, blk, 0, c->stream, a); break;
-                default: hipLaunchKernelGGL(cls_encode_escape<256>, egrid, blk, 0, c->stream, a); break;
-            }
+            with_int_else<4, 1, 2>(L.R, [&](auto r) { hipLaunchKernelGGL(cls_encode_escape<64 * decltype(r)::value>, egrid, blk, 0, c->stream, a); });
             HIP_TRY(hipGetLastError());
             HIP_TRY(hipMemcpyAsync(hist.data(), a.hist, 256 * sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
             HIP_TRY(hipStreamSynchronize(c->stream));
@@ -3479,14 +3456,12 @@ int build_stencil_classes(mg_context* c, Level& L) {
     const dim3 grid(blocks_for(L.nloc, 256)), blk(256);
     int h[2] = {0, 0};
     int rc = [&]() -> int {
-        switch (L.R) {
-            case 1: hipLaunchKernelGGL(scls_insert<1>, grid, blk, 0, c->stream, a); hipLaunchKernelGGL(scls_assign<1>, dim3(1), blk, 0, c->stream, a);
-                    hipLaunchKernelGGL(scls_encode<1>, grid, blk, 0, c->stream, a); break;
-            case 2: hipLaunchKernelGGL(scls_insert<2>, grid, blk, 0, c->stream, a); hipLaunchKernelGGL(scls_assign<2>, dim3(1), blk, 0, c->stream, a);
-                    hipLaunchKernelGGL(scls_encode<2>, grid, blk, 0, c->stream, a); break;
-            default: hipLaunchKernelGGL(scls_insert<4>, grid, blk, 0, c->stream, a); hipLaunchKernelGGL(scls_assign<4>, dim3(1), blk, 0, c->stream, a);
-                     hipLaunchKernelGGL(scls_encode<4>, grid, blk, 0, c->stream, a); break;
-        }
+        with_int_else<4, 1, 2>(L.R, [&](auto r) {
+            constexpr int R = decltype(r)::value;
+            hipLaunchKernelGGL(scls_insert<R>, grid, blk, 0, c->stream, a);
+            hipLaunchKernelGGL(scls_assign<R>, dim3(1), blk, 0, c->stream, a);
+            hipLaunchKernelGGL(scls_encode<R>, grid, blk, 0, c->stream, a);
+        });
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(h, ints, 2 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
@@ -3536,21 +3511,13 @@ int repack_sdia(mg_context* c, Level& L, int level) {
         unsigned long long* d_report = reinterpret_cast<unsigned long long*>(d_flag + 2);
         HIP_TRY(hipMemsetAsync(dvals, 0, (size_t)mslices * wu_t * S * sizeof(double), c->stream));
         const dim3 grid(blocks_for(L.nloc, 256)), blk(256);
-        switch (L.R) {
-            case 1: hipLaunchKernelGGL(sdia_fill<1>, grid, blk, 0, c->stream, a); break;
-            case 2: hipLaunchKernelGGL(sdia_fill<2>, grid, blk, 0, c->stream, a); break;
-            default: hipLaunchKernelGGL(sdia_fill<4>, grid, blk, 0, c->stream, a); break;
-        }
+        with_int_else<4, 1, 2>(L.R, [&](auto r) { hipLaunchKernelGGL(sdia_fill<decltype(r)::value>, grid, blk, 0, c->stream, a); });
         for (int attempt = 0; attempt < 2; ++attempt) {
             // ("storage_auto": pairs that differ by at most 4 units in the last place -- round-off of an assembly that sums its
             //  element contributions in varying order -- get a second try with that tolerance; the upper half of a pair is kept)
             HIP_TRY(hipMemsetAsync(d_flag, 0, 8, c->stream));
             HIP_TRY(hipMemcpyAsync(d_report, report, sizeof(report), hipMemcpyHostToDevice, c->stream));
-            switch (L.R) {
-                case 1: hipLaunchKernelGGL(sdia_check<1>, grid, blk, 0, c->stream, a, d_flag, qbits, d_report); break;
-                case 2: hipLaunchKernelGGL(sdia_check<2>, grid, blk, 0, c->stream, a, d_flag, qbits, d_report); break;
-                default: hipLaunchKernelGGL(sdia_check<4>, grid, blk, 0, c->stream, a, d_flag, qbits, d_report); break;
-            }
+            with_int_else<4, 1, 2>(L.R, [&](auto r) { hipLaunchKernelGGL(sdia_check<decltype(r)::value>, grid, blk, 0, c->stream, a, d_flag, qbits, d_report); });
             HIP_TRY(hipGetLastError());
             HIP_TRY(hipMemcpyAsync(&flag, d_flag, sizeof(int), hipMemcpyDeviceToHost, c->stream));
             HIP_TRY(hipMemcpyAsync(report, d_report, sizeof(report), hipMemcpyDeviceToHost, c->stream));
@@ -3603,12 +3570,10 @@ int alloc_ell(mg_context* c, Level& L) {
     MG_TRY(dev_alloc(c, &L.cols, ell));
     MG_TRY(dev_alloc(c, &L.dinv, (size_t)L.nslices * WAVE * L.R));
     const unsigned nb = blocks_for((int64_t)ell, 256);
-    switch (L.R) {
-        case 1: hipLaunchKernelGGL(ell_fill_padding<1>, dim3(nb), dim3(256), 0, c->stream, L.vals, L.cols, L.nslices, L.W, L.nloc, L.g.lead); break;
-        case 2: hipLaunchKernelGGL(ell_fill_padding<2>, dim3(nb), dim3(256), 0, c->stream, L.vals, L.cols, L.nslices, L.W, L.nloc, L.g.lead); break;
-        case 4: hipLaunchKernelGGL(ell_fill_padding<4>, dim3(nb), dim3(256), 0, c->stream, L.vals, L.cols, L.nslices, L.W, L.nloc, L.g.lead); break;
-        default: return fail("rows_per_lane must be 1, 2 or 4");
-    }
+    const bool known = with_int<1, 2, 4>(L.R, [&](auto r) {
+        hipLaunchKernelGGL(ell_fill_padding<decltype(r)::value>, dim3(nb), dim3(256), 0, c->stream, L.vals, L.cols, L.nslices, L.W, L.nloc, L.g.lead);
+    });
+    if (!known) return fail("rows_per_lane must be 1, 2 or 4");
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -4271,11 +4236,7 @@ int build_level_from_csr(mg_context* c, int level, Level& L, int64_t n_rows, int
     // pass 2: tiles
     MG_TRY(alloc_ell(c, L));
     const dim3 g1(blocks_for(n_rows, 256)), b1(256);
-    switch (L.R) {
-        case 1: hipLaunchKernelGGL(csr_to_ell<1>, g1, b1, 0, c->stream, a, L.vals, L.cols, L.dinv, L.W); break;
-        case 2: hipLaunchKernelGGL(csr_to_ell<2>, g1, b1, 0, c->stream, a, L.vals, L.cols, L.dinv, L.W); break;
-        default: hipLaunchKernelGGL(csr_to_ell<4>, g1, b1, 0, c->stream, a, L.vals, L.cols, L.dinv, L.W); break;
-    }
+    with_int_else<4, 1, 2>(L.R, [&](auto r) { hipLaunchKernelGGL(csr_to_ell<decltype(r)::value>, g1, b1, 0, c->stream, a, L.vals, L.cols, L.dinv, L.W); });
     HIP_TRY(hipGetLastError());
     // true non-zeros among the kept entries (== kept when pruned); counted on the caller's copy (set-up only)
     L.nnz_nonzero = L.nnz_stored;
@@ -4296,12 +4257,9 @@ int build_level_from_csr(mg_context* c, int level, Level& L, int64_t n_rows, int
 extern "C++" {
 template <int DIM>
 int launch_galerkin(mg_context* c, int fmt, const GalerkinArgs& a, dim3 grid) {
-    switch (fmt) {
-        case 0: hipLaunchKernelGGL((galerkin_p1<DIM, 0>), grid, dim3(kPlaneBlock), 0, c->stream, a); break;
-        case 1: hipLaunchKernelGGL((galerkin_p1<DIM, 1>), grid, dim3(kPlaneBlock), 0, c->stream, a); break;
-        case 2: hipLaunchKernelGGL((galerkin_p1<DIM, 2>), grid, dim3(kPlaneBlock), 0, c->stream, a); break;
-        default: hipLaunchKernelGGL((galerkin_p1<DIM, 3>), grid, dim3(kPlaneBlock), 0, c->stream, a); break;
-    }
+    with_int_else<3, 0, 1, 2>(fmt, [&](auto f) {
+        hipLaunchKernelGGL((galerkin_p1<DIM, decltype(f)::value>), grid, dim3(kPlaneBlock), 0, c->stream, a);
+    });
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -4359,7 +4317,9 @@ int galerkin_level(mg_context* c, int level) {
     a.flag = reinterpret_cast<int*>(c->partials);
     HIP_TRY(hipMemsetAsync(a.flag, 0, sizeof(int), c->stream));
     const dim3 grid = grid3(C.g, C.g.nk);
-    MG_TRY(c->dim == 3 ? launch_galerkin<3>(c, fmt, a, grid) : launch_galerkin<2>(c, fmt, a, grid));
+    int rc = 0;
+    with_int_else<2, 3>(c->dim, [&](auto dim) { rc = launch_galerkin<decltype(dim)::value>(c, fmt, a, grid); });
+    MG_TRY(rc);
     int flag = 0;
     HIP_TRY(hipMemcpyAsync(&flag, a.flag, sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -4462,11 +4422,7 @@ int mg_gen_poisson_level(mg_handle c, int level, int N, int prune_zeros) {
     return gen_stored_level(c, level, N, a.W, [&](const Level& L, dim3 grid, unsigned long long* counts) {
         const dim3 blk(kPlaneBlock);
         a.g = L.g;
-        switch (L.R) {
-            case 1: hipLaunchKernelGGL(gen_poisson<1>, grid, blk, 0, c->stream, a, L.vals, L.cols, L.dinv, L.f.rows, counts); break;
-            case 2: hipLaunchKernelGGL(gen_poisson<2>, grid, blk, 0, c->stream, a, L.vals, L.cols, L.dinv, L.f.rows, counts); break;
-            default: hipLaunchKernelGGL(gen_poisson<4>, grid, blk, 0, c->stream, a, L.vals, L.cols, L.dinv, L.f.rows, counts); break;
-        }
+        with_int_else<4, 1, 2>(L.R, [&](auto r) { hipLaunchKernelGGL(gen_poisson<decltype(r)::value>, grid, blk, 0, c->stream, a, L.vals, L.cols, L.dinv, L.f.rows, counts); });
     });
 }
 
@@ -4497,11 +4453,7 @@ int mg_gen_lattice_level(mg_handle c, int level, int N, int width, const int* co
     return gen_stored_level(c, level, N, width, [&](const Level& L, dim3 grid, unsigned long long* counts) {
         const dim3 blk(kPlaneBlock);
         a.g = L.g;
-        switch (L.R) {
-            case 1: hipLaunchKernelGGL(gen_lattice<1>, grid, blk, 0, c->stream, a, L.vals, L.cols, L.dinv, L.f.rows, counts); break;
-            case 2: hipLaunchKernelGGL(gen_lattice<2>, grid, blk, 0, c->stream, a, L.vals, L.cols, L.dinv, L.f.rows, counts); break;
-            default: hipLaunchKernelGGL(gen_lattice<4>, grid, blk, 0, c->stream, a, L.vals, L.cols, L.dinv, L.f.rows, counts); break;
-        }
+        with_int_else<4, 1, 2>(L.R, [&](auto r) { hipLaunchKernelGGL(gen_lattice<decltype(r)::value>, grid, blk, 0, c->stream, a, L.vals, L.cols, L.dinv, L.f.rows, counts); });
     });
 }
 
@@ -4548,11 +4500,7 @@ int gen_diffusion_level(mg_context* c, int level, int N, const double* d_kappa, 
     return gen_stored_level(c, level, N, d.ga.W, [&](const Level& L, dim3 grid, unsigned long long* counts) {
         const dim3 blk(kPlaneBlock);
         d.ga.g = L.g;
-        switch (L.R) {
-            case 1: hipLaunchKernelGGL(gen_diffusion<1>, grid, blk, 0, c->stream, d, L.vals, L.cols, L.dinv, L.f.rows, counts); break;
-            case 2: hipLaunchKernelGGL(gen_diffusion<2>, grid, blk, 0, c->stream, d, L.vals, L.cols, L.dinv, L.f.rows, counts); break;
-            default: hipLaunchKernelGGL(gen_diffusion<4>, grid, blk, 0, c->stream, d, L.vals, L.cols, L.dinv, L.f.rows, counts); break;
-        }
+        with_int_else<4, 1, 2>(L.R, [&](auto r) { hipLaunchKernelGGL(gen_diffusion<decltype(r)::value>, grid, blk, 0, c->stream, d, L.vals, L.cols, L.dinv, L.f.rows, counts); });
     });
 }
 
@@ -4919,7 +4867,7 @@ int mg_get_vector(mg_handle c, int level, int which, double* host, int gather) {
     MG_TRY(ensure_stage(c, L.n_global));
     ++c->downloads;
     const unsigned nb = (unsigned)std::min<int64_t>(4096, (L.n_global + 255) / 256);
-    if (gather && !L.replicated && c->comm.active()) {
+    if (gather && is_slab(c, L)) {
         // all-gather slabs in lexicographic order inside a scratch vector, then permute
         double* full = nullptr;
         MG_TRY(dev_alloc(c, &full, (size_t)L.n_global));
@@ -4936,7 +4884,7 @@ int mg_get_vector(mg_handle c, int level, int which, double* host, int gather) {
         HIP_TRY(hipMemcpy(host, c->stage, (size_t)L.n_global * 8, hipMemcpyDeviceToHost));
         return 0;
     }
-    if (!L.replicated && c->comm.active()) {
+    if (is_slab(c, L)) {
         // owned rows only: pre-load the caller's buffer so untouched entries survive
         HIP_TRY(hipMemcpyAsync(c->stage, host, (size_t)L.n_global * 8, hipMemcpyHostToDevice, c->stream));
     }
@@ -5047,11 +4995,11 @@ int mg_smooth_split(mg_handle c, int level, int nw) {
     if (nw < 0) return fail("nw must be >= 0");
     HIP_TRY(hipSetDevice(c->device));
     Level& L = c->L[level];
-    if (!L.replicated && c->comm.active()) return fail("mg_smooth_split is single-GPU only");
+    if (is_slab(c, L)) return fail("mg_smooth_split is single-GPU only");
     if (!L.err.raw) return fail("MG_VEC_ERR must hold the diagonal of D^-1");
     const unsigned nb = (unsigned)std::min<int64_t>(2048, (L.nloc + 255) / 256);
     for (int s = 0; s < nw; ++s) {
-        MG_TRY(launch_ell(c, L, MODE_SPMV, false, L.v.base, nullptr, L.v2.rows, nullptr, nullptr));
+        MG_TRY(launch_ell(c, L, level_op(L, MODE_SPMV)));
         hipLaunchKernelGGL(jacobi_split_combine, dim3(nb), dim3(256), 0, c->stream, L.v.rows, L.f.rows, L.err.rows,
                            L.v2.rows, L.v2.rows, L.nloc, c->omega);
         std::swap(L.v, L.v2);
@@ -5116,7 +5064,7 @@ int mg_quadratic_form(mg_handle c, int level, int which, double* out) {
     const unsigned grid = L.mf ? mf_plan(c, L).grid : blocks_for(L.nslices, WAVES_PER_BLOCK);
     double* parts = nullptr;
     MG_TRY(dev_alloc(c, &parts, grid));
-    int rc = launch_ell(c, L, MODE_SPMV, true, v->base, nullptr, L.v2.rows, parts, nullptr);
+    int rc = launch_ell(c, L, {.mode = MODE_SPMV, .dot = true, .x_base = v->base, .out_rows = L.v2.rows, .partials = parts});
     if (!rc) {
         hipLaunchKernelGGL(reduce_partials, dim3(1), dim3(BLOCK), 0, c->stream, parts, (int)grid, c->scalars);
         if (!L.replicated) rc = allreduce_sum(c, c->scalars, 1);
@@ -5149,14 +5097,15 @@ int mass_form(mg_context* c, Level& L, DVector& x, int slot) {
         double* parts = nullptr;
         MG_TRY(dev_alloc(c, &parts, nparts));
         unsigned grid = 0;
-        int rc = launch_ell(c, M, MODE_SPMV, true, x.base, nullptr, c->mass_out.rows, parts, nullptr, &grid);
+        int rc = launch_ell(c, M, {.mode = MODE_SPMV, .dot = true, .x_base = x.base, .out_rows = c->mass_out.rows, .partials = parts, .grid_out = &grid});
         if (!rc) hipLaunchKernelGGL(reduce_partials, dim3(1), dim3(BLOCK), 0, c->stream, parts, (int)grid, c->scalars + slot);
         if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) rc = fail("mass_form: stream error");
         dev_free(c, parts, nparts);
         MG_TRY(rc);
     } else {
         unsigned grid = 0;
-        MG_TRY(launch_ell(c, M, MODE_SPMV, true, x.base, nullptr, c->mass_out.rows, c->partials, nullptr, &grid));
+        MG_TRY(launch_ell(c, M, {.mode = MODE_SPMV, .dot = true, .x_base = x.base, .out_rows = c->mass_out.rows, .partials = c->partials,
+                                 .grid_out = &grid}));
         hipLaunchKernelGGL(reduce_partials, dim3(1), dim3(BLOCK), 0, c->stream, c->partials, (int)grid, c->scalars + slot);
     }
     HIP_TRY(hipGetLastError());
@@ -5373,15 +5322,27 @@ int mg_time_kernel(mg_handle c, const char* kernel, int level, int reps, double*
     HIP_TRY(hipEventCreate(&ev.e1));
     const hipEvent_t e0 = ev.e0, e1 = ev.e1;
     DevTemp ki_src, ki_coarse;      // "kappa_ingest": a copy of the level's kappa to read, a coarse field to write
+    // "diffusion_mf[:jacobi|:residual|:spmv|:chebyshev]": the matrix-free march in one mode, i.e. that kernel on a matrix-free level
+    // (timed as the operation `op` of that name, on a level that must be matrix-free)
+    const bool mf_key = k.rfind("diffusion_mf", 0) == 0;
+    const std::string mf_mode = !mf_key ? "" : k.size() > 12 ? k.substr(12) : ":jacobi";
+    const std::string op = !mf_key ? k : mf_mode[0] == ':' ? mf_mode.substr(1) : "";
+    // one step with x_{k-1} (the scalars of step 1 of a degree-2 polynomial on the level's interval)
+    auto cheb_step = [&]() -> int {
+        double lo = 0.0, hi = 0.0, al[2], be[2];
+        MG_TRY(cheb_interval(c, level, &lo, &hi));
+        cheb_steps(lo, hi, 2, al, be);
+        EllRequest step = level_op(L, MODE_CHEB);
+        step.alpha = al[1]; step.beta = be[1];
+        return launch_ell(c, L, step);
+    };
     auto once = [&]() -> int {
-        if (k == "jacobi") return launch_ell(c, L, MODE_JACOBI, false, L.v.base, L.f.rows, L.v2.rows, nullptr, nullptr);
-        if (k == "chebyshev") {     // one step with x_{k-1} (the scalars of step 1 of a degree-2 polynomial on the level's interval)
-            double lo = 0.0, hi = 0.0, al[2], be[2];
-            MG_TRY(cheb_interval(c, level, &lo, &hi));
-            cheb_steps(lo, hi, 2, al, be);
-            return launch_ell(c, L, MODE_CHEB, false, L.v.base, L.f.rows, L.v2.rows, nullptr, nullptr, nullptr, 0, -1, 0, 0, 0,
-                              al[1], be[1]);
-        }
+        if (mf_key && !L.mf) return fail("level is not a matrix-free diffusion level");
+        if (op == "jacobi") return launch_ell(c, L, level_op(L, MODE_JACOBI));
+        if (op == "chebyshev") return cheb_step();
+        if (op == "spmv") return launch_ell(c, L, level_op(L, MODE_SPMV));
+        if (op == "residual") return residual(c, level);
+        if (mf_key) return fail("unknown mode of diffusion_mf: " + mf_mode);
         // "jacobi2": only where mg_smooth itself pairs sweeps on this level; "jacobi2!": wherever the kernel applies
         if (k == "jacobi2" || k == "jacobi2!") {
             if (!fused_sweeps_ok(c, L, k == "jacobi2!")) return fail("level does not use the two-sweep kernel");
@@ -5392,7 +5353,7 @@ int mg_time_kernel(mg_handle c, const char* kernel, int level, int reps, double*
             const bool forced = k.find(":form") != std::string::npos;
             if (!sweepsk_ok(c, L, forced || k.find('!') != std::string::npos)) return fail("level does not use the K-sweep pass");
             c->timing_force_form = forced ? k.back() - '0' : -1;
-            const bool slab = !L.replicated && c->comm.active();
+            const bool slab = is_slab(c, L);
             if (slab && L.cls_halo != 1) return fail("the slab's class halos are not built yet (first smoother call)");
             const int rc = launch_jacobikc(c, L, slab ? std::min(std::min(c->fuse_k, 5), L.hd) : sweepsk_max(c, L), L.v.rows, L.f.rows, L.v2.rows);
             c->timing_force_form = -1;
@@ -5423,22 +5384,6 @@ int mg_time_kernel(mg_handle c, const char* kernel, int level, int reps, double*
             if (c->smoother == MG_SMOOTH_JACOBI) return fail("the configured smoother is Jacobi");
             return smooth(c, level, 1);
         }
-        if (k == "spmv") return launch_ell(c, L, MODE_SPMV, false, L.v.base, nullptr, L.v2.rows, nullptr, nullptr);
-        if (k.rfind("diffusion_mf", 0) == 0) {      // the matrix-free march in one mode: "diffusion_mf[:jacobi|:residual|:spmv|:chebyshev]"
-            if (!L.mf) return fail("level is not a matrix-free diffusion level");
-            const std::string m = k.size() > 12 ? k.substr(12) : ":jacobi";
-            if (m == ":jacobi") return launch_ell(c, L, MODE_JACOBI, false, L.v.base, L.f.rows, L.v2.rows, nullptr, nullptr);
-            if (m == ":residual") return residual(c, level);
-            if (m == ":spmv") return launch_ell(c, L, MODE_SPMV, false, L.v.base, nullptr, L.v2.rows, nullptr, nullptr);
-            if (m == ":chebyshev") {
-                double lo = 0.0, hi = 0.0, al[2], be[2];
-                MG_TRY(cheb_interval(c, level, &lo, &hi));
-                cheb_steps(lo, hi, 2, al, be);
-                return launch_ell(c, L, MODE_CHEB, false, L.v.base, L.f.rows, L.v2.rows, nullptr, nullptr, nullptr, 0, -1, 0, 0, 0,
-                                  al[1], be[1]);
-            }
-            return fail("unknown mode of diffusion_mf: " + m);
-        }
         if (k == "dkappa" || k == "dkappa_gather") {    // d(v^T A f) / d kappa: the plane march / one thread per cell, into MG_VEC_R
             MG_TRY(need_dkappa_level(c, level, "mg_time_kernel"));
             MG_TRY(vec_alloc(c, L, &L.v)); MG_TRY(vec_alloc(c, L, &L.f)); MG_TRY(vec_alloc(c, L, &L.v2));
@@ -5459,7 +5404,6 @@ int mg_time_kernel(mg_handle c, const char* kernel, int level, int reps, double*
             return launch_kappa_ingest(c, static_cast<const double*>(ki_src.p), L.kappa, static_cast<double*>(ki_coarse.p), L.N / 2,
                                        MG_KAPPA_ARITHMETIC);
         }
-        if (k == "residual") return residual(c, level);
         if (k == "restrict") return level > 0 ? restrict_to(c, level, c->restriction) : fail("level 0");
         if (k == "prolong") return level > 0 ? prolong(c, level, 1) : fail("level 0");
         if (k == "norm2") return dot_device(c, L, L.v.rows, L.v.rows, 1);

@@ -17,6 +17,34 @@ from multigrid_dolfinx_amd import _capi                              # noqa: E40
 from multigrid_dolfinx_amd.hierarchy import DeviceHierarchy          # noqa: E402
 
 
+# sweeps per pass of one smoother call of the K-sweep march on slabs: {(sweeps, most per pass): passes}
+KSLAB_PASSES = {(7, 4): [4, 3], (9, 4): [4, 3, 2], (5, 3): [3, 2], (11, 5): [5, 4, 2], (4, 2): [2, 2], (6, 4): [4, 2]}
+
+
+def expected_kslab_passes(N, index, world, mu, tune, overlap):
+    """The passes of one call of `mu` sweeps on the slabs of a level (N elements per dimension, level `index` of the
+    handle) and the launches they take, by the library's rules: the most sweeps per pass while that leaves no single
+    sweep over, at least two; with the overlap on, a pass is two launches (the planes the neighbours wait for go first)
+    where the thinnest slab has at least 4 e + 8 planes, e the planes that travel after the pass (the next pass's
+    sweeps, one after the last).  `overlap_min_rows` is 0 here and one halo plane is exchanged."""
+    N0 = N >> index
+    cuts = [((r * N0) // world) << index for r in range(world)] + [N + 1]
+    thinnest = min(b - a for a, b in zip(cuts, cuts[1:]))
+    kmax = min(tune.get("fuse_k", 5), 5, max(1, min(tune.get("halo_depth", 0), (N0 // world) << index)))
+
+    def next_pass(left):
+        k = kmax if left >= kmax + 2 or left == kmax else kmax - 1 if left == kmax + 1 else left
+        return max(2, min(k, kmax)) if left >= 2 else 0
+
+    passes, left = [], mu
+    while next_pass(left):
+        passes.append(next_pass(left))
+        left -= passes[-1]
+    assert passes == KSLAB_PASSES.get((mu, kmax), passes), (mu, kmax, passes)
+    travel = passes[1:] + [1]
+    return passes, sum(2 if overlap and thinnest >= 4 * e + 8 else 1 for e in travel)
+
+
 def main(world, dim, lo, hi, c, mu, replicate_below, overlap):
     assert "fake_rccl" in os.environ.get("MG_RCCL_LIBRARY", "")
     buf = C.create_string_buffer(128)
@@ -50,6 +78,9 @@ def main(world, dim, lo, hi, c, mu, replicate_below, overlap):
                 # (fuse_k_slab_min_sweeps 2: every pass of the call, the last pair included)
                 ran = h.smoother_launches(hi)
                 assert set(ran) == {"ksweep_slab"} and ran["ksweep_slab"][1] == mu, ran
+                # ... in the passes the split rule gives, each one launch, or two where the boundary planes go first
+                passes, launches = expected_kslab_passes(h.elements(hi), hi - lo, world, mu, tune, overlap)
+                assert ran["ksweep_slab"][0] == launches, (ran, passes, launches)
             h.prepare_cycle(hi)
             phase(h)
             h.zero_vector(hi, "v")
