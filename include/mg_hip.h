@@ -287,6 +287,26 @@ int mg_diffusion_dkappa(mg_handle h, int level, const double* a_dev, const doubl
  * Refused with an error before anything is launched: 2-D handles, slab handles, flat levels, null pointers, pointers that
  * are not device memory of the handle's device, and an out_dev that overlaps x_dev or dkappa_dev (the march reads neighbours). */
 int mg_diffusion_apply_dkappa(mg_handle h, int level, const double* dkappa_dev, const double* x_dev, double* out_dev);
+/* The two operators above with the mask of each side chosen by the caller (no reference counterpart): what a lifted
+ * inhomogeneous Dirichlet load -A_IB(kappa) g and its derivatives are written with.  A^(w) is the natural P1 stiffness matrix
+ * of a cell field w on all (N + 1)^3 nodes of the Kuhn mesh, without boundary condition: an axis edge e of cell c carries
+ * n_{c,e} w_c h / 6 (the weights of mg_gen_diffusion_level, whose matrix has the interior block of A^(kappa)).  M_set is the mask
+ * that zeroes the boundary nodes (MG_NODES_INTERIOR) or the identity (MG_NODES_ALL):
+ *     mg_diffusion_apply_dkappa_ex: out = T(w, x; rows, cols) = M_rows A^(w) M_cols x
+ *     mg_diffusion_dkappa_ex:       out[c] = D(a, b; a_nodes, b_nodes)_c = d / d w_c (M_a a)^T A^(w) (M_b b)
+ * (interior, interior) gives the bits of the two entries above.  A boundary row of T (rows = all) is the row of A^, summed as an
+ * interior row is with a cell outside the grid counting as +0.0 and a neighbour outside it reading 0; with rows = interior it is
+ * +0.0.  cols = interior zeroes every entry whose column is a boundary node, a boundary row's own diagonal included.  D applies
+ * its masks where a node is loaded; one pointer may be passed as a and b with different sets.  They close under
+ * differentiation: T with cotangent y gives w_bar = D(y, x; rows, cols) and x_bar = T(w, y; cols, rows); D with cotangent w gives
+ * a_bar = T(w, b; a_nodes, b_nodes) and b_bar = T(w, a; b_nodes, a_nodes).  The lift of Dirichlet data g is
+ * T(kappa, g_B; interior, all) with g_B = g on the boundary and 0 inside; poisson.diffusion_lift restates it.
+ * Pointers, stream, synchronisation, cell and node order and the refusals are those of the two entries above; a node set
+ * other than 0 or 1 is refused as well.  Nothing is launched by a refused call. */
+enum mg_node_set { MG_NODES_INTERIOR = 0, MG_NODES_ALL = 1 };
+int mg_diffusion_dkappa_ex(mg_handle h, int level, const double* a_dev, int a_nodes, const double* b_dev, int b_nodes, double* out_dev);
+int mg_diffusion_apply_dkappa_ex(mg_handle h, int level, const double* dkappa_dev, const double* x_dev, int rows, int cols,
+                                 double* out_dev);
 /* getJacobiMatrices (multigrid.py:48-56) as a stand-alone set-up kernel, for callers that
  * want the reference's split operands back: for every stored entry a_ij of the CSR matrix
  * writes scaled[q] = a_ij / a_ii computed as (1/a_ii) * a_ij, keep[q] = 1 unless the entry
@@ -677,6 +697,8 @@ int mg_reset_smoother_launches(mg_handle h);
  * ":residual", ":spmv", ":chebyshev" = the matrix-free diffusion march in that mode, an error on stored levels;
  * "dkappa" / "dkappa_gather" = mg_diffusion_dkappa of (MG_VEC_V, MG_VEC_F) into MG_VEC_R as the plane march / one thread per cell;
  * "apply_dkappa" = mg_diffusion_apply_dkappa with dkappa = the first N^3 entries of MG_VEC_F and x = MG_VEC_V, into MG_VEC_R;
+ * "dkappa:all" / "apply_dkappa:all" = the same operands through mg_diffusion_dkappa_ex / mg_diffusion_apply_dkappa_ex with both
+ * node sets MG_NODES_ALL;
  * "kappa_ingest" = one launch of the fused copy and coarsening of mg_gen_diffusion_hierarchy_device on a matrix-free level, from a
  * scratch copy of its kappa back into the level's own (the same bytes: the level is unchanged) and into a scratch coarse field,
  * arithmetic averaging; an error on stored levels).

@@ -19,6 +19,7 @@ MG_RESTRICT_INJECTION, MG_RESTRICT_FULL_WEIGHTING, MG_RESTRICT_TABLE, MG_RESTRIC
 MG_SMOOTH_JACOBI, MG_SMOOTH_RBGS, MG_SMOOTH_MCGS, MG_SMOOTH_CHEBYSHEV = 0, 1, 2, 3
 MG_NORM_L2, MG_NORM_MASS = 0, 1
 MG_KAPPA_ARITHMETIC, MG_KAPPA_HARMONIC = 0, 1
+MG_NODES_INTERIOR, MG_NODES_ALL = 0, 1
 # enum mg_smoother_path, in its order (mg_smoother_launches)
 SMOOTHER_PATHS = ("slice", "sweep1c", "pair_class", "pair_plain", "ksweep", "ksweep_escape", "ksweep_slab", "block", "k2d",
                   "small", "matrix_free")
@@ -81,6 +82,8 @@ SIGNATURES = {
     "mg_get_vector_device": [_H, C.c_int, C.c_int, C.c_void_p],
     "mg_diffusion_dkappa": [_H, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
     "mg_diffusion_apply_dkappa": [_H, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
+    "mg_diffusion_dkappa_ex": [_H, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p],
+    "mg_diffusion_apply_dkappa_ex": [_H, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p],
     "mg_zero_vector": [_H, C.c_int, C.c_int],
     "mg_copy_vector": [_H, C.c_int, C.c_int, C.c_int],
     "mg_smooth": [_H, C.c_int, C.c_int],

@@ -888,12 +888,18 @@ int launch_diffusion_mf(mg_context* c, const Level& L, int mode, bool dot, const
     return 0;
 }
 
-// out = (dA/dkappa . dkappa) x on a whole 3-D grid level: the SpMV march with kappa := dkappa and +0.0 on boundary rows
-// (diffusion_mf<MODE_SPMV, false, true>).  Reads the grid only; dkappa, x, out: the caller's, lexicographic, out != x.
-int launch_apply_dkappa(mg_context* c, const Level& L, const double* dkappa, const double* x, double* out) {
+// out = M_rows A^(dkappa) M_cols x on a whole 3-D grid level: the SpMV march with kappa := dkappa (diffusion_mf<MODE_SPMV, false,
+// true, rows_all, cols_all>); (interior, interior) is (dA/dkappa . dkappa) x with +0.0 on boundary rows.  Reads the grid only;
+// dkappa, x, out: the caller's, lexicographic, out != x.
+int launch_apply_dkappa(mg_context* c, const Level& L, const double* dkappa, const double* x, double* out, bool rows_all = false,
+                        bool cols_all = false) {
     const MfPlan p = mf_plan(c, L);
     const MfArgs a = mf_args(p, L, dkappa, x, out);
-    hipLaunchKernelGGL((diffusion_mf<MODE_SPMV, false, true>), dim3(p.grid), dim3(MF_NT), 0, c->stream, a);
+    const dim3 grid(p.grid), blk(MF_NT);
+    if (rows_all && cols_all) hipLaunchKernelGGL((diffusion_mf<MODE_SPMV, false, true, true, true>), grid, blk, 0, c->stream, a);
+    else if (rows_all) hipLaunchKernelGGL((diffusion_mf<MODE_SPMV, false, true, true, false>), grid, blk, 0, c->stream, a);
+    else if (cols_all) hipLaunchKernelGGL((diffusion_mf<MODE_SPMV, false, true, false, true>), grid, blk, 0, c->stream, a);
+    else hipLaunchKernelGGL((diffusion_mf<MODE_SPMV, false, true>), grid, blk, 0, c->stream, a);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -912,11 +918,14 @@ int launch_diffusion_rhs(mg_context* c, const Level& L, const double* d_kappa, d
     return 0;
 }
 
-// out[cell] = d(a^T A(kappa) b) / d kappa_cell on a whole 3-D grid level (mg_diffusion_adj.hip.h); a, b: lexicographic nodes
-int launch_dkappa(mg_context* c, const Level& L, const double* a, const double* b, double* out, bool gather) {
+// out[cell] = d(a^T A(kappa) b) / d kappa_cell on a whole 3-D grid level (mg_diffusion_adj.hip.h); a, b: lexicographic nodes,
+// their boundary entries taken as 0 unless a_all / b_all
+int launch_dkappa(mg_context* c, const Level& L, const double* a, const double* b, double* out, bool gather, bool a_all = false,
+                  bool b_all = false) {
     DkMarchArgs m{};
     DkArgs& d = m.d;
     d.a = a; d.b = b; d.out = out;
+    d.a_all = a_all; d.b_all = b_all;
     d.nx = L.g.nx; d.ny = L.g.ny; d.nz = L.g.nz; d.N = L.N; d.P = L.g.plane;
     d.scale = (1.0 / (double)L.N) / 6.0;
     if (gather) {
@@ -4929,25 +4938,19 @@ int mg_get_vector_device(mg_handle c, int level, int which, double* dev) {
     return 0;
 }
 
-int mg_diffusion_dkappa(mg_handle c, int level, const double* a_dev, const double* b_dev, double* out_dev) {
-    MG_TRY(need_dkappa_level(c, level, "mg_diffusion_dkappa"));
-    HIP_TRY(hipSetDevice(c->device));
-    MG_TRY(need_device_pointer(c, a_dev, "mg_diffusion_dkappa", "a"));
-    MG_TRY(need_device_pointer(c, b_dev, "mg_diffusion_dkappa", "b"));
-    MG_TRY(need_device_pointer(c, out_dev, "mg_diffusion_dkappa", "out"));
-    MG_TRY(launch_dkappa(c, c->L[level], a_dev, b_dev, out_dev, c->dkappa_gather != 0));
-    HIP_TRY(hipStreamSynchronize(c->stream));
+// the pointer checks of the two sensitivity entries; nothing is launched before they pass
+static int need_dkappa_operands(mg_context* c, const char* who, const double* a_dev, const double* b_dev, double* out_dev) {
+    MG_TRY(need_device_pointer(c, a_dev, who, "a"));
+    MG_TRY(need_device_pointer(c, b_dev, who, "b"));
+    MG_TRY(need_device_pointer(c, out_dev, who, "out"));
     return 0;
 }
 
-int mg_diffusion_apply_dkappa(mg_handle c, int level, const double* dkappa_dev, const double* x_dev, double* out_dev) {
-    const char* who = "mg_diffusion_apply_dkappa";
-    MG_TRY(need_dkappa_level(c, level, who));
-    HIP_TRY(hipSetDevice(c->device));
+static int need_apply_dkappa_operands(mg_context* c, const Level& L, const char* who, const double* dkappa_dev, const double* x_dev,
+                                      double* out_dev) {
     MG_TRY(need_device_pointer(c, dkappa_dev, who, "dkappa"));
     MG_TRY(need_device_pointer(c, x_dev, who, "x"));
     MG_TRY(need_device_pointer(c, out_dev, who, "out"));
-    const Level& L = c->L[level];
     // the march reads the neighbours of a row (and of a cell) while other workgroups write theirs
     const size_t nodes = (size_t)L.g.plane * (size_t)L.g.nz * 8, cells = (size_t)L.N * L.N * L.N * 8;
     const auto overlaps = [](const void* p, size_t np, const void* q, size_t nq) {
@@ -4956,7 +4959,58 @@ int mg_diffusion_apply_dkappa(mg_handle c, int level, const double* dkappa_dev, 
     };
     if (overlaps(out_dev, nodes, x_dev, nodes)) return fail(std::string(who) + ": out overlaps x (the march reads a row's neighbours)");
     if (overlaps(out_dev, nodes, dkappa_dev, cells)) return fail(std::string(who) + ": out overlaps dkappa (the march reads a row's cells)");
+    return 0;
+}
+
+static int need_node_set(const char* who, const char* what, int value) {
+    if (value != MG_NODES_INTERIOR && value != MG_NODES_ALL)
+        return fail(std::string(who) + ": " + what + " = " + std::to_string(value) +
+                    " is no node set (MG_NODES_INTERIOR = 0, MG_NODES_ALL = 1)");
+    return 0;
+}
+
+int mg_diffusion_dkappa(mg_handle c, int level, const double* a_dev, const double* b_dev, double* out_dev) {
+    MG_TRY(need_dkappa_level(c, level, "mg_diffusion_dkappa"));
+    HIP_TRY(hipSetDevice(c->device));
+    MG_TRY(need_dkappa_operands(c, "mg_diffusion_dkappa", a_dev, b_dev, out_dev));
+    MG_TRY(launch_dkappa(c, c->L[level], a_dev, b_dev, out_dev, c->dkappa_gather != 0));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int mg_diffusion_dkappa_ex(mg_handle c, int level, const double* a_dev, int a_nodes, const double* b_dev, int b_nodes, double* out_dev) {
+    const char* who = "mg_diffusion_dkappa_ex";
+    MG_TRY(need_dkappa_level(c, level, who));
+    MG_TRY(need_node_set(who, "a_nodes", a_nodes));
+    MG_TRY(need_node_set(who, "b_nodes", b_nodes));
+    HIP_TRY(hipSetDevice(c->device));
+    MG_TRY(need_dkappa_operands(c, who, a_dev, b_dev, out_dev));
+    MG_TRY(launch_dkappa(c, c->L[level], a_dev, b_dev, out_dev, c->dkappa_gather != 0, a_nodes == MG_NODES_ALL, b_nodes == MG_NODES_ALL));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int mg_diffusion_apply_dkappa(mg_handle c, int level, const double* dkappa_dev, const double* x_dev, double* out_dev) {
+    const char* who = "mg_diffusion_apply_dkappa";
+    MG_TRY(need_dkappa_level(c, level, who));
+    HIP_TRY(hipSetDevice(c->device));
+    const Level& L = c->L[level];
+    MG_TRY(need_apply_dkappa_operands(c, L, who, dkappa_dev, x_dev, out_dev));
     MG_TRY(launch_apply_dkappa(c, L, dkappa_dev, x_dev, out_dev));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int mg_diffusion_apply_dkappa_ex(mg_handle c, int level, const double* dkappa_dev, const double* x_dev, int rows, int cols,
+                                 double* out_dev) {
+    const char* who = "mg_diffusion_apply_dkappa_ex";
+    MG_TRY(need_dkappa_level(c, level, who));
+    MG_TRY(need_node_set(who, "rows", rows));
+    MG_TRY(need_node_set(who, "cols", cols));
+    HIP_TRY(hipSetDevice(c->device));
+    const Level& L = c->L[level];
+    MG_TRY(need_apply_dkappa_operands(c, L, who, dkappa_dev, x_dev, out_dev));
+    MG_TRY(launch_apply_dkappa(c, L, dkappa_dev, x_dev, out_dev, rows == MG_NODES_ALL, cols == MG_NODES_ALL));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return 0;
 }
@@ -5384,15 +5438,19 @@ int mg_time_kernel(mg_handle c, const char* kernel, int level, int reps, double*
             if (c->smoother == MG_SMOOTH_JACOBI) return fail("the configured smoother is Jacobi");
             return smooth(c, level, 1);
         }
-        if (k == "dkappa" || k == "dkappa_gather") {    // d(v^T A f) / d kappa: the plane march / one thread per cell, into MG_VEC_R
+        // d(v^T A f) / d kappa: the plane march / one thread per cell, into MG_VEC_R (":all": both vectors with their boundary entries)
+        if (k == "dkappa" || k == "dkappa_gather" || k == "dkappa:all") {
             MG_TRY(need_dkappa_level(c, level, "mg_time_kernel"));
             MG_TRY(vec_alloc(c, L, &L.v)); MG_TRY(vec_alloc(c, L, &L.f)); MG_TRY(vec_alloc(c, L, &L.v2));
-            return launch_dkappa(c, L, L.v.rows, L.f.rows, L.v2.rows, k == "dkappa_gather");
+            const bool all = k == "dkappa:all";
+            return launch_dkappa(c, L, L.v.rows, L.f.rows, L.v2.rows, k == "dkappa_gather", all, all);
         }
-        if (k == "apply_dkappa") {  // (dA/dkappa . f[:N^3]) v: the SpMV march with kappa := the direction, into MG_VEC_R
+        // (dA/dkappa . f[:N^3]) v: the SpMV march with kappa := the direction, into MG_VEC_R (":all": every row and column of A^)
+        if (k == "apply_dkappa" || k == "apply_dkappa:all") {
             MG_TRY(need_dkappa_level(c, level, "mg_time_kernel"));
             MG_TRY(vec_alloc(c, L, &L.v)); MG_TRY(vec_alloc(c, L, &L.f)); MG_TRY(vec_alloc(c, L, &L.v2));
-            return launch_apply_dkappa(c, L, L.f.rows, L.v.rows, L.v2.rows);
+            const bool all = k == "apply_dkappa:all";
+            return launch_apply_dkappa(c, L, L.f.rows, L.v.rows, L.v2.rows, all, all);
         }
         if (k == "kappa_ingest") {  // the copy and the coarsening in one pass, from a scratch copy of kappa back into the level's own
             if (!L.mf) return fail("level is not a matrix-free diffusion level");

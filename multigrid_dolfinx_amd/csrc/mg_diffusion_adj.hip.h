@@ -21,6 +21,11 @@
 // One thread per cell; a cell needs its eight corners of a and of b, read through the caches (sixteen loads, each node
 // shared by up to eight cells of neighbouring threads and planes).  Model: 8 + 8 B per node read, 8 B per cell written.
 // Nodes on the boundary are not loaded at all: the mask is the zero.
+//
+// mg_diffusion_dkappa_ex takes the mask per vector (a_all, b_all): out[c] = d / d w_c (M_A a)^T A^(w) (M_B b) with A^ the
+// natural P1 matrix of a cell field on all nodes (no boundary condition) and M the mask of the interior nodes or the
+// identity.  The mask acts where a node is loaded and nowhere else: dk_cell and its adds are the same, and (interior,
+// interior) is mg_diffusion_dkappa to the bit.  An unmasked vector is read at every corner: all of them are on the grid.
 #pragma once
 #include "mg_kernels.hip.h"
 
@@ -35,7 +40,11 @@ struct DkArgs {
     int nx, ny, nz, N;      // nodes per axis (N + 1 each), cells per axis
     int64_t P;              // nx * ny
     double scale;           // h / 6.0
+    int a_all, b_all;       // 0: the boundary entries of the vector count as 0 (not loaded); 1: every node is read
 };
+
+// one pointer passed twice is loaded once -- where both vectors are masked alike, or the one mask would serve the other
+__device__ __forceinline__ bool dk_same(const DkArgs& p) { return p.a == p.b && p.a_all == p.b_all; }
 
 __device__ __forceinline__ double dk_cell(const double (&A)[2][2][2], const double (&B)[2][2][2], double scale) {
     double s = 2.0 * ((A[0][0][1] - A[0][0][0]) * (B[0][0][1] - B[0][0][0]));
@@ -58,7 +67,7 @@ __global__ __launch_bounds__(DK_BLOCK) void diffusion_dkappa_gather(DkArgs p) {
     const int64_t t = (int64_t)blockIdx.x * DK_BLOCK + threadIdx.x;
     if (t >= (int64_t)p.N * p.N) return;
     const int ci = (int)(t % p.N), cj = (int)(t / p.N), ck = blockIdx.y;
-    const bool same = p.a == p.b;
+    const bool same = dk_same(p);
     double A[2][2][2], B[2][2][2];
 #pragma unroll
     for (int dz = 0; dz < 2; ++dz)
@@ -69,8 +78,8 @@ __global__ __launch_bounds__(DK_BLOCK) void diffusion_dkappa_gather(DkArgs p) {
                 const int i = ci + dx, j = cj + dy, k = ck + dz;
                 const bool inner = i >= 1 && i <= p.nx - 2 && j >= 1 && j <= p.ny - 2 && k >= 1 && k <= p.nz - 2;
                 const int64_t r = (int64_t)k * p.P + (int64_t)j * p.nx + i;
-                A[dz][dy][dx] = inner ? p.a[r] : 0.0;
-                B[dz][dy][dx] = inner ? (same ? A[dz][dy][dx] : p.b[r]) : 0.0;
+                A[dz][dy][dx] = inner || p.a_all ? p.a[r] : 0.0;
+                B[dz][dy][dx] = inner || p.b_all ? (same ? A[dz][dy][dx] : p.b[r]) : 0.0;
             }
     p.out[(int64_t)ck * p.N * p.N + t] = dk_cell(A, B, p.scale);
 }
@@ -108,25 +117,28 @@ __global__ __launch_bounds__(MF_NT) void diffusion_dkappa_march(DkMarchArgs m) {
     const int tx0 = tix * MF_TX, ty0 = tiy * MF_TY;
     const int ci = tx0 + lx, cj = ty0 + ly;
     const bool on_grid = ci < p.N && cj < p.N;
-    const bool same = p.a == p.b;
+    const bool same = dk_same(p);
 
-    // the elements of an image this thread fills: e = tid and tid + MF_NT; -1: a boundary node or outside the grid (0)
+    // the elements of an image this thread fills: e = tid and tid + MF_NT; -1: outside the grid (0); ni: an interior node of
+    // its plane (a masked vector reads no other)
     int64_t no[2];
     int ne[2];
+    bool ni[2];
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
         const int e = tid + q * MF_NT;
         ne[q] = e < DK_S ? e : -1;
         const int i = tx0 + e % DK_W, j = ty0 + e / DK_W;
-        no[q] = (e < DK_S && i >= 1 && i <= p.nx - 2 && j >= 1 && j <= p.ny - 2) ? (int64_t)j * p.nx + i : -1;
+        no[q] = (e < DK_S && i <= p.nx - 1 && j <= p.ny - 1) ? (int64_t)j * p.nx + i : -1;
+        ni[q] = i >= 1 && i <= p.nx - 2 && j >= 1 && j <= p.ny - 2;
     }
     auto load = [&](int plane, double (&va)[2], double (&vb)[2]) {
-        const bool ok = plane >= 1 && plane <= p.nz - 2;
+        const bool on = plane >= 0 && plane <= p.nz - 1, ok = plane >= 1 && plane <= p.nz - 2;
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
-            const bool in = ok && no[q] >= 0;
-            va[q] = in ? p.a[(int64_t)plane * p.P + no[q]] : 0.0;
-            vb[q] = in ? (same ? va[q] : p.b[(int64_t)plane * p.P + no[q]]) : 0.0;
+            const bool in = on && no[q] >= 0, inner = ok && ni[q];
+            va[q] = in && (inner || p.a_all) ? p.a[(int64_t)plane * p.P + no[q]] : 0.0;
+            vb[q] = in && (inner || p.b_all) ? (same ? va[q] : p.b[(int64_t)plane * p.P + no[q]]) : 0.0;
         }
     };
     auto park = [&](int plane, const double (&va)[2], const double (&vb)[2]) {

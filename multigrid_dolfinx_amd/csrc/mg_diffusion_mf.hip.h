@@ -32,6 +32,15 @@
 // TANGENT (MODE_SPMV only) is the derivative of that product in a direction of kappa, out = (dA/dkappa . dkappa) x
 // (mg_diffusion_apply_dkappa): A is linear in kappa, so an interior row is the same row with kappa := dkappa, of any sign,
 // and a boundary row -- the identity block does not depend on kappa -- is +0.0.  Everything else is the SpMV.
+//
+// ROWS_ALL / COLS_ALL (TANGENT only; mg_diffusion_apply_dkappa_ex) lift the two masks of that product one by one:
+// out = M_rows A^(dkappa) M_cols x with A^ the natural P1 matrix of the cell field on all nodes, no boundary condition.
+//   * ROWS_ALL: a boundary row is the row of A^ -- the same edge sums, diagonal sum, weights and fma chain, a cell outside
+//     the grid counting as +0.0 (the kappa image is padded with 0.0 instead of 1.0; interior rows never read the pad) and a
+//     neighbour outside the grid reading 0.  Without it a boundary row is +0.0 as above.
+//   * COLS_ALL keeps the entries towards boundary neighbours.  Without it every entry whose column is a boundary node is
+//     a zero in the chain: the six neighbours' and, on a boundary row, the row's own diagonal.
+// <false, false> is the kernel above, expression for expression.
 #pragma once
 #include "mg_kernels.hip.h"
 
@@ -64,9 +73,11 @@ __device__ __forceinline__ double mf_div6(double t) {
     return fma(r, c, q);
 }
 
-template <int MODE, bool DOT, bool TANGENT = false>
+template <int MODE, bool DOT, bool TANGENT = false, bool ROWS_ALL = false, bool COLS_ALL = false>
 __global__ __launch_bounds__(MF_NT) void diffusion_mf(MfArgs a) {
     static_assert(!TANGENT || (MODE == MODE_SPMV && !DOT), "the tangent is a plain SpMV with kappa := dkappa");
+    static_assert(TANGENT || (!ROWS_ALL && !COLS_ALL), "only the tangent has rows and columns on the boundary");
+    constexpr double KPAD = ROWS_ALL ? 0.0 : 1.0;       // a cell outside the grid
     __shared__ double sX[4][MF_XS];
     __shared__ double sK[3][MF_KS];
     __shared__ double s_part[MF_NT / WAVE];
@@ -91,7 +102,7 @@ __global__ __launch_bounds__(MF_NT) void diffusion_mf(MfArgs a) {
         const bool inner_ij = gi >= 1 && gi <= a.nx - 2 && gj >= 1 && gj <= a.ny - 2;
         const int64_t row_ij = (int64_t)gj * a.nx + gi;
 
-        // the elements of the images this thread loads: e = tid and tid + MF_NT; -1: outside the grid (x: 0, kappa: 1)
+        // the elements of the images this thread loads: e = tid and tid + MF_NT; -1: outside the grid (x: 0, kappa: KPAD)
         int64_t xo[2], ko[2];
         int xe[2], ke[2];
 #pragma unroll
@@ -113,7 +124,7 @@ __global__ __launch_bounds__(MF_NT) void diffusion_mf(MfArgs a) {
         auto load_k = [&](int cplane, double (&v)[2]) {
             const bool ok = cplane >= 0 && cplane < a.N;
 #pragma unroll
-            for (int q = 0; q < 2; ++q) v[q] = ok && ko[q] >= 0 ? a.kappa[(int64_t)cplane * KP + ko[q]] : 1.0;
+            for (int q = 0; q < 2; ++q) v[q] = ok && ko[q] >= 0 ? a.kappa[(int64_t)cplane * KP + ko[q]] : KPAD;
         };
         auto park_x = [&](int plane, const double (&v)[2]) {
             double* const s = sX[(plane + 4) & 3];
@@ -165,7 +176,7 @@ __global__ __launch_bounds__(MF_NT) void diffusion_mf(MfArgs a) {
             const double* const xc = sX[(k + 1) & 3];
             const double x0 = xb[cx];
             double acc = 0.0, diag = 1.0;
-            if (inner_ij && k >= 1 && k <= a.nz - 2) {
+            if (ROWS_ALL ? on_grid : inner_ij && k >= 1 && k <= a.nz - 2) {
                 const double* const k0 = sK[(k + 2) % 3];   // cell plane k-1
                 const double* const k1 = sK[k % 3];
                 double K[2][2][2];      // K[dz][dy][dx]: cell (gi - 1 + dx, gj - 1 + dy, k - 1 + dz)
@@ -192,17 +203,33 @@ __global__ __launch_bounds__(MF_NT) void diffusion_mf(MfArgs a) {
                 double t = se[2][0];
                 t = t + se[1][0]; t = t + se[0][0]; t = t + se[0][1]; t = t + se[1][1]; t = t + se[2][1];
                 diag = mf_div6(t) * hh;
-                // the stored entries -w, zero where the neighbour lies on the boundary
-                const double azl = k - 1 == 0 ? 0.0 : -(mf_div6(se[2][0]) * hh);
-                const double ayl = gj - 1 == 0 ? 0.0 : -(mf_div6(se[1][0]) * hh);
-                const double axl = gi - 1 == 0 ? 0.0 : -(mf_div6(se[0][0]) * hh);
-                const double axu = gi + 1 == a.nx - 1 ? 0.0 : -(mf_div6(se[0][1]) * hh);
-                const double ayu = gj + 1 == a.ny - 1 ? 0.0 : -(mf_div6(se[1][1]) * hh);
-                const double azu = k + 1 == a.nz - 1 ? 0.0 : -(mf_div6(se[2][1]) * hh);
+                double azl, ayl, axl, axu, ayu, azu, ad = diag;
+                if constexpr (!ROWS_ALL && !COLS_ALL) {
+                    // the stored entries -w, zero where the neighbour lies on the boundary
+                    azl = k - 1 == 0 ? 0.0 : -(mf_div6(se[2][0]) * hh);
+                    ayl = gj - 1 == 0 ? 0.0 : -(mf_div6(se[1][0]) * hh);
+                    axl = gi - 1 == 0 ? 0.0 : -(mf_div6(se[0][0]) * hh);
+                    axu = gi + 1 == a.nx - 1 ? 0.0 : -(mf_div6(se[0][1]) * hh);
+                    ayu = gj + 1 == a.ny - 1 ? 0.0 : -(mf_div6(se[1][1]) * hh);
+                    azu = k + 1 == a.nz - 1 ? 0.0 : -(mf_div6(se[2][1]) * hh);
+                } else {
+                    // the entries of A^: -w, where columns are masked zero towards a boundary node -- a neighbour is one if it
+                    // has stepped onto (or past) a face or if the row itself lies on a face of another axis
+                    const bool bi = ROWS_ALL && (gi < 1 || gi > a.nx - 2), bj = ROWS_ALL && (gj < 1 || gj > a.ny - 2);
+                    const bool bz = ROWS_ALL && (k < 1 || k > a.nz - 2);
+                    const bool mask = !COLS_ALL;
+                    azl = mask && (bi || bj || k - 1 <= 0) ? 0.0 : -(mf_div6(se[2][0]) * hh);
+                    ayl = mask && (bi || bz || gj - 1 <= 0) ? 0.0 : -(mf_div6(se[1][0]) * hh);
+                    axl = mask && (bj || bz || gi - 1 <= 0) ? 0.0 : -(mf_div6(se[0][0]) * hh);
+                    axu = mask && (bj || bz || gi + 1 >= a.nx - 1) ? 0.0 : -(mf_div6(se[0][1]) * hh);
+                    ayu = mask && (bi || bz || gj + 1 >= a.ny - 1) ? 0.0 : -(mf_div6(se[1][1]) * hh);
+                    azu = mask && (bi || bj || k + 1 >= a.nz - 1) ? 0.0 : -(mf_div6(se[2][1]) * hh);
+                    if (mask && (bi || bj || bz)) ad = 0.0;
+                }
                 acc = fma(azl, xa[cx], acc);
                 acc = fma(ayl, xb[cx - MF_XW], acc);
                 acc = fma(axl, xb[cx - 1], acc);
-                acc = fma(diag, x0, acc);
+                acc = fma(ad, x0, acc);
                 acc = fma(axu, xb[cx + 1], acc);
                 acc = fma(ayu, xb[cx + MF_XW], acc);
                 acc = fma(azu, xc[cx], acc);

@@ -28,6 +28,7 @@ _VEC = {"v": MG_VEC_V, "f": MG_VEC_F, "r": MG_VEC_R, "err": MG_VEC_ERR}
 _RESTRICT = {"direct": MG_RESTRICT_INJECTION, "injection": MG_RESTRICT_INJECTION,
              "full_weighting": MG_RESTRICT_FULL_WEIGHTING, "table": _capi.MG_RESTRICT_TABLE,
              "p1_transpose": _capi.MG_RESTRICT_P1_TRANSPOSE}
+_NODE_SETS = {"interior": _capi.MG_NODES_INTERIOR, "all": _capi.MG_NODES_ALL}
 
 
 def _csr_arrays(A):
@@ -606,19 +607,35 @@ class DeviceHierarchy:
         address `dev_ptr`; the handle's stream has finished when this returns."""
         check(self._lib.mg_get_vector_device(self._h, self._idx(level), _VEC[which], C.c_void_p(int(dev_ptr))))
 
-    def diffusion_dkappa(self, level: int, a, b, out=None):
+    @staticmethod
+    def _node_sets(**sets):
+        """The values of `enum mg_node_set` for "interior" / "all", or None where every set is "interior": the call the
+        entries without node sets serve."""
+        for what, name in sets.items():
+            if name not in _NODE_SETS:
+                raise ValueError(f"{what} must be 'interior' or 'all' (got {name!r})")
+        values = [_NODE_SETS[name] for name in sets.values()]
+        return values if any(values) else None
+
+    def diffusion_dkappa(self, level: int, a, b, out=None, a_nodes: str = "interior", b_nodes: str = "interior"):
         """d(a^T A(kappa) b) / d kappa for every cell of a 3-D grid level (`mg_diffusion_dkappa`; host restatement:
         `poisson.diffusion_dkappa`).  `a`, `b` (lexicographic nodal values, boundary entries count as 0) and `out`
         (`elements(level) ** 3` cells) are integer device addresses -- `out` is then required and nothing is returned --
         or, for tests, NumPy arrays, which are uploaded, and the result comes back as a NumPy array (into `out` if
-        given).  `a is b` passes the same pointer twice."""
+        given).  `a is b` passes the same pointer twice.  `a_nodes`, `b_nodes`: "all" keeps the boundary entries of that
+        vector (`mg_diffusion_dkappa_ex`: the derivative of (M_A a)^T A^ (M_B b) with the natural matrix A^); the defaults
+        call `mg_diffusion_dkappa`."""
+        sets = self._node_sets(a_nodes=a_nodes, b_nodes=b_nodes)
+        if sets is None:
+            entry = lambda pa, pb, po: self._lib.mg_diffusion_dkappa(self._h, self._idx(level), pa, pb, po)
+        else:
+            entry = lambda pa, pb, po: self._lib.mg_diffusion_dkappa_ex(self._h, self._idx(level), pa, sets[0], pb, sets[1], po)
         cells = self.elements(level) ** 3
         integers = [isinstance(x, (int, np.integer)) for x in (a, b)]
         if all(integers):
             if not isinstance(out, (int, np.integer)):
                 raise TypeError("with device addresses for a and b, out must be a device address too")
-            check(self._lib.mg_diffusion_dkappa(self._h, self._idx(level), C.c_void_p(int(a)), C.c_void_p(int(b)),
-                                                C.c_void_p(int(out))))
+            check(entry(C.c_void_p(int(a)), C.c_void_p(int(b)), C.c_void_p(int(out))))
             return None
         if any(integers) or isinstance(out, (int, np.integer)):
             raise TypeError("a, b and out must be all device addresses or all NumPy arrays")
@@ -628,7 +645,7 @@ class DeviceHierarchy:
             held.append(_DeviceArray(self._lib, self.device, n, _capi.as_f64(a, n)))
             held.append(held[0] if b is a else _DeviceArray(self._lib, self.device, n, _capi.as_f64(b, n)))
             held.append(_DeviceArray(self._lib, self.device, cells))
-            check(self._lib.mg_diffusion_dkappa(self._h, self._idx(level), held[0].ptr, held[1].ptr, held[2].ptr))
+            check(entry(held[0].ptr, held[1].ptr, held[2].ptr))
             got = held[2].download()
         finally:
             for d in held:
@@ -638,19 +655,25 @@ class DeviceHierarchy:
         out.reshape(-1)[:] = got
         return out
 
-    def diffusion_apply_dkappa(self, level: int, dkappa, x, out=None):
+    def diffusion_apply_dkappa(self, level: int, dkappa, x, out=None, rows: str = "interior", cols: str = "interior"):
         """(dA/dkappa . dkappa) x on a 3-D grid level, the derivative of A(kappa) x in the direction `dkappa`
         (`mg_diffusion_apply_dkappa`; host restatement: `poisson.diffusion_apply_dkappa`).  `dkappa`
         (`elements(level) ** 3` cells, any sign), `x` and `out` (lexicographic nodal values; boundary rows of `out` are 0)
         are integer device addresses -- `out` is then required, must not overlap the inputs, and nothing is returned -- or,
-        for tests, NumPy arrays, which are uploaded, and the result comes back as a NumPy array (into `out` if given)."""
+        for tests, NumPy arrays, which are uploaded, and the result comes back as a NumPy array (into `out` if given).
+        `rows`, `cols`: "all" keeps the boundary rows / the entries towards boundary columns of the natural matrix A^
+        (`mg_diffusion_apply_dkappa_ex`: M_rows A^(dkappa) M_cols x); the defaults call `mg_diffusion_apply_dkappa`."""
+        sets = self._node_sets(rows=rows, cols=cols)
+        if sets is None:
+            entry = lambda pk, px, po: self._lib.mg_diffusion_apply_dkappa(self._h, self._idx(level), pk, px, po)
+        else:
+            entry = lambda pk, px, po: self._lib.mg_diffusion_apply_dkappa_ex(self._h, self._idx(level), pk, px, sets[0], sets[1], po)
         cells = self.elements(level) ** 3
         integers = [isinstance(v, (int, np.integer)) for v in (dkappa, x)]
         if all(integers):
             if not isinstance(out, (int, np.integer)):
                 raise TypeError("with device addresses for dkappa and x, out must be a device address too")
-            check(self._lib.mg_diffusion_apply_dkappa(self._h, self._idx(level), C.c_void_p(int(dkappa)), C.c_void_p(int(x)),
-                                                      C.c_void_p(int(out))))
+            check(entry(C.c_void_p(int(dkappa)), C.c_void_p(int(x)), C.c_void_p(int(out))))
             return None
         if any(integers) or isinstance(out, (int, np.integer)):
             raise TypeError("dkappa, x and out must be all device addresses or all NumPy arrays")
@@ -660,7 +683,7 @@ class DeviceHierarchy:
             held.append(_DeviceArray(self._lib, self.device, cells, _capi.as_f64(dkappa, cells)))
             held.append(_DeviceArray(self._lib, self.device, n, _capi.as_f64(x, n)))
             held.append(_DeviceArray(self._lib, self.device, n))
-            check(self._lib.mg_diffusion_apply_dkappa(self._h, self._idx(level), held[0].ptr, held[1].ptr, held[2].ptr))
+            check(entry(held[0].ptr, held[1].ptr, held[2].ptr))
             got = held[2].download()
         finally:
             for d in held:

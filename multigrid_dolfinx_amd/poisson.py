@@ -684,7 +684,16 @@ def coarsen_kappa(kappa, dim: int, averaging: str = "arithmetic") -> np.ndarray:
     return np.ascontiguousarray(out.reshape(-1))
 
 
-def diffusion_dkappa(N: int, a, b) -> np.ndarray:
+_NODE_SETS = ("interior", "all")
+
+
+def _node_set_all(name, what: str) -> bool:
+    if name not in _NODE_SETS:
+        raise ValueError(f"{what} must be 'interior' or 'all' (got {name!r})")
+    return name == "all"
+
+
+def diffusion_dkappa(N: int, a, b, a_nodes: str = "interior", b_nodes: str = "interior") -> np.ndarray:
     """d(a^T A(kappa) b) / d kappa_c for the N^3 cells of the 3-D `diffusion_level`, as `mg_diffusion_dkappa` computes it (same
     bits: explicit adds in the order of `dk_cell`, mg_diffusion_adj.hip.h).  `a`, `b`: nodal values in lexicographic order;
     their boundary entries count as 0 (boundary rows are identity rows and interior rows have no boundary column: that block
@@ -692,19 +701,25 @@ def diffusion_dkappa(N: int, a, b) -> np.ndarray:
     corners (dz, dy, dx), an axis edge contributes (A~_upper - A~_lower) * (B~_upper - B~_lower), times 2 where the cell's two
     other local coordinates at the edge are equal; the x edges at (dz, dy) = (0,0), (0,1), (1,0), (1,1), then the y edges at
     (dz, dx), then the z edges at (dy, dx) are added one by one and the sum is scaled by (1 / N) / 6.  Flat array in the cell
-    order of `diffusion_level`."""
+    order of `diffusion_level`.
+
+    `a_nodes`, `b_nodes` ("interior" / "all") are the masks of `mg_diffusion_dkappa_ex`, D(a, b; A, B)_c =
+    d / d w_c (M_A a)^T A^(w) (M_B b) with A^ = `diffusion_natural_matrix`: "all" keeps the boundary entries of that
+    vector.  The mask acts on the values at the corners and nowhere else, so these are the device's bits as well."""
     n1 = N + 1
 
-    def corners(x):
+    def corners(x, keep_boundary):
         v = np.array(x, dtype=np.float64).reshape(-1)
         if v.size != n1 ** 3:
             raise ValueError(f"vector has {v.size} entries, the level has {n1 ** 3} nodes")
         v = v.reshape(n1, n1, n1)
-        m = np.zeros_like(v)
-        m[1:-1, 1:-1, 1:-1] = v[1:-1, 1:-1, 1:-1]
+        m = v
+        if not keep_boundary:
+            m = np.zeros_like(v)
+            m[1:-1, 1:-1, 1:-1] = v[1:-1, 1:-1, 1:-1]
         return [[[m[dz:dz + N, dy:dy + N, dx:dx + N] for dx in (0, 1)] for dy in (0, 1)] for dz in (0, 1)]
 
-    A, B = corners(a), corners(b)
+    A, B = corners(a, _node_set_all(a_nodes, "a_nodes")), corners(b, _node_set_all(b_nodes, "b_nodes"))
     edge = lambda hi, lo: (A[hi[0]][hi[1]][hi[2]] - A[lo[0]][lo[1]][lo[2]]) * (B[hi[0]][hi[1]][hi[2]] - B[lo[0]][lo[1]][lo[2]])
     s = None
     for axis in (0, 1, 2):                      # x, y, z edges; (p, q): the two other coordinates, slower one first
@@ -723,7 +738,7 @@ def diffusion_dkappa(N: int, a, b) -> np.ndarray:
     return np.ascontiguousarray((s * ((1.0 / N) / 6.0)).reshape(-1))
 
 
-def diffusion_apply_dkappa(N: int, dkappa, x) -> np.ndarray:
+def diffusion_apply_dkappa(N: int, dkappa, x, rows: str = "interior", cols: str = "interior") -> np.ndarray:
     """(dA/dkappa . dkappa) x for the 3-D `diffusion_level`: the derivative of A(kappa) x in the direction `dkappa` (N^3 values in
     the cell order of `diffusion_level`, of any sign), as `mg_diffusion_apply_dkappa` computes it.  A is linear in kappa, so an
     interior row is the row of `diffusion_level` with kappa := dkappa -- the edge sums and the diagonal sum in its order,
@@ -732,28 +747,89 @@ def diffusion_apply_dkappa(N: int, dkappa, x) -> np.ndarray:
     The same operations in the same order, but NumPy has no fma: every product here is rounded before its add, on the
     device it is not, so this restates the kernel to a rounding bound (a few ulps of the sum of the absolute values of a
     row's terms), not to the bit.  `x`: nodal values in lexicographic order, boundary entries included (an interior row has
-    no boundary column, so they do not count)."""
+    no boundary column, so they do not count).
+
+    `rows`, `cols` ("interior" / "all") are the masks of `mg_diffusion_apply_dkappa_ex`, T(w, x; R, C) = M_R A^(w) M_C x with
+    A^ = `diffusion_natural_matrix`.  rows = "all": a boundary row is the row of A^, summed like an interior row with a cell
+    outside the grid counting as 0 and a neighbour outside it reading 0.  cols = "all" keeps the entries towards boundary
+    neighbours; cols = "interior" zeroes every entry whose column is a boundary node, a boundary row's own diagonal
+    included."""
     n1 = N + 1
+    rows_all, cols_all = _node_set_all(rows, "rows"), _node_set_all(cols, "cols")
     dk = _kappa_cells(dkappa, N, 3)
     v = np.array(x, dtype=np.float64).reshape(-1)
     if v.size != n1 ** 3:
         raise ValueError(f"vector has {v.size} entries, the level has {n1 ** 3} nodes")
     h = 1.0 / N
-    se, t = _edge_sums_3d(np.pad(dk, 1, constant_values=1.0), n1)
+    se, t = _edge_sums_3d(np.pad(dk, 1, constant_values=0.0 if rows_all else 1.0), n1)
     idx = np.arange(n1 ** 3, dtype=np.int64)
     ijk = [idx % n1, (idx // n1) % n1, idx // (n1 * n1)]
-    inner = np.ones(n1 ** 3, dtype=bool)
-    for c in ijk:
-        inner &= (c >= 1) & (c <= N - 1)
+    on_face = [(c < 1) | (c > N - 1) for c in ijk]
+    inner = ~(on_face[0] | on_face[1] | on_face[2])
     strides = (1, n1, n1 * n1)
     xp = np.concatenate([np.zeros(strides[2]), v, np.zeros(strides[2])])       # a neighbour outside the grid reads 0
     nb = lambda delta: xp[strides[2] + delta:strides[2] + delta + v.size]
+
+    def masked(axis, stepped_onto_face):
+        """Is the column of the neighbour along `axis` a boundary node that `cols` masks?"""
+        if cols_all:
+            return np.zeros(n1 ** 3, dtype=bool)
+        others = [on_face[d] for d in range(3) if d != axis]
+        return stepped_onto_face | others[0] | others[1]
+
     acc = np.zeros(n1 ** 3)
     for axis in (2, 1, 0):                      # z-, y-, x-
-        a = np.where(ijk[axis] - 1 == 0, 0.0, -((se[axis][0] / 6.0) * h))
+        a = np.where(masked(axis, ijk[axis] - 1 <= 0), 0.0, -((se[axis][0] / 6.0) * h))
         acc = a * nb(-strides[axis]) + acc
-    acc = ((t / 6.0) * h) * v + acc
+    acc = np.where(inner | cols_all, (t / 6.0) * h, 0.0) * v + acc
     for axis in (0, 1, 2):                      # x+, y+, z+
-        a = np.where(ijk[axis] + 1 == N, 0.0, -((se[axis][1] / 6.0) * h))
+        a = np.where(masked(axis, ijk[axis] + 1 >= N), 0.0, -((se[axis][1] / 6.0) * h))
         acc = a * nb(strides[axis]) + acc
-    return np.where(inner, acc, 0.0)
+    return acc if rows_all else np.where(inner, acc, 0.0)
+
+
+def diffusion_natural_matrix(N: int, cells) -> sp.csr_matrix:
+    """A^(w): the natural P1 stiffness matrix of the cell field `cells` (N^3 values of any sign, cell order of `diffusion_level`)
+    on all (N + 1)^3 nodes of the Kuhn mesh, lexicographic, without boundary condition.  Assembled cell by cell (vectorised
+    over the cells): each of a cell's twelve axis edges e = (i, j) adds n_{c,e} w_c h / 6 to (i, i) and (j, j) and its negative
+    to (i, j) and (j, i), n = 2 where the cell's two other local coordinates at the edge are equal, else 1 -- the weights of
+    `diffusion_level`, whose interior block this matrix shares up to the order of the adds.  Rows sum to zero."""
+    w = _kappa_cells(cells, N, 3)
+    n1 = N + 1
+    h = 1.0 / N
+    ck, cj, ci = np.meshgrid(np.arange(N), np.arange(N), np.arange(N), indexing="ij")
+    node = lambda dx, dy, dz: (((ck + dz) * n1 + (cj + dy)) * n1 + (ci + dx)).reshape(-1)
+    wc = w.reshape(-1)
+    lower, upper, vals = [], [], []
+    for axis in range(3):
+        for p in (0, 1):
+            for q in (0, 1):                    # (p, q): the two other coordinates, slower one first
+                if axis == 0:
+                    lo, hi = (0, q, p), (1, q, p)
+                elif axis == 1:
+                    lo, hi = (q, 0, p), (q, 1, p)
+                else:
+                    lo, hi = (q, p, 0), (q, p, 1)
+                lower.append(node(*lo))
+                upper.append(node(*hi))
+                vals.append(((2.0 if p == q else 1.0) * wc) * h / 6.0)
+    i, j, we = np.concatenate(lower), np.concatenate(upper), np.concatenate(vals)
+    shape = (n1 ** 3, n1 ** 3)
+    above = sp.coo_matrix((-we, (i, j)), shape=shape).tocsr()       # i < j; its transpose has the same sums: A^ is symmetric to the bit
+    diagonal = sp.coo_matrix((np.concatenate([we, we]), (np.concatenate([i, j]), np.concatenate([i, j]))), shape=shape).tocsr()
+    A = (diagonal + above + above.T).tocsr()
+    A.sort_indices()
+    return A
+
+
+def diffusion_lift(N: int, kappa, g) -> np.ndarray:
+    """A_IB(kappa) g_B on interior rows, 0 on boundary rows: T(kappa, g_B; interior, all) with g_B = `g` on the boundary and 0
+    inside.  The right-hand side of -div(kappa grad u) = f with u = g on the boundary is f - lift on interior rows (and g on
+    the identity rows), as `diffusion_level` folds `boundary_data` into its own."""
+    n1 = N + 1
+    gv = np.array(g, dtype=np.float64).reshape(-1)
+    if gv.size != n1 ** 3:
+        raise ValueError(f"vector has {gv.size} entries, the level has {n1 ** 3} nodes")
+    gb = gv.reshape(n1, n1, n1).copy()
+    gb[1:-1, 1:-1, 1:-1] = 0.0
+    return diffusion_apply_dkappa(N, kappa, gb.reshape(-1), "interior", "all")

@@ -1,5 +1,5 @@
-"""Differentiable solves of -div(kappa grad u) = f on the device: `DiffusionSolver.solve(kappa, f) -> u` with gradients
-with respect to kappa and f by the adjoint method.
+"""Differentiable solves of -div(kappa grad u) = f, u = g on the boundary, on the device:
+`DiffusionSolver.solve(kappa, f, g) -> u` with gradients with respect to kappa, f and g by the adjoint method.
 
 The only module of the package that imports torch.  Tensors enter and leave `libmg_hip.so` by device pointer
 (`mg_set_vector_device`, `mg_get_vector_device`, `mg_diffusion_dkappa`).  So does a kappa that lives on the solver's
@@ -44,10 +44,16 @@ class DiffusionSolver:
     """u(kappa, f) = A(kappa)^-1 f for the P1 matrix of -div(kappa grad u) on the unit cube with N^3 cells
     (`poisson.diffusion_level`), solved by `mg_pcg` on a hierarchy of `n_levels` generated levels with P1 transfers.
 
-    Contract: `f` is the FULL right-hand side in lexicographic node order, boundary entries included.  Boundary rows are
-    identity rows, so u_b = f_b, and interior rows have no boundary column.  A lifted inhomogeneous Dirichlet load (the
-    -a_ib g_b terms that `mg_gen_diffusion_level` folds into its own right-hand side) depends on kappa itself; that
-    dependence is the caller's: build the lifted f from kappa with differentiable torch operations if it matters.
+    Contract: without `g`, `f` is the FULL right-hand side in lexicographic node order, boundary entries included.  Boundary
+    rows are identity rows, so u_b = f_b, and interior rows have no boundary column.  With Dirichlet data `g` ((N + 1)^3
+    float64 on the solver's device; only its boundary entries are read, its interior gets a zero gradient) the right-hand
+    side is where(boundary, g, f - T(kappa, g_B; interior, all)): the lifted load -A_IB(kappa) g_B that
+    `mg_gen_diffusion_level` folds into its own right-hand side, g_B = g on the boundary and 0 inside, and u_b = g_b.  The
+    lift depends on kappa, and it is written with the autograd functions below (T and D with a node set per side,
+    `mg_diffusion_apply_dkappa_ex` / `mg_diffusion_dkappa_ex`), so the gradients with respect to kappa, f and g and their
+    second derivatives come out of `torch.autograd` with no solve beyond those counted below: grad_kappa =
+    -D(lambda~, u; interior, all), grad_g = (grad_u - A^ lambda~) on the boundary.  The boundary entries of `f` do not
+    count then.  A kappa on the CPU goes to the device for the lift by a differentiable `.to`.
 
     `kappa`: N^3 positive float64, cell (ci, cj, ck) at (ck * N + cj) * N + ci, any shape, on the CPU (uploaded, every
     level regenerated) or on the solver's device (it stays there: the first solve generates, later ones refresh in
@@ -94,6 +100,7 @@ class DiffusionSolver:
         self.warm_start = bool(warm_start)
         self._warm = {}                 # "forward" / "adjoint": the last solution of that kind (warm_start)
         self._last_operator = None      # the _Operator of the last `solve`: what `tangent` solves again on
+        self._boundary = None           # the mask of the boundary nodes on the device (solves with g)
         self.n_solves = 0               # mg_pcg calls so far: what a product costs (a Hessian-vector product: four)
         self.last_iterations = {}       # "forward" / "adjoint" / "tangent": iterations of the last solve of that kind
         self.last_residual = {}         # ... and ||r|| / ||rhs|| of mg_pcg's recursion where it stopped (None: no iteration was needed)
@@ -107,18 +114,44 @@ class DiffusionSolver:
     def __exit__(self, *exc):
         self.close()
 
-    def solve(self, kappa: torch.Tensor, f: torch.Tensor) -> torch.Tensor:
-        return _Solve.apply(kappa, f, self, None, "forward", True)
+    def solve(self, kappa: torch.Tensor, f: torch.Tensor, g: Optional[torch.Tensor] = None) -> torch.Tensor:
+        if g is None:
+            return _Solve.apply(kappa, f, self, None, "forward", True)
+        boundary = self._boundary_mask()
+        gv, fv = self._same_size(g, "g").reshape(-1), self._same_size(f, "f").reshape(-1)
+        g_b = torch.where(boundary, gv, torch.zeros_like(gv))
+        op = self._put_operator(kappa)      # first: the lift runs on the level's grid, which the first generation sets
+        lift = _Tangent.apply(kappa.reshape(-1).to(self.device), g_b, self, "interior", "all")
+        rhs = torch.where(boundary, gv, fv - lift)
+        return _Solve.apply(kappa, rhs.view(f.shape), self, op, "forward", True)
 
-    def tangent(self, kappa: torch.Tensor, f: torch.Tensor, dkappa: torch.Tensor, df: Optional[torch.Tensor] = None):
+    def tangent(self, kappa: torch.Tensor, f: torch.Tensor, dkappa: torch.Tensor, df: Optional[torch.Tensor] = None,
+                g: Optional[torch.Tensor] = None, dg: Optional[torch.Tensor] = None):
         """(u, du): u = A(kappa)^-1 f and its derivative in the direction (dkappa, df),
         du = A^-1 (df - (dA/dkappa . dkappa) u), on the same operator: two solves, one generation.  The cheap derivative
         when kappa depends on a few parameters.  `kappa` as in `solve`; `f`, `dkappa` (N^3 float64, any sign) and `df`
-        (None: zero) on the solver's device.  The second solve counts as "tangent" in `last_iterations`."""
-        u = self.solve(kappa, f)
-        rhs = _Tangent.apply(dkappa.reshape(-1), u.reshape(-1), self).neg()
-        if df is not None:
-            rhs = self._same_size(df, "df").reshape(-1) + rhs
+        (None: zero) on the solver's device.  The second solve counts as "tangent" in `last_iterations`.
+        With Dirichlet data `g` as in `solve` and its direction `dg` (None: zero; boundary entries only): the interior rows of
+        the second right-hand side are df - T(dkappa, u; interior, all) - T(kappa, dg_B; interior, all), u with its boundary
+        values g, and du = dg on the boundary."""
+        if g is None and dg is not None:
+            raise ValueError("dg is the direction of g: it needs g")
+        u = self.solve(kappa, f, g)
+        if g is None:
+            rhs = _Tangent.apply(dkappa.reshape(-1), u.reshape(-1), self, "interior", "interior").neg()
+            if df is not None:
+                rhs = self._same_size(df, "df").reshape(-1) + rhs
+        else:
+            boundary = self._boundary_mask()
+            rhs = _Tangent.apply(dkappa.reshape(-1), u.reshape(-1), self, "interior", "all").neg()
+            if df is not None:
+                rhs = self._same_size(df, "df").reshape(-1) + rhs
+            on_boundary = torch.zeros_like(rhs)
+            if dg is not None:
+                on_boundary = self._same_size(dg, "dg").reshape(-1)
+                dg_b = torch.where(boundary, on_boundary, torch.zeros_like(on_boundary))
+                rhs = rhs - _Tangent.apply(kappa.detach().reshape(-1).to(self.device), dg_b, self, "interior", "all")
+            rhs = torch.where(boundary, on_boundary, rhs)
         du = _Solve.apply(kappa, rhs, self, self._last_operator, "tangent", True)
         return u, du.view(u.shape)
 
@@ -140,6 +173,27 @@ class DiffusionSolver:
         self._generated = True
         self._generation += 1
         return self._generation
+
+    def _boundary_mask(self) -> torch.Tensor:
+        """True on the boundary nodes, (N + 1)^3 lexicographic, on the solver's device (built by the first solve with g)."""
+        if self._boundary is None:
+            n1 = self.N + 1
+            m = torch.ones((n1, n1, n1), dtype=torch.bool, device=self.device)
+            m[1:-1, 1:-1, 1:-1] = False
+            self._boundary = m.reshape(-1)
+        return self._boundary
+
+    def _put_operator(self, kappa: torch.Tensor) -> "_Operator":
+        """Puts the caller's kappa into the hierarchy: the operator of a `solve` and of what derives from it."""
+        if kappa.dtype != torch.float64 or kappa.numel() != self.N ** 3:
+            raise ValueError(f"kappa must hold {self.N ** 3} float64")
+        if kappa.device == self.device:   # no .cpu(): a device copy that the caller's later updates do not reach feeds the library
+            kappa_kept = kappa.detach().reshape(-1).clone()
+        else:
+            kappa_kept = np.ascontiguousarray(kappa.detach().cpu().numpy().reshape(-1))
+        op = _Operator(kappa_kept, self._generate(kappa_kept))
+        self._last_operator = op
+        return op
 
     def _same_size(self, x: torch.Tensor, what: str) -> torch.Tensor:
         n = self.hierarchy.n_dofs(self.top)
@@ -193,14 +247,7 @@ class _Solve(torch.autograd.Function):
     def forward(ctx, kappa, f, solver, op, which, warm):
         rhs = solver._device_vector(f, "f" if op is None else "the right-hand side")
         if op is None:
-            if kappa.dtype != torch.float64 or kappa.numel() != solver.N ** 3:
-                raise ValueError(f"kappa must hold {solver.N ** 3} float64")
-            if kappa.device == solver.device:   # no .cpu(): a device copy that the caller's later updates do not reach feeds the library
-                kappa_kept = kappa.detach().reshape(-1).clone()
-            else:
-                kappa_kept = np.ascontiguousarray(kappa.detach().cpu().numpy().reshape(-1))
-            op = _Operator(kappa_kept, solver._generate(kappa_kept))
-            solver._last_operator = op
+            op = solver._put_operator(kappa)
         elif op.generation != solver._generation:       # another kappa has been solved since: this one's operator again
             op.generation = solver._generate(op.kappa_kept)
         u = solver._pcg(rhs, which, warm).view(f.shape)
@@ -223,51 +270,54 @@ class _Solve(torch.autograd.Function):
         grad_kappa = None
         if ctx.needs_input_grad[0]:
             shape, device = ctx.kappa_like
-            grad_kappa = _DKappa.apply(lam, u, solver).neg().view(shape).to(device)
+            grad_kappa = _DKappa.apply(lam, u, solver, "interior", "interior").neg().view(shape).to(device)
         grad_f = lam if ctx.needs_input_grad[1] else None
         return grad_kappa, grad_f, None, None, None, None
 
 
 class _DKappa(torch.autograd.Function):
-    """D(a, b) = mg_diffusion_dkappa(a, b), N^3 cells.  With cotangent w: a_bar = T(w, b), b_bar = T(w, a)."""
+    """D(a, b; A, B) = mg_diffusion_dkappa(a, b) with a node set per vector ("interior": the boundary entries count as 0),
+    N^3 cells.  With cotangent w: a_bar = T(w, b; A, B), b_bar = T(w, a; B, A)."""
 
     @staticmethod
-    def forward(ctx, a, b, solver):
+    def forward(ctx, a, b, solver, a_nodes, b_nodes):
         av, bv = solver._device_vector(a, "a"), solver._device_vector(b, "b")
         out = torch.empty(solver.N ** 3, dtype=torch.float64, device=solver.device)
         torch.cuda.current_stream(solver.device).synchronize()
-        solver.hierarchy.diffusion_dkappa(solver.top, av.data_ptr(), bv.data_ptr(), out.data_ptr())
-        ctx.solver = solver
+        solver.hierarchy.diffusion_dkappa(solver.top, av.data_ptr(), bv.data_ptr(), out.data_ptr(), a_nodes=a_nodes, b_nodes=b_nodes)
+        ctx.solver, ctx.sets = solver, (a_nodes, b_nodes)
         ctx.save_for_backward(a, b)
         return out
 
     @staticmethod
     def backward(ctx, w):
         a, b = ctx.saved_tensors
-        grad_a = _Tangent.apply(w, b, ctx.solver).view(a.shape) if ctx.needs_input_grad[0] else None
-        grad_b = _Tangent.apply(w, a, ctx.solver).view(b.shape) if ctx.needs_input_grad[1] else None
-        return grad_a, grad_b, None
+        A, B = ctx.sets
+        grad_a = _Tangent.apply(w, b, ctx.solver, A, B).view(a.shape) if ctx.needs_input_grad[0] else None
+        grad_b = _Tangent.apply(w, a, ctx.solver, B, A).view(b.shape) if ctx.needs_input_grad[1] else None
+        return grad_a, grad_b, None, None, None
 
 
 class _Tangent(torch.autograd.Function):
-    """T(w, x) = (dA/dkappa . w) x = mg_diffusion_apply_dkappa(w, x), (N + 1)^3 nodes.  With cotangent y: w_bar = D(y, x),
-    x_bar = T(w, y)."""
+    """T(w, x; R, C) = M_R A^(w) M_C x = mg_diffusion_apply_dkappa(w, x) with a node set for the rows and one for the columns
+    ((interior, interior): (dA/dkappa . w) x), (N + 1)^3 nodes.  With cotangent y: w_bar = D(y, x; R, C), x_bar = T(w, y; C, R)."""
 
     @staticmethod
-    def forward(ctx, w, x, solver):
+    def forward(ctx, w, x, solver, rows, cols):
         if w.dtype != torch.float64 or w.device != solver.device or w.numel() != solver.N ** 3:
             raise ValueError(f"the kappa direction must hold {solver.N ** 3} float64 on {solver.device}")
         wv, xv = w.detach().contiguous(), solver._device_vector(x, "x")
         out = torch.empty(xv.numel(), dtype=torch.float64, device=solver.device)
         torch.cuda.current_stream(solver.device).synchronize()
-        solver.hierarchy.diffusion_apply_dkappa(solver.top, wv.data_ptr(), xv.data_ptr(), out.data_ptr())
-        ctx.solver = solver
+        solver.hierarchy.diffusion_apply_dkappa(solver.top, wv.data_ptr(), xv.data_ptr(), out.data_ptr(), rows=rows, cols=cols)
+        ctx.solver, ctx.sets = solver, (rows, cols)
         ctx.save_for_backward(w, x)
         return out
 
     @staticmethod
     def backward(ctx, y):
         w, x = ctx.saved_tensors
-        grad_w = _DKappa.apply(y, x, ctx.solver).view(w.shape) if ctx.needs_input_grad[0] else None
-        grad_x = _Tangent.apply(w, y, ctx.solver).view(x.shape) if ctx.needs_input_grad[1] else None
-        return grad_w, grad_x, None
+        R, C = ctx.sets
+        grad_w = _DKappa.apply(y, x, ctx.solver, R, C).view(w.shape) if ctx.needs_input_grad[0] else None
+        grad_x = _Tangent.apply(w, y, ctx.solver, C, R).view(x.shape) if ctx.needs_input_grad[1] else None
+        return grad_w, grad_x, None, None, None
