@@ -295,6 +295,7 @@ struct mg_context {
     int graph_comm = 0;             // ... on slabs too: the RCCL exchanges are captured with the kernels (opt-in)
     uint64_t epoch = 1;             // bumped by every call that changes what a V-cycle launches
     std::vector<CycleGraph> graphs;
+    bool capturing = false;         // between hipStreamBeginCapture and hipStreamEndCapture of vcycle_graphed (zero_doubles)
     int use_direct = 1;             // exact block-tridiagonal coarsest solve where the level allows it
     int require_diagonal = 1;       // 0: operators without a diagonal (D^-1 R of the split smoother)
     int fuse_restrict = 1;          // residual evaluated at the coarse nodes only when restricting by injection
@@ -2547,10 +2548,22 @@ int prolong(mg_context* c, int level, int add) {
     return 0;
 }
 
-int zero_vec(mg_context* c, const Level& L, DVector& v) {
-    HIP_TRY(hipMemsetAsync(v.base, 0, (size_t)L.xlen * sizeof(double), c->stream));
+// Zeroes `count` doubles at `p` on the handle's stream.  Inside a captured V-cycle (vcycle_graphed) a kernel does it: with
+// memset nodes, a cycle replayed from torch.autograd's backward thread gave other results than the eager launches on
+// hierarchies of four and more levels -- the same key, the same addresses; with kernel nodes it
+// is bit-identical.
+int zero_doubles(mg_context* c, double* p, size_t count) {
+    if (c->capturing && count > 0) {
+        const unsigned nb = (unsigned)std::min<size_t>((count + 4 * BLOCK - 1) / (4 * BLOCK), (size_t)8 * std::max(1, c->prop.multiProcessorCount));
+        hipLaunchKernelGGL(fill_zero, dim3(std::max(1u, nb)), dim3(BLOCK), 0, c->stream, p, (int64_t)count);
+        HIP_TRY(hipGetLastError());
+        return 0;
+    }
+    HIP_TRY(hipMemsetAsync(p, 0, count * sizeof(double), c->stream));
     return 0;
 }
+
+int zero_vec(mg_context* c, const Level& L, DVector& v) { return zero_doubles(c, v.base, (size_t)L.xlen); }
 
 // sum over owned rows of x.y on the device -> c->scalars[slot]; all-reduced over slabs
 int dot_device(mg_context* c, const Level& L, const double* x_rows, const double* y_rows, int slot) {
@@ -2838,7 +2851,7 @@ int direct_solve(mg_context* c) {
     const int p = d.g.p, nb = d.g.nb;
     const size_t pp = (size_t)p * p, pw = (size_t)p * d.g.W;
     const int64_t first = std::min<int64_t>(L.nloc, p);
-    HIP_TRY(hipMemsetAsync(d.y, 0, (size_t)p * 8, c->stream));
+    MG_TRY(zero_doubles(c, d.y, (size_t)p));
     HIP_TRY(hipMemcpyAsync(d.y, L.f.rows, (size_t)first * 8, hipMemcpyDeviceToDevice, c->stream));
     const dim3 wave_grid(blocks_for(p, WAVES_PER_BLOCK)), blk(BLOCK);
     // wide rows (P2: ~20 couplings into the previous block per row): T_{k-1} y_{k-1} once, then the sparse part -- 19 + 3 us
@@ -2953,6 +2966,9 @@ int vcycle(mg_context* c, int level) {
 }
 
 void drop_graphs(mg_context* c) {
+    // (mg_vcycle and mg_fmg enqueue replays without a host synchronisation: an executable graph is not destroyed under a
+    //  launch that is still in flight.  Rare -- the cache is full, or the levels or the tuning change)
+    if (!c->graphs.empty() && c->stream) (void)hipStreamSynchronize(c->stream);
     for (auto& g : c->graphs) {
         if (g.exec) (void)hipGraphExecDestroy(g.exec);
         if (g.graph) (void)hipGraphDestroy(g.graph);
@@ -3019,7 +3035,9 @@ int vcycle_graphed(mg_context* c, int level) {
     CycleGraph g;
     g.level = level; g.epoch = c->epoch; g.pre = pre;
     HIP_TRY(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
+    c->capturing = true;
     const int rc = vcycle(c, level);
+    c->capturing = false;
     const hipError_t e = hipStreamEndCapture(c->stream, &g.graph);
     if (rc != 0 || e != hipSuccess) {
         if (g.graph) (void)hipGraphDestroy(g.graph);

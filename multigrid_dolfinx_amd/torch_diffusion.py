@@ -72,8 +72,6 @@ class DiffusionSolver:
     from a backward pass count as "adjoint" in `last_iterations`, `last_residual` and `NotConverged`; while a backward pass
     records gradients they start from zero and leave the kept warm-start solutions alone.  Without `create_graph` the
     backward pass is the one solve and one sensitivity kernel described above.  `tangent` is the forward-mode derivative.
-    Known limit: on deep hierarchies (six levels at 257^3) a third `mg_pcg` in a row on one generation
-    does not converge with captured V-cycles and raises `NotConverged`; `solver.hierarchy.set_tuning("graph", 0)` avoids it.
 
     `warm_start=True` keeps the last forward and the last adjoint solution and starts the next solve of each kind from
     them instead of from zero (kappa that moves a little between solves).  The stopping test is relative to the

@@ -4,7 +4,7 @@
            of 8 TB/s on the model both share, 8 (x) + 8 (kappa / dkappa) + 8 (out) = 24 B per row
   hvp      one Hessian-vector product through torch_diffusion.DiffusionSolver at 257^3 (six levels, every level above 0
            matrix-free, log-normal kappa (sigma 1, seed 0), J = 1/2 ||u - d||^2, rtol 1e-6 as in tools/time_dkappa.py) beside one
-           forward + backward: seconds, mg_pcg calls and iterations; both with eager V-cycles ("graph" 0, see hvp_times)
+           forward + backward: seconds, mg_pcg calls and iterations; both with the default tuning (captured V-cycles)
 
     python tools/time_tangent.py [--levels 5,7] [--json profiles/diffusion_tangent_time.json]
 """
@@ -56,11 +56,7 @@ def hvp_times(hi, n_levels):
     v = torch.randn(N ** 3, dtype=torch.float64, device="cuda", generator=gen)
     out = {"N": N, "levels": n_levels, "rtol": 1e-6, "matrix_free_min_rows": 0}
     with DiffusionSolver(N, n_levels, rtol=out["rtol"], matrix_free_min_rows=0) as solver:
-        # Eager V-cycles for both figures: with captured cycles ("graph" 1, the default) a third mg_pcg in a row on one
-        # generation of a six-level 257^3 hierarchy does not converge (stored or matrix-free, with none of the tangent
-        # kernels involved: DESIGN.md section 8), and a Hessian-vector product is four in a row.
-        solver.hierarchy.set_tuning("graph", 0)
-        out["graph"] = 0
+        out["graph"] = 1                            # captured V-cycles, the default
         for attempt in ("warm_up", "timed"):        # (the second pass: set-up work vectors and captured cycles exist)
             # kappa on the device: after the first pass the hierarchy is refreshed in place, and the times are the solves'
             k = torch.tensor(kappa, device="cuda", requires_grad=True)
