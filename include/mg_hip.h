@@ -256,6 +256,32 @@ int mg_gen_diffusion_hierarchy_device(mg_handle h, int top_level, int elements_p
  * finite -- found by a read-only pass over the caller's buffer before anything is written.  The coarsened fields are not
  * validated, as in the hierarchy calls. */
 int mg_refresh_diffusion_hierarchy(mg_handle h, int top_level, const double* kappa_dev, int averaging);
+/* No-flux (Neumann) faces for the generated diffusion levels (no reference counterpart).  dirichlet_faces is the set of the
+ * faces of the unit cube that carry the Dirichlet condition, one bit per face (enum mg_face; the default, MG_FACES_ALL = 63,
+ * is every call's behaviour before this entry existed, bit for bit and launch for launch).  A node on a face of the set is a
+ * Dirichlet node: an identity row with the boundary data, its columns zeroed and lifted into the right-hand side.  Every
+ * other node is a free node, the boundary nodes that lie only on faces outside the set included: such a node gets the
+ * natural row of the P1 matrix -- the edge sums, the diagonal sum and the scaling of an interior row with a cell outside the
+ * grid counting as +0.0 and no column outside the grid -- and the load f h^3 (T / 24), T the number of Kuhn simplices at the
+ * node that lie inside the grid (24 inside).  That is the no-flux condition; a prescribed flux is a load added on those nodes
+ * (mg_set_vector).  The level stays symmetric to the bit.
+ * The set is handle state, read when levels are generated: mg_gen_diffusion_level[_mf], the three hierarchy calls, and
+ * mg_refresh_diffusion_hierarchy, which refuses if it differs from the set the levels were generated with.  Each level
+ * remembers its set: the matrix-free march, the P1-transpose restriction (a free coarse node on a no-flux face sums the
+ * pattern without the offsets that leave the grid; a Dirichlet coarse node takes the coincident value) and mg_memory_bytes
+ * follow it.  MG_NODES_INTERIOR of the sensitivity entries below means the free nodes of the handle's set.
+ * Refused by name, the handle left as it was: 0 (no Dirichlet face: the operator would be singular), values outside 0..63,
+ * and on 2-D handles and slab handles any value but 63.  A handle that is made a slab handle after a set other than 63 was
+ * set is refused where the set is read: by the generating calls and the sensitivity entries.
+ * With levels of another set than 63, three things are refused before anything is launched:
+ *   - mg_vcycle, mg_prepare_cycle, mg_fmg and mg_pcg whose transfers are not the P1 prolongation (mg_set_prolongation_p1)
+ *     with MG_RESTRICT_P1_TRANSPOSE, and single mg_restrict / mg_prolong calls of another kind on such levels;
+ *   - the same calls over levels that were generated with different sets;
+ *   - mg_galerkin_level. */
+enum mg_face { MG_FACE_XLO = 1, MG_FACE_XHI = 2, MG_FACE_YLO = 4, MG_FACE_YHI = 8, MG_FACE_ZLO = 16, MG_FACE_ZHI = 32, MG_FACES_ALL = 63 };
+int mg_set_diffusion_faces(mg_handle h, int dirichlet_faces);
+/* *dirichlet_faces = the handle's face set */
+int mg_diffusion_faces(mg_handle h, int* dirichlet_faces);
 /* *on = 1 if the level is matrix-free, *kappa_bytes = the device bytes of its kappa (0 otherwise) */
 int mg_level_matrix_free(mg_handle h, int level, int* on, int64_t* kappa_bytes);
 /* Sensitivity of the diffusion operator to kappa (no reference counterpart): out_dev[c] = d(a^T A(kappa) b) / d kappa_c for the

@@ -60,6 +60,8 @@ SIGNATURES = {
     "mg_gen_diffusion_hierarchy_device": [_H, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int64],
     "mg_refresh_diffusion_hierarchy": [_H, C.c_int, C.c_void_p, C.c_int],
     "mg_level_matrix_free": [_H, C.c_int, _ip, _i64p],
+    "mg_set_diffusion_faces": [_H, C.c_int],
+    "mg_diffusion_faces": [_H, _ip],
     "mg_jacobi_split": [C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                         C.c_void_p, C.c_void_p],
     "mg_set_params": [_H, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int],

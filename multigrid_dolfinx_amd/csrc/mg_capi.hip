@@ -195,6 +195,7 @@ struct Level {
     bool mf = false;
     double* kappa = nullptr;
     int64_t kappa_n = 0;
+    int faces = MG_FACES_ALL;               // the face set a generated diffusion level was built with (mg_set_diffusion_faces)
     bool diffusion_hierarchy = false;       // generated by one of the diffusion hierarchy entries: mg_refresh_diffusion_hierarchy may renew it
     DVector v, v2, f, err, ftrue;
     DVector sw;                             // once-relaxed boundary planes of a slab (paired sweeps, world > 1)
@@ -287,6 +288,8 @@ struct mg_context {
     int64_t lattice_march_min_rows = 1 << 22;       // (measured on C5: the 129^3 and 65^3 lattices are faster with the gathering kernel)
     int lattice_gs2 = 0;            // nine-colour Gauss-Seidel on whole lattice levels: two colours per launch, out of place (lat_gs2;
                                     // measured slower than nine colour launches: 9.1 against 6.8 ms per sweep of the 513^3 lattice)
+    int diffusion_faces = MG_FACES_ALL;     // mg_set_diffusion_faces: the faces with a Dirichlet condition in the diffusion levels generated
+                                    // from now on, and what MG_NODES_INTERIOR masks; the other faces are no-flux faces
     int dkappa_gather = 0;          // mg_diffusion_dkappa: 1 = one thread per cell reading through the caches instead of the plane march
                                     // (1025^3: 12.5 ms against 5.75 for the march)
     int lattice_tile = 0;           // tile of that march: 0 / 1 = 64 x 16 cells (256 threads), 2 = 128 x 16 (512 threads)
@@ -606,6 +609,7 @@ void free_level(mg_context* c, Level& L) {
     dev_free(c, L.kappa, (size_t)L.kappa_n);
     L.kappa_n = 0;
     L.mf = false;
+    L.faces = MG_FACES_ALL;
     L.diffusion_hierarchy = false;
     dev_free(c, L.perm, (size_t)L.n_global);
     vec_free(c, L, &L.v);
@@ -860,6 +864,20 @@ MfPlan mf_plan_dims(const mg_context* c, int nx, int ny, int nz) {
 }
 MfPlan mf_plan(const mg_context* c, const Level& L) { return mf_plan_dims(c, L.g.nx, L.g.ny, L.g.nz); }
 
+// A face set other than all six faces lives on whole 3-D handles only.  mg_set_diffusion_faces refuses the others; a handle
+// that became a slab handle after the set was set is refused where the set is read: by the generators, the P1-transpose
+// restriction and the sensitivity entries.
+int face_set_handle(const mg_context* c, const std::string& who) {
+    if (c->diffusion_faces == MG_FACES_ALL) return 0;
+    if (c->dim != 3) return fail(who + ": the face set " + std::to_string(c->diffusion_faces) + " (mg_set_diffusion_faces) is 3-D only");
+    if (c->comm.active())
+        return fail(who + ": the face set " + std::to_string(c->diffusion_faces) + " (mg_set_diffusion_faces) needs a whole (not slab) handle");
+    return 0;
+}
+
+// the free nodes of a face set on a whole 3-D level
+FreeBox level_box(const Level& L, int faces) { return free_box(faces, L.g.nx, L.g.ny, L.g.nz); }
+
 MfArgs mf_args(const MfPlan& p, const Level& L, const double* kappa, const double* x_rows, double* out_rows) {
     MfArgs a{};
     a.x = x_rows; a.xp = out_rows; a.out = out_rows; a.kappa = kappa;
@@ -879,9 +897,11 @@ int launch_diffusion_mf(mg_context* c, const Level& L, int mode, bool dot, const
     if (grid_out) *grid_out = p.grid;
     const dim3 grid(p.grid), blk(MF_NT);
     bool known = true;
+    const MfFaceArgs fa{a, level_box(L, L.faces)};      // (levels generated with a face set: the march with the box of its free nodes)
     with_mode(mode, dot, [&](auto m, auto d) {
         constexpr int MODE = decltype(m)::value;
         if constexpr (MODE == MODE_GS) known = false;
+        else if (L.faces != MG_FACES_ALL) hipLaunchKernelGGL((diffusion_mf_faces<MODE, decltype(d)::value>), grid, blk, 0, c->stream, fa);
         else hipLaunchKernelGGL((diffusion_mf<MODE, decltype(d)::value>), grid, blk, 0, c->stream, a);
     });
     if (!known) return fail("matrix-free diffusion levels have no kernel for this mode");
@@ -891,12 +911,21 @@ int launch_diffusion_mf(mg_context* c, const Level& L, int mode, bool dot, const
 
 // out = M_rows A^(dkappa) M_cols x on a whole 3-D grid level: the SpMV march with kappa := dkappa (diffusion_mf<MODE_SPMV, false,
 // true, rows_all, cols_all>); (interior, interior) is (dA/dkappa . dkappa) x with +0.0 on boundary rows.  Reads the grid only;
-// dkappa, x, out: the caller's, lexicographic, out != x.
+// dkappa, x, out: the caller's, lexicographic, out != x.  "Interior" is the set of the free nodes of the handle's face set.
 int launch_apply_dkappa(mg_context* c, const Level& L, const double* dkappa, const double* x, double* out, bool rows_all = false,
                         bool cols_all = false) {
     const MfPlan p = mf_plan(c, L);
     const MfArgs a = mf_args(p, L, dkappa, x, out);
     const dim3 grid(p.grid), blk(MF_NT);
+    if (c->diffusion_faces != MG_FACES_ALL) {
+        const MfFaceArgs fa{a, level_box(L, c->diffusion_faces)};
+        if (rows_all && cols_all) hipLaunchKernelGGL((diffusion_mf_faces<MODE_SPMV, false, true, true, true>), grid, blk, 0, c->stream, fa);
+        else if (rows_all) hipLaunchKernelGGL((diffusion_mf_faces<MODE_SPMV, false, true, true, false>), grid, blk, 0, c->stream, fa);
+        else if (cols_all) hipLaunchKernelGGL((diffusion_mf_faces<MODE_SPMV, false, true, false, true>), grid, blk, 0, c->stream, fa);
+        else hipLaunchKernelGGL((diffusion_mf_faces<MODE_SPMV, false, true>), grid, blk, 0, c->stream, fa);
+        HIP_TRY(hipGetLastError());
+        return 0;
+    }
     if (rows_all && cols_all) hipLaunchKernelGGL((diffusion_mf<MODE_SPMV, false, true, true, true>), grid, blk, 0, c->stream, a);
     else if (rows_all) hipLaunchKernelGGL((diffusion_mf<MODE_SPMV, false, true, true, false>), grid, blk, 0, c->stream, a);
     else if (cols_all) hipLaunchKernelGGL((diffusion_mf<MODE_SPMV, false, true, false, true>), grid, blk, 0, c->stream, a);
@@ -914,6 +943,7 @@ int launch_diffusion_rhs(mg_context* c, const Level& L, const double* d_kappa, d
     a.fh = -12.0 * std::pow(a.h, 3.0);
     d.kappa = d_kappa;
     d.kc0 = 0;
+    d.box = level_box(L, L.faces);
     hipLaunchKernelGGL(gen_diffusion_rhs, grid3(L.g, L.g.nk), dim3(kPlaneBlock), 0, c->stream, d, f_rows, dinv_rows);
     HIP_TRY(hipGetLastError());
     return 0;
@@ -929,6 +959,7 @@ int launch_dkappa(mg_context* c, const Level& L, const double* a, const double* 
     d.a_all = a_all; d.b_all = b_all;
     d.nx = L.g.nx; d.ny = L.g.ny; d.nz = L.g.nz; d.N = L.N; d.P = L.g.plane;
     d.scale = (1.0 / (double)L.N) / 6.0;
+    d.box = level_box(L, c->diffusion_faces);
     if (gather) {
         const dim3 grid(blocks_for((int64_t)L.N * L.N, DK_BLOCK), (unsigned)L.N, 1u);
         hipLaunchKernelGGL(diffusion_dkappa_gather, grid, dim3(DK_BLOCK), 0, c->stream, d);
@@ -2453,6 +2484,15 @@ int check_p1_stencil(mg_context* c, Level& L) {
 int restrict_to(mg_context* c, int level, int kind) {
     Level& F = c->L[level];
     Level& C = c->L[level - 1];
+    if (F.faces != MG_FACES_ALL || C.faces != MG_FACES_ALL) {       // (a single mg_restrict call; cycles are refused before they start)
+        if (F.faces != C.faces)
+            return fail("levels " + std::to_string(level) + " and " + std::to_string(level - 1) + " were generated with different face sets (" +
+                        std::to_string(F.faces) + " and " + std::to_string(C.faces) + "): generate them with one mg_set_diffusion_faces");
+        if (kind != MG_RESTRICT_P1_TRANSPOSE)
+            return fail("level " + std::to_string(level) + " was generated with the face set " + std::to_string(F.faces) +
+                        " (mg_set_diffusion_faces): its no-flux faces need the P1 transfers (MG_RESTRICT_P1_TRANSPOSE)");
+        if (c->comm.active()) return fail("levels with a face set need a whole (not slab) handle");
+    }
     Grid gc = coarse_target_grid(c, C, F);
     if (kind == MG_RESTRICT_TABLE) {
         if (!c->rtab_count) return fail("no restriction table (mg_set_restriction_table)");
@@ -2467,9 +2507,13 @@ int restrict_to(mg_context* c, int level, int kind) {
         MG_TRY(check_p1_stencil(c, F));
         MG_TRY(check_p1_stencil(c, C));
         MG_TRY(exchange_halo(c, F, F.v2));          // (the same fine planes as full weighting)
-        with_int_else<2, 3>(c->dim, [&](auto dim) {
-            hipLaunchKernelGGL(restrict_p1t<decltype(dim)::value>, grid3(gc, gc.nk), dim3(kPlaneBlock), 0, c->stream, gc, F.g, F.v2.base, C.f.base);
-        });
+        if (C.faces != MG_FACES_ALL)                // (3-D whole levels: mg_set_diffusion_faces refuses the others)
+            hipLaunchKernelGGL(restrict_p1t_faces, grid3(gc, gc.nk), dim3(kPlaneBlock), 0, c->stream, gc, F.g,
+                               free_box(C.faces, gc.nx, gc.ny, gc.nz), F.v2.base, C.f.base);
+        else
+            with_int_else<2, 3>(c->dim, [&](auto dim) {
+                hipLaunchKernelGGL(restrict_p1t<decltype(dim)::value>, grid3(gc, gc.nk), dim3(kPlaneBlock), 0, c->stream, gc, F.g, F.v2.base, C.f.base);
+            });
     } else if (kind == MG_RESTRICT_FULL_WEIGHTING) {
         MG_TRY(exchange_halo(c, F, F.v2));
         hipLaunchKernelGGL(restrict_full_weighting, grid3(gc, gc.nk), dim3(kPlaneBlock), 0, c->stream, gc, F.g, F.v2.base,
@@ -2510,6 +2554,14 @@ int residual_restrict_fused(mg_context* c, int level) {
 int prolong(mg_context* c, int level, int add) {
     Level& F = c->L[level];
     Level& C = c->L[level - 1];
+    if (F.faces != MG_FACES_ALL || C.faces != MG_FACES_ALL) {       // (a single mg_prolong call; cycles are refused before they start)
+        if (F.faces != C.faces)
+            return fail("levels " + std::to_string(level) + " and " + std::to_string(level - 1) + " were generated with different face sets (" +
+                        std::to_string(F.faces) + " and " + std::to_string(C.faces) + "): generate them with one mg_set_diffusion_faces");
+        if (!c->p1_prolong)
+            return fail("level " + std::to_string(level) + " was generated with the face set " + std::to_string(F.faces) +
+                        " (mg_set_diffusion_faces): its no-flux faces need the P1 transfers (mg_set_prolongation_p1)");
+    }
     const bool keep = !add || c->keep_err;
     if (keep) MG_TRY(vec_alloc(c, F, &F.err));
     double* const err = keep ? F.err.base : nullptr;        // (kept: the prolonged coarse iterate goes there as well)
@@ -2983,7 +3035,24 @@ void drop_graphs(mg_context* c) {
 // swaps are re-applied on the host after a replay.
 // Everything a V-cycle from `level` builds or allocates on first use (the direct coarsest solve and its validation, the
 // colouring checks, the parked-sweep and error vectors): afterwards a cycle -- and its capture -- only enqueues work.
+// Levels generated with a face set (mg_set_diffusion_faces) run cycles with the P1 transfers only: the other restrictions
+// and prolongations hard-code "the boundary".  Only checks.
+int face_set_refusals(mg_context* c, int level) {
+    for (int l = 0; l <= level; ++l) {
+        const int faces = c->L[l].faces;
+        if (faces == MG_FACES_ALL && c->L[level].faces == MG_FACES_ALL) continue;
+        if (faces != c->L[level].faces)
+            return fail("levels " + std::to_string(level) + " and " + std::to_string(l) + " were generated with different face sets (" +
+                        std::to_string(c->L[level].faces) + " and " + std::to_string(faces) + "): generate them with one mg_set_diffusion_faces");
+        if (!c->p1_prolong || c->restriction != MG_RESTRICT_P1_TRANSPOSE)
+            return fail("level " + std::to_string(l) + " was generated with the face set " + std::to_string(faces) + " (mg_set_diffusion_faces): "
+                        "its no-flux faces need the P1 transfers (mg_set_prolongation_p1 and MG_RESTRICT_P1_TRANSPOSE)");
+    }
+    return 0;
+}
+
 int prepare_cycle(mg_context* c, int level) {
+    MG_TRY(face_set_refusals(c, level));
     // (refused here, before the colouring check and before anything is captured; smooth() refuses a single call)
     if (c->smoother == MG_SMOOTH_RBGS || c->smoother == MG_SMOOTH_MCGS)
         for (int l = 1; l <= level; ++l)
@@ -4297,6 +4366,10 @@ int galerkin_level(mg_context* c, int level) {
     MG_TRY(need_matrix(c, level));
     MG_TRY(need_grid(c, level));
     Level& F = c->L[level];
+    if (F.faces != MG_FACES_ALL)
+        return fail("mg_galerkin_level: level " + std::to_string(level) + " was generated with the face set " + std::to_string(F.faces) +
+                    " (mg_set_diffusion_faces): the Galerkin product knows Dirichlet conditions on all six faces only; generate the "
+                    "coarse level with mg_gen_diffusion_level or a diffusion hierarchy call instead");
     MG_TRY(need_stored_rows(c, F, "mg_galerkin_level (the Galerkin product; generate the level with mg_gen_diffusion_level instead)"));
     if (!F.replicated) return fail("Galerkin coarse levels need a whole fine level, not a slab");
     if (F.N < 2 || (F.N & 1)) return fail("Galerkin coarse levels need an even elements_per_dim");
@@ -4524,11 +4597,16 @@ int gen_diffusion_level(mg_context* c, int level, int N, const double* d_kappa, 
     d.ga = gen_args(c, N, prune_zeros);
     d.kappa = d_kappa;
     d.kc0 = kc0;
-    return gen_stored_level(c, level, N, d.ga.W, [&](const Level& L, dim3 grid, unsigned long long* counts) {
+    MG_TRY(face_set_handle(c, "mg_gen_diffusion_level"));
+    const int faces = c->diffusion_faces;       // (not the default: a 3-D whole handle, so L.g is the whole grid)
+    MG_TRY(gen_stored_level(c, level, N, d.ga.W, [&](const Level& L, dim3 grid, unsigned long long* counts) {
         const dim3 blk(kPlaneBlock);
         d.ga.g = L.g;
+        d.box = free_box(faces, L.g.nx, L.g.ny, L.g.nz);
         with_int_else<4, 1, 2>(L.R, [&](auto r) { hipLaunchKernelGGL(gen_diffusion<decltype(r)::value>, grid, blk, 0, c->stream, d, L.vals, L.cols, L.dinv, L.f.rows, counts); });
-    });
+    }));
+    c->L[level].faces = faces;
+    return 0;
 }
 
 }  // namespace
@@ -4570,11 +4648,14 @@ int gen_diffusion_level_mf(mg_context* c, int level, int N, double* d_kappa, int
     L.nslices = (L.nloc + (int64_t)WAVE * L.R - 1) / ((int64_t)WAVE * L.R);
     MG_TRY(alloc_level_vectors(c, L));
     if (level + 1 < c->nlev) MG_TRY(vec_alloc(c, L, &L.ftrue));     // (the true right-hand side for mg_fmg, as on stored levels)
+    L.faces = c->diffusion_faces;
     MG_TRY(fill_rhs_mf(c, L, d_kappa));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    // what the stored level would report: seven entries per interior row less the columns on the boundary, one per boundary row
-    const int64_t m = N - 1;
-    L.nnz_stored = L.nnz_nonzero = (unsigned long long)(m * m * m + 6 * m * m * (m - 1) + (L.n_global - m * m * m));
+    // what the stored level would report: one diagonal entry per row and two entries per pair of free axis neighbours (the
+    // default set: seven per interior row less the columns on the boundary, one per boundary row)
+    const FreeBox box = level_box(L, L.faces);
+    const int64_t m[3] = {box.hi[0] - box.lo[0] + 1, box.hi[1] - box.lo[1] + 1, box.hi[2] - box.lo[2] + 1};
+    L.nnz_stored = L.nnz_nonzero = (unsigned long long)(L.n_global + 2 * ((m[0] - 1) * m[1] * m[2] + m[0] * (m[1] - 1) * m[2] + m[0] * m[1] * (m[2] - 1)));
     L.rep_sym = 1;
     L.rb_ok = false;
     L.mf = true;
@@ -4587,6 +4668,7 @@ int gen_diffusion_level_mf(mg_context* c, int level, int N, double* d_kappa, int
 }
 
 int mf_refusals(mg_context* c, const std::string& who) {
+    MG_TRY(face_set_handle(c, who));
     if (c->dim != 3) return fail(who + ": matrix-free diffusion levels are 3-D only (this handle is 2-D)");
     if (c->comm.active()) return fail(who + ": matrix-free diffusion levels need a whole (not slab) handle");
     return 0;
@@ -4735,6 +4817,9 @@ int mg_refresh_diffusion_hierarchy(mg_handle c, int top_level, const double* kap
             return fail(who + ": levels " + std::to_string(l + 1) + " and " + std::to_string(l) + " come from hierarchies of different "
                         "sizes (" + std::to_string(c->L[l + 1].N) + " and " + std::to_string(L.N) + " cells per dimension)");
         if (L.mf && L.kappa_n != cell_plane(c, L.N) * L.N) return fail(who + ": level " + std::to_string(l) + " keeps a kappa of another size");
+        if (L.faces != c->diffusion_faces)
+            return fail(who + ": level " + std::to_string(l) + " was generated with the face set " + std::to_string(L.faces) +
+                        ", the handle's is " + std::to_string(c->diffusion_faces) + " now (mg_set_diffusion_faces): generate the hierarchy again");
     }
     const int N = c->L[top_level].N;
     MG_TRY(check_kappa(c, kappa_dev, cell_plane(c, N) * N, 0, N));      // read-only: a refusal leaves the old hierarchy usable
@@ -4776,6 +4861,27 @@ int mg_refresh_diffusion_hierarchy(mg_handle c, int top_level, const double* kap
         coarse.p = nullptr;
         src = coarse_p;
     }
+    return 0;
+}
+
+int mg_set_diffusion_faces(mg_handle c, int dirichlet_faces) {
+    if (!c) return fail("null handle");
+    const std::string who = "mg_set_diffusion_faces: ";
+    if (dirichlet_faces < 0 || dirichlet_faces > MG_FACES_ALL)
+        return fail(who + std::to_string(dirichlet_faces) + " is no face set (x- = 1, x+ = 2, y- = 4, y+ = 8, z- = 16, z+ = 32: 1..63)");
+    if (dirichlet_faces == 0) return fail(who + "a face set of 0 leaves no Dirichlet face: the operator would be singular");
+    if (dirichlet_faces != MG_FACES_ALL) {
+        if (c->dim != 3) return fail(who + "no-flux faces are 3-D only (this handle is 2-D)");
+        if (c->comm.active()) return fail(who + "no-flux faces need a whole (not slab) handle");
+    }
+    c->diffusion_faces = dirichlet_faces;
+    return 0;
+}
+
+int mg_diffusion_faces(mg_handle c, int* dirichlet_faces) {
+    if (!c) return fail("null handle");
+    if (!dirichlet_faces) return fail("null argument");
+    *dirichlet_faces = c->diffusion_faces;
     return 0;
 }
 
@@ -5302,6 +5408,7 @@ int mg_vcycle(mg_handle c, int level, int ncycles, double* resid_l2) {
         MG_TRY(need_matrix(c, l));
         if (level > 0) MG_TRY(need_grid(c, l));
     }
+    MG_TRY(face_set_refusals(c, level));
     HIP_TRY(hipSetDevice(c->device));
     Level& L = c->L[level];
     MG_TRY(exchange_halo(c, L, L.v));
@@ -5325,6 +5432,7 @@ int mg_fmg_ex(mg_handle c, int top, int mu0, double tol, int max_cycles, int nor
     if (norm != MG_NORM_L2 && norm != MG_NORM_MASS) return fail("unknown norm");
     if (norm == MG_NORM_MASS && c->mass_level != top) return fail("mg_fmg_ex: no mass matrix on the top level (mg_set_mass_csr)");
     if (err_hist && (!c->uexact.raw || c->uexact_level != top)) return fail("mg_fmg_ex: no exact solution on the top level (mg_set_exact)");
+    MG_TRY(face_set_refusals(c, top));
     HIP_TRY(hipSetDevice(c->device));
     for (int l = 0; l < top; ++l) {
         Level& L = c->L[l];
@@ -5376,6 +5484,7 @@ int mg_pcg(mg_handle c, int level, double rtol, int max_iter, double* resid_hist
         MG_TRY(need_matrix(c, l));
         MG_TRY(need_grid(c, l));
     }
+    MG_TRY(face_set_refusals(c, level));
     HIP_TRY(hipSetDevice(c->device));
     return fcg_solve(c, level, rtol, max_iter, resid_hist, iterations);
 }

@@ -26,6 +26,10 @@
 // natural P1 matrix of a cell field on all nodes (no boundary condition) and M the mask of the interior nodes or the
 // identity.  The mask acts where a node is loaded and nowhere else: dk_cell and its adds are the same, and (interior,
 // interior) is mg_diffusion_dkappa to the bit.  An unmasked vector is read at every corner: all of them are on the grid.
+//
+// With a face set (mg_set_diffusion_faces) the interior nodes are the free nodes of the set, nodes on no-flux faces
+// included: both kernels take the box of the free nodes (FreeBox) where they had 1 <= index <= n - 2, and nothing else
+// changes.  The default set gives that box.
 #pragma once
 #include "mg_kernels.hip.h"
 
@@ -40,7 +44,8 @@ struct DkArgs {
     int nx, ny, nz, N;      // nodes per axis (N + 1 each), cells per axis
     int64_t P;              // nx * ny
     double scale;           // h / 6.0
-    int a_all, b_all;       // 0: the boundary entries of the vector count as 0 (not loaded); 1: every node is read
+    int a_all, b_all;       // 0: the entries of the vector outside `box` count as 0 (not loaded); 1: every node is read
+    FreeBox box;            // the free nodes of the handle's face set (the default set: the interior nodes)
 };
 
 // one pointer passed twice is loaded once -- where both vectors are masked alike, or the one mask would serve the other
@@ -76,7 +81,7 @@ __global__ __launch_bounds__(DK_BLOCK) void diffusion_dkappa_gather(DkArgs p) {
 #pragma unroll
             for (int dx = 0; dx < 2; ++dx) {
                 const int i = ci + dx, j = cj + dy, k = ck + dz;
-                const bool inner = i >= 1 && i <= p.nx - 2 && j >= 1 && j <= p.ny - 2 && k >= 1 && k <= p.nz - 2;
+                const bool inner = free_node(p.box, i, j, k);
                 const int64_t r = (int64_t)k * p.P + (int64_t)j * p.nx + i;
                 A[dz][dy][dx] = inner || p.a_all ? p.a[r] : 0.0;
                 B[dz][dy][dx] = inner || p.b_all ? (same ? A[dz][dy][dx] : p.b[r]) : 0.0;
@@ -119,7 +124,7 @@ __global__ __launch_bounds__(MF_NT) void diffusion_dkappa_march(DkMarchArgs m) {
     const bool on_grid = ci < p.N && cj < p.N;
     const bool same = dk_same(p);
 
-    // the elements of an image this thread fills: e = tid and tid + MF_NT; -1: outside the grid (0); ni: an interior node of
+    // the elements of an image this thread fills: e = tid and tid + MF_NT; -1: outside the grid (0); ni: a free node of
     // its plane (a masked vector reads no other)
     int64_t no[2];
     int ne[2];
@@ -130,10 +135,10 @@ __global__ __launch_bounds__(MF_NT) void diffusion_dkappa_march(DkMarchArgs m) {
         ne[q] = e < DK_S ? e : -1;
         const int i = tx0 + e % DK_W, j = ty0 + e / DK_W;
         no[q] = (e < DK_S && i <= p.nx - 1 && j <= p.ny - 1) ? (int64_t)j * p.nx + i : -1;
-        ni[q] = i >= 1 && i <= p.nx - 2 && j >= 1 && j <= p.ny - 2;
+        ni[q] = i >= p.box.lo[0] && i <= p.box.hi[0] && j >= p.box.lo[1] && j <= p.box.hi[1];
     }
     auto load = [&](int plane, double (&va)[2], double (&vb)[2]) {
-        const bool on = plane >= 0 && plane <= p.nz - 1, ok = plane >= 1 && plane <= p.nz - 2;
+        const bool on = plane >= 0 && plane <= p.nz - 1, ok = plane >= p.box.lo[2] && plane <= p.box.hi[2];
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
             const bool in = on && no[q] >= 0, inner = ok && ni[q];

@@ -41,6 +41,14 @@
 //   * COLS_ALL keeps the entries towards boundary neighbours.  Without it every entry whose column is a boundary node is
 //     a zero in the chain: the six neighbours' and, on a boundary row, the row's own diagonal.
 // <false, false> is the kernel above, expression for expression.
+//
+// FACES (diffusion_mf_faces; levels generated with a face set, mg_set_diffusion_faces) is the same march with the box of the
+// free nodes in place of "1 <= index <= n - 2", in every mode and with every mask.  A free row on a no-flux face is rebuilt
+// from kappa like an interior row: the kappa image is padded with 0.0, x outside the grid reads 0, and the entry towards a
+// Dirichlet neighbour (or past the grid) is a zero in the fma chain -- the bits of the stored level's one-step kernel, whose
+// row has the same sums.  Dirichlet rows are identity rows (TANGENT: +0.0).  ROWS_ALL / COLS_ALL: "boundary" reads
+// "Dirichlet".  The bounds come from the host, six integers compared per axis: no bit of the set is tested in the loop.
+// The instantiations without FACES are the kernels above, untouched: handles with the default set launch those.
 #pragma once
 #include "mg_kernels.hip.h"
 
@@ -73,11 +81,16 @@ __device__ __forceinline__ double mf_div6(double t) {
     return fma(r, c, q);
 }
 
-template <int MODE, bool DOT, bool TANGENT = false, bool ROWS_ALL = false, bool COLS_ALL = false>
-__global__ __launch_bounds__(MF_NT) void diffusion_mf(MfArgs a) {
+struct MfFaceArgs {
+    MfArgs a;
+    FreeBox box;            // the free nodes of the level's face set
+};
+
+template <int MODE, bool DOT, bool TANGENT, bool ROWS_ALL, bool COLS_ALL, bool FACES>
+__device__ __forceinline__ void mf_march(const MfArgs& a, const FreeBox& box) {
     static_assert(!TANGENT || (MODE == MODE_SPMV && !DOT), "the tangent is a plain SpMV with kappa := dkappa");
     static_assert(TANGENT || (!ROWS_ALL && !COLS_ALL), "only the tangent has rows and columns on the boundary");
-    constexpr double KPAD = ROWS_ALL ? 0.0 : 1.0;       // a cell outside the grid
+    constexpr double KPAD = ROWS_ALL || FACES ? 0.0 : 1.0;      // a cell outside the grid
     __shared__ double sX[4][MF_XS];
     __shared__ double sK[3][MF_KS];
     __shared__ double s_part[MF_NT / WAVE];
@@ -99,7 +112,8 @@ __global__ __launch_bounds__(MF_NT) void diffusion_mf(MfArgs a) {
         const int tx0 = tix * MF_TX, ty0 = tiy * MF_TY;
         const int gi = tx0 + lx, gj = ty0 + ly;
         const bool on_grid = gi < a.nx && gj < a.ny;
-        const bool inner_ij = gi >= 1 && gi <= a.nx - 2 && gj >= 1 && gj <= a.ny - 2;
+        const bool inner_ij = FACES ? gi >= box.lo[0] && gi <= box.hi[0] && gj >= box.lo[1] && gj <= box.hi[1]
+                                    : gi >= 1 && gi <= a.nx - 2 && gj >= 1 && gj <= a.ny - 2;
         const int64_t row_ij = (int64_t)gj * a.nx + gi;
 
         // the elements of the images this thread loads: e = tid and tid + MF_NT; -1: outside the grid (x: 0, kappa: KPAD)
@@ -176,7 +190,7 @@ __global__ __launch_bounds__(MF_NT) void diffusion_mf(MfArgs a) {
             const double* const xc = sX[(k + 1) & 3];
             const double x0 = xb[cx];
             double acc = 0.0, diag = 1.0;
-            if (ROWS_ALL ? on_grid : inner_ij && k >= 1 && k <= a.nz - 2) {
+            if (ROWS_ALL ? on_grid : inner_ij && (FACES ? k >= box.lo[2] && k <= box.hi[2] : k >= 1 && k <= a.nz - 2)) {
                 const double* const k0 = sK[(k + 2) % 3];   // cell plane k-1
                 const double* const k1 = sK[k % 3];
                 double K[2][2][2];      // K[dz][dy][dx]: cell (gi - 1 + dx, gj - 1 + dy, k - 1 + dz)
@@ -204,7 +218,20 @@ __global__ __launch_bounds__(MF_NT) void diffusion_mf(MfArgs a) {
                 t = t + se[1][0]; t = t + se[0][0]; t = t + se[0][1]; t = t + se[1][1]; t = t + se[2][1];
                 diag = mf_div6(t) * hh;
                 double azl, ayl, axl, axu, ayu, azu, ad = diag;
-                if constexpr (!ROWS_ALL && !COLS_ALL) {
+                if constexpr (FACES) {
+                    // as below with the box: a neighbour is a Dirichlet node if it has stepped out of the free range of its
+                    // axis (past the grid included) or if the row itself is outside that of another axis
+                    const bool bi = ROWS_ALL && !(gi >= box.lo[0] && gi <= box.hi[0]), bj = ROWS_ALL && !(gj >= box.lo[1] && gj <= box.hi[1]);
+                    const bool bz = ROWS_ALL && !(k >= box.lo[2] && k <= box.hi[2]);
+                    const bool mask = !COLS_ALL;
+                    azl = mask && (bi || bj || k - 1 < box.lo[2]) ? 0.0 : -(mf_div6(se[2][0]) * hh);
+                    ayl = mask && (bi || bz || gj - 1 < box.lo[1]) ? 0.0 : -(mf_div6(se[1][0]) * hh);
+                    axl = mask && (bj || bz || gi - 1 < box.lo[0]) ? 0.0 : -(mf_div6(se[0][0]) * hh);
+                    axu = mask && (bj || bz || gi + 1 > box.hi[0]) ? 0.0 : -(mf_div6(se[0][1]) * hh);
+                    ayu = mask && (bi || bz || gj + 1 > box.hi[1]) ? 0.0 : -(mf_div6(se[1][1]) * hh);
+                    azu = mask && (bi || bj || k + 1 > box.hi[2]) ? 0.0 : -(mf_div6(se[2][1]) * hh);
+                    if (mask && (bi || bj || bz)) ad = 0.0;
+                } else if constexpr (!ROWS_ALL && !COLS_ALL) {
                     // the stored entries -w, zero where the neighbour lies on the boundary
                     azl = k - 1 == 0 ? 0.0 : -(mf_div6(se[2][0]) * hh);
                     ayl = gj - 1 == 0 ? 0.0 : -(mf_div6(se[1][0]) * hh);
@@ -268,6 +295,16 @@ __global__ __launch_bounds__(MF_NT) void diffusion_mf(MfArgs a) {
     }
 }
 
+template <int MODE, bool DOT, bool TANGENT = false, bool ROWS_ALL = false, bool COLS_ALL = false>
+__global__ __launch_bounds__(MF_NT) void diffusion_mf(MfArgs a) {
+    mf_march<MODE, DOT, TANGENT, ROWS_ALL, COLS_ALL, false>(a, FreeBox{});
+}
+
+template <int MODE, bool DOT, bool TANGENT = false, bool ROWS_ALL = false, bool COLS_ALL = false>
+__global__ __launch_bounds__(MF_NT) void diffusion_mf_faces(MfFaceArgs fa) {
+    mf_march<MODE, DOT, TANGENT, ROWS_ALL, COLS_ALL, true>(fa.a, fa.box);
+}
+
 // Right-hand side (and, for the set-up paths that need it, 1 / diagonal) of the level gen_diffusion would store, without
 // the matrix: the same expressions in the same order, one thread per node.  f / dinv may be null.
 __global__ void gen_diffusion_rhs(DiffusionArgs d, double* f, double* dinv) {
@@ -277,14 +314,14 @@ __global__ void gen_diffusion_rhs(DiffusionArgs d, double* f, double* dinv) {
     const int kl = blockIdx.y;
     const int k = a.g.k0 + kl;
     const int64_t lr = (int64_t)kl * a.g.plane + (int64_t)j * a.g.nx + i;
-    const bool bnd = gen_on_boundary(a, i, j, k);
+    const bool bnd = !free_node(d.box, i, j, k);        // a Dirichlet node
     double se[3][2] = {{0.0, 0.0}, {0.0, 0.0}, {0.0, 0.0}};
     double diag = 1.0;
     if (!bnd) {
         double K[2][2][2];
         for (int dz = 0; dz < 2; ++dz)
             for (int dy = 0; dy < 2; ++dy)
-                for (int dx = 0; dx < 2; ++dx) K[dz][dy][dx] = diff_kappa(d, i - 1 + dx, j - 1 + dy, k - 1 + dz);
+                for (int dx = 0; dx < 2; ++dx) K[dz][dy][dx] = diff_kappa_in(d, i - 1 + dx, j - 1 + dy, k - 1 + dz);
         for (int s = 0; s < 2; ++s) {
             double t = 2.0 * K[0][0][s];
             t = t + K[0][1][s]; t = t + K[1][0][s]; t = t + 2.0 * K[1][1][s];
@@ -300,13 +337,14 @@ __global__ void gen_diffusion_rhs(DiffusionArgs d, double* f, double* dinv) {
         t = t + se[1][0]; t = t + se[0][0]; t = t + se[0][1]; t = t + se[1][1]; t = t + se[2][1];
         diag = (t / 6.0) * a.h;
     }
-    double b = bnd ? gen_g(a, i, j, k) : a.fh;
+    double b = bnd ? gen_g(a, i, j, k) : diff_load(d, i, j, k);
     if (!bnd) {
         // the axis offsets in the sorted order of the pattern: z-, y-, x-, x+, y+, z+
         const int off[6][3] = {{0, 0, -1}, {0, -1, 0}, {-1, 0, 0}, {1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
         for (int t = 0; t < 6; ++t) {
             const int ii = i + off[t][0], jj = j + off[t][1], kk = k + off[t][2];
-            if (!gen_on_boundary(a, ii, jj, kk)) continue;
+            if (ii < 0 || ii >= a.g.nx || jj < 0 || jj >= a.g.ny || kk < 0 || kk >= a.g.nz) continue;
+            if (free_node(d.box, ii, jj, kk)) continue;
             const int ax = off[t][0] != 0 ? 0 : (off[t][1] != 0 ? 1 : 2);
             const double s = se[ax][t >= 3 ? 1 : 0];
             const double w = (s / 6.0) * a.h;

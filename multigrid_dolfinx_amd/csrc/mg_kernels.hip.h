@@ -1317,15 +1317,61 @@ __global__ void gen_lattice(LatticeArgs a, double* vals, int* cols, double* dinv
 // coordinates equal, 1 otherwise.  The diagonal is the sum of the row's edge sums in ascending offset order, scaled the
 // same way (sum first, scale last: kappa == 1 gives gen_poisson's entries bit for bit).  Boundary treatment, right-hand
 // side and tile layout as gen_poisson.  poisson.diffusion_level is the host restatement of this arithmetic.
+//
+// The face set (mg_set_diffusion_faces): only the nodes on the faces of the set are Dirichlet nodes (identity rows, their
+// columns lifted).  Every other node is a free node, those on the remaining faces included, and gets the natural row: the
+// same sums with a cell outside the grid counting as +0.0, no column outside the grid, and the load fh * (T / 24.0), T the
+// number of Kuhn simplices at the node inside the grid (24 inside: fh).  The kernels take the set as a box of free nodes.
+struct FreeBox {
+    int lo[3], hi[3];       // per axis (x, y, z): a node is free iff lo <= its index <= hi on every axis
+};
+
+__host__ __device__ __forceinline__ bool free_node(const FreeBox& b, int i, int j, int k) {
+    return i >= b.lo[0] && i <= b.hi[0] && j >= b.lo[1] && j <= b.hi[1] && k >= b.lo[2] && k <= b.hi[2];
+}
+
+// faces: x- = 1, x+ = 2, y- = 4, y+ = 8, z- = 16, z+ = 32 (63: the whole boundary); a 2-D grid has one node along y
+inline FreeBox free_box(int faces, int nx, int ny, int nz) {
+    FreeBox b{};
+    const int n[3] = {nx, ny, nz};
+    for (int d = 0; d < 3; ++d) {
+        b.lo[d] = (faces >> (2 * d)) & 1 ? 1 : 0;
+        b.hi[d] = (faces >> (2 * d + 1)) & 1 ? n[d] - 2 : n[d] - 1;
+    }
+    if (ny == 1) { b.lo[1] = 0; b.hi[1] = 0; }
+    return b;
+}
+
 struct DiffusionArgs {
     GenArgs ga;             // grid, N, dim, prune, W, h, fh and the sorted offsets, as gen_poisson has them
     const double* kappa;    // cell planes [kc0, ...) along the slab axis (z in 3-D, y = k in 2-D), x fastest
     int kc0;
+    FreeBox box;            // the free nodes of the face set (3-D; the default and 2-D: the interior)
 };
 
 __device__ __forceinline__ double diff_kappa(const DiffusionArgs& a, int ci, int cj, int ck) {
     const int64_t N = a.ga.N;
     return a.kappa[((int64_t)(ck - a.kc0) * (a.ga.dim == 3 ? N : 1) + cj) * N + ci];
+}
+
+// kappa of a cell around a free node, +0.0 outside the grid (3-D)
+__device__ __forceinline__ double diff_kappa_in(const DiffusionArgs& a, int ci, int cj, int ck) {
+    const int N = a.ga.N;
+    return ci >= 0 && ci < N && cj >= 0 && cj < N && ck >= 0 && ck < N ? diff_kappa(a, ci, cj, ck) : 0.0;
+}
+
+// the load of a free node (3-D): fh * (T / 24.0), 6 simplices of an in-grid cell that has the node as its (0,0,0) or
+// (1,1,1) corner and 2 of every other in-grid cell around it
+__device__ __forceinline__ double diff_load(const DiffusionArgs& a, int i, int j, int k) {
+    const int N = a.ga.N;
+    int T = 0;
+    for (int dz = 0; dz < 2; ++dz)
+        for (int dy = 0; dy < 2; ++dy)
+            for (int dx = 0; dx < 2; ++dx) {
+                const int ci = i - 1 + dx, cj = j - 1 + dy, ck = k - 1 + dz;
+                if (ci >= 0 && ci < N && cj >= 0 && cj < N && ck >= 0 && ck < N) T += dx == dy && dy == dz ? 6 : 2;
+            }
+    return a.ga.fh * ((double)T / 24.0);
 }
 
 template <int R>
@@ -1339,7 +1385,7 @@ __global__ void gen_diffusion(DiffusionArgs d, double* vals, int* cols, double* 
         const int k = a.g.k0 + kl;
         const int64_t lr = (int64_t)kl * a.g.plane + (int64_t)j * a.g.nx + i;
         const size_t base = (size_t)(lr / (WAVE * R)) * a.W * (WAVE * R) + (size_t)(lr % (WAVE * R));
-        const bool bnd = gen_on_boundary(a, i, j, k);
+        const bool bnd = a.dim == 3 ? !free_node(d.box, i, j, k) : gen_on_boundary(a, i, j, k);     // a Dirichlet node
         // se[axis][side]: edge sums towards the lower (side 0) / upper (side 1) neighbour along axis 0 (i), 1 (j), 2 (k)
         double se[3][2] = {{0.0, 0.0}, {0.0, 0.0}, {0.0, 0.0}};
         double diag = 1.0;
@@ -1348,7 +1394,7 @@ __global__ void gen_diffusion(DiffusionArgs d, double* vals, int* cols, double* 
                 double K[2][2][2];      // K[dz][dy][dx]: cell (i - 1 + dx, j - 1 + dy, k - 1 + dz)
                 for (int dz = 0; dz < 2; ++dz)
                     for (int dy = 0; dy < 2; ++dy)
-                        for (int dx = 0; dx < 2; ++dx) K[dz][dy][dx] = diff_kappa(d, i - 1 + dx, j - 1 + dy, k - 1 + dz);
+                        for (int dx = 0; dx < 2; ++dx) K[dz][dy][dx] = diff_kappa_in(d, i - 1 + dx, j - 1 + dy, k - 1 + dz);
                 // the four cells of an edge, ascending index: other-axis offsets (0,0), (1,0), (0,1), (1,1), n = 2, 1, 1, 2
                 for (int s = 0; s < 2; ++s) {
                     double t = 2.0 * K[0][0][s];
@@ -1377,7 +1423,7 @@ __global__ void gen_diffusion(DiffusionArgs d, double* vals, int* cols, double* 
                 diag = t / 2.0;
             }
         }
-        double b = bnd ? gen_g(a, i, j, k) : a.fh;
+        double b = bnd ? gen_g(a, i, j, k) : (a.dim == 3 ? diff_load(d, i, j, k) : a.fh);
         for (int t = 0; t < a.noff; ++t) {
             const int di = a.off[t][0], dj = a.off[t][1], dk = a.off[t][2];
             const int ii = i + di, jj = j + dj, kk = k + dk;
@@ -1390,7 +1436,8 @@ __global__ void gen_diffusion(DiffusionArgs d, double* vals, int* cols, double* 
                 const int ax = di != 0 ? 0 : (dj != 0 ? 1 : 2);
                 const double s = se[ax][(di + dj + dk) > 0 ? 1 : 0];
                 const double w = a.dim == 3 ? (s / 6.0) * a.h : s / 2.0;
-                if (gen_on_boundary(a, ii, jj, kk)) b = b - (-w) * gen_g(a, ii, jj, kk);
+                const bool nb = a.dim == 3 ? !free_node(d.box, ii, jj, kk) : gen_on_boundary(a, ii, jj, kk);
+                if (nb) b = b - (-w) * gen_g(a, ii, jj, kk);
                 else v = -w;
             }
             if (v != 0.0) ++nz;
@@ -1745,7 +1792,10 @@ __host__ __device__ constexpr int kuhn_slot(int di, int dj, int dk) {
 }
 
 // Prolongation: v_f(2I + p) = v_c(I) for p = 0, 0.5 * (v_c(I) + v_c(I + p)) otherwise.  One thread per fine node; reads the
-// coarse planes K and K + 1 (as prolong_correct).  ERR written when KEEP, V += ERR when ADD.
+// coarse planes K and K + 1 (as prolong_correct).  ERR written when KEEP, V += ERR when ADD.  It interpolates onto every
+// fine node, boundary nodes included, so a face set (mg_set_diffusion_faces) needs no other kernel: a free fine node on a
+// no-flux face gets its interpolated correction, and a Dirichlet fine node interpolates coarse Dirichlet nodes only, whose
+// correction is zero.
 template <bool ADD, bool KEEP>
 __global__ void prolong_p1(Grid gc, Grid gf, const double* __restrict__ vc, double* __restrict__ vf, double* __restrict__ err) {
     int i, j;
@@ -1786,6 +1836,32 @@ __global__ void restrict_p1t(Grid gc, Grid gf, const double* __restrict__ rf, do
         for (int t = 0; t < Kuhn<DIM>::K; ++t) {
             const double term = (t == Kuhn<DIM>::C ? 1.0 : 0.5) * v[t];
             s = t == 0 ? term : s + term;
+        }
+    }
+    fc[gc.lead + (int64_t)kl * gc.plane + (int64_t)j * gc.nx + i] = s;
+}
+
+// restrict_p1t with a face set (3-D, whole levels; `box`: the free coarse nodes): a free coarse node sums the pattern, one
+// on a no-flux face included, with the offsets that leave the fine grid skipped -- the same order, multiply then add, the
+// first term that is there starting the sum.  Every in-grid 2I + d of a free coarse node is a free fine node.  A Dirichlet
+// coarse node takes the coincident fine value.
+__global__ void restrict_p1t_faces(Grid gc, Grid gf, FreeBox box, const double* __restrict__ rf, double* __restrict__ fc) {
+    int i, j;
+    if (!plane_node(gc, &i, &j)) return;
+    const int kl = blockIdx.y;
+    const int K = gc.k0 + kl;
+    const double* q = rf + gf.lead + (int64_t)(2 * K - gf.k0) * gf.plane + (int64_t)(2 * j) * gf.nx + 2 * i;
+    double s = q[0];
+    if (free_node(box, i, j, K)) {
+        bool first = true;
+#pragma unroll
+        for (int t = 0; t < Kuhn<3>::K; ++t) {
+            const int fi = 2 * i + kuhn_off<3>(t, 0), fj = 2 * j + kuhn_off<3>(t, 1), fk = 2 * K + kuhn_off<3>(t, 2);
+            if (fi < 0 || fi >= gf.nx || fj < 0 || fj >= gf.ny || fk < 0 || fk >= gf.nz) continue;
+            const double v = q[(int64_t)kuhn_off<3>(t, 2) * gf.plane + (int64_t)kuhn_off<3>(t, 1) * gf.nx + kuhn_off<3>(t, 0)];
+            const double term = (t == Kuhn<3>::C ? 1.0 : 0.5) * v;
+            s = first ? term : s + term;
+            first = false;
         }
     }
     fc[gc.lead + (int64_t)kl * gc.plane + (int64_t)j * gc.nx + i] = s;

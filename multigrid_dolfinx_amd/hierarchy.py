@@ -17,7 +17,7 @@ import scipy.sparse as sp
 from . import _capi
 from ._capi import (MG_RESTRICT_FULL_WEIGHTING, MG_RESTRICT_INJECTION, MG_VEC_ERR, MG_VEC_F, MG_VEC_R,
                     MG_VEC_V, check, load, ptr)
-from .poisson import grid_index_from_coords
+from .poisson import face_set, grid_index_from_coords
 
 __all__ = ["DeviceHierarchy", "jacobi_split", "csr_check"]
 
@@ -399,6 +399,20 @@ class DeviceHierarchy:
             check(self._lib.mg_refresh_diffusion_hierarchy(self._h, self._idx(top), dev.ptr, avg))
         finally:
             dev.free()
+
+    def set_diffusion_faces(self, dirichlet=("x-", "x+", "y-", "y+", "z-", "z+")):
+        """The faces of the unit cube that carry a Dirichlet condition in the diffusion levels generated from now on
+        (`mg_set_diffusion_faces`): names "x-" .. "z+" or the integer of `poisson.face_set`.  Nodes on the other faces are
+        free nodes with the natural (no-flux) rows.  3-D, whole handles; all six faces is the default.  An integer goes to
+        the library as it is, which refuses what is no face set."""
+        faces = int(dirichlet) if isinstance(dirichlet, (int, np.integer)) else face_set(dirichlet)
+        check(self._lib.mg_set_diffusion_faces(self._h, faces))
+
+    def diffusion_faces(self) -> int:
+        """The handle's face set as an integer (`mg_diffusion_faces`): x- = 1, x+ = 2, y- = 4, y+ = 8, z- = 16, z+ = 32."""
+        faces = C.c_int(0)
+        check(self._lib.mg_diffusion_faces(self._h, C.byref(faces)))
+        return int(faces.value)
 
     def level_matrix_free(self, level: int) -> bool:
         """True if the level keeps kappa instead of a matrix (`mg_level_matrix_free`)."""

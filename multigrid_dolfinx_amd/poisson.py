@@ -572,7 +572,49 @@ def _edge_sums_3d(kp, n1):
     return se, t
 
 
-def diffusion_level(N: int, dim: int, kappa, keep_zeros: bool = True) -> Level:
+FACE_BITS = {"x-": 1, "x+": 2, "y-": 4, "y+": 8, "z-": 16, "z+": 32}
+ALL_FACES = 63
+
+
+def face_set(dirichlet_faces) -> int:
+    """The face set of `mg_set_diffusion_faces` as its integer: x- = 1, x+ = 2, y- = 4, y+ = 8, z- = 16, z+ = 32.  Takes the
+    integer, None (all six) or names ("x-", "z+", ...)."""
+    if dirichlet_faces is None:
+        return ALL_FACES
+    if isinstance(dirichlet_faces, (int, np.integer)):
+        faces = int(dirichlet_faces)
+    else:
+        faces = 0
+        for name in dirichlet_faces:
+            if name not in FACE_BITS:
+                raise ValueError(f"unknown face {name!r}: the faces are " + ", ".join(FACE_BITS))
+            faces |= FACE_BITS[name]
+    if faces < 0 or faces > ALL_FACES:
+        raise ValueError(f"dirichlet_faces = {faces} is no face set (0..63)")
+    if faces == 0:
+        raise ValueError("dirichlet_faces = 0: without a Dirichlet face the operator is singular")
+    return faces
+
+
+def free_box(N: int, dirichlet_faces=ALL_FACES):
+    """(lo, hi) per axis (x, y, z): a node is a free node of the face set iff lo[d] <= c[d] <= hi[d] on every axis -- the
+    bounds the device kernels take instead of 1 and N - 1.  Every other node is a Dirichlet node."""
+    faces = face_set(dirichlet_faces)
+    lo = [1 if faces >> (2 * d) & 1 else 0 for d in range(3)]
+    hi = [N - 1 if faces >> (2 * d + 1) & 1 else N for d in range(3)]
+    return lo, hi
+
+
+def dirichlet_mask(N: int, dirichlet_faces=ALL_FACES) -> np.ndarray:
+    """True on the Dirichlet nodes of the face set (nodes on a face whose bit is set), (N + 1)^3 lexicographic."""
+    lo, hi = free_box(N, dirichlet_faces)
+    c = np.arange(N + 1)
+    fr = [(c >= lo[d]) & (c <= hi[d]) for d in range(3)]
+    free = fr[2][:, None, None] & fr[1][None, :, None] & fr[0][None, None, :]
+    return ~free.reshape(-1)
+
+
+def diffusion_level(N: int, dim: int, kappa, keep_zeros: bool = True, dirichlet_faces=ALL_FACES) -> Level:
     """The level `mg_gen_diffusion_level` generates, assembled on the host in the kernel's operation order (same bits), in
     the hand-off conventions of `lexicographic_level`.  `kappa` holds one positive value per cell: cube (ci, cj, ck) at
     `(ck * N + cj) * N + ci`, square (ci, cy) at `cy * N + ci`.  On the Kuhn mesh the P1 stiffness of -div(kappa grad u)
@@ -580,11 +622,21 @@ def diffusion_level(N: int, dim: int, kappa, keep_zeros: bool = True) -> Level:
     (2-D) over the cells holding the edge in ascending index (n_c = 2 where the cell's other two local coordinates at the
     edge are equal, else 1), the diagonal the sum of the row's edge sums in ascending offset order, scaled the same way.
     Identity rows, zeroed columns and the lifted right-hand side as `lexicographic_level`, which kappa == 1 reproduces bit
-    for bit."""
+    for bit.
+
+    `dirichlet_faces` (3-D; `face_set`, the set of `mg_set_diffusion_faces`): only nodes on those faces are identity rows.
+    A free node on another face gets the natural row: the same sums with a cell outside the grid counting as +0.0, no
+    column outside the grid, and the load fh * (T / 24.0) with T the number of Kuhn simplices at the node inside the grid
+    (6 for an in-grid cell of which the node is the (0,0,0) or (1,1,1) corner, 2 for every other; 24 inside).  63, the
+    default, is the level above byte for byte."""
+    faces = face_set(dirichlet_faces)
+    if faces != ALL_FACES and dim != 3:
+        raise ValueError("a face set other than all six faces is 3-D only")
     kap = _kappa_cells(kappa, N, dim)
     if np.any(~(kap > 0.0)) or not np.all(np.isfinite(kap)):
         raise ValueError("kappa must be positive and finite")
-    kp = np.pad(kap, 1, constant_values=1.0)            # node (i, ..) -> cells i - 1 + d: padded index i + d
+    # node (i, ..) -> cells i - 1 + d: padded index i + d (the pad is read by rows on the boundary only)
+    kp = np.pad(kap, 1, constant_values=1.0 if faces == ALL_FACES else 0.0)
     n1 = N + 1
     h = 1.0 / N
     if dim == 3:
@@ -603,15 +655,24 @@ def diffusion_level(N: int, dim: int, kappa, keep_zeros: bool = True) -> Level:
     ijk = [idx % n1, (idx // n1) % n1]
     if dim == 3:
         ijk.append(idx // (n1 * n1))
-    on_bnd = np.zeros(n, dtype=bool)
-    for c in ijk:
-        on_bnd |= (c == 0) | (c == N)
+    on_bnd = np.zeros(n, dtype=bool)            # the Dirichlet nodes
+    for d, c in enumerate(ijk):
+        on_bnd |= ((c == 0) & bool(faces >> (2 * d) & 1)) | ((c == N) & bool(faces >> (2 * d + 1) & 1))
     coords = np.zeros((n, 3))
     for d in range(dim):
         coords[:, d] = ijk[d] / N
     g = boundary_data(coords, dim)
     strides = [1, n1, n1 * n1][:dim]
-    b = np.where(on_bnd, g, source_term(dim) * h ** dim)
+    load = source_term(dim) * h ** dim
+    if faces != ALL_FACES:
+        inside = np.pad(np.ones((N, N, N)), 1, constant_values=0.0)
+        T = np.zeros(n)
+        for dz in (0, 1):
+            for dy in (0, 1):
+                for dx in (0, 1):
+                    T += (6.0 if dx == dy == dz else 2.0) * inside[dz:dz + n1, dy:dy + n1, dx:dx + n1].reshape(-1)
+        load = load * (T / 24.0)
+    b = np.where(on_bnd, g, load)
     valid, colv, valv = [], [], []
     for o in _offsets(dim):
         ok = np.ones(n, dtype=bool)
@@ -693,7 +754,7 @@ def _node_set_all(name, what: str) -> bool:
     return name == "all"
 
 
-def diffusion_dkappa(N: int, a, b, a_nodes: str = "interior", b_nodes: str = "interior") -> np.ndarray:
+def diffusion_dkappa(N: int, a, b, a_nodes: str = "interior", b_nodes: str = "interior", dirichlet_faces=ALL_FACES) -> np.ndarray:
     """d(a^T A(kappa) b) / d kappa_c for the N^3 cells of the 3-D `diffusion_level`, as `mg_diffusion_dkappa` computes it (same
     bits: explicit adds in the order of `dk_cell`, mg_diffusion_adj.hip.h).  `a`, `b`: nodal values in lexicographic order;
     their boundary entries count as 0 (boundary rows are identity rows and interior rows have no boundary column: that block
@@ -705,8 +766,13 @@ def diffusion_dkappa(N: int, a, b, a_nodes: str = "interior", b_nodes: str = "in
 
     `a_nodes`, `b_nodes` ("interior" / "all") are the masks of `mg_diffusion_dkappa_ex`, D(a, b; A, B)_c =
     d / d w_c (M_A a)^T A^(w) (M_B b) with A^ = `diffusion_natural_matrix`: "all" keeps the boundary entries of that
-    vector.  The mask acts on the values at the corners and nowhere else, so these are the device's bits as well."""
+    vector.  The mask acts on the values at the corners and nowhere else, so these are the device's bits as well.
+
+    `dirichlet_faces` (`face_set`): "interior" is the set of the free nodes of that face set -- the entries on the Dirichlet
+    nodes count as 0, those on free boundary nodes are kept.  63 is the boundary."""
     n1 = N + 1
+    lo, hi = free_box(N, dirichlet_faces)
+    box = tuple(slice(lo[d], hi[d] + 1) for d in (2, 1, 0))
 
     def corners(x, keep_boundary):
         v = np.array(x, dtype=np.float64).reshape(-1)
@@ -716,7 +782,7 @@ def diffusion_dkappa(N: int, a, b, a_nodes: str = "interior", b_nodes: str = "in
         m = v
         if not keep_boundary:
             m = np.zeros_like(v)
-            m[1:-1, 1:-1, 1:-1] = v[1:-1, 1:-1, 1:-1]
+            m[box] = v[box]
         return [[[m[dz:dz + N, dy:dy + N, dx:dx + N] for dx in (0, 1)] for dy in (0, 1)] for dz in (0, 1)]
 
     A, B = corners(a, _node_set_all(a_nodes, "a_nodes")), corners(b, _node_set_all(b_nodes, "b_nodes"))
@@ -738,7 +804,7 @@ def diffusion_dkappa(N: int, a, b, a_nodes: str = "interior", b_nodes: str = "in
     return np.ascontiguousarray((s * ((1.0 / N) / 6.0)).reshape(-1))
 
 
-def diffusion_apply_dkappa(N: int, dkappa, x, rows: str = "interior", cols: str = "interior") -> np.ndarray:
+def diffusion_apply_dkappa(N: int, dkappa, x, rows: str = "interior", cols: str = "interior", dirichlet_faces=ALL_FACES) -> np.ndarray:
     """(dA/dkappa . dkappa) x for the 3-D `diffusion_level`: the derivative of A(kappa) x in the direction `dkappa` (N^3 values in
     the cell order of `diffusion_level`, of any sign), as `mg_diffusion_apply_dkappa` computes it.  A is linear in kappa, so an
     interior row is the row of `diffusion_level` with kappa := dkappa -- the edge sums and the diagonal sum in its order,
@@ -753,18 +819,24 @@ def diffusion_apply_dkappa(N: int, dkappa, x, rows: str = "interior", cols: str 
     A^ = `diffusion_natural_matrix`.  rows = "all": a boundary row is the row of A^, summed like an interior row with a cell
     outside the grid counting as 0 and a neighbour outside it reading 0.  cols = "all" keeps the entries towards boundary
     neighbours; cols = "interior" zeroes every entry whose column is a boundary node, a boundary row's own diagonal
-    included."""
+    included.
+
+    `dirichlet_faces` (`face_set`): "interior" is the set of the free nodes of that face set, rows and columns alike.  A free
+    row on the boundary is the row of A^ (cells outside the grid count as 0, a neighbour outside it reads 0) with the
+    entries towards Dirichlet nodes zeroed; a Dirichlet row is 0 unless rows = "all".  63 is the boundary."""
     n1 = N + 1
+    lo, hi = free_box(N, dirichlet_faces)
+    all_faces = face_set(dirichlet_faces) == ALL_FACES
     rows_all, cols_all = _node_set_all(rows, "rows"), _node_set_all(cols, "cols")
     dk = _kappa_cells(dkappa, N, 3)
     v = np.array(x, dtype=np.float64).reshape(-1)
     if v.size != n1 ** 3:
         raise ValueError(f"vector has {v.size} entries, the level has {n1 ** 3} nodes")
     h = 1.0 / N
-    se, t = _edge_sums_3d(np.pad(dk, 1, constant_values=0.0 if rows_all else 1.0), n1)
+    se, t = _edge_sums_3d(np.pad(dk, 1, constant_values=0.0 if rows_all or not all_faces else 1.0), n1)
     idx = np.arange(n1 ** 3, dtype=np.int64)
     ijk = [idx % n1, (idx // n1) % n1, idx // (n1 * n1)]
-    on_face = [(c < 1) | (c > N - 1) for c in ijk]
+    on_face = [(c < lo[d]) | (c > hi[d]) for d, c in enumerate(ijk)]
     inner = ~(on_face[0] | on_face[1] | on_face[2])
     strides = (1, n1, n1 * n1)
     xp = np.concatenate([np.zeros(strides[2]), v, np.zeros(strides[2])])       # a neighbour outside the grid reads 0
@@ -779,11 +851,11 @@ def diffusion_apply_dkappa(N: int, dkappa, x, rows: str = "interior", cols: str 
 
     acc = np.zeros(n1 ** 3)
     for axis in (2, 1, 0):                      # z-, y-, x-
-        a = np.where(masked(axis, ijk[axis] - 1 <= 0), 0.0, -((se[axis][0] / 6.0) * h))
+        a = np.where(masked(axis, ijk[axis] - 1 < lo[axis]), 0.0, -((se[axis][0] / 6.0) * h))
         acc = a * nb(-strides[axis]) + acc
     acc = np.where(inner | cols_all, (t / 6.0) * h, 0.0) * v + acc
     for axis in (0, 1, 2):                      # x+, y+, z+
-        a = np.where(masked(axis, ijk[axis] + 1 >= N), 0.0, -((se[axis][1] / 6.0) * h))
+        a = np.where(masked(axis, ijk[axis] + 1 > hi[axis]), 0.0, -((se[axis][1] / 6.0) * h))
         acc = a * nb(strides[axis]) + acc
     return acc if rows_all else np.where(inner, acc, 0.0)
 
@@ -822,14 +894,14 @@ def diffusion_natural_matrix(N: int, cells) -> sp.csr_matrix:
     return A
 
 
-def diffusion_lift(N: int, kappa, g) -> np.ndarray:
+def diffusion_lift(N: int, kappa, g, dirichlet_faces=ALL_FACES) -> np.ndarray:
     """A_IB(kappa) g_B on interior rows, 0 on boundary rows: T(kappa, g_B; interior, all) with g_B = `g` on the boundary and 0
     inside.  The right-hand side of -div(kappa grad u) = f with u = g on the boundary is f - lift on interior rows (and g on
-    the identity rows), as `diffusion_level` folds `boundary_data` into its own."""
+    the identity rows), as `diffusion_level` folds `boundary_data` into its own.  With `dirichlet_faces` (`face_set`) the
+    boundary is the set of its Dirichlet nodes and the interior that of its free nodes."""
     n1 = N + 1
     gv = np.array(g, dtype=np.float64).reshape(-1)
     if gv.size != n1 ** 3:
         raise ValueError(f"vector has {gv.size} entries, the level has {n1 ** 3} nodes")
-    gb = gv.reshape(n1, n1, n1).copy()
-    gb[1:-1, 1:-1, 1:-1] = 0.0
-    return diffusion_apply_dkappa(N, kappa, gb.reshape(-1), "interior", "all")
+    gb = np.where(dirichlet_mask(N, dirichlet_faces), gv, 0.0)
+    return diffusion_apply_dkappa(N, kappa, gb, "interior", "all", dirichlet_faces)

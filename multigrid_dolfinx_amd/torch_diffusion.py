@@ -18,6 +18,7 @@ import numpy as np
 import torch
 
 from .hierarchy import DeviceHierarchy
+from .poisson import ALL_FACES, dirichlet_mask, face_set
 
 __all__ = ["DiffusionSolver", "NotConverged"]
 
@@ -75,10 +76,18 @@ class DiffusionSolver:
 
     `warm_start=True` keeps the last forward and the last adjoint solution and starts the next solve of each kind from
     them instead of from zero (kappa that moves a little between solves).  The stopping test is relative to the
-    right-hand side either way, so the gradients are those of the converged solve."""
+    right-hand side either way, so the gradients are those of the converged solve.
+
+    `dirichlet_faces` (None: all six; names "x-" .. "z+" or the integer of `poisson.face_set`): only those faces carry the
+    Dirichlet condition (`DeviceHierarchy.set_diffusion_faces`), the others are no-flux faces whose nodes are free nodes.
+    Everything above then reads with "boundary" = the Dirichlet nodes and "interior" = the free nodes: `g` is read on the
+    Dirichlet nodes only and gets a zero gradient elsewhere, and `f` on a free boundary node is a genuine load entry -- where
+    prescribed flux data, the integral of q phi_i over the face, goes.  The derivative algebra and the solve counts are
+    the same."""
 
     def __init__(self, N: int, n_levels: int, averaging: str = "arithmetic", matrix_free_min_rows: Optional[int] = None,
-                 rtol: float = 1e-10, max_iter: int = 200, device: int = 0, warm_start: bool = False, **set_params):
+                 rtol: float = 1e-10, max_iter: int = 200, device: int = 0, warm_start: bool = False, dirichlet_faces=None,
+                 **set_params):
         if n_levels < 2 or N % (1 << (n_levels - 1)):
             raise ValueError("N must be a multiple of 2^(n_levels - 1), with at least two levels")
         self.N, self.top = int(N), n_levels - 1
@@ -92,13 +101,16 @@ class DiffusionSolver:
         params["restriction"] = "p1_transpose"
         self.hierarchy.set_params(**params)
         self.hierarchy.set_prolongation("p1")
+        self.dirichlet_faces = face_set(dirichlet_faces)
+        if self.dirichlet_faces != ALL_FACES:
+            self.hierarchy.set_diffusion_faces(self.dirichlet_faces)
         self._generation = 0
         self._generated = False         # a hierarchy call has generated the levels: a device kappa can refresh them
         self.last_generate = None       # "host" / "device" / "refresh": how the last kappa reached the hierarchy
         self.warm_start = bool(warm_start)
         self._warm = {}                 # "forward" / "adjoint": the last solution of that kind (warm_start)
         self._last_operator = None      # the _Operator of the last `solve`: what `tangent` solves again on
-        self._boundary = None           # the mask of the boundary nodes on the device (solves with g)
+        self._boundary = None           # the mask of the Dirichlet nodes on the device (solves with g)
         self.n_solves = 0               # mg_pcg calls so far: what a product costs (a Hessian-vector product: four)
         self.last_iterations = {}       # "forward" / "adjoint" / "tangent": iterations of the last solve of that kind
         self.last_residual = {}         # ... and ||r|| / ||rhs|| of mg_pcg's recursion where it stopped (None: no iteration was needed)
@@ -173,12 +185,10 @@ class DiffusionSolver:
         return self._generation
 
     def _boundary_mask(self) -> torch.Tensor:
-        """True on the boundary nodes, (N + 1)^3 lexicographic, on the solver's device (built by the first solve with g)."""
+        """True on the Dirichlet nodes -- the boundary nodes, or those on `dirichlet_faces` -- (N + 1)^3 lexicographic, on the
+        solver's device (built by the first solve with g)."""
         if self._boundary is None:
-            n1 = self.N + 1
-            m = torch.ones((n1, n1, n1), dtype=torch.bool, device=self.device)
-            m[1:-1, 1:-1, 1:-1] = False
-            self._boundary = m.reshape(-1)
+            self._boundary = torch.from_numpy(dirichlet_mask(self.N, self.dirichlet_faces)).to(self.device)
         return self._boundary
 
     def _put_operator(self, kappa: torch.Tensor) -> "_Operator":
