@@ -510,6 +510,8 @@ int mg_galerkin_hierarchy(mg_handle h, int top_level);
  *     "fuse_k5_min_rows"   ... more than four only on levels with at least this many rows (67108864: on 257^3 rows four
  *                          sweeps per pass measured best)
  *     "fuse_k_nt_store"    non-temporal stores of that march's result (experiment) (0)
+ *     "fuse_k_min_side"    ... on whole levels whose grid lines and planes hold at least this many nodes / lines (32, like the other
+ *                          plane marches; 16..32 -- tests: grids of a single tile whose lines end inside it)
  *     "fuse_k_tail"        the tiles left over for a last, nearly empty round of workgroups (fewer tiles than half the CUs) are cut
  *                          into shorter plane segments that fill that round once (1); bit-identical
  *     "fuse_k_small_tiles" 64 x 24 tiles (shape 4) on levels whose planes hold fewer 64 x 48 tiles than the GPU has CUs (0:

@@ -345,6 +345,7 @@ struct mg_context {
     int64_t fuse_k5_min_rows = (int64_t)1 << 26;       // ... five sweeps per pass on levels with at least this many rows (257^3: four measured best)
     int64_t fuse_k4_min_rows = 0;                      // ... more than three sweeps per pass on levels with at least this many rows
     int fuse_k_nt_store = 0;        // ... non-temporal stores of its result (experiment)
+    int fuse_k_min_side = 32;       // ... the shortest grid lines / fewest lines per plane of a whole level that pass takes (tests: 16)
     int fuse_k_tail = 1;            // ... the tiles left over for a last, nearly empty round of workgroups get shorter plane segments
     int fuse_k_small_tiles = 0;     // ... 64 x 24 tiles (shape 4) on levels whose planes hold fewer 64 x 48 tiles than there are CUs
     int fuse_k_pf = 1;              // ... register sets for the planes of x that arrive (2: x staged a step longer, K = 3 only; measured no faster)
@@ -1241,9 +1242,9 @@ int64_t min_slab_rows(const Level& L) {
     return (int64_t)nk * L.g.plane;
 }
 
-bool fused_sweeps_ok(const mg_context* c, const Level& L, bool ignore_size = false) {
+bool fused_sweeps_ok(const mg_context* c, const Level& L, bool ignore_size = false, int min_side = 32) {
     if (!c->fuse_sweeps || !L.sdia || L.wu != 4 || L.flat) return false;
-    if (L.g.nx < 32 || L.g.ny < 32 || min_slab_rows(L) < 8 * L.g.plane) return false;    // zero slack >= 3 slices, slabs >= 8 planes
+    if (L.g.nx < min_side || L.g.ny < min_side || min_slab_rows(L) < 8 * L.g.plane) return false;    // zero slack >= 3 slices, slabs >= 8 planes
     if (L.up[1] != 1 || L.up[2] != L.g.nx || (int64_t)L.up[3] != L.g.plane) return false;
     return ignore_size || min_slab_rows(L) >= c->fuse_min_rows;
 }
@@ -1549,7 +1550,9 @@ bool sweepsk_ok(const mg_context* c, const Level& L, bool ignore_size = false) {
     if (slab && (L.hd < 2 || L.cls_halo < 0 || c->halo_planes != 1)) return false;
     if (!ignore_size && (slab ? min_slab_rows(L) < c->fuse_k_slab_min_rows : L.nloc < c->fuse_k_min_rows)) return false;
     // (the size test of the K-sweep pass is the one above: "fuse_min_rows" is the pair pass's)
-    return fused_sweeps_ok(c, L, true) && L.g.nk >= 8;
+    // (whole levels with classes only: the march reads x, f and the class bytes, all padded by vec_reach whatever nx is)
+    const int side = slab || L.cls_escape ? 32 : c->fuse_k_min_side;
+    return fused_sweeps_ok(c, L, true, side) && L.g.nk >= 8;
 }
 
 // sweeps per pass on a whole level (with the 64 x 32 tiles of 16 waves five sweeps per pass measured best on 1025^3 and 513^3
@@ -4215,6 +4218,9 @@ int mg_set_tuning(mg_handle c, const char* key, int64_t value) {
         c->fuse_k4_min_rows = value;
     } else if (k == "fuse_k_nt_store") {
         c->fuse_k_nt_store = value != 0;
+    } else if (k == "fuse_k_min_side") {
+        if (value < 16 || value > 32) return fail("fuse_k_min_side must be in 16..32");
+        c->fuse_k_min_side = (int)value;
     } else if (k == "fuse_k_tail") {
         if (value < 0) return fail("fuse_k_tail must be >= 0");
         c->fuse_k_tail = (int)value;            // (> 1: the number of resident workgroups to plan for -- tests)

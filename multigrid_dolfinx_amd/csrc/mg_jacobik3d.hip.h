@@ -106,6 +106,19 @@ template <int K, int NW, int LPW, int M, int TR, bool ESC = false> constexpr siz
 
 // (jk3_from_west / jk3_from_east -- the value of the lane next door through DPP -- live in mg_jacobi2.hip.h)
 
+// Level caps.  Level t is valid on the tile lines [t - 1, EY - t] only (level 0 has the halo lines -1 and EY too, the result
+// exists on [K - 1, EY - K]), so the highest level a line takes part in is cap(ey) = min(ey + 1, EY - ey, K): whatever is
+// computed above it reaches no result.  A line belongs to one wave, so the caps of a wave's lines are the same for all its
+// lanes and fixed for the launch: the straight-line forms of a step exist once per KIND of wave -- the waves whose lines
+// all have cap K (`jk3_caps<K, EY, -1>`) and one kind for each wave that has a line with a lower cap (E0: its first line).
+template <int K, int EY, int E0> struct jk3_caps {
+    static constexpr int of(int l) {      // of the wave's line l
+        if (E0 < 0) return K;
+        const int ey = E0 + l, a = ey + 1 < EY - ey ? ey + 1 : EY - ey;
+        return a < K ? a : K;
+    }
+};
+
 template <int K, int NW, int LPW, int M, bool DPP, int PF, int TR, bool ESC = false, bool B1 = false>
 __device__ __forceinline__ void jk3_body(const JK3Args& a) {
     constexpr int EX = 64 * M, EY = NW * LPW, NC = M * LPW, IMG = (EY + 2) * EX;
@@ -218,6 +231,43 @@ __device__ __forceinline__ void jk3_body(const JK3Args& a) {
         if (lane + 64 * (c % M) > a.nx + 1 - tx0 || line < -2 || line > a.ny + 1) standin |= 1u << c;
     }
     const bool wlo = wave == 0, whi = wave == NW - 1;
+    // Level caps (jk3_caps) on the 64 x 32 tiles of sixteen waves, two lines each (tile shapes 7 and 8): the first two and the
+    // last two waves have lines with a cap below K (K = 3: the first and the last).  A cell with cap m < K computes the levels
+    // 1 .. m, still hands its level-m value to the image -- the line next to it, whose cap is m + 1, reads it as its -nx / +nx
+    // term -- and does nothing above: those partial sums and image slots keep their zeros and nothing reads them.
+    constexpr bool CAPS = B1 && NW == 16 && LPW == 2 && M == 1 && K >= 3;
+    using caps_all = jk3_caps<K, EY, -1>;
+    using caps_w0 = jk3_caps<K, EY, 0>;
+    using caps_w1 = jk3_caps<K, EY, LPW>;
+    using caps_w2 = jk3_caps<K, EY, EY - 2 * LPW>;
+    using caps_w3 = jk3_caps<K, EY, EY - LPW>;
+    constexpr bool CAPS1 = CAPS && (caps_w1::of(0) < K || caps_w1::of(LPW - 1) < K);
+    constexpr bool CAPS2 = CAPS && (caps_w2::of(0) < K || caps_w2::of(LPW - 1) < K);
+    // 0: all lines have cap K (one compare and a branch not taken in front of each phase); 1 .. 4: the waves above
+    const int wkind = !CAPS ? 0 : wave == 0 ? 1 : wave == NW - 1 ? 4 : (CAPS1 && wave == 1) ? 2 : (CAPS2 && wave == NW - 2) ? 3 : 0;
+    auto by_caps = [&](auto&& fn) __attribute__((always_inline)) {
+        if constexpr (CAPS) {
+            if (__builtin_expect(wkind != 0, 0)) {
+                if (wkind == 1) fn(caps_w0{});
+                else if (wkind == 4) fn(caps_w3{});
+                else if constexpr (CAPS1 && CAPS2) {
+                    if (wkind == 2) fn(caps_w1{});
+                    else fn(caps_w2{});
+                }
+                return;
+            }
+        }
+        fn(caps_all{});
+    };
+    // (general form: the same caps at run time, one scalar register per cell, compared where a level is reached -- the pin
+    //  keeps the compiler from holding every comparison's outcome in a register pair for the whole march)
+    auto cap_of = [&](int c) -> int {
+        if constexpr (!CAPS) return K;
+        const int ey = ey0 + c / M;
+        int cap = min(min(ey + 1, EY - ey), K);
+        asm volatile("" : "+v"(cap));
+        return __builtin_amdgcn_readfirstlane(cap);
+    };
 
     // Addresses: `uniform base of the plane + a byte offset fixed for the whole march` (see j2c_body).  Lines are
     // clamped to [-2, ny + 1], cells past the end of their grid line to the cell behind it, planes to the slack planes.
@@ -350,8 +400,9 @@ __device__ __forceinline__ void jk3_body(const JK3Args& a) {
     // on the cell's grid line (tile rows along the y boundary), away from the first and last planes: the entries of each cell's
     // row come from the class table once per cell and phase.  (Until the y boundary took this form too its tiles ran the
     // general one, 1.6 x slower -- and on a level with one round of workgroups, 257^3, the slowest tiles ARE the launch.)
-    auto phase_a_fast = [&](auto col_tag, const double (&X)[NC]) __attribute__((always_inline)) {
+    auto phase_a_fast = [&](auto col_tag, auto caps, const double (&X)[NC]) __attribute__((always_inline)) {
         constexpr bool COL = decltype(col_tag)::value;
+        using CAP = decltype(caps);
 #pragma unroll
         for (int r = 0; r < M; ++r) {
 #pragma unroll
@@ -366,6 +417,10 @@ __device__ __forceinline__ void jk3_body(const JK3Args& a) {
                 double nw = X[c];
 #pragma unroll
                 for (int t = 1; t <= K; ++t) {
+                    if (t > CAP::of(l)) {       // (above the line's cap: its last level goes to the image, nothing else)
+                        if (t == CAP::of(l) + 1) (B1 ? limg(bcur, t - 1) : image(t - 1))[iw] = nw;
+                        continue;
+                    }
                     if constexpr (B1) {
                         const double wd = t == 1 ? XP[c] : limg(bprev, t - 1)[iw];
                         const double s = fma(k6, nw, acc[t - 1][c]);      // +P
@@ -383,14 +438,15 @@ __device__ __forceinline__ void jk3_body(const JK3Args& a) {
                     img[iw] = nw;
                     nw = o;
                 }
-                if (k_store && (inT >> c & 1u)) store(c, nw);
+                if (CAP::of(l) == K && k_store && (inT >> c & 1u)) store(c, nw);
             }
         }
     };
     // (phase B comes in K pieces, one per level, so that the loads can go out in COMMON code between them: a load issued
     //  inside the branches of the three forms makes the compiler spill hundreds of registers)
-    auto phase_b_fast = [&](auto col_tag, const int t, const double (&X)[NC]) __attribute__((always_inline)) {
+    auto phase_b_fast = [&](auto col_tag, auto caps, const int t, const double (&X)[NC]) __attribute__((always_inline)) {
         constexpr bool COL = decltype(col_tag)::value;
+        using CAP = decltype(caps);
         const double* const img = B1 ? limg(bcur, t > 1 ? t - 1 : 1) : image(t - 1);
         double v[LPW][M], ys[M], yn[M];
 #pragma unroll
@@ -409,6 +465,7 @@ __device__ __forceinline__ void jk3_body(const JK3Args& a) {
         }
 #pragma unroll
         for (int l = 0; l < LPW; ++l) {
+            if (t > CAP::of(l)) continue;       // (the line has no level t: the reads only it needed go with it)
             double yw[M], ye[M];
             if constexpr (DPP) {
                 double fw[M], fe[M];
@@ -453,10 +510,15 @@ __device__ __forceinline__ void jk3_body(const JK3Args& a) {
             double nw = X[c];
             int pc = k_plane + shof(c);
             asm volatile("" : "+v"(pc));            // (one register per cell and step, not one per cell and level for the whole march)
+            const int cap = cap_of(c);
 #pragma unroll
             for (int t = 1; t <= K; ++t) {
                 const int j = K - t;                                  // ring index of the plane being finished
                 double* const img = B1 ? limg(bcur, t > 1 ? t - 1 : 1) : image(t - 1);
+                if (CAPS && t > cap) {
+                    if (t == cap + 1) img[iw] = nw;
+                    continue;
+                }
                 const double wd = B1 ? (t == 1 ? XP[B1 ? c : 0] : limg(bprev, t - 1)[iw]) : img[iw];
                 const dvec2_t t67 = reinterpret_cast<const dvec2_t*>(sT + CLS_W * cls_now(j, c))[3];
                 const dvec2_t t01 = reinterpret_cast<const dvec2_t*>(sT + CLS_W * cls_now(j + 1, c))[0];
@@ -490,6 +552,7 @@ __device__ __forceinline__ void jk3_body(const JK3Args& a) {
         }
 #pragma unroll
         for (int c = 0; c < NC; ++c) {
+            if (CAPS && t > cap_of(c)) continue;
             const int iw = lwof(c);
             double ys, yw, yd, ye, yn;
             if (B1 && t == 1) {
@@ -618,9 +681,15 @@ __device__ __forceinline__ void jk3_body(const JK3Args& a) {
         }
         if (a.force_form >= 0) form = a.force_form;
         // ---- phase A: finish plane k+K-t of level t, t = 1 .. K; start the plane above it ----
-        if (form == 0) phase_a_fast(std::false_type{}, X);
-        else if (form == 1) phase_a_fast(std::true_type{}, X);
-        else phase_a_general(X);
+        if constexpr (CAPS) {
+            if (form == 0) by_caps([&](auto caps) __attribute__((always_inline)) { phase_a_fast(std::false_type{}, caps, X); });
+            else if (form == 1) by_caps([&](auto caps) __attribute__((always_inline)) { phase_a_fast(std::true_type{}, caps, X); });
+            else phase_a_general(X);
+        } else {
+            if (form == 0) phase_a_fast(std::false_type{}, caps_all{}, X);
+            else if (form == 1) phase_a_fast(std::true_type{}, caps_all{}, X);
+            else phase_a_general(X);
+        }
         if constexpr (B1) {
 #pragma unroll
             for (int c = 0; c < NC; ++c) XP[c] = X[c];
@@ -665,9 +734,15 @@ __device__ __forceinline__ void jk3_body(const JK3Args& a) {
         };
 #pragma unroll
         for (int t = 1; t <= K; ++t) {
-            if (form == 0) phase_b_fast(std::false_type{}, t, X);
-            else if (form == 1) phase_b_fast(std::true_type{}, t, X);
-            else phase_b_general(t, X);
+            if constexpr (CAPS) {
+                if (form == 0) by_caps([&](auto caps) __attribute__((always_inline)) { phase_b_fast(std::false_type{}, caps, t, X); });
+                else if (form == 1) by_caps([&](auto caps) __attribute__((always_inline)) { phase_b_fast(std::true_type{}, caps, t, X); });
+                else phase_b_general(t, X);
+            } else {
+                if (form == 0) phase_b_fast(std::false_type{}, caps_all{}, t, X);
+                else if (form == 1) phase_b_fast(std::true_type{}, caps_all{}, t, X);
+                else phase_b_general(t, X);
+            }
             issue(t - 1, K);
         }
         if constexpr (!B1) __syncthreads();
