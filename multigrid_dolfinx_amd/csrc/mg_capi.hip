@@ -22,6 +22,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <type_traits>
 #include <vector>
@@ -62,13 +63,13 @@ int check_csr(int64_t n_rows, int64_t n_cols, int64_t nnz, const void* indptr, i
     return why.empty() ? 0 : fail(why);
 }
 
-// A device vector in local lexicographic storage: [pad | lower halo | owned rows | upper halo],
-// padded so that the first owned row is 32-byte aligned (the tile kernels load R rows per lane).
-struct DVector {
-    double* raw = nullptr;
-    double* base = nullptr;     // start of [lower halo | owned | upper halo]
-    double* rows = nullptr;     // first owned row = base + lead
-};
+}  // namespace
+
+// DevBuf, DVector, DevTemp: who owns device memory.  The header opens an anonymous namespace of its own and uses HIP_TRY, MG_TRY
+// and fail() from above (so that a test can compile it against a stand-in for HIP): hence the namespace closed and reopened here.
+#include "mg_devbuf.h"
+
+namespace {
 
 struct RcclApi {
     void* lib = nullptr;
@@ -158,43 +159,42 @@ struct Level {
     bool flat = false;           // no grid structure (stand-alone smoother on any matrix)
     int W = 0, R = 1;
     int64_t nslices = 0;
-    double* vals = nullptr;
-    int* cols = nullptr;                    // freed once the offset codes exist
-    unsigned long long* codes = nullptr;    // offset-coded columns (see mg_kernels.hip.h)
-    int* offsets = nullptr;
+    DevBuf<double> vals;
+    DevBuf<int> cols;                    // freed once the offset codes exist
+    DevBuf<unsigned long long> codes;    // offset-coded columns (see mg_kernels.hip.h)
+    DevBuf<int> offsets;
     int ntable = 0, dcode = 0;
     bool coded = false;
     bool rb_ok = false;                     // index parity is a valid red-black colouring of the matrix
     int mc_ok = -1;                         // the nine lattice colours are a valid colouring of the matrix (-1: not checked yet)
     // symmetric diagonal storage (replaces vals + codes when the matrix is bit-for-bit symmetric)
-    double* dvals = nullptr;
+    DevBuf<double> dvals;
     bool sdia = false;
     int wu = 0;
     int up[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     int64_t mlead = 0, mslices = 0;
     // row classes of the symmetric diagonal storage (mg_jacobi2.hip.h): one byte per row + a 256 x 8 table of full rows
-    unsigned char* cls = nullptr;
-    double* ctab = nullptr;
+    DevBuf<unsigned char> cls;
+    DevBuf<double> ctab;
     int ncls = 0;
     // stencil classes of an offset-coded level (mg_kernels.hip.h, ell_cls_apply): one byte per row + (offset, value) lists
-    unsigned char* scls = nullptr;
-    int* s_off = nullptr;
-    double* s_val = nullptr;
-    int* s_cnt = nullptr;
+    DevBuf<unsigned char> scls;
+    DevBuf<int> s_off;
+    DevBuf<double> s_val;
+    DevBuf<int> s_cnt;
     int nscls = 0;
     // ... and what the plane march of wide lattice stencils needs (mg_lattice.hip.h): entries as (di, dj, dk), the
     // most frequent classes
-    int* s_pack = nullptr;
+    DevBuf<int> s_pack;
     int lm_ntop = 0;
     int lm_top[LM_K] = {0, 0, 0, 0, 0, 0, 0, 0};
     int cmain = 0;                          // the most frequent class and its entries (passed to the kernels by value)
     double cm[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    int64_t cls_lead = 0, cls_rows = 0;     // cls[row + cls_lead], zero padding of cls_lead entries on both sides
-    double* dinv = nullptr;
+    int64_t cls_lead = 0;                   // cls[row + cls_lead], zero padding of cls_lead entries on both sides
+    DevBuf<double> dinv;
     // matrix-free diffusion level (mg_diffusion_mf.hip.h): kappa of the N^3 cells is all the matrix there is
     bool mf = false;
-    double* kappa = nullptr;
-    int64_t kappa_n = 0;
+    DevBuf<double> kappa;
     int faces = MG_FACES_ALL;               // the face set a generated diffusion level was built with (mg_set_diffusion_faces)
     bool diffusion_hierarchy = false;       // generated by one of the diffusion hierarchy entries: mg_refresh_diffusion_hierarchy may renew it
     DVector v, v2, f, err, ftrue;
@@ -204,7 +204,7 @@ struct Level {
     // matrix and the handle's settings) and the caller's interval for this level (cheb_user_lmax > 0: used instead)
     bool cheb_est_ok = false;
     double cheb_lmax_est = 0.0, cheb_user_lmin = 0.0, cheb_user_lmax = 0.0;
-    int* perm = nullptr;
+    DevBuf<int> perm;
     int p1_ok = -1;                         // stencil offsets within the Kuhn pattern of the P1 transfers (-1: not checked yet)
     std::vector<int> h_offsets;             // the offset table (linear offsets) of an offset-coded level, host copy
     unsigned long long nnz_stored = 0, nnz_nonzero = 0;
@@ -218,10 +218,10 @@ struct Level {
 struct DirectSolver {
     bool tried = false, ok = false;
     BtGeom g{};
-    double* T = nullptr;                    // nb dense p x p inverses of the Schur complements
-    int *lcol = nullptr, *ucol = nullptr;   // couplings, nb * p * W each
-    double *lval = nullptr, *uval = nullptr;
-    double *y = nullptr, *x = nullptr, *w = nullptr;
+    DevBuf<double> T;                       // nb dense p x p inverses of the Schur complements
+    DevBuf<int> lcol, ucol;                 // couplings, nb * p * W each
+    DevBuf<double> lval, uval;
+    DevBuf<double> y, x, w;
 };
 
 // One captured V-cycle (hipGraph): valid for a level, a parameter epoch and a ping-pong state.
@@ -269,19 +269,17 @@ struct mg_context {
     unsigned chunk = 8;         // XCD chunk of the block -> tile map
     int pcg_chunk = 16;
     // scratch
-    double* partials = nullptr;     // 2 * kMaxParts doubles
-    double* scalars = nullptr;      // 8 doubles
-    int* done = nullptr;
+    DevBuf<double> partials;        // 2 * kMaxParts doubles
+    DevBuf<double> scalars;         // 8 doubles
+    DevBuf<int> done;
     double* h_scalars = nullptr;    // pinned, 8 doubles + flag
-    double *pcg_r = nullptr, *pcg_z = nullptr, *pcg_q = nullptr, *pcg_part_a = nullptr, *pcg_part_b = nullptr;
+    DevBuf<double> pcg_r, pcg_z, pcg_q, pcg_part_a, pcg_part_b;     // the coarse CG, sized for level 0 (they go with it: free_level)
     DVector pcg_p;
     int pcg_parts = 0, pcg_parts_a = 0;
     int pcg_predict = 0;
-    // mg_pcg: scalars, folded / slab-reduced sums and the step kernels' partial sums (fcg_work, fcg_work_n doubles); the
-    // SpMV's partial sums of p.q (fcg_spmv, fcg_spmv_n doubles: one per block of the level's SpMV)
-    double* fcg_work = nullptr;
-    double* fcg_spmv = nullptr;
-    int64_t fcg_work_n = 0, fcg_spmv_n = 0;
+    // mg_pcg: scalars, folded / slab-reduced sums and the step kernels' partial sums (fcg_work); the
+    // SpMV's partial sums of p.q (fcg_spmv: one per block of the level's SpMV, grown on demand)
+    DevBuf<double> fcg_work, fcg_spmv;
     int use_graph = 1;              // replay whole V-cycles as hipGraphs (single GPU, direct coarsest solve)
     int comm_priority = 1;          // communication stream created with the highest priority (MG_COMM_PRIORITY=0: lowest)
     int lattice_march = 1;          // wide lattice stencils (P2 levels) as a plane march with x in LDS (mg_lattice.hip.h)
@@ -367,14 +365,14 @@ struct mg_context {
     // the reference's L2(Omega) norms (res_calculator / err_calculator, multigrid.py:203-218) on the device: a mass
     // matrix M of one level (mg_set_mass_csr), optionally the exact solution's nodal values (mg_set_exact)
     // table prolongation (mg_set_prolongation_table; null: the reference's bilinear / trilinear interpolation)
-    int* ptab_count = nullptr;
+    DevTemp ptab_count;                     // (int; the transfer tables are owned but not counted)
     int p1_prolong = 0;                     // mg_set_prolongation_p1: the P1 natural embedding (excludes the table)
-    int* rtab_count = nullptr;              // table restriction (mg_set_restriction_table), MG_RESTRICT_TABLE
-    int* rtab_off = nullptr;
-    double* rtab_w = nullptr;
+    DevTemp rtab_count;                     // table restriction (mg_set_restriction_table), MG_RESTRICT_TABLE: int
+    DevTemp rtab_off;                       // int
+    DevTemp rtab_w;                         // double
     int rtab_m = 0;
-    int* ptab_off = nullptr;
-    double* ptab_w = nullptr;
+    DevTemp ptab_off;                       // int
+    DevTemp ptab_w;                         // double
     Level mass;
     int mass_level = -1;
     DVector mass_out, diff, uexact;
@@ -384,8 +382,7 @@ struct mg_context {
     struct SmootherCount { int64_t launches = 0, sweeps = 0, tail = 0; };
     std::vector<std::array<SmootherCount, MG_PATH_COUNT>> smoother_counts;
     int jk3_tail = 0;               // the last launch of the K-sweep march split off a last round of tiles (a.ta < ntile)
-    double* stage = nullptr;        // device staging for host vectors (caller numbering)
-    int64_t stage_elems = 0;
+    DevBuf<double> stage;           // device staging for host vectors (caller numbering)
     int64_t bytes = 0;
     Comm comm;
     hipDeviceProp_t prop{};
@@ -395,23 +392,7 @@ namespace {
 
 constexpr int kMaxParts = 1024;
 
-template <class T>
-int dev_alloc(mg_context* c, T** p, size_t count) {
-    *p = nullptr;
-    if (count == 0) count = 1;
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(p), count * sizeof(T)));
-    c->bytes += (int64_t)(count * sizeof(T));
-    return 0;
-}
-
-template <class T>
-void dev_free(mg_context* c, T*& p, size_t count) {
-    if (p) {
-        (void)hipFree(p);
-        c->bytes -= (int64_t)((count ? count : 1) * sizeof(T));
-        p = nullptr;
-    }
-}
+int64_t& tracked_bytes(mg_context* c) { return c->bytes; }
 
 // Elements past the end of every vector: rows of the last, partly filled slice read (and ignore)
 // x[row] for up to 64*R - 1 rows beyond nloc in the offset-coded kernels.
@@ -431,33 +412,10 @@ inline int64_t vec_front(const Level& L) {
 inline int64_t vec_total(const Level& L) { return vec_front(L) + L.xlen + kVecSlack + vec_reach(L); }
 
 int vec_alloc(mg_context* c, const Level& L, DVector* v) {
-    if (v->raw) return 0;
-    MG_TRY(dev_alloc(c, &v->raw, (size_t)vec_total(L)));
-    v->base = v->raw + vec_front(L);
-    v->rows = v->base + L.g.lead;
-    HIP_TRY(hipMemsetAsync(v->raw, 0, (size_t)vec_total(L) * sizeof(double), c->stream));
-    return 0;
+    return v->alloc(c, (size_t)vec_total(L), (size_t)vec_front(L), (size_t)L.g.lead, c->stream);
 }
 
-void vec_free(mg_context* c, const Level& L, DVector* v) {
-    if (v->raw) {
-        dev_free(c, v->raw, (size_t)vec_total(L));
-        v->base = v->rows = nullptr;
-    }
-}
-
-// Temporary device buffer that frees itself (set-up paths have many early exits).
-struct DevTemp {
-    void* p = nullptr;
-    DevTemp() = default;
-    DevTemp(const DevTemp&) = delete;
-    DevTemp& operator=(const DevTemp&) = delete;
-    ~DevTemp() { if (p) (void)hipFree(p); }
-    int alloc(size_t bytes) {
-        HIP_TRY(hipMalloc(&p, std::max<size_t>(1, bytes)));
-        return 0;
-    }
-};
+void vec_free(DVector* v) { *v = DVector{}; }
 
 inline unsigned blocks_for(int64_t n, int per_block) { return (unsigned)((n + per_block - 1) / per_block); }
 
@@ -565,66 +523,34 @@ void free_direct(mg_context* c);
 
 void drop_graphs(mg_context* c);
 
+// The rule for device memory that is sized from a level: it is a member of that level, or it is released here with
+// the level -- level 0's factorisation and the coarse CG's vectors, the mass matrix with its work vector, the exact
+// solution with the difference vector -- because a level that is set again may have another size.  (fcg_spmv and the
+// staging buffer grow on demand instead.)  The level itself goes back to what a fresh Level is: its default member
+// initialisers are the one statement of that; only the caller's Chebyshev interval (mg_set_chebyshev_bounds, which may
+// precede the level's set-up) stays.
 void free_level(mg_context* c, Level& L) {
     ++c->epoch;
     drop_graphs(c);
-    if (&L == &c->L[0]) free_direct(c);
-    // what the handle keeps sized for this level's geometry goes with it: the mass matrix and its work vector, the
-    // exact solution and the difference vector (a level that is set again may have another size)
+    if (&L == &c->L[0]) {
+        free_direct(c);
+        c->pcg_r.reset(); c->pcg_z.reset(); c->pcg_q.reset(); c->pcg_part_a.reset(); c->pcg_part_b.reset();
+        vec_free(&c->pcg_p);
+        c->pcg_parts = c->pcg_parts_a = 0;
+    }
     if (c->mass_level >= 0 && &L == &c->L[c->mass_level]) {
-        vec_free(c, L, &c->mass_out);
+        vec_free(&c->mass_out);
         c->mass_level = -1;
         free_level(c, c->mass);
     }
     if (c->uexact_level >= 0 && &L == &c->L[c->uexact_level]) {
-        vec_free(c, L, &c->uexact);
-        vec_free(c, L, &c->diff);
+        vec_free(&c->uexact);
+        vec_free(&c->diff);
         c->uexact_level = -1;
     }
-    const size_t ell = (size_t)L.nslices * L.W * (WAVE * L.R);
-    dev_free(c, L.vals, ell);
-    dev_free(c, L.cols, ell);
-    dev_free(c, L.codes, (size_t)L.nslices * ((L.W + 7) / 8) * (WAVE * L.R));
-    dev_free(c, L.offsets, 256);
-    dev_free(c, L.dvals, (size_t)L.mslices * (L.wu > 0 ? L.wu : 1) * (WAVE * L.R));
-    dev_free(c, L.cls, (size_t)L.cls_rows);
-    dev_free(c, L.ctab, 256 * CLS_W);
-    L.ncls = 0;
-    L.cls_escape = false; L.esc_kmax = 0; L.rep_escape = 0; L.grid_decoupled = false;
-    L.cls_halo = 0;
-    L.rep_sym = -1; L.rep_sym_qbits = L.rep_cls_qbits = 0; L.rep_distinct = -1; L.rep_first_asym = -1; L.rep_max_ulps = 0;
-    dev_free(c, L.scls, (size_t)L.nslices * WAVE * L.R);
-    dev_free(c, L.s_off, (size_t)256 * L.W);
-    dev_free(c, L.s_val, (size_t)256 * L.W);
-    dev_free(c, L.s_cnt, 256);
-    dev_free(c, L.s_pack, (size_t)256 * L.W);
-    L.nscls = 0; L.lm_ntop = 0;
-    L.coded = false;
-    L.rb_ok = false;
-    L.mc_ok = -1;
-    L.p1_ok = -1;
-    L.cheb_est_ok = false; L.cheb_lmax_est = 0.0;
-    L.h_offsets.clear();
-    L.sdia = false;
-    dev_free(c, L.dinv, (size_t)L.nslices * WAVE * L.R);
-    dev_free(c, L.kappa, (size_t)L.kappa_n);
-    L.kappa_n = 0;
-    L.mf = false;
-    L.faces = MG_FACES_ALL;
-    L.diffusion_hierarchy = false;
-    dev_free(c, L.perm, (size_t)L.n_global);
-    vec_free(c, L, &L.v);
-    vec_free(c, L, &L.v2);
-    vec_free(c, L, &L.f);
-    vec_free(c, L, &L.err);
-    vec_free(c, L, &L.ftrue);
-    vec_free(c, L, &L.sw);
-    vec_free(c, L, &L.fcg_x);
-    vec_free(c, L, &L.fcg_p);
-    vec_free(c, L, &L.fcg_q);
-    vec_free(c, L, &L.fcg_b);
-    L.set = false;
-    L.has_matrix = false;
+    const double user_lmin = L.cheb_user_lmin, user_lmax = L.cheb_user_lmax;
+    L = Level{};
+    L.cheb_user_lmin = user_lmin; L.cheb_user_lmax = user_lmax;
 }
 
 // A level that is being set: what it held goes first, and unless the build ends with `return done()` what it got so far
@@ -1466,32 +1392,31 @@ int ensure_class_halos(mg_context* c, Level& L) {
     Comm& cm = c->comm;
     const bool lo = cm.rank > 0, hi = cm.rank + 1 < cm.world;
     const size_t n = (size_t)L.hd * (size_t)L.g.plane, nt = 256 * CLS_W + 8;
-    struct Buf {
-        double* p = nullptr;
-        ~Buf() { if (p) (void)hipFree(p); }
-    } send, recv, tsend, trecv, dmap;
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&send.p), 2 * n * sizeof(double)));
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&recv.p), 2 * n * sizeof(double)));
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&tsend.p), nt * sizeof(double)));
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&trecv.p), 2 * nt * sizeof(double)));
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&dmap.p), 2 * 256 * sizeof(int)));
+    DevTemp send_t, recv_t, tsend_t, trecv_t, dmap;
+    MG_TRY(send_t.alloc(2 * n * sizeof(double)));
+    MG_TRY(recv_t.alloc(2 * n * sizeof(double)));
+    MG_TRY(tsend_t.alloc(nt * sizeof(double)));
+    MG_TRY(trecv_t.alloc(2 * nt * sizeof(double)));
+    MG_TRY(dmap.alloc(2 * 256 * sizeof(int)));
+    double *const send = send_t.as<double>(), *const recv = recv_t.as<double>();
+    double *const tsend = tsend_t.as<double>(), *const trecv = trecv_t.as<double>();
     const unsigned nb = (unsigned)std::min<size_t>(4096, (n + 255) / 256);
     int ok = cls_full(L) && L.ncls > 0 && L.sdia && L.wu == 4 && L.up[1] == 1 && L.up[2] == L.g.nx && (int64_t)L.up[3] == L.g.plane ? 1 : 0;
     std::vector<double> mine(nt, 0.0), theirs(2 * nt, 0.0);
     if (ok) {
-        hipLaunchKernelGGL(bytes_to_doubles, dim3(nb), dim3(256), 0, c->stream, L.cls + L.cls_lead, send.p, (int64_t)n);
-        hipLaunchKernelGGL(bytes_to_doubles, dim3(nb), dim3(256), 0, c->stream, L.cls + L.cls_lead + L.nloc - (int64_t)n, send.p + n, (int64_t)n);
+        hipLaunchKernelGGL(bytes_to_doubles, dim3(nb), dim3(256), 0, c->stream, L.cls + L.cls_lead, send, (int64_t)n);
+        hipLaunchKernelGGL(bytes_to_doubles, dim3(nb), dim3(256), 0, c->stream, L.cls + L.cls_lead + L.nloc - (int64_t)n, send + n, (int64_t)n);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(mine.data() + 8, L.ctab, 256 * CLS_W * sizeof(double), hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
         mine[0] = (double)L.ncls;
     }
     // (a rank without classes still takes part in the exchanges: ncls = 0 tells the neighbours)
-    HIP_TRY(hipMemcpyAsync(tsend.p, mine.data(), nt * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    if (!ok) HIP_TRY(hipMemsetAsync(send.p, 0, 2 * n * sizeof(double), c->stream));
-    MG_TRY(exchange_raw(c, send.p, send.p + n, recv.p, recv.p + n, n, c->stream));
-    MG_TRY(exchange_raw(c, tsend.p, tsend.p, trecv.p, trecv.p + nt, nt, c->stream));
-    HIP_TRY(hipMemcpyAsync(theirs.data(), trecv.p, 2 * nt * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(tsend, mine.data(), nt * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    if (!ok) HIP_TRY(hipMemsetAsync(send, 0, 2 * n * sizeof(double), c->stream));
+    MG_TRY(exchange_raw(c, send, send + n, recv, recv + n, n, c->stream));
+    MG_TRY(exchange_raw(c, tsend, tsend, trecv, trecv + nt, nt, c->stream));
+    HIP_TRY(hipMemcpyAsync(theirs.data(), trecv, 2 * nt * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     std::vector<int> map(512, 0);
     int ncls = L.ncls;
@@ -1528,9 +1453,9 @@ int ensure_class_halos(mg_context* c, Level& L) {
         L.ncls = ncls;
     }
     HIP_TRY(hipMemcpyAsync(dmap.p, map.data(), 512 * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    const int* dm = reinterpret_cast<const int*>(dmap.p);
-    if (lo) hipLaunchKernelGGL(doubles_to_classes, dim3(nb), dim3(256), 0, c->stream, recv.p, dm, L.cls + L.cls_lead - (int64_t)n, (int64_t)n);
-    if (hi) hipLaunchKernelGGL(doubles_to_classes, dim3(nb), dim3(256), 0, c->stream, recv.p + n, dm + 256, L.cls + L.cls_lead + L.nloc, (int64_t)n);
+    const int* dm = dmap.as<const int>();
+    if (lo) hipLaunchKernelGGL(doubles_to_classes, dim3(nb), dim3(256), 0, c->stream, recv, dm, L.cls + L.cls_lead - (int64_t)n, (int64_t)n);
+    if (hi) hipLaunchKernelGGL(doubles_to_classes, dim3(nb), dim3(256), 0, c->stream, recv + n, dm + 256, L.cls + L.cls_lead + L.nloc, (int64_t)n);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(c->stream));
     L.cls_halo = 1;
@@ -1569,7 +1494,7 @@ int escape_window_k(mg_context* c, const Level& L, const unsigned char* cls, int
     JK3WindowArgs a{};
     a.cls = cls; a.clead = clead; a.P = L.g.plane; a.nx = L.g.nx; a.ny = L.g.ny; a.nz = L.g.nk;
     a.ntx = (a.nx + WI - 1) / WI; a.nty = (a.ny + HY - 1) / HY;
-    a.most = reinterpret_cast<unsigned*>(c->partials);
+    a.most = reinterpret_cast<unsigned*>(c->partials.get());
     HIP_TRY(hipMemsetAsync(a.most, 0, sizeof(unsigned), c->stream));
     hipLaunchKernelGGL((jk3_escape_window<K, 16, 2, 1>), dim3((unsigned)(a.ntx * a.nty)), dim3(256), 0, c->stream, a);
     HIP_TRY(hipGetLastError());
@@ -1734,7 +1659,7 @@ int check_coloring(mg_context* c, Level& L) {
     EllArgs a{};
     a.vals = L.vals; a.cols = L.cols; a.codes = L.codes; a.offsets = L.offsets; a.W = L.W;
     a.nloc = L.nloc; a.lead = L.g.lead; a.dinv = L.dinv; a.color_kind = COLOR_LATTICE9; a.grow0 = L.row0; a.gnx = L.g.nx; a.gny = L.g.ny;
-    int* d_flag = reinterpret_cast<int*>(c->partials);
+    int* d_flag = reinterpret_cast<int*>(c->partials.get());
     HIP_TRY(hipMemsetAsync(d_flag, 0, sizeof(int), c->stream));
     const dim3 grid(blocks_for(L.nloc, 256)), blk(256);
     if (L.sdia) {
@@ -2455,11 +2380,11 @@ int check_p1_stencil(mg_context* c, Level& L) {
         } else {
             DevTemp d_lin;
             MG_TRY(d_lin.alloc(sizeof(lin)));
-            int* flag = reinterpret_cast<int*>(c->partials);
+            int* flag = reinterpret_cast<int*>(c->partials.get());
             HIP_TRY(hipMemcpyAsync(d_lin.p, lin, sizeof(lin), hipMemcpyHostToDevice, c->stream));
             HIP_TRY(hipMemsetAsync(flag, 0, sizeof(int), c->stream));
             hipLaunchKernelGGL(p1_pattern_check, dim3(blocks_for(L.nloc, 256)), dim3(256), 0, c->stream, L.cols, L.nloc, L.W, L.R,
-                               L.g.lead, static_cast<const int64_t*>(d_lin.p), K, flag);
+                               L.g.lead, d_lin.as<const int64_t>(), K, flag);
             HIP_TRY(hipGetLastError());
             int h = 1;
             HIP_TRY(hipMemcpyAsync(&h, flag, sizeof(int), hipMemcpyDeviceToHost, c->stream));
@@ -2469,7 +2394,7 @@ int check_p1_stencil(mg_context* c, Level& L) {
         if (is_slab(c, L)) {
             // one verdict for every rank: a rank that refused alone would leave the others waiting in the next exchange
             double bad = ok ? 0.0 : 1.0;
-            double* d_bad = reinterpret_cast<double*>(c->partials);
+            double* d_bad = c->partials;
             HIP_TRY(hipMemcpyAsync(d_bad, &bad, sizeof(double), hipMemcpyHostToDevice, c->stream));
             MG_TRY(allreduce_sum(c, d_bad, 1));
             HIP_TRY(hipMemcpyAsync(&bad, d_bad, sizeof(double), hipMemcpyDeviceToHost, c->stream));
@@ -2498,13 +2423,13 @@ int restrict_to(mg_context* c, int level, int kind) {
     }
     Grid gc = coarse_target_grid(c, C, F);
     if (kind == MG_RESTRICT_TABLE) {
-        if (!c->rtab_count) return fail("no restriction table (mg_set_restriction_table)");
+        if (!c->rtab_count.p) return fail("no restriction table (mg_set_restriction_table)");
         // (the transpose of the P2 prolongation reaches three fine planes: on slabs the residual's halo must have room for them)
         if (is_slab(c, F)) {
             if (F.hd < 3) return fail("the table restriction reaches three fine planes: \"halo_depth\" must be at least 3 on slabs");
             MG_TRY(exchange_halo(c, F, F.v2, nullptr, 3));
         }
-        const RestrictTable t{c->rtab_count, c->rtab_off, c->rtab_w, c->rtab_m};
+        const RestrictTable t{c->rtab_count.as<int>(), c->rtab_off.as<int>(), c->rtab_w.as<double>(), c->rtab_m};
         hipLaunchKernelGGL(restrict_table, grid3(gc, gc.nk), dim3(kPlaneBlock), 0, c->stream, gc, F.g, t, F.v2.base, C.f.base);
     } else if (kind == MG_RESTRICT_P1_TRANSPOSE) {
         MG_TRY(check_p1_stencil(c, F));
@@ -2580,10 +2505,10 @@ int prolong(mg_context* c, int level, int add) {
         if (add) MG_TRY(exchange_halo(c, F, F.v));
         return 0;
     }
-    if (c->ptab_count) {
+    if (c->ptab_count.p) {
         if (is_slab(c, F) && c->halo_planes < 2)
             return fail("the table prolongation reaches two coarse planes: halo_planes must be 2 on slabs");
-        const ProlongTable t{c->ptab_count, c->ptab_off, c->ptab_w};
+        const ProlongTable t{c->ptab_count.as<int>(), c->ptab_off.as<int>(), c->ptab_w.as<double>()};
         const dim3 grid = grid3(F.g, F.g.nk), blk(kPlaneBlock);
         with_add_keep(add, keep, [&](auto ad, auto kp) {
             hipLaunchKernelGGL((prolong_table<decltype(ad)::value, decltype(kp)::value>), grid, blk, 0, c->stream, C.g, F.g, t, C.v.base, F.v.base, err);
@@ -2692,9 +2617,9 @@ int cheb_estimate(mg_context* c, int level) {
     MG_TRY(tmp.alloc((size_t)(4 * vt) * sizeof(double)));
     HIP_TRY(hipMemsetAsync(tmp.p, 0, (size_t)(4 * vt) * sizeof(double), c->stream));
     c->cheb_peak_bytes = 4 * vt * (int64_t)sizeof(double);
-    double* const raw = static_cast<double*>(tmp.p);
-    DVector p;
-    p.raw = raw; p.base = p.raw + vec_front(L); p.rows = p.base + L.g.lead;
+    double* const raw = tmp.as<double>();
+    DVector p;                  // (a view into tmp: it owns nothing)
+    p.base = raw + vec_front(L); p.rows = p.base + L.g.lead;
     double* const r = raw + vt + vec_front(L) + L.g.lead;
     double* const z = raw + 2 * vt + vec_front(L) + L.g.lead;
     double* const q = raw + 3 * vt + vec_front(L) + L.g.lead;
@@ -2705,8 +2630,8 @@ int cheb_estimate(mg_context* c, int level) {
     if (L.mf) {
         MG_TRY(mf_dinv.alloc((size_t)n * sizeof(double)));
         c->cheb_peak_bytes += n * (int64_t)sizeof(double);
-        MG_TRY(launch_diffusion_rhs(c, L, L.kappa, nullptr, static_cast<double*>(mf_dinv.p)));
-        dinv = static_cast<const double*>(mf_dinv.p);
+        MG_TRY(launch_diffusion_rhs(c, L, L.kappa, nullptr, mf_dinv.as<double>()));
+        dinv = mf_dinv.as<const double>();
     }
     const dim3 grid((unsigned)std::min<int64_t>(4096, std::max<int64_t>(1, (n + 255) / 256))), blk(256);
     auto scalar = [&](const double* x, const double* y, double* out) -> int {
@@ -2779,14 +2704,7 @@ int cheb_interval(mg_context* c, int level, double* lo, double* hi) {
     return 0;
 }
 
-void free_direct(mg_context* c) {
-    DirectSolver& d = c->direct;
-    const size_t pw = (size_t)d.g.nb * d.g.p * (d.g.W > 0 ? d.g.W : 1), np = (size_t)d.g.nb * d.g.p;
-    dev_free(c, d.T, np * d.g.p);
-    dev_free(c, d.lcol, pw); dev_free(c, d.ucol, pw); dev_free(c, d.lval, pw); dev_free(c, d.uval, pw);
-    dev_free(c, d.y, np); dev_free(c, d.x, np); dev_free(c, d.w, (size_t)d.g.p);
-    d = DirectSolver();
-}
+void free_direct(mg_context* c) { c->direct = DirectSolver{}; }
 
 EllView ell_view(const Level& L) {
     EllView e{};
@@ -2820,17 +2738,18 @@ int build_direct(mg_context* c) {
     if (p > 2304 || nb * p * p * 8 > ((int64_t)3 << 29)) return 0;     // too large to store densely: PCG
     d.g.n = L.nloc; d.g.p = (int)p; d.g.plane = (int)plane; d.g.nb = (int)nb; d.g.W = L.W;
     const size_t pw = (size_t)nb * p * L.W, np = (size_t)nb * p, pp = (size_t)p * p;
-    double *A = nullptr, *B = nullptr, *P = nullptr;       // A: block being inverted, B: row panel, P: pivot block
-    int* d_status = nullptr;
-    int rc = [&]() -> int {
-        MG_TRY(dev_alloc(c, &d.T, np * p));
-        MG_TRY(dev_alloc(c, &d.lcol, pw)); MG_TRY(dev_alloc(c, &d.ucol, pw));
-        MG_TRY(dev_alloc(c, &d.lval, pw)); MG_TRY(dev_alloc(c, &d.uval, pw));
-        MG_TRY(dev_alloc(c, &d.y, np)); MG_TRY(dev_alloc(c, &d.x, np)); MG_TRY(dev_alloc(c, &d.w, (size_t)p));
-        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&A), pp * 8));
-        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&B), (size_t)GJ_NB * p * 8));
-        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&P), (size_t)GJ_NB * GJ_NB * 8));
-        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d_status), sizeof(int)));
+    DevTemp A_t, B_t, P_t, status_t;                       // A: block being inverted, B: row panel, P: pivot block
+    int rc = [&]() -> int {                                // (a lambda: any failure must still reach free_direct below)
+        MG_TRY(d.T.alloc(c, np * p));
+        MG_TRY(d.lcol.alloc(c, pw)); MG_TRY(d.ucol.alloc(c, pw));
+        MG_TRY(d.lval.alloc(c, pw)); MG_TRY(d.uval.alloc(c, pw));
+        MG_TRY(d.y.alloc(c, np)); MG_TRY(d.x.alloc(c, np)); MG_TRY(d.w.alloc(c, (size_t)p));
+        MG_TRY(A_t.alloc(pp * 8));
+        MG_TRY(B_t.alloc((size_t)GJ_NB * p * 8));
+        MG_TRY(P_t.alloc((size_t)GJ_NB * GJ_NB * 8));
+        MG_TRY(status_t.alloc(sizeof(int)));
+        double *const A = A_t.as<double>(), *const B = B_t.as<double>(), *const P = P_t.as<double>();
+        int* const d_status = status_t.as<int>();
         HIP_TRY(hipMemsetAsync(d_status, 0, sizeof(int), c->stream));
         const EllView e = ell_view(L);
         const dim3 rows_grid(blocks_for(p, 128)), rows_blk(128);
@@ -2864,7 +2783,6 @@ int build_direct(mg_context* c) {
         d.ok = status == 0;
         return 0;
     }();
-    (void)hipFree(A); (void)hipFree(B); (void)hipFree(P); (void)hipFree(d_status);
     if (rc || !d.ok) { free_direct(c); d.tried = true; }
     return rc;
 }
@@ -2878,9 +2796,10 @@ int validate_direct(mg_context* c) {
     DirectSolver& d = c->direct;
     if (!d.ok) return 0;
     Level& L = c->L[0];
-    double* saved = nullptr;
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&saved), (size_t)L.xlen * 8));
-    int rc = [&]() -> int {
+    DevTemp saved_t;
+    MG_TRY(saved_t.alloc((size_t)L.xlen * 8));
+    double* const saved = saved_t.as<double>();
+    int rc = [&]() -> int {                                // (a lambda: a failed check must still drop the factorisation)
         HIP_TRY(hipMemcpyAsync(saved, L.f.base, (size_t)L.xlen * 8, hipMemcpyDeviceToDevice, c->stream));
         std::vector<double> ones((size_t)L.nloc, 1.0);
         HIP_TRY(hipMemcpyAsync(L.f.rows, ones.data(), (size_t)L.nloc * 8, hipMemcpyHostToDevice, c->stream));
@@ -2895,7 +2814,6 @@ int validate_direct(mg_context* c) {
         HIP_TRY(hipStreamSynchronize(c->stream));
         return 0;
     }();
-    (void)hipFree(saved);
     if (rc || !d.ok) { free_direct(c); d.tried = true; }
     return rc;
 }
@@ -2952,14 +2870,14 @@ int pcg_solve(mg_context* c, int* iters_out, double* rel_out) {
     if (L.g.lead != 0) return fail("coarsest level must not be distributed");
     const int64_t n = L.nloc;
     if (!c->pcg_r) {
-        MG_TRY(dev_alloc(c, &c->pcg_r, (size_t)n + 4));
-        MG_TRY(dev_alloc(c, &c->pcg_z, (size_t)n + 4));
-        MG_TRY(dev_alloc(c, &c->pcg_q, (size_t)n + 4));
+        MG_TRY(c->pcg_r.alloc(c, (size_t)n + 4));
+        MG_TRY(c->pcg_z.alloc(c, (size_t)n + 4));
+        MG_TRY(c->pcg_q.alloc(c, (size_t)n + 4));
         MG_TRY(vec_alloc(c, L, &c->pcg_p));
         c->pcg_parts = (int)std::min<int64_t>(512, std::max<int64_t>(1, (n + BLOCK - 1) / BLOCK));
         c->pcg_parts_a = (int)std::max<unsigned>(blocks_for(L.nslices, WAVES_PER_BLOCK), (unsigned)c->pcg_parts);
-        MG_TRY(dev_alloc(c, &c->pcg_part_a, (size_t)c->pcg_parts_a));
-        MG_TRY(dev_alloc(c, &c->pcg_part_b, (size_t)2 * c->pcg_parts));
+        MG_TRY(c->pcg_part_a.alloc(c, (size_t)c->pcg_parts_a));
+        MG_TRY(c->pcg_part_b.alloc(c, (size_t)2 * c->pcg_parts));
     }
     PcgArgs a{};
     a.x = L.v.rows; a.r = c->pcg_r; a.z = c->pcg_z; a.p = c->pcg_p.rows; a.q = c->pcg_q;
@@ -3190,17 +3108,11 @@ int fcg_solve(mg_context* c, int level, double rtol, int max_iter, double* hist,
     MG_TRY(vec_alloc(c, L, &L.fcg_b));
     const int64_t gmax = 4 * std::max(1, c->prop.multiProcessorCount);
     if (!c->fcg_work) {
-        c->fcg_work_n = 8 + kFcgFold + 3 * gmax;
-        MG_TRY(dev_alloc(c, &c->fcg_work, (size_t)c->fcg_work_n));
+        MG_TRY(c->fcg_work.alloc(c, (size_t)(8 + kFcgFold + 3 * gmax)));
     }
     // partial sums of the SpMV (launch_ell with dot): one per block of the level's kernel
     const int64_t nspmv = L.mf ? (int64_t)mf_plan(c, L).grid : (int64_t)blocks_for(L.nslices, WAVES_PER_BLOCK);
-    if (c->fcg_spmv_n < nspmv) {
-        dev_free(c, c->fcg_spmv, (size_t)c->fcg_spmv_n);
-        c->fcg_spmv_n = 0;
-        MG_TRY(dev_alloc(c, &c->fcg_spmv, (size_t)nspmv));
-        c->fcg_spmv_n = nspmv;
-    }
+    if ((int64_t)c->fcg_spmv.count() < nspmv) MG_TRY(c->fcg_spmv.alloc(c, (size_t)nspmv));
     const FcgWork w = fcg_work(c);
     const size_t bytes = (size_t)L.xlen * sizeof(double);
 
@@ -3236,7 +3148,7 @@ int fcg_solve(mg_context* c, int level, double rtol, int max_iter, double* hist,
             unsigned nsp = 0;
             MG_TRY(launch_ell(c, L, {.mode = MODE_SPMV, .dot = true, .x_base = L.fcg_p.base, .out_rows = L.fcg_q.rows, .partials = c->fcg_spmv,
                                      .grid_out = &nsp}));
-            if ((int64_t)nsp > c->fcg_spmv_n) return fail("mg_pcg: SpMV partial sums overflow");
+            if ((size_t)nsp > c->fcg_spmv.count()) return fail("mg_pcg: SpMV partial sums overflow");
             const double* pq = c->fcg_spmv;
             int64_t npq = nsp;
             MG_TRY(fcg_sums(c, L, pq, npq, 1, kFcgFold, w.fold_pq, w.tot_pq));
@@ -3277,12 +3189,8 @@ int fcg_solve(mg_context* c, int level, double rtol, int max_iter, double* hist,
 }
 
 int ensure_stage(mg_context* c, int64_t elems) {
-    if (c->stage_elems >= elems) return 0;
-    dev_free(c, c->stage, (size_t)c->stage_elems);
-    c->stage_elems = 0;
-    MG_TRY(dev_alloc(c, &c->stage, (size_t)elems));
-    c->stage_elems = elems;
-    return 0;
+    if ((int64_t)c->stage.count() >= elems) return 0;
+    return c->stage.alloc(c, (size_t)elems);
 }
 
 int upload_vector(mg_context* c, Level& L, DVector& v, const double* host) {
@@ -3301,13 +3209,13 @@ int upload_vector(mg_context* c, Level& L, DVector& v, const double* host) {
 // values and a specialised width; otherwise the int32 kernels stay in use.
 int encode_level(mg_context* c, Level& L) {
     if (!c->use_codes || !coded_width(L.W)) return 0;
-    int* d_table = nullptr;
-    int* d_count = nullptr;
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d_table), kDeltaSlots * sizeof(int)));
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d_count), 2 * sizeof(int)));
     std::vector<int> h_table(kDeltaSlots, kDeltaEmpty);
     int h_counts[2] = {0, 0};
-    int rc = [&]() -> int {
+    {
+        DevTemp table_t, count_t;
+        MG_TRY(table_t.alloc(kDeltaSlots * sizeof(int)));
+        MG_TRY(count_t.alloc(2 * sizeof(int)));
+        int *const d_table = table_t.as<int>(), *const d_count = count_t.as<int>();
         HIP_TRY(hipMemcpyAsync(d_table, h_table.data(), kDeltaSlots * sizeof(int), hipMemcpyHostToDevice, c->stream));
         HIP_TRY(hipMemsetAsync(d_count, 0, 2 * sizeof(int), c->stream));
         const int64_t total = L.nslices * L.W * (WAVE * L.R);
@@ -3317,11 +3225,7 @@ int encode_level(mg_context* c, Level& L) {
         HIP_TRY(hipMemcpyAsync(h_counts, d_count, 2 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipMemcpyAsync(h_table.data(), d_table, kDeltaSlots * sizeof(int), hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
-        return 0;
-    }();
-    (void)hipFree(d_table);
-    (void)hipFree(d_count);
-    if (rc) return rc;
+    }
     const int h_count = h_counts[0];
     if (h_counts[1] || h_count > 255) return 0;     // irregular numbering: keep int32 columns
     std::vector<int> offs;
@@ -3338,15 +3242,15 @@ int encode_level(mg_context* c, Level& L) {
     for (int o : offs)
         if (o != 0 && (o & 1) == 0) L.rb_ok = false;       // a coupling inside one colour
     offs.resize(256, 0);
-    MG_TRY(dev_alloc(c, &L.offsets, 256));
+    MG_TRY(L.offsets.alloc(c, 256));
     HIP_TRY(hipMemcpyAsync(L.offsets, offs.data(), 256 * sizeof(int), hipMemcpyHostToDevice, c->stream));
     const int CW = (L.W + 7) / 8;
-    MG_TRY(dev_alloc(c, &L.codes, (size_t)L.nslices * CW * (WAVE * L.R)));
+    MG_TRY(L.codes.alloc(c, (size_t)L.nslices * CW * (WAVE * L.R)));
     const dim3 grid(blocks_for(L.nslices * (WAVE * L.R), 256)), blk(256);
     with_int_else<4, 1, 2>(L.R, [&](auto r) { hipLaunchKernelGGL(ell_encode<decltype(r)::value>, grid, blk, 0, c->stream, L.cols, L.codes, L.nslices, L.W, L.nloc, L.g.lead, L.offsets, L.ntable, L.dcode); });
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(c->stream));
-    dev_free(c, L.cols, (size_t)L.nslices * L.W * (WAVE * L.R));      // 4*W bytes per row back
+    L.cols.reset();                                                   // 4*W bytes per row back
     L.coded = true;
     return 0;
 }
@@ -3366,27 +3270,25 @@ int build_row_classes(mg_context* c, Level& L) {
 
 int build_row_classes_q(mg_context* c, Level& L, int qbits) {
     // scratch: hash tags | slot values | count, flag, slot_class[CLS_SLOTS], hist[256]
-    struct Scratch {
-        char* p = nullptr;
-        ~Scratch() { if (p) (void)hipFree(p); }
-    } scratch;
+    DevTemp scratch_t;
     const size_t tag_bytes = CLS_SLOTS * sizeof(unsigned long long), val_bytes = (size_t)CLS_SLOTS * CLS_W * sizeof(double);
     const size_t int_bytes = (2 + CLS_SLOTS + 256) * sizeof(int);
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&scratch.p), tag_bytes + val_bytes + int_bytes));
-    HIP_TRY(hipMemsetAsync(scratch.p, 0, tag_bytes + val_bytes + int_bytes, c->stream));
-    int* const ints = reinterpret_cast<int*>(scratch.p + tag_bytes + val_bytes);
+    MG_TRY(scratch_t.alloc(tag_bytes + val_bytes + int_bytes));
+    char* const scratch = scratch_t.as<char>();
+    HIP_TRY(hipMemsetAsync(scratch, 0, tag_bytes + val_bytes + int_bytes, c->stream));
+    int* const ints = reinterpret_cast<int*>(scratch + tag_bytes + val_bytes);
     // padded like the vectors (vec_reach) so that the pass can read whole tiles around the level unpredicated
     const int64_t cls_lead = ((std::max(L.mlead, vec_reach(L) + (int64_t)L.hd * L.g.plane) + 255) / 256) * 256;
     const int64_t cls_rows = cls_lead + L.nloc + cls_lead + 512;
-    unsigned char* cls = nullptr;
-    double* ctab = nullptr;
-    MG_TRY(dev_alloc(c, &cls, (size_t)cls_rows));
-    MG_TRY(dev_alloc(c, &ctab, 256 * CLS_W));
+    DevBuf<unsigned char> cls;          // built here, the level's once the dictionary holds
+    DevBuf<double> ctab;
+    MG_TRY(cls.alloc(c, (size_t)cls_rows));
+    MG_TRY(ctab.alloc(c, 256 * CLS_W));
     ClsArgs a{};
     a.dvals = L.dvals; a.wu = L.wu; a.nloc = L.nloc; a.mlead = L.mlead;
     for (int t = 0; t < 4; ++t) a.up[t] = L.up[t];
-    a.tags = reinterpret_cast<unsigned long long*>(scratch.p);
-    a.svals = reinterpret_cast<double*>(scratch.p + tag_bytes);
+    a.tags = reinterpret_cast<unsigned long long*>(scratch);
+    a.svals = reinterpret_cast<double*>(scratch + tag_bytes);
     a.count = ints; a.flag = ints + 1; a.slot_class = ints + 2;
     a.hist = reinterpret_cast<unsigned*>(ints + 2 + CLS_SLOTS);
     a.ctab = ctab; a.cls = cls; a.crows = cls_rows; a.clead = cls_lead; a.qbits = qbits;
@@ -3394,31 +3296,28 @@ int build_row_classes_q(mg_context* c, Level& L, int qbits) {
     int h[2] = {0, 0};
     std::vector<unsigned> hist(256, 0u);
     std::vector<double> tab(256 * CLS_W, 0.0);
-    int rc = [&]() -> int {
-        with_int_else<4, 1, 2>(L.R, [&](auto r) { hipLaunchKernelGGL(cls_insert<64 * decltype(r)::value>, grid, blk, 0, c->stream, a); });
-        hipLaunchKernelGGL(cls_assign, dim3(1), dim3(64), 0, c->stream, a);
-        with_int_else<4, 1, 2>(L.R, [&](auto r) { hipLaunchKernelGGL(cls_encode<64 * decltype(r)::value>, egrid, blk, 0, c->stream, a); });
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(h, ints, 2 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipMemcpyAsync(hist.data(), a.hist, 256 * sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipMemcpyAsync(tab.data(), ctab, 256 * CLS_W * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        return 0;
-    }();
-    if (!rc) { L.rep_distinct = h[0]; L.rep_cls_qbits = qbits; }
+    with_int_else<4, 1, 2>(L.R, [&](auto r) { hipLaunchKernelGGL(cls_insert<64 * decltype(r)::value>, grid, blk, 0, c->stream, a); });
+    hipLaunchKernelGGL(cls_assign, dim3(1), dim3(64), 0, c->stream, a);
+    with_int_else<4, 1, 2>(L.R, [&](auto r) { hipLaunchKernelGGL(cls_encode<64 * decltype(r)::value>, egrid, blk, 0, c->stream, a); });
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(h, ints, 2 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(hist.data(), a.hist, 256 * sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(tab.data(), ctab, 256 * CLS_W * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    L.rep_distinct = h[0]; L.rep_cls_qbits = qbits;
+    int rc = 0;
     bool escape = false;
-    if (!rc && (h[0] > 255 || h[1]) && c->cls_escape && L.wu == 4 && !L.flat && L.nloc >= (1 << 16)) {
+    if ((h[0] > 255 || h[1]) && c->cls_escape && L.wu == 4 && !L.flat && L.nloc >= (1 << 16)) {
         // More than 255 distinct rows.  If most rows are still copies of a few (a uniform mesh with some odd rows: other
         // material, other boundary condition), the 254 most frequent rows -- found on a sample of 2^20 rows spread over the
         // level -- keep their class bytes and every other row gets CLS_ESCAPE: the K-sweep march reads such a row from the
         // symmetric diagonal storage.  Worth it while at least three quarters of the rows have a class.
         rc = [&]() -> int {
-            unsigned* slot_count = nullptr;
-            struct Free { unsigned*& p; ~Free() { if (p) (void)hipFree(p); } } guard{slot_count};
-            // (slot counts | one bit per hash value: seen once)
-            HIP_TRY(hipMalloc(reinterpret_cast<void**>(&slot_count), (CLS_SLOTS + CLS_SEEN_BITS / 32) * sizeof(unsigned)));
+            DevTemp slot_count_t;       // (slot counts | one bit per hash value: seen once)
+            MG_TRY(slot_count_t.alloc((CLS_SLOTS + CLS_SEEN_BITS / 32) * sizeof(unsigned)));
+            unsigned* const slot_count = slot_count_t.as<unsigned>();
             HIP_TRY(hipMemsetAsync(slot_count, 0, (CLS_SLOTS + CLS_SEEN_BITS / 32) * sizeof(unsigned), c->stream));
-            HIP_TRY(hipMemsetAsync(scratch.p, 0, tag_bytes + val_bytes + int_bytes, c->stream));
+            HIP_TRY(hipMemsetAsync(scratch, 0, tag_bytes + val_bytes + int_bytes, c->stream));
             const int64_t nsample = std::min<int64_t>(L.nloc, (int64_t)1 << 20);
             const dim3 sgrid(blocks_for(nsample, 256));
             with_int_else<4, 1, 2>(L.R, [&](auto r) { hipLaunchKernelGGL(cls_sample_insert<64 * decltype(r)::value>, sgrid, blk, 0, c->stream, a, nsample, slot_count, slot_count + CLS_SLOTS); });
@@ -3458,12 +3357,8 @@ int build_row_classes_q(mg_context* c, Level& L, int qbits) {
                          (long long)L.nloc, qbits, hist[CLS_ESCAPE], kmax, rc);
         if (escape) { h[0] = 254; h[1] = 0; L.esc_kmax = kmax; L.rep_escape = hist[CLS_ESCAPE]; }
     }
-    if (rc || h[0] > 255 || h[1]) {                 // too many distinct rows (or a hash collision): plain pass
-        dev_free(c, cls, (size_t)cls_rows);
-        dev_free(c, ctab, 256 * CLS_W);
-        return rc;
-    }
-    L.cls = cls; L.ctab = ctab; L.ncls = h[0] + 1; L.cls_lead = cls_lead; L.cls_rows = cls_rows;
+    if (rc || h[0] > 255 || h[1]) return rc;        // too many distinct rows (or a hash collision): plain pass
+    L.cls = std::move(cls); L.ctab = std::move(ctab); L.ncls = h[0] + 1; L.cls_lead = cls_lead;
     L.cls_escape = escape && L.rep_escape > 0;
     if (escape) hist[CLS_ESCAPE] = 0;               // (never the most frequent class)
     L.cmain = 0;
@@ -3474,7 +3369,7 @@ int build_row_classes_q(mg_context* c, Level& L, int qbits) {
     if (L.wu == 4 && !L.cls_escape && !L.flat && L.up[1] == 1 && L.up[2] == L.g.nx && (int64_t)L.up[3] == L.g.plane) {
         JBCheckArgs k{};
         k.cls = L.cls + L.cls_lead; k.ctab = L.ctab; k.nx = L.g.nx; k.ny = L.g.ny; k.nz = L.g.nk; k.P = L.g.plane; k.n = L.nloc;
-        k.flag = reinterpret_cast<int*>(c->partials);
+        k.flag = reinterpret_cast<int*>(c->partials.get());
         HIP_TRY(hipMemsetAsync(k.flag, 0, sizeof(int), c->stream));
         hipLaunchKernelGGL(sdia_grid_decoupled, dim3(blocks_for(L.nloc, 256)), dim3(256), 0, c->stream, k);
         HIP_TRY(hipGetLastError());
@@ -3507,7 +3402,7 @@ int prepare_lat_march(mg_context* c, Level& L) {
             if (std::llabs(dk) > 2 || std::llabs(dj) > 2 || std::llabs(di) > 2) return 0;
             pack[(size_t)cl * L.W + t] = (int)(((dk + 2) << 16) | ((dj + 2) << 8) | (di + 2));
         }
-    int* d_hist = reinterpret_cast<int*>(c->partials);
+    int* d_hist = reinterpret_cast<int*>(c->partials.get());
     HIP_TRY(hipMemsetAsync(d_hist, 0, 256 * sizeof(int), c->stream));
     hipLaunchKernelGGL(lm_class_histogram, dim3(1024), dim3(256), 0, c->stream, L.scls, L.nloc, d_hist);
     HIP_TRY(hipGetLastError());
@@ -3516,7 +3411,7 @@ int prepare_lat_march(mg_context* c, Level& L) {
     std::vector<int> order(L.nscls);
     for (int i = 0; i < L.nscls; ++i) order[i] = i;
     std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return hist[x] > hist[y]; });
-    MG_TRY(dev_alloc(c, &L.s_pack, n));
+    MG_TRY(L.s_pack.alloc(c, n));
     HIP_TRY(hipMemcpy(L.s_pack, pack.data(), n * sizeof(int), hipMemcpyHostToDevice));
     L.lm_ntop = std::min<int>(LM_K, L.nscls);
     for (int t = 0; t < L.lm_ntop; ++t) L.lm_top[t] = order[t];
@@ -3525,52 +3420,44 @@ int prepare_lat_march(mg_context* c, Level& L) {
 
 int build_stencil_classes(mg_context* c, Level& L) {
     if (!c->use_classes || !L.coded || L.sdia || L.flat || L.W < 8) return 0;
-    struct Scratch {
-        char* p = nullptr;
-        ~Scratch() { if (p) (void)hipFree(p); }
-    } scratch;
+    DevTemp scratch_t;
     const size_t tag_bytes = SCLS_SLOTS * sizeof(unsigned long long), row_bytes = SCLS_SLOTS * sizeof(int64_t);
     const size_t int_bytes = (2 + SCLS_SLOTS) * sizeof(int);
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&scratch.p), tag_bytes + row_bytes + int_bytes));
-    HIP_TRY(hipMemsetAsync(scratch.p, 0, tag_bytes + row_bytes + int_bytes, c->stream));
-    int* const ints = reinterpret_cast<int*>(scratch.p + tag_bytes + row_bytes);
-    unsigned char* cls = nullptr;
-    int *s_off = nullptr, *s_cnt = nullptr;
-    double* s_val = nullptr;
+    MG_TRY(scratch_t.alloc(tag_bytes + row_bytes + int_bytes));
+    char* const scratch = scratch_t.as<char>();
+    HIP_TRY(hipMemsetAsync(scratch, 0, tag_bytes + row_bytes + int_bytes, c->stream));
+    int* const ints = reinterpret_cast<int*>(scratch + tag_bytes + row_bytes);
+    DevBuf<unsigned char> cls;          // built here, the level's once the dictionary holds
+    DevBuf<int> s_off, s_cnt;
+    DevBuf<double> s_val;
     const size_t crows = (size_t)L.nslices * WAVE * L.R;
-    MG_TRY(dev_alloc(c, &cls, crows));
-    MG_TRY(dev_alloc(c, &s_off, (size_t)256 * L.W));
-    MG_TRY(dev_alloc(c, &s_val, (size_t)256 * L.W));
-    MG_TRY(dev_alloc(c, &s_cnt, 256));
+    MG_TRY(cls.alloc(c, crows));
+    MG_TRY(s_off.alloc(c, (size_t)256 * L.W));
+    MG_TRY(s_val.alloc(c, (size_t)256 * L.W));
+    MG_TRY(s_cnt.alloc(c, 256));
     HIP_TRY(hipMemsetAsync(cls, 0, crows, c->stream));
     HIP_TRY(hipMemsetAsync(s_off, 0, (size_t)256 * L.W * sizeof(int), c->stream));
     HIP_TRY(hipMemsetAsync(s_val, 0, (size_t)256 * L.W * sizeof(double), c->stream));
     HIP_TRY(hipMemsetAsync(s_cnt, 0, 256 * sizeof(int), c->stream));
     SclsArgs a{};
     a.vals = L.vals; a.codes = L.codes; a.offsets = L.offsets; a.W = L.W; a.dcode = L.dcode; a.nloc = L.nloc; a.nslices = L.nslices;
-    a.tags = reinterpret_cast<unsigned long long*>(scratch.p);
-    a.slot_row = reinterpret_cast<int64_t*>(scratch.p + tag_bytes);
+    a.tags = reinterpret_cast<unsigned long long*>(scratch);
+    a.slot_row = reinterpret_cast<int64_t*>(scratch + tag_bytes);
     a.count = ints; a.flag = ints + 1; a.slot_class = ints + 2;
     a.cls = cls; a.s_off = s_off; a.s_val = s_val; a.s_cnt = s_cnt;
     const dim3 grid(blocks_for(L.nloc, 256)), blk(256);
     int h[2] = {0, 0};
-    int rc = [&]() -> int {
-        with_int_else<4, 1, 2>(L.R, [&](auto r) {
-            constexpr int R = decltype(r)::value;
-            hipLaunchKernelGGL(scls_insert<R>, grid, blk, 0, c->stream, a);
-            hipLaunchKernelGGL(scls_assign<R>, dim3(1), blk, 0, c->stream, a);
-            hipLaunchKernelGGL(scls_encode<R>, grid, blk, 0, c->stream, a);
-        });
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(h, ints, 2 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        return 0;
-    }();
-    if (rc || h[0] > 255 || h[1]) {
-        dev_free(c, cls, crows); dev_free(c, s_off, (size_t)256 * L.W); dev_free(c, s_val, (size_t)256 * L.W); dev_free(c, s_cnt, 256);
-        return rc;
-    }
-    L.scls = cls; L.s_off = s_off; L.s_val = s_val; L.s_cnt = s_cnt; L.nscls = h[0];
+    with_int_else<4, 1, 2>(L.R, [&](auto r) {
+        constexpr int R = decltype(r)::value;
+        hipLaunchKernelGGL(scls_insert<R>, grid, blk, 0, c->stream, a);
+        hipLaunchKernelGGL(scls_assign<R>, dim3(1), blk, 0, c->stream, a);
+        hipLaunchKernelGGL(scls_encode<R>, grid, blk, 0, c->stream, a);
+    });
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(h, ints, 2 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (h[0] > 255 || h[1]) return 0;               // too many distinct rows (or a hash collision): the gathering kernel
+    L.scls = std::move(cls); L.s_off = std::move(s_off); L.s_val = std::move(s_val); L.s_cnt = std::move(s_cnt); L.nscls = h[0];
     return prepare_lat_march(c, L);
 }
 
@@ -3598,51 +3485,43 @@ int repack_sdia(mg_context* c, Level& L, int level) {
     a.vals = L.vals; a.codes = L.codes; a.offsets = L.offsets; a.W = L.W; a.WU = wu_t; a.NU = wu; a.dcode = L.dcode;
     for (int t = 0; t < 8; ++t) a.up[t] = t < wu ? up[t] : 0;
     a.nloc = L.nloc; a.mlead = mlead;
-    double* dvals = nullptr;
-    MG_TRY(dev_alloc(c, &dvals, (size_t)mslices * wu_t * S));
+    DevBuf<double> dvals;               // built here, the level's once the matrix has proved symmetric
+    MG_TRY(dvals.alloc(c, (size_t)mslices * wu_t * S));
     a.dvals = dvals;
-    int* d_flag = nullptr;              // flag | pad | report[2] (first asymmetric row + 1, largest ulp distance of a pair)
+    DevTemp flag_t;                     // flag | pad | report[2] (first asymmetric row + 1, largest ulp distance of a pair)
     int flag = 0;
     unsigned long long report[2] = {~0ull, 0ull};
     int qbits = c->storage_qbits;
-    int rc = [&]() -> int {
-        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d_flag), 8 + 2 * sizeof(unsigned long long)));
-        unsigned long long* d_report = reinterpret_cast<unsigned long long*>(d_flag + 2);
-        HIP_TRY(hipMemsetAsync(dvals, 0, (size_t)mslices * wu_t * S * sizeof(double), c->stream));
-        const dim3 grid(blocks_for(L.nloc, 256)), blk(256);
-        with_int_else<4, 1, 2>(L.R, [&](auto r) { hipLaunchKernelGGL(sdia_fill<decltype(r)::value>, grid, blk, 0, c->stream, a); });
-        for (int attempt = 0; attempt < 2; ++attempt) {
-            // ("storage_auto": pairs that differ by at most 4 units in the last place -- round-off of an assembly that sums its
-            //  element contributions in varying order -- get a second try with that tolerance; the upper half of a pair is kept)
-            HIP_TRY(hipMemsetAsync(d_flag, 0, 8, c->stream));
-            HIP_TRY(hipMemcpyAsync(d_report, report, sizeof(report), hipMemcpyHostToDevice, c->stream));
-            with_int_else<4, 1, 2>(L.R, [&](auto r) { hipLaunchKernelGGL(sdia_check<decltype(r)::value>, grid, blk, 0, c->stream, a, d_flag, qbits, d_report); });
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipMemcpyAsync(&flag, d_flag, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-            HIP_TRY(hipMemcpyAsync(report, d_report, sizeof(report), hipMemcpyDeviceToHost, c->stream));
-            HIP_TRY(hipStreamSynchronize(c->stream));
-            if (!(flag && attempt == 0 && c->storage_auto && qbits == 0 && report[1] <= 4)) break;
-            qbits = 2;
-            report[0] = ~0ull; report[1] = 0ull;
-        }
-        return 0;
-    }();
-    (void)hipFree(d_flag);
-    if (!rc) {
-        L.rep_first_asym = report[0] == ~0ull ? -1 : (int64_t)report[0] - 1;
-        L.rep_max_ulps = report[1] >= (1ull << 62) ? -1 : (int64_t)report[1];
-        L.rep_sym = flag ? 0 : (report[0] == ~0ull ? 1 : 2);
-        L.rep_sym_qbits = flag ? 0 : qbits;
+    MG_TRY(flag_t.alloc(8 + 2 * sizeof(unsigned long long)));
+    int* const d_flag = flag_t.as<int>();
+    unsigned long long* d_report = reinterpret_cast<unsigned long long*>(d_flag + 2);
+    HIP_TRY(hipMemsetAsync(dvals, 0, (size_t)mslices * wu_t * S * sizeof(double), c->stream));
+    const dim3 grid(blocks_for(L.nloc, 256)), blk(256);
+    with_int_else<4, 1, 2>(L.R, [&](auto r) { hipLaunchKernelGGL(sdia_fill<decltype(r)::value>, grid, blk, 0, c->stream, a); });
+    for (int attempt = 0; attempt < 2; ++attempt) {
+        // ("storage_auto": pairs that differ by at most 4 units in the last place -- round-off of an assembly that sums its
+        //  element contributions in varying order -- get a second try with that tolerance; the upper half of a pair is kept)
+        HIP_TRY(hipMemsetAsync(d_flag, 0, 8, c->stream));
+        HIP_TRY(hipMemcpyAsync(d_report, report, sizeof(report), hipMemcpyHostToDevice, c->stream));
+        with_int_else<4, 1, 2>(L.R, [&](auto r) { hipLaunchKernelGGL(sdia_check<decltype(r)::value>, grid, blk, 0, c->stream, a, d_flag, qbits, d_report); });
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(&flag, d_flag, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(report, d_report, sizeof(report), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        if (!(flag && attempt == 0 && c->storage_auto && qbits == 0 && report[1] <= 4)) break;
+        qbits = 2;
+        report[0] = ~0ull; report[1] = 0ull;
     }
-    if (rc || flag) {                                           // not symmetric: keep the coded form
-        dev_free(c, dvals, (size_t)mslices * wu_t * S);
-        return rc;
-    }
-    L.dvals = dvals; L.sdia = true; L.wu = wu_t; L.mlead = mlead; L.mslices = mslices;
+    L.rep_first_asym = report[0] == ~0ull ? -1 : (int64_t)report[0] - 1;
+    L.rep_max_ulps = report[1] >= (1ull << 62) ? -1 : (int64_t)report[1];
+    L.rep_sym = flag ? 0 : (report[0] == ~0ull ? 1 : 2);
+    L.rep_sym_qbits = flag ? 0 : qbits;
+    if (flag) return 0;                                         // not symmetric: keep the coded form
+    L.dvals = std::move(dvals); L.sdia = true; L.wu = wu_t; L.mlead = mlead; L.mslices = mslices;
     for (int t = 0; t < 8; ++t) L.up[t] = t < wu ? up[t] : 0;
     // padded template slots (wu < wu_t) hold zeros and offset 0: they add 0 * x[row]
-    dev_free(c, L.vals, (size_t)L.nslices * L.W * S);
-    dev_free(c, L.codes, (size_t)L.nslices * ((L.W + 7) / 8) * S);
+    L.vals.reset();
+    L.codes.reset();
     return build_row_classes(c, L);
 }
 
@@ -3665,9 +3544,9 @@ int alloc_ell(mg_context* c, Level& L) {
     L.R = c->rows_per_lane;
     L.nslices = (L.nloc + (int64_t)WAVE * L.R - 1) / ((int64_t)WAVE * L.R);
     const size_t ell = (size_t)L.nslices * L.W * (WAVE * L.R);
-    MG_TRY(dev_alloc(c, &L.vals, ell));
-    MG_TRY(dev_alloc(c, &L.cols, ell));
-    MG_TRY(dev_alloc(c, &L.dinv, (size_t)L.nslices * WAVE * L.R));
+    MG_TRY(L.vals.alloc(c, ell));
+    MG_TRY(L.cols.alloc(c, ell));
+    MG_TRY(L.dinv.alloc(c, (size_t)L.nslices * WAVE * L.R));
     const unsigned nb = blocks_for((int64_t)ell, 256);
     const bool known = with_int<1, 2, 4>(L.R, [&](auto r) {
         hipLaunchKernelGGL(ell_fill_padding<decltype(r)::value>, dim3(nb), dim3(256), 0, c->stream, L.vals, L.cols, L.nslices, L.W, L.nloc, L.g.lead);
@@ -3715,7 +3594,7 @@ int gen_stored_level(mg_context* c, int level, int N, int W, Launch launch) {
     L.W = W;
     MG_TRY(alloc_ell(c, L));
     MG_TRY(alloc_level_vectors(c, L));
-    unsigned long long* d_counts = reinterpret_cast<unsigned long long*>(c->partials);
+    unsigned long long* d_counts = reinterpret_cast<unsigned long long*>(c->partials.get());
     HIP_TRY(hipMemsetAsync(d_counts, 0, 2 * sizeof(unsigned long long), c->stream));
     launch(L, grid3(L.g, L.g.nk), d_counts);
     HIP_TRY(hipGetLastError());
@@ -3746,6 +3625,25 @@ GenArgs gen_args(const mg_context* c, int N, int prune_zeros) {
     return a;
 }
 
+// The end of a handle, whole or half-created: what is no device memory is destroyed by hand, the memory by its owners
+// (DevBuf / DVector members of the handle, its levels and the direct solver).
+struct ContextDeleter {
+    void operator()(mg_context* c) const {
+        (void)hipSetDevice(c->device);
+        if (c->stream) (void)hipStreamSynchronize(c->stream);
+        if (c->comm_stream) (void)hipStreamSynchronize(c->comm_stream);
+        drop_graphs(c);
+        if (c->h_scalars) (void)hipHostFree(c->h_scalars);
+        if (c->comm.h_stage) (void)hipHostFree(c->comm.h_stage);
+        if (c->comm.nccl) g_rccl.CommDestroy(c->comm.nccl);
+        if (c->ev_boundary) (void)hipEventDestroy(c->ev_boundary);
+        if (c->ev_halo) (void)hipEventDestroy(c->ev_halo);
+        if (c->comm_stream) (void)hipStreamDestroy(c->comm_stream);
+        if (c->stream) (void)hipStreamDestroy(c->stream);
+        delete c;
+    }
+};
+
 }  // namespace
 
 // =====================================================================================================
@@ -3763,7 +3661,8 @@ int mg_create(int n_levels, int dim, int device, mg_handle* out) {
     if (ndev <= 0) return fail("no HIP device visible: this library has no CPU path");
     if (device < 0 || device >= ndev) return fail("device index out of range");
     HIP_TRY(hipSetDevice(device));
-    mg_context* c = new mg_context();
+    std::unique_ptr<mg_context, ContextDeleter> owner(new mg_context());       // (a failure below leaves nothing behind)
+    mg_context* const c = owner.get();
     if (const char* e = std::getenv("MG_COMM_PRIORITY")) c->comm_priority = std::atoi(e) != 0;      // experiments only
     c->dim = dim;
     c->nlev = n_levels;
@@ -3781,46 +3680,17 @@ int mg_create(int n_levels, int dim, int device, mg_handle* out) {
     }
     HIP_TRY(hipEventCreateWithFlags(&c->ev_boundary, hipEventDisableTiming));
     HIP_TRY(hipEventCreateWithFlags(&c->ev_halo, hipEventDisableTiming));
-    MG_TRY(dev_alloc(c, &c->partials, 2 * kMaxParts));
-    MG_TRY(dev_alloc(c, &c->scalars, 8));
-    MG_TRY(dev_alloc(c, &c->done, 1));
+    MG_TRY(c->partials.alloc(c, 2 * kMaxParts));
+    MG_TRY(c->scalars.alloc(c, 8));
+    MG_TRY(c->done.alloc(c, 1));
     HIP_TRY(hipMemsetAsync(c->done, 0, sizeof(int), c->stream));
     HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&c->h_scalars), 16 * sizeof(double), hipHostMallocDefault));
-    *out = c;
+    *out = owner.release();
     return 0;
 }
 
 int mg_destroy(mg_handle c) {
-    if (!c) return 0;
-    (void)hipSetDevice(c->device);
-    (void)hipStreamSynchronize(c->stream);
-    if (c->comm_stream) (void)hipStreamSynchronize(c->comm_stream);
-    drop_graphs(c);
-    for (auto& L : c->L) free_level(c, L);
-    free_level(c, c->mass);
-    (void)hipFree(c->mass_out.raw); (void)hipFree(c->diff.raw); (void)hipFree(c->uexact.raw);
-    (void)hipFree(c->ptab_count); (void)hipFree(c->ptab_off); (void)hipFree(c->ptab_w);
-    (void)hipFree(c->rtab_count); (void)hipFree(c->rtab_off); (void)hipFree(c->rtab_w);
-    (void)hipFree(c->partials);
-    (void)hipFree(c->scalars);
-    (void)hipFree(c->done);
-    (void)hipFree(c->pcg_r);
-    (void)hipFree(c->pcg_z);
-    (void)hipFree(c->pcg_q);
-    (void)hipFree(c->pcg_p.raw);
-    (void)hipFree(c->pcg_part_a);
-    (void)hipFree(c->pcg_part_b);
-    (void)hipFree(c->fcg_work);
-    (void)hipFree(c->fcg_spmv);
-    (void)hipFree(c->stage);
-    if (c->h_scalars) (void)hipHostFree(c->h_scalars);
-    if (c->comm.h_stage) (void)hipHostFree(c->comm.h_stage);
-    if (c->comm.nccl) g_rccl.CommDestroy(c->comm.nccl);
-    if (c->ev_boundary) (void)hipEventDestroy(c->ev_boundary);
-    if (c->ev_halo) (void)hipEventDestroy(c->ev_halo);
-    if (c->comm_stream) (void)hipStreamDestroy(c->comm_stream);
-    (void)hipStreamDestroy(c->stream);
-    delete c;
+    if (c) ContextDeleter{}(c);
     return 0;
 }
 
@@ -3848,13 +3718,14 @@ int mg_comm_selftest(int device) {
     ncclComm_t comm = nullptr;
     NCCL_TRY(g_rccl.CommInitRank(&comm, 1, id, 0));
     hipStream_t s = nullptr;
-    double* d = nullptr;
+    DevTemp d_t;
     const int n = 1024;
     std::vector<double> h(3 * n);
     for (int i = 0; i < n; ++i) { h[i] = 1.0 + i; h[n + i] = 0.0; h[2 * n + i] = -1.0; }
     int rc = [&]() -> int {
         HIP_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d), 3 * n * sizeof(double)));
+        MG_TRY(d_t.alloc(3 * n * sizeof(double)));
+        double* const d = d_t.as<double>();
         HIP_TRY(hipMemcpyAsync(d, h.data(), 3 * n * sizeof(double), hipMemcpyHostToDevice, s));
         NCCL_TRY(g_rccl.AllReduce(d, d, n, ncclDouble, ncclSum, comm, s));            // one rank: unchanged
         NCCL_TRY(g_rccl.GroupStart());
@@ -3870,7 +3741,6 @@ int mg_comm_selftest(int device) {
             if (h[i] != 1.0 + i || h[n + i] != 1.0 + i || h[2 * n + i] != -1.0) return fail("RCCL self-test: wrong data");
         return 0;
     }();
-    if (d) (void)hipFree(d);
     if (s) (void)hipStreamDestroy(s);
     g_rccl.CommDestroy(comm);
     return rc;
@@ -3981,8 +3851,7 @@ int mg_set_prolongation_table(mg_handle c, const int* count, const int* offsets,
     HIP_TRY(hipSetDevice(c->device));
     ++c->epoch;
     (void)hipStreamSynchronize(c->stream);
-    (void)hipFree(c->ptab_count); (void)hipFree(c->ptab_off); (void)hipFree(c->ptab_w);
-    c->ptab_count = nullptr; c->ptab_off = nullptr; c->ptab_w = nullptr;
+    c->ptab_count.reset(); c->ptab_off.reset(); c->ptab_w.reset();
     c->p1_prolong = 0;                                            // (a table and the P1 embedding exclude each other)
     if (!count && !offsets && !weights) return 0;                 // back to the reference's interpolation
     if (!count || !offsets || !weights) return fail("null table");
@@ -3992,12 +3861,12 @@ int mg_set_prolongation_table(mg_handle c, const int* count, const int* offsets,
             for (int d = 0; d < 3; ++d)
                 if (offsets[(r * 10 + e) * 3 + d] < 0 || offsets[(r * 10 + e) * 3 + d] > 2) return fail("table offsets must be 0..2");
     }
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->ptab_count), 64 * sizeof(int)));
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->ptab_off), 64 * 10 * 3 * sizeof(int)));
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->ptab_w), 64 * 10 * sizeof(double)));
-    HIP_TRY(hipMemcpy(c->ptab_count, count, 64 * sizeof(int), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(c->ptab_off, offsets, 64 * 10 * 3 * sizeof(int), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(c->ptab_w, weights, 64 * 10 * sizeof(double), hipMemcpyHostToDevice));
+    MG_TRY(c->ptab_count.alloc(64 * sizeof(int)));
+    MG_TRY(c->ptab_off.alloc(64 * 10 * 3 * sizeof(int)));
+    MG_TRY(c->ptab_w.alloc(64 * 10 * sizeof(double)));
+    HIP_TRY(hipMemcpy(c->ptab_count.p, count, 64 * sizeof(int), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(c->ptab_off.p, offsets, 64 * 10 * 3 * sizeof(int), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(c->ptab_w.p, weights, 64 * 10 * sizeof(double), hipMemcpyHostToDevice));
     return 0;
 }
 
@@ -4006,10 +3875,9 @@ int mg_set_prolongation_p1(mg_handle c, int enable) {
     if (enable != 0 && enable != 1) return fail("enable must be 0 or 1");
     HIP_TRY(hipSetDevice(c->device));
     ++c->epoch;
-    if (enable && c->ptab_count) {                                // a table and the P1 embedding exclude each other
+    if (enable && c->ptab_count.p) {                                // a table and the P1 embedding exclude each other
         (void)hipStreamSynchronize(c->stream);
-        (void)hipFree(c->ptab_count); (void)hipFree(c->ptab_off); (void)hipFree(c->ptab_w);
-        c->ptab_count = nullptr; c->ptab_off = nullptr; c->ptab_w = nullptr;
+        c->ptab_count.reset(); c->ptab_off.reset(); c->ptab_w.reset();
     }
     c->p1_prolong = enable;
     return 0;
@@ -4020,8 +3888,7 @@ int mg_set_restriction_table(mg_handle c, int max_entries, const int* count, con
     HIP_TRY(hipSetDevice(c->device));
     ++c->epoch;
     (void)hipStreamSynchronize(c->stream);
-    (void)hipFree(c->rtab_count); (void)hipFree(c->rtab_off); (void)hipFree(c->rtab_w);
-    c->rtab_count = nullptr; c->rtab_off = nullptr; c->rtab_w = nullptr; c->rtab_m = 0;
+    c->rtab_count.reset(); c->rtab_off.reset(); c->rtab_w.reset(); c->rtab_m = 0;
     if (!count && !offsets && !weights) return 0;
     if (!count || !offsets || !weights || max_entries < 1 || max_entries > 4096) return fail("bad restriction table");
     for (int t = 0; t < 8; ++t) {
@@ -4031,12 +3898,12 @@ int mg_set_restriction_table(mg_handle c, int max_entries, const int* count, con
                 if (std::abs(offsets[((size_t)t * max_entries + e) * 3 + d]) > 4) return fail("table offsets must be within +-4");
     }
     const size_t n = (size_t)8 * max_entries;
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->rtab_count), 8 * sizeof(int)));
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->rtab_off), n * 3 * sizeof(int)));
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->rtab_w), n * sizeof(double)));
-    HIP_TRY(hipMemcpy(c->rtab_count, count, 8 * sizeof(int), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(c->rtab_off, offsets, n * 3 * sizeof(int), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(c->rtab_w, weights, n * sizeof(double), hipMemcpyHostToDevice));
+    MG_TRY(c->rtab_count.alloc(8 * sizeof(int)));
+    MG_TRY(c->rtab_off.alloc(n * 3 * sizeof(int)));
+    MG_TRY(c->rtab_w.alloc(n * sizeof(double)));
+    HIP_TRY(hipMemcpy(c->rtab_count.p, count, 8 * sizeof(int), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(c->rtab_off.p, offsets, n * 3 * sizeof(int), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(c->rtab_w.p, weights, n * sizeof(double), hipMemcpyHostToDevice));
     c->rtab_m = max_entries;
     return 0;
 }
@@ -4266,7 +4133,7 @@ int upload_permutation(mg_context* c, Level& L, const int64_t* grid_index, int64
         seen[(size_t)p] = 1;
         p32[(size_t)d] = (int)p;
     }
-    MG_TRY(dev_alloc(c, &L.perm, (size_t)n_rows));
+    MG_TRY(L.perm.alloc(c, (size_t)n_rows));
     HIP_TRY(hipMemcpy(L.perm, p32.data(), (size_t)n_rows * 4, hipMemcpyHostToDevice));
     return 0;
 }
@@ -4319,12 +4186,12 @@ int build_level_from_csr(mg_context* c, int level, Level& L, int64_t n_rows, int
     }
     CsrArgs a{};
     a.indptr = dp_ptr; a.indptr64 = indptr_is_64; a.indices = static_cast<const int*>(dp_idx); a.data = static_cast<const double*>(dp_val);
-    a.perm = local_cols ? static_cast<const int*>(d_map.p) : L.perm;
+    a.perm = local_cols ? d_map.as<const int>() : L.perm;
     a.n = n_rows; a.row0 = L.row0; a.nloc = L.nloc; a.lead = L.g.lead; a.xlen = L.xlen;
     a.prune = prune_zeros;
     a.sort = device_csr ? 0 : 1;
     // pass 1: widest kept row, kept entries, sanity flags
-    unsigned long long* d_stats = reinterpret_cast<unsigned long long*>(c->partials);
+    unsigned long long* d_stats = reinterpret_cast<unsigned long long*>(c->partials.get());
     HIP_TRY(hipMemsetAsync(d_stats, 0, 4 * sizeof(unsigned long long), c->stream));
     hipLaunchKernelGGL(csr_scan, dim3(blocks_for(n_rows, 256)), dim3(256), 0, c->stream, a, d_stats);
     unsigned long long stats[4] = {0, 0, 0, 0};
@@ -4419,8 +4286,8 @@ int galerkin_level(mg_context* c, int level) {
     MG_TRY(d_idx.alloc((size_t)nnz * 4));
     MG_TRY(d_val.alloc((size_t)nnz * 8));
     a.gc = C.g;
-    a.indptr = static_cast<int64_t*>(d_ptr.p); a.indices = static_cast<int*>(d_idx.p); a.data = static_cast<double*>(d_val.p);
-    a.flag = reinterpret_cast<int*>(c->partials);
+    a.indptr = d_ptr.as<int64_t>(); a.indices = d_idx.as<int>(); a.data = d_val.as<double>();
+    a.flag = reinterpret_cast<int*>(c->partials.get());
     HIP_TRY(hipMemsetAsync(a.flag, 0, sizeof(int), c->stream));
     const dim3 grid = grid3(C.g, C.g.nk);
     int rc = 0;
@@ -4430,8 +4297,8 @@ int galerkin_level(mg_context* c, int level) {
     HIP_TRY(hipMemcpyAsync(&flag, a.flag, sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (flag) return fail("a Galerkin entry falls outside the coarse Kuhn pattern");
-    MG_TRY(build_level_from_csr(c, level - 1, C, n, nnz, d_ptr.p, 1, static_cast<const int32_t*>(d_idx.p),
-                                static_cast<const double*>(d_val.p), nullptr, 1, true, nullptr, 0, true));
+    MG_TRY(build_level_from_csr(c, level - 1, C, n, nnz, d_ptr.p, 1, d_idx.as<const int32_t>(),
+                                d_val.as<const double>(), nullptr, 1, true, nullptr, 0, true));
     return build.done();
 }
 
@@ -4554,8 +4421,8 @@ int mg_gen_lattice_level(mg_handle c, int level, int N, int width, const int* co
     HIP_TRY(hipMemcpy(d_load.p, load, 8 * sizeof(double), hipMemcpyHostToDevice));
     LatticeArgs a{};
     a.N = N; a.dim = c->dim; a.W = width;
-    a.count = static_cast<const int*>(d_count.p); a.off = static_cast<const int*>(d_off.p);
-    a.val = static_cast<const double*>(d_val.p); a.load = static_cast<const double*>(d_load.p);
+    a.count = d_count.as<const int>(); a.off = d_off.as<const int>();
+    a.val = d_val.as<const double>(); a.load = d_load.as<const double>();
     return gen_stored_level(c, level, N, width, [&](const Level& L, dim3 grid, unsigned long long* counts) {
         const dim3 blk(kPlaneBlock);
         a.g = L.g;
@@ -4581,7 +4448,7 @@ int check_kappa(mg_context* c, const double* d_kappa, int64_t n, int64_t base, i
     HIP_TRY(hipMemsetAsync(d_first.p, 0xff, sizeof(unsigned long long), c->stream));
     const unsigned nb = (unsigned)std::max<int64_t>(1, std::min<int64_t>(8192, (n + 255) / 256));
     hipLaunchKernelGGL(kappa_check, dim3(nb), dim3(256), 0, c->stream, d_kappa, n, base,
-                       static_cast<unsigned long long*>(d_first.p));
+                       d_first.as<unsigned long long>());
     HIP_TRY(hipGetLastError());
     unsigned long long first = 0;
     HIP_TRY(hipMemcpyAsync(&first, d_first.p, sizeof(first), hipMemcpyDeviceToHost, c->stream));
@@ -4630,8 +4497,8 @@ int mg_gen_diffusion_level(mg_handle c, int level, int N, const double* kappa, i
     DevTemp d_kappa;
     MG_TRY(d_kappa.alloc((size_t)n * 8));
     HIP_TRY(hipMemcpy(d_kappa.p, kappa + (size_t)kc0 * cp, (size_t)n * 8, hipMemcpyHostToDevice));
-    MG_TRY(check_kappa(c, static_cast<const double*>(d_kappa.p), n, (int64_t)kc0 * cp, N));
-    return gen_diffusion_level(c, level, N, static_cast<const double*>(d_kappa.p), kc0, prune_zeros);
+    MG_TRY(check_kappa(c, d_kappa.as<const double>(), n, (int64_t)kc0 * cp, N));
+    return gen_diffusion_level(c, level, N, d_kappa.as<const double>(), kc0, prune_zeros);
 }
 
 namespace {
@@ -4644,8 +4511,9 @@ int fill_rhs_mf(mg_context* c, Level& L, const double* d_kappa) {
     return 0;
 }
 
-// the matrix-free level from a whole device kappa (N^3 cells), which the level takes over on success
-int gen_diffusion_level_mf(mg_context* c, int level, int N, double* d_kappa, int64_t n) {
+// the matrix-free level from a whole device kappa (N^3 cells, n of them), which the level takes over on success
+int gen_diffusion_level_mf(mg_context* c, int level, int N, DevTemp& kappa, int64_t n) {
+    const double* const d_kappa = kappa.as<const double>();
     Level& L = c->L[level];
     LevelBuild build(c, L);
     MG_TRY(setup_geometry(c, L, level, N));
@@ -4665,9 +4533,7 @@ int gen_diffusion_level_mf(mg_context* c, int level, int N, double* d_kappa, int
     L.rep_sym = 1;
     L.rb_ok = false;
     L.mf = true;
-    L.kappa = d_kappa;
-    L.kappa_n = n;
-    c->bytes += n * (int64_t)sizeof(double);
+    L.kappa.adopt(c, kappa.release<double>(), (size_t)n);
     L.set = true;
     L.has_matrix = true;
     return build.done();
@@ -4697,10 +4563,8 @@ int mg_gen_diffusion_level_mf(mg_handle c, int level, int N, const double* kappa
     DevTemp d_kappa;
     MG_TRY(d_kappa.alloc((size_t)n * 8));
     HIP_TRY(hipMemcpy(d_kappa.p, kappa, (size_t)n * 8, hipMemcpyHostToDevice));
-    MG_TRY(check_kappa(c, static_cast<const double*>(d_kappa.p), n, 0, N));
-    MG_TRY(gen_diffusion_level_mf(c, level, N, static_cast<double*>(d_kappa.p), n));
-    d_kappa.p = nullptr;                         // the level owns it now
-    return 0;
+    MG_TRY(check_kappa(c, d_kappa.as<const double>(), n, 0, N));
+    return gen_diffusion_level_mf(c, level, N, d_kappa, n);
 }
 
 namespace {
@@ -4754,18 +4618,12 @@ int gen_diffusion_hierarchy(mg_context* c, int top_level, int N, const double* s
         if (l > 0) {
             const int Nc = Nl / 2;
             MG_TRY(coarse.alloc((size_t)(cell_plane(c, Nc) * Nc) * 8));
-            MG_TRY(launch_kappa_ingest(c, src, static_cast<double*>(own.p), static_cast<double*>(coarse.p), Nc, averaging));
+            MG_TRY(launch_kappa_ingest(c, src, own.as<double>(), coarse.as<double>(), Nc, averaging));
             HIP_TRY(hipStreamSynchronize(c->stream));
         }
-        if (mf) {
-            DevTemp& mine = own.p ? own : held;
-            MG_TRY(gen_diffusion_level_mf(c, l, Nl, static_cast<double*>(mine.p), n));
-            mine.p = nullptr;                   // the level owns it now
-        }
-        if (held.p) { HIP_TRY(hipFree(held.p)); held.p = nullptr; }
-        held.p = coarse.p;
-        coarse.p = nullptr;
-        src = static_cast<const double*>(held.p);
+        if (mf) MG_TRY(gen_diffusion_level_mf(c, l, Nl, own.p ? own : held, n));
+        held = std::move(coarse);
+        src = held.as<const double>();
         c->L[l].diffusion_hierarchy = true;
     }
     return 0;
@@ -4782,7 +4640,7 @@ int gen_diffusion_hierarchy_host(mg_context* c, const std::string& who, int top_
     DevTemp held;
     MG_TRY(held.alloc((size_t)n * 8));
     HIP_TRY(hipMemcpy(held.p, kappa_top, (size_t)n * 8, hipMemcpyHostToDevice));
-    return gen_diffusion_hierarchy(c, top_level, N, static_cast<const double*>(held.p), held, averaging, min_rows);
+    return gen_diffusion_hierarchy(c, top_level, N, held.as<const double>(), held, averaging, min_rows);
 }
 
 }  // namespace
@@ -4822,7 +4680,7 @@ int mg_refresh_diffusion_hierarchy(mg_handle c, int top_level, const double* kap
         if (l < top_level && 2 * L.N != c->L[l + 1].N)
             return fail(who + ": levels " + std::to_string(l + 1) + " and " + std::to_string(l) + " come from hierarchies of different "
                         "sizes (" + std::to_string(c->L[l + 1].N) + " and " + std::to_string(L.N) + " cells per dimension)");
-        if (L.mf && L.kappa_n != cell_plane(c, L.N) * L.N) return fail(who + ": level " + std::to_string(l) + " keeps a kappa of another size");
+        if (L.mf && (int64_t)L.kappa.count() != cell_plane(c, L.N) * L.N) return fail(who + ": level " + std::to_string(l) + " keeps a kappa of another size");
         if (L.faces != c->diffusion_faces)
             return fail(who + ": level " + std::to_string(l) + " was generated with the face set " + std::to_string(L.faces) +
                         ", the handle's is " + std::to_string(c->diffusion_faces) + " now (mg_set_diffusion_faces): generate the hierarchy again");
@@ -4852,9 +4710,9 @@ int mg_refresh_diffusion_hierarchy(mg_handle c, int top_level, const double* kap
             if (c->L[l - 1].mf) coarse_p = c->L[l - 1].kappa;
             else {
                 MG_TRY(coarse.alloc((size_t)(cell_plane(c, Nc) * Nc) * 8));
-                coarse_p = static_cast<double*>(coarse.p);
+                coarse_p = coarse.as<double>();
             }
-            MG_TRY(launch_kappa_ingest(c, src, mf && src != L.kappa ? L.kappa : nullptr, coarse_p, Nc, averaging));
+            MG_TRY(launch_kappa_ingest(c, src, mf && src != L.kappa ? L.kappa.get() : nullptr, coarse_p, Nc, averaging));
         }
         if (mf) {                               // kappa overwritten in place; the vectors are those of a fresh level
             MG_TRY(fill_rhs_mf(c, L, L.kappa));
@@ -4862,9 +4720,7 @@ int mg_refresh_diffusion_hierarchy(mg_handle c, int top_level, const double* kap
             HIP_TRY(hipMemsetAsync(L.v2.raw, 0, (size_t)vec_total(L) * sizeof(double), c->stream));
         }
         HIP_TRY(hipStreamSynchronize(c->stream));
-        if (held.p) { HIP_TRY(hipFree(held.p)); held.p = nullptr; }
-        held.p = coarse.p;
-        coarse.p = nullptr;
+        held = std::move(coarse);
         src = coarse_p;
     }
     return 0;
@@ -4895,7 +4751,7 @@ int mg_level_matrix_free(mg_handle c, int level, int* on, int64_t* kappa_bytes) 
     MG_TRY(check_level(c, level));
     const Level& L = c->L[level];
     if (on) *on = L.mf ? 1 : 0;
-    if (kappa_bytes) *kappa_bytes = L.mf ? L.kappa_n * (int64_t)sizeof(double) : 0;
+    if (kappa_bytes) *kappa_bytes = L.mf ? (int64_t)(L.kappa.count() * sizeof(double)) : 0;
     return 0;
 }
 
@@ -4908,37 +4764,26 @@ int mg_jacobi_split(int device, int64_t n_rows, int64_t nnz, const void* indptr,
     HIP_TRY(hipGetDeviceCount(&ndev));
     if (ndev <= 0) return fail("no HIP device visible: this library has no CPU path");
     HIP_TRY(hipSetDevice(device));
-    void* d_ptr = nullptr;
-    int* d_idx = nullptr;
-    double *d_val = nullptr, *d_dinv = nullptr, *d_scaled = nullptr;
-    unsigned char* d_keep = nullptr;
+    DevTemp d_ptr, d_idx, d_val, d_dinv, d_scaled, d_keep;
     const size_t ptr_bytes = (size_t)(n_rows + 1) * (indptr_is_64 ? 8 : 4);
-    const size_t nz = std::max<size_t>(1, (size_t)nnz);
-    auto cleanup = [&]() {
-        (void)hipFree(d_ptr); (void)hipFree(d_idx); (void)hipFree(d_val);
-        (void)hipFree(d_dinv); (void)hipFree(d_scaled); (void)hipFree(d_keep);
-    };
-    int rc = [&]() -> int {
-        HIP_TRY(hipMalloc(&d_ptr, ptr_bytes));
-        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d_idx), nz * 4));
-        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d_val), nz * 8));
-        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d_dinv), std::max<size_t>(1, (size_t)n_rows) * 8));
-        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d_scaled), nz * 8));
-        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d_keep), nz));
-        HIP_TRY(hipMemcpy(d_ptr, indptr, ptr_bytes, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d_idx, indices, (size_t)nnz * 4, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d_val, data, (size_t)nnz * 8, hipMemcpyHostToDevice));
-        CsrArgs a{};
-        a.indptr = d_ptr; a.indptr64 = indptr_is_64; a.indices = d_idx; a.data = d_val; a.n = n_rows;
-        hipLaunchKernelGGL(jacobi_split, dim3(blocks_for(n_rows, 256)), dim3(256), 0, 0, a, d_dinv, d_scaled, d_keep);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpy(dinv, d_dinv, (size_t)n_rows * 8, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(scaled, d_scaled, (size_t)nnz * 8, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(keep, d_keep, (size_t)nnz, hipMemcpyDeviceToHost));
-        return 0;
-    }();
-    cleanup();
-    return rc;
+    MG_TRY(d_ptr.alloc(ptr_bytes));
+    MG_TRY(d_idx.alloc((size_t)nnz * 4));
+    MG_TRY(d_val.alloc((size_t)nnz * 8));
+    MG_TRY(d_dinv.alloc((size_t)n_rows * 8));
+    MG_TRY(d_scaled.alloc((size_t)nnz * 8));
+    MG_TRY(d_keep.alloc((size_t)nnz));
+    HIP_TRY(hipMemcpy(d_ptr.p, indptr, ptr_bytes, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_idx.p, indices, (size_t)nnz * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_val.p, data, (size_t)nnz * 8, hipMemcpyHostToDevice));
+    CsrArgs a{};
+    a.indptr = d_ptr.p; a.indptr64 = indptr_is_64; a.indices = d_idx.as<int>(); a.data = d_val.as<double>(); a.n = n_rows;
+    hipLaunchKernelGGL(jacobi_split, dim3(blocks_for(n_rows, 256)), dim3(256), 0, 0, a, d_dinv.as<double>(), d_scaled.as<double>(),
+                       d_keep.as<unsigned char>());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(dinv, d_dinv.p, (size_t)n_rows * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(scaled, d_scaled.p, (size_t)nnz * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(keep, d_keep.p, (size_t)nnz, hipMemcpyDeviceToHost));
+    return 0;
 }
 
 int mg_level_info(mg_handle c, int level, int64_t* n_global, int64_t* n_local, int64_t* row0, int64_t* nnz_stored,
@@ -5008,18 +4853,13 @@ int mg_get_vector(mg_handle c, int level, int which, double* host, int gather) {
     const unsigned nb = (unsigned)std::min<int64_t>(4096, (L.n_global + 255) / 256);
     if (gather && is_slab(c, L)) {
         // all-gather slabs in lexicographic order inside a scratch vector, then permute
-        double* full = nullptr;
-        MG_TRY(dev_alloc(c, &full, (size_t)L.n_global));
+        DevBuf<double> full;
+        MG_TRY(full.alloc(c, (size_t)L.n_global));
         HIP_TRY(hipMemcpyAsync(full + L.row0, v->rows, (size_t)L.nloc * 8, hipMemcpyDeviceToDevice, c->stream));
-        int rc = allgather_planes(c, L.splits, L.g.plane, full);
-        if (!rc) {
-            hipLaunchKernelGGL(gather_out, dim3(nb), dim3(256), 0, c->stream, full, L.perm, L.n_global, (int64_t)0,
-                               L.n_global, (int64_t)0, c->stage);
-        }
-        hipError_t e = hipStreamSynchronize(c->stream);
-        dev_free(c, full, (size_t)L.n_global);
-        if (rc) return rc;
-        HIP_TRY(e);
+        MG_TRY(allgather_planes(c, L.splits, L.g.plane, full));
+        hipLaunchKernelGGL(gather_out, dim3(nb), dim3(256), 0, c->stream, full, L.perm, L.n_global, (int64_t)0,
+                           L.n_global, (int64_t)0, c->stage);
+        HIP_TRY(hipStreamSynchronize(c->stream));
         HIP_TRY(hipMemcpy(host, c->stage, (size_t)L.n_global * 8, hipMemcpyDeviceToHost));
         return 0;
     }
@@ -5246,20 +5086,13 @@ int mg_quadratic_form(mg_handle c, int level, int which, double* out) {
     if (!v || !v->raw || v == &L.v2) return fail("vector is not available for a quadratic form");
     MG_TRY(exchange_halo(c, L, *v));
     const unsigned grid = L.mf ? mf_plan(c, L).grid : blocks_for(L.nslices, WAVES_PER_BLOCK);
-    double* parts = nullptr;
-    MG_TRY(dev_alloc(c, &parts, grid));
-    int rc = launch_ell(c, L, {.mode = MODE_SPMV, .dot = true, .x_base = v->base, .out_rows = L.v2.rows, .partials = parts});
-    if (!rc) {
-        hipLaunchKernelGGL(reduce_partials, dim3(1), dim3(BLOCK), 0, c->stream, parts, (int)grid, c->scalars);
-        if (!L.replicated) rc = allreduce_sum(c, c->scalars, 1);
-    }
-    if (!rc) {
-        hipError_t e = hipMemcpyAsync(c->h_scalars, c->scalars, sizeof(double), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess) rc = fail(hipGetErrorString(e));
-    }
-    dev_free(c, parts, grid);
-    if (rc) return rc;
+    DevBuf<double> parts;
+    MG_TRY(parts.alloc(c, grid));
+    MG_TRY(launch_ell(c, L, {.mode = MODE_SPMV, .dot = true, .x_base = v->base, .out_rows = L.v2.rows, .partials = parts}));
+    hipLaunchKernelGGL(reduce_partials, dim3(1), dim3(BLOCK), 0, c->stream, parts, (int)grid, c->scalars);
+    if (!L.replicated) MG_TRY(allreduce_sum(c, c->scalars, 1));
+    HIP_TRY(hipMemcpyAsync(c->h_scalars, c->scalars, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
     *out = c->h_scalars[0];
     return 0;
 }
@@ -5278,14 +5111,12 @@ int mass_form(mg_context* c, Level& L, DVector& x, int slot) {
     const unsigned nparts = blocks_for(M.nslices, WAVES_PER_BLOCK);
     if (nparts > 2 * kMaxParts) {
         // more partial sums than the handle's scratch holds: a buffer of its own for this call
-        double* parts = nullptr;
-        MG_TRY(dev_alloc(c, &parts, nparts));
+        DevBuf<double> parts;
+        MG_TRY(parts.alloc(c, nparts));
         unsigned grid = 0;
-        int rc = launch_ell(c, M, {.mode = MODE_SPMV, .dot = true, .x_base = x.base, .out_rows = c->mass_out.rows, .partials = parts, .grid_out = &grid});
-        if (!rc) hipLaunchKernelGGL(reduce_partials, dim3(1), dim3(BLOCK), 0, c->stream, parts, (int)grid, c->scalars + slot);
-        if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) rc = fail("mass_form: stream error");
-        dev_free(c, parts, nparts);
-        MG_TRY(rc);
+        MG_TRY(launch_ell(c, M, {.mode = MODE_SPMV, .dot = true, .x_base = x.base, .out_rows = c->mass_out.rows, .partials = parts, .grid_out = &grid}));
+        hipLaunchKernelGGL(reduce_partials, dim3(1), dim3(BLOCK), 0, c->stream, parts, (int)grid, c->scalars + slot);
+        if (hipStreamSynchronize(c->stream) != hipSuccess) return fail("mass_form: stream error");
     } else {
         unsigned grid = 0;
         MG_TRY(launch_ell(c, M, {.mode = MODE_SPMV, .dot = true, .x_base = x.base, .out_rows = c->mass_out.rows, .partials = c->partials,
@@ -5340,14 +5171,12 @@ int mg_set_mass_csr(mg_handle c, int level, int64_t n_rows, int64_t nnz, const v
     Level& L = c->L[level];
     if (n_rows != L.n_global) return fail("mass matrix has " + std::to_string(n_rows) + " rows, level has " + std::to_string(L.n_global));
     Level& M = c->mass;
-    // the work vector of mass_form is sized for the level the previous mass matrix belonged to
-    if (c->mass_out.raw && c->mass_level >= 0) vec_free(c, c->L[c->mass_level], &c->mass_out);
+    vec_free(&c->mass_out);             // (sized for the level the previous mass matrix belonged to)
     LevelBuild build(c, M);
     c->mass_level = -1;
-    M = Level();
     MG_TRY(setup_geometry(c, M, level, L.N));
     if (L.perm) {                       // the level's DoF numbering
-        MG_TRY(dev_alloc(c, &M.perm, (size_t)L.n_global));
+        MG_TRY(M.perm.alloc(c, (size_t)L.n_global));
         if (hipMemcpy(M.perm, L.perm, (size_t)L.n_global * sizeof(int), hipMemcpyDeviceToDevice) != hipSuccess)
             return fail("copy of the level's permutation failed");
     }
@@ -5362,10 +5191,7 @@ int mg_set_exact(mg_handle c, int level, const double* host) {
     if (!host) return fail("null host vector");
     HIP_TRY(hipSetDevice(c->device));
     Level& L = c->L[level];
-    if (c->uexact.raw && c->uexact_level != level) {
-        vec_free(c, c->L[c->uexact_level], &c->uexact);
-        if (c->diff.raw) vec_free(c, c->L[c->uexact_level], &c->diff);
-    }
+    if (c->uexact_level != level) { vec_free(&c->uexact); vec_free(&c->diff); }
     MG_TRY(vec_alloc(c, L, &c->uexact));
     c->uexact_level = level;
     return upload_vector(c, L, c->uexact, host);
@@ -5588,11 +5414,11 @@ int mg_time_kernel(mg_handle c, const char* kernel, int level, int reps, double*
         if (k == "kappa_ingest") {  // the copy and the coarsening in one pass, from a scratch copy of kappa back into the level's own
             if (!L.mf) return fail("level is not a matrix-free diffusion level");
             if (!ki_src.p) {
-                MG_TRY(ki_src.alloc((size_t)L.kappa_n * 8));
-                MG_TRY(ki_coarse.alloc((size_t)(L.kappa_n / 8) * 8));
-                HIP_TRY(hipMemcpyAsync(ki_src.p, L.kappa, (size_t)L.kappa_n * 8, hipMemcpyDeviceToDevice, c->stream));
+                MG_TRY(ki_src.alloc(L.kappa.count() * 8));
+                MG_TRY(ki_coarse.alloc((L.kappa.count() / 8) * 8));
+                HIP_TRY(hipMemcpyAsync(ki_src.p, L.kappa, L.kappa.count() * 8, hipMemcpyDeviceToDevice, c->stream));
             }
-            return launch_kappa_ingest(c, static_cast<const double*>(ki_src.p), L.kappa, static_cast<double*>(ki_coarse.p), L.N / 2,
+            return launch_kappa_ingest(c, ki_src.as<const double>(), L.kappa, ki_coarse.as<double>(), L.N / 2,
                                        MG_KAPPA_ARITHMETIC);
         }
         if (k == "restrict") return level > 0 ? restrict_to(c, level, c->restriction) : fail("level 0");
