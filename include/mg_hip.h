@@ -282,6 +282,39 @@ enum mg_face { MG_FACE_XLO = 1, MG_FACE_XHI = 2, MG_FACE_YLO = 4, MG_FACE_YHI = 
 int mg_set_diffusion_faces(mg_handle h, int dirichlet_faces);
 /* *dirichlet_faces = the handle's face set */
 int mg_diffusion_faces(mg_handle h, int* dirichlet_faces);
+/* A lumped reaction term for the generated diffusion levels (no reference counterpart): the operator A(kappa) + R(sigma) of
+ * -div(kappa grad u) + sigma u, R diagonal.  sigma is one double per cell of a 3-D grid of elements_per_dim^3 cells, in the cell
+ * order of mg_gen_diffusion_level, finite and >= 0 (zero is allowed).  R of a cell field w is the row-sum lumped P1 mass of the
+ * Kuhn mesh with the weights of the load:
+ *     R(w)_i = ((sum over the 8 cells c around node i, in ascending index, of t_{c,i} w_c) / 24) * h^3,   h = 1 / N,
+ * t = 6 where i is the cell's (0,0,0) or (1,1,1) corner, else 2; a cell outside the grid counts as +0.0 (w == 1: the load of
+ * f == 1 on a free node).  A free row of a generated level gets diag = (the stiffness diagonal as before) + R(sigma)_i, one
+ * more addition; Dirichlet rows stay identity rows; off-diagonals, the lifted right-hand side and the load do not change.
+ * One implicit Euler step of du/dt - div(kappa grad u) = f is the solve with sigma = 1 / dt and the right-hand side
+ * b + R(1 / dt) u_old.  Summation order: reaction_diag (mg_kernels.hip.h); poisson.reaction_diag and
+ * poisson.diffusion_level(sigma=...) restate it bit for bit.
+ * The field is handle state, like the face set: the handle keeps its own device copy (counted by mg_memory_bytes), and it is
+ * read where levels are generated -- mg_gen_diffusion_level[_mf], the three hierarchy calls and
+ * mg_refresh_diffusion_hierarchy.  A generating call whose elements_per_dim (the top level's, for a hierarchy) differs from the
+ * field's is refused by name before any level is touched.  Coarse levels rediscretise with the arithmetic mean of the 2^3
+ * children, whatever `averaging` says for kappa (mass is additive).  Each level remembers whether it was generated with a
+ * reaction diagonal (mg_level_reaction); a matrix-free level keeps the nodal R(sigma), 8 bytes per row, and its march reads it
+ * (40 bytes per row and sweep instead of 32).  mg_refresh_diffusion_hierarchy is refused if the handle has a field and the
+ * levels were generated without one, or the reverse; the values may differ (a new dt, a new sigma iterate).  A handle that
+ * never sets a field launches the kernels and allocates the bytes it did before these entries existed.
+ * A null pointer clears the field.  The device variant takes its pointer under the contract of
+ * mg_gen_diffusion_hierarchy_device (device memory of the handle's device, complete before the call; it is copied on the
+ * handle's stream, which is synchronised before return).  Refused by name, the handle left as it was: 2-D handles, slab
+ * handles (a handle made a slab handle after the field was set is refused at the generating calls), a non-positive
+ * elements_per_dim, a device pointer to the host variant, a pointer that is not device memory of the handle's device to the
+ * device variant, and a sigma that is negative or not finite, the first such cell named.  The face set 0 stays refused as
+ * singular whatever sigma is. */
+int mg_set_diffusion_reaction(mg_handle h, int elements_per_dim, const double* sigma_host);
+int mg_set_diffusion_reaction_device(mg_handle h, int elements_per_dim, const double* sigma_dev);
+/* *on = 1 if the handle holds a reaction field, *elements_per_dim = its cells per dimension (0, 0 otherwise) */
+int mg_diffusion_reaction(mg_handle h, int* on, int* elements_per_dim);
+/* *on = 1 if the level was generated with a reaction diagonal */
+int mg_level_reaction(mg_handle h, int level, int* on);
 /* *on = 1 if the level is matrix-free, *kappa_bytes = the device bytes of its kappa (0 otherwise) */
 int mg_level_matrix_free(mg_handle h, int level, int* on, int64_t* kappa_bytes);
 /* Sensitivity of the diffusion operator to kappa (no reference counterpart): out_dev[c] = d(a^T A(kappa) b) / d kappa_c for the
@@ -333,6 +366,21 @@ enum mg_node_set { MG_NODES_INTERIOR = 0, MG_NODES_ALL = 1 };
 int mg_diffusion_dkappa_ex(mg_handle h, int level, const double* a_dev, int a_nodes, const double* b_dev, int b_nodes, double* out_dev);
 int mg_diffusion_apply_dkappa_ex(mg_handle h, int level, const double* dkappa_dev, const double* x_dev, int rows, int cols,
                                  double* out_dev);
+/* The two sensitivity operators of the reaction term (no reference counterpart).  R is linear in sigma and diagonal:
+ *     mg_diffusion_apply_dsigma: out_i = T_sigma(dsigma, x)_i = R(dsigma)_i x_i on the free nodes of the handle's face set,
+ *                                +0.0 on its Dirichlet nodes; dsigma may have any sign;
+ *     mg_diffusion_dsigma:       out_c = D_sigma(a, b)_c = (h^3 / 24) sum over the 8 corners i of cell c of t_{c,i} a~_i b~_i,
+ *                                a~, b~ = a, b with the Dirichlet nodes taken as 0.
+ * They are adjoint, a . T_sigma(w, x) = w . D_sigma(a, x), and close under differentiation: D_sigma with cotangent w gives
+ * a_bar = T_sigma(w, b) and b_bar = T_sigma(w, a); T_sigma with cotangent y gives w_bar = D_sigma(y, x) and
+ * x_bar = T_sigma(w, y).  With the adjoint solve (A + R) lambda = dJ/du, dJ/dsigma = -D_sigma(lambda, u).  Neither reads sigma
+ * or a matrix: any whole 3-D grid level will do, as with mg_diffusion_dkappa.  Summation order: mg_diffusion_adj.hip.h;
+ * poisson.diffusion_dsigma and poisson.diffusion_apply_dsigma restate them bit for bit (no fma in either).
+ * Pointers, cell and node order, stream and synchronisation are those of mg_diffusion_dkappa / mg_diffusion_apply_dkappa.
+ * Refused with an error before anything is launched: 2-D handles, slab handles, flat levels, null pointers, pointers that
+ * are not device memory of the handle's device, and an out_dev that overlaps an input. */
+int mg_diffusion_dsigma(mg_handle h, int level, const double* a_dev, const double* b_dev, double* out_dev);
+int mg_diffusion_apply_dsigma(mg_handle h, int level, const double* dsigma_dev, const double* x_dev, double* out_dev);
 /* getJacobiMatrices (multigrid.py:48-56) as a stand-alone set-up kernel, for callers that
  * want the reference's split operands back: for every stored entry a_ij of the CSR matrix
  * writes scaled[q] = a_ij / a_ii computed as (1/a_ii) * a_ij, keep[q] = 1 unless the entry
@@ -727,6 +775,9 @@ int mg_reset_smoother_launches(mg_handle h);
  * "apply_dkappa" = mg_diffusion_apply_dkappa with dkappa = the first N^3 entries of MG_VEC_F and x = MG_VEC_V, into MG_VEC_R;
  * "dkappa:all" / "apply_dkappa:all" = the same operands through mg_diffusion_dkappa_ex / mg_diffusion_apply_dkappa_ex with both
  * node sets MG_NODES_ALL;
+ * "dsigma" = mg_diffusion_dsigma of (MG_VEC_V, MG_VEC_F) into the first N^3 entries of MG_VEC_R; "apply_dsigma" =
+ * mg_diffusion_apply_dsigma with dsigma = the first N^3 entries of MG_VEC_F and x = MG_VEC_V, into MG_VEC_R (the
+ * "diffusion_mf" keys time the march with the reaction term on a level that has one);
  * "kappa_ingest" = one launch of the fused copy and coarsening of mg_gen_diffusion_hierarchy_device on a matrix-free level, from a
  * scratch copy of its kappa back into the level's own (the same bytes: the level is unchanged) and into a scratch coarse field,
  * arithmetic averaging; an error on stored levels).

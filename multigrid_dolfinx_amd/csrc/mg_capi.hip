@@ -197,6 +197,8 @@ struct Level {
     DevBuf<double> kappa;
     int faces = MG_FACES_ALL;               // the face set a generated diffusion level was built with (mg_set_diffusion_faces)
     bool diffusion_hierarchy = false;       // generated by one of the diffusion hierarchy entries: mg_refresh_diffusion_hierarchy may renew it
+    bool react = false;                     // generated with a reaction diagonal R(sigma) (mg_set_diffusion_reaction) ...
+    DevBuf<double> rdiag;                   // ... which a matrix-free level keeps as one more row vector (nodal, not sigma itself)
     DVector v, v2, f, err, ftrue;
     DVector sw;                             // once-relaxed boundary planes of a slab (paired sweeps, world > 1)
     DVector fcg_x, fcg_p, fcg_q, fcg_b;     // mg_pcg on this level: iterate, direction, A p, the saved right-hand side
@@ -288,6 +290,8 @@ struct mg_context {
                                     // measured slower than nine colour launches: 9.1 against 6.8 ms per sweep of the 513^3 lattice)
     int diffusion_faces = MG_FACES_ALL;     // mg_set_diffusion_faces: the faces with a Dirichlet condition in the diffusion levels generated
                                     // from now on, and what MG_NODES_INTERIOR masks; the other faces are no-flux faces
+    DevBuf<double> sigma;           // mg_set_diffusion_reaction: the handle's copy of sigma, sigma_N^3 cells (empty: no reaction term), read
+    int sigma_N = 0;                // where diffusion levels are generated
     int dkappa_gather = 0;          // mg_diffusion_dkappa: 1 = one thread per cell reading through the caches instead of the plane march
                                     // (1025^3: 12.5 ms against 5.75 for the march)
     int lattice_tile = 0;           // tile of that march: 0 / 1 = 64 x 16 cells (256 threads), 2 = 128 x 16 (512 threads)
@@ -805,6 +809,53 @@ int face_set_handle(const mg_context* c, const std::string& who) {
 // the free nodes of a face set on a whole 3-D level
 FreeBox level_box(const Level& L, int faces) { return free_box(faces, L.g.nx, L.g.ny, L.g.nz); }
 
+// The reaction field (mg_set_diffusion_reaction) lives on whole 3-D handles only, like a face set: a handle that became a
+// slab handle after the field was set is refused where the field is read, by the generators.  So is a level of another size.
+int reaction_handle(const mg_context* c, const std::string& who, int N) {
+    if (!c->sigma) return 0;
+    if (c->dim != 3) return fail(who + ": the reaction term (mg_set_diffusion_reaction) is 3-D only");
+    if (c->comm.active()) return fail(who + ": the reaction term (mg_set_diffusion_reaction) needs a whole (not slab) handle");
+    if (N != c->sigma_N)
+        return fail(who + ": elements_per_dim = " + std::to_string(N) + ", the reaction field (mg_set_diffusion_reaction) has " +
+                    std::to_string(c->sigma_N) + " cells per dimension: set a field of the level's size, or clear it");
+    return 0;
+}
+
+// nodal R(w) of a cell field on a whole 3-D grid of N cells per dimension (reaction_diag, mg_kernels.hip.h); out: (N + 1)^3
+int launch_reaction_diag(mg_context* c, const double* w, double* out, int N) {
+    const double h = 1.0 / (double)N;
+    const dim3 grid(blocks_for(((int64_t)N + 1) * (N + 1), RD_BLOCK), (unsigned)(N + 1), 1u);
+    hipLaunchKernelGGL(reaction_diag, grid, dim3(RD_BLOCK), 0, c->stream, w, out, N, std::pow(h, 3.0));
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// T_sigma(w, x) = R(w) x on the free nodes of the handle's face set, +0.0 elsewhere / its adjoint D_sigma(a, b) per cell
+// (mg_diffusion_adj.hip.h); whole 3-D grid levels, the caller's lexicographic buffers
+DsArgs ds_args(const mg_context* c, const Level& L, const double* a, const double* b, double* out) {
+    DsArgs d{};
+    d.a = a; d.b = b; d.out = out;
+    d.nx = L.g.nx; d.ny = L.g.ny; d.nz = L.g.nz; d.N = L.N; d.P = L.g.plane;
+    d.box = level_box(L, c->diffusion_faces);
+    return d;
+}
+
+int launch_apply_dsigma(mg_context* c, const Level& L, const double* dsigma, const double* x, double* out) {
+    DsArgs d = ds_args(c, L, dsigma, x, out);
+    d.scale = std::pow(1.0 / (double)L.N, 3.0);
+    hipLaunchKernelGGL(diffusion_apply_dsigma, dim3(blocks_for(L.g.plane, DK_BLOCK), (unsigned)L.g.nz, 1u), dim3(DK_BLOCK), 0, c->stream, d);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int launch_dsigma(mg_context* c, const Level& L, const double* a, const double* b, double* out) {
+    DsArgs d = ds_args(c, L, a, b, out);
+    d.scale = std::pow(1.0 / (double)L.N, 3.0) / 24.0;
+    hipLaunchKernelGGL(diffusion_dsigma, dim3(blocks_for((int64_t)L.N * L.N, DK_BLOCK), (unsigned)L.N, 1u), dim3(DK_BLOCK), 0, c->stream, d);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 MfArgs mf_args(const MfPlan& p, const Level& L, const double* kappa, const double* x_rows, double* out_rows) {
     MfArgs a{};
     a.x = x_rows; a.xp = out_rows; a.out = out_rows; a.kappa = kappa;
@@ -828,7 +879,11 @@ int launch_diffusion_mf(mg_context* c, const Level& L, int mode, bool dot, const
     with_mode(mode, dot, [&](auto m, auto d) {
         constexpr int MODE = decltype(m)::value;
         if constexpr (MODE == MODE_GS) known = false;
-        else if (L.faces != MG_FACES_ALL) hipLaunchKernelGGL((diffusion_mf_faces<MODE, decltype(d)::value>), grid, blk, 0, c->stream, fa);
+        else if (L.react) {                         // A(kappa) + R(sigma): the march with the level's nodal R(sigma)
+            const MfReactArgs ra{a, fa.box, L.rdiag};
+            if (L.faces != MG_FACES_ALL) hipLaunchKernelGGL((diffusion_mf_react<MODE, decltype(d)::value, true>), grid, blk, 0, c->stream, ra);
+            else hipLaunchKernelGGL((diffusion_mf_react<MODE, decltype(d)::value, false>), grid, blk, 0, c->stream, ra);
+        } else if (L.faces != MG_FACES_ALL) hipLaunchKernelGGL((diffusion_mf_faces<MODE, decltype(d)::value>), grid, blk, 0, c->stream, fa);
         else hipLaunchKernelGGL((diffusion_mf<MODE, decltype(d)::value>), grid, blk, 0, c->stream, a);
     });
     if (!known) return fail("matrix-free diffusion levels have no kernel for this mode");
@@ -871,6 +926,7 @@ int launch_diffusion_rhs(mg_context* c, const Level& L, const double* d_kappa, d
     d.kappa = d_kappa;
     d.kc0 = 0;
     d.box = level_box(L, L.faces);
+    d.react = L.react ? L.rdiag.get() : nullptr;
     hipLaunchKernelGGL(gen_diffusion_rhs, grid3(L.g, L.g.nk), dim3(kPlaneBlock), 0, c->stream, d, f_rows, dinv_rows);
     HIP_TRY(hipGetLastError());
     return 0;
@@ -900,9 +956,9 @@ int launch_dkappa(mg_context* c, const Level& L, const double* a, const double* 
 }
 
 // mg_diffusion_dkappa and the device-pointer vector calls: whole 3-D grid levels / whole handles, refused by name otherwise
-int need_dkappa_level(mg_context* c, int level, const char* who) {
+int need_dkappa_level(mg_context* c, int level, const char* who, const char* field = "kappa") {
     if (!c) return fail("null handle");
-    if (c->dim != 3) return fail(std::string(who) + ": the kappa sensitivity is 3-D only (this handle is 2-D)");
+    if (c->dim != 3) return fail(std::string(who) + ": the " + field + " sensitivity is 3-D only (this handle is 2-D)");
     if (c->comm.active()) return fail(std::string(who) + " needs a whole (not slab) handle");
     MG_TRY(check_level(c, level));
     if (c->L[level].flat) return fail(std::string(who) + ": level " + std::to_string(level) + " is flat (no grid): it has no cells");
@@ -4464,13 +4520,19 @@ int check_kappa(mg_context* c, const double* d_kappa, int64_t n, int64_t base, i
     return fail("kappa must be positive and finite: cell " + cell + ") = index " + std::to_string(q) + " holds " + val);
 }
 
-// the stored level from a device kappa holding cell planes [kc0, ...)
-int gen_diffusion_level(mg_context* c, int level, int N, const double* d_kappa, int kc0, int prune_zeros) {
+// the stored level from a device kappa holding cell planes [kc0, ...); d_sigma: the level's N^3 reaction cells or null
+int gen_diffusion_level(mg_context* c, int level, int N, const double* d_kappa, int kc0, int prune_zeros, const double* d_sigma) {
     DiffusionArgs d{};
     d.ga = gen_args(c, N, prune_zeros);
     d.kappa = d_kappa;
     d.kc0 = kc0;
     MG_TRY(face_set_handle(c, "mg_gen_diffusion_level"));
+    DevTemp rdiag;                              // nodal R(sigma): read by the generating kernel and not kept
+    if (d_sigma) {
+        MG_TRY(rdiag.alloc((size_t)(N + 1) * (N + 1) * (N + 1) * 8));
+        MG_TRY(launch_reaction_diag(c, d_sigma, rdiag.as<double>(), N));
+        d.react = rdiag.as<const double>();
+    }
     const int faces = c->diffusion_faces;       // (not the default: a 3-D whole handle, so L.g is the whole grid)
     MG_TRY(gen_stored_level(c, level, N, d.ga.W, [&](const Level& L, dim3 grid, unsigned long long* counts) {
         const dim3 blk(kPlaneBlock);
@@ -4479,6 +4541,7 @@ int gen_diffusion_level(mg_context* c, int level, int N, const double* d_kappa, 
         with_int_else<4, 1, 2>(L.R, [&](auto r) { hipLaunchKernelGGL(gen_diffusion<decltype(r)::value>, grid, blk, 0, c->stream, d, L.vals, L.cols, L.dinv, L.f.rows, counts); });
     }));
     c->L[level].faces = faces;
+    c->L[level].react = d_sigma != nullptr;
     return 0;
 }
 
@@ -4489,6 +4552,7 @@ int mg_gen_diffusion_level(mg_handle c, int level, int N, const double* kappa, i
     if (N <= 0) return fail("elements_per_dim must be positive");
     if (!kappa) return fail("null kappa");
     HIP_TRY(hipSetDevice(c->device));
+    MG_TRY(reaction_handle(c, "mg_gen_diffusion_level", N));
     Level geo;                                   // checked before the level is touched: a refusal leaves it as it was
     MG_TRY(setup_geometry(c, geo, level, N));
     int kc0 = 0, kc1 = 0;
@@ -4498,7 +4562,7 @@ int mg_gen_diffusion_level(mg_handle c, int level, int N, const double* kappa, i
     MG_TRY(d_kappa.alloc((size_t)n * 8));
     HIP_TRY(hipMemcpy(d_kappa.p, kappa + (size_t)kc0 * cp, (size_t)n * 8, hipMemcpyHostToDevice));
     MG_TRY(check_kappa(c, d_kappa.as<const double>(), n, (int64_t)kc0 * cp, N));
-    return gen_diffusion_level(c, level, N, d_kappa.as<const double>(), kc0, prune_zeros);
+    return gen_diffusion_level(c, level, N, d_kappa.as<const double>(), kc0, prune_zeros, c->sigma);
 }
 
 namespace {
@@ -4511,8 +4575,9 @@ int fill_rhs_mf(mg_context* c, Level& L, const double* d_kappa) {
     return 0;
 }
 
-// the matrix-free level from a whole device kappa (N^3 cells, n of them), which the level takes over on success
-int gen_diffusion_level_mf(mg_context* c, int level, int N, DevTemp& kappa, int64_t n) {
+// the matrix-free level from a whole device kappa (N^3 cells, n of them), which the level takes over on success; d_sigma:
+// the level's N^3 reaction cells or null -- the level keeps their nodal R(sigma), not the cells
+int gen_diffusion_level_mf(mg_context* c, int level, int N, DevTemp& kappa, int64_t n, const double* d_sigma) {
     const double* const d_kappa = kappa.as<const double>();
     Level& L = c->L[level];
     LevelBuild build(c, L);
@@ -4523,6 +4588,11 @@ int gen_diffusion_level_mf(mg_context* c, int level, int N, DevTemp& kappa, int6
     MG_TRY(alloc_level_vectors(c, L));
     if (level + 1 < c->nlev) MG_TRY(vec_alloc(c, L, &L.ftrue));     // (the true right-hand side for mg_fmg, as on stored levels)
     L.faces = c->diffusion_faces;
+    if (d_sigma) {
+        MG_TRY(L.rdiag.alloc(c, (size_t)L.n_global));
+        MG_TRY(launch_reaction_diag(c, d_sigma, L.rdiag, N));
+        L.react = true;
+    }
     MG_TRY(fill_rhs_mf(c, L, d_kappa));
     HIP_TRY(hipStreamSynchronize(c->stream));
     // what the stored level would report: one diagonal entry per row and two entries per pair of free axis neighbours (the
@@ -4557,6 +4627,7 @@ int mg_gen_diffusion_level_mf(mg_handle c, int level, int N, const double* kappa
     if (N <= 0) return fail("elements_per_dim must be positive");
     if (!kappa) return fail("null kappa");
     HIP_TRY(hipSetDevice(c->device));
+    MG_TRY(reaction_handle(c, "mg_gen_diffusion_level_mf", N));
     Level geo;                                   // checked before the level is touched: a refusal leaves it as it was
     MG_TRY(setup_geometry(c, geo, level, N));
     const int64_t n = cell_plane(c, N) * N;
@@ -4564,7 +4635,7 @@ int mg_gen_diffusion_level_mf(mg_handle c, int level, int N, const double* kappa
     MG_TRY(d_kappa.alloc((size_t)n * 8));
     HIP_TRY(hipMemcpy(d_kappa.p, kappa, (size_t)n * 8, hipMemcpyHostToDevice));
     MG_TRY(check_kappa(c, d_kappa.as<const double>(), n, 0, N));
-    return gen_diffusion_level_mf(c, level, N, d_kappa, n);
+    return gen_diffusion_level_mf(c, level, N, d_kappa, n, c->sigma);
 }
 
 namespace {
@@ -4595,6 +4666,7 @@ int hierarchy_refusals(mg_context* c, const std::string& who, int top_level, int
     if (N % (1 << top_level))
         return fail(who + " needs an even elements_per_dim on every level above level 0 (" + std::to_string(N) +
                     " is not N0 * 2^" + std::to_string(top_level) + ")");
+    MG_TRY(reaction_handle(c, who, N));
     Level geo;
     return setup_geometry(c, geo, top_level, N);
 }
@@ -4605,25 +4677,38 @@ int hierarchy_refusals(mg_context* c, const std::string& who, int top_level, int
 // the coarsened field of the level above -- and empty where `src` is the caller's buffer, which is only read.  A
 // matrix-free level takes a held field over as it is and gets its own copy of a borrowed one from the pass that coarsens
 // it.  At most two kappa fields are alive at a time besides those the matrix-free levels keep.
+// The handle's reaction field (mg_set_diffusion_reaction) walks beside kappa: borrowed on the top level, below it the
+// arithmetic mean of the 2^3 children whatever `averaging` says (mass is additive), by the same pass; besides the handle's
+// own, at most two sigma fields are alive at a time, and no level keeps one.
 int gen_diffusion_hierarchy(mg_context* c, int top_level, int N, const double* src, DevTemp& held, int averaging,
                             int64_t min_rows) {
     MG_TRY(check_kappa(c, src, cell_plane(c, N) * N, 0, N));
+    const double* ssrc = c->sigma;              // (hierarchy_refusals: of the top level's size)
+    DevTemp sheld;
     for (int l = top_level, Nl = N; l >= 0; --l, Nl /= 2) {
         const int64_t n = cell_plane(c, Nl) * Nl;
         const int64_t rows = c->dim == 3 ? ((int64_t)Nl + 1) * (Nl + 1) * (Nl + 1) : ((int64_t)Nl + 1) * (Nl + 1);
         const bool mf = l > 0 && rows >= min_rows;
-        if (!mf) MG_TRY(gen_diffusion_level(c, l, Nl, src, 0, 1));
-        DevTemp own, coarse;
+        if (!mf) MG_TRY(gen_diffusion_level(c, l, Nl, src, 0, 1, ssrc));
+        DevTemp own, coarse, scoarse;
         if (mf && !held.p) MG_TRY(own.alloc((size_t)n * 8));       // (matrix-free levels are above level 0: the pass below copies)
         if (l > 0) {
             const int Nc = Nl / 2;
             MG_TRY(coarse.alloc((size_t)(cell_plane(c, Nc) * Nc) * 8));
             MG_TRY(launch_kappa_ingest(c, src, own.as<double>(), coarse.as<double>(), Nc, averaging));
+            if (ssrc) {
+                MG_TRY(scoarse.alloc((size_t)(cell_plane(c, Nc) * Nc) * 8));
+                MG_TRY(launch_kappa_ingest(c, ssrc, nullptr, scoarse.as<double>(), Nc, MG_KAPPA_ARITHMETIC));
+            }
             HIP_TRY(hipStreamSynchronize(c->stream));
         }
-        if (mf) MG_TRY(gen_diffusion_level_mf(c, l, Nl, own.p ? own : held, n));
+        if (mf) MG_TRY(gen_diffusion_level_mf(c, l, Nl, own.p ? own : held, n, ssrc));
         held = std::move(coarse);
         src = held.as<const double>();
+        if (ssrc) {
+            sheld = std::move(scoarse);
+            ssrc = sheld.as<const double>();
+        }
         c->L[l].diffusion_hierarchy = true;
     }
     return 0;
@@ -4684,8 +4769,12 @@ int mg_refresh_diffusion_hierarchy(mg_handle c, int top_level, const double* kap
         if (L.faces != c->diffusion_faces)
             return fail(who + ": level " + std::to_string(l) + " was generated with the face set " + std::to_string(L.faces) +
                         ", the handle's is " + std::to_string(c->diffusion_faces) + " now (mg_set_diffusion_faces): generate the hierarchy again");
+        if (L.react != (c->sigma.get() != nullptr))
+            return fail(who + ": level " + std::to_string(l) + " was generated " + (L.react ? "with" : "without") + " a reaction term, the handle has " +
+                        (c->sigma ? "a" : "no") + " reaction field now (mg_set_diffusion_reaction): generate the hierarchy again");
     }
     const int N = c->L[top_level].N;
+    MG_TRY(reaction_handle(c, who, N));
     MG_TRY(check_kappa(c, kappa_dev, cell_plane(c, N) * N, 0, N));      // read-only: a refusal leaves the old hierarchy usable
     // whatever the old matrices fed goes: captured cycles, level 0's factorisation, every level's Chebyshev estimate
     ++c->epoch;
@@ -4696,14 +4785,22 @@ int mg_refresh_diffusion_hierarchy(mg_handle c, int top_level, const double* kap
     // above it coarsens straight into its kappa and nothing is allocated or freed for it
     const double* src = kappa_dev;
     DevTemp held;                               // src where it is a temporary: the coarsened field above a stored level
+    const double* ssrc = c->sigma;              // the reaction field walks beside kappa; a matrix-free level's R(sigma) is rewritten in place
+    DevTemp sheld;
     for (int l = top_level, Nl = N; l >= 0; --l, Nl /= 2) {
         Level& L = c->L[l];
         const bool mf = L.mf;
         if (!mf) {                              // stored: the level is rebuilt by the pipeline that made it
-            MG_TRY(gen_diffusion_level(c, l, Nl, src, 0, 1));
+            MG_TRY(gen_diffusion_level(c, l, Nl, src, 0, 1, ssrc));
             L.diffusion_hierarchy = true;
+        } else if (ssrc) {
+            MG_TRY(launch_reaction_diag(c, ssrc, L.rdiag, Nl));
         }
-        DevTemp coarse;
+        DevTemp coarse, scoarse;
+        if (l > 0 && ssrc) {
+            MG_TRY(scoarse.alloc((size_t)(cell_plane(c, Nl / 2) * (Nl / 2)) * 8));
+            MG_TRY(launch_kappa_ingest(c, ssrc, nullptr, scoarse.as<double>(), Nl / 2, MG_KAPPA_ARITHMETIC));
+        }
         double* coarse_p = nullptr;
         if (l > 0) {
             const int Nc = Nl / 2;
@@ -4722,6 +4819,10 @@ int mg_refresh_diffusion_hierarchy(mg_handle c, int top_level, const double* kap
         HIP_TRY(hipStreamSynchronize(c->stream));
         held = std::move(coarse);
         src = coarse_p;
+        if (ssrc) {
+            sheld = std::move(scoarse);
+            ssrc = sheld.as<const double>();
+        }
     }
     return 0;
 }
@@ -4744,6 +4845,101 @@ int mg_diffusion_faces(mg_handle c, int* dirichlet_faces) {
     if (!c) return fail("null handle");
     if (!dirichlet_faces) return fail("null argument");
     *dirichlet_faces = c->diffusion_faces;
+    return 0;
+}
+
+namespace {
+
+// the first cell of the device sigma that is not a finite double >= 0, as an error (check_kappa's wording)
+int check_sigma(mg_context* c, const std::string& who, const double* d_sigma, int64_t n, int N) {
+    DevTemp d_first;
+    MG_TRY(d_first.alloc(sizeof(unsigned long long)));
+    HIP_TRY(hipMemsetAsync(d_first.p, 0xff, sizeof(unsigned long long), c->stream));
+    const unsigned nb = (unsigned)std::max<int64_t>(1, std::min<int64_t>(8192, (n + 255) / 256));
+    hipLaunchKernelGGL(sigma_check, dim3(nb), dim3(256), 0, c->stream, d_sigma, n, d_first.as<unsigned long long>());
+    HIP_TRY(hipGetLastError());
+    unsigned long long first = 0;
+    HIP_TRY(hipMemcpyAsync(&first, d_first.p, sizeof(first), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (first == ~0ull) return 0;
+    double x = 0.0;
+    HIP_TRY(hipMemcpy(&x, d_sigma + first, sizeof(double), hipMemcpyDeviceToHost));
+    const int64_t q = (int64_t)first;
+    char val[40];
+    snprintf(val, sizeof(val), "%.17g", x);
+    return fail(who + ": sigma must be finite and not negative: cell (" + std::to_string(q % N) + ", " + std::to_string((q / N) % N) + ", " +
+                std::to_string(q / ((int64_t)N * N)) + ") = index " + std::to_string(q) + " holds " + val);
+}
+
+// what both variants of mg_set_diffusion_reaction refuse before they look at the pointer
+int reaction_refusals(mg_context* c, const std::string& who, int N) {
+    if (c->dim != 3) return fail(who + ": the reaction term is 3-D only (this handle is 2-D)");
+    if (c->comm.active()) return fail(who + ": the reaction term needs a whole (not slab) handle");
+    if (N <= 0) return fail(who + ": elements_per_dim must be positive");
+    return 0;
+}
+
+// the checked field becomes the handle's; until here the handle is as it was
+int adopt_sigma(mg_context* c, const std::string& who, DevTemp& field, int N) {
+    const int64_t n = (int64_t)N * N * N;
+    MG_TRY(check_sigma(c, who, field.as<const double>(), n, N));
+    c->sigma.adopt(c, field.release<double>(), (size_t)n);
+    c->sigma_N = N;
+    return 0;
+}
+
+}  // namespace
+
+int mg_set_diffusion_reaction(mg_handle c, int N, const double* sigma_host) {
+    if (!c) return fail("null handle");
+    const std::string who = "mg_set_diffusion_reaction";
+    if (!sigma_host) {
+        c->sigma.reset();
+        c->sigma_N = 0;
+        return 0;
+    }
+    MG_TRY(reaction_refusals(c, who, N));
+    HIP_TRY(hipSetDevice(c->device));
+    hipPointerAttribute_t at{};
+    const hipError_t e = hipPointerGetAttributes(&at, sigma_host);
+    if (e != hipSuccess) (void)hipGetLastError();       // (an unregistered host pointer is an error of the query in some runtimes)
+    if (e == hipSuccess && at.type == hipMemoryTypeDevice)
+        return fail(who + ": sigma is not host memory (a device pointer? mg_set_diffusion_reaction_device takes those)");
+    const size_t bytes = (size_t)N * N * N * 8;
+    DevTemp field;
+    MG_TRY(field.alloc(bytes));
+    HIP_TRY(hipMemcpy(field.p, sigma_host, bytes, hipMemcpyHostToDevice));
+    return adopt_sigma(c, who, field, N);
+}
+
+int mg_set_diffusion_reaction_device(mg_handle c, int N, const double* sigma_dev) {
+    if (!c) return fail("null handle");
+    const std::string who = "mg_set_diffusion_reaction_device";
+    if (!sigma_dev) {
+        c->sigma.reset();
+        c->sigma_N = 0;
+        return 0;
+    }
+    MG_TRY(reaction_refusals(c, who, N));
+    HIP_TRY(hipSetDevice(c->device));
+    MG_TRY(need_device_pointer(c, sigma_dev, who.c_str(), "sigma"));
+    const size_t bytes = (size_t)N * N * N * 8;
+    DevTemp field;
+    MG_TRY(field.alloc(bytes));
+    HIP_TRY(hipMemcpyAsync(field.p, sigma_dev, bytes, hipMemcpyDeviceToDevice, c->stream));
+    return adopt_sigma(c, who, field, N);
+}
+
+int mg_diffusion_reaction(mg_handle c, int* on, int* elements_per_dim) {
+    if (!c) return fail("null handle");
+    if (on) *on = c->sigma ? 1 : 0;
+    if (elements_per_dim) *elements_per_dim = c->sigma_N;
+    return 0;
+}
+
+int mg_level_reaction(mg_handle c, int level, int* on) {
+    MG_TRY(check_level(c, level));
+    if (on) *on = c->L[level].react ? 1 : 0;
     return 0;
 }
 
@@ -4981,6 +5177,46 @@ int mg_diffusion_apply_dkappa_ex(mg_handle c, int level, const double* dkappa_de
     const Level& L = c->L[level];
     MG_TRY(need_apply_dkappa_operands(c, L, who, dkappa_dev, x_dev, out_dev));
     MG_TRY(launch_apply_dkappa(c, L, dkappa_dev, x_dev, out_dev, rows == MG_NODES_ALL, cols == MG_NODES_ALL));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// the pointer checks of the two sigma sensitivities: device memory of the handle's device, out apart from the inputs (other
+// threads read them while a thread writes its entry of out)
+static int need_dsigma_operands(mg_context* c, const char* who, const char* first, const void* p, size_t np, const char* second,
+                                const void* q, size_t nq, const void* out, size_t nout) {
+    MG_TRY(need_device_pointer(c, p, who, first));
+    MG_TRY(need_device_pointer(c, q, who, second));
+    MG_TRY(need_device_pointer(c, out, who, "out"));
+    const auto overlaps = [](const void* x, size_t nx, const void* y, size_t ny) {
+        const uintptr_t a = (uintptr_t)x, b = (uintptr_t)y;
+        return a < b + ny && b < a + nx;
+    };
+    if (overlaps(out, nout, p, np)) return fail(std::string(who) + ": out overlaps " + first);
+    if (overlaps(out, nout, q, nq)) return fail(std::string(who) + ": out overlaps " + second);
+    return 0;
+}
+
+int mg_diffusion_dsigma(mg_handle c, int level, const double* a_dev, const double* b_dev, double* out_dev) {
+    const char* who = "mg_diffusion_dsigma";
+    MG_TRY(need_dkappa_level(c, level, who, "sigma"));
+    HIP_TRY(hipSetDevice(c->device));
+    const Level& L = c->L[level];
+    const size_t nodes = (size_t)L.g.plane * (size_t)L.g.nz * 8, cells = (size_t)L.N * L.N * L.N * 8;
+    MG_TRY(need_dsigma_operands(c, who, "a", a_dev, nodes, "b", b_dev, nodes, out_dev, cells));
+    MG_TRY(launch_dsigma(c, L, a_dev, b_dev, out_dev));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int mg_diffusion_apply_dsigma(mg_handle c, int level, const double* dsigma_dev, const double* x_dev, double* out_dev) {
+    const char* who = "mg_diffusion_apply_dsigma";
+    MG_TRY(need_dkappa_level(c, level, who, "sigma"));
+    HIP_TRY(hipSetDevice(c->device));
+    const Level& L = c->L[level];
+    const size_t nodes = (size_t)L.g.plane * (size_t)L.g.nz * 8, cells = (size_t)L.N * L.N * L.N * 8;
+    MG_TRY(need_dsigma_operands(c, who, "dsigma", dsigma_dev, cells, "x", x_dev, nodes, out_dev, nodes));
+    MG_TRY(launch_apply_dsigma(c, L, dsigma_dev, x_dev, out_dev));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return 0;
 }
@@ -5410,6 +5646,12 @@ int mg_time_kernel(mg_handle c, const char* kernel, int level, int reps, double*
             MG_TRY(vec_alloc(c, L, &L.v)); MG_TRY(vec_alloc(c, L, &L.f)); MG_TRY(vec_alloc(c, L, &L.v2));
             const bool all = k == "apply_dkappa:all";
             return launch_apply_dkappa(c, L, L.f.rows, L.v.rows, L.v2.rows, all, all);
+        }
+        // the sigma sensitivities: D_sigma(v, f) into MG_VEC_R[:N^3] / T_sigma(f[:N^3], v) into MG_VEC_R
+        if (k == "dsigma" || k == "apply_dsigma") {
+            MG_TRY(need_dkappa_level(c, level, "mg_time_kernel", "sigma"));
+            MG_TRY(vec_alloc(c, L, &L.v)); MG_TRY(vec_alloc(c, L, &L.f)); MG_TRY(vec_alloc(c, L, &L.v2));
+            return k == "dsigma" ? launch_dsigma(c, L, L.v.rows, L.f.rows, L.v2.rows) : launch_apply_dsigma(c, L, L.f.rows, L.v.rows, L.v2.rows);
         }
         if (k == "kappa_ingest") {  // the copy and the coarsening in one pass, from a scratch copy of kappa back into the level's own
             if (!L.mf) return fail("level is not a matrix-free diffusion level");

@@ -89,6 +89,59 @@ __global__ __launch_bounds__(DK_BLOCK) void diffusion_dkappa_gather(DkArgs p) {
     p.out[(int64_t)ck * p.N * p.N + t] = dk_cell(A, B, p.scale);
 }
 
+// ---- sensitivities of the lumped reaction term R(sigma) (mg_kernels.hip.h, reaction_diag) --------------------------------
+// R is diagonal and linear in sigma.  T_sigma(w, x)_i = R(w)_i x_i on free nodes and +0.0 on Dirichlet nodes
+// (diffusion_apply_dsigma), and its adjoint D_sigma(a, b)_c = scale * sum_i t_{c,i} a~_i b~_i over the eight corners of cell c
+// (diffusion_dsigma), a~ and b~ taking Dirichlet nodes as 0:  a . T_sigma(w, x) = w . D_sigma(a, x).  Neither reads sigma or a
+// matrix.  The bits are DEFINED here and restated by poisson.diffusion_dsigma / diffusion_apply_dsigma:
+//   * D: one accumulator starts with 6.0 * (A * B) of corner (0,0,0) and takes t * (A * B) of the other corners in ascending
+//     (dz, dy, dx), t = 6.0 at (1,1,1) and 2.0 elsewhere; out = acc * scale with scale = h^3 / 24.0 from the host.  The mask
+//     acts where a node is loaded, as in diffusion_dkappa_gather.
+//   * T: react_node's sum (mg_kernels.hip.h), then one product with x.  No fma: -ffp-contract=off.
+// Streaming kernels: D reads 8 + 8 B per node through the caches and writes 8 B per cell, T reads 8 B per cell and per node
+// and writes 8 B per node.
+struct DsArgs {
+    const double* a;        // D: a, T: the direction dsigma ([N][N][N] cells)
+    const double* b;        // D: b (may be a), T: x
+    double* out;            // D: cells, T: nodes
+    int nx, ny, nz, N;
+    int64_t P;
+    double scale;           // D: h^3 / 24.0, T: h^3
+    FreeBox box;
+};
+
+__global__ __launch_bounds__(DK_BLOCK) void diffusion_dsigma(DsArgs p) {
+    const int64_t t = (int64_t)blockIdx.x * DK_BLOCK + threadIdx.x;
+    if (t >= (int64_t)p.N * p.N) return;
+    const int ci = (int)(t % p.N), cj = (int)(t / p.N), ck = blockIdx.y;
+    const bool same = p.a == p.b;
+    double s = 0.0;
+#pragma unroll
+    for (int dz = 0; dz < 2; ++dz)
+#pragma unroll
+        for (int dy = 0; dy < 2; ++dy)
+#pragma unroll
+            for (int dx = 0; dx < 2; ++dx) {
+                const int i = ci + dx, j = cj + dy, k = ck + dz;
+                const bool inner = free_node(p.box, i, j, k);
+                const int64_t r = (int64_t)k * p.P + (int64_t)j * p.nx + i;
+                const double A = inner ? p.a[r] : 0.0;
+                const double B = inner ? (same ? A : p.b[r]) : 0.0;
+                const double term = (dx == dy && dy == dz ? 6.0 : 2.0) * (A * B);
+                s = dz + dy + dx == 0 ? term : s + term;
+            }
+    p.out[(int64_t)ck * p.N * p.N + t] = s * p.scale;
+}
+
+// blockIdx.x: DK_BLOCK nodes of a node plane, blockIdx.y: the plane
+__global__ __launch_bounds__(DK_BLOCK) void diffusion_apply_dsigma(DsArgs p) {
+    const int64_t t = (int64_t)blockIdx.x * DK_BLOCK + threadIdx.x;
+    if (t >= p.P) return;
+    const int i = (int)(t % p.nx), j = (int)(t / p.nx), k = blockIdx.y;
+    const int64_t r = (int64_t)k * p.P + t;
+    p.out[r] = free_node(p.box, i, j, k) ? react_node(p.a, p.N, i, j, k, p.scale) * p.b[r] : 0.0;
+}
+
 // The plane march, in the shape of diffusion_mf (mg_diffusion_mf.hip.h): a tile of MF_TX x MF_TY cells goes up through the cell
 // planes of a z segment.  The masked images of a and b (tile + one line of nodes in x and y) of node planes k and k + 1 are
 // in LDS, two slots per vector: step k reads plane k + 1 (the corners of plane k stay in registers from the step before),

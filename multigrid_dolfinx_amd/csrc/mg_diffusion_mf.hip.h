@@ -49,6 +49,16 @@
 // row has the same sums.  Dirichlet rows are identity rows (TANGENT: +0.0).  ROWS_ALL / COLS_ALL: "boundary" reads
 // "Dirichlet".  The bounds come from the host, six integers compared per axis: no bit of the set is tested in the loop.
 // The instantiations without FACES are the kernels above, untouched: handles with the default set launch those.
+//
+// REACT (diffusion_mf_react; levels generated with a reaction term, mg_set_diffusion_reaction) is the operator A(kappa) +
+// R(sigma) with R diagonal: every non-TANGENT mode, with and without the box of a face set.  The level keeps the nodal
+// R(sigma) of reaction_diag (mg_kernels.hip.h) as one more row vector and not sigma itself.  The march loads r of a row where
+// it loads f, one step ahead, with a plain load (every sweep reads it again), and a free row takes diag + r -- the stored
+// level's diagonal, gen_diffusion's one more addition -- at the diagonal's place in the fma chain and as the d of the Jacobi
+// and Chebyshev epilogues.  Identity rows do not read it.  No LDS image and no barrier is added.
+// Per row and sweep: 8 (x) + 8 (f) + 8 (kappa) + 8 (r) + 8 (out) = 40 B instead of 32, 32 B instead of 24 for the SpMV, 48 B
+// instead of 40 for a Chebyshev step.
+// <..., REACT = false> are the kernels above, untouched: a level without a reaction term launches those.
 #pragma once
 #include "mg_kernels.hip.h"
 
@@ -86,8 +96,15 @@ struct MfFaceArgs {
     FreeBox box;            // the free nodes of the level's face set
 };
 
-template <int MODE, bool DOT, bool TANGENT, bool ROWS_ALL, bool COLS_ALL, bool FACES>
-__device__ __forceinline__ void mf_march(const MfArgs& a, const FreeBox& box) {
+struct MfReactArgs {
+    MfArgs a;
+    FreeBox box;            // the free nodes of the level's face set (the default set: the interior nodes)
+    const double* r;        // nodal R(sigma), row-based
+};
+
+template <int MODE, bool DOT, bool TANGENT, bool ROWS_ALL, bool COLS_ALL, bool FACES, bool REACT = false>
+__device__ __forceinline__ void mf_march(const MfArgs& a, const FreeBox& box, const double* react = nullptr) {
+    static_assert(!REACT || !TANGENT, "the reaction term does not depend on kappa");
     static_assert(!TANGENT || (MODE == MODE_SPMV && !DOT), "the tangent is a plain SpMV with kappa := dkappa");
     static_assert(TANGENT || (!ROWS_ALL && !COLS_ALL), "only the tangent has rows and columns on the boundary");
     constexpr double KPAD = ROWS_ALL || FACES ? 0.0 : 1.0;      // a cell outside the grid
@@ -160,9 +177,11 @@ __device__ __forceinline__ void mf_march(const MfArgs& a, const FreeBox& box) {
             fv = WANT_F && ok ? __builtin_nontemporal_load(a.f + r) : 0.0;
             pv = want_xp && ok ? a.xp[r] : 0.0;
         };
+        auto load_r = [&](int plane) { return on_grid && plane < a.nz ? react[(int64_t)plane * a.P + row_ij] : 0.0; };
 
         // ---- warm-up: what step z0 finds in place ----
         double xr[2], kr[2], f1, p1, f2 = 0.0, p2 = 0.0;
+        double r1 = 0.0, r2 = 0.0;      // REACT: R(sigma) of this row in planes k and k + 1
         load_x(z0 - 1, xr); park_x(z0 - 1, xr);
         load_x(z0, xr); park_x(z0, xr);
         load_x(z0 + 1, xr); park_x(z0 + 1, xr);
@@ -171,6 +190,7 @@ __device__ __forceinline__ void mf_march(const MfArgs& a, const FreeBox& box) {
         load_x(z0 + 2, xr);
         load_k(z0 + 1, kr);
         load_f(z0, f1, p1);
+        if constexpr (REACT) r1 = load_r(z0);
         __syncthreads();
 
         const int cx = (ly + 1) * MF_XW + lx + 1;       // this node in an x image
@@ -184,6 +204,8 @@ __device__ __forceinline__ void mf_march(const MfArgs& a, const FreeBox& box) {
             load_x(k + 3, xr);
             load_k(k + 2, kr);
             if (k + 1 < z1) load_f(k + 1, f2, p2);     // (plane z1 is another workgroup's: it may be writing xp = out there)
+            if constexpr (REACT)
+                if (k + 1 < z1) r2 = load_r(k + 1);
 
             const double* const xa = sX[(k + 3) & 3];   // plane k-1
             const double* const xb = sX[k & 3];
@@ -217,6 +239,7 @@ __device__ __forceinline__ void mf_march(const MfArgs& a, const FreeBox& box) {
                 double t = se[2][0];
                 t = t + se[1][0]; t = t + se[0][0]; t = t + se[0][1]; t = t + se[1][1]; t = t + se[2][1];
                 diag = mf_div6(t) * hh;
+                if constexpr (REACT) diag = diag + r1;
                 double azl, ayl, axl, axu, ayu, azu, ad = diag;
                 if constexpr (FACES) {
                     // as below with the box: a neighbour is a Dirichlet node if it has stepped out of the free range of its
@@ -279,6 +302,7 @@ __device__ __forceinline__ void mf_march(const MfArgs& a, const FreeBox& box) {
                 a.out[(int64_t)k * a.P + row_ij] = o;
             }
             f1 = f2; p1 = p2;
+            if constexpr (REACT) r1 = r2;
             __syncthreads();
         }
     }
@@ -303,6 +327,12 @@ __global__ __launch_bounds__(MF_NT) void diffusion_mf(MfArgs a) {
 template <int MODE, bool DOT, bool TANGENT = false, bool ROWS_ALL = false, bool COLS_ALL = false>
 __global__ __launch_bounds__(MF_NT) void diffusion_mf_faces(MfFaceArgs fa) {
     mf_march<MODE, DOT, TANGENT, ROWS_ALL, COLS_ALL, true>(fa.a, fa.box);
+}
+
+// the march with a reaction term, on the box of the level's face set (FACES) or on the interior nodes
+template <int MODE, bool DOT, bool FACES>
+__global__ __launch_bounds__(MF_NT) void diffusion_mf_react(MfReactArgs ra) {
+    mf_march<MODE, DOT, false, false, false, FACES, true>(ra.a, ra.box, ra.r);
 }
 
 // Right-hand side (and, for the set-up paths that need it, 1 / diagonal) of the level gen_diffusion would store, without
@@ -336,6 +366,7 @@ __global__ void gen_diffusion_rhs(DiffusionArgs d, double* f, double* dinv) {
         double t = se[2][0];
         t = t + se[1][0]; t = t + se[0][0]; t = t + se[0][1]; t = t + se[1][1]; t = t + se[2][1];
         diag = (t / 6.0) * a.h;
+        if (d.react) diag = diag + d.react[lr];
     }
     double b = bnd ? gen_g(a, i, j, k) : diff_load(d, i, j, k);
     if (!bnd) {

@@ -1347,6 +1347,7 @@ struct DiffusionArgs {
     const double* kappa;    // cell planes [kc0, ...) along the slab axis (z in 3-D, y = k in 2-D), x fastest
     int kc0;
     FreeBox box;            // the free nodes of the face set (3-D; the default and 2-D: the interior)
+    const double* react;    // nodal R(sigma), row-based (reaction_diag), added to the diagonal of free rows; null: no reaction term
 };
 
 __device__ __forceinline__ double diff_kappa(const DiffusionArgs& a, int ci, int cj, int ck) {
@@ -1410,6 +1411,7 @@ __global__ void gen_diffusion(DiffusionArgs d, double* vals, int* cols, double* 
                 double t = se[2][0];
                 t = t + se[1][0]; t = t + se[0][0]; t = t + se[0][1]; t = t + se[1][1]; t = t + se[2][1];
                 diag = (t / 6.0) * a.h;
+                if (d.react) diag = diag + d.react[lr];     // the lumped reaction term (3-D whole levels): one more addition
             } else {
                 double K[2][2];         // K[dy][dx]: cell (i - 1 + dx, k - 1 + dy)
                 for (int dy = 0; dy < 2; ++dy)
@@ -1457,6 +1459,51 @@ __global__ void gen_diffusion(DiffusionArgs d, double* vals, int* cols, double* 
     if ((threadIdx.x & 63) == 0) {
         atomicAdd(&counts[0], (unsigned long long)ksum);
         atomicAdd(&counts[1], (unsigned long long)zsum);
+    }
+}
+
+// ---- lumped reaction term R(sigma), one sigma per cell (mg_set_diffusion_reaction) ----------------------------------
+// The row-sum lumped P1 mass of the Kuhn mesh weighted by a cell field w, per node of a whole 3-D level, with diff_load's
+// weights: R(w)_i = ((sum_c t_c w_c) / 24.0) * h3 over the 8 cells around node i in ascending index (dz, dy, dx), t = 6.0
+// where the node is the cell's (0,0,0) or (1,1,1) corner, else 2.0; a cell outside the grid counts as +0.0; h3 = h^3 comes
+// from the host.  One accumulator starts with the first product and takes the other seven one by one
+// (poisson.reaction_diag restates it, same bits; -ffp-contract=off: no product is fused into an add).  w == 1 gives
+// diff_load's T / 24.0.  Every node gets its value, Dirichlet nodes included: the readers (gen_diffusion, gen_diffusion_rhs,
+// the matrix-free march, diffusion_apply_dsigma) use it on free rows only.
+__device__ __forceinline__ double react_node(const double* __restrict__ w, int N, int i, int j, int k, double h3) {
+    double s = 0.0;
+#pragma unroll
+    for (int dz = 0; dz < 2; ++dz)
+#pragma unroll
+        for (int dy = 0; dy < 2; ++dy)
+#pragma unroll
+            for (int dx = 0; dx < 2; ++dx) {
+                const int ci = i - 1 + dx, cj = j - 1 + dy, ck = k - 1 + dz;
+                const bool in = ci >= 0 && ci < N && cj >= 0 && cj < N && ck >= 0 && ck < N;
+                const double v = in ? w[((int64_t)ck * N + cj) * N + ci] : 0.0;
+                const double t = (dx == dy && dy == dz ? 6.0 : 2.0) * v;
+                s = dz + dy + dx == 0 ? t : s + t;
+            }
+    return (s / 24.0) * h3;
+}
+
+constexpr int RD_BLOCK = 256;
+
+// blockIdx.x: RD_BLOCK nodes of a node plane (x fastest), blockIdx.y: the plane; out: lexicographic nodes (the rows of a
+// whole level).  Model: 8 B per cell read through the caches (eight loads per node), 8 B per node written.
+__global__ __launch_bounds__(RD_BLOCK) void reaction_diag(const double* __restrict__ w, double* __restrict__ out, int N, double h3) {
+    const int n1 = N + 1;
+    const int64_t t = (int64_t)blockIdx.x * RD_BLOCK + threadIdx.x;
+    if (t >= (int64_t)n1 * n1) return;
+    const int i = (int)(t % n1), j = (int)(t / n1), k = blockIdx.y;
+    out[(int64_t)k * n1 * n1 + t] = react_node(w, N, i, j, k, h3);
+}
+
+// Set-up check of a sigma field: as kappa_check, for entries that are not finite doubles >= 0 (zero is allowed).
+__global__ void sigma_check(const double* __restrict__ sigma, int64_t n, unsigned long long* first) {
+    for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < n; q += (int64_t)gridDim.x * blockDim.x) {
+        const double x = sigma[q];
+        if (!(x >= 0.0 && x <= 1.7976931348623157e308)) atomicMin(first, (unsigned long long)q);
     }
 }
 

@@ -414,6 +414,38 @@ class DeviceHierarchy:
         check(self._lib.mg_diffusion_faces(self._h, C.byref(faces)))
         return int(faces.value)
 
+    def set_diffusion_reaction(self, sigma, N: Optional[int] = None):
+        """The reaction field of the diffusion levels generated from now on (`mg_set_diffusion_reaction`): the operator
+        A(kappa) + R(sigma) with the lumped diagonal of `poisson.reaction_diag`.  `sigma`: one finite value >= 0 per cell of
+        the level it is meant for (the top level of a hierarchy call), as a NumPy array -- its size gives the cells per
+        dimension unless `N` does -- or as an integer device address with `N=` (`mg_set_diffusion_reaction_device`).  The
+        handle keeps its own copy.  None clears the field.  3-D, whole handles."""
+        if sigma is None:
+            check(self._lib.mg_set_diffusion_reaction(self._h, 0, None))
+            return
+        if isinstance(sigma, (int, np.integer)):
+            if N is None:
+                raise TypeError("a device address needs N=, the cells per dimension of the field")
+            check(self._lib.mg_set_diffusion_reaction_device(self._h, int(N), C.c_void_p(int(sigma))))
+            return
+        s = np.ascontiguousarray(np.asarray(sigma, dtype=np.float64).reshape(-1))
+        n = int(round(s.size ** (1.0 / 3.0))) if N is None else int(N)
+        if n ** 3 != s.size:
+            raise ValueError(f"sigma has {s.size} entries, which is not {n}^3 cells")
+        check(self._lib.mg_set_diffusion_reaction(self._h, n, ptr(s)))
+
+    def diffusion_reaction(self):
+        """(on, cells per dimension) of the handle's reaction field (`mg_diffusion_reaction`); (0, 0) without one."""
+        on, n = C.c_int(0), C.c_int(0)
+        check(self._lib.mg_diffusion_reaction(self._h, C.byref(on), C.byref(n)))
+        return int(on.value), int(n.value)
+
+    def level_reaction(self, level: int) -> bool:
+        """True if the level was generated with a reaction diagonal (`mg_level_reaction`)."""
+        on = C.c_int(0)
+        check(self._lib.mg_level_reaction(self._h, self._idx(level), C.byref(on)))
+        return bool(on.value)
+
     def level_matrix_free(self, level: int) -> bool:
         """True if the level keeps kappa instead of a matrix (`mg_level_matrix_free`)."""
         on = C.c_int(0)
@@ -706,6 +738,50 @@ class DeviceHierarchy:
             return got
         out.reshape(-1)[:] = got
         return out
+
+    def _sigma_entry(self, entry, names, first, n_first, second, n_second, out, n_out):
+        """One of the two sigma sensitivity entries on device addresses or, for tests, on NumPy arrays (uploaded; the
+        result comes back as a NumPy array, into `out` if given)."""
+        integers = [isinstance(v, (int, np.integer)) for v in (first, second)]
+        if all(integers):
+            if not isinstance(out, (int, np.integer)):
+                raise TypeError(f"with device addresses for {names}, out must be a device address too")
+            check(entry(C.c_void_p(int(first)), C.c_void_p(int(second)), C.c_void_p(int(out))))
+            return None
+        if any(integers) or isinstance(out, (int, np.integer)):
+            raise TypeError(f"{names} and out must be all device addresses or all NumPy arrays")
+        held = []
+        try:
+            held.append(_DeviceArray(self._lib, self.device, n_first, _capi.as_f64(first, n_first)))
+            held.append(held[0] if second is first else _DeviceArray(self._lib, self.device, n_second, _capi.as_f64(second, n_second)))
+            held.append(_DeviceArray(self._lib, self.device, n_out))
+            check(entry(held[0].ptr, held[1].ptr, held[2].ptr))
+            got = held[2].download()
+        finally:
+            for d in held:
+                d.free()
+        if out is None:
+            return got
+        out.reshape(-1)[:] = got
+        return out
+
+    def diffusion_dsigma(self, level: int, a, b, out=None):
+        """D_sigma(a, b): d(a^T R(sigma) b) / d sigma for every cell of a 3-D grid level (`mg_diffusion_dsigma`; host
+        restatement: `poisson.diffusion_dsigma`, same bits).  `a`, `b` (lexicographic nodal values, entries on the Dirichlet
+        nodes of the handle's face set count as 0) and `out` (`elements(level) ** 3` cells): device addresses or NumPy
+        arrays, as in `diffusion_dkappa`."""
+        entry = lambda pa, pb, po: self._lib.mg_diffusion_dsigma(self._h, self._idx(level), pa, pb, po)
+        n = self.n_dofs(level)
+        return self._sigma_entry(entry, "a and b", a, n, b, n, out, self.elements(level) ** 3)
+
+    def diffusion_apply_dsigma(self, level: int, dsigma, x, out=None):
+        """T_sigma(dsigma, x) = R(dsigma) x on the free nodes of the handle's face set, 0 on its Dirichlet nodes
+        (`mg_diffusion_apply_dsigma`; host restatement: `poisson.diffusion_apply_dsigma`, same bits).  `dsigma`
+        (`elements(level) ** 3` cells, any sign), `x` and `out` (lexicographic nodal values): device addresses or NumPy
+        arrays, as in `diffusion_apply_dkappa`."""
+        entry = lambda ps, px, po: self._lib.mg_diffusion_apply_dsigma(self._h, self._idx(level), ps, px, po)
+        n = self.n_dofs(level)
+        return self._sigma_entry(entry, "dsigma and x", dsigma, self.elements(level) ** 3, x, n, out, n)
 
     def zero_vector(self, level: int, which: str = "v"):
         check(self._lib.mg_zero_vector(self._h, self._idx(level), _VEC[which]))

@@ -614,7 +614,34 @@ def dirichlet_mask(N: int, dirichlet_faces=ALL_FACES) -> np.ndarray:
     return ~free.reshape(-1)
 
 
-def diffusion_level(N: int, dim: int, kappa, keep_zeros: bool = True, dirichlet_faces=ALL_FACES) -> Level:
+def _cells_around_nodes(w, N: int):
+    """W[dz][dy][dx]: per node (i, j, k) of the (N + 1)^3 grid the value of cell (i - 1 + dx, j - 1 + dy, k - 1 + dz), +0.0
+    outside the grid."""
+    n1 = N + 1
+    wp = np.pad(_kappa_cells(w, N, 3), 1, constant_values=0.0)
+    return [[[wp[dz:dz + n1, dy:dy + n1, dx:dx + n1].reshape(-1) for dx in (0, 1)] for dy in (0, 1)] for dz in (0, 1)]
+
+
+def reaction_diag(N: int, w, dirichlet_faces=ALL_FACES) -> np.ndarray:
+    """R(w): the diagonal of the lumped reaction term of a cell field `w` (N^3 values of any sign, cell order of
+    `diffusion_level`) on the (N + 1)^3 nodes, as the device computes it (`reaction_diag`, mg_kernels.hip.h; same bits).  The
+    row-sum lumped P1 mass of the Kuhn mesh with the weights of the load: over the 8 cells around a node in ascending index
+    (dz, dy, dx), t * w_c with t = 6 where the node is the cell's (0,0,0) or (1,1,1) corner and 2 otherwise, a cell outside
+    the grid counting as +0.0, added one by one; then (sum / 24.0) * h^3.  w == 1 gives h^3 (T / 24), the load of f == 1.
+    Dirichlet nodes of `dirichlet_faces` (`face_set`) get +0.0: R acts on free rows only."""
+    W = _cells_around_nodes(w, N)
+    h = 1.0 / N
+    s = None
+    for dz in (0, 1):
+        for dy in (0, 1):
+            for dx in (0, 1):
+                t = (6.0 if dx == dy == dz else 2.0) * W[dz][dy][dx]
+                s = t if s is None else s + t
+    r = (s / 24.0) * h ** 3
+    return np.where(dirichlet_mask(N, dirichlet_faces), 0.0, r)
+
+
+def diffusion_level(N: int, dim: int, kappa, keep_zeros: bool = True, dirichlet_faces=ALL_FACES, sigma=None) -> Level:
     """The level `mg_gen_diffusion_level` generates, assembled on the host in the kernel's operation order (same bits), in
     the hand-off conventions of `lexicographic_level`.  `kappa` holds one positive value per cell: cube (ci, cj, ck) at
     `(ck * N + cj) * N + ci`, square (ci, cy) at `cy * N + ci`.  On the Kuhn mesh the P1 stiffness of -div(kappa grad u)
@@ -628,10 +655,21 @@ def diffusion_level(N: int, dim: int, kappa, keep_zeros: bool = True, dirichlet_
     A free node on another face gets the natural row: the same sums with a cell outside the grid counting as +0.0, no
     column outside the grid, and the load fh * (T / 24.0) with T the number of Kuhn simplices at the node inside the grid
     (6 for an in-grid cell of which the node is the (0,0,0) or (1,1,1) corner, 2 for every other; 24 inside).  63, the
-    default, is the level above byte for byte."""
+    default, is the level above byte for byte.
+
+    `sigma` (3-D; `mg_set_diffusion_reaction`): one finite value >= 0 per cell, the operator A(kappa) + R(sigma).  A free row's
+    diagonal is the stiffness diagonal above plus `reaction_diag(N, sigma)` of its node, one more addition; identity rows, the
+    off-diagonals, the lifted right-hand side and the load do not change.  None, the default, is the level above byte for
+    byte."""
     faces = face_set(dirichlet_faces)
     if faces != ALL_FACES and dim != 3:
         raise ValueError("a face set other than all six faces is 3-D only")
+    if sigma is not None:
+        if dim != 3:
+            raise ValueError("the reaction term is 3-D only")
+        sig = _kappa_cells(sigma, N, 3)
+        if not np.all(np.isfinite(sig)) or np.any(sig < 0.0):
+            raise ValueError("sigma must be finite and not negative")
     kap = _kappa_cells(kappa, N, dim)
     if np.any(~(kap > 0.0)) or not np.all(np.isfinite(kap)):
         raise ValueError("kappa must be positive and finite")
@@ -642,6 +680,8 @@ def diffusion_level(N: int, dim: int, kappa, keep_zeros: bool = True, dirichlet_
     if dim == 3:
         se, t = _edge_sums_3d(kp, n1)
         diag = (t / 6.0) * h
+        if sigma is not None:
+            diag = diag + reaction_diag(N, sig, faces)
         weight = lambda s: (s / 6.0) * h
     else:
         K = [[kp[dy:dy + n1, dx:dx + n1].reshape(-1) for dx in (0, 1)] for dy in (0, 1)]
@@ -743,6 +783,62 @@ def coarsen_kappa(kappa, dim: int, averaging: str = "arithmetic") -> np.ndarray:
     m = float(2 ** dim)
     out = m / s if averaging == "harmonic" else s * (1.0 / m)
     return np.ascontiguousarray(out.reshape(-1))
+
+
+def coarsen_sigma(sigma, averaging: str = "arithmetic") -> np.ndarray:
+    """sigma of the coarse cells (N / 2 per dimension) as the diffusion hierarchy calls compute it: the arithmetic mean of the
+    2^3 children in `coarsen_kappa`'s order, whatever `averaging` says for kappa -- mass is additive.  `averaging` is taken so
+    that the two fields can be coarsened by one call pattern, and only checked."""
+    if averaging not in ("arithmetic", "harmonic"):
+        raise ValueError("averaging must be 'arithmetic' or 'harmonic'")
+    return coarsen_kappa(sigma, 3, "arithmetic")
+
+
+def diffusion_dsigma(N: int, a, b, dirichlet_faces=ALL_FACES) -> np.ndarray:
+    """D_sigma(a, b): d(a^T R(sigma) b) / d sigma_c for the N^3 cells, as `mg_diffusion_dsigma` computes it (same bits).  With
+    A~, B~ the values of `a`, `b` at a cell's corners (dz, dy, dx), the Dirichlet nodes of `dirichlet_faces` taken as 0:
+    t * (A~ * B~) with t = 6 at (0,0,0) and (1,1,1) and 2 elsewhere, added one by one in ascending (dz, dy, dx), times
+    h^3 / 24.0.  R is linear in sigma: no sigma is read.  The adjoint of `diffusion_apply_dsigma`:
+    a . T_sigma(w, x) = w . D_sigma(a, x)."""
+    n1 = N + 1
+    free = ~dirichlet_mask(N, dirichlet_faces)
+
+    def corners(x):
+        v = np.array(x, dtype=np.float64).reshape(-1)
+        if v.size != n1 ** 3:
+            raise ValueError(f"vector has {v.size} entries, the level has {n1 ** 3} nodes")
+        m = np.where(free, v, 0.0).reshape(n1, n1, n1)
+        return [[[m[dz:dz + N, dy:dy + N, dx:dx + N] for dx in (0, 1)] for dy in (0, 1)] for dz in (0, 1)]
+
+    A, B = corners(a), corners(b)
+    s = None
+    for dz in (0, 1):
+        for dy in (0, 1):
+            for dx in (0, 1):
+                t = (6.0 if dx == dy == dz else 2.0) * (A[dz][dy][dx] * B[dz][dy][dx])
+                s = t if s is None else s + t
+    h = 1.0 / N
+    return np.ascontiguousarray((s * (h ** 3 / 24.0)).reshape(-1))
+
+
+def diffusion_apply_dsigma(N: int, dsigma, x, dirichlet_faces=ALL_FACES) -> np.ndarray:
+    """T_sigma(dsigma, x) = R(dsigma) x on the free nodes of `dirichlet_faces`, +0.0 on its Dirichlet nodes, as
+    `mg_diffusion_apply_dsigma` computes it (same bits: `reaction_diag`'s sum, then one product).  The derivative of
+    (A(kappa) + R(sigma)) x in the direction `dsigma`, of any sign; with dsigma = 1 / dt it is the M u / dt of an implicit
+    Euler step."""
+    n1 = N + 1
+    v = np.array(x, dtype=np.float64).reshape(-1)
+    if v.size != n1 ** 3:
+        raise ValueError(f"vector has {v.size} entries, the level has {n1 ** 3} nodes")
+    W = _cells_around_nodes(dsigma, N)
+    s = None
+    for dz in (0, 1):
+        for dy in (0, 1):
+            for dx in (0, 1):
+                t = (6.0 if dx == dy == dz else 2.0) * W[dz][dy][dx]
+                s = t if s is None else s + t
+    r = (s / 24.0) * (1.0 / N) ** 3
+    return np.where(dirichlet_mask(N, dirichlet_faces), 0.0, r * v)
 
 
 _NODE_SETS = ("interior", "all")

@@ -83,7 +83,21 @@ class DiffusionSolver:
     Everything above then reads with "boundary" = the Dirichlet nodes and "interior" = the free nodes: `g` is read on the
     Dirichlet nodes only and gets a zero gradient elsewhere, and `f` on a free boundary node is a genuine load entry -- where
     prescribed flux data, the integral of q phi_i over the face, goes.  The derivative algebra and the solve counts are
-    the same."""
+    the same.
+
+    `sigma` (`solve`, `tangent`): N^3 float64 >= 0 in kappa's cell order, on the solver's device or the CPU, a
+    differentiable input like kappa.  The operator is then A(kappa) + R(sigma) with the lumped reaction diagonal of
+    `poisson.reaction_diag` (`DeviceHierarchy.set_diffusion_reaction`): absorption, a screened Poisson problem, or with
+    sigma = 1 / dt one implicit Euler step of du/dt - div(kappa grad u) = f, whose right-hand side is
+    b + `reaction_apply`(sigma, u_old).  grad_sigma = -D_sigma(lambda, u) comes from the adjoint solve that gives grad_kappa;
+    the lift of `g` does not involve sigma (R is diagonal).  D_sigma and T_sigma close under differentiation as D and T do,
+    so `create_graph=True` gives the kappa-kappa, kappa-sigma and sigma-sigma blocks of a Hessian-vector product, in the same
+    number of solves.  The operator of a solve keeps sigma with kappa; going from solves with sigma to solves without, or
+    the reverse, generates the hierarchy again instead of refreshing it (`last_generate`).
+
+    `solve(..., same_operator=True)` solves on the operator of the last `solve` without touching the hierarchy, as `tangent`
+    does: the caller asserts that kappa and sigma hold the values of that solve (the steps of a time march with a constant
+    dt).  Gradients with respect to them still flow.  `n_generations` counts the generations and refreshes."""
 
     def __init__(self, N: int, n_levels: int, averaging: str = "arithmetic", matrix_free_min_rows: Optional[int] = None,
                  rtol: float = 1e-10, max_iter: int = 200, device: int = 0, warm_start: bool = False, dirichlet_faces=None,
@@ -106,10 +120,12 @@ class DiffusionSolver:
             self.hierarchy.set_diffusion_faces(self.dirichlet_faces)
         self._generation = 0
         self._generated = False         # a hierarchy call has generated the levels: a device kappa can refresh them
+        self._generated_react = False   # ... with a reaction field: a refresh needs the same state
         self.last_generate = None       # "host" / "device" / "refresh": how the last kappa reached the hierarchy
         self.warm_start = bool(warm_start)
         self._warm = {}                 # "forward" / "adjoint": the last solution of that kind (warm_start)
         self._last_operator = None      # the _Operator of the last `solve`: what `tangent` solves again on
+        self._grid_only = False         # `reaction_apply` before the first solve has made the top level a grid-only level
         self._boundary = None           # the mask of the Dirichlet nodes on the device (solves with g)
         self.n_solves = 0               # mg_pcg calls so far: what a product costs (a Hessian-vector product: four)
         self.last_iterations = {}       # "forward" / "adjoint" / "tangent": iterations of the last solve of that kind
@@ -124,29 +140,57 @@ class DiffusionSolver:
     def __exit__(self, *exc):
         self.close()
 
-    def solve(self, kappa: torch.Tensor, f: torch.Tensor, g: Optional[torch.Tensor] = None) -> torch.Tensor:
+    @property
+    def n_generations(self) -> int:
+        """Hierarchy generations and refreshes so far: what a march with `same_operator=True` saves."""
+        return self._generation
+
+    def solve(self, kappa: torch.Tensor, f: torch.Tensor, g: Optional[torch.Tensor] = None,
+              sigma: Optional[torch.Tensor] = None, same_operator: bool = False) -> torch.Tensor:
+        op = None
+        if same_operator:
+            op = self._last_operator
+            if op is None:
+                raise ValueError("same_operator=True reuses the operator of the last solve: there has been none")
+            if (sigma is None) != (op.sigma_kept is None):
+                raise ValueError("same_operator=True: the last solve had " + ("no" if sigma is not None else "a") + " sigma")
         if g is None:
-            return _Solve.apply(kappa, f, self, None, "forward", True)
+            return _Solve.apply(kappa, f, self, op, "forward", True, sigma)
         boundary = self._boundary_mask()
         gv, fv = self._same_size(g, "g").reshape(-1), self._same_size(f, "f").reshape(-1)
         g_b = torch.where(boundary, gv, torch.zeros_like(gv))
-        op = self._put_operator(kappa)      # first: the lift runs on the level's grid, which the first generation sets
+        if op is None:
+            op = self._put_operator(kappa, sigma)   # first: the lift runs on the level's grid, which the first generation sets
         lift = _Tangent.apply(kappa.reshape(-1).to(self.device), g_b, self, "interior", "all")
         rhs = torch.where(boundary, gv, fv - lift)
-        return _Solve.apply(kappa, rhs.view(f.shape), self, op, "forward", True)
+        return _Solve.apply(kappa, rhs.view(f.shape), self, op, "forward", True, sigma)
+
+    def reaction_apply(self, w: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
+        """T_sigma(w, x) = R(w) x on the free nodes, 0 on the Dirichlet nodes (`mg_diffusion_apply_dsigma`), differentiable in
+        both: with w = 1 / dt in every cell the M u / dt of an implicit Euler step.  `w`: N^3 float64 of any sign, on the
+        solver's device or the CPU; `x`: (N + 1)^3 float64 on the solver's device."""
+        if not self._generated and not self._grid_only:     # the kernel reads the top level's grid and nothing else
+            self.hierarchy.set_level_grid(self.top)
+            self._grid_only = True
+        return _TSigma.apply(w.reshape(-1).to(self.device), x.reshape(-1), self).view(x.shape)
 
     def tangent(self, kappa: torch.Tensor, f: torch.Tensor, dkappa: torch.Tensor, df: Optional[torch.Tensor] = None,
-                g: Optional[torch.Tensor] = None, dg: Optional[torch.Tensor] = None):
+                g: Optional[torch.Tensor] = None, dg: Optional[torch.Tensor] = None, sigma: Optional[torch.Tensor] = None,
+                dsigma: Optional[torch.Tensor] = None):
         """(u, du): u = A(kappa)^-1 f and its derivative in the direction (dkappa, df),
         du = A^-1 (df - (dA/dkappa . dkappa) u), on the same operator: two solves, one generation.  The cheap derivative
         when kappa depends on a few parameters.  `kappa` as in `solve`; `f`, `dkappa` (N^3 float64, any sign) and `df`
         (None: zero) on the solver's device.  The second solve counts as "tangent" in `last_iterations`.
         With Dirichlet data `g` as in `solve` and its direction `dg` (None: zero; boundary entries only): the interior rows of
         the second right-hand side are df - T(dkappa, u; interior, all) - T(kappa, dg_B; interior, all), u with its boundary
-        values g, and du = dg on the boundary."""
+        values g, and du = dg on the boundary.
+        With `sigma` as in `solve` and its direction `dsigma` (None: zero; N^3 float64 of any sign on the solver's device) the
+        operator is A(kappa) + R(sigma) and the second right-hand side loses T_sigma(dsigma, u) on the free rows."""
         if g is None and dg is not None:
             raise ValueError("dg is the direction of g: it needs g")
-        u = self.solve(kappa, f, g)
+        if sigma is None and dsigma is not None:
+            raise ValueError("dsigma is the direction of sigma: it needs sigma")
+        u = self.solve(kappa, f, g, sigma)
         if g is None:
             rhs = _Tangent.apply(dkappa.reshape(-1), u.reshape(-1), self, "interior", "interior").neg()
             if df is not None:
@@ -161,13 +205,29 @@ class DiffusionSolver:
                 on_boundary = self._same_size(dg, "dg").reshape(-1)
                 dg_b = torch.where(boundary, on_boundary, torch.zeros_like(on_boundary))
                 rhs = rhs - _Tangent.apply(kappa.detach().reshape(-1).to(self.device), dg_b, self, "interior", "all")
+            if dsigma is not None:
+                rhs = rhs - _TSigma.apply(dsigma.reshape(-1), u.reshape(-1), self)
             rhs = torch.where(boundary, on_boundary, rhs)
-        du = _Solve.apply(kappa, rhs, self, self._last_operator, "tangent", True)
+        if g is None and dsigma is not None:
+            rhs = rhs - _TSigma.apply(dsigma.reshape(-1), u.reshape(-1), self)
+        du = _Solve.apply(kappa, rhs, self, self._last_operator, "tangent", True, sigma)
         return u, du.view(u.shape)
 
     # ---- what the autograd function calls --------------------------------------------------------------------
-    def _generate(self, kappa) -> int:
-        """`kappa`: a host array (today's path) or a contiguous float64 tensor on the solver's device."""
+    def _generate(self, kappa, sigma=None) -> int:
+        """`kappa`: a host array (today's path) or a contiguous float64 tensor on the solver's device; `sigma`: None, or the
+        reaction field as one of the two.  The handle's field is set (or cleared) first: the generating calls read it."""
+        react = sigma is not None
+        if react or self._generated_react:
+            if sigma is None or isinstance(sigma, np.ndarray):
+                self.hierarchy.set_diffusion_reaction(sigma)
+            else:
+                torch.cuda.current_stream(self.device).synchronize()
+                self.hierarchy.set_diffusion_reaction(sigma.data_ptr(), N=self.N)
+        if react != self._generated_react:      # levels with and without a reaction diagonal do not refresh into each other
+            self._generated = False
+        self._generated_react = react
+        self._grid_only = False
         if isinstance(kappa, np.ndarray):
             self.hierarchy.gen_diffusion_hierarchy(kappa, self.averaging, matrix_free_min_rows=self.matrix_free_min_rows)
             self.last_generate = "host"
@@ -191,15 +251,22 @@ class DiffusionSolver:
             self._boundary = torch.from_numpy(dirichlet_mask(self.N, self.dirichlet_faces)).to(self.device)
         return self._boundary
 
-    def _put_operator(self, kappa: torch.Tensor) -> "_Operator":
-        """Puts the caller's kappa into the hierarchy: the operator of a `solve` and of what derives from it."""
+    def _put_operator(self, kappa: torch.Tensor, sigma: Optional[torch.Tensor] = None) -> "_Operator":
+        """Puts the caller's kappa (and sigma) into the hierarchy: the operator of a `solve` and of what derives from it."""
         if kappa.dtype != torch.float64 or kappa.numel() != self.N ** 3:
             raise ValueError(f"kappa must hold {self.N ** 3} float64")
-        if kappa.device == self.device:   # no .cpu(): a device copy that the caller's later updates do not reach feeds the library
-            kappa_kept = kappa.detach().reshape(-1).clone()
-        else:
-            kappa_kept = np.ascontiguousarray(kappa.detach().cpu().numpy().reshape(-1))
-        op = _Operator(kappa_kept, self._generate(kappa_kept))
+        if sigma is not None and (sigma.dtype != torch.float64 or sigma.numel() != self.N ** 3):
+            raise ValueError(f"sigma must hold {self.N ** 3} float64")
+
+        def kept(x):
+            if x is None:
+                return None
+            if x.device == self.device:   # no .cpu(): a device copy that the caller's later updates do not reach feeds the library
+                return x.detach().reshape(-1).clone(memory_format=torch.contiguous_format)
+            return np.ascontiguousarray(x.detach().cpu().numpy().reshape(-1))
+
+        kappa_kept, sigma_kept = kept(kappa), kept(sigma)
+        op = _Operator(kappa_kept, self._generate(kappa_kept, sigma_kept), sigma_kept)
         self._last_operator = op
         return op
 
@@ -238,32 +305,38 @@ class DiffusionSolver:
 
 
 class _Operator:
-    """The kappa of one `solve` as the library takes it (a host array or a device copy) and the generation of the
-    hierarchy that holds it: what the solves nested in that solve's backward passes share, so that they neither upload
+    """The kappa (and the sigma, or None) of one `solve` as the library takes them (a host array or a device copy) and the
+    generation of the hierarchy that holds them: what the solves nested in that solve's backward passes share, so that they neither upload
     nor regenerate an operator that is still in place."""
 
-    def __init__(self, kappa_kept, generation):
-        self.kappa_kept, self.generation = kappa_kept, generation
+    def __init__(self, kappa_kept, generation, sigma_kept=None):
+        self.kappa_kept, self.generation, self.sigma_kept = kappa_kept, generation, sigma_kept
 
 
 class _Solve(torch.autograd.Function):
     """S(kappa, f) = A(kappa)^-1 f.  `op` None: the caller's solve, which puts kappa into the hierarchy.  `op` given: a solve
     on the operator of an earlier one (from a backward pass, or `tangent`); `kappa` is then only what the gradient is
-    taken with respect to (None: nobody asked), and the hierarchy is touched only if another kappa has been solved since."""
+    taken with respect to (None: nobody asked), and the hierarchy is touched only if another kappa has been solved since.
+    An optional seventh argument is sigma: the operator is A(kappa) + R(sigma), and sigma is to the reaction term what kappa
+    is to the stiffness -- on a given `op`, only what the gradient is taken with respect to."""
 
     @staticmethod
-    def forward(ctx, kappa, f, solver, op, which, warm):
+    def forward(ctx, kappa, f, solver, op, which, warm, *rest):
+        sigma = rest[0] if rest else None
         rhs = solver._device_vector(f, "f" if op is None else "the right-hand side")
         if op is None:
-            op = solver._put_operator(kappa)
+            op = solver._put_operator(kappa, sigma)
         elif op.generation != solver._generation:       # another kappa has been solved since: this one's operator again
-            op.generation = solver._generate(op.kappa_kept)
+            op.generation = solver._generate(op.kappa_kept, op.sigma_kept)
         u = solver._pcg(rhs, which, warm).view(f.shape)
         ctx.solver, ctx.op = solver, op
         ctx.kappa_like = None if kappa is None else (kappa.shape, kappa.device)
         # kappa is kept as what the gradient is taken with respect to, never for its values (those are op.kappa_kept): not
         # through save_for_backward, whose version check would refuse a caller who has overwritten the tensor since
         ctx.kappa = kappa if ctx.needs_input_grad[0] else None
+        ctx.n_rest = len(rest)
+        ctx.sigma_like = None if sigma is None else (sigma.shape, sigma.device)
+        ctx.sigma = sigma if rest and ctx.needs_input_grad[6] else None     # (as kappa: never for its values)
         ctx.save_for_backward(u)
         return u
 
@@ -274,13 +347,19 @@ class _Solve(torch.autograd.Function):
         # one mg_pcg and one sensitivity kernel.
         solver = ctx.solver
         kappa, (u,) = ctx.kappa, ctx.saved_tensors
-        lam = _Solve.apply(kappa, grad_u, solver, ctx.op, "adjoint", not torch.is_grad_enabled())
+        lam = _Solve.apply(kappa, grad_u, solver, ctx.op, "adjoint", not torch.is_grad_enabled(), *([ctx.sigma] * ctx.n_rest))
         grad_kappa = None
         if ctx.needs_input_grad[0]:
             shape, device = ctx.kappa_like
             grad_kappa = _DKappa.apply(lam, u, solver, "interior", "interior").neg().view(shape).to(device)
         grad_f = lam if ctx.needs_input_grad[1] else None
-        return grad_kappa, grad_f, None, None, None, None
+        if not ctx.n_rest:
+            return grad_kappa, grad_f, None, None, None, None
+        grad_sigma = None
+        if ctx.sigma is not None:
+            shape, device = ctx.sigma_like
+            grad_sigma = _DSigma.apply(lam, u, solver).neg().view(shape).to(device)
+        return grad_kappa, grad_f, None, None, None, None, grad_sigma
 
 
 class _DKappa(torch.autograd.Function):
@@ -329,3 +408,49 @@ class _Tangent(torch.autograd.Function):
         grad_w = _DKappa.apply(y, x, ctx.solver, R, C).view(w.shape) if ctx.needs_input_grad[0] else None
         grad_x = _Tangent.apply(w, y, ctx.solver, C, R).view(x.shape) if ctx.needs_input_grad[1] else None
         return grad_w, grad_x, None, None, None
+
+
+class _DSigma(torch.autograd.Function):
+    """D_sigma(a, b) = mg_diffusion_dsigma(a, b), N^3 cells; the entries of a and b on the Dirichlet nodes count as 0.  With
+    cotangent w: a_bar = T_sigma(w, b), b_bar = T_sigma(w, a)."""
+
+    @staticmethod
+    def forward(ctx, a, b, solver):
+        av, bv = solver._device_vector(a, "a"), solver._device_vector(b, "b")
+        out = torch.empty(solver.N ** 3, dtype=torch.float64, device=solver.device)
+        torch.cuda.current_stream(solver.device).synchronize()
+        solver.hierarchy.diffusion_dsigma(solver.top, av.data_ptr(), bv.data_ptr(), out.data_ptr())
+        ctx.solver = solver
+        ctx.save_for_backward(a, b)
+        return out
+
+    @staticmethod
+    def backward(ctx, w):
+        a, b = ctx.saved_tensors
+        grad_a = _TSigma.apply(w, b, ctx.solver).view(a.shape) if ctx.needs_input_grad[0] else None
+        grad_b = _TSigma.apply(w, a, ctx.solver).view(b.shape) if ctx.needs_input_grad[1] else None
+        return grad_a, grad_b, None
+
+
+class _TSigma(torch.autograd.Function):
+    """T_sigma(w, x) = R(w) x = mg_diffusion_apply_dsigma(w, x) on the free nodes, 0 on the Dirichlet nodes, (N + 1)^3 nodes.
+    With cotangent y: w_bar = D_sigma(y, x), x_bar = T_sigma(w, y) (R is diagonal)."""
+
+    @staticmethod
+    def forward(ctx, w, x, solver):
+        if w.dtype != torch.float64 or w.device != solver.device or w.numel() != solver.N ** 3:
+            raise ValueError(f"the sigma direction must hold {solver.N ** 3} float64 on {solver.device}")
+        wv, xv = w.detach().contiguous(), solver._device_vector(x, "x")
+        out = torch.empty(xv.numel(), dtype=torch.float64, device=solver.device)
+        torch.cuda.current_stream(solver.device).synchronize()
+        solver.hierarchy.diffusion_apply_dsigma(solver.top, wv.data_ptr(), xv.data_ptr(), out.data_ptr())
+        ctx.solver = solver
+        ctx.save_for_backward(w, x)
+        return out
+
+    @staticmethod
+    def backward(ctx, y):
+        w, x = ctx.saved_tensors
+        grad_w = _DSigma.apply(y, x, ctx.solver).view(w.shape) if ctx.needs_input_grad[0] else None
+        grad_x = _TSigma.apply(w, y, ctx.solver).view(x.shape) if ctx.needs_input_grad[1] else None
+        return grad_w, grad_x, None
