@@ -315,6 +315,47 @@ int mg_set_diffusion_reaction_device(mg_handle h, int elements_per_dim, const do
 int mg_diffusion_reaction(mg_handle h, int* on, int* elements_per_dim);
 /* *on = 1 if the level was generated with a reaction diagonal */
 int mg_level_reaction(mg_handle h, int level, int* on);
+/* Robin (convective) faces for the generated diffusion levels (no reference counterpart): on a face outside the Dirichlet
+ * set the condition
+ *     kappa du/dn + alpha (u - u_ext) = 0,   alpha >= 0 varying over the face,
+ * instead of the no-flux condition (alpha == 0).  A field belongs to one face (`face`: exactly one bit of enum mg_face) and
+ * holds elements_per_dim^2 doubles, one per boundary face-cell, finite and >= 0.  With (a, b) the two in-plane axes of the
+ * face in ascending order -- x-faces: (y, z), y-faces: (x, z), z-faces: (x, y) -- face-cell (ca, cb) sits at cb * N + ca.
+ * The Kuhn split cuts every boundary face-cell into two triangles along the diagonal from its in-plane (0,0) to its (1,1)
+ * corner; the row-sum lumped P1 boundary mass gives each vertex of a triangle h^2 / 6.  For a free node i on a field face F
+ *     b_F(alpha)_i = ((sum over the 4 face-cells q of F around i, in ascending index (db, da), of t_{q,i} alpha_q) / 6.0) * h^2,
+ * t = 2 where i is the face-cell's in-plane (0,0) or (1,1) corner, else 1; a face-cell outside the face counts as +0.0; one
+ * accumulator starts with the first product and takes the others one by one; h^2 = pow(h, 2) from the host.  B(alpha)_i is
+ * the sum of b_F over the field faces that contain i in ascending face-bit order, the first term starting the accumulator,
+ * and +0.0 on every node on no field face and on every Dirichlet node (alpha == 1 on a face: the face load of q == 1).
+ * A free row of a generated level gets diag = (the stiffness diagonal as before) + d_i by one more addition, with
+ * d_i = B(alpha)_i, or d_i = R(sigma)_i + B(alpha)_i, formed as that sum, where the handle also holds a reaction field.
+ * Off-diagonals, identity rows, the lifted right-hand side and the load do not change; the ambient load
+ * alpha u_ext int phi_i is mg_diffusion_apply_drobin(alpha, u_ext), which the caller adds to its right-hand side.
+ * Summation order: robin_diag (mg_kernels.hip.h); poisson.robin_diag and poisson.diffusion_level(robin=...) restate it bit
+ * for bit.
+ * The fields are handle state, like the reaction field: the handle keeps its own device copies (counted by
+ * mg_memory_bytes), and they are read where levels are generated -- mg_gen_diffusion_level[_mf], the three hierarchy calls
+ * and mg_refresh_diffusion_hierarchy.  Coarse levels rediscretise with the arithmetic mean of the 2 x 2 children face-cells,
+ * whatever `averaging` says for kappa (boundary mass is additive).  Each level remembers the faces it was generated with
+ * (mg_level_robin); mg_level_reaction keeps meaning "generated with sigma".  A matrix-free level keeps the nodal
+ * B(alpha), or R(sigma) + B(alpha), 8 bytes per row, and its march is that of the reaction term (40 bytes per row and sweep
+ * instead of 32, also without a reaction field: a march that formed B from the face fields was measured slower).
+ * A handle that never sets a field launches the kernels and allocates the bytes it did before these entries existed.
+ * A null pointer clears the field of that face.  The device variant takes its pointer under the contract of
+ * mg_set_diffusion_reaction_device.  Refused by name, the handle left as it was: 2-D handles, slab handles, a `face` that is
+ * not exactly one bit, a non-positive elements_per_dim or one other than that of the fields held on other faces, a device
+ * pointer to the host variant and the reverse, and an alpha that is negative or not finite, the first such face-cell named.
+ * The generating calls refuse, before any level is touched, a field on a face of the handle's Dirichlet set and an
+ * elements_per_dim other than the fields'; mg_refresh_diffusion_hierarchy refuses a set of field faces other than the
+ * levels' (the values may differ).  The face set 0 stays refused as singular whatever alpha is. */
+int mg_set_diffusion_robin(mg_handle h, int elements_per_dim, int face, const double* alpha_host);
+int mg_set_diffusion_robin_device(mg_handle h, int elements_per_dim, int face, const double* alpha_dev);
+/* *faces = the faces on which the handle holds a Robin field (bits of enum mg_face), *elements_per_dim = their face-cells per
+ * dimension (0, 0 without a field) */
+int mg_diffusion_robin(mg_handle h, int* faces, int* elements_per_dim);
+/* *faces = the faces whose Robin field the level was generated with (0: none) */
+int mg_level_robin(mg_handle h, int level, int* faces);
 /* *on = 1 if the level is matrix-free, *kappa_bytes = the device bytes of its kappa (0 otherwise) */
 int mg_level_matrix_free(mg_handle h, int level, int* on, int64_t* kappa_bytes);
 /* Sensitivity of the diffusion operator to kappa (no reference counterpart): out_dev[c] = d(a^T A(kappa) b) / d kappa_c for the
@@ -381,6 +422,19 @@ int mg_diffusion_apply_dkappa_ex(mg_handle h, int level, const double* dkappa_de
  * are not device memory of the handle's device, and an out_dev that overlaps an input. */
 int mg_diffusion_dsigma(mg_handle h, int level, const double* a_dev, const double* b_dev, double* out_dev);
 int mg_diffusion_apply_dsigma(mg_handle h, int level, const double* dsigma_dev, const double* x_dev, double* out_dev);
+/* The two sensitivity operators of the Robin term, per face F (no reference counterpart).  B is linear in alpha and diagonal:
+ *     mg_diffusion_apply_drobin: out_i = T_alpha,F(dalpha, x)_i = b_F(dalpha)_i x_i on the free nodes of face F (those of the
+ *                                handle's face set), +0.0 on every other node of the level; dalpha (N^2) may have any sign;
+ *     mg_diffusion_drobin:       out_q = D_alpha,F(a, b)_q = (h^2 / 6) sum over the 4 corners i of face-cell q of
+ *                                t_{q,i} a~_i b~_i, a~, b~ = a, b with the Dirichlet nodes taken as 0; out: N^2 face-cells.
+ * They are adjoint, a . T(w, x) = w . D(a, x), and close under differentiation as D_sigma / T_sigma do.  With the adjoint solve
+ * (A + R + B) lambda = dJ/du, dJ/dalpha_F = -D_alpha,F(lambda, u).  Neither reads alpha or a matrix.  Summation order:
+ * mg_diffusion_adj.hip.h; poisson.diffusion_drobin and poisson.diffusion_apply_drobin restate them bit for bit (no fma in
+ * either).  Pointers, node order, stream and synchronisation are those of mg_diffusion_dsigma / mg_diffusion_apply_dsigma.
+ * Refused with an error before anything is launched: what those entries refuse, a `face` that is not exactly one bit, and a
+ * face of the handle's Dirichlet set. */
+int mg_diffusion_drobin(mg_handle h, int level, int face, const double* a_dev, const double* b_dev, double* out_dev);
+int mg_diffusion_apply_drobin(mg_handle h, int level, int face, const double* dalpha_dev, const double* x_dev, double* out_dev);
 /* getJacobiMatrices (multigrid.py:48-56) as a stand-alone set-up kernel, for callers that
  * want the reference's split operands back: for every stored entry a_ij of the CSR matrix
  * writes scaled[q] = a_ij / a_ii computed as (1/a_ii) * a_ij, keep[q] = 1 unless the entry
@@ -778,6 +832,9 @@ int mg_reset_smoother_launches(mg_handle h);
  * "dsigma" = mg_diffusion_dsigma of (MG_VEC_V, MG_VEC_F) into the first N^3 entries of MG_VEC_R; "apply_dsigma" =
  * mg_diffusion_apply_dsigma with dsigma = the first N^3 entries of MG_VEC_F and x = MG_VEC_V, into MG_VEC_R (the
  * "diffusion_mf" keys time the march with the reaction term on a level that has one);
+ * "drobin" = mg_diffusion_drobin of face z+ of (MG_VEC_V, MG_VEC_F) into the first N^2 entries of MG_VEC_R; "apply_drobin" =
+ * mg_diffusion_apply_drobin of face z+ with dalpha = the first N^2 entries of MG_VEC_F and x = MG_VEC_V, into MG_VEC_R (an
+ * error where z+ is a Dirichlet face of the handle's set);
  * "kappa_ingest" = one launch of the fused copy and coarsening of mg_gen_diffusion_hierarchy_device on a matrix-free level, from a
  * scratch copy of its kappa back into the level's own (the same bytes: the level is unchanged) and into a scratch coarse field,
  * arithmetic averaging; an error on stored levels).

@@ -66,6 +66,10 @@ SIGNATURES = {
     "mg_set_diffusion_reaction_device": [_H, C.c_int, C.c_void_p],
     "mg_diffusion_reaction": [_H, _ip, _ip],
     "mg_level_reaction": [_H, C.c_int, _ip],
+    "mg_set_diffusion_robin": [_H, C.c_int, C.c_int, C.c_void_p],
+    "mg_set_diffusion_robin_device": [_H, C.c_int, C.c_int, C.c_void_p],
+    "mg_diffusion_robin": [_H, _ip, _ip],
+    "mg_level_robin": [_H, C.c_int, _ip],
     "mg_jacobi_split": [C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                         C.c_void_p, C.c_void_p],
     "mg_set_params": [_H, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int],
@@ -92,6 +96,8 @@ SIGNATURES = {
     "mg_diffusion_apply_dkappa_ex": [_H, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p],
     "mg_diffusion_dsigma": [_H, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
     "mg_diffusion_apply_dsigma": [_H, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
+    "mg_diffusion_drobin": [_H, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
+    "mg_diffusion_apply_drobin": [_H, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
     "mg_zero_vector": [_H, C.c_int, C.c_int],
     "mg_copy_vector": [_H, C.c_int, C.c_int, C.c_int],
     "mg_smooth": [_H, C.c_int, C.c_int],

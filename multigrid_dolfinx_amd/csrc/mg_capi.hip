@@ -199,6 +199,8 @@ struct Level {
     bool diffusion_hierarchy = false;       // generated by one of the diffusion hierarchy entries: mg_refresh_diffusion_hierarchy may renew it
     bool react = false;                     // generated with a reaction diagonal R(sigma) (mg_set_diffusion_reaction) ...
     DevBuf<double> rdiag;                   // ... which a matrix-free level keeps as one more row vector (nodal, not sigma itself)
+    int robin = 0;                          // the faces whose Robin field the level was generated with (mg_set_diffusion_robin): B(alpha) is
+                                            // one more term of that nodal vector, rdiag = B or R + B (react stays "generated with sigma")
     DVector v, v2, f, err, ftrue;
     DVector sw;                             // once-relaxed boundary planes of a slab (paired sweeps, world > 1)
     DVector fcg_x, fcg_p, fcg_q, fcg_b;     // mg_pcg on this level: iterate, direction, A p, the saved right-hand side
@@ -292,6 +294,8 @@ struct mg_context {
                                     // from now on, and what MG_NODES_INTERIOR masks; the other faces are no-flux faces
     DevBuf<double> sigma;           // mg_set_diffusion_reaction: the handle's copy of sigma, sigma_N^3 cells (empty: no reaction term), read
     int sigma_N = 0;                // where diffusion levels are generated
+    DevBuf<double> alpha[6];        // mg_set_diffusion_robin: the handle's copies of the Robin fields by face bit (x-, x+, y-, y+, z-, z+),
+    int alpha_N = 0;                // alpha_N^2 face-cells each (empty: no field on that face), read where sigma is
     int dkappa_gather = 0;          // mg_diffusion_dkappa: 1 = one thread per cell reading through the caches instead of the plane march
                                     // (1025^3: 12.5 ms against 5.75 for the march)
     int lattice_tile = 0;           // tile of that march: 0 / 1 = 64 x 16 cells (256 threads), 2 = 128 x 16 (512 threads)
@@ -830,6 +834,107 @@ int launch_reaction_diag(mg_context* c, const double* w, double* out, int N) {
     return 0;
 }
 
+// The Robin fields (mg_set_diffusion_robin) are read where the reaction field is, under the same conditions; a field on a
+// face of the Dirichlet set has no free node to act on and is refused where levels are generated.
+int robin_faces(const mg_context* c) {
+    int faces = 0;
+    for (int f = 0; f < 6; ++f)
+        if (c->alpha[f]) faces |= 1 << f;
+    return faces;
+}
+
+int robin_handle(const mg_context* c, const std::string& who, int N) {
+    const int faces = robin_faces(c);
+    if (!faces) return 0;
+    if (c->dim != 3) return fail(who + ": Robin faces (mg_set_diffusion_robin) are 3-D only");
+    if (c->comm.active()) return fail(who + ": Robin faces (mg_set_diffusion_robin) need a whole (not slab) handle");
+    if (faces & c->diffusion_faces)
+        return fail(who + ": the handle holds Robin fields on the faces " + std::to_string(faces) + " (mg_set_diffusion_robin) and its Dirichlet "
+                    "face set is " + std::to_string(c->diffusion_faces) + " (mg_set_diffusion_faces): face " +
+                    std::to_string(faces & c->diffusion_faces & -(faces & c->diffusion_faces)) + " cannot be both");
+    if (N != c->alpha_N)
+        return fail(who + ": elements_per_dim = " + std::to_string(N) + ", the Robin fields (mg_set_diffusion_robin) have " +
+                    std::to_string(c->alpha_N) + " face-cells per dimension: set fields of the level's size, or clear them");
+    return 0;
+}
+
+// The Robin fields of one level on their way down a hierarchy: the handle's on the top level (borrowed), below it the
+// arithmetic mean of the 2 x 2 children whatever the kappa averaging (boundary mass is additive), held here.
+struct RobinWalk {
+    RobinFaces rf{};
+    int faces = 0;
+    DevTemp held[6], coarse[6];
+    explicit RobinWalk(const mg_context* c) : faces(robin_faces(c)) {
+        for (int f = 0; f < 6; ++f) rf.f[f] = c->alpha[f];
+    }
+    // the fields of the level below (Nc face-cells per dimension) into `coarse`, on the handle's stream
+    int coarsen(mg_context* c, int Nc) {
+        for (int f = 0; f < 6; ++f) {
+            if (!rf.f[f]) continue;
+            const int64_t nc = (int64_t)Nc * Nc;
+            MG_TRY(coarse[f].alloc((size_t)nc * 8));
+            const unsigned nb = (unsigned)std::max<int64_t>(1, std::min<int64_t>(2048, (nc + KI_BLOCK - 1) / KI_BLOCK));
+            hipLaunchKernelGGL(kappa_ingest<2>, dim3(nb), dim3(KI_BLOCK), 0, c->stream, rf.f[f], (double*)nullptr, coarse[f].as<double>(), Nc, 0, 0);
+            HIP_TRY(hipGetLastError());
+        }
+        return 0;
+    }
+    // one level down (the stream is synchronised: the fields of the level above go)
+    void descend() {
+        for (int f = 0; f < 6; ++f) {
+            if (!rf.f[f]) continue;
+            held[f] = std::move(coarse[f]);
+            rf.f[f] = held[f].as<const double>();
+        }
+    }
+};
+
+// nodal B(alpha) of the level's Robin fields on a whole 3-D grid of N cells per dimension (robin_diag, mg_kernels.hip.h),
+// +0.0 on the Dirichlet nodes of the face set; add: out holds R(sigma) and becomes R(sigma) + B(alpha)
+int launch_robin_diag(mg_context* c, const RobinFaces& rf, int dirichlet_faces, double* out, int N, bool add) {
+    const double h = 1.0 / (double)N;
+    const dim3 grid(blocks_for(((int64_t)N + 1) * (N + 1), RD_BLOCK), (unsigned)(N + 1), 1u);
+    hipLaunchKernelGGL(robin_diag, grid, dim3(RD_BLOCK), 0, c->stream, rf, free_box(dirichlet_faces, N + 1, N + 1, N + 1), out, N,
+                       std::pow(h, 2.0), add ? 1 : 0);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// the one nodal term d of a free row's diagonal: R(sigma), B(alpha), or R(sigma) + B(alpha) formed as that sum
+int launch_nodal_diag(mg_context* c, const double* d_sigma, const RobinWalk& rw, double* out, int N) {
+    if (d_sigma) MG_TRY(launch_reaction_diag(c, d_sigma, out, N));
+    if (rw.faces) MG_TRY(launch_robin_diag(c, rw.rf, c->diffusion_faces, out, N, d_sigma != nullptr));
+    return 0;
+}
+
+// T_alpha,F(w, x) = b_F(w) x on the free nodes of face F, +0.0 elsewhere / its adjoint D_alpha,F(a, b) per face-cell
+// (mg_diffusion_adj.hip.h); whole 3-D grid levels, the caller's lexicographic buffers; fi: the face's bit number
+DrArgs dr_args(const mg_context* c, const Level& L, int fi, const double* a, const double* b, double* out) {
+    DrArgs d{};
+    d.a = a; d.b = b; d.out = out;
+    d.nx = L.g.nx; d.nz = L.g.nz; d.N = L.N; d.P = L.g.plane;
+    d.axis = fi >> 1;
+    d.at = (fi & 1) ? L.N : 0;
+    d.box = level_box(L, c->diffusion_faces);
+    return d;
+}
+
+int launch_apply_drobin(mg_context* c, const Level& L, int fi, const double* dalpha, const double* x, double* out) {
+    DrArgs d = dr_args(c, L, fi, dalpha, x, out);
+    d.scale = std::pow(1.0 / (double)L.N, 2.0);
+    hipLaunchKernelGGL(diffusion_apply_drobin, dim3(blocks_for(L.g.plane, DK_BLOCK), (unsigned)L.g.nz, 1u), dim3(DK_BLOCK), 0, c->stream, d);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int launch_drobin(mg_context* c, const Level& L, int fi, const double* a, const double* b, double* out) {
+    DrArgs d = dr_args(c, L, fi, a, b, out);
+    d.scale = std::pow(1.0 / (double)L.N, 2.0) / 6.0;
+    hipLaunchKernelGGL(diffusion_drobin, dim3(blocks_for((int64_t)L.N * L.N, DK_BLOCK)), dim3(DK_BLOCK), 0, c->stream, d);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 // T_sigma(w, x) = R(w) x on the free nodes of the handle's face set, +0.0 elsewhere / its adjoint D_sigma(a, b) per cell
 // (mg_diffusion_adj.hip.h); whole 3-D grid levels, the caller's lexicographic buffers
 DsArgs ds_args(const mg_context* c, const Level& L, const double* a, const double* b, double* out) {
@@ -879,7 +984,7 @@ int launch_diffusion_mf(mg_context* c, const Level& L, int mode, bool dot, const
     with_mode(mode, dot, [&](auto m, auto d) {
         constexpr int MODE = decltype(m)::value;
         if constexpr (MODE == MODE_GS) known = false;
-        else if (L.react) {                         // A(kappa) + R(sigma): the march with the level's nodal R(sigma)
+        else if (L.rdiag) {                         // A(kappa) + R(sigma) and / or B(alpha): the march with the level's nodal diagonal term
             const MfReactArgs ra{a, fa.box, L.rdiag};
             if (L.faces != MG_FACES_ALL) hipLaunchKernelGGL((diffusion_mf_react<MODE, decltype(d)::value, true>), grid, blk, 0, c->stream, ra);
             else hipLaunchKernelGGL((diffusion_mf_react<MODE, decltype(d)::value, false>), grid, blk, 0, c->stream, ra);
@@ -926,7 +1031,7 @@ int launch_diffusion_rhs(mg_context* c, const Level& L, const double* d_kappa, d
     d.kappa = d_kappa;
     d.kc0 = 0;
     d.box = level_box(L, L.faces);
-    d.react = L.react ? L.rdiag.get() : nullptr;
+    d.react = L.rdiag;                          // (a matrix-free level keeps it iff it has a reaction term or Robin fields)
     hipLaunchKernelGGL(gen_diffusion_rhs, grid3(L.g, L.g.nk), dim3(kPlaneBlock), 0, c->stream, d, f_rows, dinv_rows);
     HIP_TRY(hipGetLastError());
     return 0;
@@ -4520,17 +4625,19 @@ int check_kappa(mg_context* c, const double* d_kappa, int64_t n, int64_t base, i
     return fail("kappa must be positive and finite: cell " + cell + ") = index " + std::to_string(q) + " holds " + val);
 }
 
-// the stored level from a device kappa holding cell planes [kc0, ...); d_sigma: the level's N^3 reaction cells or null
-int gen_diffusion_level(mg_context* c, int level, int N, const double* d_kappa, int kc0, int prune_zeros, const double* d_sigma) {
+// the stored level from a device kappa holding cell planes [kc0, ...); d_sigma: the level's N^3 reaction cells or null;
+// rw: the level's Robin fields
+int gen_diffusion_level(mg_context* c, int level, int N, const double* d_kappa, int kc0, int prune_zeros, const double* d_sigma,
+                        const RobinWalk& rw) {
     DiffusionArgs d{};
     d.ga = gen_args(c, N, prune_zeros);
     d.kappa = d_kappa;
     d.kc0 = kc0;
     MG_TRY(face_set_handle(c, "mg_gen_diffusion_level"));
-    DevTemp rdiag;                              // nodal R(sigma): read by the generating kernel and not kept
-    if (d_sigma) {
+    DevTemp rdiag;                              // nodal R(sigma) [+ B(alpha)]: read by the generating kernel and not kept
+    if (d_sigma || rw.faces) {
         MG_TRY(rdiag.alloc((size_t)(N + 1) * (N + 1) * (N + 1) * 8));
-        MG_TRY(launch_reaction_diag(c, d_sigma, rdiag.as<double>(), N));
+        MG_TRY(launch_nodal_diag(c, d_sigma, rw, rdiag.as<double>(), N));
         d.react = rdiag.as<const double>();
     }
     const int faces = c->diffusion_faces;       // (not the default: a 3-D whole handle, so L.g is the whole grid)
@@ -4542,6 +4649,7 @@ int gen_diffusion_level(mg_context* c, int level, int N, const double* d_kappa, 
     }));
     c->L[level].faces = faces;
     c->L[level].react = d_sigma != nullptr;
+    c->L[level].robin = rw.faces;
     return 0;
 }
 
@@ -4553,6 +4661,7 @@ int mg_gen_diffusion_level(mg_handle c, int level, int N, const double* kappa, i
     if (!kappa) return fail("null kappa");
     HIP_TRY(hipSetDevice(c->device));
     MG_TRY(reaction_handle(c, "mg_gen_diffusion_level", N));
+    MG_TRY(robin_handle(c, "mg_gen_diffusion_level", N));
     Level geo;                                   // checked before the level is touched: a refusal leaves it as it was
     MG_TRY(setup_geometry(c, geo, level, N));
     int kc0 = 0, kc1 = 0;
@@ -4562,7 +4671,7 @@ int mg_gen_diffusion_level(mg_handle c, int level, int N, const double* kappa, i
     MG_TRY(d_kappa.alloc((size_t)n * 8));
     HIP_TRY(hipMemcpy(d_kappa.p, kappa + (size_t)kc0 * cp, (size_t)n * 8, hipMemcpyHostToDevice));
     MG_TRY(check_kappa(c, d_kappa.as<const double>(), n, (int64_t)kc0 * cp, N));
-    return gen_diffusion_level(c, level, N, d_kappa.as<const double>(), kc0, prune_zeros, c->sigma);
+    return gen_diffusion_level(c, level, N, d_kappa.as<const double>(), kc0, prune_zeros, c->sigma, RobinWalk(c));
 }
 
 namespace {
@@ -4576,8 +4685,9 @@ int fill_rhs_mf(mg_context* c, Level& L, const double* d_kappa) {
 }
 
 // the matrix-free level from a whole device kappa (N^3 cells, n of them), which the level takes over on success; d_sigma:
-// the level's N^3 reaction cells or null -- the level keeps their nodal R(sigma), not the cells
-int gen_diffusion_level_mf(mg_context* c, int level, int N, DevTemp& kappa, int64_t n, const double* d_sigma) {
+// the level's N^3 reaction cells or null -- the level keeps their nodal R(sigma), not the cells; rw: the level's Robin
+// fields, whose B(alpha) is folded into that nodal vector (R + B, or B alone)
+int gen_diffusion_level_mf(mg_context* c, int level, int N, DevTemp& kappa, int64_t n, const double* d_sigma, const RobinWalk& rw) {
     const double* const d_kappa = kappa.as<const double>();
     Level& L = c->L[level];
     LevelBuild build(c, L);
@@ -4588,11 +4698,12 @@ int gen_diffusion_level_mf(mg_context* c, int level, int N, DevTemp& kappa, int6
     MG_TRY(alloc_level_vectors(c, L));
     if (level + 1 < c->nlev) MG_TRY(vec_alloc(c, L, &L.ftrue));     // (the true right-hand side for mg_fmg, as on stored levels)
     L.faces = c->diffusion_faces;
-    if (d_sigma) {
+    if (d_sigma || rw.faces) {
         MG_TRY(L.rdiag.alloc(c, (size_t)L.n_global));
-        MG_TRY(launch_reaction_diag(c, d_sigma, L.rdiag, N));
-        L.react = true;
+        MG_TRY(launch_nodal_diag(c, d_sigma, rw, L.rdiag, N));
     }
+    L.react = d_sigma != nullptr;
+    L.robin = rw.faces;
     MG_TRY(fill_rhs_mf(c, L, d_kappa));
     HIP_TRY(hipStreamSynchronize(c->stream));
     // what the stored level would report: one diagonal entry per row and two entries per pair of free axis neighbours (the
@@ -4628,6 +4739,7 @@ int mg_gen_diffusion_level_mf(mg_handle c, int level, int N, const double* kappa
     if (!kappa) return fail("null kappa");
     HIP_TRY(hipSetDevice(c->device));
     MG_TRY(reaction_handle(c, "mg_gen_diffusion_level_mf", N));
+    MG_TRY(robin_handle(c, "mg_gen_diffusion_level_mf", N));
     Level geo;                                   // checked before the level is touched: a refusal leaves it as it was
     MG_TRY(setup_geometry(c, geo, level, N));
     const int64_t n = cell_plane(c, N) * N;
@@ -4635,7 +4747,7 @@ int mg_gen_diffusion_level_mf(mg_handle c, int level, int N, const double* kappa
     MG_TRY(d_kappa.alloc((size_t)n * 8));
     HIP_TRY(hipMemcpy(d_kappa.p, kappa, (size_t)n * 8, hipMemcpyHostToDevice));
     MG_TRY(check_kappa(c, d_kappa.as<const double>(), n, 0, N));
-    return gen_diffusion_level_mf(c, level, N, d_kappa, n, c->sigma);
+    return gen_diffusion_level_mf(c, level, N, d_kappa, n, c->sigma, RobinWalk(c));
 }
 
 namespace {
@@ -4667,6 +4779,7 @@ int hierarchy_refusals(mg_context* c, const std::string& who, int top_level, int
         return fail(who + " needs an even elements_per_dim on every level above level 0 (" + std::to_string(N) +
                     " is not N0 * 2^" + std::to_string(top_level) + ")");
     MG_TRY(reaction_handle(c, who, N));
+    MG_TRY(robin_handle(c, who, N));
     Level geo;
     return setup_geometry(c, geo, top_level, N);
 }
@@ -4679,17 +4792,19 @@ int hierarchy_refusals(mg_context* c, const std::string& who, int top_level, int
 // it.  At most two kappa fields are alive at a time besides those the matrix-free levels keep.
 // The handle's reaction field (mg_set_diffusion_reaction) walks beside kappa: borrowed on the top level, below it the
 // arithmetic mean of the 2^3 children whatever `averaging` says (mass is additive), by the same pass; besides the handle's
-// own, at most two sigma fields are alive at a time, and no level keeps one.
+// own, at most two sigma fields are alive at a time, and no level keeps one.  The Robin fields (mg_set_diffusion_robin)
+// walk the same way, 2 x 2 children per face-cell (RobinWalk).
 int gen_diffusion_hierarchy(mg_context* c, int top_level, int N, const double* src, DevTemp& held, int averaging,
                             int64_t min_rows) {
     MG_TRY(check_kappa(c, src, cell_plane(c, N) * N, 0, N));
     const double* ssrc = c->sigma;              // (hierarchy_refusals: of the top level's size)
     DevTemp sheld;
+    RobinWalk rw(c);
     for (int l = top_level, Nl = N; l >= 0; --l, Nl /= 2) {
         const int64_t n = cell_plane(c, Nl) * Nl;
         const int64_t rows = c->dim == 3 ? ((int64_t)Nl + 1) * (Nl + 1) * (Nl + 1) : ((int64_t)Nl + 1) * (Nl + 1);
         const bool mf = l > 0 && rows >= min_rows;
-        if (!mf) MG_TRY(gen_diffusion_level(c, l, Nl, src, 0, 1, ssrc));
+        if (!mf) MG_TRY(gen_diffusion_level(c, l, Nl, src, 0, 1, ssrc, rw));
         DevTemp own, coarse, scoarse;
         if (mf && !held.p) MG_TRY(own.alloc((size_t)n * 8));       // (matrix-free levels are above level 0: the pass below copies)
         if (l > 0) {
@@ -4700,9 +4815,11 @@ int gen_diffusion_hierarchy(mg_context* c, int top_level, int N, const double* s
                 MG_TRY(scoarse.alloc((size_t)(cell_plane(c, Nc) * Nc) * 8));
                 MG_TRY(launch_kappa_ingest(c, ssrc, nullptr, scoarse.as<double>(), Nc, MG_KAPPA_ARITHMETIC));
             }
+            MG_TRY(rw.coarsen(c, Nc));
             HIP_TRY(hipStreamSynchronize(c->stream));
         }
-        if (mf) MG_TRY(gen_diffusion_level_mf(c, l, Nl, own.p ? own : held, n, ssrc));
+        if (mf) MG_TRY(gen_diffusion_level_mf(c, l, Nl, own.p ? own : held, n, ssrc, rw));
+        if (l > 0) rw.descend();
         held = std::move(coarse);
         src = held.as<const double>();
         if (ssrc) {
@@ -4772,9 +4889,13 @@ int mg_refresh_diffusion_hierarchy(mg_handle c, int top_level, const double* kap
         if (L.react != (c->sigma.get() != nullptr))
             return fail(who + ": level " + std::to_string(l) + " was generated " + (L.react ? "with" : "without") + " a reaction term, the handle has " +
                         (c->sigma ? "a" : "no") + " reaction field now (mg_set_diffusion_reaction): generate the hierarchy again");
+        if (L.robin != robin_faces(c))
+            return fail(who + ": level " + std::to_string(l) + " was generated with Robin fields on the faces " + std::to_string(L.robin) +
+                        ", the handle holds fields on the faces " + std::to_string(robin_faces(c)) + " now (mg_set_diffusion_robin): generate the hierarchy again");
     }
     const int N = c->L[top_level].N;
     MG_TRY(reaction_handle(c, who, N));
+    MG_TRY(robin_handle(c, who, N));
     MG_TRY(check_kappa(c, kappa_dev, cell_plane(c, N) * N, 0, N));      // read-only: a refusal leaves the old hierarchy usable
     // whatever the old matrices fed goes: captured cycles, level 0's factorisation, every level's Chebyshev estimate
     ++c->epoch;
@@ -4787,15 +4908,17 @@ int mg_refresh_diffusion_hierarchy(mg_handle c, int top_level, const double* kap
     DevTemp held;                               // src where it is a temporary: the coarsened field above a stored level
     const double* ssrc = c->sigma;              // the reaction field walks beside kappa; a matrix-free level's R(sigma) is rewritten in place
     DevTemp sheld;
+    RobinWalk rw(c);                            // the Robin fields too: a matrix-free level's nodal vector is rewritten in place
     for (int l = top_level, Nl = N; l >= 0; --l, Nl /= 2) {
         Level& L = c->L[l];
         const bool mf = L.mf;
         if (!mf) {                              // stored: the level is rebuilt by the pipeline that made it
-            MG_TRY(gen_diffusion_level(c, l, Nl, src, 0, 1, ssrc));
+            MG_TRY(gen_diffusion_level(c, l, Nl, src, 0, 1, ssrc, rw));
             L.diffusion_hierarchy = true;
-        } else if (ssrc) {
-            MG_TRY(launch_reaction_diag(c, ssrc, L.rdiag, Nl));
+        } else if (ssrc || rw.faces) {
+            MG_TRY(launch_nodal_diag(c, ssrc, rw, L.rdiag, Nl));
         }
+        if (l > 0) MG_TRY(rw.coarsen(c, Nl / 2));
         DevTemp coarse, scoarse;
         if (l > 0 && ssrc) {
             MG_TRY(scoarse.alloc((size_t)(cell_plane(c, Nl / 2) * (Nl / 2)) * 8));
@@ -4817,6 +4940,7 @@ int mg_refresh_diffusion_hierarchy(mg_handle c, int top_level, const double* kap
             HIP_TRY(hipMemsetAsync(L.v2.raw, 0, (size_t)vec_total(L) * sizeof(double), c->stream));
         }
         HIP_TRY(hipStreamSynchronize(c->stream));
+        if (l > 0) rw.descend();
         held = std::move(coarse);
         src = coarse_p;
         if (ssrc) {
@@ -4940,6 +5064,97 @@ int mg_diffusion_reaction(mg_handle c, int* on, int* elements_per_dim) {
 int mg_level_reaction(mg_handle c, int level, int* on) {
     MG_TRY(check_level(c, level));
     if (on) *on = c->L[level].react ? 1 : 0;
+    return 0;
+}
+
+namespace {
+
+// the bit number of a face that is exactly one bit of enum mg_face, -1 otherwise
+int face_index(int face) {
+    for (int f = 0; f < 6; ++f)
+        if (face == 1 << f) return f;
+    return -1;
+}
+
+int bad_face(const std::string& who, int face) {
+    return fail(who + ": face = " + std::to_string(face) + " is not exactly one face (x- = 1, x+ = 2, y- = 4, y+ = 8, z- = 16, z+ = 32)");
+}
+
+// one Robin field into the handle: refusals, the copy, the check; until the last line the handle is as it was
+int set_diffusion_robin(mg_context* c, const std::string& who, int N, int face, const double* alpha, bool device) {
+    if (!c) return fail("null handle");
+    const int fi = face_index(face);
+    if (fi < 0) return bad_face(who, face);
+    if (!alpha) {
+        c->alpha[fi].reset();
+        if (!robin_faces(c)) c->alpha_N = 0;
+        return 0;
+    }
+    if (c->dim != 3) return fail(who + ": Robin faces are 3-D only (this handle is 2-D)");
+    if (c->comm.active()) return fail(who + ": Robin faces need a whole (not slab) handle");
+    if (N <= 0) return fail(who + ": elements_per_dim must be positive");
+    if ((robin_faces(c) & ~face) && N != c->alpha_N)
+        return fail(who + ": elements_per_dim = " + std::to_string(N) + ", the fields the handle holds on other faces have " +
+                    std::to_string(c->alpha_N) + " face-cells per dimension: clear them first");
+    HIP_TRY(hipSetDevice(c->device));
+    const int64_t n = (int64_t)N * N;
+    DevTemp field;
+    if (device) {
+        MG_TRY(need_device_pointer(c, alpha, who.c_str(), "alpha"));
+        MG_TRY(field.alloc((size_t)n * 8));
+        HIP_TRY(hipMemcpyAsync(field.p, alpha, (size_t)n * 8, hipMemcpyDeviceToDevice, c->stream));
+    } else {
+        hipPointerAttribute_t at{};
+        const hipError_t e = hipPointerGetAttributes(&at, alpha);
+        if (e != hipSuccess) (void)hipGetLastError();       // (an unregistered host pointer is an error of the query in some runtimes)
+        if (e == hipSuccess && at.type == hipMemoryTypeDevice)
+            return fail(who + ": alpha is not host memory (a device pointer? mg_set_diffusion_robin_device takes those)");
+        MG_TRY(field.alloc((size_t)n * 8));
+        HIP_TRY(hipMemcpy(field.p, alpha, (size_t)n * 8, hipMemcpyHostToDevice));
+    }
+    // the first face-cell that is not a finite double >= 0 (sigma_check: the same condition), as an error
+    DevTemp d_first;
+    MG_TRY(d_first.alloc(sizeof(unsigned long long)));
+    HIP_TRY(hipMemsetAsync(d_first.p, 0xff, sizeof(unsigned long long), c->stream));
+    const unsigned nb = (unsigned)std::max<int64_t>(1, std::min<int64_t>(8192, (n + 255) / 256));
+    hipLaunchKernelGGL(sigma_check, dim3(nb), dim3(256), 0, c->stream, field.as<const double>(), n, d_first.as<unsigned long long>());
+    HIP_TRY(hipGetLastError());
+    unsigned long long first = 0;
+    HIP_TRY(hipMemcpyAsync(&first, d_first.p, sizeof(first), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (first != ~0ull) {
+        double x = 0.0;
+        HIP_TRY(hipMemcpy(&x, field.as<const double>() + first, sizeof(double), hipMemcpyDeviceToHost));
+        char val[40];
+        snprintf(val, sizeof(val), "%.17g", x);
+        return fail(who + ": alpha must be finite and not negative: face-cell (" + std::to_string((int64_t)first % N) + ", " +
+                    std::to_string((int64_t)first / N) + ") of face " + std::to_string(face) + " = index " + std::to_string(first) + " holds " + val);
+    }
+    c->alpha[fi].adopt(c, field.release<double>(), (size_t)n);
+    c->alpha_N = N;
+    return 0;
+}
+
+}  // namespace
+
+int mg_set_diffusion_robin(mg_handle c, int N, int face, const double* alpha_host) {
+    return set_diffusion_robin(c, "mg_set_diffusion_robin", N, face, alpha_host, false);
+}
+
+int mg_set_diffusion_robin_device(mg_handle c, int N, int face, const double* alpha_dev) {
+    return set_diffusion_robin(c, "mg_set_diffusion_robin_device", N, face, alpha_dev, true);
+}
+
+int mg_diffusion_robin(mg_handle c, int* faces, int* elements_per_dim) {
+    if (!c) return fail("null handle");
+    if (faces) *faces = robin_faces(c);
+    if (elements_per_dim) *elements_per_dim = c->alpha_N;
+    return 0;
+}
+
+int mg_level_robin(mg_handle c, int level, int* faces) {
+    MG_TRY(check_level(c, level));
+    if (faces) *faces = c->L[level].robin;
     return 0;
 }
 
@@ -5217,6 +5432,44 @@ int mg_diffusion_apply_dsigma(mg_handle c, int level, const double* dsigma_dev, 
     const size_t nodes = (size_t)L.g.plane * (size_t)L.g.nz * 8, cells = (size_t)L.N * L.N * L.N * 8;
     MG_TRY(need_dsigma_operands(c, who, "dsigma", dsigma_dev, cells, "x", x_dev, nodes, out_dev, nodes));
     MG_TRY(launch_apply_dsigma(c, L, dsigma_dev, x_dev, out_dev));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// what the two Robin sensitivities refuse beyond the sigma entries: a face that is not one face or lies in the Dirichlet set
+static int need_drobin_face(mg_context* c, const char* who, int face, int* fi) {
+    *fi = face_index(face);
+    if (*fi < 0) return bad_face(who, face);
+    if (face & c->diffusion_faces)
+        return fail(std::string(who) + ": face " + std::to_string(face) + " is a Dirichlet face of the handle's face set " +
+                    std::to_string(c->diffusion_faces) + " (mg_set_diffusion_faces): it has no free node");
+    return 0;
+}
+
+int mg_diffusion_drobin(mg_handle c, int level, int face, const double* a_dev, const double* b_dev, double* out_dev) {
+    const char* who = "mg_diffusion_drobin";
+    MG_TRY(need_dkappa_level(c, level, who, "Robin"));
+    int fi = -1;
+    MG_TRY(need_drobin_face(c, who, face, &fi));
+    HIP_TRY(hipSetDevice(c->device));
+    const Level& L = c->L[level];
+    const size_t nodes = (size_t)L.g.plane * (size_t)L.g.nz * 8, cells = (size_t)L.N * L.N * 8;
+    MG_TRY(need_dsigma_operands(c, who, "a", a_dev, nodes, "b", b_dev, nodes, out_dev, cells));
+    MG_TRY(launch_drobin(c, L, fi, a_dev, b_dev, out_dev));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int mg_diffusion_apply_drobin(mg_handle c, int level, int face, const double* dalpha_dev, const double* x_dev, double* out_dev) {
+    const char* who = "mg_diffusion_apply_drobin";
+    MG_TRY(need_dkappa_level(c, level, who, "Robin"));
+    int fi = -1;
+    MG_TRY(need_drobin_face(c, who, face, &fi));
+    HIP_TRY(hipSetDevice(c->device));
+    const Level& L = c->L[level];
+    const size_t nodes = (size_t)L.g.plane * (size_t)L.g.nz * 8, cells = (size_t)L.N * L.N * 8;
+    MG_TRY(need_dsigma_operands(c, who, "dalpha", dalpha_dev, cells, "x", x_dev, nodes, out_dev, nodes));
+    MG_TRY(launch_apply_drobin(c, L, fi, dalpha_dev, x_dev, out_dev));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return 0;
 }
@@ -5652,6 +5905,14 @@ int mg_time_kernel(mg_handle c, const char* kernel, int level, int reps, double*
             MG_TRY(need_dkappa_level(c, level, "mg_time_kernel", "sigma"));
             MG_TRY(vec_alloc(c, L, &L.v)); MG_TRY(vec_alloc(c, L, &L.f)); MG_TRY(vec_alloc(c, L, &L.v2));
             return k == "dsigma" ? launch_dsigma(c, L, L.v.rows, L.f.rows, L.v2.rows) : launch_apply_dsigma(c, L, L.f.rows, L.v.rows, L.v2.rows);
+        }
+        // the Robin sensitivities of face z+: D(v, f) into MG_VEC_R[:N^2] / T(f[:N^2], v) into MG_VEC_R
+        if (k == "drobin" || k == "apply_drobin") {
+            MG_TRY(need_dkappa_level(c, level, "mg_time_kernel", "Robin"));
+            int fi = -1;
+            MG_TRY(need_drobin_face(c, "mg_time_kernel", MG_FACE_ZHI, &fi));
+            MG_TRY(vec_alloc(c, L, &L.v)); MG_TRY(vec_alloc(c, L, &L.f)); MG_TRY(vec_alloc(c, L, &L.v2));
+            return k == "drobin" ? launch_drobin(c, L, fi, L.v.rows, L.f.rows, L.v2.rows) : launch_apply_drobin(c, L, fi, L.f.rows, L.v.rows, L.v2.rows);
         }
         if (k == "kappa_ingest") {  // the copy and the coarsening in one pass, from a scratch copy of kappa back into the level's own
             if (!L.mf) return fail("level is not a matrix-free diffusion level");

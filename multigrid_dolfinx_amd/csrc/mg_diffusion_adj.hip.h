@@ -142,6 +142,65 @@ __global__ __launch_bounds__(DK_BLOCK) void diffusion_apply_dsigma(DsArgs p) {
     p.out[r] = free_node(p.box, i, j, k) ? react_node(p.a, p.N, i, j, k, p.scale) * p.b[r] : 0.0;
 }
 
+// ---- sensitivities of the lumped Robin term B(alpha) (mg_kernels.hip.h, robin_diag), per face F ------------------------
+// B is diagonal and linear in alpha.  T_alpha,F(w, x)_i = b_F(w)_i x_i on the free nodes of F and +0.0 on every other node
+// of the level (diffusion_apply_drobin), and its adjoint D_alpha,F(a, b)_q = scale * sum_i t_{q,i} a~_i b~_i over the four
+// corners of face-cell q (diffusion_drobin), a~ and b~ taking Dirichlet nodes as 0.  The bits are DEFINED here and restated
+// by poisson.diffusion_drobin / diffusion_apply_drobin:
+//   * D: one accumulator starts with 2.0 * (A * B) of corner (0,0) and takes t * (A * B) of the others in ascending
+//     (db, da), t = 2.0 at (1,1) and 1.0 elsewhere; out = acc * scale with scale = h^2 / 6.0 from the host.
+//   * T: robin_face_node's sum, then one product with x.  No fma: -ffp-contract=off.
+// D reads 8 + 8 B per face node and writes 8 B per face-cell; T writes all n_global nodes (8 B each) and reads x and the
+// field on the face only.
+struct DrArgs {
+    const double* a;        // D: a, T: the direction dalpha ([N][N] face-cells)
+    const double* b;        // D: b (may be a), T: x
+    double* out;            // D: face-cells, T: nodes
+    int nx, nz, N;
+    int axis, at;           // the face: normal to `axis`, at node index `at` (0 or N) along it
+    int64_t P;
+    double scale;           // D: h^2 / 6.0, T: h^2
+    FreeBox box;
+};
+
+__global__ __launch_bounds__(DK_BLOCK) void diffusion_drobin(DrArgs p) {
+    const int64_t t = (int64_t)blockIdx.x * DK_BLOCK + threadIdx.x;
+    if (t >= (int64_t)p.N * p.N) return;
+    const int ca = (int)(t % p.N), cb = (int)(t / p.N);
+    const bool same = p.a == p.b;
+    double s = 0.0;
+#pragma unroll
+    for (int db = 0; db < 2; ++db)
+#pragma unroll
+        for (int da = 0; da < 2; ++da) {
+            const int pa = ca + da, pb = cb + db;
+            const int i = p.axis == 0 ? p.at : pa, j = p.axis == 0 ? pa : (p.axis == 1 ? p.at : pb), k = p.axis == 2 ? p.at : pb;
+            const bool inner = free_node(p.box, i, j, k);
+            const int64_t r = (int64_t)k * p.P + (int64_t)j * p.nx + i;
+            const double A = inner ? p.a[r] : 0.0;
+            const double B = inner ? (same ? A : p.b[r]) : 0.0;
+            const double term = (da == db ? 2.0 : 1.0) * (A * B);
+            s = db + da == 0 ? term : s + term;
+        }
+    p.out[t] = s * p.scale;
+}
+
+// blockIdx.x: DK_BLOCK nodes of a node plane, blockIdx.y: the plane
+__global__ __launch_bounds__(DK_BLOCK) void diffusion_apply_drobin(DrArgs p) {
+    const int64_t t = (int64_t)blockIdx.x * DK_BLOCK + threadIdx.x;
+    if (t >= p.P) return;
+    const int i = (int)(t % p.nx), j = (int)(t / p.nx), k = blockIdx.y;
+    const int64_t r = (int64_t)k * p.P + t;
+    const int c = p.axis == 0 ? i : (p.axis == 1 ? j : k);
+    double o = 0.0;
+    if (c == p.at && free_node(p.box, i, j, k)) {
+        int pa, pb;
+        face_plane(p.axis, i, j, k, pa, pb);
+        o = robin_face_node(p.a, p.N, pa, pb, p.scale) * p.b[r];
+    }
+    p.out[r] = o;
+}
+
 // The plane march, in the shape of diffusion_mf (mg_diffusion_mf.hip.h): a tile of MF_TX x MF_TY cells goes up through the cell
 // planes of a z segment.  The masked images of a and b (tile + one line of nodes in x and y) of node planes k and k + 1 are
 // in LDS, two slots per vector: step k reads plane k + 1 (the corners of plane k stay in registers from the step before),

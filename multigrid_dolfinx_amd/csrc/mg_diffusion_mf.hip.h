@@ -59,6 +59,11 @@
 // Per row and sweep: 8 (x) + 8 (f) + 8 (kappa) + 8 (r) + 8 (out) = 40 B instead of 32, 32 B instead of 24 for the SpMV, 48 B
 // instead of 40 for a Chebyshev step.
 // <..., REACT = false> are the kernels above, untouched: a level without a reaction term launches those.
+//
+// Robin fields (mg_set_diffusion_robin) need no kernel of their own: a level generated with them keeps the nodal
+// B(alpha), or R(sigma) + B(alpha), of robin_diag (mg_kernels.hip.h) as that row vector and runs the REACT kernels as they
+// are.  A variant that formed B of the rows on a field face from the face fields instead of streaming the vector (32 B per
+// row) was measured slower than these and is not kept ("Robin faces").
 #pragma once
 #include "mg_kernels.hip.h"
 

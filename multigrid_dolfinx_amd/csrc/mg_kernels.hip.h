@@ -1507,6 +1507,71 @@ __global__ void sigma_check(const double* __restrict__ sigma, int64_t n, unsigne
     }
 }
 
+// ---- lumped Robin term B(alpha), one alpha per boundary face-cell (mg_set_diffusion_robin) ----------------------------
+// kappa du/dn + alpha (u - u_ext) = 0 on a face outside the Dirichlet set.  A field belongs to one face and holds N^2
+// values, face-cell (ca, cb) at cb * N + ca with (a, b) the two in-plane axes in ascending order (x-faces: (y, z), y-faces:
+// (x, z), z-faces: (x, y)).  The Kuhn split cuts a boundary face-cell along the diagonal from its in-plane (0,0) to its
+// (1,1) corner, so the row-sum lumped P1 boundary mass gives a node of face F
+//     b_F(w)_i = ((sum_q t_q w_q) / 6.0) * h2
+// over the 4 face-cells around it in ascending index (db, da), t = 2.0 where the node is the face-cell's (0,0) or (1,1)
+// corner (da == db), else 1.0; a face-cell outside the face counts as +0.0; h2 = h^2 comes from the host.  One accumulator
+// starts with the first product and takes the other three one by one (-ffp-contract=off).  B(alpha)_i is the sum of b_F
+// over the field faces that contain the node in ascending face-bit order, the first term starting the accumulator; +0.0 on
+// a node on no field face and on every Dirichlet node.  poisson.robin_diag restates it, same bits.
+struct RobinFaces {
+    const double* f[6];     // by face bit (x-, x+, y-, y+, z-, z+): the N^2 face-cells, or null
+};
+
+// the in-plane coordinates of node (i, j, k) on a face normal to `axis`
+__device__ __forceinline__ void face_plane(int axis, int i, int j, int k, int& pa, int& pb) {
+    pa = axis == 0 ? j : i;
+    pb = axis == 2 ? j : k;
+}
+
+__device__ __forceinline__ double robin_face_node(const double* __restrict__ w, int N, int pa, int pb, double h2) {
+    double s = 0.0;
+#pragma unroll
+    for (int db = 0; db < 2; ++db)
+#pragma unroll
+        for (int da = 0; da < 2; ++da) {
+            const int ca = pa - 1 + da, cb = pb - 1 + db;
+            const bool in = ca >= 0 && ca < N && cb >= 0 && cb < N;
+            const double v = in ? w[cb * N + ca] : 0.0;        // (N^2 < 2^31 on any grid whose N^3 cells fit a device)
+            const double t = (da == db ? 2.0 : 1.0) * v;
+            s = db + da == 0 ? t : s + t;
+        }
+    return (s / 6.0) * h2;
+}
+
+__device__ __forceinline__ double robin_node(const RobinFaces& rf, const FreeBox& box, int N, int i, int j, int k, double h2) {
+    if (!free_node(box, i, j, k)) return 0.0;
+    double B = 0.0;         // (+0.0 + b is b to the bit: alpha >= 0 makes every b >= +0.0, so the first term starts the sum)
+#pragma unroll
+    for (int axis = 0; axis < 3; ++axis) {      // (a node lies on at most one face per axis: ascending face-bit order)
+        const int c = axis == 0 ? i : (axis == 1 ? j : k);
+        const double* const w = c == 0 ? rf.f[2 * axis] : (c == N ? rf.f[2 * axis + 1] : nullptr);
+        if (w == nullptr) continue;
+        int pa, pb;
+        face_plane(axis, i, j, k, pa, pb);
+        const double b = robin_face_node(w, N, pa, pb, h2);
+        B = B + b;
+    }
+    return B;
+}
+
+// blockIdx.x: RD_BLOCK nodes of a node plane, blockIdx.y: the plane, as reaction_diag.  add: out holds R(sigma) and becomes
+// R(sigma) + B(alpha), formed as that sum; otherwise out = B(alpha) on every node.  A set-up kernel: every node of the
+// level is visited although the term lives on O(N^2) of them (8 B per node written, and read with add).
+__global__ __launch_bounds__(RD_BLOCK) void robin_diag(RobinFaces rf, FreeBox box, double* __restrict__ out, int N, double h2, int add) {
+    const int n1 = N + 1;
+    const int64_t t = (int64_t)blockIdx.x * RD_BLOCK + threadIdx.x;
+    if (t >= (int64_t)n1 * n1) return;
+    const int i = (int)(t % n1), j = (int)(t / n1), k = blockIdx.y;
+    const int64_t r = (int64_t)k * n1 * n1 + t;
+    const double B = robin_node(rf, box, N, i, j, k, h2);
+    out[r] = add ? out[r] + B : B;
+}
+
 // Set-up check of a kappa field: the lowest index (plus `base`) of an entry that is not a positive finite double, by an
 // atomic minimum into *first (the caller sets it to ~0 first).
 __global__ void kappa_check(const double* __restrict__ kappa, int64_t n, int64_t base, unsigned long long* first) {

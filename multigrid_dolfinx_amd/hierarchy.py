@@ -17,6 +17,7 @@ import scipy.sparse as sp
 from . import _capi
 from ._capi import (MG_RESTRICT_FULL_WEIGHTING, MG_RESTRICT_INJECTION, MG_VEC_ERR, MG_VEC_F, MG_VEC_R,
                     MG_VEC_V, check, load, ptr)
+from . import poisson
 from .poisson import face_set, grid_index_from_coords
 
 __all__ = ["DeviceHierarchy", "jacobi_split", "csr_check"]
@@ -446,6 +447,42 @@ class DeviceHierarchy:
         check(self._lib.mg_level_reaction(self._h, self._idx(level), C.byref(on)))
         return bool(on.value)
 
+    def set_diffusion_robin(self, face, alpha, N: Optional[int] = None):
+        """The Robin field of one face for the diffusion levels generated from now on (`mg_set_diffusion_robin`): the
+        condition kappa du/dn + alpha (u - u_ext) = 0 there, with the lumped diagonal of `poisson.robin_diag`.  `face`: a
+        name ("z+") or one bit of the face set.  `alpha`: one finite value >= 0 per boundary face-cell of the level it is
+        meant for (the top level of a hierarchy call), face-cell (ca, cb) at `cb * N + ca` with (a, b) the in-plane axes in
+        ascending order, as a NumPy array -- its size gives the cells per dimension unless `N` does -- or as an integer
+        device address with `N=` (`mg_set_diffusion_robin_device`).  The handle keeps its own copy.  None clears the face's
+        field.  3-D, whole handles."""
+        bit = poisson._one_face(face)
+        if alpha is None:
+            check(self._lib.mg_set_diffusion_robin(self._h, 0, bit, None))
+            return
+        if isinstance(alpha, (int, np.integer)):
+            if N is None:
+                raise TypeError("a device address needs N=, the cells per dimension of the field")
+            check(self._lib.mg_set_diffusion_robin_device(self._h, int(N), bit, C.c_void_p(int(alpha))))
+            return
+        a = np.ascontiguousarray(np.asarray(alpha, dtype=np.float64).reshape(-1))
+        n = int(round(a.size ** 0.5)) if N is None else int(N)
+        if n * n != a.size:
+            raise ValueError(f"alpha has {a.size} entries, which is not {n}^2 face-cells")
+        check(self._lib.mg_set_diffusion_robin(self._h, n, bit, ptr(a)))
+
+    def diffusion_robin(self):
+        """(faces, cells per dimension) of the handle's Robin fields (`mg_diffusion_robin`): the bits of the faces that hold
+        one; (0, 0) without any."""
+        faces, n = C.c_int(0), C.c_int(0)
+        check(self._lib.mg_diffusion_robin(self._h, C.byref(faces), C.byref(n)))
+        return int(faces.value), int(n.value)
+
+    def level_robin(self, level: int) -> int:
+        """The faces whose Robin field the level was generated with, as bits (`mg_level_robin`); 0: none."""
+        faces = C.c_int(0)
+        check(self._lib.mg_level_robin(self._h, self._idx(level), C.byref(faces)))
+        return int(faces.value)
+
     def level_matrix_free(self, level: int) -> bool:
         """True if the level keeps kappa instead of a matrix (`mg_level_matrix_free`)."""
         on = C.c_int(0)
@@ -782,6 +819,26 @@ class DeviceHierarchy:
         entry = lambda ps, px, po: self._lib.mg_diffusion_apply_dsigma(self._h, self._idx(level), ps, px, po)
         n = self.n_dofs(level)
         return self._sigma_entry(entry, "dsigma and x", dsigma, self.elements(level) ** 3, x, n, out, n)
+
+    def diffusion_drobin(self, level: int, face, a, b, out=None):
+        """D_alpha,F(a, b): d(a^T B(alpha) b) / d alpha for every boundary face-cell of `face` on a 3-D grid level
+        (`mg_diffusion_drobin`; host restatement: `poisson.diffusion_drobin`, same bits).  `a`, `b` (lexicographic nodal
+        values, entries on the Dirichlet nodes of the handle's face set count as 0) and `out` (`elements(level) ** 2`
+        face-cells): device addresses or NumPy arrays, as in `diffusion_dsigma`."""
+        bit = poisson._one_face(face)
+        entry = lambda pa, pb, po: self._lib.mg_diffusion_drobin(self._h, self._idx(level), bit, pa, pb, po)
+        n = self.n_dofs(level)
+        return self._sigma_entry(entry, "a and b", a, n, b, n, out, self.elements(level) ** 2)
+
+    def diffusion_apply_drobin(self, level: int, face, dalpha, x, out=None):
+        """T_alpha,F(dalpha, x) = b_F(dalpha) x on the free nodes of `face`, 0 on every other node
+        (`mg_diffusion_apply_drobin`; host restatement: `poisson.diffusion_apply_drobin`, same bits).  `dalpha`
+        (`elements(level) ** 2` face-cells, any sign), `x` and `out` (lexicographic nodal values): device addresses or NumPy
+        arrays, as in `diffusion_apply_dsigma`."""
+        bit = poisson._one_face(face)
+        entry = lambda pw, px, po: self._lib.mg_diffusion_apply_drobin(self._h, self._idx(level), bit, pw, px, po)
+        n = self.n_dofs(level)
+        return self._sigma_entry(entry, "dalpha and x", dalpha, self.elements(level) ** 2, x, n, out, n)
 
     def zero_vector(self, level: int, which: str = "v"):
         check(self._lib.mg_zero_vector(self._h, self._idx(level), _VEC[which]))

@@ -641,7 +641,146 @@ def reaction_diag(N: int, w, dirichlet_faces=ALL_FACES) -> np.ndarray:
     return np.where(dirichlet_mask(N, dirichlet_faces), 0.0, r)
 
 
-def diffusion_level(N: int, dim: int, kappa, keep_zeros: bool = True, dirichlet_faces=ALL_FACES, sigma=None) -> Level:
+def _one_face(face) -> int:
+    """One face of the cube as its bit, from the bit or the name."""
+    bit = FACE_BITS.get(face) if isinstance(face, str) else (int(face) if isinstance(face, (int, np.integer)) else None)
+    if bit not in FACE_BITS.values():
+        raise ValueError(f"{face!r} is not one face: the faces are " + ", ".join(f"{k} = {v}" for k, v in FACE_BITS.items()))
+    return bit
+
+
+def _robin_fields(N: int, robin, dirichlet_faces=None, signed: bool = False) -> dict:
+    """`robin` (face name or bit -> N^2 values) as {bit: (N, N) array [cb][ca]} in ascending bit order, checked."""
+    out = {}
+    for face, alpha in robin.items():
+        bit = _one_face(face)
+        if bit in out:
+            raise ValueError(f"face {bit} is given twice")
+        if alpha is None:
+            continue
+        al = _kappa_cells(alpha, N, 2)
+        if not signed and (not np.all(np.isfinite(al)) or np.any(al < 0.0)):
+            raise ValueError("alpha must be finite and not negative")
+        if dirichlet_faces is not None and face_set(dirichlet_faces) & bit:
+            raise ValueError(f"face {bit} is a Dirichlet face of the set {face_set(dirichlet_faces)}: it cannot hold a Robin field")
+        out[bit] = al
+    return dict(sorted(out.items()))
+
+
+def _face_cells_around_nodes(w, N: int) -> np.ndarray:
+    """((sum over the 4 face-cells around an in-plane node, ascending (db, da), of t w) / 6.0) * h^2 on the (N + 1)^2 nodes
+    [pb][pa] of a face: t = 2 where the node is the face-cell's in-plane (0,0) or (1,1) corner (da == db), else 1; a
+    face-cell outside the face counts as +0.0; added one by one."""
+    n1 = N + 1
+    wp = np.pad(w, 1, constant_values=0.0)
+    s = None
+    for db in (0, 1):
+        for da in (0, 1):
+            t = (2.0 if da == db else 1.0) * wp[db:db + n1, da:da + n1]
+            s = t if s is None else s + t
+    h = 1.0 / N
+    return (s / 6.0) * h ** 2
+
+
+def _on_face(field2d, N: int, bit: int) -> np.ndarray:
+    """The (N + 1)^3 nodal array [k][j][i] that holds `field2d` ([pb][pa], in-plane axes ascending) on the face and +0.0
+    elsewhere."""
+    n1 = N + 1
+    out = np.zeros((n1, n1, n1))
+    axis, side = (bit.bit_length() - 1) // 2, (bit.bit_length() - 1) % 2
+    at = N if side else 0
+    if axis == 0:
+        out[:, :, at] = field2d
+    elif axis == 1:
+        out[:, at, :] = field2d
+    else:
+        out[at, :, :] = field2d
+    return out
+
+
+def _face_plane(nodal, N: int, bit: int) -> np.ndarray:
+    """The (N + 1)^2 values [pb][pa] of a nodal vector on a face."""
+    n1 = N + 1
+    v = nodal.reshape(n1, n1, n1)
+    axis, side = (bit.bit_length() - 1) // 2, (bit.bit_length() - 1) % 2
+    at = N if side else 0
+    return v[:, :, at] if axis == 0 else (v[:, at, :] if axis == 1 else v[at, :, :])
+
+
+def robin_diag(N: int, robin, dirichlet_faces=ALL_FACES) -> np.ndarray:
+    """B(alpha): the diagonal of the lumped Robin term kappa du/dn + alpha (u - u_ext) = 0 on the (N + 1)^3 nodes, as the
+    device computes it (`robin_diag`, mg_kernels.hip.h; same bits).  `robin` maps a face (name or bit) to its N^2 values
+    alpha >= 0, face-cell (ca, cb) at `cb * N + ca` with (a, b) the two in-plane axes in ascending order.  The Kuhn split
+    cuts a boundary face-cell along the diagonal from its in-plane (0,0) to its (1,1) corner; the row-sum lumped P1 boundary
+    mass gives, per face F,
+        b_F(alpha)_i = ((sum over the 4 face-cells around node i, ascending (db, da), of t alpha_q) / 6.0) * h^2,
+    t = 2 at the (0,0) and (1,1) corners, else 1, a face-cell outside the face counting as +0.0, added one by one.  B is the
+    sum of b_F over the faces that contain the node in ascending face-bit order, the first term starting the accumulator;
+    +0.0 on every node on no field face and on every Dirichlet node of `dirichlet_faces`.  A face of the Dirichlet set cannot
+    hold a field."""
+    fields = _robin_fields(N, robin, dirichlet_faces)
+    n1 = N + 1
+    B = np.zeros((n1, n1, n1))
+    for bit, al in fields.items():          # (+0.0 + b is b: every term is >= +0.0)
+        B = B + _on_face(_face_cells_around_nodes(al, N), N, bit)
+    return np.where(dirichlet_mask(N, dirichlet_faces), 0.0, B.reshape(-1))
+
+
+def coarsen_robin(robin):
+    """The Robin fields of the coarse level (N / 2 face-cells per dimension) as the diffusion hierarchy calls compute them:
+    the arithmetic mean of the 2 x 2 children in `coarsen_kappa`'s 2-D order, whatever the kappa averaging (boundary mass is
+    additive).  Takes one field or a mapping of faces to fields and returns the same kind."""
+    if isinstance(robin, dict):
+        return {face: None if alpha is None else coarsen_kappa(alpha, 2, "arithmetic") for face, alpha in robin.items()}
+    return coarsen_kappa(robin, 2, "arithmetic")
+
+
+def diffusion_drobin(N: int, face, a, b, dirichlet_faces=ALL_FACES) -> np.ndarray:
+    """D_alpha,F(a, b): d(a^T B(alpha) b) / d alpha_q for the N^2 face-cells of `face`, as `mg_diffusion_drobin` computes it
+    (same bits).  With A~, B~ the values of `a`, `b` at a face-cell's corners (db, da), Dirichlet nodes of `dirichlet_faces`
+    taken as 0: t * (A~ * B~) with t = 2 at (0,0) and (1,1) and 1 elsewhere, added one by one in ascending (db, da), times
+    h^2 / 6.0.  The adjoint of `diffusion_apply_drobin`: a . T(w, x) = w . D(a, x)."""
+    bit = _one_face(face)
+    if face_set(dirichlet_faces) & bit:
+        raise ValueError(f"face {bit} is a Dirichlet face of the set {face_set(dirichlet_faces)}")
+    n1 = N + 1
+    free = ~dirichlet_mask(N, dirichlet_faces)
+
+    def corners(x):
+        v = np.array(x, dtype=np.float64).reshape(-1)
+        if v.size != n1 ** 3:
+            raise ValueError(f"vector has {v.size} entries, the level has {n1 ** 3} nodes")
+        m = _face_plane(np.where(free, v, 0.0), N, bit)
+        return [[m[db:db + N, da:da + N] for da in (0, 1)] for db in (0, 1)]
+
+    A, Bc = corners(a), corners(b)
+    s = None
+    for db in (0, 1):
+        for da in (0, 1):
+            t = (2.0 if da == db else 1.0) * (A[db][da] * Bc[db][da])
+            s = t if s is None else s + t
+    h = 1.0 / N
+    return np.ascontiguousarray((s * (h ** 2 / 6.0)).reshape(-1))
+
+
+def diffusion_apply_drobin(N: int, face, dalpha, x, dirichlet_faces=ALL_FACES) -> np.ndarray:
+    """T_alpha,F(dalpha, x)_i = b_F(dalpha)_i x_i on the free nodes of `face`, +0.0 on every other node, as
+    `mg_diffusion_apply_drobin` computes it (same bits: `robin_diag`'s face sum, then one product).  `dalpha`: N^2 values of
+    any sign.  With dalpha = alpha and x = u_ext it is the ambient load alpha u_ext int phi_i that the caller adds to f."""
+    bit = _one_face(face)
+    if face_set(dirichlet_faces) & bit:
+        raise ValueError(f"face {bit} is a Dirichlet face of the set {face_set(dirichlet_faces)}")
+    n1 = N + 1
+    v = np.array(x, dtype=np.float64).reshape(-1)
+    if v.size != n1 ** 3:
+        raise ValueError(f"vector has {v.size} entries, the level has {n1 ** 3} nodes")
+    w = _kappa_cells(dalpha, N, 2)
+    bF = _on_face(_face_cells_around_nodes(w, N), N, bit).reshape(-1)
+    on = _on_face(np.ones((n1, n1)), N, bit).reshape(-1) > 0.0
+    return np.where(on & ~dirichlet_mask(N, dirichlet_faces), bF * v, 0.0)
+
+
+def diffusion_level(N: int, dim: int, kappa, keep_zeros: bool = True, dirichlet_faces=ALL_FACES, sigma=None, robin=None) -> Level:
     """The level `mg_gen_diffusion_level` generates, assembled on the host in the kernel's operation order (same bits), in
     the hand-off conventions of `lexicographic_level`.  `kappa` holds one positive value per cell: cube (ci, cj, ck) at
     `(ck * N + cj) * N + ci`, square (ci, cy) at `cy * N + ci`.  On the Kuhn mesh the P1 stiffness of -div(kappa grad u)
@@ -660,6 +799,12 @@ def diffusion_level(N: int, dim: int, kappa, keep_zeros: bool = True, dirichlet_
     `sigma` (3-D; `mg_set_diffusion_reaction`): one finite value >= 0 per cell, the operator A(kappa) + R(sigma).  A free row's
     diagonal is the stiffness diagonal above plus `reaction_diag(N, sigma)` of its node, one more addition; identity rows, the
     off-diagonals, the lifted right-hand side and the load do not change.  None, the default, is the level above byte for
+    byte.
+
+    `robin` (3-D; `mg_set_diffusion_robin`): a mapping of faces outside the Dirichlet set to N^2 values alpha >= 0 each, the
+    condition kappa du/dn + alpha (u - u_ext) = 0 there.  A free row's diagonal gets one nodal term by one more addition:
+    `robin_diag(N, robin)` of its node, or `reaction_diag + robin_diag`, formed as that sum, with a `sigma`.  Nothing else
+    changes; the ambient load is the caller's (`diffusion_apply_drobin`).  None, the default, is the level above byte for
     byte."""
     faces = face_set(dirichlet_faces)
     if faces != ALL_FACES and dim != 3:
@@ -670,6 +815,8 @@ def diffusion_level(N: int, dim: int, kappa, keep_zeros: bool = True, dirichlet_
         sig = _kappa_cells(sigma, N, 3)
         if not np.all(np.isfinite(sig)) or np.any(sig < 0.0):
             raise ValueError("sigma must be finite and not negative")
+    if robin is not None and dim != 3:
+        raise ValueError("Robin faces are 3-D only")
     kap = _kappa_cells(kappa, N, dim)
     if np.any(~(kap > 0.0)) or not np.all(np.isfinite(kap)):
         raise ValueError("kappa must be positive and finite")
@@ -680,7 +827,10 @@ def diffusion_level(N: int, dim: int, kappa, keep_zeros: bool = True, dirichlet_
     if dim == 3:
         se, t = _edge_sums_3d(kp, n1)
         diag = (t / 6.0) * h
-        if sigma is not None:
+        if robin is not None and _robin_fields(N, robin, faces):
+            B = robin_diag(N, robin, faces)
+            diag = diag + (reaction_diag(N, sig, faces) + B if sigma is not None else B)
+        elif sigma is not None:
             diag = diag + reaction_diag(N, sig, faces)
         weight = lambda s: (s / 6.0) * h
     else:

@@ -18,7 +18,7 @@ import numpy as np
 import torch
 
 from .hierarchy import DeviceHierarchy
-from .poisson import ALL_FACES, dirichlet_mask, face_set
+from .poisson import ALL_FACES, _one_face, dirichlet_mask, face_set
 
 __all__ = ["DiffusionSolver", "NotConverged"]
 
@@ -96,8 +96,19 @@ class DiffusionSolver:
     the reverse, generates the hierarchy again instead of refreshing it (`last_generate`).
 
     `solve(..., same_operator=True)` solves on the operator of the last `solve` without touching the hierarchy, as `tangent`
-    does: the caller asserts that kappa and sigma hold the values of that solve (the steps of a time march with a constant
-    dt).  Gradients with respect to them still flow.  `n_generations` counts the generations and refreshes."""
+    does: the caller asserts that kappa, sigma and the Robin fields hold the values of that solve (the steps of a time march
+    with a constant dt).  Gradients with respect to them still flow.  `n_generations` counts the generations and refreshes.
+
+    `robin` (`solve`, `tangent`): a mapping of faces outside `dirichlet_faces` (names "x-" .. "z+" or bits) to N^2 float64
+    alpha >= 0, one per boundary face-cell (face-cell (ca, cb) at cb * N + ca, (a, b) the in-plane axes in ascending order),
+    on the solver's device or the CPU, each a differentiable input.  Those faces carry kappa du/dn + alpha (u - u_ext) = 0
+    instead of the no-flux condition: the operator gains the lumped boundary diagonal B(alpha) of `poisson.robin_diag`
+    (`DeviceHierarchy.set_diffusion_robin`), and the ambient load alpha u_ext int phi_i is `robin_apply`(face, alpha, u_ext),
+    which the caller adds to `f`.  grad_alpha_F = -D_alpha,F(lambda, u) comes from the one adjoint solve; the lift of `g`
+    involves no alpha.  D_alpha and T_alpha close under differentiation, so `create_graph=True` gives the kappa-alpha,
+    alpha-kappa and alpha-alpha blocks of a Hessian-vector product in the same number of solves.  The operator of a solve
+    keeps the fields beside kappa and sigma; changing WHICH faces hold a field generates the hierarchy again instead of
+    refreshing it (`last_generate`)."""
 
     def __init__(self, N: int, n_levels: int, averaging: str = "arithmetic", matrix_free_min_rows: Optional[int] = None,
                  rtol: float = 1e-10, max_iter: int = 200, device: int = 0, warm_start: bool = False, dirichlet_faces=None,
@@ -121,6 +132,7 @@ class DiffusionSolver:
         self._generation = 0
         self._generated = False         # a hierarchy call has generated the levels: a device kappa can refresh them
         self._generated_react = False   # ... with a reaction field: a refresh needs the same state
+        self._generated_robin = ()      # ... and with Robin fields on these faces (bits)
         self.last_generate = None       # "host" / "device" / "refresh": how the last kappa reached the hierarchy
         self.warm_start = bool(warm_start)
         self._warm = {}                 # "forward" / "adjoint": the last solution of that kind (warm_start)
@@ -145,8 +157,27 @@ class DiffusionSolver:
         """Hierarchy generations and refreshes so far: what a march with `same_operator=True` saves."""
         return self._generation
 
+    def _robin_inputs(self, robin, what: str = "robin"):
+        """(bits, tensors) of a mapping of faces to N^2 float64 tensors, in ascending bit order; ((), ()) for None."""
+        if not robin:
+            return (), ()
+        fields = {}
+        for face, alpha in robin.items():
+            bit = _one_face(face)
+            if bit in fields:
+                raise ValueError(f"{what}: face {bit} is given twice")
+            if bit & self.dirichlet_faces:
+                raise ValueError(f"{what}: face {bit} is a Dirichlet face of this solver (dirichlet_faces = {self.dirichlet_faces})")
+            if alpha.dtype != torch.float64 or alpha.numel() != self.N ** 2:
+                raise ValueError(f"{what}: the field of face {bit} must hold {self.N ** 2} float64")
+            fields[bit] = alpha
+        bits = tuple(sorted(fields))
+        return bits, tuple(fields[b] for b in bits)
+
     def solve(self, kappa: torch.Tensor, f: torch.Tensor, g: Optional[torch.Tensor] = None,
-              sigma: Optional[torch.Tensor] = None, same_operator: bool = False) -> torch.Tensor:
+              sigma: Optional[torch.Tensor] = None, same_operator: bool = False, robin=None) -> torch.Tensor:
+        bits, alphas = self._robin_inputs(robin)
+        rest = (sigma,) if not bits else (sigma, bits) + alphas     # (what _Solve takes after `warm`)
         op = None
         if same_operator:
             op = self._last_operator
@@ -154,16 +185,27 @@ class DiffusionSolver:
                 raise ValueError("same_operator=True reuses the operator of the last solve: there has been none")
             if (sigma is None) != (op.sigma_kept is None):
                 raise ValueError("same_operator=True: the last solve had " + ("no" if sigma is not None else "a") + " sigma")
+            if bits != tuple(sorted(op.robin_kept)):
+                raise ValueError(f"same_operator=True: the last solve had Robin fields on the faces {sorted(op.robin_kept)}")
         if g is None:
-            return _Solve.apply(kappa, f, self, op, "forward", True, sigma)
+            return _Solve.apply(kappa, f, self, op, "forward", True, *rest)
         boundary = self._boundary_mask()
         gv, fv = self._same_size(g, "g").reshape(-1), self._same_size(f, "f").reshape(-1)
         g_b = torch.where(boundary, gv, torch.zeros_like(gv))
         if op is None:
-            op = self._put_operator(kappa, sigma)   # first: the lift runs on the level's grid, which the first generation sets
+            op = self._put_operator(kappa, sigma, dict(zip(bits, alphas)))  # first: the lift runs on the level's grid, which the first generation sets
         lift = _Tangent.apply(kappa.reshape(-1).to(self.device), g_b, self, "interior", "all")
         rhs = torch.where(boundary, gv, fv - lift)
-        return _Solve.apply(kappa, rhs.view(f.shape), self, op, "forward", True, sigma)
+        return _Solve.apply(kappa, rhs.view(f.shape), self, op, "forward", True, *rest)
+
+    def robin_apply(self, face, w: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
+        """T_alpha,F(w, x) = b_F(w) x on the free nodes of `face`, 0 on every other node (`mg_diffusion_apply_drobin`),
+        differentiable in both: with w = alpha and x = u_ext the ambient load of a Robin face.  `w`: N^2 float64 of any sign,
+        on the solver's device or the CPU; `x`: (N + 1)^3 float64 on the solver's device."""
+        if not self._generated and not self._grid_only:     # the kernel reads the top level's grid and nothing else
+            self.hierarchy.set_level_grid(self.top)
+            self._grid_only = True
+        return _TRobin.apply(w.reshape(-1).to(self.device), x.reshape(-1), self, _one_face(face)).view(x.shape)
 
     def reaction_apply(self, w: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
         """T_sigma(w, x) = R(w) x on the free nodes, 0 on the Dirichlet nodes (`mg_diffusion_apply_dsigma`), differentiable in
@@ -176,7 +218,7 @@ class DiffusionSolver:
 
     def tangent(self, kappa: torch.Tensor, f: torch.Tensor, dkappa: torch.Tensor, df: Optional[torch.Tensor] = None,
                 g: Optional[torch.Tensor] = None, dg: Optional[torch.Tensor] = None, sigma: Optional[torch.Tensor] = None,
-                dsigma: Optional[torch.Tensor] = None):
+                dsigma: Optional[torch.Tensor] = None, robin=None, drobin=None):
         """(u, du): u = A(kappa)^-1 f and its derivative in the direction (dkappa, df),
         du = A^-1 (df - (dA/dkappa . dkappa) u), on the same operator: two solves, one generation.  The cheap derivative
         when kappa depends on a few parameters.  `kappa` as in `solve`; `f`, `dkappa` (N^3 float64, any sign) and `df`
@@ -185,12 +227,18 @@ class DiffusionSolver:
         the second right-hand side are df - T(dkappa, u; interior, all) - T(kappa, dg_B; interior, all), u with its boundary
         values g, and du = dg on the boundary.
         With `sigma` as in `solve` and its direction `dsigma` (None: zero; N^3 float64 of any sign on the solver's device) the
-        operator is A(kappa) + R(sigma) and the second right-hand side loses T_sigma(dsigma, u) on the free rows."""
+        operator is A(kappa) + R(sigma) and the second right-hand side loses T_sigma(dsigma, u) on the free rows.
+        With `robin` as in `solve` and its directions `drobin` (a mapping of some of those faces to N^2 float64 of any sign on
+        the solver's device) it loses T_alpha,F(drobin[F], u) too."""
         if g is None and dg is not None:
             raise ValueError("dg is the direction of g: it needs g")
         if sigma is None and dsigma is not None:
             raise ValueError("dsigma is the direction of sigma: it needs sigma")
-        u = self.solve(kappa, f, g, sigma)
+        bits, alphas = self._robin_inputs(robin)
+        dbits, dalphas = self._robin_inputs(drobin, "drobin")
+        if set(dbits) - set(bits):
+            raise ValueError("drobin holds the directions of robin: it needs a field on each of its faces")
+        u = self.solve(kappa, f, g, sigma, robin=robin)
         if g is None:
             rhs = _Tangent.apply(dkappa.reshape(-1), u.reshape(-1), self, "interior", "interior").neg()
             if df is not None:
@@ -207,16 +255,34 @@ class DiffusionSolver:
                 rhs = rhs - _Tangent.apply(kappa.detach().reshape(-1).to(self.device), dg_b, self, "interior", "all")
             if dsigma is not None:
                 rhs = rhs - _TSigma.apply(dsigma.reshape(-1), u.reshape(-1), self)
+            for bit, dalpha in zip(dbits, dalphas):
+                rhs = rhs - _TRobin.apply(dalpha.reshape(-1), u.reshape(-1), self, bit)
             rhs = torch.where(boundary, on_boundary, rhs)
         if g is None and dsigma is not None:
             rhs = rhs - _TSigma.apply(dsigma.reshape(-1), u.reshape(-1), self)
-        du = _Solve.apply(kappa, rhs, self, self._last_operator, "tangent", True, sigma)
+        if g is None:
+            for bit, dalpha in zip(dbits, dalphas):
+                rhs = rhs - _TRobin.apply(dalpha.reshape(-1), u.reshape(-1), self, bit)
+        rest = (sigma,) if not bits else (sigma, bits) + alphas
+        du = _Solve.apply(kappa, rhs, self, self._last_operator, "tangent", True, *rest)
         return u, du.view(u.shape)
 
     # ---- what the autograd function calls --------------------------------------------------------------------
-    def _generate(self, kappa, sigma=None) -> int:
+    def _generate(self, kappa, sigma=None, robin=None) -> int:
         """`kappa`: a host array (today's path) or a contiguous float64 tensor on the solver's device; `sigma`: None, or the
-        reaction field as one of the two.  The handle's field is set (or cleared) first: the generating calls read it."""
+        reaction field as one of the two; `robin`: None, or the Robin fields by face bit, each as one of the two.  The
+        handle's fields are set (or cleared) first: the generating calls read them."""
+        robin = robin or {}
+        for bit in sorted(set(robin) | set(self._generated_robin)):
+            alpha = robin.get(bit)
+            if alpha is None or isinstance(alpha, np.ndarray):
+                self.hierarchy.set_diffusion_robin(bit, alpha)
+            else:
+                torch.cuda.current_stream(self.device).synchronize()
+                self.hierarchy.set_diffusion_robin(bit, alpha.data_ptr(), N=self.N)
+        if tuple(sorted(robin)) != self._generated_robin:   # levels with fields on other faces do not refresh into each other
+            self._generated = False
+        self._generated_robin = tuple(sorted(robin))
         react = sigma is not None
         if react or self._generated_react:
             if sigma is None or isinstance(sigma, np.ndarray):
@@ -251,8 +317,9 @@ class DiffusionSolver:
             self._boundary = torch.from_numpy(dirichlet_mask(self.N, self.dirichlet_faces)).to(self.device)
         return self._boundary
 
-    def _put_operator(self, kappa: torch.Tensor, sigma: Optional[torch.Tensor] = None) -> "_Operator":
-        """Puts the caller's kappa (and sigma) into the hierarchy: the operator of a `solve` and of what derives from it."""
+    def _put_operator(self, kappa: torch.Tensor, sigma: Optional[torch.Tensor] = None, robin=None) -> "_Operator":
+        """Puts the caller's kappa (and sigma, and the Robin fields by face bit) into the hierarchy: the operator of a
+        `solve` and of what derives from it."""
         if kappa.dtype != torch.float64 or kappa.numel() != self.N ** 3:
             raise ValueError(f"kappa must hold {self.N ** 3} float64")
         if sigma is not None and (sigma.dtype != torch.float64 or sigma.numel() != self.N ** 3):
@@ -266,7 +333,8 @@ class DiffusionSolver:
             return np.ascontiguousarray(x.detach().cpu().numpy().reshape(-1))
 
         kappa_kept, sigma_kept = kept(kappa), kept(sigma)
-        op = _Operator(kappa_kept, self._generate(kappa_kept, sigma_kept), sigma_kept)
+        robin_kept = {bit: kept(alpha) for bit, alpha in (robin or {}).items()}
+        op = _Operator(kappa_kept, self._generate(kappa_kept, sigma_kept, robin_kept), sigma_kept, robin_kept)
         self._last_operator = op
         return op
 
@@ -305,12 +373,13 @@ class DiffusionSolver:
 
 
 class _Operator:
-    """The kappa (and the sigma, or None) of one `solve` as the library takes them (a host array or a device copy) and the
-    generation of the hierarchy that holds them: what the solves nested in that solve's backward passes share, so that they neither upload
+    """The kappa (and the sigma, or None, and the Robin fields by face bit) of one `solve` as the library takes them (a host
+    array or a device copy) and the generation of the hierarchy that holds them: what the solves nested in that solve's backward passes share, so that they neither upload
     nor regenerate an operator that is still in place."""
 
-    def __init__(self, kappa_kept, generation, sigma_kept=None):
+    def __init__(self, kappa_kept, generation, sigma_kept=None, robin_kept=None):
         self.kappa_kept, self.generation, self.sigma_kept = kappa_kept, generation, sigma_kept
+        self.robin_kept = robin_kept or {}
 
 
 class _Solve(torch.autograd.Function):
@@ -318,16 +387,19 @@ class _Solve(torch.autograd.Function):
     on the operator of an earlier one (from a backward pass, or `tangent`); `kappa` is then only what the gradient is
     taken with respect to (None: nobody asked), and the hierarchy is touched only if another kappa has been solved since.
     An optional seventh argument is sigma: the operator is A(kappa) + R(sigma), and sigma is to the reaction term what kappa
-    is to the stiffness -- on a given `op`, only what the gradient is taken with respect to."""
+    is to the stiffness -- on a given `op`, only what the gradient is taken with respect to.  After sigma (None: no reaction
+    term) may come the Robin fields: the tuple of their face bits, ascending, then one alpha per face -- the operator is
+    A(kappa) + R(sigma) + B(alpha), and each alpha is to its face what sigma is to the reaction term."""
 
     @staticmethod
     def forward(ctx, kappa, f, solver, op, which, warm, *rest):
         sigma = rest[0] if rest else None
         rhs = solver._device_vector(f, "f" if op is None else "the right-hand side")
+        bits, alphas = (rest[1], rest[2:]) if len(rest) > 1 else ((), ())
         if op is None:
-            op = solver._put_operator(kappa, sigma)
+            op = solver._put_operator(kappa, sigma, dict(zip(bits, alphas)))
         elif op.generation != solver._generation:       # another kappa has been solved since: this one's operator again
-            op.generation = solver._generate(op.kappa_kept, op.sigma_kept)
+            op.generation = solver._generate(op.kappa_kept, op.sigma_kept, op.robin_kept)
         u = solver._pcg(rhs, which, warm).view(f.shape)
         ctx.solver, ctx.op = solver, op
         ctx.kappa_like = None if kappa is None else (kappa.shape, kappa.device)
@@ -337,6 +409,9 @@ class _Solve(torch.autograd.Function):
         ctx.n_rest = len(rest)
         ctx.sigma_like = None if sigma is None else (sigma.shape, sigma.device)
         ctx.sigma = sigma if rest and ctx.needs_input_grad[6] else None     # (as kappa: never for its values)
+        ctx.bits = bits
+        ctx.alpha_like = [None if a is None else (a.shape, a.device) for a in alphas]
+        ctx.alphas = [a if a is not None and ctx.needs_input_grad[8 + q] else None for q, a in enumerate(alphas)]
         ctx.save_for_backward(u)
         return u
 
@@ -347,7 +422,8 @@ class _Solve(torch.autograd.Function):
         # one mg_pcg and one sensitivity kernel.
         solver = ctx.solver
         kappa, (u,) = ctx.kappa, ctx.saved_tensors
-        lam = _Solve.apply(kappa, grad_u, solver, ctx.op, "adjoint", not torch.is_grad_enabled(), *([ctx.sigma] * ctx.n_rest))
+        rest = [ctx.sigma] * min(ctx.n_rest, 1) + ([ctx.bits] + ctx.alphas if ctx.n_rest > 1 else [])
+        lam = _Solve.apply(kappa, grad_u, solver, ctx.op, "adjoint", not torch.is_grad_enabled(), *rest)
         grad_kappa = None
         if ctx.needs_input_grad[0]:
             shape, device = ctx.kappa_like
@@ -359,7 +435,12 @@ class _Solve(torch.autograd.Function):
         if ctx.sigma is not None:
             shape, device = ctx.sigma_like
             grad_sigma = _DSigma.apply(lam, u, solver).neg().view(shape).to(device)
-        return grad_kappa, grad_f, None, None, None, None, grad_sigma
+        if ctx.n_rest == 1:
+            return grad_kappa, grad_f, None, None, None, None, grad_sigma
+        grad_alphas = []
+        for bit, alpha, like in zip(ctx.bits, ctx.alphas, ctx.alpha_like):
+            grad_alphas.append(None if alpha is None else _DRobin.apply(lam, u, solver, bit).neg().view(like[0]).to(like[1]))
+        return (grad_kappa, grad_f, None, None, None, None, grad_sigma, None, *grad_alphas)
 
 
 class _DKappa(torch.autograd.Function):
@@ -454,3 +535,49 @@ class _TSigma(torch.autograd.Function):
         grad_w = _DSigma.apply(y, x, ctx.solver).view(w.shape) if ctx.needs_input_grad[0] else None
         grad_x = _TSigma.apply(w, y, ctx.solver).view(x.shape) if ctx.needs_input_grad[1] else None
         return grad_w, grad_x, None
+
+
+class _DRobin(torch.autograd.Function):
+    """D_alpha,F(a, b) = mg_diffusion_drobin(a, b) of the face with bit `bit`, N^2 face-cells; the entries of a and b on the
+    Dirichlet nodes count as 0.  With cotangent w: a_bar = T_alpha,F(w, b), b_bar = T_alpha,F(w, a)."""
+
+    @staticmethod
+    def forward(ctx, a, b, solver, bit):
+        av, bv = solver._device_vector(a, "a"), solver._device_vector(b, "b")
+        out = torch.empty(solver.N ** 2, dtype=torch.float64, device=solver.device)
+        torch.cuda.current_stream(solver.device).synchronize()
+        solver.hierarchy.diffusion_drobin(solver.top, bit, av.data_ptr(), bv.data_ptr(), out.data_ptr())
+        ctx.solver, ctx.bit = solver, bit
+        ctx.save_for_backward(a, b)
+        return out
+
+    @staticmethod
+    def backward(ctx, w):
+        a, b = ctx.saved_tensors
+        grad_a = _TRobin.apply(w, b, ctx.solver, ctx.bit).view(a.shape) if ctx.needs_input_grad[0] else None
+        grad_b = _TRobin.apply(w, a, ctx.solver, ctx.bit).view(b.shape) if ctx.needs_input_grad[1] else None
+        return grad_a, grad_b, None, None
+
+
+class _TRobin(torch.autograd.Function):
+    """T_alpha,F(w, x) = b_F(w) x = mg_diffusion_apply_drobin(w, x) on the free nodes of the face with bit `bit`, 0 on every
+    other node, (N + 1)^3 nodes.  With cotangent y: w_bar = D_alpha,F(y, x), x_bar = T_alpha,F(w, y) (B is diagonal)."""
+
+    @staticmethod
+    def forward(ctx, w, x, solver, bit):
+        if w.dtype != torch.float64 or w.device != solver.device or w.numel() != solver.N ** 2:
+            raise ValueError(f"the alpha direction must hold {solver.N ** 2} float64 on {solver.device}")
+        wv, xv = w.detach().contiguous(), solver._device_vector(x, "x")
+        out = torch.empty(xv.numel(), dtype=torch.float64, device=solver.device)
+        torch.cuda.current_stream(solver.device).synchronize()
+        solver.hierarchy.diffusion_apply_drobin(solver.top, bit, wv.data_ptr(), xv.data_ptr(), out.data_ptr())
+        ctx.solver, ctx.bit = solver, bit
+        ctx.save_for_backward(w, x)
+        return out
+
+    @staticmethod
+    def backward(ctx, y):
+        w, x = ctx.saved_tensors
+        grad_w = _DRobin.apply(y, x, ctx.solver, ctx.bit).view(w.shape) if ctx.needs_input_grad[0] else None
+        grad_x = _TRobin.apply(w, y, ctx.solver, ctx.bit).view(x.shape) if ctx.needs_input_grad[1] else None
+        return grad_w, grad_x, None, None
