@@ -650,6 +650,9 @@ int mg_galerkin_hierarchy(mg_handle h, int top_level);
  *     "cls_blocks_per_cu"  persistent blocks per CU of the one-sweep class kernels (4)
  *     "coarse_direct"      exact block-tridiagonal coarsest solve, 0 = PCG (1)
  *     "pcg_chunk"          PCG iterations enqueued between convergence checks (16)
+ *     "mf_batch"           batched solves (mg_apply_batch, mg_pcg_batch): the most lanes one fused launch of the matrix-free march
+ *                          takes, 0..4; 0 or 1 = never fuse, every lane runs the one-vector kernel (4; DESIGN.md, "Batched
+ *                          solves"); bit-identical whatever the value
  *     "lattice_march"      wide lattice stencils (3-D P2 levels with stencil classes) as a plane march with five planes of x in
  *                          LDS instead of gathers from global memory (1); bit-identical either way
  *     "lattice_march_min_rows"  ... only on levels with at least this many owned rows (4194304)
@@ -779,6 +782,53 @@ int mg_fmg_ex(mg_handle h, int top_level, int mu0, double tol, int max_cycles, i
  * downloads do not change).  Slabs: every dot product is all-reduced.  No reference counterpart (the reference solves
  * with V-cycles / FMG only). */
 int mg_pcg(mg_handle h, int level, double rtol, int max_iter, double* resid_hist, int* iterations);
+
+/* ---- batched solves: one operator, several right-hand sides (no reference counterpart) ----------------------------------------
+ * A "lane" is one right-hand side with everything a solve and its V-cycle write: MG_VEC_V, its ping-pong partner (MG_VEC_R),
+ * MG_VEC_F and MG_VEC_ERR of every level up to the call's, mg_pcg's four work vectors, its scalars and partial sums.  Lane 0 is
+ * the handle's own set; lanes 1 .. nb - 1 are allocated by the first batch call that needs them, counted by mg_memory_bytes,
+ * kept for later calls with the same or a smaller nb (and by mg_refresh_diffusion_hierarchy), and freed by mg_release_batch, by
+ * mg_destroy and whenever a level of the hierarchy is set again with another size.  A handle that never calls a batch entry
+ * allocates and launches exactly what it did without them.
+ *
+ * Every operation of the solve and of its V-cycle is done for all active lanes before the next operation starts.  On a
+ * matrix-free diffusion level the Jacobi sweeps, the residual and the SpMV with its dot product take the active lanes in ascending
+ * order in groups of at most "mf_batch" lanes, ONE launch per group: the march rebuilds each row from kappa once and applies it to
+ * every vector of the group (diffusion_mf_batch, mg_diffusion_mf_batch.hip.h), with the level's own plan, so every double and every
+ * partial sum has the bits of the one-vector kernel.  A group of one runs that kernel.  Everything else -- stored levels, the
+ * transfers, the coarsest solve, mg_pcg's vector kernels and folds, a Chebyshev smoother -- runs once per lane with the one-vector
+ * code.  Batched cycles run eagerly (no capture, no replay; eager and replayed cycles agree to the bit).  A fused launch counts
+ * under MG_PATH_MATRIX_FREE as 1 launch and as many sweeps as it has lanes: sweeps / launches shows the fusion.
+ *
+ * Pointer arrays are HOST arrays of nb DEVICE pointers, each to the level's n_global doubles in the numbering of
+ * mg_set_vector_device.  After a batch call the levels, the factorisation, the Chebyshev intervals, the cached graphs and the
+ * tuning are as before, and a following mg_pcg gives the bits it gives on a handle that never ran a batch; the handle's own
+ * MG_VEC_V, MG_VEC_F and MG_VEC_R are UNSPECIFIED (they were lane 0's).  Refused by name before anything is launched or
+ * allocated: nb outside 1..MG_BATCH_MAX, null arrays or pointers, a pointer that is not device memory of the handle's device, an
+ * output that overlaps another lane's output or any input (its own included: the march reads neighbours), slab handles, 2-D
+ * handles, flat levels; mg_pcg_batch also level 0, a Gauss-Seidel smoother with a matrix-free level in the cycle, and whatever
+ * mg_pcg refuses (face-set and transfer mismatches, levels without a matrix).
+ *
+ * mg_apply_batch  out_b = one Jacobi sweep of x_b with the handle's omega (MG_BATCH_JACOBI; the handle's smoother must be
+ *                 Jacobi), f_b - A x_b (MG_BATCH_RESIDUAL) or A x_b (MG_BATCH_SPMV; f_dev is ignored and may be null), for
+ *                 b = 0 .. nb - 1 on a stored or matrix-free level: the bits of mg_smooth(level, 1), mg_residual and the SpMV of
+ *                 mg_pcg / mg_quadratic_form on MG_VEC_V = x_b, MG_VEC_F = f_b.  dots (SpMV only, may be null): dots[b] =
+ *                 x_b . A x_b on the host, the bits of mg_quadratic_form.
+ * mg_pcg_batch    lane b's x_dev[b] (the initial guess on entry, the solution on return), resid_hist[b * max(1, max_iter) + k]
+ *                 and iterations[b] are, bit for bit, those of mg_set_vector_device(F = f_b), mg_set_vector_device(V = x_b),
+ *                 mg_pcg(level, rtol, max_iter), mg_get_vector_device(V) on the same handle, for any nb and any mix of lanes.
+ *                 The lanes run in lockstep, each with its own alpha, beta, dots and stopping test; a lane that has stopped
+ *                 leaves the batch and its x is not touched again.  resid_hist and iterations may be null.
+ * mg_batch_info   lanes held beyond the handle's own (0 until a call with nb >= 2) and their device bytes
+ * mg_release_batch  frees them */
+#define MG_BATCH_MAX 32
+enum mg_batch_op { MG_BATCH_JACOBI = 0, MG_BATCH_RESIDUAL = 1, MG_BATCH_SPMV = 2 };
+int mg_apply_batch(mg_handle h, int level, int op, int nb, const double* const* x_dev, const double* const* f_dev,
+                   double* const* out_dev, double* dots /* [nb] or NULL */);
+int mg_pcg_batch(mg_handle h, int level, int nb, const double* const* f_dev, double* const* x_dev, double rtol, int max_iter,
+                 double* resid_hist /* [nb][max(1, max_iter)] */, int* iterations /* [nb] */);
+int mg_batch_info(mg_handle h, int* lanes, int64_t* bytes);
+int mg_release_batch(mg_handle h);
 /* Bookkeeping for tests: whole-vector host -> device / device -> host copies made through this handle so far,
  * V-cycles replayed from a captured hipGraph, graphs currently cached.  No reference counterpart. */
 int mg_counters(mg_handle h, int64_t* uploads, int64_t* downloads, int64_t* graph_replays, int* graphs_cached);
@@ -837,7 +887,9 @@ int mg_reset_smoother_launches(mg_handle h);
  * error where z+ is a Dirichlet face of the handle's set);
  * "kappa_ingest" = one launch of the fused copy and coarsening of mg_gen_diffusion_hierarchy_device on a matrix-free level, from a
  * scratch copy of its kappa back into the level's own (the same bytes: the level is unchanged) and into a scratch coarse field,
- * arithmetic averaging; an error on stored levels).
+ * arithmetic averaging; an error on stored levels);
+ * "diffusion_mf_batch<NV>:jacobi", ":residual", ":spmv" (NV = 2, 3, 4) = one fused launch of the matrix-free march over NV vectors
+ * (mg_apply_batch, mg_pcg_batch): MG_VEC_V, MG_VEC_F, MG_VEC_R and scratch copies of them; an error on stored levels.
  * Used by bench.py for the roofline figure; its launches leave mg_smoother_launches as they were.  mg_sync waits for
  * the handle's stream. */
 int mg_time_kernel(mg_handle h, const char* kernel, int level, int reps, double* avg_ms);

@@ -20,6 +20,8 @@ MG_SMOOTH_JACOBI, MG_SMOOTH_RBGS, MG_SMOOTH_MCGS, MG_SMOOTH_CHEBYSHEV = 0, 1, 2,
 MG_NORM_L2, MG_NORM_MASS = 0, 1
 MG_KAPPA_ARITHMETIC, MG_KAPPA_HARMONIC = 0, 1
 MG_NODES_INTERIOR, MG_NODES_ALL = 0, 1
+MG_BATCH_MAX = 32
+MG_BATCH_JACOBI, MG_BATCH_RESIDUAL, MG_BATCH_SPMV = 0, 1, 2
 # enum mg_smoother_path, in its order (mg_smoother_launches)
 SMOOTHER_PATHS = ("slice", "sweep1c", "pair_class", "pair_plain", "ksweep", "ksweep_escape", "ksweep_slab", "block", "k2d",
                   "small", "matrix_free")
@@ -116,6 +118,10 @@ SIGNATURES = {
     "mg_set_exact": [_H, C.c_int, C.c_void_p],
     "mg_fmg_ex": [_H, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_void_p, _ip],
     "mg_pcg": [_H, C.c_int, C.c_double, C.c_int, C.c_void_p, _ip],
+    "mg_apply_batch": [_H, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    "mg_pcg_batch": [_H, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.c_void_p, C.c_void_p],
+    "mg_batch_info": [_H, _ip, _i64p],
+    "mg_release_batch": [_H],
     "mg_counters": [_H, _i64p, _i64p, _i64p, _ip],
     "mg_smoother_launches": [_H, C.c_int, C.c_int, _i64p, _i64p, _i64p],
     "mg_reset_smoother_launches": [_H],

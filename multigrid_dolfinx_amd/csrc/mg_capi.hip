@@ -10,6 +10,7 @@
 #include "mg_jacobiblk.hip.h"
 #include "mg_lattice.hip.h"
 #include "mg_diffusion_mf.hip.h"
+#include "mg_diffusion_mf_batch.hip.h"
 #include "mg_diffusion_adj.hip.h"
 #include "mg_diffusion_kappa.hip.h"
 
@@ -228,6 +229,17 @@ struct DirectSolver {
     DevBuf<double> y, x, w;
 };
 
+// One lane of a batched solve (mg_pcg_batch, mg_apply_batch): the per-level vectors a solve and its V-cycle write -- V, its
+// ping-pong partner (= R), F, ERR and mg_pcg's four work vectors -- and mg_pcg's scalars and partial sums.  A lane is swapped
+// into the levels (and the handle) around every call that runs per lane; lane 0 is the handle's own set.
+struct LaneLevel {
+    DVector v, v2, f, err, fcg_x, fcg_p, fcg_q, fcg_b;
+};
+struct Lane {
+    std::vector<LaneLevel> lv;              // by level
+    DevBuf<double> fcg_work, fcg_spmv;
+};
+
 // One captured V-cycle (hipGraph): valid for a level, a parameter epoch and a ping-pong state.
 struct CycleGraph {
     int level = -1;
@@ -284,7 +296,13 @@ struct mg_context {
     // mg_pcg: scalars, folded / slab-reduced sums and the step kernels' partial sums (fcg_work); the
     // SpMV's partial sums of p.q (fcg_spmv: one per block of the level's SpMV, grown on demand)
     DevBuf<double> fcg_work, fcg_spmv;
-    int use_graph = 1;              // replay whole V-cycles as hipGraphs (single GPU, direct coarsest solve)
+    // batched solves: lanes 1, 2, ... (lane 0 is the handle's own vectors), allocated at the first batch call that needs them and
+    // kept until mg_release_batch, mg_destroy or a level set again with another size; "mf_batch": the most lanes one fused
+    // launch of the matrix-free march takes (0 / 1: never fuse; DESIGN.md, "Batched solves")
+    std::vector<Lane> lanes;
+    int mf_batch = 4;
+    double* h_lanes = nullptr;      // pinned, MG_BATCH_MAX doubles: every lane's ||r||^2 of an iteration in one host round trip (first mg_pcg_batch)
+    int use_graph = 1;             // replay whole V-cycles as hipGraphs (single GPU, direct coarsest solve)
     int comm_priority = 1;          // communication stream created with the highest priority (MG_COMM_PRIORITY=0: lowest)
     int lattice_march = 1;          // wide lattice stencils (P2 levels) as a plane march with x in LDS (mg_lattice.hip.h)
     int64_t lattice_march_min_rows = 1 << 22;       // (measured on C5: the 129^3 and 65^3 lattices are faster with the gathering kernel)
@@ -465,7 +483,20 @@ int need_grid(mg_context* c, int level) {
 // ---- slab geometry ---------------------------------------------------------------------------
 // Plane boundaries on the coarsest grid t_g = floor(g*N0/G) (t_G = N0+1); level l uses
 // t_g * 2^l, so coarse plane K and fine plane 2K always live on the same rank.
+int setup_geometry_sized(mg_context* c, Level& L, int level, int N, int64_t flat_rows);
+
 int setup_geometry(mg_context* c, Level& L, int level, int N, int64_t flat_rows = 0) {
+    MG_TRY(setup_geometry_sized(c, L, level, N, flat_rows));
+    // the lanes of batched solves hold vectors of the levels' sizes: a level that is set again with another size frees them all
+    for (const Lane& lane : c->lanes)
+        if ((size_t)level < lane.lv.size() && lane.lv[(size_t)level].v.raw && (int64_t)lane.lv[(size_t)level].v.raw.count() != vec_total(L)) {
+            c->lanes.clear();
+            break;
+        }
+    return 0;
+}
+
+int setup_geometry_sized(mg_context* c, Level& L, int level, int N, int64_t flat_rows) {
     const int dim = c->dim;
     const Comm& cm = c->comm;
     Grid& g = L.g;
@@ -992,6 +1023,42 @@ int launch_diffusion_mf(mg_context* c, const Level& L, int mode, bool dot, const
         else hipLaunchKernelGGL((diffusion_mf<MODE, decltype(d)::value>), grid, blk, 0, c->stream, a);
     });
     if (!known) return fail("matrix-free diffusion levels have no kernel for this mode");
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// The same march over nv = 2 .. MF_BATCH_MAX vectors in one launch (mg_diffusion_mf_batch.hip.h): the level's plan, the row
+// rebuilt once per node.  Jacobi, residual and SpMV (with or without the partial sums, one array of the plan's grid per vector).
+int launch_diffusion_mf_batch(mg_context* c, const Level& L, int mode, bool dot, int nv, const double* const* x_rows,
+                              const double* const* f_rows, double* const* out_rows, double* const* partials) {
+    if (mode != MODE_JACOBI && mode != MODE_RESIDUAL && mode != MODE_SPMV)
+        return fail("the batched matrix-free march runs Jacobi, residual and SpMV launches only");
+    const MfPlan p = mf_plan(c, L);
+    const dim3 grid(p.grid), blk(MF_NT);
+    const bool known = with_int<2, 3, 4>(nv, [&](auto n) {
+        constexpr int NV = decltype(n)::value;
+        MfBatchArgs<NV> ba{};
+        ba.a = mf_args(p, L, L.kappa, nullptr, nullptr);
+        ba.a.omega = c->omega;
+        ba.box = level_box(L, L.faces);
+        ba.r = L.rdiag;
+        for (int v = 0; v < NV; ++v) {
+            ba.x[v] = x_rows[v]; ba.f[v] = f_rows ? f_rows[v] : nullptr; ba.out[v] = out_rows[v];
+            ba.partials[v] = partials ? partials[v] : nullptr;
+        }
+        with_mode(mode, dot, [&](auto m, auto d) {
+            constexpr int MODE = decltype(m)::value;
+            constexpr bool DOT = decltype(d)::value;
+            if constexpr (MODE == MODE_JACOBI || MODE == MODE_RESIDUAL || MODE == MODE_SPMV)
+                with_bool(L.faces != MG_FACES_ALL, [&](auto fc) {
+                    with_bool(L.rdiag.get() != nullptr, [&](auto re) {
+                        hipLaunchKernelGGL((diffusion_mf_batch<NV, MODE, DOT, decltype(fc)::value, decltype(re)::value>), grid, blk, 0,
+                                           c->stream, ba);
+                    });
+                });
+        });
+    });
+    if (!known) return fail("the batched matrix-free march takes 2.." + std::to_string(MF_BATCH_MAX) + " vectors per launch");
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -3349,6 +3416,378 @@ int fcg_solve(mg_context* c, int level, double rtol, int max_iter, double* hist,
     return 0;
 }
 
+// ---- batched solves: one operator, several right-hand sides (mg_apply_batch, mg_pcg_batch) ----------------------------------
+// Every operation of a solve and of its V-cycle is done for all active lanes before the next one starts.  On a matrix-free level
+// the Jacobi sweeps, the residual and the SpMV take the active lanes in ascending order in groups of at most "mf_batch", one
+// fused launch per group (a group of one: the one-vector kernel); everything else -- stored levels, transfers, the coarsest solve,
+// the fcg_* kernels and folds, a Chebyshev smoother -- runs once per lane with the one-vector code, the lane's vectors swapped
+// into the levels around the call.  Cycles run eagerly (no capture, no replay): eager and replayed cycles agree to the bit.
+
+void swap_lane(mg_context* c, Lane& lane, int lo, int top) {
+    for (int l = lo; l <= top; ++l) {
+        Level& L = c->L[l];
+        LaneLevel& v = lane.lv[(size_t)l];
+        std::swap(L.v, v.v); std::swap(L.v2, v.v2); std::swap(L.f, v.f); std::swap(L.err, v.err);
+        std::swap(L.fcg_x, v.fcg_x); std::swap(L.fcg_p, v.fcg_p); std::swap(L.fcg_q, v.fcg_q); std::swap(L.fcg_b, v.fcg_b);
+    }
+    std::swap(c->fcg_work, lane.fcg_work);
+    std::swap(c->fcg_spmv, lane.fcg_spmv);
+}
+
+int64_t lane_bytes(const Lane& lane) {
+    size_t n = lane.fcg_work.count() + lane.fcg_spmv.count();
+    for (const LaneLevel& v : lane.lv)
+        for (const DVector* d : {&v.v, &v.v2, &v.f, &v.err, &v.fcg_x, &v.fcg_p, &v.fcg_q, &v.fcg_b}) n += d->raw.count();
+    return (int64_t)(n * sizeof(double));
+}
+
+// lanes 1 .. nb - 1 with V, its partner and F on levels lo .. top (what a level's set-up gives the handle's own lane); the
+// rest is allocated where the one-vector code allocates it, with the lane swapped in
+int ensure_lanes(mg_context* c, int nb, int lo, int top) {
+    if ((int)c->lanes.size() < nb - 1) c->lanes.resize((size_t)(nb - 1));
+    for (int b = 0; b < nb - 1; ++b) {
+        Lane& lane = c->lanes[(size_t)b];
+        lane.lv.resize((size_t)c->nlev);
+        for (int l = lo; l <= top; ++l) {
+            LaneLevel& v = lane.lv[(size_t)l];
+            MG_TRY(vec_alloc(c, c->L[l], &v.v));
+            MG_TRY(vec_alloc(c, c->L[l], &v.v2));
+            MG_TRY(vec_alloc(c, c->L[l], &v.f));
+        }
+    }
+    return 0;
+}
+
+// The lanes of one batch call.  While it lives the handle's own vectors of levels lo .. top are lane 0's record and the levels
+// hold the lane that is entered (none: empty vectors); its end puts the handle's own back, whatever happened in between.
+struct BatchScope {
+    mg_context* c;
+    int lo, top, in = -1;
+    Lane own;
+    std::vector<Lane*> lane;
+    BatchScope(mg_context* c_, int lo_, int top_, int nb) : c(c_), lo(lo_), top(top_) {
+        own.lv.resize((size_t)c->nlev);
+        swap_lane(c, own, lo, top);
+        lane.push_back(&own);
+        for (int b = 1; b < nb; ++b) lane.push_back(&c->lanes[(size_t)(b - 1)]);
+    }
+    BatchScope(const BatchScope&) = delete;
+    BatchScope& operator=(const BatchScope&) = delete;
+    ~BatchScope() {
+        if (in >= 0) leave();
+        swap_lane(c, own, lo, top);
+    }
+    void enter(int b) { swap_lane(c, *lane[(size_t)b], lo, top); in = b; }
+    void leave() { swap_lane(c, *lane[(size_t)in], lo, top); in = -1; }
+    LaneLevel& at(int b, int level) { return lane[(size_t)b]->lv[(size_t)level]; }
+    // f(b) with lane b's vectors in the levels, for every lane of `act` in ascending order
+    template <class F>
+    int each(const std::vector<int>& act, F&& f) {
+        for (int b : act) {
+            enter(b);
+            const int rc = f(b);
+            leave();
+            MG_TRY(rc);
+        }
+        return 0;
+    }
+};
+
+inline bool mf_fused(const mg_context* c, const Level& L, size_t lanes) { return L.mf && c->mf_batch >= 2 && lanes >= 2; }
+
+// One launch of the march per group of at most "mf_batch" lanes of `act`.  ops(b, &x_rows, &f_rows, &out_rows, &partials) names
+// lane b's operands; single(b) runs the one-vector kernel for a group of one (lane b entered); after(b, nv) follows the launch for
+// each of its lanes, nv = the lanes of the launch for the first of them and 0 for the others (so a launch is counted once).
+template <class Ops, class Single, class After>
+int mf_groups(mg_context* c, BatchScope& s, const Level& L, int mode, bool dot, const std::vector<int>& act, Ops&& ops, Single&& single,
+              After&& after) {
+    const size_t most = (size_t)std::min(c->mf_batch, MF_BATCH_MAX);
+    for (size_t g0 = 0; g0 < act.size(); g0 += most) {
+        const int nv = (int)std::min(most, act.size() - g0);
+        if (nv == 1) {
+            const int b = act[g0];
+            s.enter(b);
+            const int rc = single(b);
+            s.leave();
+            MG_TRY(rc);
+            after(b, 1);
+            continue;
+        }
+        const double *x[MF_BATCH_MAX] = {}, *f[MF_BATCH_MAX] = {};
+        double *out[MF_BATCH_MAX] = {}, *parts[MF_BATCH_MAX] = {};
+        for (int v = 0; v < nv; ++v) ops(act[g0 + (size_t)v], &x[v], &f[v], &out[v], &parts[v]);
+        MG_TRY(launch_diffusion_mf_batch(c, L, mode, dot, nv, x, f, out, parts));
+        for (int v = 0; v < nv; ++v) after(act[g0 + (size_t)v], v == 0 ? nv : 0);
+    }
+    return 0;
+}
+
+// nw smoother sweeps of every lane of `act` on `level`
+int smooth_batch(mg_context* c, BatchScope& s, int level, int nw, const std::vector<int>& act) {
+    Level& L = c->L[level];
+    if (!(mf_fused(c, L, act.size()) && c->smoother == MG_SMOOTH_JACOBI)) return s.each(act, [&](int) { return smooth(c, level, nw); });
+    for (int sw = 0; sw < nw; ++sw)
+        MG_TRY(mf_groups(c, s, L, MODE_JACOBI, false, act,
+            [&](int b, const double** x, const double** f, double** out, double**) {
+                LaneLevel& v = s.at(b, level);
+                *x = v.v.base + L.g.lead; *f = v.f.rows; *out = v.v2.rows;
+            },
+            [&](int) { return smooth_matrix_free(c, level, 1); },
+            [&](int b, int nv) {
+                if (nv > 1) count_pass(c, level, MG_PATH_MATRIX_FREE, 1, nv);      // one launch, a sweep of each of its lanes
+                if (nv != 1) std::swap(s.at(b, level).v, s.at(b, level).v2);       // (a group of one swapped its own)
+            }));
+    return 0;
+}
+
+// R = F - A V of every lane of `act` on `level`
+int residual_batch(mg_context* c, BatchScope& s, int level, const std::vector<int>& act) {
+    Level& L = c->L[level];
+    if (!mf_fused(c, L, act.size())) return s.each(act, [&](int) { return residual(c, level); });
+    return mf_groups(c, s, L, MODE_RESIDUAL, false, act,
+        [&](int b, const double** x, const double** f, double** out, double**) {
+            LaneLevel& v = s.at(b, level);
+            *x = v.v.base + L.g.lead; *f = v.f.rows; *out = v.v2.rows;
+        },
+        [&](int) { return residual(c, level); }, [](int, int) {});
+}
+
+// vcycle() for every lane of `act`, operation by operation
+int vcycle_batch(mg_context* c, BatchScope& s, int level, const std::vector<int>& act) {
+    if (level == 0) return s.each(act, [&](int) { return coarse_solve(c, nullptr, nullptr); });
+    Level& C = c->L[level - 1];
+    MG_TRY(smooth_batch(c, s, level, c->mu1, act));
+    if (c->restriction == MG_RESTRICT_INJECTION && c->fuse_restrict && !c->L[level].mf) {
+        MG_TRY(s.each(act, [&](int) { return residual_restrict_fused(c, level); }));
+    } else {
+        MG_TRY(residual_batch(c, s, level, act));
+        MG_TRY(s.each(act, [&](int) { return restrict_to(c, level, c->restriction); }));
+    }
+    MG_TRY(s.each(act, [&](int) { return zero_vec(c, C, C.v); }));
+    MG_TRY(vcycle_batch(c, s, level - 1, act));
+    MG_TRY(s.each(act, [&](int) { return prolong(c, level, 1); }));
+    MG_TRY(smooth_batch(c, s, level, c->mu2, act));
+    return 0;
+}
+
+// fcg_solve() for nb lanes in lockstep: every lane has its own alpha, beta, dots and stopping test, and a lane that has stopped
+// leaves the batch.  On entry lane b's V and F of `level` hold its start and right-hand side; on return V = x, F = b, R = F - A x
+// as fcg_solve leaves them.  hist: nb rows of `stride` entries.
+int fcg_solve_batch(mg_context* c, BatchScope& s, int level, int nb, double rtol, int max_iter, double* hist, int stride, int* iters_out) {
+    Level& L = c->L[level];
+    struct LaneState {
+        FcgArgs a{};
+        FcgWork w{};
+        double tol = 0.0;
+        int it = 0;
+    };
+    std::vector<LaneState> st((size_t)nb);
+    std::vector<int> all((size_t)nb), act;
+    for (int b = 0; b < nb; ++b) all[(size_t)b] = b;
+    const int64_t gmax = 4 * std::max(1, c->prop.multiProcessorCount);
+    const int64_t nspmv = L.mf ? (int64_t)mf_plan(c, L).grid : (int64_t)blocks_for(L.nslices, WAVES_PER_BLOCK);
+    const size_t bytes = (size_t)L.xlen * sizeof(double);
+    const dim3 grid(fcg_grid(c, L)), blk(BLOCK);
+    if (!c->h_lanes) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&c->h_lanes), MG_BATCH_MAX * sizeof(double), hipHostMallocDefault));
+
+    // x = V, b = F, r = F - A x (in F)
+    MG_TRY(s.each(all, [&](int b) -> int {
+        LaneState& t = st[(size_t)b];
+        MG_TRY(prepare_cycle(c, level));
+        MG_TRY(vec_alloc(c, L, &L.fcg_x));
+        MG_TRY(vec_alloc(c, L, &L.fcg_p));
+        MG_TRY(vec_alloc(c, L, &L.fcg_q));
+        MG_TRY(vec_alloc(c, L, &L.fcg_b));
+        if (!c->fcg_work) MG_TRY(c->fcg_work.alloc(c, (size_t)(8 + kFcgFold + 3 * gmax)));
+        if ((int64_t)c->fcg_spmv.count() < nspmv) MG_TRY(c->fcg_spmv.alloc(c, (size_t)nspmv));
+        t.w = fcg_work(c);
+        HIP_TRY(hipMemcpyAsync(L.fcg_b.base, L.f.base, bytes, hipMemcpyDeviceToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(L.fcg_x.base, L.v.base, bytes, hipMemcpyDeviceToDevice, c->stream));
+        return 0;
+    }));
+    auto first_residual = [&](int) {
+        return launch_ell(c, L, {.mode = MODE_RESIDUAL, .x_base = L.fcg_x.base, .f_rows = L.fcg_b.rows, .out_rows = L.f.rows});
+    };
+    if (mf_fused(c, L, all.size())) {
+        MG_TRY(mf_groups(c, s, L, MODE_RESIDUAL, false, all,
+            [&](int b, const double** x, const double** f, double** out, double**) {
+                LaneLevel& v = s.at(b, level);
+                *x = v.fcg_x.base + L.g.lead; *f = v.fcg_b.rows; *out = v.f.rows;
+            },
+            first_residual, [](int, int) {}));
+    } else {
+        MG_TRY(s.each(all, first_residual));
+    }
+    MG_TRY(s.each(all, [&](int b) -> int {
+        LaneState& t = st[(size_t)b];
+        double bnorm = 0.0, rnorm = 0.0;
+        MG_TRY(norm2(c, L, L.fcg_b.rows, &bnorm));
+        MG_TRY(norm2(c, L, L.f.rows, &rnorm));
+        t.tol = rtol > 0.0 ? rtol * bnorm : -1.0;
+        FcgArgs& a = t.a;
+        a.x = L.fcg_x.rows; a.r = L.f.rows; a.p = L.fcg_p.rows; a.q = L.fcg_q.rows; a.sc = t.w.sc; a.n = L.nloc;
+        for (const double* v : {(const double*)a.x, (const double*)a.r, (const double*)a.p, a.q})
+            if (reinterpret_cast<uintptr_t>(v) % 16) return fail("mg_pcg_batch: misaligned work vector");
+        if (max_iter > 0 && rnorm > t.tol && rnorm > 0.0) act.push_back(b);
+        return 0;
+    }));
+
+    // z = one V-cycle from a zero guess on r, for every active lane (fcg_precondition)
+    auto precondition = [&](bool v_zeroed) -> int {
+        if (!v_zeroed) MG_TRY(s.each(act, [&](int) { return zero_vec(c, L, L.v); }));
+        MG_TRY(vcycle_batch(c, s, level, act));
+        for (int b : act) {
+            st[(size_t)b].a.z = s.at(b, level).v.rows;
+            if (reinterpret_cast<uintptr_t>(st[(size_t)b].a.z) % 16) return fail("mg_pcg_batch: misaligned iterate");
+        }
+        return 0;
+    };
+    if (!act.empty()) {
+        MG_TRY(precondition(false));
+        MG_TRY(s.each(act, [&](int b) -> int {
+            LaneState& t = st[(size_t)b];
+            t.a.out = t.w.part_dots;
+            hipLaunchKernelGGL(fcg_dots<false>, grid, blk, 0, c->stream, t.a);
+            hipLaunchKernelGGL(fcg_direction<true>, grid, blk, 0, c->stream, t.a);
+            const double* dots = t.w.part_dots;
+            int64_t nd = grid.x;
+            MG_TRY(fcg_sums(c, L, dots, nd, 2, INT64_MAX, nullptr, t.w.tot_dots));
+            t.a.dots = dots; t.a.nd = (int)nd;
+            return 0;
+        }));
+    }
+    while (!act.empty()) {
+        // q = A p with the partial sums of p.q
+        auto spmv_one = [&](int) -> int {
+            unsigned nsp = 0;
+            MG_TRY(launch_ell(c, L, {.mode = MODE_SPMV, .dot = true, .x_base = L.fcg_p.base, .out_rows = L.fcg_q.rows, .partials = c->fcg_spmv,
+                                     .grid_out = &nsp}));
+            if ((size_t)nsp > c->fcg_spmv.count()) return fail("mg_pcg_batch: SpMV partial sums overflow");
+            return 0;
+        };
+        if (mf_fused(c, L, act.size())) {
+            MG_TRY(mf_groups(c, s, L, MODE_SPMV, true, act,
+                [&](int b, const double** x, const double**, double** out, double** parts) {
+                    LaneLevel& v = s.at(b, level);
+                    *x = v.fcg_p.base + L.g.lead; *out = v.fcg_q.rows; *parts = s.lane[(size_t)b]->fcg_spmv;
+                },
+                spmv_one, [](int, int) {}));
+        } else {
+            MG_TRY(s.each(act, spmv_one));
+        }
+        // alpha, x += alpha p, r -= alpha q; every lane's ||r||^2 to the host in one round trip; who goes on
+        std::vector<int> next;
+        bool v_zeroed = false;
+        MG_TRY(s.each(act, [&](int b) -> int {
+            LaneState& t = st[(size_t)b];
+            const double* pq = c->fcg_spmv;
+            int64_t npq = nspmv;
+            MG_TRY(fcg_sums(c, L, pq, npq, 1, kFcgFold, t.w.fold_pq, t.w.tot_pq));
+            t.a.pq = pq; t.a.npq = (int)npq;
+            t.a.out = t.w.part_rr;
+            t.a.vz = L.g.lead == 0 && L.xlen == L.nloc ? L.v.rows : nullptr;
+            v_zeroed = t.a.vz != nullptr;
+            hipLaunchKernelGGL(fcg_update, grid, blk, 0, c->stream, t.a);
+            hipLaunchKernelGGL(fcg_fold, dim3(1), blk, 0, c->stream, t.w.part_rr, (int64_t)grid.x, 1, t.w.tot_rr);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipMemcpyAsync(c->h_lanes + b, t.w.tot_rr, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+            return 0;
+        }));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        for (int b : act) {
+            LaneState& t = st[(size_t)b];
+            const double rn = std::sqrt(c->h_lanes[b]);
+            if (hist) hist[(size_t)b * (size_t)stride + (size_t)t.it] = rn;
+            ++t.it;
+            if (!(rn <= t.tol || rn == 0.0 || t.it >= max_iter)) next.push_back(b);
+        }
+        act = next;
+        if (act.empty()) break;
+        // z = M r; r.z and z.q; p = z + beta p
+        MG_TRY(precondition(v_zeroed));
+        MG_TRY(s.each(act, [&](int b) -> int {
+            LaneState& t = st[(size_t)b];
+            t.a.out = t.w.part_dots;
+            hipLaunchKernelGGL(fcg_dots<true>, grid, blk, 0, c->stream, t.a);
+            const double* dots = t.w.part_dots;
+            int64_t nd = grid.x;
+            MG_TRY(fcg_sums(c, L, dots, nd, 2, INT64_MAX, nullptr, t.w.tot_dots));
+            t.a.dots = dots; t.a.nd = (int)nd;
+            hipLaunchKernelGGL(fcg_direction<false>, grid, blk, 0, c->stream, t.a);
+            HIP_TRY(hipGetLastError());
+            return 0;
+        }));
+    }
+    // V = x, F = b bit for bit, R = F - A x
+    MG_TRY(s.each(all, [&](int b) -> int {
+        HIP_TRY(hipMemcpyAsync(L.v.base, L.fcg_x.base, bytes, hipMemcpyDeviceToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(L.f.base, L.fcg_b.base, bytes, hipMemcpyDeviceToDevice, c->stream));
+        if (iters_out) iters_out[b] = st[(size_t)b].it;
+        return 0;
+    }));
+    MG_TRY(residual_batch(c, s, level, all));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// the permute kernels of mg_set_vector_device / mg_get_vector_device on a vector of the level (no synchronisation)
+int scatter_to(mg_context* c, Level& L, DVector& v, const double* dev) {
+    MG_TRY(vec_alloc(c, L, &v));
+    const unsigned nb = (unsigned)std::min<int64_t>(4096, (L.n_global + 255) / 256);
+    hipLaunchKernelGGL(scatter_in, dim3(nb), dim3(256), 0, c->stream, dev, L.perm, L.n_global, L.row0, L.g.lead, L.xlen, v.base);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+int gather_from(mg_context* c, Level& L, DVector& v, double* dev) {
+    const unsigned nb = (unsigned)std::min<int64_t>(4096, (L.n_global + 255) / 256);
+    hipLaunchKernelGGL(gather_out, dim3(nb), dim3(256), 0, c->stream, v.base, L.perm, L.n_global, L.row0, L.nloc, L.g.lead, dev);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// What both batch entries refuse before anything is launched or allocated: the handle, the level, the lane count, the pointers.
+// in[k] / out: host arrays of nb device pointers of n_global doubles (in[k] may be null: not read); no out may overlap another
+// lane's out or any input.
+int batch_refusals(mg_context* c, const std::string& who, int level, int nb, const double* const* in0, const double* const* in1,
+                   double* const* out, const char* in0_name, const char* in1_name, const char* out_name) {
+    if (!c) return fail("null handle");
+    if (c->dim != 3) return fail(who + ": batched solves are 3-D only (this handle is 2-D)");
+    if (c->comm.active()) return fail(who + " needs a whole (not slab) handle");
+    MG_TRY(check_level(c, level));
+    const Level& L = c->L[level];
+    if (L.flat) return fail(who + ": level " + std::to_string(level) + " is flat (no grid)");
+    if (nb < 1 || nb > MG_BATCH_MAX)
+        return fail(who + ": nb = " + std::to_string(nb) + " is outside 1.." + std::to_string(MG_BATCH_MAX) + " (MG_BATCH_MAX)");
+    if (!out || (in0_name && !in0) || (in1_name && !in1)) return fail(who + ": null pointer array");
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t len = (size_t)L.n_global * sizeof(double);
+    struct Range { const char* p; const char* name; int lane; bool out; };
+    std::vector<Range> r;
+    for (int b = 0; b < nb; ++b) {
+        const std::string lane = "[" + std::to_string(b) + "]";
+        if (in0_name) {
+            MG_TRY(need_device_pointer(c, in0[b], who.c_str(), (in0_name + lane).c_str()));
+            r.push_back({reinterpret_cast<const char*>(in0[b]), in0_name, b, false});
+        }
+        if (in1_name) {
+            MG_TRY(need_device_pointer(c, in1[b], who.c_str(), (in1_name + lane).c_str()));
+            r.push_back({reinterpret_cast<const char*>(in1[b]), in1_name, b, false});
+        }
+        MG_TRY(need_device_pointer(c, out[b], who.c_str(), (out_name + lane).c_str()));
+        r.push_back({reinterpret_cast<const char*>(out[b]), out_name, b, true});
+    }
+    for (const Range& o : r) {
+        if (!o.out) continue;
+        for (const Range& q : r) {
+            if (&q == &o || (q.out && q.lane <= o.lane)) continue;
+            if (o.p < q.p + len && q.p < o.p + len)
+                return fail(who + ": " + o.name + "[" + std::to_string(o.lane) + "] overlaps " + q.name + "[" + std::to_string(q.lane) +
+                            "]: every lane's output is memory of its own");
+        }
+    }
+    return 0;
+}
+
 int ensure_stage(mg_context* c, int64_t elems) {
     if ((int64_t)c->stage.count() >= elems) return 0;
     return c->stage.alloc(c, (size_t)elems);
@@ -3795,6 +4234,7 @@ struct ContextDeleter {
         if (c->comm_stream) (void)hipStreamSynchronize(c->comm_stream);
         drop_graphs(c);
         if (c->h_scalars) (void)hipHostFree(c->h_scalars);
+        if (c->h_lanes) (void)hipHostFree(c->h_lanes);
         if (c->comm.h_stage) (void)hipHostFree(c->comm.h_stage);
         if (c->comm.nccl) g_rccl.CommDestroy(c->comm.nccl);
         if (c->ev_boundary) (void)hipEventDestroy(c->ev_boundary);
@@ -4275,6 +4715,9 @@ int mg_set_tuning(mg_handle c, const char* key, int64_t value) {
     } else if (k == "pcg_chunk") {
         if (value < 1) return fail("pcg_chunk must be positive");
         c->pcg_chunk = (int)value;
+    } else if (k == "mf_batch") {
+        if (value < 0 || value > MF_BATCH_MAX) return fail("mf_batch must be in 0.." + std::to_string(MF_BATCH_MAX) + " (0 or 1: never fuse)");
+        c->mf_batch = (int)value;
     } else {
         return fail("unknown tuning key " + k);
     }
@@ -5810,6 +6253,114 @@ int mg_pcg(mg_handle c, int level, double rtol, int max_iter, double* resid_hist
     return fcg_solve(c, level, rtol, max_iter, resid_hist, iterations);
 }
 
+int mg_pcg_batch(mg_handle c, int level, int nb, const double* const* f_dev, double* const* x_dev, double rtol, int max_iter,
+                 double* resid_hist, int* iterations) {
+    const std::string who = "mg_pcg_batch";
+    MG_TRY(batch_refusals(c, who, level, nb, f_dev, nullptr, x_dev, "f_dev", nullptr, "x_dev"));
+    if (level < 1) return fail(who + ": level 0 is the coarsest level: the V-cycle preconditioner needs level >= 1");
+    if (max_iter < 0) return fail(who + ": max_iter must not be negative");
+    for (int l = 0; l <= level; ++l) {
+        MG_TRY(need_matrix(c, l));
+        MG_TRY(need_grid(c, l));
+        if (c->L[l].mf && l >= 1 && (c->smoother == MG_SMOOTH_RBGS || c->smoother == MG_SMOOTH_MCGS))
+            return fail(who + ": level " + std::to_string(l) + " is a matrix-free diffusion level: Gauss-Seidel smoothers (RBGS, MCGS) "
+                        "need stored rows; use Jacobi or Chebyshev");
+    }
+    MG_TRY(face_set_refusals(c, level));
+    // what mg_pcg refuses only where the cycle is prepared (the P1 stencil check, the colouring, the factorisation, the Chebyshev
+    // interval) is refused here, with the handle's own vectors in place, before a lane is allocated or a vector overwritten
+    MG_TRY(prepare_cycle(c, level));
+    MG_TRY(ensure_lanes(c, nb, 0, level));
+    Level& L = c->L[level];
+    std::vector<int> all((size_t)nb);
+    for (int b = 0; b < nb; ++b) all[(size_t)b] = b;
+    BatchScope s(c, 0, level, nb);
+    MG_TRY(s.each(all, [&](int b) -> int {
+        MG_TRY(scatter_to(c, L, L.f, f_dev[b]));
+        return scatter_to(c, L, L.v, x_dev[b]);
+    }));
+    MG_TRY(fcg_solve_batch(c, s, level, nb, rtol, max_iter, resid_hist, std::max(1, max_iter), iterations));
+    MG_TRY(s.each(all, [&](int b) { return gather_from(c, L, L.v, x_dev[b]); }));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int mg_apply_batch(mg_handle c, int level, int op, int nb, const double* const* x_dev, const double* const* f_dev,
+                   double* const* out_dev, double* dots) {
+    const std::string who = "mg_apply_batch";
+    if (op != MG_BATCH_JACOBI && op != MG_BATCH_RESIDUAL && op != MG_BATCH_SPMV) return fail(who + ": unknown operation " + std::to_string(op));
+    const bool spmv = op == MG_BATCH_SPMV;
+    MG_TRY(batch_refusals(c, who, level, nb, x_dev, spmv ? nullptr : f_dev, out_dev, "x_dev", spmv ? nullptr : "f_dev", "out_dev"));
+    MG_TRY(need_matrix(c, level));
+    if (dots && !spmv) return fail(who + ": dots are the SpMV's (x . A x)");
+    if (op == MG_BATCH_JACOBI && c->smoother != MG_SMOOTH_JACOBI)
+        return fail(who + ": MG_BATCH_JACOBI is a sweep of the Jacobi smoother; the handle's smoother is another one (mg_set_params)");
+    MG_TRY(ensure_lanes(c, nb, level, level));       // (one level's operation: only that level's vectors)
+    Level& L = c->L[level];
+    std::vector<int> all((size_t)nb);
+    for (int b = 0; b < nb; ++b) all[(size_t)b] = b;
+    BatchScope s(c, level, level, nb);
+    MG_TRY(s.each(all, [&](int b) -> int {
+        if (!spmv) MG_TRY(scatter_to(c, L, L.f, f_dev[b]));
+        return scatter_to(c, L, L.v, x_dev[b]);
+    }));
+    if (op == MG_BATCH_JACOBI) {
+        MG_TRY(smooth_batch(c, s, level, 1, all));
+        MG_TRY(s.each(all, [&](int b) { return gather_from(c, L, L.v, out_dev[b]); }));
+    } else if (op == MG_BATCH_RESIDUAL) {
+        MG_TRY(residual_batch(c, s, level, all));
+        MG_TRY(s.each(all, [&](int b) { return gather_from(c, L, L.v2, out_dev[b]); }));
+    } else {
+        // out = A x into R; with dots the partial sums of x . A x, summed as mg_quadratic_form sums them
+        const unsigned grid = L.mf ? mf_plan(c, L).grid : blocks_for(L.nslices, WAVES_PER_BLOCK);
+        std::vector<DevBuf<double>> parts(dots ? (size_t)nb : 0);
+        for (auto& p : parts) MG_TRY(p.alloc(c, grid));
+        auto one = [&](int b) {
+            return launch_ell(c, L, {.mode = MODE_SPMV, .dot = dots != nullptr, .x_base = L.v.base, .out_rows = L.v2.rows,
+                                     .partials = dots ? parts[(size_t)b].get() : nullptr});
+        };
+        if (mf_fused(c, L, all.size())) {
+            MG_TRY(mf_groups(c, s, L, MODE_SPMV, dots != nullptr, all,
+                [&](int b, const double** x, const double**, double** out, double** pp) {
+                    LaneLevel& v = s.at(b, level);
+                    *x = v.v.base + L.g.lead; *out = v.v2.rows; *pp = dots ? parts[(size_t)b].get() : nullptr;
+                },
+                one, [](int, int) {}));
+        } else {
+            MG_TRY(s.each(all, one));
+        }
+        MG_TRY(s.each(all, [&](int b) -> int {
+            MG_TRY(gather_from(c, L, L.v2, out_dev[b]));
+            if (!dots) return 0;
+            hipLaunchKernelGGL(reduce_partials, dim3(1), dim3(BLOCK), 0, c->stream, parts[(size_t)b].get(), (int)grid, c->scalars.get());
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipMemcpyAsync(c->h_scalars, c->scalars, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(hipStreamSynchronize(c->stream));
+            dots[b] = c->h_scalars[0];
+            return 0;
+        }));
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int mg_batch_info(mg_handle c, int* lanes, int64_t* bytes) {
+    if (!c) return fail("null handle");
+    int64_t n = 0;
+    for (const Lane& lane : c->lanes) n += lane_bytes(lane);
+    if (lanes) *lanes = (int)c->lanes.size();
+    if (bytes) *bytes = n;
+    return 0;
+}
+
+int mg_release_batch(mg_handle c) {
+    if (!c) return fail("null handle");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    c->lanes.clear();
+    return 0;
+}
+
 int mg_time_kernel(mg_handle c, const char* kernel, int level, int reps, double* avg_ms) {
     MG_TRY(need_matrix(c, level));
     if (!kernel || !avg_ms || reps < 1) return fail("bad arguments");
@@ -5826,6 +6377,38 @@ int mg_time_kernel(mg_handle c, const char* kernel, int level, int reps, double*
     DevTemp ki_src, ki_coarse;      // "kappa_ingest": a copy of the level's kappa to read, a coarse field to write
     // "diffusion_mf[:jacobi|:residual|:spmv|:chebyshev]": the matrix-free march in one mode, i.e. that kernel on a matrix-free level
     // (timed as the operation `op` of that name, on a level that must be matrix-free)
+    // "diffusion_mf_batch<NV>:jacobi|residual|spmv": one fused launch of the march over NV vectors -- V, F, R and scratch copies
+    // of them for the other vectors (uncounted, freed on return)
+    if (k.rfind("diffusion_mf_batch", 0) == 0) {
+        if (!L.mf) return fail("level is not a matrix-free diffusion level");
+        const int nv = k.size() > 18 ? k[18] - '0' : 0;
+        const std::string mode = k.size() > 19 ? k.substr(19) : "";
+        const int m = mode == ":jacobi" ? MODE_JACOBI : mode == ":residual" ? MODE_RESIDUAL : mode == ":spmv" ? MODE_SPMV : -1;
+        if (nv < 2 || nv > MF_BATCH_MAX || m < 0) return fail("unknown kernel " + k);
+        DevTemp scratch[3 * MF_BATCH_MAX];
+        const double *x[MF_BATCH_MAX] = {L.v.rows}, *f[MF_BATCH_MAX] = {L.f.rows};
+        double* out[MF_BATCH_MAX] = {L.v2.rows};
+        const size_t total = (size_t)vec_total(L) * sizeof(double), off = (size_t)(vec_front(L) + L.g.lead);
+        const DVector* src[3] = {&L.v, &L.f, &L.v2};
+        for (int v = 1; v < nv; ++v) {
+            double* p[3];
+            for (int q = 0; q < 3; ++q) {
+                MG_TRY(scratch[3 * v + q].alloc(total));
+                HIP_TRY(hipMemcpyAsync(scratch[3 * v + q].p, src[q]->raw, total, hipMemcpyDeviceToDevice, c->stream));
+                p[q] = scratch[3 * v + q].as<double>() + off;
+            }
+            x[v] = p[0]; f[v] = p[1]; out[v] = p[2];
+        }
+        MG_TRY(launch_diffusion_mf_batch(c, L, m, false, nv, x, f, out, nullptr));      // warm-up
+        HIP_TRY(hipEventRecord(e0, c->stream));
+        for (int r = 0; r < reps; ++r) MG_TRY(launch_diffusion_mf_batch(c, L, m, false, nv, x, f, out, nullptr));
+        HIP_TRY(hipEventRecord(e1, c->stream));
+        HIP_TRY(hipEventSynchronize(e1));
+        float ms = 0.f;
+        HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
+        *avg_ms = (double)ms / reps;
+        return 0;
+    }
     const bool mf_key = k.rfind("diffusion_mf", 0) == 0;
     const std::string mf_mode = !mf_key ? "" : k.size() > 12 ? k.substr(12) : ":jacobi";
     const std::string op = !mf_key ? k : mf_mode[0] == ':' ? mf_mode.substr(1) : "";

@@ -921,6 +921,57 @@ class DeviceHierarchy:
         check(self._lib.mg_pcg(self._h, self._idx(level), float(rtol), int(max_iter), ptr(hist), C.byref(done)))
         return hist[:done.value].copy()
 
+    # ---- batched solves: one operator, several right-hand sides ---------------------------------------
+    @staticmethod
+    def _ptr_array(ptrs, nb=None):
+        """A host array of device addresses (None: a null array); with `nb`, its length is checked."""
+        if ptrs is None:
+            return None
+        ptrs = [int(p) for p in ptrs]
+        if nb is not None and len(ptrs) != nb:
+            raise ValueError(f"{len(ptrs)} pointers for {nb} lanes")
+        return (C.c_void_p * len(ptrs))(*ptrs)
+
+    def apply_batch(self, op: str, x_ptrs, f_ptrs, out_ptrs, level: Optional[int] = None, dots: bool = False):
+        """`mg_apply_batch`: for every lane b, out_b = one Jacobi sweep of x_b ("jacobi"), f_b - A x_b ("residual") or A x_b
+        ("spmv"; `f_ptrs` may be None) on `level` (default: the finest), with the bits of the one-vector kernels.  The
+        arguments are sequences of integer device addresses of `n_dofs(level)` float64 each, in the caller's DoF numbering.
+        `dots=True` ("spmv" only) returns x_b . A x_b per lane as a NumPy array; otherwise None.  The handle's own "v", "f"
+        and "r" are unspecified afterwards."""
+        level = self.finest_level if level is None else level
+        nb = len(x_ptrs)
+        d = np.zeros(max(1, nb)) if dots else None
+        check(self._lib.mg_apply_batch(self._h, self._idx(level), {"jacobi": _capi.MG_BATCH_JACOBI, "residual": _capi.MG_BATCH_RESIDUAL,
+                                                                    "spmv": _capi.MG_BATCH_SPMV}[op], nb,
+                                       self._ptr_array(x_ptrs), self._ptr_array(f_ptrs, nb), self._ptr_array(out_ptrs, nb),
+                                       ptr(d) if dots else None))
+        return d[:nb].copy() if dots else None
+
+    def pcg_batch(self, f_ptrs, x_ptrs, rtol: float = 1e-11, max_iter: int = 200, level: Optional[int] = None):
+        """`mg_pcg_batch`: `pcg` for several right-hand sides of one operator in lockstep.  `f_ptrs[b]` / `x_ptrs[b]` are integer
+        device addresses of `n_dofs(level)` float64 (the right-hand side; the initial guess on entry and the solution on
+        return).  Returns the list of the lanes' residual histories, each bit for bit what `set_vector_device("f")`,
+        `set_vector_device("v")`, `pcg`, `get_vector_device("v")` give for that lane alone.  The handle's own "v", "f" and
+        "r" are unspecified afterwards."""
+        level = self.finest_level if level is None else level
+        nb = len(f_ptrs)
+        stride = max(1, int(max_iter))
+        hist = np.zeros((max(1, nb), stride))
+        done = (C.c_int * max(1, nb))()
+        check(self._lib.mg_pcg_batch(self._h, self._idx(level), nb, self._ptr_array(f_ptrs), self._ptr_array(x_ptrs, nb),
+                                     float(rtol), int(max_iter), ptr(hist), done))
+        return [hist[b, :done[b]].copy() for b in range(nb)]
+
+    def batch_info(self) -> dict:
+        """Lanes held for batched solves beyond the handle's own vectors, and their device bytes (`mg_batch_info`)."""
+        lanes, b = C.c_int(), C.c_int64()
+        check(self._lib.mg_batch_info(self._h, C.byref(lanes), C.byref(b)))
+        return {"lanes": int(lanes.value), "bytes": int(b.value)}
+
+    def release_batch(self):
+        """Frees the lanes of batched solves (`mg_release_batch`); the next batch call allocates them again."""
+        check(self._lib.mg_release_batch(self._h))
+
     def set_mass(self, level: int, M):
         """The P1 mass matrix of `level` (SciPy CSR, the level's DoF numbering) for the L2(Omega) norms of fmg."""
         indptr, is64, indices, data = _csr_arrays(M)

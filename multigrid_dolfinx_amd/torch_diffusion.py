@@ -108,7 +108,19 @@ class DiffusionSolver:
     involves no alpha.  D_alpha and T_alpha close under differentiation, so `create_graph=True` gives the kappa-alpha,
     alpha-kappa and alpha-alpha blocks of a Hessian-vector product in the same number of solves.  The operator of a solve
     keeps the fields beside kappa and sigma; changing WHICH faces hold a field generates the hierarchy again instead of
-    refreshing it (`last_generate`)."""
+    refreshing it (`last_generate`).
+
+    `solve_many(kappa, F, g=None, sigma=None, same_operator=False, robin=None) -> U` solves one operator for the B >= 1
+    right-hand sides F[0], F[1], ... ((N + 1)^3 float64 each, B leading rows, on the solver's device; `g`: None, one field
+    shared by all lanes, or B fields) in ONE generation and ONE batched solve (`DeviceHierarchy.pcg_batch`): on matrix-free
+    levels the march rebuilds each row from kappa once for several lanes.  U[b] has the bits of `solve(kappa, F[b], ...)`.  The
+    backward pass is one more batched solve with the B cotangents, then grad_F = Lambda, grad_kappa = -(D(lambda_0, u_0) +
+    D(lambda_1, u_1) + ...) summed in ascending lane order (grad_sigma and grad_alpha alike), grad_g per lane as in `solve`
+    and summed over the lanes where g is shared.  It is written with the autograd functions themselves, so `create_graph=True`
+    works and a Hessian-vector product of a sum over B sources is four batched solves.  `n_solves` grows by B per batched
+    solve and `n_batched_solves` by 1; `last_iterations[kind]` is the largest lane count and `last_lane_iterations[kind]`
+    holds them all; if any lane reaches `max_iter`, `NotConverged` names the lanes.  `warm_start` keeps the last batched
+    solution of each kind and reuses it when B is the same.  `tangent` is not batched."""
 
     def __init__(self, N: int, n_levels: int, averaging: str = "arithmetic", matrix_free_min_rows: Optional[int] = None,
                  rtol: float = 1e-10, max_iter: int = 200, device: int = 0, warm_start: bool = False, dirichlet_faces=None,
@@ -142,8 +154,13 @@ class DiffusionSolver:
         self.n_solves = 0               # mg_pcg calls so far: what a product costs (a Hessian-vector product: four)
         self.last_iterations = {}       # "forward" / "adjoint" / "tangent": iterations of the last solve of that kind
         self.last_residual = {}         # ... and ||r|| / ||rhs|| of mg_pcg's recursion where it stopped (None: no iteration was needed)
+        self.n_batched_solves = 0       # mg_pcg_batch calls so far (`solve_many`): each adds its lanes to n_solves
+        self.last_lane_iterations = {}  # ... the iterations of every lane of the last batched solve of that kind
+        self._warm_many = {}            # ... its solution (warm_start; reused when the next one has as many lanes)
 
     def close(self):
+        if self.n_batched_solves and self.hierarchy._h:
+            self.hierarchy.release_batch()
         self.hierarchy.close()
 
     def __enter__(self):
@@ -197,6 +214,50 @@ class DiffusionSolver:
         lift = _Tangent.apply(kappa.reshape(-1).to(self.device), g_b, self, "interior", "all")
         rhs = torch.where(boundary, gv, fv - lift)
         return _Solve.apply(kappa, rhs.view(f.shape), self, op, "forward", True, *rest)
+
+    def solve_many(self, kappa: torch.Tensor, F: torch.Tensor, g: Optional[torch.Tensor] = None,
+                   sigma: Optional[torch.Tensor] = None, same_operator: bool = False, robin=None) -> torch.Tensor:
+        """`solve` for the B right-hand sides F[0] .. F[B - 1] on one operator: one generation, one batched solve forward and
+        one backward (see the class)."""
+        n = self.hierarchy.n_dofs(self.top)
+        if F.dtype != torch.float64 or F.device != self.device or F.dim() < 2 or F.shape[0] < 1 or F[0].numel() != n:
+            raise ValueError(f"F must hold B >= 1 leading rows of {n} float64 on {self.device} (got {tuple(F.shape)} {F.dtype} on {F.device})")
+        B = F.shape[0]
+        bits, alphas = self._robin_inputs(robin)
+        rest = (sigma,) if not bits else (sigma, bits) + alphas     # (what _SolveMany takes after `warm`)
+        op = None
+        if same_operator:
+            op = self._last_operator
+            if op is None:
+                raise ValueError("same_operator=True reuses the operator of the last solve: there has been none")
+            if (sigma is None) != (op.sigma_kept is None):
+                raise ValueError("same_operator=True: the last solve had " + ("no" if sigma is not None else "a") + " sigma")
+            if bits != tuple(sorted(op.robin_kept)):
+                raise ValueError(f"same_operator=True: the last solve had Robin fields on the faces {sorted(op.robin_kept)}")
+        if g is None:
+            return _SolveMany.apply(kappa, F, self, op, "forward", True, *rest)
+        if g.dtype != torch.float64 or g.device != self.device or g.numel() not in (n, B * n) or (g.numel() == B * n and B > 1 and g.shape[0] != B):
+            raise ValueError(f"g must hold {n} float64 (shared by all lanes) or {B} leading rows of them on {self.device}")
+        shared = g.numel() == n and not (B == 1 and g.dim() == F.dim())
+        boundary = self._boundary_mask()
+        Fv = F.reshape(B, n)
+        if op is None:
+            op = self._put_operator(kappa, sigma, dict(zip(bits, alphas)))  # first: the lift runs on the level's grid, which the first generation sets
+        kv = kappa.reshape(-1).to(self.device)
+
+        def lifted(gv, fv):
+            g_b = torch.where(boundary, gv, torch.zeros_like(gv))
+            return torch.where(boundary, gv, fv - _Tangent.apply(kv, g_b, self, "interior", "all"))
+
+        if shared:      # one lift for all lanes: autograd sums its lanes' contributions
+            gv = g.reshape(-1)
+            g_b = torch.where(boundary, gv, torch.zeros_like(gv))
+            lift = _Tangent.apply(kv, g_b, self, "interior", "all")
+            rhs = torch.where(boundary, gv, Fv - lift)
+        else:
+            gv = g.reshape(B, n)
+            rhs = torch.stack([lifted(gv[b], Fv[b]) for b in range(B)])
+        return _SolveMany.apply(kappa, rhs.view(F.shape), self, op, "forward", True, *rest)
 
     def robin_apply(self, face, w: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
         """T_alpha,F(w, x) = b_F(w) x on the free nodes of `face`, 0 on every other node (`mg_diffusion_apply_drobin`),
@@ -372,6 +433,39 @@ class DiffusionSolver:
         return x
 
 
+    def _pcg_many(self, rhs: torch.Tensor, which: str, warm: bool = True) -> torch.Tensor:
+        """A x_b = rhs[b] for every row of the contiguous (B, n) `rhs`, in one `pcg_batch` (at most MG_BATCH_MAX lanes per
+        call), from zero or from the last batched solution of this kind with as many lanes (warm_start and `warm`)."""
+        from ._capi import MG_BATCH_MAX
+        h = self.hierarchy
+        warm = warm and self.warm_start
+        B, n = rhs.shape
+        x0 = self._warm_many.get(which) if warm else None
+        x = x0.clone() if x0 is not None and x0.shape == rhs.shape else torch.zeros_like(rhs)
+        torch.cuda.current_stream(self.device).synchronize()        # rhs and x are complete before the handle's stream reads them
+        step = 8 * n
+        hists = []
+        for b0 in range(0, B, MG_BATCH_MAX):
+            lanes = range(b0, min(B, b0 + MG_BATCH_MAX))
+            hists += h.pcg_batch([rhs.data_ptr() + b * step for b in lanes], [x.data_ptr() + b * step for b in lanes],
+                                 rtol=self.rtol, max_iter=self.max_iter, level=self.top)
+        self.n_solves += B
+        self.n_batched_solves += 1
+        its = [len(hist) for hist in hists]
+        norms = torch.linalg.vector_norm(rhs, dim=1).tolist()
+        self.last_iterations[which] = max(its)
+        self.last_lane_iterations[which] = its
+        ratios = [float(hist[-1]) / nb for hist, nb in zip(hists, norms) if len(hist)]
+        self.last_residual[which] = max(ratios) if ratios else None
+        late = [b for b, (hist, nb) in enumerate(zip(hists, norms)) if len(hist) >= self.max_iter and not hist[-1] <= self.rtol * nb]
+        if late:
+            raise NotConverged(f"the batched {which} solve reached max_iter = {self.max_iter} in the lanes {late} of {B} "
+                               f"(||r|| = {', '.join('%.3e' % hists[b][-1] for b in late)}; rtol {self.rtol:g}): no gradient is returned")
+        if warm:
+            self._warm_many[which] = x.clone()
+        return x
+
+
 class _Operator:
     """The kappa (and the sigma, or None, and the Robin fields by face bit) of one `solve` as the library takes them (a host
     array or a device copy) and the generation of the hierarchy that holds them: what the solves nested in that solve's backward passes share, so that they neither upload
@@ -441,6 +535,71 @@ class _Solve(torch.autograd.Function):
         for bit, alpha, like in zip(ctx.bits, ctx.alphas, ctx.alpha_like):
             grad_alphas.append(None if alpha is None else _DRobin.apply(lam, u, solver, bit).neg().view(like[0]).to(like[1]))
         return (grad_kappa, grad_f, None, None, None, None, grad_sigma, None, *grad_alphas)
+
+
+class _SolveMany(torch.autograd.Function):
+    """S for B right-hand sides on one operator: U[b] = A^-1 F[b], one batched solve (`DiffusionSolver._pcg_many`).  The
+    arguments are `_Solve`'s with F of B leading rows; the backward pass is `_Solve`'s with the nested solve batched and D
+    applied per lane, the lanes' terms summed in ascending order with the first term starting the accumulator."""
+
+    @staticmethod
+    def forward(ctx, kappa, F, solver, op, which, warm, *rest):
+        sigma = rest[0] if rest else None
+        n = solver.hierarchy.n_dofs(solver.top)
+        if F.dtype != torch.float64 or F.device != solver.device or F.dim() < 2 or F[0].numel() != n:
+            raise ValueError(f"the right-hand sides must hold leading rows of {n} float64 on {solver.device}")
+        rhs = F.detach().contiguous().view(F.shape[0], n)
+        bits, alphas = (rest[1], rest[2:]) if len(rest) > 1 else ((), ())
+        if op is None:
+            op = solver._put_operator(kappa, sigma, dict(zip(bits, alphas)))
+        elif op.generation != solver._generation:       # another kappa has been solved since: this one's operator again
+            op.generation = solver._generate(op.kappa_kept, op.sigma_kept, op.robin_kept)
+        U = solver._pcg_many(rhs, which, warm).view(F.shape)
+        ctx.solver, ctx.op = solver, op
+        ctx.kappa_like = None if kappa is None else (kappa.shape, kappa.device)
+        ctx.kappa = kappa if ctx.needs_input_grad[0] else None      # (as in _Solve: what the gradient is taken with respect to)
+        ctx.n_rest = len(rest)
+        ctx.sigma_like = None if sigma is None else (sigma.shape, sigma.device)
+        ctx.sigma = sigma if rest and ctx.needs_input_grad[6] else None
+        ctx.bits = bits
+        ctx.alpha_like = [None if a is None else (a.shape, a.device) for a in alphas]
+        ctx.alphas = [a if a is not None and ctx.needs_input_grad[8 + q] else None for q, a in enumerate(alphas)]
+        ctx.save_for_backward(U)
+        return U
+
+    @staticmethod
+    def backward(ctx, grad_U):
+        solver = ctx.solver
+        kappa, (U,) = ctx.kappa, ctx.saved_tensors
+        rest = [ctx.sigma] * min(ctx.n_rest, 1) + ([ctx.bits] + ctx.alphas if ctx.n_rest > 1 else [])
+        Lam = _SolveMany.apply(kappa, grad_U, solver, ctx.op, "adjoint", not torch.is_grad_enabled(), *rest)
+        B = U.shape[0]
+        Uv, Lv = U.reshape(B, -1), Lam.reshape(B, -1)
+
+        def over_lanes(term):
+            acc = term(Lv[0], Uv[0])
+            for b in range(1, B):
+                acc = acc + term(Lv[b], Uv[b])
+            return acc
+
+        grad_kappa = None
+        if ctx.needs_input_grad[0]:
+            shape, device = ctx.kappa_like
+            grad_kappa = over_lanes(lambda lam, u: _DKappa.apply(lam, u, solver, "interior", "interior")).neg().view(shape).to(device)
+        grad_F = Lam if ctx.needs_input_grad[1] else None
+        if not ctx.n_rest:
+            return grad_kappa, grad_F, None, None, None, None
+        grad_sigma = None
+        if ctx.sigma is not None:
+            shape, device = ctx.sigma_like
+            grad_sigma = over_lanes(lambda lam, u: _DSigma.apply(lam, u, solver)).neg().view(shape).to(device)
+        if ctx.n_rest == 1:
+            return grad_kappa, grad_F, None, None, None, None, grad_sigma
+        grad_alphas = []
+        for bit, alpha, like in zip(ctx.bits, ctx.alphas, ctx.alpha_like):
+            grad_alphas.append(None if alpha is None else
+                               over_lanes(lambda lam, u: _DRobin.apply(lam, u, solver, bit)).neg().view(like[0]).to(like[1]))
+        return (grad_kappa, grad_F, None, None, None, None, grad_sigma, None, *grad_alphas)
 
 
 class _DKappa(torch.autograd.Function):
