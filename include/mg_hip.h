@@ -435,6 +435,27 @@ int mg_diffusion_apply_dsigma(mg_handle h, int level, const double* dsigma_dev, 
  * face of the handle's Dirichlet set. */
 int mg_diffusion_drobin(mg_handle h, int level, int face, const double* a_dev, const double* b_dev, double* out_dev);
 int mg_diffusion_apply_drobin(mg_handle h, int level, int face, const double* dalpha_dev, const double* x_dev, double* out_dev);
+/* Cell gradients and fluxes of a nodal field (no reference counterpart).  On a 3-D grid level with N^3 cells, h = 1 / N, cells
+ * in kappa's order (ck * N + cj) * N + ci, nodes lexicographic, a 3-component cell field with component d in {x, y, z} at
+ * d * N^3 + cell:
+ *     mg_diffusion_cell_gradient:     out = F(w, x), 3 N^3: F_{d,c} = w_c G_d(x)_c with G(x)_c the mean of grad x_h over the six
+ *                                     Kuhn simplices of cell c -- (N / 6) times the sum over the cell's four edges of axis d of
+ *                                     n (x_upper - x_lower), n = 2, 1, 1, 2 as in mg_diffusion_dkappa.  w_dev null: F = G, no
+ *                                     product.  No mask: x is the field itself, Dirichlet values included.  q = -F(kappa, u) is
+ *                                     the exact cell average of -kappa grad u_h;
+ *     mg_diffusion_cell_gradient_t:   out = F^T(w, p), nodes: the transpose of F in x, p a 3-component cell field;
+ *     mg_diffusion_cell_gradient_dot: out = C(p, x), N^3: out_c = p_{x,c} G_x + p_{y,c} G_y + p_{z,c} G_z.
+ * They are adjoint up to rounding, <p, F(w, x)> = <x, F^T(w, p)> = <w, C(p, x)>, and close under differentiation: F with
+ * cotangent P gives w_bar = C(P, x), x_bar = F^T(w, P); F^T with cotangent y gives w_bar = C(p, y), p_bar = F(w, y); C with
+ * cotangent z gives p_bar = F(z, x), x_bar = F^T(z, p).  None reads kappa or a matrix: any whole 3-D grid level will do, stored,
+ * matrix-free or grid-only (mg_set_level_grid).  Summation order: mg_diffusion_flux.hip.h; poisson.diffusion_cell_gradient,
+ * diffusion_cell_gradient_t and diffusion_cell_gradient_dot restate them bit for bit (no fma in any).  They run on the
+ * handle's stream, which is synchronised before return; nothing crosses to the host and no handle memory is allocated.
+ * Refused with an error before anything is launched: 2-D handles, slab handles, flat levels, null pointers other than w_dev,
+ * pointers that are not device memory of the handle's device, and an out_dev that overlaps an input. */
+int mg_diffusion_cell_gradient(mg_handle h, int level, const double* w_dev, const double* x_dev, double* out_dev);
+int mg_diffusion_cell_gradient_t(mg_handle h, int level, const double* w_dev, const double* p_dev, double* out_dev);
+int mg_diffusion_cell_gradient_dot(mg_handle h, int level, const double* p_dev, const double* x_dev, double* out_dev);
 /* getJacobiMatrices (multigrid.py:48-56) as a stand-alone set-up kernel, for callers that
  * want the reference's split operands back: for every stored entry a_ij of the CSR matrix
  * writes scaled[q] = a_ij / a_ii computed as (1/a_ii) * a_ij, keep[q] = 1 unless the entry
@@ -890,6 +911,11 @@ int mg_reset_smoother_launches(mg_handle h);
  * arithmetic averaging; an error on stored levels);
  * "diffusion_mf_batch<NV>:jacobi", ":residual", ":spmv" (NV = 2, 3, 4) = one fused launch of the matrix-free march over NV vectors
  * (mg_apply_batch, mg_pcg_batch): MG_VEC_V, MG_VEC_F, MG_VEC_R and scratch copies of them; an error on stored levels.
+ * "cell_grad" = mg_diffusion_cell_gradient with w = the first N^3 entries of MG_VEC_F and x = MG_VEC_V into a scratch of 3 N^3 whose
+ * first entries (as many as MG_VEC_R holds) are copied to MG_VEC_R after the timed region; "cell_grad_nw" = the same with w null;
+ * "cell_grad_dot" = mg_diffusion_cell_gradient_dot of x = MG_VEC_V and a scratch p whose components x, y, z are the first N^3 entries
+ * of MG_VEC_V, MG_VEC_F, MG_VEC_V, into the first N^3 entries of MG_VEC_R; "cell_grad_t" = mg_diffusion_cell_gradient_t of that w and
+ * that p into MG_VEC_R; the scratch is allocated and freed outside the timed region.
  * Used by bench.py for the roofline figure; its launches leave mg_smoother_launches as they were.  mg_sync waits for
  * the handle's stream. */
 int mg_time_kernel(mg_handle h, const char* kernel, int level, int reps, double* avg_ms);

@@ -12,6 +12,7 @@
 #include "mg_diffusion_mf.hip.h"
 #include "mg_diffusion_mf_batch.hip.h"
 #include "mg_diffusion_adj.hip.h"
+#include "mg_diffusion_flux.hip.h"
 #include "mg_diffusion_kappa.hip.h"
 
 #include <dlfcn.h>
@@ -1148,6 +1149,33 @@ int need_device_pointer(mg_context* c, const void* p, const char* who, const cha
     if (at.device != c->device)
         return fail(std::string(who) + ": " + what + " lives on device " + std::to_string(at.device) + ", the handle on device " +
                     std::to_string(c->device));
+    return 0;
+}
+
+// The cell gradient family on a whole 3-D grid level (mg_diffusion_flux.hip.h): F(w, x) -> 3 N^3 and C(p, x) -> N^3, one thread per
+// cell; F^T(w, p) -> nodes, one thread per node.  The caller's lexicographic buffers.
+CgArgs cg_args(const Level& L, const double* w, const double* p, const double* x, double* out) {
+    CgArgs a{};
+    a.w = w; a.p = p; a.x = x; a.out = out;
+    a.nx = L.g.nx; a.ny = L.g.ny; a.nz = L.g.nz; a.N = L.N; a.P = L.g.plane;
+    a.C3 = (int64_t)L.N * L.N * L.N;
+    a.s = (double)L.N / 6.0;
+    return a;
+}
+
+template <int KIND>
+int launch_cell_grad(mg_context* c, const Level& L, const double* w, const double* p, const double* x, double* out) {
+    const CgArgs a = cg_args(L, w, p, x, out);
+    const dim3 grid(blocks_for((int64_t)L.N * L.N, DK_BLOCK), (unsigned)L.N, 1u);
+    hipLaunchKernelGGL((cell_grad_cells<KIND>), grid, dim3(DK_BLOCK), 0, c->stream, a);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int launch_cell_grad_t(mg_context* c, const Level& L, const double* w, const double* p, double* out) {
+    const CgArgs a = cg_args(L, w, p, nullptr, out);
+    hipLaunchKernelGGL(cell_grad_t, dim3(blocks_for(L.g.plane, DK_BLOCK), (unsigned)L.g.nz, 1u), dim3(DK_BLOCK), 0, c->stream, a);
+    HIP_TRY(hipGetLastError());
     return 0;
 }
 
@@ -5917,6 +5945,68 @@ int mg_diffusion_apply_drobin(mg_handle c, int level, int face, const double* da
     return 0;
 }
 
+// the cell gradient family: whole 3-D grid levels, refused by name otherwise
+static int need_cell_grad_level(mg_context* c, int level, const char* who) {
+    if (!c) return fail("null handle");
+    if (c->dim != 3) return fail(std::string(who) + ": the cell gradient is 3-D only (this handle is 2-D)");
+    if (c->comm.active()) return fail(std::string(who) + " needs a whole (not slab) handle");
+    MG_TRY(check_level(c, level));
+    if (c->L[level].flat) return fail(std::string(who) + ": level " + std::to_string(level) + " is flat (no grid): it has no cells");
+    return 0;
+}
+
+// ... and their pointers: device memory of the handle's device (`w`, the one that may be null, is `first` of F and F^T), out
+// apart from the inputs (other threads read them while a thread writes its entries of out)
+static int need_cell_grad_operands(mg_context* c, const char* who, const char* first, const void* p, size_t np, bool first_optional,
+                                   const char* second, const void* q, size_t nq, const void* out, size_t nout) {
+    if (p || !first_optional) MG_TRY(need_device_pointer(c, p, who, first));
+    MG_TRY(need_device_pointer(c, q, who, second));
+    MG_TRY(need_device_pointer(c, out, who, "out"));
+    const auto overlaps = [](const void* x, size_t nx, const void* y, size_t ny) {
+        const uintptr_t a = (uintptr_t)x, b = (uintptr_t)y;
+        return a < b + ny && b < a + nx;
+    };
+    if (p && overlaps(out, nout, p, np)) return fail(std::string(who) + ": out overlaps " + first);
+    if (overlaps(out, nout, q, nq)) return fail(std::string(who) + ": out overlaps " + second);
+    return 0;
+}
+
+int mg_diffusion_cell_gradient(mg_handle c, int level, const double* w_dev, const double* x_dev, double* out_dev) {
+    const char* who = "mg_diffusion_cell_gradient";
+    MG_TRY(need_cell_grad_level(c, level, who));
+    HIP_TRY(hipSetDevice(c->device));
+    const Level& L = c->L[level];
+    const size_t nodes = (size_t)L.g.plane * (size_t)L.g.nz * 8, cells = (size_t)L.N * L.N * L.N * 8;
+    MG_TRY(need_cell_grad_operands(c, who, "w", w_dev, cells, true, "x", x_dev, nodes, out_dev, 3 * cells));
+    MG_TRY(launch_cell_grad<CG_F>(c, L, w_dev, nullptr, x_dev, out_dev));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int mg_diffusion_cell_gradient_t(mg_handle c, int level, const double* w_dev, const double* p_dev, double* out_dev) {
+    const char* who = "mg_diffusion_cell_gradient_t";
+    MG_TRY(need_cell_grad_level(c, level, who));
+    HIP_TRY(hipSetDevice(c->device));
+    const Level& L = c->L[level];
+    const size_t nodes = (size_t)L.g.plane * (size_t)L.g.nz * 8, cells = (size_t)L.N * L.N * L.N * 8;
+    MG_TRY(need_cell_grad_operands(c, who, "w", w_dev, cells, true, "p", p_dev, 3 * cells, out_dev, nodes));
+    MG_TRY(launch_cell_grad_t(c, L, w_dev, p_dev, out_dev));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int mg_diffusion_cell_gradient_dot(mg_handle c, int level, const double* p_dev, const double* x_dev, double* out_dev) {
+    const char* who = "mg_diffusion_cell_gradient_dot";
+    MG_TRY(need_cell_grad_level(c, level, who));
+    HIP_TRY(hipSetDevice(c->device));
+    const Level& L = c->L[level];
+    const size_t nodes = (size_t)L.g.plane * (size_t)L.g.nz * 8, cells = (size_t)L.N * L.N * L.N * 8;
+    MG_TRY(need_cell_grad_operands(c, who, "p", p_dev, 3 * cells, false, "x", x_dev, nodes, out_dev, cells));
+    MG_TRY(launch_cell_grad<CG_C>(c, L, nullptr, p_dev, x_dev, out_dev));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
 int mg_zero_vector(mg_handle c, int level, int which) {
     MG_TRY(check_level(c, level));
     Level& L = c->L[level];
@@ -6404,6 +6494,43 @@ int mg_time_kernel(mg_handle c, const char* kernel, int level, int reps, double*
         for (int r = 0; r < reps; ++r) MG_TRY(launch_diffusion_mf_batch(c, L, m, false, nv, x, f, out, nullptr));
         HIP_TRY(hipEventRecord(e1, c->stream));
         HIP_TRY(hipEventSynchronize(e1));
+        float ms = 0.f;
+        HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
+        *avg_ms = (double)ms / reps;
+        return 0;
+    }
+    // the cell gradient family (mg_diffusion_flux.hip.h) with w = F[:N^3], x = V and p = (V, F, V)[:N^3] per component in a scratch
+    // of 3 N^3 (uncounted, freed on return): "cell_grad" = F(w, x), "cell_grad_nw" = F(null, x), into a scratch whose first entries
+    // (as many as R holds) are copied to R after the timed region; "cell_grad_dot" = C(p, x) into R[:N^3]; "cell_grad_t" =
+    // F^T(w, p) into R
+    if (k.rfind("cell_grad", 0) == 0) {
+        MG_TRY(need_cell_grad_level(c, level, "mg_time_kernel"));
+        const bool f_form = k == "cell_grad" || k == "cell_grad_nw", c_form = k == "cell_grad_dot", t_form = k == "cell_grad_t";
+        if (!(f_form || c_form || t_form)) return fail("unknown kernel " + k);
+        MG_TRY(vec_alloc(c, L, &L.v)); MG_TRY(vec_alloc(c, L, &L.f)); MG_TRY(vec_alloc(c, L, &L.v2));
+        const size_t cells = (size_t)L.N * L.N * L.N;
+        DevTemp three;
+        MG_TRY(three.alloc(3 * cells * sizeof(double)));
+        double* t3 = three.as<double>();
+        const double* w = k == "cell_grad_nw" ? nullptr : L.f.rows;
+        if (!f_form) {
+            const double* src[3] = {L.v.rows, L.f.rows, L.v.rows};
+            for (int d = 0; d < 3; ++d)
+                HIP_TRY(hipMemcpyAsync(t3 + d * cells, src[d], cells * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+        }
+        auto run = [&]() -> int {
+            if (f_form) return launch_cell_grad<CG_F>(c, L, w, nullptr, L.v.rows, t3);
+            if (c_form) return launch_cell_grad<CG_C>(c, L, nullptr, t3, L.v.rows, L.v2.rows);
+            return launch_cell_grad_t(c, L, w, t3, L.v2.rows);
+        };
+        MG_TRY(run());      // warm-up
+        HIP_TRY(hipEventRecord(e0, c->stream));
+        for (int r = 0; r < reps; ++r) MG_TRY(run());
+        HIP_TRY(hipEventRecord(e1, c->stream));
+        if (f_form)
+            HIP_TRY(hipMemcpyAsync(L.v2.rows, t3, std::min((size_t)L.n_global, 3 * cells) * sizeof(double), hipMemcpyDeviceToDevice,
+                                   c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
         float ms = 0.f;
         HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
         *avg_ms = (double)ms / reps;

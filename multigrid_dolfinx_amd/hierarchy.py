@@ -840,6 +840,57 @@ class DeviceHierarchy:
         n = self.n_dofs(level)
         return self._sigma_entry(entry, "dalpha and x", dalpha, self.elements(level) ** 2, x, n, out, n)
 
+    def _weighted_entry(self, entry, names, w, n_w, second, n_second, out, n_out):
+        """`_sigma_entry` for the two cell gradient entries whose first operand, the cell weight `w`, may be None (a null
+        pointer: no weight)."""
+        if w is not None:
+            return self._sigma_entry(entry, names, w, n_w, second, n_second, out, n_out)
+        if isinstance(second, (int, np.integer)):
+            if not isinstance(out, (int, np.integer)):
+                raise TypeError(f"with a device address for {names}, out must be a device address too")
+            check(entry(C.c_void_p(0), C.c_void_p(int(second)), C.c_void_p(int(out))))
+            return None
+        if isinstance(out, (int, np.integer)):
+            raise TypeError(f"{names} and out must be all device addresses or all NumPy arrays")
+        held = []
+        try:
+            held.append(_DeviceArray(self._lib, self.device, n_second, _capi.as_f64(second, n_second)))
+            held.append(_DeviceArray(self._lib, self.device, n_out))
+            check(entry(C.c_void_p(0), held[0].ptr, held[1].ptr))
+            got = held[1].download()
+        finally:
+            for d in held:
+                d.free()
+        if out is None:
+            return got
+        out.reshape(-1)[:] = got
+        return out
+
+    def diffusion_cell_gradient(self, level: int, w, x, out=None):
+        """F(w, x): the cell gradient of the nodal field `x` weighted by the cell field `w` on a 3-D grid level, 3 N^3 values with
+        component d at d * N^3 + cell (`mg_diffusion_cell_gradient`; host restatement: `poisson.diffusion_cell_gradient`, same
+        bits).  `w`: `elements(level) ** 3` cells of any sign, or None (the plain gradient); -F(kappa, u) is the cell average
+        of the flux.  Device addresses or NumPy arrays, as in `diffusion_dkappa`."""
+        entry = lambda pw, px, po: self._lib.mg_diffusion_cell_gradient(self._h, self._idx(level), pw, px, po)
+        cells = self.elements(level) ** 3
+        return self._weighted_entry(entry, "w and x" if w is not None else "x", w, cells, x, self.n_dofs(level), out, 3 * cells)
+
+    def diffusion_cell_gradient_t(self, level: int, w, p, out=None):
+        """F^T(w, p): the transpose of `diffusion_cell_gradient` in x, applied to the 3-component cell field `p` (3 N^3), nodal
+        values (`mg_diffusion_cell_gradient_t`; host restatement: `poisson.diffusion_cell_gradient_t`, same bits).  `w` as in
+        `diffusion_cell_gradient`.  Device addresses or NumPy arrays, as in `diffusion_dkappa`."""
+        entry = lambda pw, pp, po: self._lib.mg_diffusion_cell_gradient_t(self._h, self._idx(level), pw, pp, po)
+        cells = self.elements(level) ** 3
+        return self._weighted_entry(entry, "w and p" if w is not None else "p", w, cells, p, 3 * cells, out, self.n_dofs(level))
+
+    def diffusion_cell_gradient_dot(self, level: int, p, x, out=None):
+        """C(p, x): per cell the product of the 3-component cell field `p` (3 N^3) with the cell gradient of the nodal field `x`,
+        N^3 values (`mg_diffusion_cell_gradient_dot`; host restatement: `poisson.diffusion_cell_gradient_dot`, same bits).
+        Device addresses or NumPy arrays, as in `diffusion_dkappa`."""
+        entry = lambda pp, px, po: self._lib.mg_diffusion_cell_gradient_dot(self._h, self._idx(level), pp, px, po)
+        cells = self.elements(level) ** 3
+        return self._sigma_entry(entry, "p and x", p, 3 * cells, x, self.n_dofs(level), out, cells)
+
     def zero_vector(self, level: int, which: str = "v"):
         check(self._lib.mg_zero_vector(self._h, self._idx(level), _VEC[which]))
 

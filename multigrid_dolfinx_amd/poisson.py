@@ -1050,6 +1050,89 @@ def diffusion_dkappa(N: int, a, b, a_nodes: str = "interior", b_nodes: str = "in
     return np.ascontiguousarray((s * ((1.0 / N) / 6.0)).reshape(-1))
 
 
+def _cell_gradient_axes(N: int, x):
+    """[G_x, G_y, G_z], each [N][N][N]: the mean of grad x_h over the six Kuhn simplices of every cell, with the adds of
+    `cg_grad` (mg_diffusion_flux.hip.h): per axis one accumulator over the cell's four edges of that axis in `dk_cell`'s edge
+    order with the weights 2, 1, 1, 2, times N / 6.0.  No mask."""
+    n1 = N + 1
+    v = np.array(x, dtype=np.float64).reshape(-1)
+    if v.size != n1 ** 3:
+        raise ValueError(f"vector has {v.size} entries, the level has {n1 ** 3} nodes")
+    v = v.reshape(n1, n1, n1)
+    U = [[[v[dz:dz + N, dy:dy + N, dx:dx + N] for dx in (0, 1)] for dy in (0, 1)] for dz in (0, 1)]
+    s = N / 6.0
+    G = []
+    for axis in (0, 1, 2):                      # x, y, z edges; (p, q): the two other coordinates, slower one first
+        acc = None
+        for p in (0, 1):
+            for q in (0, 1):
+                if axis == 0:
+                    hi, lo = (p, q, 1), (p, q, 0)
+                elif axis == 1:
+                    hi, lo = (p, 1, q), (p, 0, q)
+                else:
+                    hi, lo = (1, p, q), (0, p, q)
+                t = U[hi[0]][hi[1]][hi[2]] - U[lo[0]][lo[1]][lo[2]]
+                if p == q:
+                    t = 2.0 * t
+                acc = t if acc is None else acc + t
+        G.append(acc * s)
+    return G
+
+
+def _cell_field3(p, N: int) -> np.ndarray:
+    v = np.array(p, dtype=np.float64).reshape(-1)
+    if v.size != 3 * N ** 3:
+        raise ValueError(f"a 3-component cell field has {3 * N ** 3} entries (got {v.size})")
+    return v.reshape(3, N, N, N)
+
+
+def diffusion_cell_gradient(N: int, w, x) -> np.ndarray:
+    """F(w, x), 3 N^3: F_{d,c} = w_c * G_d(x)_c with G(x)_c the mean of grad x_h over the six Kuhn simplices of cell c, as
+    `mg_diffusion_cell_gradient` computes it (same bits: the adds of `cg_cell_f`, mg_diffusion_flux.hip.h).  `w`: N^3 cell values
+    of any sign in the cell order of `diffusion_level`, or None (F = G, no product); `x`: nodal values in lexicographic order,
+    read as they are (no mask).  Component d in (x, y, z) at d * N^3 + cell.  -F(kappa, u) is the cell average of the flux
+    -kappa grad u_h."""
+    G = _cell_gradient_axes(N, x)
+    if w is not None:
+        wc = _kappa_cells(w, N, 3)
+        G = [wc * g for g in G]
+    return np.ascontiguousarray(np.stack(G).reshape(-1))
+
+
+def diffusion_cell_gradient_dot(N: int, p, x) -> np.ndarray:
+    """C(p, x), N^3: out_c = ((p_{x,c} * G_x) + p_{y,c} * G_y) + p_{z,c} * G_z, as `mg_diffusion_cell_gradient_dot` computes it
+    (same bits).  <w, C(p, x)> = <p, F(w, x)> up to rounding."""
+    G = _cell_gradient_axes(N, x)
+    P = _cell_field3(p, N)
+    return np.ascontiguousarray((((P[0] * G[0]) + P[1] * G[1]) + P[2] * G[2]).reshape(-1))
+
+
+def diffusion_cell_gradient_t(N: int, w, p) -> np.ndarray:
+    """F^T(w, p), (N + 1)^3 nodes: the transpose of `diffusion_cell_gradient` in x, as `mg_diffusion_cell_gradient_t` computes it
+    (same bits: the order of `cg_node_t`, mg_diffusion_flux.hip.h).  One accumulator per node starts at +0.0 and takes the cells
+    (k + oz, j + oy, i + ox) around node (i, j, k) in ascending (oz, oy, ox), each offset -1 then 0, cells outside the grid
+    adding nothing; inside a cell q_d = w_c * p_{d,c} (p_{d,c} with `w` None), then for x, y, z: + or - (2.0 * q_d where the
+    node's two other local coordinates in the cell are equal, else q_d), + where the offset along that axis is -1; the sum
+    times N / 6.0."""
+    n1 = N + 1
+    Q = _cell_field3(p, N)
+    if w is not None:
+        wc = _kappa_cells(w, N, 3)
+        Q = np.stack([wc * Q[d] for d in range(3)])
+    pad = np.zeros((3, N + 2, N + 2, N + 2))            # (a cell outside the grid adds 0.0: the accumulator is never -0.0)
+    pad[:, 1:-1, 1:-1, 1:-1] = Q
+    acc = np.zeros((n1, n1, n1))
+    for oz in (-1, 0):
+        for oy in (-1, 0):
+            for ox in (-1, 0):
+                q = pad[:, 1 + oz:1 + oz + n1, 1 + oy:1 + oy + n1, 1 + ox:1 + ox + n1]
+                for d, (off, same) in enumerate(((ox, oy == oz), (oy, ox == oz), (oz, ox == oy))):
+                    t = 2.0 * q[d] if same else q[d]
+                    acc = acc + t if off < 0 else acc - t
+    return np.ascontiguousarray((acc * (N / 6.0)).reshape(-1))
+
+
 def diffusion_apply_dkappa(N: int, dkappa, x, rows: str = "interior", cols: str = "interior", dirichlet_faces=ALL_FACES) -> np.ndarray:
     """(dA/dkappa . dkappa) x for the 3-D `diffusion_level`: the derivative of A(kappa) x in the direction `dkappa` (N^3 values in
     the cell order of `diffusion_level`, of any sign), as `mg_diffusion_apply_dkappa` computes it.  A is linear in kappa, so an

@@ -120,7 +120,13 @@ class DiffusionSolver:
     works and a Hessian-vector product of a sum over B sources is four batched solves.  `n_solves` grows by B per batched
     solve and `n_batched_solves` by 1; `last_iterations[kind]` is the largest lane count and `last_lane_iterations[kind]`
     holds them all; if any lane reaches `max_iter`, `NotConverged` names the lanes.  `warm_start` keeps the last batched
-    solution of each kind and reuses it when B is the same.  `tangent` is not batched."""
+    solution of each kind and reuses it when B is the same.  `tangent` is not batched.
+
+    `gradient(u, weight=None)` and `flux(kappa, u)` = -`gradient`(u, kappa) give the cell gradient and the flux q = -kappa grad u
+    of a nodal field, (3, N, N, N) indexed [d, ck, cj, ci]: per cell the mean of grad u_h over its six simplices
+    (`mg_diffusion_cell_gradient`), differentiable in both arguments to second order through F, its transpose and its
+    contraction (`_CellGrad`, `_CellGradT`, `_CellGradDot`), which close under differentiation as D and T do.  They read the top
+    level's grid and nothing else: they work before the first solve and leave the hierarchy and the counters alone."""
 
     def __init__(self, N: int, n_levels: int, averaging: str = "arithmetic", matrix_free_min_rows: Optional[int] = None,
                  rtol: float = 1e-10, max_iter: int = 200, device: int = 0, warm_start: bool = False, dirichlet_faces=None,
@@ -276,6 +282,23 @@ class DiffusionSolver:
             self.hierarchy.set_level_grid(self.top)
             self._grid_only = True
         return _TSigma.apply(w.reshape(-1).to(self.device), x.reshape(-1), self).view(x.shape)
+
+    def gradient(self, u: torch.Tensor, weight: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The cell gradient of the nodal field `u`, (3, N, N, N) indexed [d, ck, cj, ci]: per cell the mean of grad u_h over
+        its six simplices (`mg_diffusion_cell_gradient`), times `weight` (N^3 float64 of any sign in kappa's cell order, on the
+        solver's device or the CPU) where one is given.  Differentiable in both to second order.  `u`: (N + 1)^3 float64 on
+        the solver's device, read as it is (Dirichlet values included).  Works before the first solve and leaves the
+        hierarchy alone: `n_generations` and `n_solves` do not move."""
+        if not self._generated and not self._grid_only:     # the kernel reads the top level's grid and nothing else
+            self.hierarchy.set_level_grid(self.top)
+            self._grid_only = True
+        w = None if weight is None else weight.reshape(-1).to(self.device)
+        return _CellGrad.apply(w, self._same_size(u, "u").reshape(-1), self).view(3, self.N, self.N, self.N)
+
+    def flux(self, kappa: torch.Tensor, u: torch.Tensor) -> torch.Tensor:
+        """q = -kappa grad u per cell, (3, N, N, N): the exact cell average of the flux of the P1 field, -`gradient`(u, kappa).
+        With u a pressure it is the Darcy velocity, with u a temperature the heat flux."""
+        return -self.gradient(u, weight=kappa)
 
     def tangent(self, kappa: torch.Tensor, f: torch.Tensor, dkappa: torch.Tensor, df: Optional[torch.Tensor] = None,
                 g: Optional[torch.Tensor] = None, dg: Optional[torch.Tensor] = None, sigma: Optional[torch.Tensor] = None,
@@ -740,3 +763,78 @@ class _TRobin(torch.autograd.Function):
         grad_w = _DRobin.apply(y, x, ctx.solver, ctx.bit).view(w.shape) if ctx.needs_input_grad[0] else None
         grad_x = _TRobin.apply(w, y, ctx.solver, ctx.bit).view(x.shape) if ctx.needs_input_grad[1] else None
         return grad_w, grad_x, None, None
+
+
+def _cell_field(solver, t: torch.Tensor, count: int, what: str) -> torch.Tensor:
+    n = count * solver.N ** 3
+    if t.dtype != torch.float64 or t.device != solver.device or t.numel() != n:
+        raise ValueError(f"{what} must hold {n} float64 on {solver.device} (got {t.numel()} {t.dtype} on {t.device})")
+    return t.detach().contiguous()
+
+
+class _CellGrad(torch.autograd.Function):
+    """F(w, x) = mg_diffusion_cell_gradient(w, x), 3 N^3: the cell gradient of the nodal field x weighted by the cell field w
+    (None: no weight).  With cotangent P: w_bar = C(P, x), x_bar = F^T(w, P)."""
+
+    @staticmethod
+    def forward(ctx, w, x, solver):
+        wv = None if w is None else _cell_field(solver, w, 1, "the cell weight")
+        xv = solver._device_vector(x, "x")
+        out = torch.empty(3 * solver.N ** 3, dtype=torch.float64, device=solver.device)
+        torch.cuda.current_stream(solver.device).synchronize()
+        solver.hierarchy.diffusion_cell_gradient(solver.top, None if wv is None else wv.data_ptr(), xv.data_ptr(), out.data_ptr())
+        ctx.solver, ctx.weighted = solver, w is not None
+        ctx.save_for_backward(w, x)
+        return out
+
+    @staticmethod
+    def backward(ctx, P):
+        w, x = ctx.saved_tensors
+        grad_w = _CellGradDot.apply(P, x, ctx.solver).view(w.shape) if ctx.weighted and ctx.needs_input_grad[0] else None
+        grad_x = _CellGradT.apply(w, P, ctx.solver).view(x.shape) if ctx.needs_input_grad[1] else None
+        return grad_w, grad_x, None
+
+
+class _CellGradT(torch.autograd.Function):
+    """F^T(w, p) = mg_diffusion_cell_gradient_t(w, p), (N + 1)^3 nodes: the transpose of F in x.  With cotangent y:
+    w_bar = C(p, y), p_bar = F(w, y)."""
+
+    @staticmethod
+    def forward(ctx, w, p, solver):
+        wv = None if w is None else _cell_field(solver, w, 1, "the cell weight")
+        pv = _cell_field(solver, p, 3, "the cell field")
+        out = torch.empty(solver.hierarchy.n_dofs(solver.top), dtype=torch.float64, device=solver.device)
+        torch.cuda.current_stream(solver.device).synchronize()
+        solver.hierarchy.diffusion_cell_gradient_t(solver.top, None if wv is None else wv.data_ptr(), pv.data_ptr(), out.data_ptr())
+        ctx.solver, ctx.weighted = solver, w is not None
+        ctx.save_for_backward(w, p)
+        return out
+
+    @staticmethod
+    def backward(ctx, y):
+        w, p = ctx.saved_tensors
+        grad_w = _CellGradDot.apply(p, y, ctx.solver).view(w.shape) if ctx.weighted and ctx.needs_input_grad[0] else None
+        grad_p = _CellGrad.apply(w, y, ctx.solver).view(p.shape) if ctx.needs_input_grad[1] else None
+        return grad_w, grad_p, None
+
+
+class _CellGradDot(torch.autograd.Function):
+    """C(p, x) = mg_diffusion_cell_gradient_dot(p, x), N^3 cells: p_c . G(x)_c.  With cotangent z: p_bar = F(z, x),
+    x_bar = F^T(z, p)."""
+
+    @staticmethod
+    def forward(ctx, p, x, solver):
+        pv, xv = _cell_field(solver, p, 3, "the cell field"), solver._device_vector(x, "x")
+        out = torch.empty(solver.N ** 3, dtype=torch.float64, device=solver.device)
+        torch.cuda.current_stream(solver.device).synchronize()
+        solver.hierarchy.diffusion_cell_gradient_dot(solver.top, pv.data_ptr(), xv.data_ptr(), out.data_ptr())
+        ctx.solver = solver
+        ctx.save_for_backward(p, x)
+        return out
+
+    @staticmethod
+    def backward(ctx, z):
+        p, x = ctx.saved_tensors
+        grad_p = _CellGrad.apply(z, x, ctx.solver).view(p.shape) if ctx.needs_input_grad[0] else None
+        grad_x = _CellGradT.apply(z, p, ctx.solver).view(x.shape) if ctx.needs_input_grad[1] else None
+        return grad_p, grad_x, None

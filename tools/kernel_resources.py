@@ -3,7 +3,7 @@ code object's notes.
 
     python tools/kernel_resources.py [text=jacobikc]
 
-Names behind tables of DESIGN.md: jacobikc, diffusion_mf, diffusion_mf_batch, diffusion_dkappa, kappa_ingest.
+Names behind tables of DESIGN.md: jacobikc, diffusion_mf, diffusion_mf_batch, diffusion_dkappa, kappa_ingest, cell_grad.
 """
 import os
 import re
