@@ -24,6 +24,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <memory>
 #include <string>
 #include <type_traits>
@@ -3344,6 +3345,129 @@ int fcg_sums(mg_context* c, const Level& L, const double*& parts, int64_t& np, i
     return 0;
 }
 
+// The steps of one solve, in the order fcg_solve calls them; fcg_solve_batch calls the same steps for every lane in lockstep,
+// each with the lane's vectors in the level.  What a solve carries from step to step:
+struct FcgState {
+    const char* who;        // "mg_pcg" / "mg_pcg_batch": the prefix of a refusal
+    FcgArgs a{};
+    FcgWork w{};
+    double tol = 0.0;
+    bool go = false;        // the first residual is above the tolerance: there is an iteration to do
+    int it = 0;
+};
+
+// partial sums of the SpMV (launch_ell with dot): one per block of the level's kernel
+int64_t fcg_spmv_blocks(const mg_context* c, const Level& L) {
+    return L.mf ? (int64_t)mf_plan(c, L).grid : (int64_t)blocks_for(L.nslices, WAVES_PER_BLOCK);
+}
+
+// start: the level's fcg_* vectors and the work buffers; x = V, b = F
+int fcg_start(mg_context* c, int level, FcgState& t) {
+    Level& L = c->L[level];
+    MG_TRY(prepare_cycle(c, level));
+    MG_TRY(vec_alloc(c, L, &L.fcg_x));
+    MG_TRY(vec_alloc(c, L, &L.fcg_p));
+    MG_TRY(vec_alloc(c, L, &L.fcg_q));
+    MG_TRY(vec_alloc(c, L, &L.fcg_b));
+    const int64_t gmax = 4 * std::max(1, c->prop.multiProcessorCount);
+    if (!c->fcg_work) MG_TRY(c->fcg_work.alloc(c, (size_t)(8 + kFcgFold + 3 * gmax)));
+    const int64_t nspmv = fcg_spmv_blocks(c, L);
+    if ((int64_t)c->fcg_spmv.count() < nspmv) MG_TRY(c->fcg_spmv.alloc(c, (size_t)nspmv));
+    t.w = fcg_work(c);
+    const size_t bytes = (size_t)L.xlen * sizeof(double);
+    HIP_TRY(hipMemcpyAsync(L.fcg_b.base, L.f.base, bytes, hipMemcpyDeviceToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(L.fcg_x.base, L.v.base, bytes, hipMemcpyDeviceToDevice, c->stream));
+    return 0;
+}
+
+// ... and the first residual, r = b - A x (in F); a step of its own because the batch fuses it over lanes where it can
+int fcg_first_residual(mg_context* c, Level& L) {
+    return launch_ell(c, L, {.mode = MODE_RESIDUAL, .x_base = L.fcg_x.base, .f_rows = L.fcg_b.rows, .out_rows = L.f.rows});
+}
+
+// tolerance and arguments
+int fcg_arguments(mg_context* c, Level& L, FcgState& t, double rtol, int max_iter) {
+    double bnorm = 0.0, rnorm = 0.0;
+    MG_TRY(norm2(c, L, L.fcg_b.rows, &bnorm));
+    MG_TRY(norm2(c, L, L.f.rows, &rnorm));
+    t.tol = rtol > 0.0 ? rtol * bnorm : -1.0;
+    FcgArgs& a = t.a;
+    a.x = L.fcg_x.rows; a.r = L.f.rows; a.p = L.fcg_p.rows; a.q = L.fcg_q.rows; a.sc = t.w.sc; a.n = L.nloc;
+    for (const double* v : {(const double*)a.x, (const double*)a.r, (const double*)a.p, a.q})
+        if (reinterpret_cast<uintptr_t>(v) % 16) return fail(std::string(t.who) + ": misaligned work vector");
+    t.go = max_iter > 0 && rnorm > t.tol && rnorm > 0.0;
+    return 0;
+}
+
+// the partial sums of fcg_dots (r.z and z.q) summed for fcg_direction
+int fcg_dots_summed(mg_context* c, const Level& L, FcgState& t, int64_t nd) {
+    const double* dots = t.w.part_dots;
+    MG_TRY(fcg_sums(c, L, dots, nd, 2, INT64_MAX, nullptr, t.w.tot_dots));
+    t.a.dots = dots; t.a.nd = (int)nd;
+    return 0;
+}
+
+// first direction, after z = M r: p = z
+int fcg_first_direction(mg_context* c, const Level& L, FcgState& t) {
+    const dim3 grid(fcg_grid(c, L)), blk(BLOCK);
+    t.a.out = t.w.part_dots;
+    hipLaunchKernelGGL(fcg_dots<false>, grid, blk, 0, c->stream, t.a);
+    hipLaunchKernelGGL(fcg_direction<true>, grid, blk, 0, c->stream, t.a);
+    return fcg_dots_summed(c, L, t, grid.x);
+}
+
+// q = A p with the partial sums of p.q in c->fcg_spmv (one lane; the batch fuses lanes where it can)
+int fcg_spmv(mg_context* c, Level& L, const FcgState& t, unsigned* nsp) {
+    MG_TRY(launch_ell(c, L, {.mode = MODE_SPMV, .dot = true, .x_base = L.fcg_p.base, .out_rows = L.fcg_q.rows, .partials = c->fcg_spmv,
+                             .grid_out = nsp}));
+    if ((size_t)*nsp > c->fcg_spmv.count()) return fail(std::string(t.who) + ": SpMV partial sums overflow");
+    return 0;
+}
+
+// update: alpha from the npq partial sums of p.q, x += alpha p, r -= alpha q, and ||r||^2 (summed over the slabs where
+// `slabs`) on its way to the host slot `rr`; the caller synchronises the stream before it reads it
+int fcg_update_step(mg_context* c, Level& L, FcgState& t, int64_t npq, bool slabs, double* rr) {
+    const dim3 grid(fcg_grid(c, L)), blk(BLOCK);
+    const double* pq = c->fcg_spmv;
+    MG_TRY(fcg_sums(c, L, pq, npq, 1, kFcgFold, t.w.fold_pq, t.w.tot_pq));
+    t.a.pq = pq; t.a.npq = (int)npq;
+    t.a.out = t.w.part_rr;
+    t.a.vz = L.g.lead == 0 && L.xlen == L.nloc ? L.v.rows : nullptr;    // whole levels: fcg_update zeroes V for the next cycle
+    hipLaunchKernelGGL(fcg_update, grid, blk, 0, c->stream, t.a);
+    hipLaunchKernelGGL(fcg_fold, dim3(1), blk, 0, c->stream, t.w.part_rr, (int64_t)grid.x, 1, t.w.tot_rr);
+    HIP_TRY(hipGetLastError());
+    if (slabs) MG_TRY(allreduce_sum(c, t.w.tot_rr, 1));
+    HIP_TRY(hipMemcpyAsync(rr, t.w.tot_rr, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    return 0;
+}
+
+// what the host does with ||r||^2: the history, the count, and whether the solve goes on
+bool fcg_goes_on(FcgState& t, double rr, int max_iter, double* hist) {
+    const double rn = std::sqrt(rr);
+    if (hist) hist[t.it] = rn;
+    ++t.it;
+    return !(rn <= t.tol || rn == 0.0 || t.it >= max_iter);
+}
+
+// next direction, after z = M r: r.z and z.q; p = z + beta p
+int fcg_next_direction(mg_context* c, const Level& L, FcgState& t) {
+    const dim3 grid(fcg_grid(c, L)), blk(BLOCK);
+    t.a.out = t.w.part_dots;
+    hipLaunchKernelGGL(fcg_dots<true>, grid, blk, 0, c->stream, t.a);
+    MG_TRY(fcg_dots_summed(c, L, t, grid.x));
+    hipLaunchKernelGGL(fcg_direction<false>, grid, blk, 0, c->stream, t.a);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// finish: V = x, F = b bit for bit (R = F - A x is the caller's)
+int fcg_finish(mg_context* c, Level& L) {
+    const size_t bytes = (size_t)L.xlen * sizeof(double);
+    HIP_TRY(hipMemcpyAsync(L.v.base, L.fcg_x.base, bytes, hipMemcpyDeviceToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(L.f.base, L.fcg_b.base, bytes, hipMemcpyDeviceToDevice, c->stream));
+    return 0;
+}
+
 // z = one V(mu1, mu2) cycle from a zero guess on r (= F); the cycle may swap the level's V buffers, so z is read after it.
 // v_zeroed: fcg_update has zeroed V (whole levels: V is the owned rows and nothing else)
 int fcg_precondition(mg_context* c, int level, FcgArgs& a, bool v_zeroed) {
@@ -3357,90 +3481,31 @@ int fcg_precondition(mg_context* c, int level, FcgArgs& a, bool v_zeroed) {
 
 int fcg_solve(mg_context* c, int level, double rtol, int max_iter, double* hist, int* iters_out) {
     Level& L = c->L[level];
-    MG_TRY(prepare_cycle(c, level));
-    MG_TRY(vec_alloc(c, L, &L.fcg_x));
-    MG_TRY(vec_alloc(c, L, &L.fcg_p));
-    MG_TRY(vec_alloc(c, L, &L.fcg_q));
-    MG_TRY(vec_alloc(c, L, &L.fcg_b));
-    const int64_t gmax = 4 * std::max(1, c->prop.multiProcessorCount);
-    if (!c->fcg_work) {
-        MG_TRY(c->fcg_work.alloc(c, (size_t)(8 + kFcgFold + 3 * gmax)));
-    }
-    // partial sums of the SpMV (launch_ell with dot): one per block of the level's kernel
-    const int64_t nspmv = L.mf ? (int64_t)mf_plan(c, L).grid : (int64_t)blocks_for(L.nslices, WAVES_PER_BLOCK);
-    if ((int64_t)c->fcg_spmv.count() < nspmv) MG_TRY(c->fcg_spmv.alloc(c, (size_t)nspmv));
-    const FcgWork w = fcg_work(c);
-    const size_t bytes = (size_t)L.xlen * sizeof(double);
-
-    // x = V, b = F, r = F - A x (in F)
-    HIP_TRY(hipMemcpyAsync(L.fcg_b.base, L.f.base, bytes, hipMemcpyDeviceToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(L.fcg_x.base, L.v.base, bytes, hipMemcpyDeviceToDevice, c->stream));
+    FcgState t{"mg_pcg"};
+    MG_TRY(fcg_start(c, level, t));
     MG_TRY(exchange_halo(c, L, L.fcg_x));
-    MG_TRY(launch_ell(c, L, {.mode = MODE_RESIDUAL, .x_base = L.fcg_x.base, .f_rows = L.fcg_b.rows, .out_rows = L.f.rows}));
-    double bnorm = 0.0, rnorm = 0.0;
-    MG_TRY(norm2(c, L, L.fcg_b.rows, &bnorm));
-    MG_TRY(norm2(c, L, L.f.rows, &rnorm));
-    const double tol = rtol > 0.0 ? rtol * bnorm : -1.0;
-
-    FcgArgs a{};
-    a.x = L.fcg_x.rows; a.r = L.f.rows; a.p = L.fcg_p.rows; a.q = L.fcg_q.rows; a.sc = w.sc; a.n = L.nloc;
-    for (const double* v : {(const double*)a.x, (const double*)a.r, (const double*)a.p, a.q})
-        if (reinterpret_cast<uintptr_t>(v) % 16) return fail("mg_pcg: misaligned work vector");
-    const dim3 grid(fcg_grid(c, L)), blk(BLOCK);
-    int it = 0;
-    if (max_iter > 0 && rnorm > tol && rnorm > 0.0) {
-        // z = M r, p = z
-        MG_TRY(fcg_precondition(c, level, a, false));
-        a.out = w.part_dots;
-        hipLaunchKernelGGL(fcg_dots<false>, grid, blk, 0, c->stream, a);
-        hipLaunchKernelGGL(fcg_direction<true>, grid, blk, 0, c->stream, a);
-        const double* dots = w.part_dots;
-        int64_t nd = grid.x;
-        MG_TRY(fcg_sums(c, L, dots, nd, 2, INT64_MAX, nullptr, w.tot_dots));
-        a.dots = dots; a.nd = (int)nd;
+    MG_TRY(fcg_first_residual(c, L));
+    MG_TRY(fcg_arguments(c, L, t, rtol, max_iter));
+    if (t.go) {
+        MG_TRY(fcg_precondition(c, level, t.a, false));
+        MG_TRY(fcg_first_direction(c, L, t));
         for (;;) {
-            // q = A p with the partial sums of p.q
             MG_TRY(exchange_halo(c, L, L.fcg_p));
             unsigned nsp = 0;
-            MG_TRY(launch_ell(c, L, {.mode = MODE_SPMV, .dot = true, .x_base = L.fcg_p.base, .out_rows = L.fcg_q.rows, .partials = c->fcg_spmv,
-                                     .grid_out = &nsp}));
-            if ((size_t)nsp > c->fcg_spmv.count()) return fail("mg_pcg: SpMV partial sums overflow");
-            const double* pq = c->fcg_spmv;
-            int64_t npq = nsp;
-            MG_TRY(fcg_sums(c, L, pq, npq, 1, kFcgFold, w.fold_pq, w.tot_pq));
-            a.pq = pq; a.npq = (int)npq;
-            // alpha, x += alpha p, r -= alpha q, ||r||^2 to the host
-            a.out = w.part_rr;
-            a.vz = L.g.lead == 0 && L.xlen == L.nloc ? L.v.rows : nullptr;
-            hipLaunchKernelGGL(fcg_update, grid, blk, 0, c->stream, a);
-            hipLaunchKernelGGL(fcg_fold, dim3(1), blk, 0, c->stream, w.part_rr, (int64_t)grid.x, 1, w.tot_rr);
-            HIP_TRY(hipGetLastError());
-            if (!L.replicated) MG_TRY(allreduce_sum(c, w.tot_rr, 1));
-            HIP_TRY(hipMemcpyAsync(c->h_scalars, w.tot_rr, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+            MG_TRY(fcg_spmv(c, L, t, &nsp));
+            MG_TRY(fcg_update_step(c, L, t, nsp, !L.replicated, c->h_scalars));
             HIP_TRY(hipStreamSynchronize(c->stream));
-            const double rn = std::sqrt(c->h_scalars[0]);
-            if (hist) hist[it] = rn;
-            ++it;
-            if (rn <= tol || rn == 0.0 || it >= max_iter) break;
-            // z = M r; r.z and z.q; p = z + beta p
-            MG_TRY(fcg_precondition(c, level, a, a.vz != nullptr));
-            a.out = w.part_dots;
-            hipLaunchKernelGGL(fcg_dots<true>, grid, blk, 0, c->stream, a);
-            dots = w.part_dots;
-            nd = grid.x;
-            MG_TRY(fcg_sums(c, L, dots, nd, 2, INT64_MAX, nullptr, w.tot_dots));
-            a.dots = dots; a.nd = (int)nd;
-            hipLaunchKernelGGL(fcg_direction<false>, grid, blk, 0, c->stream, a);
-            HIP_TRY(hipGetLastError());
+            if (!fcg_goes_on(t, c->h_scalars[0], max_iter, hist)) break;
+            MG_TRY(fcg_precondition(c, level, t.a, t.a.vz != nullptr));
+            MG_TRY(fcg_next_direction(c, L, t));
         }
     }
-    // V = x, F = b bit for bit, R = F - A x
-    HIP_TRY(hipMemcpyAsync(L.v.base, L.fcg_x.base, bytes, hipMemcpyDeviceToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(L.f.base, L.fcg_b.base, bytes, hipMemcpyDeviceToDevice, c->stream));
+    // ... and R = F - A x
+    MG_TRY(fcg_finish(c, L));
     MG_TRY(exchange_halo(c, L, L.v));
     MG_TRY(residual(c, level));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    if (iters_out) *iters_out = it;
+    if (iters_out) *iters_out = t.it;
     return 0;
 }
 
@@ -3603,39 +3668,13 @@ int vcycle_batch(mg_context* c, BatchScope& s, int level, const std::vector<int>
 // as fcg_solve leaves them.  hist: nb rows of `stride` entries.
 int fcg_solve_batch(mg_context* c, BatchScope& s, int level, int nb, double rtol, int max_iter, double* hist, int stride, int* iters_out) {
     Level& L = c->L[level];
-    struct LaneState {
-        FcgArgs a{};
-        FcgWork w{};
-        double tol = 0.0;
-        int it = 0;
-    };
-    std::vector<LaneState> st((size_t)nb);
+    std::vector<FcgState> st((size_t)nb, FcgState{"mg_pcg_batch"});
     std::vector<int> all((size_t)nb), act;
     for (int b = 0; b < nb; ++b) all[(size_t)b] = b;
-    const int64_t gmax = 4 * std::max(1, c->prop.multiProcessorCount);
-    const int64_t nspmv = L.mf ? (int64_t)mf_plan(c, L).grid : (int64_t)blocks_for(L.nslices, WAVES_PER_BLOCK);
-    const size_t bytes = (size_t)L.xlen * sizeof(double);
-    const dim3 grid(fcg_grid(c, L)), blk(BLOCK);
     if (!c->h_lanes) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&c->h_lanes), MG_BATCH_MAX * sizeof(double), hipHostMallocDefault));
 
-    // x = V, b = F, r = F - A x (in F)
-    MG_TRY(s.each(all, [&](int b) -> int {
-        LaneState& t = st[(size_t)b];
-        MG_TRY(prepare_cycle(c, level));
-        MG_TRY(vec_alloc(c, L, &L.fcg_x));
-        MG_TRY(vec_alloc(c, L, &L.fcg_p));
-        MG_TRY(vec_alloc(c, L, &L.fcg_q));
-        MG_TRY(vec_alloc(c, L, &L.fcg_b));
-        if (!c->fcg_work) MG_TRY(c->fcg_work.alloc(c, (size_t)(8 + kFcgFold + 3 * gmax)));
-        if ((int64_t)c->fcg_spmv.count() < nspmv) MG_TRY(c->fcg_spmv.alloc(c, (size_t)nspmv));
-        t.w = fcg_work(c);
-        HIP_TRY(hipMemcpyAsync(L.fcg_b.base, L.f.base, bytes, hipMemcpyDeviceToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(L.fcg_x.base, L.v.base, bytes, hipMemcpyDeviceToDevice, c->stream));
-        return 0;
-    }));
-    auto first_residual = [&](int) {
-        return launch_ell(c, L, {.mode = MODE_RESIDUAL, .x_base = L.fcg_x.base, .f_rows = L.fcg_b.rows, .out_rows = L.f.rows});
-    };
+    MG_TRY(s.each(all, [&](int b) { return fcg_start(c, level, st[(size_t)b]); }));
+    auto first_residual = [&](int) { return fcg_first_residual(c, L); };
     if (mf_fused(c, L, all.size())) {
         MG_TRY(mf_groups(c, s, L, MODE_RESIDUAL, false, all,
             [&](int b, const double** x, const double** f, double** out, double**) {
@@ -3647,16 +3686,8 @@ int fcg_solve_batch(mg_context* c, BatchScope& s, int level, int nb, double rtol
         MG_TRY(s.each(all, first_residual));
     }
     MG_TRY(s.each(all, [&](int b) -> int {
-        LaneState& t = st[(size_t)b];
-        double bnorm = 0.0, rnorm = 0.0;
-        MG_TRY(norm2(c, L, L.fcg_b.rows, &bnorm));
-        MG_TRY(norm2(c, L, L.f.rows, &rnorm));
-        t.tol = rtol > 0.0 ? rtol * bnorm : -1.0;
-        FcgArgs& a = t.a;
-        a.x = L.fcg_x.rows; a.r = L.f.rows; a.p = L.fcg_p.rows; a.q = L.fcg_q.rows; a.sc = t.w.sc; a.n = L.nloc;
-        for (const double* v : {(const double*)a.x, (const double*)a.r, (const double*)a.p, a.q})
-            if (reinterpret_cast<uintptr_t>(v) % 16) return fail("mg_pcg_batch: misaligned work vector");
-        if (max_iter > 0 && rnorm > t.tol && rnorm > 0.0) act.push_back(b);
+        MG_TRY(fcg_arguments(c, L, st[(size_t)b], rtol, max_iter));
+        if (st[(size_t)b].go) act.push_back(b);
         return 0;
     }));
 
@@ -3672,26 +3703,13 @@ int fcg_solve_batch(mg_context* c, BatchScope& s, int level, int nb, double rtol
     };
     if (!act.empty()) {
         MG_TRY(precondition(false));
-        MG_TRY(s.each(act, [&](int b) -> int {
-            LaneState& t = st[(size_t)b];
-            t.a.out = t.w.part_dots;
-            hipLaunchKernelGGL(fcg_dots<false>, grid, blk, 0, c->stream, t.a);
-            hipLaunchKernelGGL(fcg_direction<true>, grid, blk, 0, c->stream, t.a);
-            const double* dots = t.w.part_dots;
-            int64_t nd = grid.x;
-            MG_TRY(fcg_sums(c, L, dots, nd, 2, INT64_MAX, nullptr, t.w.tot_dots));
-            t.a.dots = dots; t.a.nd = (int)nd;
-            return 0;
-        }));
+        MG_TRY(s.each(act, [&](int b) { return fcg_first_direction(c, L, st[(size_t)b]); }));
     }
+    const int64_t nspmv = fcg_spmv_blocks(c, L);
     while (!act.empty()) {
-        // q = A p with the partial sums of p.q
-        auto spmv_one = [&](int) -> int {
+        auto spmv_one = [&](int b) -> int {
             unsigned nsp = 0;
-            MG_TRY(launch_ell(c, L, {.mode = MODE_SPMV, .dot = true, .x_base = L.fcg_p.base, .out_rows = L.fcg_q.rows, .partials = c->fcg_spmv,
-                                     .grid_out = &nsp}));
-            if ((size_t)nsp > c->fcg_spmv.count()) return fail("mg_pcg_batch: SpMV partial sums overflow");
-            return 0;
+            return fcg_spmv(c, L, st[(size_t)b], &nsp);
         };
         if (mf_fused(c, L, act.size())) {
             MG_TRY(mf_groups(c, s, L, MODE_SPMV, true, act,
@@ -3703,55 +3721,22 @@ int fcg_solve_batch(mg_context* c, BatchScope& s, int level, int nb, double rtol
         } else {
             MG_TRY(s.each(act, spmv_one));
         }
-        // alpha, x += alpha p, r -= alpha q; every lane's ||r||^2 to the host in one round trip; who goes on
-        std::vector<int> next;
-        bool v_zeroed = false;
-        MG_TRY(s.each(act, [&](int b) -> int {
-            LaneState& t = st[(size_t)b];
-            const double* pq = c->fcg_spmv;
-            int64_t npq = nspmv;
-            MG_TRY(fcg_sums(c, L, pq, npq, 1, kFcgFold, t.w.fold_pq, t.w.tot_pq));
-            t.a.pq = pq; t.a.npq = (int)npq;
-            t.a.out = t.w.part_rr;
-            t.a.vz = L.g.lead == 0 && L.xlen == L.nloc ? L.v.rows : nullptr;
-            v_zeroed = t.a.vz != nullptr;
-            hipLaunchKernelGGL(fcg_update, grid, blk, 0, c->stream, t.a);
-            hipLaunchKernelGGL(fcg_fold, dim3(1), blk, 0, c->stream, t.w.part_rr, (int64_t)grid.x, 1, t.w.tot_rr);
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipMemcpyAsync(c->h_lanes + b, t.w.tot_rr, sizeof(double), hipMemcpyDeviceToHost, c->stream));
-            return 0;
-        }));
+        // every lane's ||r||^2 to the host in one round trip; who goes on
+        MG_TRY(s.each(act, [&](int b) { return fcg_update_step(c, L, st[(size_t)b], nspmv, false, c->h_lanes + b); }));
         HIP_TRY(hipStreamSynchronize(c->stream));
-        for (int b : act) {
-            LaneState& t = st[(size_t)b];
-            const double rn = std::sqrt(c->h_lanes[b]);
-            if (hist) hist[(size_t)b * (size_t)stride + (size_t)t.it] = rn;
-            ++t.it;
-            if (!(rn <= t.tol || rn == 0.0 || t.it >= max_iter)) next.push_back(b);
-        }
+        const bool v_zeroed = st[(size_t)act.back()].a.vz != nullptr;
+        std::vector<int> next;
+        for (int b : act)
+            if (fcg_goes_on(st[(size_t)b], c->h_lanes[b], max_iter, hist ? hist + (size_t)b * (size_t)stride : nullptr)) next.push_back(b);
         act = next;
         if (act.empty()) break;
-        // z = M r; r.z and z.q; p = z + beta p
         MG_TRY(precondition(v_zeroed));
-        MG_TRY(s.each(act, [&](int b) -> int {
-            LaneState& t = st[(size_t)b];
-            t.a.out = t.w.part_dots;
-            hipLaunchKernelGGL(fcg_dots<true>, grid, blk, 0, c->stream, t.a);
-            const double* dots = t.w.part_dots;
-            int64_t nd = grid.x;
-            MG_TRY(fcg_sums(c, L, dots, nd, 2, INT64_MAX, nullptr, t.w.tot_dots));
-            t.a.dots = dots; t.a.nd = (int)nd;
-            hipLaunchKernelGGL(fcg_direction<false>, grid, blk, 0, c->stream, t.a);
-            HIP_TRY(hipGetLastError());
-            return 0;
-        }));
+        MG_TRY(s.each(act, [&](int b) { return fcg_next_direction(c, L, st[(size_t)b]); }));
     }
-    // V = x, F = b bit for bit, R = F - A x
+    // ... and R = F - A x
     MG_TRY(s.each(all, [&](int b) -> int {
-        HIP_TRY(hipMemcpyAsync(L.v.base, L.fcg_x.base, bytes, hipMemcpyDeviceToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(L.f.base, L.fcg_b.base, bytes, hipMemcpyDeviceToDevice, c->stream));
         if (iters_out) iters_out[b] = st[(size_t)b].it;
-        return 0;
+        return fcg_finish(c, L);
     }));
     MG_TRY(residual_batch(c, s, level, all));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -3771,6 +3756,12 @@ int gather_from(mg_context* c, Level& L, DVector& v, double* dev) {
     hipLaunchKernelGGL(gather_out, dim3(nb), dim3(256), 0, c->stream, v.base, L.perm, L.n_global, L.row0, L.nloc, L.g.lead, dev);
     HIP_TRY(hipGetLastError());
     return 0;
+}
+
+// true where [p, p + np) and [q, q + nq) have a byte in common
+static bool overlaps(const void* p, size_t np, const void* q, size_t nq) {
+    const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
+    return a < b + nq && b < a + np;
 }
 
 // What both batch entries refuse before anything is launched or allocated: the handle, the level, the lane count, the pointers.
@@ -3808,7 +3799,7 @@ int batch_refusals(mg_context* c, const std::string& who, int level, int nb, con
         if (!o.out) continue;
         for (const Range& q : r) {
             if (&q == &o || (q.out && q.lane <= o.lane)) continue;
-            if (o.p < q.p + len && q.p < o.p + len)
+            if (overlaps(o.p, len, q.p, len))
                 return fail(who + ": " + o.name + "[" + std::to_string(o.lane) + "] overlaps " + q.name + "[" + std::to_string(q.lane) +
                             "]: every lane's output is memory of its own");
         }
@@ -5790,29 +5781,23 @@ int mg_get_vector_device(mg_handle c, int level, int which, double* dev) {
     return 0;
 }
 
-// the pointer checks of the two sensitivity entries; nothing is launched before they pass
-static int need_dkappa_operands(mg_context* c, const char* who, const double* a_dev, const double* b_dev, double* out_dev) {
-    MG_TRY(need_device_pointer(c, a_dev, who, "a"));
-    MG_TRY(need_device_pointer(c, b_dev, who, "b"));
-    MG_TRY(need_device_pointer(c, out_dev, who, "out"));
+// One input of a sensitivity or cell gradient entry, for the checks that pass before anything is launched: device memory of
+// the handle's device (`optional`: or null) and, where `apart` is not null, no byte in common with the output, which other
+// threads read while a thread writes its entries; `apart` is the reason appended to that refusal.
+struct Operand { const char* name; const void* p; size_t bytes; bool optional; const char* apart; };
+
+static int need_operands(mg_context* c, const char* who, std::initializer_list<Operand> in, const void* out, size_t out_bytes) {
+    for (const Operand& o : in)
+        if (o.p || !o.optional) MG_TRY(need_device_pointer(c, o.p, who, o.name));
+    MG_TRY(need_device_pointer(c, out, who, "out"));
+    for (const Operand& o : in)
+        if (o.p && o.apart && overlaps(out, out_bytes, o.p, o.bytes)) return fail(std::string(who) + ": out overlaps " + o.name + o.apart);
     return 0;
 }
 
-static int need_apply_dkappa_operands(mg_context* c, const Level& L, const char* who, const double* dkappa_dev, const double* x_dev,
-                                      double* out_dev) {
-    MG_TRY(need_device_pointer(c, dkappa_dev, who, "dkappa"));
-    MG_TRY(need_device_pointer(c, x_dev, who, "x"));
-    MG_TRY(need_device_pointer(c, out_dev, who, "out"));
-    // the march reads the neighbours of a row (and of a cell) while other workgroups write theirs
-    const size_t nodes = (size_t)L.g.plane * (size_t)L.g.nz * 8, cells = (size_t)L.N * L.N * L.N * 8;
-    const auto overlaps = [](const void* p, size_t np, const void* q, size_t nq) {
-        const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
-        return a < b + nq && b < a + np;
-    };
-    if (overlaps(out_dev, nodes, x_dev, nodes)) return fail(std::string(who) + ": out overlaps x (the march reads a row's neighbours)");
-    if (overlaps(out_dev, nodes, dkappa_dev, cells)) return fail(std::string(who) + ": out overlaps dkappa (the march reads a row's cells)");
-    return 0;
-}
+static size_t node_bytes(const Level& L) { return (size_t)L.g.plane * (size_t)L.g.nz * 8; }
+static size_t cell_bytes(const Level& L) { return (size_t)L.N * L.N * L.N * 8; }
+static size_t face_cell_bytes(const Level& L) { return (size_t)L.N * L.N * 8; }
 
 static int need_node_set(const char* who, const char* what, int value) {
     if (value != MG_NODES_INTERIOR && value != MG_NODES_ALL)
@@ -5821,66 +5806,51 @@ static int need_node_set(const char* who, const char* what, int value) {
     return 0;
 }
 
-int mg_diffusion_dkappa(mg_handle c, int level, const double* a_dev, const double* b_dev, double* out_dev) {
-    MG_TRY(need_dkappa_level(c, level, "mg_diffusion_dkappa"));
-    HIP_TRY(hipSetDevice(c->device));
-    MG_TRY(need_dkappa_operands(c, "mg_diffusion_dkappa", a_dev, b_dev, out_dev));
-    MG_TRY(launch_dkappa(c, c->L[level], a_dev, b_dev, out_dev, c->dkappa_gather != 0));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return 0;
-}
-
-int mg_diffusion_dkappa_ex(mg_handle c, int level, const double* a_dev, int a_nodes, const double* b_dev, int b_nodes, double* out_dev) {
-    const char* who = "mg_diffusion_dkappa_ex";
+// the two kappa sensitivities under the name of the entry called: the plain entries are the _ex forms with both node sets
+// MG_NODES_INTERIOR
+static int diffusion_dkappa(const char* who, mg_context* c, int level, const double* a_dev, int a_nodes, const double* b_dev, int b_nodes,
+                            double* out_dev) {
     MG_TRY(need_dkappa_level(c, level, who));
     MG_TRY(need_node_set(who, "a_nodes", a_nodes));
     MG_TRY(need_node_set(who, "b_nodes", b_nodes));
     HIP_TRY(hipSetDevice(c->device));
-    MG_TRY(need_dkappa_operands(c, who, a_dev, b_dev, out_dev));
-    MG_TRY(launch_dkappa(c, c->L[level], a_dev, b_dev, out_dev, c->dkappa_gather != 0, a_nodes == MG_NODES_ALL, b_nodes == MG_NODES_ALL));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return 0;
-}
-
-int mg_diffusion_apply_dkappa(mg_handle c, int level, const double* dkappa_dev, const double* x_dev, double* out_dev) {
-    const char* who = "mg_diffusion_apply_dkappa";
-    MG_TRY(need_dkappa_level(c, level, who));
-    HIP_TRY(hipSetDevice(c->device));
     const Level& L = c->L[level];
-    MG_TRY(need_apply_dkappa_operands(c, L, who, dkappa_dev, x_dev, out_dev));
-    MG_TRY(launch_apply_dkappa(c, L, dkappa_dev, x_dev, out_dev));
+    MG_TRY(need_operands(c, who, {{"a", a_dev, node_bytes(L), false, nullptr}, {"b", b_dev, node_bytes(L), false, nullptr}}, out_dev, cell_bytes(L)));
+    MG_TRY(launch_dkappa(c, L, a_dev, b_dev, out_dev, c->dkappa_gather != 0, a_nodes == MG_NODES_ALL, b_nodes == MG_NODES_ALL));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return 0;
 }
 
-int mg_diffusion_apply_dkappa_ex(mg_handle c, int level, const double* dkappa_dev, const double* x_dev, int rows, int cols,
-                                 double* out_dev) {
-    const char* who = "mg_diffusion_apply_dkappa_ex";
+static int diffusion_apply_dkappa(const char* who, mg_context* c, int level, const double* dkappa_dev, const double* x_dev, int rows, int cols,
+                                  double* out_dev) {
     MG_TRY(need_dkappa_level(c, level, who));
     MG_TRY(need_node_set(who, "rows", rows));
     MG_TRY(need_node_set(who, "cols", cols));
     HIP_TRY(hipSetDevice(c->device));
     const Level& L = c->L[level];
-    MG_TRY(need_apply_dkappa_operands(c, L, who, dkappa_dev, x_dev, out_dev));
+    // the march reads the neighbours of a row (and of a cell) while other workgroups write theirs
+    MG_TRY(need_operands(c, who, {{"dkappa", dkappa_dev, cell_bytes(L), false, " (the march reads a row's cells)"},
+                                  {"x", x_dev, node_bytes(L), false, " (the march reads a row's neighbours)"}}, out_dev, node_bytes(L)));
     MG_TRY(launch_apply_dkappa(c, L, dkappa_dev, x_dev, out_dev, rows == MG_NODES_ALL, cols == MG_NODES_ALL));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return 0;
 }
 
-// the pointer checks of the two sigma sensitivities: device memory of the handle's device, out apart from the inputs (other
-// threads read them while a thread writes its entry of out)
-static int need_dsigma_operands(mg_context* c, const char* who, const char* first, const void* p, size_t np, const char* second,
-                                const void* q, size_t nq, const void* out, size_t nout) {
-    MG_TRY(need_device_pointer(c, p, who, first));
-    MG_TRY(need_device_pointer(c, q, who, second));
-    MG_TRY(need_device_pointer(c, out, who, "out"));
-    const auto overlaps = [](const void* x, size_t nx, const void* y, size_t ny) {
-        const uintptr_t a = (uintptr_t)x, b = (uintptr_t)y;
-        return a < b + ny && b < a + nx;
-    };
-    if (overlaps(out, nout, p, np)) return fail(std::string(who) + ": out overlaps " + first);
-    if (overlaps(out, nout, q, nq)) return fail(std::string(who) + ": out overlaps " + second);
-    return 0;
+int mg_diffusion_dkappa(mg_handle c, int level, const double* a_dev, const double* b_dev, double* out_dev) {
+    return diffusion_dkappa("mg_diffusion_dkappa", c, level, a_dev, MG_NODES_INTERIOR, b_dev, MG_NODES_INTERIOR, out_dev);
+}
+
+int mg_diffusion_dkappa_ex(mg_handle c, int level, const double* a_dev, int a_nodes, const double* b_dev, int b_nodes, double* out_dev) {
+    return diffusion_dkappa("mg_diffusion_dkappa_ex", c, level, a_dev, a_nodes, b_dev, b_nodes, out_dev);
+}
+
+int mg_diffusion_apply_dkappa(mg_handle c, int level, const double* dkappa_dev, const double* x_dev, double* out_dev) {
+    return diffusion_apply_dkappa("mg_diffusion_apply_dkappa", c, level, dkappa_dev, x_dev, MG_NODES_INTERIOR, MG_NODES_INTERIOR, out_dev);
+}
+
+int mg_diffusion_apply_dkappa_ex(mg_handle c, int level, const double* dkappa_dev, const double* x_dev, int rows, int cols,
+                                 double* out_dev) {
+    return diffusion_apply_dkappa("mg_diffusion_apply_dkappa_ex", c, level, dkappa_dev, x_dev, rows, cols, out_dev);
 }
 
 int mg_diffusion_dsigma(mg_handle c, int level, const double* a_dev, const double* b_dev, double* out_dev) {
@@ -5888,8 +5858,7 @@ int mg_diffusion_dsigma(mg_handle c, int level, const double* a_dev, const doubl
     MG_TRY(need_dkappa_level(c, level, who, "sigma"));
     HIP_TRY(hipSetDevice(c->device));
     const Level& L = c->L[level];
-    const size_t nodes = (size_t)L.g.plane * (size_t)L.g.nz * 8, cells = (size_t)L.N * L.N * L.N * 8;
-    MG_TRY(need_dsigma_operands(c, who, "a", a_dev, nodes, "b", b_dev, nodes, out_dev, cells));
+    MG_TRY(need_operands(c, who, {{"a", a_dev, node_bytes(L), false, ""}, {"b", b_dev, node_bytes(L), false, ""}}, out_dev, cell_bytes(L)));
     MG_TRY(launch_dsigma(c, L, a_dev, b_dev, out_dev));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return 0;
@@ -5900,8 +5869,7 @@ int mg_diffusion_apply_dsigma(mg_handle c, int level, const double* dsigma_dev, 
     MG_TRY(need_dkappa_level(c, level, who, "sigma"));
     HIP_TRY(hipSetDevice(c->device));
     const Level& L = c->L[level];
-    const size_t nodes = (size_t)L.g.plane * (size_t)L.g.nz * 8, cells = (size_t)L.N * L.N * L.N * 8;
-    MG_TRY(need_dsigma_operands(c, who, "dsigma", dsigma_dev, cells, "x", x_dev, nodes, out_dev, nodes));
+    MG_TRY(need_operands(c, who, {{"dsigma", dsigma_dev, cell_bytes(L), false, ""}, {"x", x_dev, node_bytes(L), false, ""}}, out_dev, node_bytes(L)));
     MG_TRY(launch_apply_dsigma(c, L, dsigma_dev, x_dev, out_dev));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return 0;
@@ -5924,8 +5892,7 @@ int mg_diffusion_drobin(mg_handle c, int level, int face, const double* a_dev, c
     MG_TRY(need_drobin_face(c, who, face, &fi));
     HIP_TRY(hipSetDevice(c->device));
     const Level& L = c->L[level];
-    const size_t nodes = (size_t)L.g.plane * (size_t)L.g.nz * 8, cells = (size_t)L.N * L.N * 8;
-    MG_TRY(need_dsigma_operands(c, who, "a", a_dev, nodes, "b", b_dev, nodes, out_dev, cells));
+    MG_TRY(need_operands(c, who, {{"a", a_dev, node_bytes(L), false, ""}, {"b", b_dev, node_bytes(L), false, ""}}, out_dev, face_cell_bytes(L)));
     MG_TRY(launch_drobin(c, L, fi, a_dev, b_dev, out_dev));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return 0;
@@ -5938,8 +5905,7 @@ int mg_diffusion_apply_drobin(mg_handle c, int level, int face, const double* da
     MG_TRY(need_drobin_face(c, who, face, &fi));
     HIP_TRY(hipSetDevice(c->device));
     const Level& L = c->L[level];
-    const size_t nodes = (size_t)L.g.plane * (size_t)L.g.nz * 8, cells = (size_t)L.N * L.N * 8;
-    MG_TRY(need_dsigma_operands(c, who, "dalpha", dalpha_dev, cells, "x", x_dev, nodes, out_dev, nodes));
+    MG_TRY(need_operands(c, who, {{"dalpha", dalpha_dev, face_cell_bytes(L), false, ""}, {"x", x_dev, node_bytes(L), false, ""}}, out_dev, node_bytes(L)));
     MG_TRY(launch_apply_drobin(c, L, fi, dalpha_dev, x_dev, out_dev));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return 0;
@@ -5955,29 +5921,12 @@ static int need_cell_grad_level(mg_context* c, int level, const char* who) {
     return 0;
 }
 
-// ... and their pointers: device memory of the handle's device (`w`, the one that may be null, is `first` of F and F^T), out
-// apart from the inputs (other threads read them while a thread writes its entries of out)
-static int need_cell_grad_operands(mg_context* c, const char* who, const char* first, const void* p, size_t np, bool first_optional,
-                                   const char* second, const void* q, size_t nq, const void* out, size_t nout) {
-    if (p || !first_optional) MG_TRY(need_device_pointer(c, p, who, first));
-    MG_TRY(need_device_pointer(c, q, who, second));
-    MG_TRY(need_device_pointer(c, out, who, "out"));
-    const auto overlaps = [](const void* x, size_t nx, const void* y, size_t ny) {
-        const uintptr_t a = (uintptr_t)x, b = (uintptr_t)y;
-        return a < b + ny && b < a + nx;
-    };
-    if (p && overlaps(out, nout, p, np)) return fail(std::string(who) + ": out overlaps " + first);
-    if (overlaps(out, nout, q, nq)) return fail(std::string(who) + ": out overlaps " + second);
-    return 0;
-}
-
 int mg_diffusion_cell_gradient(mg_handle c, int level, const double* w_dev, const double* x_dev, double* out_dev) {
     const char* who = "mg_diffusion_cell_gradient";
     MG_TRY(need_cell_grad_level(c, level, who));
     HIP_TRY(hipSetDevice(c->device));
     const Level& L = c->L[level];
-    const size_t nodes = (size_t)L.g.plane * (size_t)L.g.nz * 8, cells = (size_t)L.N * L.N * L.N * 8;
-    MG_TRY(need_cell_grad_operands(c, who, "w", w_dev, cells, true, "x", x_dev, nodes, out_dev, 3 * cells));
+    MG_TRY(need_operands(c, who, {{"w", w_dev, cell_bytes(L), true, ""}, {"x", x_dev, node_bytes(L), false, ""}}, out_dev, 3 * cell_bytes(L)));
     MG_TRY(launch_cell_grad<CG_F>(c, L, w_dev, nullptr, x_dev, out_dev));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return 0;
@@ -5988,8 +5937,7 @@ int mg_diffusion_cell_gradient_t(mg_handle c, int level, const double* w_dev, co
     MG_TRY(need_cell_grad_level(c, level, who));
     HIP_TRY(hipSetDevice(c->device));
     const Level& L = c->L[level];
-    const size_t nodes = (size_t)L.g.plane * (size_t)L.g.nz * 8, cells = (size_t)L.N * L.N * L.N * 8;
-    MG_TRY(need_cell_grad_operands(c, who, "w", w_dev, cells, true, "p", p_dev, 3 * cells, out_dev, nodes));
+    MG_TRY(need_operands(c, who, {{"w", w_dev, cell_bytes(L), true, ""}, {"p", p_dev, 3 * cell_bytes(L), false, ""}}, out_dev, node_bytes(L)));
     MG_TRY(launch_cell_grad_t(c, L, w_dev, p_dev, out_dev));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return 0;
@@ -6000,8 +5948,7 @@ int mg_diffusion_cell_gradient_dot(mg_handle c, int level, const double* p_dev, 
     MG_TRY(need_cell_grad_level(c, level, who));
     HIP_TRY(hipSetDevice(c->device));
     const Level& L = c->L[level];
-    const size_t nodes = (size_t)L.g.plane * (size_t)L.g.nz * 8, cells = (size_t)L.N * L.N * L.N * 8;
-    MG_TRY(need_cell_grad_operands(c, who, "p", p_dev, 3 * cells, false, "x", x_dev, nodes, out_dev, cells));
+    MG_TRY(need_operands(c, who, {{"p", p_dev, 3 * cell_bytes(L), false, ""}, {"x", x_dev, node_bytes(L), false, ""}}, out_dev, cell_bytes(L)));
     MG_TRY(launch_cell_grad<CG_C>(c, L, nullptr, p_dev, x_dev, out_dev));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return 0;

@@ -700,6 +700,41 @@ class DeviceHierarchy:
         values = [_NODE_SETS[name] for name in sets.values()]
         return values if any(values) else None
 
+    def _sensitivity(self, entry, operands, n_out, out):
+        """One sensitivity or cell gradient entry, `entry(*operand pointers, out pointer)`, on integer device addresses --
+        `out` is then required and nothing is returned -- or, for tests, on NumPy arrays, which are uploaded, and the result
+        (`n_out` values) comes back as a NumPy array (into `out` if given).  `operands`: (name, value, length, may be None)
+        each; a None that may be one is passed as a null pointer.  An array given for two operands of one length (`a is b`)
+        is uploaded once and its pointer passed twice."""
+        is_address = lambda v: isinstance(v, (int, np.integer))
+        given = [(name, v) for name, v, _, optional in operands if not (optional and v is None)]
+        names = [name for name, _ in given]
+        addresses = [is_address(v) for _, v in given]
+        if all(addresses):
+            if not is_address(out):
+                raise TypeError(("with device addresses for " if len(names) > 1 else "with a device address for ") +
+                                " and ".join(names) + ", out must be a device address too")
+            check(entry(*[C.c_void_p(0 if v is None else int(v)) for _, v, _, _ in operands], C.c_void_p(int(out))))
+            return None
+        if any(addresses) or is_address(out):
+            raise TypeError(", ".join(names) + " and out must be all device addresses or all NumPy arrays")
+        held = {}
+        try:
+            for _, v, n, optional in operands:
+                if not (optional and v is None) and (id(v), n) not in held:
+                    held[id(v), n] = _DeviceArray(self._lib, self.device, n, _capi.as_f64(v, n))
+            result = held["out"] = _DeviceArray(self._lib, self.device, n_out)
+            check(entry(*[C.c_void_p(0) if optional and v is None else held[id(v), n].ptr for _, v, n, optional in operands],
+                        result.ptr))
+            got = result.download()
+        finally:
+            for d in held.values():
+                d.free()
+        if out is None:
+            return got
+        out.reshape(-1)[:] = got
+        return out
+
     def diffusion_dkappa(self, level: int, a, b, out=None, a_nodes: str = "interior", b_nodes: str = "interior"):
         """d(a^T A(kappa) b) / d kappa for every cell of a 3-D grid level (`mg_diffusion_dkappa`; host restatement:
         `poisson.diffusion_dkappa`).  `a`, `b` (lexicographic nodal values, boundary entries count as 0) and `out`
@@ -713,30 +748,8 @@ class DeviceHierarchy:
             entry = lambda pa, pb, po: self._lib.mg_diffusion_dkappa(self._h, self._idx(level), pa, pb, po)
         else:
             entry = lambda pa, pb, po: self._lib.mg_diffusion_dkappa_ex(self._h, self._idx(level), pa, sets[0], pb, sets[1], po)
-        cells = self.elements(level) ** 3
-        integers = [isinstance(x, (int, np.integer)) for x in (a, b)]
-        if all(integers):
-            if not isinstance(out, (int, np.integer)):
-                raise TypeError("with device addresses for a and b, out must be a device address too")
-            check(entry(C.c_void_p(int(a)), C.c_void_p(int(b)), C.c_void_p(int(out))))
-            return None
-        if any(integers) or isinstance(out, (int, np.integer)):
-            raise TypeError("a, b and out must be all device addresses or all NumPy arrays")
         n = self.n_dofs(level)
-        held = []
-        try:
-            held.append(_DeviceArray(self._lib, self.device, n, _capi.as_f64(a, n)))
-            held.append(held[0] if b is a else _DeviceArray(self._lib, self.device, n, _capi.as_f64(b, n)))
-            held.append(_DeviceArray(self._lib, self.device, cells))
-            check(entry(held[0].ptr, held[1].ptr, held[2].ptr))
-            got = held[2].download()
-        finally:
-            for d in held:
-                d.free()
-        if out is None:
-            return got
-        out.reshape(-1)[:] = got
-        return out
+        return self._sensitivity(entry, [("a", a, n, False), ("b", b, n, False)], self.elements(level) ** 3, out)
 
     def diffusion_apply_dkappa(self, level: int, dkappa, x, out=None, rows: str = "interior", cols: str = "interior"):
         """(dA/dkappa . dkappa) x on a 3-D grid level, the derivative of A(kappa) x in the direction `dkappa`
@@ -751,56 +764,8 @@ class DeviceHierarchy:
             entry = lambda pk, px, po: self._lib.mg_diffusion_apply_dkappa(self._h, self._idx(level), pk, px, po)
         else:
             entry = lambda pk, px, po: self._lib.mg_diffusion_apply_dkappa_ex(self._h, self._idx(level), pk, px, sets[0], sets[1], po)
-        cells = self.elements(level) ** 3
-        integers = [isinstance(v, (int, np.integer)) for v in (dkappa, x)]
-        if all(integers):
-            if not isinstance(out, (int, np.integer)):
-                raise TypeError("with device addresses for dkappa and x, out must be a device address too")
-            check(entry(C.c_void_p(int(dkappa)), C.c_void_p(int(x)), C.c_void_p(int(out))))
-            return None
-        if any(integers) or isinstance(out, (int, np.integer)):
-            raise TypeError("dkappa, x and out must be all device addresses or all NumPy arrays")
         n = self.n_dofs(level)
-        held = []
-        try:
-            held.append(_DeviceArray(self._lib, self.device, cells, _capi.as_f64(dkappa, cells)))
-            held.append(_DeviceArray(self._lib, self.device, n, _capi.as_f64(x, n)))
-            held.append(_DeviceArray(self._lib, self.device, n))
-            check(entry(held[0].ptr, held[1].ptr, held[2].ptr))
-            got = held[2].download()
-        finally:
-            for d in held:
-                d.free()
-        if out is None:
-            return got
-        out.reshape(-1)[:] = got
-        return out
-
-    def _sigma_entry(self, entry, names, first, n_first, second, n_second, out, n_out):
-        """One of the two sigma sensitivity entries on device addresses or, for tests, on NumPy arrays (uploaded; the
-        result comes back as a NumPy array, into `out` if given)."""
-        integers = [isinstance(v, (int, np.integer)) for v in (first, second)]
-        if all(integers):
-            if not isinstance(out, (int, np.integer)):
-                raise TypeError(f"with device addresses for {names}, out must be a device address too")
-            check(entry(C.c_void_p(int(first)), C.c_void_p(int(second)), C.c_void_p(int(out))))
-            return None
-        if any(integers) or isinstance(out, (int, np.integer)):
-            raise TypeError(f"{names} and out must be all device addresses or all NumPy arrays")
-        held = []
-        try:
-            held.append(_DeviceArray(self._lib, self.device, n_first, _capi.as_f64(first, n_first)))
-            held.append(held[0] if second is first else _DeviceArray(self._lib, self.device, n_second, _capi.as_f64(second, n_second)))
-            held.append(_DeviceArray(self._lib, self.device, n_out))
-            check(entry(held[0].ptr, held[1].ptr, held[2].ptr))
-            got = held[2].download()
-        finally:
-            for d in held:
-                d.free()
-        if out is None:
-            return got
-        out.reshape(-1)[:] = got
-        return out
+        return self._sensitivity(entry, [("dkappa", dkappa, self.elements(level) ** 3, False), ("x", x, n, False)], n, out)
 
     def diffusion_dsigma(self, level: int, a, b, out=None):
         """D_sigma(a, b): d(a^T R(sigma) b) / d sigma for every cell of a 3-D grid level (`mg_diffusion_dsigma`; host
@@ -809,7 +774,7 @@ class DeviceHierarchy:
         arrays, as in `diffusion_dkappa`."""
         entry = lambda pa, pb, po: self._lib.mg_diffusion_dsigma(self._h, self._idx(level), pa, pb, po)
         n = self.n_dofs(level)
-        return self._sigma_entry(entry, "a and b", a, n, b, n, out, self.elements(level) ** 3)
+        return self._sensitivity(entry, [("a", a, n, False), ("b", b, n, False)], self.elements(level) ** 3, out)
 
     def diffusion_apply_dsigma(self, level: int, dsigma, x, out=None):
         """T_sigma(dsigma, x) = R(dsigma) x on the free nodes of the handle's face set, 0 on its Dirichlet nodes
@@ -818,7 +783,7 @@ class DeviceHierarchy:
         arrays, as in `diffusion_apply_dkappa`."""
         entry = lambda ps, px, po: self._lib.mg_diffusion_apply_dsigma(self._h, self._idx(level), ps, px, po)
         n = self.n_dofs(level)
-        return self._sigma_entry(entry, "dsigma and x", dsigma, self.elements(level) ** 3, x, n, out, n)
+        return self._sensitivity(entry, [("dsigma", dsigma, self.elements(level) ** 3, False), ("x", x, n, False)], n, out)
 
     def diffusion_drobin(self, level: int, face, a, b, out=None):
         """D_alpha,F(a, b): d(a^T B(alpha) b) / d alpha for every boundary face-cell of `face` on a 3-D grid level
@@ -828,7 +793,7 @@ class DeviceHierarchy:
         bit = poisson._one_face(face)
         entry = lambda pa, pb, po: self._lib.mg_diffusion_drobin(self._h, self._idx(level), bit, pa, pb, po)
         n = self.n_dofs(level)
-        return self._sigma_entry(entry, "a and b", a, n, b, n, out, self.elements(level) ** 2)
+        return self._sensitivity(entry, [("a", a, n, False), ("b", b, n, False)], self.elements(level) ** 2, out)
 
     def diffusion_apply_drobin(self, level: int, face, dalpha, x, out=None):
         """T_alpha,F(dalpha, x) = b_F(dalpha) x on the free nodes of `face`, 0 on every other node
@@ -838,33 +803,7 @@ class DeviceHierarchy:
         bit = poisson._one_face(face)
         entry = lambda pw, px, po: self._lib.mg_diffusion_apply_drobin(self._h, self._idx(level), bit, pw, px, po)
         n = self.n_dofs(level)
-        return self._sigma_entry(entry, "dalpha and x", dalpha, self.elements(level) ** 2, x, n, out, n)
-
-    def _weighted_entry(self, entry, names, w, n_w, second, n_second, out, n_out):
-        """`_sigma_entry` for the two cell gradient entries whose first operand, the cell weight `w`, may be None (a null
-        pointer: no weight)."""
-        if w is not None:
-            return self._sigma_entry(entry, names, w, n_w, second, n_second, out, n_out)
-        if isinstance(second, (int, np.integer)):
-            if not isinstance(out, (int, np.integer)):
-                raise TypeError(f"with a device address for {names}, out must be a device address too")
-            check(entry(C.c_void_p(0), C.c_void_p(int(second)), C.c_void_p(int(out))))
-            return None
-        if isinstance(out, (int, np.integer)):
-            raise TypeError(f"{names} and out must be all device addresses or all NumPy arrays")
-        held = []
-        try:
-            held.append(_DeviceArray(self._lib, self.device, n_second, _capi.as_f64(second, n_second)))
-            held.append(_DeviceArray(self._lib, self.device, n_out))
-            check(entry(C.c_void_p(0), held[0].ptr, held[1].ptr))
-            got = held[1].download()
-        finally:
-            for d in held:
-                d.free()
-        if out is None:
-            return got
-        out.reshape(-1)[:] = got
-        return out
+        return self._sensitivity(entry, [("dalpha", dalpha, self.elements(level) ** 2, False), ("x", x, n, False)], n, out)
 
     def diffusion_cell_gradient(self, level: int, w, x, out=None):
         """F(w, x): the cell gradient of the nodal field `x` weighted by the cell field `w` on a 3-D grid level, 3 N^3 values with
@@ -873,7 +812,7 @@ class DeviceHierarchy:
         of the flux.  Device addresses or NumPy arrays, as in `diffusion_dkappa`."""
         entry = lambda pw, px, po: self._lib.mg_diffusion_cell_gradient(self._h, self._idx(level), pw, px, po)
         cells = self.elements(level) ** 3
-        return self._weighted_entry(entry, "w and x" if w is not None else "x", w, cells, x, self.n_dofs(level), out, 3 * cells)
+        return self._sensitivity(entry, [("w", w, cells, True), ("x", x, self.n_dofs(level), False)], 3 * cells, out)
 
     def diffusion_cell_gradient_t(self, level: int, w, p, out=None):
         """F^T(w, p): the transpose of `diffusion_cell_gradient` in x, applied to the 3-component cell field `p` (3 N^3), nodal
@@ -881,7 +820,7 @@ class DeviceHierarchy:
         `diffusion_cell_gradient`.  Device addresses or NumPy arrays, as in `diffusion_dkappa`."""
         entry = lambda pw, pp, po: self._lib.mg_diffusion_cell_gradient_t(self._h, self._idx(level), pw, pp, po)
         cells = self.elements(level) ** 3
-        return self._weighted_entry(entry, "w and p" if w is not None else "p", w, cells, p, 3 * cells, out, self.n_dofs(level))
+        return self._sensitivity(entry, [("w", w, cells, True), ("p", p, 3 * cells, False)], self.n_dofs(level), out)
 
     def diffusion_cell_gradient_dot(self, level: int, p, x, out=None):
         """C(p, x): per cell the product of the 3-component cell field `p` (3 N^3) with the cell gradient of the nodal field `x`,
@@ -889,7 +828,7 @@ class DeviceHierarchy:
         Device addresses or NumPy arrays, as in `diffusion_dkappa`."""
         entry = lambda pp, px, po: self._lib.mg_diffusion_cell_gradient_dot(self._h, self._idx(level), pp, px, po)
         cells = self.elements(level) ** 3
-        return self._sigma_entry(entry, "p and x", p, 3 * cells, x, self.n_dofs(level), out, cells)
+        return self._sensitivity(entry, [("p", p, 3 * cells, False), ("x", x, self.n_dofs(level), False)], cells, out)
 
     def zero_vector(self, level: int, which: str = "v"):
         check(self._lib.mg_zero_vector(self._h, self._idx(level), _VEC[which]))

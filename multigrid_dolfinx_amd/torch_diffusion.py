@@ -197,29 +197,36 @@ class DiffusionSolver:
         bits = tuple(sorted(fields))
         return bits, tuple(fields[b] for b in bits)
 
+    def _operator_to_reuse(self, same_operator: bool, sigma, bits) -> Optional["_Operator"]:
+        """None, or with `same_operator` the operator of the last solve, which must have had what this one has."""
+        if not same_operator:
+            return None
+        op = self._last_operator
+        if op is None:
+            raise ValueError("same_operator=True reuses the operator of the last solve: there has been none")
+        if (sigma is None) != (op.sigma_kept is None):
+            raise ValueError("same_operator=True: the last solve had " + ("no" if sigma is not None else "a") + " sigma")
+        if bits != tuple(sorted(op.robin_kept)):
+            raise ValueError(f"same_operator=True: the last solve had Robin fields on the faces {sorted(op.robin_kept)}")
+        return op
+
+    def _lifted(self, kv: torch.Tensor, gv: torch.Tensor, fv: torch.Tensor) -> torch.Tensor:
+        """where(boundary, g, f - T(kappa, g_B; interior, all)) for one g and one f, or several rows of them."""
+        boundary = self._boundary_mask()
+        g_b = torch.where(boundary, gv, torch.zeros_like(gv))
+        return torch.where(boundary, gv, fv - _T.apply(kv, g_b, self, _kappa_field("interior", "all")))
+
     def solve(self, kappa: torch.Tensor, f: torch.Tensor, g: Optional[torch.Tensor] = None,
               sigma: Optional[torch.Tensor] = None, same_operator: bool = False, robin=None) -> torch.Tensor:
         bits, alphas = self._robin_inputs(robin)
-        rest = (sigma,) if not bits else (sigma, bits) + alphas     # (what _Solve takes after `warm`)
-        op = None
-        if same_operator:
-            op = self._last_operator
-            if op is None:
-                raise ValueError("same_operator=True reuses the operator of the last solve: there has been none")
-            if (sigma is None) != (op.sigma_kept is None):
-                raise ValueError("same_operator=True: the last solve had " + ("no" if sigma is not None else "a") + " sigma")
-            if bits != tuple(sorted(op.robin_kept)):
-                raise ValueError(f"same_operator=True: the last solve had Robin fields on the faces {sorted(op.robin_kept)}")
+        op = self._operator_to_reuse(same_operator, sigma, bits)
         if g is None:
-            return _Solve.apply(kappa, f, self, op, "forward", True, *rest)
-        boundary = self._boundary_mask()
+            return _Solve.apply(kappa, f, self, op, "forward", True, False, sigma, bits, *alphas)
         gv, fv = self._same_size(g, "g").reshape(-1), self._same_size(f, "f").reshape(-1)
-        g_b = torch.where(boundary, gv, torch.zeros_like(gv))
         if op is None:
             op = self._put_operator(kappa, sigma, dict(zip(bits, alphas)))  # first: the lift runs on the level's grid, which the first generation sets
-        lift = _Tangent.apply(kappa.reshape(-1).to(self.device), g_b, self, "interior", "all")
-        rhs = torch.where(boundary, gv, fv - lift)
-        return _Solve.apply(kappa, rhs.view(f.shape), self, op, "forward", True, *rest)
+        rhs = self._lifted(kappa.reshape(-1).to(self.device), gv, fv)
+        return _Solve.apply(kappa, rhs.view(f.shape), self, op, "forward", True, False, sigma, bits, *alphas)
 
     def solve_many(self, kappa: torch.Tensor, F: torch.Tensor, g: Optional[torch.Tensor] = None,
                    sigma: Optional[torch.Tensor] = None, same_operator: bool = False, robin=None) -> torch.Tensor:
@@ -230,58 +237,43 @@ class DiffusionSolver:
             raise ValueError(f"F must hold B >= 1 leading rows of {n} float64 on {self.device} (got {tuple(F.shape)} {F.dtype} on {F.device})")
         B = F.shape[0]
         bits, alphas = self._robin_inputs(robin)
-        rest = (sigma,) if not bits else (sigma, bits) + alphas     # (what _SolveMany takes after `warm`)
-        op = None
-        if same_operator:
-            op = self._last_operator
-            if op is None:
-                raise ValueError("same_operator=True reuses the operator of the last solve: there has been none")
-            if (sigma is None) != (op.sigma_kept is None):
-                raise ValueError("same_operator=True: the last solve had " + ("no" if sigma is not None else "a") + " sigma")
-            if bits != tuple(sorted(op.robin_kept)):
-                raise ValueError(f"same_operator=True: the last solve had Robin fields on the faces {sorted(op.robin_kept)}")
+        op = self._operator_to_reuse(same_operator, sigma, bits)
         if g is None:
-            return _SolveMany.apply(kappa, F, self, op, "forward", True, *rest)
+            return _Solve.apply(kappa, F, self, op, "forward", True, True, sigma, bits, *alphas)
         if g.dtype != torch.float64 or g.device != self.device or g.numel() not in (n, B * n) or (g.numel() == B * n and B > 1 and g.shape[0] != B):
             raise ValueError(f"g must hold {n} float64 (shared by all lanes) or {B} leading rows of them on {self.device}")
         shared = g.numel() == n and not (B == 1 and g.dim() == F.dim())
-        boundary = self._boundary_mask()
         Fv = F.reshape(B, n)
         if op is None:
             op = self._put_operator(kappa, sigma, dict(zip(bits, alphas)))  # first: the lift runs on the level's grid, which the first generation sets
         kv = kappa.reshape(-1).to(self.device)
-
-        def lifted(gv, fv):
-            g_b = torch.where(boundary, gv, torch.zeros_like(gv))
-            return torch.where(boundary, gv, fv - _Tangent.apply(kv, g_b, self, "interior", "all"))
-
         if shared:      # one lift for all lanes: autograd sums its lanes' contributions
-            gv = g.reshape(-1)
-            g_b = torch.where(boundary, gv, torch.zeros_like(gv))
-            lift = _Tangent.apply(kv, g_b, self, "interior", "all")
-            rhs = torch.where(boundary, gv, Fv - lift)
+            rhs = self._lifted(kv, g.reshape(-1), Fv)
         else:
             gv = g.reshape(B, n)
-            rhs = torch.stack([lifted(gv[b], Fv[b]) for b in range(B)])
-        return _SolveMany.apply(kappa, rhs.view(F.shape), self, op, "forward", True, *rest)
+            rhs = torch.stack([self._lifted(kv, gv[b], Fv[b]) for b in range(B)])
+        return _Solve.apply(kappa, rhs.view(F.shape), self, op, "forward", True, True, sigma, bits, *alphas)
+
+    def _top_level_grid(self):
+        """The kernels of `robin_apply`, `reaction_apply` and `gradient` read the top level's grid and nothing else: before the
+        first solve has generated the level, it becomes a grid-only level."""
+        if not self._generated and not self._grid_only:
+            self.hierarchy.set_level_grid(self.top)
+            self._grid_only = True
 
     def robin_apply(self, face, w: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
         """T_alpha,F(w, x) = b_F(w) x on the free nodes of `face`, 0 on every other node (`mg_diffusion_apply_drobin`),
         differentiable in both: with w = alpha and x = u_ext the ambient load of a Robin face.  `w`: N^2 float64 of any sign,
         on the solver's device or the CPU; `x`: (N + 1)^3 float64 on the solver's device."""
-        if not self._generated and not self._grid_only:     # the kernel reads the top level's grid and nothing else
-            self.hierarchy.set_level_grid(self.top)
-            self._grid_only = True
-        return _TRobin.apply(w.reshape(-1).to(self.device), x.reshape(-1), self, _one_face(face)).view(x.shape)
+        self._top_level_grid()
+        return _T.apply(w.reshape(-1).to(self.device), x.reshape(-1), self, _alpha_field(_one_face(face))).view(x.shape)
 
     def reaction_apply(self, w: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
         """T_sigma(w, x) = R(w) x on the free nodes, 0 on the Dirichlet nodes (`mg_diffusion_apply_dsigma`), differentiable in
         both: with w = 1 / dt in every cell the M u / dt of an implicit Euler step.  `w`: N^3 float64 of any sign, on the
         solver's device or the CPU; `x`: (N + 1)^3 float64 on the solver's device."""
-        if not self._generated and not self._grid_only:     # the kernel reads the top level's grid and nothing else
-            self.hierarchy.set_level_grid(self.top)
-            self._grid_only = True
-        return _TSigma.apply(w.reshape(-1).to(self.device), x.reshape(-1), self).view(x.shape)
+        self._top_level_grid()
+        return _T.apply(w.reshape(-1).to(self.device), x.reshape(-1), self, _SIGMA_FIELD).view(x.shape)
 
     def gradient(self, u: torch.Tensor, weight: Optional[torch.Tensor] = None) -> torch.Tensor:
         """The cell gradient of the nodal field `u`, (3, N, N, N) indexed [d, ck, cj, ci]: per cell the mean of grad u_h over
@@ -289,9 +281,7 @@ class DiffusionSolver:
         solver's device or the CPU) where one is given.  Differentiable in both to second order.  `u`: (N + 1)^3 float64 on
         the solver's device, read as it is (Dirichlet values included).  Works before the first solve and leaves the
         hierarchy alone: `n_generations` and `n_solves` do not move."""
-        if not self._generated and not self._grid_only:     # the kernel reads the top level's grid and nothing else
-            self.hierarchy.set_level_grid(self.top)
-            self._grid_only = True
+        self._top_level_grid()
         w = None if weight is None else weight.reshape(-1).to(self.device)
         return _CellGrad.apply(w, self._same_size(u, "u").reshape(-1), self).view(3, self.N, self.N, self.N)
 
@@ -323,73 +313,58 @@ class DiffusionSolver:
         if set(dbits) - set(bits):
             raise ValueError("drobin holds the directions of robin: it needs a field on each of its faces")
         u = self.solve(kappa, f, g, sigma, robin=robin)
-        if g is None:
-            rhs = _Tangent.apply(dkappa.reshape(-1), u.reshape(-1), self, "interior", "interior").neg()
-            if df is not None:
-                rhs = self._same_size(df, "df").reshape(-1) + rhs
-        else:
-            boundary = self._boundary_mask()
-            rhs = _Tangent.apply(dkappa.reshape(-1), u.reshape(-1), self, "interior", "all").neg()
-            if df is not None:
-                rhs = self._same_size(df, "df").reshape(-1) + rhs
-            on_boundary = torch.zeros_like(rhs)
-            if dg is not None:
-                on_boundary = self._same_size(dg, "dg").reshape(-1)
-                dg_b = torch.where(boundary, on_boundary, torch.zeros_like(on_boundary))
-                rhs = rhs - _Tangent.apply(kappa.detach().reshape(-1).to(self.device), dg_b, self, "interior", "all")
-            if dsigma is not None:
-                rhs = rhs - _TSigma.apply(dsigma.reshape(-1), u.reshape(-1), self)
-            for bit, dalpha in zip(dbits, dalphas):
-                rhs = rhs - _TRobin.apply(dalpha.reshape(-1), u.reshape(-1), self, bit)
-            rhs = torch.where(boundary, on_boundary, rhs)
-        if g is None and dsigma is not None:
-            rhs = rhs - _TSigma.apply(dsigma.reshape(-1), u.reshape(-1), self)
-        if g is None:
-            for bit, dalpha in zip(dbits, dalphas):
-                rhs = rhs - _TRobin.apply(dalpha.reshape(-1), u.reshape(-1), self, bit)
-        rest = (sigma,) if not bits else (sigma, bits) + alphas
-        du = _Solve.apply(kappa, rhs, self, self._last_operator, "tangent", True, *rest)
+        uv = u.reshape(-1)
+        rhs = _T.apply(dkappa.reshape(-1), uv, self, _kappa_field("interior", "interior" if g is None else "all")).neg()
+        if df is not None:
+            rhs = self._same_size(df, "df").reshape(-1) + rhs
+        on_boundary = torch.zeros_like(rhs)
+        if dg is not None:
+            on_boundary = self._same_size(dg, "dg").reshape(-1)
+            dg_b = torch.where(self._boundary_mask(), on_boundary, torch.zeros_like(on_boundary))
+            rhs = rhs - _T.apply(kappa.detach().reshape(-1).to(self.device), dg_b, self, _kappa_field("interior", "all"))
+        if dsigma is not None:
+            rhs = rhs - _T.apply(dsigma.reshape(-1), uv, self, _SIGMA_FIELD)
+        for bit, dalpha in zip(dbits, dalphas):
+            rhs = rhs - _T.apply(dalpha.reshape(-1), uv, self, _alpha_field(bit))
+        if g is not None:
+            rhs = torch.where(self._boundary_mask(), on_boundary, rhs)
+        du = _Solve.apply(kappa, rhs, self, self._last_operator, "tangent", True, False, sigma, bits, *alphas)
         return u, du.view(u.shape)
 
     # ---- what the autograd function calls --------------------------------------------------------------------
+    def _as_library_takes(self, x):
+        """A field as the hierarchy's calls take it: None and a host array as they are, a tensor on the solver's device as its
+        address, once the current stream has finished writing it and the handle's stream may read it."""
+        if x is None or isinstance(x, np.ndarray):
+            return x
+        torch.cuda.current_stream(self.device).synchronize()
+        return x.data_ptr()
+
     def _generate(self, kappa, sigma=None, robin=None) -> int:
         """`kappa`: a host array (today's path) or a contiguous float64 tensor on the solver's device; `sigma`: None, or the
         reaction field as one of the two; `robin`: None, or the Robin fields by face bit, each as one of the two.  The
         handle's fields are set (or cleared) first: the generating calls read them."""
         robin = robin or {}
         for bit in sorted(set(robin) | set(self._generated_robin)):
-            alpha = robin.get(bit)
-            if alpha is None or isinstance(alpha, np.ndarray):
-                self.hierarchy.set_diffusion_robin(bit, alpha)
-            else:
-                torch.cuda.current_stream(self.device).synchronize()
-                self.hierarchy.set_diffusion_robin(bit, alpha.data_ptr(), N=self.N)
+            self.hierarchy.set_diffusion_robin(bit, self._as_library_takes(robin.get(bit)), N=self.N)
         if tuple(sorted(robin)) != self._generated_robin:   # levels with fields on other faces do not refresh into each other
             self._generated = False
         self._generated_robin = tuple(sorted(robin))
         react = sigma is not None
         if react or self._generated_react:
-            if sigma is None or isinstance(sigma, np.ndarray):
-                self.hierarchy.set_diffusion_reaction(sigma)
-            else:
-                torch.cuda.current_stream(self.device).synchronize()
-                self.hierarchy.set_diffusion_reaction(sigma.data_ptr(), N=self.N)
+            self.hierarchy.set_diffusion_reaction(self._as_library_takes(sigma), N=self.N)
         if react != self._generated_react:      # levels with and without a reaction diagonal do not refresh into each other
             self._generated = False
         self._generated_react = react
         self._grid_only = False
-        if isinstance(kappa, np.ndarray):
-            self.hierarchy.gen_diffusion_hierarchy(kappa, self.averaging, matrix_free_min_rows=self.matrix_free_min_rows)
-            self.last_generate = "host"
+        on_host = isinstance(kappa, np.ndarray)
+        if self._generated and not on_host:
+            self.hierarchy.refresh_diffusion_hierarchy(self._as_library_takes(kappa), self.averaging)
+            self.last_generate = "refresh"
         else:
-            torch.cuda.current_stream(self.device).synchronize()    # kappa is complete before the handle's stream reads it
-            if self._generated:
-                self.hierarchy.refresh_diffusion_hierarchy(kappa.data_ptr(), self.averaging)
-                self.last_generate = "refresh"
-            else:
-                self.hierarchy.gen_diffusion_hierarchy(kappa.data_ptr(), self.averaging,
-                                                       matrix_free_min_rows=self.matrix_free_min_rows)
-                self.last_generate = "device"
+            self.hierarchy.gen_diffusion_hierarchy(self._as_library_takes(kappa), self.averaging,
+                                                   matrix_free_min_rows=self.matrix_free_min_rows)
+            self.last_generate = "host" if on_host else "device"
         self._generated = True
         self._generation += 1
         return self._generation
@@ -422,11 +397,13 @@ class DiffusionSolver:
         self._last_operator = op
         return op
 
-    def _same_size(self, x: torch.Tensor, what: str) -> torch.Tensor:
-        n = self.hierarchy.n_dofs(self.top)
+    def _holds(self, x: torch.Tensor, n: int, what: str) -> torch.Tensor:
         if x.dtype != torch.float64 or x.device != self.device or x.numel() != n:
             raise ValueError(f"{what} must hold {n} float64 on {self.device} (got {x.numel()} {x.dtype} on {x.device})")
         return x
+
+    def _same_size(self, x: torch.Tensor, what: str) -> torch.Tensor:
+        return self._holds(x, self.hierarchy.n_dofs(self.top), what)
 
     def _device_vector(self, x: torch.Tensor, what: str) -> torch.Tensor:
         return self._same_size(x, what).detach().contiguous()
@@ -503,32 +480,34 @@ class _Solve(torch.autograd.Function):
     """S(kappa, f) = A(kappa)^-1 f.  `op` None: the caller's solve, which puts kappa into the hierarchy.  `op` given: a solve
     on the operator of an earlier one (from a backward pass, or `tangent`); `kappa` is then only what the gradient is
     taken with respect to (None: nobody asked), and the hierarchy is touched only if another kappa has been solved since.
-    An optional seventh argument is sigma: the operator is A(kappa) + R(sigma), and sigma is to the reaction term what kappa
-    is to the stiffness -- on a given `op`, only what the gradient is taken with respect to.  After sigma (None: no reaction
-    term) may come the Robin fields: the tuple of their face bits, ascending, then one alpha per face -- the operator is
-    A(kappa) + R(sigma) + B(alpha), and each alpha is to its face what sigma is to the reaction term."""
+    After `warm` come, each optional but in this order: `many` (True: `f` holds B leading rows, U[b] = A^-1 F[b] in one batched
+    solve, `DiffusionSolver._pcg_many`), `sigma` (None: no reaction term; the operator is A(kappa) + R(sigma), and sigma is
+    to the reaction term what kappa is to the stiffness -- on a given `op`, only what the gradient is taken with respect to),
+    the tuple of the Robin fields' face bits, ascending, and one alpha per face: the operator is A(kappa) + R(sigma) +
+    B(alpha), and each alpha is to its face what sigma is to the reaction term."""
 
     @staticmethod
-    def forward(ctx, kappa, f, solver, op, which, warm, *rest):
-        sigma = rest[0] if rest else None
-        rhs = solver._device_vector(f, "f" if op is None else "the right-hand side")
-        bits, alphas = (rest[1], rest[2:]) if len(rest) > 1 else ((), ())
+    def forward(ctx, kappa, f, solver, op, which, warm, *fields):
+        many, sigma, bits, *alphas = fields + (False, None, ())[len(fields):]
+        if many:
+            n = solver.hierarchy.n_dofs(solver.top)
+            if f.dtype != torch.float64 or f.device != solver.device or f.dim() < 2 or f[0].numel() != n:
+                raise ValueError(f"the right-hand sides must hold leading rows of {n} float64 on {solver.device}")
+            rhs = f.detach().contiguous().view(f.shape[0], n)
+        else:
+            rhs = solver._device_vector(f, "f" if op is None else "the right-hand side")
         if op is None:
             op = solver._put_operator(kappa, sigma, dict(zip(bits, alphas)))
         elif op.generation != solver._generation:       # another kappa has been solved since: this one's operator again
             op.generation = solver._generate(op.kappa_kept, op.sigma_kept, op.robin_kept)
-        u = solver._pcg(rhs, which, warm).view(f.shape)
-        ctx.solver, ctx.op = solver, op
-        ctx.kappa_like = None if kappa is None else (kappa.shape, kappa.device)
-        # kappa is kept as what the gradient is taken with respect to, never for its values (those are op.kappa_kept): not
-        # through save_for_backward, whose version check would refuse a caller who has overwritten the tensor since
-        ctx.kappa = kappa if ctx.needs_input_grad[0] else None
-        ctx.n_rest = len(rest)
-        ctx.sigma_like = None if sigma is None else (sigma.shape, sigma.device)
-        ctx.sigma = sigma if rest and ctx.needs_input_grad[6] else None     # (as kappa: never for its values)
-        ctx.bits = bits
-        ctx.alpha_like = [None if a is None else (a.shape, a.device) for a in alphas]
-        ctx.alphas = [a if a is not None and ctx.needs_input_grad[8 + q] else None for q, a in enumerate(alphas)]
+        u = (solver._pcg_many if many else solver._pcg)(rhs, which, warm).view(f.shape)
+        ctx.solver, ctx.op, ctx.many, ctx.bits, ctx.n_inputs = solver, op, many, bits, 6 + len(fields)
+        # kappa, sigma and the alphas are kept as what the gradient is taken with respect to, never for their values (those
+        # are op.kappa_kept, ...): not through save_for_backward, whose version check would refuse a caller who has
+        # overwritten the tensor since
+        coefficients = {0: kappa, 7: sigma, **{9 + q: a for q, a in enumerate(alphas)}}
+        ctx.like = {i: (c.shape, c.device) for i, c in coefficients.items() if c is not None}
+        ctx.wanted = {i: c if i in ctx.like and ctx.needs_input_grad[i] else None for i, c in coefficients.items()}
         ctx.save_for_backward(u)
         return u
 
@@ -536,240 +515,114 @@ class _Solve(torch.autograd.Function):
     def backward(ctx, grad_u):
         # lambda = S(kappa, grad_u), grad_f = lambda, grad_kappa = -D(lambda, u): A is symmetric.  Written with the functions
         # themselves, so that under create_graph autograd can differentiate it again; without, it runs under no_grad and is
-        # one mg_pcg and one sensitivity kernel.
-        solver = ctx.solver
-        kappa, (u,) = ctx.kappa, ctx.saved_tensors
-        rest = [ctx.sigma] * min(ctx.n_rest, 1) + ([ctx.bits] + ctx.alphas if ctx.n_rest > 1 else [])
-        lam = _Solve.apply(kappa, grad_u, solver, ctx.op, "adjoint", not torch.is_grad_enabled(), *rest)
-        grad_kappa = None
-        if ctx.needs_input_grad[0]:
-            shape, device = ctx.kappa_like
-            grad_kappa = _DKappa.apply(lam, u, solver, "interior", "interior").neg().view(shape).to(device)
-        grad_f = lam if ctx.needs_input_grad[1] else None
-        if not ctx.n_rest:
-            return grad_kappa, grad_f, None, None, None, None
-        grad_sigma = None
-        if ctx.sigma is not None:
-            shape, device = ctx.sigma_like
-            grad_sigma = _DSigma.apply(lam, u, solver).neg().view(shape).to(device)
-        if ctx.n_rest == 1:
-            return grad_kappa, grad_f, None, None, None, None, grad_sigma
-        grad_alphas = []
-        for bit, alpha, like in zip(ctx.bits, ctx.alphas, ctx.alpha_like):
-            grad_alphas.append(None if alpha is None else _DRobin.apply(lam, u, solver, bit).neg().view(like[0]).to(like[1]))
-        return (grad_kappa, grad_f, None, None, None, None, grad_sigma, None, *grad_alphas)
+        # one mg_pcg and one sensitivity kernel.  With B lanes the nested solve is batched and D is applied per lane, the
+        # lanes' terms summed in ascending order with the first term starting the accumulator.
+        solver, wanted = ctx.solver, ctx.wanted
+        (u,) = ctx.saved_tensors
+        lam = _Solve.apply(wanted[0], grad_u, solver, ctx.op, "adjoint", not torch.is_grad_enabled(), ctx.many, wanted[7],
+                           ctx.bits, *[wanted[9 + q] for q in range(len(ctx.bits))])
+        lanes = u.shape[0] if ctx.many else 1
+        lam_of, u_of = (lam.reshape(lanes, -1), u.reshape(lanes, -1)) if ctx.many else ((lam,), (u,))
+
+        def minus_d(i, field):
+            if wanted[i] is None:
+                return None
+            acc = _D.apply(lam_of[0], u_of[0], solver, field)
+            for b in range(1, lanes):
+                acc = acc + _D.apply(lam_of[b], u_of[b], solver, field)
+            shape, device = ctx.like[i]
+            return acc.neg().view(shape).to(device)
+
+        grads = [minus_d(0, _kappa_field("interior", "interior")), lam if ctx.needs_input_grad[1] else None, None, None, None,
+                 None, None, minus_d(7, _SIGMA_FIELD), None] + [minus_d(9 + q, _alpha_field(bit)) for q, bit in enumerate(ctx.bits)]
+        return tuple(grads[:ctx.n_inputs])
 
 
-class _SolveMany(torch.autograd.Function):
-    """S for B right-hand sides on one operator: U[b] = A^-1 F[b], one batched solve (`DiffusionSolver._pcg_many`).  The
-    arguments are `_Solve`'s with F of B leading rows; the backward pass is `_Solve`'s with the nested solve batched and D
-    applied per lane, the lanes' terms summed in ascending order with the first term starting the accumulator."""
+class _Field:
+    """A coefficient field of the operator as D and T see it: kappa with a node set per side, sigma, or the alpha of one face.
+    `d(hierarchy, level, a, b, out)` and `t(hierarchy, level, w, x, out)` are its two entries on `DeviceHierarchy` (with the
+    field's own extra argument, the node sets or the face bit, in place), `noun` is what the refusal of a direction of the
+    wrong size calls it, N^`power` its length, and `transposed` the field of the transposed operator (kappa: the node sets
+    swapped; R and B are diagonal)."""
 
-    @staticmethod
-    def forward(ctx, kappa, F, solver, op, which, warm, *rest):
-        sigma = rest[0] if rest else None
-        n = solver.hierarchy.n_dofs(solver.top)
-        if F.dtype != torch.float64 or F.device != solver.device or F.dim() < 2 or F[0].numel() != n:
-            raise ValueError(f"the right-hand sides must hold leading rows of {n} float64 on {solver.device}")
-        rhs = F.detach().contiguous().view(F.shape[0], n)
-        bits, alphas = (rest[1], rest[2:]) if len(rest) > 1 else ((), ())
-        if op is None:
-            op = solver._put_operator(kappa, sigma, dict(zip(bits, alphas)))
-        elif op.generation != solver._generation:       # another kappa has been solved since: this one's operator again
-            op.generation = solver._generate(op.kappa_kept, op.sigma_kept, op.robin_kept)
-        U = solver._pcg_many(rhs, which, warm).view(F.shape)
-        ctx.solver, ctx.op = solver, op
-        ctx.kappa_like = None if kappa is None else (kappa.shape, kappa.device)
-        ctx.kappa = kappa if ctx.needs_input_grad[0] else None      # (as in _Solve: what the gradient is taken with respect to)
-        ctx.n_rest = len(rest)
-        ctx.sigma_like = None if sigma is None else (sigma.shape, sigma.device)
-        ctx.sigma = sigma if rest and ctx.needs_input_grad[6] else None
-        ctx.bits = bits
-        ctx.alpha_like = [None if a is None else (a.shape, a.device) for a in alphas]
-        ctx.alphas = [a if a is not None and ctx.needs_input_grad[8 + q] else None for q, a in enumerate(alphas)]
-        ctx.save_for_backward(U)
-        return U
-
-    @staticmethod
-    def backward(ctx, grad_U):
-        solver = ctx.solver
-        kappa, (U,) = ctx.kappa, ctx.saved_tensors
-        rest = [ctx.sigma] * min(ctx.n_rest, 1) + ([ctx.bits] + ctx.alphas if ctx.n_rest > 1 else [])
-        Lam = _SolveMany.apply(kappa, grad_U, solver, ctx.op, "adjoint", not torch.is_grad_enabled(), *rest)
-        B = U.shape[0]
-        Uv, Lv = U.reshape(B, -1), Lam.reshape(B, -1)
-
-        def over_lanes(term):
-            acc = term(Lv[0], Uv[0])
-            for b in range(1, B):
-                acc = acc + term(Lv[b], Uv[b])
-            return acc
-
-        grad_kappa = None
-        if ctx.needs_input_grad[0]:
-            shape, device = ctx.kappa_like
-            grad_kappa = over_lanes(lambda lam, u: _DKappa.apply(lam, u, solver, "interior", "interior")).neg().view(shape).to(device)
-        grad_F = Lam if ctx.needs_input_grad[1] else None
-        if not ctx.n_rest:
-            return grad_kappa, grad_F, None, None, None, None
-        grad_sigma = None
-        if ctx.sigma is not None:
-            shape, device = ctx.sigma_like
-            grad_sigma = over_lanes(lambda lam, u: _DSigma.apply(lam, u, solver)).neg().view(shape).to(device)
-        if ctx.n_rest == 1:
-            return grad_kappa, grad_F, None, None, None, None, grad_sigma
-        grad_alphas = []
-        for bit, alpha, like in zip(ctx.bits, ctx.alphas, ctx.alpha_like):
-            grad_alphas.append(None if alpha is None else
-                               over_lanes(lambda lam, u: _DRobin.apply(lam, u, solver, bit)).neg().view(like[0]).to(like[1]))
-        return (grad_kappa, grad_F, None, None, None, None, grad_sigma, None, *grad_alphas)
+    def __init__(self, noun, power, d, t, transposed=None):
+        self.noun, self.power, self.d, self.t = noun, power, d, t
+        self.transposed = transposed or (lambda: self)
 
 
-class _DKappa(torch.autograd.Function):
-    """D(a, b; A, B) = mg_diffusion_dkappa(a, b) with a node set per vector ("interior": the boundary entries count as 0),
-    N^3 cells.  With cotangent w: a_bar = T(w, b; A, B), b_bar = T(w, a; B, A)."""
+def _kappa_field(rows: str, cols: str) -> _Field:
+    """D(a, b; A, B) = mg_diffusion_dkappa(a, b) with a node set per vector ("interior": the boundary entries count as 0), and
+    T(w, x; R, C) = M_R A^(w) M_C x = mg_diffusion_apply_dkappa(w, x) with a node set for the rows and one for the columns
+    ((interior, interior): (dA/dkappa . w) x); N^3 cells."""
+    return _Field("kappa", 3, lambda h, level, a, b, out: h.diffusion_dkappa(level, a, b, out, rows, cols),
+                  lambda h, level, w, x, out: h.diffusion_apply_dkappa(level, w, x, out, rows, cols), lambda: _kappa_field(cols, rows))
+
+
+# D_sigma(a, b) = mg_diffusion_dsigma(a, b) and T_sigma(w, x) = R(w) x = mg_diffusion_apply_dsigma(w, x) on the free nodes, 0
+# on the Dirichlet nodes, whose entries of a and b count as 0; N^3 cells
+_SIGMA_FIELD = _Field("sigma", 3, DeviceHierarchy.diffusion_dsigma, DeviceHierarchy.diffusion_apply_dsigma)
+
+
+def _alpha_field(bit: int) -> _Field:
+    """D_alpha,F(a, b) = mg_diffusion_drobin(a, b) and T_alpha,F(w, x) = b_F(w) x = mg_diffusion_apply_drobin(w, x) on the
+    free nodes of the face with bit `bit`, 0 on every other node; N^2 face-cells."""
+    return _Field("alpha", 2, lambda h, level, a, b, out: h.diffusion_drobin(level, bit, a, b, out),
+                  lambda h, level, w, x, out: h.diffusion_apply_drobin(level, bit, w, x, out))
+
+
+def _launch(solver, entry, n_out: int, *operands) -> torch.Tensor:
+    """What every autograd function below does forward: `entry(top level, *addresses of the operands, address of the
+    result)` on `n_out` fresh float64, once the current stream has finished with the operands (checked, detached and
+    contiguous already; None: a null pointer), which the handle's stream reads."""
+    out = torch.empty(n_out, dtype=torch.float64, device=solver.device)
+    torch.cuda.current_stream(solver.device).synchronize()
+    entry(solver.top, *[None if t is None else t.data_ptr() for t in operands], out.data_ptr())
+    return out
+
+
+class _D(torch.autograd.Function):
+    """D(a, b) of a `_Field`: the derivative of a^T (the field's term of the operator) b with respect to the field, one value
+    per cell.  With cotangent w: a_bar = T(w, b), b_bar = T^T(w, a), T^T the T of the transposed field."""
 
     @staticmethod
-    def forward(ctx, a, b, solver, a_nodes, b_nodes):
-        av, bv = solver._device_vector(a, "a"), solver._device_vector(b, "b")
-        out = torch.empty(solver.N ** 3, dtype=torch.float64, device=solver.device)
-        torch.cuda.current_stream(solver.device).synchronize()
-        solver.hierarchy.diffusion_dkappa(solver.top, av.data_ptr(), bv.data_ptr(), out.data_ptr(), a_nodes=a_nodes, b_nodes=b_nodes)
-        ctx.solver, ctx.sets = solver, (a_nodes, b_nodes)
+    def forward(ctx, a, b, solver, field):
+        ctx.solver, ctx.field = solver, field
         ctx.save_for_backward(a, b)
-        return out
+        return _launch(solver, lambda *args: field.d(solver.hierarchy, *args), solver.N ** field.power,
+                       solver._device_vector(a, "a"), solver._device_vector(b, "b"))
 
     @staticmethod
     def backward(ctx, w):
         a, b = ctx.saved_tensors
-        A, B = ctx.sets
-        grad_a = _Tangent.apply(w, b, ctx.solver, A, B).view(a.shape) if ctx.needs_input_grad[0] else None
-        grad_b = _Tangent.apply(w, a, ctx.solver, B, A).view(b.shape) if ctx.needs_input_grad[1] else None
-        return grad_a, grad_b, None, None, None
-
-
-class _Tangent(torch.autograd.Function):
-    """T(w, x; R, C) = M_R A^(w) M_C x = mg_diffusion_apply_dkappa(w, x) with a node set for the rows and one for the columns
-    ((interior, interior): (dA/dkappa . w) x), (N + 1)^3 nodes.  With cotangent y: w_bar = D(y, x; R, C), x_bar = T(w, y; C, R)."""
-
-    @staticmethod
-    def forward(ctx, w, x, solver, rows, cols):
-        if w.dtype != torch.float64 or w.device != solver.device or w.numel() != solver.N ** 3:
-            raise ValueError(f"the kappa direction must hold {solver.N ** 3} float64 on {solver.device}")
-        wv, xv = w.detach().contiguous(), solver._device_vector(x, "x")
-        out = torch.empty(xv.numel(), dtype=torch.float64, device=solver.device)
-        torch.cuda.current_stream(solver.device).synchronize()
-        solver.hierarchy.diffusion_apply_dkappa(solver.top, wv.data_ptr(), xv.data_ptr(), out.data_ptr(), rows=rows, cols=cols)
-        ctx.solver, ctx.sets = solver, (rows, cols)
-        ctx.save_for_backward(w, x)
-        return out
-
-    @staticmethod
-    def backward(ctx, y):
-        w, x = ctx.saved_tensors
-        R, C = ctx.sets
-        grad_w = _DKappa.apply(y, x, ctx.solver, R, C).view(w.shape) if ctx.needs_input_grad[0] else None
-        grad_x = _Tangent.apply(w, y, ctx.solver, C, R).view(x.shape) if ctx.needs_input_grad[1] else None
-        return grad_w, grad_x, None, None, None
-
-
-class _DSigma(torch.autograd.Function):
-    """D_sigma(a, b) = mg_diffusion_dsigma(a, b), N^3 cells; the entries of a and b on the Dirichlet nodes count as 0.  With
-    cotangent w: a_bar = T_sigma(w, b), b_bar = T_sigma(w, a)."""
-
-    @staticmethod
-    def forward(ctx, a, b, solver):
-        av, bv = solver._device_vector(a, "a"), solver._device_vector(b, "b")
-        out = torch.empty(solver.N ** 3, dtype=torch.float64, device=solver.device)
-        torch.cuda.current_stream(solver.device).synchronize()
-        solver.hierarchy.diffusion_dsigma(solver.top, av.data_ptr(), bv.data_ptr(), out.data_ptr())
-        ctx.solver = solver
-        ctx.save_for_backward(a, b)
-        return out
-
-    @staticmethod
-    def backward(ctx, w):
-        a, b = ctx.saved_tensors
-        grad_a = _TSigma.apply(w, b, ctx.solver).view(a.shape) if ctx.needs_input_grad[0] else None
-        grad_b = _TSigma.apply(w, a, ctx.solver).view(b.shape) if ctx.needs_input_grad[1] else None
-        return grad_a, grad_b, None
-
-
-class _TSigma(torch.autograd.Function):
-    """T_sigma(w, x) = R(w) x = mg_diffusion_apply_dsigma(w, x) on the free nodes, 0 on the Dirichlet nodes, (N + 1)^3 nodes.
-    With cotangent y: w_bar = D_sigma(y, x), x_bar = T_sigma(w, y) (R is diagonal)."""
-
-    @staticmethod
-    def forward(ctx, w, x, solver):
-        if w.dtype != torch.float64 or w.device != solver.device or w.numel() != solver.N ** 3:
-            raise ValueError(f"the sigma direction must hold {solver.N ** 3} float64 on {solver.device}")
-        wv, xv = w.detach().contiguous(), solver._device_vector(x, "x")
-        out = torch.empty(xv.numel(), dtype=torch.float64, device=solver.device)
-        torch.cuda.current_stream(solver.device).synchronize()
-        solver.hierarchy.diffusion_apply_dsigma(solver.top, wv.data_ptr(), xv.data_ptr(), out.data_ptr())
-        ctx.solver = solver
-        ctx.save_for_backward(w, x)
-        return out
-
-    @staticmethod
-    def backward(ctx, y):
-        w, x = ctx.saved_tensors
-        grad_w = _DSigma.apply(y, x, ctx.solver).view(w.shape) if ctx.needs_input_grad[0] else None
-        grad_x = _TSigma.apply(w, y, ctx.solver).view(x.shape) if ctx.needs_input_grad[1] else None
-        return grad_w, grad_x, None
-
-
-class _DRobin(torch.autograd.Function):
-    """D_alpha,F(a, b) = mg_diffusion_drobin(a, b) of the face with bit `bit`, N^2 face-cells; the entries of a and b on the
-    Dirichlet nodes count as 0.  With cotangent w: a_bar = T_alpha,F(w, b), b_bar = T_alpha,F(w, a)."""
-
-    @staticmethod
-    def forward(ctx, a, b, solver, bit):
-        av, bv = solver._device_vector(a, "a"), solver._device_vector(b, "b")
-        out = torch.empty(solver.N ** 2, dtype=torch.float64, device=solver.device)
-        torch.cuda.current_stream(solver.device).synchronize()
-        solver.hierarchy.diffusion_drobin(solver.top, bit, av.data_ptr(), bv.data_ptr(), out.data_ptr())
-        ctx.solver, ctx.bit = solver, bit
-        ctx.save_for_backward(a, b)
-        return out
-
-    @staticmethod
-    def backward(ctx, w):
-        a, b = ctx.saved_tensors
-        grad_a = _TRobin.apply(w, b, ctx.solver, ctx.bit).view(a.shape) if ctx.needs_input_grad[0] else None
-        grad_b = _TRobin.apply(w, a, ctx.solver, ctx.bit).view(b.shape) if ctx.needs_input_grad[1] else None
+        grad_a = _T.apply(w, b, ctx.solver, ctx.field).view(a.shape) if ctx.needs_input_grad[0] else None
+        grad_b = _T.apply(w, a, ctx.solver, ctx.field.transposed()).view(b.shape) if ctx.needs_input_grad[1] else None
         return grad_a, grad_b, None, None
 
 
-class _TRobin(torch.autograd.Function):
-    """T_alpha,F(w, x) = b_F(w) x = mg_diffusion_apply_drobin(w, x) on the free nodes of the face with bit `bit`, 0 on every
-    other node, (N + 1)^3 nodes.  With cotangent y: w_bar = D_alpha,F(y, x), x_bar = T_alpha,F(w, y) (B is diagonal)."""
+class _T(torch.autograd.Function):
+    """T(w, x) of a `_Field`: the field's term of the operator with the direction w in the field's place, applied to x,
+    (N + 1)^3 nodes.  With cotangent y: w_bar = D(y, x), x_bar = T^T(w, y)."""
 
     @staticmethod
-    def forward(ctx, w, x, solver, bit):
-        if w.dtype != torch.float64 or w.device != solver.device or w.numel() != solver.N ** 2:
-            raise ValueError(f"the alpha direction must hold {solver.N ** 2} float64 on {solver.device}")
-        wv, xv = w.detach().contiguous(), solver._device_vector(x, "x")
-        out = torch.empty(xv.numel(), dtype=torch.float64, device=solver.device)
-        torch.cuda.current_stream(solver.device).synchronize()
-        solver.hierarchy.diffusion_apply_drobin(solver.top, bit, wv.data_ptr(), xv.data_ptr(), out.data_ptr())
-        ctx.solver, ctx.bit = solver, bit
+    def forward(ctx, w, x, solver, field):
+        cells = solver.N ** field.power
+        if w.dtype != torch.float64 or w.device != solver.device or w.numel() != cells:
+            raise ValueError(f"the {field.noun} direction must hold {cells} float64 on {solver.device}")
+        ctx.solver, ctx.field = solver, field
         ctx.save_for_backward(w, x)
-        return out
+        return _launch(solver, lambda *args: field.t(solver.hierarchy, *args), solver.hierarchy.n_dofs(solver.top),
+                       w.detach().contiguous(), solver._device_vector(x, "x"))
 
     @staticmethod
     def backward(ctx, y):
         w, x = ctx.saved_tensors
-        grad_w = _DRobin.apply(y, x, ctx.solver, ctx.bit).view(w.shape) if ctx.needs_input_grad[0] else None
-        grad_x = _TRobin.apply(w, y, ctx.solver, ctx.bit).view(x.shape) if ctx.needs_input_grad[1] else None
+        grad_w = _D.apply(y, x, ctx.solver, ctx.field).view(w.shape) if ctx.needs_input_grad[0] else None
+        grad_x = _T.apply(w, y, ctx.solver, ctx.field.transposed()).view(x.shape) if ctx.needs_input_grad[1] else None
         return grad_w, grad_x, None, None
 
 
-def _cell_field(solver, t: torch.Tensor, count: int, what: str) -> torch.Tensor:
-    n = count * solver.N ** 3
-    if t.dtype != torch.float64 or t.device != solver.device or t.numel() != n:
-        raise ValueError(f"{what} must hold {n} float64 on {solver.device} (got {t.numel()} {t.dtype} on {t.device})")
-    return t.detach().contiguous()
+def _cell_field(solver, t: Optional[torch.Tensor], count: int, what: str) -> Optional[torch.Tensor]:
+    return None if t is None else solver._holds(t, count * solver.N ** 3, what).detach().contiguous()
 
 
 class _CellGrad(torch.autograd.Function):
@@ -778,14 +631,10 @@ class _CellGrad(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, w, x, solver):
-        wv = None if w is None else _cell_field(solver, w, 1, "the cell weight")
-        xv = solver._device_vector(x, "x")
-        out = torch.empty(3 * solver.N ** 3, dtype=torch.float64, device=solver.device)
-        torch.cuda.current_stream(solver.device).synchronize()
-        solver.hierarchy.diffusion_cell_gradient(solver.top, None if wv is None else wv.data_ptr(), xv.data_ptr(), out.data_ptr())
         ctx.solver, ctx.weighted = solver, w is not None
         ctx.save_for_backward(w, x)
-        return out
+        return _launch(solver, solver.hierarchy.diffusion_cell_gradient, 3 * solver.N ** 3,
+                       _cell_field(solver, w, 1, "the cell weight"), solver._device_vector(x, "x"))
 
     @staticmethod
     def backward(ctx, P):
@@ -801,14 +650,10 @@ class _CellGradT(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, w, p, solver):
-        wv = None if w is None else _cell_field(solver, w, 1, "the cell weight")
-        pv = _cell_field(solver, p, 3, "the cell field")
-        out = torch.empty(solver.hierarchy.n_dofs(solver.top), dtype=torch.float64, device=solver.device)
-        torch.cuda.current_stream(solver.device).synchronize()
-        solver.hierarchy.diffusion_cell_gradient_t(solver.top, None if wv is None else wv.data_ptr(), pv.data_ptr(), out.data_ptr())
         ctx.solver, ctx.weighted = solver, w is not None
         ctx.save_for_backward(w, p)
-        return out
+        return _launch(solver, solver.hierarchy.diffusion_cell_gradient_t, solver.hierarchy.n_dofs(solver.top),
+                       _cell_field(solver, w, 1, "the cell weight"), _cell_field(solver, p, 3, "the cell field"))
 
     @staticmethod
     def backward(ctx, y):
@@ -824,13 +669,10 @@ class _CellGradDot(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, p, x, solver):
-        pv, xv = _cell_field(solver, p, 3, "the cell field"), solver._device_vector(x, "x")
-        out = torch.empty(solver.N ** 3, dtype=torch.float64, device=solver.device)
-        torch.cuda.current_stream(solver.device).synchronize()
-        solver.hierarchy.diffusion_cell_gradient_dot(solver.top, pv.data_ptr(), xv.data_ptr(), out.data_ptr())
         ctx.solver = solver
         ctx.save_for_backward(p, x)
-        return out
+        return _launch(solver, solver.hierarchy.diffusion_cell_gradient_dot, solver.N ** 3,
+                       _cell_field(solver, p, 3, "the cell field"), solver._device_vector(x, "x"))
 
     @staticmethod
     def backward(ctx, z):

@@ -110,6 +110,13 @@ ROBIN_MEASURED = 8.561e-13
 ROBIN_LIMIT = 8 * ROBIN_MEASURED
 
 
+# `tangent` with every direction at once (tangent_worker): u and du against the host, configuration (a), both storages, with
+# g and without.  Measured once on an MI355X (stored and matrix-free alike to three digits): with g u 7.226e-13, du 4.491e-13;
+# without g u 7.206e-13, du 4.502e-13; 19 iterations per solve.  8 x the largest, by the rule above:
+TANGENT_MEASURED = 7.226e-13
+TANGENT_LIMIT = 8 * TANGENT_MEASURED
+
+
 def _case(config):
     from tests.diffusion_workers import lognormal_kappa
     N = 16
@@ -185,6 +192,55 @@ def solver_worker():
                     worst = max(worst, max(figures))
     _check_limit(worst, ROBIN_LIMIT)
     print("solver ok")
+
+
+def host_tangent(op, f, g, dkappa, df, dg, dsigma, dalpha):
+    """(u, du) in the direction (dkappa, df, dg, dsigma, dalpha by face, a subset of the field faces).  With g: the free rows of
+    du's right-hand side are df - T(dkappa, u; interior, all) - T(kappa, dg_B; interior, all) - T_sigma(dsigma, u) -
+    sum_F T_alpha,F(dalpha_F, u), dg_B = dg on the Dirichlet nodes and 0 on the free ones, and the Dirichlet rows are dg.
+    Without g (f the full right-hand side, u_b = f_b): the columns are "interior", there is no dg term, and the Dirichlet rows
+    are those of the full df, as tests/diffusion_tangent_workers.py has them."""
+    free = op.free
+    if g is None:
+        u = op.solve(f)
+        rhs = df - op.T(dkappa, u, "interior", "interior")
+    else:
+        u = op.solve(lifted_rhs(op.N, op.kappa, f, g, op.faces))
+        rhs = df - op.T(dkappa, u, "interior", "all") - op.T(op.kappa, np.where(free, 0.0, dg), "interior", "all")
+    rhs = rhs - poisson.diffusion_apply_dsigma(op.N, dsigma, u, op.faces) - op.Tr(dalpha, u)
+    return u, op.solve(np.where(free, rhs, df if g is None else dg))
+
+
+def tangent_worker():
+    """`DiffusionSolver.tangent` with everything at once -- df, g and dg, sigma and dsigma, Robin fields on both field faces and
+    a direction on one of them only -- and again with g = None, dg = None, configuration (a), both storages: u and du against
+    the host, two solves and one generation per call (TANGENT_LIMIT holds the measured figure)."""
+    import torch
+    from multigrid_dolfinx_amd.torch_diffusion import DiffusionSolver
+    N, faces, kappa, sigma, robin, f, d, g, vk, va = _case("a")
+    rng = np.random.default_rng(41)
+    dg, dsigma = rng.standard_normal((N + 1) ** 3), rng.standard_normal(N ** 3)
+    dkappa, df, dalpha = vk, d, {32: va[32]}
+    dev = lambda x: torch.tensor(x, device="cuda")
+    op = HostOperator(N, kappa, sigma, robin, faces)
+    want = {True: host_tangent(op, f, g, dkappa, df, dg, dsigma, dalpha),
+            False: host_tangent(op, f, None, dkappa, df, None, dsigma, dalpha)}
+    worst = 0.0
+    for name, min_rows in (("stored", None), ("matrix_free", 0)):
+        with DiffusionSolver(N, 2, rtol=1e-12, matrix_free_min_rows=min_rows, dirichlet_faces=faces) as solver:
+            fields = {face: dev(robin[face]) for face in robin}
+            for with_g in (True, False):
+                ut, dut = solver.tangent(dev(kappa), dev(f), dev(dkappa), dev(df), g=dev(g) if with_g else None,
+                                         dg=dev(dg) if with_g else None, sigma=dev(sigma), dsigma=dev(dsigma), robin=fields,
+                                         drobin={face: dev(x) for face, x in dalpha.items()})
+                assert solver.hierarchy.level_matrix_free(1) == (name == "matrix_free")
+                assert set(solver.last_iterations) == {"forward", "tangent"}
+                figures = (_rel(ut.cpu().numpy(), want[with_g][0]), _rel(dut.cpu().numpy(), want[with_g][1]))
+                print(name, "g" if with_g else "no g", "iterations", solver.last_iterations, "rel l2: u %.3e  du %.3e" % figures, flush=True)
+                worst = max(worst, max(figures))
+            assert solver.n_solves == 4 and solver.n_generations == 2, (solver.n_solves, solver.n_generations)
+    _check_limit(worst, TANGENT_LIMIT)
+    print("tangent ok")
 
 
 def switch_worker():

@@ -798,5 +798,13 @@ def test_diffusion_solver_with_robin_fields_against_the_host():
 
 
 @pytest.mark.gpu
+def test_diffusion_solver_tangent_with_every_direction_against_the_host():
+    """`tangent` with df, g and dg, sigma and dsigma, Robin fields on both field faces and drobin on one of them, and the same
+    call with g = None, dg = None: configuration (a), N = 16, stored and matrix-free, u and du against HostOperator
+    (`tangent_worker`; TANGENT_LIMIT holds the measured figure)."""
+    assert "tangent ok" in _torch_first("tangent_worker")
+
+
+@pytest.mark.gpu
 def test_diffusion_solver_switches_between_sets_of_field_faces():
     assert "switch ok" in _torch_first("switch_worker")
