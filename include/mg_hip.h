@@ -643,6 +643,11 @@ int mg_galerkin_hierarchy(mg_handle h, int top_level);
  *                          (three sweeps per pass only) (1: measured no slower)
  *     "fuse_k_dpp"         0 = the -1 / +1 neighbours of that march come through LDS instead of the neighbouring lanes'
  *                          registers (experiment, tile 0 only: measured 1.4 x slower) (1)
+ *     "fuse_k_plan"        march plans: the level's class bytes are inspected once per level, tile shape and K (which planes of
+ *                          which wave hold the main class only, or the classes of the plane before), and the steps of that
+ *                          march that run inside such a run load and inspect no classes (1); 0 = every step does;
+ *                          bit-identical.  Whole levels without escape rows, 64 x 32 tiles ("fuse_k_shape" 7 and 8); see
+ *                          mg_march_plan
  *     "fuse_classes"       that pass reads one class byte per row instead of the 32-byte row where the level has
  *                          row classes (1); bit-identical either way
  *     "fuse_plain"         that pass on levels WITHOUT row classes: 2 = round-2 structure (sdia_jacobi2p), 1 = round 1's (2);
@@ -881,6 +886,16 @@ enum mg_smoother_path {
 };
 int mg_smoother_launches(mg_handle h, int level, int path, int64_t* launches, int64_t* sweeps, int64_t* tail_launches);
 int mg_reset_smoother_launches(mg_handle h);
+
+/* The march plan ("fuse_k_plan") the K-sweep march of `sweeps` sweeps per pass (3..5) uses on `level` under the handle's
+ * present tuning.  A wave of a tile keeps its longest run of consecutive planes in which all the class bytes it loads are
+ * the level's main class, and its longest run in which each of them is what it was in the plane before:
+ *   waves, planes               the (tile, wave) pairs that have a run of the first kind; the planes of those runs summed
+ *   const_waves, const_planes   the same for runs of the second kind that are not the pair's run of the first kind
+ * All 0 where no plan exists: not built yet (the first such launch outside a capture, or mg_prepare_cycle, builds it),
+ * "fuse_k_plan" 0, or a launch that takes none (slabs, levels with escape rows, other tile shapes).  A plan is dropped
+ * when the level's classes are rebuilt.  Null pointers are skipped.  For tests. */
+int mg_march_plan(mg_handle h, int level, int sweeps, int64_t* waves, int64_t* planes, int64_t* const_waves, int64_t* const_planes);
 
 /* ---- measurement -----------------------------------------------------------------------------
  * mg_time_kernel: average duration in milliseconds of `reps` back-to-back launches of

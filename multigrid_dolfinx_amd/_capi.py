@@ -127,6 +127,7 @@ SIGNATURES = {
     "mg_release_batch": [_H],
     "mg_counters": [_H, _i64p, _i64p, _i64p, _ip],
     "mg_smoother_launches": [_H, C.c_int, C.c_int, _i64p, _i64p, _i64p],
+    "mg_march_plan": [_H, C.c_int, C.c_int, _i64p, _i64p, _i64p, _i64p],
     "mg_reset_smoother_launches": [_H],
     "mg_time_kernel": [_H, C.c_char_p, C.c_int, C.c_int, _dp],
     "mg_sync": [_H],

@@ -191,6 +191,15 @@ struct Level {
     DevBuf<int> s_pack;
     int lm_ntop = 0;
     int lm_top[LM_K] = {0, 0, 0, 0, 0, 0, 0, 0};
+    // march plans of the K-sweep pass (mg_jacobik3d.hip.h, jk3_plan): per (tile, wave) the run of planes whose classes are all
+    // `cmain` and the run whose classes do not change from plane to plane, one plan per K = 3, 4, 5 and tile shape 7, 8
+    // (march_plan_slot).  Built at the first such launch outside a capture (or by prepare_cycle), dropped wherever `cls` is
+    // installed; waves[i] / planes[i]: waves with a run of kind i (a constant run that is the cmain run counts there only), planes in them
+    struct MarchPlan {
+        DevBuf<int> iv;
+        int64_t waves[2] = {0, 0}, planes[2] = {0, 0};
+    };
+    MarchPlan plan[6];
     int cmain = 0;                          // the most frequent class and its entries (passed to the kernels by value)
     double cm[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     int64_t cls_lead = 0;                   // cls[row + cls_lead], zero padding of cls_lead entries on both sides
@@ -376,6 +385,9 @@ struct mg_context {
     int fuse_k_small_tiles = 0;     // ... 64 x 24 tiles (shape 4) on levels whose planes hold fewer 64 x 48 tiles than there are CUs
     int fuse_k_pf = 1;              // ... register sets for the planes of x that arrive (2: x staged a step longer, K = 3 only; measured no faster)
     int fuse_k_dpp = 1;             // ... -1 / +1 neighbours from the neighbouring lanes' registers (0: through LDS, tile 0 only)
+    int fuse_k_plan = 1;            // ... march plans: steps whose planes are known to hold the main class only, or the same classes
+                                    // plane after plane, load and inspect no classes (whole levels without escape rows, tile
+                                    // shapes 7 and 8; 0: every step does)
     std::vector<const void*> large_lds_kernels;     // kernels whose dynamic-LDS limit has been raised (allow_large_lds)
     int fuse_shape = 1;             // launch shape of the class-coded pass (launch_jacobi2); 1 measured best
     int fuse_wi = 0;                // experiments: cells per tile line with a second sweep (0: chosen per level)
@@ -1783,6 +1795,46 @@ int jk3_shape(const mg_context* c, int K) {
     return c->fuse_k_shape >= 0 ? c->fuse_k_shape : (K >= 5 ? 8 : 7);
 }
 
+// ... on a level with `ncls` classes (shapes 3 and up keep 64 rows of the class table in LDS or run one workgroup of 16 waves
+// per CU: levels with more classes take shape 1)
+int jk3_shape_for(const mg_context* c, int K, int ncls) {
+    return jk3_shape(c, K) >= 3 && ncls > 64 ? 1 : jk3_shape(c, K);
+}
+
+// March plans (jk3_plan).  Which launches take one: whole levels without escape rows on the 64 x 32 tiles of 16 waves
+// (shapes 7 and 8), three to five sweeps per pass.  Slabs and levels with escape rows are deliberately left out: a slab's
+// plane range differs per rank and its launches are split, and escape rows are what the class loads are there to find.
+int march_plan_slot(const mg_context* c, const Level& L, int K) {
+    if (!c->fuse_k_plan || !c->fuse_k_dpp || K < 3 || K > 5 || !L.cls || L.cls_escape || is_slab(c, L)) return -1;
+    const int shape = jk3_shape_for(c, K, L.ncls);
+    return shape == 7 || shape == 8 ? (K - 3) * 2 + (shape - 7) : -1;
+}
+
+// builds the level's plan of `slot` if it is missing (allocates and synchronises: not inside a capture)
+int ensure_march_plan(mg_context* c, Level& L, int K, int slot) {
+    Level::MarchPlan& mp = L.plan[slot];
+    if (mp.iv) return 0;
+    JK3PlanArgs a{};
+    a.cls = L.cls; a.clead = L.cls_lead; a.P = L.g.plane; a.nx = L.g.nx; a.ny = L.g.ny; a.nz = L.g.nk; a.cmain = L.cmain;
+    const int WI = 64 - 2 * K, HY = 32 - 2 * K + 2;         // (shapes 7 and 8 share their tiles)
+    a.ntx = (a.nx + WI - 1) / WI; a.nty = (a.ny + HY - 1) / HY;
+    const size_t n = (size_t)a.ntx * a.nty * 16 * 4;
+    DevBuf<int> iv;
+    MG_TRY(iv.alloc(c, n));
+    a.plan = iv;
+    with_int<3, 4, 5>(K, [&](auto k) { hipLaunchKernelGGL((jk3_plan<decltype(k)::value, 16, 2, 1>), dim3((unsigned)(a.ntx * a.nty)), dim3(16 * WAVE), 0, c->stream, a); });
+    HIP_TRY(hipGetLastError());
+    std::vector<int> h(n);
+    HIP_TRY(hipMemcpyAsync(h.data(), iv, n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (size_t i = 0; i < n; i += 4) {
+        if (h[i + 1] > h[i]) { ++mp.waves[0]; mp.planes[0] += h[i + 1] - h[i]; }
+        if (h[i + 3] > h[i + 2] && (h[i + 2] != h[i] || h[i + 3] != h[i + 1])) { ++mp.waves[1]; mp.planes[1] += h[i + 3] - h[i + 2]; }
+    }
+    mp.iv = std::move(iv);
+    return 0;
+}
+
 template <int K, int NW, int LPW, int M, bool DPP, int PF = 1, int WPE = (NW == 12 ? 3 : 2), int TR = 256, bool ESC = false, bool B1 = false>
 int launch_jacobikc_t(mg_context* c, JK3Args a, bool finest, const JK3Range& zr, int seglen) {
     constexpr int EX = 64 * M, EY = NW * LPW, WI = EX - 2 * K, HY = EY - 2 * K + 2;
@@ -1848,7 +1900,7 @@ template <int K, int PF>
 int launch_jacobikc_kp(mg_context* c, const JK3Args& a, bool finest, const JK3Range& zr, int seglen) {
     if (!c->fuse_k_dpp) return launch_jacobikc_t<K, 12, 2, 2, false, PF>(c, a, finest, zr, seglen);     // (experiment: -1 / +1 neighbours through LDS)
     // shapes 3..5: 64 x 24 tiles, two workgroups per CU (class table of 64 rows); levels with more classes take shape 1
-    int shape = jk3_shape(c, K) >= 3 && a.ncls > 64 ? 1 : jk3_shape(c, K);
+    int shape = jk3_shape_for(c, K, a.ncls);
     // planes with fewer 64 x 48 tiles than the GPU has CUs (the 513^2 and 257^2 planes of a slab's coarser levels): half
     // as tall tiles, two workgroups per CU
     if (shape == 1 && a.ncls <= 64 && K <= 4 && c->fuse_k_small_tiles) {
@@ -1887,7 +1939,7 @@ int launch_jacobikc_k(mg_context* c, const JK3Args& a, bool finest, const JK3Ran
 
 // out = K Jacobi sweeps applied to x (2 <= K <= 5) on the owned planes [zr) of the level (null: all of them); on slabs the
 // level's K halo planes of x and K - 1 of f must be valid
-int launch_jacobikc(mg_context* c, const Level& L, int K, const double* x_rows, const double* f_rows, double* out_rows,
+int launch_jacobikc(mg_context* c, Level& L, int K, const double* x_rows, const double* f_rows, double* out_rows,
                     const JK3Range* zr = nullptr, int seglen = 0) {
     JK3Args a{};
     a.x = x_rows; a.f = f_rows; a.out = out_rows;
@@ -1900,6 +1952,16 @@ int launch_jacobikc(mg_context* c, const Level& L, int K, const double* x_rows, 
     if (L.cls_escape && K > L.esc_kmax) return fail("too many escape rows per tile for that many sweeps per pass");
     a.force_form = c->timing_force_form;
     a.nt_store = c->fuse_k_nt_store;
+    // the march plan: built here when it is missing, but for a launch that is being captured (prepare_cycle builds the plans
+    // of captured cycles) -- that one runs without, to the same result
+    if (const int slot = march_plan_slot(c, L, K); slot >= 0 && a.force_form < 0 && !zr) {
+        if (!L.plan[slot].iv) {
+            hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+            HIP_TRY(hipStreamIsCapturing(c->stream, &st));
+            if (st == hipStreamCaptureStatusNone) MG_TRY(ensure_march_plan(c, L, K, slot));
+        }
+        a.plan = L.plan[slot].iv;
+    }
     a.escape = L.cls_escape ? 1 : 0; a.dvals = L.dvals; a.mlead = L.mlead; a.sshift = L.R == 1 ? 6 : (L.R == 2 ? 7 : 8);
     const JK3Range whole{0, L.g.nk, 0, 0};
     c->jk3_tail = 0;
@@ -3251,6 +3313,15 @@ int prepare_cycle(mg_context* c, int level) {
             }
     if (c->keep_err)
         for (int l = 1; l <= level; ++l) MG_TRY(vec_alloc(c, c->L[l], &c->L[l].err));
+    // (the march plans of the passes jacobi_ksweep makes of mu1 and mu2 sweeps: an allocation and a synchronisation each)
+    if (c->smoother == MG_SMOOTH_JACOBI)
+        for (int l = 1; l <= level; ++l) {
+            Level& L = c->L[l];
+            if (L.mf || is_slab(c, L) || !sweepsk_ok(c, L)) continue;
+            for (const int mu : {c->mu1, c->mu2})
+                for (int nw = mu, k; nw >= 3 && (k = next_pass(nw, sweepsk_max(c, L))) >= 3; nw -= k)
+                    if (const int slot = march_plan_slot(c, L, k); slot >= 0) MG_TRY(ensure_march_plan(c, L, k, slot));
+        }
     if (c->smoother == MG_SMOOTH_CHEBYSHEV)                // (the estimate synchronises: not inside a capture)
         for (int l = 1; l <= level; ++l) {
             double lo = 0.0, hi = 0.0;
@@ -3978,6 +4049,7 @@ int build_row_classes_q(mg_context* c, Level& L, int qbits) {
     }
     if (rc || h[0] > 255 || h[1]) return rc;        // too many distinct rows (or a hash collision): plain pass
     L.cls = std::move(cls); L.ctab = std::move(ctab); L.ncls = h[0] + 1; L.cls_lead = cls_lead;
+    for (auto& mp : L.plan) mp = Level::MarchPlan{};            // (march plans describe the classes they were built from)
     L.cls_escape = escape && L.rep_escape > 0;
     if (escape) hist[CLS_ESCAPE] = 0;               // (never the most frequent class)
     L.cmain = 0;
@@ -4718,6 +4790,8 @@ int mg_set_tuning(mg_handle c, const char* key, int64_t value) {
         c->fuse_k_pf = (int)value;
     } else if (k == "fuse_k_dpp") {
         c->fuse_k_dpp = value != 0;
+    } else if (k == "fuse_k_plan") {
+        c->fuse_k_plan = value != 0;
     } else if (k == "fuse_k_segments") {
         if (value < 0) return fail("fuse_k_segments must be >= 0");
         c->fuse_k_segments = (int)value;
@@ -6182,6 +6256,22 @@ int mg_smoother_launches(mg_handle c, int level, int path, int64_t* launches, in
     if (launches) *launches = n.launches;
     if (sweeps) *sweeps = n.sweeps;
     if (tail_launches) *tail_launches = n.tail;
+    return 0;
+}
+
+int mg_march_plan(mg_handle c, int level, int sweeps, int64_t* waves, int64_t* planes, int64_t* const_waves, int64_t* const_planes) {
+    MG_TRY(check_level(c, level));
+    const Level& L = c->L[level];
+    int64_t* const out[4] = {waves, planes, const_waves, const_planes};
+    for (int64_t* o : out)
+        if (o) *o = 0;
+    const int slot = march_plan_slot(c, L, sweeps);
+    if (slot < 0 || !L.plan[slot].iv) return 0;
+    const Level::MarchPlan& mp = L.plan[slot];
+    if (waves) *waves = mp.waves[0];
+    if (planes) *planes = mp.planes[0];
+    if (const_waves) *const_waves = mp.waves[1];
+    if (const_planes) *const_planes = mp.planes[1];
     return 0;
 }
 

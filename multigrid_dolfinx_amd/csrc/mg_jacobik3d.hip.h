@@ -29,6 +29,8 @@
 // A wave whose cells of the planes k .. k+K all carry the level's most frequent class (the interior stencil), in a
 // step whose planes all exist, runs straight-line code with the entries in scalar registers; other waves (next to the
 // boundary, first / last planes) take the general path: per cell group either the scalar entries or the class table.
+// On whole levels the steps of the straight-line forms are known before the launch (the march plan, jk3_plan below): a wave
+// inside a planned run of planes loads and inspects no classes at all.
 // Everything is done in ROW space like the other passes (cell <-> row whether or not it wraps around a grid line; rows
 // outside the level are zeros at every level), with the same fma chain and the same IEEE division as sdia_cls_body:
 // bit-identical to K single sweeps.  Out-of-grid cells that the tile clamps (lines beyond ny + 1 or below -2, cells
@@ -69,7 +71,22 @@ struct JK3Args {
     int64_t mlead;
     int sshift;
     int force_form;             // -1; timing experiments (mg_time_kernel only, results are wrong): every step in form 0 / 1 / 2
+    // march plan (jk3_plan): per (tile, wave) the planes [p0, p1) in which all the wave's cells carry class `cmain` and the
+    // planes [q0, q1) in which every one of them keeps its class, four ints; null: no plan, every step loads and inspects
+    // its classes (slabs, levels with escape rows, other tile shapes)
+    const int* plan;
 };
+
+// Where a tile cell's double lies, as a byte offset from `base of the plane - bias` (>> 3: where its class byte lies from
+// jk3_class_base): lines clamped to [-2, ny + 1], cells past the end of their grid line to the cell behind it.  The march
+// and the plan (jk3_plan) both take their class addresses from these two functions, so the plan speaks about exactly the
+// bytes whose loads it replaces.
+__device__ __forceinline__ unsigned jk3_cell_offset(int line, int col, int nx, int ny, int tx0, int xcl, int bias) {
+    return 8u * (unsigned)(min(max(line, -2), ny + 1) * nx + tx0 + min(col, xcl) + bias);
+}
+__device__ __forceinline__ const unsigned char* jk3_class_base(const unsigned char* cls, int64_t clead, int bias) {
+    return cls + clead - bias;
+}
 
 // Rows of class CLS_ESCAPE (levels with more than 255 distinct rows, mg_jacobi2.hip.h): when a plane arrives, every lane
 // that holds such a row fetches its seven entries from the symmetric diagonal storage into a row of a POOL behind the
@@ -276,7 +293,7 @@ __device__ __forceinline__ void jk3_body(const JK3Args& a) {
     unsigned eo[NC], eor[M];    // byte offsets of the cells' doubles (>> 3: of their class bytes)
 #pragma unroll
     for (int c = 0; c < NC; ++c)
-        eo[c] = 8u * (unsigned)(min(max(ty0 + ey0 + c / M, -2), a.ny + 1) * a.nx + tx0 + min(lane + 64 * (c % M), xcl) + bias);
+        eo[c] = jk3_cell_offset(ty0 + ey0 + c / M, lane + 64 * (c % M), a.nx, a.ny, tx0, xcl, bias);
 #pragma unroll
     for (int r = 0; r < M; ++r)
         eor[r] = 8u * (unsigned)((wlo ? max(ty0 - 1, -2) : min(ty0 + EY, a.ny + 1)) * a.nx + tx0 + min(lane + 64 * r, xcl) + bias);
@@ -284,11 +301,11 @@ __device__ __forceinline__ void jk3_body(const JK3Args& a) {
     if constexpr (B1) {
 #pragma unroll
         for (int r = 0; r < M; ++r) {
-            eos[r] = 8u * (unsigned)(min(max(ty0 + ey0 - 1, -2), a.ny + 1) * a.nx + tx0 + min(lane + 64 * r, xcl) + bias);
-            eon[r] = 8u * (unsigned)(min(max(ty0 + ey0 + LPW, -2), a.ny + 1) * a.nx + tx0 + min(lane + 64 * r, xcl) + bias);
+            eos[r] = jk3_cell_offset(ty0 + ey0 - 1, lane + 64 * r, a.nx, a.ny, tx0, xcl, bias);
+            eon[r] = jk3_cell_offset(ty0 + ey0 + LPW, lane + 64 * r, a.nx, a.ny, tx0, xcl, bias);
         }
     }
-    const unsigned char* const clsb = a.cls + a.clead - bias;
+    const unsigned char* const clsb = jk3_class_base(a.cls, a.clead, bias);
     const double* const xb0 = a.x - bias;
     const double* const fb0 = a.f - bias;
     auto sbase = [](const void* p) -> gcptr_t {
@@ -312,6 +329,44 @@ __device__ __forceinline__ void jk3_body(const JK3Args& a) {
         return (int)*(const __attribute__((address_space(1))) u32_unaligned_t*)(b + e);
     };
     const int pmin = -a.plo - 1, pmax = a.nz + a.phi;
+
+    // Planned steps (march plan).  On a whole level (plo = phi = 0) the step k takes one of the straight-line forms when
+    //   k >= 1 and k + K + 1 < nz      every row the step touches exists (planes k-1 .. k+K+1 through sh), and
+    //   form 0:  fast == ALLFAST       all 64 x NC class bytes of the ring's planes k .. k+K are `cmain`, or else
+    //   form 1:  `same`                every cell's class byte is the same in the ring's planes k .. k+K.
+    // The plan gives the wave two runs of planes: [p0, p1), all class bytes are cmain, and [q0, q1), every cell's class byte
+    // is the same in all planes of the run (the two are equal or disjoint: a run of cmain planes is a run of constant
+    // classes, and the longest of either kind is kept).  The third / fourth line holds when r0 <= k and k + K <= r1 - 1
+    // for the run [r0, r1).  A segment's ring holds real planes from its step z0 - K on (the K steps before it run on the
+    // zeros the ring starts with and take the form those give), so the steps
+    //   [klo, khi) = [max(r0, 1, z0 - K), min(r1 - K, nz - K - 1))
+    // are steps to which today's test gives form 0 (run p) or, since a constant class that is not cmain everywhere fails
+    // the form-0 test, form 1 (run q), known without looking at a class: they load no classes, move no ring and decide
+    // nothing.  A segment uses the run that gives it more such steps.  Step k's loads bring the plane that step k + PF
+    // consumes, so the class loads stop with the loads for step klo and resume with those for step khi.  Step klo - 1
+    // exists and is an ordinary one; it leaves the classes of the plane klo in cw[0], where form 1 reads them and where
+    // they stay.  In step khi the ring's planes khi .. khi+K-1 (all below r1) get those classes and their flags, as
+    // today's path would hold them, and the plane khi + K arrives from memory.
+    constexpr bool PLANNED = !ESC && NW == 16 && LPW == 2 && M == 1 && K >= 3;    // tile shapes 7 and 8
+    int klo = 0x7fffffff, khi = 0x7fffffff, kform = 0;
+    if constexpr (PLANNED) {
+        if (a.plan) {
+            const int* const pw = a.plan + 4 * ((int)tt * NW + wave);
+            const int top = a.nz - K - 1;
+            const int lo0 = max(max(pw[0], 1), z0 - K), hi0 = min(pw[1] - K, top);
+            const int lo1 = max(max(pw[2], 1), z0 - K), hi1 = min(pw[3] - K, top);
+            const int n0 = min(hi0, z1) - lo0, n1 = min(hi1, z1) - lo1;
+            if (n0 > 0 && n0 >= n1) {
+                klo = __builtin_amdgcn_readfirstlane(lo0);
+                khi = __builtin_amdgcn_readfirstlane(hi0);
+            } else if (n1 > 0) {
+                klo = __builtin_amdgcn_readfirstlane(lo1);
+                khi = __builtin_amdgcn_readfirstlane(hi1);
+                kform = 1;
+            }
+        }
+    }
+    auto interior_step = [&](int k) -> bool { return PLANNED && k >= klo && k < khi; };
 
     // registers per cell: K partial sums; f of the planes k .. k+K-1; x, f and the class of the plane that arrives
     double acc[K][NC], fr[K][NC];
@@ -344,7 +399,8 @@ __device__ __forceinline__ void jk3_body(const JK3Args& a) {
     // while nothing computes -- measured: the burst added its whole issue time to the step.
     // Slice i: x and the classes of its cells of `plane` into a register set (the y ring with the last slice), f of the
     // plane `fplane` into the slot of the ring that has just become free (a step needs it one step after x of that plane).
-    auto load_slice = [&](const int i, const int n, const int plane, const int fplane, double (&X)[NC], int (&C)[NC], double (&hy)[M])
+    // (`noc`, wave-uniform: the step that consumes the plane is an interior one -- no class loads)
+    auto load_slice = [&](const int i, const int n, const int plane, const int fplane, const bool noc, double (&X)[NC], int (&C)[NC], double (&hy)[M])
         __attribute__((always_inline)) {
         const int64_t o = (int64_t)min(max(plane, pmin), pmax) * a.P;
         const gcptr_t cb = sbase(clsb + o);
@@ -354,7 +410,7 @@ __device__ __forceinline__ void jk3_body(const JK3Args& a) {
         for (int c = 0; c < NC; ++c) {
             if ((c * n) / NC != i) continue;
             X[c] = ldd(xb, eo[c]);
-            C[c] = ldc(cb, eo[c]);
+            if (!noc) C[c] = ldc(cb, eo[c]);
             if constexpr (PF == 2) FN[c] = ldd(fb, eo[c]);
             else fr[K - 1][c] = ldd(fb, eo[c]);
         }
@@ -601,82 +657,102 @@ __device__ __forceinline__ void jk3_body(const JK3Args& a) {
         // (the loaded values are first touched HERE: left alone the compiler masks the class bytes right behind their
         //  loads, a step early, and every wave then waits for its loads before the barrier instead of computing)
 #pragma unroll
-        for (int c = 0; c < NC; ++c) {
-            asm volatile("" : "+v"(C[c]));
-            asm volatile("" : "+v"(X[c]));
-            C[c] &= 255;
-        }
-        if constexpr (ESC) {
-            // rows of class CLS_ESCAPE: their entries into pool rows, the pool row as the cell's class (see jk3_pool)
-            if (a.escape) {
-                const int64_t mp = (int64_t)min(max(k + K, pmin), pmax) * a.P - bias + a.mlead;
-                const int sh = a.sshift;
-                const double* const dv = a.dvals;
-                auto at = [&](int64_t m, int slot) -> double { return dv[((((m >> sh) << 2) + slot) << sh) + (m & (((int64_t)1 << sh) - 1))]; };
-                // (one counter update per wave and plane; the loads of all its cells in flight together)
-                unsigned long long em[NC];
-                unsigned total = 0u;
+        for (int c = 0; c < NC; ++c) asm volatile("" : "+v"(X[c]));
+        const bool interior = interior_step(k);     // (wave-uniform, from scalar registers)
+        if constexpr (PLANNED) {
+            if (k == khi) {     // the first step behind the planned ones: the ring as today's path would hold it
+                unsigned m = 0;
 #pragma unroll
-                for (int c = 0; c < NC; ++c) {
-                    if (C[c] == CLS_ESCAPE && (standin >> c & 1u)) C[c] = 0;
-                    em[c] = __ballot(C[c] == CLS_ESCAPE);
-                    total += (unsigned)__popcll(em[c]);
-                }
-                if (total != 0u) {
-                    unsigned b0 = 0u;
-                    if (lane == 0) b0 = atomicAdd(esc_count, total);
-                    b0 = (unsigned)__builtin_amdgcn_readfirstlane((int)b0);
-                    double e[NC][7];
+                for (int c = 0; c < NC; ++c)
+                    if (__builtin_amdgcn_readfirstlane((int)(__ballot(cls_of(0, c) != cmain) == 0ull))) m |= 1u << c;
+                fast = 0;
 #pragma unroll
-                    for (int c = 0; c < NC; ++c) {
-                        if (C[c] == CLS_ESCAPE) {
-                            const int64_t m = mp + (int64_t)(eo[c] >> 3);
-                            e[c][0] = at(m - a.P, 3); e[c][1] = at(m - a.nx, 2); e[c][2] = at(m - 1, 1);
-                            e[c][3] = at(m, 0); e[c][4] = at(m, 1); e[c][5] = at(m, 2); e[c][6] = at(m, 3);
-                        }
-                    }
+                for (int j = 0; j < K; ++j) {
+                    fast |= (unsigned long long)m << (j * NC);
 #pragma unroll
-                    for (int c = 0; c < NC; ++c) {
-                        if (C[c] == CLS_ESCAPE) {
-                            const unsigned below = __builtin_amdgcn_mbcnt_hi((unsigned)(em[c] >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)em[c], 0u));
-                            const int row = DYN0 + (int)((b0 + below) & (unsigned)(jk3_pool(K) - 1));
-                            double* const tr = sT + CLS_W * row;
-#pragma unroll
-                            for (int i = 0; i < 7; ++i) tr[i] = e[c][i];
-                            tr[7] = a.omega * (1.0 / (e[c][3] != 0.0 ? e[c][3] : 1.0));
-                            C[c] = row;
-                        }
-                        b0 += (unsigned)__popcll(em[c]);
-                    }
+                    for (int q = 0; q < CW; ++q) cw[j][q] = cw[0][q];
                 }
             }
         }
-        {
-            unsigned m = 0;
-#pragma unroll
-            for (int q = 0; q < CW; ++q) cw[K][q] = 0u;
+        int form = kform;
+        if (!interior) {
 #pragma unroll
             for (int c = 0; c < NC; ++c) {
-                cw[K][c / CPR] |= (unsigned)C[c] << (CBITS * (c % CPR));
-                if (__builtin_amdgcn_readfirstlane((int)(__ballot(C[c] != cmain) == 0ull))) m |= 1u << c;
+                asm volatile("" : "+v"(C[c]));
+                C[c] &= 255;
             }
-            fast |= (unsigned long long)m << (K * NC);
-        }
-        // which form: 0 = interior stencil everywhere in this wave's cells of the planes k .. k+K, 1 = every cell's class the
-        // same in all those planes -- both only where every row the step touches exists (planes k-1 .. k+K+1 through sh) or lies on a
-        // neighbouring slab (there a level's values beyond its plane range are wrong instead of zero, and reach no
-        // result) --, 2 = general
-        int form = 2;
-        if ((a.plo > 0 || k >= 1) && (a.phi > 0 || k + K + 1 < a.nz)) {
-            if (fast == ALLFAST) {
-                form = 0;
-            } else {
-                bool same = true;
+            if constexpr (ESC) {
+                // rows of class CLS_ESCAPE: their entries into pool rows, the pool row as the cell's class (see jk3_pool)
+                if (a.escape) {
+                    const int64_t mp = (int64_t)min(max(k + K, pmin), pmax) * a.P - bias + a.mlead;
+                    const int sh = a.sshift;
+                    const double* const dv = a.dvals;
+                    auto at = [&](int64_t m, int slot) -> double { return dv[((((m >> sh) << 2) + slot) << sh) + (m & (((int64_t)1 << sh) - 1))]; };
+                    // (one counter update per wave and plane; the loads of all its cells in flight together)
+                    unsigned long long em[NC];
+                    unsigned total = 0u;
 #pragma unroll
-                for (int j = 0; j <= K; ++j)
+                    for (int c = 0; c < NC; ++c) {
+                        if (C[c] == CLS_ESCAPE && (standin >> c & 1u)) C[c] = 0;
+                        em[c] = __ballot(C[c] == CLS_ESCAPE);
+                        total += (unsigned)__popcll(em[c]);
+                    }
+                    if (total != 0u) {
+                        unsigned b0 = 0u;
+                        if (lane == 0) b0 = atomicAdd(esc_count, total);
+                        b0 = (unsigned)__builtin_amdgcn_readfirstlane((int)b0);
+                        double e[NC][7];
 #pragma unroll
-                    for (int c = 0; c < NC; ++c) same = same && cls_of(j, c) == cls_of(0, c);
-                if (__builtin_amdgcn_readfirstlane((int)(__ballot(!same) == 0ull))) form = 1;
+                        for (int c = 0; c < NC; ++c) {
+                            if (C[c] == CLS_ESCAPE) {
+                                const int64_t m = mp + (int64_t)(eo[c] >> 3);
+                                e[c][0] = at(m - a.P, 3); e[c][1] = at(m - a.nx, 2); e[c][2] = at(m - 1, 1);
+                                e[c][3] = at(m, 0); e[c][4] = at(m, 1); e[c][5] = at(m, 2); e[c][6] = at(m, 3);
+                            }
+                        }
+#pragma unroll
+                        for (int c = 0; c < NC; ++c) {
+                            if (C[c] == CLS_ESCAPE) {
+                                const unsigned below = __builtin_amdgcn_mbcnt_hi((unsigned)(em[c] >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)em[c], 0u));
+                                const int row = DYN0 + (int)((b0 + below) & (unsigned)(jk3_pool(K) - 1));
+                                double* const tr = sT + CLS_W * row;
+#pragma unroll
+                                for (int i = 0; i < 7; ++i) tr[i] = e[c][i];
+                                tr[7] = a.omega * (1.0 / (e[c][3] != 0.0 ? e[c][3] : 1.0));
+                                C[c] = row;
+                            }
+                            b0 += (unsigned)__popcll(em[c]);
+                        }
+                    }
+                }
+            }
+            {
+                unsigned m = 0;
+#pragma unroll
+                for (int q = 0; q < CW; ++q) cw[K][q] = 0u;
+#pragma unroll
+                for (int c = 0; c < NC; ++c) {
+                    cw[K][c / CPR] |= (unsigned)C[c] << (CBITS * (c % CPR));
+                    if (__builtin_amdgcn_readfirstlane((int)(__ballot(C[c] != cmain) == 0ull))) m |= 1u << c;
+                }
+                fast |= (unsigned long long)m << (K * NC);
+            }
+            // which form: 0 = interior stencil everywhere in this wave's cells of the planes k .. k+K, 1 = every cell's class the
+            // same in all those planes -- both only where every row the step touches exists (planes k-1 .. k+K+1 through sh) or lies on a
+            // neighbouring slab (there a level's values beyond its plane range are wrong instead of zero, and reach no
+            // result) --, 2 = general
+            form = 2;
+            if ((a.plo > 0 || k >= 1) && (a.phi > 0 || k + K + 1 < a.nz)) {
+                if (fast == ALLFAST) {
+                    form = 0;
+                } else {
+                    bool same = true;
+#pragma unroll
+                    for (int j = 0; j <= K; ++j)
+#pragma unroll
+                        for (int c = 0; c < NC; ++c) same = same && cls_of(j, c) == cls_of(0, c);
+                    if (__builtin_amdgcn_readfirstlane((int)(__ballot(!same) == 0ull))) form = 1;
+                }
             }
         }
         if (a.force_form >= 0) form = a.force_form;
@@ -705,11 +781,13 @@ __device__ __forceinline__ void jk3_body(const JK3Args& a) {
             for (int j = 0; j + 1 < K; ++j) fr[j][c] = fr[j + 1][c];
             asm volatile("" : "+v"(fr[K - 2][c]));
         }
+        if (!interior) {
 #pragma unroll
-        for (int j = 0; j < K; ++j)
+            for (int j = 0; j < K; ++j)
 #pragma unroll
-            for (int q = 0; q < CW; ++q) cw[j][q] = cw[j + 1][q];
-        fast >>= NC;
+                for (int q = 0; q < CW; ++q) cw[j][q] = cw[j + 1][q];
+            fast >>= NC;
+        }
         __syncthreads();
         // ---- phase B: the in-plane terms of the planes started above (ring index K - t of the moved ring); the next
         //      loads go out between its pieces ----
@@ -728,8 +806,8 @@ __device__ __forceinline__ void jk3_body(const JK3Args& a) {
         }
         auto issue = [&](const int i, const int n) __attribute__((always_inline)) {
             __builtin_amdgcn_sched_barrier(0);
-            if constexpr (PF == 2) load_slice(i, n, k + K + 2, k + K + 1, XN, CN, hyN);
-            else load_slice(i, n, k + K + 1, k + K, X, C, hy);
+            if constexpr (PF == 2) load_slice(i, n, k + K + 2, k + K + 1, interior_step(k + 2), XN, CN, hyN);
+            else load_slice(i, n, k + K + 1, k + K, interior_step(k + 1), X, C, hy);
             __builtin_amdgcn_sched_barrier(0);
         };
 #pragma unroll
@@ -748,11 +826,11 @@ __device__ __forceinline__ void jk3_body(const JK3Args& a) {
         if constexpr (!B1) __syncthreads();
     };
 
-    load_slice(0, 1, z0 - K, z0 - K - 1, XA, CA, hyA);
+    load_slice(0, 1, z0 - K, z0 - K - 1, false, XA, CA, hyA);
     if constexpr (PF == 2) {
 #pragma unroll
         for (int c = 0; c < NC; ++c) fr[K - 1][c] = FN[c];      // (the first slice's f went to the staging set)
-        load_slice(0, 1, z0 - K + 1, z0 - K, XB, CB, hyB);
+        load_slice(0, 1, z0 - K + 1, z0 - K, false, XB, CB, hyB);
     }
     __syncthreads();
 
@@ -829,6 +907,77 @@ __global__ __launch_bounds__(256) void jk3_escape_window(JK3WindowArgs a) {
         }
     }
     if (threadIdx.x == 0 && best) atomicMax(a.most, best);
+}
+
+// The march plan of a whole level for the tiles of the march <K, NW, LPW, M>: one workgroup per tile, shaped like the
+// march's, walks the planes; every wave looks at the class bytes the march's wave would load for the plane (the same
+// offsets, jk3_cell_offset / jk3_class_base) and keeps two runs of consecutive planes, the longest of their kind and the
+// first of equally long ones (r0 = r1 = 0: none):
+//   [p0, p1)  all of them are `cmain`                                   (form 0 of the march's steps)
+//   [q0, q1)  every one of them is what it was in the plane before      (form 1)
+// plan[4 * (tile * NW + wave) + 0 .. 3] = p0, p1, q0, q1.  The classes belong to the matrix: built once per level, tile
+// shape and K, dropped when the level's classes change.
+struct JK3PlanArgs {
+    const unsigned char* cls;
+    int64_t clead, P;
+    int nx, ny, nz, ntx, nty, cmain;
+    int* plan;
+};
+
+template <int K, int NW, int LPW, int M>
+__global__ __launch_bounds__(NW * WAVE) void jk3_plan(JK3PlanArgs a) {
+    constexpr int EX = 64 * M, EY = NW * LPW, NC = M * LPW, WI = EX - 2 * K, HY = EY - 2 * K + 2;
+    constexpr int U = 4;        // planes whose bytes are in flight together
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const unsigned tt = blockIdx.x;
+    const int tiy = (int)(tt / (unsigned)a.ntx), tix = (int)(tt % (unsigned)a.ntx);
+    const int tx0 = tix * WI - K, ty0 = tiy * HY - (K - 1);
+    const int ey0 = wave * LPW, bias = 2 * a.nx + K + 2, xcl = a.nx + 1 - tx0;
+    unsigned eo[NC];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) eo[c] = jk3_cell_offset(ty0 + ey0 + c / M, lane + 64 * (c % M), a.nx, a.ny, tx0, xcl, bias);
+    const unsigned char* const clsb = jk3_class_base(a.cls, a.clead, bias);
+    int p0 = 0, p1 = 0, prun = 0;       // the best run of cmain planes; where the present one starts
+    int q0 = 0, q1 = 0, qrun = 0;       // ... of planes with the classes of the plane before
+    int prev[NC];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) prev[c] = -1;
+    for (int pb = 0; pb < a.nz; pb += U) {
+        int cl[U][NC];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const unsigned char* const cb = clsb + (int64_t)min(pb + u, a.nz - 1) * a.P;
+#pragma unroll
+            for (int c = 0; c < NC; ++c) cl[u][c] = cb[eo[c] >> 3];
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int p = pb + u;
+            if (p >= a.nz) break;
+            bool all = true, same = true;
+#pragma unroll
+            for (int c = 0; c < NC; ++c) {
+                all = all && cl[u][c] == a.cmain;
+                same = same && cl[u][c] == prev[c];
+                prev[c] = cl[u][c];
+            }
+            if (__ballot(!all) != 0ull) {
+                if (p - prun > p1 - p0) { p0 = prun; p1 = p; }
+                prun = p + 1;
+            }
+            if (__ballot(!same) != 0ull) {          // (the plane starts a run of its own)
+                if (p - qrun > q1 - q0) { q0 = qrun; q1 = p; }
+                qrun = p;
+            }
+        }
+    }
+    if (a.nz - prun > p1 - p0) { p0 = prun; p1 = a.nz; }
+    if (a.nz - qrun > q1 - q0) { q0 = qrun; q1 = a.nz; }
+    if (lane == 0) {
+        int* const pw = a.plan + 4 * ((int)tt * NW + wave);
+        pw[0] = p0; pw[1] = p1; pw[2] = q0; pw[3] = q1;
+    }
 }
 
 }  // namespace mgk

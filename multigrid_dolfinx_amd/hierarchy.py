@@ -995,6 +995,14 @@ class DeviceHierarchy:
     def reset_smoother_launches(self):
         check(self._lib.mg_reset_smoother_launches(self._h))
 
+    def march_plan(self, level: int, sweeps: int) -> tuple:
+        """(waves, planes, const_waves, const_planes) of the march plan the K-sweep march of `sweeps` sweeps per pass uses
+        on `level` (`mg_march_plan`): the (tile, wave) pairs with a run of main-class planes and the planes in those
+        runs, and the same for the other runs of planes with unchanging classes; zeros where there is no plan."""
+        out = [C.c_int64() for _ in range(4)]
+        check(self._lib.mg_march_plan(self._h, self._idx(level), sweeps, *[C.byref(v) for v in out]))
+        return tuple(int(v.value) for v in out)
+
     def set_level_grid(self, level: int, grid_index=None):
         """Geometry + numbering only (transfer operators without a matrix)."""
         n = self.n_dofs(level)

@@ -1,7 +1,7 @@
 """Times the K-sweep pass (mg_jacobik3d.hip.h) on the finest level of BASELINE config 4 under a list of tuning settings,
 next to the two-sweep pass, and whole V(50,50) cycles with and without it.
 
-    python tools/time_ksweep.py [finest_level=7] [reps=6] ["fuse_k=4" "fuse_k=4,fuse_k_shape=1" ...]
+    python tools/time_ksweep.py [finest_level=7] [reps=6] ["fuse_k=4" "fuse_k=4,fuse_k_shape=1" "fuse_k=5,fuse_k_plan=0" ...]
 """
 import os
 import sys
@@ -36,6 +36,7 @@ with DeviceHierarchy.synthetic(3, 2, hi, c=8, mu1=50, mu2=50) as h:
         h.set_tuning("fuse_k_segments", 0)
         h.set_tuning("fuse_k_dpp", 1)
         h.set_tuning("fuse_k_pf", 1)
+        h.set_tuning("fuse_k_plan", 1)
     if os.environ.get("MG_SKIP_CYCLES"):
         sys.exit(0)
     for k in (0, 3, 4, 5):
