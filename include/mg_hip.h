@@ -599,7 +599,9 @@ int mg_galerkin_hierarchy(mg_handle h, int top_level);
  *     "xcd_chunk"          consecutive tiles per XCD in the chunked block -> tile map (8)
  *     "strip_slices"       slices per XCD strip, 0 = chunked map only (64)
  *     "nontemporal"        streaming loads for once-read matrix / right-hand-side data (1)
- *     "lds_pad"            dynamic LDS bytes per block on large levels = occupancy cap (32768)
+ *     "lds_pad"            dynamic LDS bytes per block of the one-sweep kernels on stored levels of at least 100000 slices
+ *                          that run without row classes (none, or "class_sweeps" 0) = occupancy cap, 0..153600 (150 KiB: one block per CU); the kernels do not
+ *                          use the bytes; bit-identical (32768)
  *     "overlap"            halo exchange on the communication stream behind the interior sweep (1)
  *     "overlap_min_rows"   ... only on levels with at least this many owned rows (4194304)
  *     "slab_pair_form"     overlapped pair sweeps on slabs: 0 = the exchange chain computes its own first sweep of the boundary

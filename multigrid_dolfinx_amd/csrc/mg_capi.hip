@@ -290,7 +290,9 @@ struct mg_context {
     // Dynamic LDS bytes requested per block by the symmetric-diagonal launches on large levels.  The kernels do not
     // use it; it caps the resident blocks per CU at 160 KiB / pad = 5 (20 waves instead of the 28 the register
     // budget allows), which measured 2.4 % faster on the 1025^3 sweep in an interleaved A/B (tools/ab_lds_pad.py:
-    // 11.64 vs 11.93 ms; 3 blocks per CU: 14.2 ms) -- fewer concurrent streams per HBM page.
+    // 11.64 vs 11.93 ms; 3 blocks per CU: 14.2 ms) -- fewer concurrent streams per HBM page.  At most kLdsPadMax: with the
+    // 32 bytes of static LDS of the dot-product form a block still fits the CU's 160 KiB (one block per CU).
+    static constexpr int kLdsPadMax = 150 * 1024;
     int lds_pad = 32768;
     int rows_per_lane = 2;      // measured best on MI355X (profiles/): 16 B value loads per lane
     unsigned chunk = 8;         // XCD chunk of the block -> tile map
@@ -1273,15 +1275,21 @@ int launch_ell(mg_context* c, const Level& L, const EllRequest& q) {
             });
         }
         const unsigned lds = a.nslices >= 100000 ? (unsigned)c->lds_pad : 0u;      // ("lds_pad", see mg_context)
-        return tiles([&](auto r, auto m, auto d, auto nt) {
+        // (a pad above the default is an experiment: like every launch that may ask for more than 64 KiB of dynamic LDS,
+        //  the kernel gets the attribute first, once, for the largest pad mg_set_tuning accepts)
+        int rc = 0;
+        const int launched = tiles([&](auto r, auto m, auto d, auto nt) {
             constexpr int R = decltype(r)::value, MODE = decltype(m)::value;
             constexpr bool DOT = decltype(d)::value, NT = decltype(nt)::value;
             with_int_else<8, 3, 4>(L.wu, [&](auto wu) {
                 constexpr int WU = decltype(wu)::value;
-                if (MODE == MODE_JACOBI && finest) hipLaunchKernelGGL((sdia_jacobi_finest<WU, R, NT>), dim3(grid), blk, lds, c->stream, a);
-                else hipLaunchKernelGGL((sdia_apply<WU, R, MODE, DOT, NT>), dim3(grid), blk, lds, c->stream, a);
+                void (*const kern[2])(EllArgs) = {sdia_apply<WU, R, MODE, DOT, NT>, sdia_jacobi_finest<WU, R, NT>};
+                const int which = MODE == MODE_JACOBI && finest ? 1 : 0;
+                if (lds > 48u * 1024u) rc =allow_large_lds(c, reinterpret_cast<const void*>(kern[which]), (size_t)mg_context::kLdsPadMax);
+                if (rc == 0) hipLaunchKernelGGL(kern[which], dim3(grid), blk, lds, c->stream, a);
             });
         });
+        return rc ? rc : launched;
     }
     if (L.coded && L.scls && c->class_sweeps) {
         // whole 3-D lattice levels: plane march with x in LDS (mg_lattice.hip.h)
@@ -4681,7 +4689,7 @@ int mg_set_tuning(mg_handle c, const char* key, int64_t value) {
     } else if (k == "nontemporal") {
         c->nontemporal = value != 0;
     } else if (k == "lds_pad") {
-        if (value < 0 || value > 160 * 1024) return fail("lds_pad out of range");
+        if (value < 0 || value > mg_context::kLdsPadMax) return fail("lds_pad must be in 0.." + std::to_string(mg_context::kLdsPadMax));
         c->lds_pad = (int)value;
     } else if (k == "halo_planes") {
         if (value != 1 && value != 2) return fail("halo_planes must be 1 or 2");

@@ -81,6 +81,17 @@ def main(world, dim, lo, hi, c, mu, replicate_below, overlap):
                 # ... in the passes the split rule gives, each one launch, or two where the boundary planes go first
                 passes, launches = expected_kslab_passes(h.elements(hi), hi - lo, world, mu, tune, overlap)
                 assert ran["ksweep_slab"][0] == launches, (ran, passes, launches)
+            if os.environ.get("MG_TEST_EXPECT_PAIR_LAUNCHES"):
+                # the pair pass on this slab, and by its launches per pair which form: two for the pass and the boundary
+                # chain's one-sweep launch in sequence, three for either overlapped form ("slab_pair_form")
+                per_pair = int(os.environ["MG_TEST_EXPECT_PAIR_LAUNCHES"])
+                h.zero_vector(hi, "v")
+                h.smooth(hi, mu)
+                want = {"pair_class": (per_pair * (mu // 2), 2 * (mu // 2), 0)}
+                if mu % 2:
+                    want["slice"] = (2 if overlap else 1, 1, 0)
+                ran = h.smoother_launches(hi)
+                assert ran == want, (ran, want)
             h.prepare_cycle(hi)
             phase(h)
             h.zero_vector(hi, "v")

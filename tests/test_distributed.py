@@ -59,8 +59,11 @@ def test_paired_sweeps_on_slabs_match_single_handle(world, mu, segments):
     """The two-sweep kernel on slabs (129^3 and 65^3 unknowns, both distributed): interior rows get both sweeps in
     one pass, the slices holding a slab's first / last plane get their second sweep from the one-sweep kernel after
     the once-relaxed boundary planes have been exchanged.  Bit-identical to the single-handle run, odd sweep
-    counts included.  With >= 4 plane segments per slab the pass is split so that both exchanges of a pair travel
-    behind interior segments (boundary segments first)."""
+    counts included.  The worker sets "overlap_min_rows" 0, so the overlap is on: the chain that waits for the neighbours
+    (first sweep of the boundary planes, exchange, finishing sweep, exchange) runs on the communication stream beside ONE
+    launch of the pass over the whole slab ("slab_pair_form" 0, the default).  The other form, boundary segments of the
+    pass first and its interior segments beside the chain ("slab_pair_form" 1), and the launch counts of both run in
+    tests/test_tuning_paths.py."""
     from tests.dist_workers import gpu_slab_worker
     _spawn(gpu_slab_worker, world, 3, 2, 4, 8, mu, 0, "gen", {"fuse_min_rows": 0, "fuse_segments": segments})
 
