@@ -1,7 +1,13 @@
 #!/usr/bin/env python3
 """bench.py -- V-cycles/s and achieved HBM GB/s of the geometric-multigrid hot path.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c4|c3|c2|c1] [--mu 50] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c4|c3|c2|c1] [--mu 50] [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and no more: it sets the hierarchy up, runs W warm-up and K timed steps,
+writes the outputs if asked to, and prints the result line.  --full adds, after that and without touching the timed steps,
+everything else this script measures and checks (full_measurements and cpu_baseline below): the dominant kernel under HIP
+events and the roofline figures, the cycles without row classes and with odd rows, V(2,2) cycles, the residual after one
+more cycle, the oracle's cycles on the CPU.
 
 A "step" is one V(mu, mu) cycle (V_cycle_scheme, multigrid.py:231-268) of the synthetic P1
 Poisson hierarchy named by --config, device-resident from start to end (the hierarchy and the
@@ -87,10 +93,15 @@ def parse():
     ap.add_argument("--transport", default="rccl", choices=["rccl", "gloo"],
                     help="slab transport for N > 1: RCCL over xGMI (default) or host-staged gloo callbacks "
                          "(debugging on a box with fewer GPUs than ranks; slow, never a headline number)")
-    ap.add_argument("--kernel-reps", type=int, default=20)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-odd-rows", action="store_true", help="skip the extra hierarchy with 1 %% odd rows (value_with_odd_rows)")
-    ap.add_argument("--cpu-sample-level", type=int, default=4, help="finest level of the CPU sample (N = 8*2^l)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check everything else: per-kernel and roofline figures, the "
+                         "cycles without row classes and with odd rows, V(2,2) cycles, the residual, the CPU baseline")
+    ap.add_argument("--kernel-reps", type=int, default=20, help="with --full: launches per HIP-event kernel timing")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the oracle's cycles on the CPU")
+    ap.add_argument("--no-odd-rows", action="store_true",
+                    help="with --full: skip the extra hierarchy with 1 %% odd rows (value_with_odd_rows)")
+    ap.add_argument("--cpu-sample-level", type=int, default=4,
+                    help="with --full: finest level of the CPU sample (N = 8*2^l)")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
                     help="write the finest level's iterate after the timed cycles to DIR/v.npy (float64, lexicographic order; "
                          "a fixed seeded sample with its indices in DIR/v_index.npy when the whole vector exceeds 64 MB)")
@@ -389,31 +400,14 @@ def launch_own_ranks(gpus):
     return rc
 
 
-def main():
-    args = parse()
-    if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        raise SystemExit(launch_own_ranks(args.gpus))
+def full_measurements(args, rv, h):
+    """--full: what the benchmark measures and checks besides the headline figure, after the timed cycles (and after
+    --dump-outputs has read what they left): the residual after one more cycle, the dominant kernel under HIP events
+    and the roofline figures priced on it, the same cycles without row classes, V(2,2) cycles, the same cycles on a
+    second hierarchy with 1 % odd rows.  Closes `h` -- the second hierarchy takes its place in device memory -- and
+    returns the keys these legs add to the result line, the handle's device memory in bytes and the device's name."""
+    dim, lo, hi, _ = CONFIGS[args.config]
     p2 = args.config == "c5"
-    if args.mu is None:
-        args.mu = 2 if p2 else 50
-    if args.omega is None:
-        args.omega = 1.0 if p2 else 2.0 / 3.0
-    # Contract: ONE JSON line on stdout.  RCCL (version banner at communicator set-up), gloo and the HIP
-    # runtime write to the C-level stdout at times, so file descriptor 1 points at stderr for the whole run and
-    # the JSON line goes to the real stdout at the very end.
-    sys.stdout.flush()
-    real_stdout = os.dup(1)
-    os.dup2(2, 1)
-    rv = Rendezvous(args.gpus)
-    dim, lo, hi, desc = CONFIGS[args.config]
-    t_setup = time.perf_counter()
-    h = build_hierarchy(args, rv)
-    h.sync()
-    t_setup = time.perf_counter() - t_setup
-
-    elapsed = timed_cycles(h, rv, hi, args.warmup, args.steps)
-    if args.dump_outputs:
-        dump_outputs(args.dump_outputs, h, rv, hi)
     res_after = h.vcycle(hi, 1, residuals=True)[0]          # untimed: convergence evidence
     f_norm = h.norm2(hi, "f")
 
@@ -564,6 +558,81 @@ def main():
                         "value": k_odd / timed_cycles(ho, rv, hi, 1, k_odd),
                         "note": "same V-cycles on a hierarchy whose levels have 1 % rows unlike any other (more than 255 distinct rows)"}
 
+    extras = {
+        "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                     "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_note,
+                     "kernel": kernel_id + (" (one fine-level nine-colour Gauss-Seidel sweep; kernel_ms is the sum of its launches"
+                                            if gs_ms else
+                                            f" ({sweeps_per_launch} fine-level weighted-Jacobi sweeps per launch" if pair_ms else
+                                            " (one fine-level weighted-Jacobi sweep per launch") +
+                               (", class-coded rows)" if dom_classes else ")"),
+                     "bytes_model": (f"{fmt_row} B per row and launch = what the shipped format must stream: "
+                                     + ("1 class byte" if dom_classes else "matrix as stored")
+                                     + " + x 8 + f 8 + out 8" + ("" if info["symmetric_diagonals"] or info["offset_codes"] else " + D^-1 8")
+                                     + "; rows_per_launch x that / kernel_ms"),
+                     "format_bytes_per_row": fmt_row, "sweeps_per_launch": sweeps_per_launch,
+                     "kernel_ms": dom_ms, "algorithmic_bytes_per_launch": bytes_launch,
+                     "rows_per_launch": n_loc, "nonzeros_per_launch": z_loc, "per_gpu": True,
+                     "row_classes": info.get("row_classes", 0),
+                     "storage": ("symmetric diagonals" if info["symmetric_diagonals"] else
+                                 "offset-coded ELL" if info["offset_codes"] else "ELL with int32 columns"),
+                     # what crosses the L2/fabric boundary per second (PMC): includes tile rims and re-reads
+                     "traffic_GBs": (traffic / (dom_ms * 1e-3) / 1e9) if traffic else None,
+                     "traffic_frac_of_peak": (traffic / (dom_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if traffic else None,
+                     "pair_pass_kernel_ms": pair2_ms,
+                     "pair_pass_frac": (fmt_row * n_loc / (pair2_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if pair2_ms else None,
+                     "single_sweep_kernel_ms": jac_ms,
+                     "single_sweep_frac": format_bytes_per_row(classes_in_sweep) * n_loc / (jac_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                     "residual_kernel_ms": res_ms,
+                     "residual_frac": (format_bytes_per_row(classes_in_sweep) - 0) * n_loc / (res_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                     "kernel_ms_without_row_classes": pair_plain_ms,
+                     "frac_without_row_classes": (format_bytes_per_row(False) * n_loc / (pair_plain_ms * 1e-3) / 1e9 / HBM_PEAK_GBS)
+                                                 if pair_plain_ms else None,
+                     # SURVEY.md 8(d)'s CSR model of the same sweeps (12 z + 36 n per sweep) over the same time: how much
+                     # faster than a kernel that streams CSR at the same byte rate -- NOT a fraction of the roofline
+                     "csr_model_bytes_per_launch": csr_model_bytes,
+                     "speedup_vs_csr_model": csr_model_bytes / bytes_launch},
+        "value_without_row_classes": value_plain,
+        "value_with_odd_rows": odd_rows,
+        "v22_cycles_per_s": v22_per_s, "residual_l2_after": res_after, "rhs_l2": f_norm,
+    }
+    return extras, mem, dev
+
+
+def main():
+    args = parse()
+    if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
+        raise SystemExit(launch_own_ranks(args.gpus))
+    p2 = args.config == "c5"
+    if args.mu is None:
+        args.mu = 2 if p2 else 50
+    if args.omega is None:
+        args.omega = 1.0 if p2 else 2.0 / 3.0
+    # Contract: ONE JSON line on stdout.  RCCL (version banner at communicator set-up), gloo and the HIP
+    # runtime write to the C-level stdout at times, so file descriptor 1 points at stderr for the whole run and
+    # the JSON line goes to the real stdout at the very end.
+    sys.stdout.flush()
+    real_stdout = os.dup(1)
+    os.dup2(2, 1)
+    rv = Rendezvous(args.gpus)
+    dim, lo, hi, desc = CONFIGS[args.config]
+    t_setup = time.perf_counter()
+    h = build_hierarchy(args, rv)
+    h.sync()
+    t_setup = time.perf_counter() - t_setup
+
+    elapsed = timed_cycles(h, rv, hi, args.warmup, args.steps)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, h, rv, hi)
+    # a plain run ends here: nothing but what the headline figure needs has touched the GPU
+    extras = {}
+    if args.full:
+        extras, mem, dev = full_measurements(args, rv, h)
+    else:
+        mem = h.memory_bytes()
+        dev = h.device_info()
+        h.close()
+
     out = None
     if rv.rank == 0:
         per_s = args.steps / elapsed
@@ -583,45 +652,11 @@ def main():
                        "levels": hi - lo + 1, "dim": dim, "elements_per_dim": 8 * 2 ** hi,
                        "parallelism": (f"slab{args.gpus}" + ("-gloo-host-staged" if args.transport == "gloo" else ""))
                                       if args.gpus > 1 else "single"},
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_note,
-                         "kernel": kernel_id + (" (one fine-level nine-colour Gauss-Seidel sweep; kernel_ms is the sum of its launches"
-                                                if gs_ms else
-                                                f" ({sweeps_per_launch} fine-level weighted-Jacobi sweeps per launch" if pair_ms else
-                                                " (one fine-level weighted-Jacobi sweep per launch") +
-                                   (", class-coded rows)" if dom_classes else ")"),
-                         "bytes_model": (f"{fmt_row} B per row and launch = what the shipped format must stream: "
-                                         + ("1 class byte" if dom_classes else "matrix as stored")
-                                         + " + x 8 + f 8 + out 8" + ("" if info["symmetric_diagonals"] or info["offset_codes"] else " + D^-1 8")
-                                         + "; rows_per_launch x that / kernel_ms"),
-                         "format_bytes_per_row": fmt_row, "sweeps_per_launch": sweeps_per_launch,
-                         "kernel_ms": dom_ms, "algorithmic_bytes_per_launch": bytes_launch,
-                         "rows_per_launch": n_loc, "nonzeros_per_launch": z_loc, "per_gpu": True,
-                         "row_classes": info.get("row_classes", 0),
-                         "storage": ("symmetric diagonals" if info["symmetric_diagonals"] else
-                                     "offset-coded ELL" if info["offset_codes"] else "ELL with int32 columns"),
-                         # what crosses the L2/fabric boundary per second (PMC): includes tile rims and re-reads
-                         "traffic_GBs": (traffic / (dom_ms * 1e-3) / 1e9) if traffic else None,
-                         "traffic_frac_of_peak": (traffic / (dom_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if traffic else None,
-                         "pair_pass_kernel_ms": pair2_ms,
-                         "pair_pass_frac": (fmt_row * n_loc / (pair2_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if pair2_ms else None,
-                         "single_sweep_kernel_ms": jac_ms,
-                         "single_sweep_frac": format_bytes_per_row(classes_in_sweep) * n_loc / (jac_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                         "residual_kernel_ms": res_ms,
-                         "residual_frac": (format_bytes_per_row(classes_in_sweep) - 0) * n_loc / (res_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                         "kernel_ms_without_row_classes": pair_plain_ms,
-                         "frac_without_row_classes": (format_bytes_per_row(False) * n_loc / (pair_plain_ms * 1e-3) / 1e9 / HBM_PEAK_GBS)
-                                                     if pair_plain_ms else None,
-                         # SURVEY.md 8(d)'s CSR model of the same sweeps (12 z + 36 n per sweep) over the same time: how much
-                         # faster than a kernel that streams CSR at the same byte rate -- NOT a fraction of the roofline
-                         "csr_model_bytes_per_launch": csr_model_bytes,
-                         "speedup_vs_csr_model": csr_model_bytes / bytes_launch},
-            "value_without_row_classes": value_plain,
-            "value_with_odd_rows": odd_rows,
-            "v22_cycles_per_s": v22_per_s, "residual_l2_after": res_after, "rhs_l2": f_norm,
+            "full": args.full,
+            **extras,
             "setup_s": t_setup, "device_memory_GB_per_gpu": mem / 1e9, "device": dev,
         }
-        if not args.no_cpu_baseline and args.gpus == 1:
+        if args.full and not args.no_cpu_baseline and args.gpus == 1:
             out["cpu_baseline"] = cpu_baseline(args)
     rv.barrier()
     rv.close()

@@ -1,4 +1,5 @@
-"""bench.py's output contract: exactly one JSON line on stdout with the agreed keys (GPU, smallest config)."""
+"""bench.py's output contract: exactly one JSON line on stdout with the agreed keys, the headline ones in a plain run and
+all of them with --full (GPU, smallest config)."""
 import json
 import os
 import subprocess
@@ -9,9 +10,114 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
+HEADLINE_KEYS = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+                 "vs_baseline", "dtype", "data", "config", "full")
+FULL_ONLY_KEYS = ("roofline", "value_without_row_classes", "value_with_odd_rows", "v22_cycles_per_s", "residual_l2_after",
+                  "rhs_l2", "cpu_baseline")
+
+
+@pytest.mark.gpu
+def test_plain_bench_run_prints_the_headline_line_only():
+    """Without --full: one JSON line with the headline keys saying what they say in a --full run, and none of the
+    figures that take runs of their own."""
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--config", "c1", "--steps", "3",
+                          "--warmup", "1"], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-3000:]
+    lines = [l for l in out.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, out.stdout[:2000]
+    d = json.loads(lines[0])
+    for key in HEADLINE_KEYS:
+        assert key in d, key
+    for key in FULL_ONLY_KEYS:
+        assert key not in d, key
+    assert d["full"] is False and d["n_gpus"] == 1 and d["steps"] == 3 and d["warmup"] == 1
+    assert d["higher_is_better"] is True and d["unit"] == "V-cycles/s" and d["dtype"] == "f64"
+    assert d["value"] > 0 and abs(d["ms_per_step"] * d["value"] - 1000.0) < 1e-6 * 1000.0
+    assert "workload" in d["config"] and d["setup_s"] > 0 and d["device_memory_GB_per_gpu"] > 0
+
+
+class _RecordingHierarchy:
+    """Stands in for the device hierarchy: records every call, and knows only the calls a plain run may make."""
+
+    def __init__(self):
+        self.calls = []
+
+    def sync(self):
+        self.calls.append(("sync",))
+
+    def zero_vector(self, level, name):
+        self.calls.append(("zero_vector", level, name))
+
+    def vcycle(self, level, n):
+        self.calls.append(("vcycle", level, n))
+
+    def memory_bytes(self):
+        self.calls.append(("memory_bytes",))
+        return 1 << 20
+
+    def device_info(self):
+        self.calls.append(("device_info",))
+        return "stub"
+
+    def close(self):
+        self.calls.append(("close",))
+
+
+def test_plain_bench_run_does_only_what_the_headline_needs(monkeypatch, capfd):
+    """Without --full the hierarchy sees set-up, the warm-up and the timed cycles, each followed by a wait, and the two
+    cheap queries of the result line -- no kernel timing, no tuning switch, no further cycle (CPU: a recording stand-in
+    that has no other method); the oracle's CPU cycles do not run either."""
+    import bench
+
+    h = _RecordingHierarchy()
+    monkeypatch.setattr(bench, "build_hierarchy", lambda args, rv: h)
+    monkeypatch.setattr(bench, "cpu_baseline", lambda args: pytest.fail("a plain run timed the CPU baseline"))
+    for name in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
+        monkeypatch.delenv(name, raising=False)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "4", "--warmup", "2"])
+    assert bench.parse().full is False
+    bench.main()
+    assert h.calls == [("sync",), ("zero_vector", 7, "v"), ("vcycle", 7, 2), ("sync",), ("vcycle", 7, 4), ("sync",),
+                       ("memory_bytes",), ("device_info",), ("close",)]
+    lines = [l for l in capfd.readouterr().out.splitlines() if l.strip()]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    for key in HEADLINE_KEYS:
+        assert key in d, key
+    for key in FULL_ONLY_KEYS:
+        assert key not in d, key
+    assert d["full"] is False and d["steps"] == 4 and d["warmup"] == 2 and d["higher_is_better"] is True
+    assert d["value"] > 0 and abs(d["ms_per_step"] * d["value"] - 1000.0) < 1e-6 * 1000.0
+
+
+def test_full_bench_run_hands_the_hierarchy_on_after_the_timed_cycles(monkeypatch, capfd):
+    """--full: the same set-up, warm-up and timed cycles, then everything else the script measures on the same
+    hierarchy, its keys in the one result line (CPU: stand-ins for the hierarchy and for both further legs)."""
+    import bench
+
+    h = _RecordingHierarchy()
+    monkeypatch.setattr(bench, "build_hierarchy", lambda args, rv: h)
+    for name in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
+        monkeypatch.delenv(name, raising=False)
+    seen = []
+    monkeypatch.setattr(bench, "full_measurements", lambda args, rv, hh: (seen.append(hh) or {"roofline": {}}, 1 << 20, "stub"))
+    monkeypatch.setattr(bench, "cpu_baseline", lambda args: {"value": 1.0})
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "4", "--warmup", "2", "--full"])
+    assert bench.parse().full is True
+    bench.main()
+    assert seen == [h]
+    assert h.calls == [("sync",), ("zero_vector", 7, "v"), ("vcycle", 7, 2), ("sync",), ("vcycle", 7, 4), ("sync",)]
+    lines = [l for l in capfd.readouterr().out.splitlines() if l.strip()]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["full"] is True and d["roofline"] == {} and d["cpu_baseline"] == {"value": 1.0}
+    assert d["steps"] == 4 and d["warmup"] == 2 and abs(d["ms_per_step"] * d["value"] - 1000.0) < 1e-6 * 1000.0
+
+
 @pytest.mark.gpu
 def test_bench_prints_one_json_line_with_the_contract_keys():
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "c1", "--steps", "3", "--warmup", "1"],
+    """--full: the headline keys and everything else the script measures, in one JSON line."""
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "c1", "--steps", "3", "--warmup", "1", "--full"],
                          capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
@@ -87,7 +193,7 @@ def test_bench_with_two_ranks_starts_itself():
     transport (the RCCL transport needs one GPU per rank): one JSON line, n_gpus 2, strong scaling."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--config", "c3", "--transport", "gloo",
-                          "--mu", "2", "--steps", "2", "--warmup", "1", "--kernel-reps", "2"],
+                          "--mu", "2", "--steps", "2", "--warmup", "1", "--kernel-reps", "2", "--full"],
                          capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]

@@ -15,7 +15,7 @@ echo "== profile" >> "$LOG"
 timeout -k 10 600 bash tools/profile_round.sh "$TAG" >> "$LOG" 2>&1
 for c in c1 c2 c3 c5; do
   echo "== bench $c" >> "$LOG"
-  timeout -k 10 300 python bench.py --config $c --steps 20 --warmup 3 > "$OUT/${TAG}_${c}_bench.json" 2> "$OUT/${TAG}_${c}_bench.err"; echo "rc=$?" >> "$LOG"
+  timeout -k 10 300 python bench.py --full --config $c --steps 20 --warmup 3 > "$OUT/${TAG}_${c}_bench.json" 2> "$OUT/${TAG}_${c}_bench.err"; echo "rc=$?" >> "$LOG"
 done
 echo "== slab probe" >> "$LOG"
 export MG_RCCL_LIBRARY=$R/tests/fake_rccl/libfake_rccl.so
