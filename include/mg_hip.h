@@ -456,6 +456,36 @@ int mg_diffusion_apply_drobin(mg_handle h, int level, int face, const double* da
 int mg_diffusion_cell_gradient(mg_handle h, int level, const double* w_dev, const double* x_dev, double* out_dev);
 int mg_diffusion_cell_gradient_t(mg_handle h, int level, const double* w_dev, const double* p_dev, double* out_dev);
 int mg_diffusion_cell_gradient_dot(mg_handle h, int level, const double* p_dev, const double* x_dev, double* out_dev);
+/* Point sources and point observations (no reference counterpart).  On a 3-D grid level with N cells per axis, nodes
+ * lexicographic (k * n1 + j) * n1 + i with n1 = N + 1, pts_dev M x 3 doubles, row m = (x, y, z) of point m in [0, 1]^3.  Per
+ * axis d: t = p_d * (double)N, c_d = min((int)floor(t), N - 1), xi_d = t - (double)c_d; pi sorts xi in descending order, stably
+ * (a tie: the lower axis first).  The point lies in the Kuhn simplex of cell c with the vertices n0 = node(c), n1 = n0 +
+ * stride(pi0), n2 = n1 + stride(pi1), n3 = n2 + stride(pi2) and the weights l0 = 1.0 - xi_pi0, l1 = xi_pi0 - xi_pi1, l2 = xi_pi1
+ * - xi_pi2, l3 = xi_pi2:
+ *     mg_diffusion_point_sample:     out = S(x), M: the P1 interpolant, out_m = ((l0 x[n0] + l1 x[n1]) + l2 x[n2]) + l3 x[n3].
+ *                                    No mask: x is the field itself, Dirichlet values included;
+ *     mg_diffusion_point_load:       out = S^T(w), nodes: the consistent point load sum_m w_m int delta(x - x_m) phi_i; point m
+ *                                    contributes l_v w_m to node n_v;
+ *     mg_diffusion_point_gradient:   out = G(x), M x 3: the gradient of the located simplex, component pi0 = (x[n1] - x[n0]) N,
+ *                                    pi1 = (x[n2] - x[n1]) N, pi2 = (x[n3] - x[n2]) N;
+ *     mg_diffusion_point_gradient_t: out = G^T(p), nodes, p M x 3: with P_a = p[m][pi_a] point m contributes (0.0 - P_0) N,
+ *                                    (P_0 - P_1) N, (P_1 - P_2) N, P_2 N to n0 .. n3.
+ * In both transposes a node starts at +0.0 and takes its contributions in ascending point index, an untouched node is +0.0, and
+ * two calls give the same bits however many points share a node: no floating-point atomic, but a stable radix sort of the 4 M
+ * (node, contribution) pairs by node and one thread per run (mg_diffusion_points.hip.h).  They are adjoint up to rounding,
+ * <w, S(x)> = <x, S^T(w)>, <p, G(x)> = <x, G^T(p)>, and close under differentiation in the fields; d S(x)_m / d pts_m = G(x)_m
+ * inside the located simplex (x_h kinks on simplex faces), G is piecewise constant in pts.  None reads kappa or a matrix: any
+ * whole 3-D grid level will do, stored, matrix-free or grid-only (mg_set_level_grid).  poisson.diffusion_point_locate,
+ * diffusion_point_sample, _load, _gradient and _gradient_t restate them bit for bit (no fma in any).  They run on the handle's
+ * stream, which is synchronised before return; the temporaries of the transposes (128 M bytes and the sort's) are freed on
+ * return and no handle memory, vector or counter is touched.  Refused with an error before anything is allocated or launched:
+ * a null handle, 2-D handles, slab handles, flat and unset levels, M < 1 (and M > 2^31), null pointers, pointers that are not device memory of
+ * the handle's device, and an out_dev that overlaps an input.  Refused after one checking kernel, with out_dev unwritten: a
+ * coordinate that is not finite or lies outside [0, 1]; the message names the lowest offending point index. */
+int mg_diffusion_point_sample(mg_handle h, int level, int64_t M, const double* pts_dev, const double* x_dev, double* out_dev);
+int mg_diffusion_point_load(mg_handle h, int level, int64_t M, const double* pts_dev, const double* w_dev, double* out_dev);
+int mg_diffusion_point_gradient(mg_handle h, int level, int64_t M, const double* pts_dev, const double* x_dev, double* out_dev);
+int mg_diffusion_point_gradient_t(mg_handle h, int level, int64_t M, const double* pts_dev, const double* p_dev, double* out_dev);
 /* getJacobiMatrices (multigrid.py:48-56) as a stand-alone set-up kernel, for callers that
  * want the reference's split operands back: for every stored entry a_ij of the CSR matrix
  * writes scaled[q] = a_ij / a_ii computed as (1/a_ii) * a_ij, keep[q] = 1 unless the entry

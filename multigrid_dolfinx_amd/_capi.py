@@ -101,6 +101,10 @@ SIGNATURES = {
     "mg_diffusion_cell_gradient": [_H, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
     "mg_diffusion_cell_gradient_t": [_H, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
     "mg_diffusion_cell_gradient_dot": [_H, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
+    "mg_diffusion_point_sample": [_H, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p],
+    "mg_diffusion_point_load": [_H, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p],
+    "mg_diffusion_point_gradient": [_H, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p],
+    "mg_diffusion_point_gradient_t": [_H, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p],
     "mg_diffusion_drobin": [_H, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
     "mg_diffusion_apply_drobin": [_H, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
     "mg_zero_vector": [_H, C.c_int, C.c_int],

@@ -13,6 +13,7 @@
 #include "mg_diffusion_mf_batch.hip.h"
 #include "mg_diffusion_adj.hip.h"
 #include "mg_diffusion_flux.hip.h"
+#include "mg_diffusion_points.hip.h"
 #include "mg_diffusion_kappa.hip.h"
 
 #include <dlfcn.h>
@@ -6034,6 +6035,121 @@ int mg_diffusion_cell_gradient_dot(mg_handle c, int level, const double* p_dev, 
     MG_TRY(launch_cell_grad<CG_C>(c, L, nullptr, p_dev, x_dev, out_dev));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return 0;
+}
+
+// The point family (mg_diffusion_points.hip.h) on a whole 3-D grid level, every refusal with the entry's name: what the cell
+// gradient family refuses, M < 1, and -- after one checking kernel -- a coordinate outside [0, 1], by the lowest offending point
+// index (an integer min, as check_kappa).
+static int need_point_level(mg_context* c, int level, const char* who) {
+    const std::string w(who);
+    if (!c) return fail(w + ": null handle");
+    if (c->dim != 3) return fail(w + ": points are located on 3-D levels only (this handle is 2-D)");
+    if (c->comm.active()) return fail(w + " needs a whole (not slab) handle");
+    if (level < 0 || level >= c->nlev) return fail(w + ": level " + std::to_string(level) + " out of range");
+    if (!c->L[level].set) return fail(w + ": level " + std::to_string(level) + " has not been set");
+    if (c->L[level].flat) return fail(w + ": level " + std::to_string(level) + " is flat (no grid): it has no cells");
+    return 0;
+}
+
+static int need_points(mg_context* c, const char* who, int64_t M, const double* pts) {
+    DevTemp d_first;
+    MG_TRY(d_first.alloc(sizeof(unsigned long long)));
+    HIP_TRY(hipMemsetAsync(d_first.p, 0xff, sizeof(unsigned long long), c->stream));
+    const unsigned nb = (unsigned)std::max<int64_t>(1, std::min<int64_t>(8192, (3 * M + 255) / 256));
+    hipLaunchKernelGGL(pt_check, dim3(nb), dim3(256), 0, c->stream, pts, 3 * M, d_first.as<unsigned long long>());
+    HIP_TRY(hipGetLastError());
+    unsigned long long first = 0;
+    HIP_TRY(hipMemcpyAsync(&first, d_first.p, sizeof(first), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (first == ~0ull) return 0;
+    double x[3] = {0.0, 0.0, 0.0};
+    HIP_TRY(hipMemcpy(x, pts + 3 * first, sizeof(x), hipMemcpyDeviceToHost));
+    char val[120];
+    snprintf(val, sizeof(val), "(%.17g, %.17g, %.17g)", x[0], x[1], x[2]);
+    return fail(std::string(who) + ": a point must lie in the unit cube, every coordinate finite and in [0, 1]: point " +
+                std::to_string(first) + " is " + val);
+}
+
+static int need_point_count(const char* who, int64_t M) {
+    if (M < 1) return fail(std::string(who) + ": M = " + std::to_string(M) + " (at least one point is needed)");
+    if (M > (int64_t)1 << 31) return fail(std::string(who) + ": M = " + std::to_string(M) + " is more than 2^31 points");
+    return 0;
+}
+
+static PtArgs pt_args(const Level& L, int64_t M, const double* pts, const double* x, double* out, uint64_t* keys) {
+    PtArgs a{};
+    a.pts = pts; a.x = x; a.out = out; a.keys = keys;
+    a.M = M; a.nx = L.g.nx; a.plane = L.g.plane; a.N = L.N;
+    return a;
+}
+
+// S (GRAD false) or G (GRAD true) of the field x at the points
+static int point_gather(mg_context* c, const bool GRAD, const char* who, int level, int64_t M, const double* pts, const double* x, double* out) {
+    MG_TRY(need_point_level(c, level, who));
+    MG_TRY(need_point_count(who, M));
+    HIP_TRY(hipSetDevice(c->device));
+    const Level& L = c->L[level];
+    MG_TRY(need_operands(c, who, {{"pts", pts, (size_t)M * 24, false, ""}, {"x", x, node_bytes(L), false, ""}}, out,
+                         (size_t)M * (GRAD ? 24 : 8)));
+    MG_TRY(need_points(c, who, M, pts));
+    const PtArgs a = pt_args(L, M, pts, x, out, nullptr);
+    if (GRAD) hipLaunchKernelGGL(pt_gradient, dim3(blocks_for(M, PT_BLOCK)), dim3(PT_BLOCK), 0, c->stream, a);
+    else hipLaunchKernelGGL(pt_sample, dim3(blocks_for(M, PT_BLOCK)), dim3(PT_BLOCK), 0, c->stream, a);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// S^T (GRAD false, in = w, M) or G^T (GRAD true, in = p, M x 3) onto the nodes: pairs, a stable sort by node, one add per run
+static int point_scatter(mg_context* c, const bool GRAD, const char* who, int level, int64_t M, const double* pts, const double* in, double* out) {
+    MG_TRY(need_point_level(c, level, who));
+    MG_TRY(need_point_count(who, M));
+    HIP_TRY(hipSetDevice(c->device));
+    const Level& L = c->L[level];
+    MG_TRY(need_operands(c, who, {{"pts", pts, (size_t)M * 24, false, ""}, {GRAD ? "p" : "w", in, (size_t)M * (GRAD ? 24 : 8), false, ""}},
+                         out, node_bytes(L)));
+    MG_TRY(need_points(c, who, M, pts));
+    const size_t n = 4 * (size_t)M;
+    const uint64_t nodes = (uint64_t)L.g.plane * (uint64_t)L.g.nz;
+    unsigned bits = 1;                                      // the bits of the largest node id
+    while (bits < 64 && ((nodes - 1) >> bits) != 0) ++bits;
+    DevTemp keys_t, keys_s, vals_t, vals_s, sort_t;
+    MG_TRY(keys_t.alloc(n * 8));
+    MG_TRY(keys_s.alloc(n * 8));
+    MG_TRY(vals_t.alloc(n * 8));
+    MG_TRY(vals_s.alloc(n * 8));
+    size_t sort_bytes = 0;
+    HIP_TRY(rocprim::radix_sort_pairs(nullptr, sort_bytes, keys_t.as<uint64_t>(), keys_s.as<uint64_t>(), vals_t.as<double>(),
+                                      vals_s.as<double>(), n, 0u, bits, c->stream));
+    MG_TRY(sort_t.alloc(sort_bytes));
+    HIP_TRY(hipMemsetAsync(out, 0, node_bytes(L), c->stream));
+    const PtArgs a = pt_args(L, M, pts, in, vals_t.as<double>(), keys_t.as<uint64_t>());
+    if (GRAD) hipLaunchKernelGGL(pt_contrib<true>, dim3(blocks_for(M, PT_BLOCK)), dim3(PT_BLOCK), 0, c->stream, a);
+    else hipLaunchKernelGGL(pt_contrib<false>, dim3(blocks_for(M, PT_BLOCK)), dim3(PT_BLOCK), 0, c->stream, a);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(rocprim::radix_sort_pairs(sort_t.p, sort_bytes, keys_t.as<uint64_t>(), keys_s.as<uint64_t>(), vals_t.as<double>(),
+                                      vals_s.as<double>(), n, 0u, bits, c->stream));
+    hipLaunchKernelGGL(pt_run_sum, dim3(blocks_for((int64_t)n, PT_BLOCK)), dim3(PT_BLOCK), 0, c->stream, keys_s.as<const uint64_t>(),
+                       vals_s.as<const double>(), (int64_t)n, out);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(c->stream));              // the temporaries are freed on return
+    return 0;
+}
+
+int mg_diffusion_point_sample(mg_handle c, int level, int64_t M, const double* pts_dev, const double* x_dev, double* out_dev) {
+    return point_gather(c, false, "mg_diffusion_point_sample", level, M, pts_dev, x_dev, out_dev);
+}
+
+int mg_diffusion_point_load(mg_handle c, int level, int64_t M, const double* pts_dev, const double* w_dev, double* out_dev) {
+    return point_scatter(c, false, "mg_diffusion_point_load", level, M, pts_dev, w_dev, out_dev);
+}
+
+int mg_diffusion_point_gradient(mg_handle c, int level, int64_t M, const double* pts_dev, const double* x_dev, double* out_dev) {
+    return point_gather(c, true, "mg_diffusion_point_gradient", level, M, pts_dev, x_dev, out_dev);
+}
+
+int mg_diffusion_point_gradient_t(mg_handle c, int level, int64_t M, const double* pts_dev, const double* p_dev, double* out_dev) {
+    return point_scatter(c, true, "mg_diffusion_point_gradient_t", level, M, pts_dev, p_dev, out_dev);
 }
 
 int mg_zero_vector(mg_handle c, int level, int which) {

@@ -830,6 +830,37 @@ class DeviceHierarchy:
         cells = self.elements(level) ** 3
         return self._sensitivity(entry, [("p", p, 3 * cells, False), ("x", x, self.n_dofs(level), False)], cells, out)
 
+    def _point_entry(self, fn, level: int, M: int):
+        return lambda pp, pv, po: fn(self._h, self._idx(level), C.c_int64(int(M)), pp, pv, po)
+
+    def diffusion_point_sample(self, level: int, M: int, pts, x, out=None):
+        """S(x, pts): the P1 interpolant of the nodal field `x` of a 3-D grid level at the `M` points `pts` (M x 3, rows (x, y, z)
+        in the unit cube), M values (`mg_diffusion_point_sample`; host restatement: `poisson.diffusion_point_sample`, same
+        bits).  Device addresses or NumPy arrays, as in `diffusion_cell_gradient`."""
+        entry = self._point_entry(self._lib.mg_diffusion_point_sample, level, M)
+        return self._sensitivity(entry, [("pts", pts, 3 * M, False), ("x", x, self.n_dofs(level), False)], M, out)
+
+    def diffusion_point_load(self, level: int, M: int, pts, w, out=None):
+        """S^T(w, pts): the consistent point load of the weights `w` (M) at the points `pts`, nodal values, summed per node in
+        ascending point index (`mg_diffusion_point_load`; host restatement: `poisson.diffusion_point_load`, same bits).
+        Device addresses or NumPy arrays, as in `diffusion_cell_gradient`."""
+        entry = self._point_entry(self._lib.mg_diffusion_point_load, level, M)
+        return self._sensitivity(entry, [("pts", pts, 3 * M, False), ("w", w, M, False)], self.n_dofs(level), out)
+
+    def diffusion_point_gradient(self, level: int, M: int, pts, x, out=None):
+        """G(x, pts): the gradient of the nodal field `x` in the simplex that holds each point, M x 3 values
+        (`mg_diffusion_point_gradient`; host restatement: `poisson.diffusion_point_gradient`, same bits).  Device addresses
+        or NumPy arrays, as in `diffusion_cell_gradient`."""
+        entry = self._point_entry(self._lib.mg_diffusion_point_gradient, level, M)
+        return self._sensitivity(entry, [("pts", pts, 3 * M, False), ("x", x, self.n_dofs(level), False)], 3 * M, out)
+
+    def diffusion_point_gradient_t(self, level: int, M: int, pts, p, out=None):
+        """G^T(p, pts): the transpose of `diffusion_point_gradient` in x applied to `p` (M x 3), nodal values, summed per node in
+        ascending point index (`mg_diffusion_point_gradient_t`; host restatement: `poisson.diffusion_point_gradient_t`, same
+        bits).  Device addresses or NumPy arrays, as in `diffusion_cell_gradient`."""
+        entry = self._point_entry(self._lib.mg_diffusion_point_gradient_t, level, M)
+        return self._sensitivity(entry, [("pts", pts, 3 * M, False), ("p", p, 3 * M, False)], self.n_dofs(level), out)
+
     def zero_vector(self, level: int, which: str = "v"):
         check(self._lib.mg_zero_vector(self._h, self._idx(level), _VEC[which]))
 

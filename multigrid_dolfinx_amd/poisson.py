@@ -1133,6 +1133,104 @@ def diffusion_cell_gradient_t(N: int, w, p) -> np.ndarray:
     return np.ascontiguousarray((acc * (N / 6.0)).reshape(-1))
 
 
+def _points(pts) -> np.ndarray:
+    P = np.array(pts, dtype=np.float64)
+    if P.ndim != 2 or P.shape[1] != 3 or P.shape[0] < 1:
+        raise ValueError(f"points are an (M, 3) array with M >= 1 (got shape {P.shape})")
+    bad = np.flatnonzero(~((P >= 0.0) & (P <= 1.0)).all(axis=1))
+    if bad.size:
+        m = int(bad[0])
+        raise ValueError(f"a point must lie in the unit cube, every coordinate finite and in [0, 1]: point {m} is "
+                         f"({P[m, 0]!r}, {P[m, 1]!r}, {P[m, 2]!r})")
+    return P
+
+
+def _nodal(x, N: int) -> np.ndarray:
+    v = np.array(x, dtype=np.float64).reshape(-1)
+    if v.size != (N + 1) ** 3:
+        raise ValueError(f"vector has {v.size} entries, the level has {(N + 1) ** 3} nodes")
+    return v
+
+
+def diffusion_point_locate(N: int, pts):
+    """The Kuhn simplex of the 3-D `diffusion_level` mesh that holds each point, as `pt_locate` (mg_diffusion_points.hip.h) finds
+    it, same bits.  `pts`: (M, 3), row m = (x, y, z) in [0, 1]^3 (anything else is a ValueError that names the lowest
+    offending point).  Per axis d: t = p_d * float(N), c_d = min(int(floor(t)), N - 1), xi_d = t - float(c_d) (exact; p_d = 1
+    gives c_d = N - 1, xi_d = 1).  pi sorts xi in descending order, stably: on a tie the lower axis comes first.  Returns
+    (nodes, weights, pi): nodes (M, 4) int64 = n0 = node(c), n1 = n0 + stride(pi0), n2 = n1 + stride(pi1), n3 = n2 + stride(pi2)
+    with the strides (1, N + 1, (N + 1)^2) of x, y, z; weights (M, 4) = 1.0 - xi_pi0, xi_pi0 - xi_pi1, xi_pi1 - xi_pi2, xi_pi2;
+    pi (M, 3) int64."""
+    P = _points(pts)
+    n1 = N + 1
+    t = P * float(N)
+    c = np.minimum(np.floor(t).astype(np.int64), N - 1)
+    xi = t - c.astype(np.float64)
+    pi = np.argsort(-xi, axis=1, kind="stable").astype(np.int64)
+    s = np.take_along_axis(xi, pi, axis=1)
+    stride = np.array([1, n1, n1 * n1], dtype=np.int64)[pi]
+    n0 = (c[:, 2] * n1 + c[:, 1]) * n1 + c[:, 0]
+    nodes = np.stack([n0, n0 + stride[:, 0], n0 + stride[:, 0] + stride[:, 1], n0 + stride[:, 0] + stride[:, 1] + stride[:, 2]], axis=1)
+    lam = np.stack([1.0 - s[:, 0], s[:, 0] - s[:, 1], s[:, 1] - s[:, 2], s[:, 2]], axis=1)
+    return nodes, lam, pi
+
+
+def diffusion_point_sample(N: int, pts, x) -> np.ndarray:
+    """S(x, pts), M values: the P1 interpolant of the nodal field `x` (lexicographic, read as it is: no mask) at the points, as
+    `mg_diffusion_point_sample` computes it (same bits): out_m = ((l0 * x[n0] + l1 * x[n1]) + l2 * x[n2]) + l3 * x[n3] with
+    the vertices and weights of `diffusion_point_locate`."""
+    n, lam, _ = diffusion_point_locate(N, pts)
+    v = _nodal(x, N)
+    return ((lam[:, 0] * v[n[:, 0]] + lam[:, 1] * v[n[:, 1]]) + lam[:, 2] * v[n[:, 2]]) + lam[:, 3] * v[n[:, 3]]
+
+
+def diffusion_point_gradient(N: int, pts, x) -> np.ndarray:
+    """G(x, pts), (M, 3): the gradient of x_h in the simplex that holds each point, as `mg_diffusion_point_gradient` computes it
+    (same bits): component pi0 = (x[n1] - x[n0]) * float(N), pi1 = (x[n2] - x[n1]) * float(N), pi2 = (x[n3] - x[n2]) * float(N)."""
+    n, _, pi = diffusion_point_locate(N, pts)
+    v = _nodal(x, N)
+    out = np.empty((n.shape[0], 3))
+    rows = np.arange(n.shape[0])
+    for a in range(3):
+        out[rows, pi[:, a]] = (v[n[:, a + 1]] - v[n[:, a]]) * float(N)
+    return out
+
+
+def _point_scatter(N: int, nodes, contrib) -> np.ndarray:
+    """Every node starts at +0.0 and takes the contributions of the points in ascending point index.  `np.add.at` is unbuffered
+    and walks its indices front to back, so this is a SEQUENTIAL sum over the points, one vertex column at a time; the four
+    vertices of one point are distinct nodes, so the column order does not show in any node's sum."""
+    out = np.zeros((N + 1) ** 3)
+    np.add.at(out, nodes.reshape(-1), contrib.reshape(-1))          # index 4 m + v: ascending m
+    return out
+
+
+def diffusion_point_load(N: int, pts, w) -> np.ndarray:
+    """S^T(w, pts), (N + 1)^3 nodes: the consistent point load sum_m w_m int delta(x - x_m) phi_i, as `mg_diffusion_point_load`
+    computes it (same bits).  Point m contributes l_v * w_m to node n_v (`diffusion_point_locate`); a node starts at +0.0 and
+    takes its contributions in ascending point index -- a sequential loop over the points (`np.add.at`, unbuffered, front to
+    back), which is what the device's stable sort by node and one add per run reproduce.  Untouched nodes are +0.0."""
+    n, lam, _ = diffusion_point_locate(N, pts)
+    wv = np.array(w, dtype=np.float64).reshape(-1)
+    if wv.size != n.shape[0]:
+        raise ValueError(f"{n.shape[0]} points need {n.shape[0]} weights (got {wv.size})")
+    return _point_scatter(N, n, lam * wv[:, None])
+
+
+def diffusion_point_gradient_t(N: int, pts, p) -> np.ndarray:
+    """G^T(p, pts), (N + 1)^3 nodes: the transpose of `diffusion_point_gradient` in x, as `mg_diffusion_point_gradient_t`
+    computes it (same bits).  With P_a = p[m][pi_a] point m contributes (0.0 - P_0) * float(N), (P_0 - P_1) * float(N),
+    (P_1 - P_2) * float(N), P_2 * float(N) to n0 .. n3; the nodes are summed as in `diffusion_point_load`: sequentially, in
+    ascending point index, from +0.0."""
+    n, _, pi = diffusion_point_locate(N, pts)
+    pv = np.array(p, dtype=np.float64).reshape(-1)
+    if pv.size != 3 * n.shape[0]:
+        raise ValueError(f"{n.shape[0]} points need {3 * n.shape[0]} components (got {pv.size})")
+    P = np.take_along_axis(pv.reshape(-1, 3), pi, axis=1)
+    Nd = float(N)
+    contrib = np.stack([(0.0 - P[:, 0]) * Nd, (P[:, 0] - P[:, 1]) * Nd, (P[:, 1] - P[:, 2]) * Nd, P[:, 2] * Nd], axis=1)
+    return _point_scatter(N, n, contrib)
+
+
 def diffusion_apply_dkappa(N: int, dkappa, x, rows: str = "interior", cols: str = "interior", dirichlet_faces=ALL_FACES) -> np.ndarray:
     """(dA/dkappa . dkappa) x for the 3-D `diffusion_level`: the derivative of A(kappa) x in the direction `dkappa` (N^3 values in
     the cell order of `diffusion_level`, of any sign), as `mg_diffusion_apply_dkappa` computes it.  A is linear in kappa, so an

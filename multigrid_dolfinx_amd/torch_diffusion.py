@@ -126,7 +126,14 @@ class DiffusionSolver:
     of a nodal field, (3, N, N, N) indexed [d, ck, cj, ci]: per cell the mean of grad u_h over its six simplices
     (`mg_diffusion_cell_gradient`), differentiable in both arguments to second order through F, its transpose and its
     contraction (`_CellGrad`, `_CellGradT`, `_CellGradDot`), which close under differentiation as D and T do.  They read the top
-    level's grid and nothing else: they work before the first solve and leave the hierarchy and the counters alone."""
+    level's grid and nothing else: they work before the first solve and leave the hierarchy and the counters alone.
+
+    `sample(u, points)`, `point_load(points, w)` and `sample_gradient(u, points)` put observations and sources anywhere in the
+    unit cube: the P1 interpolant S on the located Kuhn simplex, its transpose S^T (the consistent point load) and the
+    simplex gradient G (`mg_diffusion_point_sample`, `_load`, `_gradient`, `_gradient_t`), differentiable to second order in
+    the fields and in the positions (`_PointSample`, `_PointLoad`, `_PointGrad`, `_PointGradT`, which close under
+    differentiation).  The position derivative is the one inside the located simplex.  They too read the top level's grid
+    alone."""
 
     def __init__(self, N: int, n_levels: int, averaging: str = "arithmetic", matrix_free_min_rows: Optional[int] = None,
                  rtol: float = 1e-10, max_iter: int = 200, device: int = 0, warm_start: bool = False, dirichlet_faces=None,
@@ -289,6 +296,37 @@ class DiffusionSolver:
         """q = -kappa grad u per cell, (3, N, N, N): the exact cell average of the flux of the P1 field, -`gradient`(u, kappa).
         With u a pressure it is the Darcy velocity, with u a temperature the heat flux."""
         return -self.gradient(u, weight=kappa)
+
+    def sample(self, u: torch.Tensor, points: torch.Tensor) -> torch.Tensor:
+        """u_h at the points, (M,): the P1 interpolant on the Kuhn simplices the operator is built on
+        (`mg_diffusion_point_sample`), not a trilinear one.  `u`: (N + 1)^3 float64 on the solver's device, read as it is
+        (Dirichlet values included); `points`: (M, 3) float64 rows (x, y, z) in [0, 1]^3 on the solver's device.
+        Differentiable to second order in `u` and in `points`.  The position derivative is the derivative inside the
+        located simplex, grad u_h there (`sample_gradient`): u_h is piecewise linear and kinks on simplex faces, so at a point
+        on a face it is the one-sided derivative of the simplex that `poisson.diffusion_point_locate` picks.  Works before
+        the first solve and leaves the hierarchy alone: `n_generations` and `n_solves` do not move."""
+        self._top_level_grid()
+        return _PointSample.apply(self._same_size(u, "u").reshape(-1), points, self)
+
+    def point_load(self, points: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
+        """The consistent load of point sources of strength `w` (M float64 on the solver's device) at `points` ((M, 3), as in
+        `sample`): f_i = sum_m w_m phi_i(x_m), the transpose of `sample` (`mg_diffusion_point_load`), (N + 1, N + 1, N + 1)
+        indexed [k, j, i].  Each node sums its points in ascending point index: the same bits on every call.  Differentiable
+        to second order in `w` and in `points`; the position derivative is the one inside the located simplex, as in `sample`.
+        A point in a boundary cell puts load on Dirichlet nodes.  `solve(kappa, f)` without `g` reads the entries of `f` on
+        Dirichlet nodes as boundary values, so a point-source solve is `solve(kappa, point_load(X, w), g=zeros)`: with `g`
+        given, `f` on Dirichlet nodes does not count.  Works before the first solve and leaves the hierarchy alone."""
+        self._top_level_grid()
+        n1 = self.N + 1
+        return _PointLoad.apply(w.reshape(-1), points, self).view(n1, n1, n1)
+
+    def sample_gradient(self, u: torch.Tensor, points: torch.Tensor) -> torch.Tensor:
+        """grad u_h at the points, (M, 3) with components (x, y, z): the gradient of the simplex that holds each point
+        (`mg_diffusion_point_gradient`).  `u` and `points` as in `sample`.  Differentiable to second order in `u`; piecewise
+        constant in `points`, which get no derivative: u_h is piecewise linear and its gradient jumps on simplex faces.
+        Works before the first solve and leaves the hierarchy alone."""
+        self._top_level_grid()
+        return _PointGrad.apply(self._same_size(u, "u").reshape(-1), points, self)
 
     def tangent(self, kappa: torch.Tensor, f: torch.Tensor, dkappa: torch.Tensor, df: Optional[torch.Tensor] = None,
                 g: Optional[torch.Tensor] = None, dg: Optional[torch.Tensor] = None, sigma: Optional[torch.Tensor] = None,
@@ -680,3 +718,90 @@ class _CellGradDot(torch.autograd.Function):
         grad_p = _CellGrad.apply(z, x, ctx.solver).view(p.shape) if ctx.needs_input_grad[0] else None
         grad_x = _CellGradT.apply(z, p, ctx.solver).view(x.shape) if ctx.needs_input_grad[1] else None
         return grad_p, grad_x, None
+
+
+def _points(solver, X: torch.Tensor) -> torch.Tensor:
+    if X.dtype != torch.float64 or X.device != solver.device or X.dim() != 2 or X.shape[1] != 3 or X.shape[0] < 1:
+        raise ValueError(f"points must be (M, 3) float64 with M >= 1 on {solver.device} (got {tuple(X.shape)} {X.dtype} on {X.device})")
+    return X.detach().contiguous()
+
+
+def _point_launch(solver, method, n_out: int, X: torch.Tensor, v: torch.Tensor) -> torch.Tensor:
+    M = X.shape[0]
+    return _launch(solver, lambda level, pp, pv, po: method(level, M, pp, pv, po), n_out, X, v)
+
+
+class _PointSample(torch.autograd.Function):
+    """S(u, X) = mg_diffusion_point_sample, M values: the P1 interpolant of the nodal field u at the points X.  With cotangent
+    y: u_bar = S^T(y, X), X_bar = y[:, None] * G(u, X) -- the derivative inside the located simplex."""
+
+    @staticmethod
+    def forward(ctx, u, X, solver):
+        ctx.solver = solver
+        ctx.save_for_backward(u, X)
+        return _point_launch(solver, solver.hierarchy.diffusion_point_sample, X.shape[0], _points(solver, X),
+                             solver._device_vector(u, "u"))
+
+    @staticmethod
+    def backward(ctx, y):
+        u, X = ctx.saved_tensors
+        grad_u = _PointLoad.apply(y, X, ctx.solver).view(u.shape) if ctx.needs_input_grad[0] else None
+        grad_X = y[:, None] * _PointGrad.apply(u, X, ctx.solver) if ctx.needs_input_grad[1] else None
+        return grad_u, grad_X, None
+
+
+class _PointLoad(torch.autograd.Function):
+    """S^T(w, X) = mg_diffusion_point_load, (N + 1)^3 nodes: the consistent point load of the weights w at the points X.  With
+    cotangent y (nodes): w_bar = S(y, X), X_bar = w[:, None] * G(y, X)."""
+
+    @staticmethod
+    def forward(ctx, w, X, solver):
+        ctx.solver = solver
+        ctx.save_for_backward(w, X)
+        Xc = _points(solver, X)
+        return _point_launch(solver, solver.hierarchy.diffusion_point_load, solver.hierarchy.n_dofs(solver.top), Xc,
+                             solver._holds(w, Xc.shape[0], "the point weights").detach().contiguous())
+
+    @staticmethod
+    def backward(ctx, y):
+        w, X = ctx.saved_tensors
+        grad_w = _PointSample.apply(y, X, ctx.solver).view(w.shape) if ctx.needs_input_grad[0] else None
+        grad_X = w.reshape(-1)[:, None] * _PointGrad.apply(y, X, ctx.solver) if ctx.needs_input_grad[1] else None
+        return grad_w, grad_X, None
+
+
+class _PointGrad(torch.autograd.Function):
+    """G(u, X) = mg_diffusion_point_gradient, (M, 3): the gradient of u_h in the simplex that holds each point.  With cotangent
+    P: u_bar = G^T(P, X); piecewise constant in X, so X gets no derivative."""
+
+    @staticmethod
+    def forward(ctx, u, X, solver):
+        ctx.solver = solver
+        ctx.save_for_backward(u, X)
+        return _point_launch(solver, solver.hierarchy.diffusion_point_gradient, 3 * X.shape[0], _points(solver, X),
+                             solver._device_vector(u, "u")).view(-1, 3)
+
+    @staticmethod
+    def backward(ctx, P):
+        u, X = ctx.saved_tensors
+        grad_u = _PointGradT.apply(P, X, ctx.solver).view(u.shape) if ctx.needs_input_grad[0] else None
+        return grad_u, None, None
+
+
+class _PointGradT(torch.autograd.Function):
+    """G^T(p, X) = mg_diffusion_point_gradient_t, (N + 1)^3 nodes: the transpose of G in u.  With cotangent y: p_bar = G(y, X);
+    X gets no derivative."""
+
+    @staticmethod
+    def forward(ctx, p, X, solver):
+        ctx.solver = solver
+        ctx.save_for_backward(p, X)
+        Xc = _points(solver, X)
+        return _point_launch(solver, solver.hierarchy.diffusion_point_gradient_t, solver.hierarchy.n_dofs(solver.top), Xc,
+                             solver._holds(p, 3 * Xc.shape[0], "the point vectors").detach().contiguous())
+
+    @staticmethod
+    def backward(ctx, y):
+        p, X = ctx.saved_tensors
+        grad_p = _PointGrad.apply(y, X, ctx.solver).view(p.shape) if ctx.needs_input_grad[0] else None
+        return grad_p, None, None
