@@ -486,6 +486,41 @@ int mg_diffusion_point_sample(mg_handle h, int level, int64_t M, const double* p
 int mg_diffusion_point_load(mg_handle h, int level, int64_t M, const double* pts_dev, const double* w_dev, double* out_dev);
 int mg_diffusion_point_gradient(mg_handle h, int level, int64_t M, const double* pts_dev, const double* x_dev, double* out_dev);
 int mg_diffusion_point_gradient_t(mg_handle h, int level, int64_t M, const double* pts_dev, const double* p_dev, double* out_dev);
+/* Located point sets: the four point operators for one fixed set of points and any number of fields per call (no reference
+ * counterpart).  A set is checked, located and sorted once; its calls launch no checking kernel, allocate nothing, sort nothing
+ * and make no host round trip besides the final synchronisation.
+ *   mg_points_create   copies the M points of pts_dev (the caller's array may be freed or overwritten afterwards), locates them
+ *       on `level` with the rule above, orders the 4 M (node, slot = 4 m + v) pairs by node with the stable radix sort of the
+ *       transposes, and keeps, in device memory that mg_memory_bytes counts: the points (24 M bytes), one 16-byte record per
+ *       sorted slot (weight, point index, vertex and the two axes its gradient term reads: 64 M bytes) and the R runs of equal
+ *       node (run_start[R + 1], run_node[R]: 16 R + 8 bytes).  Its temporaries are freed on return; no vector, level, counter,
+ *       graph or lane of the handle is touched.  The set belongs to the handle: mg_destroy frees the sets that are left.
+ *       Refused by name exactly as mg_diffusion_point_* refuse: before any allocation a null handle, 2-D and slab handles, flat
+ *       and unset levels, M < 1 (and M > 2^31), null pointers and pointers that are not device memory of the handle's device;
+ *       after the one checking kernel a coordinate that is not finite or outside [0, 1], the lowest offending point named,
+ *       with no set made (*ps is null).
+ *   mg_points_destroy  frees a set.  Every entry looks its set up in the handle's list before it reads anything of it: a set
+ *       that is unknown, destroyed already or another handle's is refused by name, never dereferenced.
+ *   mg_points_info     the level and its N at creation, M, the number of runs, the slots in the longest run and the set's
+ *       device bytes; any output pointer may be null.
+ *   mg_points_sample / _load / _gradient / _gradient_t   for every lane b < nb: out_b = S(x_b) (M doubles), S^T(w_b) (the
+ *       level's nodes), G(x_b) (M x 3), G^T(p_b) (nodes).  Pointer arrays are HOST arrays of nb DEVICE pointers, as in
+ *       mg_apply_batch.  For every b, out_b has bit for bit the bytes mg_diffusion_point_sample / _load / _gradient /
+ *       _gradient_t write for the same points and operand -- for any nb, any mix of lanes, on every call.  In a transpose an
+ *       untouched node is +0.0 and a node takes its contributions in ascending point index onto +0.0: one thread walks a run
+ *       front to back for all lanes of a launch group (four lanes per launch, ascending).  No floating-point atomic, no fused
+ *       product.  Two lanes may share an input pointer.  They run on the handle's stream, which is synchronised before return.
+ *       Refused before anything is launched: nb outside 1..MG_BATCH_MAX, null arrays or pointers, a pointer that is not device
+ *       memory of the handle's device, an output that overlaps another lane's output or any lane's input, and a level that is
+ *       no longer set or has been set again with another N (the message says which N the set was located on). */
+typedef struct mg_points* mg_points_handle;
+int mg_points_create(mg_handle h, int level, int64_t M, const double* pts_dev, mg_points_handle* ps);
+int mg_points_destroy(mg_handle h, mg_points_handle ps);
+int mg_points_info(mg_handle h, mg_points_handle ps, int* level, int* N, int64_t* M, int64_t* runs, int64_t* longest_run, int64_t* bytes);
+int mg_points_sample(mg_handle h, mg_points_handle ps, int nb, const double* const* x_dev, double* const* out_dev);
+int mg_points_load(mg_handle h, mg_points_handle ps, int nb, const double* const* w_dev, double* const* out_dev);
+int mg_points_gradient(mg_handle h, mg_points_handle ps, int nb, const double* const* x_dev, double* const* out_dev);
+int mg_points_gradient_t(mg_handle h, mg_points_handle ps, int nb, const double* const* p_dev, double* const* out_dev);
 /* getJacobiMatrices (multigrid.py:48-56) as a stand-alone set-up kernel, for callers that
  * want the reference's split operands back: for every stored entry a_ij of the CSR matrix
  * writes scaled[q] = a_ij / a_ii computed as (1/a_ii) * a_ij, keep[q] = 1 unless the entry

@@ -105,6 +105,13 @@ SIGNATURES = {
     "mg_diffusion_point_load": [_H, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p],
     "mg_diffusion_point_gradient": [_H, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p],
     "mg_diffusion_point_gradient_t": [_H, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p],
+    "mg_points_create": [_H, C.c_int, C.c_int64, C.c_void_p, C.POINTER(C.c_void_p)],
+    "mg_points_destroy": [_H, C.c_void_p],
+    "mg_points_info": [_H, C.c_void_p, _ip, _ip, _i64p, _i64p, _i64p, _i64p],
+    "mg_points_sample": [_H, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p],
+    "mg_points_load": [_H, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p],
+    "mg_points_gradient": [_H, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p],
+    "mg_points_gradient_t": [_H, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p],
     "mg_diffusion_drobin": [_H, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
     "mg_diffusion_apply_drobin": [_H, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
     "mg_zero_vector": [_H, C.c_int, C.c_int],

@@ -261,6 +261,19 @@ struct CycleGraph {
     hipGraphExec_t exec = nullptr;
 };
 
+// A located point set (mg_points_create; mg_diffusion_points.hip.h, "Located point sets"): device memory of its own, counted in
+// the handle's ledger, owned by the handle's list `point_sets` -- an entry looks a set up there before it reads a member.
+struct mg_points {
+    int level = -1, N = 0;                  // the level it was located on and that level's cells per axis then
+    int64_t M = 0, R = 0, longest = 0;      // points, runs of equal node among the 4 M sorted slots, slots in the longest run
+    DevBuf<double> pts;                     // 3 M: the set's copy
+    DevBuf<PtSlot> rec;                     // 4 M: the slots in the stable order by node
+    DevBuf<int64_t> run_start, run_node;    // R + 1, R
+    int64_t bytes() const {
+        return (int64_t)(pts.count() * sizeof(double) + rec.count() * sizeof(PtSlot) + (run_start.count() + run_node.count()) * sizeof(int64_t));
+    }
+};
+
 struct mg_context {
     int dim = 2, nlev = 0, device = 0;
     hipStream_t stream = nullptr;
@@ -426,6 +439,8 @@ struct mg_context {
     std::vector<std::array<SmootherCount, MG_PATH_COUNT>> smoother_counts;
     int jk3_tail = 0;               // the last launch of the K-sweep march split off a last round of tiles (a.ta < ntile)
     DevBuf<double> stage;           // device staging for host vectors (caller numbering)
+    std::vector<std::unique_ptr<mg_points>> point_sets;     // mg_points_create .. mg_points_destroy; what is left goes with the handle
+    int pt_group = PT_SET_NV;       // lanes per launch of the mg_points_* entries (MG_POINT_GROUP=1..8: measurements only; same bits)
     int64_t bytes = 0;
     Comm comm;
     hipDeviceProp_t prop{};
@@ -4365,6 +4380,7 @@ int mg_create(int n_levels, int dim, int device, mg_handle* out) {
     std::unique_ptr<mg_context, ContextDeleter> owner(new mg_context());       // (a failure below leaves nothing behind)
     mg_context* const c = owner.get();
     if (const char* e = std::getenv("MG_COMM_PRIORITY")) c->comm_priority = std::atoi(e) != 0;      // experiments only
+    if (const char* e = std::getenv("MG_POINT_GROUP")) c->pt_group = std::min(8, std::max(1, std::atoi(e)));    // measurements only
     c->dim = dim;
     c->nlev = n_levels;
     c->device = device;
@@ -6150,6 +6166,185 @@ int mg_diffusion_point_gradient(mg_handle c, int level, int64_t M, const double*
 
 int mg_diffusion_point_gradient_t(mg_handle c, int level, int64_t M, const double* pts_dev, const double* p_dev, double* out_dev) {
     return point_scatter(c, true, "mg_diffusion_point_gradient_t", level, M, pts_dev, p_dev, out_dev);
+}
+
+// ---- located point sets: checked, located and sorted once, then any number of lanes per call ------------------------------------
+static PtArgs pt_set_locate_args(const mg_points& ps, const Level& L, uint64_t* keys) {
+    return pt_args(L, ps.M, ps.pts, nullptr, nullptr, keys);
+}
+
+int mg_points_create(mg_handle c, int level, int64_t M, const double* pts_dev, mg_points_handle* out) {
+    const char* who = "mg_points_create";
+    if (out) *out = nullptr;
+    MG_TRY(need_point_level(c, level, who));
+    MG_TRY(need_point_count(who, M));
+    if (!out) return fail(std::string(who) + ": null pointer (the set)");
+    HIP_TRY(hipSetDevice(c->device));
+    MG_TRY(need_device_pointer(c, pts_dev, who, "pts"));
+    MG_TRY(need_points(c, who, M, pts_dev));
+    const Level& L = c->L[level];
+    std::unique_ptr<mg_points> owner(new mg_points());          // (a failure below leaves nothing behind)
+    mg_points& ps = *owner;
+    ps.level = level; ps.N = L.N; ps.M = M;
+    const size_t n = 4 * (size_t)M;
+    MG_TRY(ps.pts.alloc(c, 3 * (size_t)M));
+    HIP_TRY(hipMemcpyAsync(ps.pts, pts_dev, (size_t)M * 24, hipMemcpyDeviceToDevice, c->stream));
+    const uint64_t nodes = (uint64_t)L.g.plane * (uint64_t)L.g.nz;
+    unsigned bits = 1;                                      // the bits of the largest node id, as point_scatter
+    while (bits < 64 && ((nodes - 1) >> bits) != 0) ++bits;
+    DevTemp keys_t, keys_s, slots_t, slots_s, sort_t, head_t, starts_t, count_t, select_t;
+    MG_TRY(keys_t.alloc(n * 8));
+    MG_TRY(keys_s.alloc(n * 8));
+    MG_TRY(slots_t.alloc(n * 8));
+    MG_TRY(slots_s.alloc(n * 8));
+    MG_TRY(head_t.alloc(n));
+    MG_TRY(starts_t.alloc((n + 1) * 8));
+    MG_TRY(count_t.alloc(2 * sizeof(unsigned long long)));      // the number of runs; the longest run
+    size_t sort_bytes = 0, select_bytes = 0;
+    HIP_TRY(rocprim::radix_sort_pairs(nullptr, sort_bytes, keys_t.as<uint64_t>(), keys_s.as<uint64_t>(), slots_t.as<uint64_t>(),
+                                      slots_s.as<uint64_t>(), n, 0u, bits, c->stream));
+    HIP_TRY(rocprim::select(nullptr, select_bytes, rocprim::counting_iterator<int64_t>(0), head_t.as<unsigned char>(), starts_t.as<int64_t>(),
+                            count_t.as<unsigned long long>(), n, c->stream));
+    MG_TRY(sort_t.alloc(sort_bytes));
+    MG_TRY(select_t.alloc(select_bytes));
+    MG_TRY(ps.rec.alloc(c, n));
+    hipLaunchKernelGGL(pt_set_pairs, dim3(blocks_for(M, PT_BLOCK)), dim3(PT_BLOCK), 0, c->stream, pt_set_locate_args(ps, L, keys_t.as<uint64_t>()),
+                       slots_t.as<uint64_t>());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(rocprim::radix_sort_pairs(sort_t.p, sort_bytes, keys_t.as<uint64_t>(), keys_s.as<uint64_t>(), slots_t.as<uint64_t>(),
+                                      slots_s.as<uint64_t>(), n, 0u, bits, c->stream));
+    hipLaunchKernelGGL(pt_set_records, dim3(blocks_for((int64_t)n, PT_BLOCK)), dim3(PT_BLOCK), 0, c->stream, pt_set_locate_args(ps, L, nullptr),
+                       keys_s.as<const uint64_t>(), slots_s.as<const uint64_t>(), (int64_t)n, ps.rec.get(), head_t.as<unsigned char>());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemsetAsync(count_t.p, 0, 2 * sizeof(unsigned long long), c->stream));
+    HIP_TRY(rocprim::select(select_t.p, select_bytes, rocprim::counting_iterator<int64_t>(0), head_t.as<unsigned char>(), starts_t.as<int64_t>(),
+                            count_t.as<unsigned long long>(), n, c->stream));
+    unsigned long long counts[2] = {0, 0};
+    HIP_TRY(hipMemcpyAsync(counts, count_t.p, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    const int64_t R = (int64_t)counts[0];
+    if (R < 1 || (size_t)R > n) return fail(std::string(who) + ": the run count is inconsistent");
+    ps.R = R;
+    MG_TRY(ps.run_start.alloc(c, (size_t)R + 1));
+    MG_TRY(ps.run_node.alloc(c, (size_t)R));
+    HIP_TRY(hipMemcpyAsync(ps.run_start, starts_t.p, (size_t)R * 8, hipMemcpyDeviceToDevice, c->stream));
+    hipLaunchKernelGGL(pt_set_runs, dim3(blocks_for(R, PT_BLOCK)), dim3(PT_BLOCK), 0, c->stream, keys_s.as<const uint64_t>(), (int64_t)n, R,
+                       ps.run_start.get(), ps.run_node.get(), count_t.as<unsigned long long>() + 1);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(counts + 1, count_t.as<unsigned long long>() + 1, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));              // the temporaries are freed on return
+    ps.longest = (int64_t)counts[1];
+    c->point_sets.push_back(std::move(owner));
+    *out = c->point_sets.back().get();
+    return 0;
+}
+
+// the handle's own set behind `ps`, or null: nothing of `ps` is read before it is found in the list
+static mg_points* own_point_set(mg_context* c, const mg_points* ps) {
+    for (const auto& s : c->point_sets)
+        if (s.get() == ps) return s.get();
+    return nullptr;
+}
+
+static int need_point_set(mg_context* c, const mg_points* ps, const char* who) {
+    const std::string w(who);
+    if (!c) return fail(w + ": null handle");
+    if (!ps) return fail(w + ": null point set");
+    if (!own_point_set(c, ps))
+        return fail(w + ": this is no live point set of this handle (destroyed already, or made by another handle)");
+    return 0;
+}
+
+int mg_points_destroy(mg_handle c, mg_points_handle ps) {
+    MG_TRY(need_point_set(c, ps, "mg_points_destroy"));
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (auto it = c->point_sets.begin(); it != c->point_sets.end(); ++it)
+        if (it->get() == ps) { c->point_sets.erase(it); break; }
+    return 0;
+}
+
+int mg_points_info(mg_handle c, mg_points_handle ps, int* level, int* N, int64_t* M, int64_t* runs, int64_t* longest_run, int64_t* bytes) {
+    MG_TRY(need_point_set(c, ps, "mg_points_info"));
+    if (level) *level = ps->level;
+    if (N) *N = ps->N;
+    if (M) *M = ps->M;
+    if (runs) *runs = ps->R;
+    if (longest_run) *longest_run = ps->longest;
+    if (bytes) *bytes = ps->bytes();
+    return 0;
+}
+
+// What the four batched entries refuse before anything is launched, and then their launches: the lanes in ascending groups of
+// c->pt_group, the last group with what is left.  GATHER: S / G (in: nodes; out: M or 3 M); otherwise S^T / G^T (in: M or 3 M; out:
+// nodes, zeroed on the stream first).
+static int point_set_apply(mg_context* c, mg_points* ps, const bool GATHER, const bool GRAD, const char* who, const char* in_name, int nb,
+                           const double* const* in, double* const* out) {
+    const std::string w(who);
+    MG_TRY(need_point_set(c, ps, who));
+    const Level& L = c->L[ps->level];
+    if (!L.set || L.flat || L.N != ps->N)
+        return fail(w + ": level " + std::to_string(ps->level) + (L.set && !L.flat ? " has been set again with N = " + std::to_string(L.N)
+                                                                                  : std::string(" is no longer a set grid level")) +
+                    "; this set was located on N = " + std::to_string(ps->N) + " (make a new one)");
+    if (nb < 1 || nb > MG_BATCH_MAX)
+        return fail(w + ": nb = " + std::to_string(nb) + " is outside 1.." + std::to_string(MG_BATCH_MAX) + " (MG_BATCH_MAX)");
+    if (!in || !out) return fail(w + ": null pointer array");
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t per_point = (size_t)ps->M * (GRAD ? 24 : 8);
+    const size_t in_bytes = GATHER ? node_bytes(L) : per_point, out_bytes = GATHER ? per_point : node_bytes(L);
+    for (int b = 0; b < nb; ++b) {
+        const std::string lane = "[" + std::to_string(b) + "]";
+        MG_TRY(need_device_pointer(c, in[b], who, (in_name + lane).c_str()));
+        MG_TRY(need_device_pointer(c, out[b], who, ("out" + lane).c_str()));
+    }
+    for (int b = 0; b < nb; ++b) {
+        for (int q = 0; q < nb; ++q) {
+            if (overlaps(out[b], out_bytes, in[q], in_bytes))
+                return fail(w + ": out[" + std::to_string(b) + "] overlaps " + in_name + "[" + std::to_string(q) +
+                            "]: every lane's output is memory of its own");
+            if (q > b && overlaps(out[b], out_bytes, out[q], out_bytes))
+                return fail(w + ": out[" + std::to_string(b) + "] overlaps out[" + std::to_string(q) + "]: every lane's output is memory of its own");
+        }
+    }
+    if (!GATHER)
+        for (int b = 0; b < nb; ++b) HIP_TRY(hipMemsetAsync(out[b], 0, out_bytes, c->stream));
+    const int64_t threads = GATHER ? ps->M : ps->R;
+    const dim3 grid(blocks_for(threads, PT_BLOCK)), blk(PT_BLOCK);
+    for (int b0 = 0; b0 < nb; b0 += c->pt_group) {
+        const int nv = std::min(c->pt_group, nb - b0);
+        const bool known = with_int<1, 2, 3, 4, 5, 6, 7, 8>(nv, [&](auto n) {
+            constexpr int NV = decltype(n)::value;
+            PtSetArgs<NV> a{};
+            a.pts = ps->pts; a.rec = ps->rec; a.run_start = ps->run_start; a.run_node = ps->run_node;
+            a.M = ps->M; a.R = ps->R; a.nx = L.g.nx; a.plane = L.g.plane; a.N = L.N;
+            for (int v = 0; v < NV; ++v) { a.in[v] = in[b0 + v]; a.out[v] = out[b0 + v]; }
+            with_bool(GRAD, [&](auto g) {
+                if (GATHER) hipLaunchKernelGGL((pt_set_gather<decltype(g)::value, NV>), grid, blk, 0, c->stream, a);
+                else hipLaunchKernelGGL((pt_set_scatter<decltype(g)::value, NV>), grid, blk, 0, c->stream, a);
+            });
+        });
+        if (!known) return fail(w + ": no kernel for a launch group of " + std::to_string(nv) + " lanes");
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int mg_points_sample(mg_handle c, mg_points_handle ps, int nb, const double* const* x_dev, double* const* out_dev) {
+    return point_set_apply(c, ps, true, false, "mg_points_sample", "x", nb, x_dev, out_dev);
+}
+
+int mg_points_load(mg_handle c, mg_points_handle ps, int nb, const double* const* w_dev, double* const* out_dev) {
+    return point_set_apply(c, ps, false, false, "mg_points_load", "w", nb, w_dev, out_dev);
+}
+
+int mg_points_gradient(mg_handle c, mg_points_handle ps, int nb, const double* const* x_dev, double* const* out_dev) {
+    return point_set_apply(c, ps, true, true, "mg_points_gradient", "x", nb, x_dev, out_dev);
+}
+
+int mg_points_gradient_t(mg_handle c, mg_points_handle ps, int nb, const double* const* p_dev, double* const* out_dev) {
+    return point_set_apply(c, ps, false, true, "mg_points_gradient_t", "p", nb, p_dev, out_dev);
 }
 
 int mg_zero_vector(mg_handle c, int level, int which) {

@@ -27,6 +27,8 @@
 // share a node.
 #pragma once
 #include <rocprim/device/device_radix_sort.hpp>
+#include <rocprim/device/device_select.hpp>
+#include <rocprim/iterator/counting_iterator.hpp>
 
 namespace mgk {
 
@@ -149,6 +151,139 @@ __global__ __launch_bounds__(PT_BLOCK) void pt_run_sum(const uint64_t* __restric
     double acc = 0.0;
     for (int64_t j = i; j < n && keys[j] == key; ++j) acc = acc + vals[j];
     out[key] = acc;
+}
+
+}  // namespace mgk
+
+// ---- Located point sets (mg_points_*) ----------------------------------------------------------------------------------------
+// A set keeps what depends on the point positions alone, so that a call with nb lanes launches only the kernels that touch the
+// operands: the set's own copy of the points (the gathers locate from it with pt_locate, once per point and launch group), and,
+// for the transposes, the 4 M slots 4 m + v in the stable order by node -- per sorted slot one PtSlot record -- with the runs of
+// equal node: run_start[R + 1] (sorted positions) and run_node[R].  One thread per run walks its records front to back, which
+// is ascending point index, reads each record once per launch group of up to PT_SET_NV lanes, adds onto +0.0 per lane and
+// stores once per lane and node: the adds and their order are those of pt_contrib + pt_run_sum, so the bits are too.
+namespace mgk {
+
+constexpr int PT_SET_NV = 4;        // lanes per launch group ("Located point sets": the measured choice)
+
+// One sorted slot.  S^T: contribution lam * w[m].  G^T: vertex v of the path takes (A - B) * Nd with A = p[3 m + a] (v = 0: 0.0)
+// and B = p[3 m + b]; v = 3 takes p[3 m + a] * Nd.  code = v | a << 2 | b << 4, a = pi[v - 1], b = pi[v].
+struct PtSlot {
+    double lam;
+    uint32_t m;
+    uint32_t code;
+};
+
+// the pairs of the sort: key = node, value = slot 4 m + v
+__global__ __launch_bounds__(PT_BLOCK) void pt_set_pairs(PtArgs a, uint64_t* __restrict__ slots) {
+    const int64_t m = (int64_t)blockIdx.x * PT_BLOCK + threadIdx.x;
+    if (m >= a.M) return;
+    const PtLoc q = pt_locate(a.pts, m, a.N, a.nx, a.plane);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        a.keys[4 * m + k] = (uint64_t)q.n[k];
+        slots[4 * m + k] = (uint64_t)(4 * m + k);
+    }
+}
+
+// per sorted position: the record of its slot, and whether it heads a run of equal nodes
+__global__ __launch_bounds__(PT_BLOCK) void pt_set_records(PtArgs a, const uint64_t* __restrict__ keys_s, const uint64_t* __restrict__ slots_s,
+                                                           int64_t n, PtSlot* __restrict__ rec, unsigned char* __restrict__ head) {
+    const int64_t i = (int64_t)blockIdx.x * PT_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const uint64_t s = slots_s[i];
+    const int64_t m = (int64_t)(s >> 2);
+    const int v = (int)(s & 3);
+    const PtLoc q = pt_locate(a.pts, m, a.N, a.nx, a.plane);
+    const int pa = v == 0 ? 0 : v == 1 ? q.pi[0] : v == 2 ? q.pi[1] : q.pi[2];
+    const int pb = v == 0 ? q.pi[0] : v == 1 ? q.pi[1] : v == 2 ? q.pi[2] : 0;
+    PtSlot r;
+    r.lam = v == 0 ? q.lam[0] : v == 1 ? q.lam[1] : v == 2 ? q.lam[2] : q.lam[3];
+    r.m = (uint32_t)m;
+    r.code = (uint32_t)v | (uint32_t)pa << 2 | (uint32_t)pb << 4;
+    rec[i] = r;
+    head[i] = (i == 0 || keys_s[i - 1] != keys_s[i]) ? 1 : 0;
+}
+
+// run_start[R] = n, run_node[r] = the node of run r, and the longest run (an integer max)
+__global__ __launch_bounds__(PT_BLOCK) void pt_set_runs(const uint64_t* __restrict__ keys_s, int64_t n, int64_t R, int64_t* __restrict__ run_start,
+                                                        int64_t* __restrict__ run_node, unsigned long long* longest) {
+    const int64_t r = (int64_t)blockIdx.x * PT_BLOCK + threadIdx.x;
+    if (r >= R) return;
+    const int64_t s0 = run_start[r];
+    const int64_t s1 = r + 1 < R ? run_start[r + 1] : n;    // (run_start[R] is written by the thread of the last run)
+    if (r + 1 == R) run_start[R] = n;
+    run_node[r] = (int64_t)keys_s[s0];
+    atomicMax(longest, (unsigned long long)(s1 - s0));
+}
+
+template <int NV>
+struct PtSetArgs {
+    const double* pts;              // the set's copy, M x 3
+    const PtSlot* rec;              // 4 M, sorted
+    const int64_t* run_start;       // R + 1
+    const int64_t* run_node;        // R
+    const double* in[NV];
+    double* out[NV];
+    int64_t M, R;
+    int64_t nx, plane;
+    int N;
+};
+
+// S (GRAD false) or G (GRAD true) of NV fields: one thread per point, located once
+template <bool GRAD, int NV>
+__global__ __launch_bounds__(PT_BLOCK) void pt_set_gather(PtSetArgs<NV> a) {
+    const int64_t m = (int64_t)blockIdx.x * PT_BLOCK + threadIdx.x;
+    if (m >= a.M) return;
+    const PtLoc q = pt_locate(a.pts, m, a.N, a.nx, a.plane);
+    const double Nd = (double)a.N;
+#pragma unroll
+    for (int b = 0; b < NV; ++b) {
+        const double* __restrict__ x = a.in[b];
+        const double u0 = x[q.n[0]], u1 = x[q.n[1]], u2 = x[q.n[2]], u3 = x[q.n[3]];
+        if constexpr (GRAD) {
+            a.out[b][3 * m + q.pi[0]] = (u1 - u0) * Nd;
+            a.out[b][3 * m + q.pi[1]] = (u2 - u1) * Nd;
+            a.out[b][3 * m + q.pi[2]] = (u3 - u2) * Nd;
+        } else {
+            a.out[b][m] = ((q.lam[0] * u0 + q.lam[1] * u1) + q.lam[2] * u2) + q.lam[3] * u3;
+        }
+    }
+}
+
+// S^T (GRAD false, in = w) or G^T (GRAD true, in = p) of NV operands onto zeroed outputs: one thread per run of equal node
+template <bool GRAD, int NV>
+__global__ __launch_bounds__(PT_BLOCK) void pt_set_scatter(PtSetArgs<NV> a) {
+    const int64_t r = (int64_t)blockIdx.x * PT_BLOCK + threadIdx.x;
+    if (r >= a.R) return;
+    const int64_t s0 = a.run_start[r], s1 = a.run_start[r + 1];
+    const double Nd = (double)a.N;
+    double acc[NV];
+#pragma unroll
+    for (int b = 0; b < NV; ++b) acc[b] = 0.0;
+    for (int64_t j = s0; j < s1; ++j) {
+        const PtSlot s = a.rec[j];
+        const int64_t m = (int64_t)s.m;
+        if constexpr (GRAD) {
+            const int v = (int)(s.code & 3u);
+            const int64_t ia = 3 * m + (int64_t)((s.code >> 2) & 3u), ib = 3 * m + (int64_t)((s.code >> 4) & 3u);
+#pragma unroll
+            for (int b = 0; b < NV; ++b) {
+                const double A = v == 0 ? 0.0 : a.in[b][ia];
+                const double c = v == 3 ? A * Nd : (A - a.in[b][ib]) * Nd;
+                acc[b] = acc[b] + c;
+            }
+        } else {
+#pragma unroll
+            for (int b = 0; b < NV; ++b) {
+                const double c = s.lam * a.in[b][m];
+                acc[b] = acc[b] + c;
+            }
+        }
+    }
+    const int64_t node = a.run_node[r];
+#pragma unroll
+    for (int b = 0; b < NV; ++b) a.out[b][node] = acc[b];
 }
 
 }  // namespace mgk

@@ -20,7 +20,7 @@ from ._capi import (MG_RESTRICT_FULL_WEIGHTING, MG_RESTRICT_INJECTION, MG_VEC_ER
 from . import poisson
 from .poisson import face_set, grid_index_from_coords
 
-__all__ = ["DeviceHierarchy", "jacobi_split", "csr_check"]
+__all__ = ["DeviceHierarchy", "PointSet", "jacobi_split", "csr_check"]
 
 # lower_ratio of the Chebyshev interval by default (include/mg_hip.h, mg_set_chebyshev)
 CHEB_LOWER_RATIO = 6.0
@@ -861,6 +861,13 @@ class DeviceHierarchy:
         entry = self._point_entry(self._lib.mg_diffusion_point_gradient_t, level, M)
         return self._sensitivity(entry, [("pts", pts, 3 * M, False), ("p", p, 3 * M, False)], self.n_dofs(level), out)
 
+    def points(self, level: int, pts) -> "PointSet":
+        """A located point set on `level` (`mg_points_create`): `pts` is an (M, 3) NumPy array of rows (x, y, z) in the unit
+        cube, or a pair (integer device address, M).  The points are copied, checked, located and sorted once; the returned
+        `PointSet` then serves S, S^T, G and G^T for any number of fields per call.  Close it (or use it as a context manager);
+        the handle frees what is left."""
+        return PointSet(self, level, pts)
+
     def zero_vector(self, level: int, which: str = "v"):
         check(self._lib.mg_zero_vector(self._h, self._idx(level), _VEC[which]))
 
@@ -1061,3 +1068,106 @@ class DeviceHierarchy:
 
     def sync(self):
         check(self._lib.mg_sync(self._h))
+
+
+class PointSet:
+    """A located point set of one `DeviceHierarchy` (`mg_points_create`; make it with `DeviceHierarchy.points`).  The four
+    `*_many` methods take one operand per lane -- a sequence of integer device addresses together with `outs`, a sequence of
+    as many device addresses, and return None; or, for tests, a sequence of NumPy arrays (a (B, ...) array will do), which
+    are uploaded, an array that appears twice (`a is b`) once, and return a (B, ...) NumPy array.  Every lane has the bits of
+    the matching `diffusion_point_*` call.  At most `MG_BATCH_MAX` lanes per call."""
+
+    def __init__(self, hierarchy: DeviceHierarchy, level: int, pts):
+        self._hier, self._lib, self.level = hierarchy, hierarchy._lib, level
+        self._ps = C.c_void_p()
+        idx = hierarchy._idx(level)
+        if isinstance(pts, tuple) and len(pts) == 2 and isinstance(pts[0], (int, np.integer)):
+            check(self._lib.mg_points_create(hierarchy._h, idx, C.c_int64(int(pts[1])), C.c_void_p(int(pts[0])), C.byref(self._ps)))
+        else:
+            P = np.ascontiguousarray(np.asarray(pts, dtype=np.float64))
+            if P.ndim != 2 or P.shape[1] != 3:
+                raise ValueError(f"points are an (M, 3) array (got shape {P.shape})")
+            d = _DeviceArray(self._lib, hierarchy.device, P.size, P.reshape(-1))
+            try:
+                check(self._lib.mg_points_create(hierarchy._h, idx, C.c_int64(P.shape[0]), d.ptr, C.byref(self._ps)))
+            finally:
+                d.free()        # the set has its own copy
+        self.M = self.info["M"]
+
+    # ---- life cycle ---------------------------------------------------------------------
+    def close(self):
+        """`mg_points_destroy`; a second close, or one after the hierarchy was closed (which freed the set), does nothing."""
+        if getattr(self, "_ps", None) is not None and self._ps and self._hier._h:
+            ps, self._ps = self._ps, C.c_void_p()
+            check(self._lib.mg_points_destroy(self._hier._h, ps))
+        self._ps = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    @property
+    def handle(self) -> C.c_void_p:
+        if not self._ps:
+            raise _capi.MgError("this point set has been closed")
+        return self._ps
+
+    @property
+    def info(self) -> dict:
+        """`mg_points_info`: the level index inside the handle and its N at creation, M, the runs of equal node among the 4 M
+        sorted slots, the slots in the longest run and the set's device bytes."""
+        level, N = C.c_int(), C.c_int()
+        M, runs, longest, b = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
+        check(self._lib.mg_points_info(self._hier._h, self.handle, C.byref(level), C.byref(N), C.byref(M), C.byref(runs),
+                                       C.byref(longest), C.byref(b)))
+        return {"level": int(level.value), "N": int(N.value), "M": int(M.value), "runs": int(runs.value),
+                "longest_run": int(longest.value), "bytes": int(b.value)}
+
+    # ---- the four operators ---------------------------------------------------------------
+    def _many(self, fn, ins, outs, n_in: int, n_out: int):
+        is_address = lambda v: isinstance(v, (int, np.integer))
+        ins = list(ins)
+        nb = len(ins)
+        if nb and all(is_address(v) for v in ins):
+            if outs is None or len(outs) != nb or not all(is_address(v) for v in outs):
+                raise TypeError(f"with device addresses for the {nb} lanes, outs must be {nb} device addresses too")
+            check(fn(self._hier._h, self.handle, nb, DeviceHierarchy._ptr_array(ins), DeviceHierarchy._ptr_array(outs)))
+            return None
+        if outs is not None or any(is_address(v) for v in ins):
+            raise TypeError("the lanes and outs must be all device addresses, or NumPy arrays without outs")
+        held, results = {}, []
+        try:
+            for v in ins:
+                if id(v) not in held:
+                    held[id(v)] = _DeviceArray(self._lib, self._hier.device, n_in, _capi.as_f64(v, n_in))
+            results = [_DeviceArray(self._lib, self._hier.device, n_out) for _ in ins]
+            check(fn(self._hier._h, self.handle, nb, DeviceHierarchy._ptr_array([held[id(v)].ptr.value for v in ins]),
+                     DeviceHierarchy._ptr_array([r.ptr.value for r in results])))
+            return np.stack([r.download() for r in results]) if results else np.zeros((0, n_out))
+        finally:
+            for d in list(held.values()) + results:
+                d.free()
+
+    def sample_many(self, xs, outs=None):
+        """out_b = S(x_b), M values per lane (`mg_points_sample`)."""
+        return self._many(self._lib.mg_points_sample, xs, outs, self._hier.n_dofs(self.level), self.M)
+
+    def load_many(self, ws, outs=None):
+        """out_b = S^T(w_b), the level's nodes per lane (`mg_points_load`)."""
+        return self._many(self._lib.mg_points_load, ws, outs, self.M, self._hier.n_dofs(self.level))
+
+    def gradient_many(self, xs, outs=None):
+        """out_b = G(x_b), 3 M values per lane, row m = (d/dx, d/dy, d/dz) at point m (`mg_points_gradient`)."""
+        return self._many(self._lib.mg_points_gradient, xs, outs, self._hier.n_dofs(self.level), 3 * self.M)
+
+    def gradient_t_many(self, ps, outs=None):
+        """out_b = G^T(p_b), the level's nodes per lane (`mg_points_gradient_t`)."""
+        return self._many(self._lib.mg_points_gradient_t, ps, outs, 3 * self.M, self._hier.n_dofs(self.level))

@@ -1231,6 +1231,23 @@ def diffusion_point_gradient_t(N: int, pts, p) -> np.ndarray:
     return _point_scatter(N, n, contrib)
 
 
+def diffusion_point_runs(N: int, pts):
+    """What a located point set (`mg_points_create`) keeps for the transposes: the 4 M slots 4 m + v (vertex v of point m, node
+    `diffusion_point_locate(N, pts)[0][m, v]`) in the STABLE order by node, and the runs of equal node in that order.  Returns
+    (slot_order, run_start, run_node): slot_order (4 M,) int64, a permutation along which the nodes do not decrease and, inside
+    a run, the slots -- so the point indices -- ascend; run_start (R + 1,) int64, run r being slot_order[run_start[r] :
+    run_start[r + 1]], run_start[R] = 4 M; run_node (R,) int64, strictly ascending.  Adding a run's contributions front to back
+    onto +0.0 is the sequential sum of `diffusion_point_load` and `diffusion_point_gradient_t`.  R and the longest run are what
+    `mg_points_info` reports."""
+    nodes, _, _ = diffusion_point_locate(N, pts)
+    flat = nodes.reshape(-1)
+    slot_order = np.argsort(flat, kind="stable").astype(np.int64)
+    along = flat[slot_order]
+    heads = np.flatnonzero(np.concatenate(([True], along[1:] != along[:-1])))
+    run_start = np.concatenate((heads, [flat.size])).astype(np.int64)
+    return slot_order, run_start, along[heads].astype(np.int64)
+
+
 def diffusion_apply_dkappa(N: int, dkappa, x, rows: str = "interior", cols: str = "interior", dirichlet_faces=ALL_FACES) -> np.ndarray:
     """(dA/dkappa . dkappa) x for the 3-D `diffusion_level`: the derivative of A(kappa) x in the direction `dkappa` (N^3 values in
     the cell order of `diffusion_level`, of any sign), as `mg_diffusion_apply_dkappa` computes it.  A is linear in kappa, so an

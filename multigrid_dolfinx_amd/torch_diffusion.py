@@ -20,7 +20,7 @@ import torch
 from .hierarchy import DeviceHierarchy
 from .poisson import ALL_FACES, _one_face, dirichlet_mask, face_set
 
-__all__ = ["DiffusionSolver", "NotConverged"]
+__all__ = ["DiffusionSolver", "LocatedPoints", "NotConverged"]
 
 
 class NotConverged(RuntimeError):
@@ -304,8 +304,12 @@ class DiffusionSolver:
         Differentiable to second order in `u` and in `points`.  The position derivative is the derivative inside the
         located simplex, grad u_h there (`sample_gradient`): u_h is piecewise linear and kinks on simplex faces, so at a point
         on a face it is the one-sided derivative of the simplex that `poisson.diffusion_point_locate` picks.  Works before
-        the first solve and leaves the hierarchy alone: `n_generations` and `n_solves` do not move."""
+        the first solve and leaves the hierarchy alone: `n_generations` and `n_solves` do not move.  `points` may be the
+        `LocatedPoints` of `locate` instead, here and in `point_load` and `sample_gradient`: the same bits without the
+        per-call check, allocations and sort."""
         self._top_level_grid()
+        if isinstance(points, LocatedPoints):
+            return self.sample_many(self._same_size(u, "u").reshape(1, -1), points)[0]
         return _PointSample.apply(self._same_size(u, "u").reshape(-1), points, self)
 
     def point_load(self, points: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
@@ -318,6 +322,8 @@ class DiffusionSolver:
         given, `f` on Dirichlet nodes does not count.  Works before the first solve and leaves the hierarchy alone."""
         self._top_level_grid()
         n1 = self.N + 1
+        if isinstance(points, LocatedPoints):
+            return self.point_load_many(points, w.reshape(1, -1))[0]
         return _PointLoad.apply(w.reshape(-1), points, self).view(n1, n1, n1)
 
     def sample_gradient(self, u: torch.Tensor, points: torch.Tensor) -> torch.Tensor:
@@ -326,7 +332,46 @@ class DiffusionSolver:
         constant in `points`, which get no derivative: u_h is piecewise linear and its gradient jumps on simplex faces.
         Works before the first solve and leaves the hierarchy alone."""
         self._top_level_grid()
+        if isinstance(points, LocatedPoints):
+            return self.sample_gradient_many(self._same_size(u, "u").reshape(1, -1), points)[0]
         return _PointGrad.apply(self._same_size(u, "u").reshape(-1), points, self)
+
+    def locate(self, points: torch.Tensor) -> "LocatedPoints":
+        """The points ((M, 3) float64 rows (x, y, z) in [0, 1]^3 on the solver's device) checked, located and sorted once on the
+        top level (`mg_points_create`): a `LocatedPoints`, which `sample`, `point_load` and `sample_gradient` take in place of
+        the tensor -- same bits, without the per-call check, allocations and sort -- and which the `_many` forms need.  The
+        set is a snapshot: after an in-place change of `points` every use raises (locate again).  Works before the first
+        solve and moves neither `n_generations` nor `n_solves`."""
+        self._top_level_grid()
+        return LocatedPoints(self, points)
+
+    def _located(self, P: "LocatedPoints") -> "LocatedPoints":
+        if not isinstance(P, LocatedPoints) or P.solver is not self:
+            raise TypeError("the batched point functions take the LocatedPoints of this solver's locate()")
+        return P.fresh()
+
+    def sample_many(self, U: torch.Tensor, P: "LocatedPoints") -> torch.Tensor:
+        """`sample` of the B fields U[0] .. U[B - 1] ((B, ...) with (N + 1)^3 float64 each) at a located set, (B, M): one
+        sequence of launch groups forward and one backward for all lanes (`mg_points_sample`), every lane with the bits of
+        `sample(U[b], X)`.  Differentiable to second order in U and, where the tensor P was located from requires grad, in the
+        positions: that tensor receives sum_b y_b[:, None] * grad u_b,h at the points."""
+        P = self._located(P)
+        n = self.hierarchy.n_dofs(self.top)
+        return _SetSample.apply(U.reshape(U.shape[0], -1) if U.dim() >= 2 and U[0].numel() == n else U, P.source, P)
+
+    def point_load_many(self, P: "LocatedPoints", W: torch.Tensor) -> torch.Tensor:
+        """`point_load` of the B weight vectors W[0] .. W[B - 1] ((B, M)) at a located set, (B, N + 1, N + 1, N + 1)
+        (`mg_points_load`), every lane with the bits of `point_load(X, W[b])`.  Differentiable as `sample_many`."""
+        P = self._located(P)
+        n1 = self.N + 1
+        return _SetLoad.apply(W, P.source, P).view(-1, n1, n1, n1)
+
+    def sample_gradient_many(self, U: torch.Tensor, P: "LocatedPoints") -> torch.Tensor:
+        """`sample_gradient` of the B fields of U at a located set, (B, M, 3) (`mg_points_gradient`), every lane with the bits of
+        `sample_gradient(U[b], X)`.  Differentiable to second order in U; the positions get no derivative."""
+        P = self._located(P)
+        n = self.hierarchy.n_dofs(self.top)
+        return _SetGrad.apply(U.reshape(U.shape[0], -1) if U.dim() >= 2 and U[0].numel() == n else U, P.source, P)
 
     def tangent(self, kappa: torch.Tensor, f: torch.Tensor, dkappa: torch.Tensor, df: Optional[torch.Tensor] = None,
                 g: Optional[torch.Tensor] = None, dg: Optional[torch.Tensor] = None, sigma: Optional[torch.Tensor] = None,
@@ -805,3 +850,123 @@ class _PointGradT(torch.autograd.Function):
         p, X = ctx.saved_tensors
         grad_p = _PointGrad.apply(y, X, ctx.solver).view(p.shape) if ctx.needs_input_grad[0] else None
         return grad_p, None, None
+
+
+class LocatedPoints:
+    """A point set located once on the solver's top level (`DiffusionSolver.locate`; `mg_points_create`): what `sample`,
+    `point_load`, `sample_gradient` and their `_many` forms take in place of the (M, 3) tensor.  It remembers the tensor it was
+    made from: that tensor receives the position derivatives if it requires grad, and once it has been written in place
+    (its `_version` has moved: an optimiser stepped it) every use raises, because the located simplices are those of the old
+    positions -- call `locate` again.  Closing it (or the solver) frees the device memory of the set."""
+
+    def __init__(self, solver: "DiffusionSolver", points: torch.Tensor):
+        X = _points(solver, points)
+        self.solver, self.source, self.M = solver, points, X.shape[0]
+        self._version = points._version
+        torch.cuda.current_stream(solver.device).synchronize()      # the points are complete before the handle's stream copies them
+        self.set = solver.hierarchy.points(solver.top, (X.data_ptr(), self.M))
+
+    @property
+    def info(self) -> dict:
+        return self.set.info
+
+    def close(self):
+        self.set.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def fresh(self) -> "LocatedPoints":
+        """Itself, or a RuntimeError if the tensor it was located from has been written since."""
+        if self.source._version != self._version:
+            raise RuntimeError("the tensor these points were located from has been modified in place since (version "
+                               f"{self._version} -> {self.source._version}): the located simplices are stale; call locate again")
+        return self
+
+
+def _set_launch(P: LocatedPoints, method, V: torch.Tensor, n_in: int, n_out: int, what: str) -> torch.Tensor:
+    """`method` (one of the `PointSet.*_many`) on the rows of the (B, n_in) `V`, at most MG_BATCH_MAX lanes per call in
+    ascending chunks, into a fresh (B, n_out)."""
+    from ._capi import MG_BATCH_MAX
+    solver = P.fresh().solver
+    if V.dtype != torch.float64 or V.device != solver.device or V.dim() != 2 or V.shape[0] < 1 or V.shape[1] != n_in:
+        raise ValueError(f"{what} must hold B >= 1 rows of {n_in} float64 on {solver.device} (got {tuple(V.shape)} {V.dtype} on {V.device})")
+    Vc = V.detach().contiguous()
+    B = Vc.shape[0]
+    out = torch.empty((B, n_out), dtype=torch.float64, device=solver.device)
+    torch.cuda.current_stream(solver.device).synchronize()
+    for b0 in range(0, B, MG_BATCH_MAX):
+        lanes = range(b0, min(B, b0 + MG_BATCH_MAX))
+        method([Vc.data_ptr() + 8 * n_in * b for b in lanes], [out.data_ptr() + 8 * n_out * b for b in lanes])
+    return out
+
+
+def _position_grad(ctx, weights: torch.Tensor, fields: torch.Tensor) -> Optional[torch.Tensor]:
+    """The position derivative of S and S^T summed over the lanes: sum_b weights_b[:, None] * G(fields_b, X)."""
+    if not ctx.needs_input_grad[1]:
+        return None
+    return (weights[:, :, None] * _SetGrad.apply(fields, ctx.P.source, ctx.P)).sum(0)
+
+
+class _SetSample(torch.autograd.Function):
+    """S(U, P) = mg_points_sample, (B, M): `_PointSample` for B fields on a located set.  X is the tensor the set was located
+    from (it only receives the position derivative).  With cotangent Y: U_bar = S^T(Y, P), X_bar = sum_b Y_b[:, None] G(U_b, P)."""
+
+    @staticmethod
+    def forward(ctx, U, X, P):
+        ctx.P = P
+        ctx.save_for_backward(U)
+        return _set_launch(P, P.set.sample_many, U, P.solver.hierarchy.n_dofs(P.solver.top), P.M, "the fields")
+
+    @staticmethod
+    def backward(ctx, Y):
+        U, = ctx.saved_tensors
+        grad_U = _SetLoad.apply(Y, ctx.P.source, ctx.P) if ctx.needs_input_grad[0] else None
+        return grad_U, _position_grad(ctx, Y, U), None
+
+
+class _SetLoad(torch.autograd.Function):
+    """S^T(W, P) = mg_points_load, (B, nodes).  With cotangent Y: W_bar = S(Y, P), X_bar = sum_b W_b[:, None] G(Y_b, P)."""
+
+    @staticmethod
+    def forward(ctx, W, X, P):
+        ctx.P = P
+        ctx.save_for_backward(W)
+        return _set_launch(P, P.set.load_many, W, P.M, P.solver.hierarchy.n_dofs(P.solver.top), "the point weights")
+
+    @staticmethod
+    def backward(ctx, Y):
+        W, = ctx.saved_tensors
+        grad_W = _SetSample.apply(Y, ctx.P.source, ctx.P) if ctx.needs_input_grad[0] else None
+        return grad_W, _position_grad(ctx, W, Y), None
+
+
+class _SetGrad(torch.autograd.Function):
+    """G(U, P) = mg_points_gradient, (B, M, 3).  With cotangent Q: U_bar = G^T(Q, P); piecewise constant in the positions."""
+
+    @staticmethod
+    def forward(ctx, U, X, P):
+        ctx.P = P
+        return _set_launch(P, P.set.gradient_many, U, P.solver.hierarchy.n_dofs(P.solver.top), 3 * P.M, "the fields").view(-1, P.M, 3)
+
+    @staticmethod
+    def backward(ctx, Q):
+        grad_U = _SetGradT.apply(Q.reshape(Q.shape[0], -1), ctx.P.source, ctx.P) if ctx.needs_input_grad[0] else None
+        return grad_U, None, None
+
+
+class _SetGradT(torch.autograd.Function):
+    """G^T(Q, P) = mg_points_gradient_t, (B, nodes), Q (B, 3 M).  With cotangent Y: Q_bar = G(Y, P)."""
+
+    @staticmethod
+    def forward(ctx, Q, X, P):
+        ctx.P = P
+        return _set_launch(P, P.set.gradient_t_many, Q, 3 * P.M, P.solver.hierarchy.n_dofs(P.solver.top), "the point vectors")
+
+    @staticmethod
+    def backward(ctx, Y):
+        grad_Q = _SetGrad.apply(Y, ctx.P.source, ctx.P).reshape(Y.shape[0], -1) if ctx.needs_input_grad[0] else None
+        return grad_Q, None, None
