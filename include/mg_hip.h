@@ -687,7 +687,13 @@ int mg_galerkin_hierarchy(mg_handle h, int top_level);
  *                          sweeps and at most one pair (50 = 10 x 5); 0 .. 2 = pairs only (5); bit-identical to single sweeps
  *     "fuse_k_shape"       tile of that march: 0 = 128 x 24 cells (12 waves x 2 grid lines), 1 = 64 x 48 (12 waves x 4 lines),
  *                          2 = 128 x 24 (8 waves x 3 lines), 3 / 4 / 5 = 64 x 24 by 6 / 8 / 4 waves with two workgroups per CU
- *                          (levels of at most 64 row classes), 6 / 7 = 64 x 48 / 64 x 32 by 16 waves (7: no register spills up to five sweeps, measured best)
+ *                          (levels of at most 64 row classes), 6 / 7 = 64 x 48 / 64 x 32 by 16 waves (7: no register spills up to five sweeps),
+ *                          8 = 7 with one barrier per step, 9 = 8 on 64 x 36 tiles whose first and last wave own the four rim
+ *                          lines each (28 result lines per tile instead of 24; five sweeps per pass on whole levels without
+ *                          escape rows -- a handle that asks for 9 gets 8 on slabs and 7 below five sweeps); 0..9, or -1: for
+ *                          five sweeps per pass 9 on whole levels of at least "fuse_k_rim_min_rows" rows and 8 elsewhere, 7 for
+ *                          three and four (-1)
+ *     "fuse_k_rim_min_rows"  ... (67108864: 513^3 and 1025^3 rows, where shape 9 was measured against shape 8)
  *     "fuse_k_segments"    plane segments per tile of that march, 0 = chosen by its cost model (0)
  *     "fuse_k_slab_min_rows"  ... on slabs (below): levels whose smallest slab has at least this many rows (1048576)
  *     "fuse_k_slab_min_sweeps"  ... and smoother calls of at least this many sweeps (4)
@@ -713,7 +719,7 @@ int mg_galerkin_hierarchy(mg_handle h, int top_level);
  *     "fuse_k_plan"        march plans: the level's class bytes are inspected once per level, tile shape and K (which planes of
  *                          which wave hold the main class only, or the classes of the plane before), and the steps of that
  *                          march that run inside such a run load and inspect no classes (1); 0 = every step does;
- *                          bit-identical.  Whole levels without escape rows, 64 x 32 tiles ("fuse_k_shape" 7 and 8); see
+ *                          bit-identical.  Whole levels without escape rows, "fuse_k_shape" 7, 8 and 9; see
  *                          mg_march_plan
  *     "fuse_classes"       that pass reads one class byte per row instead of the 32-byte row where the level has
  *                          row classes (1); bit-identical either way

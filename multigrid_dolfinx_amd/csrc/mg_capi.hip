@@ -193,14 +193,14 @@ struct Level {
     int lm_ntop = 0;
     int lm_top[LM_K] = {0, 0, 0, 0, 0, 0, 0, 0};
     // march plans of the K-sweep pass (mg_jacobik3d.hip.h, jk3_plan): per (tile, wave) the run of planes whose classes are all
-    // `cmain` and the run whose classes do not change from plane to plane, one plan per K = 3, 4, 5 and tile shape 7, 8
-    // (march_plan_slot).  Built at the first such launch outside a capture (or by prepare_cycle), dropped wherever `cls` is
+    // `cmain` and the run whose classes do not change from plane to plane, one plan per K = 3, 4, 5 and tile shape 7, 8, and
+    // one for shape 9 (K = 5; march_plan_slot).  Built at the first such launch outside a capture (or by prepare_cycle), dropped wherever `cls` is
     // installed; waves[i] / planes[i]: waves with a run of kind i (a constant run that is the cmain run counts there only), planes in them
     struct MarchPlan {
         DevBuf<int> iv;
         int64_t waves[2] = {0, 0}, planes[2] = {0, 0};
     };
-    MarchPlan plan[6];
+    MarchPlan plan[7];
     int cmain = 0;                          // the most frequent class and its entries (passed to the kernels by value)
     double cm[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     int64_t cls_lead = 0;                   // cls[row + cls_lead], zero padding of cls_lead entries on both sides
@@ -381,8 +381,11 @@ struct mg_context {
     int fuse_k_shape = -1;          // ... its tile: 0 = 128 x 24 cells (12 waves x 2 lines), 1 = 64 x 48 (12 waves x 4 lines),
                                     // 2 = 128 x 24 (8 waves x 3 lines, 256 registers), 3 .. 5 = 64 x 24 by 6 / 8 / 4 waves, two workgroups
                                     // per CU, 6 = 64 x 48 by 16 waves, 7 = 64 x 32 by 16 waves (no spills up to five sweeps), 8 = shape 7
-                                    // with one barrier per step (level 0 in registers, images double-buffered); -1: 8 for five sweeps
-                                    // per pass, 7 for three and four (jk3_shape)
+                                    // with one barrier per step (level 0 in registers, images double-buffered), 9 = shape 8 on 64 x 36
+                                    // tiles whose first and last wave own the four rim lines (five sweeps on whole levels; elsewhere
+                                    // it stands for 8, for 7 below five sweeps); -1: for five sweeps per pass 9 on whole levels of at
+                                    // least "fuse_k_rim_min_rows" rows and 8 elsewhere, 7 for three and four (jk3_shape_for)
+    int64_t fuse_k_rim_min_rows = (int64_t)1 << 26;    // ... (513^3 and 1025^3 rows: where shape 9 was measured against shape 8)
     int fuse_k_segments = 0;        // ... plane segments per tile (0: chosen from the item count)
     int timing_force_form = -1;     // mg_time_kernel("jacobik3:formN"): every step of the K-sweep pass in one form (wrong results; how fast
                                     // each form is by itself)
@@ -1815,22 +1818,32 @@ int escape_kmax(mg_context* c, const Level& L, const unsigned char* cls, int64_t
 struct JK3Range { int za0, za1, zb0, zb1; };
 
 // the tile shape of a K-sweep pass ("fuse_k_shape"; -1: chosen by K)
+// (shape 9, rim waves, exists for five sweeps per pass: with fewer it stands for shape 7)
 int jk3_shape(const mg_context* c, int K) {
-    return c->fuse_k_shape >= 0 ? c->fuse_k_shape : (K >= 5 ? 8 : 7);
+    const int shape = c->fuse_k_shape >= 0 ? c->fuse_k_shape : (K >= 5 ? 8 : 7);
+    return shape == 9 && K < 5 ? 7 : shape;
 }
 
 // ... on a level with `ncls` classes (shapes 3 and up keep 64 rows of the class table in LDS or run one workgroup of 16 waves
-// per CU: levels with more classes take shape 1)
-int jk3_shape_for(const mg_context* c, int K, int ncls) {
-    return jk3_shape(c, K) >= 3 && ncls > 64 ? 1 : jk3_shape(c, K);
+// per CU: levels with more classes take shape 1) and `rows` rows; `whole`: not a slab.  Shape 9 marches whole levels: slabs
+// take shape 8; chosen by K, five sweeps per pass take it on whole levels of at least "fuse_k_rim_min_rows" rows (the sizes it
+// was measured at, 513^3 and 1025^3).
+int jk3_shape_for(const mg_context* c, int K, int ncls, bool whole, int64_t rows) {
+    int shape = jk3_shape(c, K);
+    if (c->fuse_k_shape < 0 && K >= 5 && rows >= c->fuse_k_rim_min_rows) shape = 9;
+    if (shape >= 3 && ncls > 64) return 1;
+    return shape == 9 && !whole ? 8 : shape;
 }
 
 // March plans (jk3_plan).  Which launches take one: whole levels without escape rows on the 64 x 32 tiles of 16 waves
-// (shapes 7 and 8), three to five sweeps per pass.  Slabs and levels with escape rows are deliberately left out: a slab's
-// plane range differs per rank and its launches are split, and escape rows are what the class loads are there to find.
+// (shapes 7 and 8), three to five sweeps per pass, and on the 64 x 36 tiles of shape 9 (five sweeps: the last slot).  Slabs
+// and levels with escape rows are deliberately left out: a slab's plane range differs per rank and its launches are split,
+// and escape rows are what the class loads are there to find.
+constexpr int MARCH_PLAN_SLOT_RIM = 6;
 int march_plan_slot(const mg_context* c, const Level& L, int K) {
     if (!c->fuse_k_plan || !c->fuse_k_dpp || K < 3 || K > 5 || !L.cls || L.cls_escape || is_slab(c, L)) return -1;
-    const int shape = jk3_shape_for(c, K, L.ncls);
+    const int shape = jk3_shape_for(c, K, L.ncls, true, L.nloc);
+    if (shape == 9) return MARCH_PLAN_SLOT_RIM;
     return shape == 7 || shape == 8 ? (K - 3) * 2 + (shape - 7) : -1;
 }
 
@@ -1840,13 +1853,15 @@ int ensure_march_plan(mg_context* c, Level& L, int K, int slot) {
     if (mp.iv) return 0;
     JK3PlanArgs a{};
     a.cls = L.cls; a.clead = L.cls_lead; a.P = L.g.plane; a.nx = L.g.nx; a.ny = L.g.ny; a.nz = L.g.nk; a.cmain = L.cmain;
-    const int WI = 64 - 2 * K, HY = 32 - 2 * K + 2;         // (shapes 7 and 8 share their tiles)
+    const bool rim = slot == MARCH_PLAN_SLOT_RIM;           // (K = 5)
+    const int WI = 64 - 2 * K, HY = rim ? jk3_rim_map<5>::HY : 32 - 2 * K + 2;         // (shapes 7 and 8 share their tiles)
     a.ntx = (a.nx + WI - 1) / WI; a.nty = (a.ny + HY - 1) / HY;
     const size_t n = (size_t)a.ntx * a.nty * 16 * 4;
     DevBuf<int> iv;
     MG_TRY(iv.alloc(c, n));
     a.plan = iv;
-    with_int<3, 4, 5>(K, [&](auto k) { hipLaunchKernelGGL((jk3_plan<decltype(k)::value, 16, 2, 1>), dim3((unsigned)(a.ntx * a.nty)), dim3(16 * WAVE), 0, c->stream, a); });
+    if (rim) hipLaunchKernelGGL((jk3_plan_rim<5>), dim3((unsigned)(a.ntx * a.nty)), dim3(16 * WAVE), 0, c->stream, a);
+    else with_int<3, 4, 5>(K, [&](auto k) { hipLaunchKernelGGL((jk3_plan<decltype(k)::value, 16, 2, 1>), dim3((unsigned)(a.ntx * a.nty)), dim3(16 * WAVE), 0, c->stream, a); });
     HIP_TRY(hipGetLastError());
     std::vector<int> h(n);
     HIP_TRY(hipMemcpyAsync(h.data(), iv, n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
@@ -1859,13 +1874,15 @@ int ensure_march_plan(mg_context* c, Level& L, int K, int slot) {
     return 0;
 }
 
-template <int K, int NW, int LPW, int M, bool DPP, int PF = 1, int WPE = (NW == 12 ? 3 : 2), int TR = 256, bool ESC = false, bool B1 = false>
+// (RIM: the tiles of shape 9, jk3_rim_map -- sixteen waves, the lines per wave are the map's)
+template <int K, int NW, int LPW, int M, bool DPP, int PF = 1, int WPE = (NW == 12 ? 3 : 2), int TR = 256, bool ESC = false, bool B1 = false, bool RIM = false>
 int launch_jacobikc_t(mg_context* c, JK3Args a, bool finest, const JK3Range& zr, int seglen) {
-    constexpr int EX = 64 * M, EY = NW * LPW, WI = EX - 2 * K, HY = EY - 2 * K + 2;
+    static_assert(!RIM || (NW == jk3_rim_map<K>::NW && M == 1 && DPP && PF == 1 && WPE == 4 && !ESC && B1), "shape 9 is shape 8 with another line map");
+    constexpr int EX = 64 * M, EY = RIM ? jk3_rim_map<K>::EY : NW * LPW, WI = EX - 2 * K, HY = EY - 2 * K + 2;
     a.ntx = (a.nx + WI - 1) / WI;
     a.nty = (a.ny + HY - 1) / HY;
     const int64_t ntile = (int64_t)a.ntx * a.nty;
-    constexpr size_t lds = B1 ? jk3b_lds_bytes<K, NW, LPW, M, TR>() : jk3_lds_bytes<K, NW, LPW, M, TR, ESC>();
+    constexpr size_t lds = RIM ? jk3r_lds_bytes<K, TR>() : B1 ? jk3b_lds_bytes<K, NW, LPW, M, TR>() : jk3_lds_bytes<K, NW, LPW, M, TR, ESC>();
     static_assert(lds <= 160 * 1024, "one CU's LDS");
     a.za0 = zr.za0; a.za1 = zr.za1; a.zb0 = zr.zb0; a.zb1 = zr.zb1;
     const int planes = std::max(0, zr.za1 - zr.za0) + std::max(0, zr.zb1 - zr.zb0);
@@ -1911,6 +1928,7 @@ int launch_jacobikc_t(mg_context* c, JK3Args a, bool finest, const JK3Range& zr,
     if (a.ncls > TR) return fail("more row classes than this tile shape keeps in LDS");
     void (*kern)(JK3Args) = nullptr;
     if constexpr (ESC) kern = sdia_jacobikc_escape<K, NW, LPW, M, DPP, PF, WPE, TR>;
+    else if constexpr (RIM) kern = finest ? sdia_jacobikc_finest_rim<K, TR> : sdia_jacobikc_rim<K, TR>;
     else if constexpr (B1) kern = finest ? sdia_jacobikc_finest_b1<K, NW, LPW, M, WPE, TR> : sdia_jacobikc_b1<K, NW, LPW, M, WPE, TR>;
     else kern = finest ? sdia_jacobikc_finest<K, NW, LPW, M, DPP, PF, WPE, TR> : sdia_jacobikc<K, NW, LPW, M, DPP, PF, WPE, TR>;
     MG_TRY(allow_large_lds(c, reinterpret_cast<const void*>(kern), lds));
@@ -1921,10 +1939,10 @@ int launch_jacobikc_t(mg_context* c, JK3Args a, bool finest, const JK3Range& zr,
 }
 
 template <int K, int PF>
-int launch_jacobikc_kp(mg_context* c, const JK3Args& a, bool finest, const JK3Range& zr, int seglen) {
+int launch_jacobikc_kp(mg_context* c, const JK3Args& a, bool finest, const JK3Range& zr, int seglen, bool whole) {
     if (!c->fuse_k_dpp) return launch_jacobikc_t<K, 12, 2, 2, false, PF>(c, a, finest, zr, seglen);     // (experiment: -1 / +1 neighbours through LDS)
     // shapes 3..5: 64 x 24 tiles, two workgroups per CU (class table of 64 rows); levels with more classes take shape 1
-    int shape = jk3_shape_for(c, K, a.ncls);
+    int shape = jk3_shape_for(c, K, a.ncls, whole, a.P * a.nz);
     // planes with fewer 64 x 48 tiles than the GPU has CUs (the 513^2 and 257^2 planes of a slab's coarser levels): half
     // as tall tiles, two workgroups per CU
     if (shape == 1 && a.ncls <= 64 && K <= 4 && c->fuse_k_small_tiles) {
@@ -1941,12 +1959,14 @@ int launch_jacobikc_kp(mg_context* c, const JK3Args& a, bool finest, const JK3Ra
         case 7: return launch_jacobikc_t<K, 16, 2, 1, true, PF, 4>(c, a, finest, zr, seglen);                                      // 64 x 32 by 16 waves
         case 8: if constexpr (PF == 1) return launch_jacobikc_t<K, 16, 2, 1, true, 1, 4, 256, false, true>(c, a, finest, zr, seglen);  // ... one barrier per step
                 else return fail("tile shape 8 stages one plane of x (fuse_k_pf 1)");
+        case 9: if constexpr (K == 5 && PF == 1) return launch_jacobikc_t<K, 16, 2, 1, true, 1, 4, 64, false, true, true>(c, a, finest, zr, seglen);  // ... rim waves, 64 x 36
+                else return fail("tile shape 9 takes five sweeps per pass and stages one plane of x");
         default: return launch_jacobikc_t<K, 12, 2, 2, true, PF>(c, a, finest, zr, seglen);
     }
 }
 
 template <int K>
-int launch_jacobikc_k(mg_context* c, const JK3Args& a, bool finest, const JK3Range& zr, int seglen) {
+int launch_jacobikc_k(mg_context* c, const JK3Args& a, bool finest, const JK3Range& zr, int seglen, bool whole) {
     // levels with rows of class CLS_ESCAPE: the variant that fetches them, one tile shape (the one escape_window() checked)
     if (a.escape) {
         if constexpr (K >= 3) return launch_jacobikc_t<K, 16, 2, 1, true, 1, 4, 256, true>(c, a, finest, zr, seglen);
@@ -1954,11 +1974,11 @@ int launch_jacobikc_k(mg_context* c, const JK3Args& a, bool finest, const JK3Ran
     }
     // a second plane of x staged in registers ("fuse_k_pf" 2) fits the register budget with three sweeps only
     if constexpr (K == 3 || K == 4) {
-        if (c->fuse_k_pf == 2 && (K == 3 || jk3_shape(c, K) == 7)) return launch_jacobikc_kp<K, 2>(c, a, finest, zr, seglen);
+        if (c->fuse_k_pf == 2 && (K == 3 || jk3_shape(c, K) == 7)) return launch_jacobikc_kp<K, 2>(c, a, finest, zr, seglen, whole);
     }
     // (two sweeps per pass: slabs only, where a pass also saves an exchange; one tile shape)
     if constexpr (K == 2) return launch_jacobikc_t<K, 12, 4, 1, true, 1>(c, a, finest, zr, seglen);
-    else return launch_jacobikc_kp<K, 1>(c, a, finest, zr, seglen);
+    else return launch_jacobikc_kp<K, 1>(c, a, finest, zr, seglen, whole);
 }
 
 // out = K Jacobi sweeps applied to x (2 <= K <= 5) on the owned planes [zr) of the level (null: all of them); on slabs the
@@ -1990,7 +2010,7 @@ int launch_jacobikc(mg_context* c, Level& L, int K, const double* x_rows, const 
     const JK3Range whole{0, L.g.nk, 0, 0};
     c->jk3_tail = 0;
     int rc = 0;
-    if (!with_int<2, 3, 4, 5>(K, [&](auto k) { rc = launch_jacobikc_k<decltype(k)::value>(c, a, is_finest(c, L), zr ? *zr : whole, seglen); }))
+    if (!with_int<2, 3, 4, 5>(K, [&](auto k) { rc = launch_jacobikc_k<decltype(k)::value>(c, a, is_finest(c, L), zr ? *zr : whole, seglen, !dist); }))
         return fail("sweeps per pass must be in 2..5");
     return rc;
 }
@@ -4785,7 +4805,7 @@ int mg_set_tuning(mg_handle c, const char* key, int64_t value) {
         if (value < 0 || value > 5) return fail("fuse_k must be in 0..5 (below 3: pairs of sweeps only)");
         c->fuse_k = (int)value;
     } else if (k == "fuse_k_shape") {
-        if (value < -1 || value > 8) return fail("fuse_k_shape must be 0..8, or -1 (by sweeps per pass)");
+        if (value < -1 || value > 9) return fail("fuse_k_shape must be 0..9, or -1 (by sweeps per pass)");
         c->fuse_k_shape = (int)value;
     } else if (k == "fuse_k_slab_min_rows") {
         c->fuse_k_slab_min_rows = value;
@@ -4798,6 +4818,8 @@ int mg_set_tuning(mg_handle c, const char* key, int64_t value) {
         c->fuse_k_small_rows = value;
     } else if (k == "fuse_k5_min_rows") {
         c->fuse_k5_min_rows = value;
+    } else if (k == "fuse_k_rim_min_rows") {
+        c->fuse_k_rim_min_rows = value;
     } else if (k == "fuse_k4_min_rows") {
         c->fuse_k4_min_rows = value;
     } else if (k == "fuse_k_nt_store") {

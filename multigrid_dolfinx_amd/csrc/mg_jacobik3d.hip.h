@@ -871,6 +871,463 @@ void sdia_jacobikc_escape(JK3Args a) {
     jk3_body<K, NW, LPW, M, DPP, PF, TR, true>(a);
 }
 
+// Rim waves (tile shape 9).  On the 64 x 32 tiles of shape 8 the lines 0 .. K-2 and EY-K+1 .. EY-1 carry the halo levels (caps
+// 1 .. K-1, jk3_caps) and store nothing; two waves on either side own them, two lines each, and compute 3 and 7 line-levels a
+// step (K = 5) where the other twelve compute 10 -- the step is as long as its full-cap waves make it, so two waves' worth of
+// its time buys no result line.  Here ONE wave on either side owns all K - 1 rim lines (caps 1 + 2 + .. + K-1 = K (K-1) / 2
+// line-levels: as many as the K line-levels of each of an interior wave's two lines when K = 5), and the fourteen waves between
+// them own two full-cap lines each: EY = 2 (K - 1) + 28 lines, of which HY = 28 get all K sweeps.  Everything else is shape
+// 8's: one barrier per step, level 0 in registers, the images double-buffered by parity, DPP neighbours, march plans.
+// The line map: which lines a wave owns.  The march, the plan (jk3_plan_rim) and the host's tile counts all read it.
+template <int K> struct jk3_rim_map {
+    static constexpr int NW = 16, RL = K - 1;               // waves; lines of a rim wave
+    static constexpr int NLM = RL > 2 ? RL : 2;             // the most lines a wave owns
+    static constexpr int EY = 2 * RL + 2 * (NW - 2), HY = EY - 2 * K + 2, WI = 64 - 2 * K;
+    static constexpr int first(int wave) { return wave == 0 ? 0 : wave == NW - 1 ? EY - RL : RL + 2 * (wave - 1); }
+    static constexpr int lines(int wave) { return wave == 0 || wave == NW - 1 ? RL : 2; }
+};
+// ... and the kinds of wave: 0 = two lines of cap K, 1 = wave 0 (caps 1 .. K-1), 2 = the last wave (caps K-1 .. 1).  A kind is
+// a type: the march runs one plane loop per kind, chosen once per wave, so that the registers of a loop are those of its kind
+// (K (K-1) / 2 partial sums and ring values of f on a rim wave, not K for each of its K - 1 lines).
+template <int K, int KIND> struct jk3_rim_kind {
+    static constexpr int NL = KIND == 0 ? 2 : K - 1;
+    static constexpr int cap(int l) { return KIND == 0 ? K : KIND == 1 ? l + 1 : K - 1 - l; }
+};
+
+template <int K, int TR> constexpr size_t jk3r_lds_bytes() {
+    return sizeof(double) * (TR * CLS_W + (size_t)(2 * (K - 1) * (jk3_rim_map<K>::EY + 1) + 1) * 64);
+}
+
+template <int K, int TR>
+__device__ __forceinline__ void jk3_rim_body(const JK3Args& a) {
+    using MAP = jk3_rim_map<K>;
+    constexpr int EX = 64, NW = MAP::NW, EY = MAP::EY, NCM = MAP::NLM, WI = MAP::WI, HY = MAP::HY;
+    constexpr int IS = (EY + 1) * EX, PS = (K - 1) * IS;      // image stride and parity stride, in doubles (jk3b_lds_doubles)
+    static_assert(CLS_W == 8, "table rows of eight doubles");
+    static_assert(K >= 3 && NCM <= 4, "a wave's class bytes of a plane live in one register");
+    static_assert(NCM * (K + 1) <= 64, "the fast-path flags live in one scalar register pair");
+    static_assert(8 * ((K - 2) * IS + (NCM + 1) * EX) < 65536, "every LDS access of a step is `register + 16-bit immediate`");
+    extern __shared__ double j2_smem[];
+    double* const sT = j2_smem;
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+
+    unsigned id;
+    {
+        const unsigned b = blockIdx.x, xcd = b & 7u, j = b >> 3, ch = a.xcd_chunk;
+        id = ((j / ch) * 8u + xcd) * ch + (j % ch);
+    }
+    if (id >= a.nitems) return;
+    const unsigned ntile = (unsigned)(a.ntx * a.nty);
+    const int nsa = (a.za1 - a.za0 + a.seglen - 1) / a.seglen;
+    const int nsb = (a.zb1 - a.zb0 + a.seglen - 1) / a.seglen;
+    const unsigned items_a = (unsigned)a.ta * (unsigned)(nsa + max(nsb, 0));
+    unsigned tt;
+    int z0, z1;
+    if (id < items_a) {
+        const int seg = (int)(id / (unsigned)a.ta);
+        tt = id % (unsigned)a.ta;
+        z0 = seg < nsa ? a.za0 + seg * a.seglen : a.zb0 + (seg - nsa) * a.seglen;
+        z1 = min(seg < nsa ? a.za1 : a.zb1, z0 + a.seglen);
+    } else {
+        const unsigned j = id - items_a, tb = ntile - (unsigned)a.ta;
+        tt = (unsigned)a.ta + j % tb;
+        z0 = a.za0 + (int)(j / tb) * a.seglen_b;
+        z1 = min(a.za1, z0 + a.seglen_b);
+    }
+    const int tiy = (int)(tt / (unsigned)a.ntx), tix = (int)(tt % (unsigned)a.ntx);
+    if (z1 <= z0) return;
+    const int tx0 = tix * WI - K, ty0 = tiy * HY - (K - 1);   // grid position of cell (0, 0)
+
+    {
+        const int nt = a.ncls * CLS_W;
+        for (int i = threadIdx.x; i < nt; i += NW * WAVE) {
+            double v = a.ctab[i];
+            if ((i & (CLS_W - 1)) == CLS_W - 1) {
+                const double d = a.ctab[i - 4];
+                v = a.omega * (1.0 / (d != 0.0 ? d : 1.0));
+            }
+            sT[i] = v;
+        }
+        constexpr int NZ = (2 * (K - 1) * (EY + 1) + 1) * EX;
+        for (int i = threadIdx.x; i < NZ; i += NW * WAVE) sT[TR * CLS_W + i] = 0.0;
+    }
+    const double m0 = a.cm[0], m1 = a.cm[1], m2 = a.cm[2], m3 = a.cm[3], m4 = a.cm[4], m5 = a.cm[5], m6 = a.cm[6];
+    const double mcf = a.omega * (1.0 / (m3 != 0.0 ? m3 : 1.0));
+    const int cmain = a.cmain;
+
+    // cell l of this thread: ex = lane, ey = ey0 + l, l < the lines of the wave's kind (what is set up for the cells beyond
+    // them, on the fourteen waves with two lines, is never used)
+    const int ey0 = MAP::first(wave);
+    const int wkind = wave == 0 ? 1 : wave == NW - 1 ? 2 : 0;
+    int bcur = 0, bprev = 0;    // level 1 of the step's parity / of the step before, at the line below the wave's first (see jk3_body)
+    // ... of parity 0; the one register the march keeps of the lane (the table and a line are multiples of 64 doubles: the
+    // lane is its low six bits)
+    int lbase = TR * CLS_W + ey0 * EX + lane;
+    asm volatile("" : "+v"(lbase));
+    auto limg = [&](int base, int t) -> double* { return j2_smem + base + (t - 1) * IS + EX; };
+    unsigned inT = 0;           // bit l: this lane's cell l gets all K sweeps and lies on the grid
+#pragma unroll
+    for (int l = 0; l < NCM; ++l) {
+        const int ey = ey0 + l;
+        if (lane >= K && lane < EX - K && ey >= K - 1 && ey <= EY - K && tx0 + lane < a.nx && ty0 + ey < a.ny) inT |= 1u << l;
+    }
+    // the row of cell l in plane p exists  <=>  the level holds plane p + sh(l), sh = -1, 0, +1 (general form only: worked out
+    // where it is used, from scalars and the lane, instead of living in a register through the march)
+    auto shof = [&](int l) -> int {
+        const int64_t r = (int64_t)(ty0 + ey0 + l) * a.nx + (tx0 + (lbase & 63));
+        return r < 0 ? -1 : (r >= a.P ? 1 : 0);
+    };
+
+    const int bias = 2 * a.nx + K + 2;
+    const int xcl = a.nx + 1 - tx0;
+    unsigned eo[NCM];           // byte offsets of the cells' doubles (>> 3: of their class bytes)
+#pragma unroll
+    for (int l = 0; l < NCM; ++l) {
+        eo[l] = jk3_cell_offset(ty0 + ey0 + l, lane, a.nx, a.ny, tx0, xcl, bias);
+        asm volatile("" : "+v"(eo[l]));     // (one register per cell: left alone the compiler keeps the class byte's offset too)
+    }
+    // the lines below / above the wave's
+    const unsigned eos = jk3_cell_offset(ty0 + ey0 - 1, lane, a.nx, a.ny, tx0, xcl, bias);
+    const unsigned eon = jk3_cell_offset(ty0 + ey0 + MAP::lines(wave), lane, a.nx, a.ny, tx0, xcl, bias);
+    const unsigned char* const clsb = jk3_class_base(a.cls, a.clead, bias);
+    const double* const xb0 = a.x - bias;
+    const double* const fb0 = a.f - bias;
+    auto sbase = [](const void* p) -> gcptr_t {
+        const unsigned long long u = (unsigned long long)p;
+        const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)u);
+        const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(u >> 32));
+        return (gcptr_t)(((unsigned long long)hi << 32) | lo);
+    };
+    auto ldd = [](gcptr_t b, unsigned e8) -> double {
+        asm volatile("" : "+v"(e8));
+        return *(const __attribute__((address_space(1))) double*)(b + e8);
+    };
+    typedef unsigned int __attribute__((aligned(1))) u32_unaligned_t;
+    auto ldc = [](gcptr_t b, unsigned e8) -> int {
+        unsigned e = e8 >> 3;
+        asm volatile("" : "+v"(e));
+        return (int)*(const __attribute__((address_space(1))) u32_unaligned_t*)(b + e);
+    };
+    const int pmin = -a.plo - 1, pmax = a.nz + a.phi;
+
+    // planned steps: see jk3_body
+    int klo = 0x7fffffff, khi = 0x7fffffff, kform = 0;
+    if (a.plan) {
+        const int* const pw = a.plan + 4 * ((int)tt * NW + wave);
+        const int top = a.nz - K - 1;
+        const int lo0 = max(max(pw[0], 1), z0 - K), hi0 = min(pw[1] - K, top);
+        const int lo1 = max(max(pw[2], 1), z0 - K), hi1 = min(pw[3] - K, top);
+        const int n0 = min(hi0, z1) - lo0, n1 = min(hi1, z1) - lo1;
+        if (n0 > 0 && n0 >= n1) {
+            klo = __builtin_amdgcn_readfirstlane(lo0);
+            khi = __builtin_amdgcn_readfirstlane(hi0);
+        } else if (n1 > 0) {
+            klo = __builtin_amdgcn_readfirstlane(lo1);
+            khi = __builtin_amdgcn_readfirstlane(hi1);
+            kform = 1;
+        }
+    }
+    auto interior_step = [&](int k) -> bool { return k >= klo && k < khi; };
+
+    // registers per cell: partial sums and f of the levels up to the line's cap; x (X: the plane that arrives, XP: the one
+    // before), the class of the plane that arrives; per wave x of the lines below / above its lines
+    double acc[K][NCM], fr[K][NCM], X[NCM], XP[NCM], hS = 0.0, hN = 0.0;
+    int C[NCM];
+    unsigned cw[K + 1];         // class bytes of the planes k .. k+K, a byte per cell
+    unsigned long long fast = 0;        // wave-uniform; bit j*NL + l: all 64 cells l of plane k+j are of class cmain
+#pragma unroll
+    for (int l = 0; l < NCM; ++l) {
+#pragma unroll
+        for (int t = 0; t < K; ++t) acc[t][l] = fr[t][l] = 0.0;
+        X[l] = XP[l] = 0.0;
+        C[l] = 0;
+    }
+#pragma unroll
+    for (int j = 0; j <= K; ++j) cw[j] = 0u;
+
+    // slice i of n of the loads of a step (see jk3_body): x and, off plan, the classes of `plane`, f of `fplane`
+    auto load_slice = [&](auto kind, const int i, const int n, const int plane, const int fplane, const bool noc) __attribute__((always_inline)) {
+        constexpr int NL = decltype(kind)::NL;
+        const int64_t o = (int64_t)min(max(plane, pmin), pmax) * a.P;
+        const gcptr_t cb = sbase(clsb + o);
+        const gcptr_t xb = sbase(xb0 + o);
+        const gcptr_t fb = sbase(fb0 + (int64_t)min(max(fplane, pmin), pmax) * a.P);
+#pragma unroll
+        for (int l = 0; l < NL; ++l) {
+            if ((l * n) / NL != i) continue;
+            X[l] = ldd(xb, eo[l]);
+            if (!noc) C[l] = ldc(cb, eo[l]);
+            fr[K - 1][l] = ldd(fb, eo[l]);
+        }
+        if (i == n - 1) { hS = ldd(xb, eos); hN = ldd(xb, eon); }
+    };
+    auto cls_of = [&](int j, int l) -> int { return (int)((cw[j] >> (8 * l)) & 255u); };
+    auto cls_now = [&](int j, int l) -> int {       // (general form: extracted anew at every use)
+        unsigned w = cw[j];
+        asm volatile("" : "+v"(w));
+        return (int)((w >> (8 * l)) & 255u);
+    };
+    int k_plane = 0;
+    bool k_store = false;
+    __attribute__((address_space(1))) char* k_out = nullptr;
+    auto store = [&](int l, double v) {
+        unsigned e8 = eo[l];
+        asm volatile("" : "+v"(e8));
+        if (a.nt_store) __builtin_nontemporal_store(v, (__attribute__((address_space(1))) double*)(k_out + e8));
+        else *(__attribute__((address_space(1))) double*)(k_out + e8) = v;
+    };
+    int lo_t[K + 1], n_t[K + 1];
+#pragma unroll
+    for (int t = 1; t <= K; ++t) {
+        lo_t[t] = -min(a.plo, K - t);
+        n_t[t] = a.nz + min(a.phi, K - t) - lo_t[t];
+    }
+
+    // ---- the three forms of a step, as in jk3_body (B1), over the lines and caps of the wave's kind ----
+    auto phase_a_fast = [&](auto col_tag, auto kind) __attribute__((always_inline)) {
+        constexpr bool COL = decltype(col_tag)::value;
+        using KD = decltype(kind);
+#pragma unroll
+        for (int l = 0; l < KD::NL; ++l) {
+            const int iw = l * EX;
+            double k0 = m0, k6 = m6, kcf = mcf;
+            if constexpr (COL) {
+                const dvec2_t* const tr = reinterpret_cast<const dvec2_t*>(sT + CLS_W * cls_of(0, l));
+                const dvec2_t t01 = tr[0], t67 = tr[3];
+                k0 = t01.x; k6 = t67.x; kcf = t67.y;
+            }
+            double nw = X[l];
+#pragma unroll
+            for (int t = 1; t <= K; ++t) {
+                if (t > KD::cap(l)) {           // (above the line's cap: its last level goes to the image, nothing else)
+                    if (t == KD::cap(l) + 1) limg(bcur, t - 1)[iw] = nw;
+                    continue;
+                }
+                const double wd = t == 1 ? XP[l] : limg(bprev, t - 1)[iw];
+                const double s = fma(k6, nw, acc[t - 1][l]);      // +P
+                const double o = wd + kcf * (fr[K - t][l] - s);
+                acc[t - 1][l] = fma(k0, wd, 0.0);                 // -P of the plane above
+                if (t > 1) limg(bcur, t - 1)[iw] = nw;
+                nw = o;
+            }
+            if (KD::cap(l) == K && k_store && (inT >> l & 1u)) store(l, nw);
+        }
+    };
+    auto phase_b_fast = [&](auto col_tag, auto kind, const int t) __attribute__((always_inline)) {
+        constexpr bool COL = decltype(col_tag)::value;
+        using KD = decltype(kind);
+        constexpr int NL = KD::NL;
+        const double* const img = limg(bcur, t > 1 ? t - 1 : 1);
+        double v[NL], ys, yn;
+        if (t == 1) {           // (level 0: registers)
+            ys = hS;
+#pragma unroll
+            for (int l = 0; l < NL; ++l) v[l] = X[l];
+            yn = hN;
+        } else {
+            ys = img[-EX];
+#pragma unroll
+            for (int l = 0; l < NL; ++l) v[l] = img[l * EX];
+            yn = img[NL * EX];
+        }
+#pragma unroll
+        for (int l = 0; l < NL; ++l) {
+            if (t > KD::cap(l)) continue;       // (the line has no level t: the reads only it needed go with it)
+            const double yw = jk3_from_west(v[l]), ye = jk3_from_east(v[l]);
+            double k1 = m1, k2 = m2, k3 = m3, k4 = m4, k5 = m5;
+            if constexpr (COL) {
+                const dvec2_t* const tr = reinterpret_cast<const dvec2_t*>(sT + CLS_W * cls_of(0, l));
+                const dvec2_t t01 = tr[0], t23 = tr[1], t45 = tr[2];
+                k1 = t01.y; k2 = t23.x; k3 = t23.y; k4 = t45.x; k5 = t45.y;
+            }
+            double s = acc[t - 1][l];
+            s = fma(k1, l > 0 ? v[l > 0 ? l - 1 : 0] : ys, s);
+            s = fma(k2, yw, s);
+            s = fma(k3, v[l], s);
+            s = fma(k4, ye, s);
+            s = fma(k5, l + 1 < NL ? v[l + 1 < NL ? l + 1 : l] : yn, s);
+            acc[t - 1][l] = s;
+        }
+    };
+    // General form: every cell's entries from the class table, rows outside the level masked to zero.
+    auto phase_a_general = [&](auto kind) __attribute__((always_inline)) {
+        using KD = decltype(kind);
+#pragma unroll
+        for (int l = 0; l < KD::NL; ++l) {
+            const int iw = l * EX;
+            double nw = X[l];
+            int pc = k_plane + shof(l);
+            asm volatile("" : "+v"(pc));
+#pragma unroll
+            for (int t = 1; t <= K; ++t) {
+                const int j = K - t;                                  // ring index of the plane being finished
+                double* const img = limg(bcur, t > 1 ? t - 1 : 1);
+                if (t > KD::cap(l)) {
+                    if (t == KD::cap(l) + 1) img[iw] = nw;
+                    continue;
+                }
+                const double wd = t == 1 ? XP[l] : limg(bprev, t - 1)[iw];
+                const dvec2_t t67 = reinterpret_cast<const dvec2_t*>(sT + CLS_W * cls_now(j, l))[3];
+                const dvec2_t t01 = reinterpret_cast<const dvec2_t*>(sT + CLS_W * cls_now(j + 1, l))[0];
+                const double s = fma(t67.x, nw, acc[t - 1][l]);
+                double o = wd + t67.y * (fr[j][l] - s);
+                o = (unsigned)(pc + j - lo_t[t]) < (unsigned)n_t[t] ? o : 0.0;
+                acc[t - 1][l] = fma(t01.x, wd, 0.0);
+                if (t > 1) img[iw] = nw;
+                nw = o;
+                __builtin_amdgcn_sched_barrier(0);      // (rare path: one cell and level at a time)
+            }
+            if (KD::cap(l) == K && k_store && (inT >> l & 1u)) store(l, nw);
+        }
+    };
+    auto phase_b_general = [&](auto kind, const int t) __attribute__((always_inline)) {
+        using KD = decltype(kind);
+        constexpr int NL = KD::NL;
+        double x0w[NL], x0e[NL];        // (level 0: the -1 / +1 neighbours through DPP, all cells' before the first use)
+        if (t == 1) {
+#pragma unroll
+            for (int l = 0; l < NL; ++l) { x0w[l] = jk3_from_west(X[l]); x0e[l] = jk3_from_east(X[l]); }
+        }
+#pragma unroll
+        for (int l = 0; l < NL; ++l) {
+            if (t > KD::cap(l)) continue;
+            const int iw = l * EX;
+            double ys, yw, yd, ye, yn;
+            if (t == 1) {
+                ys = l > 0 ? X[l > 0 ? l - 1 : l] : hS;
+                yw = x0w[l]; yd = X[l]; ye = x0e[l];
+                yn = l + 1 < NL ? X[l + 1 < NL ? l + 1 : l] : hN;
+            } else {
+                const double* const img = limg(bcur, t - 1);
+                ys = img[iw - EX]; yw = img[iw - 1]; yd = img[iw]; ye = img[iw + 1]; yn = img[iw + EX];
+            }
+            const dvec2_t* const tr = reinterpret_cast<const dvec2_t*>(sT + CLS_W * cls_now(K - t, l));
+            const dvec2_t t01 = tr[0], t23 = tr[1], t45 = tr[2];
+            double s = acc[t - 1][l];
+            s = fma(t01.y, ys, s);
+            s = fma(t23.x, yw, s);
+            s = fma(t23.y, yd, s);
+            s = fma(t45.x, ye, s);
+            s = fma(t45.y, yn, s);
+            acc[t - 1][l] = s;
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    };
+
+    // One step (jk3_body, B1): `X, C, hS, hN` hold plane k+K; the loads of plane k+K+1 go out between the pieces of phase B.
+    auto step = [&](auto kind, const int k) __attribute__((always_inline)) {
+        using KD = decltype(kind);
+        constexpr int NL = KD::NL;
+        constexpr unsigned long long ALLFAST = (1ull << (NL * (K + 1))) - 1ull;
+        k_plane = k; k_store = k >= z0;
+        bcur = lbase + (k & 1) * PS;
+        bprev = lbase + ((k + 1) & 1) * PS;
+        asm volatile("" : "+v"(bcur));
+        asm volatile("" : "+v"(bprev));
+        {
+            const unsigned long long u = (unsigned long long)(a.out - bias + (int64_t)k * a.P);
+            const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)u);
+            const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(u >> 32));
+            k_out = (__attribute__((address_space(1))) char*)(((unsigned long long)hi << 32) | lo);
+        }
+        // ---- the plane k+K has arrived: its classes join the ring (the loaded values are first touched here) ----
+#pragma unroll
+        for (int l = 0; l < NL; ++l) asm volatile("" : "+v"(X[l]));
+        const bool interior = interior_step(k);     // (wave-uniform, from scalar registers)
+        if (k == khi) {         // the first step behind the planned ones: the ring as the unplanned path would hold it
+            unsigned m = 0;
+#pragma unroll
+            for (int l = 0; l < NL; ++l)
+                if (__builtin_amdgcn_readfirstlane((int)(__ballot(cls_of(0, l) != cmain) == 0ull))) m |= 1u << l;
+            fast = 0;
+#pragma unroll
+            for (int j = 0; j < K; ++j) {
+                fast |= (unsigned long long)m << (j * NL);
+                cw[j] = cw[0];
+            }
+        }
+        int form = kform;
+        if (!interior) {
+            unsigned m = 0;
+            cw[K] = 0u;
+#pragma unroll
+            for (int l = 0; l < NL; ++l) {
+                asm volatile("" : "+v"(C[l]));
+                C[l] &= 255;
+                cw[K] |= (unsigned)C[l] << (8 * l);
+                if (__builtin_amdgcn_readfirstlane((int)(__ballot(C[l] != cmain) == 0ull))) m |= 1u << l;
+            }
+            fast |= (unsigned long long)m << (K * NL);
+            // which form (jk3_body): 0 = interior stencil in all the wave's cells of the planes k .. k+K, 1 = every cell's class
+            // the same in those planes -- both only where every row the step touches exists --, 2 = general
+            form = 2;
+            if ((a.plo > 0 || k >= 1) && (a.phi > 0 || k + K + 1 < a.nz)) {
+                if (fast == ALLFAST) {
+                    form = 0;
+                } else {
+                    bool same = true;
+#pragma unroll
+                    for (int j = 1; j <= K; ++j) same = same && cw[j] == cw[0];
+                    if (__builtin_amdgcn_readfirstlane((int)(__ballot(!same) == 0ull))) form = 1;
+                }
+            }
+        }
+        if (a.force_form >= 0) form = a.force_form;
+        // ---- phase A: finish plane k+K-t of level t, t = 1 .. cap; start the plane above it ----
+        if (form == 0) phase_a_fast(std::false_type{}, kind);
+        else if (form == 1) phase_a_fast(std::true_type{}, kind);
+        else phase_a_general(kind);
+#pragma unroll
+        for (int l = 0; l < NL; ++l) XP[l] = X[l];
+        // ---- the rings move on; the next loads go out ----
+#pragma unroll
+        for (int l = 0; l < NL; ++l) {
+#pragma unroll
+            for (int j = 0; j + 1 < K; ++j) fr[j][l] = fr[j + 1][l];
+            if (KD::cap(l) >= 2) asm volatile("" : "+v"(fr[K - 2][l]));
+        }
+        if (!interior) {
+#pragma unroll
+            for (int j = 0; j < K; ++j) cw[j] = cw[j + 1];
+            fast >>= NL;
+        }
+        __syncthreads();
+        // ---- phase B: the in-plane terms of the planes started above; the next loads go out between its pieces ----
+#pragma unroll
+        for (int t = 1; t <= K; ++t) {
+            if (form == 0) phase_b_fast(std::false_type{}, kind, t);
+            else if (form == 1) phase_b_fast(std::true_type{}, kind, t);
+            else phase_b_general(kind, t);
+            __builtin_amdgcn_sched_barrier(0);
+            load_slice(kind, t - 1, K, k + K + 1, k + K, interior_step(k + 1));
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    };
+
+    // one plane loop per kind of wave; every wave passes the same barriers, one before the first step and one in each
+    auto march = [&](auto kind) __attribute__((always_inline)) {
+        load_slice(kind, 0, 1, z0 - K, z0 - K - 1, false);
+        __syncthreads();
+        for (int k = z0 - 2 * K; k < z1; ++k) step(kind, k);
+    };
+    if (wkind == 0) march(jk3_rim_kind<K, 0>{});
+    else if (wkind == 1) march(jk3_rim_kind<K, 1>{});
+    else march(jk3_rim_kind<K, 2>{});
+}
+
+// tile shape 9: rim waves (64 x 36 tiles for K = 5, 28 result lines)
+template <int K, int TR>
+__global__ __attribute__((amdgpu_flat_work_group_size(16 * WAVE, 16 * WAVE), amdgpu_waves_per_eu(4, 4)))
+void sdia_jacobikc_rim(JK3Args a) {
+    jk3_rim_body<K, TR>(a);
+}
+template <int K, int TR>
+__global__ __attribute__((amdgpu_flat_work_group_size(16 * WAVE, 16 * WAVE), amdgpu_waves_per_eu(4, 4)))
+void sdia_jacobikc_finest_rim(JK3Args a) {
+    jk3_rim_body<K, TR>(a);
+}
+
 // The most pool rows any tile of the march <K, NW, LPW, M> takes within K + 2 consecutive planes: one workgroup per tile
 // counts the cells of class CLS_ESCAPE plane by plane -- the tile's cells at the very rows the march reads their classes
 // from, but for the clamped ones (`standin` there) -- and keeps the largest sum over a window of planes.
@@ -924,20 +1381,11 @@ struct JK3PlanArgs {
     int* plan;
 };
 
-template <int K, int NW, int LPW, int M>
-__global__ __launch_bounds__(NW * WAVE) void jk3_plan(JK3PlanArgs a) {
-    constexpr int EX = 64 * M, EY = NW * LPW, NC = M * LPW, WI = EX - 2 * K, HY = EY - 2 * K + 2;
+// (the walk over the planes: `eo` the wave's cells as the march addresses them, `pw` where its four ints go)
+template <int NC>
+__device__ __forceinline__ void jk3_plan_walk(const JK3PlanArgs& a, const unsigned char* const clsb, const unsigned (&eo)[NC], int* const pw) {
     constexpr int U = 4;        // planes whose bytes are in flight together
     const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const unsigned tt = blockIdx.x;
-    const int tiy = (int)(tt / (unsigned)a.ntx), tix = (int)(tt % (unsigned)a.ntx);
-    const int tx0 = tix * WI - K, ty0 = tiy * HY - (K - 1);
-    const int ey0 = wave * LPW, bias = 2 * a.nx + K + 2, xcl = a.nx + 1 - tx0;
-    unsigned eo[NC];
-#pragma unroll
-    for (int c = 0; c < NC; ++c) eo[c] = jk3_cell_offset(ty0 + ey0 + c / M, lane + 64 * (c % M), a.nx, a.ny, tx0, xcl, bias);
-    const unsigned char* const clsb = jk3_class_base(a.cls, a.clead, bias);
     int p0 = 0, p1 = 0, prun = 0;       // the best run of cmain planes; where the present one starts
     int q0 = 0, q1 = 0, qrun = 0;       // ... of planes with the classes of the plane before
     int prev[NC];
@@ -974,10 +1422,38 @@ __global__ __launch_bounds__(NW * WAVE) void jk3_plan(JK3PlanArgs a) {
     }
     if (a.nz - prun > p1 - p0) { p0 = prun; p1 = a.nz; }
     if (a.nz - qrun > q1 - q0) { q0 = qrun; q1 = a.nz; }
-    if (lane == 0) {
-        int* const pw = a.plan + 4 * ((int)tt * NW + wave);
-        pw[0] = p0; pw[1] = p1; pw[2] = q0; pw[3] = q1;
-    }
+    if (lane == 0) { pw[0] = p0; pw[1] = p1; pw[2] = q0; pw[3] = q1; }
+}
+
+template <int K, int NW, int LPW, int M>
+__global__ __launch_bounds__(NW * WAVE) void jk3_plan(JK3PlanArgs a) {
+    constexpr int EX = 64 * M, EY = NW * LPW, NC = M * LPW, WI = EX - 2 * K, HY = EY - 2 * K + 2;
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const unsigned tt = blockIdx.x;
+    const int tiy = (int)(tt / (unsigned)a.ntx), tix = (int)(tt % (unsigned)a.ntx);
+    const int tx0 = tix * WI - K, ty0 = tiy * HY - (K - 1);
+    const int ey0 = wave * LPW, bias = 2 * a.nx + K + 2, xcl = a.nx + 1 - tx0;
+    unsigned eo[NC];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) eo[c] = jk3_cell_offset(ty0 + ey0 + c / M, lane + 64 * (c % M), a.nx, a.ny, tx0, xcl, bias);
+    jk3_plan_walk<NC>(a, jk3_class_base(a.cls, a.clead, bias), eo, a.plan + 4 * ((int)tt * NW + wave));
+}
+
+// ... for the tiles of shape 9 (jk3_rim_map): a wave with fewer lines than the longest looks at its last line again
+template <int K>
+__global__ __launch_bounds__(16 * WAVE) void jk3_plan_rim(JK3PlanArgs a) {
+    using MAP = jk3_rim_map<K>;
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const unsigned tt = blockIdx.x;
+    const int tiy = (int)(tt / (unsigned)a.ntx), tix = (int)(tt % (unsigned)a.ntx);
+    const int tx0 = tix * MAP::WI - K, ty0 = tiy * MAP::HY - (K - 1);
+    const int ey0 = MAP::first(wave), nl = MAP::lines(wave), bias = 2 * a.nx + K + 2, xcl = a.nx + 1 - tx0;
+    unsigned eo[MAP::NLM];
+#pragma unroll
+    for (int l = 0; l < MAP::NLM; ++l) eo[l] = jk3_cell_offset(ty0 + ey0 + min(l, nl - 1), lane, a.nx, a.ny, tx0, xcl, bias);
+    jk3_plan_walk<MAP::NLM>(a, jk3_class_base(a.cls, a.clead, bias), eo, a.plan + 4 * ((int)tt * MAP::NW + wave));
 }
 
 }  // namespace mgk

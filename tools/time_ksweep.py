@@ -2,6 +2,9 @@
 next to the two-sweep pass, and whole V(50,50) cycles with and without it.
 
     python tools/time_ksweep.py [finest_level=7] [reps=6] ["fuse_k=4" "fuse_k=4,fuse_k_shape=1" "fuse_k=5,fuse_k_plan=0" ...]
+
+"fuse_k_shape" is reset to 7 after every setting, so a five-sweep shape is named in each: "fuse_k=5,fuse_k_shape=8"
+"fuse_k=5,fuse_k_shape=9" (rim waves) alternating is profiles/r08_ksweep_time_rim.txt.
 """
 import os
 import sys
