@@ -714,6 +714,12 @@ int mg_galerkin_hierarchy(mg_handle h, int top_level);
  *                          measured slower)
  *     "fuse_k_pf"          register sets for the planes of x that arrive: 2 = a second set keeps x staged one step longer
  *                          (three sweeps per pass only) (1: measured no slower)
+ *     "fuse_k_load_early"  tile shape 9: 1 = the loads of the next plane go out as soon as their registers are free -- f and, off
+ *                          plan, the classes in front of the step's barrier, x of all the wave's lines in one group behind the
+ *                          first piece of phase B -- instead of in five slices between the pieces (1); 0 or 1, bit-identical;
+ *                          ignored where the launch is not of shape 9
+ *     "fuse_k_load_early_min_rows"  ... on levels with at least this many rows (536870912: 1025^3 rows gain 4 %, 513^3 rows
+ *                          measured no faster)
  *     "fuse_k_dpp"         0 = the -1 / +1 neighbours of that march come through LDS instead of the neighbouring lanes'
  *                          registers (experiment, tile 0 only: measured 1.4 x slower) (1)
  *     "fuse_k_plan"        march plans: the level's class bytes are inspected once per level, tile shape and K (which planes of

@@ -403,6 +403,8 @@ struct mg_context {
     int fuse_k_tail = 1;            // ... the tiles left over for a last, nearly empty round of workgroups get shorter plane segments
     int fuse_k_small_tiles = 0;     // ... 64 x 24 tiles (shape 4) on levels whose planes hold fewer 64 x 48 tiles than there are CUs
     int fuse_k_pf = 1;              // ... register sets for the planes of x that arrive (2: x staged a step longer, K = 3 only; measured no faster)
+    int fuse_k_load_early = 1;      // ... tile shape 9: the next plane's loads go out as soon as their registers are free (jk3_rim_body)
+    int64_t fuse_k_load_early_min_rows = (int64_t)1 << 29;     // ... on levels of at least this many rows (1025^3: -4 %; 513^3: no faster)
     int fuse_k_dpp = 1;             // ... -1 / +1 neighbours from the neighbouring lanes' registers (0: through LDS, tile 0 only)
     int fuse_k_plan = 1;            // ... march plans: steps whose planes are known to hold the main class only, or the same classes
                                     // plane after plane, load and inspect no classes (whole levels without escape rows, tile
@@ -1874,10 +1876,13 @@ int ensure_march_plan(mg_context* c, Level& L, int K, int slot) {
     return 0;
 }
 
-// (RIM: the tiles of shape 9, jk3_rim_map -- sixteen waves, the lines per wave are the map's)
-template <int K, int NW, int LPW, int M, bool DPP, int PF = 1, int WPE = (NW == 12 ? 3 : 2), int TR = 256, bool ESC = false, bool B1 = false, bool RIM = false>
+// (RIM: the tiles of shape 9, jk3_rim_map -- sixteen waves, the lines per wave are the map's; EARLY: its variant that issues
+// the next plane's loads early, "fuse_k_load_early")
+template <int K, int NW, int LPW, int M, bool DPP, int PF = 1, int WPE = (NW == 12 ? 3 : 2), int TR = 256, bool ESC = false, bool B1 = false, bool RIM = false,
+          bool EARLY = false>
 int launch_jacobikc_t(mg_context* c, JK3Args a, bool finest, const JK3Range& zr, int seglen) {
     static_assert(!RIM || (NW == jk3_rim_map<K>::NW && M == 1 && DPP && PF == 1 && WPE == 4 && !ESC && B1), "shape 9 is shape 8 with another line map");
+    static_assert(RIM || !EARLY, "only shape 9 has the variant");
     constexpr int EX = 64 * M, EY = RIM ? jk3_rim_map<K>::EY : NW * LPW, WI = EX - 2 * K, HY = EY - 2 * K + 2;
     a.ntx = (a.nx + WI - 1) / WI;
     a.nty = (a.ny + HY - 1) / HY;
@@ -1928,6 +1933,7 @@ int launch_jacobikc_t(mg_context* c, JK3Args a, bool finest, const JK3Range& zr,
     if (a.ncls > TR) return fail("more row classes than this tile shape keeps in LDS");
     void (*kern)(JK3Args) = nullptr;
     if constexpr (ESC) kern = sdia_jacobikc_escape<K, NW, LPW, M, DPP, PF, WPE, TR>;
+    else if constexpr (RIM && EARLY) kern = finest ? sdia_jacobikc_finest_rim_early<K, TR> : sdia_jacobikc_rim_early<K, TR>;
     else if constexpr (RIM) kern = finest ? sdia_jacobikc_finest_rim<K, TR> : sdia_jacobikc_rim<K, TR>;
     else if constexpr (B1) kern = finest ? sdia_jacobikc_finest_b1<K, NW, LPW, M, WPE, TR> : sdia_jacobikc_b1<K, NW, LPW, M, WPE, TR>;
     else kern = finest ? sdia_jacobikc_finest<K, NW, LPW, M, DPP, PF, WPE, TR> : sdia_jacobikc<K, NW, LPW, M, DPP, PF, WPE, TR>;
@@ -1959,8 +1965,11 @@ int launch_jacobikc_kp(mg_context* c, const JK3Args& a, bool finest, const JK3Ra
         case 7: return launch_jacobikc_t<K, 16, 2, 1, true, PF, 4>(c, a, finest, zr, seglen);                                      // 64 x 32 by 16 waves
         case 8: if constexpr (PF == 1) return launch_jacobikc_t<K, 16, 2, 1, true, 1, 4, 256, false, true>(c, a, finest, zr, seglen);  // ... one barrier per step
                 else return fail("tile shape 8 stages one plane of x (fuse_k_pf 1)");
-        case 9: if constexpr (K == 5 && PF == 1) return launch_jacobikc_t<K, 16, 2, 1, true, 1, 4, 64, false, true, true>(c, a, finest, zr, seglen);  // ... rim waves, 64 x 36
-                else return fail("tile shape 9 takes five sweeps per pass and stages one plane of x");
+        case 9: if constexpr (K == 5 && PF == 1) {                                                                                  // ... rim waves, 64 x 36
+                    if (c->fuse_k_load_early && a.P * a.nz >= c->fuse_k_load_early_min_rows)
+                        return launch_jacobikc_t<K, 16, 2, 1, true, 1, 4, 64, false, true, true, true>(c, a, finest, zr, seglen);
+                    return launch_jacobikc_t<K, 16, 2, 1, true, 1, 4, 64, false, true, true>(c, a, finest, zr, seglen);
+                } else return fail("tile shape 9 takes five sweeps per pass and stages one plane of x");
         default: return launch_jacobikc_t<K, 12, 2, 2, true, PF>(c, a, finest, zr, seglen);
     }
 }
@@ -4835,6 +4844,12 @@ int mg_set_tuning(mg_handle c, const char* key, int64_t value) {
     } else if (k == "fuse_k_pf") {
         if (value != 1 && value != 2) return fail("fuse_k_pf must be 1 or 2");
         c->fuse_k_pf = (int)value;
+    } else if (k == "fuse_k_load_early") {
+        if (value != 0 && value != 1) return fail("fuse_k_load_early must be 0 or 1");
+        c->fuse_k_load_early = (int)value;
+    } else if (k == "fuse_k_load_early_min_rows") {
+        if (value < 0) return fail("fuse_k_load_early_min_rows must be >= 0");
+        c->fuse_k_load_early_min_rows = value;
     } else if (k == "fuse_k_dpp") {
         c->fuse_k_dpp = value != 0;
     } else if (k == "fuse_k_plan") {

@@ -898,7 +898,10 @@ template <int K, int TR> constexpr size_t jk3r_lds_bytes() {
     return sizeof(double) * (TR * CLS_W + (size_t)(2 * (K - 1) * (jk3_rim_map<K>::EY + 1) + 1) * 64);
 }
 
-template <int K, int TR>
+// EARLY ("fuse_k_load_early"): false = the loads of the next plane go out in K slices, one behind each piece of phase B; true =
+// each goes out as soon as its register is free -- f and, off plan, the classes behind the ring shift in front of the barrier,
+// x of the wave's lines and of the lines below / above them in one group behind piece 1 of phase B.
+template <int K, int TR, bool EARLY = false>
 __device__ __forceinline__ void jk3_rim_body(const JK3Args& a) {
     using MAP = jk3_rim_map<K>;
     constexpr int EX = 64, NW = MAP::NW, EY = MAP::EY, NCM = MAP::NLM, WI = MAP::WI, HY = MAP::HY;
@@ -1061,6 +1064,25 @@ __device__ __forceinline__ void jk3_rim_body(const JK3Args& a) {
             fr[K - 1][l] = ldd(fb, eo[l]);
         }
         if (i == n - 1) { hS = ldd(xb, eos); hN = ldd(xb, eon); }
+    };
+    // ... the same loads by the register they need (EARLY): f of `fplane` and, off plan, the classes of `plane`; x of `plane`
+    auto load_f_classes = [&](auto kind, const int plane, const int fplane, const bool noc) __attribute__((always_inline)) {
+        constexpr int NL = decltype(kind)::NL;
+        const gcptr_t cb = sbase(clsb + (int64_t)min(max(plane, pmin), pmax) * a.P);
+        const gcptr_t fb = sbase(fb0 + (int64_t)min(max(fplane, pmin), pmax) * a.P);
+#pragma unroll
+        for (int l = 0; l < NL; ++l) {
+            if (!noc) C[l] = ldc(cb, eo[l]);
+            fr[K - 1][l] = ldd(fb, eo[l]);
+        }
+    };
+    auto load_x = [&](auto kind, const int plane) __attribute__((always_inline)) {
+        constexpr int NL = decltype(kind)::NL;
+        const gcptr_t xb = sbase(xb0 + (int64_t)min(max(plane, pmin), pmax) * a.P);
+#pragma unroll
+        for (int l = 0; l < NL; ++l) X[l] = ldd(xb, eo[l]);
+        hS = ldd(xb, eos);
+        hN = ldd(xb, eon);
     };
     auto cls_of = [&](int j, int l) -> int { return (int)((cw[j] >> (8 * l)) & 255u); };
     auto cls_now = [&](int j, int l) -> int {       // (general form: extracted anew at every use)
@@ -1292,15 +1314,22 @@ __device__ __forceinline__ void jk3_rim_body(const JK3Args& a) {
             for (int j = 0; j < K; ++j) cw[j] = cw[j + 1];
             fast >>= NL;
         }
+        if constexpr (EARLY) {  // (f's newest ring slot and the class registers are free from here on)
+            __builtin_amdgcn_sched_barrier(0);
+            load_f_classes(kind, k + K + 1, k + K, interior_step(k + 1));
+            __builtin_amdgcn_sched_barrier(0);
+        }
         __syncthreads();
-        // ---- phase B: the in-plane terms of the planes started above; the next loads go out between its pieces ----
+        // ---- phase B: the in-plane terms of the planes started above; the next loads go out between its pieces (EARLY: x
+        // behind the first, which is the last to read plane k+K's) ----
 #pragma unroll
         for (int t = 1; t <= K; ++t) {
             if (form == 0) phase_b_fast(std::false_type{}, kind, t);
             else if (form == 1) phase_b_fast(std::true_type{}, kind, t);
             else phase_b_general(kind, t);
             __builtin_amdgcn_sched_barrier(0);
-            load_slice(kind, t - 1, K, k + K + 1, k + K, interior_step(k + 1));
+            if constexpr (!EARLY) load_slice(kind, t - 1, K, k + K + 1, k + K, interior_step(k + 1));
+            else if (t == 1) load_x(kind, k + K + 1);
             __builtin_amdgcn_sched_barrier(0);
         }
     };
@@ -1326,6 +1355,17 @@ template <int K, int TR>
 __global__ __attribute__((amdgpu_flat_work_group_size(16 * WAVE, 16 * WAVE), amdgpu_waves_per_eu(4, 4)))
 void sdia_jacobikc_finest_rim(JK3Args a) {
     jk3_rim_body<K, TR>(a);
+}
+// ... with the next plane's loads issued as early as their registers are free (jk3_rim_body, EARLY)
+template <int K, int TR>
+__global__ __attribute__((amdgpu_flat_work_group_size(16 * WAVE, 16 * WAVE), amdgpu_waves_per_eu(4, 4)))
+void sdia_jacobikc_rim_early(JK3Args a) {
+    jk3_rim_body<K, TR, true>(a);
+}
+template <int K, int TR>
+__global__ __attribute__((amdgpu_flat_work_group_size(16 * WAVE, 16 * WAVE), amdgpu_waves_per_eu(4, 4)))
+void sdia_jacobikc_finest_rim_early(JK3Args a) {
+    jk3_rim_body<K, TR, true>(a);
 }
 
 // The most pool rows any tile of the march <K, NW, LPW, M> takes within K + 2 consecutive planes: one workgroup per tile

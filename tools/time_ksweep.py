@@ -4,7 +4,9 @@ next to the two-sweep pass, and whole V(50,50) cycles with and without it.
     python tools/time_ksweep.py [finest_level=7] [reps=6] ["fuse_k=4" "fuse_k=4,fuse_k_shape=1" "fuse_k=5,fuse_k_plan=0" ...]
 
 "fuse_k_shape" is reset to 7 after every setting, so a five-sweep shape is named in each: "fuse_k=5,fuse_k_shape=8"
-"fuse_k=5,fuse_k_shape=9" (rim waves) alternating is profiles/r08_ksweep_time_rim.txt.
+"fuse_k=5,fuse_k_shape=9" (rim waves) alternating is profiles/r08_ksweep_time_rim.txt.  "fuse_k_load_early" is reset to 1 likewise
+(profiles/r09_ksweep_time_early.txt: "fuse_k=5,fuse_k_shape=9,fuse_k_load_early=0" alternating with
+"fuse_k=5,fuse_k_shape=9,fuse_k_load_early=1,fuse_k_load_early_min_rows=0").
 """
 import os
 import sys
@@ -40,6 +42,7 @@ with DeviceHierarchy.synthetic(3, 2, hi, c=8, mu1=50, mu2=50) as h:
         h.set_tuning("fuse_k_dpp", 1)
         h.set_tuning("fuse_k_pf", 1)
         h.set_tuning("fuse_k_plan", 1)
+        h.set_tuning("fuse_k_load_early", 1)
     if os.environ.get("MG_SKIP_CYCLES"):
         sys.exit(0)
     for k in (0, 3, 4, 5):
