@@ -685,14 +685,14 @@ int mg_galerkin_hierarchy(mg_handle h, int top_level);
  *     "fuse_k"             Jacobi sweeps per pass of the K-sweep march (mg_jacobik3d.hip.h) on whole seven-point levels with
  *                          row classes: a smoother call of nw sweeps (multigrid.py:223-228) runs as passes of 3 .. "fuse_k"
  *                          sweeps and at most one pair (50 = 10 x 5); 0 .. 2 = pairs only (5); bit-identical to single sweeps
- *     "fuse_k_shape"       tile of that march: 0 = 128 x 24 cells (12 waves x 2 grid lines), 1 = 64 x 48 (12 waves x 4 lines),
- *                          2 = 128 x 24 (8 waves x 3 lines), 3 / 4 / 5 = 64 x 24 by 6 / 8 / 4 waves with two workgroups per CU
- *                          (levels of at most 64 row classes), 6 / 7 = 64 x 48 / 64 x 32 by 16 waves (7: no register spills up to five sweeps),
- *                          8 = 7 with one barrier per step, 9 = 8 on 64 x 36 tiles whose first and last wave own the four rim
+ *     "fuse_k_shape"       tile of that march: 1 = 64 x 48 cells (12 waves x 4 grid lines), 4 = 64 x 24 by 8 waves with two
+ *                          workgroups per CU (levels of at most 64 row classes), 7 = 64 x 32 by 16 waves (no register spills up to
+ *                          five sweeps), 8 = 7 with one barrier per step, 9 = 8 on 64 x 36 tiles whose first and last wave own the four rim
  *                          lines each (28 result lines per tile instead of 24; five sweeps per pass on whole levels without
- *                          escape rows -- a handle that asks for 9 gets 8 on slabs and 7 below five sweeps); 0..9, or -1: for
- *                          five sweeps per pass 9 on whole levels of at least "fuse_k_rim_min_rows" rows and 8 elsewhere, 7 for
- *                          three and four (-1)
+ *                          escape rows -- a handle that asks for 9 gets 8 on slabs and 7 below five sweeps); 1, 4, 7, 8, 9,
+ *                          or -1: for five sweeps per pass 9 on whole levels of at least "fuse_k_rim_min_rows" rows and 8
+ *                          elsewhere, 7 for three and four (-1).  The shapes 0, 2, 3, 5 and 6 were measured slower and retired:
+ *                          those values are refused
  *     "fuse_k_rim_min_rows"  ... (67108864: 513^3 and 1025^3 rows, where shape 9 was measured against shape 8)
  *     "fuse_k_segments"    plane segments per tile of that march, 0 = chosen by its cost model (0)
  *     "fuse_k_slab_min_rows"  ... on slabs (below): levels whose smallest slab has at least this many rows (1048576)
@@ -712,16 +712,12 @@ int mg_galerkin_hierarchy(mg_handle h, int top_level);
  *                          into shorter plane segments that fill that round once (1); bit-identical
  *     "fuse_k_small_tiles" 64 x 24 tiles (shape 4) on levels whose planes hold fewer 64 x 48 tiles than the GPU has CUs (0:
  *                          measured slower)
- *     "fuse_k_pf"          register sets for the planes of x that arrive: 2 = a second set keeps x staged one step longer
- *                          (three sweeps per pass only) (1: measured no slower)
  *     "fuse_k_load_early"  tile shape 9: 1 = the loads of the next plane go out as soon as their registers are free -- f and, off
  *                          plan, the classes in front of the step's barrier, x of all the wave's lines in one group behind the
  *                          first piece of phase B -- instead of in five slices between the pieces (1); 0 or 1, bit-identical;
  *                          ignored where the launch is not of shape 9
  *     "fuse_k_load_early_min_rows"  ... on levels with at least this many rows (536870912: 1025^3 rows gain 4 %, 513^3 rows
  *                          measured no faster)
- *     "fuse_k_dpp"         0 = the -1 / +1 neighbours of that march come through LDS instead of the neighbouring lanes'
- *                          registers (experiment, tile 0 only: measured 1.4 x slower) (1)
  *     "fuse_k_plan"        march plans: the level's class bytes are inspected once per level, tile shape and K (which planes of
  *                          which wave hold the main class only, or the classes of the plane before), and the steps of that
  *                          march that run inside such a run load and inspect no classes (1); 0 = every step does;

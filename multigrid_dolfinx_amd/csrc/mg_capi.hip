@@ -378,13 +378,13 @@ struct mg_context {
     int fuse_plain = 2;             // the pass on the stored rows (no classes): 2 = round-2 structure (sdia_jacobi2p), 1 = round 1's
     int class_sweeps = 1;           // so do the one-sweep kernels (residual, single Jacobi / Gauss-Seidel sweeps, SpMV)
     int fuse_k = 5;                 // sweeps per pass of the class-coded K-sweep march (mg_jacobik3d.hip.h): 3..5; < 3: pairs only
-    int fuse_k_shape = -1;          // ... its tile: 0 = 128 x 24 cells (12 waves x 2 lines), 1 = 64 x 48 (12 waves x 4 lines),
-                                    // 2 = 128 x 24 (8 waves x 3 lines, 256 registers), 3 .. 5 = 64 x 24 by 6 / 8 / 4 waves, two workgroups
-                                    // per CU, 6 = 64 x 48 by 16 waves, 7 = 64 x 32 by 16 waves (no spills up to five sweeps), 8 = shape 7
+    int fuse_k_shape = -1;          // ... its tile: 1 = 64 x 48 cells (12 waves x 4 lines), 4 = 64 x 24 (8 waves x 3 lines, two workgroups
+                                    // per CU), 7 = 64 x 32 by 16 waves (no spills up to five sweeps), 8 = shape 7
                                     // with one barrier per step (level 0 in registers, images double-buffered), 9 = shape 8 on 64 x 36
                                     // tiles whose first and last wave own the four rim lines (five sweeps on whole levels; elsewhere
                                     // it stands for 8, for 7 below five sweeps); -1: for five sweeps per pass 9 on whole levels of at
-                                    // least "fuse_k_rim_min_rows" rows and 8 elsewhere, 7 for three and four (jk3_shape_for)
+                                    // least "fuse_k_rim_min_rows" rows and 8 elsewhere, 7 for three and four (jk3_shape_for).  The
+                                    // shapes 0, 2, 3, 5 and 6 were measured slower and retired ("Tile shape")
     int64_t fuse_k_rim_min_rows = (int64_t)1 << 26;    // ... (513^3 and 1025^3 rows: where shape 9 was measured against shape 8)
     int fuse_k_segments = 0;        // ... plane segments per tile (0: chosen from the item count)
     int timing_force_form = -1;     // mg_time_kernel("jacobik3:formN"): every step of the K-sweep pass in one form (wrong results; how fast
@@ -402,10 +402,8 @@ struct mg_context {
     int fuse_k_min_side = 32;       // ... the shortest grid lines / fewest lines per plane of a whole level that pass takes (tests: 16)
     int fuse_k_tail = 1;            // ... the tiles left over for a last, nearly empty round of workgroups get shorter plane segments
     int fuse_k_small_tiles = 0;     // ... 64 x 24 tiles (shape 4) on levels whose planes hold fewer 64 x 48 tiles than there are CUs
-    int fuse_k_pf = 1;              // ... register sets for the planes of x that arrive (2: x staged a step longer, K = 3 only; measured no faster)
     int fuse_k_load_early = 1;      // ... tile shape 9: the next plane's loads go out as soon as their registers are free (jk3_rim_body)
     int64_t fuse_k_load_early_min_rows = (int64_t)1 << 29;     // ... on levels of at least this many rows (1025^3: -4 %; 513^3: no faster)
-    int fuse_k_dpp = 1;             // ... -1 / +1 neighbours from the neighbouring lanes' registers (0: through LDS, tile 0 only)
     int fuse_k_plan = 1;            // ... march plans: steps whose planes are known to hold the main class only, or the same classes
                                     // plane after plane, load and inspect no classes (whole levels without escape rows, tile
                                     // shapes 7 and 8; 0: every step does)
@@ -1794,7 +1792,7 @@ int escape_window_k(mg_context* c, const Level& L, const unsigned char* cls, int
     a.ntx = (a.nx + WI - 1) / WI; a.nty = (a.ny + HY - 1) / HY;
     a.most = reinterpret_cast<unsigned*>(c->partials.get());
     HIP_TRY(hipMemsetAsync(a.most, 0, sizeof(unsigned), c->stream));
-    hipLaunchKernelGGL((jk3_escape_window<K, 16, 2, 1>), dim3((unsigned)(a.ntx * a.nty)), dim3(256), 0, c->stream, a);
+    hipLaunchKernelGGL((jk3_escape_window<K, 16, 2>), dim3((unsigned)(a.ntx * a.nty)), dim3(256), 0, c->stream, a);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(most, a.most, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -1843,7 +1841,7 @@ int jk3_shape_for(const mg_context* c, int K, int ncls, bool whole, int64_t rows
 // and escape rows are what the class loads are there to find.
 constexpr int MARCH_PLAN_SLOT_RIM = 6;
 int march_plan_slot(const mg_context* c, const Level& L, int K) {
-    if (!c->fuse_k_plan || !c->fuse_k_dpp || K < 3 || K > 5 || !L.cls || L.cls_escape || is_slab(c, L)) return -1;
+    if (!c->fuse_k_plan || K < 3 || K > 5 || !L.cls || L.cls_escape || is_slab(c, L)) return -1;
     const int shape = jk3_shape_for(c, K, L.ncls, true, L.nloc);
     if (shape == 9) return MARCH_PLAN_SLOT_RIM;
     return shape == 7 || shape == 8 ? (K - 3) * 2 + (shape - 7) : -1;
@@ -1863,7 +1861,7 @@ int ensure_march_plan(mg_context* c, Level& L, int K, int slot) {
     MG_TRY(iv.alloc(c, n));
     a.plan = iv;
     if (rim) hipLaunchKernelGGL((jk3_plan_rim<5>), dim3((unsigned)(a.ntx * a.nty)), dim3(16 * WAVE), 0, c->stream, a);
-    else with_int<3, 4, 5>(K, [&](auto k) { hipLaunchKernelGGL((jk3_plan<decltype(k)::value, 16, 2, 1>), dim3((unsigned)(a.ntx * a.nty)), dim3(16 * WAVE), 0, c->stream, a); });
+    else with_int<3, 4, 5>(K, [&](auto k) { hipLaunchKernelGGL((jk3_plan<decltype(k)::value, 16, 2>), dim3((unsigned)(a.ntx * a.nty)), dim3(16 * WAVE), 0, c->stream, a); });
     HIP_TRY(hipGetLastError());
     std::vector<int> h(n);
     HIP_TRY(hipMemcpyAsync(h.data(), iv, n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
@@ -1878,16 +1876,15 @@ int ensure_march_plan(mg_context* c, Level& L, int K, int slot) {
 
 // (RIM: the tiles of shape 9, jk3_rim_map -- sixteen waves, the lines per wave are the map's; EARLY: its variant that issues
 // the next plane's loads early, "fuse_k_load_early")
-template <int K, int NW, int LPW, int M, bool DPP, int PF = 1, int WPE = (NW == 12 ? 3 : 2), int TR = 256, bool ESC = false, bool B1 = false, bool RIM = false,
-          bool EARLY = false>
+template <int K, int NW, int LPW, int WPE = (NW == 12 ? 3 : 2), int TR = 256, bool ESC = false, bool B1 = false, bool RIM = false, bool EARLY = false>
 int launch_jacobikc_t(mg_context* c, JK3Args a, bool finest, const JK3Range& zr, int seglen) {
-    static_assert(!RIM || (NW == jk3_rim_map<K>::NW && M == 1 && DPP && PF == 1 && WPE == 4 && !ESC && B1), "shape 9 is shape 8 with another line map");
+    static_assert(!RIM || (NW == jk3_rim_map<K>::NW && WPE == 4 && !ESC && B1), "shape 9 is shape 8 with another line map");
     static_assert(RIM || !EARLY, "only shape 9 has the variant");
-    constexpr int EX = 64 * M, EY = RIM ? jk3_rim_map<K>::EY : NW * LPW, WI = EX - 2 * K, HY = EY - 2 * K + 2;
+    constexpr int EX = 64, EY = RIM ? jk3_rim_map<K>::EY : NW * LPW, WI = EX - 2 * K, HY = EY - 2 * K + 2;
     a.ntx = (a.nx + WI - 1) / WI;
     a.nty = (a.ny + HY - 1) / HY;
     const int64_t ntile = (int64_t)a.ntx * a.nty;
-    constexpr size_t lds = RIM ? jk3r_lds_bytes<K, TR>() : B1 ? jk3b_lds_bytes<K, NW, LPW, M, TR>() : jk3_lds_bytes<K, NW, LPW, M, TR, ESC>();
+    constexpr size_t lds = RIM ? jk3r_lds_bytes<K, TR>() : B1 ? jk3b_lds_bytes<K, NW, LPW, TR>() : jk3_lds_bytes<K, NW, LPW, TR, ESC>();
     static_assert(lds <= 160 * 1024, "one CU's LDS");
     a.za0 = zr.za0; a.za1 = zr.za1; a.zb0 = zr.zb0; a.zb1 = zr.zb1;
     const int planes = std::max(0, zr.za1 - zr.za0) + std::max(0, zr.zb1 - zr.zb0);
@@ -1932,11 +1929,11 @@ int launch_jacobikc_t(mg_context* c, JK3Args a, bool finest, const JK3Range& zr,
     a.nitems = (unsigned)items;
     if (a.ncls > TR) return fail("more row classes than this tile shape keeps in LDS");
     void (*kern)(JK3Args) = nullptr;
-    if constexpr (ESC) kern = sdia_jacobikc_escape<K, NW, LPW, M, DPP, PF, WPE, TR>;
+    if constexpr (ESC) kern = sdia_jacobikc_escape<K, NW, LPW, WPE, TR>;
     else if constexpr (RIM && EARLY) kern = finest ? sdia_jacobikc_finest_rim_early<K, TR> : sdia_jacobikc_rim_early<K, TR>;
     else if constexpr (RIM) kern = finest ? sdia_jacobikc_finest_rim<K, TR> : sdia_jacobikc_rim<K, TR>;
-    else if constexpr (B1) kern = finest ? sdia_jacobikc_finest_b1<K, NW, LPW, M, WPE, TR> : sdia_jacobikc_b1<K, NW, LPW, M, WPE, TR>;
-    else kern = finest ? sdia_jacobikc_finest<K, NW, LPW, M, DPP, PF, WPE, TR> : sdia_jacobikc<K, NW, LPW, M, DPP, PF, WPE, TR>;
+    else if constexpr (B1) kern = finest ? sdia_jacobikc_finest_b1<K, NW, LPW, WPE, TR> : sdia_jacobikc_b1<K, NW, LPW, WPE, TR>;
+    else kern = finest ? sdia_jacobikc_finest<K, NW, LPW, WPE, TR> : sdia_jacobikc<K, NW, LPW, WPE, TR>;
     MG_TRY(allow_large_lds(c, reinterpret_cast<const void*>(kern), lds));
     hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * WAVE), lds, c->stream, a);
     HIP_TRY(hipGetLastError());
@@ -1944,50 +1941,39 @@ int launch_jacobikc_t(mg_context* c, JK3Args a, bool finest, const JK3Range& zr,
     return 0;
 }
 
-template <int K, int PF>
-int launch_jacobikc_kp(mg_context* c, const JK3Args& a, bool finest, const JK3Range& zr, int seglen, bool whole) {
-    if (!c->fuse_k_dpp) return launch_jacobikc_t<K, 12, 2, 2, false, PF>(c, a, finest, zr, seglen);     // (experiment: -1 / +1 neighbours through LDS)
-    // shapes 3..5: 64 x 24 tiles, two workgroups per CU (class table of 64 rows); levels with more classes take shape 1
-    int shape = jk3_shape_for(c, K, a.ncls, whole, a.P * a.nz);
-    // planes with fewer 64 x 48 tiles than the GPU has CUs (the 513^2 and 257^2 planes of a slab's coarser levels): half
-    // as tall tiles, two workgroups per CU
-    if (shape == 1 && a.ncls <= 64 && K <= 4 && c->fuse_k_small_tiles) {
-        constexpr int WI = 64 - 2 * K, HY = 48 - 2 * K + 2;
-        if ((int64_t)((a.nx + WI - 1) / WI) * ((a.ny + HY - 1) / HY) < std::max(1, c->prop.multiProcessorCount)) shape = 4;
-    }
-    switch (shape) {
-        case 1: return launch_jacobikc_t<K, 12, 4, 1, true, PF>(c, a, finest, zr, seglen);
-        case 2: return launch_jacobikc_t<K, 8, 3, 2, true, PF>(c, a, finest, zr, seglen);
-        case 3: return launch_jacobikc_t<K, 6, 4, 1, true, PF, 3, 64>(c, a, finest, zr, seglen);
-        case 4: return launch_jacobikc_t<K, 8, 3, 1, true, PF, 4, 64>(c, a, finest, zr, seglen);
-        case 5: if constexpr (K <= 4) return launch_jacobikc_t<K, 4, 6, 1, true, PF, 2, 64>(c, a, finest, zr, seglen);
-        case 6: if constexpr (K <= 4 && PF == 1) return launch_jacobikc_t<K, 16, 3, 1, true, 1, 4>(c, a, finest, zr, seglen);      // 64 x 48 by 16 waves
-        case 7: return launch_jacobikc_t<K, 16, 2, 1, true, PF, 4>(c, a, finest, zr, seglen);                                      // 64 x 32 by 16 waves
-        case 8: if constexpr (PF == 1) return launch_jacobikc_t<K, 16, 2, 1, true, 1, 4, 256, false, true>(c, a, finest, zr, seglen);  // ... one barrier per step
-                else return fail("tile shape 8 stages one plane of x (fuse_k_pf 1)");
-        case 9: if constexpr (K == 5 && PF == 1) {                                                                                  // ... rim waves, 64 x 36
-                    if (c->fuse_k_load_early && a.P * a.nz >= c->fuse_k_load_early_min_rows)
-                        return launch_jacobikc_t<K, 16, 2, 1, true, 1, 4, 64, false, true, true, true>(c, a, finest, zr, seglen);
-                    return launch_jacobikc_t<K, 16, 2, 1, true, 1, 4, 64, false, true, true>(c, a, finest, zr, seglen);
-                } else return fail("tile shape 9 takes five sweeps per pass and stages one plane of x");
-        default: return launch_jacobikc_t<K, 12, 2, 2, true, PF>(c, a, finest, zr, seglen);
-    }
-}
-
 template <int K>
 int launch_jacobikc_k(mg_context* c, const JK3Args& a, bool finest, const JK3Range& zr, int seglen, bool whole) {
     // levels with rows of class CLS_ESCAPE: the variant that fetches them, one tile shape (the one escape_window() checked)
     if (a.escape) {
-        if constexpr (K >= 3) return launch_jacobikc_t<K, 16, 2, 1, true, 1, 4, 256, true>(c, a, finest, zr, seglen);
+        if constexpr (K >= 3) return launch_jacobikc_t<K, 16, 2, 4, 256, true>(c, a, finest, zr, seglen);
         else return fail("levels with escape rows take three to five sweeps per pass");
     }
-    // a second plane of x staged in registers ("fuse_k_pf" 2) fits the register budget with three sweeps only
-    if constexpr (K == 3 || K == 4) {
-        if (c->fuse_k_pf == 2 && (K == 3 || jk3_shape(c, K) == 7)) return launch_jacobikc_kp<K, 2>(c, a, finest, zr, seglen, whole);
-    }
     // (two sweeps per pass: slabs only, where a pass also saves an exchange; one tile shape)
-    if constexpr (K == 2) return launch_jacobikc_t<K, 12, 4, 1, true, 1>(c, a, finest, zr, seglen);
-    else return launch_jacobikc_kp<K, 1>(c, a, finest, zr, seglen, whole);
+    if constexpr (K == 2) {
+        return launch_jacobikc_t<K, 12, 4>(c, a, finest, zr, seglen);
+    } else {
+        // shape 4 and shapes 7 to 9 keep 64 rows of the class table in LDS or run one workgroup of 16 waves per CU; levels with
+        // more classes take shape 1
+        int shape = jk3_shape_for(c, K, a.ncls, whole, a.P * a.nz);
+        // planes with fewer 64 x 48 tiles than the GPU has CUs (the 513^2 and 257^2 planes of a slab's coarser levels): half
+        // as tall tiles, two workgroups per CU
+        if (shape == 1 && a.ncls <= 64 && K <= 4 && c->fuse_k_small_tiles) {
+            constexpr int WI = 64 - 2 * K, HY = 48 - 2 * K + 2;
+            if ((int64_t)((a.nx + WI - 1) / WI) * ((a.ny + HY - 1) / HY) < std::max(1, c->prop.multiProcessorCount)) shape = 4;
+        }
+        switch (shape) {
+            case 1: return launch_jacobikc_t<K, 12, 4>(c, a, finest, zr, seglen);                           // 64 x 48 by 12 waves
+            case 4: return launch_jacobikc_t<K, 8, 3, 4, 64>(c, a, finest, zr, seglen);                     // 64 x 24 by 8 waves, two workgroups per CU
+            case 7: return launch_jacobikc_t<K, 16, 2, 4>(c, a, finest, zr, seglen);                        // 64 x 32 by 16 waves
+            case 8: return launch_jacobikc_t<K, 16, 2, 4, 256, false, true>(c, a, finest, zr, seglen);      // ... one barrier per step
+            case 9: if constexpr (K == 5) {                                                                 // ... rim waves, 64 x 36
+                        if (c->fuse_k_load_early && a.P * a.nz >= c->fuse_k_load_early_min_rows)
+                            return launch_jacobikc_t<K, 16, 2, 4, 64, false, true, true, true>(c, a, finest, zr, seglen);
+                        return launch_jacobikc_t<K, 16, 2, 4, 64, false, true, true>(c, a, finest, zr, seglen);
+                    } else return fail("tile shape 9 takes five sweeps per pass");
+            default: return fail("no such tile shape");
+        }
+    }
 }
 
 // out = K Jacobi sweeps applied to x (2 <= K <= 5) on the owned planes [zr) of the level (null: all of them); on slabs the
@@ -4814,7 +4800,8 @@ int mg_set_tuning(mg_handle c, const char* key, int64_t value) {
         if (value < 0 || value > 5) return fail("fuse_k must be in 0..5 (below 3: pairs of sweeps only)");
         c->fuse_k = (int)value;
     } else if (k == "fuse_k_shape") {
-        if (value < -1 || value > 9) return fail("fuse_k_shape must be 0..9, or -1 (by sweeps per pass)");
+        if (value == 0 || value == 2 || value == 3 || value == 5 || value == 6) return fail("fuse_k_shape: the tile shapes 0, 2, 3, 5 and 6 were retired");
+        if (value != -1 && value != 1 && value != 4 && (value < 7 || value > 9)) return fail("fuse_k_shape must be 1, 4, 7, 8 or 9, or -1 (by sweeps per pass)");
         c->fuse_k_shape = (int)value;
     } else if (k == "fuse_k_slab_min_rows") {
         c->fuse_k_slab_min_rows = value;
@@ -4841,17 +4828,12 @@ int mg_set_tuning(mg_handle c, const char* key, int64_t value) {
         c->fuse_k_tail = (int)value;            // (> 1: the number of resident workgroups to plan for -- tests)
     } else if (k == "fuse_k_small_tiles") {
         c->fuse_k_small_tiles = value != 0;
-    } else if (k == "fuse_k_pf") {
-        if (value != 1 && value != 2) return fail("fuse_k_pf must be 1 or 2");
-        c->fuse_k_pf = (int)value;
     } else if (k == "fuse_k_load_early") {
         if (value != 0 && value != 1) return fail("fuse_k_load_early must be 0 or 1");
         c->fuse_k_load_early = (int)value;
     } else if (k == "fuse_k_load_early_min_rows") {
         if (value < 0) return fail("fuse_k_load_early_min_rows must be >= 0");
         c->fuse_k_load_early_min_rows = value;
-    } else if (k == "fuse_k_dpp") {
-        c->fuse_k_dpp = value != 0;
     } else if (k == "fuse_k_plan") {
         c->fuse_k_plan = value != 0;
     } else if (k == "fuse_k_segments") {

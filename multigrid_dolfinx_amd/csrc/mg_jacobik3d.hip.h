@@ -18,8 +18,8 @@
 //   barrier
 //   phase B  the in-plane terms (-nx, -1, 0, +1, +nx) of the planes started in phase A.  A thread reads its own cells'
 //            values back from the images and the line below / above its lines; the -1 / +1 neighbours are its own
-//            values of the neighbouring lanes (DPP wave rotates; the lane at a 64-cell seam takes the rotated value of
-//            the cell next door), the +-nx neighbours between a thread's own lines are its own registers.
+//            values of the neighbouring lanes (DPP wave rotates: a tile line is the 64 lanes of one wave), the +-nx
+//            neighbours between a thread's own lines are its own registers.
 //   barrier
 // so per cell and level there are K partial sums in registers and ONE plane image in LDS -- K (EY+2) x EX images in
 // all --, not three planes of every level, and per cell, level and step the LDS sees one write and three reads.  f is
@@ -36,6 +36,15 @@
 // bit-identical to K single sweeps.  Out-of-grid cells that the tile clamps (lines beyond ny + 1 or below -2, cells
 // past the end of a grid line) hold finite, wrong values; they reach grid rows only through couplings that do not
 // exist (stored zeros), so no result depends on them.
+//
+// Tile shapes ("fuse_k_shape"; all are 64 cells wide, a wave owns LPW whole lines and a thread NC = LPW cells, one per line):
+//   1  64 x 48, 12 waves x 4 lines          jk3_body<K, 12, 4>       also levels of more than 64 classes, and K = 2 on slabs
+//   4  64 x 24,  8 waves x 3 lines          jk3_body<K, 8, 3>        two workgroups per CU, 64 table rows ("fuse_k_small_tiles")
+//   7  64 x 32, 16 waves x 2 lines          jk3_body<K, 16, 2>       three and four sweeps per pass; with ESC, levels with escape rows
+//   8  shape 7 with one barrier per step    jk3_body<K, 16, 2, .., B1>   five sweeps per pass; slabs
+//   9  64 x 36, rim waves                   jk3_rim_body<5>          five sweeps per pass on the large whole levels
+// (128-cell lines, -1 / +1 neighbours through LDS, a second register set for the arriving plane and the 64 x 24 / 64 x 48
+// tiles by 4, 6 and 16 waves were measured slower and are gone: DESIGN.md, "Tile shape".)
 //
 // Slabs: with K halo planes of x (and K - 1 of f and the classes) on either side a rank relaxes level t on the planes
 // [-(K-t), nz + (K-t)) of its neighbours too (plo / phi), so K sweeps need ONE exchange and no boundary chain.
@@ -98,8 +107,8 @@ __device__ __forceinline__ const unsigned char* jk3_class_base(const unsigned ch
 constexpr int jk3_pool(int K) { return K >= 5 ? 512 : 1024; }
 
 // (TR: rows of the class table kept in LDS -- 256, or 64 for the shapes that run two workgroups per CU)
-template <int K, int NW, int LPW, int M, int TR> constexpr size_t jk3_lds_doubles() {
-    return TR * CLS_W + (size_t)K * (NW * LPW + 2) * (64 * M) + 2 * (64 * M + 2);
+template <int K, int NW, int LPW, int TR> constexpr size_t jk3_lds_doubles() {
+    return TR * CLS_W + (size_t)K * (NW * LPW + 2) * 64 + 2 * (64 + 2);
 }
 // One barrier per step (tile shape 8, `B1`): level 0 is not kept in LDS at all -- a wave has x of its own lines in registers
 // and loads the line above and the line below them too (lines its neighbour waves load in the same step: they come from
@@ -109,15 +118,15 @@ template <int K, int NW, int LPW, int M, int TR> constexpr size_t jk3_lds_double
 // B(k + 1) lies between them.  Images of EY lines, stride EY + 1: the zero lines between them (and before the first) are
 // the line below and above the tile of every level >= 1 (those rows were always outside the level's valid region).
 //   [zero] [level 1, parity 0] [zero] [level 2, parity 0] [zero] ... [level K-1, parity 1] [zero]
-template <int K, int NW, int LPW, int M, int TR> constexpr size_t jk3b_lds_doubles() {
-    return TR * CLS_W + (size_t)(2 * (K - 1) * (NW * LPW + 1) + 1) * (64 * M);
+template <int K, int NW, int LPW, int TR> constexpr size_t jk3b_lds_doubles() {
+    return TR * CLS_W + (size_t)(2 * (K - 1) * (NW * LPW + 1) + 1) * 64;
 }
-template <int K, int NW, int LPW, int M, int TR> constexpr size_t jk3b_lds_bytes() {
-    return sizeof(double) * jk3b_lds_doubles<K, NW, LPW, M, TR>();
+template <int K, int NW, int LPW, int TR> constexpr size_t jk3b_lds_bytes() {
+    return sizeof(double) * jk3b_lds_doubles<K, NW, LPW, TR>();
 }
 
-template <int K, int NW, int LPW, int M, int TR, bool ESC = false> constexpr size_t jk3_lds_bytes() {
-    constexpr size_t base = jk3_lds_doubles<K, NW, LPW, M, TR>();
+template <int K, int NW, int LPW, int TR, bool ESC = false> constexpr size_t jk3_lds_bytes() {
+    constexpr size_t base = jk3_lds_doubles<K, NW, LPW, TR>();
     return sizeof(double) * (ESC ? (base + CLS_W - 1) / CLS_W * CLS_W + (size_t)(jk3_pool(K) + 1) * CLS_W : base);
 }
 
@@ -136,21 +145,20 @@ template <int K, int EY, int E0> struct jk3_caps {
     }
 };
 
-template <int K, int NW, int LPW, int M, bool DPP, int PF, int TR, bool ESC = false, bool B1 = false>
+template <int K, int NW, int LPW, int TR, bool ESC = false, bool B1 = false>
 __device__ __forceinline__ void jk3_body(const JK3Args& a) {
-    constexpr int EX = 64 * M, EY = NW * LPW, NC = M * LPW, IMG = (EY + 2) * EX;
+    constexpr int EX = 64, EY = NW * LPW, NC = LPW, IMG = (EY + 2) * EX;
     // (B1) image stride and parity stride, in doubles
     constexpr int IS = (EY + 1) * EX, PS = (K - 1) * IS;
-    static_assert(!B1 || (DPP && PF == 1 && !ESC), "one barrier per step: DPP neighbours, one plane of x in flight, no escape rows");
+    static_assert(!B1 || !ESC, "one barrier per step: no escape rows");
     // classes in the ring: a byte per cell, four cells to a register -- sixteen bits where pool rows are classes too
     constexpr int CBITS = ESC ? 16 : 8, CPR = 32 / CBITS, CW = (NC + CPR - 1) / CPR;
     constexpr unsigned CMASK = (1u << CBITS) - 1u;
-    constexpr int DYN0 = (int)((jk3_lds_doubles<K, NW, LPW, M, TR>() + CLS_W - 1) / CLS_W);   // the pool's first row, counted from sT
+    constexpr int DYN0 = (int)((jk3_lds_doubles<K, NW, LPW, TR>() + CLS_W - 1) / CLS_W);   // the pool's first row, counted from sT
     static_assert(CLS_W == 8, "table rows of eight doubles");
     constexpr int WI = EX - 2 * K, HY = EY - 2 * K + 2;       // cells per line / lines of a tile that get all K sweeps
     static_assert(NC * (K + 1) <= 64, "the fast-path flags live in one scalar register pair");
     static_assert(WI > 0 && HY > 0, "tile too small for K sweeps");
-    static_assert(PF == 1 || PF == 2, "planes of x in flight");
     extern __shared__ double j2_smem[];
     double* const sT = j2_smem;                               // 256 x 8   entries of the row classes, [7] = omega / diagonal
     double* const sI = sT + TR * CLS_W + (EX + 2);           // K x (EY+2) x EX   one plane of level t, origin (0,-1)
@@ -206,10 +214,10 @@ __device__ __forceinline__ void jk3_body(const JK3Args& a) {
     const double mcf = a.omega * (1.0 / (m3 != 0.0 ? m3 : 1.0));
     const int cmain = a.cmain;
 
-    // cell c = l*M + r of this thread: ex = lane + 64 r, ey = wave*LPW + l
+    // cell c of this thread: ex = lane, ey = wave*LPW + c
     const int ey0 = wave * LPW;
     const int lw0 = (ey0 + 1) * EX + lane;
-    auto lwof = [&](int c) -> int { return (c / M) * EX + 64 * (c % M); };      // cell c relative to cell 0
+    auto lwof = [&](int c) -> int { return c * EX; };      // cell c relative to cell 0
     // cell 0 in the images 0, 1 / 2, 3 / 4: one address register per pair, so that every LDS access of the march is
     // `register + 16-bit immediate` (the images span more than 64 KB; left alone the compiler keeps an address per
     // cell and image)
@@ -225,15 +233,15 @@ __device__ __forceinline__ void jk3_body(const JK3Args& a) {
     int bcur = 0, bprev = 0;
     auto limg = [&](int base, int t) -> double* { return j2_smem + base + (t - 1) * IS + EX; };
     double XP[B1 ? NC : 1];     // (B1) x of the plane before the newest, own cells: the value level 1 relaxes
-    double hS[M], hN[M];        // (B1) x of the line below / above this wave's lines, of the newest plane
+    double hS, hN;              // (B1) x of the line below / above this wave's lines, of the newest plane
     unsigned inT = 0;           // bit c: this lane's cell c gets all K sweeps and lies on the grid
     const int64_t rb0 = (int64_t)(ty0 + ey0) * a.nx + (tx0 + lane);
-    auto rowof = [&](int c) -> int64_t { return rb0 + (int64_t)(c / M) * a.nx + 64 * (c % M); };
+    auto rowof = [&](int c) -> int64_t { return rb0 + (int64_t)c * a.nx; };
     // the row of cell c in plane p exists  <=>  the level's plane range holds p + sh(c), sh = -1, 0, +1 (two bits per cell)
     unsigned shw = 0;
 #pragma unroll
     for (int c = 0; c < NC; ++c) {
-        const int ex = lane + 64 * (c % M), ey = ey0 + c / M;
+        const int ex = lane, ey = ey0 + c;
         if (ex >= K && ex < EX - K && ey >= K - 1 && ey <= EY - K && tx0 + ex < a.nx && ty0 + ey < a.ny) inT |= 1u << c;
         const int64_t r = rowof(c);
         shw |= (r < 0 ? 0u : (r >= a.P ? 2u : 1u)) << (2 * c);
@@ -244,15 +252,15 @@ __device__ __forceinline__ void jk3_body(const JK3Args& a) {
     unsigned standin = 0;
 #pragma unroll
     for (int c = 0; c < NC; ++c) {
-        const int line = ty0 + ey0 + c / M;
-        if (lane + 64 * (c % M) > a.nx + 1 - tx0 || line < -2 || line > a.ny + 1) standin |= 1u << c;
+        const int line = ty0 + ey0 + c;
+        if (lane > a.nx + 1 - tx0 || line < -2 || line > a.ny + 1) standin |= 1u << c;
     }
     const bool wlo = wave == 0, whi = wave == NW - 1;
     // Level caps (jk3_caps) on the 64 x 32 tiles of sixteen waves, two lines each (tile shapes 7 and 8): the first two and the
     // last two waves have lines with a cap below K (K = 3: the first and the last).  A cell with cap m < K computes the levels
     // 1 .. m, still hands its level-m value to the image -- the line next to it, whose cap is m + 1, reads it as its -nx / +nx
     // term -- and does nothing above: those partial sums and image slots keep their zeros and nothing reads them.
-    constexpr bool CAPS = B1 && NW == 16 && LPW == 2 && M == 1 && K >= 3;
+    constexpr bool CAPS = B1 && NW == 16 && LPW == 2 && K >= 3;
     using caps_all = jk3_caps<K, EY, -1>;
     using caps_w0 = jk3_caps<K, EY, 0>;
     using caps_w1 = jk3_caps<K, EY, LPW>;
@@ -280,7 +288,7 @@ __device__ __forceinline__ void jk3_body(const JK3Args& a) {
     //  keeps the compiler from holding every comparison's outcome in a register pair for the whole march)
     auto cap_of = [&](int c) -> int {
         if constexpr (!CAPS) return K;
-        const int ey = ey0 + c / M;
+        const int ey = ey0 + c;
         int cap = min(min(ey + 1, EY - ey), K);
         asm volatile("" : "+v"(cap));
         return __builtin_amdgcn_readfirstlane(cap);
@@ -290,20 +298,16 @@ __device__ __forceinline__ void jk3_body(const JK3Args& a) {
     // clamped to [-2, ny + 1], cells past the end of their grid line to the cell behind it, planes to the slack planes.
     const int bias = 2 * a.nx + K + 2;
     const int xcl = a.nx + 1 - tx0;
-    unsigned eo[NC], eor[M];    // byte offsets of the cells' doubles (>> 3: of their class bytes)
+    unsigned eo[NC];            // byte offsets of the cells' doubles (>> 3: of their class bytes)
 #pragma unroll
-    for (int c = 0; c < NC; ++c)
-        eo[c] = jk3_cell_offset(ty0 + ey0 + c / M, lane + 64 * (c % M), a.nx, a.ny, tx0, xcl, bias);
-#pragma unroll
-    for (int r = 0; r < M; ++r)
-        eor[r] = 8u * (unsigned)((wlo ? max(ty0 - 1, -2) : min(ty0 + EY, a.ny + 1)) * a.nx + tx0 + min(lane + 64 * r, xcl) + bias);
-    unsigned eos[B1 ? M : 1], eon[B1 ? M : 1];      // (B1) the lines below / above the wave's, clamped like `eo`
+    for (int c = 0; c < NC; ++c) eo[c] = jk3_cell_offset(ty0 + ey0 + c, lane, a.nx, a.ny, tx0, xcl, bias);
+    // ... of the line above the tile (the last wave loads it) / below it (the first wave)
+    const int above = min(ty0 + EY, a.ny + 1), below = max(ty0 - 1, -2);
+    const unsigned eor = 8u * (unsigned)(bias + tx0 + min(lane, xcl) + (wlo ? below : above) * a.nx);
+    unsigned eos = 0, eon = 0;  // (B1) the lines below / above the wave's, clamped like `eo`
     if constexpr (B1) {
-#pragma unroll
-        for (int r = 0; r < M; ++r) {
-            eos[r] = jk3_cell_offset(ty0 + ey0 - 1, lane + 64 * r, a.nx, a.ny, tx0, xcl, bias);
-            eon[r] = jk3_cell_offset(ty0 + ey0 + LPW, lane + 64 * r, a.nx, a.ny, tx0, xcl, bias);
-        }
+        eos = jk3_cell_offset(ty0 + ey0 - 1, lane, a.nx, a.ny, tx0, xcl, bias);
+        eon = jk3_cell_offset(ty0 + ey0 + LPW, lane, a.nx, a.ny, tx0, xcl, bias);
     }
     const unsigned char* const clsb = jk3_class_base(a.cls, a.clead, bias);
     const double* const xb0 = a.x - bias;
@@ -342,12 +346,12 @@ __device__ __forceinline__ void jk3_body(const JK3Args& a) {
     //   [klo, khi) = [max(r0, 1, z0 - K), min(r1 - K, nz - K - 1))
     // are steps to which today's test gives form 0 (run p) or, since a constant class that is not cmain everywhere fails
     // the form-0 test, form 1 (run q), known without looking at a class: they load no classes, move no ring and decide
-    // nothing.  A segment uses the run that gives it more such steps.  Step k's loads bring the plane that step k + PF
+    // nothing.  A segment uses the run that gives it more such steps.  Step k's loads bring the plane that step k + 1
     // consumes, so the class loads stop with the loads for step klo and resume with those for step khi.  Step klo - 1
     // exists and is an ordinary one; it leaves the classes of the plane klo in cw[0], where form 1 reads them and where
     // they stay.  In step khi the ring's planes khi .. khi+K-1 (all below r1) get those classes and their flags, as
     // today's path would hold them, and the plane khi + K arrives from memory.
-    constexpr bool PLANNED = !ESC && NW == 16 && LPW == 2 && M == 1 && K >= 3;    // tile shapes 7 and 8
+    constexpr bool PLANNED = !ESC && NW == 16 && LPW == 2 && K >= 3;    // tile shapes 7 and 8
     int klo = 0x7fffffff, khi = 0x7fffffff, kform = 0;
     if constexpr (PLANNED) {
         if (a.plan) {
@@ -370,10 +374,9 @@ __device__ __forceinline__ void jk3_body(const JK3Args& a) {
 
     // registers per cell: K partial sums; f of the planes k .. k+K-1; x, f and the class of the plane that arrives
     double acc[K][NC], fr[K][NC];
-    // x, the classes and the y ring of x of the planes that arrive: PF sets, taken in turn by successive steps
-    double XA[NC], XB[PF == 2 ? NC : 1], hyA[M], hyB[PF == 2 ? M : 1];
-    int CA[NC], CB[PF == 2 ? NC : 1];
-    double FN[PF == 2 ? NC : 1];            // (PF = 2) f of the plane after the newest of the ring, staged like x
+    // x and the classes of the plane that arrives, own cells; (first / last wave) x of the line below / above the tile
+    double X[NC], hy = 0.0;
+    int C[NC];
     unsigned cw[K + 1][CW];     // class bytes of the planes k .. k+K, four cells to a register
     unsigned long long fast = 0;        // wave-uniform; bit j*NC + c: all 64 cells c of plane k+j are of class cmain
     constexpr unsigned long long ALLFAST = (NC * (K + 1) == 64) ? ~0ull : ((1ull << (NC * (K + 1))) - 1ull);
@@ -381,27 +384,24 @@ __device__ __forceinline__ void jk3_body(const JK3Args& a) {
     for (int c = 0; c < NC; ++c) {
 #pragma unroll
         for (int t = 0; t < K; ++t) acc[t][c] = fr[t][c] = 0.0;
-        XA[c] = 0.0;
-        CA[c] = 0;
+        X[c] = 0.0;
+        C[c] = 0;
     }
 #pragma unroll
     for (int j = 0; j <= K; ++j)
 #pragma unroll
         for (int q = 0; q < CW; ++q) cw[j][q] = 0u;
-#pragma unroll
-    for (int r = 0; r < M; ++r) hyA[r] = hS[r] = hN[r] = 0.0;
-    XB[0] = 0.0; hyB[0] = 0.0; CB[0] = 0; FN[0] = 0.0;
+    hS = hN = 0.0;
 #pragma unroll
     for (int c = 0; c < (B1 ? NC : 1); ++c) XP[c] = 0.0;   // (level 0 below the first plane: the zeros of the image it replaces)
 
     // Loads are issued in slices, slice i of n between the pieces of phase B: issued in one burst (14 per wave, all twelve
     // waves at the same point of the step) they keep every wave at the vector-memory issue port in front of the barrier
     // while nothing computes -- measured: the burst added its whole issue time to the step.
-    // Slice i: x and the classes of its cells of `plane` into a register set (the y ring with the last slice), f of the
+    // Slice i: x and the classes of its cells of `plane` into X and C (the y ring with the last slice), f of the
     // plane `fplane` into the slot of the ring that has just become free (a step needs it one step after x of that plane).
     // (`noc`, wave-uniform: the step that consumes the plane is an interior one -- no class loads)
-    auto load_slice = [&](const int i, const int n, const int plane, const int fplane, const bool noc, double (&X)[NC], int (&C)[NC], double (&hy)[M])
-        __attribute__((always_inline)) {
+    auto load_slice = [&](const int i, const int n, const int plane, const int fplane, const bool noc) __attribute__((always_inline)) {
         const int64_t o = (int64_t)min(max(plane, pmin), pmax) * a.P;
         const gcptr_t cb = sbase(clsb + o);
         const gcptr_t xb = sbase(xb0 + o);
@@ -411,17 +411,12 @@ __device__ __forceinline__ void jk3_body(const JK3Args& a) {
             if ((c * n) / NC != i) continue;
             X[c] = ldd(xb, eo[c]);
             if (!noc) C[c] = ldc(cb, eo[c]);
-            if constexpr (PF == 2) FN[c] = ldd(fb, eo[c]);
-            else fr[K - 1][c] = ldd(fb, eo[c]);
+            fr[K - 1][c] = ldd(fb, eo[c]);
         }
         if constexpr (B1) {
-            if (i == n - 1) {
-#pragma unroll
-                for (int r = 0; r < M; ++r) { hS[r] = ldd(xb, eos[r]); hN[r] = ldd(xb, eon[r]); }
-            }
+            if (i == n - 1) { hS = ldd(xb, eos); hN = ldd(xb, eon); }
         } else if (i == n - 1 && (wlo || whi)) {
-#pragma unroll
-            for (int r = 0; r < M; ++r) hy[r] = ldd(xb, eor[r]);
+            hy = ldd(xb, eor);
         }
     };
     auto cls_of = [&](int j, int c) -> int { return (int)((cw[j][c / CPR] >> (CBITS * (c % CPR))) & CMASK); };
@@ -456,110 +451,82 @@ __device__ __forceinline__ void jk3_body(const JK3Args& a) {
     // on the cell's grid line (tile rows along the y boundary), away from the first and last planes: the entries of each cell's
     // row come from the class table once per cell and phase.  (Until the y boundary took this form too its tiles ran the
     // general one, 1.6 x slower -- and on a level with one round of workgroups, 257^3, the slowest tiles ARE the launch.)
-    auto phase_a_fast = [&](auto col_tag, auto caps, const double (&X)[NC]) __attribute__((always_inline)) {
+    auto phase_a_fast = [&](auto col_tag, auto caps) __attribute__((always_inline)) {
         constexpr bool COL = decltype(col_tag)::value;
         using CAP = decltype(caps);
 #pragma unroll
-        for (int r = 0; r < M; ++r) {
+        for (int c = 0; c < NC; ++c) {      // (cell c lies on the wave's line c)
+            const int iw = lwof(c);
+            double k0 = m0, k6 = m6, kcf = mcf;
+            if constexpr (COL) {
+                const dvec2_t* const tr = reinterpret_cast<const dvec2_t*>(sT + CLS_W * cls_of(0, c));
+                const dvec2_t t01 = tr[0], t67 = tr[3];
+                k0 = t01.x; k6 = t67.x; kcf = t67.y;
+            }
+            double nw = X[c];
 #pragma unroll
-            for (int l = 0; l < LPW; ++l) {
-                const int c = l * M + r, iw = lwof(c);
-                double k0 = m0, k6 = m6, kcf = mcf;
-                if constexpr (COL) {
-                    const dvec2_t* const tr = reinterpret_cast<const dvec2_t*>(sT + CLS_W * cls_of(0, c));
-                    const dvec2_t t01 = tr[0], t67 = tr[3];
-                    k0 = t01.x; k6 = t67.x; kcf = t67.y;
+            for (int t = 1; t <= K; ++t) {
+                if (t > CAP::of(c)) {       // (above the line's cap: its last level goes to the image, nothing else)
+                    if (t == CAP::of(c) + 1) (B1 ? limg(bcur, t - 1) : image(t - 1))[iw] = nw;
+                    continue;
                 }
-                double nw = X[c];
-#pragma unroll
-                for (int t = 1; t <= K; ++t) {
-                    if (t > CAP::of(l)) {       // (above the line's cap: its last level goes to the image, nothing else)
-                        if (t == CAP::of(l) + 1) (B1 ? limg(bcur, t - 1) : image(t - 1))[iw] = nw;
-                        continue;
-                    }
-                    if constexpr (B1) {
-                        const double wd = t == 1 ? XP[c] : limg(bprev, t - 1)[iw];
-                        const double s = fma(k6, nw, acc[t - 1][c]);      // +P
-                        const double o = wd + kcf * (fr[K - t][c] - s);
-                        acc[t - 1][c] = fma(k0, wd, 0.0);                 // -P of the plane above
-                        if (t > 1) limg(bcur, t - 1)[iw] = nw;
-                        nw = o;
-                        continue;
-                    }
-                    double* const img = image(t - 1);
-                    const double wd = img[iw];
+                if constexpr (B1) {
+                    const double wd = t == 1 ? XP[c] : limg(bprev, t - 1)[iw];
                     const double s = fma(k6, nw, acc[t - 1][c]);      // +P
                     const double o = wd + kcf * (fr[K - t][c] - s);
                     acc[t - 1][c] = fma(k0, wd, 0.0);                 // -P of the plane above
-                    img[iw] = nw;
+                    if (t > 1) limg(bcur, t - 1)[iw] = nw;
                     nw = o;
+                    continue;
                 }
-                if (CAP::of(l) == K && k_store && (inT >> c & 1u)) store(c, nw);
+                double* const img = image(t - 1);
+                const double wd = img[iw];
+                const double s = fma(k6, nw, acc[t - 1][c]);      // +P
+                const double o = wd + kcf * (fr[K - t][c] - s);
+                acc[t - 1][c] = fma(k0, wd, 0.0);                 // -P of the plane above
+                img[iw] = nw;
+                nw = o;
             }
+            if (CAP::of(c) == K && k_store && (inT >> c & 1u)) store(c, nw);
         }
     };
     // (phase B comes in K pieces, one per level, so that the loads can go out in COMMON code between them: a load issued
     //  inside the branches of the three forms makes the compiler spill hundreds of registers)
-    auto phase_b_fast = [&](auto col_tag, auto caps, const int t, const double (&X)[NC]) __attribute__((always_inline)) {
+    auto phase_b_fast = [&](auto col_tag, auto caps, const int t) __attribute__((always_inline)) {
         constexpr bool COL = decltype(col_tag)::value;
         using CAP = decltype(caps);
         const double* const img = B1 ? limg(bcur, t > 1 ? t - 1 : 1) : image(t - 1);
-        double v[LPW][M], ys[M], yn[M];
+        double v[LPW], ys, yn;      // level t-1 on the wave's lines, the line below and the line above them
+        if (B1 && t == 1) {         // (level 0: registers)
+            ys = hS; yn = hN;
 #pragma unroll
-        for (int r = 0; r < M; ++r) {
-            if (B1 && t == 1) {         // (level 0: registers)
-                ys[r] = hS[r];
+            for (int l = 0; l < LPW; ++l) v[l] = X[l];
+        } else {
+            ys = img[-EX]; yn = img[LPW * EX];
 #pragma unroll
-                for (int l = 0; l < LPW; ++l) v[l][r] = X[l * M + r];
-                yn[r] = hN[r];
-                continue;
-            }
-            ys[r] = img[-EX + 64 * r];
-#pragma unroll
-            for (int l = 0; l < LPW; ++l) v[l][r] = img[l * EX + 64 * r];
-            yn[r] = img[LPW * EX + 64 * r];
+            for (int l = 0; l < LPW; ++l) v[l] = img[l * EX];
         }
 #pragma unroll
-        for (int l = 0; l < LPW; ++l) {
-            if (t > CAP::of(l)) continue;       // (the line has no level t: the reads only it needed go with it)
-            double yw[M], ye[M];
-            if constexpr (DPP) {
-                double fw[M], fe[M];
-#pragma unroll
-                for (int r = 0; r < M; ++r) { fw[r] = jk3_from_west(v[l][r]); fe[r] = jk3_from_east(v[l][r]); }
-#pragma unroll
-                for (int r = 0; r < M; ++r) {
-                    yw[r] = (r > 0 && lane == 0) ? fw[r > 0 ? r - 1 : 0] : fw[r];
-                    ye[r] = (r + 1 < M && lane == 63) ? fe[r + 1 < M ? r + 1 : r] : fe[r];
-                }
-            } else {
-#pragma unroll
-                for (int r = 0; r < M; ++r) {
-                    yw[r] = img[l * EX + 64 * r - 1];
-                    ye[r] = img[l * EX + 64 * r + 1];
-                }
+        for (int c = 0; c < NC; ++c) {
+            if (t > CAP::of(c)) continue;       // (the line has no level t: the reads only it needed go with it)
+            const double yw = jk3_from_west(v[c]), ye = jk3_from_east(v[c]);
+            double k1 = m1, k2 = m2, k3 = m3, k4 = m4, k5 = m5;
+            if constexpr (COL) {
+                const dvec2_t* const tr = reinterpret_cast<const dvec2_t*>(sT + CLS_W * cls_of(0, c));
+                const dvec2_t t01 = tr[0], t23 = tr[1], t45 = tr[2];
+                k1 = t01.y; k2 = t23.x; k3 = t23.y; k4 = t45.x; k5 = t45.y;
             }
-#pragma unroll
-            for (int r = 0; r < M; ++r) {
-                const int c = l * M + r;
-                double k1 = m1, k2 = m2, k3 = m3, k4 = m4, k5 = m5;
-                if constexpr (COL) {
-                    const dvec2_t* const tr = reinterpret_cast<const dvec2_t*>(sT + CLS_W * cls_of(0, c));
-                    const dvec2_t t01 = tr[0], t23 = tr[1], t45 = tr[2];
-                    k1 = t01.y; k2 = t23.x; k3 = t23.y; k4 = t45.x; k5 = t45.y;
-                }
-                double s = acc[t - 1][c];
-                s = fma(k1, l > 0 ? v[l > 0 ? l - 1 : 0][r] : ys[r], s);
-                s = fma(k2, yw[r], s);
-                s = fma(k3, v[l][r], s);
-                s = fma(k4, ye[r], s);
-                s = fma(k5, l + 1 < LPW ? v[l + 1 < LPW ? l + 1 : l][r] : yn[r], s);
-                acc[t - 1][c] = s;
-            }
+            double s = acc[t - 1][c];
+            s = fma(k1, c > 0 ? v[c > 0 ? c - 1 : 0] : ys, s);
+            s = fma(k2, yw, s);
+            s = fma(k3, v[c], s);
+            s = fma(k4, ye, s);
+            s = fma(k5, c + 1 < LPW ? v[c + 1 < LPW ? c + 1 : c] : yn, s);
+            acc[t - 1][c] = s;
         }
     };
     // General form: every cell's entries from the class table, rows outside the level masked to zero.
-    auto phase_a_general = [&](const double (&X)[NC]) __attribute__((always_inline)) {
+    auto phase_a_general = [&]() __attribute__((always_inline)) {
 #pragma unroll
         for (int c = 0; c < NC; ++c) {
             const int iw = lwof(c);
@@ -590,20 +557,13 @@ __device__ __forceinline__ void jk3_body(const JK3Args& a) {
             if (k_store && (inT >> c & 1u)) store(c, nw);
         }
     };
-    auto phase_b_general = [&](const int t, const double (&X)[NC]) __attribute__((always_inline)) {
+    auto phase_b_general = [&](const int t) __attribute__((always_inline)) {
         // (B1, level 0: the -1 / +1 neighbours through DPP as in the straight-line form, all cells' before the first use)
         double x0w[B1 ? NC : 1], x0e[B1 ? NC : 1];
         if constexpr (B1) {
             if (t == 1) {
-                double fw[NC], fe[NC];
 #pragma unroll
-                for (int c = 0; c < NC; ++c) { fw[c] = jk3_from_west(X[c]); fe[c] = jk3_from_east(X[c]); }
-#pragma unroll
-                for (int c = 0; c < NC; ++c) {
-                    const int r = c % M;
-                    x0w[c] = (r > 0 && lane == 0) ? fw[r > 0 ? c - 1 : c] : fw[c];
-                    x0e[c] = (r + 1 < M && lane == 63) ? fe[r + 1 < M ? c + 1 : c] : fe[c];
-                }
+                for (int c = 0; c < NC; ++c) { x0w[c] = jk3_from_west(X[c]); x0e[c] = jk3_from_east(X[c]); }
             }
         }
 #pragma unroll
@@ -612,10 +572,9 @@ __device__ __forceinline__ void jk3_body(const JK3Args& a) {
             const int iw = lwof(c);
             double ys, yw, yd, ye, yn;
             if (B1 && t == 1) {
-                const int l = c / M, r = c % M;
-                ys = l > 0 ? X[l > 0 ? c - M : c] : hS[r];
+                ys = c > 0 ? X[c > 0 ? c - 1 : c] : hS;
                 yw = x0w[B1 ? c : 0]; yd = X[c]; ye = x0e[B1 ? c : 0];
-                yn = l + 1 < LPW ? X[l + 1 < LPW ? c + M : c] : hN[r];
+                yn = c + 1 < LPW ? X[c + 1 < LPW ? c + 1 : c] : hN;
             } else {
                 const double* const img = B1 ? limg(bcur, t > 1 ? t - 1 : 1) : image(t - 1);
                 ys = img[iw - EX]; yw = img[iw - 1]; yd = img[iw]; ye = img[iw + 1]; yn = img[iw + EX];
@@ -633,13 +592,9 @@ __device__ __forceinline__ void jk3_body(const JK3Args& a) {
         }
     };
 
-    // One step: `X, C, hy` hold plane k+K (arrived).  PF = 1: when phase A has consumed them, the loads of plane k+K+1 go out
-    // into the same registers and are in flight through phase B.  PF = 2: a second set `XN, CN, hyN` holds plane k+K+1, in
-    // flight since the step before (with f of plane k+K in `FN`); behind phase A the first set takes the second one over (a
-    // whole step after those loads went out) and the loads of plane k+K+2 go out into the second set: a plane is in
-    // flight at all times.
-    auto step = [&](const int k, double (&X)[NC], int (&C)[NC], double (&hy)[M], double (&XN)[PF == 2 ? NC : 1],
-                    int (&CN)[PF == 2 ? NC : 1], double (&hyN)[PF == 2 ? M : 1]) __attribute__((always_inline)) {
+    // One step: `X, C, hy` hold plane k+K (arrived).  When phase A has consumed them, the loads of plane k+K+1 go out into the
+    // same registers and are in flight through phase B.
+    auto step = [&](const int k) __attribute__((always_inline)) {
         k_plane = k; k_store = k >= z0;
         if constexpr (B1) {
             bcur = TR * CLS_W + ey0 * EX + lane + (k & 1) * PS;
@@ -758,21 +713,19 @@ __device__ __forceinline__ void jk3_body(const JK3Args& a) {
         if (a.force_form >= 0) form = a.force_form;
         // ---- phase A: finish plane k+K-t of level t, t = 1 .. K; start the plane above it ----
         if constexpr (CAPS) {
-            if (form == 0) by_caps([&](auto caps) __attribute__((always_inline)) { phase_a_fast(std::false_type{}, caps, X); });
-            else if (form == 1) by_caps([&](auto caps) __attribute__((always_inline)) { phase_a_fast(std::true_type{}, caps, X); });
-            else phase_a_general(X);
+            if (form == 0) by_caps([&](auto caps) __attribute__((always_inline)) { phase_a_fast(std::false_type{}, caps); });
+            else if (form == 1) by_caps([&](auto caps) __attribute__((always_inline)) { phase_a_fast(std::true_type{}, caps); });
+            else phase_a_general();
         } else {
-            if (form == 0) phase_a_fast(std::false_type{}, caps_all{}, X);
-            else if (form == 1) phase_a_fast(std::true_type{}, caps_all{}, X);
-            else phase_a_general(X);
+            if (form == 0) phase_a_fast(std::false_type{}, caps_all{});
+            else if (form == 1) phase_a_fast(std::true_type{}, caps_all{});
+            else phase_a_general();
         }
         if constexpr (B1) {
 #pragma unroll
             for (int c = 0; c < NC; ++c) XP[c] = X[c];
         } else if (wlo || whi) {
-            double* const ring = image(0) + (wlo ? -EX : LPW * EX);
-#pragma unroll
-            for (int r = 0; r < M; ++r) ring[64 * r] = hy[r];
+            image(0)[wlo ? -EX : LPW * EX] = hy;
         }
         // ---- the rings move on; the next loads go out ----
 #pragma unroll
@@ -791,84 +744,65 @@ __device__ __forceinline__ void jk3_body(const JK3Args& a) {
         __syncthreads();
         // ---- phase B: the in-plane terms of the planes started above (ring index K - t of the moved ring); the next
         //      loads go out between its pieces ----
-        if constexpr (PF == 2) {
-#pragma unroll
-            for (int c = 0; c < NC; ++c) {
-                X[c] = XN[c]; C[c] = CN[c]; fr[K - 1][c] = FN[c];
-                asm volatile("" : "+v"(X[c]));
-                asm volatile("" : "+v"(C[c]));
-                asm volatile("" : "+v"(fr[K - 1][c]));
-            }
-            if (wlo || whi) {
-#pragma unroll
-                for (int r = 0; r < M; ++r) { hy[r] = hyN[r]; asm volatile("" : "+v"(hy[r])); }
-            }
-        }
         auto issue = [&](const int i, const int n) __attribute__((always_inline)) {
             __builtin_amdgcn_sched_barrier(0);
-            if constexpr (PF == 2) load_slice(i, n, k + K + 2, k + K + 1, interior_step(k + 2), XN, CN, hyN);
-            else load_slice(i, n, k + K + 1, k + K, interior_step(k + 1), X, C, hy);
+            load_slice(i, n, k + K + 1, k + K, interior_step(k + 1));
             __builtin_amdgcn_sched_barrier(0);
         };
 #pragma unroll
         for (int t = 1; t <= K; ++t) {
             if constexpr (CAPS) {
-                if (form == 0) by_caps([&](auto caps) __attribute__((always_inline)) { phase_b_fast(std::false_type{}, caps, t, X); });
-                else if (form == 1) by_caps([&](auto caps) __attribute__((always_inline)) { phase_b_fast(std::true_type{}, caps, t, X); });
-                else phase_b_general(t, X);
+                if (form == 0) by_caps([&](auto caps) __attribute__((always_inline)) { phase_b_fast(std::false_type{}, caps, t); });
+                else if (form == 1) by_caps([&](auto caps) __attribute__((always_inline)) { phase_b_fast(std::true_type{}, caps, t); });
+                else phase_b_general(t);
             } else {
-                if (form == 0) phase_b_fast(std::false_type{}, caps_all{}, t, X);
-                else if (form == 1) phase_b_fast(std::true_type{}, caps_all{}, t, X);
-                else phase_b_general(t, X);
+                if (form == 0) phase_b_fast(std::false_type{}, caps_all{}, t);
+                else if (form == 1) phase_b_fast(std::true_type{}, caps_all{}, t);
+                else phase_b_general(t);
             }
             issue(t - 1, K);
         }
         if constexpr (!B1) __syncthreads();
     };
 
-    load_slice(0, 1, z0 - K, z0 - K - 1, false, XA, CA, hyA);
-    if constexpr (PF == 2) {
-#pragma unroll
-        for (int c = 0; c < NC; ++c) fr[K - 1][c] = FN[c];      // (the first slice's f went to the staging set)
-        load_slice(0, 1, z0 - K + 1, z0 - K, false, XB, CB, hyB);
-    }
+    load_slice(0, 1, z0 - K, z0 - K - 1, false);
     __syncthreads();
 
-    for (int k = z0 - 2 * K; k < z1; ++k) step(k, XA, CA, hyA, XB, CB, hyB);
+    for (int k = z0 - 2 * K; k < z1; ++k) step(k);
 }
 
 // WPE: waves per SIMD the register budget is set for (12-wave workgroups: 3, one per CU; 6- and 8-wave workgroups: 3 / 4,
 // two per CU, so that one workgroup's waves run while the other's wait at a barrier)
-template <int K, int NW, int LPW, int M, bool DPP, int PF, int WPE, int TR>
+template <int K, int NW, int LPW, int WPE, int TR>
 __global__ __attribute__((amdgpu_flat_work_group_size(NW * WAVE, NW * WAVE), amdgpu_waves_per_eu(WPE, WPE)))
 void sdia_jacobikc(JK3Args a) {
-    jk3_body<K, NW, LPW, M, DPP, PF, TR>(a);
+    jk3_body<K, NW, LPW, TR>(a);
 }
 
 // (its own symbol for the finest level, so that profiler summaries list the dominant launches apart)
-template <int K, int NW, int LPW, int M, bool DPP, int PF, int WPE, int TR>
+template <int K, int NW, int LPW, int WPE, int TR>
 __global__ __attribute__((amdgpu_flat_work_group_size(NW * WAVE, NW * WAVE), amdgpu_waves_per_eu(WPE, WPE)))
 void sdia_jacobikc_finest(JK3Args a) {
-    jk3_body<K, NW, LPW, M, DPP, PF, TR>(a);
+    jk3_body<K, NW, LPW, TR>(a);
 }
 
 // tile shape 8: one barrier per step (see jk3b_lds_doubles)
-template <int K, int NW, int LPW, int M, int WPE, int TR>
+template <int K, int NW, int LPW, int WPE, int TR>
 __global__ __attribute__((amdgpu_flat_work_group_size(NW * WAVE, NW * WAVE), amdgpu_waves_per_eu(WPE, WPE)))
 void sdia_jacobikc_b1(JK3Args a) {
-    jk3_body<K, NW, LPW, M, true, 1, TR, false, true>(a);
+    jk3_body<K, NW, LPW, TR, false, true>(a);
 }
-template <int K, int NW, int LPW, int M, int WPE, int TR>
+template <int K, int NW, int LPW, int WPE, int TR>
 __global__ __attribute__((amdgpu_flat_work_group_size(NW * WAVE, NW * WAVE), amdgpu_waves_per_eu(WPE, WPE)))
 void sdia_jacobikc_finest_b1(JK3Args a) {
-    jk3_body<K, NW, LPW, M, true, 1, TR, false, true>(a);
+    jk3_body<K, NW, LPW, TR, false, true>(a);
 }
 
 // (levels with rows of class CLS_ESCAPE)
-template <int K, int NW, int LPW, int M, bool DPP, int PF, int WPE, int TR>
+template <int K, int NW, int LPW, int WPE, int TR>
 __global__ __attribute__((amdgpu_flat_work_group_size(NW * WAVE, NW * WAVE), amdgpu_waves_per_eu(WPE, WPE)))
 void sdia_jacobikc_escape(JK3Args a) {
-    jk3_body<K, NW, LPW, M, DPP, PF, TR, true>(a);
+    jk3_body<K, NW, LPW, TR, true>(a);
 }
 
 // Rim waves (tile shape 9).  On the 64 x 32 tiles of shape 8 the lines 0 .. K-2 and EY-K+1 .. EY-1 carry the halo levels (caps
@@ -1368,7 +1302,7 @@ void sdia_jacobikc_finest_rim_early(JK3Args a) {
     jk3_rim_body<K, TR, true>(a);
 }
 
-// The most pool rows any tile of the march <K, NW, LPW, M> takes within K + 2 consecutive planes: one workgroup per tile
+// The most pool rows any tile of the march <K, NW, LPW> takes within K + 2 consecutive planes: one workgroup per tile
 // counts the cells of class CLS_ESCAPE plane by plane -- the tile's cells at the very rows the march reads their classes
 // from, but for the clamped ones (`standin` there) -- and keeps the largest sum over a window of planes.
 struct JK3WindowArgs {
@@ -1378,9 +1312,9 @@ struct JK3WindowArgs {
     unsigned* most;
 };
 
-template <int K, int NW, int LPW, int M>
+template <int K, int NW, int LPW>
 __global__ __launch_bounds__(256) void jk3_escape_window(JK3WindowArgs a) {
-    constexpr int EX = 64 * M, EY = NW * LPW, WI = EX - 2 * K, HY = EY - 2 * K + 2, W = K + 2;
+    constexpr int EX = 64, EY = NW * LPW, WI = EX - 2 * K, HY = EY - 2 * K + 2, W = K + 2;
     __shared__ unsigned s_ring[W], s_plane;
     const int tiy = (int)(blockIdx.x / (unsigned)a.ntx), tix = (int)(blockIdx.x % (unsigned)a.ntx);
     const int tx0 = tix * WI - K, ty0 = tiy * HY - (K - 1), xcl = a.nx + 1 - tx0;
@@ -1406,7 +1340,7 @@ __global__ __launch_bounds__(256) void jk3_escape_window(JK3WindowArgs a) {
     if (threadIdx.x == 0 && best) atomicMax(a.most, best);
 }
 
-// The march plan of a whole level for the tiles of the march <K, NW, LPW, M>: one workgroup per tile, shaped like the
+// The march plan of a whole level for the tiles of the march <K, NW, LPW>: one workgroup per tile, shaped like the
 // march's, walks the planes; every wave looks at the class bytes the march's wave would load for the plane (the same
 // offsets, jk3_cell_offset / jk3_class_base) and keeps two runs of consecutive planes, the longest of their kind and the
 // first of equally long ones (r0 = r1 = 0: none):
@@ -1465,9 +1399,9 @@ __device__ __forceinline__ void jk3_plan_walk(const JK3PlanArgs& a, const unsign
     if (lane == 0) { pw[0] = p0; pw[1] = p1; pw[2] = q0; pw[3] = q1; }
 }
 
-template <int K, int NW, int LPW, int M>
+template <int K, int NW, int LPW>
 __global__ __launch_bounds__(NW * WAVE) void jk3_plan(JK3PlanArgs a) {
-    constexpr int EX = 64 * M, EY = NW * LPW, NC = M * LPW, WI = EX - 2 * K, HY = EY - 2 * K + 2;
+    constexpr int EX = 64, EY = NW * LPW, NC = LPW, WI = EX - 2 * K, HY = EY - 2 * K + 2;
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const unsigned tt = blockIdx.x;
@@ -1476,7 +1410,7 @@ __global__ __launch_bounds__(NW * WAVE) void jk3_plan(JK3PlanArgs a) {
     const int ey0 = wave * LPW, bias = 2 * a.nx + K + 2, xcl = a.nx + 1 - tx0;
     unsigned eo[NC];
 #pragma unroll
-    for (int c = 0; c < NC; ++c) eo[c] = jk3_cell_offset(ty0 + ey0 + c / M, lane + 64 * (c % M), a.nx, a.ny, tx0, xcl, bias);
+    for (int c = 0; c < NC; ++c) eo[c] = jk3_cell_offset(ty0 + ey0 + c, lane, a.nx, a.ny, tx0, xcl, bias);
     jk3_plan_walk<NC>(a, jk3_class_base(a.cls, a.clead, bias), eo, a.plan + 4 * ((int)tt * NW + wave));
 }
 

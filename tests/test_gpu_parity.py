@@ -710,7 +710,7 @@ _MARCH = dict(_SMALL, fuse_block=0)
     (dict(), {"block": (34, 100)}),                                             # 50 = 16 x 3 + 2 per call
     (dict(_MARCH), {"ksweep": (20, 100)}),                                      # five sweeps per pass (< fuse_k_small_rows)
     (dict(_MARCH, fuse_k=0), {"pair_class": (50, 100)}),
-    (dict(_MARCH, fuse_k=3, fuse_k_shape=0), {"ksweep": (32, 96), "pair_class": (2, 4)}),       # 50 = 16 x 3 + a pair
+    (dict(_MARCH, fuse_k=3, fuse_k_shape=1), {"ksweep": (32, 96), "pair_class": (2, 4)}),       # 50 = 16 x 3 + a pair
     (dict(_MARCH, fuse_k=5, fuse_k_shape=4), {"ksweep": (20, 100)}),
     (dict(_MARCH, fuse_classes=0, class_sweeps=0), {"pair_plain": (50, 100)}),
     (dict(_MARCH, fuse_k=4), {"ksweep": (24, 96), "pair_class": (2, 4)}),       # 50 = 12 x 4 + a pair
@@ -1304,7 +1304,7 @@ def test_two_sweep_kernel_is_bit_identical_to_single_sweeps(c, lo, hi):
     rng = np.random.default_rng(c)
     want = {}
     # (fuse_k=0: pairs of sweeps only, the two-sweep pass; fuse_k=3..5: the K-sweep march of mg_jacobik3d.hip.h in its
-    #  three tile shapes, with and without the DPP neighbour exchange, with one / several plane segments)
+    #  tile shapes 1, 4, 7 and 8, with one / several plane segments)
     reference = dict(fuse_sweeps=0, fuse_small=0, fuse_block=0, fuse_k=0)
     variants = [reference, dict(), dict(fuse_sweeps=0), dict(fuse_k=0), dict(fuse_k=0, fuse_segments=1),
                 dict(fuse_k=0, fuse_segments=3), dict(fuse_classes=0), dict(fuse_classes=0, fuse_plain_shape=1),
@@ -1314,12 +1314,12 @@ def test_two_sweep_kernel_is_bit_identical_to_single_sweeps(c, lo, hi):
                 dict(fuse_segments=5, fuse_nontemporal=1, fuse_classes=0), dict(rows_per_lane=1),
                 dict(rows_per_lane=4, fuse_segments=2), dict(rows_per_lane=1, row_classes=0),
                 dict(fuse_k=3), dict(fuse_k=4, fuse_k_segments=1), dict(fuse_k=5, fuse_k_segments=3), dict(fuse_k=4, fuse_k_shape=1),
-                dict(fuse_k=5, fuse_k_shape=1, fuse_k_segments=2), dict(fuse_k=4, fuse_k_shape=2), dict(fuse_k=3, fuse_k_shape=2, fuse_k_segments=4),
-                dict(fuse_k=4, fuse_k_dpp=0), dict(fuse_k=3, fuse_k_dpp=0, fuse_k_segments=2),
-                dict(fuse_k=3, fuse_k_shape=3), dict(fuse_k=4, fuse_k_shape=3, fuse_k_segments=2), dict(fuse_k=5, fuse_k_shape=3),
-                dict(fuse_k=3, fuse_k_shape=4, fuse_k_segments=3), dict(fuse_k=4, fuse_k_shape=4), dict(fuse_k=4, fuse_k_shape=5),
-                dict(fuse_k=3, fuse_k_shape=1, fuse_k_pf=2), dict(fuse_k=3, fuse_k_shape=2, fuse_k_pf=2, fuse_k_segments=2),
-                dict(fuse_k=3, fuse_k_shape=6), dict(fuse_k=4, fuse_k_shape=7, fuse_k_segments=2),
+                dict(fuse_k=5, fuse_k_shape=1, fuse_k_segments=2), dict(fuse_k=4, fuse_k_shape=7), dict(fuse_k=3, fuse_k_shape=1, fuse_k_segments=4),
+                dict(fuse_k=3, fuse_k_shape=4, fuse_k_segments=2),
+                dict(fuse_k=3, fuse_k_shape=4), dict(fuse_k=4, fuse_k_shape=1, fuse_k_segments=2), dict(fuse_k=5, fuse_k_shape=7),
+                dict(fuse_k=3, fuse_k_shape=4, fuse_k_segments=3), dict(fuse_k=4, fuse_k_shape=4),
+                dict(fuse_k=3, fuse_k_shape=1), dict(fuse_k=3, fuse_k_shape=1, fuse_k_segments=2),
+                dict(fuse_k=4, fuse_k_shape=7, fuse_k_segments=2),
                 # (the tiles of a last, nearly empty round in shorter segments: planned for 4 / 5 / 7 resident workgroups so
                 #  that these few-tile grids have such a tail; 0: every tile alike)
                 dict(fuse_k=5, fuse_k_tail=4), dict(fuse_k=4, fuse_k_tail=5, fuse_k_shape=1), dict(fuse_k=3, fuse_k_tail=7),

@@ -85,14 +85,13 @@ def test_march_kernels_of_shapes_7_and_8_fit_the_register_budget():
     notes = _kernel_notes()
     want = []
     for k in (3, 4, 5):
-        want += [f"void mgk::{kind}<{k}, 16, 2, 1, 4, 256>(mgk::JK3Args)" for kind in ("sdia_jacobikc_b1", "sdia_jacobikc_finest_b1")]
-        want += [f"void mgk::{kind}<{k}, 16, 2, 1, true, 1, 4, 256>(mgk::JK3Args)"
-                 for kind in ("sdia_jacobikc", "sdia_jacobikc_finest", "sdia_jacobikc_escape")]
+        want += [f"void mgk::{kind}<{k}, 16, 2, 4, 256>(mgk::JK3Args)"
+                 for kind in ("sdia_jacobikc_b1", "sdia_jacobikc_finest_b1", "sdia_jacobikc", "sdia_jacobikc_finest", "sdia_jacobikc_escape")]
     march = sorted(n for n in notes if "jacobikc" in n)
     for name in want:
         assert name in notes, (name, march)
-    # ... and whatever else of the two shapes the library holds (a second plane of x staged: `fuse_k_pf` 2)
-    both = [n for n in march if re.search(r"sdia_jacobikc\w*<[345], 16, 2, 1, ", n)]
+    # ... and whatever else of the two shapes the library holds
+    both = [n for n in march if re.search(r"sdia_jacobikc\w*<[345], 16, 2, ", n)]
     assert set(want) <= set(both)
     for name in both:
         vgpr, spilled, scratch = notes[name]

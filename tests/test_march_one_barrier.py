@@ -48,7 +48,7 @@ def test_shape8_kernels_fit_the_register_budget():
     notes = _kernel_notes()
     for k in (3, 4, 5):
         for kind in ("sdia_jacobikc_b1", "sdia_jacobikc_finest_b1"):
-            name = f"void mgk::{kind}<{k}, 16, 2, 1, 4, 256>(mgk::JK3Args)"
+            name = f"void mgk::{kind}<{k}, 16, 2, 4, 256>(mgk::JK3Args)"
             assert name in notes, (name, sorted(n for n in notes if "jacobikc" in n))
             vgpr, spilled, scratch = notes[name]
             assert vgpr <= 128 and spilled == 0 and scratch == 0, (name, notes[name])

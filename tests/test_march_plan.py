@@ -295,14 +295,14 @@ def test_plan_kernels_fit_the_register_budget():
     """jk3_plan for K = 3, 4, 5 and every march kernel of the 64 x 32 tiles that reads a plan (shapes 7 and 8, not the escape
     variant): present in the gfx950 code object, at most 128 VGPRs (sixteen waves per workgroup), nothing spilled, no scratch."""
     notes = _kernel_notes()
-    want = [f"void mgk::jk3_plan<{k}, 16, 2, 1>(mgk::JK3PlanArgs)" for k in (3, 4, 5)]
+    want = [f"void mgk::jk3_plan<{k}, 16, 2>(mgk::JK3PlanArgs)" for k in (3, 4, 5)]
     for k in (3, 4, 5):
-        want += [f"void mgk::{kind}<{k}, 16, 2, 1, 4, 256>(mgk::JK3Args)" for kind in ("sdia_jacobikc_b1", "sdia_jacobikc_finest_b1")]
-        want += [f"void mgk::{kind}<{k}, 16, 2, 1, true, 1, 4, 256>(mgk::JK3Args)" for kind in ("sdia_jacobikc", "sdia_jacobikc_finest")]
+        want += [f"void mgk::{kind}<{k}, 16, 2, 4, 256>(mgk::JK3Args)"
+                 for kind in ("sdia_jacobikc_b1", "sdia_jacobikc_finest_b1", "sdia_jacobikc", "sdia_jacobikc_finest")]
     have = sorted(n for n in notes if "jacobikc" in n or "jk3_plan" in n)
     for name in want:
         assert name in notes, (name, have)
-    planned = [n for n in have if re.search(r"sdia_jacobikc(_finest)?(_b1)?<[345], 16, 2, 1, ", n) or "jk3_plan" in n]
+    planned = [n for n in have if re.search(r"sdia_jacobikc(_finest)?(_b1)?<[345], 16, 2, ", n) or "jk3_plan" in n]
     assert set(want) <= set(planned)
     for name in planned:
         vgpr, spilled, scratch = notes[name]

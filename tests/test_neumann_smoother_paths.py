@@ -39,7 +39,7 @@ tests/test_gpu_parity.py's `_paths_3d` with the block pass's default size window
   fuse_block 0, fuse_k 0 (and fuse_segments 3)      pair_class
   fuse_block 0, fuse_classes 0 (and on `lognormal`, with the plain tile shapes)   pair_plain
   fuse_block 0, fuse_sweeps 0                       sweep1c against the reference's slices
-  fuse_k 3, 4, 5 x fuse_k_shape 8, 7 x fuse_k_segments 1, 3; fuse_k_tail 4 / 5; fuse_k_dpp 0     ksweep
+  fuse_k 3, 4, 5 x fuse_k_shape 8, 7 x fuse_k_segments 1, 3; fuse_k_tail 4 / 5; fuse_k 4 in fuse_k_shape 1     ksweep
   fuse_block 2 x fuse_block_k 2, 3, 4 x fuse_block_ez 11, 19                                     block
   `patch`, row_escape on                            ksweep_escape, the level keeping its 255 classes
 each on the finest level of its handle and on a level that is not the finest (the marches have a kernel for either).  The full
@@ -84,7 +84,7 @@ FULL_VARIANTS = SHORT_VARIANTS + [
     dict(_NO_BLOCK, fuse_k=0), dict(_NO_BLOCK, fuse_k=0, fuse_segments=3), dict(_NO_BLOCK, fuse_classes=0), dict(_NO_BLOCK, fuse_sweeps=0),
 ] + [dict(_NO_BLOCK, fuse_k=k, fuse_k_shape=shape, fuse_k_segments=seg) for k in (3, 4, 5) for shape in (8, 7) for seg in (1, 3)] + [
     dict(_NO_BLOCK, fuse_k=5, fuse_k_shape=8, fuse_k_tail=4), dict(_NO_BLOCK, fuse_k=4, fuse_k_shape=7, fuse_k_tail=5),
-    dict(_NO_BLOCK, fuse_k=4, fuse_k_dpp=0),
+    dict(_NO_BLOCK, fuse_k=4, fuse_k_shape=1),
     dict(fuse_block=2), dict(fuse_block=2, fuse_block_k=2, fuse_block_ez=11), dict(fuse_block=2, fuse_block_k=4, fuse_block_ez=11),
     dict(fuse_block=2, fuse_block_k=2, fuse_block_ez=19), dict(fuse_block=2, fuse_block_k=3, fuse_block_ez=19),
     dict(fuse_block=2, fuse_block_k=4, fuse_block_ez=19)]

@@ -15,6 +15,7 @@ the path that ran.
   cls_blocks_per_cu    1, 3, 64: residual, Jacobi sweep (finest and middle level) and x^T A x at 65^3 and 129^3
   lds_pad              0, 32768, 65536, 153600 on levels of at least 100000 slices without row classes; 153601 refused
   fuse_k_nt_store, fuse_k_small_tiles   the K-sweep march with the switch on
+  fuse_k_shape         1, 4, 7, 8, 9, -1 accepted; the retired shapes 0, 2, 3, 5, 6 refused; the retired keys unknown
   slab_pair_form       0 and 1 with the overlap on, two and three ranks over the in-process RCCL stand-in
   pcg_chunk            1, 5, 16, 64: iteration count, relative residual and solution of the coarsest-level PCG
   gen_odd_rows         what the generator perturbs, against the header's contract"""
@@ -425,6 +426,29 @@ def test_march_with_small_tiles(k, c):
         assert set(ran) == {"ksweep"} and ran["ksweep"][:2] == (2, 2 * k), (tuning, ran)
     assert np.array_equal(got[1], got[0]), _differ(got[1], got[0])
     assert np.array_equal(got[1], _single_sweeps(c, 2 * k)), _differ(got[1], _single_sweeps(c, 2 * k))
+
+
+@pytest.mark.gpu
+def test_retired_march_shapes_and_knobs_are_refused():
+    """The tile shapes 0, 2, 3, 5 and 6 of the K-sweep march and the keys "fuse_k_dpp" and "fuse_k_pf" were retired: the shapes
+    are refused by that word, the keys are unknown, the shapes that exist are accepted, and the handle goes on working with
+    the last accepted value.  One handle at 17^3; no kernel runs."""
+    from multigrid_dolfinx_amd._capi import MgError
+    from multigrid_dolfinx_amd.hierarchy import DeviceHierarchy
+    with DeviceHierarchy.synthetic(3, 1, 3, c=2) as h:
+        for shape in (1, 4, 7, 8, 9, -1):
+            h.set_tuning("fuse_k_shape", shape)
+        for shape in (0, 2, 3, 5, 6):
+            with pytest.raises(MgError, match="fuse_k_shape.*0, 2, 3, 5 and 6 were retired"):
+                h.set_tuning("fuse_k_shape", shape)
+        for shape in (-2, 10):
+            with pytest.raises(MgError, match="fuse_k_shape must be 1, 4, 7, 8 or 9, or -1"):
+                h.set_tuning("fuse_k_shape", shape)
+        for key in ("fuse_k_dpp", "fuse_k_pf"):
+            for value in (0, 1, 2):
+                with pytest.raises(MgError, match="unknown tuning key " + key):
+                    h.set_tuning(key, value)
+        h.set_tuning("fuse_k_shape", 7)
 
 
 # ---- 7. overlapped pair sweeps on slabs -------------------------------------------------------------------------------------------------

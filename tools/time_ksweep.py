@@ -17,7 +17,7 @@ from multigrid_dolfinx_amd.hierarchy import DeviceHierarchy          # noqa: E40
 
 hi = int(sys.argv[1]) if len(sys.argv) > 1 else 7
 reps = int(sys.argv[2]) if len(sys.argv) > 2 else 6
-specs = sys.argv[3:] or ["fuse_k=3", "fuse_k=4", "fuse_k=5", "fuse_k=4,fuse_k_shape=1", "fuse_k=4,fuse_k_shape=2", "fuse_k=4,fuse_k_dpp=0"]
+specs = sys.argv[3:] or ["fuse_k=3", "fuse_k=4", "fuse_k=5", "fuse_k=4,fuse_k_shape=1"]
 with DeviceHierarchy.synthetic(3, 2, hi, c=8, mu1=50, mu2=50) as h:
     n = h.level_info(hi)["n_global"]
     ms = h.time_kernel("jacobi2!", hi, reps)
@@ -39,8 +39,6 @@ with DeviceHierarchy.synthetic(3, 2, hi, c=8, mu1=50, mu2=50) as h:
         print(f"{spec:44s} {ms:8.3f} ms = {ms / k:6.3f} ms per sweep, {25 * n / ms / 1e6:7.1f} GB/s on 25 B/row", flush=True)
         h.set_tuning("fuse_k_shape", 7)
         h.set_tuning("fuse_k_segments", 0)
-        h.set_tuning("fuse_k_dpp", 1)
-        h.set_tuning("fuse_k_pf", 1)
         h.set_tuning("fuse_k_plan", 1)
         h.set_tuning("fuse_k_load_early", 1)
     if os.environ.get("MG_SKIP_CYCLES"):
