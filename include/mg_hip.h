@@ -930,6 +930,80 @@ int mg_pcg_batch(mg_handle h, int level, int nb, const double* const* f_dev, dou
                  double* resid_hist /* [nb][max(1, max_iter)] */, int* iterations /* [nb] */);
 int mg_batch_info(mg_handle h, int* lanes, int64_t* bytes);
 int mg_release_batch(mg_handle h);
+
+/* ---- smallest eigenpairs: K u = lambda M(rho) u by multigrid-preconditioned LOBPCG (no reference counterpart) -----------
+ * K is the level's operator (A(kappa) + R(sigma) + B(alpha) on the free nodes of a generated diffusion level), M(rho) = R(rho)
+ * the lumped mass of a cell field rho (the reaction_diag kernel, +0.0 on the Dirichlet nodes of the level's face set).  The
+ * eigenvalues are the decay rates of rho u_t = div(kappa grad u) - sigma u under the handle's boundary conditions.
+ *
+ * mg_eigs  the k smallest eigenpairs with a block of `block` vectors, 1 <= k <= block <= MG_EIGS_MAX; the vectors beyond k are
+ *          guards that keep a cluster at the block's edge from stalling the wanted ones.
+ *   rho_dev   N^3 cell values > 0 on the device in the cell order of mg_gen_diffusion_level; NULL: rho = 1.
+ *   x_dev     HOST array of `block` DEVICE pointers to n_global doubles each, in the numbering of mg_set_vector_device.  warm = 0:
+ *             the library fills the start block itself, cheb_hash(row + lane * n_global) with `row` the level's lexicographic row
+ *             (the global index of a whole level), zero on the Dirichlet nodes; warm = 1: the start block is read from x_dev, Dirichlet
+ *             entries taken as 0.  On return x_dev[j], j < block, are the Ritz vectors: M-orthonormal, exactly +0.0 on Dirichlet nodes.
+ *   lambda    [block], ascending; resid [block]: ||K x_j - lambda_j M x_j||_2 / (lambda_j ||M x_j||_2).
+ *   iterations, restarts (may be null): iterations done / iterations that dropped P.
+ *   It stops when resid[j] <= rtol for all j < k, or after max_iter iterations; reaching max_iter is not an error (as in mg_pcg).
+ *
+ *   The start block takes one Rayleigh-Ritz step by itself (K X by the level's SpMV, X^T K X and X^T M X, the dense solve, X and K X
+ *   rotated); it counts as no iteration, so a converged warm start returns after 0 iterations.  One iteration:
+ *     1. R_j = K x_j - lambda_j M x_j with both norms of the stopping test: ONE vector kernel per lane (eigs_residual: 24 B read, 8 B
+ *        written per row, the sums in the same pass; a block_combine with the nodal weight would read as much and need the norms
+ *        from two more Gram launches), a fold per lane, one download of 2 block doubles.
+ *     2. W = one V-cycle from a zero guess on each R_j through the lanes of the batched solves (vcycle_batch: fused Jacobi and
+ *        residual launches on matrix-free levels, eager like every batched cycle); W is lane j's MG_VEC_V and is not copied.
+ *        Then W <- W - X (X^T M W), one Gram launch set, a download of block^2 doubles and one in-place block_combine: the
+ *        residual of a vector that has converged below the rounding of its Ritz value is a multiple of M x, and its cycle a
+ *        multiple of x.
+ *     3. K W through the fused matrix-free SpMV (groups of "mf_batch" lanes) or the stored level's SpMV per lane.
+ *     4. S = [X W P] (no P in the first iteration).  S^T K S and S^T M S by block_gram, tiles on and above the diagonal; X^T M X = I
+ *        and X^T K X = diag lambda need no launch.  The columns are scaled to unit M-norm in the two matrices on the host and
+ *        the scale goes into the coefficients: the numbers of scaled columns without a pass over the vectors.
+ *     5. One download of the two matrices, the dense generalised eigenproblem on the host (Cholesky of S^T M S, cyclic Jacobi:
+ *        mg_dense_eig.h), then block_combine for X, K X (in place) and P, K P: K is applied to W only.
+ *     6. A failed Cholesky step (a pivot <= n eps times the largest diagonal entry) redoes the step with S = [X W] and counts a
+ *        restart; if that fails too the call returns an error by name.
+ *   The block that is about to be returned (converged, or max_iter reached) takes the start block's step once more -- K X applied,
+ *   both Gram matrices computed, nothing taken as known -- and the stopping test is repeated on the result: the iteration rotates
+ *   K X with X, and a nearly dependent [X W P] costs orthonormality of the order eps cond(S^T M S), which this step takes back to
+ *   rounding level.  It counts as no iteration.  Soft locking of converged vectors is not done.
+ *
+ *   Work vectors X, K X, K W, P, K P (block each), M, the kernels' partial sums and the folded sums are allocated at the first
+ *   call and kept for later calls on the same level with the same or a smaller block; the lanes of the batched solves (mg_batch_info)
+ *   are used for R and W.  mg_memory_bytes and mg_eigs_info count them; mg_release_eigs, mg_destroy, mg_release_batch and a level
+ *   set again with another size free them.  A handle that never calls these entries allocates and launches what it did before.
+ *   After a call the levels, the factorisation, the Chebyshev intervals, the cached graphs and the tuning are as before and a
+ *   following mg_pcg gives the bits it gives on a handle that never ran mg_eigs; the handle's own MG_VEC_V, MG_VEC_F and MG_VEC_R
+ *   are UNSPECIFIED, as after a batch call.
+ *
+ *   Refused by name before anything is launched or allocated: everything mg_pcg_batch refuses (2-D and slab handles, flat levels,
+ *   level 0, face-set and transfer mismatches, a Gauss-Seidel smoother with a matrix-free level in the cycle, pointers that are not
+ *   this device's memory), k or block out of range, x pointers that overlap each other, a rho that is not finite or not > 0 (the
+ *   first such cell is named; found by a kernel like the sigma check), rtol <= 0 together with max_iter <= 0.
+ *
+ * mg_block_gram     out[i * nb + j] = a_i . (d * b_j) over the level's n_global rows, na, nb in 1..24, d_dev NULL: no weight.  Tiles
+ *                   of at most 4 x 4 pairs, one pass over 4 + 4 (+ 1) vectors each (block_gram, mg_block.hip.h); every block writes
+ *                   its partial sums and a fold sums them in a fixed order: no atomics, the same bytes every time, and a pair has
+ *                   the same bits whatever tile it was computed in (a 1 x 1 call gives the bits of the pair in a 9 x 9 call).
+ *                   na == nb and a_dev[i] == b_dev[i] for all i: a symmetric Gram matrix, only the tiles on and above the diagonal
+ *                   are computed, every pair i > j is the mirror of (j, i): the matrix is symmetric to the bit.
+ * mg_block_combine  out_o = sum_i coeff[i * no + o] s_i, i ascending, the first product and then one fma per input; ns in 1..24, no
+ *                   in 1..8.  An output may BE one of the inputs (every row of every input is read before an output row is
+ *                   written); any other overlap is refused.
+ *   Both take HOST arrays of DEVICE pointers to n_global doubles, 16-byte aligned, and apply the checks above to them.
+ * mg_eigs_info      the largest block the work vectors were allocated for (0: none) and their device bytes
+ * mg_release_eigs   frees them */
+#define MG_EIGS_MAX 8
+int mg_eigs(mg_handle h, int level, int k, int block, const double* rho_dev, double* const* x_dev, int warm,
+            double rtol, int max_iter, double* lambda, double* resid, int* iterations, int* restarts);
+int mg_block_gram(mg_handle h, int level, int na, const double* const* a_dev, int nb, const double* const* b_dev,
+                  const double* d_dev /* nodal weight or NULL */, double* out /* host, na x nb, row-major */);
+int mg_block_combine(mg_handle h, int level, int ns, const double* const* s_dev, int no, const double* coeff /* host, ns x no */,
+                     double* const* out_dev);
+int mg_eigs_info(mg_handle h, int* block, int64_t* bytes);
+int mg_release_eigs(mg_handle h);
 /* Bookkeeping for tests: whole-vector host -> device / device -> host copies made through this handle so far,
  * V-cycles replayed from a captured hipGraph, graphs currently cached.  No reference counterpart. */
 int mg_counters(mg_handle h, int64_t* uploads, int64_t* downloads, int64_t* graph_replays, int* graphs_cached);

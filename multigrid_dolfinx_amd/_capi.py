@@ -22,6 +22,7 @@ MG_KAPPA_ARITHMETIC, MG_KAPPA_HARMONIC = 0, 1
 MG_NODES_INTERIOR, MG_NODES_ALL = 0, 1
 MG_BATCH_MAX = 32
 MG_BATCH_JACOBI, MG_BATCH_RESIDUAL, MG_BATCH_SPMV = 0, 1, 2
+MG_EIGS_MAX = 8
 # enum mg_smoother_path, in its order (mg_smoother_launches)
 SMOOTHER_PATHS = ("slice", "sweep1c", "pair_class", "pair_plain", "ksweep", "ksweep_escape", "ksweep_slab", "block", "k2d",
                   "small", "matrix_free")
@@ -136,6 +137,11 @@ SIGNATURES = {
     "mg_pcg_batch": [_H, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.c_void_p, C.c_void_p],
     "mg_batch_info": [_H, _ip, _i64p],
     "mg_release_batch": [_H],
+    "mg_eigs": [_H, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_void_p, C.c_void_p, _ip, _ip],
+    "mg_block_gram": [_H, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
+    "mg_block_combine": [_H, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p],
+    "mg_eigs_info": [_H, _ip, _i64p],
+    "mg_release_eigs": [_H],
     "mg_counters": [_H, _i64p, _i64p, _i64p, _ip],
     "mg_smoother_launches": [_H, C.c_int, C.c_int, _i64p, _i64p, _i64p],
     "mg_march_plan": [_H, C.c_int, C.c_int, _i64p, _i64p, _i64p, _i64p],

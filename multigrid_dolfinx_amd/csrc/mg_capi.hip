@@ -15,6 +15,8 @@
 #include "mg_diffusion_flux.hip.h"
 #include "mg_diffusion_points.hip.h"
 #include "mg_diffusion_kappa.hip.h"
+#include "mg_block.hip.h"
+#include "mg_dense_eig.h"
 
 #include <dlfcn.h>
 #include <rccl/rccl.h>
@@ -252,6 +254,23 @@ struct Lane {
     DevBuf<double> fcg_work, fcg_spmv;
 };
 
+// What mg_eigs keeps between calls: the block X and K X, K W, P, K P of the iteration on one level (W itself is the cycle's result
+// in the lanes' MG_VEC_V), the lumped mass M(rho), the kernels' partial sums and the folded sums on their way to the host.
+// Allocated at the first call, kept for calls with the same level and the same or a smaller block; counted in the ledger.
+struct EigsWork {
+    int level = -1, block = 0;
+    int64_t vec_total = 0;
+    std::vector<DVector> x, kx, kw, p, kp;
+    DVector m;
+    DevBuf<double> parts, sums;
+    int64_t bytes() const {
+        size_t n = m.raw.count() + parts.count() + sums.count();
+        for (const auto* set : {&x, &kx, &kw, &p, &kp})
+            for (const DVector& v : *set) n += v.raw.count();
+        return (int64_t)(n * sizeof(double));
+    }
+};
+
 // One captured V-cycle (hipGraph): valid for a level, a parameter epoch and a ping-pong state.
 struct CycleGraph {
     int level = -1;
@@ -327,6 +346,7 @@ struct mg_context {
     // kept until mg_release_batch, mg_destroy or a level set again with another size; "mf_batch": the most lanes one fused
     // launch of the matrix-free march takes (0 / 1: never fuse; DESIGN.md, "Batched solves")
     std::vector<Lane> lanes;
+    EigsWork eigs;                  // mg_eigs: its work vectors (freed by mg_release_eigs, mg_destroy and wherever the lanes are)
     int mf_batch = 4;
     double* h_lanes = nullptr;      // pinned, MG_BATCH_MAX doubles: every lane's ||r||^2 of an iteration in one host round trip (first mg_pcg_batch)
     int use_graph = 1;             // replay whole V-cycles as hipGraphs (single GPU, direct coarsest solve)
@@ -526,8 +546,10 @@ int setup_geometry(mg_context* c, Level& L, int level, int N, int64_t flat_rows 
     for (const Lane& lane : c->lanes)
         if ((size_t)level < lane.lv.size() && lane.lv[(size_t)level].v.raw && (int64_t)lane.lv[(size_t)level].v.raw.count() != vec_total(L)) {
             c->lanes.clear();
+            c->eigs = EigsWork{};
             break;
         }
+    if (c->eigs.level == level && c->eigs.vec_total != vec_total(L)) c->eigs = EigsWork{};
     return 0;
 }
 
@@ -3917,6 +3939,365 @@ int batch_refusals(mg_context* c, const std::string& who, int level, int nb, con
     return 0;
 }
 
+// ---- smallest eigenpairs by LOBPCG (mg_eigs) and its two block kernels (mg_block.hip.h) -----------------------------------------
+
+// the grid of the streaming block kernels: fcg_grid, a function of the level and the device alone (block_gram's sums depend on it)
+unsigned gram_grid(const mg_context* c, const Level& L) { return fcg_grid(c, L); }
+
+constexpr size_t kEigsSums = 2 * (size_t)BC_MAX_IN * BC_MAX_IN + 2 * MG_EIGS_MAX;   // two Gram matrices, or the residual norms
+
+// partial sums of the block kernels (one tile at a time) and the folded sums; uncounted scratch where `ew` is a temporary's
+int ensure_block_scratch(mg_context* c, const Level& L, EigsWork& ew) {
+    const size_t parts = (size_t)gram_grid(c, L) * BG_MAX * BG_MAX;
+    if (ew.parts.count() < parts) MG_TRY(ew.parts.alloc(c, parts));
+    if (ew.sums.count() < kEigsSums) MG_TRY(ew.sums.alloc(c, kEigsSums));
+    return 0;
+}
+
+// Tiles of block_gram launches whose folded sums wait in ew.sums for one download; each knows where its pairs go on the host.
+struct GramBatch {
+    struct Tile { double* dst; int ld, r, col, na, nb; size_t off; bool mirror, upper; };
+    std::vector<Tile> tiles;
+    size_t used = 0;
+};
+
+// a_i . (d * b_j), i < na, j < nb, tiled by BG_MAX x BG_MAX: pair (i, j) goes to dst[(r0 + i) * ld + c0 + j].  sym: a == b, only
+// the tiles on and above the diagonal are computed and of a tile on the diagonal the pairs i <= j are used, so the matrix is
+// symmetric to the bit.  mirror: a pair of any tile (always where sym) also goes to dst[(c0 + j) * ld + r0 + i].
+int gram_enqueue(mg_context* c, const Level& L, EigsWork& ew, GramBatch& gb, double* dst, int ld, int r0, int c0, int na,
+                 const double* const* a, int nb, const double* const* b, const double* d, bool sym, bool mirror) {
+    const dim3 grid(gram_grid(c, L)), blk(BLOCK);
+    for (int ti = 0; ti < na; ti += BG_MAX)
+        for (int tj = sym ? ti : 0; tj < nb; tj += BG_MAX) {
+            const int NA = std::min(BG_MAX, na - ti), NB = std::min(BG_MAX, nb - tj);
+            if (gb.used + (size_t)(NA * NB) > ew.sums.count()) return fail("block_gram: more sums than the buffer holds");
+            GramArgs g{};
+            for (int i = 0; i < NA; ++i) g.a[i] = a[ti + i];
+            for (int j = 0; j < NB; ++j) g.b[j] = b[tj + j];
+            g.d = d; g.out = ew.parts; g.n = L.nloc;
+            with_int<1, 2, 3, 4>(NA, [&](auto ia) {
+                with_int<1, 2, 3, 4>(NB, [&](auto ib) {
+                    with_bool(d != nullptr, [&](auto w) {
+                        hipLaunchKernelGGL((block_gram<decltype(ia)::value, decltype(ib)::value, decltype(w)::value>), grid, blk, 0, c->stream, g);
+                    });
+                });
+            });
+            hipLaunchKernelGGL(fcg_fold, dim3(1), blk, 0, c->stream, ew.parts.get(), (int64_t)grid.x, NA * NB, ew.sums.get() + gb.used);
+            HIP_TRY(hipGetLastError());
+            gb.tiles.push_back({dst, ld, r0 + ti, c0 + tj, NA, NB, gb.used, sym || mirror, sym && tj == ti});
+            gb.used += (size_t)(NA * NB);
+        }
+    return 0;
+}
+
+// one download of everything enqueued, then every pair to its place
+int gram_collect(mg_context* c, EigsWork& ew, GramBatch& gb) {
+    std::vector<double> h(std::max<size_t>(1, gb.used));
+    HIP_TRY(hipMemcpyAsync(h.data(), ew.sums.get(), gb.used * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (const GramBatch::Tile& t : gb.tiles)
+        for (int i = 0; i < t.na; ++i)
+            for (int j = t.upper ? i : 0; j < t.nb; ++j) {
+                const double v = h[t.off + (size_t)(i * t.nb + j)];
+                t.dst[(size_t)(t.r + i) * t.ld + t.col + j] = v;
+                if (t.mirror) t.dst[(size_t)(t.col + j) * t.ld + t.r + i] = v;
+            }
+    gb.tiles.clear();
+    gb.used = 0;
+    return 0;
+}
+
+// out_o = sum_i coeff[i * no + o] s_i over the level's rows; an output may be one of the inputs
+int launch_block_combine(mg_context* c, const Level& L, int ns, const double* const* s, int no, const double* coeff, double* const* out) {
+    CombineArgs g{};
+    for (int i = 0; i < ns; ++i) g.s[i] = s[i];
+    for (int o = 0; o < no; ++o) g.out[o] = out[o];
+    for (int i = 0; i < ns * no; ++i) g.c[i] = coeff[i];
+    g.n = L.nloc;
+    const dim3 grid(gram_grid(c, L)), blk(BLOCK);
+    const bool known = with_int<1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21, 22, 23, 24>(ns, [&](auto is) {
+        with_int<1, 2, 3, 4, 5, 6, 7, 8>(no, [&](auto io) {
+            hipLaunchKernelGGL((block_combine<decltype(is)::value, decltype(io)::value>), grid, blk, 0, c->stream, g);
+        });
+    });
+    if (!known || no < 1 || no > BC_MAX_OUT) return fail("block_combine takes 1..24 inputs and 1..8 outputs");
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// what mg_block_gram and mg_block_combine refuse about the handle, the level and one array of device pointers
+int block_level_refusals(mg_context* c, const std::string& who, int level) {
+    if (!c) return fail("null handle");
+    if (c->dim != 3) return fail(who + ": the block kernels are 3-D only (this handle is 2-D)");
+    if (c->comm.active()) return fail(who + " needs a whole (not slab) handle");
+    MG_TRY(check_level(c, level));
+    if (c->L[level].flat) return fail(who + ": level " + std::to_string(level) + " is flat (no grid)");
+    return 0;
+}
+int block_pointer_refusals(mg_context* c, const std::string& who, int n, const double* const* p, const char* name) {
+    if (!p) return fail(who + ": null pointer array (" + name + ")");
+    for (int i = 0; i < n; ++i) {
+        const std::string what = std::string(name) + "[" + std::to_string(i) + "]";
+        MG_TRY(need_device_pointer(c, p[i], who.c_str(), what.c_str()));
+        if (reinterpret_cast<uintptr_t>(p[i]) % 16) return fail(who + ": " + what + " is not 16-byte aligned");
+    }
+    return 0;
+}
+
+// the first cell of a device rho that is not a finite double > 0, as an error (check_sigma's wording)
+int check_rho(mg_context* c, const std::string& who, const double* d_rho, int64_t n, int N) {
+    DevTemp d_first;
+    MG_TRY(d_first.alloc(sizeof(unsigned long long)));
+    HIP_TRY(hipMemsetAsync(d_first.p, 0xff, sizeof(unsigned long long), c->stream));
+    const unsigned nb = (unsigned)std::max<int64_t>(1, std::min<int64_t>(8192, (n + 255) / 256));
+    hipLaunchKernelGGL(rho_check, dim3(nb), dim3(256), 0, c->stream, d_rho, n, d_first.as<unsigned long long>());
+    HIP_TRY(hipGetLastError());
+    unsigned long long first = 0;
+    HIP_TRY(hipMemcpyAsync(&first, d_first.p, sizeof(first), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (first == ~0ull) return 0;
+    double x = 0.0;
+    HIP_TRY(hipMemcpy(&x, d_rho + first, sizeof(double), hipMemcpyDeviceToHost));
+    const int64_t q = (int64_t)first;
+    char val[40];
+    snprintf(val, sizeof(val), "%.17g", x);
+    return fail(who + ": rho must be finite and positive: cell (" + std::to_string(q % N) + ", " + std::to_string((q / N) % N) + ", " +
+                std::to_string(q / ((int64_t)N * N)) + ") = index " + std::to_string(q) + " holds " + val);
+}
+
+// the work vectors of mg_eigs for `block` vectors on `level` (kept: a call with the same level and a smaller block finds them)
+int ensure_eigs(mg_context* c, int level, int block) {
+    const Level& L = c->L[level];
+    EigsWork& ew = c->eigs;
+    if (ew.level != level || ew.vec_total != vec_total(L)) ew = EigsWork{};
+    ew.level = level;
+    ew.vec_total = vec_total(L);
+    MG_TRY(vec_alloc(c, L, &ew.m));
+    for (auto* set : {&ew.x, &ew.kx, &ew.kw, &ew.p, &ew.kp}) {
+        if ((int)set->size() < block) set->resize((size_t)block);
+        for (int j = 0; j < block; ++j) MG_TRY(vec_alloc(c, L, &(*set)[(size_t)j]));
+    }
+    ew.block = std::max(ew.block, block);
+    return ensure_block_scratch(c, L, ew);
+}
+
+// The iteration of mg_eigs (see include/mg_hip.h).  On entry lanes 0 .. block - 1 exist and `s` holds them.
+int eigs_solve(mg_context* c, BatchScope& s, int level, int k, int block, const double* rho_dev, double* const* x_dev, int warm,
+               double rtol, int max_iter, double* lambda, double* resid, int* iterations, int* restarts) {
+    const std::string who = "mg_eigs";
+    Level& L = c->L[level];
+    EigsWork& ew = c->eigs;
+    const int64_t n = L.nloc;
+    const int b = block;
+    const unsigned nbk = (unsigned)std::max<int64_t>(1, std::min<int64_t>(4096, (n + 255) / 256));
+    const dim3 fgrid(gram_grid(c, L)), blk(BLOCK);
+    std::vector<int> all((size_t)b);
+    for (int j = 0; j < b; ++j) all[(size_t)j] = j;
+
+    // M = R(rho), +0.0 on the Dirichlet nodes of the level's face set
+    {
+        DevTemp ones;
+        const int64_t cells = (int64_t)L.N * L.N * L.N;
+        if (!rho_dev) {
+            MG_TRY(ones.alloc((size_t)cells * sizeof(double)));
+            hipLaunchKernelGGL(eigs_fill, dim3(nbk), dim3(256), 0, c->stream, ones.as<double>(), cells, 1.0);
+            HIP_TRY(hipGetLastError());
+        }
+        MG_TRY(launch_reaction_diag(c, rho_dev ? rho_dev : ones.as<const double>(), ew.m.rows, L.N));
+        hipLaunchKernelGGL(eigs_mass_mask, dim3(nbk), dim3(256), 0, c->stream, ew.m.rows, level_box(L, L.faces), L.g.nx, L.g.ny, n);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(c->stream));       // (`ones` goes)
+    }
+    const double* const m = ew.m.rows;
+
+    // the start block
+    for (int j = 0; j < b; ++j) {
+        if (warm) {
+            MG_TRY(scatter_to(c, L, ew.x[(size_t)j], x_dev[j]));
+            hipLaunchKernelGGL(eigs_mask, dim3(nbk), dim3(256), 0, c->stream, ew.x[(size_t)j].rows, m, n);
+        } else {
+            hipLaunchKernelGGL(eigs_start, dim3(nbk), dim3(256), 0, c->stream, ew.x[(size_t)j].rows, m, n, (uint64_t)j * (uint64_t)L.n_global);
+        }
+        HIP_TRY(hipGetLastError());
+    }
+
+    // out_j = K x_j for the whole block: one fused launch per group of lanes on a matrix-free level, the level's SpMV per lane
+    // elsewhere.  xs null: x_j is the cycle's result, lane j's MG_VEC_V.
+    auto apply_K = [&](std::vector<DVector>* xs, std::vector<DVector>& outs) -> int {
+        auto one = [&](int j) {
+            return launch_ell(c, L, {.mode = MODE_SPMV, .x_base = xs ? (*xs)[(size_t)j].base : L.v.base, .out_rows = outs[(size_t)j].rows});
+        };
+        if (!mf_fused(c, L, all.size())) return s.each(all, one);
+        return mf_groups(c, s, L, MODE_SPMV, false, all,
+            [&](int j, const double** x, const double**, double** out, double** parts) {
+                *x = (xs ? (*xs)[(size_t)j].base : s.at(j, level).v.base) + L.g.lead; *out = outs[(size_t)j].rows; *parts = nullptr;
+            },
+            one, [](int, int) {});
+    };
+
+    // One Rayleigh-Ritz step on the columns S (and K S), `known` leading columns being M-orthonormal Ritz vectors with the
+    // values lam[] (their Gram blocks need no launch).  The columns are scaled to unit M-norm in the Gram matrices, and the scale
+    // goes into the coefficients: the same numbers as scaling the vectors, without a pass over them.  X, K X <- the b lowest
+    // Ritz vectors, P, K P <- their part outside X.  1: the Cholesky factorisation of S^T M S failed.
+    std::vector<double> lam((size_t)b, 0.0);
+    auto rayleigh_ritz = [&](int mcols, const std::vector<const double*>& S, const std::vector<const double*>& KS, int known) -> int {
+        std::vector<double> gk((size_t)(mcols * mcols), 0.0), gm((size_t)(mcols * mcols), 0.0);
+        GramBatch gb;
+        for (int pass = 0; pass < 2; ++pass) {
+            double* dst = pass == 0 ? gk.data() : gm.data();
+            const double* const* right = pass == 0 ? KS.data() : S.data();
+            const double* d = pass == 0 ? nullptr : m;
+            if (known > 0 && mcols > known)
+                MG_TRY(gram_enqueue(c, L, ew, gb, dst, mcols, 0, known, known, S.data(), mcols - known, right + known, d, false, true));
+            MG_TRY(gram_enqueue(c, L, ew, gb, dst, mcols, known, known, mcols - known, S.data() + known, mcols - known, right + known, d, true, false));
+        }
+        MG_TRY(gram_collect(c, ew, gb));
+        for (int i = 0; i < known; ++i) { gk[(size_t)(i * mcols + i)] = lam[(size_t)i]; gm[(size_t)(i * mcols + i)] = 1.0; }
+        std::vector<double> scale((size_t)mcols);
+        for (int i = 0; i < mcols; ++i) {
+            const double d = gm[(size_t)(i * mcols + i)];
+            if (!std::isfinite(d)) return fail(who + ": a basis vector has a non-finite M-norm");
+            if (!(d > 0.0)) return 1;       // (a zero column: as dependent as a basis gets)
+            scale[(size_t)i] = 1.0 / std::sqrt(d);
+        }
+        for (int i = 0; i < mcols; ++i)
+            for (int j = 0; j < mcols; ++j) {
+                gk[(size_t)(i * mcols + j)] *= scale[(size_t)i] * scale[(size_t)j];
+                gm[(size_t)(i * mcols + j)] = i == j ? 1.0 : gm[(size_t)(i * mcols + j)] * (scale[(size_t)i] * scale[(size_t)j]);
+            }
+        std::vector<double> theta((size_t)mcols), C((size_t)(mcols * mcols));
+        if (!dense_sym_def_eig(mcols, gk.data(), gm.data(), theta.data(), C.data())) return 1;
+        std::vector<double> cx((size_t)(mcols * b)), cp((size_t)(std::max(1, mcols - b) * b));
+        for (int i = 0; i < mcols; ++i)
+            for (int e = 0; e < b; ++e) {
+                const double v = C[(size_t)(i * mcols + e)] * scale[(size_t)i];
+                if (!std::isfinite(v)) return fail(who + ": the Ritz step gave a non-finite coefficient");
+                cx[(size_t)(i * b + e)] = v;
+                if (i >= b) cp[(size_t)((i - b) * b + e)] = v;
+            }
+        for (int e = 0; e < b; ++e) lam[(size_t)e] = theta[(size_t)e];
+        std::vector<double*> ox((size_t)b), okx((size_t)b), op((size_t)b), okp((size_t)b);
+        for (int e = 0; e < b; ++e) {
+            ox[(size_t)e] = ew.x[(size_t)e].rows; okx[(size_t)e] = ew.kx[(size_t)e].rows;
+            op[(size_t)e] = ew.p[(size_t)e].rows; okp[(size_t)e] = ew.kp[(size_t)e].rows;
+        }
+        // X before P: X reads the old P, P reads no X (rows of one launch are read before they are written: in place)
+        MG_TRY(launch_block_combine(c, L, mcols, S.data(), b, cx.data(), ox.data()));
+        MG_TRY(launch_block_combine(c, L, mcols, KS.data(), b, cx.data(), okx.data()));
+        if (mcols > b) {
+            MG_TRY(launch_block_combine(c, L, mcols - b, S.data() + b, b, cp.data(), op.data()));
+            MG_TRY(launch_block_combine(c, L, mcols - b, KS.data() + b, b, cp.data(), okp.data()));
+        }
+        return 0;
+    };
+
+    auto columns = [&](bool with_w, bool with_p, std::vector<const double*>& S, std::vector<const double*>& KS) {
+        S.clear(); KS.clear();
+        for (int j = 0; j < b; ++j) { S.push_back(ew.x[(size_t)j].rows); KS.push_back(ew.kx[(size_t)j].rows); }
+        if (with_w) for (int j = 0; j < b; ++j) { S.push_back(s.at(j, level).v.rows); KS.push_back(ew.kw[(size_t)j].rows); }
+        if (with_p) for (int j = 0; j < b; ++j) { S.push_back(ew.p[(size_t)j].rows); KS.push_back(ew.kp[(size_t)j].rows); }
+    };
+
+    // Rayleigh-Ritz on the start block alone: M-orthonormal X, K X and lambda
+    std::vector<const double*> S, KS;
+    MG_TRY(apply_K(&ew.x, ew.kx));
+    columns(false, false, S, KS);
+    {
+        const int rc = rayleigh_ritz(b, S, KS, 0);
+        if (rc == 1) return fail(who + ": the start block is linearly dependent to working precision (the Cholesky factorisation of X^T M X failed)");
+        MG_TRY(rc);
+    }
+
+    // `fresh`: X, K X and lambda come from a Rayleigh-Ritz step on X alone with K X applied and both Gram matrices computed (the
+    // start block's step).  The iteration rotates K X with X and takes X^T M X = I and X^T K X = diag lambda as known, and a nearly
+    // dependent [X W P] costs the Ritz vectors orthonormality of the order eps cond(S^T M S); so the block that is about to be
+    // returned takes such a step once more, and the stopping test is repeated on what it gives.
+    int it = 0, dropped = 0;
+    bool have_p = false, fresh = true;
+    std::vector<double> h(2 * (size_t)b);
+    for (;;) {
+        // R_j = K x_j - lambda_j M x_j into lane j's MG_VEC_F with both norms of the stopping test: one kernel per lane
+        for (int j = 0; j < b; ++j) {
+            EigsResidArgs a{ew.kx[(size_t)j].rows, ew.x[(size_t)j].rows, m, s.at(j, level).f.rows, ew.parts, lam[(size_t)j], n};
+            hipLaunchKernelGGL(eigs_residual, fgrid, blk, 0, c->stream, a);
+            hipLaunchKernelGGL(fcg_fold, dim3(1), blk, 0, c->stream, ew.parts.get(), (int64_t)fgrid.x, 2, ew.sums.get() + 2 * j);
+        }
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(h.data(), ew.sums.get(), h.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        bool converged = true;
+        for (int j = 0; j < b; ++j) {
+            resid[j] = std::sqrt(h[2 * (size_t)j]) / (std::fabs(lam[(size_t)j]) * std::sqrt(h[2 * (size_t)j + 1]));
+            if (j < k && !(resid[j] <= rtol)) converged = false;
+        }
+        if (converged || it >= max_iter) {
+            if (fresh) break;
+            MG_TRY(apply_K(&ew.x, ew.kx));
+            columns(false, false, S, KS);
+            const int rc = rayleigh_ritz(b, S, KS, 0);
+            if (rc == 1) return fail(who + ": the Ritz vectors are linearly dependent to working precision (the Cholesky factorisation of X^T M X failed)");
+            MG_TRY(rc);
+            fresh = true;
+            continue;
+        }
+        fresh = false;
+
+        // W = one V-cycle from a zero guess on each R_j, +0.0 on the Dirichlet rows; K W
+        MG_TRY(s.each(all, [&](int) { return zero_vec(c, L, L.v); }));
+        MG_TRY(vcycle_batch(c, s, level, all));
+        for (int j = 0; j < b; ++j) {
+            double* w = s.at(j, level).v.rows;
+            if (reinterpret_cast<uintptr_t>(w) % 16) return fail(who + ": misaligned iterate");
+            hipLaunchKernelGGL(eigs_mask, dim3(nbk), dim3(256), 0, c->stream, w, m, n);
+        }
+        HIP_TRY(hipGetLastError());
+        // W <- W - X (X^T M W).  The residual of a vector that has converged below the rounding of its Ritz value is that
+        // rounding times M x, whose cycle is a multiple of x: without the projection [X W] is then dependent to working precision.
+        {
+            columns(true, false, S, KS);
+            std::vector<double> xw((size_t)(b * b)), coeff((size_t)(2 * b * b), 0.0);
+            GramBatch gb;
+            MG_TRY(gram_enqueue(c, L, ew, gb, xw.data(), b, 0, 0, b, S.data(), b, S.data() + b, m, false, false));
+            MG_TRY(gram_collect(c, ew, gb));
+            for (int i = 0; i < b; ++i)
+                for (int j = 0; j < b; ++j) {
+                    if (!std::isfinite(xw[(size_t)(i * b + j)])) return fail(who + ": iteration " + std::to_string(it) + ": the cycle gave a non-finite vector");
+                    coeff[(size_t)(i * b + j)] = -xw[(size_t)(i * b + j)];
+                }
+            for (int j = 0; j < b; ++j) coeff[(size_t)((b + j) * b + j)] = 1.0;
+            std::vector<double*> w((size_t)b);
+            for (int j = 0; j < b; ++j) w[(size_t)j] = s.at(j, level).v.rows;
+            MG_TRY(launch_block_combine(c, L, 2 * b, S.data(), b, coeff.data(), w.data()));
+        }
+        MG_TRY(apply_K(nullptr, ew.kw));
+
+        columns(true, have_p, S, KS);
+        int rc = rayleigh_ritz((have_p ? 3 : 2) * b, S, KS, b);
+        if (rc == 1 && have_p) {        // [X W P] is dependent to working precision: once more without P
+            ++dropped;
+            columns(true, false, S, KS);
+            rc = rayleigh_ritz(2 * b, S, KS, b);
+        }
+        if (rc == 1)
+            return fail(who + ": iteration " + std::to_string(it) + ": the basis [X W] is linearly dependent to working precision (the Cholesky "
+                        "factorisation of its Gram matrix failed)");
+        MG_TRY(rc);
+        have_p = true;
+        ++it;
+    }
+
+    for (int j = 0; j < b; ++j) {
+        lambda[j] = lam[(size_t)j];
+        hipLaunchKernelGGL(eigs_mask, dim3(nbk), dim3(256), 0, c->stream, ew.x[(size_t)j].rows, m, n);
+        HIP_TRY(hipGetLastError());
+        MG_TRY(gather_from(c, L, ew.x[(size_t)j], x_dev[j]));
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (iterations) *iterations = it;
+    if (restarts) *restarts = dropped;
+    return 0;
+}
+
 int ensure_stage(mg_context* c, int64_t elems) {
     if ((int64_t)c->stage.count() >= elems) return 0;
     return c->stage.alloc(c, (size_t)elems);
@@ -6823,6 +7204,103 @@ int mg_release_batch(mg_handle c) {
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->lanes.clear();
+    c->eigs = EigsWork{};
+    return 0;
+}
+
+int mg_eigs(mg_handle c, int level, int k, int block, const double* rho_dev, double* const* x_dev, int warm, double rtol, int max_iter,
+            double* lambda, double* resid, int* iterations, int* restarts) {
+    const std::string who = "mg_eigs";
+    if (!c) return fail("null handle");
+    if (block < 1 || block > MG_EIGS_MAX)
+        return fail(who + ": block = " + std::to_string(block) + " is outside 1.." + std::to_string(MG_EIGS_MAX) + " (MG_EIGS_MAX)");
+    if (k < 1 || k > block) return fail(who + ": k = " + std::to_string(k) + " is outside 1..block = " + std::to_string(block));
+    if (!(rtol > 0.0) && max_iter <= 0) return fail(who + ": rtol <= 0 and max_iter <= 0: nothing would stop the iteration");
+    if (!lambda || !resid) return fail(who + ": null pointer (lambda, resid)");
+    MG_TRY(batch_refusals(c, who, level, block, nullptr, nullptr, x_dev, nullptr, nullptr, "x_dev"));
+    if (level < 1) return fail(who + ": level 0 is the coarsest level: the V-cycle preconditioner needs level >= 1");
+    for (int l = 0; l <= level; ++l) {
+        MG_TRY(need_matrix(c, l));
+        MG_TRY(need_grid(c, l));
+        if (c->L[l].mf && l >= 1 && (c->smoother == MG_SMOOTH_RBGS || c->smoother == MG_SMOOTH_MCGS))
+            return fail(who + ": level " + std::to_string(l) + " is a matrix-free diffusion level: Gauss-Seidel smoothers (RBGS, MCGS) "
+                        "need stored rows; use Jacobi or Chebyshev");
+    }
+    MG_TRY(face_set_refusals(c, level));
+    const Level& L = c->L[level];
+    const int64_t n1 = (int64_t)L.N + 1;
+    if (L.N < 1 || L.n_global != n1 * n1 * n1 || L.g.lead != 0 || L.xlen != L.nloc)
+        return fail(who + ": level " + std::to_string(level) + " is no whole grid of (N + 1)^3 nodes");
+    if (rho_dev) {
+        MG_TRY(need_device_pointer(c, rho_dev, who.c_str(), "rho_dev"));
+        MG_TRY(check_rho(c, who, rho_dev, (int64_t)L.N * L.N * L.N, L.N));
+    }
+    MG_TRY(prepare_cycle(c, level));
+    MG_TRY(ensure_lanes(c, block, 0, level));
+    MG_TRY(ensure_eigs(c, level, block));
+    BatchScope s(c, 0, level, block);
+    return eigs_solve(c, s, level, k, block, rho_dev, x_dev, warm, rtol, max_iter, lambda, resid, iterations, restarts);
+}
+
+int mg_block_gram(mg_handle c, int level, int na, const double* const* a_dev, int nb, const double* const* b_dev, const double* d_dev,
+                  double* out) {
+    const std::string who = "mg_block_gram";
+    MG_TRY(block_level_refusals(c, who, level));
+    if (na < 1 || na > BC_MAX_IN || nb < 1 || nb > BC_MAX_IN)
+        return fail(who + ": na = " + std::to_string(na) + ", nb = " + std::to_string(nb) + ": both must be in 1.." + std::to_string(BC_MAX_IN));
+    if (!out) return fail(who + ": null pointer (out)");
+    HIP_TRY(hipSetDevice(c->device));
+    MG_TRY(block_pointer_refusals(c, who, na, a_dev, "a_dev"));
+    MG_TRY(block_pointer_refusals(c, who, nb, b_dev, "b_dev"));
+    if (d_dev) MG_TRY(block_pointer_refusals(c, who, 1, &d_dev, "d_dev"));
+    const Level& L = c->L[level];
+    bool sym = na == nb;
+    for (int i = 0; sym && i < na; ++i) sym = a_dev[i] == b_dev[i];
+    // (scratch of this call: freed on return, mg_memory_bytes is as before)
+    EigsWork scratch;
+    MG_TRY(ensure_block_scratch(c, L, scratch));
+    GramBatch gb;
+    MG_TRY(gram_enqueue(c, L, scratch, gb, out, nb, 0, 0, na, a_dev, nb, b_dev, d_dev, sym, false));
+    return gram_collect(c, scratch, gb);
+}
+
+int mg_block_combine(mg_handle c, int level, int ns, const double* const* s_dev, int no, const double* coeff, double* const* out_dev) {
+    const std::string who = "mg_block_combine";
+    MG_TRY(block_level_refusals(c, who, level));
+    if (ns < 1 || ns > BC_MAX_IN) return fail(who + ": ns = " + std::to_string(ns) + " is outside 1.." + std::to_string(BC_MAX_IN));
+    if (no < 1 || no > BC_MAX_OUT) return fail(who + ": no = " + std::to_string(no) + " is outside 1.." + std::to_string(BC_MAX_OUT));
+    if (!coeff) return fail(who + ": null pointer (coeff)");
+    HIP_TRY(hipSetDevice(c->device));
+    MG_TRY(block_pointer_refusals(c, who, ns, s_dev, "s_dev"));
+    MG_TRY(block_pointer_refusals(c, who, no, out_dev, "out_dev"));
+    const Level& L = c->L[level];
+    const size_t len = (size_t)L.n_global * sizeof(double);
+    for (int o = 0; o < no; ++o) {
+        for (int q = 0; q < o; ++q)
+            if (overlaps(out_dev[o], len, out_dev[q], len))
+                return fail(who + ": out_dev[" + std::to_string(o) + "] overlaps out_dev[" + std::to_string(q) + "]");
+        for (int i = 0; i < ns; ++i)
+            if (out_dev[o] != s_dev[i] && overlaps(out_dev[o], len, s_dev[i], len))
+                return fail(who + ": out_dev[" + std::to_string(o) + "] overlaps s_dev[" + std::to_string(i) + "] without being it: an output "
+                            "may be one of the inputs, nothing in between");
+    }
+    MG_TRY(launch_block_combine(c, L, ns, s_dev, no, coeff, out_dev));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int mg_eigs_info(mg_handle c, int* block, int64_t* bytes) {
+    if (!c) return fail("null handle");
+    if (block) *block = c->eigs.block;
+    if (bytes) *bytes = c->eigs.bytes();
+    return 0;
+}
+
+int mg_release_eigs(mg_handle c) {
+    if (!c) return fail("null handle");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    c->eigs = EigsWork{};
     return 0;
 }
 

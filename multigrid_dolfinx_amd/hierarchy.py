@@ -1000,6 +1000,78 @@ class DeviceHierarchy:
         """Frees the lanes of batched solves (`mg_release_batch`); the next batch call allocates them again."""
         check(self._lib.mg_release_batch(self._h))
 
+    # ---- smallest eigenpairs of the level's operator against the lumped mass M(rho) --------------------
+    def eigs(self, k: int, block: Optional[int] = None, rho=None, x_ptrs=None, warm: bool = False, rtol: float = 1e-8,
+             max_iter: int = 100, level: Optional[int] = None) -> dict:
+        """`mg_eigs`: the `k` smallest eigenpairs of K u = lambda M(rho) u on `level` (default: the finest) by LOBPCG with one
+        V-cycle per vector and iteration as preconditioner, on a block of `block` vectors (default min(MG_EIGS_MAX, k + 2); the
+        vectors beyond k are guards).  `rho`: None (rho = 1), an integer device address of N^3 float64, or an array of N^3 cell
+        values (uploaded for the call).  `x_ptrs`: `block` integer device addresses of `n_dofs(level)` float64 in the caller's
+        DoF numbering -- the start block with `warm=True`, the M-orthonormal Ritz vectors on return; None: buffers of the call,
+        returned as the NumPy array "x" of shape (block, n_dofs).  Returns {"lambda", "resid", "iterations", "restarts"[, "x"]};
+        reaching `max_iter` is not an error.  The handle's own "v", "f" and "r" are unspecified afterwards."""
+        level = self.finest_level if level is None else level
+        block = min(_capi.MG_EIGS_MAX, int(k) + 2) if block is None else int(block)
+        held = []
+        try:
+            if rho is None or isinstance(rho, (int, np.integer)):
+                rho_ptr = None if rho is None else C.c_void_p(int(rho))
+            else:
+                host = _capi.as_f64(rho)
+                held.append(_DeviceArray(self._lib, self.device, host.size, host))
+                rho_ptr = held[-1].ptr
+            own = x_ptrs is None
+            if own:
+                if warm:
+                    raise ValueError("a warm start needs x_ptrs")
+                xs = [_DeviceArray(self._lib, self.device, self.n_dofs(level)) for _ in range(max(0, block))]
+                held += xs
+                x_ptrs = [a.ptr.value for a in xs]
+            lam, res = np.zeros(max(1, block)), np.zeros(max(1, block))
+            its, restarts = C.c_int(), C.c_int()
+            check(self._lib.mg_eigs(self._h, self._idx(level), int(k), block, rho_ptr, self._ptr_array(x_ptrs), int(bool(warm)),
+                                    float(rtol), int(max_iter), ptr(lam), ptr(res), C.byref(its), C.byref(restarts)))
+            out = {"lambda": lam[:block].copy(), "resid": res[:block].copy(), "iterations": int(its.value),
+                   "restarts": int(restarts.value)}
+            if own:
+                out["x"] = np.stack([a.download() for a in xs])
+            return out
+        finally:
+            for a in held:
+                a.free()
+
+    def block_gram(self, a_ptrs, b_ptrs, d_ptr=None, level: Optional[int] = None) -> np.ndarray:
+        """`mg_block_gram`: the matrix a_i . (d * b_j) of vectors of `level` (default: the finest) given as integer device
+        addresses of `n_dofs(level)` float64, 16-byte aligned; `d_ptr`: a nodal weight or None.  Deterministic, and a pair has
+        the same bits whatever the shape of the call; the same pointers on both sides give a symmetric matrix from its upper
+        tiles."""
+        level = self.finest_level if level is None else level
+        na, nb = len(a_ptrs), len(b_ptrs)
+        out = np.zeros((max(1, na), max(1, nb)))
+        check(self._lib.mg_block_gram(self._h, self._idx(level), na, self._ptr_array(a_ptrs), nb, self._ptr_array(b_ptrs),
+                                      None if d_ptr is None else C.c_void_p(int(d_ptr)), ptr(out)))
+        return out[:na, :nb].copy()
+
+    def block_combine(self, s_ptrs, coeff, out_ptrs, level: Optional[int] = None):
+        """`mg_block_combine`: out_o = sum_i coeff[i, o] s_i on vectors of `level` given as integer device addresses; an output
+        may be one of the inputs."""
+        level = self.finest_level if level is None else level
+        ns, no = len(s_ptrs), len(out_ptrs)
+        c = np.ascontiguousarray(np.asarray(coeff, dtype=np.float64))
+        if c.shape != (ns, no):
+            raise ValueError(f"coeff has shape {c.shape}, expected {(ns, no)}")
+        check(self._lib.mg_block_combine(self._h, self._idx(level), ns, self._ptr_array(s_ptrs), no, ptr(c), self._ptr_array(out_ptrs)))
+
+    def eigs_info(self) -> dict:
+        """The largest block `eigs` has work vectors for, and their device bytes (`mg_eigs_info`)."""
+        blk, b = C.c_int(), C.c_int64()
+        check(self._lib.mg_eigs_info(self._h, C.byref(blk), C.byref(b)))
+        return {"block": int(blk.value), "bytes": int(b.value)}
+
+    def release_eigs(self):
+        """Frees the work vectors of `eigs` (`mg_release_eigs`); the next call allocates them again."""
+        check(self._lib.mg_release_eigs(self._h))
+
     def set_mass(self, level: int, M):
         """The P1 mass matrix of `level` (SciPy CSR, the level's DoF numbering) for the L2(Omega) norms of fmg."""
         indptr, is64, indices, data = _csr_arrays(M)

@@ -1349,3 +1349,29 @@ def diffusion_lift(N: int, kappa, g, dirichlet_faces=ALL_FACES) -> np.ndarray:
         raise ValueError(f"vector has {gv.size} entries, the level has {n1 ** 3} nodes")
     gb = np.where(dirichlet_mask(N, dirichlet_faces), gv, 0.0)
     return diffusion_apply_dkappa(N, kappa, gb, "interior", "all", dirichlet_faces)
+
+
+def diffusion_eigs_reference(N: int, kappa, k: int, rho=None, dirichlet_faces=ALL_FACES, sigma=None, robin=None):
+    """The `k` smallest eigenpairs of K u = lambda M(rho) u on the host: K the free block of `diffusion_level(N, 3, kappa, ...)`
+    (A(kappa) + R(sigma) + B(alpha)), M(rho) = `reaction_diag(N, rho)` on the free nodes (rho = 1: None), by
+    `scipy.sparse.linalg.eigsh` in shift-invert mode at 0.  Returns (lam, U): lam ascending, U of shape (k, (N + 1)^3) with
+    u^T M u = 1 and +0.0 on the Dirichlet nodes.  The host statement of what `mg_eigs` computes; the sign of a vector and the
+    basis of a degenerate cluster are eigsh's."""
+    from scipy.sparse.linalg import eigsh
+    n1 = N + 1
+    free = np.flatnonzero(~dirichlet_mask(N, dirichlet_faces))
+    A = diffusion_level(N, 3, kappa, dirichlet_faces=dirichlet_faces, sigma=sigma, robin=robin).A.tocsr()
+    K = A[free][:, free].tocsc()
+    m = reaction_diag(N, np.ones(N ** 3) if rho is None else rho, dirichlet_faces)[free]
+    if not np.all(m > 0.0):
+        raise ValueError("rho must be positive")
+    if not 1 <= k < free.size:
+        raise ValueError(f"k = {k} is outside 1..{free.size - 1}")
+    v0 = np.cos(np.arange(free.size) * 0.7311 + 0.3)          # (a fixed start: the same call gives the same numbers)
+    lam, V = eigsh(K, k=k, M=sp.diags(m).tocsc(), sigma=0.0, which="LM", v0=v0, tol=0)
+    order = np.argsort(lam, kind="stable")
+    lam, V = lam[order], V[:, order]
+    V = V / np.sqrt(np.einsum("ij,i,ij->j", V, m, V))
+    U = np.zeros((k, n1 ** 3))
+    U[:, free] = V.T
+    return lam, U

@@ -261,6 +261,29 @@ class DiffusionSolver:
             rhs = torch.stack([self._lifted(kv, gv[b], Fv[b]) for b in range(B)])
         return _Solve.apply(kappa, rhs.view(F.shape), self, op, "forward", True, True, sigma, bits, *alphas)
 
+    def eigenpairs(self, kappa: torch.Tensor, k: int, *, rho: Optional[torch.Tensor] = None, sigma: Optional[torch.Tensor] = None,
+                   robin=None, block: Optional[int] = None, x0: Optional[torch.Tensor] = None, rtol: float = 1e-8,
+                   max_iter: int = 100, same_operator: bool = False):
+        """The `k` smallest eigenpairs of K u = lambda M(rho) u, K = A(kappa) + R(sigma) + B(alpha) on the free nodes and
+        M(rho) = R(rho) the lumped mass (rho: N^3 float64 > 0 on the solver's device; None: 1): the decay rates and shapes of
+        rho u_t = div(kappa grad u) - sigma u under the solver's boundary conditions, by `DeviceHierarchy.eigs` (LOBPCG, one
+        V-cycle per vector and iteration; `block` vectors, default min(MG_EIGS_MAX, k + 2)).  The operator is put in place as
+        `solve` puts it; `same_operator=True` reuses the generation of the last solve.  Returns `(lam, U)`: `lam` of shape
+        (k,), ascending; `U` of shape (k, N + 1, N + 1, N + 1), detached, u^T M u = 1, exactly 0 on the Dirichlet nodes, each
+        vector's sign chosen so that its entry of largest magnitude is positive (the lowest index on ties).  `x0`: a previous
+        `U`, or a (block, ...) tensor, as a warm start (rows it lacks are filled with seeded noise).  Raises `NotConverged`
+        when one of the first k residuals ||K u - lam M u|| / (lam ||M u||) is above `rtol` after `max_iter` iterations.
+
+        `lam` is differentiable to FIRST order in kappa, sigma, every alpha and rho: d lam_j = D(u_j, u_j) . dkappa +
+        D_sigma(u_j, u_j) . dsigma + D_F(u_j, u_j) . dalpha_F - lam_j D_sigma(u_j, u_j) . drho, one sensitivity launch per
+        vector and field and no solve.  That gradient is defined for a SIMPLE eigenvalue and for the SUM over a whole cluster
+        of equal eigenvalues; it is NOT defined for one member of a degenerate cluster, whose vector is an arbitrary element
+        of the eigenspace (the closed-form cube's (1,1,2) triple, say): differentiate the cluster's sum, or break the
+        symmetry.  Second derivatives need eigenvector derivatives and are not provided: differentiating twice raises."""
+        bits, alphas = self._robin_inputs(robin)
+        op = self._operator_to_reuse(same_operator, sigma, bits)
+        return _Eigs.apply(kappa, self, op, int(k), block, x0, float(rtol), int(max_iter), rho, sigma, bits, *alphas)
+
     def _top_level_grid(self):
         """The kernels of `robin_apply`, `reaction_apply` and `gradient` read the top level's grid and nothing else: before the
         first solve has generated the level, it becomes a grid-only level."""
@@ -618,6 +641,79 @@ class _Solve(torch.autograd.Function):
 
         grads = [minus_d(0, _kappa_field("interior", "interior")), lam if ctx.needs_input_grad[1] else None, None, None, None,
                  None, None, minus_d(7, _SIGMA_FIELD), None] + [minus_d(9 + q, _alpha_field(bit)) for q, bit in enumerate(ctx.bits)]
+        return tuple(grads[:ctx.n_inputs])
+
+
+class _Eigs(torch.autograd.Function):
+    """(lam, U) of `DiffusionSolver.eigenpairs`.  Backward: sum_j lam_bar_j (d lam_j / d field) with the first-order formulas
+    of an M-normalised eigenvector, by the D entries at (u_j, u_j); once differentiable."""
+
+    @staticmethod
+    def forward(ctx, kappa, solver, op, k, block, x0, rtol, max_iter, rho, sigma, bits, *alphas):
+        from ._capi import MG_EIGS_MAX
+        h, n = solver.hierarchy, solver.hierarchy.n_dofs(solver.top)
+        block = min(MG_EIGS_MAX, k + 2) if block is None else int(block)
+        if not 1 <= k <= block <= MG_EIGS_MAX:
+            raise ValueError(f"1 <= k <= block <= {MG_EIGS_MAX} (MG_EIGS_MAX) is required, got k = {k}, block = {block}")
+        rho_kept = None
+        if rho is not None:
+            rho_kept = solver._holds(rho, solver.N ** 3, "rho").detach().reshape(-1).contiguous()
+        X = torch.zeros(block, n, dtype=torch.float64, device=solver.device)
+        if x0 is not None:
+            if x0.dtype != torch.float64 or x0.device != solver.device or x0.dim() < 2 or x0[0].numel() != n or not 1 <= x0.shape[0] <= block:
+                raise ValueError(f"x0 must hold 1..{block} leading rows of {n} float64 on {solver.device}")
+            have = x0.shape[0]
+            X[:have] = x0.detach().reshape(have, n)
+            if have < block:
+                X[have:] = torch.randn(block - have, n, dtype=torch.float64, generator=torch.Generator().manual_seed(have)).to(solver.device)
+        if op is None:
+            op = solver._put_operator(kappa, sigma, dict(zip(bits, alphas)))
+        elif op.generation != solver._generation:       # another kappa has been solved since: this one's operator again
+            op.generation = solver._generate(op.kappa_kept, op.sigma_kept, op.robin_kept)
+        torch.cuda.current_stream(solver.device).synchronize()      # X and rho are complete before the handle's stream reads them
+        out = h.eigs(k, block, rho=None if rho_kept is None else rho_kept.data_ptr(), x_ptrs=[X.data_ptr() + 8 * n * j for j in range(block)],
+                     warm=x0 is not None, rtol=rtol, max_iter=max_iter, level=solver.top)
+        solver.last_iterations["eigs"] = out["iterations"]
+        solver.last_residual["eigs"] = float(out["resid"][:k].max())
+        solver.last_eigs = out
+        if not bool((out["resid"][:k] <= rtol).all()):
+            raise NotConverged(f"the eigenpairs reached max_iter = {max_iter} with residuals "
+                               f"{', '.join('%.3e' % r for r in out['resid'][:k])} (rtol {rtol:g})")
+        U = X[:k]
+        at = U.abs().argmax(dim=1, keepdim=True)
+        U = U * torch.where(U.gather(1, at) < 0, -1.0, 1.0)
+        lam = torch.tensor(out["lambda"][:k], dtype=torch.float64, device=solver.device)
+        coefficients = {0: kappa, 8: rho, 9: sigma, **{11 + q: a for q, a in enumerate(alphas)}}
+        ctx.like = {i: (c.shape, c.device) for i, c in coefficients.items() if c is not None}
+        ctx.wanted = {i: i in ctx.like and ctx.needs_input_grad[i] for i in coefficients}
+        ctx.solver, ctx.bits, ctx.n_inputs = solver, bits, 11 + len(alphas)
+        ctx.save_for_backward(lam, U)
+        U = U.view(k, solver.N + 1, solver.N + 1, solver.N + 1)
+        ctx.mark_non_differentiable(U)
+        return lam, U
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_lam, grad_U):
+        solver = ctx.solver
+        lam, U = ctx.saved_tensors
+        g = grad_lam.to(solver.device)
+
+        def d(field, j):
+            return _launch(solver, lambda *args: field.d(solver.hierarchy, *args), solver.N ** field.power, U[j], U[j])
+
+        def summed(i, field, weight=None):
+            if not ctx.wanted[i]:
+                return None
+            acc = None
+            for j in range(U.shape[0]):
+                term = (g[j] if weight is None else g[j] * weight[j]) * d(field, j)
+                acc = term if acc is None else acc + term
+            shape, device = ctx.like[i]
+            return acc.view(shape).to(device)
+
+        grads = [summed(0, _kappa_field("interior", "interior"))] + [None] * 7 + [summed(8, _SIGMA_FIELD, -lam), summed(9, _SIGMA_FIELD), None]
+        grads += [summed(11 + q, _alpha_field(bit)) for q, bit in enumerate(ctx.bits)]
         return tuple(grads[:ctx.n_inputs])
 
 

@@ -4,7 +4,8 @@ code object's notes.
     python tools/kernel_resources.py [text=jacobikc]
 
 Names behind tables of DESIGN.md: jacobikc (every tile shape of the K-sweep march, `sdia_jacobikc_rim` of shape 9 included),
-jk3_plan (`jk3_plan` and `jk3_plan_rim`), diffusion_mf, diffusion_mf_batch, diffusion_dkappa, kappa_ingest, cell_grad.
+jk3_plan (`jk3_plan` and `jk3_plan_rim`), diffusion_mf, diffusion_mf_batch, diffusion_dkappa, kappa_ingest, cell_grad,
+block_gram, block_combine.
 """
 import os
 import re
