@@ -282,6 +282,37 @@ enum mg_face { MG_FACE_XLO = 1, MG_FACE_XHI = 2, MG_FACE_YLO = 4, MG_FACE_YHI = 
 int mg_set_diffusion_faces(mg_handle h, int dirichlet_faces);
 /* *dirichlet_faces = the handle's face set */
 int mg_diffusion_faces(mg_handle h, int* dirichlet_faces);
+/* Insulated bodies: no Dirichlet node at all (no reference counterpart).  mg_set_diffusion_insulated puts the handle's face
+ * set at "no Dirichlet node": mg_diffusion_faces then reports 0, every node of a level generated from now on is a free node
+ * with the natural row, and Robin fields may sit on any of the six faces.  3-D whole handles only: 2-D and slab handles are
+ * refused by name, the handle left as it was.  A later mg_set_diffusion_faces with a valid set leaves the state;
+ * mg_set_diffusion_faces(h, 0) stays refused as before.  Everything a face set other than 63 refuses stays refused.
+ * With every node free A(kappa) has zero row sums: its null space is the constants.  Two cases, by what the levels held
+ * when they were generated:
+ *   - regular: a reaction diagonal (mg_set_diffusion_reaction) or at least one Robin diagonal (mg_set_diffusion_robin)
+ *     makes the operator regular, and every call works as on any face set; nothing is projected.  A field that is zero
+ *     everywhere is the caller's mistake: the solve does not converge.
+ *   - singular: neither.  Let w be the lumped mass of rho = 1 on the all-free grid (w_i = the integral of the hat
+ *     function, reaction_diag of ones), s = w.1, Q = I - 1 w^T / s.  mg_pcg computes x = Q A^+ Q^T b, that is
+ *         A x = b - w (1.b) / s,   w.x = 0:
+ *     a uniform source density is taken off the load to make it compatible, and the solution has integral zero.
+ *     mg_pcg turns the right-hand side into Q^T b once, makes every preconditioned residual mean-free (Euclidean
+ *     weights) before it is used, returns Q x in MG_VEC_V and tests ||r|| <= rtol ||Q^T b||.  A projected right-hand side
+ *     of zero gives Q x0 after zero iterations.  MG_VEC_F holds the projected load Q^T b after the call (not the caller's
+ *     b), and MG_VEC_R = Q^T b - A x.  The coarsest level is factorised with node 0 pinned (identity row, column dropped),
+ *     solved with a mean-free right-hand side and made mean-free: the pseudo-inverse for a consistent load, in the same
+ *     launches as the regular solve and in a captured cycle; the coarse CG ("coarse_direct" 0) gets the same two
+ *     projections.  mg_vcycle and mg_prepare_cycle work.  Refused by name in the singular case, before anything is
+ *     launched: mg_pcg_batch, mg_eigs, mg_fmg, and cycles with the Chebyshev or a Gauss-Seidel smoother.
+ * w lives with the handle (built at the first projected solve, counted in mg_memory_bytes, freed with the handle). */
+int mg_set_diffusion_insulated(mg_handle h);
+/* *singular = 1 where solves from `level` run projected: the levels 0 .. level were generated on an insulated handle and
+ * none of them holds a reaction or Robin diagonal; else 0 */
+int mg_diffusion_nullspace(mg_handle h, int level, int* singular);
+/* x -= mean in place over n doubles of device memory, *mean = the mean removed: (w.x) / (w.1) with weights, (1.x) / n with
+ * w_dev null.  x_dev and w_dev are 16-byte aligned.  Deterministic: per-workgroup partial sums in a fixed order over a grid
+ * that depends on n only, folded by one block; no floating-point atomics, the same bits on every run. */
+int mg_remove_mean(mg_handle h, double* x_dev, const double* w_dev, int64_t n, double* mean);
 /* A lumped reaction term for the generated diffusion levels (no reference counterpart): the operator A(kappa) + R(sigma) of
  * -div(kappa grad u) + sigma u, R diagonal.  sigma is one double per cell of a 3-D grid of elements_per_dim^3 cells, in the cell
  * order of mg_gen_diffusion_level, finite and >= 0 (zero is allowed).  R of a cell field w is the row-sum lumped P1 mass of the

@@ -65,6 +65,9 @@ SIGNATURES = {
     "mg_level_matrix_free": [_H, C.c_int, _ip, _i64p],
     "mg_set_diffusion_faces": [_H, C.c_int],
     "mg_diffusion_faces": [_H, _ip],
+    "mg_set_diffusion_insulated": [_H],
+    "mg_diffusion_nullspace": [_H, C.c_int, _ip],
+    "mg_remove_mean": [_H, C.c_void_p, C.c_void_p, C.c_int64, _dp],
     "mg_set_diffusion_reaction": [_H, C.c_int, C.c_void_p],
     "mg_set_diffusion_reaction_device": [_H, C.c_int, C.c_void_p],
     "mg_diffusion_reaction": [_H, _ip, _ip],

@@ -16,6 +16,7 @@
 #include "mg_diffusion_points.hip.h"
 #include "mg_diffusion_kappa.hip.h"
 #include "mg_block.hip.h"
+#include "mg_nullspace.hip.h"
 #include "mg_dense_eig.h"
 
 #include <dlfcn.h>
@@ -236,6 +237,7 @@ struct Level {
 // Block-tridiagonal LU of the coarsest level (mg_direct.hip.h)
 struct DirectSolver {
     bool tried = false, ok = false;
+    bool pinned = false;                    // a singular level 0 (level_singular): factorised with node 0 pinned
     BtGeom g{};
     DevBuf<double> T;                       // nb dense p x p inverses of the Schur complements
     DevBuf<int> lcol, ucol;                 // couplings, nb * p * W each
@@ -357,6 +359,12 @@ struct mg_context {
                                     // measured slower than nine colour launches: 9.1 against 6.8 ms per sweep of the 513^3 lattice)
     int diffusion_faces = MG_FACES_ALL;     // mg_set_diffusion_faces: the faces with a Dirichlet condition in the diffusion levels generated
                                     // from now on, and what MG_NODES_INTERIOR masks; the other faces are no-flux faces
+    // insulated bodies (mg_set_diffusion_insulated sets the face set 0): the lumped mass w of rho = 1 on the all-free grid of
+    // ns_N cells per dimension with 1 / (w.1), built at the first projected solve of a level of that size, and the mean
+    // removals' partial sums and total (ns_part: ns_blocks(rows) + 1 doubles, the total last)
+    DevBuf<double> ns_w, ns_part;
+    int ns_N = 0;
+    double ns_inv_s = 0.0;
     DevBuf<double> sigma;           // mg_set_diffusion_reaction: the handle's copy of sigma, sigma_N^3 cells (empty: no reaction term), read
     int sigma_N = 0;                // where diffusion levels are generated
     DevBuf<double> alpha[6];        // mg_set_diffusion_robin: the handle's copies of the Robin fields by face bit (x-, x+, y-, y+, z-, z+),
@@ -3086,6 +3094,84 @@ int cheb_interval(mg_context* c, int level, double* lo, double* hi) {
 
 void free_direct(mg_context* c) { c->direct = DirectSolver{}; }
 
+// ---- insulated bodies: levels with no Dirichlet node (mg_set_diffusion_insulated) -----------------------------------------
+// A generated level with the face set 0 and neither a reaction nor a Robin diagonal has zero row sums: its null space is the
+// constants.  A cycle from `level` is singular when its levels are (face_set_refusals: they share one face set).
+bool level_singular(const Level& L) { return L.set && L.faces == 0 && !L.react && !L.robin; }
+bool cycle_singular(const mg_context* c, int level) {
+    for (int l = 0; l <= level; ++l)
+        if (!level_singular(c->L[l])) return false;
+    return true;
+}
+
+// what has no projected form (batched solves, eigenpairs, FMG) refuses a singular cycle by name, before anything is launched
+int singular_refusal(const mg_context* c, const std::string& who, int level) {
+    if (!cycle_singular(c, level)) return 0;
+    return fail(who + ": the levels are those of an insulated body with neither a reaction nor a Robin term (mg_set_diffusion_insulated): "
+                "the operator is singular, and only mg_pcg, mg_vcycle and the single-level operations handle its null space");
+}
+
+// the partial sums of a mean removal over n rows; an allocation: not inside a capture (prepare_cycle, fcg_start)
+// (sized for the largest level that is set, so a cycle from a higher level finds it in place; should it grow all the same,
+// the captured cycles that hold its address go first)
+void drop_graphs(mg_context* c);
+int ns_workspace(mg_context* c, int64_t n) {
+    for (int l = 0; l < c->nlev; ++l)
+        if (c->L[l].set) n = std::max<int64_t>(n, c->L[l].nloc);
+    const size_t need = (size_t)ns_blocks(n) + 1;
+    if (c->ns_part.count() >= need) return 0;
+    drop_graphs(c);
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return c->ns_part.alloc(c, need);
+}
+
+// x -= u * inv_denom * sum(w x) over n rows (w null: sum(x); u null: the constant), mg_nullspace.hip.h; x, w and u are
+// 16-byte aligned row pointers.  Three kernel launches and nothing else, so a captured cycle gains kernel nodes only.
+int ns_remove(mg_context* c, double* x, const double* w, const double* u, int64_t n, double inv_denom, double* mean_out = nullptr) {
+    for (const double* v : {(const double*)x, w, u})
+        if (reinterpret_cast<uintptr_t>(v) % 16) return fail("mean removal: misaligned vector");
+    const int64_t nb = ns_blocks(n);
+    if ((int64_t)c->ns_part.count() < nb + 1) return fail("mean removal: no workspace");
+    double* const part = c->ns_part;
+    hipLaunchKernelGGL(ns_partial, dim3((unsigned)nb), dim3(BLOCK), 0, c->stream, (const double*)x, w, n, part);
+    hipLaunchKernelGGL(fcg_fold, dim3(1), dim3(BLOCK), 0, c->stream, (const double*)part, nb, 1, part + nb);
+    hipLaunchKernelGGL(ns_subtract, dim3((unsigned)nb), dim3(BLOCK), 0, c->stream, x, u, n, (const double*)(part + nb), inv_denom, mean_out);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int launch_reaction_diag(mg_context* c, const double* w, double* out, int N);
+
+// w = the lumped mass of rho = 1 on the all-free grid of L (reaction_diag of ones) and 1 / (w.1); kept until a level of
+// another size asks.  Allocates and synchronises: not inside a capture.
+int ns_weights(mg_context* c, const Level& L) {
+    const int64_t n1 = (int64_t)L.N + 1;
+    if (L.N < 1 || L.n_global != n1 * n1 * n1 || L.g.lead != 0 || L.xlen != L.nloc)
+        return fail("insulated solve: the level is no whole grid of (N + 1)^3 nodes");
+    MG_TRY(ns_workspace(c, L.nloc));
+    if (c->ns_w && c->ns_N == L.N) return 0;
+    c->ns_N = 0;
+    const size_t cells = (size_t)L.N * L.N * L.N;
+    DevTemp ones;
+    MG_TRY(ones.alloc(cells * 8));
+    std::vector<double> h(cells, 1.0);
+    HIP_TRY(hipMemcpyAsync(ones.p, h.data(), cells * 8, hipMemcpyHostToDevice, c->stream));
+    MG_TRY(c->ns_w.alloc(c, (size_t)L.nloc));
+    MG_TRY(launch_reaction_diag(c, ones.as<const double>(), c->ns_w, L.N));
+    const int64_t nb = ns_blocks(L.nloc);
+    double* const part = c->ns_part;
+    hipLaunchKernelGGL(ns_partial, dim3((unsigned)nb), dim3(BLOCK), 0, c->stream, (const double*)c->ns_w, (const double*)nullptr, (int64_t)L.nloc, part);
+    hipLaunchKernelGGL(fcg_fold, dim3(1), dim3(BLOCK), 0, c->stream, (const double*)part, nb, 1, part + nb);
+    HIP_TRY(hipGetLastError());
+    double s = 0.0;
+    HIP_TRY(hipMemcpyAsync(&s, part + nb, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (!(s > 0.0)) return fail("insulated solve: the lumped mass does not sum to a positive number");
+    c->ns_inv_s = 1.0 / s;
+    c->ns_N = L.N;
+    return 0;
+}
+
 EllView ell_view(const Level& L) {
     EllView e{};
     e.vals = L.vals; e.cols = L.cols; e.codes = L.codes; e.offsets = L.offsets;
@@ -3117,6 +3203,9 @@ int build_direct(mg_context* c) {
     const int64_t nb = (nz + G - 1) / G;
     if (p > 2304 || nb * p * p * 8 > ((int64_t)3 << 29)) return 0;     // too large to store densely: PCG
     d.g.n = L.nloc; d.g.p = (int)p; d.g.plane = (int)plane; d.g.nb = (int)nb; d.g.W = L.W;
+    // a singular level 0 is factorised with node 0 pinned: the rest of the operator is regular, and for a consistent
+    // right-hand side the solve is exact in every row, node 0's included (mg_nullspace.hip.h; DESIGN.md, "Insulated bodies")
+    d.pinned = level_singular(L);
     const size_t pw = (size_t)nb * p * L.W, np = (size_t)nb * p, pp = (size_t)p * p;
     DevTemp A_t, B_t, P_t, status_t;                       // A: block being inverted, B: row panel, P: pivot block
     int rc = [&]() -> int {                                // (a lambda: any failure must still reach free_direct below)
@@ -3138,6 +3227,7 @@ int build_direct(mg_context* c) {
             const size_t ko = (size_t)k * p * L.W;
             HIP_TRY(hipMemsetAsync(A, 0, pp * 8, c->stream));
             hipLaunchKernelGGL(bt_extract_dense, rows_grid, rows_blk, 0, c->stream, e, d.g, k, A, d_status);
+            if (k == 0 && d.pinned) hipLaunchKernelGGL(ns_pin_dense, rows_grid, rows_blk, 0, c->stream, A, (int)p);
             hipLaunchKernelGGL(bt_extract_coupling, rows_grid, rows_blk, 0, c->stream, e, d.g, k, d.lcol + ko, d.lval + ko,
                                d.ucol + ko, d.uval + ko);
             if (k > 0) {
@@ -3154,6 +3244,7 @@ int build_direct(mg_context* c) {
                                    A, B);
                 hipLaunchKernelGGL(gj_finish, dim3(blocks_for(p, 128)), dim3(128), 0, c->stream, (int)p, k0, nbk, A, P, B);
             }
+            if (k == 0 && d.pinned) hipLaunchKernelGGL(ns_unpin_inverse, dim3(1), dim3(64), 0, c->stream, A);
             HIP_TRY(hipGetLastError());
             HIP_TRY(hipMemcpyAsync(d.T + (size_t)k * pp, A, pp * 8, hipMemcpyDeviceToDevice, c->stream));
         }
@@ -3182,13 +3273,22 @@ int validate_direct(mg_context* c) {
     int rc = [&]() -> int {                                // (a lambda: a failed check must still drop the factorisation)
         HIP_TRY(hipMemcpyAsync(saved, L.f.base, (size_t)L.xlen * 8, hipMemcpyDeviceToDevice, c->stream));
         std::vector<double> ones((size_t)L.nloc, 1.0);
+        double fn = std::sqrt((double)L.nloc);
+        if (d.pinned) {                             // a singular level solves consistent loads only: a ramp with sum zero
+            double ff = 0.0;
+            for (int64_t i = 0; i < L.nloc; ++i) {
+                ones[(size_t)i] = (double)i - 0.5 * (double)(L.nloc - 1);
+                ff += ones[(size_t)i] * ones[(size_t)i];
+            }
+            fn = std::sqrt(ff);
+        }
         HIP_TRY(hipMemcpyAsync(L.f.rows, ones.data(), (size_t)L.nloc * 8, hipMemcpyHostToDevice, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
         MG_TRY(direct_solve(c));
         MG_TRY(residual(c, 0));
         double rn = 0.0;
         MG_TRY(norm2(c, L, L.v2.rows, &rn));
-        const double rel = rn / std::sqrt((double)L.nloc);
+        const double rel = rn / fn;
         if (!(rel <= 1e-9)) d.ok = false;           // also catches NaN
         HIP_TRY(hipMemcpyAsync(L.f.base, saved, (size_t)L.xlen * 8, hipMemcpyDeviceToDevice, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
@@ -3233,7 +3333,7 @@ int pcg_solve(mg_context* c, int* iters_out, double* rel_out);
 
 // Coarsest level: v = A^-1 f, standing in for the reference's exact spsolve (multigrid.py:239-241):
 // the block-tridiagonal LU where the level allows it, otherwise Jacobi-preconditioned CG.
-int coarse_solve(mg_context* c, int* iters_out, double* rel_out) {
+int coarse_solve_regular(mg_context* c, int* iters_out, double* rel_out) {
     if (!c->direct.tried) { MG_TRY(build_direct(c)); MG_TRY(validate_direct(c)); }
     if (c->direct.ok) {
         if (iters_out) *iters_out = 0;
@@ -3241,6 +3341,19 @@ int coarse_solve(mg_context* c, int* iters_out, double* rel_out) {
         return direct_solve(c);
     }
     return pcg_solve(c, iters_out, rel_out);
+}
+
+// A singular level 0 (level_singular): the right-hand side is made mean-free first -- restricted residuals are, up to
+// rounding, because the P1 embedding reproduces constants when every node is free -- and so is the result, which makes it
+// K0^+ f: the pinned factorisation (build_direct) or the coarse CG solve the consistent system exactly.
+int coarse_solve(mg_context* c, int* iters_out, double* rel_out) {
+    Level& L = c->L[0];
+    if (!level_singular(L)) return coarse_solve_regular(c, iters_out, rel_out);
+    if (!c->capturing) MG_TRY(ns_workspace(c, L.nloc));
+    const double inv_n = 1.0 / (double)L.nloc;
+    MG_TRY(ns_remove(c, L.f.rows, nullptr, nullptr, L.nloc, inv_n));
+    MG_TRY(coarse_solve_regular(c, iters_out, rel_out));
+    return ns_remove(c, L.v.rows, nullptr, nullptr, L.nloc, inv_n);
 }
 
 // Jacobi-preconditioned CG run to `coarse_rtol`.  Iterations are enqueued in batches; only the 4-byte
@@ -3354,6 +3467,13 @@ int face_set_refusals(mg_context* c, int level) {
 
 int prepare_cycle(mg_context* c, int level) {
     MG_TRY(face_set_refusals(c, level));
+    if (cycle_singular(c, level)) {
+        if (c->smoother != MG_SMOOTH_JACOBI)
+            return fail("the levels are those of an insulated body with neither a reaction nor a Robin term (mg_set_diffusion_insulated): "
+                        "the operator is singular, and the Chebyshev and Gauss-Seidel smoothers (CHEBYSHEV, RBGS, MCGS) were not written "
+                        "for one; use Jacobi");
+        MG_TRY(ns_workspace(c, std::max(c->L[level].nloc, c->L[0].nloc)));
+    }
     // (refused here, before the colouring check and before anything is captured; smooth() refuses a single call)
     if (c->smoother == MG_SMOOTH_RBGS || c->smoother == MG_SMOOTH_MCGS)
         for (int l = 1; l <= level; ++l)
@@ -3484,6 +3604,7 @@ struct FcgState {
     FcgArgs a{};
     FcgWork w{};
     double tol = 0.0;
+    double bnorm = 0.0;     // ||b||, the right-hand side the tolerance is relative to
     bool go = false;        // the first residual is above the tolerance: there is an iteration to do
     int it = 0;
 };
@@ -3523,6 +3644,7 @@ int fcg_arguments(mg_context* c, Level& L, FcgState& t, double rtol, int max_ite
     MG_TRY(norm2(c, L, L.fcg_b.rows, &bnorm));
     MG_TRY(norm2(c, L, L.f.rows, &rnorm));
     t.tol = rtol > 0.0 ? rtol * bnorm : -1.0;
+    t.bnorm = bnorm;
     FcgArgs& a = t.a;
     a.x = L.fcg_x.rows; a.r = L.f.rows; a.p = L.fcg_p.rows; a.q = L.fcg_q.rows; a.sc = t.w.sc; a.n = L.nloc;
     for (const double* v : {(const double*)a.x, (const double*)a.r, (const double*)a.p, a.q})
@@ -3614,12 +3736,22 @@ int fcg_precondition(mg_context* c, int level, FcgArgs& a, bool v_zeroed) {
 int fcg_solve(mg_context* c, int level, double rtol, int max_iter, double* hist, int* iters_out) {
     Level& L = c->L[level];
     FcgState t{"mg_pcg"};
+    // An insulated body's singular operator (cycle_singular; DESIGN.md, "Insulated bodies"): the solve is x = Q A^+ Q^T b.
+    // b becomes Q^T b once, every preconditioned residual is made mean-free (Euclidean weights: the preconditioner stays
+    // symmetric on the complement of the constants and the iterate cannot drift along them), the result is Q x; the
+    // stopping test is relative to Q^T b, which is what MG_VEC_F holds afterwards.
+    const bool ns = cycle_singular(c, level);
+    if (ns) MG_TRY(ns_weights(c, L));
+    const double inv_n = 1.0 / (double)L.nloc;
     MG_TRY(fcg_start(c, level, t));
+    if (ns) MG_TRY(ns_remove(c, L.fcg_b.rows, nullptr, c->ns_w, L.nloc, c->ns_inv_s));
     MG_TRY(exchange_halo(c, L, L.fcg_x));
     MG_TRY(fcg_first_residual(c, L));
     MG_TRY(fcg_arguments(c, L, t, rtol, max_iter));
+    if (ns && t.bnorm == 0.0) t.go = false;      // a projected right-hand side of zero: Q x0 after zero iterations
     if (t.go) {
         MG_TRY(fcg_precondition(c, level, t.a, false));
+        if (ns) MG_TRY(ns_remove(c, L.v.rows, nullptr, nullptr, L.nloc, inv_n));
         MG_TRY(fcg_first_direction(c, L, t));
         for (;;) {
             MG_TRY(exchange_halo(c, L, L.fcg_p));
@@ -3629,9 +3761,11 @@ int fcg_solve(mg_context* c, int level, double rtol, int max_iter, double* hist,
             HIP_TRY(hipStreamSynchronize(c->stream));
             if (!fcg_goes_on(t, c->h_scalars[0], max_iter, hist)) break;
             MG_TRY(fcg_precondition(c, level, t.a, t.a.vz != nullptr));
+            if (ns) MG_TRY(ns_remove(c, L.v.rows, nullptr, nullptr, L.nloc, inv_n));
             MG_TRY(fcg_next_direction(c, L, t));
         }
     }
+    if (ns) MG_TRY(ns_remove(c, L.fcg_x.rows, c->ns_w, nullptr, L.nloc, c->ns_inv_s));
     // ... and R = F - A x
     MG_TRY(fcg_finish(c, L));
     MG_TRY(exchange_halo(c, L, L.v));
@@ -5926,6 +6060,50 @@ int mg_set_diffusion_faces(mg_handle c, int dirichlet_faces) {
     return 0;
 }
 
+int mg_set_diffusion_insulated(mg_handle c) {
+    if (!c) return fail("null handle");
+    const std::string who = "mg_set_diffusion_insulated: ";
+    if (c->dim != 3) return fail(who + "insulated bodies are 3-D only (this handle is 2-D)");
+    if (c->comm.active()) return fail(who + "insulated bodies need a whole (not slab) handle");
+    c->diffusion_faces = 0;
+    return 0;
+}
+
+int mg_diffusion_nullspace(mg_handle c, int level, int* singular) {
+    MG_TRY(check_level(c, level));
+    if (!singular) return fail("null argument");
+    *singular = cycle_singular(c, level) ? 1 : 0;
+    return 0;
+}
+
+int mg_remove_mean(mg_handle c, double* x_dev, const double* w_dev, int64_t n, double* mean) {
+    const std::string who = "mg_remove_mean";
+    if (!c) return fail("null handle");
+    if (n < 1) return fail(who + ": n must be positive");
+    HIP_TRY(hipSetDevice(c->device));
+    MG_TRY(need_device_pointer(c, x_dev, who.c_str(), "x_dev"));
+    if (w_dev) MG_TRY(need_device_pointer(c, w_dev, who.c_str(), "w_dev"));
+    if (reinterpret_cast<uintptr_t>(x_dev) % 16 || reinterpret_cast<uintptr_t>(w_dev) % 16)
+        return fail(who + ": x_dev and w_dev must be 16-byte aligned");
+    MG_TRY(ns_workspace(c, n));
+    double denom = (double)n;
+    const int64_t nb = ns_blocks(n);
+    double* const part = c->ns_part;
+    if (w_dev) {                                // the sum of the weights, by the same kernels
+        hipLaunchKernelGGL(ns_partial, dim3((unsigned)nb), dim3(BLOCK), 0, c->stream, w_dev, (const double*)nullptr, n, part);
+        hipLaunchKernelGGL(fcg_fold, dim3(1), dim3(BLOCK), 0, c->stream, (const double*)part, nb, 1, part + nb);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(&denom, part + nb, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        if (!(denom > 0.0)) return fail(who + ": the weights do not sum to a positive number");
+    }
+    MG_TRY(ns_remove(c, x_dev, w_dev, nullptr, n, 1.0 / denom, c->scalars.get()));
+    HIP_TRY(hipMemcpyAsync(c->h_scalars, c->scalars, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (mean) *mean = c->h_scalars[0];
+    return 0;
+}
+
 int mg_diffusion_faces(mg_handle c, int* dirichlet_faces) {
     if (!c) return fail("null handle");
     if (!dirichlet_faces) return fail("null argument");
@@ -7043,6 +7221,7 @@ int mg_fmg_ex(mg_handle c, int top, int mu0, double tol, int max_cycles, int nor
     if (norm == MG_NORM_MASS && c->mass_level != top) return fail("mg_fmg_ex: no mass matrix on the top level (mg_set_mass_csr)");
     if (err_hist && (!c->uexact.raw || c->uexact_level != top)) return fail("mg_fmg_ex: no exact solution on the top level (mg_set_exact)");
     MG_TRY(face_set_refusals(c, top));
+    MG_TRY(singular_refusal(c, "mg_fmg", top));
     HIP_TRY(hipSetDevice(c->device));
     for (int l = 0; l < top; ++l) {
         Level& L = c->L[l];
@@ -7113,6 +7292,7 @@ int mg_pcg_batch(mg_handle c, int level, int nb, const double* const* f_dev, dou
                         "need stored rows; use Jacobi or Chebyshev");
     }
     MG_TRY(face_set_refusals(c, level));
+    MG_TRY(singular_refusal(c, who, level));
     // what mg_pcg refuses only where the cycle is prepared (the P1 stencil check, the colouring, the factorisation, the Chebyshev
     // interval) is refused here, with the handle's own vectors in place, before a lane is allocated or a vector overwritten
     MG_TRY(prepare_cycle(c, level));
@@ -7227,6 +7407,7 @@ int mg_eigs(mg_handle c, int level, int k, int block, const double* rho_dev, dou
                         "need stored rows; use Jacobi or Chebyshev");
     }
     MG_TRY(face_set_refusals(c, level));
+    MG_TRY(singular_refusal(c, who, level));
     const Level& L = c->L[level];
     const int64_t n1 = (int64_t)L.N + 1;
     if (L.N < 1 || L.n_global != n1 * n1 * n1 || L.g.lead != 0 || L.xlen != L.nloc)

@@ -409,6 +409,28 @@ class DeviceHierarchy:
         faces = int(dirichlet) if isinstance(dirichlet, (int, np.integer)) else face_set(dirichlet)
         check(self._lib.mg_set_diffusion_faces(self._h, faces))
 
+    def set_diffusion_insulated(self):
+        """No Dirichlet node in the diffusion levels generated from now on (`mg_set_diffusion_insulated`): every node is a
+        free node, `diffusion_faces` reports 0, Robin fields may sit on any face.  3-D, whole handles.  With a reaction or a
+        Robin field the operator is regular and everything works as on any face set; with neither it is singular and `pcg`
+        computes the projected solve u = Q A^+ Q^T f (mg_hip.h), while `pcg_batch`, `eigs`, `fmg` and the Chebyshev and
+        Gauss-Seidel smoothers are refused.  `set_diffusion_faces` with a valid set leaves the state."""
+        check(self._lib.mg_set_diffusion_insulated(self._h))
+
+    def diffusion_nullspace(self, level: Optional[int] = None) -> bool:
+        """True where solves from `level` run projected (`mg_diffusion_nullspace`): the levels up to it were generated on an
+        insulated handle and none holds a reaction or Robin diagonal."""
+        out = C.c_int(0)
+        check(self._lib.mg_diffusion_nullspace(self._h, self._idx(self.finest_level if level is None else level), C.byref(out)))
+        return bool(out.value)
+
+    def remove_mean(self, x_ptr: int, n: int, w_ptr: Optional[int] = None) -> float:
+        """x -= its mean, in place over `n` doubles of device memory at `x_ptr` (`mg_remove_mean`): (w.x) / (w.1) with the
+        weights at `w_ptr`, (1.x) / n without.  Both 16-byte aligned.  Returns the mean removed; the same bits on every run."""
+        out = C.c_double(0.0)
+        check(self._lib.mg_remove_mean(self._h, C.c_void_p(x_ptr), C.c_void_p(w_ptr) if w_ptr else None, int(n), C.byref(out)))
+        return float(out.value)
+
     def diffusion_faces(self) -> int:
         """The handle's face set as an integer (`mg_diffusion_faces`): x- = 1, x+ = 2, y- = 4, y+ = 8, z- = 16, z+ = 32."""
         faces = C.c_int(0)
@@ -942,7 +964,10 @@ class DeviceHierarchy:
         """Flexible CG preconditioned by one V(mu1, mu2) cycle per iteration (`mg_pcg`), from "v" on A x = "f" of `level`
         (default: the finest) until ||r||_2 <= rtol ||f||_2 or `max_iter` iterations (rtol <= 0: exactly that many).
         Returns ||r_k||_2 of the recursion after every iteration; the iterate is in "v", "f" is unchanged and "r" holds
-        f - A x.  After `fmg(mu0, tol=0)` it starts from the FMG iterate."""
+        f - A x.  After `fmg(mu0, tol=0)` it starts from the FMG iterate.
+        On the singular levels of an insulated handle (`set_diffusion_insulated`, `diffusion_nullspace`) it computes the
+        projected solve Q A^+ Q^T f: the tolerance is relative to Q^T f, which is what "f" holds afterwards, "v" has
+        w.v = 0, and a Q^T f of zero returns Q v after no iteration."""
         level = self.finest_level if level is None else level
         hist = np.zeros(max(1, int(max_iter)))
         done = C.c_int()

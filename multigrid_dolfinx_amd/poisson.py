@@ -576,11 +576,28 @@ FACE_BITS = {"x-": 1, "x+": 2, "y-": 4, "y+": 8, "z-": 16, "z+": 32}
 ALL_FACES = 63
 
 
+INSULATED = "insulated"
+
+
+class _NoFaces(int):
+    """What `face_set` makes of `INSULATED`: equal to 0, and the one zero `face_set` takes back, so the functions that hand a
+    face set on as its integer keep working.  The plain integer 0 stays refused."""
+
+    def __repr__(self):
+        return "face_set('insulated')"
+
+
+_NO_FACES = _NoFaces(0)
+
+
 def face_set(dirichlet_faces) -> int:
     """The face set of `mg_set_diffusion_faces` as its integer: x- = 1, x+ = 2, y- = 4, y+ = 8, z- = 16, z+ = 32.  Takes the
-    integer, None (all six) or names ("x-", "z+", ...)."""
+    integer, None (all six) or names ("x-", "z+", ...).  `INSULATED` ("insulated") is the one spelling of the empty set, the
+    body with no Dirichlet node of `mg_set_diffusion_insulated`: it gives 0.  The integer 0 is refused."""
     if dirichlet_faces is None:
         return ALL_FACES
+    if isinstance(dirichlet_faces, _NoFaces) or (isinstance(dirichlet_faces, str) and dirichlet_faces == INSULATED):
+        return _NO_FACES
     if isinstance(dirichlet_faces, (int, np.integer)):
         faces = int(dirichlet_faces)
     else:
@@ -1375,3 +1392,34 @@ def diffusion_eigs_reference(N: int, kappa, k: int, rho=None, dirichlet_faces=AL
     U = np.zeros((k, n1 ** 3))
     U[:, free] = V.T
     return lam, U
+
+
+def insulated_solve_reference(N: int, kappa, f, sigma=None, robin=None, averaging: str = "arithmetic") -> np.ndarray:
+    """The host statement of the insulated solve (`mg_set_diffusion_insulated`; DESIGN.md, "Insulated bodies"): u on the
+    (N + 1)^3 nodes for the load `f`, with A = `diffusion_level(N, 3, kappa, dirichlet_faces=INSULATED, sigma=.., robin=..).A`.
+
+    Regular case -- `sigma` given, or `robin` with at least one field: A is regular and u = A^-1 f, a plain sparse solve.
+    Singular case -- neither: A has zero row sums.  With w = `reaction_diag(N, ones, INSULATED)` (w_i = the integral of the
+    hat function) and s = w.1, u = Q A^+ Q^T f, Q = I - 1 w^T / s, the solution of the bordered system
+
+        [[A, w], [w^T, 0]] [u; mu] = [f; 0]:       A u = f - w (1.f) / s,   w.u = 0   (mu = (1.f) / s),
+
+    followed by u - 1 (w.u) / s, which takes the rounding of the factorisation out of w.u.
+
+    `averaging` is the coarsening of the device hierarchy and does not enter a one-level solve; it is taken so that a call
+    reads like the device's."""
+    from scipy.sparse.linalg import spsolve
+    if averaging not in ("arithmetic", "harmonic"):
+        raise ValueError("unknown kappa averaging")
+    n = (N + 1) ** 3
+    fv = np.array(f, dtype=np.float64).reshape(-1)
+    if fv.size != n:
+        raise ValueError(f"vector has {fv.size} entries, the level has {n} nodes")
+    has_robin = robin is not None and bool(_robin_fields(N, robin, _NO_FACES))
+    A = diffusion_level(N, 3, kappa, dirichlet_faces=INSULATED, sigma=sigma, robin=robin if has_robin else None).A.tocsc()
+    if sigma is not None or has_robin:
+        return np.asarray(spsolve(A, fv)).reshape(-1)
+    w = reaction_diag(N, np.ones(N ** 3), INSULATED)
+    K = sp.bmat([[A, sp.csc_matrix(w.reshape(-1, 1))], [sp.csc_matrix(w.reshape(1, -1)), None]], format="csc")
+    u = np.asarray(spsolve(K, np.concatenate([fv, [0.0]]))).reshape(-1)[:n]
+    return u - (w @ u) / w.sum()                # (Q once more: the sparse LU leaves w.u at its own rounding, not at that of u)

@@ -99,6 +99,17 @@ class DiffusionSolver:
     does: the caller asserts that kappa, sigma and the Robin fields hold the values of that solve (the steps of a time march
     with a constant dt).  Gradients with respect to them still flow.  `n_generations` counts the generations and refreshes.
 
+    `dirichlet_faces="insulated"` (`poisson.INSULATED`): no Dirichlet node at all (`DeviceHierarchy.set_diffusion_insulated`;
+    DESIGN.md, "Insulated bodies").  `g` must be None -- anything else raises ValueError -- and `robin` may name any of the six
+    faces.  With `sigma` or at least one Robin field the operator is regular and everything is as on any face set (an
+    implicit heat step of an insulated body, convective cooling all round); a field that is zero everywhere is the caller's
+    mistake and ends in `NotConverged`.  With neither the operator is singular (its null space is the constants) and
+    `solve` returns u = S f, S = Q A^+ Q^T with Q = I - 1 w^T / s, w the lumped mass of rho = 1 and s = w.1: A u = f - w (1.f) / s
+    and w.u = 0 -- a uniform source density is taken off the load, and u_h has integral zero.  S is symmetric and dS = -S dA S,
+    so the adjoint solve is the same projected solve, grad_f = lambda, grad_kappa = -D(lambda, u): first and second
+    derivatives and `tangent` are as everywhere.  `solve_many` and `eigenpairs` raise in the singular case and work in the
+    regular one; going between solves with and without sigma or alpha regenerates the hierarchy, as on any face set.
+
     `robin` (`solve`, `tangent`): a mapping of faces outside `dirichlet_faces` (names "x-" .. "z+" or bits) to N^2 float64
     alpha >= 0, one per boundary face-cell (face-cell (ca, cb) at cb * N + ca, (a, b) the in-plane axes in ascending order),
     on the solver's device or the CPU, each a differentiable input.  Those faces carry kappa du/dn + alpha (u - u_ext) = 0
@@ -152,7 +163,10 @@ class DiffusionSolver:
         self.hierarchy.set_params(**params)
         self.hierarchy.set_prolongation("p1")
         self.dirichlet_faces = face_set(dirichlet_faces)
-        if self.dirichlet_faces != ALL_FACES:
+        self.insulated = self.dirichlet_faces == 0      # (`face_set`: only "insulated" gives 0)
+        if self.insulated:
+            self.hierarchy.set_diffusion_insulated()
+        elif self.dirichlet_faces != ALL_FACES:
             self.hierarchy.set_diffusion_faces(self.dirichlet_faces)
         self._generation = 0
         self._generated = False         # a hierarchy call has generated the levels: a device kappa can refresh them
@@ -204,6 +218,14 @@ class DiffusionSolver:
         bits = tuple(sorted(fields))
         return bits, tuple(fields[b] for b in bits)
 
+    def _no_dirichlet_data(self, g, what: str = "g"):
+        if self.insulated and g is not None:
+            raise ValueError(f"the insulated solver (dirichlet_faces=\"insulated\") has no Dirichlet node: {what} must be None")
+
+    def _singular(self, sigma, bits) -> bool:
+        """The insulated solver with neither a reaction nor a Robin field: the operator is singular and `solve` projects."""
+        return self.insulated and sigma is None and not bits
+
     def _operator_to_reuse(self, same_operator: bool, sigma, bits) -> Optional["_Operator"]:
         """None, or with `same_operator` the operator of the last solve, which must have had what this one has."""
         if not same_operator:
@@ -225,6 +247,7 @@ class DiffusionSolver:
 
     def solve(self, kappa: torch.Tensor, f: torch.Tensor, g: Optional[torch.Tensor] = None,
               sigma: Optional[torch.Tensor] = None, same_operator: bool = False, robin=None) -> torch.Tensor:
+        self._no_dirichlet_data(g)
         bits, alphas = self._robin_inputs(robin)
         op = self._operator_to_reuse(same_operator, sigma, bits)
         if g is None:
@@ -243,7 +266,11 @@ class DiffusionSolver:
         if F.dtype != torch.float64 or F.device != self.device or F.dim() < 2 or F.shape[0] < 1 or F[0].numel() != n:
             raise ValueError(f"F must hold B >= 1 leading rows of {n} float64 on {self.device} (got {tuple(F.shape)} {F.dtype} on {F.device})")
         B = F.shape[0]
+        self._no_dirichlet_data(g)
         bits, alphas = self._robin_inputs(robin)
+        if self._singular(sigma, bits):
+            raise ValueError("solve_many: the insulated solver with neither sigma nor robin has a singular operator, and batched "
+                             "solves have no projected form: call solve per right-hand side")
         op = self._operator_to_reuse(same_operator, sigma, bits)
         if g is None:
             return _Solve.apply(kappa, F, self, op, "forward", True, True, sigma, bits, *alphas)
@@ -281,6 +308,9 @@ class DiffusionSolver:
         of the eigenspace (the closed-form cube's (1,1,2) triple, say): differentiate the cluster's sum, or break the
         symmetry.  Second derivatives need eigenvector derivatives and are not provided: differentiating twice raises."""
         bits, alphas = self._robin_inputs(robin)
+        if self._singular(sigma, bits):
+            raise ValueError("eigenpairs: the insulated solver with neither sigma nor robin has a singular operator (its smallest "
+                             "eigenvalue is 0, the constants): eigenpairs are not provided for it")
         op = self._operator_to_reuse(same_operator, sigma, bits)
         return _Eigs.apply(kappa, self, op, int(k), block, x0, float(rtol), int(max_iter), rho, sigma, bits, *alphas)
 
@@ -410,6 +440,7 @@ class DiffusionSolver:
         operator is A(kappa) + R(sigma) and the second right-hand side loses T_sigma(dsigma, u) on the free rows.
         With `robin` as in `solve` and its directions `drobin` (a mapping of some of those faces to N^2 float64 of any sign on
         the solver's device) it loses T_alpha,F(drobin[F], u) too."""
+        self._no_dirichlet_data(g)
         if g is None and dg is not None:
             raise ValueError("dg is the direction of g: it needs g")
         if sigma is None and dsigma is not None:

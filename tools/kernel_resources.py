@@ -5,7 +5,7 @@ code object's notes.
 
 Names behind tables of DESIGN.md: jacobikc (every tile shape of the K-sweep march, `sdia_jacobikc_rim` of shape 9 included),
 jk3_plan (`jk3_plan` and `jk3_plan_rim`), diffusion_mf, diffusion_mf_batch, diffusion_dkappa, kappa_ingest, cell_grad,
-block_gram, block_combine.
+block_gram, block_combine, ns_ (the mean removal and the coarsest pin of the insulated solves).
 """
 import os
 import re
